@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X hot path: reenactment frames/sec, 1 source -> N driver frames (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--image-size 512] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--image-size 512] [--batch B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times K steps and prints one JSON line with the headline (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds per timed step) and the configuration.  --dump-outputs DIR writes the
+uint8 frames of the last timed step (rank 0's) as float32 to DIR/frames.npy, so that two builds can be compared output for
+output: weights and inputs are seeded, identical from run to run.
 
 One "step" = one pass of the per-frame hot path (a3, a4, a5-uv, a1 x2 with a2 fused, a9, a11) over one batch of
 B synthetic driver frames that share one source identity, inputs resident in HBM.  Workload at N=1: released
@@ -13,7 +18,9 @@ the repo), synthetic embeddings/poses.  Multi-GPU: frames shard across ranks, pe
 pass runs on rank 0 and its canonical volume is broadcast over RCCL once per identity, outside the timed region
 (reported as source_pass_ms / broadcast_ms).
 
-The JSON line also carries
+With --full the JSON line also carries (each measured in runs of its own behind the timed region; --no-extras,
+--no-cpu-baseline, --no-sustained and --strong-frames 0 leave parts out)
+  source_pass_ms, broadcast_ms, weak_scaling, strong_scaling beside a weak headline, host_affinity, sustained_mfma, extras
   roofline      the dominant kernel -- conv_igemm_bf16x3_kernel (fp32 3x3 convolution on the 16-bit matrix pipes: the two-term
                 fp16 split with its device-checked range by default, the three-term bf16 split with EMO_CONV_PRECISION=bf16x3)
                 or, with EMO_CONV_PRECISION=f32, conv_igemm_kernel (fp32 MFMA): algorithmic FLOPs of its launches in the timed
@@ -592,6 +599,21 @@ def sustained_mfma(dev, seconds=1.2):
     return out
 
 
+DUMP_MAX_ELEMENTS = 16_000_000           # float32: at most 64 MB of outputs per run
+
+
+def dump_outputs(dirname, frames):
+    """DIR/frames.npy: the step's uint8 frames [B, S, S, 3] as float32 -- or, past DUMP_MAX_ELEMENTS, a fixed seeded sample of
+    their elements (flattened, in ascending index order)"""
+    import numpy as np
+    x = frames.cpu()
+    if x.numel() > DUMP_MAX_ELEMENTS:
+        idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMENTS].sort().values
+        x = x.reshape(-1)[idx]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "frames.npy"), x.numpy().astype(np.float32))
+
+
 def relaunch_under_torchrun(n):
     """`python bench.py --gpus N` with N > 1 and no rendezvous environment: start N ranks ourselves (one process per GPU,
     RCCL backend) exactly as the driver would -- python -m torch.distributed.run on 127.0.0.1 -- and relay its output."""
@@ -629,10 +651,20 @@ def main():
                          "sharded contiguously over the ranks -- rank 0's source pass, the broadcast of its cache, every rank's shard "
                          "in batches of --batch and the uint8 D2H ring all inside the timed region; the line says scaling: strong")
     ap.add_argument("--strong-frames", type=int, default=512,
-                    help="weak-scaling runs also report one strong-scaling figure (strong_scaling in the line) on a clip of this "
+                    help="with --full, weak-scaling runs also report one strong-scaling figure (strong_scaling in the line) on a clip of this "
                          "many frames; 0 skips it")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary figures behind the timed region (source pass and broadcast times, roofline "
+                         "meters, sustained MFMA rate, strong-scaling figure of a weak run, extras, CPU baseline); the --no-* "
+                         "flags and --strong-frames select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the uint8 frames of the last one (rank 0's) as float32 to DIR/frames.npy")
     a = ap.parse_args()
 
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if a.dump_outputs and a.total_frames:
+        raise SystemExit("--dump-outputs writes the frames of the weak-scaling step; a --total-frames clip does not keep its frames")
     if a.total_frames and a.no_source_pass:          # (every rank sees the same flags: no rank is left waiting in a collective)
         raise SystemExit("--total-frames times the source pass of every clip: it cannot be combined with --no-source-pass")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -671,13 +703,15 @@ def main():
         srt_s = [t.to(dev) for t in (1 + 0.05 * torch.randn(1, 3, generator=g), 0.3 * torch.randn(1, 3, generator=g),
                                     0.05 * torch.randn(1, 3, generator=g))]
         th_s = ops.pose_theta(*srt_s)
-        for _ in range(2):                                          # warm-up: lazy weight packing and allocator (first call), and a
-            hp.source_pass(img, idt_cpu.to(dev), pose_s, th_s)      # GPU that is awake (the first call is mostly host work)
-        torch.cuda.synchronize()
-        t0 = time.time()
+        if a.full:                                                      # source_pass_ms
+            for _ in range(2):                                          # warm-up: lazy weight packing and allocator (first call), and a
+                hp.source_pass(img, idt_cpu.to(dev), pose_s, th_s)      # GPU that is awake (the first call is mostly host work)
+            torch.cuda.synchronize()
+            t0 = time.time()
         canonical = hp.source_pass(img, idt_cpu.to(dev), pose_s, th_s)
-        torch.cuda.synchronize()
-        source_ms = (time.time() - t0) * 1e3
+        if a.full:
+            torch.cuda.synchronize()
+            source_ms = (time.time() - t0) * 1e3
         cache = {"canonical": canonical, "idt_embed": idt_cpu.to(dev), "theta_src": th_s}
     shapes = dict(canonical=(1, c, d, s, s), idt_embed=(1, cfg["gen_max_channels"], 4, 4), theta_src=(1, 4, 4))
     names = list(shapes)
@@ -685,7 +719,7 @@ def main():
     bc = lambda: parallel.broadcast_source_cache(cache, shapes, src=0, device=dev, world=world, rank=rank, names=names,
                                                  exchange_shapes=False)
     broadcast_ms = None
-    if world > 1:
+    if world > 1 and a.full:
         bc()                               # first collective: communicator set-up, not the steady-state cost
         parallel.barrier()
         torch.cuda.synchronize()
@@ -729,21 +763,64 @@ def main():
     strong = None
     if a.total_frames:
         # STRONG scaling is the headline of this invocation: a step = one clip (class StrongClip), K = --steps clips behind W =
-        # --warmup untimed ones; the weak-scaling step below is still run (briefly) for the per-kernel figures of the line
+        # --warmup untimed ones; with --full the weak-scaling step below is still run (briefly) for the per-kernel figures of the line
         strong = strong_scaling(hp, cfg, dev, rank, world, a.total_frames, B, S, a.seed, a.steps, a.warmup, not a.no_graph)
-    for _ in range(a.warmup):
-        step()
-    parallel.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        out = step()
-    torch.cuda.synchronize()
-    parallel.barrier()
-    elapsed = parallel.max_over_ranks(time.perf_counter() - t0, device=dev)
+    if not a.total_frames or a.full:
+        for _ in range(a.warmup):
+            step()
+        parallel.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            out = step()
+        torch.cuda.synchronize()
+        parallel.barrier()
+        elapsed = parallel.max_over_ranks(time.perf_counter() - t0, device=dev)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, out)
+
+    if rank == 0:
+        if strong is not None:
+            fps, ms_per_step = strong["frames_per_s"], strong["ms_per_clip"]
+        else:
+            fps, ms_per_step = world * B * a.steps / elapsed, elapsed / a.steps * 1e3
+        rec = {
+            "metric": "reenactment frames/sec @512x512, 1-src->N-driver" if S == 512 else f"reenactment frames/sec @{S}x{S}, 1-src->N-driver",
+            "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if strong is not None else "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "dtype_note": f"tensors, norms, epilogue and accumulation fp32; conv operand form: {hp.precision} (config.conv_arithmetic)",
+            "config": {"workload": (f"released stage-1 architecture R{S}, full HIP driver pass (pose theta, warp embed, uv WarpGenerator, "
+                                    f"2x 3-D grid_sample, decoder, uint8 pack), 1 source identity, {B} driver frames per GPU per step"
+                                    if strong is None else
+                                    f"released stage-1 architecture R{S}: one clip of {a.total_frames} driver frames of one source identity per "
+                                    f"step, sharded contiguously over {world} rank(s) -- source pass on rank 0, one broadcast of its cache, "
+                                    f"full HIP driver pass in batches of {B}, uint8 frames D2H into a pinned ring, all inside the timed region"),
+                       "image_size": S, "frames_per_gpu_per_step": B,
+                       "weights": ("seeded random, reference key layout" if a.raw_weights else
+                                   "seeded trained-like (spectral norms ~1, |uv delta| < ~1 voxel, unsaturated image), reference key layout"),
+                       "conv_arithmetic": {"bf16x3": "fp32 tensors and accumulation; 3x3 / 3x3x3 convs of the decoder and the WarpGenerator that a 256-position tile of the split kernel fits: every fp32 operand split exactly "
+                                                     "into 3 bf16 terms, 6 partial products on the bf16 matrix pipes (error vs fp64 <= "
+                                                     "the fp32 MFMA kernel's, tests/test_conv_bf16x3_gpu.py); other convs: fp32 MFMA",
+                                           "f16x2": "fp32 tensors and accumulation; 3x3 / 3x3x3 convs of the decoder and the WarpGenerator that a 256-position tile of the split kernel fits: every scaled fp32 operand as two "
+                                                    "fp16 terms (2^-24 relative), 3 partial products on the fp16 matrix pipes (mean error vs fp64 "
+                                                    + F16X2_FP64_RATIO + "); the operand range is checked on the device by every "
+                                                    "launch and a guarded bf16x3 launch recomputes a layer that left it "
+                                                    "(tests/test_conv_bf16x3_gpu.py); the decoder's four 1x1 layers: the same split on "
+                                                    "the pointwise kernel (guarded fp32 MFMA recomputation); other convs: fp32 MFMA",
+                                           "f32": "exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) in every convolution"}[hp.precision],
+                       "step_launch": step_launch,
+                       "parallelism": f"frame-parallel x{world}" if world > 1 else "single GPU"},
+            "strong_scaling": strong,
+        }
+        if not a.full:
+            print(json.dumps(rec), flush=True)
+    if not a.full:
+        return
+
     strong_extra = None
     if not a.total_frames and a.strong_frames and not a.no_source_pass:
-        # one strong-scaling figure beside the weak headline (2 clips behind 1 untimed), so that a plain `--gpus N` sweep also
+        # one strong-scaling figure beside the weak headline (2 clips behind 1 untimed), so that a `--gpus N --full` sweep also
         # yields the fixed-total-work curve of BASELINE configs[3]
         strong_extra = strong_scaling(hp, cfg, dev, rank, world, a.strong_frames, B, S, a.seed, 2, 1, not a.no_graph)
 
@@ -808,13 +885,9 @@ def main():
             sustained = sustained_mfma(dev)
         except Exception as e:                                    # a diagnostic must never cost the headline line
             sustained = {"error": repr(e)}
-    frames = world * B * a.steps
-    fps = frames / elapsed
-    weak = {"scaling": "weak", "frames_per_s": round(fps, 3), "ms_per_step": round(elapsed / a.steps * 1e3, 3),
+    weak = {"scaling": "weak", "frames_per_s": round(world * B * a.steps / elapsed, 3), "ms_per_step": round(elapsed / a.steps * 1e3, 3),
             "frames_per_gpu_per_step": B, "what": "the same step with the per-GPU batch fixed and the inputs replayed (source pass and "
                                                   "broadcast outside the timed region)"}
-    if strong is not None:
-        fps, elapsed = strong["frames_per_s"], strong["ms_per_clip"] * 1e-3 * a.steps
     conv_ms = conv_meter.total_ms()
     samp_ms = samp_meter.total_ms()
     conv_tflops = conv_meter.flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
@@ -906,38 +979,12 @@ def main():
                                         f"(implied clock {sustained['bare']['implied_clock_ghz']} GHz) / {products} products")
         return r
 
-    rec = {
-        "metric": "reenactment frames/sec @512x512, 1-src->N-driver" if S == 512 else f"reenactment frames/sec @{S}x{S}, 1-src->N-driver",
-        "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong" if strong is not None else "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "dtype_note": f"tensors, norms, epilogue and accumulation fp32; conv operand form: {hp.precision} (config.conv_arithmetic)",
-        "config": {"workload": (f"released stage-1 architecture R{S}, full HIP driver pass (pose theta, warp embed, uv WarpGenerator, "
-                                f"2x 3-D grid_sample, decoder, uint8 pack), 1 source identity, {B} driver frames per GPU per step"
-                                if strong is None else
-                                f"released stage-1 architecture R{S}: one clip of {a.total_frames} driver frames of one source identity per "
-                                f"step, sharded contiguously over {world} rank(s) -- source pass on rank 0, one broadcast of its cache, "
-                                f"full HIP driver pass in batches of {B}, uint8 frames D2H into a pinned ring, all inside the timed region"),
-                   "image_size": S, "frames_per_gpu_per_step": B,
-                   "weights": ("seeded random, reference key layout" if a.raw_weights else
-                               "seeded trained-like (spectral norms ~1, |uv delta| < ~1 voxel, unsaturated image), reference key layout"),
-                   "conv_arithmetic": {"bf16x3": "fp32 tensors and accumulation; 3x3 / 3x3x3 convs of the decoder and the WarpGenerator that a 256-position tile of the split kernel fits: every fp32 operand split exactly "
-                                                 "into 3 bf16 terms, 6 partial products on the bf16 matrix pipes (error vs fp64 <= "
-                                                 "the fp32 MFMA kernel's, tests/test_conv_bf16x3_gpu.py); other convs: fp32 MFMA",
-                                       "f16x2": "fp32 tensors and accumulation; 3x3 / 3x3x3 convs of the decoder and the WarpGenerator that a 256-position tile of the split kernel fits: every scaled fp32 operand as two "
-                                                "fp16 terms (2^-24 relative), 3 partial products on the fp16 matrix pipes (mean error vs fp64 "
-                                                + F16X2_FP64_RATIO + "); the operand range is checked on the device by every "
-                                                "launch and a guarded bf16x3 launch recomputes a layer that left it "
-                                                "(tests/test_conv_bf16x3_gpu.py); the decoder's four 1x1 layers: the same split on "
-                                                "the pointwise kernel (guarded fp32 MFMA recomputation); other convs: fp32 MFMA",
-                                       "f32": "exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) in every convolution"}[hp.precision],
-                   "step_launch": step_launch,
-                   "f16x2_layers_recomputed_after_range_check": recomputed,
-                   "metered_pass": (f"roofline figures: the same {a.steps} steps launched eagerly with HIP events around every conv / "
-                                    f"sampler launch, each behind {blockers} graph replays so that the host is ahead of the GPU (host "
-                                    f"enqueue time of a metered step: {host_enqueue_ms:.1f} ms); "
-                                    f"{elapsed_metered / a.steps * 1e3:.2f} ms of GPU time per metered step"),
-                   "parallelism": f"frame-parallel x{world}" if world > 1 else "single GPU"},
+    rec["config"].update({"f16x2_layers_recomputed_after_range_check": recomputed,
+                          "metered_pass": (f"roofline figures: the same {a.steps} steps launched eagerly with HIP events around every conv / "
+                                           f"sampler launch, each behind {blockers} graph replays so that the host is ahead of the GPU (host "
+                                           f"enqueue time of a metered step: {host_enqueue_ms:.1f} ms); "
+                                           f"{elapsed_metered / a.steps * 1e3:.2f} ms of GPU time per metered step")})
+    rec.update({
         "roofline": conv_roofline(dom),
         "roofline_sampler": {"bound": "hbm", "kernel": "gs3d_cl_v2 / gs3d_cl2ncdhw_v2 (3-D grid_sample, channels-last)",
                              "achieved": round(samp_gbps, 1), "peak": PEAK_HBM_GBPS, "unit": "GB/s",
@@ -950,7 +997,7 @@ def main():
         "weak_scaling": weak if strong is not None else None,
         "source_pass_ms": None if source_ms is None else round(source_ms, 2),
         "broadcast_ms": None if broadcast_ms is None else round(broadcast_ms, 3),   # one flat RCCL broadcast of the source cache, max over ranks
-    }
+    })
     if world == 1 and not a.no_extras:
         try:
             rec["extras"] = extras(cfg, sd, hp, ccl, idt, pose, srt, dev, S)

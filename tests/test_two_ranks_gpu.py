@@ -201,7 +201,7 @@ def _bench_line(args, world, share_gpu=True):
         env.pop(k, None)
     if share_gpu and world > 1:
         env.update(EMO_FORCE_DEVICE="0", EMO_DIST_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--no-cpu-baseline", "--no-extras"] + args,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full", "--no-cpu-baseline", "--no-extras"] + args,
                        env=env, capture_output=True, text=True, timeout=1500)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])

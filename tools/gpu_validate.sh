@@ -19,9 +19,12 @@ tail -3 gpurun_out/${TAG}_pytest.log; tail -1 gpurun_out/${TAG}_smoke.log
 fi
 [ $PART = tests ] && exit 0
 SHORT=0; [ $PART = bench-short ] && SHORT=1
-timeout 900 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-EMO_CONV_PRECISION=bf16x3 timeout 600 python bench.py --no-extras --no-cpu-baseline > gpurun_out/${TAG}_bench_bf16x3.json 2>> gpurun_out/${TAG}_bench.err
-EMO_DIST_BACKEND=gloo EMO_FORCE_DEVICE=0 timeout 600 python bench.py --gpus 2 --steps 2 --warmup 1 --batch 4 --no-cpu-baseline > gpurun_out/${TAG}_bench_2ranks_1gpu.json 2>> gpurun_out/${TAG}_bench.err
+# the bench records (--full: with roofline, extras, CPU baseline) go to $OUT, which tools/collect_profiles.py reads as well:
+# the directory the other logs of the run are in
+OUT=${OUT:?set OUT to the directory of the run logs}; mkdir -p $OUT
+timeout 900 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+EMO_CONV_PRECISION=bf16x3 timeout 600 python bench.py --full --no-extras --no-cpu-baseline > $OUT/${TAG}_bench_bf16x3.json 2>> $OUT/${TAG}_bench.err
+EMO_DIST_BACKEND=gloo EMO_FORCE_DEVICE=0 timeout 600 python bench.py --gpus 2 --steps 2 --warmup 1 --batch 4 --full --no-cpu-baseline > $OUT/${TAG}_bench_2ranks_1gpu.json 2>> $OUT/${TAG}_bench.err
 timeout 400 python tools/bench_conv.py 16 --bf16x3 --f16x2 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_conv.jsonl
 timeout 300 python tools/bench_driver.py 512 1 4 16 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_driver512.jsonl
 timeout 300 python tools/bench_driver.py 512 1 16 --f32 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_driver512_f32.jsonl
@@ -30,7 +33,7 @@ timeout 300 python tools/bench_driver.py 512 1 16 --bf16x3 2>&1 | grep -v amdgpu
 timeout 60 tools/microbench/mfma_stream > gpurun_out/${TAG}_mfma_stream.jsonl 2>&1
 bash tools/profile_bench.sh ${TAG}
 if [ $SHORT = 0 ]; then
-timeout 300 python bench.py --image-size 256 --batch 32 --no-cpu-baseline > gpurun_out/${TAG}_bench256.json 2>> gpurun_out/${TAG}_bench.err
+timeout 300 python bench.py --image-size 256 --batch 32 --full --no-cpu-baseline > $OUT/${TAG}_bench256.json 2>> $OUT/${TAG}_bench.err
 timeout 300 python tools/bench_stage2.py 8 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_stage2.jsonl
 timeout 300 python tools/bench_sampler.py 16 64 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_sampler.jsonl
 timeout 300 python tools/bench_pipeline.py 512 1 16 2>&1 | grep -v amdgpu.ids > gpurun_out/${TAG}_pipeline.jsonl
@@ -41,4 +44,4 @@ bash tools/pmc_sampler.sh ${TAG}_p4tile 16 0.03 p4 > gpurun_out/${TAG}_pmc_sampl
 bash tools/profile_f16.sh ${TAG}
 fi
 [ -f gpurun_out/${TAG}_pytest.log ] && tail -3 gpurun_out/${TAG}_pytest.log
-cut -c1-400 gpurun_out/${TAG}_bench.json
+cut -c1-400 $OUT/${TAG}_bench.json
