@@ -20,13 +20,16 @@ conv_launch_fn conv_lookup_f16x2_3x3(int, int);
 conv_launch_fn conv_lookup_f16x2_1x1(int, int);
 conv_launch_fn conv_lookup_f16x2_3x3_bm32(int, int);
 conv_launch_fn conv_lookup_f16w8_3x3(int, int);
+int conv_f16x2_up2_launch(ConvArgs, hipStream_t);   // conv_inst_f16x2_up2.hip
 
 // MFMA operand format (accumulation and all tensors in HBM are fp32 either way).  PREC_S: every fp32 operand as the exact sum
 // of three bf16 terms, six partial products (conv_igemm_bf16x3.h) -- fp32 results on the bf16 pipes
 // PREC_S2: the scaled operand as two fp16 terms, three partial products (same kernel, SPLIT = 2; opt-in)
 // PREC_H1: plain fp16 operands on the eight-wave two-tile kernel (conv_igemm_f16x2_w8.h, NPROD = 1): weights = the first plane
 // of the split layout
-enum { PREC_F32 = 0, PREC_F16 = 1, PREC_S = 2, PREC_S2 = 3, PREC_H1 = 4 };
+// PREC_S2U: the fp16 split of a 3x3 layer with the fused nearest x2 upsample as four 2x2 phase convolutions on the low-res input
+// (conv_inst_f16x2_up2.hip; weights: emoportraits_amd.pack.pack_weight_f16x2_up2)
+enum { PREC_F32 = 0, PREC_F16 = 1, PREC_S = 2, PREC_S2 = 3, PREC_H1 = 4, PREC_S2U = 5 };
 
 static int shape_of_width(int Wl) {
   if (Wl >= 128 && Wl % 128 == 0) return SHAPE_W128;
@@ -39,6 +42,7 @@ static int shape_of_width(int Wl) {
 
 static int kc_of(int KH, int KW, int cfg, int prec = PREC_F32) {
   if (prec == PREC_H1) return (cfg == CFG_D && KH == 3 && KW == 3) ? 32 : 0;   // two 16-channel k-blocks per stage
+  if (prec == PREC_S2U) return (cfg == CFG_D && KH == 3 && KW == 3) ? 16 : 0;
   if (prec == PREC_S2 && cfg == CFG_D && KH == 1 && KW == 1) return 32;   // conv_igemm_f16x2_p1.h: pointwise, 32 channels per stage
   if (prec == PREC_S2 && cfg == CFG_F && KH == 3 && KW == 3) return 16;   // fp16 split on 32-row channel tiles (conv_igemm_bf16x3.h, BMT = 32)
   if (prec == PREC_S || prec == PREC_S2) return (cfg == CFG_D && KH == 3 && KW == 3) ? 16 : 0;
@@ -166,6 +170,10 @@ static int conv_igemm_dispatch(int prec, const float* x, const void* wpk, const 
     if (!(KH == 3 && KW == 3 && (KD == 1 || KD == 3)) || cfg != CFG_D || Cin % 8 || ksplit != 1 || run_if != nullptr) return EMO_ERR_UNSUPPORTED;
     if (!(in_scale > 0.0f && w_scale > 0.0f)) return EMO_ERR_BAD_ARG;
     fn = conv_lookup_f16w8_3x3(a.Wl, ups);
+  } else if (prec == PREC_S2U) {
+    if (!(KH == 3 && KW == 3 && KD == 1) || !ups || cfg != CFG_D || ksplit != 1 || run_if != nullptr) return EMO_ERR_UNSUPPORTED;
+    if (!(in_scale > 0.0f && w_scale > 0.0f)) return EMO_ERR_BAD_ARG;
+    fn = &conv_f16x2_up2_launch;
   } else if (prec == PREC_S2 && KH == 1 && KW == 1) {
     // pointwise layers on the fp16 split (conv_igemm_f16x2_p1.h): one launch form, no K split
     if (KD != 1 || cfg != CFG_D || Cin % 8 || ksplit != 1 || run_if != nullptr) return EMO_ERR_UNSUPPORTED;
@@ -251,6 +259,11 @@ extern "C" int emo_conv_igemm_f16x2(const float* x, const void* wpk2, const floa
                                     int H, int W, int KD, int KH, int KW, int ups, int relu_in, int act, int res_ups,
                                     int cfg, int ksplit, float* workspace, float* gn_stats, void* stream, float in_scale,
                                     float w_scale, int* overflow_flag) {
+  // ABI 11: cfg EMO_CONV_CFG_F16X2_UP2 -- wpk2 holds the phase kernels of a 3x3 layer with the fused upsample (include/emo_hip.h)
+  if (cfg == EMO_CONV_CFG_F16X2_UP2)
+    return conv_igemm_dispatch(PREC_S2U, x, wpk2, bias, scale, shift, res, out, N, Cin, Cout, D, H, W, KD, KH, KW, ups,
+                               relu_in, act, res_ups, CFG_D, ksplit, workspace, gn_stats, stream, in_scale, w_scale,
+                               overflow_flag, nullptr);
   return conv_igemm_dispatch(PREC_S2, x, wpk2, bias, scale, shift, res, out, N, Cin, Cout, D, H, W, KD, KH, KW, ups,
                              relu_in, act, res_ups, cfg, ksplit, workspace, gn_stats, stream, in_scale, w_scale,
                              overflow_flag, nullptr);
@@ -294,3 +307,4 @@ extern "C" int emo_conv_igemm_f16w8(const float* x, const void* wpk1, const floa
   return conv_igemm_dispatch(PREC_H1, x, wpk1, bias, scale, shift, res, out, N, Cin, Cout, D, H, W, KD, KH, KW, ups,
                              relu_in, act, res_ups, cfg, ksplit, workspace, gn_stats, stream, 1.0f, w_scale, nullptr, nullptr);
 }
+

@@ -1,0 +1,417 @@
+// The decoder's up-convolutions conv3x3(up2_nearest(relu(gn_affine(x)))) in the fp16 split (SPLIT = 2, as conv_igemm_bf16x3.h:
+// two fp16 terms of the scaled operands, three products, fp32 accumulation, device-checked operand range) as FOUR 2x2 PHASE
+// convolutions on the low-resolution input -- "UP2".
+//
+// Why.  Under nearest x2 upsampling the output pixel (2i + p, 2j + q) reads low-res rows i - 1 + p .. i + p and columns
+// j - 1 + q .. j + q only: kernel row a of phase p is the sum of the 3x3 kernel rows R_p[a] (R_0 = {0}, {1, 2}; R_1 = {0, 1}, {2}),
+// columns likewise.  So the layer is four 2x2 convolutions of x with pre-summed weights (emoportraits_amd.pack.pack_weight_f16x2_up2):
+// 4 Cin MACs per output instead of 9 Cin -- 2.25x fewer MFMAs, and a shorter accumulation.  Zero padding stays exact (high-res
+// row -1 reads low-res row -1, row 2H reads low-res row H).
+//
+// Item: one 64-channel output tile x a low-res region of 2 rows x 64 columns (a high-res 4 x 128 block, two 4 x 64 statistics
+// tiles).  Stage: 16 input channels, one converted (2 + 2) x (64 + 2) low-res patch in LDS (the staging of conv_igemm_bf16x3.h
+// and conv_igemm_f16x2_ct2.h on a low-res tile, no upsampling gather).  Half-stage h = row phase p: its kernel W[h] holds the 8 taps
+// (2 column phases x 2 x 2) of that phase, 32 KiB.  Wave w = (q = w & 1, low-res row g = w >> 1): it runs column phase q on the
+// 64 positions of its row, 4 tap steps per half-stage, and keeps both row phases' accumulators (2 x 128 registers, as the
+// two-tile kernel).  One barrier per half-stage, everything in flight drained there (vmcnt(0)):
+//   (cg, h)  steps 0 .. 2  pieces 2 .. 7 of the next half-stage's kernel into W[h ^ 1]
+//            step 3        barrier; pieces 0, 1 of the half-stage after it into W[h]; fragments of the next half-stage's step 0
+//   (cg, 0)  steps 0 .. 3  the patch of stage cg + 1 converted from the raw registers into P[pp ^ 1], one pixel per step
+//   (cg, 1)  steps 0 .. 2  the raw loads of stage cg + 2
+// Epilogue: through LDS, 32 channels at a time -- the waves' column phases interleaved into whole 128-column high-res rows, + bias,
+// 16-byte stores, the (mean, M2) of the two 4 x 64 tiles (the TileStats layout of block config D).  No residual, no activation.
+// The kernel lives in this instantiation file (not a header) so that the CPU emulation of tests/emul/convlib.py, which rewrites
+// the instantiation files and a fixed list of headers, compiles it.
+#include "conv_dispatch.h"
+#include "conv_igemm_bf16x3.h"
+#include "conv_split_pair_common.h"
+
+struct ConvCfgUp2 {
+  static constexpr int BM = 64, TM = 2, TP = 2, KC = 16, NPL = 2;
+  static constexpr int TRL = 2, TWL = 64;                // low-res extent of an item
+  static constexpr int PR = TRL + 2, NQ = TWL / 4, NQ1 = NQ + 1;
+  static constexpr int SUB = ((PR * NQ1 + 4 + 11) / 16) * 16 + 4;
+  static constexpr int CHS = 4 * SUB, NG = 2, QPG = 128, NHQ = 2 * PR;
+  // (16-byte slots)
+  static constexpr int WPLANE = 2 * BM;                  // one plane of a tap: [half][BM]
+  static constexpr int WTAP = NPL * WPLANE;
+  static constexpr int WST = 8 * WTAP;                   // a half-stage's kernel: [q][a][b][plane][half][BM] -- 32 KiB
+  static constexpr int WST_BYTES = WST * 16;
+  static constexpr int PPL = NG * CHS, PBUF = NPL * PPL;
+  static constexpr int OFF_P = 0, OFF_W = 2 * PBUF, OFF_SCT = OFF_W + 2 * WST;
+  static constexpr int SCT = 1024;
+  static constexpr int OFF_BIAS_F = OFF_SCT * 4 + 2 * SCT;          // (float index) [BM]
+  static constexpr int EPI_CS = 4 * 132 + 4;                         // floats per channel of the epilogue image: 4 rows of 128 + 4
+  static constexpr int LDS_BYTES = (OFF_BIAS_F + BM) * 4;
+  static_assert(32 * EPI_CS <= OFF_SCT * 4, "the epilogue image lives in the patch and kernel buffers");
+  static_assert(WST_BYTES == 32 * 1024, "eight 1 KiB pieces per wave and half-stage");
+  static_assert(PR * NQ + NHQ <= QPG, "one interior quad or one halo pixel per thread and stage");
+  static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+};
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
+  using Cfg = ConvCfgUp2;
+  using opx8 = halfx8;
+  constexpr int NPL = 2, NPROD = 3;
+  constexpr int BM = Cfg::BM, TM = Cfg::TM, TP = Cfg::TP, KC = Cfg::KC;
+  constexpr int PR = Cfg::PR, NQ = Cfg::NQ, NQ1 = Cfg::NQ1, SUB = Cfg::SUB, CHS = Cfg::CHS, QPG = Cfg::QPG;
+  constexpr int NHQ = Cfg::NHQ, PPL = Cfg::PPL, PBUF = Cfg::PBUF;
+  // (names of the shared staging macros: a low-res tile without the upsampling gather)
+  constexpr bool UPS = false;
+  constexpr int TW = Cfg::TWL, TWS = Cfg::TWL;
+
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5, l32 = lane & 31;
+  const int wq = wave & 1;                               // column phase of the wave
+  const int p0 = (wave >> 1) * TP * 32;                  // its 64 positions: low-res row wave >> 1 of the item
+  float sat_m = 0.0f;
+
+  const int HW = a.H * a.W;
+  const bool has_affine = a.scale != nullptr;
+  const float in_scale = a.in_scale;
+  constexpr float CLAMP_HI = 65504.0f;
+  const float clamp_lo = a.relu_in ? 0.0f : -CLAMP_HI;
+  const int nst = a.n_cchunks;
+  const int nptiles = a.tiles_x * a.tiles_y;
+
+  // ---- staging map (conv_igemm_bf16x3.h) ----
+  const int q_u = tid % QPG;
+  const int q_g = __builtin_amdgcn_readfirstlane(tid / QPG);
+  const bool is_quad = q_u < PR * NQ;
+  const int hq = q_u - PR * NQ;
+  const bool is_halo = !is_quad && hq < NHQ;
+  const int h_side = hq & 1;
+  const int q_r = is_quad ? q_u / NQ : (is_halo ? hq >> 1 : 0);
+  const int q_c = is_quad ? q_u - q_r * NQ : 0;
+  int q_slb[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int dump = q_g * CHS + i * SUB + PR * NQ1 + (q_u & 3);
+    const int own = is_quad ? q_g * CHS + i * SUB + q_r * NQ1 + q_c : q_g * CHS + h_side * SUB + q_r * NQ1 + NQ;
+    q_slb[i] = ((is_quad || (is_halo && i == (h_side ? 0 : 3))) ? own : dump) * 16;
+  }
+
+  floatx16 acc_lo[2][TM][TP], acc_hi[2][TM][TP];         // [row phase]
+
+  // ---- work items: (sample, low-res tile, channel tile), XCD-contiguous, channel tile fastest; persistent blocks ----
+  const int q8 = a.n_work >> 3, r8 = a.n_work & 7;
+  const int xcd = blockIdx.x & 7;
+  const int n_mine = q8 + (xcd < r8 ? 1 : 0);
+  const int l_base = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+  const int l_stride = (gridDim.x + 7) >> 3;
+// byte address of the packed kernel of (channel tile c_, stage k_, row phase p_)
+#define EMO_U_WPTR(c_, k_, p_) (reinterpret_cast<const char*>(a.wpk) + ((long)((c_) * nst + (k_)) * 2 + (p_)) * Cfg::WST_BYTES)
+
+  const int a_off = (half * BM + l32) * 16;
+  EMO_P_DECLARE_B_OFF()
+
+  const char* const lds_c = reinterpret_cast<const char*>(smem);
+  char* const lds_w = reinterpret_cast<char*>(smem);
+  opx8 fa_[2][NPL][TM], fb_[2][NPL][TP];
+// fragments of tap (a_, b_) of half-stage buffer hb_ (patch buffer at byte pbyte_): the wave's column phase wq
+#define EMO_U_LOAD_FRAGS_PLANE(set_, pl_, hb_, pbyte_, a_, b_)                                        \
+  {                                                                                                   \
+    _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                    \
+      fa_[set_][pl_][i] = *reinterpret_cast<const opx8*>(lds_c + a_off + (Cfg::OFF_W + (hb_) * Cfg::WST + \
+          ((wq * 4 + (a_) * 2 + (b_)) * NPL + (pl_)) * Cfg::WPLANE + i * 32) * 16);                   \
+    _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                    \
+      fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + (EMO_P_B_OFF(j, (hb_) + (a_), wq + (b_)) + (pbyte_)) + ((pl_) * PPL) * 16); \
+  }
+
+  float* const sct = smem + Cfg::OFF_SCT * 4;
+  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(smem);
+  const unsigned lane16 = (unsigned)lane * 16u;
+
+  floatx4 qv[8];
+  float q_lo, q_hi;
+  int q_tix;
+  floatx4 q_sc, q_sh;
+  opx8 cv_h, cv_m;
+  emo_intx4 xrs = emo_raw_buffer(a.x);
+  unsigned usoff[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) usoff[u] = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)u * (unsigned)HW * 4u));
+  unsigned lq_off = 0;
+  bool lq_ok = false;
+  unsigned q_vo;
+// the raw loads of stage st_ (16 input channels)
+#define EMO_U_ISSUE_BEGIN(st_)                                                                        \
+  {                                                                                                   \
+    const int c0_ = (st_) * KC + q_g * 8;                                                             \
+    const bool cv_ = c0_ < a.Cin;                                                                     \
+    const int cs_ = cv_ ? c0_ : 0;                                                                    \
+    const bool keep_ = lq_ok && cv_;                                                                  \
+    q_lo = keep_ ? clamp_lo : 0.0f;                                                                   \
+    q_hi = keep_ ? CLAMP_HI : 0.0f;                                                                   \
+    q_vo = lq_off + (unsigned)cs_ * (unsigned)HW * 4u;                                                \
+    q_tix = (has_affine ? cs_ : (cs_ & (Cfg::SCT - 1))) >> 2;                                         \
+  }
+#define EMO_U_ISSUE_LOADS(u0_, u1_)                                                                   \
+  { _Pragma("unroll") for (int u = (u0_); u < (u1_); u += 2) emo_bload4x2_pinned(xrs, q_vo, usoff[u], usoff[u + 1], qv[u], qv[u + 1]); }
+#define EMO_U_HALF_TABLE(hf_)                                                                         \
+  {                                                                                                   \
+    const floatx4* t4_ = reinterpret_cast<const floatx4*>(sct) + q_tix + (hf_);                       \
+    q_sc = t4_[0]; q_sh = t4_[Cfg::SCT / 4];                                                          \
+  }
+#define EMO_U_TOUCH_QUAD() { _Pragma("unroll") for (int u = 0; u < 8; ++u) emo_touch4(qv[u]); }
+// conversion of pixel i_ of the raw registers (both halves of the lane's 8 channels) into the patch buffer at byte pbyte_
+#define EMO_U_CONV_PIXEL(pbyte_, i_)                                                                  \
+  {                                                                                                   \
+    _Pragma("unroll") for (int hf_ = 0; hf_ < 2; ++hf_) {                                             \
+      EMO_U_HALF_TABLE(hf_)                                                                           \
+      float t_[4];                                                                                    \
+      _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                   \
+        t_[k] = __fmaf_rn(qv[4 * hf_ + k][i_], q_sc[k], q_sh[k]);                                     \
+      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[0])), __builtin_fabsf(t_[1])); \
+      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[2])), __builtin_fabsf(t_[3])); \
+      _Pragma("unroll") for (int k = 0; k < 4; k += 2)                                                \
+        emo_split_f16x2_pair(__builtin_amdgcn_fmed3f(t_[k], q_lo, q_hi), __builtin_amdgcn_fmed3f(t_[k + 1], q_lo, q_hi), \
+                             cv_h, cv_m, 4 * hf_ + k);                                                \
+    }                                                                                                 \
+    char* d_ = lds_w + (q_slb[i_] + (pbyte_));                                                        \
+    *reinterpret_cast<opx8*>(d_) = cv_h;                                                              \
+    *reinterpret_cast<opx8*>(d_ + PPL * 16) = cv_m;                                                   \
+  }
+// piece k_ = 0 .. 7 of a half-stage's kernel (wave w copies the 1 KiB pieces w + 4 k) into W[wb_]
+#define EMO_U_DMA_PIECE(ptr_, wb_, k_)                                                                \
+  {                                                                                                   \
+    const int j_ = wave + 4 * (k_);                                                                   \
+    emo_dma16_pinned_s((ptr_) + j_ * 1024, lane16, smem_lds + (unsigned)((Cfg::OFF_W + (wb_) * Cfg::WST) * 16 + j_ * 1024)); \
+  }
+
+  constexpr int PA3[3] = {1, 0, 0}, PB3[3] = {0, 1, 0};
+  constexpr int NTE = Cfg::SCT / 256;
+
+  for (int idx8 = blockIdx.x >> 3; idx8 < n_mine; idx8 += l_stride) {
+    // ---- item ----
+    const int l_ = l_base + idx8;
+    const int cotile = __builtin_amdgcn_readfirstlane(l_ % a.n_cotiles);
+    const int rest_ = l_ / a.n_cotiles;
+    const int it_n = __builtin_amdgcn_readfirstlane(rest_ / nptiles);
+    const int lt_ = rest_ - it_n * nptiles;
+    const int x0 = __builtin_amdgcn_readfirstlane((lt_ % a.tiles_x) * Cfg::TWL);     // low-res origin
+    const int y0 = __builtin_amdgcn_readfirstlane((lt_ / a.tiles_x) * Cfg::TRL);
+    {
+      const int q_y_ = y0 - 1 + q_r;
+      const int q_x_ = is_quad ? x0 + 4 * q_c : (h_side ? x0 + TWS : x0 - 4);
+      lq_ok = (is_quad || is_halo) && (unsigned)q_y_ < (unsigned)a.H && q_x_ >= 0 && q_x_ < a.W;
+      lq_off = lq_ok ? (unsigned)(q_y_ * a.W + q_x_) * 4u : 0u;
+    }
+    xrs = emo_raw_buffer(a.x + (long)it_n * a.Cin * HW);
+
+    // ---- prologue: tables, bias, the whole kernel of (stage 0, p = 0), pieces 0, 1 of (0, 1), patch 0 converted, loads of stage 1 ----
+#pragma unroll
+    for (int u = 0; u < 8; ++u) asm volatile("" : "=v"(qv[u]));
+    asm volatile("" : "=v"(cv_h));
+    asm volatile("" : "=v"(cv_m));
+    {
+      const char* const w0_ = EMO_U_WPTR(cotile, 0, 0);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) EMO_U_DMA_PIECE(w0_, 0, k)
+      const char* const w1_ = EMO_U_WPTR(cotile, 0, 1);
+      EMO_U_DMA_PIECE(w1_, 1, 0)
+      EMO_U_DMA_PIECE(w1_, 1, 1)
+    }
+    EMO_U_ISSUE_BEGIN(0)
+    EMO_U_ISSUE_LOADS(0, 8)
+#pragma unroll
+    for (int k = 0; k < NTE; ++k) {       // (without an affine the index wraps at SCT: identity entries)
+      const int c = tid + 256 * k;
+      if (c < min(a.Cin, Cfg::SCT)) {
+        const bool real = has_affine;
+        sct[c] = (real ? a.scale[(long)it_n * a.Cin + c] : 1.0f) * in_scale;
+        sct[Cfg::SCT + c] = (real ? a.shift[(long)it_n * a.Cin + c] : 0.0f) * in_scale;
+      }
+    }
+    if (tid < BM) smem[Cfg::OFF_BIAS_F + tid] = a.bias != nullptr ? a.bias[cotile * BM + tid] : 0.0f;
+    EMO_P_WAIT(0);
+    EMO_U_TOUCH_QUAD()
+    __syncthreads();   // scale / shift tables visible
+#pragma unroll
+    for (int i = 0; i < 4; ++i) EMO_U_CONV_PIXEL(Cfg::OFF_P * 16, i)
+    EMO_U_ISSUE_BEGIN(nst > 1 ? 1 : 0)
+    EMO_U_ISSUE_LOADS(0, 8)
+    EMO_P_BARRIER(0);                    // (P[0] visible, W[0] and the loads of stage 1 landed)
+    EMO_U_TOUCH_QUAD()
+
+    // ---- K loop ----
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TP; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { acc_lo[c][i][j][r] = 0.0f; acc_hi[c][i][j][r] = 0.0f; }
+#pragma unroll
+    for (int pl = 0; pl < NPL; ++pl) EMO_U_LOAD_FRAGS_PLANE(0, pl, 0, Cfg::OFF_P * 16, 0, 0)
+    int pp = 0;
+    for (int cg = 0; cg < nst; ++cg) {
+      const int pcur_b = (Cfg::OFF_P + pp * PBUF) * 16, pnxt_b = (Cfg::OFF_P + (pp ^ 1) * PBUF) * 16;
+      const bool last_ = cg + 1 >= nst;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        // t = (cg, h); t + 1 = (cg, 1) resp. (cg + 1, 0); t + 2 = (cg + 1, h).  Past the item's end nothing is fetched
+        const bool have1_ = h == 0 || !last_, have2_ = !last_;
+        const char* const dma1 = EMO_U_WPTR(cotile, h == 0 ? cg : cg + 1, h ^ 1);
+        const char* const dma2 = EMO_U_WPTR(cotile, cg + 1, h);
+        if (EMO_CONV_SETPRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int gs = 0; gs < 4; ++gs) {
+          const int fcur = (h * 4 + gs) & 1, fnxt = fcur ^ 1;
+          if (gs == 3) { EMO_P_BARRIER(0); }
+          if (gs == 3 && h == 1) EMO_U_TOUCH_QUAD()
+          if (gs == 0 && h == 1) {
+            const int tgt_ = cg + 2 < nst ? cg + 2 : nst - 1;     // (past the end: a dead re-load)
+            EMO_U_ISSUE_BEGIN(tgt_)
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          {
+            const int an = gs < 3 ? (gs + 1) >> 1 : 0, bn = gs < 3 ? (gs + 1) & 1 : 0;
+            const int hbn = gs < 3 ? h : h ^ 1;
+            const int pbn = (gs == 3 && h == 1) ? pnxt_b : pcur_b;
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl) {
+              EMO_U_LOAD_FRAGS_PLANE(fnxt, pl, hbn, pbn, an, bn)
+              if (gs < 3 && have1_) EMO_U_DMA_PIECE(dma1, h ^ 1, 2 + 2 * gs + pl)
+              if (gs == 3 && have2_) EMO_U_DMA_PIECE(dma2, h, pl)
+              if (h == 1 && gs == 0) EMO_U_ISSUE_LOADS(2 * pl, 2 * pl + 2)
+              if (h == 1 && gs > 0 && gs < 3 && pl == 0) EMO_U_ISSUE_LOADS(2 + 2 * gs, 4 + 2 * gs)
+            }
+          }
+          if (h == 0) EMO_U_CONV_PIXEL(pnxt_b, gs)
+#pragma unroll
+          for (int p = 0; p < NPROD; ++p) {
+            const int pa = PA3[p], pb = PB3[p];
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+              for (int j = 0; j < TP; ++j) {
+                floatx16& acc_ = (pa == 0 && pb == 0) ? acc_lo[h][i][j] : acc_hi[h][i][j];
+                acc_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb_[fcur][pb][j], fa_[fcur][pa][i], acc_, 0, 0, 0);
+              }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (EMO_CONV_SETPRIO) __builtin_amdgcn_s_setprio(0);
+      }
+      pp ^= 1;
+    }
+
+    // ---- epilogue: 32 channels at a time through an LDS image [channel][4 high-res rows][128 columns (+ 4)] ----
+    EMO_P_WAIT(0);
+    __syncthreads();
+    const bool want_stats = a.gn_stats != nullptr;
+    const int Ho = a.Hl, Wo = a.Wl;
+    const unsigned oplane = (unsigned)Ho * Wo;
+    const int tiles_xo = Wo / 64;
+    const int ec = tid >> 4, eu = tid & 15;                 // read-out: channel ec (+ 16), columns 4 eu + 64 k
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int j = 0; j < TP; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float v = (emo_acc_read(acc_lo[p][i][j][r]) + emo_acc_read(acc_hi[p][i][j][r])) * a.out_scale;
+            const int m = (r >> 2) * 8 + half * 4 + (r & 3);          // low-res column j * 32 + m of the wave's row
+            const int hr = 2 * (wave >> 1) + p, col = 2 * (j * 32 + m) + wq;
+            smem[l32 * Cfg::EPI_CS + hr * 132 + col] = v;
+          }
+      __syncthreads();
+#pragma unroll
+      for (int cc = 0; cc < 2; ++cc) {
+        const int c = cc * 16 + ec;
+        const int co = cotile * BM + i * 32 + c;
+        const float bs = smem[Cfg::OFF_BIAS_F + i * 32 + c];
+        float* const obase = a.out + ((long)it_n * a.Cout + co) * oplane;
+        float s_[2] = {0.0f, 0.0f};
+        floatx4 v_[4][2];
+#pragma unroll
+        for (int hr = 0; hr < 4; ++hr)
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            floatx4 v = *reinterpret_cast<const floatx4*>(smem + c * Cfg::EPI_CS + hr * 132 + 4 * eu + 64 * k);
+            v = v + floatx4{bs, bs, bs, bs};
+            v_[hr][k] = v;
+            float* const op = obase + (unsigned)(2 * y0 + hr) * Wo + (2 * x0 + 4 * eu + 64 * k);
+            if (EMO_CONV_NT_STORE) __builtin_nontemporal_store(v, reinterpret_cast<floatx4*>(op));
+            else *reinterpret_cast<floatx4*>(op) = v;
+            s_[k] += (v[0] + v[1]) + (v[2] + v[3]);
+          }
+        if (want_stats) {
+          // (mean, M2) of the two 4 x 64 tiles: 16 lanes of a DPP row per channel, 16 values per lane and tile
+          emo_row16_sum_n<2>(s_);
+          float m2_[2] = {0.0f, 0.0f};
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            s_[k] *= 1.0f / 256.0f;
+#pragma unroll
+            for (int hr = 0; hr < 4; ++hr)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const float d = v_[hr][k][e] - s_[k];
+                m2_[k] = __fmaf_rn(d, d, m2_[k]);
+              }
+          }
+          emo_row16_sum_n<2>(m2_);
+          if (eu == 0) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const int ptile = (y0 >> 1) * tiles_xo + (x0 >> 5) + k;       // the 4 x 64 high-res tile
+              reinterpret_cast<float2*>(a.gn_stats)[((long)it_n * (oplane / 256) + ptile) * a.Cout + co] = make_float2(s_[k], m2_[k]);
+            }
+          }
+        }
+      }
+      __syncthreads();       // (the image is rewritten by the next channel block, the buffers by the next item's prologue)
+    }
+  }
+  if (a.sat_flag != nullptr && sat_m > 65504.0f) *a.sat_flag = 1;   // (every writer stores the same value)
+#undef EMO_U_WPTR
+#undef EMO_U_LOAD_FRAGS_PLANE
+#undef EMO_U_ISSUE_BEGIN
+#undef EMO_U_ISSUE_LOADS
+#undef EMO_U_HALF_TABLE
+#undef EMO_U_TOUCH_QUAD
+#undef EMO_U_CONV_PIXEL
+#undef EMO_U_DMA_PIECE
+}
+
+// The launch form (emoportraits_amd.pack.up2_launch_fits mirrors every check): 2-D, 3x3 with the fused nearest x2 upsample, no
+// K split, no residual, no activation, not a guarded launch, whole 64-channel tiles, a multiple of 8 input channels (at most SCT
+// with an affine), a low-res width that is a multiple of 64 and an even low-res height, 16-byte aligned input and output, input
+// offsets inside 2^32 bytes per sample, output planes inside 2^31 elements.
+int conv_f16x2_up2_launch(ConvArgs a, hipStream_t s) {
+  using Cfg = ConvCfgUp2;
+  if (a.KD != 1 || a.D != 1 || a.ksplit != 1 || a.res != nullptr || a.act != EMO_ACT_NONE || a.run_if != nullptr) return EMO_ERR_UNSUPPORTED;
+  if (a.Cout % Cfg::BM || a.Cin % 8 || (a.scale && a.Cin > Cfg::SCT)) return EMO_ERR_UNSUPPORTED;
+  if (a.W % Cfg::TWL || a.H % Cfg::TRL) return EMO_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<unsigned long long>(a.x) & 15ull) || (reinterpret_cast<unsigned long long>(a.out) & 15ull)) return EMO_ERR_ALIGN;
+  if ((unsigned long long)a.Cin * a.H * a.W * 4ull >= (1ull << 32) || (long)a.Hl * a.Wl >= (1l << 31)) return EMO_ERR_UNSUPPORTED;
+  const long nt = (long)(a.W / Cfg::TWL) * (a.H / Cfg::TRL);
+  const int cot = a.Cout / Cfg::BM;
+  if (a.N > 65535 || nt * cot * a.N > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
+  auto kern = conv_igemm_f16x2_up2_kernel;
+  const int rc = emo_raise_dynamic_lds(kern);
+  if (rc != EMO_OK) return rc;
+  a.tiles_x = a.W / Cfg::TWL;
+  a.tiles_y = a.H / Cfg::TRL;
+  a.tiles_z = 1;
+  a.n_cchunks = (a.Cin + Cfg::KC - 1) / Cfg::KC;
+  a.stages_per_split = a.n_cchunks;
+  a.partial = nullptr;
+  a.cot0 = 0;
+  a.n_cotiles = cot;
+  a.n_work = (int)(nt * cot * a.N);
+  const int ncu = emo_cu_count();
+  const int grid = a.n_work > ncu ? ncu : a.n_work;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
+  return emo_launch_status();
+}

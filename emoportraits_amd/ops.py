@@ -327,6 +327,11 @@ def conv_igemm(x, layer, scale=None, shift=None, relu_in=False, ups=False, res=N
     if want_stats and ks == 1 and (D * Hl * Wl) % bp == 0:
         stats = TileStats(torch.empty((N, D * Hl * Wl // bp, layer.cout, 2), device=x.device, dtype=torch.float32), bp)
     layer.last_plan = (cfg, ks, prec)        # which kernel ran (bench.py meters the kernels separately)
+    # the fp16 split of an up-convolution as four 2x2 phase convolutions (emo_conv_igemm_f16x2, cfg CFG_F16X2_UP2): same plan
+    up2 = prec == "f16x2" and not pointwise_split and cfg == pack_mod.CFG_D and ks == 1 and not three_d and pack_mod.up2_launch_fits(
+        layer.cout, Cin, layer.kd, layer.kh, layer.kw, N, H, W, ups, affine=scale is not None, res=res is not None, act=act,
+        aligned16=x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0)
+    layer.last_form = "up2" if up2 else None
     entry = {"f32": lib.emo_conv_igemm_f32, "f16": lib.emo_conv_igemm_f16acc32, "bf16x3": lib.emo_conv_igemm_bf16x3,
              "f16x2": lib.emo_conv_igemm_f16x2, "f16w8": lib.emo_conv_igemm_f16w8}[prec]
     wpk = layer.packed(cfg, prec)
@@ -356,8 +361,13 @@ def conv_igemm(x, layer, scale=None, shift=None, relu_in=False, ups=False, res=N
             if stats is not None:
                 gks = 1
             gplan = (gcfg, gks, layer.packed(gcfg))
-        rc = entry(hip.ptr(x), hip.ptr(wpk), *common, pack_mod.F16X2_IN_SCALE, layer.w_scale, flag)
-        hip.check(rc, f"emo_conv_igemm_f16x2[{layer.name}]")
+        if up2:
+            ucommon = common[:18] + (pack_mod.CFG_F16X2_UP2,) + common[19:]
+            rc = entry(hip.ptr(x), hip.ptr(layer.packed(cfg, "f16x2_up2")), *ucommon, pack_mod.F16X2_IN_SCALE, layer.w_scale_up2, flag)
+            hip.check(rc, f"emo_conv_igemm_f16x2[{layer.name}, phase form]")
+        else:
+            rc = entry(hip.ptr(x), hip.ptr(wpk), *common, pack_mod.F16X2_IN_SCALE, layer.w_scale, flag)
+            hip.check(rc, f"emo_conv_igemm_f16x2[{layer.name}]")
         if gplan is not None:
             gcfg, gks, gw = gplan
             gws = torch.empty((gks, out.numel()), device=x.device, dtype=torch.float32) if gks > 1 else None

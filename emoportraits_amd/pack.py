@@ -208,6 +208,62 @@ def pack_weight_f16x2(w, bm=None):
     return planes.view(-1), w_scale
 
 
+# the phase form of a 3x3 layer with the fused nearest x2 upsample (emo_conv_igemm_f16x2 with cfg CFG_F16X2_UP2 = 7, ABI 11;
+# csrc/conv_inst_f16x2_up2.hip):
+# kernel row a of row phase p sums the 3x3 rows UP2_TAPS[p][a], columns likewise; EMO_CONV_UP2=0 keeps such layers on the direct
+# kernels (A/B switch, read at every launch)
+UP2_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+CFG_F16X2_UP2 = 7     # include/emo_hip.h EMO_CONV_CFG_F16X2_UP2: not a block config of the planner, a weight layout of the C entry
+
+
+def up2_enabled():
+    return __import__("os").environ.get("EMO_CONV_UP2", "1") != "0"
+
+
+def pack_weight_f16x2_up2(w):
+    """operand layout of emo_conv_igemm_f16x2 with cfg CFG_F16X2_UP2: the four 2x2 phase kernels w_pq[a][b] = sum of w[r][s] over r in
+    UP2_TAPS[p][a], s in UP2_TAPS[q][b], summed in fp64, as two fp16 planes of w_pq * w_scale (one power of two for all 16 phase
+    taps, max|w_pq| * w_scale in [512, 1024), both planes split from fp64),
+    [co_tile][cin chunk of 16][p][q][a][b][plane][half][BM = 64][8] (channel in chunk = 8 * half + 0..7) -> (flat fp16, w_scale)"""
+    if w.dim() == 5:
+        if w.shape[2] != 1:
+            raise ValueError("2-D layers only")
+        w = w[:, :, 0]
+    cout, cin, kh, kw = w.shape
+    if (kh, kw) != (3, 3):
+        raise ValueError("3x3 kernels only")
+    bm, kc = BF16X3_BM, BF16X3_KC
+    n_cot = -(-cout // bm)
+    n_cc = -(-cin // kc)
+    wd = w.double()
+    rows = torch.stack([torch.stack([wd[:, :, list(rs)].sum(2) for rs in UP2_TAPS[p]], 2) for p in range(2)], 2)   # [co, ci, p, a, s]
+    ph = torch.stack([torch.stack([rows[..., list(cs)].sum(-1) for cs in UP2_TAPS[q]], -1) for q in range(2)], 3)  # [co, ci, p, q, a, b]
+    wmax = float(ph.abs().max())
+    w_scale = 2.0 ** math.floor(math.log2(1023.0 / wmax)) if wmax > 0 else 1.0
+    wp = torch.zeros((n_cot * bm, n_cc * kc, 2, 2, 2, 2), dtype=torch.float64)
+    wp[:cout, :cin] = ph * w_scale
+    w1 = wp.to(torch.float16)
+    w2 = (wp - w1.double()).to(torch.float16)
+    planes = torch.stack((w1, w2), 0)
+    # [plane, cot, BM, cc, half, k8, p, q, a, b] -> [cot, cc, p, q, a, b, plane, half, BM, k8]
+    planes = planes.view(2, n_cot, bm, n_cc, 2, 8, 2, 2, 2, 2).permute(1, 3, 6, 7, 8, 9, 0, 4, 2, 5).contiguous()
+    return planes.view(-1), w_scale
+
+
+def up2_launch_fits(cout, cin, kd, kh, kw, N, H, W, ups, affine=False, res=False, act="none", ksplit=1, aligned16=True):
+    """the launch form of the phase kernel (conv_f16x2_up2_launch and its dispatch -- every check of the C side has its
+    mirror here): nearest x2 upsample, 2-D 3x3, whole 64-channel tiles, 8-channel groups (at most the 1024-entry scale table
+    with an affine), a low-res width that is a multiple of 64 and an even low-res height, no residual, no activation, no K split,
+    16-byte aligned input and output, 32-bit byte offsets inside a sample's input"""
+    if not up2_enabled() or not ups or kd != 1 or (kh, kw) != (3, 3) or res or act != "none" or ksplit != 1 or not aligned16:
+        return False
+    if cout % BF16X3_BM or cin % 8 or (affine and cin > 1024) or W % 64 or H % 2:
+        return False
+    if cin * H * W * 4 >= (1 << 32) or 4 * H * W >= (1 << 31) or H * W >= (1 << 30):
+        return False
+    return N <= 65535 and (W // 64) * (H // 2) * (cout // BF16X3_BM) * N <= 0x7fffffff
+
+
 def pack_weight_f16w8(w):
     """operand layout of emo_conv_igemm_f16w8 (plain fp16 operands on the eight-wave two-tile kernel): the fp16-split layout with
     its two PLANES holding the two 16-channel K BLOCKS of a 32-channel stage,
@@ -562,6 +618,12 @@ class PackedConv:
 
     def packed(self, cfg, precision="f32"):
         """packed weights for a block config: fp32 layout, or the fp16 operand layout (64 x 256 and 128 x 256 tiles)"""
+        if precision == "f16x2_up2":
+            # (on demand: only layers that run with the fused upsample need the phase kernels)
+            if "f16x2_up2" not in self._packed:
+                flat, self.w_scale_up2 = pack_weight_f16x2_up2(self._weight)
+                self._packed["f16x2_up2"] = flat.to(self.device)
+            return self._packed["f16x2_up2"]
         if precision == "f16w8":
             if "f16w8" not in self._packed:
                 flat, self.w_scale16 = pack_weight_f16w8(self._weight)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 10
+#define EMO_ABI_VERSION 11
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -289,6 +289,21 @@ int emo_conv_igemm_f16x2(const float* x, const void* wpk2, const float* bias,
  * with BM = 32 (emoportraits_amd.pack.pack_weight_f16x2(w, bm=32)); 4 x 64 position tiles (W % 64 == 0, H % 4 == 0), no fused
  * upsample.  The guarded recomputation of such a layer is emo_conv_igemm_bf16x3 with cfg 3 and the BM = 64 weights, as for
  * every 3x3 layer. */
+/* ABI 11.  emo_conv_igemm_f16x2 with cfg = EMO_CONV_CFG_F16X2_UP2: a 3x3 layer with the fused nearest x2 upsample (ups = 1) as
+ * four 2x2 PHASE convolutions on the low-res input (csrc/conv_inst_f16x2_up2.hip): output pixel (2i + p, 2j + q) = sum over
+ * a, b in {0, 1} of w_pq[a][b] . x[i - 1 + p + a][j - 1 + q + b], w_pq[a][b] = sum of the 3x3 taps w[r][s], r in R_p[a],
+ * s in R_q[b], R_0 = ({0}, {1, 2}), R_1 = ({0, 1}, {2}) -- 4 instead of 9 Cin MACs per output.  Same arithmetic (two fp16 terms
+ * of the scaled operands, three products, fp32 accumulation), operand-range contract and overflow_flag as above; the guarded
+ * recomputation behind it is the same emo_conv_igemm_bf16x3 launch (cfg 3, the DIRECT 3x3 weights).
+ *   wpk2 then is [co_tile][Cin chunk of 16][p][q][a][b][plane 1|2][half][BM = 64][8] fp16 of w_pq * w_scale, the sums taken in
+ *          fp64 from the fp32 weights, w_scale = the power of two that puts max|w_pq| into [512, 1024), both planes split from
+ *          fp64 (channel in chunk = 8 * half + 0..7; emoportraits_amd.pack.pack_weight_f16x2_up2).
+ * Launch form (emoportraits_amd.pack.up2_launch_fits mirrors every check): ups 1, D 1, KD 1, KH = KW = 3, ksplit 1, no residual,
+ * act EMO_ACT_NONE, Cout % 64 == 0, Cin % 8 == 0 (Cin <= 1024 with scale / shift), W % 64 == 0, H % 2 == 0, 16-byte aligned
+ * x and out, Cin * H * W * 4 < 2^32; EMO_ERR_UNSUPPORTED (EMO_ERR_ALIGN) otherwise.  gn_stats: the TileStats layout of block
+ * config D, [N][4 x 64 output tiles][Cout][2]. */
+#define EMO_CONV_CFG_F16X2_UP2 7
+
 int emo_conv_igemm_f32_guarded(const float* x, const float* wpk, const float* bias,
                                const float* scale, const float* shift, const float* res, float* out,
                                int N, int Cin, int Cout, int D, int H, int W, int KD, int KH, int KW,
