@@ -86,26 +86,46 @@ __device__ __forceinline__ void compute_taps(float gx, float gy, float gz, int D
   t.inb = m;
 }
 
+// Volume of sample n in a bank (the indexed entry): one load per block -- n is uniform across it -- kept in a scalar register.
+// False for an index outside [0, num_vols): the block then writes zeros and reads nothing of the bank.
+__device__ __forceinline__ bool bank_volume(int n, int& vsel, const int* __restrict__ vol_index, int num_vols) {
+  const int vi = __builtin_amdgcn_readfirstlane(vol_index[n]);
+  vsel = vi;
+  return (unsigned)vi < (unsigned)num_vols;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // NCDHW -> NCDHW.  grid = (ceil(nvox/256), channel chunks, N); one lane per output voxel.
 // ------------------------------------------------------------------------------------------------------
-template <int PAD, int MODE>
+// BankArgs (every sampler kernel of this file): empty, or (const int* vol_index, int num_vols) for the indexed entry
+// (emo_grid_sample3d_indexed_f32) -- sample n then reads volume vol_index[n] of a bank whose volumes are vol_bstride floats apart.
+// Empty, a kernel has the parameter list and code it has without a bank.
+template <int PAD, int MODE, typename... BankArgs>
 __global__ __launch_bounds__(256) void gs3d_ncdhw_kernel(
     const float* __restrict__ vol, const float* __restrict__ grid, const float* __restrict__ theta,
     const float* __restrict__ lin_x, const float* __restrict__ lin_y, const float* __restrict__ lin_z,
-    float* __restrict__ out, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, int c_per_block) {
+    float* __restrict__ out, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, int c_per_block, BankArgs... bank) {
+  constexpr bool IDX = sizeof...(BankArgs) != 0;
   const int nvox = Do * Ho * Wo;
   const int vox = blockIdx.x * 256 + threadIdx.x;
   if (vox >= nvox) return;
   const int n = blockIdx.z;
   const int c0 = blockIdx.y * c_per_block;
   const int c1 = min(c0 + c_per_block, C);
+  int vsel = n;
+  if constexpr (IDX) {
+    if (!bank_volume(n, vsel, bank...)) {
+      float* op = out + ((long)n * C + c0) * nvox + vox;
+      for (int c = c0; c < c1; ++c, op += nvox) *op = 0.0f;
+      return;
+    }
+  }
   float gx, gy, gz;
   load_coord<MODE>(grid, theta, lin_x, lin_y, lin_z, n, vox, nvox, Ho, Wo, gx, gy, gz);
   Taps t;
   compute_taps<PAD>(gx, gy, gz, D, H, W, t);
   const long DHW = (long)D * H * W;
-  const float* vp = vol + (long)n * vol_bstride + (long)c0 * DHW;
+  const float* vp = vol + (long)vsel * vol_bstride + (long)c0 * DHW;
   float* op = out + ((long)n * C + c0) * nvox + vox;
   int c = c0;
   for (; c + 4 <= c1; c += 4) {
@@ -288,20 +308,30 @@ struct ItemWalk {
 };
 
 // NDHWC -> NDHWC, 1-D grid of N * ceil(nvox/VPB) blocks
-template <int PAD, int MODE, int VPB, int ORDER, bool FMA>
+template <int PAD, int MODE, int VPB, int ORDER, bool FMA, typename... BankArgs>
 __global__ __launch_bounds__(256) void gs3d_cl_v2_kernel(
     const float* __restrict__ vol, const float* __restrict__ grid, const float* __restrict__ theta,
     const float* __restrict__ lin_x, const float* __restrict__ lin_y, const float* __restrict__ lin_z,
-    float* __restrict__ out, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, int bps) {
+    float* __restrict__ out, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, int bps, BankArgs... bank) {
+  constexpr bool IDX = sizeof...(BankArgs) != 0;
   __shared__ TapRec recs[VPB];
   const int LPV = C >> 2;
   const int nvox = Do * Ho * Wo;
   int n, blk;
   block_to_work<ORDER>(blockIdx.x, gridDim.x, bps, Do, n, blk);
   const int vox0 = blk * VPB;
+  int vsel = n;
+  if constexpr (IDX) {
+    if (!bank_volume(n, vsel, bank...)) {
+      const int nitems = min(VPB, nvox - vox0) * LPV;
+      float4* obase = reinterpret_cast<float4*>(out) + ((long)n * nvox + vox0) * LPV;
+      for (int item = threadIdx.x; item < nitems; item += 256) obase[item] = make_float4(0.f, 0.f, 0.f, 0.f);
+      return;
+    }
+  }
   stage_taps<PAD, MODE, VPB>(recs, grid, theta, lin_x, lin_y, lin_z, n, vox0, nvox, D, H, W, Ho, Wo);
   __syncthreads();
-  const char* vbytes = reinterpret_cast<const char*>(vol + (long)n * vol_bstride);
+  const char* vbytes = reinterpret_cast<const char*>(vol + (long)vsel * vol_bstride);
   const unsigned row_bytes = (unsigned)C * 4u;
   const int nitems = min(VPB, nvox - vox0) * LPV;
   float4* obase = reinterpret_cast<float4*>(out) + ((long)n * nvox + vox0) * LPV;
@@ -316,21 +346,32 @@ __global__ __launch_bounds__(256) void gs3d_cl_v2_kernel(
 // (48 KB at C = 96) instead of the 2x2x65 of an x-row (100 KB): half the L1 fills per output voxel.  The samplers are
 // bound by the per-CU L1 path (64-byte granules per clock + outstanding-miss capacity), not by L2 or HBM
 // (archive/profiles/r2_pmc_sampler_*.json), so fewer fills per voxel is the lever.  Needs Do, Ho, Wo multiples of 4.
-template <int PAD, int MODE, int ORDER>
+template <int PAD, int MODE, int ORDER, typename... BankArgs>
 __global__ __launch_bounds__(256) void gs3d_cl_brick_kernel(
     const float* __restrict__ vol, const float* __restrict__ grid, const float* __restrict__ theta,
     const float* __restrict__ lin_x, const float* __restrict__ lin_y, const float* __restrict__ lin_z,
-    float* __restrict__ out, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, int bps) {
+    float* __restrict__ out, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, int bps, BankArgs... bank) {
+  constexpr bool IDX = sizeof...(BankArgs) != 0;
   __shared__ TapRec recs[64];
   __shared__ int vox_of[64];
   const int LPV = C >> 2;
   const int nvox = Do * Ho * Wo;
   int n, blk;
   block_to_work<ORDER>(blockIdx.x, gridDim.x, bps, Do >> 2, n, blk);
+  int vsel = n;
+  if constexpr (IDX) {
+    if (!bank_volume(n, vsel, bank...)) {
+      float4* obase = reinterpret_cast<float4*>(out) + (long)n * nvox * LPV;
+      ItemWalk w(threadIdx.x, LPV);
+      for (int item = threadIdx.x; item < 64 * LPV; item += 256, w.next())
+        obase[(long)brick_voxel(blk, w.v, Ho, Wo) * LPV + w.q] = make_float4(0.f, 0.f, 0.f, 0.f);
+      return;
+    }
+  }
   stage_taps<PAD, MODE, 64, true>(recs, grid, theta, lin_x, lin_y, lin_z, n, blk, nvox, D, H, W, Ho, Wo);
   if (threadIdx.x < 64) vox_of[threadIdx.x] = brick_voxel(blk, threadIdx.x, Ho, Wo);
   __syncthreads();
-  const char* vbytes = reinterpret_cast<const char*>(vol + (long)n * vol_bstride);
+  const char* vbytes = reinterpret_cast<const char*>(vol + (long)vsel * vol_bstride);
   const unsigned row_bytes = (unsigned)C * 4u;
   float4* obase = reinterpret_cast<float4*>(out) + (long)n * nvox * LPV;
   ItemWalk w(threadIdx.x, LPV);
@@ -341,11 +382,12 @@ __global__ __launch_bounds__(256) void gs3d_cl_brick_kernel(
 }
 
 // NDHWC -> NCDHW, 1-D grid; dynamic LDS = VPB tap records + C * (VPB + 1) floats (transpose tile)
-template <int PAD, int MODE, int VPB, int ORDER, bool FMA>
+template <int PAD, int MODE, int VPB, int ORDER, bool FMA, typename... BankArgs>
 __global__ __launch_bounds__(256) void gs3d_cl2ncdhw_v2_kernel(
     const float* __restrict__ vol, const float* __restrict__ grid, const float* __restrict__ theta,
     const float* __restrict__ lin_x, const float* __restrict__ lin_y, const float* __restrict__ lin_z,
-    float* __restrict__ out, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, int bps, int nt_out) {
+    float* __restrict__ out, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, int bps, int nt_out, BankArgs... bank) {
+  constexpr bool IDX = sizeof...(BankArgs) != 0;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   TapRec* recs = reinterpret_cast<TapRec*>(smem);                 // VPB * 80 B
   float* tile = smem + VPB * (sizeof(TapRec) / 4);                 // [C][VPB + 1]
@@ -355,9 +397,22 @@ __global__ __launch_bounds__(256) void gs3d_cl2ncdhw_v2_kernel(
   int n, blk;
   block_to_work<ORDER>(blockIdx.x, gridDim.x, bps, Do, n, blk);
   const int vox0 = blk * VPB;
+  int vsel = n;
+  if constexpr (IDX) {
+    if (!bank_volume(n, vsel, bank...)) {
+      const int nv = min(VPB, nvox - vox0);
+      float* obase = out + (long)n * C * nvox + vox0;
+      for (int i = threadIdx.x; i < C * VPB; i += 256) {
+        const int c = i / VPB;
+        const int v = i - c * VPB;
+        if (v < nv) obase[(long)c * nvox + v] = 0.0f;
+      }
+      return;
+    }
+  }
   stage_taps<PAD, MODE, VPB>(recs, grid, theta, lin_x, lin_y, lin_z, n, vox0, nvox, D, H, W, Ho, Wo);
   __syncthreads();
-  const char* vbytes = reinterpret_cast<const char*>(vol + (long)n * vol_bstride);
+  const char* vbytes = reinterpret_cast<const char*>(vol + (long)vsel * vol_bstride);
   const unsigned row_bytes = (unsigned)C * 4u;
   const int nv = min(VPB, nvox - vox0);
   const int nitems = nv * LPV;
@@ -388,23 +443,42 @@ __global__ __launch_bounds__(256) void gs3d_cl2ncdhw_v2_kernel(
 
 constexpr int CL_VPB = 64;      // output voxels per block of the row-shaped kernels
 
+// The volume bank of the indexed entry: sample n reads volume index[n] of `num`.  index == nullptr: the plain entry (kernels with
+// an empty BankArgs); with a bank their (const int*, int) instantiations run, in the same block order.
+struct Bank {
+  const int* index;
+  int num;
+};
+
 template <int PAD, int MODE, int ORDER, bool FMA = false>
 int launch_cl_v2(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
                  const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-                 long vol_bstride, bool out_cl, hipStream_t s, int nt_out = 0) {
+                 long vol_bstride, bool out_cl, hipStream_t s, int nt_out, Bank bank) {
   const int nvox = Do * Ho * Wo;
   const int bps = emo_cdiv(nvox, CL_VPB);
   const long total = (long)bps * N;
   if (total > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
   if (ORDER == 3 && ((N & 7) || (bps % Do) || (nvox % CL_VPB) || ((bps / Do) % 8)))   // whole slices / groups, N % 8 == 0
     return launch_cl_v2<PAD, MODE, 1, FMA>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                           out_cl, s, nt_out);
+                                           out_cl, s, nt_out, bank);
+  const size_t lds = CL_VPB * sizeof(TapRec) + (size_t)C * (CL_VPB + 1) * sizeof(float);
+  if (!out_cl && lds > 64 * 1024) return EMO_ERR_UNSUPPORTED;
+  if constexpr (ORDER == 1) {     // (a bank never gets ORDER 3, which is for one shared volume: dispatch_cl_v2)
+    if (bank.index) {
+      if (out_cl)
+        hipLaunchKernelGGL((gs3d_cl_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA, const int*, int>), dim3((unsigned)total), dim3(256), 0, s, vol, grid,
+                           theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, bank.index, bank.num);
+      else
+        hipLaunchKernelGGL((gs3d_cl2ncdhw_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA, const int*, int>), dim3((unsigned)total), dim3(256), lds, s,
+                           vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, nt_out, bank.index,
+                           bank.num);
+      return emo_launch_status();
+    }
+  }
   if (out_cl) {
     hipLaunchKernelGGL((gs3d_cl_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA>), dim3((unsigned)total), dim3(256), 0, s, vol, grid,
                        theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps);
   } else {
-    const size_t lds = CL_VPB * sizeof(TapRec) + (size_t)C * (CL_VPB + 1) * sizeof(float);
-    if (lds > 64 * 1024) return EMO_ERR_UNSUPPORTED;
     hipLaunchKernelGGL((gs3d_cl2ncdhw_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA>), dim3((unsigned)total), dim3(256), lds, s, vol,
                        grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, nt_out);
   }
@@ -421,29 +495,34 @@ int launch_cl_v2(const float* vol, const float* grid, const float* theta, const 
 template <int PAD, int MODE>
 int dispatch_cl_v2(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
                    const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-                   long vol_bstride, bool out_cl, int variant, hipStream_t s) {
+                   long vol_bstride, bool out_cl, int variant, hipStream_t s, Bank bank) {
   if (variant < 0 || variant > 7) return EMO_ERR_BAD_ARG;
   const int nt_out = (variant & 2) && !out_cl;
+  const bool shared = vol_bstride == 0 && !bank.index;
   if ((variant & 1) && out_cl && !(Do & 3) && !(Ho & 3) && !(Wo & 3)) {
     const int bps = (Do * Ho * Wo) >> 6;
     const long total = (long)bps * N;
     if (total > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((gs3d_cl_brick_kernel<PAD, MODE, 1>), dim3((unsigned)total), dim3(256), 0, s, vol, grid, theta, lin_x,
-                       lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps);
+    if (bank.index)
+      hipLaunchKernelGGL((gs3d_cl_brick_kernel<PAD, MODE, 1, const int*, int>), dim3((unsigned)total), dim3(256), 0, s, vol, grid, theta, lin_x,
+                         lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, bank.index, bank.num);
+    else
+      hipLaunchKernelGGL((gs3d_cl_brick_kernel<PAD, MODE, 1>), dim3((unsigned)total), dim3(256), 0, s, vol, grid, theta, lin_x,
+                         lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps);
     return emo_launch_status();
   }
   if (variant & 4) {      // fused multiply-add accumulation (gather_quad<true>): row kernels only
-    if (vol_bstride == 0 && N >= 8)
+    if (shared && N >= 8)
       return launch_cl_v2<PAD, MODE, 3, true>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                              out_cl, s, nt_out);
+                                              out_cl, s, nt_out, bank);
     return launch_cl_v2<PAD, MODE, 1, true>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                            out_cl, s, nt_out);
+                                            out_cl, s, nt_out, bank);
   }
-  if (vol_bstride == 0 && N >= 8)
+  if (shared && N >= 8)
     return launch_cl_v2<PAD, MODE, 3>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                      out_cl, s, nt_out);
+                                      out_cl, s, nt_out, bank);
   return launch_cl_v2<PAD, MODE, 1>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                    out_cl, s, nt_out);
+                                    out_cl, s, nt_out, bank);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -472,19 +551,23 @@ __global__ __launch_bounds__(256) void repack_kernel(const float* __restrict__ i
 template <int PAD, int MODE>
 int launch(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
            const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-           long vol_bstride, int in_layout, int out_layout, int variant, hipStream_t s) {
+           long vol_bstride, int in_layout, int out_layout, int variant, hipStream_t s, Bank bank) {
   const int nvox = Do * Ho * Wo;
   if (in_layout == EMO_LAYOUT_NCDHW && out_layout == EMO_LAYOUT_NCDHW) {
     int cpb = variant > 0 ? variant : 8;
     if (cpb > C) cpb = C;
     dim3 g(emo_cdiv(nvox, 256), emo_cdiv(C, cpb), N);
-    hipLaunchKernelGGL((gs3d_ncdhw_kernel<PAD, MODE>), g, dim3(256), 0, s, vol, grid, theta, lin_x, lin_y, lin_z,
-                       out, C, D, H, W, Do, Ho, Wo, vol_bstride, cpb);
+    if (bank.index)
+      hipLaunchKernelGGL((gs3d_ncdhw_kernel<PAD, MODE, const int*, int>), g, dim3(256), 0, s, vol, grid, theta, lin_x, lin_y, lin_z,
+                         out, C, D, H, W, Do, Ho, Wo, vol_bstride, cpb, bank.index, bank.num);
+    else
+      hipLaunchKernelGGL((gs3d_ncdhw_kernel<PAD, MODE>), g, dim3(256), 0, s, vol, grid, theta, lin_x, lin_y, lin_z,
+                         out, C, D, H, W, Do, Ho, Wo, vol_bstride, cpb);
   } else if (in_layout == EMO_LAYOUT_NDHWC && (out_layout == EMO_LAYOUT_NDHWC || out_layout == EMO_LAYOUT_NCDHW)) {
     if (C % 4) return EMO_ERR_UNSUPPORTED;
     if ((long)D * H * W * C * 4 >= (1L << 32)) return EMO_ERR_UNSUPPORTED;   // 32-bit byte offsets
     return dispatch_cl_v2<PAD, MODE>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                     out_layout == EMO_LAYOUT_NDHWC, variant, s);
+                                     out_layout == EMO_LAYOUT_NDHWC, variant, s, bank);
   } else {
     return EMO_ERR_UNSUPPORTED;
   }
@@ -515,15 +598,15 @@ __global__ __launch_bounds__(256) void affine_grid3d_kernel(const float* __restr
 template <int PAD>
 int launch_pad(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
                const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-               long vol_bstride, int in_layout, int out_layout, int variant, int grid_kind, hipStream_t s) {
+               long vol_bstride, int in_layout, int out_layout, int variant, int grid_kind, hipStream_t s, Bank bank) {
   if (theta)
     return launch<PAD, MODE_THETA>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                   in_layout, out_layout, variant, s);
+                                   in_layout, out_layout, variant, s, bank);
   if (grid_kind == 1)
     return launch<PAD, MODE_DELTA>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                   in_layout, out_layout, variant, s);
+                                   in_layout, out_layout, variant, s, bank);
   return launch<PAD, MODE_GRID>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                in_layout, out_layout, variant, s);
+                                in_layout, out_layout, variant, s, bank);
 }
 
 }  // namespace
@@ -534,10 +617,11 @@ int emo_gs3d_tile_dispatch(const float* vol, const float* grid, const float* the
                            int grid_kind, void* stream);
 int emo_repack_p4_dispatch(const float* in, float* out, int N, int C, int DHW, int to_p4, void* stream);
 
-extern "C" int emo_grid_sample3d_f32(const float* vol, const float* grid, const float* theta, const float* lin_x,
-                                     const float* lin_y, const float* lin_z, float* out, int N, int C, int D, int H,
-                                     int W, int Do, int Ho, int Wo, int64_t vol_batch_stride, int padding_mode,
-                                     int in_layout, int out_layout, int variant, int grid_kind, void* stream) {
+namespace {
+
+int sample3d(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y, const float* lin_z,
+             float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo, int64_t vol_batch_stride, int padding_mode,
+             int in_layout, int out_layout, int variant, int grid_kind, void* stream, Bank bank) {
   if (!vol || !out || (!grid && !theta)) return EMO_ERR_BAD_ARG;
   if (grid_kind != 0 && grid_kind != 1) return EMO_ERR_BAD_ARG;
   if ((theta || grid_kind == 1) && (!lin_x || !lin_y || !lin_z)) return EMO_ERR_BAD_ARG;
@@ -547,6 +631,7 @@ extern "C" int emo_grid_sample3d_f32(const float* vol, const float* grid, const 
   if (N > 65535) return EMO_ERR_UNSUPPORTED;
   if ((long)D * H * W >= (1L << 31) / 4 || (long)Do * Ho * Wo >= (1L << 31) / 4) return EMO_ERR_UNSUPPORTED;
   if (!emo_aligned16(vol) || !emo_aligned16(out)) return EMO_ERR_ALIGN;
+  if (bank.index && (in_layout == EMO_LAYOUT_P4 || (variant & EMO_GS3D_TILE_FLAG))) return EMO_ERR_UNSUPPORTED;
   if (in_layout == EMO_LAYOUT_P4)
     return emo_gs3d_tile_dispatch(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_batch_stride,
                                   padding_mode, in_layout, out_layout, variant & ~EMO_GS3D_TILE_FLAG, grid_kind, stream);
@@ -561,16 +646,39 @@ extern "C" int emo_grid_sample3d_f32(const float* vol, const float* grid, const 
   switch (padding_mode) {
     case EMO_PAD_ZEROS:
       return launch_pad<EMO_PAD_ZEROS>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo,
-                                       vol_batch_stride, in_layout, out_layout, variant, grid_kind, s);
+                                       vol_batch_stride, in_layout, out_layout, variant, grid_kind, s, bank);
     case EMO_PAD_BORDER:
       return launch_pad<EMO_PAD_BORDER>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo,
-                                        vol_batch_stride, in_layout, out_layout, variant, grid_kind, s);
+                                        vol_batch_stride, in_layout, out_layout, variant, grid_kind, s, bank);
     case EMO_PAD_REFLECTION:
       return launch_pad<EMO_PAD_REFLECTION>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo,
-                                            vol_batch_stride, in_layout, out_layout, variant, grid_kind, s);
+                                            vol_batch_stride, in_layout, out_layout, variant, grid_kind, s, bank);
     default:
       return EMO_ERR_BAD_ARG;
   }
+}
+
+}  // namespace
+
+extern "C" int emo_grid_sample3d_f32(const float* vol, const float* grid, const float* theta, const float* lin_x,
+                                     const float* lin_y, const float* lin_z, float* out, int N, int C, int D, int H,
+                                     int W, int Do, int Ho, int Wo, int64_t vol_batch_stride, int padding_mode,
+                                     int in_layout, int out_layout, int variant, int grid_kind, void* stream) {
+  return sample3d(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_batch_stride, padding_mode, in_layout,
+                  out_layout, variant, grid_kind, stream, Bank{nullptr, 0});
+}
+
+// Frame n samples volume vol_index[n] of a bank of num_vols volumes, C * D * H * W floats apart (several source identities in one
+// driver batch).  The channels-last kernels and the planar direct gather only; an index outside [0, num_vols) yields a zero frame.
+extern "C" int emo_grid_sample3d_indexed_f32(const float* vol_bank, const int32_t* vol_index, int num_vols, const float* grid,
+                                             const float* theta, const float* lin_x, const float* lin_y, const float* lin_z,
+                                             float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
+                                             int padding_mode, int in_layout, int out_layout, int variant, int grid_kind,
+                                             void* stream) {
+  if (!vol_index || num_vols <= 0) return EMO_ERR_BAD_ARG;
+  if (C <= 0 || D <= 0 || H <= 0 || W <= 0) return EMO_ERR_BAD_ARG;
+  return sample3d(vol_bank, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, (int64_t)C * D * H * W,
+                  padding_mode, in_layout, out_layout, variant, grid_kind, stream, Bank{vol_index, num_vols});
 }
 
 extern "C" int emo_affine_grid3d_f32(const float* theta, const float* lin_x, const float* lin_y, const float* lin_z,

@@ -9,6 +9,7 @@
 //                               (downsampling_layers['avgpool'(_3d)], utils.py:962-967; warp_generator_resnet.py:118,
 //                               unet_3d.py:84-86,192-193, local_encoder.py via ResBlock stride 2).
 //   emo_add_f32                 out = (a + b[i % period]) * alpha  (Unet3D skip sum unet_3d.py:281; embed mix va.py:857).
+//   emo_add_rows_indexed_f32    out[b] = (a[b] + table[index[b]]) * alpha  (the same mix, one identity per row).
 #include "common.h"
 
 namespace {
@@ -267,6 +268,24 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, c
     out[i] = (a[i] + b[i % period]) * alpha;
 }
 
+// out[b][i] = (a[b][i] + table[index[b]][i]) * alpha with add_kernel's roundings (separate add and multiply); grid (x, B).  The row
+// index is uniform across a block: one load, kept in a scalar register.  An index outside [0, num_rows) writes a zero row.
+__global__ __launch_bounds__(256) void add_rows_indexed_kernel(const float* __restrict__ a, const float* __restrict__ table,
+                                                               const int* __restrict__ index, float* __restrict__ out,
+                                                               long row, int num_rows, float alpha) {
+  const int b = blockIdx.y;
+  const int k = __builtin_amdgcn_readfirstlane(index[b]);
+  const float* ap = a + (long)b * row;
+  float* op = out + (long)b * row;
+  if ((unsigned)k >= (unsigned)num_rows) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < row; i += (long)gridDim.x * 256) op[i] = 0.0f;
+    return;
+  }
+  const float* tp = table + (long)k * row;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < row; i += (long)gridDim.x * 256)
+    op[i] = (ap[i] + tp[i]) * alpha;
+}
+
 // F.interpolate(x, size=(Ho, Wo), mode='bilinear' | 'bicubic', align_corners=False) on 4-D tensors (ATen
 // UpSampleBilinear2d / UpSampleBicubic2d: area_pixel_compute_source_index + cubic convolution, A = -0.75).
 // Wrapper glue of the reference: bicubic resize of source / driver crops to image_size (notebooks/infer.py:399-401,
@@ -444,6 +463,16 @@ extern "C" int emo_add_f32(const float* a, const float* b, float* out, int64_t n
   if (!a || !b || !out || n <= 0 || period <= 0) return EMO_ERR_BAD_ARG;
   hipLaunchKernelGGL(add_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long)n,
                      (long)period, alpha);
+  return emo_launch_status();
+}
+
+extern "C" int emo_add_rows_indexed_f32(const float* a, const float* table, const int32_t* index, float* out, int B, int num_rows,
+                                        int64_t row, float alpha, void* stream) {
+  if (!a || !table || !index || !out || B <= 0 || num_rows <= 0 || row <= 0) return EMO_ERR_BAD_ARG;
+  if (B > 65535) return EMO_ERR_UNSUPPORTED;
+  const unsigned gx = (unsigned)(row < 256L * 64 ? emo_cdiv(row, 256) : 64);
+  hipLaunchKernelGGL(add_rows_indexed_kernel, dim3(gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, table, index, out,
+                     (long)row, num_rows, alpha);
   return emo_launch_status();
 }
 

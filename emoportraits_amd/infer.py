@@ -19,7 +19,11 @@ and their source-side counterparts added here (`custome_source_pose_embed`, `cus
 
 Extension over the reference (which is batch-1, F5): driver inputs may carry a batch dimension, and
 `animate()` streams N driver frames in device-sized batches, sharded across ranks (emoportraits_amd/parallel.py).
+With `identity_capacity=K` the wrapper also keeps a bank of K source identities on the device (`store_identity`,
+`load_identity`, `drop_identity`, `identities`, `share_identity`), and `animate` / `animate_frames(identities=...)` render
+frames of several identities in one driver batch.
 """
+import operator
 import os
 import pathlib
 from argparse import Namespace
@@ -99,7 +103,7 @@ class InferenceWrapper:
                  fixed_bounding_box=False, project_dir='./', folder='mp_logs', model_='va',
                  torch_home='', debug=False, print_model=False, print_params=True, args_overwrite={}, state_dict=None,
                  pose_momentum=0.5, rank=0, args_path=None, embedders=None, head_pose_regressor_path=None,
-                 use_graphs=True, precision=None):
+                 use_graphs=True, precision=None, identity_capacity=0):
         if not use_gpu:
             raise RuntimeError("emoportraits_amd runs on MI355X only: use_gpu=False is not supported (no CPU path)")
         if model_ != 'va':
@@ -148,6 +152,12 @@ class InferenceWrapper:
             first = 0 if use_graphs == 'capture_first' else 1
             self._graphed['driver'] = graphs.Graphed(
                 lambda pose, theta: self.hot_path.driver_pass(self._canonical_cl, self.idt_embed, pose, theta), eager_calls=first)
+            if identity_capacity > 0:
+                # the bank pass reads the bank buffers (fixed addresses) and the per-frame slots (an input of the graph): new
+                # indices and newly stored identities take effect on replay
+                self._graphed['driver_bank'] = graphs.Graphed(
+                    lambda pose, theta, ident: self.hot_path.driver_pass(self._bank_cl, self._bank_idt, pose, theta, identity=ident),
+                    eager_calls=first)
             hp_net, ex_net = native.get('head_pose_regressor'), native.get('expression_embedder')
             if hp_net is not None and self.embedders['head_pose_regressor'] is hp_net:
                 self._graphed['head_pose_regressor'] = graphs.Graphed(lambda crop: hp_net.forward(crop, True), eager_calls=first)
@@ -169,6 +179,7 @@ class InferenceWrapper:
         self.target_latent_volume = None
         self._canonical_cl = None
         self._crop_tracker = None
+        self._init_identity_bank(int(identity_capacity))
 
     # ------------------------------------------------------------------------------------------------------
     def _native_embedders(self, found, head_pose_regressor_path):
@@ -203,6 +214,116 @@ class InferenceWrapper:
                 self._canonical_cl.copy_(cl)
             else:
                 self._canonical_cl = cl
+
+    # ---- identity bank --------------------------------------------------------------------------------------------
+    def _init_identity_bank(self, capacity):
+        """K slots preallocated on the device (captured graphs hold their addresses): channels-last canonical volumes
+        [K,d,s,s,c] (25.2 MB per slot at the released config), idt_embed [K,C,es,es], source theta [K,4,4]"""
+        if capacity < 0:
+            raise ValueError("identity_capacity must be >= 0")
+        self.identity_capacity = capacity
+        self._bank_used = [False] * capacity
+        if capacity == 0:
+            self._bank_cl = self._bank_idt = self._bank_theta = None
+            return
+        c, d, s = self.cfg["latent_volume_channels"], self.cfg["latent_volume_depth"], self.cfg["latent_volume_size"]
+        es = self.cfg["gen_embed_size"]
+        f32 = dict(device=self.device, dtype=torch.float32)
+        self._bank_cl = torch.zeros((capacity, d, s, s, c), **f32)
+        self._bank_idt = torch.zeros((capacity, self.cfg["gen_max_channels"], es, es), **f32)
+        self._bank_theta = torch.zeros((capacity, 4, 4), **f32)
+
+    def _slot(self, slot, occupied=True):
+        if self.identity_capacity == 0:
+            raise ValueError("this wrapper has no identity bank: construct it with identity_capacity=K")
+        try:
+            slot = operator.index(slot) if not isinstance(slot, bool) else None
+        except TypeError:
+            slot = None
+        if slot is None or not 0 <= slot < self.identity_capacity:
+            raise ValueError(f"slot {slot!r} is not in [0, {self.identity_capacity})")
+        if occupied and not self._bank_used[slot]:
+            raise ValueError(f"slot {slot} holds no identity")
+        return slot
+
+    def _bank_write(self, slot, canonical_cl, idt_embed, theta_src):
+        if idt_embed.numel() != self._bank_idt[slot].numel():
+            raise ValueError(f"idt_embed {tuple(idt_embed.shape)} does not fit a slot {tuple(self._bank_idt.shape[1:])}")
+        self._bank_cl[slot].copy_(canonical_cl.reshape(self._bank_cl.shape[1:]))
+        self._bank_idt[slot].copy_(idt_embed.reshape(self._bank_idt.shape[1:]))
+        self._bank_theta[slot].copy_(theta_src.reshape(4, 4))
+        self._bank_used[slot] = True
+
+    def store_identity(self, slot=None):
+        """Copy the current identity (what forward(source_image=...) or share_source() left behind) into `slot` (None: the
+        first free one); returns the slot"""
+        if self.identity_capacity == 0:
+            self._slot(0)                  # (raises: no bank)
+        if self._canonical_cl is None or getattr(self, 'idt_embed', None) is None:
+            raise RuntimeError("no current identity: call forward with a source_image (or share_source) first")
+        if getattr(self, 'pred_source_theta', None) is None:
+            raise RuntimeError("the current identity has no source theta")
+        if slot is None:
+            free = [k for k, used in enumerate(self._bank_used) if not used]
+            if not free:
+                raise ValueError(f"all {self.identity_capacity} identity slots are occupied: drop_identity one first")
+            slot = free[0]
+        slot = self._slot(slot, occupied=False)
+        self._bank_write(slot, self._canonical_cl, self.idt_embed, self.pred_source_theta)
+        return slot
+
+    def load_identity(self, slot):
+        """Make a stored identity current: forward(driver_image=...) then renders it.  Copied into the existing buffers as
+        _set_source_cache does; target_latent_volume (NCDHW) is one repack of the channels-last slot."""
+        slot = self._slot(slot)
+        cl = self._bank_cl[slot:slot + 1]
+        self.target_latent_volume = ops.volume_to_channels_first(cl)
+        if self.use_graphs and self._canonical_cl is not None and self._canonical_cl.shape == cl.shape:
+            self._canonical_cl.copy_(cl)
+        else:
+            self._canonical_cl = cl.clone()
+        self._set_source_cache(idt_embed=self._bank_idt[slot:slot + 1].clone())
+        self.pred_source_theta = self._bank_theta[slot:slot + 1].clone()
+
+    def drop_identity(self, slot):
+        self._bank_used[self._slot(slot)] = False
+
+    def identities(self):
+        """occupied slots, ascending"""
+        return [k for k, used in enumerate(self._bank_used) if used]
+
+    def share_identity(self, slot, src_rank=0):
+        """Broadcast slot `slot` of rank `src_rank` into the same slot on every rank (one flat buffer,
+        parallel.broadcast_source_cache)"""
+        slot = self._slot(slot, occupied=self.rank == src_rank)
+        src = self.rank == src_rank
+        cache = parallel.broadcast_source_cache(
+            dict(canonical_cl=self._bank_cl[slot:slot + 1] if src else None, idt_embed=self._bank_idt[slot:slot + 1] if src else None,
+                 theta_src=self._bank_theta[slot:slot + 1] if src else None),
+            shapes=dict(canonical_cl=(1,) + tuple(self._bank_cl.shape[1:]), idt_embed=(1,) + tuple(self._bank_idt.shape[1:]), theta_src=(1, 4, 4)),
+            names=['canonical_cl', 'idt_embed', 'theta_src'], src=src_rank, device=self.device, world=self.world, rank=self.rank,
+            exchange_shapes=False)
+        if not src:
+            self._bank_write(slot, cache["canonical_cl"], cache["idt_embed"], cache["theta_src"])
+
+    def _frame_identities(self, identities, n=None):
+        """per-frame slots -> int32 host tensor, every slot checked on the host (the device never sees an unknown slot)"""
+        if self.identity_capacity == 0:
+            raise ValueError("identities= needs an identity bank: construct the wrapper with identity_capacity=K")
+        ids = torch.as_tensor(identities).detach().cpu()
+        if ids.dim() != 1 or ids.dtype.is_floating_point or ids.dtype == torch.bool:
+            raise ValueError("identities must be a 1-D integer sequence of slots, one per frame")
+        if n is not None and ids.shape[0] != n:
+            raise ValueError(f"identities has {ids.shape[0]} entries for {n} frames")
+        for k in sorted(set(ids.tolist())):
+            self._slot(int(k))
+        return ids.to(torch.int32)
+
+    def _drive_bank(self, pose, theta, ident):
+        g = self._graphed.get('driver_bank')
+        if g is not None:
+            return g(pose, theta, ident)
+        return self.hot_path.driver_pass(self._bank_cl, self._bank_idt, pose, theta, identity=ident)
 
     def _head_pose(self, crop):
         g = self._graphed.get('head_pose_regressor')
@@ -462,24 +583,28 @@ class InferenceWrapper:
     __call__ = forward
 
     # ------------------------------------------------------------------------------------------------------
-    def animate(self, target_pose_embeds, target_srt, batch_size=16, as_uint8=True):
+    def animate(self, target_pose_embeds, target_srt, batch_size=16, as_uint8=True, identities=None):
         """1 source -> N driver frames (the BASELINE metric).  Frames are sharded contiguously across ranks
         (SURVEY.md section 8e); each rank walks its shard in batches of `batch_size`.  Yields (first_frame_index, frames)
-        with frames a uint8 [B,H,W,3] (or fp32 [B,3,H,W]) DEVICE tensor -- no host sync inside the loop."""
-        if self._canonical_cl is None:
-            raise RuntimeError("call forward with a source_image first")
+        with frames a uint8 [B,H,W,3] (or fp32 [B,3,H,W]) DEVICE tensor -- no host sync inside the loop.
+        identities: slot of the identity bank per frame ([N], over the whole frame stream; each rank takes its slice) -- the
+        frames of a batch may then belong to different identities."""
         N = target_pose_embeds.shape[0]
+        ids = None if identities is None else self._frame_identities(identities, N)
+        if ids is None and self._canonical_cl is None:
+            raise RuntimeError("call forward with a source_image first")
         lo, hi = parallel.shard_range(N, self.rank, self.world)
+        ids_dev = None if ids is None else ids[lo:hi].to(self.device)
         for b0 in range(lo, hi, batch_size):
             b1 = min(b0 + batch_size, hi)
             pose = target_pose_embeds[b0:b1].to(self.device).float().contiguous()
             srt = [t[b0:b1].to(self.device).float().contiguous() for t in target_srt]
             theta = ops.pose_theta(*srt)
-            img = self._drive(pose, theta)
+            img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ids_dev[b0 - lo:b1 - lo])
             yield b0, (ops.pack_rgb8(img) if as_uint8 else img)
 
     # ------------------------------------------------------------------------------------------------------
-    def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False):
+    def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  frames: uint8 [N,H,W,3] tensor (host, ideally pinned, or device) or an iterable of such chunks --
         decoded video frames, uploaded as BYTES.  Per batch, all on the device and without a host synchronisation:
@@ -498,8 +623,15 @@ class InferenceWrapper:
         event has completed, i.e. the host only ever waits for a batch that is `ring - 1` batches behind the GPU.
         Yields (first_frame_index, uint8 [b,S,S,3]) -- a view of a pinned ring slot, valid ONLY until the generator is resumed
         (the next batch's copy may be queued into the same slot right away: consume or copy it before calling next()) --
-        or, with to_host=False, the device tensor.  Frames are sharded contiguously across ranks as in animate()."""
-        if self._canonical_cl is None:
+        or, with to_host=False, the device tensor.  Frames are sharded contiguously across ranks as in animate().
+        identities: slot of the identity bank per frame, over the whole frame stream (as in animate()); not with smooth_pose,
+        whose EMA is one state per stream."""
+        ids = None
+        if identities is not None:
+            if smooth_pose:
+                raise ValueError("smooth_pose=True smooths one pose stream: it does not combine with identities=")
+            ids = self._frame_identities(identities, frames.shape[0] if isinstance(frames, torch.Tensor) else None)
+        elif self._canonical_cl is None:
             raise RuntimeError("call forward with a source_image first")
         S = self.cfg["image_size"]
         chunks = [frames] if isinstance(frames, torch.Tensor) else frames
@@ -555,7 +687,10 @@ class InferenceWrapper:
             if chunk.dtype != torch.uint8 or chunk.dim() != 4 or chunk.shape[-1] != 3:
                 raise ValueError("frames must be uint8 [N,H,W,3]")
             n = chunk.shape[0]
+            if ids is not None and base + n > ids.shape[0]:
+                raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
             lo, hi = parallel.shard_range(n, self.rank, self.world)
+            ids_dev = None if ids is None else ids[base + lo:base + hi].to(self.device)
             spans = [(b0, min(b0 + batch_size, hi)) for b0 in range(lo, hi, batch_size)]
             smoothed, kept = None, {}
             if smooth_pose:
@@ -581,7 +716,9 @@ class InferenceWrapper:
                 theta = smoothed[b0 - lo:b1 - lo] if smoothed is not None else self._head_pose(crops)[0]
                 self.pred_target_theta = theta                                   # (as forward() leaves it: infer.py:584)
                 pose, _ = self._expression(crops, theta, 'a driver call')
-                out = ops.pack_rgb8(self._drive(pose, theta.float().contiguous()))
+                theta = theta.float().contiguous()
+                img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ids_dev[b0 - lo:b1 - lo])
+                out = ops.pack_rgb8(img)
                 if not to_host:
                     yield base + b0, out
                     continue

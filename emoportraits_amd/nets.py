@@ -112,12 +112,16 @@ class WarpEmbed:
                     sd["warp_embed_head_orig_nw.weight_v"].float())
         self.w_head = _dev(w.reshape(w.shape[0], w.shape[1]), device)                   # [C, C]
 
-    def __call__(self, pose_embed, idt_embed):
-        """pose_embed [B,E], idt_embed [1,C,es,es] -> warp embed [B, C, es*es]"""
+    def __call__(self, pose_embed, idt_embed, identity=None):
+        """pose_embed [B,E], idt_embed [1,C,es,es] -> warp embed [B, C, es*es].  With identity (int32 [B] on the device),
+        idt_embed is a bank [K,C,es,es] and row b adds idt_embed[identity[b]]"""
         B = pose_embed.shape[0]
         nn = self.es * self.es
         e = ops.small_gemm(self.w_lin, pose_embed.reshape(B, -1, 1), 1)                  # [B, C*nn, 1]
-        x = ops.add(e, idt_embed.reshape(-1), 0.5)                                       # (e + idt) * 0.5
+        if identity is not None:
+            x = ops.add_rows_indexed(e, idt_embed.reshape(idt_embed.shape[0], -1, 1), identity, 0.5)
+        else:
+            x = ops.add(e, idt_embed.reshape(-1), 0.5)                                   # (e + idt) * 0.5
         return ops.small_gemm(self.w_head, x.view(B, -1, nn), nn)                        # [B, C, nn]
 
 
@@ -381,10 +385,13 @@ class HotPath:
         return ops.volume_to_channels_last(canonical)
 
     # ---- per driver batch ---------------------------------------------------------------------------
-    def driver_pass(self, canonical_cl, idt_embed, target_pose_embed, theta_drv, keep=False):
+    def driver_pass(self, canonical_cl, idt_embed, target_pose_embed, theta_drv, keep=False, identity=None):
+        """identity=None: one identity, canonical_cl [1,d,s,s,c] and idt_embed [1,C,es,es].  identity (int32 [B] on the device):
+        frame b renders identity[b] of a bank, canonical_cl [K,d,s,s,c] and idt_embed [K,C,es,es] -- the warp embedding adds that
+        row's idt_embed and the uv sampler reads that row's volume; every other launch is the same as without a bank."""
         B = target_pose_embed.shape[0]
         self._clear_flags()
-        emb = self.embed(target_pose_embed, idt_embed)
+        emb = self.embed(target_pose_embed, idt_embed, identity)
         delta_uv = self.uv_generator(emb)
         lay = "ndhwc"
         aligned = torch.empty((B, self.c, self.d, self.s, self.s), device=self.device, dtype=torch.float32)
@@ -393,7 +400,7 @@ class HotPath:
         for a in range(0, B, step):
             b = min(B, a + step)
             warped = ops.grid_sample3d(canonical_cl, delta=delta_uv[a:b], padding_mode=self.pad, in_layout=lay, out_layout=lay,
-                                       variant=self.sampler_uv_variant)
+                                       variant=self.sampler_uv_variant, vol_index=None if identity is None else identity[a:b])
             ops.grid_sample3d(warped, theta=theta3[a:b], padding_mode=self.pad, in_layout=lay, out_layout="ncdhw",
                               out=aligned[a:b], variant=self.sampler_rot_variant)
         feat = aligned.view(B, self.c * self.d, self.s, self.s)

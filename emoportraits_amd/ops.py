@@ -21,7 +21,7 @@ def _lattice(n, device_index):
 
 
 def grid_sample3d(vol, grid=None, theta=None, padding_mode="zeros", in_layout="ncdhw", out_layout="ncdhw",
-                  variant=0, out=None, delta=None):
+                  variant=0, out=None, delta=None, vol_index=None):
     """5-D trilinear grid_sample, align_corners=False  (== F.grid_sample(vol, grid, padding_mode=...)).
 
     vol    [Nv,C,D,H,W] ('ncdhw'), [Nv,C/4,D,H,W,4] ('p4': packed channel quads, the layout of the LDS-staged tile kernels,
@@ -33,6 +33,9 @@ def grid_sample3d(vol, grid=None, theta=None, padding_mode="zeros", in_layout="n
            the identity lattice (notebooks/infer.py:583-588), generated inside the kernel, output size = D,H,W.
     delta  [N,3,Do,Ho,Wo] planar deltas: grid = identity lattice + delta (WarpGenerator output,
            warp_generator_resnet.py:178) without materialising the grid.
+    vol_index  int32 [N] on the volume's device: sample n reads volume vol_index[n] of the bank `vol` (any Nv >= 1; layouts
+           'ndhwc' -> 'ndhwc' / 'ncdhw' and 'ncdhw' -> 'ncdhw' with the direct gather).  An index outside [0, Nv) gives a zero
+           sample: the device reads the index, so the host cannot check it at launch.
     """
     lib = hip.load()
     hip.require_cuda_f32(vol, grid, delta)
@@ -75,6 +78,9 @@ def grid_sample3d(vol, grid=None, theta=None, padding_mode="zeros", in_layout="n
         if grid is None or grid.dim() != 5 or grid.shape[-1] != 3:
             raise ValueError("grid must be [N,Do,Ho,Wo,3]")
         N, Do, Ho, Wo, _ = grid.shape
+    if vol_index is not None:
+        return _grid_sample3d_indexed(lib, vol, vol_index, grid, theta, lx, ly, lz, N, C, D, H, W, Do, Ho, Wo, padding_mode,
+                                      in_layout, out_layout, variant, grid_kind, out, layouts)
     if Nv not in (1, N):
         raise ValueError(f"volume batch {Nv} does not match grid batch {N}")
     stride = 0 if (Nv == 1 and N > 1) else C * D * H * W
@@ -99,6 +105,38 @@ def grid_sample3d(vol, grid=None, theta=None, padding_mode="zeros", in_layout="n
                                    hip.ptr(out), N, C, D, H, W, Do, Ho, Wo, stride, hip.PAD_MODES[padding_mode],
                                    layouts[in_layout], layouts[out_layout], int(variant), grid_kind, hip.current_stream())
     hip.check(rc, "emo_grid_sample3d_f32")
+    return out
+
+
+def _check_index(index, n, device, what):
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32:
+        raise ValueError(f"{what} must be an int32 tensor")
+    if index.device != device:
+        raise ValueError(f"{what} is on {index.device}, the data on {device}")
+    if index.dim() != 1 or index.shape[0] != n or not index.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous [{n}] tensor, got {tuple(index.shape)}")
+
+
+def _grid_sample3d_indexed(lib, vol, vol_index, grid, theta, lx, ly, lz, N, C, D, H, W, Do, Ho, Wo, padding_mode, in_layout,
+                           out_layout, variant, grid_kind, out, layouts):
+    """grid_sample3d(vol_index=...): emo_grid_sample3d_indexed_f32 over the bank `vol` [K, ...]"""
+    _check_index(vol_index, N, vol.device, "vol_index")
+    if in_layout == "p4" or (in_layout == "ncdhw" and out_layout != "ncdhw") or (in_layout == "ndhwc" and out_layout == "p4"):
+        raise ValueError("vol_index: the layouts are 'ndhwc' -> 'ndhwc' / 'ncdhw' and 'ncdhw' -> 'ncdhw'")
+    if in_layout == "ncdhw" and int(variant) & TILE:
+        raise ValueError("vol_index: the LDS-staged planar kernel (TILE) takes no bank")
+    shape = {"ndhwc": (N, Do, Ho, Wo, C), "ncdhw": (N, C, Do, Ho, Wo)}[out_layout]
+    if out is None:
+        out = torch.empty(shape, device=vol.device, dtype=torch.float32)
+    else:
+        hip.require_cuda_f32(out)
+        if tuple(out.shape) != shape:
+            raise ValueError("bad out shape")
+    rc = lib.emo_grid_sample3d_indexed_f32(hip.ptr(vol), hip.ptr(vol_index), vol.shape[0], hip.ptr(grid), hip.ptr(theta),
+                                           hip.ptr(lx), hip.ptr(ly), hip.ptr(lz), hip.ptr(out), N, C, D, H, W, Do, Ho, Wo,
+                                           hip.PAD_MODES[padding_mode], layouts[in_layout], layouts[out_layout], int(variant),
+                                           grid_kind, hip.current_stream())
+    hip.check(rc, "emo_grid_sample3d_indexed_f32")
     return out
 
 
@@ -488,6 +526,22 @@ def add(a, b, alpha=1.0, out=None):
         out = torch.empty_like(a)
     hip.check(lib.emo_add_f32(hip.ptr(a), hip.ptr(b), hip.ptr(out), a.numel(), b.numel(), float(alpha), hip.current_stream()),
               "emo_add_f32")
+    return out
+
+
+def add_rows_indexed(a, table, index, alpha=1.0, out=None):
+    """(a[b] + table[index[b]]) * alpha per row b: a [B, ...], table [K, ...] with the same row shape, index int32 [B] on the
+    same device.  An index outside [0, K) gives a zero row.  Equal indices give bit for bit add(a, table[k], alpha)."""
+    lib = hip.load()
+    hip.require_cuda_f32(a, table)
+    B, K = a.shape[0], table.shape[0]
+    if a.dim() < 1 or table.dim() < 1 or a[0].numel() != table[0].numel() or a.numel() == 0 or K == 0:
+        raise ValueError(f"rows of a {tuple(a.shape)} and table {tuple(table.shape)} differ")
+    _check_index(index, B, a.device, "index")
+    if out is None:
+        out = torch.empty_like(a)
+    hip.check(lib.emo_add_rows_indexed_f32(hip.ptr(a), hip.ptr(table), hip.ptr(index), hip.ptr(out), B, K, a[0].numel(),
+                                           float(alpha), hip.current_stream()), "emo_add_rows_indexed_f32")
     return out
 
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 11
+#define EMO_ABI_VERSION 12
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -102,6 +102,21 @@ int emo_grid_sample3d_f32(const float* vol, const float* grid, const float* thet
                           int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
                           int64_t vol_batch_stride, int padding_mode,
                           int in_layout, int out_layout, int variant, int grid_kind, void* stream);
+
+/* ABI 12.  emo_grid_sample3d_f32 over a BANK of volumes (several source identities in one driver batch): frame n samples volume
+ * vol_index[n] of `vol_bank`, num_vols volumes of C*D*H*W floats each, back to back in in_layout:
+ *   vol_bank   [num_vols, C, D, H, W] (NCDHW) or [num_vols, D, H, W, C] (NDHWC)
+ *   vol_index  [N] int32, DEVICE memory (read by the kernels: a graph replay sees its current contents)
+ * Everything else means what it means in emo_grid_sample3d_f32.  Served: NDHWC -> NDHWC and NDHWC -> NCDHW (every variant bit of
+ * those kernels, the 4x4x4 bricks and fma accumulation included) and the planar direct gather NCDHW -> NCDHW.  in_layout
+ * EMO_LAYOUT_P4 or the tile flag (bit 30): EMO_ERR_UNSUPPORTED.  vol_index NULL or num_vols <= 0: EMO_ERR_BAD_ARG.  An index
+ * outside [0, num_vols) makes that frame all zeros; the bank is not read for it. */
+int emo_grid_sample3d_indexed_f32(const float* vol_bank, const int32_t* vol_index, int num_vols,
+                                  const float* grid, const float* theta,
+                                  const float* lin_x, const float* lin_y, const float* lin_z,
+                                  float* out,
+                                  int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
+                                  int padding_mode, int in_layout, int out_layout, int variant, int grid_kind, void* stream);
 
 /* a2 alone -- the rotation warp as a tensor: grid[n,z,y,x,:] = theta[n,:3,:4] . (lin_x[x], lin_y[y], lin_z[z], 1), the same
  * fma chain the theta variant of emo_grid_sample3d_f32 evaluates in-kernel.  Replaces
@@ -341,6 +356,11 @@ int emo_upsample_trilinear_gn_sums_f32(const float* x, float* out, int N, int C,
                                        void* stream);
 int emo_avgpool_f32(const float* x, float* out, int64_t NC, int D, int H, int W, int kd, int kh, int kw, void* stream);
 int emo_add_f32(const float* a, const float* b, float* out, int64_t n, int64_t period, float alpha, void* stream);
+/* ABI 12.  emo_add_f32 with one table row per batch row: out[b][i] = (a[b][i] + table[index[b]][i]) * alpha, the same roundings
+ * (add, then multiply), so rows whose indices are all equal are bit for bit the `period` form with b = that table row.
+ *   a, out [B, row]; table [num_rows, row]; index [B] int32, DEVICE memory.  An index outside [0, num_rows) writes a zero row. */
+int emo_add_rows_indexed_f32(const float* a, const float* table, const int32_t* index, float* out, int B, int num_rows,
+                             int64_t row, float alpha, void* stream);
 
 /* f4 -- F.interpolate(x, size=(Ho, Wo), mode='bilinear' (bicubic = 0) | 'bicubic' (1), align_corners=False) on NC
  * planes of H x W: the wrappers' crop resize (notebooks/infer.py:346,399-401,548-552; notebooks/infer_s2.py:360-362).
