@@ -171,6 +171,178 @@ __global__ __launch_bounds__(64) void mat4_inverse_kernel(const float* __restric
     for (int j = 0; j < 4; ++j) out[b * 16 + i * 4 + j] = (float)m[i][4 + j];
 }
 
+// notebooks/infer.py:686-736 get_mixing_theta for ONE source and ONE target per frame (hostglue.mixing_theta with a single
+// source: its roll along the source axis is then a no-op), one thread per frame, fp64 from the fp32 inputs.
+// The polar decomposition L = U P of a 3x3 linear part comes from a one-sided Jacobi SVD run to convergence: columns of
+// A = L V are made orthogonal by plane rotations (V accumulates them), then sigma_j = |a_j|, U = [a_j / sigma_j] V^T and
+// P = V diag(sigma) V^T -- scipy.linalg.polar's own formula, for det L < 0 as well (U is then a reflection).
+__device__ inline bool finite_f64(double x) { return (x - x) == 0.0; }   // false for +-inf and nan (no fast-math in either build)
+
+__device__ inline void polar3(const double L[3][3], double U[3][3], double P[3][3]) {
+  double a[3][3], v[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      a[i][j] = L[i][j];
+      v[i][j] = i == j ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < 40; ++sweep) {
+    bool rotated = false;
+    for (int pq = 0; pq < 3; ++pq) {
+      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+      double alpha = 0.0, beta = 0.0, gamma = 0.0;
+      for (int i = 0; i < 3; ++i) {
+        alpha += a[i][p] * a[i][p];
+        beta += a[i][q] * a[i][q];
+        gamma += a[i][p] * a[i][q];
+      }
+      if (!(fabs(gamma) > 4e-16 * sqrt(alpha * beta))) continue;
+      rotated = true;
+      const double zeta = (beta - alpha) / (2.0 * gamma);
+      const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+      for (int i = 0; i < 3; ++i) {
+        const double ap = a[i][p], aq = a[i][q];
+        a[i][p] = c * ap - s * aq;
+        a[i][q] = s * ap + c * aq;
+        const double vp = v[i][p], vq = v[i][q];
+        v[i][p] = c * vp - s * vq;
+        v[i][q] = s * vp + c * vq;
+      }
+    }
+    if (!rotated) break;
+  }
+  double sigma[3];
+  for (int j = 0; j < 3; ++j) {
+    sigma[j] = sqrt(a[0][j] * a[0][j] + a[1][j] * a[1][j] + a[2][j] * a[2][j]);
+    if (sigma[j] > 0.0)
+      for (int i = 0; i < 3; ++i) a[i][j] /= sigma[j];
+  }
+  // a rank-deficient L (outside the conditioning this serves): complete a zero column from the other two
+  for (int j = 0; j < 3; ++j)
+    if (!(sigma[j] > 0.0)) {
+      const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      a[0][j] = a[1][j1] * a[2][j2] - a[2][j1] * a[1][j2];
+      a[1][j] = a[2][j1] * a[0][j2] - a[0][j1] * a[2][j2];
+      a[2][j] = a[0][j1] * a[1][j2] - a[1][j1] * a[0][j2];
+    }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double u = 0.0, p = 0.0;
+      for (int k = 0; k < 3; ++k) {
+        u += a[i][k] * v[j][k];
+        p += v[i][k] * sigma[k] * v[j][k];
+      }
+      U[i][j] = u;
+      P[i][j] = p;
+    }
+}
+
+__global__ __launch_bounds__(64) void mixing_theta_kernel(const float* __restrict__ target, const float* __restrict__ source,
+                                                          const int* __restrict__ index, int B, int K, int mix_old,
+                                                          float* __restrict__ out) {
+  const int n = blockIdx.x * 64 + threadIdx.x;
+  if (n >= B) return;
+  const float* tg = target + (long)n * 16;
+  float* o = out + (long)n * 16;
+  double res[3][4];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) res[i][j] = (double)tg[i * 4 + j];     // the driver pose: every fallback but one
+  const int k = index ? index[n] : 0;
+  bool src_ok = k >= 0 && k < K;                    // (an unknown slot reads no source memory)
+  double Ls[3][3], Lt[3][3];
+  if (src_ok) {
+    const float* sr = source + (long)k * 16;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        Ls[i][j] = (double)sr[i * 4 + j];
+        src_ok = src_ok && finite_f64(Ls[i][j]);
+      }
+  }
+  if (src_ok) {                                     // else: the source decomposition "failed" (:718-719), the driver pose
+    bool tgt_ok = true;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        Lt[i][j] = res[i][j];
+        tgt_ok = tgt_ok && finite_f64(Lt[i][j]);
+      }
+    double Us[3][3], Ps[3][3];
+    polar3(Ls, Us, Ps);
+    if (!tgt_ok) {                                  // :724-725: the source stretch, no translation
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) res[i][j] = Ps[i][j];
+        res[i][3] = 0.0;
+      }
+    } else {
+      double Ut[3][3], Pt[3][3];
+      polar3(Lt, Ut, Pt);
+      const double t[3] = {res[0][3], res[1][3], res[2][3]};
+      if (mix_old) {                                // :727-728 translation @ tgt_rot @ src_stretch = [U_t P_s | t_t]
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) {
+            double acc = 0.0;
+            for (int q = 0; q < 3; ++q) acc += Ut[i][q] * Ps[q][j];
+            res[i][j] = acc;
+          }
+      } else {                                      // :729-730 src_stretch * mean(tgt_stretch) / mean(src_stretch) @ tgt_rot @ T
+        double ms = 1.0, mt = 1.0;                  // (means of the 4x4 homogeneous stretches: the 1 at (3,3) counts)
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) {
+            ms += Ps[i][j];
+            mt += Pt[i][j];
+          }
+        ms /= 16.0;
+        mt /= 16.0;
+        double X[3][3], A[3][3];
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) X[i][j] = Ps[i][j] * mt / ms;
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) {
+            double acc = 0.0;
+            for (int q = 0; q < 3; ++q) acc += X[i][q] * Ut[q][j];
+            A[i][j] = acc;
+          }
+        for (int i = 0; i < 3; ++i) {
+          for (int j = 0; j < 3; ++j) res[i][j] = A[i][j];
+          res[i][3] = A[i][0] * t[0] + A[i][1] * t[1] + A[i][2] * t[2];
+        }
+      }
+    }
+  }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) o[i * 4 + j] = (float)res[i][j];
+  o[12] = 0.0f; o[13] = 0.0f; o[14] = 0.0f; o[15] = 1.0f;
+}
+
+// notebooks/infer.py:571-581 smooth_pose, one EMA stream per source identity: frame i belongs to stream stream_of[i] (NULL:
+// all to stream 0) and is smoothed within that stream's frames in frame order, fp32 exactly as hostglue.ema_scan (two
+// rounded products, one rounded sum).  One thread per stream walks all 16 elements, so the stream's flag is read and
+// written by one thread only.
+__global__ __launch_bounds__(64) void theta_ema_scan_kernel(const float* __restrict__ values, const int* __restrict__ stream_of,
+                                                            float* __restrict__ state, int* __restrict__ has_state, int n, int K,
+                                                            float m, float om, float* __restrict__ out) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= K) return;
+  bool has = has_state[k] != 0;
+  float cur[16];
+  for (int e = 0; e < 16; ++e) cur[e] = has ? state[(long)k * 16 + e] : 0.0f;
+  for (int i = 0; i < n; ++i) {
+    if ((stream_of ? stream_of[i] : 0) != k) continue;
+    const float* v = values + (long)i * 16;
+    float* o = out + (long)i * 16;
+    for (int e = 0; e < 16; ++e) {
+      if (!has) cur[e] = v[e];
+      const float a = v[e] * m, b = cur[e] * om;
+      cur[e] = a + b;
+      o[e] = cur[e];
+    }
+    has = true;
+  }
+  if (has) {
+    for (int e = 0; e < 16; ++e) state[(long)k * 16 + e] = cur[e];
+    has_state[k] = 1;
+  }
+}
+
 }  // namespace
 
 extern "C" int emo_small_gemm_f32(const float* A, const float* B, float* C, int M, int K, int NN, int batch,
@@ -231,5 +403,21 @@ extern "C" int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int 
 extern "C" int emo_mat4_inverse_f32(const float* in, float* out, int B, void* stream) {
   if (!in || !out || B <= 0) return EMO_ERR_BAD_ARG;
   hipLaunchKernelGGL(mat4_inverse_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, in, out, B);
+  return emo_launch_status();
+}
+
+extern "C" int emo_mixing_theta_f32(const float* target, const float* source, const int32_t* index, int B, int K, int mix_old,
+                                    float* out, void* stream) {
+  if (!target || !source || !out || B <= 0 || K <= 0) return EMO_ERR_BAD_ARG;
+  hipLaunchKernelGGL(mixing_theta_kernel, dim3(emo_cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, target, source, index, B, K,
+                     mix_old ? 1 : 0, out);
+  return emo_launch_status();
+}
+
+extern "C" int emo_theta_ema_scan_f32(const float* values, const int32_t* stream_of, float* state, int32_t* has_state, int n, int K,
+                                      float m, float om, float* out, void* stream) {
+  if (!values || !state || !has_state || !out || n <= 0 || K <= 0) return EMO_ERR_BAD_ARG;
+  hipLaunchKernelGGL(theta_ema_scan_kernel, dim3(emo_cdiv(K, 64)), dim3(64), 0, (hipStream_t)stream, values, stream_of, state,
+                     has_state, n, K, m, om, out);
   return emo_launch_status();
 }

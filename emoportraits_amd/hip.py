@@ -60,6 +60,8 @@ SIGNATURES = {
     "emo_affine_add_relu_f32": [_c_void] * 7 + [_c_i64, _c_i64, _c_int, _c_void],
     "emo_grid_sample2d_f32": [_c_void] * 6 + [_c_int] * 6 + [_c_void],
     "emo_mat4_inverse_f32": [_c_void, _c_void, _c_int, _c_void],
+    "emo_mixing_theta_f32": [_c_void, _c_void, _c_void, _c_int, _c_int, _c_int, _c_void, _c_void],
+    "emo_theta_ema_scan_f32": [_c_void] * 4 + [_c_int, _c_int, _c_float, _c_float, _c_void, _c_void],
     "emo_mul_mask_f32": [_c_void, _c_void, _c_void, _c_int, _c_int, _c_i64, _c_void],
     "emo_stage2_compose_f32": [_c_void] * 5 + [_c_int, _c_int, _c_i64, _c_void],
     "emo_small_gemm_f32": [_c_void] * 3 + [_c_int] * 4 + [_c_i64, _c_i64, _c_void],

@@ -21,7 +21,10 @@ Extension over the reference (which is batch-1, F5): driver inputs may carry a b
 `animate()` streams N driver frames in device-sized batches, sharded across ranks (emoportraits_amd/parallel.py).
 With `identity_capacity=K` the wrapper also keeps a bank of K source identities on the device (`store_identity`,
 `load_identity`, `drop_identity`, `identities`, `share_identity`), and `animate` / `animate_frames(identities=...)` render
-frames of several identities in one driver batch.
+frames of several identities in one driver batch.  Both batched entry points take forward()'s pose controls -- `mix` / `mix_old`
+(get_mixing_theta), `target_theta` and `smooth_pose` -- on the device (ops.mixing_theta, ops.theta_ema_scan, a gather of the
+source thetas): with a bank, every frame is mixed against its own identity's source theta, and with smooth_per_identity=True
+smoothed within its own identity's frame sequence (one EMA stream per slot, reset by store / drop / reset_pose_state).
 """
 import operator
 import os
@@ -225,6 +228,7 @@ class InferenceWrapper:
         self._bank_used = [False] * capacity
         if capacity == 0:
             self._bank_cl = self._bank_idt = self._bank_theta = None
+            self._bank_pose, self._bank_pose_has = None, None
             return
         c, d, s = self.cfg["latent_volume_channels"], self.cfg["latent_volume_depth"], self.cfg["latent_volume_size"]
         es = self.cfg["gen_embed_size"]
@@ -232,6 +236,9 @@ class InferenceWrapper:
         self._bank_cl = torch.zeros((capacity, d, s, s, c), **f32)
         self._bank_idt = torch.zeros((capacity, self.cfg["gen_max_channels"], es, es), **f32)
         self._bank_theta = torch.zeros((capacity, 4, 4), **f32)
+        # smooth_pose state of each slot's own frame stream (ops.theta_ema_scan): EMA value, and whether the stream has begun
+        self._bank_pose = torch.zeros((capacity, 4, 4), **f32)
+        self._bank_pose_has = torch.zeros((capacity,), device=self.device, dtype=torch.int32)
 
     def _slot(self, slot, occupied=True):
         if self.identity_capacity == 0:
@@ -253,6 +260,7 @@ class InferenceWrapper:
         self._bank_idt[slot].copy_(idt_embed.reshape(self._bank_idt.shape[1:]))
         self._bank_theta[slot].copy_(theta_src.reshape(4, 4))
         self._bank_used[slot] = True
+        self._bank_pose_has[slot] = 0             # a new identity starts a new smooth_pose stream
 
     def store_identity(self, slot=None):
         """Copy the current identity (what forward(source_image=...) or share_source() left behind) into `slot` (None: the
@@ -286,7 +294,20 @@ class InferenceWrapper:
         self.pred_source_theta = self._bank_theta[slot:slot + 1].clone()
 
     def drop_identity(self, slot):
-        self._bank_used[self._slot(slot)] = False
+        slot = self._slot(slot)
+        self._bank_used[slot] = False
+        self._bank_pose_has[slot] = 0
+
+    def reset_pose_state(self, slots=None):
+        """Restart smooth_pose: slots=None clears the single-identity state (`self.theta`) and every slot's stream; otherwise
+        only the streams of the given bank slots"""
+        if slots is None:
+            self.theta = None
+            if self.identity_capacity > 0:
+                self._bank_pose_has.zero_()
+            return
+        for k in ([slots] if not isinstance(slots, (list, tuple, range, torch.Tensor)) else slots):
+            self._bank_pose_has[self._slot(int(k), occupied=False)] = 0
 
     def identities(self):
         """occupied slots, ascending"""
@@ -450,6 +471,49 @@ class InferenceWrapper:
         self.theta = torch.from_numpy(state).to(self.device)
         return torch.from_numpy(sm).to(self.device)
 
+    @staticmethod
+    def _check_smoothing(identities, smooth_pose, smooth_per_identity):
+        """smooth_pose over a bank is one EMA stream PER SLOT, which is not the one stream of the driver video the single-identity
+        path smooths (frames of one driver clip spread over several identities would each skip the others' frames): the caller
+        asks for it explicitly"""
+        if identities is not None and smooth_pose and not smooth_per_identity:
+            raise ValueError("smooth_pose=True smooths one pose stream: with identities= pass smooth_per_identity=True to smooth "
+                             "each identity's frames as a stream of its own")
+
+    def _source_theta(self, what):
+        theta = getattr(self, 'pred_source_theta', None)
+        if theta is None:
+            raise RuntimeError(f"{what} needs the current identity's source theta: call forward with a source_image (or "
+                               f"share_source) first")
+        return theta.reshape(1, 4, 4).float().contiguous()
+
+    def _pose_controls(self, theta, ids_dev, mix, mix_old, smooth):
+        """forward()'s order (infer.py:568-581) on a batch of driver thetas IN FRAME ORDER: mix against each frame's identity
+        (bank slot ids_dev[i], or the current identity), then smooth_pose -- with a bank one stream per slot on the device, else
+        the single stream in `self.theta` (the host scan, as before)"""
+        theta = theta.float().contiguous()
+        if theta.shape[0] == 0:
+            return theta
+        if mix:
+            if ids_dev is None:
+                theta = ops.mixing_theta(theta, self._source_theta('mix=True'), None, mix_old)
+            else:
+                theta = ops.mixing_theta(theta, self._bank_theta, ids_dev, mix_old)
+        if smooth:
+            if ids_dev is None:
+                theta = self._smooth_thetas(theta)
+            else:
+                theta = ops.theta_ema_scan(theta, ids_dev, self._bank_pose, self._bank_pose_has, self.pose_momentum)
+        return theta
+
+    def _render_theta(self, theta, ids_dev, target_theta):
+        """target_theta=False: the frame is rendered in its identity's own head pose (infer.py:584), a device-side gather"""
+        if target_theta:
+            return theta.float().contiguous()
+        if ids_dev is None:
+            return self._source_theta('target_theta=False').expand(theta.shape[0], 4, 4).contiguous()
+        return self._bank_theta.index_select(0, ids_dev).contiguous()
+
     def to_image(self, img_u8_hwc):
         from PIL import Image
         return Image.fromarray(img_u8_hwc)
@@ -468,6 +532,7 @@ class InferenceWrapper:
             if reset_tracking:
                 self.center = self.size = self.theta = self.delta_yaw = self.delta_pitch = None
                 self._crop_tracker = None
+                self.reset_pose_state()
             self.mix, self.mix_old = mix, mix_old
             if delta_yaw is not None:
                 self.delta_yaw = delta_yaw
@@ -583,28 +648,58 @@ class InferenceWrapper:
     __call__ = forward
 
     # ------------------------------------------------------------------------------------------------------
-    def animate(self, target_pose_embeds, target_srt, batch_size=16, as_uint8=True, identities=None):
+    def animate(self, target_pose_embeds, target_srt, batch_size=16, as_uint8=True, identities=None, mix=False, mix_old=True,
+                target_theta=True, smooth_pose=False, smooth_per_identity=False):
         """1 source -> N driver frames (the BASELINE metric).  Frames are sharded contiguously across ranks
         (SURVEY.md section 8e); each rank walks its shard in batches of `batch_size`.  Yields (first_frame_index, frames)
         with frames a uint8 [B,H,W,3] (or fp32 [B,3,H,W]) DEVICE tensor -- no host sync inside the loop.
         identities: slot of the identity bank per frame ([N], over the whole frame stream; each rank takes its slice) -- the
-        frames of a batch may then belong to different identities."""
+        frames of a batch may then belong to different identities.
+        mix / mix_old / target_theta / smooth_pose: forward()'s pose controls (infer.py:568-584), all on the device.  mix keeps
+        each frame's identity's face stretch (its bank slot's source theta, or the current identity's); target_theta=False
+        renders in that identity's own head pose.  smooth_pose is a scan over the FRAME ORDER: every rank forms the thetas of
+        the whole stream from target_srt (16 floats per frame) and scans them, then renders its own slice -- 1 rank and N ranks
+        give the same frames.  Without identities the state is `self.theta` (carried from call to call, as in forward); with
+        them, smooth_pose needs smooth_per_identity=True, and each slot then has its own stream."""
+        self._check_smoothing(identities, smooth_pose, smooth_per_identity)
         N = target_pose_embeds.shape[0]
         ids = None if identities is None else self._frame_identities(identities, N)
         if ids is None and self._canonical_cl is None:
             raise RuntimeError("call forward with a source_image first")
+        if ids is None and (mix or not target_theta):
+            self._source_theta('mix=True' if mix else 'target_theta=False')
         lo, hi = parallel.shard_range(N, self.rank, self.world)
         ids_dev = None if ids is None else ids[lo:hi].to(self.device)
+        smoothed = None
+        if smooth_pose and N > 0:
+            theta = ops.pose_theta(*[t.to(self.device).float().contiguous() for t in target_srt])
+            if ids is None:
+                theta = self._pose_controls(theta, None, mix, mix_old, False)
+                state = torch.zeros((1, 4, 4), device=self.device, dtype=torch.float32)
+                has = torch.zeros((1,), device=self.device, dtype=torch.int32)
+                if self.theta is not None:
+                    state.copy_(self.theta.reshape(1, 4, 4))
+                    has.fill_(1)
+                smoothed = ops.theta_ema_scan(theta, None, state, has, self.pose_momentum)[lo:hi]
+                self.theta = state[0]
+            else:
+                smoothed = self._pose_controls(theta, ids.to(self.device), mix, mix_old, True)[lo:hi]
         for b0 in range(lo, hi, batch_size):
             b1 = min(b0 + batch_size, hi)
             pose = target_pose_embeds[b0:b1].to(self.device).float().contiguous()
-            srt = [t[b0:b1].to(self.device).float().contiguous() for t in target_srt]
-            theta = ops.pose_theta(*srt)
-            img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ids_dev[b0 - lo:b1 - lo])
+            ident = None if ids is None else ids_dev[b0 - lo:b1 - lo]
+            if smoothed is not None:
+                theta = smoothed[b0 - lo:b1 - lo]
+            else:
+                srt = [t[b0:b1].to(self.device).float().contiguous() for t in target_srt]
+                theta = self._pose_controls(ops.pose_theta(*srt), ident, mix, mix_old, False)
+            theta = self._render_theta(theta, ident, target_theta)
+            img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ident)
             yield b0, (ops.pack_rgb8(img) if as_uint8 else img)
 
     # ------------------------------------------------------------------------------------------------------
-    def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None):
+    def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
+                       mix=False, mix_old=True, target_theta=True, smooth_per_identity=False):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  frames: uint8 [N,H,W,3] tensor (host, ideally pinned, or device) or an iterable of such chunks --
         decoded video frames, uploaded as BYTES.  Per batch, all on the device and without a host synchronisation:
@@ -624,15 +719,21 @@ class InferenceWrapper:
         Yields (first_frame_index, uint8 [b,S,S,3]) -- a view of a pinned ring slot, valid ONLY until the generator is resumed
         (the next batch's copy may be queued into the same slot right away: consume or copy it before calling next()) --
         or, with to_host=False, the device tensor.  Frames are sharded contiguously across ranks as in animate().
-        identities: slot of the identity bank per frame, over the whole frame stream (as in animate()); not with smooth_pose,
-        whose EMA is one state per stream."""
+        identities: slot of the identity bank per frame, over the whole frame stream (as in animate()).
+        mix / mix_old / target_theta: forward()'s pose controls (infer.py:568-569, :584), per frame against that frame's
+        identity, on the device (ops.mixing_theta; a gather of the bank's source thetas).  The order is forward()'s: regressed
+        theta -> mix -> smooth_pose -> expression embedder -> render (with the source theta if target_theta=False).  With
+        identities, smooth_pose needs smooth_per_identity=True (else ValueError): each frame is then smoothed within its own
+        identity's frame sequence, as if every identity had its own wrapper: one stream per slot, scanned on the device (ops.theta_ema_scan) over the whole gathered chunk on every rank, so
+        the slot states stay identical across ranks; store_identity / drop_identity / reset_pose_state reset a slot's stream."""
         ids = None
+        self._check_smoothing(identities, smooth_pose, smooth_per_identity)
         if identities is not None:
-            if smooth_pose:
-                raise ValueError("smooth_pose=True smooths one pose stream: it does not combine with identities=")
             ids = self._frame_identities(identities, frames.shape[0] if isinstance(frames, torch.Tensor) else None)
         elif self._canonical_cl is None:
             raise RuntimeError("call forward with a source_image first")
+        elif mix or not target_theta:
+            self._source_theta('mix=True' if mix else 'target_theta=False')
         S = self.cfg["image_size"]
         chunks = [frames] if isinstance(frames, torch.Tensor) else frames
         copy_stream = torch.cuda.Stream(device=self.device) if to_host else None
@@ -691,6 +792,7 @@ class InferenceWrapper:
                 raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
             lo, hi = parallel.shard_range(n, self.rank, self.world)
             ids_dev = None if ids is None else ids[base + lo:base + hi].to(self.device)
+            ids_chunk = None if ids is None or not smooth_pose else ids[base:base + n].to(self.device)
             spans = [(b0, min(b0 + batch_size, hi)) for b0 in range(lo, hi, batch_size)]
             smoothed, kept = None, {}
             if smooth_pose:
@@ -702,8 +804,10 @@ class InferenceWrapper:
                     if keep_crops:
                         kept[b0] = crops
                 local = torch.cat(local) if local else torch.empty((0, 4, 4), device=self.device)
+                if mix:
+                    local = self._pose_controls(local, ids_dev, True, mix_old, False)
                 every = parallel.gather_shards(local, n, self.rank, self.world)        # [n,4,4] on every rank, frame order
-                smoothed = self._smooth_thetas(every)[lo:hi]
+                smoothed = self._pose_controls(every, ids_chunk, False, mix_old, True)[lo:hi]
             # (every span whose crops stayed resident from the head-pose pass needs no second upload)
             todo = [sp for sp in spans if sp[0] not in kept]
             fresh = uploaded(chunk, todo)
@@ -713,11 +817,17 @@ class InferenceWrapper:
                     f0, f1, u8 = next(fresh)
                     assert (f0, f1) == (b0, b1)
                     crops = crops_of(u8, base, b0, b1)
-                theta = smoothed[b0 - lo:b1 - lo] if smoothed is not None else self._head_pose(crops)[0]
+                ident = None if ids is None else ids_dev[b0 - lo:b1 - lo]
+                if smoothed is not None:
+                    theta = smoothed[b0 - lo:b1 - lo]
+                else:
+                    theta = self._head_pose(crops)[0]
+                    if mix:
+                        theta = self._pose_controls(theta, ident, True, mix_old, False)
                 self.pred_target_theta = theta                                   # (as forward() leaves it: infer.py:584)
                 pose, _ = self._expression(crops, theta, 'a driver call')
-                theta = theta.float().contiguous()
-                img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ids_dev[b0 - lo:b1 - lo])
+                theta = self._render_theta(theta, ident, target_theta)
+                img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ident)
                 out = ops.pack_rgb8(img)
                 if not to_host:
                     yield base + b0, out

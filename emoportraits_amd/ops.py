@@ -772,3 +772,45 @@ def mat4_inverse(m):
     out = torch.empty_like(m)
     hip.check(lib.emo_mat4_inverse_f32(hip.ptr(m), hip.ptr(out), m.shape[0], hip.current_stream()), "emo_mat4_inverse_f32")
     return out
+
+
+def mixing_theta(target, source_bank, index=None, mix_old=True):
+    """notebooks/infer.py:686-736 get_mixing_theta on the device, per frame: the stretch of its source theta
+    source_bank[index[n]] with the rotation and translation of target[n].  target [B,4,4], source_bank [K,4,4], index int32 [B]
+    on the same device or None (every frame: source 0) -> [B,4,4] (row 3 = (0,0,0,1)).  An index outside [0, K) passes the
+    target through.  fp64 inside, as hostglue.mixing_theta; no host synchronisation."""
+    lib = hip.load()
+    hip.require_cuda_f32(target, source_bank)
+    if target.dim() != 3 or target.shape[1:] != (4, 4) or source_bank.dim() != 3 or source_bank.shape[1:] != (4, 4):
+        raise ValueError(f"mixing_theta expects [B,4,4] and [K,4,4], got {tuple(target.shape)} and {tuple(source_bank.shape)}")
+    B, K = target.shape[0], source_bank.shape[0]
+    if B == 0 or K == 0:
+        raise ValueError("mixing_theta: empty target or source bank")
+    if index is not None:
+        _check_index(index, B, target.device, "index")
+    out = torch.empty_like(target)
+    hip.check(lib.emo_mixing_theta_f32(hip.ptr(target), hip.ptr(source_bank), hip.ptr(index), B, K, int(bool(mix_old)),
+                                       hip.ptr(out), hip.current_stream()), "emo_mixing_theta_f32")
+    return out
+
+
+def theta_ema_scan(values, stream_of, state, has_state, momentum):
+    """notebooks/infer.py:571-581 smooth_pose over a batch IN FRAME ORDER with one EMA stream per identity, on the device:
+    values [n,4,4], stream_of int32 [n] (or None: one stream, 0), state [K,4,4] and has_state int32 [K] updated in place.
+    Per stream bit for bit hostglue.ema_scan (1 - momentum rounded to fp32 once, as there) -> smoothed [n,4,4]."""
+    import numpy as np
+    lib = hip.load()
+    hip.require_cuda_f32(values, state)
+    if values.dim() != 3 or values.shape[1:] != (4, 4) or state.dim() != 3 or state.shape[1:] != (4, 4):
+        raise ValueError(f"theta_ema_scan expects [n,4,4] values and [K,4,4] state, got {tuple(values.shape)}, {tuple(state.shape)}")
+    n, K = values.shape[0], state.shape[0]
+    if n == 0 or K == 0:
+        raise ValueError("theta_ema_scan: no frames or no streams")
+    _check_index(has_state, K, state.device, "has_state")
+    if stream_of is not None:
+        _check_index(stream_of, n, values.device, "stream_of")
+    out = torch.empty_like(values)
+    m, om = float(np.float32(momentum)), float(np.float32(1 - momentum))
+    hip.check(lib.emo_theta_ema_scan_f32(hip.ptr(values), hip.ptr(stream_of), hip.ptr(state), hip.ptr(has_state), n, K, m, om,
+                                         hip.ptr(out), hip.current_stream()), "emo_theta_ema_scan_f32")
+    return out

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 12
+#define EMO_ABI_VERSION 13
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -429,6 +429,23 @@ int emo_pose_theta_f32(const float* scale, int scale_cols, const float* rotation
                        float* theta, int B, void* stream);
 /* inverse of B row-major 4x4 matrices (`theta.float().inverse()`: notebooks/infer.py:443, expression_embedder.py:185-188) */
 int emo_mat4_inverse_f32(const float* in, float* out, int B, void* stream);
+/* ABI 13.  notebooks/infer.py:686-736 get_mixing_theta on the device, one frame per thread: frame n keeps the stretch of source
+ * theta source[index[n]] and takes rotation and translation from target[n] (hostglue.mixing_theta for one source and one target).
+ *   target [B,4,4], source [K,4,4] (a bank of source thetas), index [B] int32 DEVICE memory or NULL (every frame: source 0),
+ *   out [B,4,4]: rows 0..2 the mixed theta, row 3 (0,0,0,1).
+ * fp64 from the fp32 inputs, each output rounded to fp32 once; polar decomposition by a one-sided Jacobi SVD (det < 0 included).
+ * mix_old != 0: [U_t P_s | t_t]; 0: P_s4 * mean(P_t4) / mean(P_s4) @ U_t4 @ T4 on the 4x4 homogeneous matrices.  A non-finite
+ * source linear part, or an index outside [0, K) (the source is then not read), gives the target unchanged; a non-finite
+ * target linear part gives [P_s | 0]. */
+int emo_mixing_theta_f32(const float* target, const float* source, const int32_t* index, int B, int K, int mix_old, float* out,
+                         void* stream);
+/* ABI 13.  notebooks/infer.py:571-581 smooth_pose with one EMA stream per source identity: frame i (values [n,16], frame order)
+ * belongs to stream stream_of[i] ([n] int32 DEVICE memory, or NULL: stream 0).  state [K,16] and has_state [K] int32 are read and
+ * written: a stream without state starts at its first frame's value, then cur = v * m + cur * om (two rounded fp32 products,
+ * one rounded sum), out[i] = cur -- per stream bit for bit hostglue.ema_scan with om = fp32(1 - momentum) formed by the caller.
+ * A stream index outside [0, K) leaves its frames unwritten. */
+int emo_theta_ema_scan_f32(const float* values, const int32_t* stream_of, float* state, int32_t* has_state, int n, int K, float m,
+                           float om, float* out, void* stream);
 int emo_pack_rgb8(const float* img, uint8_t* out, int N, int H, int W, void* stream);
 int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int W, void* stream);
 

@@ -4,6 +4,7 @@
     python tools/animate_video.py --project <project_dir> --experiment <exp> --checkpoint <file> \
         --source source.png --frames <dir of PNG/JPG frames | frames.npy (uint8 [N,H,W,3])> --out <dir> [--batch 16]
         [--windows windows.json]   # optional per-frame crop windows [[x_lo, y_lo, side], ...] from a face detector
+        [--mix [--mix-new]] [--source-pose] [--smooth-pose]   # forward()'s pose controls (mix, mix_old=False, target_theta=False)
 
 Frame I/O is host work (PIL / numpy): decoded frames are handed to InferenceWrapper.animate_frames as uint8 chunks in pinned
 memory; crop, bicubic resize, both embedders, the hot path and the uint8 packing run on the GPU without a host sync, and
@@ -51,6 +52,10 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--graphs", action="store_true")
+    ap.add_argument("--mix", action="store_true", help="keep the source's face stretch, take the driver's rotation + translation")
+    ap.add_argument("--mix-new", action="store_true", help="with --mix: the reference's mix_old=False formula")
+    ap.add_argument("--source-pose", action="store_true", help="render in the source's own head pose (target_theta=False)")
+    ap.add_argument("--smooth-pose", action="store_true", help="EMA over the driver head poses (smooth_pose=True)")
     a = ap.parse_args()
     from PIL import Image
     from notebooks.infer import InferenceWrapper
@@ -64,7 +69,9 @@ def main():
     windows = json.load(open(a.windows)) if a.windows else None
     os.makedirs(a.out, exist_ok=True)
     t0, n = time.perf_counter(), 0
-    for first, u8 in w.animate_frames(load_frames(a.frames, 8 * a.batch), batch_size=a.batch, windows=windows):
+    frames = load_frames(a.frames, 8 * a.batch)
+    for first, u8 in w.animate_frames(frames, batch_size=a.batch, windows=windows, mix=a.mix, mix_old=not a.mix_new,
+                                      target_theta=not a.source_pose, smooth_pose=a.smooth_pose):
         arr = u8.numpy()
         for j in range(arr.shape[0]):
             Image.fromarray(arr[j]).save(os.path.join(a.out, f"{first + j:06d}.png"))
