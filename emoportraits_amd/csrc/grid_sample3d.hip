@@ -528,14 +528,23 @@ int dispatch_cl_v2(const float* vol, const float* grid, const float* theta, cons
 // ------------------------------------------------------------------------------------------------------
 // layout repack [N][C][S] <-> [N][S][C] through a 64x64 LDS tile
 // ------------------------------------------------------------------------------------------------------
+// RowArgs: empty, or (const int* row, int num_rows) for the indexed entry (emo_volume_repack_indexed_f32) -- matrix n is then
+// written to matrix row[n] of the output bank, and a row outside [0, num_rows) writes nothing.  Empty, the kernel has the
+// parameter list and code it has without rows.
+template <typename... RowArgs>
 __global__ __launch_bounds__(256) void repack_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                     int R, int Ccols) {
+                                                     int R, int Ccols, RowArgs... rows) {
   // in: [n][R][Ccols] -> out: [n][Ccols][R]
   __shared__ float tile[64][65];
   const int n = blockIdx.z;
   const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
   const float* ip = in + (long)n * R * Ccols;
   float* op = out + (long)n * R * Ccols;
+  if constexpr (sizeof...(RowArgs) != 0) {
+    int rsel;
+    if (!bank_volume(n, rsel, rows...)) return;        // uniform over the block: no barrier is skipped by part of it
+    op = out + (long)rsel * R * Ccols;                  // 64-bit row base: a bank of R512 slots passes 2^31 floats
+  }
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   for (int i = ty; i < 64; i += 4) {
     const int r = r0 + i, c = c0 + tx;
@@ -702,6 +711,18 @@ extern "C" int emo_volume_repack_f32(const float* in, float* out, int N, int C, 
   const int Ccols = to_channels_last ? DHW : C;   // columns of the input matrix
   dim3 g(emo_cdiv(Ccols, 64), emo_cdiv(R, 64), N);
   if (g.y > 65535) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(repack_kernel, g, dim3(256), 0, (hipStream_t)stream, in, out, R, Ccols);
+  hipLaunchKernelGGL(repack_kernel<>, g, dim3(256), 0, (hipStream_t)stream, in, out, R, Ccols);
+  return emo_launch_status();
+}
+
+// emo_volume_repack_f32(to_channels_last = 1) of N volumes into rows row[n] of a channels-last bank of num_rows volumes
+extern "C" int emo_volume_repack_indexed_f32(const float* in, float* bank, const int32_t* row, int N, int C, int DHW,
+                                             int num_rows, void* stream) {
+  if (!in || !bank || !row || N <= 0 || C <= 0 || DHW <= 0 || num_rows <= 0) return EMO_ERR_BAD_ARG;
+  if (N > 65535) return EMO_ERR_UNSUPPORTED;
+  dim3 g(emo_cdiv(DHW, 64), emo_cdiv(C, 64), N);
+  if (g.y > 65535) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL((repack_kernel<const int*, int>), g, dim3(256), 0, (hipStream_t)stream, in, bank, C, DHW, (const int*)row,
+                     num_rows);
   return emo_launch_status();
 }

@@ -27,6 +27,7 @@ SIGNATURES = {
     "emo_grid_sample3d_indexed_f32": [_c_void, _c_void, _c_int] + [_c_void] * 6 + [_c_int] * 13 + [_c_void],
     "emo_affine_grid3d_f32": [_c_void] * 5 + [_c_int] * 4 + [_c_void],
     "emo_volume_repack_f32": [_c_void, _c_void, _c_int, _c_int, _c_int, _c_int, _c_void],
+    "emo_volume_repack_indexed_f32": [_c_void, _c_void, _c_void, _c_int, _c_int, _c_int, _c_int, _c_void],
     "emo_groupnorm_workspace_bytes": [_c_int, _c_int],
     "emo_groupnorm_affine_f32": [_c_void, _c_int, _c_int, _c_i64, _c_int, _c_float] + [_c_void] * 4 + [_c_i64]
                                 + [_c_void] * 5 + [_c_i64, _c_void],

@@ -123,3 +123,49 @@ def ema_scan(values, state, momentum):
         cur = v[i] * m + cur * om
         out[i] = cur
     return out, cur
+
+
+def enrolment_plan(used, n_sources, slots=None, batch_size=8, world=1):
+    """InferenceWrapper.enrol_identities on the host, before anything is launched -> (slots, chunks, owners).
+    used: the occupied flag of every bank slot.  slots=None takes the n_sources lowest free slots; an explicit list may name
+    occupied slots (they are overwritten, as store_identity(slot) overwrites).  Chunk j is the sources
+    [j * batch_size, (j + 1) * batch_size) whatever the world size, and rank r owns the contiguous chunk range
+    parallel.shard_range(len(chunks), r, world); owners[j] is the rank that computes chunk j.  ValueError for a bank without
+    slots, no sources, too few free slots, a duplicate or out-of-range slot and a batch size below 1.  A pure function of its
+    arguments: every rank passes the same ones and takes the same decision."""
+    import operator
+    from .parallel import shard_range
+    capacity = len(used)
+    if capacity == 0:
+        raise ValueError("this wrapper has no identity bank: construct it with identity_capacity=K")
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+    if n_sources == 0:
+        raise ValueError("no sources to enrol")
+    if slots is None:
+        free = [k for k, u in enumerate(used) if not u]
+        if len(free) < n_sources:
+            raise ValueError(f"{n_sources} sources, {len(free)} free identity slots of {capacity}: drop_identity some or pass slots=")
+        slots = free[:n_sources]
+    else:
+        out = []
+        for k in slots:
+            try:
+                k = operator.index(k) if not isinstance(k, bool) else None
+            except TypeError:
+                k = None
+            if k is None or not 0 <= k < capacity:
+                raise ValueError(f"slot {k!r} is not in [0, {capacity})")
+            out.append(k)
+        slots = out
+        if len(slots) != n_sources:
+            raise ValueError(f"{len(slots)} slots for {n_sources} sources")
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"slots {slots} name a slot twice")
+    n_chunks = -(-n_sources // batch_size)
+    chunks = [(j * batch_size, min((j + 1) * batch_size, n_sources)) for j in range(n_chunks)]
+    owners = [0] * n_chunks
+    for r in range(world):
+        lo, hi = shard_range(n_chunks, r, world)
+        owners[lo:hi] = [r] * (hi - lo)
+    return slots, chunks, owners

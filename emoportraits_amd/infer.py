@@ -20,7 +20,8 @@ and their source-side counterparts added here (`custome_source_pose_embed`, `cus
 Extension over the reference (which is batch-1, F5): driver inputs may carry a batch dimension, and
 `animate()` streams N driver frames in device-sized batches, sharded across ranks (emoportraits_amd/parallel.py).
 With `identity_capacity=K` the wrapper also keeps a bank of K source identities on the device (`store_identity`,
-`load_identity`, `drop_identity`, `identities`, `share_identity`), and `animate` / `animate_frames(identities=...)` render
+`load_identity`, `drop_identity`, `identities`, `share_identity`; `enrol_identities` fills it K sources at a time, sharded across
+ranks), and `animate` / `animate_frames(identities=...)` render
 frames of several identities in one driver batch.  Both batched entry points take forward()'s pose controls -- `mix` / `mix_old`
 (get_mixing_theta), `target_theta` and `smooth_pose` -- on the device (ops.mixing_theta, ops.theta_ema_scan, a gather of the
 source thetas): with a bank, every frame is mixed against its own identity's source theta, and with smooth_per_identity=True
@@ -326,6 +327,178 @@ class InferenceWrapper:
             exchange_shapes=False)
         if not src:
             self._bank_write(slot, cache["canonical_cl"], cache["idt_embed"], cache["theta_src"])
+
+    def enrol_identities(self, sources, source_masks=None, slots=None, crop=False, windows=None, batch_size=8,
+                         custome_idt_embed=None, custome_source_pose_embed=None, custome_source_theta_embed=None):
+        """Enrol K source identities into bank slots in chunks of `batch_size`: per chunk the mask products (ops.mul_mask), the
+        embedders and HotPath.source_pass run at batch b, the canonical volumes go into their bank rows in one launch
+        (ops.volume_to_channels_last_indexed) and the idt_embed / theta rows by device index copies -- no host synchronisation
+        inside a chunk.  Identity k gets the semantics of forward(source_image=sources[k], source_mask=source_masks[k],
+        crop=crop, custome_*=...[k]) followed by store_identity(slots[k]).
+        sources: a list of images or a float tensor [K,3,H,W] (what forward takes, stacked), or uint8 frames [K,H,W,3] (host
+        or device, animate_frames' input) with optional windows[k] = (x_lo, y_lo, side), cropped as animate_frames crops.
+        custome_*: K-row tensors; the theta as [K,4,4] or (scale, rotation, translation) of [K,3] each.
+        slots=None takes the K lowest free slots; explicit slots may overwrite occupied ones.  Every check runs on the host
+        before the first launch (ValueError; the bank is untouched).  The current identity is left as it is.
+        On several ranks every rank calls with the same arguments: chunk j is sources [j * batch_size, (j + 1) * batch_size),
+        rank r computes the chunks parallel.shard_range(n_chunks, r, world), and each chunk's owner broadcasts {canonical,
+        idt_embed, theta} in one flat buffer, from which every rank, the owner included, writes its rows -- the bank is the
+        same bit for bit on every rank and for any number of ranks.  Returns the slots in the order of `sources`."""
+        with torch.no_grad():
+            return self._enrol_identities(sources, source_masks, slots, crop, windows, batch_size, custome_idt_embed,
+                                          custome_source_pose_embed, custome_source_theta_embed)
+
+    def _enrol_identities(self, sources, source_masks, slots, crop, windows, batch_size, custome_idt_embed,
+                          custome_source_pose_embed, custome_source_theta_embed):
+        S = self.cfg["image_size"]
+        video = isinstance(sources, torch.Tensor) and sources.dtype == torch.uint8
+        if isinstance(sources, torch.Tensor):
+            if video and (sources.dim() != 4 or sources.shape[-1] != 3):
+                raise ValueError(f"uint8 sources must be frames [K,H,W,3], got {tuple(sources.shape)}")
+            if not video and (sources.dim() != 4 or sources.shape[1] < 3):
+                raise ValueError(f"float sources must be [K,3,H,W], got {tuple(sources.shape)}")
+            K = sources.shape[0]
+        elif isinstance(sources, (list, tuple)):
+            K = len(sources)
+        else:
+            raise ValueError("sources: a list of images, a float tensor [K,3,H,W] or uint8 frames [K,H,W,3]")
+        slots, chunks, owners = hostglue.enrolment_plan(self._bank_used, K, slots, batch_size, self.world)
+        if video and crop:
+            raise ValueError("uint8 frames are cropped by windows= (crop=True detects faces in images)")
+        if windows is not None and not video:
+            raise ValueError("windows= crops uint8 frames [K,H,W,3]")
+        win_host = None
+        if windows is not None:
+            H, W = sources.shape[1], sources.shape[2]
+            win_host = torch.tensor([[int(w[0]), int(w[1]), int(w[2]), int(w[2])] for w in windows], dtype=torch.int32).reshape(-1, 4)
+            if win_host.shape[0] != K:
+                raise ValueError(f"{win_host.shape[0]} windows for {K} sources")
+            lo, side = win_host[:, :2], win_host[:, 2]
+            if not (bool((lo >= 0).all()) and bool((side > 0).all()) and bool((lo[:, 0] + side <= W).all())
+                    and bool((lo[:, 1] + side <= H).all())):
+                raise ValueError(f"a crop window is not inside the {W}x{H} frame")
+        parsing = 'face_parsing' in self.embedders
+        masks = None
+        if source_masks is not None:
+            ms = [source_masks[i] for i in range(source_masks.shape[0])] if isinstance(source_masks, torch.Tensor) else list(source_masks)
+            if len(ms) != K:
+                raise ValueError(f"{len(ms)} source masks for {K} sources")
+            if any(m.numel() != S * S for m in ms):
+                raise ValueError(f"a source mask is not one {S}x{S} plane")
+        elif not parsing:
+            raise ValueError("enrolment needs source_masks= (or a 'face_parsing' embedder): the reference masks the source with "
+                             "BiSeNet face parsing (infer.py:410-417)")
+
+        def rows(t, what, row_shape=None):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[0] != K:
+                raise ValueError(f"{what}: expected a tensor of {K} rows, got {getattr(t, 'shape', type(t))}")
+            if row_shape is not None and tuple(t.shape[1:]) != tuple(row_shape):
+                raise ValueError(f"{what}: rows {tuple(t.shape[1:])}, expected {tuple(row_shape)}")
+            return t
+        rows(custome_idt_embed, 'custome_idt_embed')
+        if custome_idt_embed is not None and custome_idt_embed[0].numel() != self._bank_idt[0].numel():
+            raise ValueError(f"custome_idt_embed rows {tuple(custome_idt_embed.shape[1:])} do not fit a slot "
+                             f"{tuple(self._bank_idt.shape[1:])}")
+        rows(custome_source_pose_embed, 'custome_source_pose_embed')
+        theta_in = custome_source_theta_embed
+        if theta_in is not None:
+            if isinstance(theta_in, torch.Tensor):
+                rows(theta_in, 'custome_source_theta_embed', (4, 4))
+            elif isinstance(theta_in, (tuple, list)) and len(theta_in) == 3:
+                for t in theta_in:
+                    rows(t, 'custome_source_theta_embed (scale, rotation, translation)', (3,))
+            else:
+                raise ValueError("custome_source_theta_embed: a [K,4,4] tensor or (scale, rotation, translation)")
+        if custome_idt_embed is None:
+            self._need('idt_embedder', 'enrolment')
+        if theta_in is None:
+            self._need('head_pose_regressor', 'enrolment')
+        if custome_source_pose_embed is None:
+            self._need('expression_embedder', 'enrolment')
+        images = None if video else (list(sources) if isinstance(sources, (list, tuple)) else [sources[i] for i in range(K)])
+        boxes = None
+        if crop and 'cropper' not in self.embedders:
+            # forward(crop=True) renders a zero crop where no face was found: found here, before anything is launched
+            det = self._need('face_detector', 'crop=True')
+            boxes = []
+            for i, img in enumerate(images):
+                rel = det(img)
+                t = self.convert_to_tensor(img)[0, :3]
+                face = None if rel is None else hostglue.detection_to_face(*rel, t.shape[2], t.shape[1])
+                win = hostglue.crop_window(face, t.shape[2], t.shape[1])
+                if win is None:
+                    raise ValueError(f"source {i}: no face found (forward would render a zero crop for it; nothing was enrolled)")
+                boxes.append((t, win))
+
+        # ---- device: inputs uploaded once, then chunk by chunk without a host synchronisation
+        dev = self.device
+        rows32 = torch.tensor(slots, dtype=torch.int32).to(dev)
+        rows64 = rows32.long()
+        masks = None if source_masks is None else torch.cat([m.reshape(1, 1, S, S) for m in ms]).to(dev).float().contiguous()
+        up = lambda t: None if t is None else t.to(dev).float().contiguous()
+        idt_all, pose_all = up(custome_idt_embed), up(custome_source_pose_embed)
+        theta_all = None
+        if theta_in is not None:
+            theta_all = self._theta_from(theta_in)[0]
+        if video:
+            u8 = sources.to(dev).contiguous()
+            win_dev = None if win_host is None else win_host.to(dev)
+            crops_all = None
+        elif not crop:
+            crops_all = torch.cat([self._prepare_image(img) for img in images])               # (as forward, per image)
+        elif boxes is None:
+            crops_all = self.embedders['cropper'](images).to(dev)
+        else:
+            crops_all = torch.cat([ops.resize2d(t[None].to(dev).float().contiguous(), (S, S), "bicubic",
+                                                window=(x_lo, y_lo, side, side), clamp01=True) for t, (x_lo, y_lo, side, _) in boxes])
+        es_shape = tuple(self._bank_idt.shape[1:])
+        hp = self.hot_path
+
+        def compute(a, b):
+            if video:
+                x = ops.unpack_rgb8(u8[a:b])                                    # animate_frames' crops_of, one launch per chunk
+                if win_dev is not None:
+                    crop_img = ops.resize2d_windows(x, (S, S), win_dev[a:b], "bicubic", clamp01=True)
+                else:
+                    crop_img = ops.resize2d(x, (S, S), "bicubic") if x.shape[-2:] != (S, S) else x
+            else:
+                crop_img = crops_all[a:b].float().contiguous()
+            m = None if masks is None else masks[a:b]
+            face = (self.embedders['face_parsing'](crop_img) > 0.6).float().contiguous() if parsing else m   # infer.py:408-411
+            crop_m = ops.mul_mask(crop_img, face)
+            masked = ops.mul_mask(crop_m, m if m is not None else face)
+            idt = idt_all[a:b] if idt_all is not None else self._need('idt_embedder', 'enrolment')(masked)
+            theta = theta_all[a:b] if theta_all is not None else self._head_pose(crop_m)[0]
+            pose = pose_all[a:b] if pose_all is not None else self._expression(crop_m, theta, 'enrolment')[0]
+            theta = theta.float().contiguous()
+            canonical = hp.source_pass(masked, idt.float().contiguous(), pose.float().contiguous(), theta)
+            return dict(canonical=canonical, idt_embed=idt.float().reshape((b - a,) + es_shape), theta_src=theta.reshape(b - a, 4, 4))
+
+        def write(part, a, b):
+            ops.volume_to_channels_last_indexed(part["canonical"], self._bank_cl, rows32[a:b])
+            self._bank_idt.index_copy_(0, rows64[a:b], part["idt_embed"])
+            self._bank_theta.index_copy_(0, rows64[a:b], part["theta_src"])
+
+        if self.world == 1:
+            for a, b in chunks:
+                write(compute(a, b), a, b)
+        else:
+            # each rank computes its own chunks first, then every chunk travels from its owner, in chunk order
+            mine = {j: compute(a, b) for j, (a, b) in enumerate(chunks) if owners[j] == self.rank}
+            c, d, s = self.cfg["latent_volume_channels"], self.cfg["latent_volume_depth"], self.cfg["latent_volume_size"]
+            for j, (a, b) in enumerate(chunks):
+                n = b - a
+                part = parallel.broadcast_source_cache(
+                    mine.pop(j, {}), shapes=dict(canonical=(n, c, d, s, s), idt_embed=(n,) + es_shape, theta_src=(n, 4, 4)),
+                    names=['canonical', 'idt_embed', 'theta_src'], src=owners[j], device=dev, world=self.world, rank=self.rank,
+                    exchange_shapes=False)
+                write(part, a, b)
+        for k in slots:
+            self._bank_used[k] = True
+        self._bank_pose_has.index_fill_(0, rows64, 0)              # a new identity starts a new smooth_pose stream
+        return slots
 
     def _frame_identities(self, identities, n=None):
         """per-frame slots -> int32 host tensor, every slot checked on the host (the device never sees an unknown slot)"""

@@ -360,15 +360,18 @@ class HotPath:
 
     # ---- per identity -------------------------------------------------------------------------------
     def source_pass(self, source_img_masked, idt_embed, source_pose_embed, theta_src, keep=False):
-        """-> canonical volume [1,c,d,s,s] (NCDHW, as the reference caches it in self.target_latent_volume)"""
+        """-> canonical volumes [B,c,d,s,s] (NCDHW, as the reference caches it in self.target_latent_volume) of B source
+        identities: source_img_masked [B,3,S,S], idt_embed [B,C,es,es], source_pose_embed [B,E], theta_src [B,4,4].  Every
+        launch takes the batch (per-sample idt rows, volumes and thetas); B = 1 is the reference's one identity per call."""
         c, d, s = self.c, self.d, self.s
+        B = source_img_masked.shape[0]
         self._clear_flags()
         latents = self.local_encoder(source_img_masked)
         emb = self.embed(source_pose_embed, idt_embed)
         delta_xy = self.xy_generator(emb)
-        # (the [1, c*d, s, s] -> [1, c, d, s, s] view regroups the channels: the 2-D tile statistics of `latents` do not
+        # (the [B, c*d, s, s] -> [B, c, d, s, s] view regroups the channels: the 2-D tile statistics of `latents` do not
         # describe the 3-D GroupNorm groups, so the first VPN norm reduces its own)
-        vol = self.volume_source(latents.view(1, c, d, s, s))
+        vol = self.volume_source(latents.view(B, c, d, s, s))
         inv = ops.mat4_inverse(theta_src.float().contiguous())            # infer.py:443 on the device: no host round trip
         # both sampler calls through the channels-last kernels (one repack in, NCDHW out): 2.5x the NCDHW gather's rate
         rot = ops.grid_sample3d(ops.volume_to_channels_last(vol), theta=inv, padding_mode=self.pad, in_layout="ndhwc",

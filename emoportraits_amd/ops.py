@@ -169,6 +169,23 @@ def volume_to_channels_last(vol):
     return out
 
 
+def volume_to_channels_last_indexed(vol, bank, row):
+    """bank[row[n]] = volume_to_channels_last(vol[n:n+1]) bit for bit, in one launch: vol [N,C,D,H,W], bank [K,D,H,W,C] (written
+    in place), row int32 [N] on the same device.  A row outside [0, K) writes nothing: the device reads the rows, so the host
+    cannot check them at launch.  Returns bank."""
+    lib = hip.load()
+    hip.require_cuda_f32(vol, bank)
+    if vol.dim() != 5 or bank.dim() != 5:
+        raise ValueError(f"vol {tuple(vol.shape)} and bank {tuple(bank.shape)} must be 5-D")
+    N, C, D, H, W = vol.shape
+    if tuple(bank.shape[1:]) != (D, H, W, C):
+        raise ValueError(f"a row of bank {tuple(bank.shape)} does not hold the channels-last volume {(D, H, W, C)}")
+    _check_index(row, N, vol.device, "row")
+    hip.check(lib.emo_volume_repack_indexed_f32(hip.ptr(vol), hip.ptr(bank), hip.ptr(row), N, C, D * H * W, bank.shape[0],
+                                                hip.current_stream()), "emo_volume_repack_indexed_f32")
+    return bank
+
+
 TILE = 1 << 30      # grid_sample3d(variant=TILE | tuning): NCDHW -> NCDHW through the LDS-staged planar kernel
 
 

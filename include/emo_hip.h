@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 13
+#define EMO_ABI_VERSION 14
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -128,6 +128,16 @@ int emo_affine_grid3d_f32(const float* theta, const float* lin_x, const float* l
 /* Layout repack of a 5-D volume (used once per identity on the cached canonical volume, notebooks/infer.py:507
  * `self.target_latent_volume`).  to_channels_last: 0 NDHWC -> NCDHW, 1 NCDHW -> NDHWC, 4 NCDHW -> P4, 5 P4 -> NCDHW. */
 int emo_volume_repack_f32(const float* in, float* out, int N, int C, int DHW, int to_channels_last, void* stream);
+
+/* ABI 14.  emo_volume_repack_f32(..., to_channels_last = 1) of N volumes into rows of a channels-last BANK (enrolment of several
+ * source identities at once): bank[row[n]] = the NDHWC repack of in[n], the same 64x64 LDS-tile transpose, so every written row
+ * is bit-identical to emo_volume_repack_f32(in + n * C * DHW, ..., 1).
+ *   in    [N, C, D, H, W] (NCDHW; DHW = D * H * W)
+ *   bank  [num_rows, D, H, W, C]
+ *   row   [N] int32, DEVICE memory.  A row outside [0, num_rows) writes nothing.
+ * in, bank or row NULL, N, C, DHW or num_rows <= 0: EMO_ERR_BAD_ARG.  N > 65535: EMO_ERR_UNSUPPORTED. */
+int emo_volume_repack_indexed_f32(const float* in, float* bank, const int32_t* row, int N, int C, int DHW, int num_rows,
+                                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * a10 -- GroupNorm statistics folded to a per-(sample, channel) affine.
