@@ -364,6 +364,139 @@ __global__ __launch_bounds__(256) void resize2d_windows_kernel(const float* __re
   }
 }
 
+// ---- emo_paste_windows_rgb8 (ABI 15): the inverse of resize2d_windows_kernel's crop -- the rendered S x S image of every frame,
+// resized to its window's side, feathered and blended into the frame's bytes in place (definition: include/emo_hip.h).
+
+// what a window must satisfy to be pasted (the entry point refuses a host-side list that fails it; the kernel leaves the frame of
+// a device-side window that fails it untouched): a square of side s inside the frame, downscaling by at most 4
+__host__ __device__ inline bool paste_window_ok(int x0, int y0, int w, int h, int S, int Hf, int Wf) {
+  return w > 0 && w == h && x0 >= 0 && y0 >= 0 && x0 <= Wf - w && y0 <= Hf - h && 4l * w >= S;
+}
+
+// ATen's antialiased bicubic filter (UpSampleKernel.cpp, _upsample_bicubic2d_aa: A = -0.5, support 2)
+__device__ __forceinline__ float cubic_aa(float x) {
+  x = fabsf(x);
+  return x < 1.0f ? cubic1(x, -0.5f) : (x < 2.0f ? cubic2(x, -0.5f) : 0.0f);
+}
+
+// One output index of an antialiased axis S -> s (ATen _compute_indices_min_size_weights_aa, align_corners=False, scale = S / s
+// >= 1): taps [lo, hi) around center = scale * (i + 0.5), tap j weighs cubic_aa((j - center + 0.5) / scale) / (their sum)
+struct AaTaps { int lo, hi; float center, inv_total; };
+__device__ __forceinline__ AaTaps aa_taps(int i, float scale, float inv_scale, int S) {
+  AaTaps t;
+  const float support = 2.0f * scale;
+  t.center = scale * ((float)i + 0.5f);
+  t.lo = (int)(t.center - support + 0.5f);
+  t.lo = t.lo < 0 ? 0 : t.lo;
+  t.hi = (int)(t.center + support + 0.5f);
+  t.hi = t.hi > S ? S : t.hi;
+  float total = 0.0f;
+  for (int j = t.lo; j < t.hi; ++j) total += cubic_aa(((float)j - t.center + 0.5f) * inv_scale);
+  t.inv_total = __fdiv_rn(1.0f, total);
+  return t;
+}
+
+// r[c] = clamp(R(img)[c, y, x], 0, 1) * 255 of one window pixel; im = the frame's [3,S,S] image.  s >= S: resize2d_at's bicubic;
+// s < S: the antialiased one, rows first (ATen resamples the width, then the height), ty = the taps of row y.  The weights are
+// evaluated where they are used (up to 17 x 17 taps at scale 4: no register arrays with run-time indices, i.e. no scratch).
+__device__ __forceinline__ void paste_render(const float* __restrict__ im, int S, int s, float scale, float inv_scale,
+                                             const AaTaps& ty, int y, int x, float r[3]) {
+  const long SS = (long)S * S;
+  if (s >= S) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c] = resize2d_at(im + c * SS, S, S, S, scale, scale, y, x, 1, 1) * 255.0f;
+    return;
+  }
+  const AaTaps tx = aa_taps(x, scale, inv_scale, S);
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  for (int yy = ty.lo; yy < ty.hi; ++yy) {
+    const float wy = cubic_aa(((float)yy - ty.center + 0.5f) * inv_scale) * ty.inv_total;
+    const float* p = im + (long)yy * S;
+    float row[3] = {0.0f, 0.0f, 0.0f};
+    for (int xx = tx.lo; xx < tx.hi; ++xx) {
+      const float wx = cubic_aa(((float)xx - tx.center + 0.5f) * inv_scale) * tx.inv_total;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) row[c] += wx * p[c * SS + xx];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += wy * row[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) r[c] = fminf(fmaxf(acc[c], 0.0f), 1.0f) * 255.0f;
+}
+
+// the blend weight of window pixel (y, x): the feather ramp from the window's edge (fs = feather * s; 1 where feather == 0) times
+// the matte resized to the window (bilinear, no antialias)
+__device__ __forceinline__ float paste_alpha(const float* __restrict__ mt, int S, int s, float scale, float feather, float fs,
+                                             int y, int x) {
+  float a = 1.0f;
+  if (feather > 0.0f) {
+    const float cy = (float)y + 0.5f, cx = (float)x + 0.5f;
+    const float d = fminf(fminf(cy, (float)s - cy), fminf(cx, (float)s - cx));
+    a = fminf(fmaxf(__fdiv_rn(d, fs), 0.0f), 1.0f);
+  }
+  if (mt) a = fminf(fmaxf(a * resize2d_at(mt, S, S, S, scale, scale, y, x, 0, 0), 0.0f), 1.0f);   // (a matte outside [0,1]: clipped)
+  return a;
+}
+
+// (1 - a) f + a r, truncated like pack_rgb8_kernel: a == 1 gives pack_rgb8's byte, a == 0 the frame's, both exactly
+__device__ __forceinline__ unsigned paste_blend(float a, unsigned f, float r) { return (unsigned)(uint8_t)((1.0f - a) * (float)f + a * r); }
+
+// Work items: (frame, window row, run of 4 pixels), grid-stride over N * smax rows * Q runs with smax a host-known bound of the
+// window sides -- the windows themselves are only read on the device.  A pixel is 3 bytes and a window's x0 is arbitrary, so the
+// runs of a row start at its first pixel whose byte address is a multiple of 4 (`head` = address & 3 pixels in: 3 * head = -head
+// mod 4): a run inside the row is 12 bytes = three aligned dwords, read and written as such; run 0 is the head in front of that
+// pixel and the last run the tail, byte by byte.  No byte outside the window is read or written, and no two items share a dword.
+__global__ __launch_bounds__(256) void paste_windows_kernel(const float* __restrict__ img, const float* __restrict__ matte,
+                                                            const int* __restrict__ win, uint8_t* __restrict__ frames,
+                                                            unsigned total, int S, int Hf, int Wf, unsigned smax, float feather) {
+  const unsigned Q = (smax + 3u) / 4u + 1u;
+  const long SS = (long)S * S;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const unsigned q = i % Q, rr = i / Q;
+    const int y = (int)(rr % smax);
+    const long n = rr / smax;
+    const int* const w4 = win + 4 * n;
+    const int wx0 = w4[0], wy0 = w4[1], s = w4[2];
+    if (!paste_window_ok(wx0, wy0, s, w4[3], S, Hf, Wf) || y >= s) continue;
+    uint8_t* const row = frames + ((n * Hf + wy0 + y) * Wf + wx0) * 3;
+    const int head = (int)(reinterpret_cast<uintptr_t>(row) & 3);
+    const int xa = head + 4 * ((int)q - 1);
+    if (xa >= s) continue;
+    const float scale = (float)S / (float)s, inv_scale = __fdiv_rn(1.0f, scale), fs = feather * (float)s;
+    const float* const im = img + n * 3 * SS;
+    const float* const mt = matte ? matte + n * SS : nullptr;
+    AaTaps ty = {0, 0, 0.0f, 0.0f};
+    if (s < S) ty = aa_taps(y, scale, inv_scale, S);
+    if (xa >= 0 && xa + 4 <= s) {
+      uint32_t* const dw = reinterpret_cast<uint32_t*>(row + 3 * xa);
+      const uint32_t f[3] = {dw[0], dw[1], dw[2]};
+      uint32_t o[3] = {0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float r[3];
+        paste_render(im, S, s, scale, inv_scale, ty, y, xa + j, r);
+        const float a = paste_alpha(mt, S, s, scale, feather, fs, y, xa + j);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int k = 3 * j + c;
+          o[k >> 2] |= paste_blend(a, (f[k >> 2] >> (8 * (k & 3))) & 255u, r[c]) << (8 * (k & 3));
+        }
+      }
+      dw[0] = o[0]; dw[1] = o[1]; dw[2] = o[2];
+    } else {
+      const int xe = xa + 4 < s ? xa + 4 : s;
+      for (int x = xa < 0 ? 0 : xa; x < xe; ++x) {
+        float r[3];
+        paste_render(im, S, s, scale, inv_scale, ty, y, x, r);
+        const float a = paste_alpha(mt, S, s, scale, feather, fs, y, x);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) row[3 * x + c] = (uint8_t)paste_blend(a, row[3 * x + c], r[c]);
+      }
+    }
+  }
+}
+
 // stage-2 glue (notebooks/infer_s2.py:365-375)
 __global__ __launch_bounds__(256) void mul_mask_kernel(const float* __restrict__ img, const float* __restrict__ mask,
                                                        float* __restrict__ out, long N, int C, long HW) {
@@ -504,5 +637,26 @@ extern "C" int emo_resize2d_windows_f32(const float* x, int64_t plane_stride, in
   if (!x || !out || !windows || N <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || row_stride <= 0 || plane_stride < 0) return EMO_ERR_BAD_ARG;
   hipLaunchKernelGGL(resize2d_windows_kernel, dim3(grid_for((long)N * C * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, x,
                      (long)plane_stride, (long)row_stride, windows, out, (long)N, C, Ho, Wo, bicubic, clamp01);
+  return emo_launch_status();
+}
+
+extern "C" int emo_paste_windows_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                                      uint8_t* frames, int N, int S, int Hf, int Wf, float feather, void* stream) {
+  if (!img || !windows || !frames || N <= 0 || S <= 0 || Hf <= 0 || Wf <= 0) return EMO_ERR_BAD_ARG;
+  if (!(feather >= 0.0f && feather <= 0.5f)) return EMO_ERR_BAD_ARG;
+  int smax = Hf < Wf ? Hf : Wf;                    // windows that only the device knows: any valid side
+  if (windows_host) {
+    smax = 0;
+    for (int n = 0; n < N; ++n) {
+      const int32_t* w = windows_host + 4 * n;
+      if (w[2] <= 0 || w[3] <= 0 || w[0] < 0 || w[1] < 0 || w[0] > Wf - w[2] || w[1] > Hf - w[3]) return EMO_ERR_BAD_ARG;
+      if (!paste_window_ok(w[0], w[1], w[2], w[3], S, Hf, Wf)) return EMO_ERR_UNSUPPORTED;   // not square, or 4 s < S
+      smax = w[2] > smax ? w[2] : smax;
+    }
+  }
+  const long total = (long)N * smax * ((smax + 3) / 4 + 1);
+  if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(paste_windows_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frames,
+                     (unsigned)total, S, Hf, Wf, (unsigned)smax, feather);
   return emo_launch_status();
 }

@@ -871,8 +871,50 @@ class InferenceWrapper:
             yield b0, (ops.pack_rgb8(img) if as_uint8 else img)
 
     # ------------------------------------------------------------------------------------------------------
+    def _paste_matte(self, paste_matte, what):
+        """paste_matte -> None | callable img [b,3,S,S] -> [b,1,S,S]  (True: embedders['matting']; a tensor: itself, for the one
+        batch it belongs to)"""
+        if paste_matte is None or paste_matte is False:
+            return None
+        if paste_matte is True:
+            return self._need('matting', what)
+        if isinstance(paste_matte, torch.Tensor):
+            return lambda img: paste_matte
+        if not callable(paste_matte):
+            raise ValueError("paste_matte: None, True (embedders['matting']) or a callable img [b,3,S,S] -> [b,1,S,S]")
+        return paste_matte
+
+    @staticmethod
+    def _paste_windows(windows):
+        """(x_lo, y_lo, side) per frame, as animate_frames takes them (a fourth entry must repeat the side) -> (x0, y0, s, s)"""
+        out = []
+        for w in windows:
+            w = [int(v) for v in w]
+            if len(w) not in (3, 4) or (len(w) == 4 and w[3] != w[2]):
+                raise ValueError(f"paste window {tuple(w)}: expected (x_lo, y_lo, side)")
+            out.append((w[0], w[1], w[2], w[2]))
+        return out
+
+    def paste_back(self, frames_u8, rendered, windows, feather=0.0625, matte=None):
+        """The inverse of the crop: `rendered` [N,3,S,S] fp32 (the hot path's image, before emo_pack_rgb8) goes back into the
+        frames the crops came from, frame i where its window windows[i] = (x_lo, y_lo, side) was -- resized to side x side
+        (bicubic; antialiased when that shrinks it, down to S / 4), blended over the frame with a feathered edge of
+        feather * side pixels and, if given, a matte ([N,1,S,S] in [0,1], a callable img -> matte, or True =
+        embedders['matting']).  One launch (ops.paste_windows / emo_paste_windows_rgb8).
+        frames_u8: uint8 [N,Hf,Wf,3], host or device; it is NOT modified (a host tensor is uploaded, a device tensor cloned).
+        Returns the device uint8 [N,Hf,Wf,3].  feather = 1/16 of the window is a taste default, not a measured optimum."""
+        if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+            raise ValueError("frames must be uint8 [N,H,W,3]")
+        fn = self._paste_matte(matte, 'matte=True')
+        wins = windows if isinstance(windows, torch.Tensor) and windows.is_cuda else self._paste_windows(windows)
+        img = rendered.to(self.device).float().contiguous()
+        m = None if fn is None else fn(img).to(self.device).float().contiguous()
+        full = frames_u8.to(self.device, copy=True).contiguous()
+        return ops.paste_windows(full, img, wins, feather, m)
+
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
-                       mix=False, mix_old=True, target_theta=True, smooth_per_identity=False):
+                       mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
+                       paste_matte=None, as_uint8=True):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  frames: uint8 [N,H,W,3] tensor (host, ideally pinned, or device) or an iterable of such chunks --
         decoded video frames, uploaded as BYTES.  Per batch, all on the device and without a host synchronisation:
@@ -898,7 +940,32 @@ class InferenceWrapper:
         theta -> mix -> smooth_pose -> expression embedder -> render (with the source theta if target_theta=False).  With
         identities, smooth_pose needs smooth_per_identity=True (else ValueError): each frame is then smoothed within its own
         identity's frame sequence, as if every identity had its own wrapper: one stream per slot, scanned on the device (ops.theta_ema_scan) over the whole gathered chunk on every rank, so
-        the slot states stay identical across ranks; store_identity / drop_identity / reset_pose_state reset a slot's stream."""
+        the slot states stay identical across ranks; store_identity / drop_identity / reset_pose_state reset a slot's stream.
+        paste_back=True: frames in -> FRAMES out.  Each batch's rendered fp32 image goes back into the batch's uploaded frame bytes
+        where the crop windows were (paste_back(); one launch, emo_paste_windows_rgb8, in place of emo_pack_rgb8) and what is
+        yielded is (first_frame_index, uint8 [b,Hf,Wf,3]); the pinned ring then holds full frames (a chunk of another frame size
+        gets a new ring).  Needs `windows` (ValueError otherwise, before anything is launched), sides >= image_size / 4.  A host
+        chunk's device copy is private and is pasted into in place; a device-resident chunk is cloned span by span: the caller's
+        frames stay untouched.  With smooth_pose the head-pose pass keeps crops, not frames, so the render pass uploads the
+        spans of a host chunk once more.  feather: width of the blended edge as a fraction of the window side (1/16: a taste
+        default, not a measured optimum); paste_matte: None, a callable img [b,3,S,S] -> [b,1,S,S] in [0,1], or True =
+        embedders['matting'].  Each rank pastes its own shard: no collective.
+        as_uint8=False (with to_host=False, without paste_back): the fp32 [b,3,S,S] device image itself, as animate() yields it
+        -- what paste_back() takes as `rendered` (with captured graphs it is the graph's output buffer: consume or clone it
+        before resuming the generator)."""
+        matte_fn = None
+        if not as_uint8 and (to_host or paste_back):
+            raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
+        if paste_back:
+            if windows is None:
+                raise ValueError("paste_back=True needs windows=: one (x_lo, y_lo, side) per frame says where each rendered crop goes")
+            if not 0.0 <= float(feather) <= 0.5:
+                raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
+            matte_fn = self._paste_matte(paste_matte, 'paste_matte=True')
+            paste_wins = self._paste_windows(windows)
+            if any(4 * w[2] < self.cfg["image_size"] for w in paste_wins):
+                raise ValueError(f"a paste window is smaller than a quarter of the {self.cfg['image_size']}-pixel image: downscaling "
+                                 f"stops at image_size / 4")
         ids = None
         self._check_smoothing(identities, smooth_pose, smooth_per_identity)
         if identities is not None:
@@ -981,15 +1048,17 @@ class InferenceWrapper:
                     local = self._pose_controls(local, ids_dev, True, mix_old, False)
                 every = parallel.gather_shards(local, n, self.rank, self.world)        # [n,4,4] on every rank, frame order
                 smoothed = self._pose_controls(every, ids_chunk, False, mix_old, True)[lo:hi]
-            # (every span whose crops stayed resident from the head-pose pass needs no second upload)
-            todo = [sp for sp in spans if sp[0] not in kept]
+            # (every span whose crops stayed resident from the head-pose pass needs no second upload -- unless its frames are
+            # what the render is pasted into: the crops were kept, 3 MB per frame, not the frames, 6 MB at 1080p)
+            todo = spans if paste_back else [sp for sp in spans if sp[0] not in kept]
             fresh = uploaded(chunk, todo)
             for b0, b1 in spans:
                 crops = kept.pop(b0, None)
-                if crops is None:
+                if crops is None or paste_back:
                     f0, f1, u8 = next(fresh)
                     assert (f0, f1) == (b0, b1)
-                    crops = crops_of(u8, base, b0, b1)
+                    if crops is None:
+                        crops = crops_of(u8, base, b0, b1)
                 ident = None if ids is None else ids_dev[b0 - lo:b1 - lo]
                 if smoothed is not None:
                     theta = smoothed[b0 - lo:b1 - lo]
@@ -1001,12 +1070,21 @@ class InferenceWrapper:
                 pose, _ = self._expression(crops, theta, 'a driver call')
                 theta = self._render_theta(theta, ident, target_theta)
                 img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ident)
-                out = ops.pack_rgb8(img)
+                if paste_back:
+                    full = u8.clone() if chunk.is_cuda else u8                   # (a host chunk's upload is this span's own)
+                    out = ops.paste_windows(full, img, paste_wins[base + b0:base + b1], feather,
+                                            None if matte_fn is None else matte_fn(img).float().contiguous())
+                else:
+                    out = ops.pack_rgb8(img) if as_uint8 else img
                 if not to_host:
                     yield base + b0, out
                     continue
+                if slots and slots[0].shape[1:] != out.shape[1:]:                # full frames of another size: a new ring
+                    yield from drain(0)
+                    slots.clear()
+                    k = 0
                 if len(slots) < ring:
-                    slots.append(torch.empty((batch_size, S, S, 3), dtype=torch.uint8, pin_memory=True))
+                    slots.append(torch.empty((batch_size,) + tuple(out.shape[1:]), dtype=torch.uint8, pin_memory=True))
                 slot = k % ring
                 k += 1
                 copy_stream.wait_stream(torch.cuda.current_stream())

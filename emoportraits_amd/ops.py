@@ -696,6 +696,51 @@ def resize2d_windows(x, size, windows, mode="bicubic", clamp01=False):
     return out
 
 
+def paste_windows(frames_u8, img, windows, feather=0.0, matte=None):
+    """The inverse of resize2d_windows' crop, in ONE launch and IN PLACE: img [N,3,S,S] fp32 (the renderer's output) goes back
+    into frames_u8 [N,Hf,Wf,3] uint8 where each frame's SQUARE window (x0, y0, s, s) was -- bicubic resize to (s, s)
+    (antialiased where s < S), clamp(0,1) * 255, blended as (1 - a) * frame + a * image and truncated like pack_rgb8, with a =
+    the feather ramp of width feather * s from the window's edge (1 where feather == 0) times `matte` [N,1,S,S] in [0,1]
+    resized bilinearly (include/emo_hip.h has the definition).  windows = one (x0, y0, w, h) per frame: a host sequence
+    (checked and uploaded here: inside the frame, square, s >= S / 4) or an int32 [N,4] device tensor (trusted: the kernel
+    leaves the frame of a window that fails those checks untouched).  Bytes outside the windows are neither read nor written.
+    Returns frames_u8."""
+    lib = hip.load()
+    hip.require_cuda_f32(img, matte)
+    if frames_u8.device != img.device or frames_u8.dtype != torch.uint8 or not frames_u8.is_contiguous() or frames_u8.dim() != 4:
+        raise RuntimeError("paste_windows expects a contiguous uint8 tensor [N,H,W,3] on the images' device")
+    N, Hf, Wf, C = frames_u8.shape
+    if C != 3 or img.dim() != 4 or img.shape[0] != N or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
+        raise ValueError(f"frames {tuple(frames_u8.shape)} and images {tuple(img.shape)}: expected [N,Hf,Wf,3] and [N,3,S,S]")
+    S = img.shape[2]
+    if matte is not None and tuple(matte.shape) != (N, 1, S, S):
+        raise ValueError(f"matte {tuple(matte.shape)}: expected {(N, 1, S, S)}")
+    if not 0.0 <= float(feather) <= 0.5:
+        raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
+    host = None
+    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+        win = windows
+        if win.device != img.device or win.dtype != torch.int32 or tuple(win.shape) != (N, 4) or not win.is_contiguous():
+            raise RuntimeError("windows must be a contiguous int32 cuda tensor [N,4]")
+    else:
+        host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
+        if host.shape[0] != N:
+            raise ValueError(f"{host.shape[0]} windows for {N} frames")
+        lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
+        if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi[:, 0] <= Wf).all()) and bool((hi[:, 1] <= Hf).all())):
+            raise ValueError(f"a paste window is not inside the {Wf}x{Hf} frame")
+        if not bool((host[:, 2] == host[:, 3]).all()):
+            raise ValueError("paste windows must be square")
+        if not bool((4 * host[:, 2] >= S).all()):
+            raise ValueError(f"a paste window is smaller than a quarter of the {S}x{S} image: downscaling stops at S / 4")
+        win = host.to(frames_u8.device, non_blocking=True)
+    if N == 0:
+        return frames_u8
+    hip.check(lib.emo_paste_windows_rgb8(hip.ptr(img), hip.ptr(matte), hip.ptr(win), hip.ptr(host), hip.ptr(frames_u8), N, S, Hf, Wf,
+                                         float(feather), hip.current_stream()), "emo_paste_windows_rgb8")
+    return frames_u8
+
+
 def device_cu_count():
     """compute units of the current device as the C launchers count them (include/emo_hip.h, ABI 9)"""
     return hip.load().emo_device_cu_count()

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 14
+#define EMO_ABI_VERSION 15
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -458,6 +458,26 @@ int emo_theta_ema_scan_f32(const float* values, const int32_t* stream_of, float*
                            float om, float* out, void* stream);
 int emo_pack_rgb8(const float* img, uint8_t* out, int N, int H, int W, void* stream);
 int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int W, void* stream);
+
+/* ABI 15.  The inverse of the crop of emo_resize2d_windows_f32: the rendered S x S image of every frame goes back into that
+ * frame's bytes, where its crop window was.  One launch per batch, frames updated IN PLACE inside the windows only: a byte
+ * outside its frame's window is neither read nor written.
+ *   img [N,3,S,S] fp32 (any range); matte [N,1,S,S] fp32 in [0,1] or NULL; windows N x (x0, y0, w, h) int32, DEVICE memory;
+ *   windows_host the same N x 4 values in HOST memory, or NULL; frames [N,Hf,Wf,3] uint8; 0 <= feather <= 0.5.
+ * Frame n, window (x0, y0, s, s), every pixel (y, x) with 0 <= y, x < s, every channel c:
+ *   r   = clamp(R(img[n])[c, y, x], 0, 1) * 255, R = F.interpolate(size=(s, s), mode='bicubic', align_corners=False,
+ *         antialias=(s < S)): for s >= S the arithmetic of emo_resize2d_f32 (A = -0.75); for s < S ATen's separable antialiased
+ *         bicubic (A = -0.5, scale = S / s, taps within 2 * scale of scale * (i + 0.5), weights normalised by their sum)
+ *   a   = clamp(min(d(y), d(x)) / (feather * s), 0, 1), d(i) = min(i + 0.5, s - (i + 0.5)); 1 where feather == 0; times the
+ *         matte resized to (s, s) (bilinear, align_corners=False, no antialias: emo_resize2d_f32's) where one is given
+ *   out = (uint8)((1 - a) * f + a * r), f the frame's byte: truncation, as emo_pack_rgb8.  In this form a == 1 gives
+ *         emo_pack_rgb8's byte and a == 0 the frame's byte, exactly.
+ * With windows_host, every window is checked before anything is launched: w or h <= 0 or a window that leaves the frame is
+ * EMO_ERR_BAD_ARG, w != h or 4 * s < S (downscaling by more than 4) EMO_ERR_UNSUPPORTED, and the grid covers the largest side.
+ * Without it (windows that only exist on the device) the grid covers min(Hf, Wf), and a frame whose device-side window fails
+ * one of those checks is left untouched by the kernel: nothing is ever written outside a frame or outside a valid window. */
+int emo_paste_windows_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                           uint8_t* frames, int N, int S, int Hf, int Wf, float feather, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@
         --source source.png --frames <dir of PNG/JPG frames | frames.npy (uint8 [N,H,W,3])> --out <dir> [--batch 16]
         [--windows windows.json]   # optional per-frame crop windows [[x_lo, y_lo, side], ...] from a face detector
         [--mix [--mix-new]] [--source-pose] [--smooth-pose]   # forward()'s pose controls (mix, mix_old=False, target_theta=False)
+        [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
 
 Frame I/O is host work (PIL / numpy): decoded frames are handed to InferenceWrapper.animate_frames as uint8 chunks in pinned
 memory; crop, bicubic resize, both embedders, the hot path and the uint8 packing run on the GPU without a host sync, and
@@ -56,6 +57,8 @@ def main():
     ap.add_argument("--mix-new", action="store_true", help="with --mix: the reference's mix_old=False formula")
     ap.add_argument("--source-pose", action="store_true", help="render in the source's own head pose (target_theta=False)")
     ap.add_argument("--smooth-pose", action="store_true", help="EMA over the driver head poses (smooth_pose=True)")
+    ap.add_argument("--paste-back", action="store_true", help="write the full frames with the rendered crop pasted back (needs --windows)")
+    ap.add_argument("--feather", type=float, default=0.0625, help="with --paste-back: blended edge as a fraction of the window side")
     a = ap.parse_args()
     from PIL import Image
     from notebooks.infer import InferenceWrapper
@@ -71,7 +74,8 @@ def main():
     t0, n = time.perf_counter(), 0
     frames = load_frames(a.frames, 8 * a.batch)
     for first, u8 in w.animate_frames(frames, batch_size=a.batch, windows=windows, mix=a.mix, mix_old=not a.mix_new,
-                                      target_theta=not a.source_pose, smooth_pose=a.smooth_pose):
+                                      target_theta=not a.source_pose, smooth_pose=a.smooth_pose, paste_back=a.paste_back,
+                                      feather=a.feather):
         arr = u8.numpy()
         for j in range(arr.shape[0]):
             Image.fromarray(arr[j]).save(os.path.join(a.out, f"{first + j:06d}.png"))
