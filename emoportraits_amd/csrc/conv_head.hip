@@ -12,6 +12,12 @@
 // Arithmetic per output: acc = fma(w[o][c], relu(fma(x, scale, shift)), acc) for c = 0 .. Cin-1 in order, + bias, activation --
 // the operations of the implicit-GEMM kernel's staging and epilogue with a sequential fp32 sum over the channels in place of
 // the MFMA's blocked one (held to the same bounds against the oracle: tests/test_kernels_gpu.py, test_bench_config_parity_gpu.py).
+//
+// The same channel walk with another epilogue is the tail of stage 2 (emo_stage2_head_f32, ABI 16): norm -> ReLU -> 1x1 conv
+// 32 -> 3 -> tanh at the full resolution (decoder_s2_old.py:444-456), the residual added to the stage-1 image under the
+// matte x face mask, clamped (notebooks/infer_s2.py:365-375) and written as fp32 planes and / or as the HWC bytes of
+// pack_rgb8_kernel -- one launch where the chain emo_conv_head_f32(tanh) -> emo_stage2_compose_f32 -> emo_pack_rgb8 is three,
+// with the same operations in the same order: bit-identical to that chain in both outputs.
 #include "common.h"
 
 namespace {
@@ -23,11 +29,21 @@ __device__ __forceinline__ float head_act(float v, int act) {
   return v;
 }
 
-template <int COUT>
+// what the stage-2 epilogue reads and writes beside the convolution's own operands (unused by the plain head)
+struct Stage2Tail {
+  const float* img;        // [N,3,S]
+  const float* mask;       // [N,1,S]
+  const float* face_mask;  // [N,1,S] or NULL (= 1)
+  uint8_t* out_u8;         // [N,S,3] or NULL
+};
+
+// STAGE2 = false: out = act(acc + bias), COUT planes.  true (COUT == 3, act == tanh): out = clamp(img + tanh(acc + bias) *
+// (mask * face_mask), 0, 1) into `out` (fp32 planes, may be NULL) and tail.out_u8 (bytes, may be NULL)
+template <int COUT, bool STAGE2>
 __global__ __launch_bounds__(256) void conv_head_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ bias, const float* __restrict__ scale,
                                                         const float* __restrict__ shift, float* __restrict__ out, int Cin,
-                                                        long S, int relu_in, int act) {
+                                                        long S, int relu_in, int act, Stage2Tail tail) {
   const int n = blockIdx.y;
   const long q = (long)blockIdx.x * 256 + threadIdx.x;          // quad of positions
   if (4 * q >= S) return;
@@ -82,12 +98,58 @@ __global__ __launch_bounds__(256) void conv_head_kernel(const float* __restrict_
       for (int j = 0; j < 4; ++j) acc[o][j] = __fmaf_rn(wv, e[j], acc[o][j]);
     }
   }
-  float4* op = reinterpret_cast<float4*>(out + (long)n * COUT * S) + q;
+  if constexpr (!STAGE2) {
+    float4* op = reinterpret_cast<float4*>(out + (long)n * COUT * S) + q;
 #pragma unroll
-  for (int o = 0; o < COUT; ++o) {
-    const float b = bias ? bias[o] : 0.0f;
-    op[(long)o * S4] = make_float4(head_act(acc[o][0] + b, act), head_act(acc[o][1] + b, act), head_act(acc[o][2] + b, act),
-                                   head_act(acc[o][3] + b, act));
+    for (int o = 0; o < COUT; ++o) {
+      const float b = bias ? bias[o] : 0.0f;
+      op[(long)o * S4] = make_float4(head_act(acc[o][0] + b, act), head_act(acc[o][1] + b, act), head_act(acc[o][2] + b, act),
+                                     head_act(acc[o][3] + b, act));
+    }
+  } else {
+    static_assert(!STAGE2 || COUT == 3, "the stage-2 tail writes an RGB image");
+    // the operations of stage2_compose_kernel and pack_rgb8_kernel, each rounded on its own (the build's -ffp-contract=off)
+    const float4 m4 = reinterpret_cast<const float4*>(tail.mask + (long)n * S)[q];
+    float gate[4] = {m4.x, m4.y, m4.z, m4.w};
+    if (tail.face_mask) {
+      const float4 f4 = reinterpret_cast<const float4*>(tail.face_mask + (long)n * S)[q];
+      gate[0] = gate[0] * f4.x; gate[1] = gate[1] * f4.y; gate[2] = gate[2] * f4.z; gate[3] = gate[3] * f4.w;
+    }
+    const float4* ip = reinterpret_cast<const float4*>(tail.img + (long)n * COUT * S) + q;
+    float4 im[COUT];
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) im[o] = ip[(long)o * S4];
+    float v[COUT][4];
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) {
+      const float b = bias ? bias[o] : 0.0f;
+      const float i4[4] = {im[o].x, im[o].y, im[o].z, im[o].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float t = i4[j] + head_act(acc[o][j] + b, EMO_ACT_TANH) * gate[j];
+        v[o][j] = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+      }
+    }
+    if (out) {
+      float4* op = reinterpret_cast<float4*>(out + (long)n * COUT * S) + q;
+#pragma unroll
+      for (int o = 0; o < COUT; ++o) op[(long)o * S4] = make_float4(v[o][0], v[o][1], v[o][2], v[o][3]);
+    }
+    if (tail.out_u8) {
+      // four pixels x RGB = 12 bytes at a 4-byte aligned address (S % 4 == 0): three dwords, byte k of the run in bits 8 (k % 4)
+      uint32_t d[3] = {0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) {
+          const int k = j * 3 + o;
+          d[k >> 2] |= (uint32_t)(uint8_t)(v[o][j] * 255.0f) << (8 * (k & 3));
+        }
+      uint32_t* bp = reinterpret_cast<uint32_t*>(tail.out_u8 + ((long)n * S + 4 * q) * 3);
+      bp[0] = d[0];
+      bp[1] = d[1];
+      bp[2] = d[2];
+    }
   }
 }
 
@@ -108,11 +170,35 @@ extern "C" int emo_conv_head_f32(const float* x, const float* w, const float* bi
   if (blocks > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)blocks, (unsigned)N);
   hipStream_t s = (hipStream_t)stream;
+  const Stage2Tail none = {nullptr, nullptr, nullptr, nullptr};
   switch (Cout) {
-    case 1: hipLaunchKernelGGL(conv_head_kernel<1>, grid, dim3(256), 0, s, x, w, bias, scale, shift, out, Cin, (long)S, relu_in, act); break;
-    case 2: hipLaunchKernelGGL(conv_head_kernel<2>, grid, dim3(256), 0, s, x, w, bias, scale, shift, out, Cin, (long)S, relu_in, act); break;
-    case 3: hipLaunchKernelGGL(conv_head_kernel<3>, grid, dim3(256), 0, s, x, w, bias, scale, shift, out, Cin, (long)S, relu_in, act); break;
-    default: hipLaunchKernelGGL(conv_head_kernel<4>, grid, dim3(256), 0, s, x, w, bias, scale, shift, out, Cin, (long)S, relu_in, act); break;
+    case 1: hipLaunchKernelGGL((conv_head_kernel<1, false>), grid, dim3(256), 0, s, x, w, bias, scale, shift, out, Cin, (long)S, relu_in, act, none); break;
+    case 2: hipLaunchKernelGGL((conv_head_kernel<2, false>), grid, dim3(256), 0, s, x, w, bias, scale, shift, out, Cin, (long)S, relu_in, act, none); break;
+    case 3: hipLaunchKernelGGL((conv_head_kernel<3, false>), grid, dim3(256), 0, s, x, w, bias, scale, shift, out, Cin, (long)S, relu_in, act, none); break;
+    default: hipLaunchKernelGGL((conv_head_kernel<4, false>), grid, dim3(256), 0, s, x, w, bias, scale, shift, out, Cin, (long)S, relu_in, act, none); break;
   }
+  return emo_launch_status();
+}
+
+// ABI 16.  The tail of stage 2 in one launch (include/emo_hip.h has the definition):
+//   out = clamp(img + tanh(bias + sum_c w[o][c] * in(x[n][c][p])) * (mask * face_mask), 0, 1),  3 output channels
+// x [N, Cin, S], w [3][Cin] plain row-major, img [N,3,S], mask [N,1,S], face_mask [N,1,S] or NULL (= 1), out_f32 [N,3,S] or NULL,
+// out_u8 [N,S,3] or NULL (at least one of the two).  Refusals as emo_conv_head_f32; out_u8 4-byte aligned.
+extern "C" int emo_stage2_head_f32(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
+                                   const float* img, const float* mask, const float* face_mask, float* out_f32, uint8_t* out_u8,
+                                   int N, int Cin, int64_t S, int relu_in, void* stream) {
+  if (!x || !w || !img || !mask || N <= 0 || Cin <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
+  if (!out_f32 && !out_u8) return EMO_ERR_BAD_ARG;
+  if ((scale == nullptr) != (shift == nullptr)) return EMO_ERR_BAD_ARG;
+  if ((S & 3) || N > 65535) return EMO_ERR_UNSUPPORTED;
+  const uintptr_t quads = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(mask) |
+                          reinterpret_cast<uintptr_t>(face_mask) | reinterpret_cast<uintptr_t>(out_f32);
+  if ((quads & 15) != 0 || (reinterpret_cast<uintptr_t>(out_u8) & 3) != 0) return EMO_ERR_ALIGN;
+  const long blocks = (S / 4 + 255) / 256;
+  if (blocks > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)blocks, (unsigned)N);
+  const Stage2Tail tail = {img, mask, face_mask, out_u8};
+  hipLaunchKernelGGL((conv_head_kernel<3, true>), grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, scale, shift, out_f32, Cin,
+                     (long)S, relu_in, EMO_ACT_TANH, tail);
   return emo_launch_status();
 }

@@ -153,7 +153,7 @@ class InferenceWrapper:
         self.use_graphs = bool(use_graphs)
         self._graphed = {}
         if self.use_graphs:
-            first = 0 if use_graphs == 'capture_first' else 1
+            first = self._graph_eager_calls = 0 if use_graphs == 'capture_first' else 1
             self._graphed['driver'] = graphs.Graphed(
                 lambda pose, theta: self.hot_path.driver_pass(self._canonical_cl, self.idt_embed, pose, theta), eager_calls=first)
             if identity_capacity > 0:
@@ -184,6 +184,7 @@ class InferenceWrapper:
         self._canonical_cl = None
         self._crop_tracker = None
         self._init_identity_bank(int(identity_capacity))
+        self._stage2 = self._stage2_wrapper = None                                 # attach_stage2()
 
     # ------------------------------------------------------------------------------------------------------
     def _native_embedders(self, found, head_pose_regressor_path):
@@ -513,6 +514,77 @@ class InferenceWrapper:
             self._slot(int(k))
         return ids.to(torch.int32)
 
+    # ---- stage 2 in the video path -----------------------------------------------------------------------------------
+    def attach_stage2(self, stage2):
+        """Give animate() / animate_frames() the refinement model their refine=True runs after every rendered batch: a
+        stage2.InferenceWrapper (its 'matting' / 'face_parsing' embedders and its `cloth` flag then supply the masks, as in its
+        own forward()) or a bare stage2.Stage2 (masks from refine_masks=); None detaches.  With use_graphs the stage-2 pass
+        (Stage2.refine_frames) is captured per batch shape under the policy of the stage-1 sequences: first call of a shape
+        eager, second captured, later ones replayed.  The mask callables are third-party nets and always run eagerly, between
+        the two graphs.  In the 'f16x2' mode a stage-2 pass clears the device's range-check words, so ops.overflow_events() of
+        the stage-1 pass of the same batch is gone once the batch is yielded."""
+        from . import stage2 as s2
+        for k in ('stage2_u8', 'stage2_f32'):
+            self._graphed.pop(k, None)
+        self._stage2 = self._stage2_wrapper = None
+        if stage2 is None:
+            return
+        model = stage2.model_two if isinstance(stage2, s2.InferenceWrapper) else stage2
+        if not isinstance(model, s2.Stage2):
+            raise TypeError("attach_stage2 takes a stage2.InferenceWrapper, a stage2.Stage2 or None")
+        self._stage2 = model
+        self._stage2_wrapper = stage2 if model is not stage2 else None
+        if getattr(self, 'use_graphs', False):
+            first = getattr(self, '_graph_eager_calls', 1)
+            for out in ('u8', 'f32'):
+                self._graphed['stage2_' + out] = graphs.Graphed(
+                    lambda img, mask, face, out=out: model.refine_frames(img, mask, face, out), eager_calls=first)
+
+    def _refine_plan(self, refine, refine_masks):
+        """the checks of refine=True, before anything is launched -> None (no refinement) or the callable img [b,3,S2,S2] ->
+        (mask, face_mask) that serves the masks of a batch"""
+        if not refine:
+            if refine_masks is not None:
+                raise ValueError("refine_masks= belongs to refine=True")
+            return None
+        model = getattr(self, '_stage2', None)
+        if model is None:
+            raise ValueError("refine=True needs a stage-2 model: attach_stage2(stage2.InferenceWrapper(...)) first")
+        if torch.device(model.device) != torch.device(self.device):
+            raise ValueError(f"the attached stage-2 model is on {model.device}, this wrapper renders on {self.device}")
+        if refine_masks is not None:
+            if not callable(refine_masks):
+                raise ValueError("refine_masks: a callable img [b,3,S2,S2] -> (mask [b,1,S2,S2], face_mask [b,1,S2,S2])")
+            return refine_masks
+        w2 = self._stage2_wrapper
+        emb = {} if w2 is None else w2.embedders
+        cloth = bool(w2 is not None and w2.cloth)
+        for name in ('matting',) if cloth else ('matting', 'face_parsing'):
+            if not callable(emb.get(name)):
+                raise ValueError(f"refine=True needs the '{name}' callable of the attached stage-2 wrapper "
+                                 f"(stage2.InferenceWrapper(embedders={{'{name}': fn}})) or refine_masks=")
+        matting, parsing = emb['matting'], emb.get('face_parsing')
+
+        def masks_of(img):                                                       # stage2.InferenceWrapper.forward's choice
+            mask = matting(img)
+            return mask, (torch.ones_like(mask) if cloth else parsing(img))      # infer_s2.py:366-368
+        return masks_of
+
+    def _refine(self, img, masks_of, out):
+        """stage 1's image of a batch -> the refined batch: bilinear resize to output_size_s2 where the sizes differ
+        (infer_s2.py:360-362), the mask callables (eager), the stage-2 pass (captured with use_graphs).  out 'u8' | 'f32'"""
+        model = self._stage2
+        S2 = model.cfg["output_size_s2"]
+        if img.shape[-1] != S2 or img.shape[-2] != S2:
+            img = ops.resize2d(img, (S2, S2), "bilinear")
+        mask, face = masks_of(img)
+        mask = mask.to(self.device).float().contiguous()
+        face = face.to(self.device).float().contiguous()
+        g = self._graphed.get('stage2_' + out)
+        if g is not None:
+            return g(img, mask, face)
+        return model.refine_frames(img, mask, face, out)
+
     def _drive_bank(self, pose, theta, ident):
         g = self._graphed.get('driver_bank')
         if g is not None:
@@ -822,7 +894,7 @@ class InferenceWrapper:
 
     # ------------------------------------------------------------------------------------------------------
     def animate(self, target_pose_embeds, target_srt, batch_size=16, as_uint8=True, identities=None, mix=False, mix_old=True,
-                target_theta=True, smooth_pose=False, smooth_per_identity=False):
+                target_theta=True, smooth_pose=False, smooth_per_identity=False, refine=False, refine_masks=None):
         """1 source -> N driver frames (the BASELINE metric).  Frames are sharded contiguously across ranks
         (SURVEY.md section 8e); each rank walks its shard in batches of `batch_size`.  Yields (first_frame_index, frames)
         with frames a uint8 [B,H,W,3] (or fp32 [B,3,H,W]) DEVICE tensor -- no host sync inside the loop.
@@ -833,7 +905,10 @@ class InferenceWrapper:
         renders in that identity's own head pose.  smooth_pose is a scan over the FRAME ORDER: every rank forms the thetas of
         the whole stream from target_srt (16 floats per frame) and scans them, then renders its own slice -- 1 rank and N ranks
         give the same frames.  Without identities the state is `self.theta` (carried from call to call, as in forward); with
-        them, smooth_pose needs smooth_per_identity=True, and each slot then has its own stream."""
+        them, smooth_pose needs smooth_per_identity=True, and each slot then has its own stream.
+        refine=True: every rendered batch goes through the attached stage-2 model (attach_stage2; see animate_frames) and the
+        frames come out at its output_size_s2."""
+        masks_of = self._refine_plan(refine, refine_masks)
         self._check_smoothing(identities, smooth_pose, smooth_per_identity)
         N = target_pose_embeds.shape[0]
         ids = None if identities is None else self._frame_identities(identities, N)
@@ -868,6 +943,9 @@ class InferenceWrapper:
                 theta = self._pose_controls(ops.pose_theta(*srt), ident, mix, mix_old, False)
             theta = self._render_theta(theta, ident, target_theta)
             img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ident)
+            if masks_of is not None:
+                yield b0, self._refine(img, masks_of, "u8" if as_uint8 else "f32")
+                continue
             yield b0, (ops.pack_rgb8(img) if as_uint8 else img)
 
     # ------------------------------------------------------------------------------------------------------
@@ -914,7 +992,7 @@ class InferenceWrapper:
 
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
                        mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
-                       paste_matte=None, as_uint8=True):
+                       paste_matte=None, as_uint8=True, refine=False, refine_masks=None):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  frames: uint8 [N,H,W,3] tensor (host, ideally pinned, or device) or an iterable of such chunks --
         decoded video frames, uploaded as BYTES.  Per batch, all on the device and without a host synchronisation:
@@ -952,10 +1030,21 @@ class InferenceWrapper:
         embedders['matting'].  Each rank pastes its own shard: no collective.
         as_uint8=False (with to_host=False, without paste_back): the fp32 [b,3,S,S] device image itself, as animate() yields it
         -- what paste_back() takes as `rendered` (with captured graphs it is the graph's output buffer: consume or clone it
-        before resuming the generator)."""
+        before resuming the generator).
+        refine=True: stage 2 in the path (attach_stage2 first; ValueError before anything is launched otherwise).  Per batch,
+        where the hot path returns its image: bilinear resize to the stage-2 model's output_size_s2 if that differs from
+        image_size (infer_s2.py:360-362) -> the matte and the face mask of the resized image from the attached wrapper's
+        'matting' / 'face_parsing' callables (all ones for the face mask with its `cloth`), or both from refine_masks=img ->
+        (mask, face_mask); eager, third-party nets -> Stage2.refine_frames, a captured graph with use_graphs, whose last launch
+        (emo_stage2_head_f32) writes the bytes that go to the ring, or the fp32 image that paste_back=True pastes
+        (paste_matte is then computed on the refined image, and window sides are held to output_size_s2 / 4) or that
+        as_uint8=False yields.  Yielded crops are [b,S2,S2,3].  identities, the pose controls and smooth_pose are untouched:
+        refinement starts where the render returns, and every rank refines its own shard."""
         matte_fn = None
         if not as_uint8 and (to_host or paste_back):
             raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
+        masks_of = self._refine_plan(refine, refine_masks)
+        S_out = self.cfg["image_size"] if masks_of is None else self._stage2.cfg["output_size_s2"]
         if paste_back:
             if windows is None:
                 raise ValueError("paste_back=True needs windows=: one (x_lo, y_lo, side) per frame says where each rendered crop goes")
@@ -963,8 +1052,8 @@ class InferenceWrapper:
                 raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
             matte_fn = self._paste_matte(paste_matte, 'paste_matte=True')
             paste_wins = self._paste_windows(windows)
-            if any(4 * w[2] < self.cfg["image_size"] for w in paste_wins):
-                raise ValueError(f"a paste window is smaller than a quarter of the {self.cfg['image_size']}-pixel image: downscaling "
+            if any(4 * w[2] < S_out for w in paste_wins):
+                raise ValueError(f"a paste window is smaller than a quarter of the {S_out}-pixel image: downscaling "
                                  f"stops at image_size / 4")
         ids = None
         self._check_smoothing(identities, smooth_pose, smooth_per_identity)
@@ -1070,10 +1159,14 @@ class InferenceWrapper:
                 pose, _ = self._expression(crops, theta, 'a driver call')
                 theta = self._render_theta(theta, ident, target_theta)
                 img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ident)
+                if masks_of is not None:
+                    img = self._refine(img, masks_of, "f32" if paste_back or not as_uint8 else "u8")
                 if paste_back:
                     full = u8.clone() if chunk.is_cuda else u8                   # (a host chunk's upload is this span's own)
                     out = ops.paste_windows(full, img, paste_wins[base + b0:base + b1], feather,
                                             None if matte_fn is None else matte_fn(img).float().contiguous())
+                elif masks_of is not None:
+                    out = img                                                    # (bytes or fp32, as asked of the stage-2 tail)
                 else:
                     out = ops.pack_rgb8(img) if as_uint8 else img
                 if not to_host:

@@ -651,6 +651,39 @@ def stage2_compose(img, add_img, mask, face_mask):
     return out
 
 
+def stage2_head(x, layer, scale, shift, img, mask, face_mask=None, out="u8", relu_in=True):
+    """The tail of stage 2 in one launch (csrc/conv_head.hip, emo_stage2_head_f32): clamp(img + tanh(conv1x1(in(x))) *
+    (mask * face_mask), 0, 1) with in() the folded norm + ReLU of conv_head; x [N,Cin,H,W], layer a 1x1 conv to 3 channels, img
+    [N,3,H,W], mask / face_mask [N,1,H,W] (face_mask None = ones).  out 'u8': uint8 [N,H,W,3] as pack_rgb8 writes it; 'f32': the
+    fp32 [N,3,H,W] image; 'both': (f32, u8).  Bit-identical to conv_head(act='tanh') -> stage2_compose -> pack_rgb8, which is
+    what launch forms the stream kernel does not take run (positions not a multiple of 4, unaligned views, EMO_CONV_HEAD=0),
+    with the head on conv_igemm as Stage2.refine has it."""
+    lib = hip.load()
+    hip.require_cuda_f32(x, scale, shift, img, mask, face_mask)
+    if out not in ("u8", "f32", "both"):
+        raise ValueError(f"out={out!r}: 'u8', 'f32' or 'both'")
+    N, Cin, H, W = x.shape
+    S = H * W
+    if tuple(img.shape) != (N, 3, H, W) or mask.numel() != N * S or (face_mask is not None and face_mask.numel() != N * S):
+        raise ValueError(f"stage-2 tail: image {tuple(img.shape)} / masks do not match the activation {tuple(x.shape)}")
+    if (layer.kd, layer.kh, layer.kw) != (1, 1, 1) or layer.cout != 3:
+        raise ValueError("stage-2 tail: the head is a 1x1 convolution to 3 channels")
+    if Cin != layer.cin:
+        raise ValueError(f"conv expects {layer.cin} input channels, got {Cin}")
+    views = (x, img, mask) + (() if face_mask is None else (face_mask,))
+    if not CONV_HEAD_STREAM or S % 4 or N > 65535 or any(t.data_ptr() % 16 for t in views):
+        add = conv_igemm(x, layer, scale, shift, relu_in=relu_in, act="tanh")
+        f32 = stage2_compose(img, add, mask, torch.ones_like(mask) if face_mask is None else face_mask)
+        return f32 if out == "f32" else pack_rgb8(f32) if out == "u8" else (f32, pack_rgb8(f32))
+    f32 = torch.empty_like(img) if out != "u8" else None
+    u8 = torch.empty((N, H, W, 3), device=img.device, dtype=torch.uint8) if out != "f32" else None
+    layer.last_plan = ("head", 1, "stream")
+    hip.check(lib.emo_stage2_head_f32(hip.ptr(x), hip.ptr(layer.plain_weight()), hip.ptr(layer.bias), hip.ptr(scale), hip.ptr(shift),
+                                      hip.ptr(img), hip.ptr(mask), hip.ptr(face_mask), hip.ptr(f32), hip.ptr(u8), N, Cin, S,
+                                      int(relu_in), hip.current_stream()), f"emo_stage2_head_f32[{layer.name}]")
+    return f32 if out == "f32" else u8 if out == "u8" else (f32, u8)
+
+
 def resize2d(x, size, mode="bilinear", window=None, clamp01=False):
     """F.interpolate(x[..., y0:y0+h, x0:x0+w], size=size, mode=mode, align_corners=False) for 4-D x; mode 'bilinear' or
     'bicubic'; window = (x0, y0, w, h) reads a crop of the frame in place (default: the whole frame)"""

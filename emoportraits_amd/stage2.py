@@ -190,7 +190,8 @@ class DecoderStage2:
         self.nh = Norm(sd, prefix + ".img_decoder.dec_img_head.0", device)
         self.head = PackedConv.from_state_dict(sd, prefix + ".img_decoder.dec_img_head.2", kind, device)
 
-    def __call__(self, feat_2d):
+    def body(self, feat_2d):
+        """everything in front of the image head -> (activation [B,C,S2,S2], (scale, shift) of the head's folded norm)"""
         # GroupNorm variant: the tile statistics of every conv output travel with the tensor (nets.ResBlock); the BatchNorm
         # default has static affines and asks for none
         x, st = (ops.conv_igemm(feat_2d, self.first), None) if self.nh.bn else ops.conv_igemm(feat_2d, self.first, want_stats=True)
@@ -201,7 +202,10 @@ class DecoderStage2:
         x, st = self.feat[0](x, ups=True, x_stats=st, want_stats=True)
         for b in self.feat[1:]:
             x, st = b(x, x_stats=st, want_stats=True)
-        s, h = self.nh.affine(x, stats=st)
+        return x, self.nh.affine(x, stats=st)
+
+    def __call__(self, feat_2d):
+        x, (s, h) = self.body(feat_2d)
         return ops.conv_igemm(x, self.head, s, h, relu_in=True, act="tanh")
 
 
@@ -235,6 +239,20 @@ class Stage2:
         if keep:
             return dict(latents=lat, add=add, out=out)
         return out
+
+    def refine_frames(self, img, mask, face_mask, out="u8"):
+        """refine() for the video path: the same pass with the image head, the composition and the byte packing as ONE stream
+        launch (ops.stage2_head / emo_stage2_head_f32) in place of conv_igemm -> stage2_compose -> pack_rgb8.  out 'u8': uint8
+        [B,S2,S2,3]; 'f32': the fp32 [B,3,S2,S2] image.  Device tensors in, device tensor out, no host synchronisation: a
+        graphs.Graphed can capture it.  The head's sum over its 32 channels is sequential here and blocked on the MFMA kernel
+        refine() uses: same bounds against the oracle, not the same bits.
+        In the 'f16x2' mode the pass starts by clearing the device's range-check words (captured with it), as refine() and
+        nets.HotPath._clear_flags do: every layer has its own word, but ops.overflow_events() of a stage-1 pass of the same
+        batch must be read before this pass runs."""
+        if self.precision == "f16x2":
+            ops.clear_overflow_flags(self.device)
+        x, (s, h) = self.decoder.body(self.encoder(ops.mul_mask(img, mask)))
+        return ops.stage2_head(x, self.decoder.head, s, h, img, mask, face_mask, out=out)
 
 
 class InferenceWrapper:

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 15
+#define EMO_ABI_VERSION 16
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -345,6 +345,22 @@ int emo_conv_igemm_f32_guarded(const float* x, const float* wpk, const float* bi
  * oracle, not the same bits. */
 int emo_conv_head_f32(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
                       float* out, int N, int Cin, int Cout, int64_t S, int relu_in, int act, void* stream);
+
+/* ABI 16.  The tail of stage 2 as one stream launch: the image head norm -> ReLU -> 1x1 conv Cin -> 3 -> tanh at the full
+ * resolution (decoder_s2_old.py:444-456), the residual added under the matte x face mask and clamped (notebooks/infer_s2.py:
+ * 365-375), written as fp32 planes and / or as HWC bytes.  emo_conv_head_f32's channel walk with another epilogue:
+ *   out = clamp(img + tanh(bias[o] + sum_c w[o][c] * in(x[n][c][p])) * (mask * face_mask), 0, 1),  in(.) as emo_conv_head_f32
+ *   x [N, Cin, S], w [3][Cin] plain row-major, bias [3] or NULL, scale / shift [N, Cin] both or neither, img [N,3,S],
+ *   mask [N,1,S], face_mask [N,1,S] or NULL (= 1), out_f32 [N,3,S] or NULL, out_u8 [N,S,3] (the bytes emo_pack_rgb8 writes) or
+ *   NULL; at least one of the two outputs (EMO_ERR_BAD_ARG otherwise).
+ * The operations and their order are those of emo_conv_head_f32(act = EMO_ACT_TANH) -> emo_stage2_compose_f32 -> emo_pack_rgb8
+ * (sequential fp32 FMA sum, tanhf, gate = mask * face_mask, img + add * gate as two rounded operations, clamp, (uint8)(v * 255)):
+ * both outputs are bit-identical to that chain on the same operands.
+ * S % 4 == 0 and N <= 65535 (EMO_ERR_UNSUPPORTED otherwise); x, img, mask, face_mask, out_f32 16-byte and out_u8 4-byte aligned
+ * (EMO_ERR_ALIGN): such launches run the chain. */
+int emo_stage2_head_f32(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
+                        const float* img, const float* mask, const float* face_mask, float* out_f32, uint8_t* out_u8,
+                        int N, int Cin, int64_t S, int relu_in, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * resampling / pointwise helpers (HBM-bound, one pass)

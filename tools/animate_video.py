@@ -6,12 +6,17 @@
         [--windows windows.json]   # optional per-frame crop windows [[x_lo, y_lo, side], ...] from a face detector
         [--mix [--mix-new]] [--source-pose] [--smooth-pose]   # forward()'s pose controls (mix, mix_old=False, target_theta=False)
         [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
+        [--stage2-experiment <exp2> --stage2-checkpoint <file> [--cloth]       # refine every batch with the stage-2 model
+         (--embedders module:factory | --refine-everywhere)]                   # (<project>/logs_s2/<exp2>), inside the same path
 
 Frame I/O is host work (PIL / numpy): decoded frames are handed to InferenceWrapper.animate_frames as uint8 chunks in pinned
 memory; crop, bicubic resize, both embedders, the hot path and the uint8 packing run on the GPU without a host sync, and
 finished batches come back through the pinned D2H ring while the next ones are being computed.  Face detection, parsing
 and matting are third-party networks without sources in the reference tree: the source image must come with its mask
-(--source-mask, default all ones) and crop windows, if any, are precomputed.
+(--source-mask, default all ones) and crop windows, if any, are precomputed.  For the same reason stage 2's matte (MODNet)
+and face mask (BiSeNet) come from the caller: --embedders names a `module:factory` whose call returns {'matting': fn,
+'face_parsing': fn}, each img [b,3,S2,S2] -> [b,1,S2,S2] on the device; --refine-everywhere sets both masks to ones (the
+residual is then added over the whole crop, background included).
 """
 import argparse
 import json
@@ -59,11 +64,35 @@ def main():
     ap.add_argument("--smooth-pose", action="store_true", help="EMA over the driver head poses (smooth_pose=True)")
     ap.add_argument("--paste-back", action="store_true", help="write the full frames with the rendered crop pasted back (needs --windows)")
     ap.add_argument("--feather", type=float, default=0.0625, help="with --paste-back: blended edge as a fraction of the window side")
+    ap.add_argument("--stage2-experiment", default=None, help="refine with the stage-2 model <project>/logs_s2/<this>")
+    ap.add_argument("--stage2-checkpoint", default=None)
+    ap.add_argument("--cloth", action="store_true", help="stage 2: no face mask (all ones), as infer_s2.py's cloth=True")
+    ap.add_argument("--embedders", default=None, help="module:factory returning {'matting': fn, 'face_parsing': fn} for stage 2")
+    ap.add_argument("--refine-everywhere", action="store_true", help="stage 2 with both masks all ones (no matting / parsing nets)")
     a = ap.parse_args()
+    refine = a.stage2_experiment is not None
+    if refine and (a.stage2_checkpoint is None or (a.embedders is None) == (not a.refine_everywhere)):
+        ap.error("--stage2-experiment needs --stage2-checkpoint and one of --embedders module:factory / --refine-everywhere")
+    if not refine and (a.stage2_checkpoint or a.embedders or a.refine_everywhere or a.cloth):
+        ap.error("--stage2-checkpoint / --embedders / --refine-everywhere / --cloth belong to --stage2-experiment")
     from PIL import Image
     from notebooks.infer import InferenceWrapper
     w = InferenceWrapper(experiment_name=a.experiment, model_file_name=a.checkpoint, project_dir=a.project, folder=a.folder,
                          head_pose_regressor_path=a.head_pose_regressor, use_graphs=a.graphs)
+    refine_masks = None
+    if refine:
+        from notebooks.infer_s2 import InferenceWrapper as InferenceWrapperS2
+        embedders = None
+        if a.embedders:
+            import importlib
+            module, _, factory = a.embedders.partition(":")
+            embedders = getattr(importlib.import_module(module), factory)()
+        else:
+            def refine_masks(img):
+                ones = torch.ones((img.shape[0], 1) + tuple(img.shape[2:]), device=img.device)
+                return ones, ones
+        w.attach_stage2(InferenceWrapperS2(experiment_name=a.stage2_experiment, model_file_name=a.stage2_checkpoint,
+                                           project_dir=a.project, cloth=a.cloth, embedders=embedders))
     S = w.cfg["image_size"]
     src = Image.open(a.source).convert("RGB")
     mask = torch.ones(1, 1, S, S) if a.source_mask is None else \
@@ -75,13 +104,13 @@ def main():
     frames = load_frames(a.frames, 8 * a.batch)
     for first, u8 in w.animate_frames(frames, batch_size=a.batch, windows=windows, mix=a.mix, mix_old=not a.mix_new,
                                       target_theta=not a.source_pose, smooth_pose=a.smooth_pose, paste_back=a.paste_back,
-                                      feather=a.feather):
+                                      feather=a.feather, refine=refine, refine_masks=refine_masks):
         arr = u8.numpy()
         for j in range(arr.shape[0]):
             Image.fromarray(arr[j]).save(os.path.join(a.out, f"{first + j:06d}.png"))
         n += arr.shape[0]
     dt = time.perf_counter() - t0
-    print(json.dumps(dict(frames=n, seconds=round(dt, 3), fps=round(n / dt, 2), image_size=S, batch=a.batch)))
+    print(json.dumps(dict(frames=n, seconds=round(dt, 3), fps=round(n / dt, 2), image_size=S, batch=a.batch, refine=refine)))
 
 
 if __name__ == "__main__":
