@@ -1,0 +1,92 @@
+"""The frame plumbing of InferenceWrapper.animate_frames / enrol_identities that touches no wrapper state: crop windows, uint8
+frames -> fp32 crops, the upload-ahead of a host chunk and the pinned ring that takes finished batches back to the host."""
+import torch
+
+from . import ops
+
+
+def square_windows(windows):
+    """(x_lo, y_lo, side) per frame, as animate_frames takes them (a fourth entry must repeat the side) -> (x0, y0, s, s)"""
+    out = []
+    for w in windows:
+        w = [int(v) for v in w]
+        if len(w) not in (3, 4) or (len(w) == 4 and w[3] != w[2]):
+            raise ValueError(f"window {tuple(w)}: expected (x_lo, y_lo, side)")
+        out.append((w[0], w[1], w[2], w[2]))
+    return out
+
+
+def crops_of(u8, size, windows=None):
+    """uint8 frames [b,H,W,3] on the device -> fp32 crops [b,3,size,size]: byte -> fp32 CHW (emo_unpack_rgb8), then each frame's
+    window (x0, y0, s, s) read in place and resized, the whole batch in one launch (a host list or an int32 [b,4] device
+    tensor, ops.resize2d_windows), or without windows the whole frame, resized only where its size differs"""
+    x = ops.unpack_rgb8(u8)
+    if windows is not None:
+        return ops.resize2d_windows(x, (size, size), windows, "bicubic", clamp01=True)
+    if x.shape[-2:] != (size, size):
+        return ops.resize2d(x, (size, size), "bicubic")
+    return x
+
+
+def uploaded(chunk, spans, device, upload_stream):
+    """(b0, b1, uint8 frames on the device) for every span, with the upload of span i + 1 enqueued on a copy stream BEFORE
+    span i is handed out -- i.e. before its kernels are enqueued -- so that a host chunk's H2D copy (12.6 MB per 16 frames
+    at 512^2: 0.25 ms) runs beside the previous batch's compute instead of in front of its own (on the compute stream the
+    copy serialises with the kernels).  Device-resident chunks pass through."""
+    ahead = None
+    for span in list(spans) + [None]:
+        nxt = None
+        if span is not None:
+            b0, b1 = span
+            src = chunk[b0:b1]
+            if src.is_cuda:
+                nxt = (b0, b1, src.contiguous(), None)
+            else:
+                with torch.cuda.stream(upload_stream):
+                    t = src.to(device, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(upload_stream)
+                nxt = (b0, b1, t, ev)
+        if ahead is not None:
+            p0, p1, t, ev = ahead
+            if ev is not None:
+                torch.cuda.current_stream().wait_event(ev)
+                t.record_stream(torch.cuda.current_stream())
+            yield p0, p1, t
+        ahead = nxt
+
+
+class HostRing:
+    """Finished uint8 batches go D2H into `ring` pinned buffers on a copy stream; a batch is handed out once ITS copy event has
+    completed, i.e. the host only ever waits for a batch that is `ring - 1` batches behind the GPU.  What is handed out is a
+    view of a ring slot, valid only until the next push()."""
+
+    def __init__(self, device, ring, batch_size):
+        self.ring, self.batch_size = ring, batch_size
+        self.stream = torch.cuda.Stream(device=device)
+        self.slots, self.pending, self.k = [], [], 0     # pinned buffers; (first index, slot, n frames, event) in flight
+
+    def drain(self, keep=0):
+        while len(self.pending) > keep:
+            b0, slot, nb, ev = self.pending.pop(0)
+            ev.synchronize()
+            yield b0, self.slots[slot][:nb]
+
+    def push(self, b0, out):
+        """queue the copy of batch `out` (first frame b0) behind the compute stream; yields the batches now due"""
+        if self.slots and self.slots[0].shape[1:] != out.shape[1:]:          # full frames of another size: a new ring
+            yield from self.drain()
+            self.slots.clear()
+            self.k = 0
+        if len(self.slots) < self.ring:
+            self.slots.append(torch.empty((self.batch_size,) + tuple(out.shape[1:]), dtype=torch.uint8, pin_memory=True))
+        slot = self.k % self.ring
+        self.k += 1
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            self.slots[slot][:out.shape[0]].copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        out.record_stream(self.stream)
+        self.pending.append((b0, slot, out.shape[0], ev))
+        yield from self.drain(self.ring - 1)

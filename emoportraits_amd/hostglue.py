@@ -125,6 +125,18 @@ def ema_scan(values, state, momentum):
     return out, cur
 
 
+def bank_slot(slot, capacity):
+    """a slot of an identity bank of `capacity` slots as an int; ValueError unless it is an integer (not a bool) in range"""
+    import operator
+    try:
+        slot = operator.index(slot) if not isinstance(slot, bool) else None
+    except TypeError:
+        slot = None
+    if slot is None or not 0 <= slot < capacity:
+        raise ValueError(f"slot {slot!r} is not in [0, {capacity})")
+    return slot
+
+
 def enrolment_plan(used, n_sources, slots=None, batch_size=8, world=1):
     """InferenceWrapper.enrol_identities on the host, before anything is launched -> (slots, chunks, owners).
     used: the occupied flag of every bank slot.  slots=None takes the n_sources lowest free slots; an explicit list may name
@@ -133,7 +145,6 @@ def enrolment_plan(used, n_sources, slots=None, batch_size=8, world=1):
     parallel.shard_range(len(chunks), r, world); owners[j] is the rank that computes chunk j.  ValueError for a bank without
     slots, no sources, too few free slots, a duplicate or out-of-range slot and a batch size below 1.  A pure function of its
     arguments: every rank passes the same ones and takes the same decision."""
-    import operator
     from .parallel import shard_range
     capacity = len(used)
     if capacity == 0:
@@ -148,16 +159,7 @@ def enrolment_plan(used, n_sources, slots=None, batch_size=8, world=1):
             raise ValueError(f"{n_sources} sources, {len(free)} free identity slots of {capacity}: drop_identity some or pass slots=")
         slots = free[:n_sources]
     else:
-        out = []
-        for k in slots:
-            try:
-                k = operator.index(k) if not isinstance(k, bool) else None
-            except TypeError:
-                k = None
-            if k is None or not 0 <= k < capacity:
-                raise ValueError(f"slot {k!r} is not in [0, {capacity})")
-            out.append(k)
-        slots = out
+        slots = [bank_slot(k, capacity) for k in slots]
         if len(slots) != n_sources:
             raise ValueError(f"{len(slots)} slots for {n_sources} sources")
         if len(set(slots)) != len(slots):

@@ -27,7 +27,7 @@ frames of several identities in one driver batch.  Both batched entry points tak
 source thetas): with a bank, every frame is mixed against its own identity's source theta, and with smooth_per_identity=True
 smoothed within its own identity's frame sequence (one EMA stream per slot, reset by store / drop / reset_pose_state).
 """
-import operator
+import functools
 import os
 import pathlib
 from argparse import Namespace
@@ -36,12 +36,26 @@ import torch
 
 from . import config as cfg_mod
 from . import embedders as emb_mod
+from . import frames as frames_mod
 from . import graphs, hostglue, nets, ops, parallel, schema
 
 
 # smooth_pose in animate_frames: the crops of a rank's shard stay resident between the head-pose pass and the render pass up to
 # this many bytes (3 MB per 512^2 frame; beyond it they are cropped a second time)
 _SMOOTH_KEEP_BYTES = int(float(os.environ.get("EMO_SMOOTH_KEEP_GB", "16")) * (1 << 30))
+
+
+def _sequence(key):
+    """A per-frame launch sequence of the wrapper, written once: the decorated method is the eager path, and with use_graphs
+    the same method is what graphs.Graphed captures under `_graphed[key]` (InferenceWrapper._capture) and the call replays"""
+    def wrap(fn):
+        @functools.wraps(fn)
+        def call(self, *tensors):
+            g = self._graphed.get(key)
+            return fn(self, *tensors) if g is None else g(*tensors)
+        call.key, call.eager = key, fn
+        return call
+    return wrap
 
 
 class HipModel:
@@ -134,6 +148,7 @@ class InferenceWrapper:
             self.rank, self.world = 0, 1
         self.device = torch.device("cuda", parallel.local_device_index())
         torch.cuda.set_device(self.device)
+        self._init_state(use_graphs, int(identity_capacity), pose_momentum, fixed_bounding_box, bool(found.get('use_seg', False)))
 
         self.model_checkpoint = pathlib.Path(project_dir) / folder / experiment_name / 'checkpoints' / model_file_name
         self.model_dict = torch.load(self.model_checkpoint, map_location='cpu') if state_dict is None else state_dict
@@ -150,41 +165,40 @@ class InferenceWrapper:
         # On by default: a drop-in user calls forward() one frame at a time, which is launch-bound without the replay
         # (bench.py extras: emotion_driver_forward_fps, latency_b1_ms).  The first call of an input signature runs eagerly,
         # the second captures, later ones replay (use_graphs='eager_first' semantics; use_graphs=False never captures).
-        self.use_graphs = bool(use_graphs)
-        self._graphed = {}
-        if self.use_graphs:
-            first = self._graph_eager_calls = 0 if use_graphs == 'capture_first' else 1
-            self._graphed['driver'] = graphs.Graphed(
-                lambda pose, theta: self.hot_path.driver_pass(self._canonical_cl, self.idt_embed, pose, theta), eager_calls=first)
-            if identity_capacity > 0:
-                # the bank pass reads the bank buffers (fixed addresses) and the per-frame slots (an input of the graph): new
-                # indices and newly stored identities take effect on replay
-                self._graphed['driver_bank'] = graphs.Graphed(
-                    lambda pose, theta, ident: self.hot_path.driver_pass(self._bank_cl, self._bank_idt, pose, theta, identity=ident),
-                    eager_calls=first)
-            hp_net, ex_net = native.get('head_pose_regressor'), native.get('expression_embedder')
-            if hp_net is not None and self.embedders['head_pose_regressor'] is hp_net:
-                self._graphed['head_pose_regressor'] = graphs.Graphed(lambda crop: hp_net.forward(crop, True), eager_calls=first)
-            if ex_net is not None and self.embedders['expression_embedder'] is ex_net:
-                self._graphed['expression_embedder'] = graphs.Graphed(lambda crop, theta: ex_net(crop, theta, True)[:2],
-                                                                      eager_calls=first)
+        cls = type(self)
+        self._capture(cls._drive)
+        if self.identity_capacity > 0:
+            self._capture(cls._drive_bank)
+        for seq in (cls._head_pose, cls._expression_pass):
+            if native.get(seq.key) is not None and self.embedders[seq.key] is native[seq.key]:
+                self._capture(seq)
 
+    def _init_state(self, use_graphs=True, identity_capacity=0, pose_momentum=0.5, fixed_bounding_box=False, use_seg=False):
+        """Every attribute the methods read that is not a model, from the constructor's arguments alone (the identity bank
+        also reads `cfg` and `device`, which must be set): crop tracking, the smooth_pose state, the per-identity cache, the
+        captured graphs, the attached stage 2, the bank.  __init__ calls it before it builds the models; a test rig calls it on
+        a bare object."""
+        self.use_graphs = bool(use_graphs)
+        self._graph_eager_calls = 0 if use_graphs == 'capture_first' else 1
+        self._graphed = {}
         self.fixed_bounding_box = fixed_bounding_box
         self.momentum = 0.01
-        self.center = None
-        self.size = None
+        self.center = self.size = self._crop_tracker = None
         self.pose_momentum = pose_momentum
         self.theta = None
         self.norm_momentum = 0.1
-        self.delta_yaw = None
-        self.delta_pitch = None
+        self.delta_yaw = self.delta_pitch = None
         self.resize_warp = False
-        self.use_seg = bool(found.get('use_seg', False))
-        self.target_latent_volume = None
-        self._canonical_cl = None
-        self._crop_tracker = None
-        self._init_identity_bank(int(identity_capacity))
+        self.use_seg = use_seg
+        self.target_latent_volume = self._canonical_cl = self.idt_embed = self.pred_source_theta = None
         self._stage2 = self._stage2_wrapper = None                                 # attach_stage2()
+        self._init_identity_bank(identity_capacity)
+
+    def _capture(self, seq):
+        """with use_graphs: replay the _sequence method `seq` from a hipGraph from its (1 + _graph_eager_calls)-th call of an
+        input signature on"""
+        if self.use_graphs:
+            self._graphed[seq.key] = graphs.Graphed(functools.partial(seq.eager, self), eager_calls=self._graph_eager_calls)
 
     # ------------------------------------------------------------------------------------------------------
     def _native_embedders(self, found, head_pose_regressor_path):
@@ -204,21 +218,23 @@ class InferenceWrapper:
             out['head_pose_regressor'] = emb_mod.HeadPoseRegressor(torch.load(path, map_location='cpu'), self.device)
         return out
 
-    def _set_source_cache(self, canonical=None, idt_embed=None):
+    def _set_source_cache(self, canonical=None, idt_embed=None, canonical_cl=None):
         """per-identity cache; with graphs the captured sequences hold the buffer addresses, so a new identity is copied
-        INTO the existing buffers instead of rebinding them"""
+        INTO the existing buffers instead of rebinding them.  canonical: the NCDHW volume (kept as target_latent_volume and
+        repacked); canonical_cl: a volume that is channels-last already -- a view of a bank row, cloned where it is bound"""
         if idt_embed is not None:
-            if self.use_graphs and getattr(self, 'idt_embed', None) is not None and self.idt_embed.shape == idt_embed.shape:
+            if self.use_graphs and self.idt_embed is not None and self.idt_embed.shape == idt_embed.shape:
                 self.idt_embed.copy_(idt_embed)
             else:
                 self.idt_embed = idt_embed.clone() if self.use_graphs else idt_embed
         if canonical is not None:
             self.target_latent_volume = canonical
-            cl = self.hot_path.prepare_canonical(canonical)
+        cl = canonical_cl if canonical is None else self.hot_path.prepare_canonical(canonical)
+        if cl is not None:
             if self.use_graphs and self._canonical_cl is not None and self._canonical_cl.shape == cl.shape:
                 self._canonical_cl.copy_(cl)
             else:
-                self._canonical_cl = cl
+                self._canonical_cl = cl if canonical is not None else cl.clone()
 
     # ---- identity bank --------------------------------------------------------------------------------------------
     def _init_identity_bank(self, capacity):
@@ -245,12 +261,7 @@ class InferenceWrapper:
     def _slot(self, slot, occupied=True):
         if self.identity_capacity == 0:
             raise ValueError("this wrapper has no identity bank: construct it with identity_capacity=K")
-        try:
-            slot = operator.index(slot) if not isinstance(slot, bool) else None
-        except TypeError:
-            slot = None
-        if slot is None or not 0 <= slot < self.identity_capacity:
-            raise ValueError(f"slot {slot!r} is not in [0, {self.identity_capacity})")
+        slot = hostglue.bank_slot(slot, self.identity_capacity)
         if occupied and not self._bank_used[slot]:
             raise ValueError(f"slot {slot} holds no identity")
         return slot
@@ -269,9 +280,9 @@ class InferenceWrapper:
         first free one); returns the slot"""
         if self.identity_capacity == 0:
             self._slot(0)                  # (raises: no bank)
-        if self._canonical_cl is None or getattr(self, 'idt_embed', None) is None:
+        if self._canonical_cl is None or self.idt_embed is None:
             raise RuntimeError("no current identity: call forward with a source_image (or share_source) first")
-        if getattr(self, 'pred_source_theta', None) is None:
+        if self.pred_source_theta is None:
             raise RuntimeError("the current identity has no source theta")
         if slot is None:
             free = [k for k, used in enumerate(self._bank_used) if not used]
@@ -288,11 +299,7 @@ class InferenceWrapper:
         slot = self._slot(slot)
         cl = self._bank_cl[slot:slot + 1]
         self.target_latent_volume = ops.volume_to_channels_first(cl)
-        if self.use_graphs and self._canonical_cl is not None and self._canonical_cl.shape == cl.shape:
-            self._canonical_cl.copy_(cl)
-        else:
-            self._canonical_cl = cl.clone()
-        self._set_source_cache(idt_embed=self._bank_idt[slot:slot + 1].clone())
+        self._set_source_cache(canonical_cl=cl, idt_embed=self._bank_idt[slot:slot + 1].clone())
         self.pred_source_theta = self._bank_theta[slot:slot + 1].clone()
 
     def drop_identity(self, slot):
@@ -318,16 +325,20 @@ class InferenceWrapper:
     def share_identity(self, slot, src_rank=0):
         """Broadcast slot `slot` of rank `src_rank` into the same slot on every rank (one flat buffer,
         parallel.broadcast_source_cache)"""
-        slot = self._slot(slot, occupied=self.rank == src_rank)
         src = self.rank == src_rank
-        cache = parallel.broadcast_source_cache(
-            dict(canonical_cl=self._bank_cl[slot:slot + 1] if src else None, idt_embed=self._bank_idt[slot:slot + 1] if src else None,
-                 theta_src=self._bank_theta[slot:slot + 1] if src else None),
-            shapes=dict(canonical_cl=(1,) + tuple(self._bank_cl.shape[1:]), idt_embed=(1,) + tuple(self._bank_idt.shape[1:]), theta_src=(1, 4, 4)),
-            names=['canonical_cl', 'idt_embed', 'theta_src'], src=src_rank, device=self.device, world=self.world, rank=self.rank,
-            exchange_shapes=False)
+        slot = self._slot(slot, occupied=src)
+        rows = {} if not src else dict(canonical_cl=self._bank_cl[slot:slot + 1], idt_embed=self._bank_idt[slot:slot + 1],
+                                       theta_src=self._bank_theta[slot:slot + 1])
+        cache = self._broadcast_rows(rows, 1, src_rank, 'canonical_cl', self._bank_cl.shape[1:])
         if not src:
             self._bank_write(slot, cache["canonical_cl"], cache["idt_embed"], cache["theta_src"])
+
+    def _broadcast_rows(self, rows, n, src, volume, volume_shape):
+        """{volume, idt_embed, theta_src} of n identities from rank `src` (its `rows`; {} elsewhere) to every rank in one flat
+        buffer, the shapes known on every rank: one collective, no host synchronisation (parallel.broadcast_source_cache)"""
+        shapes = {volume: (n,) + tuple(volume_shape), 'idt_embed': (n,) + tuple(self._bank_idt.shape[1:]), 'theta_src': (n, 4, 4)}
+        return parallel.broadcast_source_cache(rows, shapes=shapes, names=list(shapes), src=src, device=self.device,
+                                               world=self.world, rank=self.rank, exchange_shapes=False)
 
     def enrol_identities(self, sources, source_masks=None, slots=None, crop=False, windows=None, batch_size=8,
                          custome_idt_embed=None, custome_source_pose_embed=None, custome_source_theta_embed=None):
@@ -346,11 +357,14 @@ class InferenceWrapper:
         idt_embed, theta} in one flat buffer, from which every rank, the owner included, writes its rows -- the bank is the
         same bit for bit on every rank and for any number of ranks.  Returns the slots in the order of `sources`."""
         with torch.no_grad():
-            return self._enrol_identities(sources, source_masks, slots, crop, windows, batch_size, custome_idt_embed,
+            plan = self._enrolment_checks(sources, source_masks, slots, crop, windows, batch_size, custome_idt_embed,
                                           custome_source_pose_embed, custome_source_theta_embed)
+            return self._enrol_identities(plan, sources, crop, custome_idt_embed, custome_source_pose_embed,
+                                          custome_source_theta_embed)
 
-    def _enrol_identities(self, sources, source_masks, slots, crop, windows, batch_size, custome_idt_embed,
+    def _enrolment_checks(self, sources, source_masks, slots, crop, windows, batch_size, custome_idt_embed,
                           custome_source_pose_embed, custome_source_theta_embed):
+        """enrol_identities on the host, before anything is launched -> what the device part needs beside the arguments"""
         S = self.cfg["image_size"]
         video = isinstance(sources, torch.Tensor) and sources.dtype == torch.uint8
         if isinstance(sources, torch.Tensor):
@@ -371,7 +385,7 @@ class InferenceWrapper:
         win_host = None
         if windows is not None:
             H, W = sources.shape[1], sources.shape[2]
-            win_host = torch.tensor([[int(w[0]), int(w[1]), int(w[2]), int(w[2])] for w in windows], dtype=torch.int32).reshape(-1, 4)
+            win_host = torch.tensor(frames_mod.square_windows(windows), dtype=torch.int32).reshape(-1, 4)
             if win_host.shape[0] != K:
                 raise ValueError(f"{win_host.shape[0]} windows for {K} sources")
             lo, side = win_host[:, :2], win_host[:, 2]
@@ -379,7 +393,7 @@ class InferenceWrapper:
                     and bool((lo[:, 1] + side <= H).all())):
                 raise ValueError(f"a crop window is not inside the {W}x{H} frame")
         parsing = 'face_parsing' in self.embedders
-        masks = None
+        ms = None
         if source_masks is not None:
             ms = [source_masks[i] for i in range(source_masks.shape[0])] if isinstance(source_masks, torch.Tensor) else list(source_masks)
             if len(ms) != K:
@@ -432,49 +446,44 @@ class InferenceWrapper:
                 if win is None:
                     raise ValueError(f"source {i}: no face found (forward would render a zero crop for it; nothing was enrolled)")
                 boxes.append((t, win))
+        return Namespace(slots=slots, chunks=chunks, owners=owners, video=video, win_host=win_host, masks=ms, images=images,
+                         boxes=boxes, parsing=parsing)
 
-        # ---- device: inputs uploaded once, then chunk by chunk without a host synchronisation
-        dev = self.device
-        rows32 = torch.tensor(slots, dtype=torch.int32).to(dev)
+    def _enrol_identities(self, plan, sources, crop, custome_idt_embed, custome_source_pose_embed, theta_in):
+        """the device part: inputs uploaded once, then chunk by chunk without a host synchronisation"""
+        S, dev = self.cfg["image_size"], self.device
+        rows32 = torch.tensor(plan.slots, dtype=torch.int32).to(dev)
         rows64 = rows32.long()
-        masks = None if source_masks is None else torch.cat([m.reshape(1, 1, S, S) for m in ms]).to(dev).float().contiguous()
+        masks = None if plan.masks is None else torch.cat([m.reshape(1, 1, S, S) for m in plan.masks]).to(dev).float().contiguous()
         up = lambda t: None if t is None else t.to(dev).float().contiguous()
         idt_all, pose_all = up(custome_idt_embed), up(custome_source_pose_embed)
-        theta_all = None
-        if theta_in is not None:
-            theta_all = self._theta_from(theta_in)[0]
-        if video:
+        theta_all = None if theta_in is None else self._theta_from(theta_in)[0]
+        if plan.video:
             u8 = sources.to(dev).contiguous()
-            win_dev = None if win_host is None else win_host.to(dev)
-            crops_all = None
+            win_dev = None if plan.win_host is None else plan.win_host.to(dev)
         elif not crop:
-            crops_all = torch.cat([self._prepare_image(img) for img in images])               # (as forward, per image)
-        elif boxes is None:
-            crops_all = self.embedders['cropper'](images).to(dev)
+            crops_all = torch.cat([self._prepare_image(img) for img in plan.images])          # (as forward, per image)
+        elif plan.boxes is None:
+            crops_all = self.embedders['cropper'](plan.images).to(dev)
         else:
             crops_all = torch.cat([ops.resize2d(t[None].to(dev).float().contiguous(), (S, S), "bicubic",
-                                                window=(x_lo, y_lo, side, side), clamp01=True) for t, (x_lo, y_lo, side, _) in boxes])
+                                                window=(x_lo, y_lo, side, side), clamp01=True) for t, (x_lo, y_lo, side, _) in plan.boxes])
         es_shape = tuple(self._bank_idt.shape[1:])
-        hp = self.hot_path
 
         def compute(a, b):
-            if video:
-                x = ops.unpack_rgb8(u8[a:b])                                    # animate_frames' crops_of, one launch per chunk
-                if win_dev is not None:
-                    crop_img = ops.resize2d_windows(x, (S, S), win_dev[a:b], "bicubic", clamp01=True)
-                else:
-                    crop_img = ops.resize2d(x, (S, S), "bicubic") if x.shape[-2:] != (S, S) else x
+            if plan.video:
+                crop_img = frames_mod.crops_of(u8[a:b], S, None if win_dev is None else win_dev[a:b])   # one launch per chunk
             else:
                 crop_img = crops_all[a:b].float().contiguous()
             m = None if masks is None else masks[a:b]
-            face = (self.embedders['face_parsing'](crop_img) > 0.6).float().contiguous() if parsing else m   # infer.py:408-411
+            face = (self.embedders['face_parsing'](crop_img) > 0.6).float().contiguous() if plan.parsing else m   # infer.py:408-411
             crop_m = ops.mul_mask(crop_img, face)
             masked = ops.mul_mask(crop_m, m if m is not None else face)
             idt = idt_all[a:b] if idt_all is not None else self._need('idt_embedder', 'enrolment')(masked)
             theta = theta_all[a:b] if theta_all is not None else self._head_pose(crop_m)[0]
             pose = pose_all[a:b] if pose_all is not None else self._expression(crop_m, theta, 'enrolment')[0]
             theta = theta.float().contiguous()
-            canonical = hp.source_pass(masked, idt.float().contiguous(), pose.float().contiguous(), theta)
+            canonical = self.hot_path.source_pass(masked, idt.float().contiguous(), pose.float().contiguous(), theta)
             return dict(canonical=canonical, idt_embed=idt.float().reshape((b - a,) + es_shape), theta_src=theta.reshape(b - a, 4, 4))
 
         def write(part, a, b):
@@ -483,23 +492,18 @@ class InferenceWrapper:
             self._bank_theta.index_copy_(0, rows64[a:b], part["theta_src"])
 
         if self.world == 1:
-            for a, b in chunks:
+            for a, b in plan.chunks:
                 write(compute(a, b), a, b)
         else:
             # each rank computes its own chunks first, then every chunk travels from its owner, in chunk order
-            mine = {j: compute(a, b) for j, (a, b) in enumerate(chunks) if owners[j] == self.rank}
+            mine = {j: compute(a, b) for j, (a, b) in enumerate(plan.chunks) if plan.owners[j] == self.rank}
             c, d, s = self.cfg["latent_volume_channels"], self.cfg["latent_volume_depth"], self.cfg["latent_volume_size"]
-            for j, (a, b) in enumerate(chunks):
-                n = b - a
-                part = parallel.broadcast_source_cache(
-                    mine.pop(j, {}), shapes=dict(canonical=(n, c, d, s, s), idt_embed=(n,) + es_shape, theta_src=(n, 4, 4)),
-                    names=['canonical', 'idt_embed', 'theta_src'], src=owners[j], device=dev, world=self.world, rank=self.rank,
-                    exchange_shapes=False)
-                write(part, a, b)
-        for k in slots:
+            for j, (a, b) in enumerate(plan.chunks):
+                write(self._broadcast_rows(mine.pop(j, {}), b - a, plan.owners[j], 'canonical', (c, d, s, s)), a, b)
+        for k in plan.slots:
             self._bank_used[k] = True
         self._bank_pose_has.index_fill_(0, rows64, 0)              # a new identity starts a new smooth_pose stream
-        return slots
+        return plan.slots
 
     def _frame_identities(self, identities, n=None):
         """per-frame slots -> int32 host tensor, every slot checked on the host (the device never sees an unknown slot)"""
@@ -534,11 +538,8 @@ class InferenceWrapper:
             raise TypeError("attach_stage2 takes a stage2.InferenceWrapper, a stage2.Stage2 or None")
         self._stage2 = model
         self._stage2_wrapper = stage2 if model is not stage2 else None
-        if getattr(self, 'use_graphs', False):
-            first = getattr(self, '_graph_eager_calls', 1)
-            for out in ('u8', 'f32'):
-                self._graphed['stage2_' + out] = graphs.Graphed(
-                    lambda img, mask, face, out=out: model.refine_frames(img, mask, face, out), eager_calls=first)
+        self._capture(type(self)._refine_u8)
+        self._capture(type(self)._refine_f32)
 
     def _refine_plan(self, refine, refine_masks):
         """the checks of refine=True, before anything is launched -> None (no refinement) or the callable img [b,3,S2,S2] ->
@@ -547,7 +548,7 @@ class InferenceWrapper:
             if refine_masks is not None:
                 raise ValueError("refine_masks= belongs to refine=True")
             return None
-        model = getattr(self, '_stage2', None)
+        model = self._stage2
         if model is None:
             raise ValueError("refine=True needs a stage-2 model: attach_stage2(stage2.InferenceWrapper(...)) first")
         if torch.device(model.device) != torch.device(self.device):
@@ -580,42 +581,44 @@ class InferenceWrapper:
         mask, face = masks_of(img)
         mask = mask.to(self.device).float().contiguous()
         face = face.to(self.device).float().contiguous()
-        g = self._graphed.get('stage2_' + out)
-        if g is not None:
-            return g(img, mask, face)
-        return model.refine_frames(img, mask, face, out)
+        return (self._refine_u8 if out == "u8" else self._refine_f32)(img, mask, face)
 
+    @_sequence('stage2_u8')
+    def _refine_u8(self, img, mask, face):
+        return self._stage2.refine_frames(img, mask, face, "u8")
+
+    @_sequence('stage2_f32')
+    def _refine_f32(self, img, mask, face):
+        return self._stage2.refine_frames(img, mask, face, "f32")
+
+    @_sequence('driver')
+    def _drive(self, pose, theta):
+        return self.hot_path.driver_pass(self._canonical_cl, self.idt_embed, pose, theta)
+
+    @_sequence('driver_bank')
     def _drive_bank(self, pose, theta, ident):
-        g = self._graphed.get('driver_bank')
-        if g is not None:
-            return g(pose, theta, ident)
+        """reads the bank buffers (fixed addresses) and the per-frame slots (an input of the graph): new indices and newly
+        stored identities take effect on replay"""
         return self.hot_path.driver_pass(self._bank_cl, self._bank_idt, pose, theta, identity=ident)
 
+    @_sequence('head_pose_regressor')
     def _head_pose(self, crop):
-        g = self._graphed.get('head_pose_regressor')
-        if g is not None:
-            return g(crop)
         return self._need('head_pose_regressor', 'a driver call')(crop, True)
+
+    @_sequence('expression_embedder')
+    def _expression_pass(self, crop, theta):
+        fn = self.embedders['expression_embedder']
+        return fn(crop, theta, True)[:2] if isinstance(fn, emb_mod.ExpressionEmbed) else fn(crop, theta)
 
     def _expression(self, crop, theta, what):
         """-> (pose_embed, aligned crop or None).  The aligned 128^2 crop is what the reference exposes as
         `target_img_align` (expression_embedder.py:233, infer.py:608); a user-supplied callable may return either the
         embedding alone or a tuple (embedding, aligned, ...)."""
-        g = self._graphed.get('expression_embedder')
-        if g is not None:
-            out = g(crop, theta.float().contiguous())
-        else:
-            fn = self._need('expression_embedder', what)
-            out = fn(crop, theta, True) if isinstance(fn, emb_mod.ExpressionEmbed) else fn(crop, theta)
+        self._need('expression_embedder', what)
+        out = self._expression_pass(crop, theta.float().contiguous())
         if isinstance(out, (tuple, list)):
             return out[0], (out[1] if len(out) > 1 else None)
         return out, None
-
-    def _drive(self, pose, theta):
-        g = self._graphed.get('driver')
-        if g is not None:
-            return g(pose, theta)
-        return self.hot_path.driver_pass(self._canonical_cl, self.idt_embed, pose, theta)
 
     def _need(self, name, what):
         fn = self.embedders.get(name)
@@ -707,36 +710,19 @@ class InferenceWrapper:
         srt = tuple(t.to(self.device).float().contiguous() for t in embed)
         return ops.pose_theta(*srt), srt
 
-    def _smooth_thetas(self, thetas):
-        """notebooks/infer.py:571-581 for a batch of thetas IN FRAME ORDER: the EMA runs once on the host over the 16 floats
-        per frame (hostglue.ema_scan: bit-identical to the reference's per-frame loop of device ops), `self.theta` carries the
-        state between calls as it does there.  One device -> host read of B x 16 floats instead of 3 B tiny launches + clones."""
-        state = None if self.theta is None else self.theta.detach().cpu().numpy()
-        sm, state = hostglue.ema_scan(thetas.detach().float().cpu().numpy(), state, self.pose_momentum)
-        self.theta = torch.from_numpy(state).to(self.device)
-        return torch.from_numpy(sm).to(self.device)
-
-    @staticmethod
-    def _check_smoothing(identities, smooth_pose, smooth_per_identity):
-        """smooth_pose over a bank is one EMA stream PER SLOT, which is not the one stream of the driver video the single-identity
-        path smooths (frames of one driver clip spread over several identities would each skip the others' frames): the caller
-        asks for it explicitly"""
-        if identities is not None and smooth_pose and not smooth_per_identity:
-            raise ValueError("smooth_pose=True smooths one pose stream: with identities= pass smooth_per_identity=True to smooth "
-                             "each identity's frames as a stream of its own")
-
     def _source_theta(self, what):
-        theta = getattr(self, 'pred_source_theta', None)
+        theta = self.pred_source_theta
         if theta is None:
             raise RuntimeError(f"{what} needs the current identity's source theta: call forward with a source_image (or "
                                f"share_source) first")
         return theta.reshape(1, 4, 4).float().contiguous()
 
     def _pose_controls(self, theta, ids_dev, mix, mix_old, smooth):
-        """forward()'s order (infer.py:568-581) on a batch of driver thetas IN FRAME ORDER: mix against each frame's identity
-        (bank slot ids_dev[i], or the current identity), then smooth_pose -- with a bank one stream per slot on the device, else
-        the single stream in `self.theta` (the host scan, as before)"""
-        theta = theta.float().contiguous()
+        """forward()'s order (infer.py:568-581) on a batch of driver thetas IN FRAME ORDER, on the device: mix against each
+        frame's identity (bank slot ids_dev[i], or the current identity), then smooth_pose (ops.theta_ema_scan, bit for bit
+        hostglue.ema_scan = the reference's per-frame loop) -- with a bank one stream per slot, else the single stream whose
+        state `self.theta` ([4,4], None before the first frame) carries from call to call as the reference's does"""
+        theta = theta.to(self.device).float().contiguous()
         if theta.shape[0] == 0:
             return theta
         if mix:
@@ -744,11 +730,16 @@ class InferenceWrapper:
                 theta = ops.mixing_theta(theta, self._source_theta('mix=True'), None, mix_old)
             else:
                 theta = ops.mixing_theta(theta, self._bank_theta, ids_dev, mix_old)
-        if smooth:
-            if ids_dev is None:
-                theta = self._smooth_thetas(theta)
-            else:
-                theta = ops.theta_ema_scan(theta, ids_dev, self._bank_pose, self._bank_pose_has, self.pose_momentum)
+        if smooth and ids_dev is not None:
+            theta = ops.theta_ema_scan(theta, ids_dev, self._bank_pose, self._bank_pose_has, self.pose_momentum)
+        elif smooth:
+            state = torch.zeros((1, 4, 4), device=self.device, dtype=torch.float32)
+            has = torch.zeros((1,), device=self.device, dtype=torch.int32)
+            if self.theta is not None:
+                state.copy_(self.theta.reshape(1, 4, 4))
+                has.fill_(1)
+            theta = ops.theta_ema_scan(theta, None, state, has, self.pose_momentum)
+            self.theta = state[0]
         return theta
 
     def _render_theta(self, theta, ids_dev, target_theta):
@@ -868,7 +859,7 @@ class InferenceWrapper:
             if mix:                                                                                    # infer.py:568-569
                 pred_target_theta = self.get_mixing_theta(self.pred_source_theta, pred_target_theta)
             if smooth_pose:                                                                            # infer.py:571-581
-                pred_target_theta = self._smooth_thetas(pred_target_theta)
+                pred_target_theta = self._pose_controls(pred_target_theta, None, False, mix_old, True)
             self.pred_target_theta = pred_target_theta
             theta_used = pred_target_theta if target_theta else self.pred_source_theta
             # the reference runs the expression embedder on every driver frame (infer.py:596-601) and only then overrides
@@ -908,30 +899,14 @@ class InferenceWrapper:
         them, smooth_pose needs smooth_per_identity=True, and each slot then has its own stream.
         refine=True: every rendered batch goes through the attached stage-2 model (attach_stage2; see animate_frames) and the
         frames come out at its output_size_s2."""
-        masks_of = self._refine_plan(refine, refine_masks)
-        self._check_smoothing(identities, smooth_pose, smooth_per_identity)
         N = target_pose_embeds.shape[0]
-        ids = None if identities is None else self._frame_identities(identities, N)
-        if ids is None and self._canonical_cl is None:
-            raise RuntimeError("call forward with a source_image first")
-        if ids is None and (mix or not target_theta):
-            self._source_theta('mix=True' if mix else 'target_theta=False')
+        masks_of, ids = self._preflight(N, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
         lo, hi = parallel.shard_range(N, self.rank, self.world)
         ids_dev = None if ids is None else ids[lo:hi].to(self.device)
         smoothed = None
         if smooth_pose and N > 0:
             theta = ops.pose_theta(*[t.to(self.device).float().contiguous() for t in target_srt])
-            if ids is None:
-                theta = self._pose_controls(theta, None, mix, mix_old, False)
-                state = torch.zeros((1, 4, 4), device=self.device, dtype=torch.float32)
-                has = torch.zeros((1,), device=self.device, dtype=torch.int32)
-                if self.theta is not None:
-                    state.copy_(self.theta.reshape(1, 4, 4))
-                    has.fill_(1)
-                smoothed = ops.theta_ema_scan(theta, None, state, has, self.pose_momentum)[lo:hi]
-                self.theta = state[0]
-            else:
-                smoothed = self._pose_controls(theta, ids.to(self.device), mix, mix_old, True)[lo:hi]
+            smoothed = self._pose_controls(theta, None if ids is None else ids.to(self.device), mix, mix_old, True)[lo:hi]
         for b0 in range(lo, hi, batch_size):
             b1 = min(b0 + batch_size, hi)
             pose = target_pose_embeds[b0:b1].to(self.device).float().contiguous()
@@ -941,12 +916,34 @@ class InferenceWrapper:
             else:
                 srt = [t[b0:b1].to(self.device).float().contiguous() for t in target_srt]
                 theta = self._pose_controls(ops.pose_theta(*srt), ident, mix, mix_old, False)
-            theta = self._render_theta(theta, ident, target_theta)
-            img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ident)
-            if masks_of is not None:
-                yield b0, self._refine(img, masks_of, "u8" if as_uint8 else "f32")
-                continue
-            yield b0, (ops.pack_rgb8(img) if as_uint8 else img)
+            yield b0, self._render(pose, theta, ident, target_theta, masks_of, "u8" if as_uint8 else "f32")
+
+    def _preflight(self, n_frames, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks):
+        """The checks of the keywords animate() and animate_frames() share, before anything is launched -> (masks_of, ids):
+        _refine_plan's callable or None, and the per-frame slots as a host tensor or None (the current identity)"""
+        masks_of = self._refine_plan(refine, refine_masks)
+        # smooth_pose over a bank is one EMA stream PER SLOT, which is not the one stream of the driver video the single-identity
+        # path smooths (frames of one driver clip spread over several identities would each skip the others' frames): the caller
+        # asks for it explicitly
+        if identities is not None and smooth_pose and not smooth_per_identity:
+            raise ValueError("smooth_pose=True smooths one pose stream: with identities= pass smooth_per_identity=True to smooth "
+                             "each identity's frames as a stream of its own")
+        if identities is not None:
+            return masks_of, self._frame_identities(identities, n_frames)
+        if self._canonical_cl is None:
+            raise RuntimeError("call forward with a source_image first")
+        if mix or not target_theta:
+            self._source_theta('mix=True' if mix else 'target_theta=False')
+        return masks_of, None
+
+    def _render(self, pose, theta, ident, target_theta, masks_of, out):
+        """The tail of a batch: the theta each frame is rendered with, the driver pass of the current identity or of the bank
+        slots `ident`, stage 2 where masks_of is given -> uint8 [b,S,S,3] (out 'u8') or the fp32 image [b,3,S,S] ('f32')"""
+        theta = self._render_theta(theta, ident, target_theta)
+        img = self._drive(pose, theta) if ident is None else self._drive_bank(pose, theta, ident)
+        if masks_of is not None:
+            return self._refine(img, masks_of, out)
+        return ops.pack_rgb8(img) if out == "u8" else img
 
     # ------------------------------------------------------------------------------------------------------
     def _paste_matte(self, paste_matte, what):
@@ -962,17 +959,6 @@ class InferenceWrapper:
             raise ValueError("paste_matte: None, True (embedders['matting']) or a callable img [b,3,S,S] -> [b,1,S,S]")
         return paste_matte
 
-    @staticmethod
-    def _paste_windows(windows):
-        """(x_lo, y_lo, side) per frame, as animate_frames takes them (a fourth entry must repeat the side) -> (x0, y0, s, s)"""
-        out = []
-        for w in windows:
-            w = [int(v) for v in w]
-            if len(w) not in (3, 4) or (len(w) == 4 and w[3] != w[2]):
-                raise ValueError(f"paste window {tuple(w)}: expected (x_lo, y_lo, side)")
-            out.append((w[0], w[1], w[2], w[2]))
-        return out
-
     def paste_back(self, frames_u8, rendered, windows, feather=0.0625, matte=None):
         """The inverse of the crop: `rendered` [N,3,S,S] fp32 (the hot path's image, before emo_pack_rgb8) goes back into the
         frames the crops came from, frame i where its window windows[i] = (x_lo, y_lo, side) was -- resized to side x side
@@ -984,7 +970,7 @@ class InferenceWrapper:
         if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
             raise ValueError("frames must be uint8 [N,H,W,3]")
         fn = self._paste_matte(matte, 'matte=True')
-        wins = windows if isinstance(windows, torch.Tensor) and windows.is_cuda else self._paste_windows(windows)
+        wins = windows if isinstance(windows, torch.Tensor) and windows.is_cuda else frames_mod.square_windows(windows)
         img = rendered.to(self.device).float().contiguous()
         m = None if fn is None else fn(img).to(self.device).float().contiguous()
         full = frames_u8.to(self.device, copy=True).contiguous()
@@ -994,126 +980,80 @@ class InferenceWrapper:
                        mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
                        paste_matte=None, as_uint8=True, refine=False, refine_masks=None):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
-        frame there).  frames: uint8 [N,H,W,3] tensor (host, ideally pinned, or device) or an iterable of such chunks --
-        decoded video frames, uploaded as BYTES.  Per batch, all on the device and without a host synchronisation:
+        frame there).  Per batch, all on the device and without a host synchronisation:
             byte -> fp32 CHW (emo_unpack_rgb8) -> crop windows read in place + bicubic resize to image_size, the whole batch in
-            one launch (emo_resize2d_windows_f32; `windows[i] = (x_lo, y_lo, side)` from the face detector +
-            hostglue.crop_window, host arithmetic; None = whole frame) -> HeadPoseRegressor -> ExpressionEmbed -> hot path ->
-            uint8 HWC.
+            one launch (emo_resize2d_windows_f32) -> HeadPoseRegressor -> ExpressionEmbed -> hot path -> uint8 HWC.
         The driver-side matte (MODNet) of the reference is computed but unused with use_seg=False (infer.py:592-601): skipped.
-        smooth_pose (infer.py:571-581) is a scan over the FRAME ORDER, so it runs before the frames are sharded (SURVEY.md
-        section 8e): per chunk, every rank regresses the head pose of its own shard, the thetas (16 floats per frame) are
-        gathered on every rank, the EMA runs once on the host over the whole chunk (hostglue.ema_scan, state carried from chunk
-        to chunk in `self.theta` exactly as the reference carries it from call to call), and only then does each rank render
-        its shard with its slice of the smoothed thetas -- 1 rank and N ranks produce the same frames.  That pass costs one
-        host synchronisation per chunk; the crops of the shard stay resident between the two passes (3 MB per frame).
-        to_host: results go D2H into a ring of `ring` pinned buffers on a copy stream; a batch is yielded once ITS copy
-        event has completed, i.e. the host only ever waits for a batch that is `ring - 1` batches behind the GPU.
-        Yields (first_frame_index, uint8 [b,S,S,3]) -- a view of a pinned ring slot, valid ONLY until the generator is resumed
-        (the next batch's copy may be queued into the same slot right away: consume or copy it before calling next()) --
-        or, with to_host=False, the device tensor.  Frames are sharded contiguously across ranks as in animate().
+        Frames are sharded contiguously across ranks as in animate().  Yields (first_frame_index, uint8 [b,S,S,3]).
+        frames: uint8 [N,H,W,3] tensor (host, ideally pinned, or device) or an iterable of such chunks -- decoded video frames,
+            uploaded as BYTES, span i + 1 beside the compute of span i (frames.uploaded).
+        windows: windows[i] = (x_lo, y_lo, side) from the face detector + hostglue.crop_window, host arithmetic; None = whole
+            frame.
+        to_host, ring: results go D2H into a ring of `ring` pinned buffers on a copy stream (frames.HostRing); a batch is
+            yielded once ITS copy event has completed, i.e. the host only ever waits for a batch that is `ring - 1` batches
+            behind the GPU.  What is yielded is a view of a pinned ring slot, valid ONLY until the generator is resumed (the
+            next batch's copy may be queued into the same slot right away: consume or copy it before calling next()) -- or,
+            with to_host=False, the device tensor.
         identities: slot of the identity bank per frame, over the whole frame stream (as in animate()).
         mix / mix_old / target_theta: forward()'s pose controls (infer.py:568-569, :584), per frame against that frame's
-        identity, on the device (ops.mixing_theta; a gather of the bank's source thetas).  The order is forward()'s: regressed
-        theta -> mix -> smooth_pose -> expression embedder -> render (with the source theta if target_theta=False).  With
-        identities, smooth_pose needs smooth_per_identity=True (else ValueError): each frame is then smoothed within its own
-        identity's frame sequence, as if every identity had its own wrapper: one stream per slot, scanned on the device (ops.theta_ema_scan) over the whole gathered chunk on every rank, so
-        the slot states stay identical across ranks; store_identity / drop_identity / reset_pose_state reset a slot's stream.
-        paste_back=True: frames in -> FRAMES out.  Each batch's rendered fp32 image goes back into the batch's uploaded frame bytes
-        where the crop windows were (paste_back(); one launch, emo_paste_windows_rgb8, in place of emo_pack_rgb8) and what is
-        yielded is (first_frame_index, uint8 [b,Hf,Wf,3]); the pinned ring then holds full frames (a chunk of another frame size
-        gets a new ring).  Needs `windows` (ValueError otherwise, before anything is launched), sides >= image_size / 4.  A host
-        chunk's device copy is private and is pasted into in place; a device-resident chunk is cloned span by span: the caller's
-        frames stay untouched.  With smooth_pose the head-pose pass keeps crops, not frames, so the render pass uploads the
-        spans of a host chunk once more.  feather: width of the blended edge as a fraction of the window side (1/16: a taste
-        default, not a measured optimum); paste_matte: None, a callable img [b,3,S,S] -> [b,1,S,S] in [0,1], or True =
-        embedders['matting'].  Each rank pastes its own shard: no collective.
+            identity, on the device (ops.mixing_theta; a gather of the bank's source thetas).  The order is forward()'s:
+            regressed theta -> mix -> smooth_pose -> expression embedder -> render (with the source theta if
+            target_theta=False).
+        smooth_pose (infer.py:571-581) is a scan over the FRAME ORDER, so it runs before the frames are sharded (SURVEY.md
+            section 8e): per chunk, every rank regresses the head pose of its own shard, the thetas (16 floats per frame) are
+            gathered on every rank, the EMA runs once on the device over the whole chunk (ops.theta_ema_scan, bit for bit
+            hostglue.ema_scan; state carried from chunk to chunk in `self.theta` exactly as the reference carries it from
+            call to call), and only then does each rank render its shard with its slice of the smoothed thetas -- 1 rank and
+            N ranks produce the same frames, and the pass needs no host synchronisation.  The crops of the shard stay
+            resident between the two passes (3 MB per frame).
+        smooth_per_identity: with identities, smooth_pose needs smooth_per_identity=True (else ValueError): each frame is then
+            smoothed within its own identity's frame sequence, as if every identity had its own wrapper: one stream per slot,
+            scanned over the whole gathered chunk on every rank, so the slot states stay identical across ranks;
+            store_identity / drop_identity / reset_pose_state reset a slot's stream.
+        paste_back=True: frames in -> FRAMES out.  Each batch's rendered fp32 image goes back into the batch's uploaded frame
+            bytes where the crop windows were (paste_back(); one launch, emo_paste_windows_rgb8, in place of emo_pack_rgb8) and
+            what is yielded is (first_frame_index, uint8 [b,Hf,Wf,3]); the pinned ring then holds full frames (a chunk of
+            another frame size gets a new ring).  Needs `windows` (ValueError otherwise, before anything is launched), sides
+            >= image_size / 4.  A host chunk's device copy is private and is pasted into in place; a device-resident chunk is
+            cloned span by span: the caller's frames stay untouched.  With smooth_pose the head-pose pass keeps crops, not
+            frames, so the render pass uploads the spans of a host chunk once more.  Each rank pastes its own shard: no
+            collective.
+        feather: width of the blended edge as a fraction of the window side (1/16: a taste default, not a measured optimum).
+        paste_matte: None, a callable img [b,3,S,S] -> [b,1,S,S] in [0,1], or True = embedders['matting'].
         as_uint8=False (with to_host=False, without paste_back): the fp32 [b,3,S,S] device image itself, as animate() yields it
-        -- what paste_back() takes as `rendered` (with captured graphs it is the graph's output buffer: consume or clone it
-        before resuming the generator).
-        refine=True: stage 2 in the path (attach_stage2 first; ValueError before anything is launched otherwise).  Per batch,
-        where the hot path returns its image: bilinear resize to the stage-2 model's output_size_s2 if that differs from
-        image_size (infer_s2.py:360-362) -> the matte and the face mask of the resized image from the attached wrapper's
-        'matting' / 'face_parsing' callables (all ones for the face mask with its `cloth`), or both from refine_masks=img ->
-        (mask, face_mask); eager, third-party nets -> Stage2.refine_frames, a captured graph with use_graphs, whose last launch
-        (emo_stage2_head_f32) writes the bytes that go to the ring, or the fp32 image that paste_back=True pastes
-        (paste_matte is then computed on the refined image, and window sides are held to output_size_s2 / 4) or that
-        as_uint8=False yields.  Yielded crops are [b,S2,S2,3].  identities, the pose controls and smooth_pose are untouched:
-        refinement starts where the render returns, and every rank refines its own shard."""
-        matte_fn = None
+            -- what paste_back() takes as `rendered` (with captured graphs it is the graph's output buffer: consume or clone
+            it before resuming the generator).
+        refine=True, refine_masks: stage 2 in the path (attach_stage2 first; ValueError before anything is launched otherwise).
+            Per batch, where the hot path returns its image: bilinear resize to the stage-2 model's output_size_s2 if that
+            differs from image_size (infer_s2.py:360-362) -> the matte and the face mask of the resized image from the attached
+            wrapper's 'matting' / 'face_parsing' callables (all ones for the face mask with its `cloth`), or both from
+            refine_masks=img -> (mask, face_mask); eager, third-party nets -> Stage2.refine_frames, a captured graph with
+            use_graphs, whose last launch (emo_stage2_head_f32) writes the bytes that go to the ring, or the fp32 image that
+            paste_back=True pastes (paste_matte is then computed on the refined image, and window sides are held to
+            output_size_s2 / 4) or that as_uint8=False yields.  Yielded crops are [b,S2,S2,3].  identities, the pose controls
+            and smooth_pose are untouched: refinement starts where the render returns, and every rank refines its own shard."""
         if not as_uint8 and (to_host or paste_back):
             raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
-        masks_of = self._refine_plan(refine, refine_masks)
-        S_out = self.cfg["image_size"] if masks_of is None else self._stage2.cfg["output_size_s2"]
+        masks_of, ids = self._preflight(frames.shape[0] if isinstance(frames, torch.Tensor) else None, identities, mix,
+                                        target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
+        wins = None if windows is None else frames_mod.square_windows(windows)
+        matte_fn = None
         if paste_back:
-            if windows is None:
+            if wins is None:
                 raise ValueError("paste_back=True needs windows=: one (x_lo, y_lo, side) per frame says where each rendered crop goes")
             if not 0.0 <= float(feather) <= 0.5:
                 raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
             matte_fn = self._paste_matte(paste_matte, 'paste_matte=True')
-            paste_wins = self._paste_windows(windows)
-            if any(4 * w[2] < S_out for w in paste_wins):
+            S_out = self.cfg["image_size"] if masks_of is None else self._stage2.cfg["output_size_s2"]
+            if any(4 * w[2] < S_out for w in wins):
                 raise ValueError(f"a paste window is smaller than a quarter of the {S_out}-pixel image: downscaling "
                                  f"stops at image_size / 4")
-        ids = None
-        self._check_smoothing(identities, smooth_pose, smooth_per_identity)
-        if identities is not None:
-            ids = self._frame_identities(identities, frames.shape[0] if isinstance(frames, torch.Tensor) else None)
-        elif self._canonical_cl is None:
-            raise RuntimeError("call forward with a source_image first")
-        elif mix or not target_theta:
-            self._source_theta('mix=True' if mix else 'target_theta=False')
         S = self.cfg["image_size"]
-        chunks = [frames] if isinstance(frames, torch.Tensor) else frames
-        copy_stream = torch.cuda.Stream(device=self.device) if to_host else None
-        slots, pending = [], []          # pinned buffers; (first index, slot, n frames, event) in flight
-
-        def drain(keep):
-            while len(pending) > keep:
-                b0, slot, nb, ev = pending.pop(0)
-                ev.synchronize()
-                yield b0, slots[slot][:nb]
-
+        out_kind = "f32" if paste_back or not as_uint8 else "u8"
+        host_ring = frames_mod.HostRing(self.device, ring, batch_size) if to_host else None
         upload_stream = torch.cuda.Stream(device=self.device)
-
-        def uploaded(chunk, spans):
-            """(b0, b1, uint8 frames on the device) for every span, with the upload of span i + 1 enqueued on a copy stream BEFORE
-            span i is handed out -- i.e. before its kernels are enqueued -- so that a host chunk's H2D copy (12.6 MB per 16 frames
-            at 512^2: 0.25 ms) runs beside the previous batch's compute instead of in front of its own (on the compute stream the
-            copy serialises with the kernels).  Device-resident chunks pass through."""
-            ahead = None
-            for span in list(spans) + [None]:
-                nxt = None
-                if span is not None:
-                    b0, b1 = span
-                    src = chunk[b0:b1]
-                    if src.is_cuda:
-                        nxt = (b0, b1, src.contiguous(), None)
-                    else:
-                        with torch.cuda.stream(upload_stream):
-                            t = src.to(self.device, non_blocking=True)
-                            ev = torch.cuda.Event()
-                            ev.record(upload_stream)
-                        nxt = (b0, b1, t, ev)
-                if ahead is not None:
-                    p0, p1, t, ev = ahead
-                    if ev is not None:
-                        torch.cuda.current_stream().wait_event(ev)
-                        t.record_stream(torch.cuda.current_stream())
-                    yield p0, p1, t
-                ahead = nxt
-
-        def crops_of(u8, base, b0, b1):
-            x = ops.unpack_rgb8(u8)
-            if windows is not None:
-                wins = [(w[0], w[1], w[2], w[2]) for w in windows[base + b0:base + b1]]
-                return ops.resize2d_windows(x, (S, S), wins, "bicubic", clamp01=True)
-            if x.shape[-2:] != (S, S):
-                return ops.resize2d(x, (S, S), "bicubic")
-            return x
-
-        base, k = 0, 0
-        for chunk in chunks:
+        base = 0
+        for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
             if chunk.dtype != torch.uint8 or chunk.dim() != 4 or chunk.shape[-1] != 3:
                 raise ValueError("frames must be uint8 [N,H,W,3]")
             n = chunk.shape[0]
@@ -1123,12 +1063,13 @@ class InferenceWrapper:
             ids_dev = None if ids is None else ids[base + lo:base + hi].to(self.device)
             ids_chunk = None if ids is None or not smooth_pose else ids[base:base + n].to(self.device)
             spans = [(b0, min(b0 + batch_size, hi)) for b0 in range(lo, hi, batch_size)]
+            crops_of = lambda u8, b0, b1: frames_mod.crops_of(u8, S, None if wins is None else wins[base + b0:base + b1])
             smoothed, kept = None, {}
             if smooth_pose:
                 keep_crops = (hi - lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
                 local = []
-                for b0, b1, u8 in uploaded(chunk, spans):
-                    crops = crops_of(u8, base, b0, b1)
+                for b0, b1, u8 in frames_mod.uploaded(chunk, spans, self.device, upload_stream):
+                    crops = crops_of(u8, b0, b1)
                     local.append(self._head_pose(crops)[0].clone())
                     if keep_crops:
                         kept[b0] = crops
@@ -1140,14 +1081,14 @@ class InferenceWrapper:
             # (every span whose crops stayed resident from the head-pose pass needs no second upload -- unless its frames are
             # what the render is pasted into: the crops were kept, 3 MB per frame, not the frames, 6 MB at 1080p)
             todo = spans if paste_back else [sp for sp in spans if sp[0] not in kept]
-            fresh = uploaded(chunk, todo)
+            fresh = frames_mod.uploaded(chunk, todo, self.device, upload_stream)
             for b0, b1 in spans:
                 crops = kept.pop(b0, None)
                 if crops is None or paste_back:
                     f0, f1, u8 = next(fresh)
                     assert (f0, f1) == (b0, b1)
                     if crops is None:
-                        crops = crops_of(u8, base, b0, b1)
+                        crops = crops_of(u8, b0, b1)
                 ident = None if ids is None else ids_dev[b0 - lo:b1 - lo]
                 if smoothed is not None:
                     theta = smoothed[b0 - lo:b1 - lo]
@@ -1157,39 +1098,18 @@ class InferenceWrapper:
                         theta = self._pose_controls(theta, ident, True, mix_old, False)
                 self.pred_target_theta = theta                                   # (as forward() leaves it: infer.py:584)
                 pose, _ = self._expression(crops, theta, 'a driver call')
-                theta = self._render_theta(theta, ident, target_theta)
-                img = self._drive(pose, theta) if ids is None else self._drive_bank(pose, theta, ident)
-                if masks_of is not None:
-                    img = self._refine(img, masks_of, "f32" if paste_back or not as_uint8 else "u8")
+                out = self._render(pose, theta, ident, target_theta, masks_of, out_kind)
                 if paste_back:
                     full = u8.clone() if chunk.is_cuda else u8                   # (a host chunk's upload is this span's own)
-                    out = ops.paste_windows(full, img, paste_wins[base + b0:base + b1], feather,
-                                            None if matte_fn is None else matte_fn(img).float().contiguous())
-                elif masks_of is not None:
-                    out = img                                                    # (bytes or fp32, as asked of the stage-2 tail)
+                    out = ops.paste_windows(full, out, wins[base + b0:base + b1], feather,
+                                            None if matte_fn is None else matte_fn(out).float().contiguous())
+                if to_host:
+                    yield from host_ring.push(base + b0, out)
                 else:
-                    out = ops.pack_rgb8(img) if as_uint8 else img
-                if not to_host:
                     yield base + b0, out
-                    continue
-                if slots and slots[0].shape[1:] != out.shape[1:]:                # full frames of another size: a new ring
-                    yield from drain(0)
-                    slots.clear()
-                    k = 0
-                if len(slots) < ring:
-                    slots.append(torch.empty((batch_size,) + tuple(out.shape[1:]), dtype=torch.uint8, pin_memory=True))
-                slot = k % ring
-                k += 1
-                copy_stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(copy_stream):
-                    slots[slot][:b1 - b0].copy_(out, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(copy_stream)
-                out.record_stream(copy_stream)
-                pending.append((base + b0, slot, b1 - b0, ev))
-                yield from drain(ring - 1)
             base += n
-        yield from drain(0)
+        if to_host:
+            yield from host_ring.drain()
 
     def share_source(self, src_rank=0):
         """RCCL broadcast of the per-identity cache computed on `src_rank`: canonical volume
@@ -1199,8 +1119,7 @@ class InferenceWrapper:
         # receivers learn its shape from the broadcast header; what the warp embedding needs is checked on the source rank
         es = self.cfg["gen_embed_size"]
         cache = parallel.broadcast_source_cache(
-            dict(canonical=self.target_latent_volume, idt_embed=getattr(self, 'idt_embed', None),
-                 theta_src=getattr(self, 'pred_source_theta', None)),
+            dict(canonical=self.target_latent_volume, idt_embed=self.idt_embed, theta_src=self.pred_source_theta),
             shapes=dict(canonical=(1, c, d, s, s), theta_src=(1, 4, 4)), names=['canonical', 'idt_embed', 'theta_src'],
             src=src_rank, device=self.device, world=self.world, rank=self.rank)
         if cache["idt_embed"].numel() != self.cfg["gen_max_channels"] * es * es:

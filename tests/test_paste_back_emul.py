@@ -213,9 +213,9 @@ def wrapper(monkeypatch, lib):
     w = object.__new__(InferenceWrapper)
     w.device, w.rank, w.world = torch.device("cpu"), 0, 1
     w.cfg = dict(image_size=128)
-    w.embedders, w._graphed, w.theta = {}, {}, None
+    w._init_state(use_graphs=False)
+    w.embedders = {}
     w._canonical_cl = torch.zeros(1)
-    w.identity_capacity = 0
     w.lib = facade
     return w
 

@@ -283,11 +283,8 @@ def wrapper(monkeypatch):
     w.device, w.rank, w.world = torch.device("cpu"), 0, 1
     w.cfg = dict(latent_volume_channels=4, latent_volume_depth=2, latent_volume_size=2, gen_embed_size=1, gen_max_channels=4,
                  image_size=8)
-    w.pose_momentum, w.theta, w.use_graphs, w._graphed, w.embedders = 0.3, None, False, {}, {}
-    w._canonical_cl = None
-    w.center = w.size = w.delta_yaw = w.delta_pitch = w._crop_tracker = None
-    w.target_latent_volume = None
-    w._init_identity_bank(3)
+    w._init_state(use_graphs=False, identity_capacity=3, pose_momentum=0.3)
+    w.embedders = {}
     th = corpus(lib)
     w.src_thetas = [torch.from_numpy(th[k]) for k in (2, 41, 47)]          # a pose_theta, a reflection, an ill-conditioned one
     for k in range(3):

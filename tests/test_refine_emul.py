@@ -54,9 +54,9 @@ def rig(monkeypatch):
     w = object.__new__(InferenceWrapper)
     w.device, w.rank, w.world = torch.device("cpu"), 0, 1
     w.cfg = dict(image_size=S)
-    w.pose_momentum, w.theta, w.use_graphs, w._graphed, w.embedders = 0.3, None, False, {}, {}
+    w._init_state(use_graphs=False, pose_momentum=0.3)
+    w.embedders = {}
     w._canonical_cl = torch.zeros(1)
-    w.identity_capacity = 0
     w.driven = []
 
     def drive(pose, theta):
