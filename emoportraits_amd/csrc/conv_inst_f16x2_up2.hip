@@ -17,14 +17,29 @@
 //   (cg, h)  steps 0 .. 2  pieces 2 .. 7 of the next half-stage's kernel into W[h ^ 1]
 //            step 3        barrier; pieces 0, 1 of the half-stage after it into W[h]; fragments of the next half-stage's step 0
 //   (cg, 0)  steps 0 .. 3  the patch of stage cg + 1 converted from the raw registers into P[pp ^ 1], one pixel per step
-//   (cg, 1)  steps 0 .. 2  the raw loads of stage cg + 2
+//   (cg, 0)  step 3        behind the last pixel's conversion: the raw loads of stage cg + 2 -- four tap steps (48 MFMAs) ahead of
+//                          the barrier of (cg, 1) that drains them (EMO_UP2_LOADS_EARLY = 0: steps 0 .. 2 of (cg, 1), one to
+//                          three steps of flight)
 // Epilogue: through LDS, 32 channels at a time -- the waves' column phases interleaved into whole 128-column high-res rows, + bias,
 // 16-byte stores, the (mean, M2) of the two 4 x 64 tiles (the TileStats layout of block config D).  No residual, no activation.
+// CHAINED items (EMO_UP2_CHAIN, the scheme of conv_igemm_f16x2_ct2.h): when the block's next item belongs to the same sample (same
+// scale / shift tables) and the item has >= 2 stages, the look-ahead of the last two stages -- dead re-stages otherwise -- fetches
+// the next item's first stage instead: kernel (stage 0, p = 0) into W[0], the raw loads of its stages 0 and 1 with ITS cursor, its
+// stage-0 patch converted into P[pp ^ 1].  The epilogue image lies in W[1] and the tail of LDS (dead at an item's end: the last
+// half-stage read W[1]), so P, W[0] and the tables survive it, and the next item starts with a short prologue: its bias entries
+// (fetched during the epilogue), pieces 0, 1 of (stage 0, p = 1) into W[1], one barrier that waits for no memory operation.
 // The kernel lives in this instantiation file (not a header) so that the CPU emulation of tests/emul/convlib.py, which rewrites
 // the instantiation files and a fixed list of headers, compiles it.
 #include "conv_dispatch.h"
 #include "conv_igemm_bf16x3.h"
 #include "conv_split_pair_common.h"
+
+#ifndef EMO_UP2_CHAIN
+#define EMO_UP2_CHAIN 1         /* 0: A/B builds -- every item runs the full prologue */
+#endif
+#ifndef EMO_UP2_LOADS_EARLY
+#define EMO_UP2_LOADS_EARLY 1   /* 0: A/B builds -- the raw loads of stage cg + 2 at steps 0 .. 2 of half-stage (cg, 1) */
+#endif
 
 struct ConvCfgUp2 {
   static constexpr int BM = 64, TM = 2, TP = 2, KC = 16, NPL = 2;
@@ -38,12 +53,16 @@ struct ConvCfgUp2 {
   static constexpr int WST = 8 * WTAP;                   // a half-stage's kernel: [q][a][b][plane][half][BM] -- 32 KiB
   static constexpr int WST_BYTES = WST * 16;
   static constexpr int PPL = NG * CHS, PBUF = NPL * PPL;
-  static constexpr int OFF_P = 0, OFF_W = 2 * PBUF, OFF_SCT = OFF_W + 2 * WST;
+  // LDS: P[0], P[1] | W[0] | scale / shift tables, bias | W[1] | tail.  The epilogue image starts at W[1] and runs into the tail
   static constexpr int SCT = 1024;
+  static constexpr int OFF_P = 0, OFF_W = 2 * PBUF, OFF_SCT = OFF_W + WST;
+  static constexpr int WSTRIDE = WST + (2 * SCT + BM) / 4;           // W[1] = W[0] + WSTRIDE: behind the tables and the bias
   static constexpr int OFF_BIAS_F = OFF_SCT * 4 + 2 * SCT;          // (float index) [BM]
   static constexpr int EPI_CS = 4 * 132 + 4;                         // floats per channel of the epilogue image: 4 rows of 128 + 4
-  static constexpr int LDS_BYTES = (OFF_BIAS_F + BM) * 4;
-  static_assert(32 * EPI_CS <= OFF_SCT * 4, "the epilogue image lives in the patch and kernel buffers");
+  static constexpr int OFF_IMG_F = (OFF_W + WSTRIDE) * 4;            // (float index) the image: over W[1] and the tail
+  static constexpr int LDS_BYTES = (OFF_IMG_F + 32 * EPI_CS) * 4;
+  static_assert(OFF_IMG_F >= OFF_BIAS_F + BM, "the epilogue image spares the patch buffers, W[0], the tables and the bias: a chained successor's");
+  static_assert(32 * EPI_CS * 4 >= WST_BYTES, "W[1] lies inside the image's allocation");
   static_assert(WST_BYTES == 32 * 1024, "eight 1 KiB pieces per wave and half-stage");
   static_assert(PR * NQ + NHQ <= QPG, "one interior quad or one halo pixel per thread and stage");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
@@ -117,7 +136,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
 #define EMO_U_LOAD_FRAGS_PLANE(set_, pl_, hb_, pbyte_, a_, b_)                                        \
   {                                                                                                   \
     _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                    \
-      fa_[set_][pl_][i] = *reinterpret_cast<const opx8*>(lds_c + a_off + (Cfg::OFF_W + (hb_) * Cfg::WST + \
+      fa_[set_][pl_][i] = *reinterpret_cast<const opx8*>(lds_c + a_off + (Cfg::OFF_W + (hb_) * Cfg::WSTRIDE + \
           ((wq * 4 + (a_) * 2 + (b_)) * NPL + (pl_)) * Cfg::WPLANE + i * 32) * 16);                   \
     _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                    \
       fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + (EMO_P_B_OFF(j, (hb_) + (a_), wq + (b_)) + (pbyte_)) + ((pl_) * PPL) * 16); \
@@ -181,65 +200,138 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
 #define EMO_U_DMA_PIECE(ptr_, wb_, k_)                                                                \
   {                                                                                                   \
     const int j_ = wave + 4 * (k_);                                                                   \
-    emo_dma16_pinned_s((ptr_) + j_ * 1024, lane16, smem_lds + (unsigned)((Cfg::OFF_W + (wb_) * Cfg::WST) * 16 + j_ * 1024)); \
+    emo_dma16_pinned_s((ptr_) + j_ * 1024, lane16, smem_lds + (unsigned)((Cfg::OFF_W + (wb_) * Cfg::WSTRIDE) * 16 + j_ * 1024)); \
   }
 
   constexpr int PA3[3] = {1, 0, 0}, PB3[3] = {0, 1, 0};
   constexpr int NTE = Cfg::SCT / 256;
 
+// work item l -> (sample, low-res tile, channel tile); every result through readfirstlane (conv_igemm_bf16x3.h)
+#define EMO_U_DECODE(P_, L_)                                                                          \
+  {                                                                                                   \
+    const int l_ = (L_);                                                                              \
+    P_##cotile = __builtin_amdgcn_readfirstlane(l_ % a.n_cotiles);                                    \
+    const int rest_ = l_ / a.n_cotiles;                                                               \
+    P_##n = __builtin_amdgcn_readfirstlane(rest_ / nptiles);                                          \
+    const int lt_ = rest_ - P_##n * nptiles;                                                          \
+    P_##x0 = __builtin_amdgcn_readfirstlane((lt_ % a.tiles_x) * Cfg::TWL);     /* low-res origin */   \
+    P_##y0 = __builtin_amdgcn_readfirstlane((lt_ / a.tiles_x) * Cfg::TRL);                            \
+  }
+// the lane's 16-byte patch load for the tile of item P_ and whether it lies inside the image
+#define EMO_U_CURSOR_OF(P_, ok_, off_)                                                                \
+  {                                                                                                   \
+    const int q_y_ = P_##y0 - 1 + q_r;                                                                \
+    const int q_x_ = is_quad ? P_##x0 + 4 * q_c : (h_side ? P_##x0 + TWS : P_##x0 - 4);               \
+    ok_ = (is_quad || is_halo) && (unsigned)q_y_ < (unsigned)a.H && q_x_ >= 0 && q_x_ < a.W;          \
+    off_ = ok_ ? (unsigned)(q_y_ * a.W + q_x_) * 4u : 0u;                                             \
+  }
+// the raw loads of stage cg + 2, first part; past the item's end: the next item's stages 0 / 1 with its cursor (chained), a dead
+// re-load of the last stage otherwise.  Indices are SELECTED: no branch
+#define EMO_U_NEXT_STAGE_BEGIN()                                                                      \
+  {                                                                                                   \
+    const bool sw_ = chain_out && cg + 2 == nst;                                                      \
+    const int tgt_ = (chain_out && cg + 2 >= nst) ? cg + 2 - nst : (cg + 2 < nst ? cg + 2 : nst - 1); \
+    lq_ok = sw_ ? nxq_ok : lq_ok;                                                                     \
+    lq_off = sw_ ? nxq_off : lq_off;                                                                  \
+    EMO_U_ISSUE_BEGIN(tgt_)                                                                           \
+  }
+#if EMO_S_TIMING == 2
+// measurement build: the cycles a wave sits in the waitcnt of a K-loop barrier and in the s_barrier itself (conv_igemm_bf16x3.h)
+#define EMO_U_LOOP_BARRIER(n_)                                                                        \
+  {                                                                                                   \
+    const unsigned long long b0_ = __builtin_amdgcn_s_memtime();                                      \
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(n_) : "memory");                              \
+    const unsigned long long b1_ = __builtin_amdgcn_s_memtime();                                      \
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                  \
+    const unsigned long long b2_ = __builtin_amdgcn_s_memtime();                                      \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                \
+    tw_wait += b1_ - b0_; tw_bar += b2_ - b1_; ++tw_n;                                                \
+  }
+#else
+#define EMO_U_LOOP_BARRIER(n_) EMO_P_BARRIER(n_)
+#endif
+
+  constexpr bool CHAIN = EMO_UP2_CHAIN != 0, LOADS_EARLY = EMO_UP2_LOADS_EARLY != 0;
+  float te_b = 0.0f;
+  bool chained_in = false;                 // this item's first stage (and the loads of its second) were staged by the previous item
+  int pp = 0;                              // patch buffer of the item's current stage
   for (int idx8 = blockIdx.x >> 3; idx8 < n_mine; idx8 += l_stride) {
-    // ---- item ----
-    const int l_ = l_base + idx8;
-    const int cotile = __builtin_amdgcn_readfirstlane(l_ % a.n_cotiles);
-    const int rest_ = l_ / a.n_cotiles;
-    const int it_n = __builtin_amdgcn_readfirstlane(rest_ / nptiles);
-    const int lt_ = rest_ - it_n * nptiles;
-    const int x0 = __builtin_amdgcn_readfirstlane((lt_ % a.tiles_x) * Cfg::TWL);     // low-res origin
-    const int y0 = __builtin_amdgcn_readfirstlane((lt_ / a.tiles_x) * Cfg::TRL);
+#if EMO_S_TIMING
+    unsigned long long tstamp[12];     // measurement builds (tools/conv_phase_timing.py): s_memtime at the phase boundaries
+    for (int k = 0; k < 12; ++k) tstamp[k] = 0;
+    unsigned long long tw_wait = 0, tw_bar = 0, tw_n = 0;
+#endif
+    EMO_S_STAMP(0)
+    // ---- item, and the block's next one ----
+    int cotile, it_n, x0, y0;
     {
-      const int q_y_ = y0 - 1 + q_r;
-      const int q_x_ = is_quad ? x0 + 4 * q_c : (h_side ? x0 + TWS : x0 - 4);
-      lq_ok = (is_quad || is_halo) && (unsigned)q_y_ < (unsigned)a.H && q_x_ >= 0 && q_x_ < a.W;
-      lq_off = lq_ok ? (unsigned)(q_y_ * a.W + q_x_) * 4u : 0u;
+      int it_cotile, it_x0, it_y0;
+      EMO_U_DECODE(it_, l_base + idx8)
+      cotile = it_cotile; x0 = it_x0; y0 = it_y0;
+    }
+    int nx_cotile = 0, nx_n = 0, nx_x0 = 0, nx_y0 = 0;
+    bool chain_out = false, nxq_ok = false;
+    unsigned nxq_off = 0;
+    if (CHAIN && idx8 + l_stride < n_mine) {
+      EMO_U_DECODE(nx_, l_base + idx8 + l_stride)
+      chain_out = nx_n == it_n && nst >= 2;
+      EMO_U_CURSOR_OF(nx_, nxq_ok, nxq_off)
     }
     xrs = emo_raw_buffer(a.x + (long)it_n * a.Cin * HW);
-
-    // ---- prologue: tables, bias, the whole kernel of (stage 0, p = 0), pieces 0, 1 of (0, 1), patch 0 converted, loads of stage 1 ----
-#pragma unroll
-    for (int u = 0; u < 8; ++u) asm volatile("" : "=v"(qv[u]));
     asm volatile("" : "=v"(cv_h));
     asm volatile("" : "=v"(cv_m));
-    {
-      const char* const w0_ = EMO_U_WPTR(cotile, 0, 0);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) EMO_U_DMA_PIECE(w0_, 0, k)
+    if (CHAIN && chained_in) {
+      // ---- chained prologue: P[pp] holds the converted patch of stage 0, W[0] the kernel of (stage 0, p = 0), qv the landed loads
+      //      of stage 1, the tables are the sample's.  What is left: the bias entries and pieces 0, 1 of (0, 1), which had no live
+      //      buffer to land in (W[1] was the epilogue image).  The barrier waits for NO memory operation: the pieces are drained
+      //      by the barrier of (0, 0), the previous item's stores drain behind the first tap steps ----
+      if (tid < BM) smem[Cfg::OFF_BIAS_F + tid] = te_b;
       const char* const w1_ = EMO_U_WPTR(cotile, 0, 1);
       EMO_U_DMA_PIECE(w1_, 1, 0)
       EMO_U_DMA_PIECE(w1_, 1, 1)
-    }
-    EMO_U_ISSUE_BEGIN(0)
-    EMO_U_ISSUE_LOADS(0, 8)
-#pragma unroll
-    for (int k = 0; k < NTE; ++k) {       // (without an affine the index wraps at SCT: identity entries)
-      const int c = tid + 256 * k;
-      if (c < min(a.Cin, Cfg::SCT)) {
-        const bool real = has_affine;
-        sct[c] = (real ? a.scale[(long)it_n * a.Cin + c] : 1.0f) * in_scale;
-        sct[Cfg::SCT + c] = (real ? a.shift[(long)it_n * a.Cin + c] : 0.0f) * in_scale;
+      EMO_P_BARRIER(40);                  // (at most 2 x 18 stores of the epilogue + these two pieces are outstanding)
+    } else {
+      // ---- full prologue: tables, bias, the whole kernel of (stage 0, p = 0), pieces 0, 1 of (0, 1), patch 0 converted, loads of stage 1 ----
+      {
+        int it_x0 = x0, it_y0 = y0;
+        EMO_U_CURSOR_OF(it_, lq_ok, lq_off)
       }
-    }
-    if (tid < BM) smem[Cfg::OFF_BIAS_F + tid] = a.bias != nullptr ? a.bias[cotile * BM + tid] : 0.0f;
-    EMO_P_WAIT(0);
-    EMO_U_TOUCH_QUAD()
-    __syncthreads();   // scale / shift tables visible
 #pragma unroll
-    for (int i = 0; i < 4; ++i) EMO_U_CONV_PIXEL(Cfg::OFF_P * 16, i)
-    EMO_U_ISSUE_BEGIN(nst > 1 ? 1 : 0)
-    EMO_U_ISSUE_LOADS(0, 8)
-    EMO_P_BARRIER(0);                    // (P[0] visible, W[0] and the loads of stage 1 landed)
-    EMO_U_TOUCH_QUAD()
+      for (int u = 0; u < 8; ++u) asm volatile("" : "=v"(qv[u]));
+      {
+        const char* const w0_ = EMO_U_WPTR(cotile, 0, 0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) EMO_U_DMA_PIECE(w0_, 0, k)
+        const char* const w1_ = EMO_U_WPTR(cotile, 0, 1);
+        EMO_U_DMA_PIECE(w1_, 1, 0)
+        EMO_U_DMA_PIECE(w1_, 1, 1)
+      }
+      EMO_U_ISSUE_BEGIN(0)
+      EMO_U_ISSUE_LOADS(0, 8)
+#pragma unroll
+      for (int k = 0; k < NTE; ++k) {       // (without an affine the index wraps at SCT: identity entries)
+        const int c = tid + 256 * k;
+        if (c < min(a.Cin, Cfg::SCT)) {
+          const bool real = has_affine;
+          sct[c] = (real ? a.scale[(long)it_n * a.Cin + c] : 1.0f) * in_scale;
+          sct[Cfg::SCT + c] = (real ? a.shift[(long)it_n * a.Cin + c] : 0.0f) * in_scale;
+        }
+      }
+      if (tid < BM) smem[Cfg::OFF_BIAS_F + tid] = a.bias != nullptr ? a.bias[cotile * BM + tid] : 0.0f;
+      EMO_P_WAIT(0);
+      EMO_U_TOUCH_QUAD()
+      __syncthreads();   // scale / shift tables visible
+#pragma unroll
+      for (int i = 0; i < 4; ++i) EMO_U_CONV_PIXEL(Cfg::OFF_P * 16, i)
+      EMO_U_ISSUE_BEGIN(nst > 1 ? 1 : 0)
+      EMO_U_ISSUE_LOADS(0, 8)
+      EMO_P_BARRIER(0);                    // (P[0] visible, W[0] and the loads of stage 1 landed)
+      EMO_U_TOUCH_QUAD()
+      pp = 0;
+    }
 
     // ---- K loop ----
+    EMO_S_STAMP(1)
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -248,28 +340,33 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
         for (int j = 0; j < TP; ++j)
 #pragma unroll
           for (int r = 0; r < 16; ++r) { acc_lo[c][i][j][r] = 0.0f; acc_hi[c][i][j][r] = 0.0f; }
+    {
+      const int pb0_ = (Cfg::OFF_P + pp * PBUF) * 16;
 #pragma unroll
-    for (int pl = 0; pl < NPL; ++pl) EMO_U_LOAD_FRAGS_PLANE(0, pl, 0, Cfg::OFF_P * 16, 0, 0)
-    int pp = 0;
+      for (int pl = 0; pl < NPL; ++pl) EMO_U_LOAD_FRAGS_PLANE(0, pl, 0, pb0_, 0, 0)
+    }
     for (int cg = 0; cg < nst; ++cg) {
       const int pcur_b = (Cfg::OFF_P + pp * PBUF) * 16, pnxt_b = (Cfg::OFF_P + (pp ^ 1) * PBUF) * 16;
       const bool last_ = cg + 1 >= nst;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        // t = (cg, h); t + 1 = (cg, 1) resp. (cg + 1, 0); t + 2 = (cg + 1, h).  Past the item's end nothing is fetched
-        const bool have1_ = h == 0 || !last_, have2_ = !last_;
-        const char* const dma1 = EMO_U_WPTR(cotile, h == 0 ? cg : cg + 1, h ^ 1);
-        const char* const dma2 = EMO_U_WPTR(cotile, cg + 1, h);
+        // t = (cg, h); t + 1 = (cg, 1) resp. (cg + 1, 0); t + 2 = (cg + 1, h).  Past the item's end: the next item's (stage 0,
+        // p = 0) into W[0] when chained -- its pieces 0, 1 as t + 2 of (last, 0), pieces 2 .. 7 as t + 1 of (last, 1) -- and the last
+        // stage again otherwise (dead: whether to fetch must not depend on chain_out, a branch on it inside the loop costs 50
+        // registers).  Pieces 0, 1 of the next item's (0, 1) would land in W[1], the epilogue image: the chained prologue fetches
+        // them.  Pointers from SELECTED indices
+        const bool past_ = last_ && chain_out;
+        const bool have1_ = CHAIN || h == 0 || !last_, have2_ = !last_ || (CHAIN && h == 0);   // (EMO_UP2_CHAIN = 0: nothing is fetched past the end)
+        const int ce_ = past_ ? nx_cotile : cotile, ke_ = last_ ? (chain_out ? 0 : nst - 1) : cg + 1;
+        const char* const dma1 = h == 0 ? EMO_U_WPTR(cotile, cg, 1) : EMO_U_WPTR(ce_, ke_, 0);
+        const char* const dma2 = EMO_U_WPTR(ce_, ke_, h);
         if (EMO_CONV_SETPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int gs = 0; gs < 4; ++gs) {
           const int fcur = (h * 4 + gs) & 1, fnxt = fcur ^ 1;
-          if (gs == 3) { EMO_P_BARRIER(0); }
+          if (gs == 3) { EMO_U_LOOP_BARRIER(0); }
           if (gs == 3 && h == 1) EMO_U_TOUCH_QUAD()
-          if (gs == 0 && h == 1) {
-            const int tgt_ = cg + 2 < nst ? cg + 2 : nst - 1;     // (past the end: a dead re-load)
-            EMO_U_ISSUE_BEGIN(tgt_)
-          }
+          if (!LOADS_EARLY && gs == 0 && h == 1) EMO_U_NEXT_STAGE_BEGIN()
           __builtin_amdgcn_sched_barrier(0);
           {
             const int an = gs < 3 ? (gs + 1) >> 1 : 0, bn = gs < 3 ? (gs + 1) & 1 : 0;
@@ -280,11 +377,17 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
               EMO_U_LOAD_FRAGS_PLANE(fnxt, pl, hbn, pbn, an, bn)
               if (gs < 3 && have1_) EMO_U_DMA_PIECE(dma1, h ^ 1, 2 + 2 * gs + pl)
               if (gs == 3 && have2_) EMO_U_DMA_PIECE(dma2, h, pl)
-              if (h == 1 && gs == 0) EMO_U_ISSUE_LOADS(2 * pl, 2 * pl + 2)
-              if (h == 1 && gs > 0 && gs < 3 && pl == 0) EMO_U_ISSUE_LOADS(2 + 2 * gs, 4 + 2 * gs)
+              if (!LOADS_EARLY && h == 1 && gs == 0) EMO_U_ISSUE_LOADS(2 * pl, 2 * pl + 2)
+              if (!LOADS_EARLY && h == 1 && gs > 0 && gs < 3 && pl == 0) EMO_U_ISSUE_LOADS(2 + 2 * gs, 4 + 2 * gs)
             }
           }
           if (h == 0) EMO_U_CONV_PIXEL(pnxt_b, gs)
+          if (LOADS_EARLY && h == 0 && gs == 3) {
+            // the raw registers are free behind the last pixel's conversion; this step's two weight pieces went out above, so the
+            // loads are the youngest operations in flight and nothing waits for them before the barrier of (cg, 1)
+            EMO_U_NEXT_STAGE_BEGIN()
+            EMO_U_ISSUE_LOADS(0, 8)
+          }
 #pragma unroll
           for (int p = 0; p < NPROD; ++p) {
             const int pa = PA3[p], pb = PB3[p];
@@ -303,9 +406,15 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
       pp ^= 1;
     }
 
-    // ---- epilogue: 32 channels at a time through an LDS image [channel][4 high-res rows][128 columns (+ 4)] ----
+    // ---- epilogue: 32 channels at a time through an LDS image [channel][4 high-res rows][128 columns (+ 4)] in W[1] + tail ----
+    EMO_S_STAMP(2)
     EMO_P_WAIT(0);
+    EMO_S_STAMP(5)
     __syncthreads();
+    EMO_S_STAMP(6)
+    EMO_S_STAMP(7)
+    float* const img = smem + Cfg::OFF_IMG_F;
+    if (CHAIN && chain_out && tid < BM) te_b = a.bias != nullptr ? a.bias[nx_cotile * BM + tid] : 0.0f;   // the next item's bias entries
     const bool want_stats = a.gn_stats != nullptr;
     const int Ho = a.Hl, Wo = a.Wl;
     const unsigned oplane = (unsigned)Ho * Wo;
@@ -322,7 +431,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
             const float v = (emo_acc_read(acc_lo[p][i][j][r]) + emo_acc_read(acc_hi[p][i][j][r])) * a.out_scale;
             const int m = (r >> 2) * 8 + half * 4 + (r & 3);          // low-res column j * 32 + m of the wave's row
             const int hr = 2 * (wave >> 1) + p, col = 2 * (j * 32 + m) + wq;
-            smem[l32 * Cfg::EPI_CS + hr * 132 + col] = v;
+            img[l32 * Cfg::EPI_CS + hr * 132 + col] = v;
           }
       __syncthreads();
 #pragma unroll
@@ -337,7 +446,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
         for (int hr = 0; hr < 4; ++hr)
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
-            floatx4 v = *reinterpret_cast<const floatx4*>(smem + c * Cfg::EPI_CS + hr * 132 + 4 * eu + 64 * k);
+            floatx4 v = *reinterpret_cast<const floatx4*>(img + c * Cfg::EPI_CS + hr * 132 + 4 * eu + 64 * k);
             v = v + floatx4{bs, bs, bs, bs};
             v_[hr][k] = v;
             float* const op = obase + (unsigned)(2 * y0 + hr) * Wo + (2 * x0 + 4 * eu + 64 * k);
@@ -370,11 +479,44 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
           }
         }
       }
-      __syncthreads();       // (the image is rewritten by the next channel block, the buffers by the next item's prologue)
+      if (i == 0) {
+        EMO_S_STAMP(8)
+        __syncthreads();     // (the image is rewritten by the next channel block)
+      }
     }
+    EMO_S_STAMP(9)
+#if EMO_S_TIMING
+    EMO_S_STAMP(3)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    EMO_S_STAMP(4)
+    {
+      const int ep_L_ = l_base + idx8;
+      if (tid == 0 && ep_L_ < EMO_S_TLOG_N) {
+        unsigned long long* t_ = emo_s_tlog + (long)ep_L_ * EMO_S_TLOG_W;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) t_[k] = tstamp[k];
+        t_[12] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_ID
+        t_[13] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);    // XCC_ID
+        t_[14] = (unsigned long long)blockIdx.x;
+        t_[15] = (unsigned long long)(chained_in ? 1 : 0);
+      }
+      if (EMO_S_TIMING == 2 && lane == 0 && ep_L_ < EMO_S_TLOG_N / 8) {   // per-wave barrier accounting: rows N/4 + 4 item + wave
+        unsigned long long* w_ = emo_s_tlog + ((long)EMO_S_TLOG_N / 4 + (long)ep_L_ * 4 + wave) * EMO_S_TLOG_W;
+        w_[0] = tw_wait; w_[1] = tw_bar; w_[2] = tw_n; w_[3] = tstamp[2] - tstamp[1];
+      }
+    }
+#endif
+    // item end: the image and the bias are rewritten by the next item (its epilogue, its prologue), the tables, the patch buffers
+    // and W by a full prologue -- every wave must be out of the epilogue first
+    __syncthreads();
+    chained_in = chain_out;
   }
   if (a.sat_flag != nullptr && sat_m > 65504.0f) *a.sat_flag = 1;   // (every writer stores the same value)
 #undef EMO_U_WPTR
+#undef EMO_U_DECODE
+#undef EMO_U_CURSOR_OF
+#undef EMO_U_NEXT_STAGE_BEGIN
+#undef EMO_U_LOOP_BARRIER
 #undef EMO_U_LOAD_FRAGS_PLANE
 #undef EMO_U_ISSUE_BEGIN
 #undef EMO_U_ISSUE_LOADS
@@ -415,3 +557,12 @@ int conv_f16x2_up2_launch(ConvArgs a, hipStream_t s) {
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
   return emo_launch_status();
 }
+
+#if EMO_S_TIMING
+// measurement builds only: the per-work-item phase stamps of the last phase-kernel launch (EMO_S_TIMING, conv_igemm_bf16x3.h)
+extern "C" int emo_debug_conv_timing_up2(unsigned long long* host_out, int n_items) {
+  if (!host_out || n_items < 0 || n_items > EMO_S_TLOG_N) return EMO_ERR_BAD_ARG;
+  if (hipDeviceSynchronize() != hipSuccess) return EMO_ERR_BAD_ARG;
+  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(emo_s_tlog), (size_t)n_items * EMO_S_TLOG_W * sizeof(unsigned long long)) == hipSuccess ? EMO_OK : EMO_ERR_BAD_ARG;
+}
+#endif

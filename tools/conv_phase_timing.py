@@ -4,6 +4,9 @@ drain / gap to the next block on the same CU, from s_memtime stamps of wave 0 of
 Needs the measurement build of the library (never the product):
     python -m emoportraits_amd.build --variant timing EMO_S_TIMING=1
     EMO_HIP_LIB=emoportraits_amd/lib/libemoportraits_hip_timing.so python tools/conv_phase_timing.py [B]
+    ... python tools/conv_phase_timing.py [B] --up2      # the decoder's three up-convolutions on the phase kernel
+                                                         # (csrc/conv_inst_f16x2_up2.hip); an EMO_S_TIMING=2 build adds, per wave,
+                                                         # the K loop's cycles in s_waitcnt and in s_barrier
 JSON lines: per (layer shape, operand mode) the median / p90 of every phase in shader cycles, the per-CU occupancy of each
 phase (sum of the phase over the CU's blocks / the CU's busy span), and the launch's wall time by HIP events.
 """
@@ -81,9 +84,60 @@ def analyse(buf):
                 cu_span_cycles_med=int(np.median(span)))
 
 
+UP2_SHAPES = [(512, 320, (64, 64)), (320, 192, (128, 128)), (192, 128, (256, 256))]      # (cin, cout, low-res dims)
+
+
+def main_up2(B, lib):
+    """the phase kernel on the decoder's up-convolutions as the decoder launches them (affine + ReLU in, tile statistics).  Beside
+    the phases of analyse(): the share of items that started with the chained prologue, and the EXPOSED time of the launch -- per
+    CU, the sum over its items of prologue + epilogue + store drain + gap (and, on an EMO_S_TIMING=2 build, the K loop's cycles in
+    s_waitcnt, the slowest wave's), in cycles and in milliseconds at the launch's effective clock"""
+    for cin, cout, dims in UP2_SHAPES:
+        x = torch.randn(B, cin, *dims, device=DEV)
+        w = torch.randn(cout, cin, 3, 3) / math.sqrt(cin * 9)
+        scale = torch.rand(B, cin, device=DEV) + 0.5
+        shift = torch.randn(B, cin, device=DEV) * 0.1
+        layer = pack.PackedConv("t", w, None, DEV, precision="f16x2")
+        kw = dict(relu_in=True, ups=True, want_stats=True)
+        out = ops.conv_igemm(x, layer, scale, shift, **kw)[0]
+        assert layer.last_form == "up2", layer.last_form
+        for _ in range(2):
+            ops.conv_igemm(x, layer, scale, shift, out=out, **kw)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        ops.conv_igemm(x, layer, scale, shift, out=out, **kw)
+        b.record()
+        torch.cuda.synchronize()
+        ms = a.elapsed_time(b)
+        n_items = B * (dims[0] // 2) * (dims[1] // 64) * (cout // 64)
+        stages = -(-cin // 16)
+        full = stamps(lib, "up2", 65536)
+        t = full[:min(n_items, 65536)]
+        rec = dict(B=B, cin=cin, cout=cout, dims=dims, ups=True, mode="up2", statistics=True, ms=round(ms, 3), stages=stages,
+                   lib=os.path.basename(os.environ.get("EMO_HIP_LIB", "product")))
+        rec.update(analyse(t))
+        rec["chained_in_share"] = round(float((t[:, 15] & 1).mean()), 4)
+        rec["eff_clock_ghz"] = round(rec["cu_span_cycles_med"] / (ms * 1e6), 3)
+        per_item = rec["prologue"]["mean"] + rec["epilogue_issue"]["mean"] + rec["store_drain"]["mean"] + max(rec["gap_to_next_block"]["mean"], 0.0)
+        waves = analyse_waves(full, n_items)
+        wait_item = 0.0
+        if waves is not None:
+            rec["waves"] = waves
+            wait_item = float(max(v["waitcnt"] for v in waves.values()))
+            rec["kloop_waitcnt_per_stage"] = round(wait_item / stages, 1)
+            rec["kloop_barrier_per_stage"] = round(float(max(v["barrier"] for v in waves.values())) / stages, 1)
+        exposed = (per_item + wait_item) * rec["blocks_per_cu"]
+        rec["exposed"] = dict(cycles_per_item_outside_kloop=round(per_item, 1), kloop_waitcnt_cycles_per_item=round(wait_item, 1),
+                              cycles_per_cu=round(exposed, 1), ms=round(exposed / (rec["eff_clock_ghz"] * 1e6), 4))
+        print(json.dumps(rec), flush=True)
+
+
 def main():
-    B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
+    B = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 16
     lib = hip.load()
+    if "--up2" in sys.argv:
+        return main_up2(B, lib)
     shapes = [(128, 128, (512, 512), False), (192, 128, (256, 256), True), (192, 192, (256, 256), False),
               (320, 320, (128, 128), False), (512, 512, (64, 64), False)]
     if "--shapes" in sys.argv:                                   # e.g. --shapes 0,4
