@@ -396,15 +396,15 @@ __device__ __forceinline__ AaTaps aa_taps(int i, float scale, float inv_scale, i
   return t;
 }
 
-// r[c] = clamp(R(img)[c, y, x], 0, 1) * 255 of one window pixel; im = the frame's [3,S,S] image.  s >= S: resize2d_at's bicubic;
+// r[c] = clamp(R(img)[c, y, x], 0, 1) of one window pixel; im = the frame's [3,S,S] image.  s >= S: resize2d_at's bicubic;
 // s < S: the antialiased one, rows first (ATen resamples the width, then the height), ty = the taps of row y.  The weights are
 // evaluated where they are used (up to 17 x 17 taps at scale 4: no register arrays with run-time indices, i.e. no scratch).
-__device__ __forceinline__ void paste_render(const float* __restrict__ im, int S, int s, float scale, float inv_scale,
-                                             const AaTaps& ty, int y, int x, float r[3]) {
+__device__ __forceinline__ void paste_render01(const float* __restrict__ im, int S, int s, float scale, float inv_scale,
+                                               const AaTaps& ty, int y, int x, float r[3]) {
   const long SS = (long)S * S;
   if (s >= S) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) r[c] = resize2d_at(im + c * SS, S, S, S, scale, scale, y, x, 1, 1) * 255.0f;
+    for (int c = 0; c < 3; ++c) r[c] = resize2d_at(im + c * SS, S, S, S, scale, scale, y, x, 1, 1);
     return;
   }
   const AaTaps tx = aa_taps(x, scale, inv_scale, S);
@@ -422,7 +422,15 @@ __device__ __forceinline__ void paste_render(const float* __restrict__ im, int S
     for (int c = 0; c < 3; ++c) acc[c] += wy * row[c];
   }
 #pragma unroll
-  for (int c = 0; c < 3; ++c) r[c] = fminf(fmaxf(acc[c], 0.0f), 1.0f) * 255.0f;
+  for (int c = 0; c < 3; ++c) r[c] = fminf(fmaxf(acc[c], 0.0f), 1.0f);
+}
+
+// the same times 255: what the rgb8 paste blends with the frame's bytes
+__device__ __forceinline__ void paste_render(const float* __restrict__ im, int S, int s, float scale, float inv_scale,
+                                             const AaTaps& ty, int y, int x, float r[3]) {
+  paste_render01(im, S, s, scale, inv_scale, ty, y, x, r);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) r[c] *= 255.0f;
 }
 
 // the blend weight of window pixel (y, x): the feather ramp from the window's edge (fs = feather * s; 1 where feather == 0) times
@@ -494,6 +502,212 @@ __global__ __launch_bounds__(256) void paste_windows_kernel(const float* __restr
         for (int c = 0; c < 3; ++c) row[3 * x + c] = (uint8_t)paste_blend(a, row[3 * x + c], r[c]);
       }
     }
+  }
+}
+
+// ---- NV12 frames (ABI 17; the definitions D, E, C and P: include/emo_hip.h).  A frame is Hf rows of Y bytes and Hf / 2 rows of
+// Wf / 2 interleaved (U, V) pairs; both planes share the row pitch and the frame stride, in bytes.
+
+// Everything derived from the matrix (Kr, Kb) and the range is formed once on the host in fp64 and rounded to fp32
+struct Nv12Coef {
+  float oy, sy, sc;          // luma offset; luma and chroma code ranges
+  float kr, kg, kb;          // y' = kr R + kg G + kb B
+  float rv, bu, gv, gu;      // decode: R = y' + rv cr, B = y' + bu cb, G = y' - gv cr - gu cb
+  float cbs, crs;            // encode: Cbc = 128 + cbs (B - y'), Crc = 128 + crs (R - y')
+};
+
+inline bool nv12_coef(int matrix, int full_range, Nv12Coef& k) {
+  double Kr, Kb;
+  if (matrix == 0) { Kr = 0.2126; Kb = 0.0722; }            // bt709
+  else if (matrix == 1) { Kr = 0.299; Kb = 0.114; }         // bt601
+  else return false;
+  const double Kg = 1.0 - Kr - Kb;
+  const double oy = full_range ? 0.0 : 16.0, sy = full_range ? 255.0 : 219.0, sc = full_range ? 255.0 : 224.0;
+  k.oy = (float)oy; k.sy = (float)sy; k.sc = (float)sc;
+  k.kr = (float)Kr; k.kg = (float)Kg; k.kb = (float)Kb;
+  k.rv = (float)(2.0 * (1.0 - Kr)); k.bu = (float)(2.0 * (1.0 - Kb));
+  k.gv = (float)(2.0 * Kr * (1.0 - Kr) / Kg); k.gu = (float)(2.0 * Kb * (1.0 - Kb) / Kg);
+  k.cbs = (float)(sc / (2.0 * (1.0 - Kb))); k.crs = (float)(sc / (2.0 * (1.0 - Kr)));
+  return true;
+}
+
+// what every NV12 entry point refuses before a launch: null planes, an odd frame, a pitch shorter than a row
+inline bool nv12_planes_ok(const void* y, const void* uv, int64_t pitch, int64_t frame_stride, int H, int W) {
+  return y && uv && H > 0 && W > 0 && !(H & 1) && !(W & 1) && pitch >= W && frame_stride >= 0;
+}
+
+__host__ __device__ inline bool nv12_window_ok(int x0, int y0, int w, int h, int Hf, int Wf) {
+  return w > 0 && h > 0 && x0 >= 0 && y0 >= 0 && x0 <= Wf - w && y0 <= Hf - h;
+}
+
+// D of frame pixel (y, x): its Y byte and the chroma pair at (y >> 1, x >> 1) -> clamped R, G, B; converted once for all three
+__device__ __forceinline__ void nv12_decode_at(const uint8_t* __restrict__ fy, const uint8_t* __restrict__ fuv, long pitch,
+                                               const Nv12Coef& k, int y, int x, float rgb[3]) {
+  const uint8_t* const c = fuv + (long)(y >> 1) * pitch + (x & ~1);
+  const float yp = __fdiv_rn((float)fy[(long)y * pitch + x] - k.oy, k.sy);
+  const float cb = __fdiv_rn((float)c[0] - 128.0f, k.sc), cr = __fdiv_rn((float)c[1] - 128.0f, k.sc);
+  const float r = yp + k.rv * cr, b = yp + k.bu * cb, g = (yp - k.gv * cr) - k.gu * cb;
+  rgb[0] = fminf(fmaxf(r, 0.0f), 1.0f);
+  rgb[1] = fminf(fmaxf(g, 0.0f), 1.0f);
+  rgb[2] = fminf(fmaxf(b, 0.0f), 1.0f);
+}
+
+// E of one pixel before the rounding: the luma code and the two chroma codes of clamp(rgb, 0, 1)
+__device__ __forceinline__ void nv12_encode(const Nv12Coef& k, const float rgb[3], float& yc, float& cbc, float& crc) {
+  const float r = fminf(fmaxf(rgb[0], 0.0f), 1.0f), g = fminf(fmaxf(rgb[1], 0.0f), 1.0f), b = fminf(fmaxf(rgb[2], 0.0f), 1.0f);
+  const float yp = (k.kr * r + k.kg * g) + k.kb * b;
+  yc = k.oy + k.sy * yp;
+  cbc = 128.0f + k.cbs * (b - yp);
+  crc = 128.0f + k.crs * (r - yp);
+}
+
+// floor(v) held to 0 ... 255; the callers add the 0.5
+__device__ __forceinline__ unsigned nv12_byte(float v) { return (unsigned)fminf(fmaxf(floorf(v), 0.0f), 255.0f); }
+
+// emo_nv12_windows_f32: one thread per output pixel, all three channels.  The arithmetic per channel is resize2d_at's bicubic on
+// the window (taps clamped into the WINDOW, rows first) with every tap decoded from its bytes where it is used: the 16 taps of
+// neighbouring outputs overlap and the bytes under them (1.5 per pixel) stay in L1 / L2, so nothing is staged in LDS -- the
+// footprint of a block grows with the window's scale (up to 8.4 source pixels per output at 1080 -> 128) and has no bound a
+// static tile could be sized for.  A window as large as the output is scale 1, where the bicubic weights are exactly (0, 1, 0,
+// 0): the pixel's own conversion, taken directly.
+__global__ __launch_bounds__(256) void nv12_windows_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp,
+                                                           long pitch, long fstride, int Hf, int Wf,
+                                                           const int* __restrict__ win, float* __restrict__ out, long N, int Ho,
+                                                           int Wo, Nv12Coef k) {
+  const long HWo = (long)Ho * Wo, total = N * HWo;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int xo = (int)(i % Wo);
+    const long r = i / Wo;
+    const int yo = (int)(r % Ho);
+    const long n = r / Ho;
+    int wx0 = 0, wy0 = 0, ww = Wf, wh = Hf;
+    if (win) { wx0 = win[4 * n]; wy0 = win[4 * n + 1]; ww = win[4 * n + 2]; wh = win[4 * n + 3]; }
+    float* const o = out + n * 3 * HWo + (long)yo * Wo + xo;
+    if (!nv12_window_ok(wx0, wy0, ww, wh, Hf, Wf)) { o[0] = 0.0f; o[HWo] = 0.0f; o[2 * HWo] = 0.0f; continue; }
+    const uint8_t* const fy = yp + n * fstride;
+    const uint8_t* const fuv = uvp + n * fstride;
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    if (ww == Wo && wh == Ho) {
+      nv12_decode_at(fy, fuv, pitch, k, wy0 + yo, wx0 + xo, acc);
+    } else {
+      const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
+      const float sy = sh * ((float)yo + 0.5f) - 0.5f, sx = sw * ((float)xo + 0.5f) - 0.5f;
+      const float fyf = floorf(sy), fxf = floorf(sx);
+      const int iy = (int)fyf, ix = (int)fxf;
+      const float ty = sy - fyf, tx = sx - fxf;
+      const float A = -0.75f;
+      const float wy[4] = {cubic2(ty + 1.0f, A), cubic1(ty, A), cubic1(1.0f - ty, A), cubic2(2.0f - ty, A)};
+      const float wx[4] = {cubic2(tx + 1.0f, A), cubic1(tx, A), cubic1(1.0f - tx, A), cubic2(2.0f - tx, A)};
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        int yy = iy - 1 + a;
+        yy = yy < 0 ? 0 : (yy > wh - 1 ? wh - 1 : yy);
+        float row[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          int xx = ix - 1 + b;
+          xx = xx < 0 ? 0 : (xx > ww - 1 ? ww - 1 : xx);
+          float rgb[3];
+          nv12_decode_at(fy, fuv, pitch, k, wy0 + yy, wx0 + xx, rgb);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) row[c] += rgb[c] * wx[b];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += row[c] * wy[a];
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] = fminf(fmaxf(acc[c], 0.0f), 1.0f);
+    }
+    o[0] = acc[0]; o[HWo] = acc[1]; o[2 * HWo] = acc[2];
+  }
+}
+
+// two adjacent bytes: one 16-bit store where the planes allow it (`pairs`: even addresses, pitch and frame stride)
+__device__ __forceinline__ void nv12_store2(uint8_t* p, unsigned lo, unsigned hi, bool pairs) {
+  if (pairs) *reinterpret_cast<uint16_t*>(p) = (uint16_t)(lo | (hi << 8));
+  else { p[0] = (uint8_t)lo; p[1] = (uint8_t)hi; }
+}
+
+// emo_pack_nv12: one work item per 2 x 2 luma block -- its four Y bytes and its (U, V) pair have no other writer
+__global__ __launch_bounds__(256) void pack_nv12_kernel(const float* __restrict__ img, uint8_t* __restrict__ yp,
+                                                        uint8_t* __restrict__ uvp, long pitch, long fstride, long N, int H, int W,
+                                                        bool pairs, Nv12Coef k) {
+  const int Hc = H >> 1, Wc = W >> 1;
+  const long HW = (long)H * W, total = N * Hc * Wc;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int cx = (int)(i % Wc);
+    const long r = i / Wc;
+    const int cy = (int)(r % Hc);
+    const long n = r / Hc;
+    const float* const src = img + n * 3 * HW + (long)(2 * cy) * W + 2 * cx;
+    float cb = 0.0f, cr = 0.0f;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+      unsigned yb[2];
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const float rgb[3] = {src[dy * W + dx], src[HW + dy * W + dx], src[2 * HW + dy * W + dx]};
+        float yc, cbc, crc;
+        nv12_encode(k, rgb, yc, cbc, crc);
+        yb[dx] = nv12_byte(yc + 0.5f);
+        cb += cbc;                               // ((c00 + c01) + c10) + c11 (0 + c00 is c00)
+        cr += crc;
+      }
+      nv12_store2(yp + n * fstride + (long)(2 * cy + dy) * pitch + 2 * cx, yb[0], yb[1], pairs);
+    }
+    nv12_store2(uvp + n * fstride + (long)cy * pitch + 2 * cx, nv12_byte(cb * 0.25f + 0.5f), nv12_byte(cr * 0.25f + 0.5f), pairs);
+  }
+}
+
+// emo_paste_windows_nv12: the work item is a chroma sample of the window's covering chroma rectangle with those of its four luma
+// pixels that lie inside the window (the image and the blend weight of each from the rgb8 paste's paste_render01 / paste_alpha),
+// grid-stride over N * cmax * cmax with cmax a host-known bound of the samples along a window side.  A luma byte outside the
+// window is neither read nor written; a chroma pair is touched only if one of its luma pixels is inside.
+__global__ __launch_bounds__(256) void paste_windows_nv12_kernel(const float* __restrict__ img, const float* __restrict__ matte,
+                                                                 const int* __restrict__ win, uint8_t* __restrict__ yp,
+                                                                 uint8_t* __restrict__ uvp, long pitch, long fstride,
+                                                                 unsigned total, int S, int Hf, int Wf, unsigned cmax,
+                                                                 float feather, Nv12Coef k) {
+  const long SS = (long)S * S;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const unsigned rr = i / cmax;
+    const long n = rr / cmax;
+    const int* const w4 = win + 4 * n;
+    const int wx0 = w4[0], wy0 = w4[1], s = w4[2];
+    if (!paste_window_ok(wx0, wy0, s, w4[3], S, Hf, Wf)) continue;
+    const int cx = (wx0 >> 1) + (int)(i % cmax), cy = (wy0 >> 1) + (int)(rr % cmax);
+    if (2 * cx >= wx0 + s || 2 * cy >= wy0 + s) continue;
+    const float scale = (float)S / (float)s, inv_scale = __fdiv_rn(1.0f, scale), fs = feather * (float)s;
+    const float* const im = img + n * 3 * SS;
+    const float* const mt = matte ? matte + n * SS : nullptr;
+    uint8_t* const fy = yp + n * fstride;
+    uint8_t* const puv = uvp + n * fstride + (long)cy * pitch + 2 * cx;
+    float a4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cb4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cr4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+      const int y = 2 * cy + dy - wy0;
+      if (y < 0 || y >= s) continue;
+      AaTaps ty = {0, 0, 0.0f, 0.0f};
+      if (s < S) ty = aa_taps(y, scale, inv_scale, S);
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const int x = 2 * cx + dx - wx0;
+        if (x < 0 || x >= s) continue;
+        float r[3], yc, cbc, crc;
+        paste_render01(im, S, s, scale, inv_scale, ty, y, x, r);
+        const float a = paste_alpha(mt, S, s, scale, feather, fs, y, x);
+        nv12_encode(k, r, yc, cbc, crc);
+        uint8_t* const py = fy + (long)(wy0 + y) * pitch + wx0 + x;
+        *py = (uint8_t)nv12_byte(((1.0f - a) * (float)*py + a * yc) + 0.5f);
+        a4[2 * dy + dx] = a;
+        cb4[2 * dy + dx] = a * cbc;
+        cr4[2 * dy + dx] = a * crc;
+      }
+    }
+    const float na = 1.0f - (((a4[0] + a4[1]) + a4[2]) + a4[3]) * 0.25f;
+    const float u = (float)puv[0], v = (float)puv[1];
+    puv[0] = (uint8_t)nv12_byte((na * u + (((cb4[0] + cb4[1]) + cb4[2]) + cb4[3]) * 0.25f) + 0.5f);
+    puv[1] = (uint8_t)nv12_byte((na * v + (((cr4[0] + cr4[1]) + cr4[2]) + cr4[3]) * 0.25f) + 0.5f);
   }
 }
 
@@ -658,5 +872,56 @@ extern "C" int emo_paste_windows_rgb8(const float* img, const float* matte, cons
   if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(paste_windows_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frames,
                      (unsigned)total, S, Hf, Wf, (unsigned)smax, feather);
+  return emo_launch_status();
+}
+
+// ---- ABI 17: NV12 frames in and out (definitions: include/emo_hip.h)
+extern "C" int emo_nv12_windows_f32(const uint8_t* y, const uint8_t* uv, int64_t pitch, int64_t frame_stride, int Hf, int Wf,
+                                    const int32_t* windows, const int32_t* windows_host, float* out, int N, int Ho, int Wo,
+                                    int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  if (!nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || !out || N <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
+  if (!nv12_coef(matrix, full_range, k) || (windows_host && !windows)) return EMO_ERR_BAD_ARG;
+  if (windows_host)
+    for (int n = 0; n < N; ++n) {
+      const int32_t* w = windows_host + 4 * n;
+      if (!nv12_window_ok(w[0], w[1], w[2], w[3], Hf, Wf)) return EMO_ERR_BAD_ARG;
+    }
+  hipLaunchKernelGGL(nv12_windows_kernel, dim3(grid_for((long)N * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, y, uv, (long)pitch,
+                     (long)frame_stride, Hf, Wf, windows, out, (long)N, Ho, Wo, k);
+  return emo_launch_status();
+}
+
+extern "C" int emo_pack_nv12(const float* img, uint8_t* y, uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int H, int W,
+                             int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  if (!img || !nv12_planes_ok(y, uv, pitch, frame_stride, H, W) || N <= 0 || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
+  const bool pairs = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(uv) | (uintptr_t)pitch | (uintptr_t)frame_stride) & 1) == 0;
+  hipLaunchKernelGGL(pack_nv12_kernel, dim3(grid_for((long)N * (H / 2) * (W / 2))), dim3(256), 0, (hipStream_t)stream, img, y, uv,
+                     (long)pitch, (long)frame_stride, (long)N, H, W, pairs, k);
+  return emo_launch_status();
+}
+
+extern "C" int emo_paste_windows_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                                      uint8_t* y, uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int S, int Hf, int Wf,
+                                      float feather, int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  if (!img || !windows || !nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || N <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
+  if (!(feather >= 0.0f && feather <= 0.5f) || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
+  int smax = Hf < Wf ? Hf : Wf;                    // windows that only the device knows: any valid side
+  if (windows_host) {
+    smax = 0;
+    for (int n = 0; n < N; ++n) {
+      const int32_t* w = windows_host + 4 * n;
+      if (!nv12_window_ok(w[0], w[1], w[2], w[3], Hf, Wf)) return EMO_ERR_BAD_ARG;
+      if (!paste_window_ok(w[0], w[1], w[2], w[3], S, Hf, Wf)) return EMO_ERR_UNSUPPORTED;   // not square, or 4 s < S
+      smax = w[2] > smax ? w[2] : smax;
+    }
+  }
+  const long cmax = smax / 2 + 1;                  // chroma samples under s luma pixels: at most s / 2 + 1 (an odd origin)
+  const long total = (long)N * cmax * cmax;
+  if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(paste_windows_nv12_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, y, uv,
+                     (long)pitch, (long)frame_stride, (unsigned)total, S, Hf, Wf, (unsigned)cmax, feather, k);
   return emo_launch_status();
 }

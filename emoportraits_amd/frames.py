@@ -16,10 +16,38 @@ def square_windows(windows):
     return out
 
 
-def crops_of(u8, size, windows=None):
+FORMATS = ("rgb8", "nv12")
+
+
+def check_format(frame_format, colorspace, what="frame_format"):
+    if frame_format not in FORMATS:
+        raise ValueError(f"{what}={frame_format!r}: 'rgb8' or 'nv12'")
+    if colorspace not in ops.NV12_MATRICES:
+        raise ValueError(f"colorspace {colorspace!r}: 'bt709' or 'bt601'")
+
+
+def check_frames(chunk, frame_format):
+    """the shape and dtype of one chunk of frames: uint8 [N,H,W,3], or NV12 uint8 [N, 3H/2, W] with H and W even"""
+    if frame_format == "rgb8":
+        if chunk.dtype != torch.uint8 or chunk.dim() != 4 or chunk.shape[-1] != 3:
+            raise ValueError("frames must be uint8 [N,H,W,3]")
+    elif chunk.dtype != torch.uint8 or chunk.dim() != 3 or chunk.shape[1] % 3 or chunk.shape[2] % 2 or 0 in chunk.shape[1:]:
+        raise ValueError(f"NV12 frames must be uint8 [N, 3H/2, W] with H and W even, got {tuple(chunk.shape)}")
+
+
+def frame_size(chunk, frame_format):
+    """(H, W) of the frames of a chunk"""
+    return (chunk.shape[1], chunk.shape[2]) if frame_format == "rgb8" else (chunk.shape[1] // 3 * 2, chunk.shape[2])
+
+
+def crops_of(u8, size, windows=None, frame_format="rgb8", colorspace="bt709", full_range=False):
     """uint8 frames [b,H,W,3] on the device -> fp32 crops [b,3,size,size]: byte -> fp32 CHW (emo_unpack_rgb8), then each frame's
     window (x0, y0, s, s) read in place and resized, the whole batch in one launch (a host list or an int32 [b,4] device
-    tensor, ops.resize2d_windows), or without windows the whole frame, resized only where its size differs"""
+    tensor, ops.resize2d_windows), or without windows the whole frame, resized only where its size differs.
+    frame_format 'nv12': NV12 frames [b, 3H/2, W] -> the same crops of the converted frames in ONE launch (ops.nv12_windows:
+    only the bytes under the windows are read, no full-frame fp32 picture is written)."""
+    if frame_format == "nv12":
+        return ops.nv12_windows(u8, (size, size), windows, colorspace, full_range)
     x = ops.unpack_rgb8(u8)
     if windows is not None:
         return ops.resize2d_windows(x, (size, size), windows, "bicubic", clamp01=True)
@@ -40,7 +68,7 @@ def uploaded(chunk, spans, device, upload_stream):
             b0, b1 = span
             src = chunk[b0:b1]
             if src.is_cuda:
-                nxt = (b0, b1, src.contiguous(), None)
+                nxt = (b0, b1, src if src.dim() == 3 else src.contiguous(), None)   # (NV12 ops take a padded view as it is)
             else:
                 with torch.cuda.stream(upload_stream):
                     t = src.to(device, non_blocking=True)

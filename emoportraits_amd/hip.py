@@ -72,6 +72,9 @@ SIGNATURES = {
     "emo_pack_rgb8": [_c_void, _c_void, _c_int, _c_int, _c_int, _c_void],
     "emo_unpack_rgb8": [_c_void, _c_void, _c_int, _c_int, _c_int, _c_void],
     "emo_paste_windows_rgb8": [_c_void] * 5 + [_c_int] * 4 + [_c_float, _c_void],
+    "emo_nv12_windows_f32": [_c_void, _c_void, _c_i64, _c_i64, _c_int, _c_int, _c_void, _c_void, _c_void] + [_c_int] * 5 + [_c_void],
+    "emo_pack_nv12": [_c_void, _c_void, _c_void, _c_i64, _c_i64] + [_c_int] * 5 + [_c_void],
+    "emo_paste_windows_nv12": [_c_void] * 6 + [_c_i64, _c_i64] + [_c_int] * 4 + [_c_float, _c_int, _c_int, _c_void],
 }
 _RESTYPES = {"emo_build_info": ctypes.c_char_p, "emo_groupnorm_workspace_bytes": _c_i64}
 

@@ -341,14 +341,16 @@ class InferenceWrapper:
                                                world=self.world, rank=self.rank, exchange_shapes=False)
 
     def enrol_identities(self, sources, source_masks=None, slots=None, crop=False, windows=None, batch_size=8,
-                         custome_idt_embed=None, custome_source_pose_embed=None, custome_source_theta_embed=None):
+                         custome_idt_embed=None, custome_source_pose_embed=None, custome_source_theta_embed=None,
+                         frame_format="rgb8", colorspace="bt709", full_range=False):
         """Enrol K source identities into bank slots in chunks of `batch_size`: per chunk the mask products (ops.mul_mask), the
         embedders and HotPath.source_pass run at batch b, the canonical volumes go into their bank rows in one launch
         (ops.volume_to_channels_last_indexed) and the idt_embed / theta rows by device index copies -- no host synchronisation
         inside a chunk.  Identity k gets the semantics of forward(source_image=sources[k], source_mask=source_masks[k],
         crop=crop, custome_*=...[k]) followed by store_identity(slots[k]).
         sources: a list of images or a float tensor [K,3,H,W] (what forward takes, stacked), or uint8 frames [K,H,W,3] (host
-        or device, animate_frames' input) with optional windows[k] = (x_lo, y_lo, side), cropped as animate_frames crops.
+        or device, animate_frames' input) with optional windows[k] = (x_lo, y_lo, side), cropped as animate_frames crops;
+        with frame_format='nv12' the uint8 frames are NV12 [K, 3H/2, W] (colorspace, full_range as in animate_frames).
         custome_*: K-row tensors; the theta as [K,4,4] or (scale, rotation, translation) of [K,3] each.
         slots=None takes the K lowest free slots; explicit slots may overwrite occupied ones.  Every check runs on the host
         before the first launch (ValueError; the bank is untouched).  The current identity is left as it is.
@@ -358,17 +360,24 @@ class InferenceWrapper:
         same bit for bit on every rank and for any number of ranks.  Returns the slots in the order of `sources`."""
         with torch.no_grad():
             plan = self._enrolment_checks(sources, source_masks, slots, crop, windows, batch_size, custome_idt_embed,
-                                          custome_source_pose_embed, custome_source_theta_embed)
+                                          custome_source_pose_embed, custome_source_theta_embed, frame_format, colorspace,
+                                          full_range)
             return self._enrol_identities(plan, sources, crop, custome_idt_embed, custome_source_pose_embed,
                                           custome_source_theta_embed)
 
     def _enrolment_checks(self, sources, source_masks, slots, crop, windows, batch_size, custome_idt_embed,
-                          custome_source_pose_embed, custome_source_theta_embed):
+                          custome_source_pose_embed, custome_source_theta_embed, frame_format="rgb8", colorspace="bt709",
+                          full_range=False):
         """enrol_identities on the host, before anything is launched -> what the device part needs beside the arguments"""
         S = self.cfg["image_size"]
+        frames_mod.check_format(frame_format, colorspace)
         video = isinstance(sources, torch.Tensor) and sources.dtype == torch.uint8
+        if frame_format == "nv12":
+            if not video:
+                raise ValueError("frame_format='nv12' describes uint8 frames [K, 3H/2, W]")
+            frames_mod.check_frames(sources, "nv12")
         if isinstance(sources, torch.Tensor):
-            if video and (sources.dim() != 4 or sources.shape[-1] != 3):
+            if video and frame_format == "rgb8" and (sources.dim() != 4 or sources.shape[-1] != 3):
                 raise ValueError(f"uint8 sources must be frames [K,H,W,3], got {tuple(sources.shape)}")
             if not video and (sources.dim() != 4 or sources.shape[1] < 3):
                 raise ValueError(f"float sources must be [K,3,H,W], got {tuple(sources.shape)}")
@@ -384,7 +393,7 @@ class InferenceWrapper:
             raise ValueError("windows= crops uint8 frames [K,H,W,3]")
         win_host = None
         if windows is not None:
-            H, W = sources.shape[1], sources.shape[2]
+            H, W = frames_mod.frame_size(sources, frame_format)
             win_host = torch.tensor(frames_mod.square_windows(windows), dtype=torch.int32).reshape(-1, 4)
             if win_host.shape[0] != K:
                 raise ValueError(f"{win_host.shape[0]} windows for {K} sources")
@@ -447,7 +456,7 @@ class InferenceWrapper:
                     raise ValueError(f"source {i}: no face found (forward would render a zero crop for it; nothing was enrolled)")
                 boxes.append((t, win))
         return Namespace(slots=slots, chunks=chunks, owners=owners, video=video, win_host=win_host, masks=ms, images=images,
-                         boxes=boxes, parsing=parsing)
+                         boxes=boxes, parsing=parsing, frame_format=(frame_format, colorspace, bool(full_range)))
 
     def _enrol_identities(self, plan, sources, crop, custome_idt_embed, custome_source_pose_embed, theta_in):
         """the device part: inputs uploaded once, then chunk by chunk without a host synchronisation"""
@@ -472,7 +481,7 @@ class InferenceWrapper:
 
         def compute(a, b):
             if plan.video:
-                crop_img = frames_mod.crops_of(u8[a:b], S, None if win_dev is None else win_dev[a:b])   # one launch per chunk
+                crop_img = frames_mod.crops_of(u8[a:b], S, None if win_dev is None else win_dev[a:b], *plan.frame_format)   # one launch per chunk
             else:
                 crop_img = crops_all[a:b].float().contiguous()
             m = None if masks is None else masks[a:b]
@@ -885,7 +894,8 @@ class InferenceWrapper:
 
     # ------------------------------------------------------------------------------------------------------
     def animate(self, target_pose_embeds, target_srt, batch_size=16, as_uint8=True, identities=None, mix=False, mix_old=True,
-                target_theta=True, smooth_pose=False, smooth_per_identity=False, refine=False, refine_masks=None):
+                target_theta=True, smooth_pose=False, smooth_per_identity=False, refine=False, refine_masks=None,
+                out_format="rgb8", colorspace="bt709", full_range=False):
         """1 source -> N driver frames (the BASELINE metric).  Frames are sharded contiguously across ranks
         (SURVEY.md section 8e); each rank walks its shard in batches of `batch_size`.  Yields (first_frame_index, frames)
         with frames a uint8 [B,H,W,3] (or fp32 [B,3,H,W]) DEVICE tensor -- no host sync inside the loop.
@@ -898,9 +908,17 @@ class InferenceWrapper:
         give the same frames.  Without identities the state is `self.theta` (carried from call to call, as in forward); with
         them, smooth_pose needs smooth_per_identity=True, and each slot then has its own stream.
         refine=True: every rendered batch goes through the attached stage-2 model (attach_stage2; see animate_frames) and the
-        frames come out at its output_size_s2."""
+        frames come out at its output_size_s2.
+        out_format='nv12' (with as_uint8): the frames come out as NV12 uint8 [B, 3S/2, S] -- the fp32 image, refined or not,
+        through ops.pack_nv12 with `colorspace` ('bt709' | 'bt601') and `full_range` (see animate_frames)."""
         N = target_pose_embeds.shape[0]
+        frames_mod.check_format(out_format, colorspace, "out_format")
+        if out_format == "nv12" and not as_uint8:
+            raise ValueError("as_uint8=False yields the fp32 image: it has no out_format")
         masks_of, ids = self._preflight(N, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
+        if out_format == "nv12":
+            self._nv12_size(masks_of)
+        out_kind = "f32" if not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
         lo, hi = parallel.shard_range(N, self.rank, self.world)
         ids_dev = None if ids is None else ids[lo:hi].to(self.device)
         smoothed = None
@@ -916,7 +934,7 @@ class InferenceWrapper:
             else:
                 srt = [t[b0:b1].to(self.device).float().contiguous() for t in target_srt]
                 theta = self._pose_controls(ops.pose_theta(*srt), ident, mix, mix_old, False)
-            yield b0, self._render(pose, theta, ident, target_theta, masks_of, "u8" if as_uint8 else "f32")
+            yield b0, self._render(pose, theta, ident, target_theta, masks_of, out_kind, (colorspace, full_range))
 
     def _preflight(self, n_frames, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks):
         """The checks of the keywords animate() and animate_frames() share, before anything is launched -> (masks_of, ids):
@@ -936,11 +954,21 @@ class InferenceWrapper:
             self._source_theta('mix=True' if mix else 'target_theta=False')
         return masks_of, None
 
-    def _render(self, pose, theta, ident, target_theta, masks_of, out):
+    def _nv12_size(self, masks_of):
+        """NV12 frames have an even side: the size of the image that would be packed, checked before anything is launched"""
+        name, S_out = ("image_size", self.cfg["image_size"]) if masks_of is None else ("output_size_s2", self._stage2.cfg["output_size_s2"])
+        if S_out % 2:
+            raise ValueError(f"NV12 output needs an even {name}, got {S_out}")
+
+    def _render(self, pose, theta, ident, target_theta, masks_of, out, nv12=("bt709", False)):
         """The tail of a batch: the theta each frame is rendered with, the driver pass of the current identity or of the bank
-        slots `ident`, stage 2 where masks_of is given -> uint8 [b,S,S,3] (out 'u8') or the fp32 image [b,3,S,S] ('f32')"""
+        slots `ident`, stage 2 where masks_of is given -> uint8 [b,S,S,3] (out 'u8'), the fp32 image [b,3,S,S] ('f32') or
+        that image as NV12 uint8 [b,3S/2,S] ('nv12': ops.pack_nv12 with nv12 = (colorspace, full_range))"""
         theta = self._render_theta(theta, ident, target_theta)
         img = self._drive(pose, theta) if ident is None else self._drive_bank(pose, theta, ident)
+        if out == "nv12":
+            img = img if masks_of is None else self._refine(img, masks_of, "f32")
+            return ops.pack_nv12(img, *nv12)
         if masks_of is not None:
             return self._refine(img, masks_of, out)
         return ops.pack_rgb8(img) if out == "u8" else img
@@ -959,26 +987,34 @@ class InferenceWrapper:
             raise ValueError("paste_matte: None, True (embedders['matting']) or a callable img [b,3,S,S] -> [b,1,S,S]")
         return paste_matte
 
-    def paste_back(self, frames_u8, rendered, windows, feather=0.0625, matte=None):
+    def paste_back(self, frames_u8, rendered, windows, feather=0.0625, matte=None, frame_format="rgb8", colorspace="bt709",
+                   full_range=False):
         """The inverse of the crop: `rendered` [N,3,S,S] fp32 (the hot path's image, before emo_pack_rgb8) goes back into the
         frames the crops came from, frame i where its window windows[i] = (x_lo, y_lo, side) was -- resized to side x side
         (bicubic; antialiased when that shrinks it, down to S / 4), blended over the frame with a feathered edge of
         feather * side pixels and, if given, a matte ([N,1,S,S] in [0,1], a callable img -> matte, or True =
         embedders['matting']).  One launch (ops.paste_windows / emo_paste_windows_rgb8).
         frames_u8: uint8 [N,Hf,Wf,3], host or device; it is NOT modified (a host tensor is uploaded, a device tensor cloned).
-        Returns the device uint8 [N,Hf,Wf,3].  feather = 1/16 of the window is a taste default, not a measured optimum."""
-        if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
-            raise ValueError("frames must be uint8 [N,H,W,3]")
+        Returns the device uint8 [N,Hf,Wf,3].  feather = 1/16 of the window is a taste default, not a measured optimum.
+        frame_format='nv12': frames_u8 is NV12 uint8 [N, 3Hf/2, Wf] and so is the result (ops.paste_windows_nv12 /
+        emo_paste_windows_nv12, with `colorspace` and `full_range` as in animate_frames)."""
+        frames_mod.check_format(frame_format, colorspace)
+        if not isinstance(frames_u8, torch.Tensor):
+            raise ValueError("frames must be a uint8 tensor")
+        frames_mod.check_frames(frames_u8, frame_format)
         fn = self._paste_matte(matte, 'matte=True')
         wins = windows if isinstance(windows, torch.Tensor) and windows.is_cuda else frames_mod.square_windows(windows)
         img = rendered.to(self.device).float().contiguous()
         m = None if fn is None else fn(img).to(self.device).float().contiguous()
+        if frame_format == "nv12":
+            return ops.paste_windows_nv12(frames_u8.to(self.device, copy=True), img, wins, feather, m, colorspace, full_range)
         full = frames_u8.to(self.device, copy=True).contiguous()
         return ops.paste_windows(full, img, wins, feather, m)
 
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
                        mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
-                       paste_matte=None, as_uint8=True, refine=False, refine_masks=None):
+                       paste_matte=None, as_uint8=True, refine=False, refine_masks=None, frame_format="rgb8", out_format=None,
+                       colorspace="bt709", full_range=False):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  Per batch, all on the device and without a host synchronisation:
             byte -> fp32 CHW (emo_unpack_rgb8) -> crop windows read in place + bicubic resize to image_size, the whole batch in
@@ -1031,7 +1067,28 @@ class InferenceWrapper:
             use_graphs, whose last launch (emo_stage2_head_f32) writes the bytes that go to the ring, or the fp32 image that
             paste_back=True pastes (paste_matte is then computed on the refined image, and window sides are held to
             output_size_s2 / 4) or that as_uint8=False yields.  Yielded crops are [b,S2,S2,3].  identities, the pose controls
-            and smooth_pose are untouched: refinement starts where the render returns, and every rank refines its own shard."""
+            and smooth_pose are untouched: refinement starts where the render returns, and every rank refines its own shard.
+        frame_format='nv12': the frames are NV12 as video decoders hand them out, uint8 [N, 3H/2, W] (H rows of Y, then H / 2
+            rows of interleaved U, V; H and W even; stride 1 along a row and a row pitch >= W, so a [..., :W] view of a padded
+            surface is taken as it is), 1.5 bytes per pixel on the bus.  The crop step is then ONE launch
+            (emo_nv12_windows_f32: the bytes under each window converted and resized; no full-frame fp32 picture).
+            colorspace 'bt709' | 'bt601' and full_range (False: Y 16 ... 235, chroma 16 ... 240) say how the bytes are read
+            and written (include/emo_hip.h has the arithmetic).
+        out_format: None = frame_format; 'rgb8' | 'nv12' asks for the other one (crops only: paste_back returns the uploaded
+            frames, so its out_format is frame_format).  NV12 crops are uint8 [b, 3S/2, S]: the fp32 image, refined or not,
+            through emo_pack_nv12 (image_size / output_size_s2 must be even); with paste_back the NV12 frames are pasted in
+            place (emo_paste_windows_nv12).  as_uint8=False has no out_format.  Everything else -- upload-ahead, the ring,
+            smooth_pose, identities, the rank sharding, the caller's frames untouched -- is as for rgb8."""
+        frames_mod.check_format(frame_format, colorspace)
+        if out_format is not None:
+            frames_mod.check_format(out_format, colorspace, "out_format")
+            if not as_uint8:
+                raise ValueError("as_uint8=False yields the fp32 device image: it has no out_format")
+        out_format = out_format or frame_format
+        if paste_back and out_format != frame_format:
+            raise ValueError(f"paste_back=True returns the uploaded {frame_format} frames: out_format={out_format!r} is not possible")
+        if isinstance(frames, torch.Tensor):
+            frames_mod.check_frames(frames, frame_format)
         if not as_uint8 and (to_host or paste_back):
             raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
         masks_of, ids = self._preflight(frames.shape[0] if isinstance(frames, torch.Tensor) else None, identities, mix,
@@ -1048,14 +1105,16 @@ class InferenceWrapper:
             if any(4 * w[2] < S_out for w in wins):
                 raise ValueError(f"a paste window is smaller than a quarter of the {S_out}-pixel image: downscaling "
                                  f"stops at image_size / 4")
+        if out_format == "nv12" and as_uint8 and not paste_back:
+            self._nv12_size(masks_of)
         S = self.cfg["image_size"]
-        out_kind = "f32" if paste_back or not as_uint8 else "u8"
+        out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
+        fmt = (frame_format, colorspace, bool(full_range))
         host_ring = frames_mod.HostRing(self.device, ring, batch_size) if to_host else None
         upload_stream = torch.cuda.Stream(device=self.device)
         base = 0
         for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
-            if chunk.dtype != torch.uint8 or chunk.dim() != 4 or chunk.shape[-1] != 3:
-                raise ValueError("frames must be uint8 [N,H,W,3]")
+            frames_mod.check_frames(chunk, frame_format)
             n = chunk.shape[0]
             if ids is not None and base + n > ids.shape[0]:
                 raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
@@ -1063,7 +1122,7 @@ class InferenceWrapper:
             ids_dev = None if ids is None else ids[base + lo:base + hi].to(self.device)
             ids_chunk = None if ids is None or not smooth_pose else ids[base:base + n].to(self.device)
             spans = [(b0, min(b0 + batch_size, hi)) for b0 in range(lo, hi, batch_size)]
-            crops_of = lambda u8, b0, b1: frames_mod.crops_of(u8, S, None if wins is None else wins[base + b0:base + b1])
+            crops_of = lambda u8, b0, b1: frames_mod.crops_of(u8, S, None if wins is None else wins[base + b0:base + b1], *fmt)
             smoothed, kept = None, {}
             if smooth_pose:
                 keep_crops = (hi - lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
@@ -1098,11 +1157,14 @@ class InferenceWrapper:
                         theta = self._pose_controls(theta, ident, True, mix_old, False)
                 self.pred_target_theta = theta                                   # (as forward() leaves it: infer.py:584)
                 pose, _ = self._expression(crops, theta, 'a driver call')
-                out = self._render(pose, theta, ident, target_theta, masks_of, out_kind)
+                out = self._render(pose, theta, ident, target_theta, masks_of, out_kind, fmt[1:])
                 if paste_back:
                     full = u8.clone() if chunk.is_cuda else u8                   # (a host chunk's upload is this span's own)
-                    out = ops.paste_windows(full, out, wins[base + b0:base + b1], feather,
-                                            None if matte_fn is None else matte_fn(out).float().contiguous())
+                    m = None if matte_fn is None else matte_fn(out).float().contiguous()
+                    if frame_format == "nv12":
+                        out = ops.paste_windows_nv12(full, out, wins[base + b0:base + b1], feather, m, *fmt[1:])
+                    else:
+                        out = ops.paste_windows(full, out, wins[base + b0:base + b1], feather, m)
                 if to_host:
                     yield from host_ring.push(base + b0, out)
                 else:

@@ -774,6 +774,122 @@ def paste_windows(frames_u8, img, windows, feather=0.0, matte=None):
     return frames_u8
 
 
+NV12_MATRICES = {"bt709": 0, "bt601": 1}
+
+
+def _nv12_planes(nv12, what):
+    """uint8 [N, 3H/2, W] NV12 frames (H rows of Y, then H/2 rows of interleaved U, V; last stride 1, row pitch >= W: a
+    [..., :W] view of a padded surface is taken as it is) -> (Y pointer, UV pointer, pitch, frame stride, N, H, W)"""
+    if nv12.dtype != torch.uint8 or nv12.dim() != 3:
+        raise RuntimeError(f"{what} expects uint8 NV12 frames [N, 3H/2, W]")
+    N, rows, W = nv12.shape
+    if rows % 3 or W % 2 or rows == 0 or W == 0:
+        raise ValueError(f"NV12 frames {tuple(nv12.shape)}: expected [N, 3H/2, W] with H and W even")
+    H = rows // 3 * 2
+    pitch, fstride = (nv12.stride(1), nv12.stride(0)) if N > 0 else (W, rows * W)
+    if nv12.stride(2) != 1 or pitch < W or (N > 1 and fstride < rows * pitch):
+        raise RuntimeError(f"{what}: NV12 frames need stride 1 along a row, a row pitch >= W and frames that do not overlap")
+    base = nv12.data_ptr()
+    return ctypes.c_void_p(base), ctypes.c_void_p(base + H * pitch), pitch, fstride, N, H, W
+
+
+def _nv12_matrix(colorspace):
+    if colorspace not in NV12_MATRICES:
+        raise ValueError(f"colorspace {colorspace!r}: 'bt709' or 'bt601'")
+    return NV12_MATRICES[colorspace]
+
+
+def _windows_arg(windows, N, Wf, Hf, device, what):
+    """windows -> (int32 [N,4] device tensor, host tensor or None): a host sequence is checked against the frame and uploaded"""
+    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+        if windows.device != device or windows.dtype != torch.int32 or tuple(windows.shape) != (N, 4) or not windows.is_contiguous():
+            raise RuntimeError("windows must be a contiguous int32 cuda tensor [N,4]")
+        return windows, None
+    host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
+    if host.shape[0] != N:
+        raise ValueError(f"{host.shape[0]} windows for {N} frames")
+    lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
+    if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi[:, 0] <= Wf).all()) and bool((hi[:, 1] <= Hf).all())):
+        raise ValueError(f"a {what} window is not inside the {Wf}x{Hf} frame")
+    return host.to(device, non_blocking=True), host
+
+
+def nv12_windows(nv12, size=None, windows=None, colorspace="bt709", full_range=False):
+    """NV12 frames uint8 [N, 3H/2, W] on the device -> fp32 [N,3,Ho,Wo] in [0,1], ONE launch (emo_nv12_windows_f32): each frame's
+    window (x0, y0, w, h) of the converted frame, resized bicubically to size = (Ho, Wo) and clamped -- bit for bit
+    resize2d_windows(..., 'bicubic', clamp01=True) of the whole-frame conversion, which is never written.  windows: a host
+    sequence (checked, uploaded), an int32 [N,4] device tensor (a window that leaves the frame gives zeros), or None = the whole
+    frame; size None = (H, W), with windows None the plain conversion.  include/emo_hip.h has the definition."""
+    lib = hip.load()
+    y, uv, pitch, fstride, N, H, W = _nv12_planes(nv12, "nv12_windows")
+    matrix = _nv12_matrix(colorspace)
+    Ho, Wo = (H, W) if size is None else size
+    out = torch.empty((N, 3, Ho, Wo), device=nv12.device, dtype=torch.float32)
+    hip.require_cuda_f32(out)                                    # (the frames' device: GPU only, like every op)
+    win, host = (None, None) if windows is None else _windows_arg(windows, N, W, H, nv12.device, "crop")
+    if N == 0:
+        return out
+    hip.check(lib.emo_nv12_windows_f32(y, uv, pitch, fstride, H, W, hip.ptr(win), hip.ptr(host), hip.ptr(out), N, Ho, Wo, matrix,
+                                       int(bool(full_range)), hip.current_stream()), "emo_nv12_windows_f32")
+    return out
+
+
+def pack_nv12(img, colorspace="bt709", full_range=False, out=None):
+    """[N,3,H,W] fp32 -> NV12 uint8 [N, 3H/2, W] (emo_pack_nv12: clamp(0,1), the matrix, luma rounded per pixel, chroma the
+    rounded mean of each 2x2 block); H and W even.  out: NV12 frames to write into (a strided view is fine)."""
+    lib = hip.load()
+    hip.require_cuda_f32(img)
+    N, C, H, W = img.shape
+    if C != 3:
+        raise ValueError("expected 3 channels")
+    if H % 2 or W % 2:
+        raise ValueError(f"NV12 needs an even height and width, got {H}x{W}")
+    matrix = _nv12_matrix(colorspace)
+    if out is None:
+        out = torch.empty((N, 3 * H // 2, W), device=img.device, dtype=torch.uint8)
+    y, uv, pitch, fstride, n, h, w = _nv12_planes(out, "pack_nv12")
+    if (n, h, w) != (N, H, W) or out.device != img.device:
+        raise ValueError(f"out {tuple(out.shape)} does not hold {N} NV12 frames of {W}x{H} on the image's device")
+    if N == 0:
+        return out
+    hip.check(lib.emo_pack_nv12(hip.ptr(img), y, uv, pitch, fstride, N, H, W, matrix, int(bool(full_range)), hip.current_stream()),
+              "emo_pack_nv12")
+    return out
+
+
+def paste_windows_nv12(nv12, img, windows, feather=0.0, matte=None, colorspace="bt709", full_range=False):
+    """paste_windows on NV12 frames uint8 [N, 3Hf/2, Wf], IN PLACE and in one launch (emo_paste_windows_nv12): the resized,
+    clamped image and the blend weight a of paste_windows; luma blended per pixel, each chroma sample under the window with the
+    mean of its (up to four) window pixels' weights and weighted chroma (include/emo_hip.h has the definition).  windows as in
+    paste_windows.  Bytes outside a window's luma rectangle and its covering chroma rectangle are neither read nor written.
+    Returns nv12."""
+    lib = hip.load()
+    hip.require_cuda_f32(img, matte)
+    if nv12.device != img.device:
+        raise RuntimeError("paste_windows_nv12 expects the NV12 frames on the images' device")
+    y, uv, pitch, fstride, N, Hf, Wf = _nv12_planes(nv12, "paste_windows_nv12")
+    matrix = _nv12_matrix(colorspace)
+    if img.dim() != 4 or img.shape[0] != N or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
+        raise ValueError(f"frames {tuple(nv12.shape)} and images {tuple(img.shape)}: expected [N,3Hf/2,Wf] and [N,3,S,S]")
+    S = img.shape[2]
+    if matte is not None and tuple(matte.shape) != (N, 1, S, S):
+        raise ValueError(f"matte {tuple(matte.shape)}: expected {(N, 1, S, S)}")
+    if not 0.0 <= float(feather) <= 0.5:
+        raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
+    win, host = _windows_arg(windows, N, Wf, Hf, img.device, "paste")
+    if host is not None:
+        if not bool((host[:, 2] == host[:, 3]).all()):
+            raise ValueError("paste windows must be square")
+        if not bool((4 * host[:, 2] >= S).all()):
+            raise ValueError(f"a paste window is smaller than a quarter of the {S}x{S} image: downscaling stops at S / 4")
+    if N == 0:
+        return nv12
+    hip.check(lib.emo_paste_windows_nv12(hip.ptr(img), hip.ptr(matte), hip.ptr(win), hip.ptr(host), y, uv, pitch, fstride, N, S, Hf,
+                                         Wf, float(feather), matrix, int(bool(full_range)), hip.current_stream()),
+              "emo_paste_windows_nv12")
+    return nv12
+
+
 def device_cu_count():
     """compute units of the current device as the C launchers count them (include/emo_hip.h, ABI 9)"""
     return hip.load().emo_device_cu_count()

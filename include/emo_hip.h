@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 16
+#define EMO_ABI_VERSION 17
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -494,6 +494,51 @@ int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int W, void* st
  * one of those checks is left untouched by the kernel: nothing is ever written outside a frame or outside a valid window. */
 int emo_paste_windows_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
                            uint8_t* frames, int N, int S, int Hf, int Wf, float feather, void* stream);
+
+/* ABI 17.  NV12 video frames in and out, converted on the device.  A frame of height H and width W, both even, is H rows of Y
+ * bytes and H / 2 rows of W / 2 interleaved (U, V) byte pairs.  Every entry point takes the pointer of the first frame's Y plane
+ * and of its UV plane, the row pitch in bytes (>= W, shared by both planes) and the stride from one frame to the next in bytes
+ * (shared too), which describes any placement of the planes a decoder uses; contiguous frames are uv = y + H * W, pitch = W,
+ * frame_stride = 3 * H * W / 2.
+ *   matrix 0 = bt709 (Kr, Kb) = (0.2126, 0.0722), 1 = bt601 (0.299, 0.114); Kg = 1 - Kr - Kb.
+ *   full_range 0: oy = 16, sy = 219, sc = 224 (limited range); otherwise oy = 0, sy = 255, sc = 255.
+ * Every coefficient derived from these is formed once in fp64 and rounded to fp32; the kernels' arithmetic is fp32, each
+ * operation rounded on its own, summed in the order written.
+ * D (bytes -> RGB in [0,1]); the chroma sample of luma pixel (y, x) is (y >> 1, x >> 1), plain replication:
+ *   y' = (Y - oy) / sy, cb = (U - 128) / sc, cr = (V - 128) / sc
+ *   R = y' + [2 (1 - Kr)] cr,  B = y' + [2 (1 - Kb)] cb,  G = (y' - [2 Kr (1 - Kr) / Kg] cr) - [2 Kb (1 - Kb) / Kg] cb,
+ *   each clamped to [0,1].
+ * E (fp32 image [3,H,W] -> bytes), on x = clamp(img, 0, 1):
+ *   y' = (Kr R + Kg G) + Kb B,  Yc = oy + sy y',  Cbc = 128 + [sc / (2 (1 - Kb))] (B - y'),  Crc = 128 + [sc / (2 (1 - Kr))] (R - y')
+ *   Y byte = floor(Yc + 0.5);  U byte (j, i) = floor((((Cbc[2j,2i] + Cbc[2j,2i+1]) + Cbc[2j+1,2i]) + Cbc[2j+1,2i+1]) * 0.25 + 0.5),
+ *   V the same from Crc; every byte held to 0 ... 255.
+ * All three refuse, before anything is launched, with EMO_ERR_BAD_ARG: a null pointer, an odd or non-positive H or W, pitch < W,
+ * a negative frame stride, a matrix other than 0 or 1.
+ *
+ * emo_nv12_windows_f32 (C): out [N,3,Ho,Wo] fp32, frame n's window (x0, y0, w, h) of D(frame n) resized as
+ *   clamp(F.interpolate(size=(Ho, Wo), mode='bicubic', align_corners=False), 0, 1) -- bit for bit what emo_resize2d_windows_f32
+ *   (bicubic, clamp01) gives on the whole-frame D, without that fp32 frame: only the bytes under the window's taps are read.
+ *   windows N x 4 int32 DEVICE memory, or NULL: every frame whole (with Ho x Wo = Hf x Wf that is D itself); windows_host the
+ *   same values in HOST memory or NULL: a window that leaves the frame is then EMO_ERR_BAD_ARG before the launch.  A frame whose
+ *   device-side window leaves the frame gets zeros.
+ * emo_pack_nv12 (E): img [N,3,H,W] fp32 -> N frames.
+ * emo_paste_windows_nv12 (P): emo_paste_windows_rgb8 on NV12 frames, in place; img, matte, windows, windows_host, S, feather and
+ *   the window checks (square, inside the frame, 4 s >= S; nothing written on refusal) as there.  With r = the resized, clamped
+ *   image in [0,1] (emo_paste_windows_rgb8's r before its * 255) and a its blend weight at a window pixel:
+ *   Y <- floor(((1 - a) Y + a Yc(r)) + 0.5) at every luma pixel of the window;
+ *   a chroma sample is touched if one of its four luma pixels lies in the window: a_i = a at those inside, 0 outside,
+ *   am = (((a_00 + a_01) + a_10) + a_11) * 0.25,
+ *   U <- floor(((1 - am) U + (((a_00 Cbc_00 + a_01 Cbc_01) + a_10 Cbc_10) + a_11 Cbc_11) * 0.25) + 0.5), V the same from Crc.
+ *   a == 0 everywhere returns the frame's bytes and a == 1 (s == S, even x0 and y0) emo_pack_nv12's, exactly.  No byte outside
+ *   the window's luma rectangle and its covering chroma rectangle is read or written, and every byte has one writer. */
+int emo_nv12_windows_f32(const uint8_t* y, const uint8_t* uv, int64_t pitch, int64_t frame_stride, int Hf, int Wf,
+                         const int32_t* windows, const int32_t* windows_host, float* out, int N, int Ho, int Wo, int matrix,
+                         int full_range, void* stream);
+int emo_pack_nv12(const float* img, uint8_t* y, uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int H, int W, int matrix,
+                  int full_range, void* stream);
+int emo_paste_windows_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host, uint8_t* y,
+                           uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int S, int Hf, int Wf, float feather, int matrix,
+                           int full_range, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,9 @@
         [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
         [--stage2-experiment <exp2> --stage2-checkpoint <file> [--cloth]       # refine every batch with the stage-2 model
          (--embedders module:factory | --refine-everywhere)]                   # (<project>/logs_s2/<exp2>), inside the same path
+        [--frame-format nv12 --frame-size WxH [--colorspace bt709|bt601] [--full-range]]   # raw NV12 video in and out:
+         --frames clip.nv12 (or .yuv) as `ffmpeg -pix_fmt nv12 -f rawvideo` writes it; --out a file, raw NV12 of the frames
+         (with --paste-back) or of the crops, which e.g. `ffmpeg -f rawvideo -pix_fmt nv12 -s WxH -i <out>` reads back
 
 Frame I/O is host work (PIL / numpy): decoded frames are handed to InferenceWrapper.animate_frames as uint8 chunks in pinned
 memory; crop, bicubic resize, both embedders, the hot path and the uint8 packing run on the GPU without a host sync, and
@@ -44,6 +47,17 @@ def load_frames(path, chunk):
         yield torch.from_numpy(np.stack(imgs)).pin_memory()
 
 
+def load_nv12(path, width, height, chunk):
+    """yields pinned uint8 [n, 3H/2, W] chunks of a raw NV12 file (frame after frame: H rows of Y, H/2 rows of interleaved U, V)"""
+    per = width * height * 3 // 2
+    size = os.path.getsize(path)
+    if size == 0 or size % per:
+        raise SystemExit(f"{path}: {size} bytes is not a whole number of {width}x{height} NV12 frames of {per} bytes")
+    arr = np.memmap(path, dtype=np.uint8, mode="r").reshape(-1, 3 * height // 2, width)
+    for a in range(0, arr.shape[0], chunk):
+        yield torch.from_numpy(np.array(arr[a:a + chunk])).pin_memory()          # (a copy: the map is read-only)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--project", required=True)
@@ -69,7 +83,23 @@ def main():
     ap.add_argument("--cloth", action="store_true", help="stage 2: no face mask (all ones), as infer_s2.py's cloth=True")
     ap.add_argument("--embedders", default=None, help="module:factory returning {'matting': fn, 'face_parsing': fn} for stage 2")
     ap.add_argument("--refine-everywhere", action="store_true", help="stage 2 with both masks all ones (no matting / parsing nets)")
+    ap.add_argument("--frame-format", default="rgb8", choices=["rgb8", "nv12"], help="nv12: --frames and --out are raw NV12 files")
+    ap.add_argument("--frame-size", default=None, help="with --frame-format nv12: WxH of the frames in --frames")
+    ap.add_argument("--colorspace", default="bt709", choices=["bt709", "bt601"])
+    ap.add_argument("--full-range", action="store_true", help="NV12 in full range (Y 0 ... 255) instead of limited (16 ... 235)")
     a = ap.parse_args()
+    nv12 = a.frame_format == "nv12"
+    if nv12:
+        try:
+            width, height = (int(v) for v in (a.frame_size or "").lower().split("x"))
+        except ValueError:
+            ap.error("--frame-format nv12 needs --frame-size WxH")
+        if width <= 0 or height <= 0 or width % 2 or height % 2:
+            ap.error("--frame-size: NV12 frames have an even width and height")
+        if not a.frames.lower().endswith((".nv12", ".yuv")):
+            ap.error("--frame-format nv12 reads a raw .nv12 / .yuv file")
+    elif a.frame_size or a.full_range or a.colorspace != "bt709":
+        ap.error("--frame-size / --colorspace / --full-range belong to --frame-format nv12")
     refine = a.stage2_experiment is not None
     if refine and (a.stage2_checkpoint is None or (a.embedders is None) == (not a.refine_everywhere)):
         ap.error("--stage2-experiment needs --stage2-checkpoint and one of --embedders module:factory / --refine-everywhere")
@@ -99,16 +129,28 @@ def main():
         torch.from_numpy(np.asarray(Image.open(a.source_mask).convert("L").resize((S, S)), dtype=np.float32) / 255.0)[None, None]
     w.forward(source_image=src, crop=False, source_mask=mask)
     windows = json.load(open(a.windows)) if a.windows else None
-    os.makedirs(a.out, exist_ok=True)
     t0, n = time.perf_counter(), 0
-    frames = load_frames(a.frames, 8 * a.batch)
+    if nv12:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        frames = load_nv12(a.frames, width, height, 8 * a.batch)
+        sink = open(a.out, "wb")
+        fmt = dict(frame_format="nv12", colorspace=a.colorspace, full_range=a.full_range)
+    else:
+        os.makedirs(a.out, exist_ok=True)
+        frames = load_frames(a.frames, 8 * a.batch)
+        sink, fmt = None, {}
     for first, u8 in w.animate_frames(frames, batch_size=a.batch, windows=windows, mix=a.mix, mix_old=not a.mix_new,
                                       target_theta=not a.source_pose, smooth_pose=a.smooth_pose, paste_back=a.paste_back,
-                                      feather=a.feather, refine=refine, refine_masks=refine_masks):
+                                      feather=a.feather, refine=refine, refine_masks=refine_masks, **fmt):
         arr = u8.numpy()
-        for j in range(arr.shape[0]):
-            Image.fromarray(arr[j]).save(os.path.join(a.out, f"{first + j:06d}.png"))
+        if nv12:
+            sink.write(arr.tobytes())                             # batches come in frame order (one rank)
+        else:
+            for j in range(arr.shape[0]):
+                Image.fromarray(arr[j]).save(os.path.join(a.out, f"{first + j:06d}.png"))
         n += arr.shape[0]
+    if sink is not None:
+        sink.close()
     dt = time.perf_counter() - t0
     print(json.dumps(dict(frames=n, seconds=round(dt, 3), fps=round(n / dt, 2), image_size=S, batch=a.batch, refine=refine)))
 
