@@ -925,3 +925,348 @@ extern "C" int emo_paste_windows_nv12(const float* img, const float* matte, cons
                      (long)pitch, (long)frame_stride, (unsigned)total, S, Hf, Wf, (unsigned)cmax, feather, k);
   return emo_launch_status();
 }
+
+// ---- ABI 18: several faces per frame (definitions: include/emo_hip.h).  M faces in F frames, face m in frame frame_of[m];
+// frame_of is sorted, so the faces of a frame are the run of consecutive entries with its value.
+namespace {
+
+// [lo, hi): the run of face m, i.e. every face of its frame
+__device__ __forceinline__ void face_run(const int* __restrict__ frame_of, int M, int m, int& lo, int& hi) {
+  const int f = frame_of[m];
+  lo = m;
+  hi = m + 1;
+  while (lo > 0 && frame_of[lo - 1] == f) --lo;
+  while (hi < M && frame_of[hi] == f) ++hi;
+}
+
+// resize2d_windows_kernel with sample m's planes those of frame frame_of[m]
+__global__ __launch_bounds__(256) void resize2d_faces_kernel(const float* __restrict__ x, long plane_stride, long row_stride,
+                                                             const int* __restrict__ win, const int* __restrict__ frame_of,
+                                                             float* __restrict__ out, long M, int F, int C, int Ho, int Wo,
+                                                             int bicubic, int clamp01) {
+  const long total = M * C * Ho * Wo;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int xo = (int)(i % Wo);
+    const long r = i / Wo;
+    const int yo = (int)(r % Ho);
+    const long mc = r / Ho, m = mc / C;
+    const int f = frame_of[m];
+    if ((unsigned)f >= (unsigned)F) { out[i] = 0.0f; continue; }
+    const int* const w4 = win + 4 * m;
+    const int wx0 = w4[0], wy0 = w4[1], ww = w4[2], wh = w4[3];
+    const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
+    out[i] = resize2d_at(x + ((long)f * C + mc % C) * plane_stride + (long)wy0 * row_stride + wx0, row_stride, wh, ww, sh, sw, yo,
+                         xo, bicubic, clamp01);
+  }
+}
+
+// nv12_windows_kernel with face m's planes those of frame frame_of[m]: the same arithmetic per output
+__global__ __launch_bounds__(256) void nv12_faces_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, long pitch,
+                                                         long fstride, int Hf, int Wf, const int* __restrict__ win,
+                                                         const int* __restrict__ frame_of, float* __restrict__ out, long M, int F,
+                                                         int Ho, int Wo, Nv12Coef k) {
+  const long HWo = (long)Ho * Wo, total = M * HWo;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int xo = (int)(i % Wo);
+    const long r = i / Wo;
+    const int yo = (int)(r % Ho);
+    const long m = r / Ho;
+    const int f = frame_of[m];
+    const int wx0 = win[4 * m], wy0 = win[4 * m + 1], ww = win[4 * m + 2], wh = win[4 * m + 3];
+    float* const o = out + m * 3 * HWo + (long)yo * Wo + xo;
+    if ((unsigned)f >= (unsigned)F || !nv12_window_ok(wx0, wy0, ww, wh, Hf, Wf)) { o[0] = 0.0f; o[HWo] = 0.0f; o[2 * HWo] = 0.0f; continue; }
+    const uint8_t* const fy = yp + f * fstride;
+    const uint8_t* const fuv = uvp + f * fstride;
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    if (ww == Wo && wh == Ho) {
+      nv12_decode_at(fy, fuv, pitch, k, wy0 + yo, wx0 + xo, acc);
+    } else {
+      const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
+      const float sy = sh * ((float)yo + 0.5f) - 0.5f, sx = sw * ((float)xo + 0.5f) - 0.5f;
+      const float fyf = floorf(sy), fxf = floorf(sx);
+      const int iy = (int)fyf, ix = (int)fxf;
+      const float ty = sy - fyf, tx = sx - fxf;
+      const float A = -0.75f;
+      const float wy[4] = {cubic2(ty + 1.0f, A), cubic1(ty, A), cubic1(1.0f - ty, A), cubic2(2.0f - ty, A)};
+      const float wx[4] = {cubic2(tx + 1.0f, A), cubic1(tx, A), cubic1(1.0f - tx, A), cubic2(2.0f - tx, A)};
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        int yy = iy - 1 + a;
+        yy = yy < 0 ? 0 : (yy > wh - 1 ? wh - 1 : yy);
+        float row[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          int xx = ix - 1 + b;
+          xx = xx < 0 ? 0 : (xx > ww - 1 ? ww - 1 : xx);
+          float rgb[3];
+          nv12_decode_at(fy, fuv, pitch, k, wy0 + yy, wx0 + xx, rgb);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) row[c] += rgb[c] * wx[b];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += row[c] * wy[a];
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] = fminf(fmaxf(acc[c], 0.0f), 1.0f);
+    }
+    o[0] = acc[0]; o[HWo] = acc[1]; o[2 * HWo] = acc[2];
+  }
+}
+
+// emo_paste_faces_rgb8.  Work items as in paste_windows_kernel: (face, window row, run of 4 pixels from the row's first dword
+// boundary).  A pixel belongs to the LAST valid face of its frame that covers it: the item of face m drops the pixels a later
+// face of the run covers, starts from the frame's bytes at the others and applies every covering face lo .. m in list order,
+// the value rounded to a byte after each -- the bytes of pasting the faces one after another.  A run of 4 pixels that is wholly
+// the item's own keeps the three aligned dwords; a mixed run, the head and the tail go byte by byte.  Every byte has one writer
+// and is read by that writer only; `win`, `frame_of` and `img` are read by the items of every face of the frame.
+__global__ __launch_bounds__(256) void paste_faces_kernel(const float* __restrict__ img, const float* __restrict__ matte,
+                                                          const int* __restrict__ win, const int* __restrict__ frame_of,
+                                                          uint8_t* __restrict__ frames, unsigned total, int M, int F, int S, int Hf,
+                                                          int Wf, unsigned smax, float feather) {
+  const unsigned Q = (smax + 3u) / 4u + 1u;
+  const long SS = (long)S * S;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const unsigned q = i % Q, rr = i / Q;
+    const int y = (int)(rr % smax);
+    const int m = (int)(rr / smax);
+    const int wx0 = win[4 * m], wy0 = win[4 * m + 1], s = win[4 * m + 2];
+    const int f = frame_of[m];
+    if ((unsigned)f >= (unsigned)F || !paste_window_ok(wx0, wy0, s, win[4 * m + 3], S, Hf, Wf) || y >= s) continue;
+    const int py = wy0 + y;
+    uint8_t* const row = frames + (((long)f * Hf + py) * Wf + wx0) * 3;
+    const int head = (int)(reinterpret_cast<uintptr_t>(row) & 3);
+    const int xa = head + 4 * ((int)q - 1);
+    if (xa >= s) continue;
+    int lo, hi;
+    face_run(frame_of, M, m, lo, hi);
+    // bit p: pixel xa + p is inside the window and no later face of the frame covers it
+    unsigned own = 0u;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) own |= (xa + p >= 0 && xa + p < s) ? 1u << p : 0u;
+    for (int j = m + 1; j < hi; ++j) {
+      const int jx = win[4 * j], jy = win[4 * j + 1], js = win[4 * j + 2];
+      if (!paste_window_ok(jx, jy, js, win[4 * j + 3], S, Hf, Wf) || py < jy || py >= jy + js) continue;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int px = wx0 + xa + p;
+        if (px >= jx && px < jx + js) own &= ~(1u << p);
+      }
+    }
+    if (!own) continue;
+    const bool whole = own == 15u;                       // (then xa >= 0 and xa + 4 <= s)
+    uint32_t* const dw = reinterpret_cast<uint32_t*>(row + 3 * xa);
+    unsigned v[12];
+    if (whole) {
+      const uint32_t d[3] = {dw[0], dw[1], dw[2]};
+#pragma unroll
+      for (int k = 0; k < 12; ++k) v[k] = (d[k >> 2] >> (8 * (k & 3))) & 255u;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) v[k] = (own >> (k / 3)) & 1u ? row[3 * xa + k] : 0u;
+    }
+    for (int j = lo; j <= m; ++j) {
+      const int jx = win[4 * j], jy = win[4 * j + 1], js = win[4 * j + 2];
+      if (!paste_window_ok(jx, jy, js, win[4 * j + 3], S, Hf, Wf) || py < jy || py >= jy + js) continue;
+      const int yj = py - jy;
+      const float scale = (float)S / (float)js, inv_scale = __fdiv_rn(1.0f, scale), fs = feather * (float)js;
+      const float* const im = img + j * 3 * SS;
+      const float* const mt = matte ? matte + j * SS : nullptr;
+      AaTaps ty = {0, 0, 0.0f, 0.0f};
+      if (js < S) ty = aa_taps(yj, scale, inv_scale, S);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int xj = wx0 + xa + p - jx;
+        if (!((own >> p) & 1u) || xj < 0 || xj >= js) continue;
+        float r[3];
+        paste_render(im, S, js, scale, inv_scale, ty, yj, xj, r);
+        const float a = paste_alpha(mt, S, js, scale, feather, fs, yj, xj);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[3 * p + c] = paste_blend(a, v[3 * p + c], r[c]);
+      }
+    }
+    if (whole) {
+      uint32_t o[3] = {0u, 0u, 0u};
+#pragma unroll
+      for (int k = 0; k < 12; ++k) o[k >> 2] |= v[k] << (8 * (k & 3));
+      dw[0] = o[0]; dw[1] = o[1]; dw[2] = o[2];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 12; ++k)
+        if ((own >> (k / 3)) & 1u) row[3 * xa + k] = (uint8_t)v[k];
+    }
+  }
+}
+
+// does the valid window (x0, y0, s) touch chroma sample (cy, cx), i.e. hold one of its four luma pixels
+__device__ __forceinline__ bool chroma_touched(int x0, int y0, int s, int cy, int cx) {
+  return cx >= (x0 >> 1) && 2 * cx < x0 + s && cy >= (y0 >> 1) && 2 * cy < y0 + s;
+}
+
+// emo_paste_faces_nv12.  Work items as in paste_windows_nv12_kernel: (face, chroma sample of its covering chroma rectangle, with
+// the sample's four luma pixels).  A sample belongs to the LAST valid face of its frame that touches it; its item starts from
+// the frame's bytes and applies every touching face lo .. m in list order with paste_windows_nv12_kernel's arithmetic, every
+// value rounded to a byte after each face.  A luma byte no window holds is neither read nor written.
+__global__ __launch_bounds__(256) void paste_faces_nv12_kernel(const float* __restrict__ img, const float* __restrict__ matte,
+                                                               const int* __restrict__ win, const int* __restrict__ frame_of,
+                                                               uint8_t* __restrict__ yp, uint8_t* __restrict__ uvp, long pitch,
+                                                               long fstride, unsigned total, int M, int F, int S, int Hf, int Wf,
+                                                               unsigned cmax, float feather, Nv12Coef k) {
+  const long SS = (long)S * S;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const unsigned rr = i / cmax;
+    const int m = (int)(rr / cmax);
+    const int wx0 = win[4 * m], wy0 = win[4 * m + 1], s = win[4 * m + 2];
+    const int f = frame_of[m];
+    if ((unsigned)f >= (unsigned)F || !paste_window_ok(wx0, wy0, s, win[4 * m + 3], S, Hf, Wf)) continue;
+    const int cx = (wx0 >> 1) + (int)(i % cmax), cy = (wy0 >> 1) + (int)(rr % cmax);
+    if (2 * cx >= wx0 + s || 2 * cy >= wy0 + s) continue;
+    int lo, hi;
+    face_run(frame_of, M, m, lo, hi);
+    bool owned = true;
+    for (int j = m + 1; j < hi; ++j) {
+      const int jx = win[4 * j], jy = win[4 * j + 1], js = win[4 * j + 2];
+      if (paste_window_ok(jx, jy, js, win[4 * j + 3], S, Hf, Wf) && chroma_touched(jx, jy, js, cy, cx)) owned = false;
+    }
+    if (!owned) continue;
+    uint8_t* const fy = yp + f * fstride + (long)(2 * cy) * pitch + 2 * cx;      // the sample's 2 x 2 luma block
+    uint8_t* const puv = uvp + f * fstride + (long)cy * pitch + 2 * cx;
+    // which of the block's luma pixels some face lo .. m holds: only those are read, carried and written
+    unsigned held = 0u;
+    for (int j = lo; j <= m; ++j) {
+      const int jx = win[4 * j], jy = win[4 * j + 1], js = win[4 * j + 2];
+      if (!paste_window_ok(jx, jy, js, win[4 * j + 3], S, Hf, Wf)) continue;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const int yj = 2 * cy + (d >> 1) - jy, xj = 2 * cx + (d & 1) - jx;
+        if (yj >= 0 && yj < js && xj >= 0 && xj < js) held |= 1u << d;
+      }
+    }
+    unsigned yb[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) yb[d] = (held >> d) & 1u ? fy[(d >> 1) * pitch + (d & 1)] : 0u;
+    unsigned u = puv[0], v = puv[1];
+    for (int j = lo; j <= m; ++j) {
+      const int jx = win[4 * j], jy = win[4 * j + 1], js = win[4 * j + 2];
+      if (!paste_window_ok(jx, jy, js, win[4 * j + 3], S, Hf, Wf) || !chroma_touched(jx, jy, js, cy, cx)) continue;
+      const float scale = (float)S / (float)js, inv_scale = __fdiv_rn(1.0f, scale), fs = feather * (float)js;
+      const float* const im = img + j * 3 * SS;
+      const float* const mt = matte ? matte + j * SS : nullptr;
+      float a4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cb4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cr4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy) {
+        const int yj = 2 * cy + dy - jy;
+        if (yj < 0 || yj >= js) continue;
+        AaTaps ty = {0, 0, 0.0f, 0.0f};
+        if (js < S) ty = aa_taps(yj, scale, inv_scale, S);
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          const int xj = 2 * cx + dx - jx;
+          if (xj < 0 || xj >= js) continue;
+          float r[3], yc, cbc, crc;
+          paste_render01(im, S, js, scale, inv_scale, ty, yj, xj, r);
+          const float a = paste_alpha(mt, S, js, scale, feather, fs, yj, xj);
+          nv12_encode(k, r, yc, cbc, crc);
+          yb[2 * dy + dx] = nv12_byte(((1.0f - a) * (float)yb[2 * dy + dx] + a * yc) + 0.5f);
+          a4[2 * dy + dx] = a;
+          cb4[2 * dy + dx] = a * cbc;
+          cr4[2 * dy + dx] = a * crc;
+        }
+      }
+      const float na = 1.0f - (((a4[0] + a4[1]) + a4[2]) + a4[3]) * 0.25f;
+      u = nv12_byte((na * (float)u + (((cb4[0] + cb4[1]) + cb4[2]) + cb4[3]) * 0.25f) + 0.5f);
+      v = nv12_byte((na * (float)v + (((cr4[0] + cr4[1]) + cr4[2]) + cr4[3]) * 0.25f) + 0.5f);
+    }
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      if ((held >> d) & 1u) fy[(d >> 1) * pitch + (d & 1)] = (uint8_t)yb[d];
+    puv[0] = (uint8_t)u;
+    puv[1] = (uint8_t)v;
+  }
+}
+
+// frame_of_host: non-decreasing, every entry in [0, F)
+inline bool frame_of_ok(const int32_t* frame_of_host, int M, int F) {
+  for (int m = 0; m < M; ++m)
+    if (frame_of_host[m] < 0 || frame_of_host[m] >= F || (m > 0 && frame_of_host[m] < frame_of_host[m - 1])) return false;
+  return true;
+}
+
+// the checks the two paste entry points share on a host-side window list -> EMO_OK and the largest side, or the refusal
+inline int paste_faces_windows(const int32_t* windows_host, int M, int S, int Hf, int Wf, int& smax) {
+  smax = Hf < Wf ? Hf : Wf;                        // windows that only the device knows: any valid side
+  if (!windows_host) return EMO_OK;
+  smax = 0;
+  for (int m = 0; m < M; ++m) {
+    const int32_t* w = windows_host + 4 * m;
+    if (!nv12_window_ok(w[0], w[1], w[2], w[3], Hf, Wf)) return EMO_ERR_BAD_ARG;
+    if (!paste_window_ok(w[0], w[1], w[2], w[3], S, Hf, Wf)) return EMO_ERR_UNSUPPORTED;   // not square, or 4 s < S
+    smax = w[2] > smax ? w[2] : smax;
+  }
+  return EMO_OK;
+}
+
+}  // namespace
+
+extern "C" int emo_resize2d_faces_f32(const float* x, int64_t plane_stride, int64_t row_stride, const int32_t* windows,
+                                      const int32_t* frame_of, float* out, int M, int F, int C, int Ho, int Wo, int bicubic,
+                                      int clamp01, void* stream) {
+  if (!x || !out || !windows || !frame_of || M < 0 || F <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || row_stride <= 0 || plane_stride < 0)
+    return EMO_ERR_BAD_ARG;
+  if (M == 0) return EMO_OK;
+  hipLaunchKernelGGL(resize2d_faces_kernel, dim3(grid_for((long)M * C * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, x,
+                     (long)plane_stride, (long)row_stride, windows, frame_of, out, (long)M, F, C, Ho, Wo, bicubic, clamp01);
+  return emo_launch_status();
+}
+
+extern "C" int emo_nv12_faces_f32(const uint8_t* y, const uint8_t* uv, int64_t pitch, int64_t frame_stride, int Hf, int Wf,
+                                  const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
+                                  const int32_t* frame_of_host, float* out, int M, int F, int Ho, int Wo, int matrix, int full_range,
+                                  void* stream) {
+  Nv12Coef k;
+  if (!nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || !out || !windows || !frame_of || M < 0 || F <= 0 || Ho <= 0 || Wo <= 0)
+    return EMO_ERR_BAD_ARG;
+  if (!nv12_coef(matrix, full_range, k) || (frame_of_host && !frame_of_ok(frame_of_host, M, F))) return EMO_ERR_BAD_ARG;
+  if (windows_host)
+    for (int m = 0; m < M; ++m) {
+      const int32_t* w = windows_host + 4 * m;
+      if (!nv12_window_ok(w[0], w[1], w[2], w[3], Hf, Wf)) return EMO_ERR_BAD_ARG;
+    }
+  if (M == 0) return EMO_OK;
+  hipLaunchKernelGGL(nv12_faces_kernel, dim3(grid_for((long)M * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, y, uv, (long)pitch,
+                     (long)frame_stride, Hf, Wf, windows, frame_of, out, (long)M, F, Ho, Wo, k);
+  return emo_launch_status();
+}
+
+extern "C" int emo_paste_faces_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                                    const int32_t* frame_of, const int32_t* frame_of_host, uint8_t* frames, int M, int F, int S,
+                                    int Hf, int Wf, float feather, void* stream) {
+  if (!img || !windows || !frame_of || !frame_of_host || !frames || M < 0 || F <= 0 || S <= 0 || Hf <= 0 || Wf <= 0) return EMO_ERR_BAD_ARG;
+  if (!(feather >= 0.0f && feather <= 0.5f) || !frame_of_ok(frame_of_host, M, F)) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = paste_faces_windows(windows_host, M, S, Hf, Wf, smax);
+  if (rc != EMO_OK || M == 0) return rc;
+  const long total = (long)M * smax * ((smax + 3) / 4 + 1);
+  if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(paste_faces_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
+                     frames, (unsigned)total, M, F, S, Hf, Wf, (unsigned)smax, feather);
+  return emo_launch_status();
+}
+
+extern "C" int emo_paste_faces_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                                    const int32_t* frame_of, const int32_t* frame_of_host, uint8_t* y, uint8_t* uv, int64_t pitch,
+                                    int64_t frame_stride, int M, int F, int S, int Hf, int Wf, float feather, int matrix,
+                                    int full_range, void* stream) {
+  Nv12Coef k;
+  if (!img || !windows || !frame_of || !frame_of_host || !nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || M < 0 || F <= 0 || S <= 0)
+    return EMO_ERR_BAD_ARG;
+  if (!(feather >= 0.0f && feather <= 0.5f) || !nv12_coef(matrix, full_range, k) || !frame_of_ok(frame_of_host, M, F)) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = paste_faces_windows(windows_host, M, S, Hf, Wf, smax);
+  if (rc != EMO_OK || M == 0) return rc;
+  const long cmax = smax / 2 + 1;                  // chroma samples under s luma pixels: at most s / 2 + 1 (an odd origin)
+  const long total = (long)M * cmax * cmax;
+  if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(paste_faces_nv12_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
+                     y, uv, (long)pitch, (long)frame_stride, (unsigned)total, M, F, S, Hf, Wf, (unsigned)cmax, feather, k);
+  return emo_launch_status();
+}

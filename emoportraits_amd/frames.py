@@ -16,6 +16,35 @@ def square_windows(windows):
     return out
 
 
+def flatten_faces(faces):
+    """faces[i] = the (x_lo, y_lo, side) windows of frame i in paste order, [] for a frame without a face, as animate_frames
+    takes them -> (the windows of every face as (x0, y0, s, s) in frame order, the number of faces of every frame)"""
+    flat, counts = [], []
+    for of_frame in faces:
+        wins = square_windows(of_frame)
+        flat += wins
+        counts.append(len(wins))
+    return flat, counts
+
+
+def face_spans(counts, lo, hi, batch_size):
+    """The batches of the frames [lo, hi) of a clip whose frame i has counts[i] faces: [(b0, b1), ...], whole frames taken
+    greedily while a batch holds at most batch_size faces (the rows of the networks' batch) and at most batch_size frames (the
+    rows of a pinned ring slot).  Batches are not padded: a clip with the same number of faces in every frame gets batches of
+    one shape.  A frame with more than batch_size faces fits no batch: ValueError."""
+    spans, b0, n_faces = [], lo, 0
+    for i in range(lo, hi):
+        if counts[i] > batch_size:
+            raise ValueError(f"frame {i} has {counts[i]} faces: more than batch_size={batch_size}")
+        if i > b0 and (n_faces + counts[i] > batch_size or i - b0 >= batch_size):
+            spans.append((b0, i))
+            b0, n_faces = i, 0
+        n_faces += counts[i]
+    if hi > b0:
+        spans.append((b0, hi))
+    return spans
+
+
 FORMATS = ("rgb8", "nv12")
 
 
@@ -40,17 +69,18 @@ def frame_size(chunk, frame_format):
     return (chunk.shape[1], chunk.shape[2]) if frame_format == "rgb8" else (chunk.shape[1] // 3 * 2, chunk.shape[2])
 
 
-def crops_of(u8, size, windows=None, frame_format="rgb8", colorspace="bt709", full_range=False):
+def crops_of(u8, size, windows=None, frame_format="rgb8", colorspace="bt709", full_range=False, frame_of=None):
     """uint8 frames [b,H,W,3] on the device -> fp32 crops [b,3,size,size]: byte -> fp32 CHW (emo_unpack_rgb8), then each frame's
     window (x0, y0, s, s) read in place and resized, the whole batch in one launch (a host list or an int32 [b,4] device
     tensor, ops.resize2d_windows), or without windows the whole frame, resized only where its size differs.
     frame_format 'nv12': NV12 frames [b, 3H/2, W] -> the same crops of the converted frames in ONE launch (ops.nv12_windows:
-    only the bytes under the windows are read, no full-frame fp32 picture is written)."""
+    only the bytes under the windows are read, no full-frame fp32 picture is written).
+    frame_of: several faces per frame -- windows[m] is cut out of frame frame_of[m], still one launch, [len(windows),3,size,size]."""
     if frame_format == "nv12":
-        return ops.nv12_windows(u8, (size, size), windows, colorspace, full_range)
+        return ops.nv12_windows(u8, (size, size), windows, colorspace, full_range, frame_of=frame_of)
     x = ops.unpack_rgb8(u8)
     if windows is not None:
-        return ops.resize2d_windows(x, (size, size), windows, "bicubic", clamp01=True)
+        return ops.resize2d_windows(x, (size, size), windows, "bicubic", clamp01=True, frame_of=frame_of)
     if x.shape[-2:] != (size, size):
         return ops.resize2d(x, (size, size), "bicubic")
     return x

@@ -987,8 +987,8 @@ class InferenceWrapper:
             raise ValueError("paste_matte: None, True (embedders['matting']) or a callable img [b,3,S,S] -> [b,1,S,S]")
         return paste_matte
 
-    def paste_back(self, frames_u8, rendered, windows, feather=0.0625, matte=None, frame_format="rgb8", colorspace="bt709",
-                   full_range=False):
+    def paste_back(self, frames_u8, rendered, windows=None, feather=0.0625, matte=None, frame_format="rgb8", colorspace="bt709",
+                   full_range=False, faces=None):
         """The inverse of the crop: `rendered` [N,3,S,S] fp32 (the hot path's image, before emo_pack_rgb8) goes back into the
         frames the crops came from, frame i where its window windows[i] = (x_lo, y_lo, side) was -- resized to side x side
         (bicubic; antialiased when that shrinks it, down to S / 4), blended over the frame with a feathered edge of
@@ -997,24 +997,37 @@ class InferenceWrapper:
         frames_u8: uint8 [N,Hf,Wf,3], host or device; it is NOT modified (a host tensor is uploaded, a device tensor cloned).
         Returns the device uint8 [N,Hf,Wf,3].  feather = 1/16 of the window is a taste default, not a measured optimum.
         frame_format='nv12': frames_u8 is NV12 uint8 [N, 3Hf/2, Wf] and so is the result (ops.paste_windows_nv12 /
-        emo_paste_windows_nv12, with `colorspace` and `full_range` as in animate_frames)."""
+        emo_paste_windows_nv12, with `colorspace` and `full_range` as in animate_frames).
+        faces= instead of windows=: several faces per frame -- faces[i] = the (x_lo, y_lo, side) of frame i in paste order ([]: no
+        face), `rendered` and the matte hold one row per face in that order, and the faces of a frame are pasted one over the
+        other, the later one on top, still in one launch (emo_paste_faces_rgb8 / emo_paste_faces_nv12)."""
         frames_mod.check_format(frame_format, colorspace)
         if not isinstance(frames_u8, torch.Tensor):
             raise ValueError("frames must be a uint8 tensor")
         frames_mod.check_frames(frames_u8, frame_format)
+        if (windows is None) == (faces is None):
+            raise ValueError("paste_back takes either windows= (one per frame) or faces= (a list per frame)")
         fn = self._paste_matte(matte, 'matte=True')
-        wins = windows if isinstance(windows, torch.Tensor) and windows.is_cuda else frames_mod.square_windows(windows)
+        frame_of = None
+        if faces is not None:
+            wins, counts = frames_mod.flatten_faces(faces)
+            if len(counts) != frames_u8.shape[0]:
+                raise ValueError(f"faces has {len(counts)} entries for {frames_u8.shape[0]} frames")
+            frame_of = [i for i, c in enumerate(counts) for _ in range(c)]
+        else:
+            wins = windows if isinstance(windows, torch.Tensor) and windows.is_cuda else frames_mod.square_windows(windows)
         img = rendered.to(self.device).float().contiguous()
         m = None if fn is None else fn(img).to(self.device).float().contiguous()
         if frame_format == "nv12":
-            return ops.paste_windows_nv12(frames_u8.to(self.device, copy=True), img, wins, feather, m, colorspace, full_range)
+            return ops.paste_windows_nv12(frames_u8.to(self.device, copy=True), img, wins, feather, m, colorspace, full_range,
+                                          frame_of=frame_of)
         full = frames_u8.to(self.device, copy=True).contiguous()
-        return ops.paste_windows(full, img, wins, feather, m)
+        return ops.paste_windows(full, img, wins, feather, m, frame_of=frame_of)
 
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
                        mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
                        paste_matte=None, as_uint8=True, refine=False, refine_masks=None, frame_format="rgb8", out_format=None,
-                       colorspace="bt709", full_range=False):
+                       colorspace="bt709", full_range=False, faces=None):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  Per batch, all on the device and without a host synchronisation:
             byte -> fp32 CHW (emo_unpack_rgb8) -> crop windows read in place + bicubic resize to image_size, the whole batch in
@@ -1078,7 +1091,19 @@ class InferenceWrapper:
             frames, so its out_format is frame_format).  NV12 crops are uint8 [b, 3S/2, S]: the fp32 image, refined or not,
             through emo_pack_nv12 (image_size / output_size_s2 must be even); with paste_back the NV12 frames are pasted in
             place (emo_paste_windows_nv12).  as_uint8=False has no out_format.  Everything else -- upload-ahead, the ring,
-            smooth_pose, identities, the rank sharding, the caller's frames untouched -- is as for rgb8."""
+            smooth_pose, identities, the rank sharding, the caller's frames untouched -- is as for rgb8.
+        faces= instead of windows= (both: ValueError): several faces per frame.  faces[i] = the (x_lo, y_lo, side) of frame i in
+            paste order, [] for a frame without a face, over the whole frame stream.  A batch is a run of whole frames with at
+            most batch_size faces and at most batch_size frames (frames.face_spans; a frame with more faces: ValueError before
+            anything is launched; batches are not padded).  Its frames are uploaded once, ONE crop launch cuts all its faces
+            out of them (emo_resize2d_faces_f32 / emo_nv12_faces_f32), the networks run on one row per face, and with
+            paste_back=True ONE launch pastes the faces of each frame in list order, the later one on top
+            (emo_paste_faces_rgb8 / emo_paste_faces_nv12): what is yielded is (first_frame_index, frames), a batch without a
+            face its frames as they came.  Without paste_back the crops are yielded as (first_face_index, crops), counted over
+            the faces of the whole stream; frames without a face yield nothing.  identities= is then one slot per FACE in
+            that order, and mix / target_theta=False work per face.  smooth_pose needs identities= and smooth_per_identity=True
+            (ValueError otherwise): every face track is its slot's stream.  Ranks shard by FRAMES and take the faces of their
+            frames; for smooth_pose the per-face thetas are gathered (parallel.gather_rows)."""
         frames_mod.check_format(frame_format, colorspace)
         if out_format is not None:
             frames_mod.check_format(out_format, colorspace, "out_format")
@@ -1091,13 +1116,28 @@ class InferenceWrapper:
             frames_mod.check_frames(frames, frame_format)
         if not as_uint8 and (to_host or paste_back):
             raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
-        masks_of, ids = self._preflight(frames.shape[0] if isinstance(frames, torch.Tensor) else None, identities, mix,
-                                        target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
-        wins = None if windows is None else frames_mod.square_windows(windows)
+        n_rows, counts = frames.shape[0] if isinstance(frames, torch.Tensor) else None, None
+        if faces is not None:
+            if windows is not None:
+                raise ValueError("faces= (a list of windows per frame) and windows= (one per frame) are mutually exclusive")
+            wins, counts = frames_mod.flatten_faces(faces)
+            if n_rows is not None and len(counts) != n_rows:
+                raise ValueError(f"faces has {len(counts)} entries for {n_rows} frames")
+            if max(counts, default=0) > batch_size:
+                raise ValueError(f"a frame has {max(counts)} faces: more than batch_size={batch_size}")
+            if smooth_pose and (identities is None or not smooth_per_identity):
+                raise ValueError("smooth_pose=True with faces= smooths every face track as its identity's stream: pass identities= "
+                                 "(one slot per face) and smooth_per_identity=True")
+            n_rows = len(wins)                                                   # identities: one slot per face
+            if identities is not None and len(identities) != n_rows:
+                raise ValueError(f"identities has {len(identities)} entries for {n_rows} faces: one slot per face")
+        else:
+            wins = None if windows is None else frames_mod.square_windows(windows)
+        masks_of, ids = self._preflight(n_rows, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
         matte_fn = None
         if paste_back:
             if wins is None:
-                raise ValueError("paste_back=True needs windows=: one (x_lo, y_lo, side) per frame says where each rendered crop goes")
+                raise ValueError("paste_back=True needs windows= or faces=: (x_lo, y_lo, side) says where each rendered crop goes")
             if not 0.0 <= float(feather) <= 0.5:
                 raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
             matte_fn = self._paste_matte(paste_matte, 'paste_matte=True')
@@ -1112,6 +1152,10 @@ class InferenceWrapper:
         fmt = (frame_format, colorspace, bool(full_range))
         host_ring = frames_mod.HostRing(self.device, ring, batch_size) if to_host else None
         upload_stream = torch.cuda.Stream(device=self.device)
+        if faces is not None:
+            yield from self._animate_faces(frames, wins, counts, ids, batch_size, host_ring, upload_stream, smooth_pose, mix, mix_old,
+                                           target_theta, paste_back, feather, matte_fn, masks_of, out_kind, fmt)
+            return
         base = 0
         for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
             frames_mod.check_frames(chunk, frame_format)
@@ -1171,6 +1215,83 @@ class InferenceWrapper:
                     yield base + b0, out
             base += n
         if to_host:
+            yield from host_ring.drain()
+
+    def _animate_faces(self, frames, wins, counts, ids, batch_size, host_ring, upload_stream, smooth_pose, mix, mix_old,
+                       target_theta, paste_back, feather, matte_fn, masks_of, out_kind, fmt):
+        """animate_frames(faces=...) behind its checks: wins = the (x0, y0, s, s) of every face of the stream in frame order,
+        counts[i] = the faces of frame i, ids = the slot of every face (host tensor) or None.  Per chunk the frames are sharded
+        across the ranks; a batch is a span of whole frames (frames.face_spans) and the rows of everything between the crop
+        and the paste are its faces."""
+        S = self.cfg["image_size"]
+        first = [0]                                                              # first[i] = faces in front of frame i
+        for c in counts:
+            first.append(first[-1] + c)
+        base = 0
+        for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
+            frames_mod.check_frames(chunk, fmt[0])
+            n = chunk.shape[0]
+            if base + n > len(counts):
+                raise ValueError(f"faces has {len(counts)} entries, the frames run past it")
+            lo, hi = parallel.shard_range(n, self.rank, self.world)
+            spans = frames_mod.face_spans(counts[base:base + n], lo, hi, batch_size)
+            rows = lambda b0, b1: (first[base + b0], first[base + b1])           # the faces of the chunk's frames [b0, b1)
+            frame_of = lambda b0, b1: [i - b0 for i in range(b0, b1) for _ in range(counts[base + i])]
+            crops_of = lambda u8, b0, b1: frames_mod.crops_of(u8, S, wins[slice(*rows(b0, b1))], *fmt, frame_of=frame_of(b0, b1))
+            with_faces = [sp for sp in spans if rows(*sp)[0] < rows(*sp)[1]]
+            m_lo, m_hi = rows(lo, hi)
+            ids_dev = None if ids is None else ids[m_lo:m_hi].to(self.device)
+            smoothed, kept = None, {}
+            if smooth_pose:
+                keep_crops = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
+                local = []
+                for b0, b1, u8 in frames_mod.uploaded(chunk, with_faces, self.device, upload_stream):
+                    crops = crops_of(u8, b0, b1)
+                    local.append(self._head_pose(crops)[0].clone())
+                    if keep_crops:
+                        kept[b0] = crops
+                local = torch.cat(local) if local else torch.empty((0, 4, 4), device=self.device)
+                if mix:
+                    local = self._pose_controls(local, ids_dev, True, mix_old, False)
+                per_rank = [rows(*parallel.shard_range(n, r, self.world)) for r in range(self.world)]
+                every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)   # face order
+                ids_chunk = ids[slice(*rows(0, n))].to(self.device)
+                smoothed = self._pose_controls(every, ids_chunk, False, mix_old, True)[m_lo - rows(0, n)[0]:m_hi - rows(0, n)[0]]
+            todo = spans if paste_back else [sp for sp in with_faces if sp[0] not in kept]
+            fresh = frames_mod.uploaded(chunk, todo, self.device, upload_stream)
+            for b0, b1 in spans if paste_back else with_faces:
+                m0, m1 = rows(b0, b1)
+                crops = kept.pop(b0, None)
+                if crops is None or paste_back:
+                    f0, f1, u8 = next(fresh)
+                    assert (f0, f1) == (b0, b1)
+                if m1 == m0:                                                     # (paste_back: frames without a face, as they came)
+                    out = u8.clone() if chunk.is_cuda else u8
+                else:
+                    if crops is None:
+                        crops = crops_of(u8, b0, b1)
+                    ident = None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo]
+                    if smoothed is not None:
+                        theta = smoothed[m0 - m_lo:m1 - m_lo]
+                    else:
+                        theta = self._head_pose(crops)[0]
+                        if mix:
+                            theta = self._pose_controls(theta, ident, True, mix_old, False)
+                    self.pred_target_theta = theta
+                    pose, _ = self._expression(crops, theta, 'a driver call')
+                    out = self._render(pose, theta, ident, target_theta, masks_of, out_kind, fmt[1:])
+                    if paste_back:
+                        full = u8.clone() if chunk.is_cuda else u8               # (a host chunk's upload is this span's own)
+                        m = None if matte_fn is None else matte_fn(out).float().contiguous()
+                        paste = ops.paste_windows_nv12 if fmt[0] == "nv12" else ops.paste_windows
+                        out = paste(full, out, wins[m0:m1], feather, m, *(fmt[1:] if fmt[0] == "nv12" else ()), frame_of=frame_of(b0, b1))
+                index = base + b0 if paste_back else m0
+                if host_ring is not None:
+                    yield from host_ring.push(index, out)
+                else:
+                    yield index, out
+            base += n
+        if host_ring is not None:
             yield from host_ring.drain()
 
     def share_source(self, src_rank=0):

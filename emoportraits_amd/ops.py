@@ -702,34 +702,56 @@ def resize2d(x, size, mode="bilinear", window=None, clamp01=False):
     return out
 
 
-def resize2d_windows(x, size, windows, mode="bicubic", clamp01=False):
+def _frame_of_arg(frame_of, F, device):
+    """frame_of, the frame of each of M faces as a host sequence -> (int32 [M] device tensor, the host tensor), checked here:
+    non-decreasing (the faces of a frame are consecutive, in paste order) and inside [0, F)"""
+    host = torch.tensor([int(v) for v in frame_of], dtype=torch.int32).reshape(-1)
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= F):
+        raise ValueError(f"frame_of names a frame outside the {F} given")
+    if bool((host[1:] < host[:-1]).any()):
+        raise ValueError("frame_of must be non-decreasing: the faces of a frame are consecutive")
+    return host.to(device, non_blocking=True), host
+
+
+def resize2d_windows(x, size, windows, mode="bicubic", clamp01=False, frame_of=None):
     """torch.cat([F.interpolate(x[i:i+1, :, y0:y0+h, x0:x0+w], size=size, mode=mode, align_corners=False) for i ...]) in ONE
     launch (notebooks/infer.py:301-352 crops every frame around its own face box): windows = one (x0, y0, w, h) per frame --
-    a host sequence (uploaded here: 16 bytes per frame) or an int32 [N,4] device tensor.  Bit-identical to resize2d per frame."""
+    a host sequence (uploaded here: 16 bytes per frame) or an int32 [N,4] device tensor.  Bit-identical to resize2d per frame.
+    frame_of (a host sequence of M ints, non-decreasing, inside [0, N)): several faces per frame -- windows has M rows, row m is
+    cut out of frame frame_of[m], and the result has M rows (emo_resize2d_faces_f32: the same bits as this op on x[frame_of])."""
     lib = hip.load()
     hip.require_cuda_f32(x)
     N, C, H, W = x.shape
+    M = N if frame_of is None else len(frame_of)
     if isinstance(windows, torch.Tensor):
         win = windows
-        if not win.is_cuda or win.dtype != torch.int32 or tuple(win.shape) != (N, 4) or not win.is_contiguous():
+        if not win.is_cuda or win.dtype != torch.int32 or tuple(win.shape) != (M, 4) or not win.is_contiguous():
             raise RuntimeError("windows must be a contiguous int32 cuda tensor [N,4]")
     else:
         host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
-        if host.shape[0] != N:
-            raise ValueError(f"{host.shape[0]} windows for {N} frames")
+        if host.shape[0] != M:
+            raise ValueError(f"{host.shape[0]} windows for {M} {'frames' if frame_of is None else 'faces'}")
         lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
         if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi[:, 0] <= W).all()) and bool((hi[:, 1] <= H).all())):
             raise ValueError(f"a resize window is not inside the {W}x{H} frame")
         win = host.to(x.device, non_blocking=True)
     Ho, Wo = size
-    out = torch.empty((N, C, Ho, Wo), device=x.device, dtype=torch.float32)
+    out = torch.empty((M, C, Ho, Wo), device=x.device, dtype=torch.float32)
+    bicubic = {"bilinear": 0, "bicubic": 1}[mode]
+    if frame_of is not None:
+        fof, _ = _frame_of_arg(frame_of, N, x.device)
+        if M == 0:
+            return out
+        hip.check(lib.emo_resize2d_faces_f32(hip.ptr(x), H * W, W, hip.ptr(win), hip.ptr(fof), hip.ptr(out), M, N, C, Ho, Wo, bicubic,
+                                             int(clamp01), hip.current_stream()), "emo_resize2d_faces_f32")
+        return out
     hip.check(lib.emo_resize2d_windows_f32(hip.ptr(x), H * W, W, hip.ptr(win), hip.ptr(out), N, C, Ho, Wo,
-                                           {"bilinear": 0, "bicubic": 1}[mode], int(clamp01), hip.current_stream()),
+                                           bicubic, int(clamp01), hip.current_stream()),
               "emo_resize2d_windows_f32")
     return out
 
 
-def paste_windows(frames_u8, img, windows, feather=0.0, matte=None):
+def paste_windows(frames_u8, img, windows, feather=0.0, matte=None, frame_of=None):
     """The inverse of resize2d_windows' crop, in ONE launch and IN PLACE: img [N,3,S,S] fp32 (the renderer's output) goes back
     into frames_u8 [N,Hf,Wf,3] uint8 where each frame's SQUARE window (x0, y0, s, s) was -- bicubic resize to (s, s)
     (antialiased where s < S), clamp(0,1) * 255, blended as (1 - a) * frame + a * image and truncated like pack_rgb8, with a =
@@ -737,12 +759,16 @@ def paste_windows(frames_u8, img, windows, feather=0.0, matte=None):
     resized bilinearly (include/emo_hip.h has the definition).  windows = one (x0, y0, w, h) per frame: a host sequence
     (checked and uploaded here: inside the frame, square, s >= S / 4) or an int32 [N,4] device tensor (trusted: the kernel
     leaves the frame of a window that fails those checks untouched).  Bytes outside the windows are neither read nor written.
-    Returns frames_u8."""
+    Returns frames_u8.
+    frame_of (a host sequence of M ints, non-decreasing, inside [0, N)): several faces per frame -- img, matte and windows have M
+    rows, face m goes into frame frame_of[m], and the faces of a frame are pasted in list order, the later one on top, still in
+    one launch (emo_paste_faces_rgb8: the bytes of pasting them one after another with this op)."""
     lib = hip.load()
     hip.require_cuda_f32(img, matte)
     if frames_u8.device != img.device or frames_u8.dtype != torch.uint8 or not frames_u8.is_contiguous() or frames_u8.dim() != 4:
         raise RuntimeError("paste_windows expects a contiguous uint8 tensor [N,H,W,3] on the images' device")
     N, Hf, Wf, C = frames_u8.shape
+    F, N = N, (N if frame_of is None else len(frame_of))                     # F frames, N rows of img / matte / windows
     if C != 3 or img.dim() != 4 or img.shape[0] != N or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
         raise ValueError(f"frames {tuple(frames_u8.shape)} and images {tuple(img.shape)}: expected [N,Hf,Wf,3] and [N,3,S,S]")
     S = img.shape[2]
@@ -758,7 +784,7 @@ def paste_windows(frames_u8, img, windows, feather=0.0, matte=None):
     else:
         host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
         if host.shape[0] != N:
-            raise ValueError(f"{host.shape[0]} windows for {N} frames")
+            raise ValueError(f"{host.shape[0]} windows for {N} {'frames' if frame_of is None else 'faces'}")
         lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
         if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi[:, 0] <= Wf).all()) and bool((hi[:, 1] <= Hf).all())):
             raise ValueError(f"a paste window is not inside the {Wf}x{Hf} frame")
@@ -767,6 +793,14 @@ def paste_windows(frames_u8, img, windows, feather=0.0, matte=None):
         if not bool((4 * host[:, 2] >= S).all()):
             raise ValueError(f"a paste window is smaller than a quarter of the {S}x{S} image: downscaling stops at S / 4")
         win = host.to(frames_u8.device, non_blocking=True)
+    if frame_of is not None:
+        fof, fof_host = _frame_of_arg(frame_of, F, frames_u8.device)
+        if N == 0:
+            return frames_u8
+        hip.check(lib.emo_paste_faces_rgb8(hip.ptr(img), hip.ptr(matte), hip.ptr(win), hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host),
+                                           hip.ptr(frames_u8), N, F, S, Hf, Wf, float(feather), hip.current_stream()),
+                  "emo_paste_faces_rgb8")
+        return frames_u8
     if N == 0:
         return frames_u8
     hip.check(lib.emo_paste_windows_rgb8(hip.ptr(img), hip.ptr(matte), hip.ptr(win), hip.ptr(host), hip.ptr(frames_u8), N, S, Hf, Wf,
@@ -814,19 +848,32 @@ def _windows_arg(windows, N, Wf, Hf, device, what):
     return host.to(device, non_blocking=True), host
 
 
-def nv12_windows(nv12, size=None, windows=None, colorspace="bt709", full_range=False):
+def nv12_windows(nv12, size=None, windows=None, colorspace="bt709", full_range=False, frame_of=None):
     """NV12 frames uint8 [N, 3H/2, W] on the device -> fp32 [N,3,Ho,Wo] in [0,1], ONE launch (emo_nv12_windows_f32): each frame's
     window (x0, y0, w, h) of the converted frame, resized bicubically to size = (Ho, Wo) and clamped -- bit for bit
     resize2d_windows(..., 'bicubic', clamp01=True) of the whole-frame conversion, which is never written.  windows: a host
     sequence (checked, uploaded), an int32 [N,4] device tensor (a window that leaves the frame gives zeros), or None = the whole
-    frame; size None = (H, W), with windows None the plain conversion.  include/emo_hip.h has the definition."""
+    frame; size None = (H, W), with windows None the plain conversion.  include/emo_hip.h has the definition.
+    frame_of (a host sequence of M ints, non-decreasing, inside [0, N)): several faces per frame -- windows has M rows, row m is
+    cut out of frame frame_of[m], and the result has M rows (emo_nv12_faces_f32: the same bits as this op on nv12[frame_of])."""
     lib = hip.load()
     y, uv, pitch, fstride, N, H, W = _nv12_planes(nv12, "nv12_windows")
     matrix = _nv12_matrix(colorspace)
     Ho, Wo = (H, W) if size is None else size
-    out = torch.empty((N, 3, Ho, Wo), device=nv12.device, dtype=torch.float32)
+    if frame_of is not None and windows is None:
+        raise ValueError("frame_of= needs windows=: one per face")
+    M = N if frame_of is None else len(frame_of)
+    out = torch.empty((M, 3, Ho, Wo), device=nv12.device, dtype=torch.float32)
     hip.require_cuda_f32(out)                                    # (the frames' device: GPU only, like every op)
-    win, host = (None, None) if windows is None else _windows_arg(windows, N, W, H, nv12.device, "crop")
+    win, host = (None, None) if windows is None else _windows_arg(windows, M, W, H, nv12.device, "crop")
+    if frame_of is not None:
+        fof, fof_host = _frame_of_arg(frame_of, N, nv12.device)
+        if M == 0:
+            return out
+        hip.check(lib.emo_nv12_faces_f32(y, uv, pitch, fstride, H, W, hip.ptr(win), hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host),
+                                         hip.ptr(out), M, N, Ho, Wo, matrix, int(bool(full_range)), hip.current_stream()),
+                  "emo_nv12_faces_f32")
+        return out
     if N == 0:
         return out
     hip.check(lib.emo_nv12_windows_f32(y, uv, pitch, fstride, H, W, hip.ptr(win), hip.ptr(host), hip.ptr(out), N, Ho, Wo, matrix,
@@ -857,18 +904,21 @@ def pack_nv12(img, colorspace="bt709", full_range=False, out=None):
     return out
 
 
-def paste_windows_nv12(nv12, img, windows, feather=0.0, matte=None, colorspace="bt709", full_range=False):
+def paste_windows_nv12(nv12, img, windows, feather=0.0, matte=None, colorspace="bt709", full_range=False, frame_of=None):
     """paste_windows on NV12 frames uint8 [N, 3Hf/2, Wf], IN PLACE and in one launch (emo_paste_windows_nv12): the resized,
     clamped image and the blend weight a of paste_windows; luma blended per pixel, each chroma sample under the window with the
     mean of its (up to four) window pixels' weights and weighted chroma (include/emo_hip.h has the definition).  windows as in
     paste_windows.  Bytes outside a window's luma rectangle and its covering chroma rectangle are neither read nor written.
-    Returns nv12."""
+    Returns nv12.
+    frame_of: several faces per frame as in paste_windows -- img, matte and windows have M rows, face m goes into frame
+    frame_of[m], the faces of a frame in list order, one launch (emo_paste_faces_nv12)."""
     lib = hip.load()
     hip.require_cuda_f32(img, matte)
     if nv12.device != img.device:
         raise RuntimeError("paste_windows_nv12 expects the NV12 frames on the images' device")
     y, uv, pitch, fstride, N, Hf, Wf = _nv12_planes(nv12, "paste_windows_nv12")
     matrix = _nv12_matrix(colorspace)
+    F, N = N, (N if frame_of is None else len(frame_of))                     # F frames, N rows of img / matte / windows
     if img.dim() != 4 or img.shape[0] != N or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
         raise ValueError(f"frames {tuple(nv12.shape)} and images {tuple(img.shape)}: expected [N,3Hf/2,Wf] and [N,3,S,S]")
     S = img.shape[2]
@@ -882,6 +932,14 @@ def paste_windows_nv12(nv12, img, windows, feather=0.0, matte=None, colorspace="
             raise ValueError("paste windows must be square")
         if not bool((4 * host[:, 2] >= S).all()):
             raise ValueError(f"a paste window is smaller than a quarter of the {S}x{S} image: downscaling stops at S / 4")
+    if frame_of is not None:
+        fof, fof_host = _frame_of_arg(frame_of, F, img.device)
+        if N == 0:
+            return nv12
+        hip.check(lib.emo_paste_faces_nv12(hip.ptr(img), hip.ptr(matte), hip.ptr(win), hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host),
+                                           y, uv, pitch, fstride, N, F, S, Hf, Wf, float(feather), matrix, int(bool(full_range)),
+                                           hip.current_stream()), "emo_paste_faces_nv12")
+        return nv12
     if N == 0:
         return nv12
     hip.check(lib.emo_paste_windows_nv12(hip.ptr(img), hip.ptr(matte), hip.ptr(win), hip.ptr(host), y, uv, pitch, fstride, N, S, Hf,

@@ -193,6 +193,32 @@ def gather_shards(local, n_items, rank=None, world=None):
     return torch.cat(rows)
 
 
+def gather_rows(local, counts, rank=None, world=None):
+    """gather_shards for shards whose sizes every rank knows but shard_range does not give: rank r holds counts[r] rows (the
+    per-face thetas of the frames of its shard, several or no faces per frame) -> all sum(counts) rows on EVERY rank, in rank
+    order.  One all_gather of equal-size padded shards."""
+    if world is None:
+        world = dist.get_world_size() if dist.is_initialized() else 1
+    if rank is None:
+        rank = dist.get_rank() if dist.is_initialized() else 0
+    counts = [int(c) for c in counts]
+    if len(counts) != world or not (0 <= rank < world):
+        raise ValueError(f"{len(counts)} row counts for {world} ranks")
+    if local.shape[0] != counts[rank]:
+        raise ValueError(f"rank {rank} holds {local.shape[0]} rows, its count is {counts[rank]}")
+    if world == 1:
+        return local
+    if not dist.is_initialized():
+        raise RuntimeError(f"gather_rows(world={world}) without a process group: call init_distributed() first")
+    if world != dist.get_world_size():
+        raise RuntimeError(f"world={world} does not match the process group's {dist.get_world_size()} ranks")
+    mine = torch.zeros((max(counts),) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
+    mine[:counts[rank]].copy_(local)
+    parts = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(parts, mine)
+    return torch.cat([parts[r][:counts[r]] for r in range(world)])
+
+
 _MAX_DIMS = 6
 
 

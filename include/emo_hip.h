@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 17
+#define EMO_ABI_VERSION 18
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -539,6 +539,43 @@ int emo_pack_nv12(const float* img, uint8_t* y, uint8_t* uv, int64_t pitch, int6
 int emo_paste_windows_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host, uint8_t* y,
                            uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int S, int Hf, int Wf, float feather, int matrix,
                            int full_range, void* stream);
+
+/* ABI 18.  Several faces per frame: M faces in F frames, face m lives in frame frame_of[m].  The crop and the paste entry points
+ * above with the frame of a row looked up instead of being the row's own number.
+ *   frame_of int32 [M], DEVICE memory, non-decreasing, every entry in [0, F) -- the faces of a frame are then the run of
+ *   consecutive entries with its number, and their order in the list is the order they are pasted in; frame_of_host the same
+ *   values in HOST memory; windows M x (x0, y0, w, h) int32 DEVICE memory and windows_host the same in HOST memory or NULL, as
+ *   above.  x / y, uv / frames hold F frames; img, matte and out hold M rows.
+ * Crops (emo_resize2d_faces_f32, emo_nv12_faces_f32): out[m] is bit for bit what emo_resize2d_windows_f32 / emo_nv12_windows_f32
+ *   gives for a batch whose frame m is frame frame_of[m].  A face whose frame_of lies outside [0, F) gets zeros; for NV12 a face
+ *   whose device-side window leaves the frame gets zeros too.
+ * Paste (emo_paste_faces_rgb8, emo_paste_faces_nv12), in place and in ONE launch: the result is bit for bit that of pasting
+ *   the M faces one after another, in list order, each with emo_paste_windows_rgb8 / emo_paste_windows_nv12 (N = 1) on its own
+ *   frame -- the frame's bytes are rounded to bytes between two faces.  Overlapping windows of one frame are therefore well
+ *   defined: the later face lies on top, blended by its own a.  No byte outside the union of the valid windows (NV12: and of
+ *   their covering chroma rectangles) is read or written; every byte has exactly one writer, and no work item reads a byte
+ *   another one writes: a pixel (NV12: a chroma sample with its four luma pixels) belongs to the last valid face of its frame
+ *   that covers (touches) it, whose work item starts from the frame's bytes and applies every covering face of the run in list
+ *   order, the value carried as a byte.  windows, frame_of, img and matte are only read.
+ * Refusals, before anything is launched and with nothing written.  EMO_ERR_BAD_ARG: a null pointer (matte, windows_host and the
+ *   crop's frame_of_host may be NULL), M < 0, F <= 0, a frame_of_host that decreases or leaves [0, F), a NULL frame_of_host for
+ *   the paste entry points (the order of the paste rests on the list being sorted), a host-side window that leaves the frame
+ *   (or has w or h <= 0), and what the single-window entry points refuse (feather, planes, matrix).  EMO_ERR_UNSUPPORTED: a
+ *   host-side paste window with w != h or 4 * s < S.  M == 0 is EMO_OK and launches nothing.  A face whose window exists only on
+ *   the device and is not a square inside the frame with 4 * s >= S, or whose device-side frame_of leaves [0, F), is treated as
+ *   absent by the paste: it neither owns nor changes a byte. */
+int emo_resize2d_faces_f32(const float* x, int64_t plane_stride, int64_t row_stride, const int32_t* windows, const int32_t* frame_of,
+                           float* out, int M, int F, int C, int Ho, int Wo, int bicubic, int clamp01, void* stream);
+int emo_nv12_faces_f32(const uint8_t* y, const uint8_t* uv, int64_t pitch, int64_t frame_stride, int Hf, int Wf,
+                       const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host,
+                       float* out, int M, int F, int Ho, int Wo, int matrix, int full_range, void* stream);
+int emo_paste_faces_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                         const int32_t* frame_of, const int32_t* frame_of_host, uint8_t* frames, int M, int F, int S, int Hf, int Wf,
+                         float feather, void* stream);
+int emo_paste_faces_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                         const int32_t* frame_of, const int32_t* frame_of_host, uint8_t* y, uint8_t* uv, int64_t pitch,
+                         int64_t frame_stride, int M, int F, int S, int Hf, int Wf, float feather, int matrix, int full_range,
+                         void* stream);
 
 #ifdef __cplusplus
 }

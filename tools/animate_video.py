@@ -4,6 +4,9 @@
     python tools/animate_video.py --project <project_dir> --experiment <exp> --checkpoint <file> \
         --source source.png --frames <dir of PNG/JPG frames | frames.npy (uint8 [N,H,W,3])> --out <dir> [--batch 16]
         [--windows windows.json]   # optional per-frame crop windows [[x_lo, y_lo, side], ...] from a face detector
+        [--faces faces.json [--sources a.png,b.png --identities ids.json]]   # several faces per frame: [[[x_lo, y_lo, side], ...],
+         ...], one list per frame in paste order ([]: no face); --sources enrols several source images into an identity bank
+         (slots 0, 1, ... in that order) and ids.json names the slot of every face, flattened in frame order
         [--mix [--mix-new]] [--source-pose] [--smooth-pose]   # forward()'s pose controls (mix, mix_old=False, target_theta=False)
         [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
         [--stage2-experiment <exp2> --stage2-checkpoint <file> [--cloth]       # refine every batch with the stage-2 model
@@ -69,6 +72,9 @@ def main():
     ap.add_argument("--source-mask", default=None)
     ap.add_argument("--frames", required=True)
     ap.add_argument("--windows", default=None)
+    ap.add_argument("--faces", default=None, help="several faces per frame: a JSON list per frame of [x_lo, y_lo, side], in paste order")
+    ap.add_argument("--sources", default=None, help="comma-separated source images enrolled into bank slots 0, 1, ... (--identities)")
+    ap.add_argument("--identities", default=None, help="JSON list: the bank slot of every frame, or with --faces of every face")
     ap.add_argument("--out", required=True)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--graphs", action="store_true")
@@ -76,7 +82,7 @@ def main():
     ap.add_argument("--mix-new", action="store_true", help="with --mix: the reference's mix_old=False formula")
     ap.add_argument("--source-pose", action="store_true", help="render in the source's own head pose (target_theta=False)")
     ap.add_argument("--smooth-pose", action="store_true", help="EMA over the driver head poses (smooth_pose=True)")
-    ap.add_argument("--paste-back", action="store_true", help="write the full frames with the rendered crop pasted back (needs --windows)")
+    ap.add_argument("--paste-back", action="store_true", help="write the full frames with the rendered crops pasted back (needs --windows or --faces)")
     ap.add_argument("--feather", type=float, default=0.0625, help="with --paste-back: blended edge as a fraction of the window side")
     ap.add_argument("--stage2-experiment", default=None, help="refine with the stage-2 model <project>/logs_s2/<this>")
     ap.add_argument("--stage2-checkpoint", default=None)
@@ -100,6 +106,13 @@ def main():
             ap.error("--frame-format nv12 reads a raw .nv12 / .yuv file")
     elif a.frame_size or a.full_range or a.colorspace != "bt709":
         ap.error("--frame-size / --colorspace / --full-range belong to --frame-format nv12")
+    if a.faces and a.windows:
+        ap.error("--faces and --windows are mutually exclusive")
+    if (a.sources is None) != (a.identities is None):
+        ap.error("--sources (the images of the bank's slots) and --identities (the slot of every face or frame) go together")
+    if a.smooth_pose and a.faces and not a.identities:
+        ap.error("--smooth-pose with --faces smooths every face track as its identity's stream: it needs --sources / --identities")
+    sources = a.sources.split(",") if a.sources else []
     refine = a.stage2_experiment is not None
     if refine and (a.stage2_checkpoint is None or (a.embedders is None) == (not a.refine_everywhere)):
         ap.error("--stage2-experiment needs --stage2-checkpoint and one of --embedders module:factory / --refine-everywhere")
@@ -108,7 +121,8 @@ def main():
     from PIL import Image
     from notebooks.infer import InferenceWrapper
     w = InferenceWrapper(experiment_name=a.experiment, model_file_name=a.checkpoint, project_dir=a.project, folder=a.folder,
-                         head_pose_regressor_path=a.head_pose_regressor, use_graphs=a.graphs)
+                         head_pose_regressor_path=a.head_pose_regressor, use_graphs=a.graphs,
+                         identity_capacity=len(sources))
     refine_masks = None
     if refine:
         from notebooks.infer_s2 import InferenceWrapper as InferenceWrapperS2
@@ -129,6 +143,11 @@ def main():
         torch.from_numpy(np.asarray(Image.open(a.source_mask).convert("L").resize((S, S)), dtype=np.float32) / 255.0)[None, None]
     w.forward(source_image=src, crop=False, source_mask=mask)
     windows = json.load(open(a.windows)) if a.windows else None
+    faces = json.load(open(a.faces)) if a.faces else None
+    identities = None
+    if sources:
+        w.enrol_identities([Image.open(f).convert("RGB") for f in sources], slots=list(range(len(sources))), batch_size=a.batch)
+        identities = json.load(open(a.identities))
     t0, n = time.perf_counter(), 0
     if nv12:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -139,8 +158,10 @@ def main():
         os.makedirs(a.out, exist_ok=True)
         frames = load_frames(a.frames, 8 * a.batch)
         sink, fmt = None, {}
-    for first, u8 in w.animate_frames(frames, batch_size=a.batch, windows=windows, mix=a.mix, mix_old=not a.mix_new,
-                                      target_theta=not a.source_pose, smooth_pose=a.smooth_pose, paste_back=a.paste_back,
+    # (without --paste-back the crops of --faces come face by face: `first` then counts faces, not frames)
+    for first, u8 in w.animate_frames(frames, batch_size=a.batch, windows=windows, faces=faces, identities=identities, mix=a.mix,
+                                      mix_old=not a.mix_new, target_theta=not a.source_pose, smooth_pose=a.smooth_pose,
+                                      smooth_per_identity=identities is not None, paste_back=a.paste_back,
                                       feather=a.feather, refine=refine, refine_masks=refine_masks, **fmt):
         arr = u8.numpy()
         if nv12:
