@@ -939,6 +939,23 @@ __device__ __forceinline__ void face_run(const int* __restrict__ frame_of, int M
   while (hi < M && frame_of[hi] == f) ++hi;
 }
 
+// ABI 19: frames of different sizes.  A row of the frame table is (byte address of the frame's first row, row pitch in bytes,
+// H, W); a RAGGED launch has one face per blockIdx.y, so the face's frame and its table row are uniform across the block and
+// are loaded once, in front of the item loop.  A frame_of outside [0, F) gives an empty frame (H = W = 0): no window fits it.
+struct FrameRow { uint8_t* base; long pitch; int H, W; };
+__device__ __forceinline__ FrameRow frame_row(const long long* __restrict__ ftab, const int* __restrict__ frame_of, int F) {
+  const int f = frame_of[blockIdx.y];
+  FrameRow r = {nullptr, 0, 0, 0};
+  if ((unsigned)f < (unsigned)F) {
+    const long long* const t = ftab + 4l * f;
+    r.base = reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(t[0]));
+    r.pitch = (long)t[1];
+    r.H = (int)t[2];
+    r.W = (int)t[3];
+  }
+  return r;
+}
+
 // resize2d_windows_kernel with sample m's planes those of frame frame_of[m]
 __global__ __launch_bounds__(256) void resize2d_faces_kernel(const float* __restrict__ x, long plane_stride, long row_stride,
                                                              const int* __restrict__ win, const int* __restrict__ frame_of,
@@ -961,16 +978,23 @@ __global__ __launch_bounds__(256) void resize2d_faces_kernel(const float* __rest
 }
 
 // nv12_windows_kernel with face m's planes those of frame frame_of[m]: the same arithmetic per output
+// RAGGED (emo_nv12_faces_ragged_f32): grid (x, M), the items of a block are the outputs of face blockIdx.y, and the planes,
+// the pitch and the size are those of the face's row of the frame table (frame stride 0: yp IS the frame)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void nv12_faces_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, long pitch,
                                                          long fstride, int Hf, int Wf, const int* __restrict__ win,
                                                          const int* __restrict__ frame_of, float* __restrict__ out, long M, int F,
-                                                         int Ho, int Wo, Nv12Coef k) {
-  const long HWo = (long)Ho * Wo, total = M * HWo;
+                                                         int Ho, int Wo, Nv12Coef k, const long long* __restrict__ ftab) {
+  const long HWo = (long)Ho * Wo, total = (RAGGED ? 1 : M) * HWo;
+  if constexpr (RAGGED) {
+    const FrameRow fr = frame_row(ftab, frame_of, F);
+    yp = fr.base; uvp = fr.base + fr.H * fr.pitch; pitch = fr.pitch; fstride = 0; Hf = fr.H; Wf = fr.W;
+  }
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int xo = (int)(i % Wo);
     const long r = i / Wo;
     const int yo = (int)(r % Ho);
-    const long m = r / Ho;
+    const long m = RAGGED ? (long)blockIdx.y : r / Ho;
     const int f = frame_of[m];
     const int wx0 = win[4 * m], wy0 = win[4 * m + 1], ww = win[4 * m + 2], wh = win[4 * m + 3];
     float* const o = out + m * 3 * HWo + (long)yo * Wo + xo;
@@ -1013,27 +1037,83 @@ __global__ __launch_bounds__(256) void nv12_faces_kernel(const uint8_t* __restri
   }
 }
 
+// emo_rgb8_faces_ragged_f32: one thread per output pixel of face blockIdx.y, all three channels.  Per channel the arithmetic is
+// resize2d_at's bicubic on the window (taps clamped into the WINDOW, rows first, clamp01) with every tap unpack_rgb8_kernel's
+// byte / 255, converted where it is read: bit for bit emo_unpack_rgb8 + emo_resize2d_faces_f32 without the fp32 frame.  The 16
+// taps of neighbouring outputs overlap and the bytes under them stay in L1 / L2 (nv12_windows_kernel's reasoning).
+__global__ __launch_bounds__(256) void rgb8_faces_ragged_kernel(const long long* __restrict__ ftab, const int* __restrict__ win,
+                                                                const int* __restrict__ frame_of, float* __restrict__ out, int F,
+                                                                int Ho, int Wo) {
+  const long HWo = (long)Ho * Wo;
+  const FrameRow fr = frame_row(ftab, frame_of, F);
+  const long m = blockIdx.y;
+  const int wx0 = win[4 * m], wy0 = win[4 * m + 1], ww = win[4 * m + 2], wh = win[4 * m + 3];
+  const bool ok = nv12_window_ok(wx0, wy0, ww, wh, fr.H, fr.W);
+  const uint8_t* const p = ok ? fr.base + (long)wy0 * fr.pitch + 3l * wx0 : nullptr;      // the window's first byte
+  const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < HWo; i += (long)gridDim.x * 256) {
+    const int xo = (int)(i % Wo), yo = (int)(i / Wo);
+    float* const o = out + m * 3 * HWo + i;
+    if (!ok) { o[0] = 0.0f; o[HWo] = 0.0f; o[2 * HWo] = 0.0f; continue; }
+    const float sy = sh * ((float)yo + 0.5f) - 0.5f, sx = sw * ((float)xo + 0.5f) - 0.5f;
+    const float fyf = floorf(sy), fxf = floorf(sx);
+    const int iy = (int)fyf, ix = (int)fxf;
+    const float ty = sy - fyf, tx = sx - fxf;
+    const float A = -0.75f;
+    const float wy[4] = {cubic2(ty + 1.0f, A), cubic1(ty, A), cubic1(1.0f - ty, A), cubic2(2.0f - ty, A)};
+    const float wx[4] = {cubic2(tx + 1.0f, A), cubic1(tx, A), cubic1(1.0f - tx, A), cubic2(2.0f - tx, A)};
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      int yy = iy - 1 + a;
+      yy = yy < 0 ? 0 : (yy > wh - 1 ? wh - 1 : yy);
+      const uint8_t* const prow = p + (long)yy * fr.pitch;
+      float row[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        int xx = ix - 1 + b;
+        xx = xx < 0 ? 0 : (xx > ww - 1 ? ww - 1 : xx);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) row[c] += __fdiv_rn((float)prow[3 * xx + c], 255.0f) * wx[b];
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] += row[c] * wy[a];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c * HWo] = fminf(fmaxf(acc[c], 0.0f), 1.0f);
+  }
+}
+
 // emo_paste_faces_rgb8.  Work items as in paste_windows_kernel: (face, window row, run of 4 pixels from the row's first dword
 // boundary).  A pixel belongs to the LAST valid face of its frame that covers it: the item of face m drops the pixels a later
 // face of the run covers, starts from the frame's bytes at the others and applies every covering face lo .. m in list order,
 // the value rounded to a byte after each -- the bytes of pasting the faces one after another.  A run of 4 pixels that is wholly
 // the item's own keeps the three aligned dwords; a mixed run, the head and the tail go byte by byte.  Every byte has one writer
 // and is read by that writer only; `win`, `frame_of` and `img` are read by the items of every face of the frame.
+// RAGGED (emo_paste_faces_ragged_rgb8): grid (x, M), `total` the items of ONE face, the face blockIdx.y; `frames`, the row pitch
+// and the size are those of the face's row of the frame table.  The head of a row is taken from its address, whatever the
+// frame's address and pitch are.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void paste_faces_kernel(const float* __restrict__ img, const float* __restrict__ matte,
                                                           const int* __restrict__ win, const int* __restrict__ frame_of,
                                                           uint8_t* __restrict__ frames, unsigned total, int M, int F, int S, int Hf,
-                                                          int Wf, unsigned smax, float feather) {
+                                                          int Wf, unsigned smax, float feather, const long long* __restrict__ ftab) {
   const unsigned Q = (smax + 3u) / 4u + 1u;
   const long SS = (long)S * S;
+  long pitch = 0;
+  if constexpr (RAGGED) {
+    const FrameRow fr = frame_row(ftab, frame_of, F);
+    frames = fr.base; pitch = fr.pitch; Hf = fr.H; Wf = fr.W;
+  }
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     const unsigned q = i % Q, rr = i / Q;
     const int y = (int)(rr % smax);
-    const int m = (int)(rr / smax);
+    const int m = RAGGED ? (int)blockIdx.y : (int)(rr / smax);
     const int wx0 = win[4 * m], wy0 = win[4 * m + 1], s = win[4 * m + 2];
     const int f = frame_of[m];
     if ((unsigned)f >= (unsigned)F || !paste_window_ok(wx0, wy0, s, win[4 * m + 3], S, Hf, Wf) || y >= s) continue;
     const int py = wy0 + y;
-    uint8_t* const row = frames + (((long)f * Hf + py) * Wf + wx0) * 3;
+    uint8_t* const row = RAGGED ? frames + (long)py * pitch + 3l * wx0 : frames + (((long)f * Hf + py) * Wf + wx0) * 3;
     const int head = (int)(reinterpret_cast<uintptr_t>(row) & 3);
     const int xa = head + 4 * ((int)q - 1);
     if (xa >= s) continue;
@@ -1106,15 +1186,22 @@ __device__ __forceinline__ bool chroma_touched(int x0, int y0, int s, int cy, in
 // the sample's four luma pixels).  A sample belongs to the LAST valid face of its frame that touches it; its item starts from
 // the frame's bytes and applies every touching face lo .. m in list order with paste_windows_nv12_kernel's arithmetic, every
 // value rounded to a byte after each face.  A luma byte no window holds is neither read nor written.
+// RAGGED (emo_paste_faces_ragged_nv12): as in paste_faces_kernel -- one face per blockIdx.y, its frame from the frame table
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void paste_faces_nv12_kernel(const float* __restrict__ img, const float* __restrict__ matte,
                                                                const int* __restrict__ win, const int* __restrict__ frame_of,
                                                                uint8_t* __restrict__ yp, uint8_t* __restrict__ uvp, long pitch,
                                                                long fstride, unsigned total, int M, int F, int S, int Hf, int Wf,
-                                                               unsigned cmax, float feather, Nv12Coef k) {
+                                                               unsigned cmax, float feather, Nv12Coef k,
+                                                               const long long* __restrict__ ftab) {
   const long SS = (long)S * S;
+  if constexpr (RAGGED) {
+    const FrameRow fr = frame_row(ftab, frame_of, F);
+    yp = fr.base; uvp = fr.base + fr.H * fr.pitch; pitch = fr.pitch; fstride = 0; Hf = fr.H; Wf = fr.W;
+  }
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     const unsigned rr = i / cmax;
-    const int m = (int)(rr / cmax);
+    const int m = RAGGED ? (int)blockIdx.y : (int)(rr / cmax);
     const int wx0 = win[4 * m], wy0 = win[4 * m + 1], s = win[4 * m + 2];
     const int f = frame_of[m];
     if ((unsigned)f >= (unsigned)F || !paste_window_ok(wx0, wy0, s, win[4 * m + 3], S, Hf, Wf)) continue;
@@ -1205,6 +1292,40 @@ inline int paste_faces_windows(const int32_t* windows_host, int M, int S, int Hf
   return EMO_OK;
 }
 
+// ABI 19.  What the four ragged entry points check on the host copy of the frame table and the lists, before a launch: every
+// row an address, a size that fits an int (NV12: even) and a pitch of at least a row's bytes; frame_of as above; a host-side
+// window inside ITS OWN frame (paste: a square with 4 s >= S).  -> EMO_OK and, for the paste, the largest side to cover.
+inline int ragged_args(const int64_t* table_host, int F, int px_bytes, bool nv12, const int32_t* windows_host,
+                       const int32_t* frame_of_host, int M, int S, bool paste, int& smax) {
+  smax = 0;
+  for (int f = 0; f < F; ++f) {
+    const int64_t* t = table_host + 4l * f;
+    if (t[0] == 0 || t[2] <= 0 || t[3] <= 0 || t[2] > 0x7fffffffl || t[3] > 0x7fffffffl / px_bytes || t[1] < t[3] * px_bytes) return EMO_ERR_BAD_ARG;
+    if (nv12 && ((t[2] | t[3]) & 1)) return EMO_ERR_BAD_ARG;
+    const int side = (int)(t[2] < t[3] ? t[2] : t[3]);
+    smax = side > smax ? side : smax;                // windows that only the device knows: any valid side of any frame
+  }
+  if (!frame_of_ok(frame_of_host, M, F)) return EMO_ERR_BAD_ARG;
+  if (!windows_host) return EMO_OK;
+  smax = 0;
+  for (int m = 0; m < M; ++m) {
+    const int32_t* w = windows_host + 4 * m;
+    const int64_t* t = table_host + 4l * frame_of_host[m];
+    if (!nv12_window_ok(w[0], w[1], w[2], w[3], (int)t[2], (int)t[3])) return EMO_ERR_BAD_ARG;
+    if (paste && !paste_window_ok(w[0], w[1], w[2], w[3], S, (int)t[2], (int)t[3])) return EMO_ERR_UNSUPPORTED;
+    smax = w[2] > smax ? w[2] : smax;
+  }
+  return EMO_OK;
+}
+
+// grid (x, M): one face per blockIdx.y, x covering `per` items of a face, about 8192 blocks in all as grid_for
+inline dim3 ragged_grid(long per, int M) {
+  const long cap = 8192 / M < 1 ? 1 : 8192 / M;
+  long g = (per + 255) / 256;
+  g = g < 1 ? 1 : (g > cap ? cap : g);
+  return dim3((unsigned)g, (unsigned)M);
+}
+
 }  // namespace
 
 extern "C" int emo_resize2d_faces_f32(const float* x, int64_t plane_stride, int64_t row_stride, const int32_t* windows,
@@ -1232,8 +1353,8 @@ extern "C" int emo_nv12_faces_f32(const uint8_t* y, const uint8_t* uv, int64_t p
       if (!nv12_window_ok(w[0], w[1], w[2], w[3], Hf, Wf)) return EMO_ERR_BAD_ARG;
     }
   if (M == 0) return EMO_OK;
-  hipLaunchKernelGGL(nv12_faces_kernel, dim3(grid_for((long)M * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, y, uv, (long)pitch,
-                     (long)frame_stride, Hf, Wf, windows, frame_of, out, (long)M, F, Ho, Wo, k);
+  hipLaunchKernelGGL(nv12_faces_kernel<false>, dim3(grid_for((long)M * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, y, uv, (long)pitch,
+                     (long)frame_stride, Hf, Wf, windows, frame_of, out, (long)M, F, Ho, Wo, k, (const long long*)nullptr);
   return emo_launch_status();
 }
 
@@ -1247,8 +1368,8 @@ extern "C" int emo_paste_faces_rgb8(const float* img, const float* matte, const 
   if (rc != EMO_OK || M == 0) return rc;
   const long total = (long)M * smax * ((smax + 3) / 4 + 1);
   if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(paste_faces_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
-                     frames, (unsigned)total, M, F, S, Hf, Wf, (unsigned)smax, feather);
+  hipLaunchKernelGGL(paste_faces_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
+                     frames, (unsigned)total, M, F, S, Hf, Wf, (unsigned)smax, feather, (const long long*)nullptr);
   return emo_launch_status();
 }
 
@@ -1266,7 +1387,72 @@ extern "C" int emo_paste_faces_nv12(const float* img, const float* matte, const 
   const long cmax = smax / 2 + 1;                  // chroma samples under s luma pixels: at most s / 2 + 1 (an odd origin)
   const long total = (long)M * cmax * cmax;
   if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(paste_faces_nv12_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
-                     y, uv, (long)pitch, (long)frame_stride, (unsigned)total, M, F, S, Hf, Wf, (unsigned)cmax, feather, k);
+  hipLaunchKernelGGL(paste_faces_nv12_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
+                     y, uv, (long)pitch, (long)frame_stride, (unsigned)total, M, F, S, Hf, Wf, (unsigned)cmax, feather, k,
+                     (const long long*)nullptr);
+  return emo_launch_status();
+}
+
+// ---- ABI 19: the frames of a batch in different sizes, addressed through a frame table (definitions: include/emo_hip.h)
+extern "C" int emo_rgb8_faces_ragged_f32(const int64_t* table, const int64_t* table_host, const int32_t* windows,
+                                         const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host,
+                                         float* out, int M, int F, int Ho, int Wo, void* stream) {
+  if (!table || !table_host || !windows || !frame_of || !frame_of_host || !out || M < 0 || F <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = ragged_args(table_host, F, 3, false, windows_host, frame_of_host, M, 0, false, smax);
+  if (rc != EMO_OK || M == 0) return rc;
+  if (M > 65535) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(rgb8_faces_ragged_kernel, ragged_grid((long)Ho * Wo, M), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const long long*>(table), windows, frame_of, out, F, Ho, Wo);
+  return emo_launch_status();
+}
+
+extern "C" int emo_nv12_faces_ragged_f32(const int64_t* table, const int64_t* table_host, const int32_t* windows,
+                                         const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host,
+                                         float* out, int M, int F, int Ho, int Wo, int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  if (!table || !table_host || !windows || !frame_of || !frame_of_host || !out || M < 0 || F <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
+  if (!nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = ragged_args(table_host, F, 1, true, windows_host, frame_of_host, M, 0, false, smax);
+  if (rc != EMO_OK || M == 0) return rc;
+  if (M > 65535) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(nv12_faces_kernel<true>, ragged_grid((long)Ho * Wo, M), dim3(256), 0, (hipStream_t)stream,
+                     (const uint8_t*)nullptr, (const uint8_t*)nullptr, 0l, 0l, 0, 0, windows, frame_of, out, (long)M, F, Ho, Wo, k,
+                     reinterpret_cast<const long long*>(table));
+  return emo_launch_status();
+}
+
+extern "C" int emo_paste_faces_ragged_rgb8(const float* img, const float* matte, const int64_t* table, const int64_t* table_host,
+                                           const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
+                                           const int32_t* frame_of_host, int M, int F, int S, float feather, void* stream) {
+  if (!img || !table || !table_host || !windows || !frame_of || !frame_of_host || M < 0 || F <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
+  if (!(feather >= 0.0f && feather <= 0.5f)) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = ragged_args(table_host, F, 3, false, windows_host, frame_of_host, M, S, true, smax);
+  if (rc != EMO_OK || M == 0) return rc;
+  const long per = (long)smax * ((smax + 3) / 4 + 1);
+  if (M > 65535 || per > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(paste_faces_kernel<true>, ragged_grid(per, M), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
+                     (uint8_t*)nullptr, (unsigned)per, M, F, S, 0, 0, (unsigned)smax, feather, reinterpret_cast<const long long*>(table));
+  return emo_launch_status();
+}
+
+extern "C" int emo_paste_faces_ragged_nv12(const float* img, const float* matte, const int64_t* table, const int64_t* table_host,
+                                           const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
+                                           const int32_t* frame_of_host, int M, int F, int S, float feather, int matrix,
+                                           int full_range, void* stream) {
+  Nv12Coef k;
+  if (!img || !table || !table_host || !windows || !frame_of || !frame_of_host || M < 0 || F <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
+  if (!(feather >= 0.0f && feather <= 0.5f) || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = ragged_args(table_host, F, 1, true, windows_host, frame_of_host, M, S, true, smax);
+  if (rc != EMO_OK || M == 0) return rc;
+  const long cmax = smax / 2 + 1;                  // chroma samples under s luma pixels: at most s / 2 + 1 (an odd origin)
+  const long per = cmax * cmax;
+  if (M > 65535 || per > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(paste_faces_nv12_kernel<true>, ragged_grid(per, M), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
+                     (uint8_t*)nullptr, (uint8_t*)nullptr, 0l, 0l, (unsigned)per, M, F, S, 0, 0, (unsigned)cmax, feather, k,
+                     reinterpret_cast<const long long*>(table));
   return emo_launch_status();
 }

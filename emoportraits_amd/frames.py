@@ -1,5 +1,7 @@
 """The frame plumbing of InferenceWrapper.animate_frames / enrol_identities that touches no wrapper state: crop windows, uint8
 frames -> fp32 crops, the upload-ahead of a host chunk and the pinned ring that takes finished batches back to the host."""
+import itertools
+
 import torch
 
 from . import ops
@@ -148,3 +150,108 @@ class HostRing:
         out.record_stream(self.stream)
         self.pending.append((b0, slot, out.shape[0], ev))
         yield from self.drain(self.ring - 1)
+
+
+# ---- video streams of different frame sizes in one batch (InferenceWrapper.animate_streams) ------------------------------------
+ARENA_ALIGN = 256
+
+
+def interleave(lengths):
+    """The frame order of several streams served together: tick t takes frame t of every stream that still has one, in stream
+    order -> [(stream, frame index in the stream)]"""
+    return [(s, t) for t in range(max(lengths, default=0)) for s, n in enumerate(lengths) if t < n]
+
+
+def check_frame(frame, frame_format):
+    """one frame of a mixed batch: uint8 [H,W,3], or NV12 uint8 [3H/2, W] with H and W even"""
+    check_frames(frame[None], frame_format)
+
+
+def arena_layout(shapes):
+    """byte offsets of the frames of a batch in one byte buffer, each at a multiple of ARENA_ALIGN -> (offsets, total bytes)"""
+    offsets, total = [], 0
+    for shape in shapes:
+        offsets.append(total)
+        n = 1
+        for d in shape:
+            n *= d
+        total += -(-n // ARENA_ALIGN) * ARENA_ALIGN
+    return offsets, total
+
+
+def arena_views(buf, shapes, offsets):
+    """the frames of a batch as views of its byte buffer (device arena or pinned ring slot)"""
+    out = []
+    for shape, off in zip(shapes, offsets):
+        n = 1
+        for d in shape:
+            n *= d
+        out.append(buf[off:off + n].view(tuple(shape)))
+    return out
+
+
+def _row_unit(frame):
+    """a device frame the mixed ops take where it lies: stride 1 along a row (a row-pitch view included); else a packed copy"""
+    unit = frame.stride(-1) == 1 and (frame.dim() == 2 or frame.stride(1) == 3)
+    return frame if unit else frame.contiguous()
+
+
+def uploaded_mixed(batches, device, upload_stream, copy_all):
+    """(frames, arena) for every batch of `batches` (each a list of frame tensors of any sizes, host or device) -- frames the
+    batch's frames on the device, arena the byte buffer that holds those of them that were copied (None: none was) -- with the
+    upload of batch i + 1 enqueued on the copy stream BEFORE batch i is handed out, as `uploaded` does for uniform chunks.
+    Every host frame goes into its place in the arena (offsets a multiple of ARENA_ALIGN) with its own asynchronous copy:
+    no host-side staging copy of frame bytes.  A device frame is used where it lies, or, with copy_all (the batch is pasted
+    into and the caller's frames stay untouched), copied into the arena too, on the compute stream when the batch is handed
+    out.  frames[i] is then a view of the arena."""
+    ahead = None
+    for batch in itertools.chain(batches, [None]):                               # (lazily: a stream's chunks are read as they are due)
+        nxt = None
+        if batch is not None:
+            inside = [copy_all or not f.is_cuda for f in batch]
+            shapes = [tuple(f.shape) for f, a in zip(batch, inside) if a]
+            offsets, total = arena_layout(shapes)
+            arena, ev, views = None, None, []
+            if total:
+                with torch.cuda.stream(upload_stream):
+                    arena = torch.empty(total, dtype=torch.uint8, device=device)
+                    views = arena_views(arena, shapes, offsets)
+                    for f, v in zip([f for f, a in zip(batch, inside) if a], views):
+                        if not f.is_cuda:
+                            v.copy_(f, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(upload_stream)
+            nxt = (batch, inside, views, arena, ev)
+        if ahead is not None:
+            batch0, inside0, views0, arena0, ev0 = ahead
+            if ev0 is not None:
+                torch.cuda.current_stream().wait_event(ev0)
+                arena0.record_stream(torch.cuda.current_stream())
+            frames, k = [], 0
+            for f, a in zip(batch0, inside0):
+                if a:
+                    if f.is_cuda:
+                        views0[k].copy_(f)
+                    frames.append(views0[k])
+                    k += 1
+                else:
+                    frames.append(_row_unit(f))
+            yield frames, arena0
+        ahead = nxt
+
+
+class ArenaRing(HostRing):
+    """HostRing for the arenas of mixed batches: a finished batch goes to the host as ONE copy of its arena into a pinned slot.
+    The slots are byte buffers; when a batch needs more than they hold, the ring is drained and re-made at that size."""
+
+    def __init__(self, device, ring):
+        super().__init__(device, ring, 0)
+
+    def push(self, tag, arena):
+        if self.slots and self.slots[0].numel() < arena.numel():
+            yield from self.drain()
+            self.slots.clear()
+            self.k = 0
+        if not self.slots:
+            self.batch_size = max(self.batch_size, arena.numel())               # (the slots' size in bytes)
+        yield from super().push(tag, arena)

@@ -79,6 +79,10 @@ SIGNATURES = {
     "emo_nv12_faces_f32": [_c_void, _c_void, _c_i64, _c_i64, _c_int, _c_int] + [_c_void] * 5 + [_c_int] * 6 + [_c_void],
     "emo_paste_faces_rgb8": [_c_void] * 7 + [_c_int] * 5 + [_c_float, _c_void],
     "emo_paste_faces_nv12": [_c_void] * 8 + [_c_i64, _c_i64] + [_c_int] * 5 + [_c_float, _c_int, _c_int, _c_void],
+    "emo_rgb8_faces_ragged_f32": [_c_void] * 7 + [_c_int] * 4 + [_c_void],
+    "emo_nv12_faces_ragged_f32": [_c_void] * 7 + [_c_int] * 6 + [_c_void],
+    "emo_paste_faces_ragged_rgb8": [_c_void] * 8 + [_c_int] * 3 + [_c_float, _c_void],
+    "emo_paste_faces_ragged_nv12": [_c_void] * 8 + [_c_int] * 3 + [_c_float, _c_int, _c_int, _c_void],
 }
 _RESTYPES = {"emo_build_info": ctypes.c_char_p, "emo_groupnorm_workspace_bytes": _c_i64}
 

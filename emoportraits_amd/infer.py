@@ -1294,6 +1294,167 @@ class InferenceWrapper:
         if host_ring is not None:
             yield from host_ring.drain()
 
+    def animate_streams(self, streams, batch_size=16, ring=3, to_host=True, smooth_pose=False, mix=False, mix_old=True,
+                        target_theta=True, paste_back=False, feather=0.0625, paste_matte=None, as_uint8=True, refine=False,
+                        refine_masks=None, frame_format="rgb8", out_format=None, colorspace="bt709", full_range=False):
+        """Several video streams of DIFFERENT frame sizes served by one driver batch: animate_frames(faces=) with the frames of a
+        batch a list instead of one tensor.  Between the crop and the paste everything is one row per face, so only the two ends
+        differ: ONE crop launch reads every face of the batch out of its own frame through a frame table
+        (ops.crop_faces_mixed: emo_rgb8_faces_ragged_f32 reads the bytes under the windows only, no full-frame fp32 picture;
+        emo_nv12_faces_ragged_f32), then the steps animate_frames runs (_head_pose, _pose_controls, _expression, _render), and
+        with paste_back=True ONE paste launch (ops.paste_faces_mixed).
+        streams: a list of mappings, one per stream --
+            'frames': uint8 [N_s,H_s,W_s,3] (NV12: [N_s,3H_s/2,W_s]) or an iterable of such chunks, host (ideally pinned) or device;
+            'windows': one (x_lo, y_lo, side) per frame, or 'faces': a list of them per frame in paste order ([]: no face); their
+                length is the stream's number of frames;
+            'identities' (optional, then in every stream): one bank slot for the stream, or one per face of the stream.
+        Order: tick t takes frame t of every stream that still has one, in stream order (frames.interleave).  A batch is a run
+        of whole frames of that sequence, taken greedily while it holds at most batch_size faces and at most batch_size frames
+        (frames.face_spans; a frame with more faces: ValueError before anything is launched).
+        The frames of a batch live in one device byte buffer, each at a 256-byte aligned offset, every host frame uploaded by
+        its own asynchronous copy, batch i + 1 before batch i's kernels (frames.uploaded_mixed).  Device frames are read where
+        they lie and copied into the arena only to be pasted into: the caller's frames stay untouched.
+        smooth_pose needs identities (ValueError otherwise): every face track is its slot's stream (animate_frames'
+        smooth_per_identity), scanned batch by batch in one pass -- the slots' states are carried on the device.
+        The other keywords and their checks are animate_frames'; there is one frame_format per call.
+        Yields, per batch, a list of (stream, frame index in the stream, out): with paste_back the pasted frame [H_s,W_s,3]
+        (NV12 [3H_s/2,W_s]) -- with to_host a view of a pinned ring slot that received the whole arena in ONE copy
+        (frames.ArenaRing), a frame without a face as it went in; otherwise that frame's crops [faces,S,S,3] (out_format 'nv12':
+        [faces,3S/2,S]; as_uint8=False: fp32 [faces,3,S,S]), frames without a face left out.  Everything yielded is valid until
+        the generator is resumed.
+        The call is rank-local: no collective, no sharding -- each rank serves its own streams."""
+        frames_mod.check_format(frame_format, colorspace)
+        if out_format is not None:
+            frames_mod.check_format(out_format, colorspace, "out_format")
+            if not as_uint8:
+                raise ValueError("as_uint8=False yields the fp32 device image: it has no out_format")
+        out_format = out_format or frame_format
+        if paste_back and out_format != frame_format:
+            raise ValueError(f"paste_back=True returns the uploaded {frame_format} frames: out_format={out_format!r} is not possible")
+        if not as_uint8 and (to_host or paste_back):
+            raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
+        faces, idents = [], []
+        for k, st in enumerate(streams):
+            if ('windows' in st) == ('faces' in st):
+                raise ValueError(f"stream {k} takes either 'windows' (one per frame) or 'faces' (a list per frame)")
+            of_stream = [[w] for w in st['windows']] if 'windows' in st else list(st['faces'])
+            flat, counts = frames_mod.flatten_faces(of_stream)
+            if isinstance(st['frames'], torch.Tensor):
+                frames_mod.check_frames(st['frames'], frame_format)
+                if st['frames'].shape[0] != len(counts):
+                    raise ValueError(f"stream {k} has {len(counts)} entries of windows / faces for {st['frames'].shape[0]} frames")
+            faces.append((flat, counts))
+            ids = st.get('identities')
+            if ids is not None:
+                ids = [int(v) for v in ids] if hasattr(ids, '__len__') else [int(ids)] * len(flat)
+                if len(ids) != len(flat):
+                    raise ValueError(f"stream {k}: identities has {len(ids)} entries for {len(flat)} faces: one slot, or one per face")
+            idents.append(ids)
+        if any(i is None for i in idents) and not all(i is None for i in idents):
+            raise ValueError("'identities' must be given in every stream or in none")
+        if smooth_pose and (not idents or idents[0] is None):
+            raise ValueError("smooth_pose=True smooths every face track as its identity's stream: give every stream 'identities'")
+        order = frames_mod.interleave([len(counts) for _, counts in faces])
+        first = [[0] for _ in faces]                                             # first[s][t] = faces of stream s in front of its frame t
+        for f, (_, counts) in zip(first, faces):
+            for c in counts:
+                f.append(f[-1] + c)
+        counts = [faces[s][1][t] for s, t in order]
+        spans = frames_mod.face_spans(counts, 0, len(order), batch_size)
+        wins = [w for s, t in order for w in faces[s][0][first[s][t]:first[s][t + 1]]]
+        identities = None if not idents or idents[0] is None else [i for s, t in order for i in idents[s][first[s][t]:first[s][t + 1]]]
+        masks_of, ids = self._preflight(len(wins), identities, mix, target_theta, smooth_pose, True, refine, refine_masks)
+        matte_fn = None
+        if paste_back:
+            if not 0.0 <= float(feather) <= 0.5:
+                raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
+            matte_fn = self._paste_matte(paste_matte, 'paste_matte=True')
+            S_out = self.cfg["image_size"] if masks_of is None else self._stage2.cfg["output_size_s2"]
+            if any(4 * w[2] < S_out for w in wins):
+                raise ValueError(f"a paste window is smaller than a quarter of the {S_out}-pixel image: downscaling "
+                                 f"stops at image_size / 4")
+        if out_format == "nv12" and as_uint8 and not paste_back:
+            self._nv12_size(masks_of)
+        S = self.cfg["image_size"]
+        out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
+        fmt = (frame_format, colorspace, bool(full_range))
+        host_ring = None if not to_host else (frames_mod.ArenaRing(self.device, ring) if paste_back
+                                              else frames_mod.HostRing(self.device, ring, batch_size))
+        upload_stream = torch.cuda.Stream(device=self.device)
+        ids_dev = None if ids is None else ids.to(self.device)
+        rows = [0]                                                               # rows[i] = faces in front of frame i of the order
+        for c in counts:
+            rows.append(rows[-1] + c)
+        todo = [sp for sp in spans if paste_back or rows[sp[0]] < rows[sp[1]]]   # (crops: a batch without a face is not uploaded)
+
+        def frames_of(k, st):
+            """the frames of stream k one by one, chunk after chunk"""
+            n = 0
+            for chunk in [st['frames']] if isinstance(st['frames'], torch.Tensor) else st['frames']:
+                frames_mod.check_frames(chunk, frame_format)
+                for i in range(chunk.shape[0]):
+                    if n == len(faces[k][1]):
+                        raise ValueError(f"stream {k}: its windows / faces have {n} entries, the frames run past it")
+                    n += 1
+                    yield chunk[i]
+        readers = [frames_of(k, st) for k, st in enumerate(streams)]
+
+        def batches():
+            at = 0
+            for b0, b1 in spans:                                                 # (every frame is taken from its stream, in order)
+                batch = []
+                for s, t in order[b0:b1]:
+                    frame = next(readers[s], None)
+                    if frame is None:
+                        raise ValueError(f"stream {s} has {t} frames, its windows / faces have {len(faces[s][1])} entries")
+                    batch.append(frame)
+                if at < len(todo) and todo[at] == (b0, b1):
+                    at += 1
+                    yield batch
+
+        def handed_out(meta, buf):
+            """a finished batch -> [(stream, frame index, out)]: the frames of an arena (or of the ring slot that received it),
+            or the rows of the crops split by frame"""
+            if paste_back:
+                shapes = [shape for _, _, shape in meta]
+                views = frames_mod.arena_views(buf, shapes, frames_mod.arena_layout(shapes)[0])
+                return [(s, t, v) for (s, t, _), v in zip(meta, views)]
+            out, m = [], 0
+            for s, t, c in meta:
+                if c:
+                    out.append((s, t, buf[m:m + c]))
+                m += c
+            return out
+
+        fresh = frames_mod.uploaded_mixed(batches(), self.device, upload_stream, paste_back)
+        for b0, b1 in todo:
+            m0, m1 = rows[b0], rows[b1]
+            frames, arena = next(fresh)
+            frame_of = [i - b0 for i in range(b0, b1) for _ in range(counts[i])]
+            out = None
+            if m1 > m0:
+                crops = ops.crop_faces_mixed(frames, S, wins[m0:m1], frame_of, *fmt)
+                ident = None if ids is None else ids_dev[m0:m1]
+                theta = self._pose_controls(self._head_pose(crops)[0], ident, mix, mix_old, smooth_pose)
+                self.pred_target_theta = theta
+                pose, _ = self._expression(crops, theta, 'a driver call')
+                out = self._render(pose, theta, ident, target_theta, masks_of, out_kind, fmt[1:])
+                if paste_back:
+                    m = None if matte_fn is None else matte_fn(out).float().contiguous()
+                    ops.paste_faces_mixed(frames, out, wins[m0:m1], frame_of, feather, m, *fmt)
+            if paste_back:
+                meta, out = [(s, t, tuple(f.shape)) for (s, t), f in zip(order[b0:b1], frames)], arena
+            else:
+                meta = [(s, t, counts[i]) for i, (s, t) in zip(range(b0, b1), order[b0:b1])]
+            if host_ring is not None:
+                for tag, buf in host_ring.push(meta, out):
+                    yield handed_out(tag, buf)
+            else:
+                yield handed_out(meta, out)
+        if host_ring is not None:
+            for tag, buf in host_ring.drain():
+                yield handed_out(tag, buf)
+
     def share_source(self, src_rank=0):
         """RCCL broadcast of the per-identity cache computed on `src_rank`: canonical volume
         (25 MB) + idt_embed (32 KB) + source theta."""

@@ -948,6 +948,140 @@ def paste_windows_nv12(nv12, img, windows, feather=0.0, matte=None, colorspace="
     return nv12
 
 
+def _mixed_rows(frames, frame_format, what):
+    """frames: a list of tensors, one per frame, uint8 [H,W,3] (rgb8) or NV12 [3H/2,W], all on one device, stride 1 along a row
+    (a row-pitch view is taken as it is) -> [(address, pitch in bytes, H, W)] of the CHECKED tensors"""
+    if frame_format not in ("rgb8", "nv12"):
+        raise ValueError(f"frame_format={frame_format!r}: 'rgb8' or 'nv12'")
+    if not isinstance(frames, (list, tuple)) or not frames:
+        raise ValueError(f"{what} takes a non-empty list of frame tensors, one per frame")
+    rows = []
+    for i, t in enumerate(frames):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device != frames[0].device:
+            raise RuntimeError(f"{what}: frame {i} must be a uint8 tensor on the device of frame 0")
+        if frame_format == "rgb8":
+            if t.dim() != 3 or t.shape[2] != 3 or 0 in t.shape:
+                raise ValueError(f"{what}: frame {i} is {tuple(t.shape)}, expected uint8 [H,W,3]")
+            (H, W), row_bytes, unit = t.shape[:2], 3 * t.shape[1], (t.stride(2) == 1 and t.stride(1) == 3)
+        else:
+            if t.dim() != 2 or t.shape[0] % 3 or t.shape[1] % 2 or 0 in t.shape:
+                raise ValueError(f"{what}: frame {i} is {tuple(t.shape)}, expected NV12 uint8 [3H/2, W] with H and W even")
+            H, W, row_bytes, unit = t.shape[0] // 3 * 2, t.shape[1], t.shape[1], t.stride(1) == 1
+        if not unit or t.stride(0) < row_bytes:
+            raise RuntimeError(f"{what}: frame {i} needs stride 1 along a row and a row pitch of at least the row's {row_bytes} bytes")
+        rows.append((t.data_ptr(), t.stride(0), H, W))
+    return rows
+
+
+def frame_table(frames, frame_format="rgb8"):
+    """The frame table of the mixed-size entry points (ABI 19) for a list of frame tensors, one per frame, each uint8 [H_i,W_i,3]
+    or NV12 [3H_i/2,W_i] on the device: int64 [F,4] rows (byte address of the first row, row pitch in bytes, H, W) ->
+    (device tensor, host tensor).  The rows are raw device addresses, so they are only ever formed here, from tensors whose
+    device, dtype, dimensions, row stride and pitch have been checked; the caller keeps the tensors alive while the table is
+    in use.  crop_faces_mixed / paste_faces_mixed build their own: no op takes a ready-made table."""
+    host = torch.tensor(_mixed_rows(frames, frame_format, "frame_table"), dtype=torch.int64).reshape(-1, 4)
+    return host.to(frames[0].device, non_blocking=True), host
+
+
+def _mixed_windows(windows, frame_of, table_host, device, S, what):
+    """the windows of M faces and their frames -> (windows device, windows host or None, frame_of device, frame_of host).  A host
+    sequence of windows is checked against each face's OWN frame (ValueError): inside it and, for a paste into an S x S image
+    (S not None), square with a side of at least S / 4 -- the checks of paste_windows"""
+    F = table_host.shape[0]
+    fof, fof_host = _frame_of_arg(frame_of, F, device)
+    M = fof_host.numel()
+    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+        if windows.device != device or windows.dtype != torch.int32 or tuple(windows.shape) != (M, 4) or not windows.is_contiguous():
+            raise RuntimeError("windows must be a contiguous int32 tensor [M,4] on the frames' device")
+        return windows, None, fof, fof_host
+    host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
+    if host.shape[0] != M:
+        raise ValueError(f"{host.shape[0]} windows for {M} faces")
+    size = table_host[fof_host.long()][:, [3, 2]]                                # (W, H) of each face's own frame
+    lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
+    if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi <= size).all())):
+        raise ValueError(f"a {what} window is not inside its own frame")
+    if S is not None:
+        if not bool((host[:, 2] == host[:, 3]).all()):
+            raise ValueError("paste windows must be square")
+        if not bool((4 * host[:, 2] >= S).all()):
+            raise ValueError(f"a paste window is smaller than a quarter of the {S}x{S} image: downscaling stops at S / 4")
+    return host.to(device, non_blocking=True), host, fof, fof_host
+
+
+def crop_faces_mixed(frames, size, windows, frame_of, frame_format="rgb8", colorspace="bt709", full_range=False):
+    """The crops of M faces out of frames of DIFFERENT sizes in ONE launch (emo_rgb8_faces_ragged_f32 /
+    emo_nv12_faces_ragged_f32): frames a list of device tensors, one per frame, uint8 [H_i,W_i,3] or NV12 [3H_i/2,W_i] (row-pitch
+    views are taken as they are); windows[m] = (x0, y0, w, h) is cut out of frames[frame_of[m]] (frame_of a host sequence,
+    non-decreasing), resized bicubically to size (an int or (Ho, Wo)) and clamped -> fp32 [M,3,Ho,Wo].  rgb8: bit for bit
+    unpack_rgb8 + resize2d_windows(..., 'bicubic', clamp01=True, frame_of=) of each frame, but only the bytes under the windows
+    are read: no full-frame fp32 picture.  nv12: nv12_windows(frame_of=)'s arithmetic.  windows: a host sequence (checked
+    against each face's own frame, ValueError) or an int32 [M,4] device tensor (a window that leaves its frame gives zeros).
+    The frame table is built here from the checked tensors (frame_table)."""
+    lib = hip.load()
+    rows = _mixed_rows(frames, frame_format, "crop_faces_mixed")
+    matrix = _nv12_matrix(colorspace)
+    device = frames[0].device
+    table_host = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
+    win, host, fof, fof_host = _mixed_windows(windows, frame_of, table_host, device, None, "crop")
+    Ho, Wo = (size, size) if isinstance(size, int) else size
+    M, F = fof_host.numel(), len(rows)
+    out = torch.empty((M, 3, Ho, Wo), device=device, dtype=torch.float32)
+    hip.require_cuda_f32(out)                                    # (the frames' device: GPU only, like every op)
+    if M == 0:
+        return out
+    table = table_host.to(device, non_blocking=True)
+    if frame_format == "nv12":
+        hip.check(lib.emo_nv12_faces_ragged_f32(hip.ptr(table), hip.ptr(table_host), hip.ptr(win), hip.ptr(host), hip.ptr(fof),
+                                                hip.ptr(fof_host), hip.ptr(out), M, F, Ho, Wo, matrix, int(bool(full_range)),
+                                                hip.current_stream()), "emo_nv12_faces_ragged_f32")
+    else:
+        hip.check(lib.emo_rgb8_faces_ragged_f32(hip.ptr(table), hip.ptr(table_host), hip.ptr(win), hip.ptr(host), hip.ptr(fof),
+                                                hip.ptr(fof_host), hip.ptr(out), M, F, Ho, Wo, hip.current_stream()),
+                  "emo_rgb8_faces_ragged_f32")
+    return out
+
+
+def paste_faces_mixed(frames, img, windows, frame_of, feather=0.0, matte=None, frame_format="rgb8", colorspace="bt709",
+                      full_range=False):
+    """paste_windows(frame_of=) / paste_windows_nv12(frame_of=) into frames of DIFFERENT sizes, IN PLACE and in ONE launch
+    (emo_paste_faces_ragged_rgb8 / emo_paste_faces_ragged_nv12): frames as in crop_faces_mixed, img [M,3,S,S] fp32, matte
+    [M,1,S,S] or None; face m goes into frames[frame_of[m]] where its square window is, the faces of a frame in list order, the
+    later one on top.  windows: a host sequence, checked against each face's OWN frame before anything is launched (inside it,
+    square, side >= S / 4: ValueError), or an int32 [M,4] device tensor (a window that fails those checks against its frame is
+    left out by the kernel).  Bytes outside the windows are neither read nor written.  Returns frames."""
+    lib = hip.load()
+    hip.require_cuda_f32(img, matte)
+    rows = _mixed_rows(frames, frame_format, "paste_faces_mixed")
+    matrix = _nv12_matrix(colorspace)
+    device = frames[0].device
+    if device != img.device:
+        raise RuntimeError("paste_faces_mixed expects the frames on the images' device")
+    if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
+        raise ValueError(f"images {tuple(img.shape)}: expected [M,3,S,S]")
+    M, S, F = img.shape[0], img.shape[2], len(rows)
+    if matte is not None and tuple(matte.shape) != (M, 1, S, S):
+        raise ValueError(f"matte {tuple(matte.shape)}: expected {(M, 1, S, S)}")
+    if not 0.0 <= float(feather) <= 0.5:
+        raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
+    table_host = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
+    win, host, fof, fof_host = _mixed_windows(windows, frame_of, table_host, device, S, "paste")
+    if fof_host.numel() != M:
+        raise ValueError(f"{fof_host.numel()} entries of frame_of for {M} images")
+    if M == 0:
+        return frames
+    table = table_host.to(device, non_blocking=True)
+    if frame_format == "nv12":
+        hip.check(lib.emo_paste_faces_ragged_nv12(hip.ptr(img), hip.ptr(matte), hip.ptr(table), hip.ptr(table_host), hip.ptr(win),
+                                                  hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host), M, F, S, float(feather), matrix,
+                                                  int(bool(full_range)), hip.current_stream()), "emo_paste_faces_ragged_nv12")
+    else:
+        hip.check(lib.emo_paste_faces_ragged_rgb8(hip.ptr(img), hip.ptr(matte), hip.ptr(table), hip.ptr(table_host), hip.ptr(win),
+                                                  hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host), M, F, S, float(feather),
+                                                  hip.current_stream()), "emo_paste_faces_ragged_rgb8")
+    return frames
+
+
 def device_cu_count():
     """compute units of the current device as the C launchers count them (include/emo_hip.h, ABI 9)"""
     return hip.load().emo_device_cu_count()

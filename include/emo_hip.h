@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 18
+#define EMO_ABI_VERSION 19
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -576,6 +576,46 @@ int emo_paste_faces_nv12(const float* img, const float* matte, const int32_t* wi
                          const int32_t* frame_of, const int32_t* frame_of_host, uint8_t* y, uint8_t* uv, int64_t pitch,
                          int64_t frame_stride, int M, int F, int S, int Hf, int Wf, float feather, int matrix, int full_range,
                          void* stream);
+
+/* ABI 19.  The frames of a batch in DIFFERENT sizes (several video streams served by one batch): the four ABI 18 entry points
+ * with the frames addressed through a frame table instead of (base, frame stride, Hf, Wf).
+ *   table int64 [F,4], DEVICE memory, one row per frame: (byte address of the frame's first row, row pitch in bytes, H, W).
+ *   rgb8: rows of W pixels of 3 bytes, pitch >= 3 W.  NV12: the address is the Y plane's, H and W are even, pitch >= W, and the
+ *   UV plane starts at address + H * pitch (both planes share the pitch).  table_host: the same values in HOST memory.  Any
+ *   address and any pitch are taken: nothing is assumed about their alignment.
+ *   windows, windows_host, frame_of, frame_of_host, img, matte, out, S, feather, matrix, full_range: as for ABI 18.
+ * The kernels only read the table.  A window is checked against ITS OWN frame's H and W, on the host (windows_host) and in the
+ * kernel (always), with the predicates of ABI 18.
+ * emo_rgb8_faces_ragged_f32: out[m] [3,Ho,Wo] is bit for bit emo_unpack_rgb8 (byte / 255) of frame frame_of[m] followed by
+ *   emo_resize2d_faces_f32(bicubic = 1, clamp01 = 1) of window m -- every byte under a tap is converted where it is read, with
+ *   the same arithmetic, and no full-frame fp32 picture is written.  A face whose frame_of lies outside [0, F), or whose
+ *   device-side window is not inside its frame (w, h > 0), gets zeros.
+ * emo_nv12_faces_ragged_f32: emo_nv12_faces_f32 with frame frame_of[m]'s own (address, pitch, H, W), the same arithmetic per
+ *   output and the same zeros.
+ * emo_paste_faces_ragged_rgb8, emo_paste_faces_ragged_nv12: emo_paste_faces_rgb8 / emo_paste_faces_nv12 with per-frame geometry,
+ *   in place and in ONE launch: the faces of a frame in list order, the later one on top, every byte with one writer -- the
+ *   bytes of pasting the faces one after another.  A face whose device-side window is not a square inside ITS frame with
+ *   4 * s >= S, or whose frame_of leaves [0, F), is absent: it neither owns nor changes a byte.
+ * Each result is therefore that of the ABI 18 entry point on a batch of uniform frames that holds every frame in its top-left
+ *   corner (NV12: the Y rows at the top of the Y plane, the UV rows at the top of the UV plane), whatever the rest holds.
+ * Refusals, before anything is launched and with nothing written.  EMO_ERR_BAD_ARG: a null pointer (matte and windows_host
+ *   may be NULL; table_host and frame_of_host may not), M < 0, F <= 0, a table row with a null address, H or W <= 0 (NV12: or
+ *   odd) or a pitch shorter than a row, a frame_of_host that decreases or leaves [0, F), a host-side window that leaves its
+ *   frame (or has w or h <= 0), feather, matrix.  EMO_ERR_UNSUPPORTED: a host-side paste window with w != h or 4 * s < S;
+ *   M > 65535 (one face per grid row).  M == 0 is EMO_OK and launches nothing. */
+int emo_rgb8_faces_ragged_f32(const int64_t* table, const int64_t* table_host, const int32_t* windows, const int32_t* windows_host,
+                              const int32_t* frame_of, const int32_t* frame_of_host, float* out, int M, int F, int Ho, int Wo,
+                              void* stream);
+int emo_nv12_faces_ragged_f32(const int64_t* table, const int64_t* table_host, const int32_t* windows, const int32_t* windows_host,
+                              const int32_t* frame_of, const int32_t* frame_of_host, float* out, int M, int F, int Ho, int Wo,
+                              int matrix, int full_range, void* stream);
+int emo_paste_faces_ragged_rgb8(const float* img, const float* matte, const int64_t* table, const int64_t* table_host,
+                                const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
+                                const int32_t* frame_of_host, int M, int F, int S, float feather, void* stream);
+int emo_paste_faces_ragged_nv12(const float* img, const float* matte, const int64_t* table, const int64_t* table_host,
+                                const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
+                                const int32_t* frame_of_host, int M, int F, int S, float feather, int matrix, int full_range,
+                                void* stream);
 
 #ifdef __cplusplus
 }
