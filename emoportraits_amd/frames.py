@@ -1,5 +1,6 @@
-"""The frame plumbing of InferenceWrapper.animate_frames / enrol_identities that touches no wrapper state: crop windows, uint8
-frames -> fp32 crops, the upload-ahead of a host chunk and the pinned ring that takes finished batches back to the host."""
+"""The frame plumbing of InferenceWrapper.animate_frames / animate_streams / paste_back / enrol_identities that touches no
+wrapper state: crop windows and the faces of a frame, uint8 frames -> fp32 crops (crops_of) and rendered crops -> frames
+(paste_into), the upload-ahead of a host chunk and the pinned ring that takes finished batches back to the host."""
 import itertools
 
 import torch
@@ -29,6 +30,11 @@ def flatten_faces(faces):
     return flat, counts
 
 
+def face_offsets(counts):
+    """[0, c0, c0 + c1, ...]: entry i = the faces in front of frame i"""
+    return [0] + list(itertools.accumulate(counts))
+
+
 def face_spans(counts, lo, hi, batch_size):
     """The batches of the frames [lo, hi) of a clip whose frame i has counts[i] faces: [(b0, b1), ...], whole frames taken
     greedily while a batch holds at most batch_size faces (the rows of the networks' batch) and at most batch_size frames (the
@@ -50,7 +56,7 @@ def face_spans(counts, lo, hi, batch_size):
 FORMATS = ("rgb8", "nv12")
 
 
-def check_format(frame_format, colorspace, what="frame_format"):
+def check_format(frame_format, colorspace="bt709", what="frame_format"):
     if frame_format not in FORMATS:
         raise ValueError(f"{what}={frame_format!r}: 'rgb8' or 'nv12'")
     if colorspace not in ops.NV12_MATRICES:
@@ -59,6 +65,7 @@ def check_format(frame_format, colorspace, what="frame_format"):
 
 def check_frames(chunk, frame_format):
     """the shape and dtype of one chunk of frames: uint8 [N,H,W,3], or NV12 uint8 [N, 3H/2, W] with H and W even"""
+    check_format(frame_format)
     if frame_format == "rgb8":
         if chunk.dtype != torch.uint8 or chunk.dim() != 4 or chunk.shape[-1] != 3:
             raise ValueError("frames must be uint8 [N,H,W,3]")
@@ -86,6 +93,15 @@ def crops_of(u8, size, windows=None, frame_format="rgb8", colorspace="bt709", fu
     if x.shape[-2:] != (size, size):
         return ops.resize2d(x, (size, size), "bicubic")
     return x
+
+
+def paste_into(full, img, wins, feather, matte, frame_format="rgb8", colorspace="bt709", full_range=False, frame_of=None):
+    """The inverse of crops_of, IN PLACE and in one launch: the rendered fp32 img [M,3,S,S] goes into the uint8 device frames
+    `full` ([b,H,W,3]: ops.paste_windows; 'nv12' [b,3H/2,W]: ops.paste_windows_nv12) where the windows were, blended with the
+    feathered edge and the matte; frame_of as in crops_of.  Returns full."""
+    if frame_format == "nv12":
+        return ops.paste_windows_nv12(full, img, wins, feather, matte, colorspace, full_range, frame_of=frame_of)
+    return ops.paste_windows(full, img, wins, feather, matte, frame_of=frame_of)
 
 
 def uploaded(chunk, spans, device, upload_stream):

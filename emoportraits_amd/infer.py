@@ -394,13 +394,7 @@ class InferenceWrapper:
         win_host = None
         if windows is not None:
             H, W = frames_mod.frame_size(sources, frame_format)
-            win_host = torch.tensor(frames_mod.square_windows(windows), dtype=torch.int32).reshape(-1, 4)
-            if win_host.shape[0] != K:
-                raise ValueError(f"{win_host.shape[0]} windows for {K} sources")
-            lo, side = win_host[:, :2], win_host[:, 2]
-            if not (bool((lo >= 0).all()) and bool((side > 0).all()) and bool((lo[:, 0] + side <= W).all())
-                    and bool((lo[:, 1] + side <= H).all())):
-                raise ValueError(f"a crop window is not inside the {W}x{H} frame")
+            win_host = ops.windows_host(frames_mod.square_windows(windows), K, (W, H), "crop", "sources")
         parsing = 'face_parsing' in self.embedders
         ms = None
         if source_masks is not None:
@@ -1018,11 +1012,9 @@ class InferenceWrapper:
             wins = windows if isinstance(windows, torch.Tensor) and windows.is_cuda else frames_mod.square_windows(windows)
         img = rendered.to(self.device).float().contiguous()
         m = None if fn is None else fn(img).to(self.device).float().contiguous()
-        if frame_format == "nv12":
-            return ops.paste_windows_nv12(frames_u8.to(self.device, copy=True), img, wins, feather, m, colorspace, full_range,
-                                          frame_of=frame_of)
-        full = frames_u8.to(self.device, copy=True).contiguous()
-        return ops.paste_windows(full, img, wins, feather, m, frame_of=frame_of)
+        full = frames_u8.to(self.device, copy=True)
+        return frames_mod.paste_into(full if frame_format == "nv12" else full.contiguous(), img, wins, feather, m, frame_format,
+                                     colorspace, full_range, frame_of)
 
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
                        mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
@@ -1104,18 +1096,8 @@ class InferenceWrapper:
             that order, and mix / target_theta=False work per face.  smooth_pose needs identities= and smooth_per_identity=True
             (ValueError otherwise): every face track is its slot's stream.  Ranks shard by FRAMES and take the faces of their
             frames; for smooth_pose the per-face thetas are gathered (parallel.gather_rows)."""
-        frames_mod.check_format(frame_format, colorspace)
-        if out_format is not None:
-            frames_mod.check_format(out_format, colorspace, "out_format")
-            if not as_uint8:
-                raise ValueError("as_uint8=False yields the fp32 device image: it has no out_format")
-        out_format = out_format or frame_format
-        if paste_back and out_format != frame_format:
-            raise ValueError(f"paste_back=True returns the uploaded {frame_format} frames: out_format={out_format!r} is not possible")
         if isinstance(frames, torch.Tensor):
             frames_mod.check_frames(frames, frame_format)
-        if not as_uint8 and (to_host or paste_back):
-            raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
         n_rows, counts = frames.shape[0] if isinstance(frames, torch.Tensor) else None, None
         if faces is not None:
             if windows is not None:
@@ -1133,6 +1115,29 @@ class InferenceWrapper:
                 raise ValueError(f"identities has {len(identities)} entries for {n_rows} faces: one slot per face")
         else:
             wins = None if windows is None else frames_mod.square_windows(windows)
+        plan = self._video_plan(n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
+                                target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format,
+                                out_format, colorspace, full_range)
+        yield from self._animate_clip(frames, wins, counts, plan)
+
+    def _video_plan(self, n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
+                    target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format,
+                    colorspace, full_range, arena=False):
+        """The checks of the keywords animate_frames() and animate_streams() share, before anything is launched, and what their
+        loops need beside the frames: wins = the (x0, y0, s, s) of every row of the call (None: whole frames), n_rows their
+        number where it is known.  -> masks_of, ids (_preflight), matte_fn (_paste_matte), out_kind (_render's `out`), fmt =
+        (frame_format, colorspace, full_range), ring = the pinned ring (None without to_host; with `arena` and paste_back a
+        frames.ArenaRing), upload_stream, and the loop's keywords as they came."""
+        frames_mod.check_format(frame_format, colorspace)
+        if out_format is not None:
+            frames_mod.check_format(out_format, colorspace, "out_format")
+            if not as_uint8:
+                raise ValueError("as_uint8=False yields the fp32 device image: it has no out_format")
+        out_format = out_format or frame_format
+        if paste_back and out_format != frame_format:
+            raise ValueError(f"paste_back=True returns the uploaded {frame_format} frames: out_format={out_format!r} is not possible")
+        if not as_uint8 and (to_host or paste_back):
+            raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
         masks_of, ids = self._preflight(n_rows, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
         matte_fn = None
         if paste_back:
@@ -1147,118 +1152,80 @@ class InferenceWrapper:
                                  f"stops at image_size / 4")
         if out_format == "nv12" and as_uint8 and not paste_back:
             self._nv12_size(masks_of)
-        S = self.cfg["image_size"]
         out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
-        fmt = (frame_format, colorspace, bool(full_range))
-        host_ring = frames_mod.HostRing(self.device, ring, batch_size) if to_host else None
-        upload_stream = torch.cuda.Stream(device=self.device)
-        if faces is not None:
-            yield from self._animate_faces(frames, wins, counts, ids, batch_size, host_ring, upload_stream, smooth_pose, mix, mix_old,
-                                           target_theta, paste_back, feather, matte_fn, masks_of, out_kind, fmt)
-            return
+        host_ring = None if not to_host else (frames_mod.ArenaRing(self.device, ring) if arena and paste_back
+                                              else frames_mod.HostRing(self.device, ring, batch_size))
+        return Namespace(masks_of=masks_of, ids=ids, matte_fn=matte_fn, out_kind=out_kind, fmt=(frame_format, colorspace, bool(full_range)),
+                         feather=feather, paste_back=paste_back, ring=host_ring, upload_stream=torch.cuda.Stream(device=self.device),
+                         batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta)
+
+    def _drive_crops(self, crops, ident, plan, theta=None, smooth=None):
+        """The sequence of one driver batch of the video paths, crops [m,3,S,S] -> (the rendered batch as plan.out_kind says, its
+        paste matte or None): head pose -> pose controls -> expression embedder -> render -> matte, in forward()'s order.
+        theta: the batch's thetas where a pass in front of the loop has formed them (the two-pass smooth_pose of a clip).
+        smooth: None = mix alone, and only where it is asked for (a clip); a bool = mix and the one-pass smooth_pose of the
+        batch's rows (streams)."""
+        if theta is None:
+            theta = self._head_pose(crops)[0]
+            if plan.mix or smooth is not None:
+                theta = self._pose_controls(theta, ident, plan.mix, plan.mix_old, bool(smooth))
+        self.pred_target_theta = theta                                           # (as forward() leaves it: infer.py:584)
+        pose, _ = self._expression(crops, theta, 'a driver call')
+        out = self._render(pose, theta, ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
+        return out, (None if plan.matte_fn is None else plan.matte_fn(out).float().contiguous())
+
+    def _animate_clip(self, frames, wins, counts, plan):
+        """animate_frames behind its checks.  A row of everything between the crop and the paste is a face: wins = the
+        (x0, y0, s, s) of every row of the stream in frame order, counts[i] = the faces of frame i, plan.ids = the slot of every
+        row (host tensor) or None.  counts=None is windows= / whole frames: one row per frame (wins None: the whole frame), the
+        per-frame entry points (frame_of=None) and the single-stream smooth_pose.  Per chunk the frames are sharded across the
+        ranks; a batch is a span of whole frames (frames.face_spans)."""
+        S, ids, paste_back = self.cfg["image_size"], plan.ids, plan.paste_back
+        first = None if counts is None else frames_mod.face_offsets(counts)
         base = 0
         for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
-            frames_mod.check_frames(chunk, frame_format)
+            frames_mod.check_frames(chunk, plan.fmt[0])
             n = chunk.shape[0]
-            if ids is not None and base + n > ids.shape[0]:
+            if counts is not None and base + n > len(counts):
+                raise ValueError(f"faces has {len(counts)} entries, the frames run past it")
+            if counts is None and ids is not None and base + n > ids.shape[0]:
                 raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
             lo, hi = parallel.shard_range(n, self.rank, self.world)
-            ids_dev = None if ids is None else ids[base + lo:base + hi].to(self.device)
-            ids_chunk = None if ids is None or not smooth_pose else ids[base:base + n].to(self.device)
-            spans = [(b0, min(b0 + batch_size, hi)) for b0 in range(lo, hi, batch_size)]
-            crops_of = lambda u8, b0, b1: frames_mod.crops_of(u8, S, None if wins is None else wins[base + b0:base + b1], *fmt)
-            smoothed, kept = None, {}
-            if smooth_pose:
-                keep_crops = (hi - lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
-                local = []
-                for b0, b1, u8 in frames_mod.uploaded(chunk, spans, self.device, upload_stream):
-                    crops = crops_of(u8, b0, b1)
-                    local.append(self._head_pose(crops)[0].clone())
-                    if keep_crops:
-                        kept[b0] = crops
-                local = torch.cat(local) if local else torch.empty((0, 4, 4), device=self.device)
-                if mix:
-                    local = self._pose_controls(local, ids_dev, True, mix_old, False)
-                every = parallel.gather_shards(local, n, self.rank, self.world)        # [n,4,4] on every rank, frame order
-                smoothed = self._pose_controls(every, ids_chunk, False, mix_old, True)[lo:hi]
-            # (every span whose crops stayed resident from the head-pose pass needs no second upload -- unless its frames are
-            # what the render is pasted into: the crops were kept, 3 MB per frame, not the frames, 6 MB at 1080p)
-            todo = spans if paste_back else [sp for sp in spans if sp[0] not in kept]
-            fresh = frames_mod.uploaded(chunk, todo, self.device, upload_stream)
-            for b0, b1 in spans:
-                crops = kept.pop(b0, None)
-                if crops is None or paste_back:
-                    f0, f1, u8 = next(fresh)
-                    assert (f0, f1) == (b0, b1)
-                    if crops is None:
-                        crops = crops_of(u8, b0, b1)
-                ident = None if ids is None else ids_dev[b0 - lo:b1 - lo]
-                if smoothed is not None:
-                    theta = smoothed[b0 - lo:b1 - lo]
-                else:
-                    theta = self._head_pose(crops)[0]
-                    if mix:
-                        theta = self._pose_controls(theta, ident, True, mix_old, False)
-                self.pred_target_theta = theta                                   # (as forward() leaves it: infer.py:584)
-                pose, _ = self._expression(crops, theta, 'a driver call')
-                out = self._render(pose, theta, ident, target_theta, masks_of, out_kind, fmt[1:])
-                if paste_back:
-                    full = u8.clone() if chunk.is_cuda else u8                   # (a host chunk's upload is this span's own)
-                    m = None if matte_fn is None else matte_fn(out).float().contiguous()
-                    if frame_format == "nv12":
-                        out = ops.paste_windows_nv12(full, out, wins[base + b0:base + b1], feather, m, *fmt[1:])
-                    else:
-                        out = ops.paste_windows(full, out, wins[base + b0:base + b1], feather, m)
-                if to_host:
-                    yield from host_ring.push(base + b0, out)
-                else:
-                    yield base + b0, out
-            base += n
-        if to_host:
-            yield from host_ring.drain()
-
-    def _animate_faces(self, frames, wins, counts, ids, batch_size, host_ring, upload_stream, smooth_pose, mix, mix_old,
-                       target_theta, paste_back, feather, matte_fn, masks_of, out_kind, fmt):
-        """animate_frames(faces=...) behind its checks: wins = the (x0, y0, s, s) of every face of the stream in frame order,
-        counts[i] = the faces of frame i, ids = the slot of every face (host tensor) or None.  Per chunk the frames are sharded
-        across the ranks; a batch is a span of whole frames (frames.face_spans) and the rows of everything between the crop
-        and the paste are its faces."""
-        S = self.cfg["image_size"]
-        first = [0]                                                              # first[i] = faces in front of frame i
-        for c in counts:
-            first.append(first[-1] + c)
-        base = 0
-        for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
-            frames_mod.check_frames(chunk, fmt[0])
-            n = chunk.shape[0]
-            if base + n > len(counts):
-                raise ValueError(f"faces has {len(counts)} entries, the frames run past it")
-            lo, hi = parallel.shard_range(n, self.rank, self.world)
-            spans = frames_mod.face_spans(counts[base:base + n], lo, hi, batch_size)
-            rows = lambda b0, b1: (first[base + b0], first[base + b1])           # the faces of the chunk's frames [b0, b1)
-            frame_of = lambda b0, b1: [i - b0 for i in range(b0, b1) for _ in range(counts[base + i])]
-            crops_of = lambda u8, b0, b1: frames_mod.crops_of(u8, S, wins[slice(*rows(b0, b1))], *fmt, frame_of=frame_of(b0, b1))
+            if counts is None:
+                spans = [(b0, min(b0 + plan.batch_size, hi)) for b0 in range(lo, hi, plan.batch_size)]
+                rows = lambda b0, b1: (base + b0, base + b1)                     # the rows of the chunk's frames [b0, b1)
+                frame_of = lambda b0, b1: None
+            else:
+                spans = frames_mod.face_spans(counts[base:base + n], lo, hi, plan.batch_size)
+                rows = lambda b0, b1: (first[base + b0], first[base + b1])
+                frame_of = lambda b0, b1: [i - b0 for i in range(b0, b1) for _ in range(counts[base + i])]
+            wins_of = lambda b0, b1: None if wins is None else wins[slice(*rows(b0, b1))]
+            crops_of = lambda u8, b0, b1: frames_mod.crops_of(u8, S, wins_of(b0, b1), *plan.fmt, frame_of=frame_of(b0, b1))
             with_faces = [sp for sp in spans if rows(*sp)[0] < rows(*sp)[1]]
             m_lo, m_hi = rows(lo, hi)
             ids_dev = None if ids is None else ids[m_lo:m_hi].to(self.device)
             smoothed, kept = None, {}
-            if smooth_pose:
+            if plan.smooth_pose:
+                # two passes: the head pose of the rank's rows, gathered and scanned in frame order on every rank, then the render
                 keep_crops = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
                 local = []
-                for b0, b1, u8 in frames_mod.uploaded(chunk, with_faces, self.device, upload_stream):
+                for b0, b1, u8 in frames_mod.uploaded(chunk, with_faces, self.device, plan.upload_stream):
                     crops = crops_of(u8, b0, b1)
                     local.append(self._head_pose(crops)[0].clone())
                     if keep_crops:
                         kept[b0] = crops
                 local = torch.cat(local) if local else torch.empty((0, 4, 4), device=self.device)
-                if mix:
-                    local = self._pose_controls(local, ids_dev, True, mix_old, False)
+                if plan.mix:
+                    local = self._pose_controls(local, ids_dev, True, plan.mix_old, False)
                 per_rank = [rows(*parallel.shard_range(n, r, self.world)) for r in range(self.world)]
-                every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)   # face order
-                ids_chunk = ids[slice(*rows(0, n))].to(self.device)
-                smoothed = self._pose_controls(every, ids_chunk, False, mix_old, True)[m_lo - rows(0, n)[0]:m_hi - rows(0, n)[0]]
+                every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)   # row order, on every rank
+                r0, r1 = rows(0, n)
+                ids_chunk = None if ids is None else ids[r0:r1].to(self.device)
+                smoothed = self._pose_controls(every, ids_chunk, False, plan.mix_old, True)[m_lo - r0:m_hi - r0]
+            # (every span whose crops stayed resident from the head-pose pass needs no second upload -- unless its frames are
+            # what the render is pasted into: the crops were kept, 3 MB per frame, not the frames, 6 MB at 1080p)
             todo = spans if paste_back else [sp for sp in with_faces if sp[0] not in kept]
-            fresh = frames_mod.uploaded(chunk, todo, self.device, upload_stream)
+            fresh = frames_mod.uploaded(chunk, todo, self.device, plan.upload_stream)
             for b0, b1 in spans if paste_back else with_faces:
                 m0, m1 = rows(b0, b1)
                 crops = kept.pop(b0, None)
@@ -1271,28 +1238,18 @@ class InferenceWrapper:
                     if crops is None:
                         crops = crops_of(u8, b0, b1)
                     ident = None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo]
-                    if smoothed is not None:
-                        theta = smoothed[m0 - m_lo:m1 - m_lo]
-                    else:
-                        theta = self._head_pose(crops)[0]
-                        if mix:
-                            theta = self._pose_controls(theta, ident, True, mix_old, False)
-                    self.pred_target_theta = theta
-                    pose, _ = self._expression(crops, theta, 'a driver call')
-                    out = self._render(pose, theta, ident, target_theta, masks_of, out_kind, fmt[1:])
+                    out, m = self._drive_crops(crops, ident, plan, None if smoothed is None else smoothed[m0 - m_lo:m1 - m_lo])
                     if paste_back:
                         full = u8.clone() if chunk.is_cuda else u8               # (a host chunk's upload is this span's own)
-                        m = None if matte_fn is None else matte_fn(out).float().contiguous()
-                        paste = ops.paste_windows_nv12 if fmt[0] == "nv12" else ops.paste_windows
-                        out = paste(full, out, wins[m0:m1], feather, m, *(fmt[1:] if fmt[0] == "nv12" else ()), frame_of=frame_of(b0, b1))
+                        out = frames_mod.paste_into(full, out, wins_of(b0, b1), plan.feather, m, *plan.fmt, frame_of=frame_of(b0, b1))
                 index = base + b0 if paste_back else m0
-                if host_ring is not None:
-                    yield from host_ring.push(index, out)
+                if plan.ring is not None:
+                    yield from plan.ring.push(index, out)
                 else:
                     yield index, out
             base += n
-        if host_ring is not None:
-            yield from host_ring.drain()
+        if plan.ring is not None:
+            yield from plan.ring.drain()
 
     def animate_streams(self, streams, batch_size=16, ring=3, to_host=True, smooth_pose=False, mix=False, mix_old=True,
                         target_theta=True, paste_back=False, feather=0.0625, paste_matte=None, as_uint8=True, refine=False,
@@ -1323,16 +1280,6 @@ class InferenceWrapper:
         [faces,3S/2,S]; as_uint8=False: fp32 [faces,3,S,S]), frames without a face left out.  Everything yielded is valid until
         the generator is resumed.
         The call is rank-local: no collective, no sharding -- each rank serves its own streams."""
-        frames_mod.check_format(frame_format, colorspace)
-        if out_format is not None:
-            frames_mod.check_format(out_format, colorspace, "out_format")
-            if not as_uint8:
-                raise ValueError("as_uint8=False yields the fp32 device image: it has no out_format")
-        out_format = out_format or frame_format
-        if paste_back and out_format != frame_format:
-            raise ValueError(f"paste_back=True returns the uploaded {frame_format} frames: out_format={out_format!r} is not possible")
-        if not as_uint8 and (to_host or paste_back):
-            raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
         faces, idents = [], []
         for k, st in enumerate(streams):
             if ('windows' in st) == ('faces' in st):
@@ -1355,36 +1302,17 @@ class InferenceWrapper:
         if smooth_pose and (not idents or idents[0] is None):
             raise ValueError("smooth_pose=True smooths every face track as its identity's stream: give every stream 'identities'")
         order = frames_mod.interleave([len(counts) for _, counts in faces])
-        first = [[0] for _ in faces]                                             # first[s][t] = faces of stream s in front of its frame t
-        for f, (_, counts) in zip(first, faces):
-            for c in counts:
-                f.append(f[-1] + c)
+        first = [frames_mod.face_offsets(counts) for _, counts in faces]         # first[s][t] = faces of stream s in front of its frame t
         counts = [faces[s][1][t] for s, t in order]
         spans = frames_mod.face_spans(counts, 0, len(order), batch_size)
         wins = [w for s, t in order for w in faces[s][0][first[s][t]:first[s][t + 1]]]
         identities = None if not idents or idents[0] is None else [i for s, t in order for i in idents[s][first[s][t]:first[s][t + 1]]]
-        masks_of, ids = self._preflight(len(wins), identities, mix, target_theta, smooth_pose, True, refine, refine_masks)
-        matte_fn = None
-        if paste_back:
-            if not 0.0 <= float(feather) <= 0.5:
-                raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
-            matte_fn = self._paste_matte(paste_matte, 'paste_matte=True')
-            S_out = self.cfg["image_size"] if masks_of is None else self._stage2.cfg["output_size_s2"]
-            if any(4 * w[2] < S_out for w in wins):
-                raise ValueError(f"a paste window is smaller than a quarter of the {S_out}-pixel image: downscaling "
-                                 f"stops at image_size / 4")
-        if out_format == "nv12" and as_uint8 and not paste_back:
-            self._nv12_size(masks_of)
-        S = self.cfg["image_size"]
-        out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
-        fmt = (frame_format, colorspace, bool(full_range))
-        host_ring = None if not to_host else (frames_mod.ArenaRing(self.device, ring) if paste_back
-                                              else frames_mod.HostRing(self.device, ring, batch_size))
-        upload_stream = torch.cuda.Stream(device=self.device)
-        ids_dev = None if ids is None else ids.to(self.device)
-        rows = [0]                                                               # rows[i] = faces in front of frame i of the order
-        for c in counts:
-            rows.append(rows[-1] + c)
+        plan = self._video_plan(len(wins), wins, identities, batch_size, ring, to_host, smooth_pose, True, mix, mix_old, target_theta,
+                                paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format, colorspace,
+                                full_range, arena=True)
+        S, host_ring = self.cfg["image_size"], plan.ring
+        ids_dev = None if plan.ids is None else plan.ids.to(self.device)
+        rows = frames_mod.face_offsets(counts)                                   # rows[i] = faces in front of frame i of the order
         todo = [sp for sp in spans if paste_back or rows[sp[0]] < rows[sp[1]]]   # (crops: a batch without a face is not uploaded)
 
         def frames_of(k, st):
@@ -1426,22 +1354,17 @@ class InferenceWrapper:
                 m += c
             return out
 
-        fresh = frames_mod.uploaded_mixed(batches(), self.device, upload_stream, paste_back)
+        fresh = frames_mod.uploaded_mixed(batches(), self.device, plan.upload_stream, paste_back)
         for b0, b1 in todo:
             m0, m1 = rows[b0], rows[b1]
             frames, arena = next(fresh)
             frame_of = [i - b0 for i in range(b0, b1) for _ in range(counts[i])]
             out = None
             if m1 > m0:
-                crops = ops.crop_faces_mixed(frames, S, wins[m0:m1], frame_of, *fmt)
-                ident = None if ids is None else ids_dev[m0:m1]
-                theta = self._pose_controls(self._head_pose(crops)[0], ident, mix, mix_old, smooth_pose)
-                self.pred_target_theta = theta
-                pose, _ = self._expression(crops, theta, 'a driver call')
-                out = self._render(pose, theta, ident, target_theta, masks_of, out_kind, fmt[1:])
+                crops = ops.crop_faces_mixed(frames, S, wins[m0:m1], frame_of, *plan.fmt)
+                out, m = self._drive_crops(crops, None if ids_dev is None else ids_dev[m0:m1], plan, smooth=smooth_pose)
                 if paste_back:
-                    m = None if matte_fn is None else matte_fn(out).float().contiguous()
-                    ops.paste_faces_mixed(frames, out, wins[m0:m1], frame_of, feather, m, *fmt)
+                    ops.paste_faces_mixed(frames, out, wins[m0:m1], frame_of, feather, m, *plan.fmt)
             if paste_back:
                 meta, out = [(s, t, tuple(f.shape)) for (s, t), f in zip(order[b0:b1], frames)], arena
             else:

@@ -713,6 +713,37 @@ def _frame_of_arg(frame_of, F, device):
     return host.to(device, non_blocking=True), host
 
 
+def windows_host(windows, M, size, what, rows="frames", paste_S=None):
+    """The host check of a window list, written once: a host sequence of M windows (x0, y0, w, h) -> int32 [M,4] host tensor, every
+    window inside its frame -- size = the (W, H) of all frames, or an [M,2] tensor, the (W, H) of each face's OWN frame -- and,
+    for a paste into an S x S image (paste_S = S), square with a side of at least S / 4.  ValueError; no device, no upload."""
+    host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
+    if host.shape[0] != M:
+        raise ValueError(f"{host.shape[0]} windows for {M} {rows}")
+    lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
+    if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi <= torch.as_tensor(size)).all())):
+        where = "its own frame" if isinstance(size, torch.Tensor) else f"the {size[0]}x{size[1]} frame"
+        raise ValueError(f"a {what} window is not inside {where}")
+    if paste_S is not None:
+        if not bool((host[:, 2] == host[:, 3]).all()):
+            raise ValueError("paste windows must be square")
+        if not bool((4 * host[:, 2] >= paste_S).all()):
+            raise ValueError(f"a paste window is smaller than a quarter of the {paste_S}x{paste_S} image: downscaling stops at S / 4")
+    return host
+
+
+def _windows_arg(windows, M, size, device, what, rows="frames", paste_S=None):
+    """windows -> (int32 [M,4] device tensor, host tensor or None): a host sequence goes through windows_host and is uploaded
+    (16 bytes per window); a ready device tensor is checked for device, dtype and shape (RuntimeError) and trusted otherwise"""
+    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+        if windows.device != device or windows.dtype != torch.int32 or tuple(windows.shape) != (M, 4) or not windows.is_contiguous():
+            raise RuntimeError("windows must be a contiguous int32 tensor [M,4] on the frames' device" if isinstance(size, torch.Tensor)
+                               else "windows must be a contiguous int32 cuda tensor [N,4]")
+        return windows, None
+    host = windows_host(windows, M, size, what, rows, paste_S)
+    return host.to(device, non_blocking=True), host
+
+
 def resize2d_windows(x, size, windows, mode="bicubic", clamp01=False, frame_of=None):
     """torch.cat([F.interpolate(x[i:i+1, :, y0:y0+h, x0:x0+w], size=size, mode=mode, align_corners=False) for i ...]) in ONE
     launch (notebooks/infer.py:301-352 crops every frame around its own face box): windows = one (x0, y0, w, h) per frame --
@@ -723,18 +754,7 @@ def resize2d_windows(x, size, windows, mode="bicubic", clamp01=False, frame_of=N
     hip.require_cuda_f32(x)
     N, C, H, W = x.shape
     M = N if frame_of is None else len(frame_of)
-    if isinstance(windows, torch.Tensor):
-        win = windows
-        if not win.is_cuda or win.dtype != torch.int32 or tuple(win.shape) != (M, 4) or not win.is_contiguous():
-            raise RuntimeError("windows must be a contiguous int32 cuda tensor [N,4]")
-    else:
-        host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
-        if host.shape[0] != M:
-            raise ValueError(f"{host.shape[0]} windows for {M} {'frames' if frame_of is None else 'faces'}")
-        lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
-        if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi[:, 0] <= W).all()) and bool((hi[:, 1] <= H).all())):
-            raise ValueError(f"a resize window is not inside the {W}x{H} frame")
-        win = host.to(x.device, non_blocking=True)
+    win, _ = _windows_arg(windows, M, (W, H), x.device, "resize", "frames" if frame_of is None else "faces")
     Ho, Wo = size
     out = torch.empty((M, C, Ho, Wo), device=x.device, dtype=torch.float32)
     bicubic = {"bilinear": 0, "bicubic": 1}[mode]
@@ -776,23 +796,7 @@ def paste_windows(frames_u8, img, windows, feather=0.0, matte=None, frame_of=Non
         raise ValueError(f"matte {tuple(matte.shape)}: expected {(N, 1, S, S)}")
     if not 0.0 <= float(feather) <= 0.5:
         raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
-    host = None
-    if isinstance(windows, torch.Tensor) and windows.is_cuda:
-        win = windows
-        if win.device != img.device or win.dtype != torch.int32 or tuple(win.shape) != (N, 4) or not win.is_contiguous():
-            raise RuntimeError("windows must be a contiguous int32 cuda tensor [N,4]")
-    else:
-        host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
-        if host.shape[0] != N:
-            raise ValueError(f"{host.shape[0]} windows for {N} {'frames' if frame_of is None else 'faces'}")
-        lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
-        if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi[:, 0] <= Wf).all()) and bool((hi[:, 1] <= Hf).all())):
-            raise ValueError(f"a paste window is not inside the {Wf}x{Hf} frame")
-        if not bool((host[:, 2] == host[:, 3]).all()):
-            raise ValueError("paste windows must be square")
-        if not bool((4 * host[:, 2] >= S).all()):
-            raise ValueError(f"a paste window is smaller than a quarter of the {S}x{S} image: downscaling stops at S / 4")
-        win = host.to(frames_u8.device, non_blocking=True)
+    win, host = _windows_arg(windows, N, (Wf, Hf), frames_u8.device, "paste", "frames" if frame_of is None else "faces", S)
     if frame_of is not None:
         fof, fof_host = _frame_of_arg(frame_of, F, frames_u8.device)
         if N == 0:
@@ -833,21 +837,6 @@ def _nv12_matrix(colorspace):
     return NV12_MATRICES[colorspace]
 
 
-def _windows_arg(windows, N, Wf, Hf, device, what):
-    """windows -> (int32 [N,4] device tensor, host tensor or None): a host sequence is checked against the frame and uploaded"""
-    if isinstance(windows, torch.Tensor) and windows.is_cuda:
-        if windows.device != device or windows.dtype != torch.int32 or tuple(windows.shape) != (N, 4) or not windows.is_contiguous():
-            raise RuntimeError("windows must be a contiguous int32 cuda tensor [N,4]")
-        return windows, None
-    host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
-    if host.shape[0] != N:
-        raise ValueError(f"{host.shape[0]} windows for {N} frames")
-    lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
-    if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi[:, 0] <= Wf).all()) and bool((hi[:, 1] <= Hf).all())):
-        raise ValueError(f"a {what} window is not inside the {Wf}x{Hf} frame")
-    return host.to(device, non_blocking=True), host
-
-
 def nv12_windows(nv12, size=None, windows=None, colorspace="bt709", full_range=False, frame_of=None):
     """NV12 frames uint8 [N, 3H/2, W] on the device -> fp32 [N,3,Ho,Wo] in [0,1], ONE launch (emo_nv12_windows_f32): each frame's
     window (x0, y0, w, h) of the converted frame, resized bicubically to size = (Ho, Wo) and clamped -- bit for bit
@@ -865,7 +854,7 @@ def nv12_windows(nv12, size=None, windows=None, colorspace="bt709", full_range=F
     M = N if frame_of is None else len(frame_of)
     out = torch.empty((M, 3, Ho, Wo), device=nv12.device, dtype=torch.float32)
     hip.require_cuda_f32(out)                                    # (the frames' device: GPU only, like every op)
-    win, host = (None, None) if windows is None else _windows_arg(windows, M, W, H, nv12.device, "crop")
+    win, host = (None, None) if windows is None else _windows_arg(windows, M, (W, H), nv12.device, "crop")
     if frame_of is not None:
         fof, fof_host = _frame_of_arg(frame_of, N, nv12.device)
         if M == 0:
@@ -926,12 +915,7 @@ def paste_windows_nv12(nv12, img, windows, feather=0.0, matte=None, colorspace="
         raise ValueError(f"matte {tuple(matte.shape)}: expected {(N, 1, S, S)}")
     if not 0.0 <= float(feather) <= 0.5:
         raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
-    win, host = _windows_arg(windows, N, Wf, Hf, img.device, "paste")
-    if host is not None:
-        if not bool((host[:, 2] == host[:, 3]).all()):
-            raise ValueError("paste windows must be square")
-        if not bool((4 * host[:, 2] >= S).all()):
-            raise ValueError(f"a paste window is smaller than a quarter of the {S}x{S} image: downscaling stops at S / 4")
+    win, host = _windows_arg(windows, N, (Wf, Hf), img.device, "paste", paste_S=S)
     if frame_of is not None:
         fof, fof_host = _frame_of_arg(frame_of, F, img.device)
         if N == 0:
@@ -990,23 +974,8 @@ def _mixed_windows(windows, frame_of, table_host, device, S, what):
     F = table_host.shape[0]
     fof, fof_host = _frame_of_arg(frame_of, F, device)
     M = fof_host.numel()
-    if isinstance(windows, torch.Tensor) and windows.is_cuda:
-        if windows.device != device or windows.dtype != torch.int32 or tuple(windows.shape) != (M, 4) or not windows.is_contiguous():
-            raise RuntimeError("windows must be a contiguous int32 tensor [M,4] on the frames' device")
-        return windows, None, fof, fof_host
-    host = torch.tensor([[int(v) for v in w] for w in windows], dtype=torch.int32).reshape(-1, 4)
-    if host.shape[0] != M:
-        raise ValueError(f"{host.shape[0]} windows for {M} faces")
-    size = table_host[fof_host.long()][:, [3, 2]]                                # (W, H) of each face's own frame
-    lo, hi = host[:, :2], host[:, :2] + host[:, 2:]
-    if not (bool((lo >= 0).all()) and bool((host[:, 2:] > 0).all()) and bool((hi <= size).all())):
-        raise ValueError(f"a {what} window is not inside its own frame")
-    if S is not None:
-        if not bool((host[:, 2] == host[:, 3]).all()):
-            raise ValueError("paste windows must be square")
-        if not bool((4 * host[:, 2] >= S).all()):
-            raise ValueError(f"a paste window is smaller than a quarter of the {S}x{S} image: downscaling stops at S / 4")
-    return host.to(device, non_blocking=True), host, fof, fof_host
+    own = table_host[fof_host.long()][:, [3, 2]]                                 # (W, H) of each face's own frame
+    return _windows_arg(windows, M, own, device, what, "faces", S) + (fof, fof_host)
 
 
 def crop_faces_mixed(frames, size, windows, frame_of, frame_format="rgb8", colorspace="bt709", full_range=False):

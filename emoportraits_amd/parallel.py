@@ -167,7 +167,7 @@ def shard_range(n_items, rank, world):
 def gather_shards(local, n_items, rank=None, world=None):
     """Rows of the contiguous shards (shard_range) of every rank -> the whole [n_items, ...] tensor on EVERY rank, in frame
     order.  Used for per-frame SCALARS only (the head-pose thetas of a clip, 16 floats per frame, in front of the smooth_pose
-    scan -- SURVEY.md section 8e caveat); frames themselves never travel.  One all_gather of equal-size padded shards."""
+    scan -- SURVEY.md section 8e caveat); frames themselves never travel.  gather_rows with the shard sizes as counts."""
     if world is None:
         world = dist.get_world_size() if dist.is_initialized() else 1
     if rank is None:
@@ -175,22 +175,8 @@ def gather_shards(local, n_items, rank=None, world=None):
     lo, hi = shard_range(n_items, rank, world)
     if local.shape[0] != hi - lo:
         raise ValueError(f"rank {rank} holds {local.shape[0]} rows, its shard of {n_items} is [{lo}, {hi})")
-    if world == 1:
-        return local
-    if not dist.is_initialized():
-        raise RuntimeError(f"gather_shards(world={world}) without a process group: call init_distributed() first")
-    if world != dist.get_world_size():
-        raise RuntimeError(f"world={world} does not match the process group's {dist.get_world_size()} ranks")
-    per = -(-n_items // world)                                  # the largest shard
-    mine = torch.zeros((per,) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
-    mine[:hi - lo].copy_(local)
-    parts = [torch.empty_like(mine) for _ in range(world)]
-    dist.all_gather(parts, mine)
-    rows = []
-    for r in range(world):
-        a, b = shard_range(n_items, r, world)
-        rows.append(parts[r][:b - a])
-    return torch.cat(rows)
+    counts = [b - a for a, b in (shard_range(n_items, r, world) for r in range(world))]
+    return gather_rows(local, counts, rank, world)          # (max(counts) = ceil(n_items / world): the same padded all_gather)
 
 
 def gather_rows(local, counts, rank=None, world=None):

@@ -8,7 +8,8 @@ which the existing tests hold to the fp64 restatement; -ffp-contract=off makes t
     of the windows changes; frame_of = arange(N) is the batched entry point; device-only windows with an invalid one among them;
   * refusals, with nothing written; M == 0;
   * the ABI table, frames.flatten_faces / face_spans, parallel.gather_rows at world 1 and at world 2 on gloo;
-  * ops.*, InferenceWrapper.paste_back(faces=) / animate_frames(faces=) on CPU tensors, calls counted.
+  * ops.*, InferenceWrapper.paste_back(faces=) / animate_frames(faces=) on CPU tensors, calls counted; animate_frames(windows=)
+    against faces= with one face per frame: one loop, the same tensors, the entry points' names apart.
 frames.face_spans: the issue that asked for it states the rule in words (whole frames, greedily, while faces <= batch_size and
 frames <= batch_size) and gives counts [2,0,3,1], batch_size 4 -> [(0,2),(2,3),(3,4)] as an example.  The example contradicts the
 rule (frames 2 and 3 hold 3 + 1 = 4 faces) and the requirement that a clip of 6 frames x 2 faces at batch_size 4 has the
@@ -534,3 +535,60 @@ def test_animate_frames_checks_its_faces_arguments_before_any_launch(wrapper, rg
     with pytest.raises(ValueError, match="inside"):
         next(w.animate_frames(frames, faces=[[(400, 0, 128)], [], [], []], to_host=False))
     assert w.lib.calls == {}
+
+
+def _renamed(calls):
+    """the call counts of a faces= run under the names of the per-frame entry points"""
+    return {dict(zip(NEW, OLD)).get(name, name): n for name, n in calls.items()}
+
+
+@pytest.mark.parametrize("bank", [False, True])
+@pytest.mark.parametrize("paste", [True, False])
+@pytest.mark.parametrize("fmt", ["rgb8", "nv12"])
+def test_windows_is_faces_with_one_face_per_frame(wrapper, rgb, nv12, fmt, paste, bank):
+    """animate_frames(windows=W) and animate_frames(faces=[[w] for w in W]) are one loop: equal indices, equal tensors, and the
+    same launches but for the entry points' names -- the per-frame ones for windows=, the *_faces_* ones for faces=.  5 frames at
+    batch_size 2: three spans, the last a tail.  With a bank: identities, mix and the per-identity smooth_pose on the way, and the
+    thetas and slots the driver pass receives are equal too."""
+    frames, _, matte = _inputs(rgb, nv12, fmt, "noise")
+    frames, W, w = torch.cat([frames, frames[:1]]), R.WINDOWS[:5], wrapper
+    kw = dict(frame_format="nv12", colorspace=MODE[0], full_range=MODE[1]) if fmt == "nv12" else {}
+    kw.update(dict(paste_back=True, feather=0.25, paste_matte=lambda img: matte[:img.shape[0]]) if paste else dict(as_uint8=False))
+    seen = []
+    if bank:
+        w.cfg.update(latent_volume_channels=4, latent_volume_depth=2, latent_volume_size=2, gen_embed_size=1, gen_max_channels=4)
+        w._init_identity_bank(2)
+        g = torch.Generator().manual_seed(7)
+        for k in range(2):
+            w._bank_write(k, torch.zeros(1, 2, 2, 2, 4), torch.zeros(1, 4, 1, 1), torch.eye(4) + 0.05 * torch.randn(4, 4, generator=g))
+        w._head_pose = lambda crops: (torch.eye(4) + 0.1 * crops.mean(dim=(1, 2, 3)).reshape(-1, 1, 1) * torch.ones(4, 4),)
+        w._drive_bank = lambda pose, theta, ident: (seen.append((theta.clone(), ident.clone())), w._drive(pose, theta))[1]
+        kw.update(identities=[0, 1, 1, 0, 1], mix=True, smooth_pose=True, smooth_per_identity=True)
+    runs = []
+    for how in (dict(windows=W), dict(faces=[[x] for x in W])):
+        w.lib.calls.clear()
+        w.uploads.clear()
+        w.driven.clear()
+        w.reset_pose_state()
+        seen.clear()
+        got = [(i, t.clone()) for i, t in w.animate_frames(frames, batch_size=2, to_host=False, **how, **kw)]
+        runs.append((got, dict(w.lib.calls), list(w.uploads), list(seen)))
+    (got_w, calls_w, up_w, seen_w), (got_f, calls_f, up_f, seen_f) = runs
+    assert [i for i, _ in got_w] == [i for i, _ in got_f] == [0, 2, 4] and [t.shape[0] for _, t in got_w] == [2, 2, 1]
+    assert all(torch.equal(a, b) for (_, a), (_, b) in zip(got_w, got_f))
+    crop, pasted = (OLD[0], OLD[2]) if fmt == "rgb8" else (OLD[1], OLD[3])
+    assert calls_w[crop] == 3 and calls_w.get(pasted, 0) == (3 if paste else 0)
+    assert not set(calls_w) & set(NEW) and not set(calls_f) & set(OLD) and _renamed(calls_f) == calls_w
+    # smooth_pose: the crops of the head-pose pass stay resident, and only a paste needs the frames a second time
+    assert up_w == up_f == [(0, 2), (2, 4), (4, 5)] * (2 if bank and paste else 1)
+    assert len(seen_w) == len(seen_f) == (3 if bank else 0)
+    assert all(torch.equal(a, c) and torch.equal(b, d) for (a, b), (c, d) in zip(seen_w, seen_f))
+
+
+def test_whole_frames_at_image_size_need_no_crop_launch(wrapper):
+    """windows=None and frames of image_size: the crop step is the byte -> fp32 unpacking alone"""
+    w = wrapper
+    clip = torch.randint(0, 256, (5, R.S, R.S, 3), generator=torch.Generator().manual_seed(1), dtype=torch.uint8)
+    got = list(w.animate_frames(clip, batch_size=2, to_host=False))
+    assert [i for i, _ in got] == [0, 2, 4] and w.lib.calls == {"emo_pack_rgb8": 3}
+    assert torch.equal(torch.cat(w.crops), (clip.permute(0, 3, 1, 2).float() / 255))
