@@ -250,11 +250,23 @@ def pack_weight_f16x2_up2(w):
     return planes.view(-1), w_scale
 
 
+def width_class(Wl):
+    """the width class the C entry point files an output width under (shape_of_width, csrc/conv_api.hip: the first thing
+    conv_igemm_dispatch asks, for every kernel): 128 for the multiples of 128, 64 / 32 / 16 / 8 for exactly those widths, None for
+    every other width -- which the entry point refuses with EMO_ERR_UNSUPPORTED whatever the kernel's own tiles would divide"""
+    if Wl is None:
+        return None
+    if Wl >= 128 and Wl % 128 == 0:
+        return 128
+    return Wl if Wl in (64, 32, 16, 8) else None
+
+
 def up2_launch_fits(cout, cin, kd, kh, kw, N, H, W, ups, affine=False, res=False, act="none", ksplit=1, aligned16=True):
     """the launch form of the phase kernel (conv_f16x2_up2_launch and its dispatch -- every check of the C side has its
     mirror here): nearest x2 upsample, 2-D 3x3, whole 64-channel tiles, 8-channel groups (at most the 1024-entry scale table
-    with an affine), a low-res width that is a multiple of 64 and an even low-res height, no residual, no activation, no K split,
-    16-byte aligned input and output, 32-bit byte offsets inside a sample's input"""
+    with an affine), a low-res width that is a multiple of 64 (the output's is then a multiple of 128: always a width class of the
+    entry point) and an even low-res height, no residual, no activation, no K split, 16-byte aligned input and output, 32-bit
+    byte offsets inside a sample's input"""
     if not up2_enabled() or not ups or kd != 1 or (kh, kw) != (3, 3) or res or act != "none" or ksplit != 1 or not aligned16:
         return False
     if cout % BF16X3_BM or cin % 8 or (affine and cin > 1024) or W % 64 or H % 2:
@@ -317,8 +329,8 @@ def f16w8_launch_fits(cout, cin, kd, kh, kw, Hl, Wl, n_pos_tiles, act="none", po
     if cout % (2 * BF16X3_BM) and not (F16_W8_ODD and cout // BF16X3_BM >= F16_W8_ODD) \
             and not f16w8_rest_fits(cout, Hl, Wl):
         return False
-    if Hl is None or Wl % 64 or Hl % 4 or positions_per_sample > (1 << 23):
-        return False
+    if Hl is None or width_class(Wl) not in (128, 64) or Hl % 4 or positions_per_sample > (1 << 23):
+        return False                                  # (4 x 64 tiles on the widths shape_of_width admits: 64 and the multiples of 128)
     min_items = int(__import__("os").environ.get("EMO_CONV_CT2_MIN_ITEMS", 2 * cu_count()))
     cot = cout // BF16X3_BM
     pairs = cot // 2 if f16w8_rest_fits(cout, Hl, Wl) else -(-cot // 2)
@@ -536,15 +548,16 @@ def f16x2_pointwise_launch_fits(Hl, Wl, ups, n_pos_tiles, cout, act="none", posi
     has its mirror here, so that a launch it would refuse with EMO_ERR_UNSUPPORTED is planned onto the fp32 MFMA kernel instead):
     4 x 64 position tiles on the source grid, no activation, at most 2^23 positions per sample (its 32-bit offsets), and enough
     pair items for two per CU of THIS device (below that the fp32 MFMA kernel's K split fills the chip better)"""
-    if Hl is None or ups or act != "none" or Wl % 64 or Hl % 4 or positions_per_sample > (1 << 23):
+    if Hl is None or ups or act != "none" or width_class(Wl) not in (128, 64) or Hl % 4 or positions_per_sample > (1 << 23):
         return False
     min_items = int(__import__("os").environ.get("EMO_F16X2_P1_MIN_ITEMS", 2 * cu_count()))      # (tests lower it to reach small shapes)
     return (n_pos_tiles // 2) * (-(-(cout // BF16X3_BM) // 2)) >= min_items
 
 
 def bf16x3_launch_fits(Hl, Wl, ups=False):
-    """output planes tiled by 4 x 64 positions, or (32- / 16-wide maps, no fused upsample) 8 x 32 / 16 x 16"""
-    return Hl is not None and ((Wl % 64 == 0 and Hl % 4 == 0) or (Wl == 32 and Hl % 8 == 0 and not ups)
+    """output planes tiled by 4 x 64 positions (widths the C entry point admits: 64 and the multiples of 128, width_class), or
+    (32- / 16-wide maps, no fused upsample) 8 x 32 / 16 x 16"""
+    return Hl is not None and ((width_class(Wl) in (128, 64) and Hl % 4 == 0) or (Wl == 32 and Hl % 8 == 0 and not ups)
                                or (Wl == 16 and Hl % 16 == 0 and not ups))
 
 

@@ -65,6 +65,40 @@ def test_driver_pass_R512_B16_bench_configuration_vs_oracle():
     assert torch.equal(dimg, got["img"])
 
 
+def test_driver_pass_R256_B32_bench_configuration_vs_oracle():
+    """bench.py also times the R256 driver pass, at 32 frames per call (r256_fps): a launch plan of its own (the plan is a function
+    of size and batch; the decoder runs 256 / 160 / 96 channels there).  Frames 0 and 31 of the batch against the oracle run
+    frame by frame, with the structure and the bounds of the R512 test above."""
+    B, frames = 32, (0, 31)
+    cfg, sd, x = _full_size(256, B, seed=256)
+    hp = nets.HotPath(sd, cfg, DEV, with_source=False)
+    d = lambda t: t.to(DEV)
+    ccl = hp.prepare_canonical(d(x["canonical"]))
+    got = hp.driver_pass(ccl, d(x["idt"]), d(x["pose_t"]), d(x["th_t"]), keep=True)
+    torch.cuda.synchronize()
+    dimg, dfeat, dimgf = hp.decoder(got["aligned"].view(B, -1, 64, 64))
+    torch.set_num_threads(min(64, os.cpu_count() or 1))
+    worst = {}
+    for i in frames:
+        with torch.no_grad():
+            ref = O.driver_pass(sd, cfg, x["canonical"], x["idt"], x["pose_t"][i:i + 1], x["th_t"][i:i + 1])
+            r_img, r_feat, r_imgf = O.decoder(sd, "decoder_nw", got["aligned"][i:i + 1].cpu().reshape(1, -1, 64, 64), cfg)
+        e = dict(warp_embed=rel(got["warp_embed"][i:i + 1], ref["warp_embed"]),
+                 delta_abs=(got["delta_uv"][i:i + 1].cpu() - ref["delta_uv"]).abs().max().item(),
+                 aligned=rel(got["aligned"][i:i + 1], ref["aligned"]), deep_f=rel(got["deep_f"][i:i + 1], ref["deep_f"]),
+                 img_f=rel(got["img_f"][i:i + 1], ref["img_f"]),
+                 img_abs=(got["img"][i:i + 1].cpu() - ref["img"]).abs().max().item(),
+                 sw_deep_f=rel(dfeat[i:i + 1], r_feat), sw_img_f=rel(dimgf[i:i + 1], r_imgf),
+                 sw_img_abs=(dimg[i:i + 1].cpu() - r_img).abs().max().item())
+        print(f"PARITY R256 B=32 (bench configuration) frame {i}:", {k: f"{v:.2e}" for k, v in e.items()})
+        for k, v in e.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    assert worst["warp_embed"] <= 1e-5 and worst["delta_abs"] <= 1e-4, worst
+    assert worst["sw_deep_f"] <= 5e-5 and worst["sw_img_f"] <= 5e-5 and worst["sw_img_abs"] <= 5e-4, worst
+    assert worst["aligned"] <= 1e-3 and worst["deep_f"] <= 1e-3 and worst["img_f"] <= 1e-3 and worst["img_abs"] <= 5e-3, worst
+    assert torch.equal(dimg, got["img"])
+
+
 def test_driver_pass_R512_B16_trained_like_checkpoint_vs_oracle():
     """The bench's own checkpoint (random_init.trained_like_state_dict: spectral norms ~1, predicted warp within one voxel of
     the identity, unsaturated image -- the released weights are not obtainable) at the bench's launch plan (B = 16): frames

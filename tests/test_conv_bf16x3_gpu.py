@@ -8,24 +8,33 @@ import torch
 import torch.nn.functional as F
 
 from emoportraits_amd import ops, pack
-from test_kernels_gpu import DEV, rel_err, run_conv
+from conv_plans import Expect, split_case
+from test_kernels_gpu import DEV, F16_CASES, F16W8_CASES, rel_err, run_conv
 
 pytestmark = pytest.mark.gpu
 
 
+def declared(case, prec, cfg, form="direct"):
+    """(run_conv arguments, Expect) of a table entry: `split=True` in an entry declares that the K loop of its launch is split"""
+    kw, says = split_case(case)
+    return kw, Expect(prec, cfg, form, says["split"])
+
+
+# every case runs the split kernel of conv_igemm_bf16x3.h on the 64 x 256 tile (plan precision = the layer's, block config D, direct
+# form); split=True: the K loop is split (asked for by the case, or by the planner for a small grid with >= 16 stages)
 CASES = [
     dict(N=2, Cin=40, Cout=120, dims=(64, 64), k=3, cfg=3, affine=True, relu_in=True, res=True),         # ragged channel group
     dict(N=2, Cin=64, Cout=64, dims=(32, 32), k=3, cfg=3, ups=True, res=True, res_ups=True, act="tanh"),
     dict(N=1, Cin=128, Cout=128, dims=(128, 128), k=3, cfg=3, affine=True, relu_in=True),
     dict(N=1, Cin=72, Cout=190, dims=(8, 64, 64), k=3, cfg=3, affine=True, relu_in=True, bias=False),   # 3-D: depth taps as stages
-    dict(N=1, Cin=96, Cout=112, dims=(64, 64), k=3, cfg=3, affine=True, relu_in=True, ksplit=3),
+    dict(N=1, Cin=96, Cout=112, dims=(64, 64), k=3, cfg=3, affine=True, relu_in=True, ksplit=3, split=True),
     dict(N=1, Cin=24, Cout=64, dims=(256, 256), k=3, cfg=3, affine=True, relu_in=True, res=True),
     dict(N=1, Cin=32, Cout=64, dims=(64, 64), k=3, cfg=3, ups=True, affine=True, relu_in=True),
     dict(N=2, Cin=16, Cout=96, dims=(32, 32), k=3, cfg=3, ups=True, affine=True),                       # one stage, no ReLU
     dict(N=1, Cin=8, Cout=64, dims=(4, 64), k=3, cfg=3),                                               # half a stage, one tile
     dict(N=3, Cin=48, Cout=200, dims=(8, 128), k=3, cfg=3, act="sigmoid"),
-    dict(N=1, Cin=512, Cout=64, dims=(64, 64), k=3, cfg=3, affine=True, relu_in=True),                 # 32 stages
-    dict(N=2, Cin=128, Cout=64, dims=(16, 32, 32), k=3, cfg=3, affine=True, relu_in=True, res=True),   # 8 x 32 tiles, 3-D
+    dict(N=1, Cin=512, Cout=64, dims=(64, 64), k=3, cfg=3, affine=True, relu_in=True, split=True),     # 32 stages, 16 blocks
+    dict(N=2, Cin=128, Cout=64, dims=(16, 32, 32), k=3, cfg=3, affine=True, relu_in=True, res=True, split=True),   # 8 x 32 tiles, 3-D
     dict(N=1, Cin=24, Cout=120, dims=(8, 32), k=3, cfg=3, bias=False),                                 # 8 x 32, one tile per plane
     dict(N=6, Cin=64, Cout=320, dims=(64, 128), k=3, cfg=3, affine=True, relu_in=True),                # 960 tiles: persistent blocks
     dict(N=2, Cin=64, Cout=128, dims=(6, 16, 16), k=3, cfg=3, affine=True, relu_in=True, res=True),    # 16 x 16 tiles, 3-D
@@ -47,13 +56,12 @@ BM32_CASES = [
 def test_fp16_split_on_32_row_channel_tiles(case):
     """layers with at most 32 output channels run a 32-row channel tile (csrc/conv_igemm_bf16x3.h, BMT = 32; block config F as
     the tile id) instead of a half-empty 64-row one: same bound, deterministic, and the launch plan says so"""
-    e, got, ref = run_conv(seed=31, precision="f16x2", **case)
+    tile = Expect("f16x2", pack.CFG_F if pack.F16X2_BM32 else pack.CFG_D)       # (asserted on the launch itself)
+    e, got, ref = run_conv(seed=31, precision="f16x2", expect=tile, **case)
     print("PARITY conv f16x2, 32-row channel tiles:", case["Cin"], case["Cout"], case["dims"], f"{e:.2e}")
     assert e < 2e-5, e
-    e2, got2, _ = run_conv(seed=31, precision="f16x2", **case)
+    e2, got2, _ = run_conv(seed=31, precision="f16x2", expect=tile, **case)
     assert torch.equal(got, got2), "two launches on the same input differ: a race in the pipeline"
-    layer = pack.PackedConv("t", torch.randn(case["Cout"], case["Cin"], *([3] * len(case["dims"]))), None, DEV, precision="f16x2")
-    assert layer.plan_for(64, case["dims"][-2], case["dims"][-1])[0] == (pack.CFG_F if pack.F16X2_BM32 else pack.CFG_D)
 
 
 def test_fp16_split_32_row_tiles_statistics_and_range_check():
@@ -93,7 +101,7 @@ def test_fp16_split_on_a_half_empty_channel_tile():
     (activation); the bf16 split declines such a layer"""
     for case in (dict(N=2, Cin=64, Cout=32, dims=(4, 64, 64), k=3, cfg=3, affine=True, relu_in=True, res=True),
                  dict(N=1, Cin=32, Cout=32, dims=(64, 64), k=3, cfg=3, affine=True, relu_in=True, act="tanh")):
-        e, got, ref = run_conv(seed=23, precision="f16x2", **case)
+        e, got, ref = run_conv(seed=23, precision="f16x2", expect=Expect("f16x2", pack.CFG_F if pack.F16X2_BM32 else pack.CFG_D), **case)
         print("PARITY conv f16x2, 32 of 64 tile rows:", case["Cin"], case["Cout"], case["dims"], f"{e:.2e}")
         assert e < 2e-5, e
     with pytest.raises(ValueError):
@@ -102,13 +110,16 @@ def test_fp16_split_on_a_half_empty_channel_tile():
 
 @pytest.mark.parametrize("precision", ["bf16x3", "f16x2"])
 @pytest.mark.parametrize("case", CASES)
-def test_conv_bf16x3_meets_the_fp32_kernel_bound(case, precision):
-    """(f16x2: the opt-in two-term fp16 split of the scaled operands, same kernel with SPLIT = 2, same bound)"""
-    e, got, ref = run_conv(seed=21, precision=precision, **case)
+def test_conv_bf16x3_meets_the_fp32_kernel_bound(case, precision, monkeypatch):
+    """(f16x2: the opt-in two-term fp16 split of the scaled operands, same kernel with SPLIT = 2, same bound -- EMO_CONV_UP2=0
+    keeps its fused-upsample case on this kernel: the phase form that would take it has tests/test_conv_up2_gpu.py)"""
+    monkeypatch.setenv("EMO_CONV_UP2", "0")
+    case, plan = declared(case, precision, pack.CFG_D)
+    e, got, ref = run_conv(seed=21, precision=precision, expect=plan, **case)
     assert got.shape == ref.shape
     print(f"PARITY conv {precision}:", case["Cin"], case["Cout"], case["dims"], f"{e:.2e}")
     assert e < 2e-5, e
-    e2, got2, _ = run_conv(seed=21, precision=precision, **case)
+    e2, got2, _ = run_conv(seed=21, precision=precision, expect=plan, **case)
     assert torch.equal(got, got2), "two launches on the same input differ: a race in the pipeline"
 
 
@@ -295,13 +306,15 @@ def test_conv_f16x2_two_tile_kernel_is_bit_identical_to_the_single_tile_kernel(c
     monkeypatch.setenv("EMO_CONV_CT2_MIN_ITEMS", "1")
     monkeypatch.setenv("EMO_CONV_CT2", "1")
     monkeypatch.setenv("EMO_CONV_W8", "1" if kernel == "w8" else "0")
-    e, got, ref = run_conv(seed=27, precision="f16x2", **case)
+    monkeypatch.setenv("EMO_CONV_UP2", "0")       # (the fused-upsample case without a residual would run the phase form, which
+    plan = Expect("f16x2", pack.CFG_D)            # has no pair kernel: every launch here is the direct form)
+    e, got, ref = run_conv(seed=27, precision="f16x2", expect=plan, **case)
     print(f"PARITY conv f16x2 two-tile kernel [{kernel}]:", case["Cin"], case["Cout"], case["dims"], f"{e:.2e}")
     assert e < 2e-5, e
-    e2, got2, _ = run_conv(seed=27, precision="f16x2", **case)
+    e2, got2, _ = run_conv(seed=27, precision="f16x2", expect=plan, **case)
     assert torch.equal(got, got2), "two launches on the same input differ: a race in the pipeline"
     monkeypatch.setenv("EMO_CONV_CT2", "0")
-    e1, single, _ = run_conv(seed=27, precision="f16x2", **case)
+    e1, single, _ = run_conv(seed=27, precision="f16x2", expect=plan, **case)
     assert torch.equal(got, single), (got - single).abs().max().item()
 
 
@@ -347,7 +360,7 @@ P1_CASES = [
     dict(N=1, Cin=64, Cout=128, dims=(64, 64), k=1, cfg=None),
     dict(N=2, Cin=192, Cout=320, dims=(32, 64), k=1, cfg=None, bias=False, res=True),                 # 5 channel tiles: half-empty pair
     dict(N=2, Cin=128, Cout=192, dims=(64, 128), k=1, cfg=None, affine=True, relu_in=True),
-    dict(N=3, Cin=320, Cout=128, dims=(16, 64), k=1, cfg=None, res=True),
+    dict(N=3, Cin=320, Cout=128, dims=(16, 64), k=1, cfg=None, res=True, f32_split=True),   # (its fp32 twin: 24 blocks, 20 stages)
     dict(N=1, Cin=64, Cout=256, dims=(4, 64, 64), k=1, cfg=None, affine=True, relu_in=True, res=True), # 3-D
     dict(N=4, Cin=1536, Cout=512, dims=(64, 64), k=1, cfg=None, bias=False),                          # the decoder's entry convolution
 ]
@@ -356,12 +369,15 @@ P1_CASES = [
 @pytest.mark.parametrize("case", P1_CASES)
 def test_conv_f16x2_pointwise_kernel(case, monkeypatch):
     monkeypatch.setenv("EMO_F16X2_P1_MIN_ITEMS", "1")
-    e, got, ref = run_conv(seed=29, precision="f16x2", **case)
+    case, says = split_case(case)
+    f32_split = says["f32_split"]
+    plan = Expect("f16x2", pack.CFG_D, "pointwise")
+    e, got, ref = run_conv(seed=29, precision="f16x2", expect=plan, **case)
     print("PARITY conv f16x2 pointwise kernel:", case["Cin"], case["Cout"], case["dims"], f"{e:.2e}")
     assert e < 2e-5, e
-    e2, got2, _ = run_conv(seed=29, precision="f16x2", **case)
+    e2, got2, _ = run_conv(seed=29, precision="f16x2", expect=plan, **case)
     assert torch.equal(got, got2), "two launches on the same input differ: a race in the pipeline"
-    e32, got32, _ = run_conv(seed=29, precision="f32", **case)
+    e32, got32, _ = run_conv(seed=29, precision="f32", expect=Expect("f32", None, split=f32_split), **case)
     assert not torch.equal(got, got32), "the fp32 MFMA kernel ran: the pointwise launch was not planned onto the split kernel"
 
 
@@ -479,3 +495,28 @@ def test_conv_bf16x3_operand_contract():
     x[0, 0, 1, 5], x[0, 0, 1, 6], x[0, 0, 1, 7] = 1e-40, -3e-39, 1.1754942e-38   # fp32 subnormals
     a, b = both(x)
     assert (a - b).abs().max().item() <= 2e-38 and (a.double() - b.double()).abs().max().item() <= 2 ** -126 * 1.01
+
+
+# ---- the declared plans are enforced ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("table,case,precision,plan", [
+    ("CASES", CASES[8], "bf16x3", Expect("bf16x3", pack.CFG_D)),
+    ("CASES", CASES[8], "f16x2", Expect("f16x2", pack.CFG_D)),
+    ("BM32_CASES", BM32_CASES[2], "f16x2", Expect("f16x2", pack.CFG_F)),
+    ("CT2_CASES", CT2_CASES[3], "f16x2", Expect("f16x2", pack.CFG_D)),
+    ("P1_CASES", P1_CASES[0], "f16x2", Expect("f16x2", pack.CFG_D, "pointwise")),
+    ("F16_CASES", F16_CASES[1], "f16", Expect("f16", pack.CFG_D)),
+    ("F16W8_CASES", F16W8_CASES[3], "f16", Expect("f16w8", pack.CFG_D)),
+], ids=lambda v: v if isinstance(v, str) else "")
+def test_run_conv_fails_a_planner_that_falls_back_to_fp32(table, case, precision, plan, monkeypatch):
+    """the exact-fp32 kernel meets every bound of the tables above, so a planner that sends their launches to it would keep every
+    case green: with PackedConv.plan_for replaced by one that always answers with the fp32 plan, run_conv must fail one case of
+    each non-fp32 table with an AssertionError that names the plan that ran"""
+    def fp32_plan(self, n_pos_tiles, *args, **kwargs):
+        return pack.plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, n_pos_tiles, self.allowed, "f32") + ("f32",)
+
+    monkeypatch.setattr(pack.PackedConv, "plan_for", fp32_plan)
+    monkeypatch.setenv("EMO_CONV_CT2_MIN_ITEMS", "1")
+    monkeypatch.setenv("EMO_F16X2_P1_MIN_ITEMS", "1")
+    kw, _ = split_case(case)
+    with pytest.raises(AssertionError, match=r"the launch ran \(precision, cfg, ksplit, form\) = \('f32', \d, \d+, 'direct'\)"):
+        run_conv(seed=1, precision=precision, expect=plan, **kw)

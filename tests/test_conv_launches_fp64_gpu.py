@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import conv_reference as R
+from conv_plans import executed
 from emoportraits_amd import config, nets, ops, pack, random_init, stage2
 from test_nets_gpu import _full_size
 
@@ -103,15 +104,7 @@ class LaunchChecker:
         xc, sc, sh, rc = _clone(x), _clone(a["scale"]), _clone(a["shift"]), _clone(a["res"])
         result = real(*args, **kwargs)
         out, st = result if a["want_stats"] else (result, None)
-        cfg, ks, prec = layer.last_plan
-        if prec == "stream":
-            form = "stream"
-        elif prec == "f16x2" and layer.pointwise_split:
-            form = "pointwise"
-        elif prec == "f16w8" and pack.f16w8_rest_fits(layer.cout, out.shape[-2], out.shape[-1]):
-            form = "f16w8_rest"
-        else:
-            form = getattr(layer, "last_form", None) or "direct"
+        prec, cfg, ks, form = executed(layer, out)
         flags = dict(relu_in=a["relu_in"], ups=a["ups"], res_ups=a["res_ups"], act=a["act"])
         yard = None
         if prec in R.SPLIT_MEAN:

@@ -256,14 +256,17 @@ def test_fp16_plan_falls_back_to_fp32_where_the_fp16_kernel_cannot_run():
     assert lay.plan_for(big, 512, 512)[2] == "f16"                   # an odd number of channel tiles (one): the older kernel
     assert pack.PackedConv("c", torch.zeros(96, 64, 3, 3), None, "cpu", precision="f16").plan_for(big, 512, 512)[2] == "f16"
     # ... an odd count >= 3: the pairs on the eight-wave kernel, the last tile on the older one (emo_conv_igemm_f16w8_rest, ABI 10) where
-    # the plane is in BOTH kernels' launch form; elsewhere (planner logic only: the C entry points admit widths that are multiples of
-    # 128, or 64 / 32 / 16 / 8) a half-empty last pair from five tiles on
+    # the plane is in BOTH kernels' launch form.  A width the C entry point files under no class (shape_of_width: multiples of 128,
+    # or 64 / 32 / 16 / 8 -- 192 is none of them) is in no fp16 kernel's launch form, whatever its tiles would divide: fp32 plan
     t3 = pack.PackedConv("t3", torch.zeros(192, 64, 3, 3), None, "cpu", precision="f16")
     t5 = pack.PackedConv("t5", torch.zeros(320, 64, 3, 3), None, "cpu", precision="f16")
     assert t3.plan_for(big, 512, 512)[2] == "f16w8" and pack.f16w8_rest_fits(192, 512, 512)
     assert t5.plan_for(big, 512, 512)[2] == "f16w8" and pack.f16w8_rest_fits(320, 512, 512)
     assert not pack.f16w8_rest_fits(192, 192, 192) and not pack.f16w8_rest_fits(128, 512, 512) and not pack.f16w8_rest_fits(64, 512, 512)
-    assert t3.plan_for(big, 192, 192)[2] == "f32" and t5.plan_for(big, 192, 192)[2] == "f16w8"
+    assert t3.plan_for(big, 192, 192)[2] == "f32" and t5.plan_for(big, 192, 192)[2] == "f32"
+    assert pack.width_class(192) is None and [pack.width_class(w) for w in (8, 16, 32, 64, 128, 256, 384)] == [8, 16, 32, 64, 128, 128, 128]
+    assert not pack.bf16x3_launch_fits(192, 192) and pack.bf16x3_launch_fits(256, 256) and pack.bf16x3_launch_fits(64, 64)
+    assert not pack.f16x2_pointwise_launch_fits(192, 192, False, big, 128) and pack.f16x2_pointwise_launch_fits(256, 256, False, big, 128)
     flat, ws = pack.pack_weight_f16w8(torch.randn(70, 24, 3, 3))
     assert flat.dtype == torch.float16 and flat.numel() == 2 * 2 * 9 * 2 * 64 * 8 and ws == 2.0 ** math.floor(math.log2(ws))
 
