@@ -1,0 +1,1 @@
+from .controls import ExpressionControls  # noqa: F401

@@ -1,0 +1,35 @@
+"""The value types of the public keywords that are more than a flag (pure Python: importing the package stays cheap)."""
+import dataclasses
+from collections.abc import Mapping
+
+
+@dataclasses.dataclass
+class ExpressionControls:
+    """The `expression=` keyword of InferenceWrapper.animate / animate_frames / animate_streams: what happens to the driver's
+    expression vectors between the expression embedder and the render, on the device (ops.expression_controls).  A row is a
+    frame, or a face with faces=.
+    relative: source expression + (driver_t - driver_first): the driver's resting face stays out of the avatar.
+    gain: a float, or one value per row -- damps (< 1) or exaggerates (> 1) the expression about the identity's source expression.
+    offset: [E] or [rows,E], added to the expression (an emotion direction, constant or per row).
+    smooth, momentum: the smooth_pose recurrence on the expression, e = e * momentum + previous * (1 - momentum), 0 < momentum <= 1.
+    override: [rows,E] in place of the expression embedder's output (the batched `custome_target_pose_embed`); the embedder is
+        then not run.
+    All defaults = no control: nothing is launched and no state is touched."""
+    relative: bool = False
+    gain: object = 1.0
+    offset: object = None
+    smooth: bool = False
+    momentum: float = 0.5
+    override: object = None
+
+    @classmethod
+    def of(cls, value):
+        """None | ExpressionControls | a mapping with the same fields -> ExpressionControls or None"""
+        if value is None or isinstance(value, cls):
+            return value
+        if isinstance(value, Mapping):
+            unknown = sorted(set(value) - {f.name for f in dataclasses.fields(cls)})
+            if unknown:
+                raise ValueError(f"expression= has no field {unknown[0]!r}")
+            return cls(**value)
+        raise ValueError("expression= takes an ExpressionControls or a mapping with its fields")

@@ -343,6 +343,60 @@ __global__ __launch_bounds__(64) void theta_ema_scan_kernel(const float* __restr
   }
 }
 
+// The expression controls of the batched entry points (include/emo_hip.h, ABI 20; hostglue.expression_controls is the contract):
+// relative transfer and gain about the identity's source expression, an additive offset, an EMA -- per stream and in row order.
+// One block per stream; a thread owns the elements j = threadIdx.x, + blockDim.x, ... of every row and of the stream's anchor
+// and EMA, and walks the n rows in order, so `out` may be `values`.  Every thread reads the stream's flags, then the barrier;
+// the block's LAST thread alone writes them, at its end (a host build that runs thread after thread reaches it last as well).
+__global__ __launch_bounds__(128) void expr_controls_kernel(const float* values, const int* __restrict__ stream_of,
+                                                            const float* __restrict__ neutral, const float* __restrict__ gain,
+                                                            const float* __restrict__ offset, float* __restrict__ anchor,
+                                                            int* has_anchor, float* __restrict__ ema, int* has_ema, int n, int E,
+                                                            int relative, int smooth, float m, float om, float* out) {
+  const int k = blockIdx.x;
+  const bool had_anchor = relative && has_anchor[k] != 0;
+  const bool had_ema = smooth && has_ema[k] != 0;
+  __syncthreads();
+  for (int j = threadIdx.x; j < E; j += blockDim.x) {
+    const long kj = (long)k * E + j;
+    bool ha = had_anchor, he = had_ema;
+    float anc = ha ? anchor[kj] : 0.0f;
+    float cur = he ? ema[kj] : 0.0f;
+    const float neu = neutral ? neutral[kj] : 0.0f;
+    for (int i = 0; i < n; ++i) {
+      if ((stream_of ? stream_of[i] : 0) != k) continue;
+      const long ij = (long)i * E + j;
+      float e = values[ij];
+      if (neutral) {
+        float r = neu;
+        if (relative) {
+          if (!ha) { anc = e; ha = true; }
+          r = anc;
+        }
+        float t = e - r;
+        if (gain) t = t * gain[i];
+        e = neu + t;
+      }
+      if (offset) e = e + offset[ij];
+      if (smooth) {
+        if (!he) { cur = e; he = true; }
+        const float a = e * m, b = cur * om;
+        cur = a + b;
+        e = cur;
+      }
+      out[ij] = e;
+    }
+    if (ha && !had_anchor) anchor[kj] = anc;
+    if (he) ema[kj] = cur;
+  }
+  if (threadIdx.x == blockDim.x - 1 && (relative || smooth)) {
+    bool seen = false;
+    for (int i = 0; i < n && !seen; ++i) seen = (stream_of ? stream_of[i] : 0) == k;
+    if (seen && relative) has_anchor[k] = 1;
+    if (seen && smooth) has_ema[k] = 1;
+  }
+}
+
 }  // namespace
 
 extern "C" int emo_small_gemm_f32(const float* A, const float* B, float* C, int M, int K, int NN, int batch,
@@ -419,5 +473,18 @@ extern "C" int emo_theta_ema_scan_f32(const float* values, const int32_t* stream
   if (!values || !state || !has_state || !out || n <= 0 || K <= 0) return EMO_ERR_BAD_ARG;
   hipLaunchKernelGGL(theta_ema_scan_kernel, dim3(emo_cdiv(K, 64)), dim3(64), 0, (hipStream_t)stream, values, stream_of, state,
                      has_state, n, K, m, om, out);
+  return emo_launch_status();
+}
+
+extern "C" int emo_expr_controls_f32(const float* values, const int32_t* stream_of, const float* neutral, const float* gain,
+                                     const float* offset, float* anchor, int32_t* has_anchor, float* ema, int32_t* has_ema, int n,
+                                     int K, int E, int relative, int smooth, float m, float om, float* out, void* stream) {
+  if (!values || !out || n <= 0 || K <= 0 || E <= 0) return EMO_ERR_BAD_ARG;
+  if ((relative || gain) && !neutral) return EMO_ERR_BAD_ARG;
+  if (relative && (!anchor || !has_anchor)) return EMO_ERR_BAD_ARG;
+  if (smooth && (!ema || !has_ema)) return EMO_ERR_BAD_ARG;
+  const int threads = E >= 128 ? 128 : emo_cdiv(E, 64) * 64;
+  hipLaunchKernelGGL(expr_controls_kernel, dim3(K), dim3(threads), 0, (hipStream_t)stream, values, stream_of, neutral, gain, offset,
+                     anchor, has_anchor, ema, has_ema, n, E, relative ? 1 : 0, smooth ? 1 : 0, m, om, out);
   return emo_launch_status();
 }

@@ -125,6 +125,62 @@ def ema_scan(values, state, momentum):
     return out, cur
 
 
+def expression_controls(values, stream_of, neutral, gain, offset, anchor, has_anchor, ema, has_ema, relative, momentum):
+    """The expression controls of the batched entry points on the host, one row after another -- the contract that
+    emo_expr_controls_f32 (ops.expression_controls) is held to bit for bit, as ema_scan is for the theta scan.  The reference has
+    no such controls beyond the `custome_target_pose_embed` override (notebooks/infer.py:603-604).
+    values [n,E] fp32 in frame order; stream_of [n] ints or None (every row: stream 0); neutral [K,E] or None; gain [n] or None;
+    offset [n,E] or None; anchor, ema [K,E] and has_anchor, has_ema [K] are the streams' states, UPDATED IN PLACE (numpy arrays;
+    None where the control that needs them is off); momentum None = no smoothing.  Row i of stream k, every operation in fp32
+    and rounded on its own:
+        with neutral:  r = neutral[k], or with `relative` the stream's anchor (its first row);  e = neutral[k] + (e - r) * gain[i]
+        with offset:   e = e + offset[i]
+        with momentum: the smooth_pose recurrence, cur = e * m + cur * fp32(1 - m), started at the stream's first e
+    -> out [n,E]; a row whose stream lies outside [0, K) is left unwritten (NaN here) and touches no state."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    if v.ndim != 2:
+        raise ValueError(f"values must be [n,E], got {v.shape}")
+    smooth = momentum is not None
+    if (relative or gain is not None) and neutral is None:
+        raise ValueError("relative transfer and gain work about a neutral expression: neutral is missing")
+    if relative and (anchor is None or has_anchor is None):
+        raise ValueError("relative transfer needs anchor and has_anchor")
+    if smooth and (ema is None or has_ema is None):
+        raise ValueError("smoothing needs ema and has_ema")
+    K = next((a.shape[0] for a in (neutral, anchor, ema) if a is not None), 1)
+    f32 = lambda a: None if a is None else np.asarray(a, dtype=np.float32)
+    neutral, gain, offset = f32(neutral), f32(gain), f32(offset)
+    if smooth:
+        m, om = np.float32(momentum), np.float32(1 - momentum)
+    out = np.full_like(v, np.nan)
+    for i in range(v.shape[0]):
+        k = 0 if stream_of is None else int(stream_of[i])
+        if not 0 <= k < K:
+            continue
+        e = v[i].copy()
+        if neutral is not None:
+            r = neutral[k]
+            if relative:
+                if not has_anchor[k]:
+                    anchor[k] = e
+                    has_anchor[k] = 1
+                r = anchor[k]
+            t = e - r
+            if gain is not None:
+                t = t * gain[i]
+            e = neutral[k] + t
+        if offset is not None:
+            e = e + offset[i]
+        if smooth:
+            if not has_ema[k]:
+                ema[k] = e
+                has_ema[k] = 1
+            e = e * m + ema[k] * om
+            ema[k] = e
+        out[i] = e
+    return out
+
+
 def bank_slot(slot, capacity):
     """a slot of an identity bank of `capacity` slots as an int; ValueError unless it is an integer (not a bool) in range"""
     import operator

@@ -38,6 +38,7 @@ from . import config as cfg_mod
 from . import embedders as emb_mod
 from . import frames as frames_mod
 from . import graphs, hostglue, nets, ops, parallel, schema
+from .controls import ExpressionControls
 
 
 # smooth_pose in animate_frames: the crops of a rank's shard stay resident between the head-pose pass and the render pass up to
@@ -191,6 +192,9 @@ class InferenceWrapper:
         self.resize_warp = False
         self.use_seg = use_seg
         self.target_latent_volume = self._canonical_cl = self.idt_embed = self.pred_source_theta = None
+        # the current identity's source expression (the expression controls' neutral) and, without a bank, the one stream's
+        # relative-transfer anchor and expression EMA ([E], None before the first row), carried from call to call as self.theta
+        self.pred_source_pose_embed = self._expr_anchor = self._expr_ema = None
         self._stage2 = self._stage2_wrapper = None                                 # attach_stage2()
         self._init_identity_bank(identity_capacity)
 
@@ -244,6 +248,10 @@ class InferenceWrapper:
             raise ValueError("identity_capacity must be >= 0")
         self.identity_capacity = capacity
         self._bank_used = [False] * capacity
+        # the expression controls' per-slot data (_expr_bank allocates it, from the width of the first row written): the source
+        # expression [K,E] and which slots have one, the relative-transfer anchor and the expression EMA [K,E] with their flags
+        self._bank_expr = self._bank_expr_anchor = self._bank_expr_anchor_has = self._bank_expr_ema = self._bank_expr_ema_has = None
+        self._bank_expr_has = [False] * capacity
         if capacity == 0:
             self._bank_cl = self._bank_idt = self._bank_theta = None
             self._bank_pose, self._bank_pose_has = None, None
@@ -266,7 +274,21 @@ class InferenceWrapper:
             raise ValueError(f"slot {slot} holds no identity")
         return slot
 
-    def _bank_write(self, slot, canonical_cl, idt_embed, theta_src):
+    def _expr_bank(self, E):
+        """the bank's expression rows, allocated at the first use from the width E of the row at hand (a bank's `cfg` need not
+        name it); every later row has that width"""
+        if self._bank_expr is None:
+            K = self.identity_capacity
+            self._bank_expr, self._bank_expr_anchor, self._bank_expr_ema = (
+                torch.zeros((K, E), device=self.device, dtype=torch.float32) for _ in range(3))
+            self._bank_expr_anchor_has, self._bank_expr_ema_has = (
+                torch.zeros((K,), device=self.device, dtype=torch.int32) for _ in range(2))
+        elif self._bank_expr.shape[1] != E:
+            raise ValueError(f"an expression row of width {E}: the identity bank holds rows of width {self._bank_expr.shape[1]}")
+
+    def _bank_write(self, slot, canonical_cl, idt_embed, theta_src, expr_src=None):
+        if expr_src is not None:
+            self._expr_bank(expr_src.numel())
         if idt_embed.numel() != self._bank_idt[slot].numel():
             raise ValueError(f"idt_embed {tuple(idt_embed.shape)} does not fit a slot {tuple(self._bank_idt.shape[1:])}")
         self._bank_cl[slot].copy_(canonical_cl.reshape(self._bank_cl.shape[1:]))
@@ -274,6 +296,10 @@ class InferenceWrapper:
         self._bank_theta[slot].copy_(theta_src.reshape(4, 4))
         self._bank_used[slot] = True
         self._bank_pose_has[slot] = 0             # a new identity starts a new smooth_pose stream
+        self._bank_expr_has[slot] = expr_src is not None     # (a slot written without a source expression has no neutral)
+        if expr_src is not None:
+            self._bank_expr[slot].copy_(expr_src.reshape(-1))
+        self.reset_expression_state([slot])
 
     def store_identity(self, slot=None):
         """Copy the current identity (what forward(source_image=...) or share_source() left behind) into `slot` (None: the
@@ -290,7 +316,7 @@ class InferenceWrapper:
                 raise ValueError(f"all {self.identity_capacity} identity slots are occupied: drop_identity one first")
             slot = free[0]
         slot = self._slot(slot, occupied=False)
-        self._bank_write(slot, self._canonical_cl, self.idt_embed, self.pred_source_theta)
+        self._bank_write(slot, self._canonical_cl, self.idt_embed, self.pred_source_theta, self.pred_source_pose_embed)
         return slot
 
     def load_identity(self, slot):
@@ -301,11 +327,28 @@ class InferenceWrapper:
         self.target_latent_volume = ops.volume_to_channels_first(cl)
         self._set_source_cache(canonical_cl=cl, idt_embed=self._bank_idt[slot:slot + 1].clone())
         self.pred_source_theta = self._bank_theta[slot:slot + 1].clone()
+        self.pred_source_pose_embed = self._bank_expr[slot:slot + 1].clone() if self._bank_expr_has[slot] else None
 
     def drop_identity(self, slot):
         slot = self._slot(slot)
         self._bank_used[slot] = False
         self._bank_pose_has[slot] = 0
+        self._bank_expr_has[slot] = False
+        self.reset_expression_state([slot])
+
+    def reset_expression_state(self, slots=None):
+        """Restart the expression controls' streams (the relative-transfer anchor and the expression EMA): slots=None clears the
+        single-identity state and every slot's; otherwise only the given bank slots'"""
+        if slots is None:
+            self._expr_anchor = self._expr_ema = None
+            slots = range(self.identity_capacity)
+        elif not isinstance(slots, (list, tuple, range, torch.Tensor)):
+            slots = [slots]
+        slots = [self._slot(int(k), occupied=False) for k in slots]
+        if self._bank_expr is not None and slots:
+            rows = torch.tensor(slots, dtype=torch.int64).to(self.device)
+            self._bank_expr_anchor_has.index_fill_(0, rows, 0)
+            self._bank_expr_ema_has.index_fill_(0, rows, 0)
 
     def reset_pose_state(self, slots=None):
         """Restart smooth_pose: slots=None clears the single-identity state (`self.theta`) and every slot's stream; otherwise
@@ -329,14 +372,20 @@ class InferenceWrapper:
         slot = self._slot(slot, occupied=src)
         rows = {} if not src else dict(canonical_cl=self._bank_cl[slot:slot + 1], idt_embed=self._bank_idt[slot:slot + 1],
                                        theta_src=self._bank_theta[slot:slot + 1])
+        if src and self._bank_expr_has[slot]:
+            rows['expr_src'] = self._bank_expr[slot:slot + 1]
         cache = self._broadcast_rows(rows, 1, src_rank, 'canonical_cl', self._bank_cl.shape[1:])
         if not src:
-            self._bank_write(slot, cache["canonical_cl"], cache["idt_embed"], cache["theta_src"])
+            self._bank_write(slot, cache["canonical_cl"], cache["idt_embed"], cache["theta_src"], cache.get("expr_src"))
 
     def _broadcast_rows(self, rows, n, src, volume, volume_shape):
-        """{volume, idt_embed, theta_src} of n identities from rank `src` (its `rows`; {} elsewhere) to every rank in one flat
-        buffer, the shapes known on every rank: one collective, no host synchronisation (parallel.broadcast_source_cache)"""
+        """{volume, idt_embed, theta_src, expr_src} of n identities from rank `src` (its `rows`; {} elsewhere) to every rank in
+        one flat buffer, the shapes known on every rank: one collective, no host synchronisation
+        (parallel.broadcast_source_cache).  expr_src, the source expressions, travels where the configuration names its width."""
         shapes = {volume: (n,) + tuple(volume_shape), 'idt_embed': (n,) + tuple(self._bank_idt.shape[1:]), 'theta_src': (n, 4, 4)}
+        E = self.cfg.get("lpe_output_channels_expression")
+        if E:
+            shapes['expr_src'] = (n, int(E))
         return parallel.broadcast_source_cache(rows, shapes=shapes, names=list(shapes), src=src, device=self.device,
                                                world=self.world, rank=self.rank, exchange_shapes=False)
 
@@ -487,12 +536,16 @@ class InferenceWrapper:
             pose = pose_all[a:b] if pose_all is not None else self._expression(crop_m, theta, 'enrolment')[0]
             theta = theta.float().contiguous()
             canonical = self.hot_path.source_pass(masked, idt.float().contiguous(), pose.float().contiguous(), theta)
-            return dict(canonical=canonical, idt_embed=idt.float().reshape((b - a,) + es_shape), theta_src=theta.reshape(b - a, 4, 4))
+            return dict(canonical=canonical, idt_embed=idt.float().reshape((b - a,) + es_shape), theta_src=theta.reshape(b - a, 4, 4),
+                        expr_src=pose.float().reshape(b - a, -1))
 
         def write(part, a, b):
             ops.volume_to_channels_last_indexed(part["canonical"], self._bank_cl, rows32[a:b])
             self._bank_idt.index_copy_(0, rows64[a:b], part["idt_embed"])
             self._bank_theta.index_copy_(0, rows64[a:b], part["theta_src"])
+            if "expr_src" in part:
+                self._expr_bank(part["expr_src"].shape[1])
+                self._bank_expr.index_copy_(0, rows64[a:b], part["expr_src"])
 
         if self.world == 1:
             for a, b in plan.chunks:
@@ -505,6 +558,8 @@ class InferenceWrapper:
                 write(self._broadcast_rows(mine.pop(j, {}), b - a, plan.owners[j], 'canonical', (c, d, s, s)), a, b)
         for k in plan.slots:
             self._bank_used[k] = True
+            self._bank_expr_has[k] = self._bank_expr is not None
+        self.reset_expression_state(plan.slots)
         self._bank_pose_has.index_fill_(0, rows64, 0)              # a new identity starts a new smooth_pose stream
         return plan.slots
 
@@ -745,6 +800,103 @@ class InferenceWrapper:
             self.theta = state[0]
         return theta
 
+    def _expression_plan(self, expression, n_rows, ids, where, faces=False):
+        """The checks of expression= (an ExpressionControls or a mapping with its fields), before anything is launched -> None
+        (no control: nothing will be launched, no state touched) or what _expression_controls needs: relative, smooth, momentum
+        (None without smooth), gain (None = 1.0 | a float | a device [rows]), offset (None | a device [E] or [rows,E]), override
+        (None | a device [rows,E]), step1 = the part about the neutral runs, scan = a control that walks the frame order.
+        n_rows: the rows of the call where known; ids: the per-row slots (host tensor) or None = the current identity."""
+        ex = ExpressionControls.of(expression)
+        if ex is None:
+            return None
+        m = float(ex.momentum)
+        if not 0.0 < m <= 1.0:
+            raise ValueError(f"expression momentum {ex.momentum} is not in (0, 1]")
+        relative, smooth = bool(ex.relative), bool(ex.smooth)
+
+        def rows(t, what, dims):
+            t = torch.as_tensor(t).detach().float()
+            if t.dim() not in dims:
+                raise ValueError(f"expression {what}: a tensor of {' or '.join(str(d) for d in dims)} dimensions, got {tuple(t.shape)}")
+            if t.dim() == (1 if what == 'gain' else 2) and n_rows is not None and t.shape[0] != n_rows:
+                raise ValueError(f"expression {what} has {t.shape[0]} rows for {n_rows} rows of the call")
+            return t
+        gain = ex.gain
+        if isinstance(gain, torch.Tensor) and gain.dim() == 0 or not isinstance(gain, torch.Tensor) and not hasattr(gain, '__len__'):
+            gain = None if float(gain) == 1.0 else float(gain)
+        else:
+            gain = rows(gain, 'gain', (1,))
+        offset = None if ex.offset is None else rows(ex.offset, 'offset', (1, 2))
+        override = None if ex.override is None else rows(ex.override, 'override', (2,))
+        if override is not None and where != 'animate_frames':
+            raise ValueError(f"expression override= replaces the expression embedder of animate_frames: {where}"
+                             + ("'s expressions are inputs already" if where == 'animate' else " takes none"))
+        if not (relative or smooth or gain is not None or offset is not None or override is not None):
+            return None
+        step1 = relative or gain is not None
+        if (relative or smooth) and ids is None and (faces or where == 'animate_streams'):
+            raise ValueError("expression relative / smooth follow every face track as its identity's stream: give identities")
+        widths = {t.shape[-1] for t in (offset, override) if t is not None}
+        if step1 and ids is None:
+            if self.pred_source_pose_embed is None:
+                raise ValueError("expression relative / gain work about the current identity's source expression, which is missing: "
+                                 "call forward with a source_image (or load_identity a slot that has one) first")
+            widths.add(self.pred_source_pose_embed.numel())
+        elif step1:
+            missing = [k for k in sorted(set(ids.tolist())) if not self._bank_expr_has[k]]
+            if missing:
+                raise ValueError(f"expression relative / gain work about each identity's source expression: slot {missing[0]} has none")
+        if ids is not None and (step1 or smooth) and self._bank_expr is not None:
+            widths.add(self._bank_expr.shape[1])
+        if len(widths) > 1:
+            raise ValueError(f"expression rows of different widths: {sorted(widths)}")
+        up = lambda t: None if t is None else t.to(self.device).contiguous()
+        return Namespace(relative=relative, smooth=smooth, momentum=m if smooth else None, step1=step1, scan=relative or smooth,
+                         gain=up(gain) if isinstance(gain, torch.Tensor) else gain, offset=up(offset), override=up(override))
+
+    @staticmethod
+    def _expression_rows(t, r0, m, what):
+        if t.shape[0] < r0 + m:
+            raise ValueError(f"expression {what} has {t.shape[0]} rows, the frames run past it")
+        return t[r0:r0 + m]
+
+    def _expression_controls(self, values, ids_dev, ex, r0):
+        """The expression controls `ex` (_expression_plan) on values [m,E] = the rows r0 ... of the call IN FRAME ORDER, one launch
+        (ops.expression_controls, bit for bit hostglue.expression_controls): every row about its identity's source expression
+        (bank slot ids_dev[i], or the current identity's), and for relative / smooth within its slot's stream, whose anchor and
+        EMA the bank carries -- without identities the one stream whose state `_expr_anchor` / `_expr_ema` carries from call to
+        call as `self.theta` does for smooth_pose"""
+        values = values.to(self.device).float().contiguous()
+        m = values.shape[0]
+        if m == 0 or not (ex.step1 or ex.scan or ex.offset is not None):          # (an override alone: nothing to compute)
+            return values
+        E = values.shape[1]
+        gain = self._expression_rows(ex.gain, r0, m, 'gain') if isinstance(ex.gain, torch.Tensor) else ex.gain
+        offset = ex.offset if ex.offset is None or ex.offset.dim() == 1 else self._expression_rows(ex.offset, r0, m, 'offset')
+        if ids_dev is not None and (ex.step1 or ex.scan):
+            self._expr_bank(E)
+            return ops.expression_controls(values, ids_dev, self._bank_expr if ex.step1 else None, gain, offset, self._bank_expr_anchor,
+                                           self._bank_expr_anchor_has, self._bank_expr_ema, self._bank_expr_ema_has, ex.relative,
+                                           ex.momentum)
+        neutral = None
+        if ex.step1:
+            neutral = self.pred_source_pose_embed.to(self.device).float().reshape(1, -1).contiguous()
+        state = {}
+        for name, on in (('_expr_anchor', ex.relative), ('_expr_ema', ex.smooth)):
+            if on:
+                rows = torch.zeros((1, E), device=self.device, dtype=torch.float32)
+                has = torch.zeros((1,), device=self.device, dtype=torch.int32)
+                if getattr(self, name) is not None:
+                    rows.copy_(getattr(self, name).reshape(1, -1))
+                    has.fill_(1)
+                state[name] = (rows, has)
+        anchor, has_anchor = state.get('_expr_anchor', (None, None))
+        ema, has_ema = state.get('_expr_ema', (None, None))
+        out = ops.expression_controls(values, None, neutral, gain, offset, anchor, has_anchor, ema, has_ema, ex.relative, ex.momentum)
+        for name, (rows, _) in state.items():
+            setattr(self, name, rows[0])
+        return out
+
     def _render_theta(self, theta, ids_dev, target_theta):
         """target_theta=False: the frame is rendered in its identity's own head pose (infer.py:584), a device-side gather"""
         if target_theta:
@@ -772,6 +924,7 @@ class InferenceWrapper:
                 self.center = self.size = self.theta = self.delta_yaw = self.delta_pitch = None
                 self._crop_tracker = None
                 self.reset_pose_state()
+                self.reset_expression_state()
             self.mix, self.mix_old = mix, mix_old
             if delta_yaw is not None:
                 self.delta_yaw = delta_yaw
@@ -889,7 +1042,7 @@ class InferenceWrapper:
     # ------------------------------------------------------------------------------------------------------
     def animate(self, target_pose_embeds, target_srt, batch_size=16, as_uint8=True, identities=None, mix=False, mix_old=True,
                 target_theta=True, smooth_pose=False, smooth_per_identity=False, refine=False, refine_masks=None,
-                out_format="rgb8", colorspace="bt709", full_range=False):
+                out_format="rgb8", colorspace="bt709", full_range=False, expression=None):
         """1 source -> N driver frames (the BASELINE metric).  Frames are sharded contiguously across ranks
         (SURVEY.md section 8e); each rank walks its shard in batches of `batch_size`.  Yields (first_frame_index, frames)
         with frames a uint8 [B,H,W,3] (or fp32 [B,3,H,W]) DEVICE tensor -- no host sync inside the loop.
@@ -904,7 +1057,10 @@ class InferenceWrapper:
         refine=True: every rendered batch goes through the attached stage-2 model (attach_stage2; see animate_frames) and the
         frames come out at its output_size_s2.
         out_format='nv12' (with as_uint8): the frames come out as NV12 uint8 [B, 3S/2, S] -- the fp32 image, refined or not,
-        through ops.pack_nv12 with `colorspace` ('bt709' | 'bt601') and `full_range` (see animate_frames)."""
+        through ops.pack_nv12 with `colorspace` ('bt709' | 'bt601') and `full_range` (see animate_frames).
+        expression: an ExpressionControls (or a mapping with its fields) applied to target_pose_embeds on the device, see
+        animate_frames; like smooth_pose, every rank runs it over the WHOLE stream in one launch and renders its slice, so the
+        frames do not depend on batch_size or on the number of ranks.  override= is a ValueError: the expressions are inputs."""
         N = target_pose_embeds.shape[0]
         frames_mod.check_format(out_format, colorspace, "out_format")
         if out_format == "nv12" and not as_uint8:
@@ -912,6 +1068,7 @@ class InferenceWrapper:
         masks_of, ids = self._preflight(N, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
         if out_format == "nv12":
             self._nv12_size(masks_of)
+        ex = self._expression_plan(expression, N, ids, 'animate')
         out_kind = "f32" if not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
         lo, hi = parallel.shard_range(N, self.rank, self.world)
         ids_dev = None if ids is None else ids[lo:hi].to(self.device)
@@ -919,9 +1076,12 @@ class InferenceWrapper:
         if smooth_pose and N > 0:
             theta = ops.pose_theta(*[t.to(self.device).float().contiguous() for t in target_srt])
             smoothed = self._pose_controls(theta, None if ids is None else ids.to(self.device), mix, mix_old, True)[lo:hi]
+        poses = None
+        if ex is not None and N > 0:
+            poses = self._expression_controls(target_pose_embeds, None if ids is None else ids.to(self.device), ex, 0)[lo:hi]
         for b0 in range(lo, hi, batch_size):
             b1 = min(b0 + batch_size, hi)
-            pose = target_pose_embeds[b0:b1].to(self.device).float().contiguous()
+            pose = target_pose_embeds[b0:b1].to(self.device).float().contiguous() if poses is None else poses[b0 - lo:b1 - lo]
             ident = None if ids is None else ids_dev[b0 - lo:b1 - lo]
             if smoothed is not None:
                 theta = smoothed[b0 - lo:b1 - lo]
@@ -1019,7 +1179,7 @@ class InferenceWrapper:
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
                        mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
                        paste_matte=None, as_uint8=True, refine=False, refine_masks=None, frame_format="rgb8", out_format=None,
-                       colorspace="bt709", full_range=False, faces=None):
+                       colorspace="bt709", full_range=False, faces=None, expression=None):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  Per batch, all on the device and without a host synchronisation:
             byte -> fp32 CHW (emo_unpack_rgb8) -> crop windows read in place + bicubic resize to image_size, the whole batch in
@@ -1095,7 +1255,23 @@ class InferenceWrapper:
             the faces of the whole stream; frames without a face yield nothing.  identities= is then one slot per FACE in
             that order, and mix / target_theta=False work per face.  smooth_pose needs identities= and smooth_per_identity=True
             (ValueError otherwise): every face track is its slot's stream.  Ranks shard by FRAMES and take the faces of their
-            frames; for smooth_pose the per-face thetas are gathered (parallel.gather_rows)."""
+            frames; for smooth_pose the per-face thetas are gathered (parallel.gather_rows).
+        expression: an ExpressionControls, or a mapping with its fields -- what happens to the expression vectors between the
+            expression embedder and the render, on the device, one launch per batch (ops.expression_controls; the contract is
+            hostglue.expression_controls, the reference has only the override, `custome_target_pose_embed`, infer.py:603-604).
+            A row is a frame, or a face with faces=.  relative: source expression + (driver_t - driver_first); gain (a float, or
+            one per row): the expression damped or exaggerated about the identity's source expression -- both work about the
+            source expression of the row's identity (its bank slot's, or the current identity's: what forward(source_image=) left
+            in pred_source_pose_embed; a missing one is a ValueError before anything is launched); offset ([E] or [rows,E]) is
+            added; smooth, momentum: the smooth_pose recurrence on the expression; override ([rows,E]) replaces the embedder's
+            output, and the embedder is then not run.  Order per batch: theta -> pose controls -> expression embedder or
+            override -> expression controls -> render.  relative and smooth are scans over the FRAME ORDER with smooth_pose's
+            rules: with identities= every row belongs to its slot's stream (anchor and EMA in the bank, reset by a new
+            identity in the slot, drop_identity and reset_expression_state), faces= then needs identities, and without
+            identities there is one stream whose state the wrapper carries from call to call.  The result does not depend on
+            batch_size, on the chunking or on the number of ranks: on one rank the state is carried from batch to batch, on
+            several the expressions of every rank's rows are gathered in row order (parallel.gather_rows) and scanned on every
+            rank before the render.  None, or all defaults: no launch, no state touched."""
         if isinstance(frames, torch.Tensor):
             frames_mod.check_frames(frames, frame_format)
         n_rows, counts = frames.shape[0] if isinstance(frames, torch.Tensor) else None, None
@@ -1117,17 +1293,18 @@ class InferenceWrapper:
             wins = None if windows is None else frames_mod.square_windows(windows)
         plan = self._video_plan(n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
                                 target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format,
-                                out_format, colorspace, full_range)
+                                out_format, colorspace, full_range, expression=expression, faces=faces is not None)
         yield from self._animate_clip(frames, wins, counts, plan)
 
     def _video_plan(self, n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
                     target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format,
-                    colorspace, full_range, arena=False):
+                    colorspace, full_range, arena=False, expression=None, where='animate_frames', faces=False):
         """The checks of the keywords animate_frames() and animate_streams() share, before anything is launched, and what their
         loops need beside the frames: wins = the (x0, y0, s, s) of every row of the call (None: whole frames), n_rows their
         number where it is known.  -> masks_of, ids (_preflight), matte_fn (_paste_matte), out_kind (_render's `out`), fmt =
         (frame_format, colorspace, full_range), ring = the pinned ring (None without to_host; with `arena` and paste_back a
-        frames.ArenaRing), upload_stream, and the loop's keywords as they came."""
+        frames.ArenaRing), upload_stream, ex = the expression controls (_expression_plan; None: none), and the loop's keywords as
+        they came."""
         frames_mod.check_format(frame_format, colorspace)
         if out_format is not None:
             frames_mod.check_format(out_format, colorspace, "out_format")
@@ -1153,15 +1330,18 @@ class InferenceWrapper:
         if out_format == "nv12" and as_uint8 and not paste_back:
             self._nv12_size(masks_of)
         out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
+        ex = self._expression_plan(expression, n_rows, ids, where, faces)
         host_ring = None if not to_host else (frames_mod.ArenaRing(self.device, ring) if arena and paste_back
                                               else frames_mod.HostRing(self.device, ring, batch_size))
         return Namespace(masks_of=masks_of, ids=ids, matte_fn=matte_fn, out_kind=out_kind, fmt=(frame_format, colorspace, bool(full_range)),
                          feather=feather, paste_back=paste_back, ring=host_ring, upload_stream=torch.cuda.Stream(device=self.device),
-                         batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta)
+                         batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta, ex=ex)
 
-    def _drive_crops(self, crops, ident, plan, theta=None, smooth=None):
+    def _drive_crops(self, crops, ident, plan, theta=None, smooth=None, row0=0, pose=None):
         """The sequence of one driver batch of the video paths, crops [m,3,S,S] -> (the rendered batch as plan.out_kind says, its
-        paste matte or None): head pose -> pose controls -> expression embedder -> render -> matte, in forward()'s order.
+        paste matte or None): head pose -> pose controls -> expression embedder (or the override) -> expression controls -> render
+        -> matte, in forward()'s order.  row0: the batch's first row in the call (the controls' per-row values); pose: the batch's
+        controlled expressions where a pass in front of the loop has formed them (a scan over the rows of several ranks).
         theta: the batch's thetas where a pass in front of the loop has formed them (the two-pass smooth_pose of a clip).
         smooth: None = mix alone, and only where it is asked for (a clip); a bool = mix and the one-pass smooth_pose of the
         batch's rows (streams)."""
@@ -1170,7 +1350,14 @@ class InferenceWrapper:
             if plan.mix or smooth is not None:
                 theta = self._pose_controls(theta, ident, plan.mix, plan.mix_old, bool(smooth))
         self.pred_target_theta = theta                                           # (as forward() leaves it: infer.py:584)
-        pose, _ = self._expression(crops, theta, 'a driver call')
+        ex = plan.ex
+        if pose is None:
+            if ex is not None and ex.override is not None:
+                pose = self._expression_rows(ex.override, row0, crops.shape[0], 'override')
+            else:
+                pose, _ = self._expression(crops, theta, 'a driver call')
+            if ex is not None:
+                pose = self._expression_controls(pose, ident, ex, row0)
         out = self._render(pose, theta, ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
         return out, (None if plan.matte_fn is None else plan.matte_fn(out).float().contiguous())
 
@@ -1180,7 +1367,7 @@ class InferenceWrapper:
         row (host tensor) or None.  counts=None is windows= / whole frames: one row per frame (wins None: the whole frame), the
         per-frame entry points (frame_of=None) and the single-stream smooth_pose.  Per chunk the frames are sharded across the
         ranks; a batch is a span of whole frames (frames.face_spans)."""
-        S, ids, paste_back = self.cfg["image_size"], plan.ids, plan.paste_back
+        S, ids, paste_back, ex = self.cfg["image_size"], plan.ids, plan.paste_back, plan.ex
         first = None if counts is None else frames_mod.face_offsets(counts)
         base = 0
         for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
@@ -1222,6 +1409,42 @@ class InferenceWrapper:
                 r0, r1 = rows(0, n)
                 ids_chunk = None if ids is None else ids[r0:r1].to(self.device)
                 smoothed = self._pose_controls(every, ids_chunk, False, plan.mix_old, True)[m_lo - r0:m_hi - r0]
+            poses, thetas = None, {}
+            if ex is not None and ex.scan and self.world > 1:
+                # relative / smooth walk the rows of every rank: the expressions of the rank's rows (the override's are known
+                # everywhere), gathered in row order and scanned on every rank, as the thetas above; then the render
+                r0, r1 = rows(0, n)
+                if ex.override is not None:
+                    every = self._expression_rows(ex.override, r0, r1 - r0, 'override')
+                else:
+                    keep_crops = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
+                    again = frames_mod.uploaded(chunk, [sp for sp in with_faces if sp[0] not in kept], self.device, plan.upload_stream)
+                    local = []
+                    for b0, b1 in with_faces:
+                        m0, m1 = rows(b0, b1)
+                        crops = kept.get(b0)
+                        if crops is None:
+                            crops = crops_of(next(again)[2], b0, b1)
+                            if keep_crops:
+                                kept[b0] = crops
+                        if smoothed is not None:
+                            theta = smoothed[m0 - m_lo:m1 - m_lo]
+                        else:
+                            theta = self._head_pose(crops)[0]
+                            if plan.mix:
+                                theta = self._pose_controls(theta, None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo], True,
+                                                            plan.mix_old, False)
+                            thetas[b0] = theta = theta.clone()
+                        local.append(self._expression(crops, theta, 'a driver call')[0].float().clone())
+                    if local:
+                        local = torch.cat(local)
+                    else:                                                        # (a rank without a row still joins the gather)
+                        E = self._bank_expr.shape[1] if self._bank_expr is not None else self.cfg["lpe_output_channels_expression"]
+                        local = torch.empty((0, E), device=self.device)
+                    per_rank = [rows(*parallel.shard_range(n, r, self.world)) for r in range(self.world)]
+                    every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)
+                ids_chunk = None if ids is None else ids[r0:r1].to(self.device)
+                poses = self._expression_controls(every, ids_chunk, ex, r0)[m_lo - r0:m_hi - r0]
             # (every span whose crops stayed resident from the head-pose pass needs no second upload -- unless its frames are
             # what the render is pasted into: the crops were kept, 3 MB per frame, not the frames, 6 MB at 1080p)
             todo = spans if paste_back else [sp for sp in with_faces if sp[0] not in kept]
@@ -1238,7 +1461,9 @@ class InferenceWrapper:
                     if crops is None:
                         crops = crops_of(u8, b0, b1)
                     ident = None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo]
-                    out, m = self._drive_crops(crops, ident, plan, None if smoothed is None else smoothed[m0 - m_lo:m1 - m_lo])
+                    theta = thetas.pop(b0, None) if smoothed is None else smoothed[m0 - m_lo:m1 - m_lo]
+                    out, m = self._drive_crops(crops, ident, plan, theta, row0=m0,
+                                               pose=None if poses is None else poses[m0 - m_lo:m1 - m_lo])
                     if paste_back:
                         full = u8.clone() if chunk.is_cuda else u8               # (a host chunk's upload is this span's own)
                         out = frames_mod.paste_into(full, out, wins_of(b0, b1), plan.feather, m, *plan.fmt, frame_of=frame_of(b0, b1))
@@ -1253,7 +1478,8 @@ class InferenceWrapper:
 
     def animate_streams(self, streams, batch_size=16, ring=3, to_host=True, smooth_pose=False, mix=False, mix_old=True,
                         target_theta=True, paste_back=False, feather=0.0625, paste_matte=None, as_uint8=True, refine=False,
-                        refine_masks=None, frame_format="rgb8", out_format=None, colorspace="bt709", full_range=False):
+                        refine_masks=None, frame_format="rgb8", out_format=None, colorspace="bt709", full_range=False,
+                        expression=None):
         """Several video streams of DIFFERENT frame sizes served by one driver batch: animate_frames(faces=) with the frames of a
         batch a list instead of one tensor.  Between the crop and the paste everything is one row per face, so only the two ends
         differ: ONE crop launch reads every face of the batch out of its own frame through a frame table
@@ -1264,7 +1490,12 @@ class InferenceWrapper:
             'frames': uint8 [N_s,H_s,W_s,3] (NV12: [N_s,3H_s/2,W_s]) or an iterable of such chunks, host (ideally pinned) or device;
             'windows': one (x_lo, y_lo, side) per frame, or 'faces': a list of them per frame in paste order ([]: no face); their
                 length is the stream's number of frames;
-            'identities' (optional, then in every stream): one bank slot for the stream, or one per face of the stream.
+            'identities' (optional, then in every stream): one bank slot for the stream, or one per face of the stream;
+            'expression' (optional): {'gain': a float or one per face of the stream, 'offset': [E] or one row per face}, in place
+                of the call's values for this stream.
+        expression: animate_frames' expression controls, here with the flags, the momentum, a scalar gain and an [E] offset (no
+            override); relative and smooth need identities, every face track is its slot's stream, scanned batch by batch in one
+            pass as smooth_pose is.  (With per-stream offsets a stream without one is given a zero offset.)
         Order: tick t takes frame t of every stream that still has one, in stream order (frames.interleave).  A batch is a run
         of whole frames of that sequence, taken greedily while it holds at most batch_size faces and at most batch_size frames
         (frames.face_spans; a frame with more faces: ValueError before anything is launched).
@@ -1307,9 +1538,11 @@ class InferenceWrapper:
         spans = frames_mod.face_spans(counts, 0, len(order), batch_size)
         wins = [w for s, t in order for w in faces[s][0][first[s][t]:first[s][t + 1]]]
         identities = None if not idents or idents[0] is None else [i for s, t in order for i in idents[s][first[s][t]:first[s][t + 1]]]
+        expression = self._stream_expression(expression, [st.get('expression') for st in streams], [len(flat) for flat, _ in faces],
+                                             [(s, first[s][t], first[s][t + 1]) for s, t in order])
         plan = self._video_plan(len(wins), wins, identities, batch_size, ring, to_host, smooth_pose, True, mix, mix_old, target_theta,
                                 paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format, colorspace,
-                                full_range, arena=True)
+                                full_range, arena=True, expression=expression, where='animate_streams')
         S, host_ring = self.cfg["image_size"], plan.ring
         ids_dev = None if plan.ids is None else plan.ids.to(self.device)
         rows = frames_mod.face_offsets(counts)                                   # rows[i] = faces in front of frame i of the order
@@ -1362,7 +1595,7 @@ class InferenceWrapper:
             out = None
             if m1 > m0:
                 crops = ops.crop_faces_mixed(frames, S, wins[m0:m1], frame_of, *plan.fmt)
-                out, m = self._drive_crops(crops, None if ids_dev is None else ids_dev[m0:m1], plan, smooth=smooth_pose)
+                out, m = self._drive_crops(crops, None if ids_dev is None else ids_dev[m0:m1], plan, smooth=smooth_pose, row0=m0)
                 if paste_back:
                     ops.paste_faces_mixed(frames, out, wins[m0:m1], frame_of, feather, m, *plan.fmt)
             if paste_back:
@@ -1378,6 +1611,50 @@ class InferenceWrapper:
             for tag, buf in host_ring.drain():
                 yield handed_out(tag, buf)
 
+    @staticmethod
+    def _stream_expression(expression, per_stream, n_faces, order):
+        """animate_streams' expression= and the streams' own 'expression' mappings -> the ExpressionControls of the call's rows:
+        per_stream[s] = stream s's {'gain', 'offset'} or None, n_faces[s] its faces, order = (stream, first face, end) of every
+        frame of the batch order.  Without a stream's own values the call's scalar gain and [E] offset stay as they are."""
+        ex = ExpressionControls.of(expression)
+        if ex is not None:
+            if ex.override is not None:
+                raise ValueError("expression override= replaces the expression embedder of animate_frames: animate_streams takes none")
+            if isinstance(ex.gain, torch.Tensor) and ex.gain.dim() > 0 or hasattr(ex.gain, '__len__') and not isinstance(ex.gain, torch.Tensor):
+                raise ValueError("animate_streams' expression gain is one float: per-face values belong to a stream's 'expression'")
+            if ex.offset is not None and torch.as_tensor(ex.offset).dim() != 1:
+                raise ValueError("animate_streams' expression offset is one [E] row: per-face rows belong to a stream's 'expression'")
+        if all(p is None for p in per_stream):
+            return ex
+        ex = ex or ExpressionControls()
+        gains, offsets = [], []
+        for s, p in enumerate(per_stream):
+            p = {} if p is None else dict(p)
+            unknown = sorted(set(p) - {'gain', 'offset'})
+            if unknown:
+                raise ValueError(f"stream {s}: its 'expression' takes 'gain' and 'offset', not {unknown[0]!r}")
+            g = torch.as_tensor(p.get('gain', ex.gain)).detach().float()
+            if g.dim() > 1 or g.dim() == 1 and g.shape[0] != n_faces[s]:
+                raise ValueError(f"stream {s}: expression gain {tuple(g.shape)} is not a float or one per face ({n_faces[s]})")
+            gains.append(g.expand(n_faces[s]))
+            o = p.get('offset', ex.offset)
+            if o is not None:
+                o = torch.as_tensor(o).detach().float()
+                if o.dim() not in (1, 2) or o.dim() == 2 and o.shape[0] != n_faces[s]:
+                    raise ValueError(f"stream {s}: expression offset {tuple(o.shape)} is not [E] or one row per face ({n_faces[s]})")
+                o = o.expand(n_faces[s], o.shape[-1])
+            offsets.append(o)
+        widths = {o.shape[1] for o in offsets if o is not None}
+        if len(widths) > 1:
+            raise ValueError(f"expression offsets of different widths: {sorted(widths)}")
+        if widths:
+            E = widths.pop()
+            offsets = [torch.zeros((n_faces[s], E)) if o is None else o for s, o in enumerate(offsets)]
+        gain = torch.cat([gains[s][a:b] for s, a, b in order]) if order else torch.zeros(0)
+        offset = torch.cat([offsets[s][a:b] for s, a, b in order]) if order and offsets[0] is not None else None
+        return ExpressionControls(relative=ex.relative, smooth=ex.smooth, momentum=ex.momentum, offset=offset,
+                                  gain=gain if bool((gain != 1.0).any()) else 1.0)
+
     def share_source(self, src_rank=0):
         """RCCL broadcast of the per-identity cache computed on `src_rank`: canonical volume
         (25 MB) + idt_embed (32 KB) + source theta."""
@@ -1385,12 +1662,16 @@ class InferenceWrapper:
         # idt_embed is [1, idt_output_channels, idt_output_size, idt_output_size] of the checkpoint's embedder config: the
         # receivers learn its shape from the broadcast header; what the warp embedding needs is checked on the source rank
         es = self.cfg["gen_embed_size"]
+        # the source expression (the expression controls' neutral) travels with it; an identity without one sends an empty row
+        expr = self.pred_source_pose_embed
+        expr = torch.zeros((1, 0), device=self.device) if expr is None else expr.reshape(1, -1)
         cache = parallel.broadcast_source_cache(
-            dict(canonical=self.target_latent_volume, idt_embed=self.idt_embed, theta_src=self.pred_source_theta),
-            shapes=dict(canonical=(1, c, d, s, s), theta_src=(1, 4, 4)), names=['canonical', 'idt_embed', 'theta_src'],
+            dict(canonical=self.target_latent_volume, idt_embed=self.idt_embed, theta_src=self.pred_source_theta, expr_src=expr),
+            shapes=dict(canonical=(1, c, d, s, s), theta_src=(1, 4, 4)), names=['canonical', 'idt_embed', 'theta_src', 'expr_src'],
             src=src_rank, device=self.device, world=self.world, rank=self.rank)
         if cache["idt_embed"].numel() != self.cfg["gen_max_channels"] * es * es:
             raise RuntimeError(f"idt_embed {tuple(cache['idt_embed'].shape)} does not match the warp embedding "
                                f"({self.cfg['gen_max_channels']} channels x {es}x{es})")
         self.pred_source_theta = cache["theta_src"]
+        self.pred_source_pose_embed = cache["expr_src"].clone() if cache["expr_src"].numel() else None
         self._set_source_cache(canonical=cache["canonical"], idt_embed=cache["idt_embed"])

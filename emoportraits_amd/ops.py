@@ -1186,3 +1186,63 @@ def theta_ema_scan(values, stream_of, state, has_state, momentum):
     hip.check(lib.emo_theta_ema_scan_f32(hip.ptr(values), hip.ptr(stream_of), hip.ptr(state), hip.ptr(has_state), n, K, m, om,
                                          hip.ptr(out), hip.current_stream()), "emo_theta_ema_scan_f32")
     return out
+
+
+def expression_controls(values, stream_of=None, neutral=None, gain=None, offset=None, anchor=None, has_anchor=None, ema=None,
+                        has_ema=None, relative=False, momentum=None, out=None):
+    """The expression controls of the batched entry points on the device (emo_expr_controls_f32; bit for bit
+    hostglue.expression_controls, which states the arithmetic): values [n,E] IN FRAME ORDER, stream_of int32 [n] (or None: one
+    stream, 0), neutral [K,E] or None, gain a float or [n] or None, offset [E] or [n,E] or None -- a scalar gain and an [E]
+    offset are broadcast to the rows here; anchor, ema [K,E] and has_anchor, has_ema int32 [K] are the streams' states, updated
+    in place; momentum None = no smoothing (else 1 - momentum is rounded to fp32 once, as in theta_ema_scan).  -> [n,E]
+    (`out`, which may be `values`, or a new tensor).  One launch, no host synchronisation."""
+    import numpy as np
+    lib = hip.load()
+    hip.require_cuda_f32(values, neutral, offset, anchor, ema, out)
+    if values.dim() != 2 or values.shape[0] == 0 or values.shape[1] == 0:
+        raise ValueError(f"expression_controls expects [n,E] values, got {tuple(values.shape)}")
+    n, E = values.shape
+    dev = values.device
+    smooth = momentum is not None
+    if (relative or gain is not None) and neutral is None:
+        raise ValueError("expression_controls: relative transfer and gain need neutral")
+    if relative and (anchor is None or has_anchor is None):
+        raise ValueError("expression_controls: relative transfer needs anchor and has_anchor")
+    if smooth and (ema is None or has_ema is None):
+        raise ValueError("expression_controls: smoothing needs ema and has_ema")
+    if smooth and not 0.0 < float(momentum) <= 1.0:
+        raise ValueError(f"expression_controls: momentum {momentum} is not in (0, 1]")
+    banks = [t for t in (neutral, anchor if relative else None, ema if smooth else None) if t is not None]
+    K = banks[0].shape[0] if banks else 1
+    for t in banks:
+        if t.dim() != 2 or tuple(t.shape) != (K, E) or K == 0:
+            raise ValueError(f"expression_controls: neutral, anchor and ema must be [K,{E}], got {tuple(t.shape)}")
+    if relative:
+        _check_index(has_anchor, K, dev, "has_anchor")
+    if smooth:
+        _check_index(has_ema, K, dev, "has_ema")
+    if stream_of is not None:
+        _check_index(stream_of, n, dev, "stream_of")
+    if gain is not None:
+        if isinstance(gain, torch.Tensor) and gain.dim() == 1:
+            hip.require_cuda_f32(gain)
+            if gain.shape[0] != n:
+                raise ValueError(f"expression_controls: gain has {gain.shape[0]} entries for {n} rows")
+        else:
+            gain = torch.full((n,), float(gain), dtype=torch.float32, device=dev)
+    if offset is not None:
+        if offset.dim() == 1 and offset.shape[0] == E:
+            offset = offset.expand(n, E).contiguous()
+        elif tuple(offset.shape) != (n, E):
+            raise ValueError(f"expression_controls: offset must be [{E}] or [{n},{E}], got {tuple(offset.shape)}")
+    if out is None:
+        out = torch.empty_like(values)
+    elif tuple(out.shape) != (n, E):
+        raise ValueError(f"expression_controls: out must be [{n},{E}], got {tuple(out.shape)}")
+    m, om = (float(np.float32(momentum)), float(np.float32(1 - momentum))) if smooth else (0.0, 0.0)
+    hip.check(lib.emo_expr_controls_f32(hip.ptr(values), hip.ptr(stream_of), hip.ptr(neutral), hip.ptr(gain), hip.ptr(offset),
+                                        hip.ptr(anchor if relative else None), hip.ptr(has_anchor if relative else None),
+                                        hip.ptr(ema if smooth else None), hip.ptr(has_ema if smooth else None), n, K, E,
+                                        int(bool(relative)), int(smooth), m, om, hip.ptr(out), hip.current_stream()),
+              "emo_expr_controls_f32")
+    return out

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 19
+#define EMO_ABI_VERSION 20
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -472,6 +472,24 @@ int emo_mixing_theta_f32(const float* target, const float* source, const int32_t
  * A stream index outside [0, K) leaves its frames unwritten. */
 int emo_theta_ema_scan_f32(const float* values, const int32_t* stream_of, float* state, int32_t* has_state, int n, int K, float m,
                            float om, float* out, void* stream);
+/* ABI 20.  The expression controls of the batched entry points: relative transfer and gain about each identity's source
+ * expression, an additive offset and an EMA, per stream and in row order.  Row i (values [n,E], frame order) belongs to stream
+ * k = stream_of[i] ([n] int32 DEVICE memory, or NULL: stream 0).  neutral [K,E] or NULL, gain [n] or NULL, offset [n,E] or NULL;
+ * anchor and ema [K,E] with their flags has_anchor and has_ema [K] int32 are read and written; out [n,E] may be `values`.
+ * For every element j, within a stream in row order, every operation fp32 and rounded on its own:
+ *   e = values[i,j]
+ *   if neutral:  r = neutral[k,j], or with `relative` anchor[k,j] -- which a stream without anchor takes from its first row
+ *                (anchor[k,j] = e, has_anchor[k] = 1 afterwards);  t = e - r;  if gain: t = t * gain[i];  e = neutral[k,j] + t
+ *   if offset:   e = e + offset[i,j]
+ *   if smooth:   a stream without EMA starts at cur = e; then a = e * m, b = cur * om, cur = a + b, e = cur as
+ *                emo_theta_ema_scan_f32 (ema[k,j] = cur, has_ema[k] = 1 afterwards), om = fp32(1 - momentum) formed by the caller
+ *   out[i,j] = e
+ * -- bit for bit hostglue.expression_controls.  A stream index outside [0, K) leaves its row unwritten and touches no state.
+ * EMO_ERR_BAD_ARG before any launch: values or out NULL; n, K or E <= 0; relative or gain without neutral; relative without
+ * anchor and has_anchor; smooth without ema and has_ema.  One block per stream, no atomics. */
+int emo_expr_controls_f32(const float* values, const int32_t* stream_of, const float* neutral, const float* gain,
+                          const float* offset, float* anchor, int32_t* has_anchor, float* ema, int32_t* has_ema, int n, int K,
+                          int E, int relative, int smooth, float m, float om, float* out, void* stream);
 int emo_pack_rgb8(const float* img, uint8_t* out, int N, int H, int W, void* stream);
 int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int W, void* stream);
 

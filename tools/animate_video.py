@@ -82,6 +82,12 @@ def main():
     ap.add_argument("--mix-new", action="store_true", help="with --mix: the reference's mix_old=False formula")
     ap.add_argument("--source-pose", action="store_true", help="render in the source's own head pose (target_theta=False)")
     ap.add_argument("--smooth-pose", action="store_true", help="EMA over the driver head poses (smooth_pose=True)")
+    ap.add_argument("--relative-expression", action="store_true",
+                    help="relative expression transfer: source expression + (driver_t - driver_first)")
+    ap.add_argument("--expression-gain", type=float, default=1.0, help="damp (< 1) or exaggerate (> 1) the expression about the source's")
+    ap.add_argument("--expression-offset", default=None, help="a .pt file with an [E] row, or one row per frame (face), added to the expression")
+    ap.add_argument("--smooth-expression", action="store_true", help="EMA over the expression vectors (see --expression-momentum)")
+    ap.add_argument("--expression-momentum", type=float, default=None, help="with --smooth-expression: 0 < M <= 1 (default 0.5)")
     ap.add_argument("--paste-back", action="store_true", help="write the full frames with the rendered crops pasted back (needs --windows or --faces)")
     ap.add_argument("--feather", type=float, default=0.0625, help="with --paste-back: blended edge as a fraction of the window side")
     ap.add_argument("--stage2-experiment", default=None, help="refine with the stage-2 model <project>/logs_s2/<this>")
@@ -112,6 +118,13 @@ def main():
         ap.error("--sources (the images of the bank's slots) and --identities (the slot of every face or frame) go together")
     if a.smooth_pose and a.faces and not a.identities:
         ap.error("--smooth-pose with --faces smooths every face track as its identity's stream: it needs --sources / --identities")
+    if a.expression_momentum is not None and not a.smooth_expression:
+        ap.error("--expression-momentum belongs to --smooth-expression")
+    if a.expression_momentum is not None and not 0.0 < a.expression_momentum <= 1.0:
+        ap.error("--expression-momentum: 0 < M <= 1")
+    if (a.relative_expression or a.smooth_expression) and a.faces and not a.identities:
+        ap.error("--relative-expression / --smooth-expression with --faces follow every face track as its identity's stream: "
+                 "they need --sources / --identities")
     sources = a.sources.split(",") if a.sources else []
     refine = a.stage2_experiment is not None
     if refine and (a.stage2_checkpoint is None or (a.embedders is None) == (not a.refine_everywhere)):
@@ -148,6 +161,9 @@ def main():
     if sources:
         w.enrol_identities([Image.open(f).convert("RGB") for f in sources], slots=list(range(len(sources))), batch_size=a.batch)
         identities = json.load(open(a.identities))
+    expression = dict(relative=a.relative_expression, gain=a.expression_gain, smooth=a.smooth_expression,
+                      momentum=0.5 if a.expression_momentum is None else a.expression_momentum,
+                      offset=None if a.expression_offset is None else torch.load(a.expression_offset, map_location="cpu"))
     t0, n = time.perf_counter(), 0
     if nv12:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -162,7 +178,7 @@ def main():
     for first, u8 in w.animate_frames(frames, batch_size=a.batch, windows=windows, faces=faces, identities=identities, mix=a.mix,
                                       mix_old=not a.mix_new, target_theta=not a.source_pose, smooth_pose=a.smooth_pose,
                                       smooth_per_identity=identities is not None, paste_back=a.paste_back,
-                                      feather=a.feather, refine=refine, refine_masks=refine_masks, **fmt):
+                                      feather=a.feather, refine=refine, refine_masks=refine_masks, expression=expression, **fmt):
         arr = u8.numpy()
         if nv12:
             sink.write(arr.tobytes())                             # batches come in frame order (one rank)
