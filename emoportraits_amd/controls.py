@@ -33,3 +33,36 @@ class ExpressionControls:
                 raise ValueError(f"expression= has no field {unknown[0]!r}")
             return cls(**value)
         raise ValueError("expression= takes an ExpressionControls or a mapping with its fields")
+
+
+@dataclasses.dataclass
+class HeadPoseControls:
+    """The `head_pose=` keyword of InferenceWrapper.animate / animate_frames / animate_streams: what happens to the driver's
+    head pose -- the (scale, rotation, translation) the head-pose regressor returns -- before theta is formed, on the device
+    (ops.head_pose_controls).  A row is a frame, or a face with faces=.
+    relative: source pose + (driver_t - driver_first): the avatar keeps its own head pose and follows the driver's head motion.
+    gain: a float, or one value per row -- damps (< 1) or exaggerates (> 1) rotation and translation about the identity's source pose.
+    rotation_offset: [3] or [rows,3], yaw, pitch, roll in radians, added to the rotation (the reference's delta_yaw / delta_pitch,
+        expression_embedder.py:302-316, plus roll).
+    translation_offset: [3] or [rows,3], added to the translation.
+    zoom: a float, or one value per row, multiplies the scale.
+    frontal: the reference's `normalize`: yaw = pitch = 0 and translation = 0; roll and scale stay the driver's.
+    All defaults = no control: nothing is launched and no state is touched."""
+    relative: bool = False
+    gain: object = 1.0
+    rotation_offset: object = None
+    translation_offset: object = None
+    zoom: object = 1.0
+    frontal: bool = False
+
+    @classmethod
+    def of(cls, value):
+        """None | HeadPoseControls | a mapping with the same fields -> HeadPoseControls or None"""
+        if value is None or isinstance(value, cls):
+            return value
+        if isinstance(value, Mapping):
+            unknown = sorted(set(value) - {f.name for f in dataclasses.fields(cls)})
+            if unknown:
+                raise ValueError(f"head_pose= has no field {unknown[0]!r}")
+            return cls(**value)
+        raise ValueError("head_pose= takes a HeadPoseControls or a mapping with its fields")

@@ -62,25 +62,25 @@ __global__ __launch_bounds__(256) void projector_finalize_kernel(const float* __
   ab[i] = beta[c] + db;
 }
 
-// utils/point_transforms.py:188-242 get_transform_matrix: theta = S @ R @ T  (one thread per sample)
-__global__ void pose_theta_kernel(const float* __restrict__ scale, int scale_cols, const float* __restrict__ rotation,
-                                  const float* __restrict__ translation, float* __restrict__ theta, int B) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const float sx = scale[b * scale_cols], sy = scale_cols == 3 ? scale[b * 3 + 1] : sx,
-              sz = scale_cols == 3 ? scale[b * 3 + 2] : sx;
+// the rotation clamp of get_transform_matrix (utils/point_transforms.py:188-242) and of ExpressionEmbed.forward_image
+// (expression_embedder.py:302-316): [-pi/2, pi] in fp32
+__device__ __forceinline__ float pose_clamp_angle(float v) {
   const float kPi = 3.14159265358979323846f;
-  auto clampf = [](float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); };
-  const float yaw = clampf(rotation[b * 3 + 0], -kPi / 2, kPi), pitch = clampf(rotation[b * 3 + 1], -kPi / 2, kPi),
-              roll = clampf(rotation[b * 3 + 2], -kPi / 2, kPi);
+  const float lo = -kPi / 2, hi = kPi;
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+
+// utils/point_transforms.py:188-242 get_transform_matrix: theta = S @ R @ T of one sample -> o[16]
+__device__ __forceinline__ void pose_theta_row(float sx, float sy, float sz, float yaw_in, float pitch_in, float roll_in, float t0,
+                                               float t1, float t2, float* __restrict__ o) {
+  const float yaw = pose_clamp_angle(yaw_in), pitch = pose_clamp_angle(pitch_in), roll = pose_clamp_angle(roll_in);
   const float yc = cosf(yaw), ys = sinf(yaw), pc = cosf(pitch), ps = sinf(pitch), rc = cosf(roll), rs = sinf(roll);
   float R[3][3];
   R[0][0] = yc * pc;  R[0][1] = yc * ps * rs - ys * rc;  R[0][2] = yc * ps * rc + ys * rs;
   R[1][0] = ys * pc;  R[1][1] = ys * ps * rs + yc * rc;  R[1][2] = ys * ps * rc - yc * rs;
   R[2][0] = -ps;      R[2][1] = pc * rs;                 R[2][2] = pc * rc;
   const float S[3] = {sx, sy, sz};
-  const float t[3] = {translation[b * 3], translation[b * 3 + 1], translation[b * 3 + 2]};
-  float* o = theta + (long)b * 16;
+  const float t[3] = {t0, t1, t2};
   for (int i = 0; i < 3; ++i) {
     float row[3];
     for (int j = 0; j < 3; ++j) { row[j] = S[i] * R[i][j]; o[i * 4 + j] = row[j]; }
@@ -88,6 +88,17 @@ __global__ void pose_theta_kernel(const float* __restrict__ scale, int scale_col
     o[i * 4 + 3] = row[0] * t[0] + row[1] * t[1] + row[2] * t[2];
   }
   o[12] = 0.0f; o[13] = 0.0f; o[14] = 0.0f; o[15] = 1.0f;
+}
+
+// one thread per sample
+__global__ void pose_theta_kernel(const float* __restrict__ scale, int scale_cols, const float* __restrict__ rotation,
+                                  const float* __restrict__ translation, float* __restrict__ theta, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float sx = scale[b * scale_cols], sy = scale_cols == 3 ? scale[b * 3 + 1] : sx,
+              sz = scale_cols == 3 ? scale[b * 3 + 2] : sx;
+  pose_theta_row(sx, sy, sz, rotation[b * 3 + 0], rotation[b * 3 + 1], rotation[b * 3 + 2], translation[b * 3],
+                 translation[b * 3 + 1], translation[b * 3 + 2], theta + (long)b * 16);
 }
 
 // notebooks/infer.py:641-644: img.clamp(0,1) -> ToPILImage (mul(255).byte(), i.e. truncation) -> HWC uint8
@@ -397,6 +408,76 @@ __global__ __launch_bounds__(128) void expr_controls_kernel(const float* values,
   }
 }
 
+// The head-pose controls of the batched entry points (include/emo_hip.h, ABI 21; hostglue.head_pose_controls is the contract):
+// the regressed (scale, rotation, translation) of every row edited before theta is formed -- frontal, relative transfer and gain
+// about the identity's source pose, offsets, zoom.  One block per stream.  Only the anchor depends on the row order: every
+// thread reads the stream's flag, then the barrier; a stream without an anchor takes it from its first row (every thread finds
+// that row for itself and holds the anchor in registers, thread 0 stores it); then the threads take the stream's rows strided
+// by blockDim.x, a whole row each: nine floats in, nine floats and theta's sixteen out.  The block's LAST thread alone writes the
+// flag, at its end (a host build that runs thread after thread reaches it last as well).  The outputs alias no input.
+__global__ __launch_bounds__(64) void head_pose_controls_kernel(
+    const float* __restrict__ scale, int scale_cols, const float* __restrict__ rotation, const float* __restrict__ translation,
+    const int* __restrict__ stream_of, const float* __restrict__ source, const float* __restrict__ gain,
+    const float* __restrict__ rotation_offset, const float* __restrict__ translation_offset, const float* __restrict__ zoom,
+    float* anchor, int* has_anchor, int n, int relative, int frontal, float* __restrict__ out_srt, float* __restrict__ out_theta) {
+  const int k = blockIdx.x;
+  const bool had_anchor = relative && has_anchor[k] != 0;
+  __syncthreads();
+  // step 0 of row i: the scale in three columns, the rotation clamped, the translation
+  auto load = [&](int i, float* p) {
+    p[0] = scale[(long)i * scale_cols];
+    p[1] = scale_cols == 3 ? scale[(long)i * 3 + 1] : p[0];
+    p[2] = scale_cols == 3 ? scale[(long)i * 3 + 2] : p[0];
+    for (int j = 0; j < 3; ++j) {
+      p[3 + j] = pose_clamp_angle(rotation[(long)i * 3 + j]);
+      p[6 + j] = translation[(long)i * 3 + j];
+    }
+  };
+  float q[9], ref[9];
+  if (source) {
+    for (int j = 0; j < 9; ++j) q[j] = source[(long)k * 9 + j];
+    for (int j = 3; j < 6; ++j) q[j] = pose_clamp_angle(q[j]);
+    for (int j = 0; j < 9; ++j) ref[j] = q[j];
+  }
+  int first = n;
+  if (relative) {
+    if (had_anchor) {
+      for (int j = 0; j < 9; ++j) ref[j] = anchor[(long)k * 9 + j];
+    } else {
+      for (int i = 0; i < n && first == n; ++i)
+        if ((stream_of ? stream_of[i] : 0) == k) first = i;
+      if (first < n) {
+        load(first, ref);
+        if (threadIdx.x == 0)
+          for (int j = 0; j < 9; ++j) anchor[(long)k * 9 + j] = ref[j];
+      }
+    }
+  }
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    if ((stream_of ? stream_of[i] : 0) != k) continue;
+    float p[9];
+    load(i, p);
+    if (frontal) { p[3] = 0.0f; p[4] = 0.0f; p[6] = 0.0f; p[7] = 0.0f; p[8] = 0.0f; }
+    if (source) {
+      for (int j = 3; j < 9; ++j) {
+        float d = p[j] - ref[j];
+        if (gain) d = d * gain[i];
+        p[j] = q[j] + d;
+      }
+      if (relative)
+        for (int j = 0; j < 3; ++j) p[j] = q[j] * __fdiv_rn(p[j], ref[j]);
+    }
+    for (int j = 0; j < 3; ++j) {
+      if (rotation_offset) p[3 + j] = p[3 + j] + rotation_offset[(long)i * 3 + j];
+      if (translation_offset) p[6 + j] = p[6 + j] + translation_offset[(long)i * 3 + j];
+      if (zoom) p[j] = p[j] * zoom[i];
+    }
+    for (int j = 0; j < 9; ++j) out_srt[(long)i * 9 + j] = p[j];
+    pose_theta_row(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], out_theta + (long)i * 16);
+  }
+  if (threadIdx.x == blockDim.x - 1 && relative && !had_anchor && first < n) has_anchor[k] = 1;
+}
+
 }  // namespace
 
 extern "C" int emo_small_gemm_f32(const float* A, const float* B, float* C, int M, int K, int NN, int batch,
@@ -486,5 +567,21 @@ extern "C" int emo_expr_controls_f32(const float* values, const int32_t* stream_
   const int threads = E >= 128 ? 128 : emo_cdiv(E, 64) * 64;
   hipLaunchKernelGGL(expr_controls_kernel, dim3(K), dim3(threads), 0, (hipStream_t)stream, values, stream_of, neutral, gain, offset,
                      anchor, has_anchor, ema, has_ema, n, E, relative ? 1 : 0, smooth ? 1 : 0, m, om, out);
+  return emo_launch_status();
+}
+
+extern "C" int emo_head_pose_controls_f32(const float* scale, int scale_cols, const float* rotation, const float* translation,
+                                          const int32_t* stream_of, const float* source, const float* gain,
+                                          const float* rotation_offset, const float* translation_offset, const float* zoom,
+                                          float* anchor, int32_t* has_anchor, int n, int K, int relative, int frontal,
+                                          float* out_srt, float* out_theta, void* stream) {
+  if (!scale || !rotation || !translation || !out_srt || !out_theta || n <= 0 || K <= 0) return EMO_ERR_BAD_ARG;
+  if (scale_cols != 1 && scale_cols != 3) return EMO_ERR_BAD_ARG;
+  if ((relative || gain) && !source) return EMO_ERR_BAD_ARG;
+  if (relative && (!anchor || !has_anchor)) return EMO_ERR_BAD_ARG;
+  if (relative && frontal) return EMO_ERR_BAD_ARG;
+  hipLaunchKernelGGL(head_pose_controls_kernel, dim3(K), dim3(64), 0, (hipStream_t)stream, scale, scale_cols, rotation, translation,
+                     stream_of, source, gain, rotation_offset, translation_offset, zoom, anchor, has_anchor, n, relative ? 1 : 0,
+                     frontal ? 1 : 0, out_srt, out_theta);
   return emo_launch_status();
 }

@@ -65,6 +65,7 @@ SIGNATURES = {
     "emo_mixing_theta_f32": [_c_void, _c_void, _c_void, _c_int, _c_int, _c_int, _c_void, _c_void],
     "emo_theta_ema_scan_f32": [_c_void] * 4 + [_c_int, _c_int, _c_float, _c_float, _c_void, _c_void],
     "emo_expr_controls_f32": [_c_void] * 9 + [_c_int] * 5 + [_c_float, _c_float, _c_void, _c_void],
+    "emo_head_pose_controls_f32": [_c_void, _c_int] + [_c_void] * 10 + [_c_int] * 4 + [_c_void] * 3,
     "emo_mul_mask_f32": [_c_void, _c_void, _c_void, _c_int, _c_int, _c_i64, _c_void],
     "emo_stage2_compose_f32": [_c_void] * 5 + [_c_int, _c_int, _c_i64, _c_void],
     "emo_small_gemm_f32": [_c_void] * 3 + [_c_int] * 4 + [_c_i64, _c_i64, _c_void],

@@ -181,6 +181,100 @@ def expression_controls(values, stream_of, neutral, gain, offset, anchor, has_an
     return out
 
 
+_POSE_CLAMP = (np.float32(-np.float32(3.14159265358979323846) / np.float32(2)), np.float32(3.14159265358979323846))
+
+
+def srt_theta(srt):
+    """get_transform_matrix (utils/point_transforms.py:188-242) of rows [n,9] = [scale | yaw pitch roll | translation] in
+    float64 -> theta [n,4,4] float64 = S R T, the rotation clamped to [-pi/2, pi]: what emo_pose_theta_f32 forms in fp32"""
+    p = np.asarray(srt, dtype=np.float64).reshape(-1, 9)
+    out = np.zeros((p.shape[0], 4, 4))
+    for i, r in enumerate(p):
+        yaw, pitch, roll = np.clip(r[3:6], -np.pi / 2, np.pi)
+        yc, ys, pc, ps, rc, rs = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
+        R = np.array([[yc * pc, yc * ps * rs - ys * rc, yc * ps * rc + ys * rs],
+                      [ys * pc, ys * ps * rs + yc * rc, ys * ps * rc - yc * rs],
+                      [-ps, pc * rs, pc * rc]])
+        SR = np.diag(r[0:3]) @ R
+        out[i, :3, :3] = SR
+        out[i, :3, 3] = SR @ r[6:9]
+        out[i, 3, 3] = 1.0
+    return out
+
+
+def head_pose_controls(scale, rotation, translation, stream_of, source, gain, rotation_offset, translation_offset, zoom, anchor,
+                       has_anchor, relative, frontal, K=None):
+    """The head-pose controls of the batched entry points on the host, one row after another -- the contract that
+    emo_head_pose_controls_f32 (ops.head_pose_controls) is held to bit for bit.  frontal and the rotation offsets are the
+    reference's `normalize`, `delta_yaw` and `delta_pitch` (ExpressionEmbed.forward_image, expression_embedder.py:302-316: the
+    rotation clamped to [-pi/2, pi], yaw = pitch = 0 and translation = 0, then the deltas added); the rest has no counterpart
+    there.  scale [n,1] or [n,3] (one column is broadcast to three), rotation and translation [n,3], frame order; stream_of [n]
+    ints or None (every row: stream 0); source [K,9] or None; gain, zoom [n] or None; rotation_offset, translation_offset [n,3]
+    or None; anchor [K,9] and has_anchor [K] are the streams' state, UPDATED IN PLACE (numpy arrays; None without `relative`);
+    K: the number of streams where neither source nor anchor says it (default 1).
+    A row is p = [sx sy sz | yaw pitch roll | tx ty tz]; row i of stream k, every operation in fp32 and rounded on its own:
+        0. p.rot = clamp(p.rot, -pi/2, pi), the fp32 constants of emo_pose_theta_f32
+        1. frontal:  yaw = pitch = 0, p.trans = 0
+        2. with source:  q = source[k], q.rot clamped;  ref = q, or with `relative` the stream's anchor (its first row after
+           step 0);  p.rot = q.rot + (p.rot - ref.rot) * gain[i],  p.trans = q.trans + (p.trans - ref.trans) * gain[i] (no
+           product without gain);  with `relative` only:  p.scale = q.scale * (p.scale / ref.scale)
+        3. p.rot += rotation_offset[i];  p.trans += translation_offset[i];  p.scale *= zoom[i]  (each where given)
+    -> (rows [n,9] fp32, theta [n,4,4] = srt_theta(rows) rounded to fp32); a row whose stream lies outside [0, K) is left
+    unwritten (NaN here) and touches no state."""
+    f32 = lambda a: None if a is None else np.asarray(a, dtype=np.float32)
+    scale, rotation, translation = (np.ascontiguousarray(a, dtype=np.float32) for a in (scale, rotation, translation))
+    if scale.ndim != 2 or scale.shape[1] not in (1, 3) or rotation.shape != (scale.shape[0], 3) or translation.shape != rotation.shape:
+        raise ValueError(f"scale [n,1] or [n,3], rotation and translation [n,3]: got {scale.shape}, {rotation.shape}, {translation.shape}")
+    if relative and frontal:
+        raise ValueError("frontal zeroes what relative transfers")
+    if (relative or gain is not None) and source is None:
+        raise ValueError("relative transfer and gain work about a source pose: source is missing")
+    if relative and (anchor is None or has_anchor is None):
+        raise ValueError("relative transfer needs anchor and has_anchor")
+    K = next((a.shape[0] for a in (source, anchor) if a is not None), 1 if K is None else K)
+    source, gain, zoom = f32(source), f32(gain), f32(zoom)
+    rotation_offset, translation_offset = f32(rotation_offset), f32(translation_offset)
+    lo, hi = _POSE_CLAMP
+    n = scale.shape[0]
+    out = np.full((n, 9), np.nan, np.float32)
+    for i in range(n):
+        k = 0 if stream_of is None else int(stream_of[i])
+        if not 0 <= k < K:
+            continue
+        p = np.empty(9, np.float32)
+        p[0:3] = scale[i]
+        p[3:6] = np.clip(rotation[i], lo, hi)
+        p[6:9] = translation[i]
+        if relative and not has_anchor[k]:
+            anchor[k] = p
+            has_anchor[k] = 1
+        if frontal:
+            p[3] = p[4] = 0.0
+            p[6:9] = 0.0
+        if source is not None:
+            q = source[k].copy()
+            q[3:6] = np.clip(q[3:6], lo, hi)
+            ref = anchor[k] if relative else q
+            d = p[3:9] - ref[3:9]
+            if gain is not None:
+                d = d * gain[i]
+            if relative:
+                p[0:3] = q[0:3] * (p[0:3] / ref[0:3])
+            p[3:9] = q[3:9] + d
+        if rotation_offset is not None:
+            p[3:6] = p[3:6] + rotation_offset[i]
+        if translation_offset is not None:
+            p[6:9] = p[6:9] + translation_offset[i]
+        if zoom is not None:
+            p[0:3] = p[0:3] * zoom[i]
+        out[i] = p
+    theta = np.full((n, 4, 4), np.nan, np.float32)
+    done = np.ones(n, dtype=bool) if stream_of is None else np.array([0 <= int(k) < K for k in stream_of], dtype=bool)
+    if done.any():
+        theta[done] = srt_theta(out[done]).astype(np.float32)
+    return out, theta
+
+
 def bank_slot(slot, capacity):
     """a slot of an identity bank of `capacity` slots as an int; ValueError unless it is an integer (not a bool) in range"""
     import operator

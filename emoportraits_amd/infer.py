@@ -38,7 +38,7 @@ from . import config as cfg_mod
 from . import embedders as emb_mod
 from . import frames as frames_mod
 from . import graphs, hostglue, nets, ops, parallel, schema
-from .controls import ExpressionControls
+from .controls import ExpressionControls, HeadPoseControls
 
 
 # smooth_pose in animate_frames: the crops of a rank's shard stay resident between the head-pose pass and the render pass up to
@@ -195,6 +195,9 @@ class InferenceWrapper:
         # the current identity's source expression (the expression controls' neutral) and, without a bank, the one stream's
         # relative-transfer anchor and expression EMA ([E], None before the first row), carried from call to call as self.theta
         self.pred_source_pose_embed = self._expr_anchor = self._expr_ema = None
+        # the current identity's source (scale, rotation, translation) as one [1,9] row (the head-pose controls' source pose; None
+        # where the source theta came as a 4x4 matrix) and, without a bank, the one stream's relative-pose anchor ([9])
+        self.pred_source_srt = self._pose_anchor = None
         self._stage2 = self._stage2_wrapper = None                                 # attach_stage2()
         self._init_identity_bank(identity_capacity)
 
@@ -252,6 +255,10 @@ class InferenceWrapper:
         # expression [K,E] and which slots have one, the relative-transfer anchor and the expression EMA [K,E] with their flags
         self._bank_expr = self._bank_expr_anchor = self._bank_expr_anchor_has = self._bank_expr_ema = self._bank_expr_ema_has = None
         self._bank_expr_has = [False] * capacity
+        # the head-pose controls' per-slot data: the source (scale, rotation, translation) [K,9] and which slots have one, the
+        # relative-pose anchor [K,9] with its device flags
+        self._bank_srt_has = [False] * capacity
+        self._bank_srt = self._bank_pose_anchor = self._bank_pose_anchor_has = None
         if capacity == 0:
             self._bank_cl = self._bank_idt = self._bank_theta = None
             self._bank_pose, self._bank_pose_has = None, None
@@ -265,6 +272,9 @@ class InferenceWrapper:
         # smooth_pose state of each slot's own frame stream (ops.theta_ema_scan): EMA value, and whether the stream has begun
         self._bank_pose = torch.zeros((capacity, 4, 4), **f32)
         self._bank_pose_has = torch.zeros((capacity,), device=self.device, dtype=torch.int32)
+        self._bank_srt = torch.zeros((capacity, 9), **f32)
+        self._bank_pose_anchor = torch.zeros((capacity, 9), **f32)
+        self._bank_pose_anchor_has = torch.zeros((capacity,), device=self.device, dtype=torch.int32)
 
     def _slot(self, slot, occupied=True):
         if self.identity_capacity == 0:
@@ -286,7 +296,7 @@ class InferenceWrapper:
         elif self._bank_expr.shape[1] != E:
             raise ValueError(f"an expression row of width {E}: the identity bank holds rows of width {self._bank_expr.shape[1]}")
 
-    def _bank_write(self, slot, canonical_cl, idt_embed, theta_src, expr_src=None):
+    def _bank_write(self, slot, canonical_cl, idt_embed, theta_src, expr_src=None, srt_src=None):
         if expr_src is not None:
             self._expr_bank(expr_src.numel())
         if idt_embed.numel() != self._bank_idt[slot].numel():
@@ -296,6 +306,10 @@ class InferenceWrapper:
         self._bank_theta[slot].copy_(theta_src.reshape(4, 4))
         self._bank_used[slot] = True
         self._bank_pose_has[slot] = 0             # a new identity starts a new smooth_pose stream
+        self._bank_pose_anchor_has[slot] = 0      # ... and a new relative-pose stream
+        self._bank_srt_has[slot] = srt_src is not None       # (a slot whose source theta came as a matrix has no source pose)
+        if srt_src is not None:
+            self._bank_srt[slot].copy_(srt_src.reshape(9))
         self._bank_expr_has[slot] = expr_src is not None     # (a slot written without a source expression has no neutral)
         if expr_src is not None:
             self._bank_expr[slot].copy_(expr_src.reshape(-1))
@@ -316,7 +330,8 @@ class InferenceWrapper:
                 raise ValueError(f"all {self.identity_capacity} identity slots are occupied: drop_identity one first")
             slot = free[0]
         slot = self._slot(slot, occupied=False)
-        self._bank_write(slot, self._canonical_cl, self.idt_embed, self.pred_source_theta, self.pred_source_pose_embed)
+        self._bank_write(slot, self._canonical_cl, self.idt_embed, self.pred_source_theta, self.pred_source_pose_embed,
+                         self.pred_source_srt)
         return slot
 
     def load_identity(self, slot):
@@ -328,11 +343,15 @@ class InferenceWrapper:
         self._set_source_cache(canonical_cl=cl, idt_embed=self._bank_idt[slot:slot + 1].clone())
         self.pred_source_theta = self._bank_theta[slot:slot + 1].clone()
         self.pred_source_pose_embed = self._bank_expr[slot:slot + 1].clone() if self._bank_expr_has[slot] else None
+        self.pred_source_srt = self._bank_srt[slot:slot + 1].clone() if self._bank_srt_has[slot] else None
+        self._pose_anchor = None                  # (a new current identity: the single stream's relative pose starts again)
 
     def drop_identity(self, slot):
         slot = self._slot(slot)
         self._bank_used[slot] = False
         self._bank_pose_has[slot] = 0
+        self._bank_pose_anchor_has[slot] = 0
+        self._bank_srt_has[slot] = False
         self._bank_expr_has[slot] = False
         self.reset_expression_state([slot])
 
@@ -351,15 +370,18 @@ class InferenceWrapper:
             self._bank_expr_ema_has.index_fill_(0, rows, 0)
 
     def reset_pose_state(self, slots=None):
-        """Restart smooth_pose: slots=None clears the single-identity state (`self.theta`) and every slot's stream; otherwise
-        only the streams of the given bank slots"""
+        """Restart smooth_pose and the head-pose controls' relative transfer: slots=None clears the single-identity state
+        (`self.theta`, the relative-pose anchor) and every slot's stream; otherwise only the streams of the given bank slots"""
         if slots is None:
-            self.theta = None
+            self.theta = self._pose_anchor = None
             if self.identity_capacity > 0:
                 self._bank_pose_has.zero_()
+                self._bank_pose_anchor_has.zero_()
             return
         for k in ([slots] if not isinstance(slots, (list, tuple, range, torch.Tensor)) else slots):
-            self._bank_pose_has[self._slot(int(k), occupied=False)] = 0
+            k = self._slot(int(k), occupied=False)
+            self._bank_pose_has[k] = 0
+            self._bank_pose_anchor_has[k] = 0
 
     def identities(self):
         """occupied slots, ascending"""
@@ -374,18 +396,25 @@ class InferenceWrapper:
                                        theta_src=self._bank_theta[slot:slot + 1])
         if src and self._bank_expr_has[slot]:
             rows['expr_src'] = self._bank_expr[slot:slot + 1]
+        if src:                                   # (a slot without a source pose sends a NaN row: the receivers read it once)
+            rows['srt_src'] = self._bank_srt[slot:slot + 1] if self._bank_srt_has[slot] else torch.full((1, 9), float('nan'))
         cache = self._broadcast_rows(rows, 1, src_rank, 'canonical_cl', self._bank_cl.shape[1:])
         if not src:
-            self._bank_write(slot, cache["canonical_cl"], cache["idt_embed"], cache["theta_src"], cache.get("expr_src"))
+            srt = cache["srt_src"]
+            self._bank_write(slot, cache["canonical_cl"], cache["idt_embed"], cache["theta_src"], cache.get("expr_src"),
+                             None if bool(torch.isnan(srt).any()) else srt)
 
-    def _broadcast_rows(self, rows, n, src, volume, volume_shape):
-        """{volume, idt_embed, theta_src, expr_src} of n identities from rank `src` (its `rows`; {} elsewhere) to every rank in
-        one flat buffer, the shapes known on every rank: one collective, no host synchronisation
-        (parallel.broadcast_source_cache).  expr_src, the source expressions, travels where the configuration names its width."""
+    def _broadcast_rows(self, rows, n, src, volume, volume_shape, srt=True):
+        """{volume, idt_embed, theta_src, expr_src, srt_src} of n identities from rank `src` (its `rows`; {} elsewhere) to every
+        rank in one flat buffer, the shapes known on every rank: one collective, no host synchronisation
+        (parallel.broadcast_source_cache).  expr_src, the source expressions, travels where the configuration names its width;
+        srt_src, the source (scale, rotation, translation) rows [n,9], unless `srt` is False."""
         shapes = {volume: (n,) + tuple(volume_shape), 'idt_embed': (n,) + tuple(self._bank_idt.shape[1:]), 'theta_src': (n, 4, 4)}
         E = self.cfg.get("lpe_output_channels_expression")
         if E:
             shapes['expr_src'] = (n, int(E))
+        if srt:
+            shapes['srt_src'] = (n, 9)
         return parallel.broadcast_source_cache(rows, shapes=shapes, names=list(shapes), src=src, device=self.device,
                                                world=self.world, rank=self.rank, exchange_shapes=False)
 
@@ -509,7 +538,9 @@ class InferenceWrapper:
         masks = None if plan.masks is None else torch.cat([m.reshape(1, 1, S, S) for m in plan.masks]).to(dev).float().contiguous()
         up = lambda t: None if t is None else t.to(dev).float().contiguous()
         idt_all, pose_all = up(custome_idt_embed), up(custome_source_pose_embed)
-        theta_all = None if theta_in is None else self._theta_from(theta_in)[0]
+        theta_all, srt_all = (None, None) if theta_in is None else self._theta_from(theta_in)
+        srt_all = None if srt_all is None else self._srt9(srt_all)
+        has_srt = not isinstance(theta_in, torch.Tensor)        # (a 4x4 source theta: the identity has no source pose)
         if plan.video:
             u8 = sources.to(dev).contiguous()
             win_dev = None if plan.win_host is None else plan.win_host.to(dev)
@@ -532,12 +563,21 @@ class InferenceWrapper:
             crop_m = ops.mul_mask(crop_img, face)
             masked = ops.mul_mask(crop_m, m if m is not None else face)
             idt = idt_all[a:b] if idt_all is not None else self._need('idt_embedder', 'enrolment')(masked)
-            theta = theta_all[a:b] if theta_all is not None else self._head_pose(crop_m)[0]
+            if theta_all is not None:
+                theta, srt = theta_all[a:b], None if srt_all is None else srt_all[a:b]
+            else:
+                theta, *srt = self._head_pose(crop_m)
+                # (a regressor that returns no (scale, rotation, translation): NaN rows, which the controls would hand on)
+                srt = self._srt9(srt) if len(srt) == 3 and all(t is not None for t in srt) else torch.full((b - a, 9), float('nan'),
+                                                                                                          device=dev)
             pose = pose_all[a:b] if pose_all is not None else self._expression(crop_m, theta, 'enrolment')[0]
             theta = theta.float().contiguous()
             canonical = self.hot_path.source_pass(masked, idt.float().contiguous(), pose.float().contiguous(), theta)
-            return dict(canonical=canonical, idt_embed=idt.float().reshape((b - a,) + es_shape), theta_src=theta.reshape(b - a, 4, 4),
+            part = dict(canonical=canonical, idt_embed=idt.float().reshape((b - a,) + es_shape), theta_src=theta.reshape(b - a, 4, 4),
                         expr_src=pose.float().reshape(b - a, -1))
+            if has_srt:
+                part["srt_src"] = srt
+            return part
 
         def write(part, a, b):
             ops.volume_to_channels_last_indexed(part["canonical"], self._bank_cl, rows32[a:b])
@@ -546,6 +586,8 @@ class InferenceWrapper:
             if "expr_src" in part:
                 self._expr_bank(part["expr_src"].shape[1])
                 self._bank_expr.index_copy_(0, rows64[a:b], part["expr_src"])
+            if has_srt:
+                self._bank_srt.index_copy_(0, rows64[a:b], part["srt_src"])
 
         if self.world == 1:
             for a, b in plan.chunks:
@@ -555,12 +597,14 @@ class InferenceWrapper:
             mine = {j: compute(a, b) for j, (a, b) in enumerate(plan.chunks) if plan.owners[j] == self.rank}
             c, d, s = self.cfg["latent_volume_channels"], self.cfg["latent_volume_depth"], self.cfg["latent_volume_size"]
             for j, (a, b) in enumerate(plan.chunks):
-                write(self._broadcast_rows(mine.pop(j, {}), b - a, plan.owners[j], 'canonical', (c, d, s, s)), a, b)
+                write(self._broadcast_rows(mine.pop(j, {}), b - a, plan.owners[j], 'canonical', (c, d, s, s), srt=has_srt), a, b)
         for k in plan.slots:
             self._bank_used[k] = True
             self._bank_expr_has[k] = self._bank_expr is not None
+            self._bank_srt_has[k] = has_srt
         self.reset_expression_state(plan.slots)
         self._bank_pose_has.index_fill_(0, rows64, 0)              # a new identity starts a new smooth_pose stream
+        self._bank_pose_anchor_has.index_fill_(0, rows64, 0)       # ... and a new relative-pose stream
         return plan.slots
 
     def _frame_identities(self, identities, n=None):
@@ -768,6 +812,11 @@ class InferenceWrapper:
         srt = tuple(t.to(self.device).float().contiguous() for t in embed)
         return ops.pose_theta(*srt), srt
 
+    def _srt9(self, srt):
+        """(scale [n,1] or [n,3], rotation [n,3], translation [n,3]) -> one [n,9] row per sample, a one-column scale broadcast"""
+        scale, rotation, translation = (t.to(self.device).float() for t in srt)
+        return torch.cat([scale.expand(scale.shape[0], 3), rotation, translation], dim=1).contiguous()
+
     def _source_theta(self, what):
         theta = self.pred_source_theta
         if theta is None:
@@ -897,6 +946,104 @@ class InferenceWrapper:
             setattr(self, name, rows[0])
         return out
 
+    def _head_pose_plan(self, head_pose, n_rows, ids, where, target_theta, faces=False):
+        """The checks of head_pose= (a HeadPoseControls or a mapping with its fields), before anything is launched -> None (no
+        control: nothing will be launched, no state touched) or what _head_pose_controls needs: relative, frontal, gain and zoom
+        (None = 1.0 | a float | a device [rows]), rotation_offset and translation_offset (None | a device [3] or [rows,3]),
+        step1 = the part about the source pose runs.  n_rows: the rows of the call where known; ids: the per-row slots (host
+        tensor) or None = the current identity."""
+        hp = HeadPoseControls.of(head_pose)
+        if hp is None:
+            return None
+        relative, frontal = bool(hp.relative), bool(hp.frontal)
+
+        def per_row(v, what):
+            if isinstance(v, torch.Tensor) and v.dim() == 0 or not isinstance(v, torch.Tensor) and not hasattr(v, '__len__'):
+                return None if float(v) == 1.0 else float(v)
+            t = torch.as_tensor(v).detach().float()
+            if t.dim() != 1:
+                raise ValueError(f"head_pose {what}: a float or one value per row, got {tuple(t.shape)}")
+            if n_rows is not None and t.shape[0] != n_rows:
+                raise ValueError(f"head_pose {what} has {t.shape[0]} rows for {n_rows} rows of the call")
+            return t
+
+        def rows3(v, what):
+            if v is None:
+                return None
+            t = torch.as_tensor(v).detach().float()
+            if t.dim() not in (1, 2) or t.shape[-1] != 3:
+                raise ValueError(f"head_pose {what}: [3] or [rows,3], got {tuple(t.shape)}")
+            if t.dim() == 2 and n_rows is not None and t.shape[0] != n_rows:
+                raise ValueError(f"head_pose {what} has {t.shape[0]} rows for {n_rows} rows of the call")
+            return t
+        gain, zoom = per_row(hp.gain, 'gain'), per_row(hp.zoom, 'zoom')
+        rot, trans = rows3(hp.rotation_offset, 'rotation_offset'), rows3(hp.translation_offset, 'translation_offset')
+        if not (relative or frontal or gain is not None or zoom is not None or rot is not None or trans is not None):
+            return None
+        if frontal and relative:
+            raise ValueError("head_pose frontal zeroes the yaw, pitch and translation that relative transfers: choose one")
+        if not target_theta:
+            raise ValueError("head_pose= edits the driver's head pose, target_theta=False renders in the source's: nothing of the "
+                             "edit would be rendered")
+        step1 = relative or gain is not None
+        if relative and ids is None and (faces or where == 'animate_streams'):
+            raise ValueError("head_pose relative follows every face track as its identity's stream: give identities")
+        if step1 and ids is None:
+            if self.pred_source_srt is None:
+                raise ValueError("head_pose relative / gain work about the current identity's source (scale, rotation, translation), "
+                                 "which is missing: call forward with a source_image and the head-pose regressor, or a "
+                                 "custome_source_theta_embed given as the triple, first")
+        elif step1:
+            missing = [k for k in sorted(set(ids.tolist())) if not self._bank_srt_has[k]]
+            if missing:
+                raise ValueError(f"head_pose relative / gain work about each identity's source (scale, rotation, translation): "
+                                 f"slot {missing[0]} has none")
+        up = lambda t: t.to(self.device).contiguous() if isinstance(t, torch.Tensor) else t
+        return Namespace(relative=relative, frontal=frontal, step1=step1, gain=up(gain), zoom=up(zoom), rotation_offset=up(rot),
+                         translation_offset=up(trans))
+
+    def _head_pose_controls(self, srt, ids_dev, hp, r0):
+        """The head-pose controls `hp` (_head_pose_plan) on srt = (scale, rotation, translation) of the rows r0 ... of the call
+        IN FRAME ORDER, one launch (ops.head_pose_controls, bit for bit hostglue.head_pose_controls) -> (the edited rows [m,9],
+        their theta [m,4,4]): every row about its identity's source pose (bank slot ids_dev[i], or the current identity's), and
+        for `relative` within its slot's stream, whose anchor the bank carries -- without identities the one stream whose anchor
+        `_pose_anchor` carries from call to call.  pred_target_srt is left as the edited triple."""
+        if srt is None or len(srt) != 3 or any(t is None for t in srt):
+            raise RuntimeError("head_pose= edits the (scale, rotation, translation) of the head-pose regressor, which returned none: "
+                               "a 'head_pose_regressor' callable must return (theta, scale, rotation, translation)")
+        scale, rotation, translation = (t.to(self.device).float().contiguous() for t in srt)
+        m = scale.shape[0]
+        if m == 0:
+            return torch.empty((0, 9), device=self.device), torch.empty((0, 4, 4), device=self.device)
+
+        def rows(t, what, whole):
+            """the rows r0 ... r0 + m of a per-row value; a float, a `whole`-dimensional tensor or None as it is"""
+            if not isinstance(t, torch.Tensor) or t.dim() == whole:
+                return t
+            if t.shape[0] < r0 + m:
+                raise ValueError(f"head_pose {what} has {t.shape[0]} rows, the frames run past it")
+            return t[r0:r0 + m].contiguous()
+        gain, zoom = rows(hp.gain, 'gain', 0), rows(hp.zoom, 'zoom', 0)
+        rot, trans = rows(hp.rotation_offset, 'rotation_offset', 1), rows(hp.translation_offset, 'translation_offset', 1)
+        if ids_dev is not None and hp.step1:
+            out = ops.head_pose_controls(scale, rotation, translation, ids_dev, self._bank_srt, gain, rot, trans, zoom,
+                                         self._bank_pose_anchor, self._bank_pose_anchor_has, hp.relative, hp.frontal)
+        else:
+            source = self.pred_source_srt.to(self.device).float().reshape(1, 9).contiguous() if hp.step1 else None
+            anchor = has = None
+            if hp.relative:
+                anchor = torch.zeros((1, 9), device=self.device, dtype=torch.float32)
+                has = torch.zeros((1,), device=self.device, dtype=torch.int32)
+                if self._pose_anchor is not None:
+                    anchor.copy_(self._pose_anchor.reshape(1, 9))
+                    has.fill_(1)
+            out = ops.head_pose_controls(scale, rotation, translation, None, source, gain, rot, trans, zoom, anchor, has, hp.relative,
+                                         hp.frontal)
+            if hp.relative:
+                self._pose_anchor = anchor[0]
+        self.pred_target_srt = tuple(out[0][:, i:i + 3] for i in (0, 3, 6))
+        return out
+
     def _render_theta(self, theta, ids_dev, target_theta):
         """target_theta=False: the frame is rendered in its identity's own head pose (infer.py:584), a device-side gather"""
         if target_theta:
@@ -963,10 +1110,14 @@ class InferenceWrapper:
                 else:
                     self._set_source_cache(idt_embed=self._need('idt_embedder', 'a source call')(masked))  # infer.py:432
                 if custome_source_theta_embed is not None:
-                    pred_source_theta = self._theta_from(custome_source_theta_embed)[0]
+                    pred_source_theta, srt = self._theta_from(custome_source_theta_embed)
                 else:
-                    pred_source_theta = self._need('head_pose_regressor', 'a source call')(source_img_crop)  # :437
+                    # (return_srt=True: the same theta, and the triple the head-pose controls work about)
+                    out = self._need('head_pose_regressor', 'a source call')(source_img_crop, True)                      # :437
+                    pred_source_theta, srt = (out[0], tuple(out[1:4])) if isinstance(out, (tuple, list)) else (out, None)
                 self.pred_source_theta = pred_source_theta
+                self.pred_source_srt = self._srt9(srt) if srt is not None and len(srt) == 3 and all(t is not None for t in srt) else None
+                self._pose_anchor = None          # a new source: the single stream's relative pose starts again
                 if custome_source_pose_embed is not None:
                     source_pose_embed = custome_source_pose_embed.to(self.device).float().contiguous()
                 else:
@@ -1042,7 +1193,7 @@ class InferenceWrapper:
     # ------------------------------------------------------------------------------------------------------
     def animate(self, target_pose_embeds, target_srt, batch_size=16, as_uint8=True, identities=None, mix=False, mix_old=True,
                 target_theta=True, smooth_pose=False, smooth_per_identity=False, refine=False, refine_masks=None,
-                out_format="rgb8", colorspace="bt709", full_range=False, expression=None):
+                out_format="rgb8", colorspace="bt709", full_range=False, expression=None, head_pose=None):
         """1 source -> N driver frames (the BASELINE metric).  Frames are sharded contiguously across ranks
         (SURVEY.md section 8e); each rank walks its shard in batches of `batch_size`.  Yields (first_frame_index, frames)
         with frames a uint8 [B,H,W,3] (or fp32 [B,3,H,W]) DEVICE tensor -- no host sync inside the loop.
@@ -1060,7 +1211,10 @@ class InferenceWrapper:
         through ops.pack_nv12 with `colorspace` ('bt709' | 'bt601') and `full_range` (see animate_frames).
         expression: an ExpressionControls (or a mapping with its fields) applied to target_pose_embeds on the device, see
         animate_frames; like smooth_pose, every rank runs it over the WHOLE stream in one launch and renders its slice, so the
-        frames do not depend on batch_size or on the number of ranks.  override= is a ValueError: the expressions are inputs."""
+        frames do not depend on batch_size or on the number of ranks.  override= is a ValueError: the expressions are inputs.
+        head_pose: a HeadPoseControls (or a mapping with its fields) applied to target_srt on the device before theta is formed,
+        see animate_frames; every rank edits the rows of the WHOLE stream in one launch (ops.head_pose_controls), mix and
+        smooth_pose then work on the edited thetas, and each rank renders its slice."""
         N = target_pose_embeds.shape[0]
         frames_mod.check_format(out_format, colorspace, "out_format")
         if out_format == "nv12" and not as_uint8:
@@ -1069,12 +1223,15 @@ class InferenceWrapper:
         if out_format == "nv12":
             self._nv12_size(masks_of)
         ex = self._expression_plan(expression, N, ids, 'animate')
+        hp = self._head_pose_plan(head_pose, N, ids, 'animate', target_theta)
         out_kind = "f32" if not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
         lo, hi = parallel.shard_range(N, self.rank, self.world)
         ids_dev = None if ids is None else ids[lo:hi].to(self.device)
-        smoothed = None
+        smoothed = edited = None
+        if hp is not None and N > 0:
+            edited = self._head_pose_controls(target_srt, None if ids is None else ids.to(self.device), hp, 0)[1]
         if smooth_pose and N > 0:
-            theta = ops.pose_theta(*[t.to(self.device).float().contiguous() for t in target_srt])
+            theta = edited if edited is not None else ops.pose_theta(*[t.to(self.device).float().contiguous() for t in target_srt])
             smoothed = self._pose_controls(theta, None if ids is None else ids.to(self.device), mix, mix_old, True)[lo:hi]
         poses = None
         if ex is not None and N > 0:
@@ -1085,6 +1242,8 @@ class InferenceWrapper:
             ident = None if ids is None else ids_dev[b0 - lo:b1 - lo]
             if smoothed is not None:
                 theta = smoothed[b0 - lo:b1 - lo]
+            elif edited is not None:
+                theta = self._pose_controls(edited[b0:b1], ident, mix, mix_old, False)
             else:
                 srt = [t[b0:b1].to(self.device).float().contiguous() for t in target_srt]
                 theta = self._pose_controls(ops.pose_theta(*srt), ident, mix, mix_old, False)
@@ -1179,7 +1338,7 @@ class InferenceWrapper:
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
                        mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
                        paste_matte=None, as_uint8=True, refine=False, refine_masks=None, frame_format="rgb8", out_format=None,
-                       colorspace="bt709", full_range=False, faces=None, expression=None):
+                       colorspace="bt709", full_range=False, faces=None, expression=None, head_pose=None):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  Per batch, all on the device and without a host synchronisation:
             byte -> fp32 CHW (emo_unpack_rgb8) -> crop windows read in place + bicubic resize to image_size, the whole batch in
@@ -1271,7 +1430,27 @@ class InferenceWrapper:
             identities there is one stream whose state the wrapper carries from call to call.  The result does not depend on
             batch_size, on the chunking or on the number of ranks: on one rank the state is carried from batch to batch, on
             several the expressions of every rank's rows are gathered in row order (parallel.gather_rows) and scanned on every
-            rank before the render.  None, or all defaults: no launch, no state touched."""
+            rank before the render.  None, or all defaults: no launch, no state touched.
+        head_pose: a HeadPoseControls, or a mapping with its fields -- what happens to the (scale, rotation, translation) the
+            head-pose regressor returns before theta is formed, on the device, one launch per batch (ops.head_pose_controls; the
+            contract is hostglue.head_pose_controls).  frontal is the reference's `normalize` and rotation_offset its delta_yaw /
+            delta_pitch (expression_embedder.py:302-316) plus roll; relative: source pose + (driver_t - driver_first); gain (a
+            float, or one per row): rotation and translation damped or exaggerated about the identity's source pose -- both work
+            about the source (scale, rotation, translation) of the row's identity (its bank slot's, or the current identity's,
+            pred_source_srt: what the regressor, or a custome_source_theta_embed given as the triple, left behind; a missing one
+            is a ValueError before anything is launched, as are frontal with relative and target_theta=False);
+            translation_offset is added, zoom multiplies the scale.  Order per batch: regressor -> head-pose controls -> mix,
+            smooth_pose on the edited theta -> expression -> render; pred_target_theta / pred_target_srt are what was rendered
+            with.  With an active edit the expression embedder is handed the regressor's OWN theta of the row, not the edited
+            one: it aligns the driver's crop by that theta, and the driver's face is where the driver's face is; without the
+            keyword it gets the mixed / smoothed theta as before.  relative follows the FRAME ORDER with smooth_pose's rules:
+            with identities= every row belongs to its slot's stream (the anchor in the bank, restarted by a new identity in the
+            slot, drop_identity and reset_pose_state), faces= then needs identities, and without identities there is one stream
+            whose anchor the wrapper carries from call to call (restarted by a new source and reset_pose_state).  The result does
+            not depend on batch_size, on the chunking or on the number of ranks: on one rank the anchor is carried on the device
+            from batch to batch, on several the regressed rows of every rank are gathered in row order (parallel.gather_rows)
+            and edited on every rank in the pass in front of the loop that smooth_pose has; without relative the edit is per row
+            and needs no gather.  None, or all defaults: no launch, no state touched, the frames bit-identical."""
         if isinstance(frames, torch.Tensor):
             frames_mod.check_frames(frames, frame_format)
         n_rows, counts = frames.shape[0] if isinstance(frames, torch.Tensor) else None, None
@@ -1293,18 +1472,18 @@ class InferenceWrapper:
             wins = None if windows is None else frames_mod.square_windows(windows)
         plan = self._video_plan(n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
                                 target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format,
-                                out_format, colorspace, full_range, expression=expression, faces=faces is not None)
+                                out_format, colorspace, full_range, expression=expression, faces=faces is not None, head_pose=head_pose)
         yield from self._animate_clip(frames, wins, counts, plan)
 
     def _video_plan(self, n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
                     target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format,
-                    colorspace, full_range, arena=False, expression=None, where='animate_frames', faces=False):
+                    colorspace, full_range, arena=False, expression=None, where='animate_frames', faces=False, head_pose=None):
         """The checks of the keywords animate_frames() and animate_streams() share, before anything is launched, and what their
         loops need beside the frames: wins = the (x0, y0, s, s) of every row of the call (None: whole frames), n_rows their
         number where it is known.  -> masks_of, ids (_preflight), matte_fn (_paste_matte), out_kind (_render's `out`), fmt =
         (frame_format, colorspace, full_range), ring = the pinned ring (None without to_host; with `arena` and paste_back a
-        frames.ArenaRing), upload_stream, ex = the expression controls (_expression_plan; None: none), and the loop's keywords as
-        they came."""
+        frames.ArenaRing), upload_stream, ex = the expression controls (_expression_plan; None: none), hp = the head-pose controls
+        (_head_pose_plan; None: none), and the loop's keywords as they came."""
         frames_mod.check_format(frame_format, colorspace)
         if out_format is not None:
             frames_mod.check_format(out_format, colorspace, "out_format")
@@ -1331,22 +1510,29 @@ class InferenceWrapper:
             self._nv12_size(masks_of)
         out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
         ex = self._expression_plan(expression, n_rows, ids, where, faces)
+        hp = self._head_pose_plan(head_pose, n_rows, ids, where, target_theta, faces)
         host_ring = None if not to_host else (frames_mod.ArenaRing(self.device, ring) if arena and paste_back
                                               else frames_mod.HostRing(self.device, ring, batch_size))
         return Namespace(masks_of=masks_of, ids=ids, matte_fn=matte_fn, out_kind=out_kind, fmt=(frame_format, colorspace, bool(full_range)),
                          feather=feather, paste_back=paste_back, ring=host_ring, upload_stream=torch.cuda.Stream(device=self.device),
-                         batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta, ex=ex)
+                         batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta, ex=ex,
+                         hp=hp)
 
-    def _drive_crops(self, crops, ident, plan, theta=None, smooth=None, row0=0, pose=None):
+    def _drive_crops(self, crops, ident, plan, theta=None, smooth=None, row0=0, pose=None, align=None):
         """The sequence of one driver batch of the video paths, crops [m,3,S,S] -> (the rendered batch as plan.out_kind says, its
         paste matte or None): head pose -> pose controls -> expression embedder (or the override) -> expression controls -> render
         -> matte, in forward()'s order.  row0: the batch's first row in the call (the controls' per-row values); pose: the batch's
         controlled expressions where a pass in front of the loop has formed them (a scan over the rows of several ranks).
         theta: the batch's thetas where a pass in front of the loop has formed them (the two-pass smooth_pose of a clip).
         smooth: None = mix alone, and only where it is asked for (a clip); a bool = mix and the one-pass smooth_pose of the
-        batch's rows (streams)."""
+        batch's rows (streams).  With head-pose controls (plan.hp) the regressed (scale, rotation, translation) are edited before
+        mix and smooth_pose, and the expression embedder is handed `align`, the regressor's own theta of the rows (formed here,
+        or by the pass that formed `theta`); align=None: the theta the batch is rendered with, as without the controls."""
         if theta is None:
-            theta = self._head_pose(crops)[0]
+            theta, *srt = self._head_pose(crops)
+            if plan.hp is not None:
+                align = theta
+                theta = self._head_pose_controls(srt, ident, plan.hp, row0)[1]
             if plan.mix or smooth is not None:
                 theta = self._pose_controls(theta, ident, plan.mix, plan.mix_old, bool(smooth))
         self.pred_target_theta = theta                                           # (as forward() leaves it: infer.py:584)
@@ -1355,7 +1541,7 @@ class InferenceWrapper:
             if ex is not None and ex.override is not None:
                 pose = self._expression_rows(ex.override, row0, crops.shape[0], 'override')
             else:
-                pose, _ = self._expression(crops, theta, 'a driver call')
+                pose, _ = self._expression(crops, theta if align is None else align, 'a driver call')
             if ex is not None:
                 pose = self._expression_controls(pose, ident, ex, row0)
         out = self._render(pose, theta, ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
@@ -1367,7 +1553,7 @@ class InferenceWrapper:
         row (host tensor) or None.  counts=None is windows= / whole frames: one row per frame (wins None: the whole frame), the
         per-frame entry points (frame_of=None) and the single-stream smooth_pose.  Per chunk the frames are sharded across the
         ranks; a batch is a span of whole frames (frames.face_spans)."""
-        S, ids, paste_back, ex = self.cfg["image_size"], plan.ids, plan.paste_back, plan.ex
+        S, ids, paste_back, ex, hp = self.cfg["image_size"], plan.ids, plan.paste_back, plan.ex, plan.hp
         first = None if counts is None else frames_mod.face_offsets(counts)
         base = 0
         for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
@@ -1391,24 +1577,43 @@ class InferenceWrapper:
             with_faces = [sp for sp in spans if rows(*sp)[0] < rows(*sp)[1]]
             m_lo, m_hi = rows(lo, hi)
             ids_dev = None if ids is None else ids[m_lo:m_hi].to(self.device)
-            smoothed, kept = None, {}
-            if plan.smooth_pose:
+            smoothed, kept, aligns = None, {}, {}
+            # a relative head pose walks the rows of every rank: their regressed (scale, rotation, translation) are gathered in row
+            # order and edited on every rank, so the anchor is the stream's first row whichever rank regressed it
+            gather_srt = hp is not None and hp.relative and self.world > 1
+            if plan.smooth_pose or gather_srt:
                 # two passes: the head pose of the rank's rows, gathered and scanned in frame order on every rank, then the render
                 keep_crops = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
                 local = []
                 for b0, b1, u8 in frames_mod.uploaded(chunk, with_faces, self.device, plan.upload_stream):
                     crops = crops_of(u8, b0, b1)
-                    local.append(self._head_pose(crops)[0].clone())
+                    theta, *srt = self._head_pose(crops)
+                    if hp is None:
+                        local.append(theta.clone())
+                    else:
+                        aligns[b0] = theta.clone()                               # (what the expression embedder aligns by)
+                        if gather_srt:
+                            local.append(self._srt9(srt))
+                        else:
+                            m0, m1 = rows(b0, b1)
+                            ident = None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo]
+                            local.append(self._head_pose_controls(srt, ident, hp, m0)[1])
                     if keep_crops:
                         kept[b0] = crops
-                local = torch.cat(local) if local else torch.empty((0, 4, 4), device=self.device)
-                if plan.mix:
-                    local = self._pose_controls(local, ids_dev, True, plan.mix_old, False)
+                local = torch.cat(local) if local else torch.empty((0, 9) if gather_srt else (0, 4, 4), device=self.device)
                 per_rank = [rows(*parallel.shard_range(n, r, self.world)) for r in range(self.world)]
-                every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)   # row order, on every rank
                 r0, r1 = rows(0, n)
                 ids_chunk = None if ids is None else ids[r0:r1].to(self.device)
-                smoothed = self._pose_controls(every, ids_chunk, False, plan.mix_old, True)[m_lo - r0:m_hi - r0]
+                if gather_srt:
+                    every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)
+                    every = tuple(every[:, i:i + 3].contiguous() for i in (0, 3, 6))
+                    local = self._head_pose_controls(every, ids_chunk, hp, r0)[1][m_lo - r0:m_hi - r0]
+                if plan.mix:
+                    local = self._pose_controls(local, ids_dev, True, plan.mix_old, False)
+                smoothed = local
+                if plan.smooth_pose:
+                    every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)   # row order, on every rank
+                    smoothed = self._pose_controls(every, ids_chunk, False, plan.mix_old, True)[m_lo - r0:m_hi - r0]
             poses, thetas = None, {}
             if ex is not None and ex.scan and self.world > 1:
                 # relative / smooth walk the rows of every rank: the expressions of the rank's rows (the override's are known
@@ -1430,12 +1635,15 @@ class InferenceWrapper:
                         if smoothed is not None:
                             theta = smoothed[m0 - m_lo:m1 - m_lo]
                         else:
-                            theta = self._head_pose(crops)[0]
+                            ident = None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo]
+                            theta, *srt = self._head_pose(crops)
+                            if hp is not None:                                   # (not relative here: the edit is per row)
+                                aligns[b0] = theta.clone()
+                                theta = self._head_pose_controls(srt, ident, hp, m0)[1]
                             if plan.mix:
-                                theta = self._pose_controls(theta, None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo], True,
-                                                            plan.mix_old, False)
+                                theta = self._pose_controls(theta, ident, True, plan.mix_old, False)
                             thetas[b0] = theta = theta.clone()
-                        local.append(self._expression(crops, theta, 'a driver call')[0].float().clone())
+                        local.append(self._expression(crops, aligns.get(b0, theta), 'a driver call')[0].float().clone())
                     if local:
                         local = torch.cat(local)
                     else:                                                        # (a rank without a row still joins the gather)
@@ -1463,7 +1671,7 @@ class InferenceWrapper:
                     ident = None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo]
                     theta = thetas.pop(b0, None) if smoothed is None else smoothed[m0 - m_lo:m1 - m_lo]
                     out, m = self._drive_crops(crops, ident, plan, theta, row0=m0,
-                                               pose=None if poses is None else poses[m0 - m_lo:m1 - m_lo])
+                                               pose=None if poses is None else poses[m0 - m_lo:m1 - m_lo], align=aligns.pop(b0, None))
                     if paste_back:
                         full = u8.clone() if chunk.is_cuda else u8               # (a host chunk's upload is this span's own)
                         out = frames_mod.paste_into(full, out, wins_of(b0, b1), plan.feather, m, *plan.fmt, frame_of=frame_of(b0, b1))
@@ -1479,7 +1687,7 @@ class InferenceWrapper:
     def animate_streams(self, streams, batch_size=16, ring=3, to_host=True, smooth_pose=False, mix=False, mix_old=True,
                         target_theta=True, paste_back=False, feather=0.0625, paste_matte=None, as_uint8=True, refine=False,
                         refine_masks=None, frame_format="rgb8", out_format=None, colorspace="bt709", full_range=False,
-                        expression=None):
+                        expression=None, head_pose=None):
         """Several video streams of DIFFERENT frame sizes served by one driver batch: animate_frames(faces=) with the frames of a
         batch a list instead of one tensor.  Between the crop and the paste everything is one row per face, so only the two ends
         differ: ONE crop launch reads every face of the batch out of its own frame through a frame table
@@ -1492,7 +1700,12 @@ class InferenceWrapper:
                 length is the stream's number of frames;
             'identities' (optional, then in every stream): one bank slot for the stream, or one per face of the stream;
             'expression' (optional): {'gain': a float or one per face of the stream, 'offset': [E] or one row per face}, in place
-                of the call's values for this stream.
+                of the call's values for this stream;
+            'head_pose' (optional): {'gain', 'zoom': a float or one per face of the stream, 'rotation_offset',
+                'translation_offset': [3] or one row per face}, in place of the call's values for this stream.
+        head_pose: animate_frames' head-pose controls, here with the flags, a scalar gain / zoom and [3] offsets; relative needs
+            identities, every face track is its slot's stream, edited batch by batch in one pass as smooth_pose is.  (With
+            per-stream offsets a stream without one is given a zero offset.)
         expression: animate_frames' expression controls, here with the flags, the momentum, a scalar gain and an [E] offset (no
             override); relative and smooth need identities, every face track is its slot's stream, scanned batch by batch in one
             pass as smooth_pose is.  (With per-stream offsets a stream without one is given a zero offset.)
@@ -1542,7 +1755,10 @@ class InferenceWrapper:
                                              [(s, first[s][t], first[s][t + 1]) for s, t in order])
         plan = self._video_plan(len(wins), wins, identities, batch_size, ring, to_host, smooth_pose, True, mix, mix_old, target_theta,
                                 paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format, colorspace,
-                                full_range, arena=True, expression=expression, where='animate_streams')
+                                full_range, arena=True, expression=expression, where='animate_streams',
+                                head_pose=self._stream_head_pose(head_pose, [st.get('head_pose') for st in streams],
+                                                                 [len(flat) for flat, _ in faces],
+                                                                 [(s, first[s][t], first[s][t + 1]) for s, t in order]))
         S, host_ring = self.cfg["image_size"], plan.ring
         ids_dev = None if plan.ids is None else plan.ids.to(self.device)
         rows = frames_mod.face_offsets(counts)                                   # rows[i] = faces in front of frame i of the order
@@ -1655,6 +1871,58 @@ class InferenceWrapper:
         return ExpressionControls(relative=ex.relative, smooth=ex.smooth, momentum=ex.momentum, offset=offset,
                                   gain=gain if bool((gain != 1.0).any()) else 1.0)
 
+    @staticmethod
+    def _stream_head_pose(head_pose, per_stream, n_faces, order):
+        """animate_streams' head_pose= and the streams' own 'head_pose' mappings -> the HeadPoseControls of the call's rows, by
+        _stream_expression's rule: per_stream[s] = stream s's {'gain', 'zoom', 'rotation_offset', 'translation_offset'} or None,
+        n_faces[s] its faces, order = (stream, first face, end) of every frame of the batch order.  Without a stream's own
+        values the call's scalar gain / zoom and [3] offsets stay as they are."""
+        hp = HeadPoseControls.of(head_pose)
+        scalar = lambda v: isinstance(v, torch.Tensor) and v.dim() == 0 or not isinstance(v, torch.Tensor) and not hasattr(v, '__len__')
+        if hp is not None:
+            for name in ('gain', 'zoom'):
+                if not scalar(getattr(hp, name)):
+                    raise ValueError(f"animate_streams' head_pose {name} is one float: per-face values belong to a stream's 'head_pose'")
+            for name in ('rotation_offset', 'translation_offset'):
+                v = getattr(hp, name)
+                if v is not None and tuple(torch.as_tensor(v).shape) != (3,):
+                    raise ValueError(f"animate_streams' head_pose {name} is one [3] row: per-face rows belong to a stream's 'head_pose'")
+        if all(p is None for p in per_stream):
+            return hp
+        hp = hp or HeadPoseControls()
+        cols = {name: [] for name in ('gain', 'zoom', 'rotation_offset', 'translation_offset')}
+        for s, p in enumerate(per_stream):
+            p = {} if p is None else dict(p)
+            unknown = sorted(set(p) - set(cols))
+            if unknown:
+                raise ValueError(f"stream {s}: its 'head_pose' takes 'gain', 'zoom', 'rotation_offset' and 'translation_offset', "
+                                 f"not {unknown[0]!r}")
+            for name in ('gain', 'zoom'):
+                g = torch.as_tensor(p.get(name, getattr(hp, name))).detach().float()
+                if g.dim() > 1 or g.dim() == 1 and g.shape[0] != n_faces[s]:
+                    raise ValueError(f"stream {s}: head_pose {name} {tuple(g.shape)} is not a float or one per face ({n_faces[s]})")
+                cols[name].append(g.expand(n_faces[s]))
+            for name in ('rotation_offset', 'translation_offset'):
+                o = p.get(name, getattr(hp, name))
+                if o is not None:
+                    o = torch.as_tensor(o).detach().float()
+                    if o.dim() not in (1, 2) or o.shape[-1] != 3 or o.dim() == 2 and o.shape[0] != n_faces[s]:
+                        raise ValueError(f"stream {s}: head_pose {name} {tuple(o.shape)} is not [3] or one row per face ({n_faces[s]}, 3)")
+                    o = o.expand(n_faces[s], 3)
+                cols[name].append(o)
+        out = {}
+        for name in ('gain', 'zoom'):
+            v = torch.cat([cols[name][s][a:b] for s, a, b in order]) if order else torch.zeros(0)
+            out[name] = v if bool((v != 1.0).any()) else 1.0
+        for name in ('rotation_offset', 'translation_offset'):
+            rows = cols[name]
+            if all(o is None for o in rows) or not order:
+                out[name] = None
+            else:
+                rows = [torch.zeros((n_faces[s], 3)) if o is None else o for s, o in enumerate(rows)]
+                out[name] = torch.cat([rows[s][a:b] for s, a, b in order])
+        return HeadPoseControls(relative=hp.relative, frontal=hp.frontal, **out)
+
     def share_source(self, src_rank=0):
         """RCCL broadcast of the per-identity cache computed on `src_rank`: canonical volume
         (25 MB) + idt_embed (32 KB) + source theta."""
@@ -1665,13 +1933,19 @@ class InferenceWrapper:
         # the source expression (the expression controls' neutral) travels with it; an identity without one sends an empty row
         expr = self.pred_source_pose_embed
         expr = torch.zeros((1, 0), device=self.device) if expr is None else expr.reshape(1, -1)
+        # ... and so does the source (scale, rotation, translation), the head-pose controls' source pose
+        srt = torch.zeros((1, 0), device=self.device) if self.pred_source_srt is None else self.pred_source_srt.reshape(1, 9)
         cache = parallel.broadcast_source_cache(
-            dict(canonical=self.target_latent_volume, idt_embed=self.idt_embed, theta_src=self.pred_source_theta, expr_src=expr),
-            shapes=dict(canonical=(1, c, d, s, s), theta_src=(1, 4, 4)), names=['canonical', 'idt_embed', 'theta_src', 'expr_src'],
+            dict(canonical=self.target_latent_volume, idt_embed=self.idt_embed, theta_src=self.pred_source_theta, expr_src=expr,
+                 srt_src=srt),
+            shapes=dict(canonical=(1, c, d, s, s), theta_src=(1, 4, 4)),
+            names=['canonical', 'idt_embed', 'theta_src', 'expr_src', 'srt_src'],
             src=src_rank, device=self.device, world=self.world, rank=self.rank)
         if cache["idt_embed"].numel() != self.cfg["gen_max_channels"] * es * es:
             raise RuntimeError(f"idt_embed {tuple(cache['idt_embed'].shape)} does not match the warp embedding "
                                f"({self.cfg['gen_max_channels']} channels x {es}x{es})")
         self.pred_source_theta = cache["theta_src"]
         self.pred_source_pose_embed = cache["expr_src"].clone() if cache["expr_src"].numel() else None
+        self.pred_source_srt = cache["srt_src"].clone() if cache["srt_src"].numel() else None
+        self._pose_anchor = None
         self._set_source_cache(canonical=cache["canonical"], idt_embed=cache["idt_embed"])

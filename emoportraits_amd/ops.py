@@ -1246,3 +1246,67 @@ def expression_controls(values, stream_of=None, neutral=None, gain=None, offset=
                                         int(bool(relative)), int(smooth), m, om, hip.ptr(out), hip.current_stream()),
               "emo_expr_controls_f32")
     return out
+
+
+def head_pose_controls(scale, rotation, translation, stream_of=None, source=None, gain=None, rotation_offset=None,
+                       translation_offset=None, zoom=None, anchor=None, has_anchor=None, relative=False, frontal=False):
+    """The head-pose controls of the batched entry points on the device (emo_head_pose_controls_f32; bit for bit
+    hostglue.head_pose_controls, which states the arithmetic): scale [n,1] or [n,3], rotation and translation [n,3] IN FRAME
+    ORDER, stream_of int32 [n] (or None: one stream, 0), source [K,9] or None (needed by relative and gain), gain and zoom a
+    float or [n] or None, rotation_offset and translation_offset [3] or [n,3] or None -- a scalar gain / zoom and a [3] offset
+    are broadcast to the rows here; anchor [K,9] and has_anchor int32 [K] are the streams' state for `relative`, updated in
+    place.  -> (srt [n,9] = the edited rows, theta [n,4,4] = ops.pose_theta of them), both new tensors: the kernel's outputs
+    alias none of its inputs.  One launch, no host synchronisation."""
+    lib = hip.load()
+    hip.require_cuda_f32(scale, rotation, translation, source, anchor)
+    if scale.dim() != 2 or scale.shape[0] == 0 or scale.shape[1] not in (1, 3):
+        raise ValueError(f"head_pose_controls expects a [n,1] or [n,3] scale, got {tuple(scale.shape)}")
+    n, dev = scale.shape[0], scale.device
+    for t, what in ((rotation, "rotation"), (translation, "translation")):
+        if tuple(t.shape) != (n, 3):
+            raise ValueError(f"head_pose_controls: {what} must be [{n},3], got {tuple(t.shape)}")
+    if relative and frontal:
+        raise ValueError("head_pose_controls: frontal zeroes what relative transfers")
+    if (relative or gain is not None) and source is None:
+        raise ValueError("head_pose_controls: relative transfer and gain need source")
+    if relative and (anchor is None or has_anchor is None):
+        raise ValueError("head_pose_controls: relative transfer needs anchor and has_anchor")
+    banks = [t for t in (source, anchor if relative else None) if t is not None]
+    K = banks[0].shape[0] if banks else 1
+    for t in banks:
+        if t.dim() != 2 or tuple(t.shape) != (K, 9) or K == 0:
+            raise ValueError(f"head_pose_controls: source and anchor must be [K,9], got {tuple(t.shape)}")
+    if relative:
+        _check_index(has_anchor, K, dev, "has_anchor")
+    if stream_of is not None:
+        _check_index(stream_of, n, dev, "stream_of")
+
+    def per_row(v, what):
+        if v is None:
+            return None
+        if isinstance(v, torch.Tensor) and v.dim() == 1:
+            hip.require_cuda_f32(v)
+            if v.shape[0] != n:
+                raise ValueError(f"head_pose_controls: {what} has {v.shape[0]} entries for {n} rows")
+            return v
+        return torch.full((n,), float(v), dtype=torch.float32, device=dev)
+
+    def rows3(v, what):
+        if v is None:
+            return None
+        hip.require_cuda_f32(v)
+        if tuple(v.shape) == (3,):
+            return v.expand(n, 3).contiguous()
+        if tuple(v.shape) != (n, 3):
+            raise ValueError(f"head_pose_controls: {what} must be [3] or [{n},3], got {tuple(v.shape)}")
+        return v
+    gain, zoom = per_row(gain, "gain"), per_row(zoom, "zoom")
+    rotation_offset, translation_offset = rows3(rotation_offset, "rotation_offset"), rows3(translation_offset, "translation_offset")
+    srt = torch.empty((n, 9), device=dev, dtype=torch.float32)
+    theta = torch.empty((n, 4, 4), device=dev, dtype=torch.float32)
+    hip.check(lib.emo_head_pose_controls_f32(hip.ptr(scale), scale.shape[1], hip.ptr(rotation), hip.ptr(translation), hip.ptr(stream_of),
+                                             hip.ptr(source), hip.ptr(gain), hip.ptr(rotation_offset), hip.ptr(translation_offset),
+                                             hip.ptr(zoom), hip.ptr(anchor if relative else None),
+                                             hip.ptr(has_anchor if relative else None), n, K, int(bool(relative)), int(bool(frontal)),
+                                             hip.ptr(srt), hip.ptr(theta), hip.current_stream()), "emo_head_pose_controls_f32")
+    return srt, theta

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 20
+#define EMO_ABI_VERSION 21
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -490,6 +490,32 @@ int emo_theta_ema_scan_f32(const float* values, const int32_t* stream_of, float*
 int emo_expr_controls_f32(const float* values, const int32_t* stream_of, const float* neutral, const float* gain,
                           const float* offset, float* anchor, int32_t* has_anchor, float* ema, int32_t* has_ema, int n, int K,
                           int E, int relative, int smooth, float m, float om, float* out, void* stream);
+/* ABI 21.  The head-pose controls of the batched entry points: the (scale, rotation, translation) of every row edited before
+ * theta is formed -- the reference's `normalize`, `delta_yaw` and `delta_pitch` (expression_embedder.py:302-316), relative
+ * transfer and gain about each identity's source pose, offsets and a zoom.  Row i (scale [n,scale_cols], scale_cols 1 or 3, a
+ * single column broadcast to three; rotation [n,3] = yaw, pitch, roll; translation [n,3]) belongs to stream k = stream_of[i]
+ * ([n] int32 DEVICE memory, or NULL: stream 0).  source [K,9] or NULL, gain [n] or NULL, rotation_offset and translation_offset
+ * [n,3] or NULL, zoom [n] or NULL; anchor [K,9] with its flags has_anchor [K] int32 is read and written.  A row is nine floats
+ * p = [sx sy sz | yaw pitch roll | tx ty tz]; every operation fp32 and rounded on its own, clamp(v) = v limited to
+ * [-pi/2, pi] with emo_pose_theta_f32's fp32 constants:
+ *   0. p.rot = clamp(p.rot)
+ *   1. if frontal:  yaw = pitch = 0, p.trans = 0   (roll and scale stay)
+ *   2. if source:   q = source[k] with q.rot = clamp(q.rot);  ref = q, or with `relative` anchor[k] -- which a stream without
+ *                   anchor takes from its first row after step 0 (has_anchor[k] = 1 afterwards);
+ *                   d = p.rot - ref.rot;  if gain: d = d * gain[i];  p.rot = q.rot + d;  the same for p.trans;
+ *                   with `relative` only:  p.scale = q.scale * (p.scale / ref.scale)
+ *   3. if rotation_offset: p.rot += rotation_offset[i];  if translation_offset: p.trans += translation_offset[i];
+ *      if zoom: p.scale *= zoom[i]
+ *   4. out_srt[i] = p ([n,9]);  out_theta[i] = S R T of p ([n,16]), bit for bit emo_pose_theta_f32 of p (which clamps once more)
+ * -- bit for bit hostglue.head_pose_controls.  A stream index outside [0, K) leaves its row unwritten and touches no state; a
+ * stream without a row keeps its flag.  out_srt and out_theta must not overlap any input.
+ * EMO_ERR_BAD_ARG before any launch: scale, rotation, translation, out_srt or out_theta NULL; n or K <= 0; scale_cols not 1 or
+ * 3; relative or gain without source; relative without anchor and has_anchor; relative together with frontal.
+ * One block per stream, its threads take the stream's rows in parallel; no atomics. */
+int emo_head_pose_controls_f32(const float* scale, int scale_cols, const float* rotation, const float* translation,
+                               const int32_t* stream_of, const float* source, const float* gain, const float* rotation_offset,
+                               const float* translation_offset, const float* zoom, float* anchor, int32_t* has_anchor, int n,
+                               int K, int relative, int frontal, float* out_srt, float* out_theta, void* stream);
 int emo_pack_rgb8(const float* img, uint8_t* out, int N, int H, int W, void* stream);
 int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int W, void* stream);
 

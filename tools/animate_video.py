@@ -8,6 +8,8 @@
          ...], one list per frame in paste order ([]: no face); --sources enrols several source images into an identity bank
          (slots 0, 1, ... in that order) and ids.json names the slot of every face, flattened in frame order
         [--mix [--mix-new]] [--source-pose] [--smooth-pose]   # forward()'s pose controls (mix, mix_old=False, target_theta=False)
+        [--relative-pose] [--pose-gain G] [--yaw R --pitch R --roll R] [--pose-zoom Z] [--frontal]   # the head-pose controls
+         (animate_frames' head_pose=): keep the avatar's own head pose and follow the driver's motion, damp it, turn the head, look ahead
         [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
         [--stage2-experiment <exp2> --stage2-checkpoint <file> [--cloth]       # refine every batch with the stage-2 model
          (--embedders module:factory | --refine-everywhere)]                   # (<project>/logs_s2/<exp2>), inside the same path
@@ -88,6 +90,13 @@ def main():
     ap.add_argument("--expression-offset", default=None, help="a .pt file with an [E] row, or one row per frame (face), added to the expression")
     ap.add_argument("--smooth-expression", action="store_true", help="EMA over the expression vectors (see --expression-momentum)")
     ap.add_argument("--expression-momentum", type=float, default=None, help="with --smooth-expression: 0 < M <= 1 (default 0.5)")
+    ap.add_argument("--relative-pose", action="store_true", help="relative head pose: source pose + (driver_t - driver_first)")
+    ap.add_argument("--pose-gain", type=float, default=1.0, help="damp (< 1) or exaggerate (> 1) the head motion about the source's pose")
+    ap.add_argument("--yaw", type=float, default=0.0, help="radians added to the yaw (the reference's delta_yaw)")
+    ap.add_argument("--pitch", type=float, default=0.0, help="radians added to the pitch (the reference's delta_pitch)")
+    ap.add_argument("--roll", type=float, default=0.0, help="radians added to the roll")
+    ap.add_argument("--pose-zoom", type=float, default=1.0, help="multiplies the head pose's scale")
+    ap.add_argument("--frontal", action="store_true", help="look straight ahead: yaw = pitch = 0, translation = 0 (the reference's normalize)")
     ap.add_argument("--paste-back", action="store_true", help="write the full frames with the rendered crops pasted back (needs --windows or --faces)")
     ap.add_argument("--feather", type=float, default=0.0625, help="with --paste-back: blended edge as a fraction of the window side")
     ap.add_argument("--stage2-experiment", default=None, help="refine with the stage-2 model <project>/logs_s2/<this>")
@@ -125,6 +134,15 @@ def main():
     if (a.relative_expression or a.smooth_expression) and a.faces and not a.identities:
         ap.error("--relative-expression / --smooth-expression with --faces follow every face track as its identity's stream: "
                  "they need --sources / --identities")
+    if a.relative_pose and a.frontal:
+        ap.error("--frontal zeroes what --relative-pose transfers: choose one")
+    if a.relative_pose and a.faces and not a.identities:
+        ap.error("--relative-pose with --faces follows every face track as its identity's stream: it needs --sources / --identities")
+    head_pose = dict(relative=a.relative_pose, gain=a.pose_gain, zoom=a.pose_zoom, frontal=a.frontal,
+                     rotation_offset=[a.yaw, a.pitch, a.roll] if a.yaw or a.pitch or a.roll else None)
+    if a.source_pose and (a.relative_pose or a.frontal or a.pose_gain != 1.0 or a.pose_zoom != 1.0 or head_pose["rotation_offset"]):
+        ap.error("--source-pose renders in the source's head pose: nothing of --relative-pose / --pose-gain / --yaw / --pitch / --roll / "
+                 "--pose-zoom / --frontal would be rendered")
     sources = a.sources.split(",") if a.sources else []
     refine = a.stage2_experiment is not None
     if refine and (a.stage2_checkpoint is None or (a.embedders is None) == (not a.refine_everywhere)):
@@ -178,7 +196,8 @@ def main():
     for first, u8 in w.animate_frames(frames, batch_size=a.batch, windows=windows, faces=faces, identities=identities, mix=a.mix,
                                       mix_old=not a.mix_new, target_theta=not a.source_pose, smooth_pose=a.smooth_pose,
                                       smooth_per_identity=identities is not None, paste_back=a.paste_back,
-                                      feather=a.feather, refine=refine, refine_masks=refine_masks, expression=expression, **fmt):
+                                      feather=a.feather, refine=refine, refine_masks=refine_masks, expression=expression,
+                                      head_pose=head_pose, **fmt):
         arr = u8.numpy()
         if nv12:
             sink.write(arr.tobytes())                             # batches come in frame order (one rank)
