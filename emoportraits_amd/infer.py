@@ -37,8 +37,7 @@ import torch
 from . import config as cfg_mod
 from . import embedders as emb_mod
 from . import frames as frames_mod
-from . import graphs, hostglue, nets, ops, parallel, schema
-from .controls import ExpressionControls, HeadPoseControls
+from . import control_streams, graphs, hostglue, nets, ops, parallel, schema
 
 
 # smooth_pose in animate_frames: the crops of a rank's shard stay resident between the head-pose pass and the render pass up to
@@ -186,20 +185,34 @@ class InferenceWrapper:
         self.momentum = 0.01
         self.center = self.size = self._crop_tracker = None
         self.pose_momentum = pose_momentum
-        self.theta = None
+        # the one stream of the current identity (smooth_pose's EMA, which `theta` reads; the controls' anchors and EMA), walked by
+        # the calls without identities=; the bank's streams, one per slot, are _init_identity_bank's
+        self._stream = control_streams.StreamStates(1, self.device, "the current identity's stream")
         self.norm_momentum = 0.1
         self.delta_yaw = self.delta_pitch = None
         self.resize_warp = False
         self.use_seg = use_seg
         self.target_latent_volume = self._canonical_cl = self.idt_embed = self.pred_source_theta = None
-        # the current identity's source expression (the expression controls' neutral) and, without a bank, the one stream's
-        # relative-transfer anchor and expression EMA ([E], None before the first row), carried from call to call as self.theta
-        self.pred_source_pose_embed = self._expr_anchor = self._expr_ema = None
-        # the current identity's source (scale, rotation, translation) as one [1,9] row (the head-pose controls' source pose; None
-        # where the source theta came as a 4x4 matrix) and, without a bank, the one stream's relative-pose anchor ([9])
-        self.pred_source_srt = self._pose_anchor = None
+        # the current identity's source expression (the expression controls' neutral) and its source (scale, rotation, translation)
+        # as one [1,9] row (the head-pose controls' source pose; None where the source theta came as a 4x4 matrix)
+        self.pred_source_pose_embed = self.pred_source_srt = None
         self._stage2 = self._stage2_wrapper = None                                 # attach_stage2()
         self._init_identity_bank(identity_capacity)
+
+    @property
+    def theta(self):
+        """smooth_pose's state without identities, under the reference's name (notebooks/infer.py:571-581): None before the
+        stream's first frame, else its EMA [4,4] (a view of the state row, which the next scan updates).  Reading it reads a
+        device flag, so it may synchronise: nothing on the batched paths does.  Assigning None restarts the stream."""
+        return self._stream.theta[0] if int(self._stream.theta_has[0]) else None
+
+    @theta.setter
+    def theta(self, value):
+        if value is None:
+            self._stream.restart(pose_ema=True)
+        else:
+            self._stream.theta[0].copy_(value.reshape(4, 4))
+            self._stream.theta_has.fill_(1)
 
     def _capture(self, seq):
         """with use_graphs: replay the _sequence method `seq` from a hipGraph from its (1 + _graph_eager_calls)-th call of an
@@ -251,17 +264,12 @@ class InferenceWrapper:
             raise ValueError("identity_capacity must be >= 0")
         self.identity_capacity = capacity
         self._bank_used = [False] * capacity
-        # the expression controls' per-slot data (_expr_bank allocates it, from the width of the first row written): the source
-        # expression [K,E] and which slots have one, the relative-transfer anchor and the expression EMA [K,E] with their flags
-        self._bank_expr = self._bank_expr_anchor = self._bank_expr_anchor_has = self._bank_expr_ema = self._bank_expr_ema_has = None
-        self._bank_expr_has = [False] * capacity
-        # the head-pose controls' per-slot data: the source (scale, rotation, translation) [K,9] and which slots have one, the
-        # relative-pose anchor [K,9] with its device flags
-        self._bank_srt_has = [False] * capacity
-        self._bank_srt = self._bank_pose_anchor = self._bank_pose_anchor_has = None
+        # the controls' per-slot sources: the source expression [K,E] (_expr_bank allocates it, from the width of the first row
+        # written) and the source (scale, rotation, translation) [K,9], and which slots have one
+        self._bank_expr = self._bank_srt = None
+        self._bank_expr_has, self._bank_srt_has = [False] * capacity, [False] * capacity
         if capacity == 0:
-            self._bank_cl = self._bank_idt = self._bank_theta = None
-            self._bank_pose, self._bank_pose_has = None, None
+            self._bank_cl = self._bank_idt = self._bank_theta = self._bank_streams = None
             return
         c, d, s = self.cfg["latent_volume_channels"], self.cfg["latent_volume_depth"], self.cfg["latent_volume_size"]
         es = self.cfg["gen_embed_size"]
@@ -269,12 +277,9 @@ class InferenceWrapper:
         self._bank_cl = torch.zeros((capacity, d, s, s, c), **f32)
         self._bank_idt = torch.zeros((capacity, self.cfg["gen_max_channels"], es, es), **f32)
         self._bank_theta = torch.zeros((capacity, 4, 4), **f32)
-        # smooth_pose state of each slot's own frame stream (ops.theta_ema_scan): EMA value, and whether the stream has begun
-        self._bank_pose = torch.zeros((capacity, 4, 4), **f32)
-        self._bank_pose_has = torch.zeros((capacity,), device=self.device, dtype=torch.int32)
         self._bank_srt = torch.zeros((capacity, 9), **f32)
-        self._bank_pose_anchor = torch.zeros((capacity, 9), **f32)
-        self._bank_pose_anchor_has = torch.zeros((capacity,), device=self.device, dtype=torch.int32)
+        # each slot's own frame stream: smooth_pose's EMA, the controls' anchors and EMA
+        self._bank_streams = control_streams.StreamStates(capacity, self.device)
 
     def _slot(self, slot, occupied=True):
         if self.identity_capacity == 0:
@@ -285,16 +290,11 @@ class InferenceWrapper:
         return slot
 
     def _expr_bank(self, E):
-        """the bank's expression rows, allocated at the first use from the width E of the row at hand (a bank's `cfg` need not
-        name it); every later row has that width"""
+        """the bank's expression rows, the slots' source expressions and their streams' anchor and EMA, allocated at the first use
+        from the width E of the row at hand (a bank's `cfg` need not name it); every later row has that width"""
+        self._bank_streams.expression(E)
         if self._bank_expr is None:
-            K = self.identity_capacity
-            self._bank_expr, self._bank_expr_anchor, self._bank_expr_ema = (
-                torch.zeros((K, E), device=self.device, dtype=torch.float32) for _ in range(3))
-            self._bank_expr_anchor_has, self._bank_expr_ema_has = (
-                torch.zeros((K,), device=self.device, dtype=torch.int32) for _ in range(2))
-        elif self._bank_expr.shape[1] != E:
-            raise ValueError(f"an expression row of width {E}: the identity bank holds rows of width {self._bank_expr.shape[1]}")
+            self._bank_expr = torch.zeros((self.identity_capacity, E), device=self.device, dtype=torch.float32)
 
     def _bank_write(self, slot, canonical_cl, idt_embed, theta_src, expr_src=None, srt_src=None):
         if expr_src is not None:
@@ -305,15 +305,13 @@ class InferenceWrapper:
         self._bank_idt[slot].copy_(idt_embed.reshape(self._bank_idt.shape[1:]))
         self._bank_theta[slot].copy_(theta_src.reshape(4, 4))
         self._bank_used[slot] = True
-        self._bank_pose_has[slot] = 0             # a new identity starts a new smooth_pose stream
-        self._bank_pose_anchor_has[slot] = 0      # ... and a new relative-pose stream
         self._bank_srt_has[slot] = srt_src is not None       # (a slot whose source theta came as a matrix has no source pose)
         if srt_src is not None:
             self._bank_srt[slot].copy_(srt_src.reshape(9))
         self._bank_expr_has[slot] = expr_src is not None     # (a slot written without a source expression has no neutral)
         if expr_src is not None:
             self._bank_expr[slot].copy_(expr_src.reshape(-1))
-        self.reset_expression_state([slot])
+        self._bank_streams.restart([slot], pose_ema=True, pose_anchor=True, expression=True)      # a new identity: new streams
 
     def store_identity(self, slot=None):
         """Copy the current identity (what forward(source_image=...) or share_source() left behind) into `slot` (None: the
@@ -344,44 +342,35 @@ class InferenceWrapper:
         self.pred_source_theta = self._bank_theta[slot:slot + 1].clone()
         self.pred_source_pose_embed = self._bank_expr[slot:slot + 1].clone() if self._bank_expr_has[slot] else None
         self.pred_source_srt = self._bank_srt[slot:slot + 1].clone() if self._bank_srt_has[slot] else None
-        self._pose_anchor = None                  # (a new current identity: the single stream's relative pose starts again)
+        self._stream.restart(pose_anchor=True)    # (a new current identity: the single stream's relative pose starts again)
 
     def drop_identity(self, slot):
         slot = self._slot(slot)
-        self._bank_used[slot] = False
-        self._bank_pose_has[slot] = 0
-        self._bank_pose_anchor_has[slot] = 0
-        self._bank_srt_has[slot] = False
-        self._bank_expr_has[slot] = False
-        self.reset_expression_state([slot])
+        self._bank_used[slot] = self._bank_srt_has[slot] = self._bank_expr_has[slot] = False
+        self._bank_streams.restart([slot], pose_ema=True, pose_anchor=True, expression=True)
 
     def reset_expression_state(self, slots=None):
         """Restart the expression controls' streams (the relative-transfer anchor and the expression EMA): slots=None clears the
         single-identity state and every slot's; otherwise only the given bank slots'"""
-        if slots is None:
-            self._expr_anchor = self._expr_ema = None
-            slots = range(self.identity_capacity)
-        elif not isinstance(slots, (list, tuple, range, torch.Tensor)):
-            slots = [slots]
-        slots = [self._slot(int(k), occupied=False) for k in slots]
-        if self._bank_expr is not None and slots:
-            rows = torch.tensor(slots, dtype=torch.int64).to(self.device)
-            self._bank_expr_anchor_has.index_fill_(0, rows, 0)
-            self._bank_expr_ema_has.index_fill_(0, rows, 0)
+        self._restart(slots, expression=True)
 
     def reset_pose_state(self, slots=None):
         """Restart smooth_pose and the head-pose controls' relative transfer: slots=None clears the single-identity state
         (`self.theta`, the relative-pose anchor) and every slot's stream; otherwise only the streams of the given bank slots"""
+        self._restart(slots, pose_ema=True, pose_anchor=True)
+
+    def _restart(self, slots, **which):
+        """slots=None: the single stream and every slot's; a slot or several: theirs (StreamStates.restart)"""
         if slots is None:
-            self.theta = self._pose_anchor = None
-            if self.identity_capacity > 0:
-                self._bank_pose_has.zero_()
-                self._bank_pose_anchor_has.zero_()
+            self._stream.restart(**which)
+            if self._bank_streams is not None:
+                self._bank_streams.restart(**which)
             return
-        for k in ([slots] if not isinstance(slots, (list, tuple, range, torch.Tensor)) else slots):
-            k = self._slot(int(k), occupied=False)
-            self._bank_pose_has[k] = 0
-            self._bank_pose_anchor_has[k] = 0
+        if not isinstance(slots, (list, tuple, range, torch.Tensor)):
+            slots = [slots]
+        rows = [self._slot(int(k), occupied=False) for k in slots]
+        if rows:
+            self._bank_streams.restart(rows, **which)
 
     def identities(self):
         """occupied slots, ascending"""
@@ -602,9 +591,7 @@ class InferenceWrapper:
             self._bank_used[k] = True
             self._bank_expr_has[k] = self._bank_expr is not None
             self._bank_srt_has[k] = has_srt
-        self.reset_expression_state(plan.slots)
-        self._bank_pose_has.index_fill_(0, rows64, 0)              # a new identity starts a new smooth_pose stream
-        self._bank_pose_anchor_has.index_fill_(0, rows64, 0)       # ... and a new relative-pose stream
+        self._bank_streams.restart(rows64, pose_ema=True, pose_anchor=True, expression=True)      # new identities: new streams
         return plan.slots
 
     def _frame_identities(self, identities, n=None):
@@ -827,8 +814,8 @@ class InferenceWrapper:
     def _pose_controls(self, theta, ids_dev, mix, mix_old, smooth):
         """forward()'s order (infer.py:568-581) on a batch of driver thetas IN FRAME ORDER, on the device: mix against each
         frame's identity (bank slot ids_dev[i], or the current identity), then smooth_pose (ops.theta_ema_scan, bit for bit
-        hostglue.ema_scan = the reference's per-frame loop) -- with a bank one stream per slot, else the single stream whose
-        state `self.theta` ([4,4], None before the first frame) carries from call to call as the reference's does"""
+        hostglue.ema_scan = the reference's per-frame loop) -- with a bank one stream per slot, else the single stream, whose
+        state (`self.theta` reads it) carries from call to call as the reference's does"""
         theta = theta.to(self.device).float().contiguous()
         if theta.shape[0] == 0:
             return theta
@@ -837,177 +824,40 @@ class InferenceWrapper:
                 theta = ops.mixing_theta(theta, self._source_theta('mix=True'), None, mix_old)
             else:
                 theta = ops.mixing_theta(theta, self._bank_theta, ids_dev, mix_old)
-        if smooth and ids_dev is not None:
-            theta = ops.theta_ema_scan(theta, ids_dev, self._bank_pose, self._bank_pose_has, self.pose_momentum)
-        elif smooth:
-            state = torch.zeros((1, 4, 4), device=self.device, dtype=torch.float32)
-            has = torch.zeros((1,), device=self.device, dtype=torch.int32)
-            if self.theta is not None:
-                state.copy_(self.theta.reshape(1, 4, 4))
-                has.fill_(1)
-            theta = ops.theta_ema_scan(theta, None, state, has, self.pose_momentum)
-            self.theta = state[0]
+        if smooth:
+            st = self._stream if ids_dev is None else self._bank_streams
+            theta = ops.theta_ema_scan(theta, ids_dev, st.theta, st.theta_has, self.pose_momentum)
         return theta
 
-    def _expression_plan(self, expression, n_rows, ids, where, faces=False):
-        """The checks of expression= (an ExpressionControls or a mapping with its fields), before anything is launched -> None
-        (no control: nothing will be launched, no state touched) or what _expression_controls needs: relative, smooth, momentum
-        (None without smooth), gain (None = 1.0 | a float | a device [rows]), offset (None | a device [E] or [rows,E]), override
-        (None | a device [rows,E]), step1 = the part about the neutral runs, scan = a control that walks the frame order.
-        n_rows: the rows of the call where known; ids: the per-row slots (host tensor) or None = the current identity."""
-        ex = ExpressionControls.of(expression)
-        if ex is None:
-            return None
-        m = float(ex.momentum)
-        if not 0.0 < m <= 1.0:
-            raise ValueError(f"expression momentum {ex.momentum} is not in (0, 1]")
-        relative, smooth = bool(ex.relative), bool(ex.smooth)
-
-        def rows(t, what, dims):
-            t = torch.as_tensor(t).detach().float()
-            if t.dim() not in dims:
-                raise ValueError(f"expression {what}: a tensor of {' or '.join(str(d) for d in dims)} dimensions, got {tuple(t.shape)}")
-            if t.dim() == (1 if what == 'gain' else 2) and n_rows is not None and t.shape[0] != n_rows:
-                raise ValueError(f"expression {what} has {t.shape[0]} rows for {n_rows} rows of the call")
-            return t
-        gain = ex.gain
-        if isinstance(gain, torch.Tensor) and gain.dim() == 0 or not isinstance(gain, torch.Tensor) and not hasattr(gain, '__len__'):
-            gain = None if float(gain) == 1.0 else float(gain)
-        else:
-            gain = rows(gain, 'gain', (1,))
-        offset = None if ex.offset is None else rows(ex.offset, 'offset', (1, 2))
-        override = None if ex.override is None else rows(ex.override, 'override', (2,))
-        if override is not None and where != 'animate_frames':
-            raise ValueError(f"expression override= replaces the expression embedder of animate_frames: {where}"
-                             + ("'s expressions are inputs already" if where == 'animate' else " takes none"))
-        if not (relative or smooth or gain is not None or offset is not None or override is not None):
-            return None
-        step1 = relative or gain is not None
-        if (relative or smooth) and ids is None and (faces or where == 'animate_streams'):
-            raise ValueError("expression relative / smooth follow every face track as its identity's stream: give identities")
-        widths = {t.shape[-1] for t in (offset, override) if t is not None}
-        if step1 and ids is None:
-            if self.pred_source_pose_embed is None:
-                raise ValueError("expression relative / gain work about the current identity's source expression, which is missing: "
-                                 "call forward with a source_image (or load_identity a slot that has one) first")
-            widths.add(self.pred_source_pose_embed.numel())
-        elif step1:
-            missing = [k for k in sorted(set(ids.tolist())) if not self._bank_expr_has[k]]
-            if missing:
-                raise ValueError(f"expression relative / gain work about each identity's source expression: slot {missing[0]} has none")
-        if ids is not None and (step1 or smooth) and self._bank_expr is not None:
-            widths.add(self._bank_expr.shape[1])
-        if len(widths) > 1:
-            raise ValueError(f"expression rows of different widths: {sorted(widths)}")
-        up = lambda t: None if t is None else t.to(self.device).contiguous()
-        return Namespace(relative=relative, smooth=smooth, momentum=m if smooth else None, step1=step1, scan=relative or smooth,
-                         gain=up(gain) if isinstance(gain, torch.Tensor) else gain, offset=up(offset), override=up(override))
-
-    @staticmethod
-    def _expression_rows(t, r0, m, what):
-        if t.shape[0] < r0 + m:
-            raise ValueError(f"expression {what} has {t.shape[0]} rows, the frames run past it")
-        return t[r0:r0 + m]
-
     def _expression_controls(self, values, ids_dev, ex, r0):
-        """The expression controls `ex` (_expression_plan) on values [m,E] = the rows r0 ... of the call IN FRAME ORDER, one launch
-        (ops.expression_controls, bit for bit hostglue.expression_controls): every row about its identity's source expression
-        (bank slot ids_dev[i], or the current identity's), and for relative / smooth within its slot's stream, whose anchor and
-        EMA the bank carries -- without identities the one stream whose state `_expr_anchor` / `_expr_ema` carries from call to
-        call as `self.theta` does for smooth_pose"""
+        """The expression controls `ex` (control_streams.expression_plan) on values [m,E] = the rows r0 ... of the call IN FRAME
+        ORDER, one launch (ops.expression_controls, bit for bit hostglue.expression_controls): every row about its identity's source
+        expression (bank slot ids_dev[i], or the current identity's), and for relative / smooth within its slot's stream -- without
+        identities the one stream of the current identity (_stream), carried from call to call as smooth_pose's is"""
         values = values.to(self.device).float().contiguous()
         m = values.shape[0]
         if m == 0 or not (ex.step1 or ex.scan or ex.offset is not None):          # (an override alone: nothing to compute)
             return values
-        E = values.shape[1]
-        gain = self._expression_rows(ex.gain, r0, m, 'gain') if isinstance(ex.gain, torch.Tensor) else ex.gain
-        offset = ex.offset if ex.offset is None or ex.offset.dim() == 1 else self._expression_rows(ex.offset, r0, m, 'offset')
-        if ids_dev is not None and (ex.step1 or ex.scan):
-            self._expr_bank(E)
-            return ops.expression_controls(values, ids_dev, self._bank_expr if ex.step1 else None, gain, offset, self._bank_expr_anchor,
-                                           self._bank_expr_anchor_has, self._bank_expr_ema, self._bank_expr_ema_has, ex.relative,
-                                           ex.momentum)
-        neutral = None
-        if ex.step1:
-            neutral = self.pred_source_pose_embed.to(self.device).float().reshape(1, -1).contiguous()
-        state = {}
-        for name, on in (('_expr_anchor', ex.relative), ('_expr_ema', ex.smooth)):
-            if on:
-                rows = torch.zeros((1, E), device=self.device, dtype=torch.float32)
-                has = torch.zeros((1,), device=self.device, dtype=torch.int32)
-                if getattr(self, name) is not None:
-                    rows.copy_(getattr(self, name).reshape(1, -1))
-                    has.fill_(1)
-                state[name] = (rows, has)
-        anchor, has_anchor = state.get('_expr_anchor', (None, None))
-        ema, has_ema = state.get('_expr_ema', (None, None))
-        out = ops.expression_controls(values, None, neutral, gain, offset, anchor, has_anchor, ema, has_ema, ex.relative, ex.momentum)
-        for name, (rows, _) in state.items():
-            setattr(self, name, rows[0])
-        return out
-
-    def _head_pose_plan(self, head_pose, n_rows, ids, where, target_theta, faces=False):
-        """The checks of head_pose= (a HeadPoseControls or a mapping with its fields), before anything is launched -> None (no
-        control: nothing will be launched, no state touched) or what _head_pose_controls needs: relative, frontal, gain and zoom
-        (None = 1.0 | a float | a device [rows]), rotation_offset and translation_offset (None | a device [3] or [rows,3]),
-        step1 = the part about the source pose runs.  n_rows: the rows of the call where known; ids: the per-row slots (host
-        tensor) or None = the current identity."""
-        hp = HeadPoseControls.of(head_pose)
-        if hp is None:
-            return None
-        relative, frontal = bool(hp.relative), bool(hp.frontal)
-
-        def per_row(v, what):
-            if isinstance(v, torch.Tensor) and v.dim() == 0 or not isinstance(v, torch.Tensor) and not hasattr(v, '__len__'):
-                return None if float(v) == 1.0 else float(v)
-            t = torch.as_tensor(v).detach().float()
-            if t.dim() != 1:
-                raise ValueError(f"head_pose {what}: a float or one value per row, got {tuple(t.shape)}")
-            if n_rows is not None and t.shape[0] != n_rows:
-                raise ValueError(f"head_pose {what} has {t.shape[0]} rows for {n_rows} rows of the call")
-            return t
-
-        def rows3(v, what):
-            if v is None:
-                return None
-            t = torch.as_tensor(v).detach().float()
-            if t.dim() not in (1, 2) or t.shape[-1] != 3:
-                raise ValueError(f"head_pose {what}: [3] or [rows,3], got {tuple(t.shape)}")
-            if t.dim() == 2 and n_rows is not None and t.shape[0] != n_rows:
-                raise ValueError(f"head_pose {what} has {t.shape[0]} rows for {n_rows} rows of the call")
-            return t
-        gain, zoom = per_row(hp.gain, 'gain'), per_row(hp.zoom, 'zoom')
-        rot, trans = rows3(hp.rotation_offset, 'rotation_offset'), rows3(hp.translation_offset, 'translation_offset')
-        if not (relative or frontal or gain is not None or zoom is not None or rot is not None or trans is not None):
-            return None
-        if frontal and relative:
-            raise ValueError("head_pose frontal zeroes the yaw, pitch and translation that relative transfers: choose one")
-        if not target_theta:
-            raise ValueError("head_pose= edits the driver's head pose, target_theta=False renders in the source's: nothing of the "
-                             "edit would be rendered")
-        step1 = relative or gain is not None
-        if relative and ids is None and (faces or where == 'animate_streams'):
-            raise ValueError("head_pose relative follows every face track as its identity's stream: give identities")
-        if step1 and ids is None:
-            if self.pred_source_srt is None:
-                raise ValueError("head_pose relative / gain work about the current identity's source (scale, rotation, translation), "
-                                 "which is missing: call forward with a source_image and the head-pose regressor, or a "
-                                 "custome_source_theta_embed given as the triple, first")
-        elif step1:
-            missing = [k for k in sorted(set(ids.tolist())) if not self._bank_srt_has[k]]
-            if missing:
-                raise ValueError(f"head_pose relative / gain work about each identity's source (scale, rotation, translation): "
-                                 f"slot {missing[0]} has none")
-        up = lambda t: t.to(self.device).contiguous() if isinstance(t, torch.Tensor) else t
-        return Namespace(relative=relative, frontal=frontal, step1=step1, gain=up(gain), zoom=up(zoom), rotation_offset=up(rot),
-                         translation_offset=up(trans))
+        gain = control_streams.rows_of(ex.gain, r0, m, 'expression gain')
+        offset = control_streams.rows_of(ex.offset, r0, m, 'expression offset', whole=1)
+        if not (ex.step1 or ex.scan):                                            # (an offset alone: no source, no stream)
+            return ops.expression_controls(values, offset=offset)
+        st = self._stream if ids_dev is None else self._bank_streams
+        if ids_dev is None:
+            st.expression(values.shape[1])
+            neutral = self.pred_source_pose_embed.to(self.device).float().reshape(1, -1).contiguous() if ex.step1 else None
+        else:
+            self._expr_bank(values.shape[1])
+            neutral = self._bank_expr if ex.step1 else None
+        return ops.expression_controls(values, ids_dev, neutral, gain, offset, st.expr_anchor, st.expr_anchor_has, st.expr_ema,
+                                       st.expr_ema_has, ex.relative, ex.momentum)
 
     def _head_pose_controls(self, srt, ids_dev, hp, r0):
-        """The head-pose controls `hp` (_head_pose_plan) on srt = (scale, rotation, translation) of the rows r0 ... of the call
-        IN FRAME ORDER, one launch (ops.head_pose_controls, bit for bit hostglue.head_pose_controls) -> (the edited rows [m,9],
-        their theta [m,4,4]): every row about its identity's source pose (bank slot ids_dev[i], or the current identity's), and
-        for `relative` within its slot's stream, whose anchor the bank carries -- without identities the one stream whose anchor
-        `_pose_anchor` carries from call to call.  pred_target_srt is left as the edited triple."""
+        """The head-pose controls `hp` (control_streams.head_pose_plan) on srt = (scale, rotation, translation) of the rows r0 ... of
+        the call IN FRAME ORDER, one launch (ops.head_pose_controls, bit for bit hostglue.head_pose_controls) -> (the edited rows
+        [m,9], their theta [m,4,4]): every row about its identity's source pose (bank slot ids_dev[i], or the current identity's),
+        and for `relative` within its slot's stream -- without identities the one stream of the current identity (_stream), whose
+        anchor carries from call to call.  pred_target_srt is left as the edited triple."""
         if srt is None or len(srt) != 3 or any(t is None for t in srt):
             raise RuntimeError("head_pose= edits the (scale, rotation, translation) of the head-pose regressor, which returned none: "
                                "a 'head_pose_regressor' callable must return (theta, scale, rotation, translation)")
@@ -1016,33 +866,26 @@ class InferenceWrapper:
         if m == 0:
             return torch.empty((0, 9), device=self.device), torch.empty((0, 4, 4), device=self.device)
 
-        def rows(t, what, whole):
-            """the rows r0 ... r0 + m of a per-row value; a float, a `whole`-dimensional tensor or None as it is"""
-            if not isinstance(t, torch.Tensor) or t.dim() == whole:
-                return t
-            if t.shape[0] < r0 + m:
-                raise ValueError(f"head_pose {what} has {t.shape[0]} rows, the frames run past it")
-            return t[r0:r0 + m].contiguous()
-        gain, zoom = rows(hp.gain, 'gain', 0), rows(hp.zoom, 'zoom', 0)
-        rot, trans = rows(hp.rotation_offset, 'rotation_offset', 1), rows(hp.translation_offset, 'translation_offset', 1)
-        if ids_dev is not None and hp.step1:
-            out = ops.head_pose_controls(scale, rotation, translation, ids_dev, self._bank_srt, gain, rot, trans, zoom,
-                                         self._bank_pose_anchor, self._bank_pose_anchor_has, hp.relative, hp.frontal)
-        else:
-            source = self.pred_source_srt.to(self.device).float().reshape(1, 9).contiguous() if hp.step1 else None
-            anchor = has = None
-            if hp.relative:
-                anchor = torch.zeros((1, 9), device=self.device, dtype=torch.float32)
-                has = torch.zeros((1,), device=self.device, dtype=torch.int32)
-                if self._pose_anchor is not None:
-                    anchor.copy_(self._pose_anchor.reshape(1, 9))
-                    has.fill_(1)
-            out = ops.head_pose_controls(scale, rotation, translation, None, source, gain, rot, trans, zoom, anchor, has, hp.relative,
-                                         hp.frontal)
-            if hp.relative:
-                self._pose_anchor = anchor[0]
+        gain, zoom = (control_streams.rows_of(getattr(hp, name), r0, m, f'head_pose {name}', whole=0) for name in ('gain', 'zoom'))
+        rot, trans = (control_streams.rows_of(getattr(hp, name), r0, m, f'head_pose {name}', whole=1)
+                      for name in ('rotation_offset', 'translation_offset'))
+        st, source = self._stream if ids_dev is None else self._bank_streams, None
+        if hp.step1:
+            source = self._bank_srt if ids_dev is not None else self.pred_source_srt.to(self.device).float().reshape(1, 9).contiguous()
+        # (without step1 there is no source and no stream: every row by itself)
+        out = ops.head_pose_controls(scale, rotation, translation, ids_dev if hp.step1 else None, source, gain, rot, trans, zoom,
+                                     st.pose_anchor, st.pose_anchor_has, hp.relative, hp.frontal)
         self.pred_target_srt = tuple(out[0][:, i:i + 3] for i in (0, 3, 6))
         return out
+
+    def _control_plans(self, expression, head_pose, n_rows, ids, where, target_theta, faces=False):
+        """the checks of expression= and head_pose=, before anything is launched -> (ex, hp): what _expression_controls and
+        _head_pose_controls need, None for a keyword that asks for nothing (control_streams.expression_plan, head_pose_plan)"""
+        ex = control_streams.expression_plan(expression, n_rows, ids, where, faces, self.device, self.pred_source_pose_embed,
+                                             self._bank_expr_has, None if self._bank_expr is None else self._bank_expr.shape[1])
+        hp = control_streams.head_pose_plan(head_pose, n_rows, ids, where, target_theta, faces, self.device, self.pred_source_srt,
+                                            self._bank_srt_has)
+        return ex, hp
 
     def _render_theta(self, theta, ids_dev, target_theta):
         """target_theta=False: the frame is rendered in its identity's own head pose (infer.py:584), a device-side gather"""
@@ -1068,7 +911,7 @@ class InferenceWrapper:
         self.target_theta = target_theta
         with torch.no_grad():
             if reset_tracking:
-                self.center = self.size = self.theta = self.delta_yaw = self.delta_pitch = None
+                self.center = self.size = self.delta_yaw = self.delta_pitch = None
                 self._crop_tracker = None
                 self.reset_pose_state()
                 self.reset_expression_state()
@@ -1117,7 +960,7 @@ class InferenceWrapper:
                     pred_source_theta, srt = (out[0], tuple(out[1:4])) if isinstance(out, (tuple, list)) else (out, None)
                 self.pred_source_theta = pred_source_theta
                 self.pred_source_srt = self._srt9(srt) if srt is not None and len(srt) == 3 and all(t is not None for t in srt) else None
-                self._pose_anchor = None          # a new source: the single stream's relative pose starts again
+                self._stream.restart(pose_anchor=True)     # a new source: the single stream's relative pose starts again
                 if custome_source_pose_embed is not None:
                     source_pose_embed = custome_source_pose_embed.to(self.device).float().contiguous()
                 else:
@@ -1222,8 +1065,7 @@ class InferenceWrapper:
         masks_of, ids = self._preflight(N, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
         if out_format == "nv12":
             self._nv12_size(masks_of)
-        ex = self._expression_plan(expression, N, ids, 'animate')
-        hp = self._head_pose_plan(head_pose, N, ids, 'animate', target_theta)
+        ex, hp = self._control_plans(expression, head_pose, N, ids, 'animate', target_theta)
         out_kind = "f32" if not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
         lo, hi = parallel.shard_range(N, self.rank, self.world)
         ids_dev = None if ids is None else ids[lo:hi].to(self.device)
@@ -1482,8 +1324,8 @@ class InferenceWrapper:
         loops need beside the frames: wins = the (x0, y0, s, s) of every row of the call (None: whole frames), n_rows their
         number where it is known.  -> masks_of, ids (_preflight), matte_fn (_paste_matte), out_kind (_render's `out`), fmt =
         (frame_format, colorspace, full_range), ring = the pinned ring (None without to_host; with `arena` and paste_back a
-        frames.ArenaRing), upload_stream, ex = the expression controls (_expression_plan; None: none), hp = the head-pose controls
-        (_head_pose_plan; None: none), and the loop's keywords as they came."""
+        frames.ArenaRing), upload_stream, ex, hp = the expression and the head-pose controls (_control_plans;
+        None: none), and the loop's keywords as they came."""
         frames_mod.check_format(frame_format, colorspace)
         if out_format is not None:
             frames_mod.check_format(out_format, colorspace, "out_format")
@@ -1509,8 +1351,7 @@ class InferenceWrapper:
         if out_format == "nv12" and as_uint8 and not paste_back:
             self._nv12_size(masks_of)
         out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
-        ex = self._expression_plan(expression, n_rows, ids, where, faces)
-        hp = self._head_pose_plan(head_pose, n_rows, ids, where, target_theta, faces)
+        ex, hp = self._control_plans(expression, head_pose, n_rows, ids, where, target_theta, faces)
         host_ring = None if not to_host else (frames_mod.ArenaRing(self.device, ring) if arena and paste_back
                                               else frames_mod.HostRing(self.device, ring, batch_size))
         return Namespace(masks_of=masks_of, ids=ids, matte_fn=matte_fn, out_kind=out_kind, fmt=(frame_format, colorspace, bool(full_range)),
@@ -1539,7 +1380,7 @@ class InferenceWrapper:
         ex = plan.ex
         if pose is None:
             if ex is not None and ex.override is not None:
-                pose = self._expression_rows(ex.override, row0, crops.shape[0], 'override')
+                pose = control_streams.rows_of(ex.override, row0, crops.shape[0], 'expression override')
             else:
                 pose, _ = self._expression(crops, theta if align is None else align, 'a driver call')
             if ex is not None:
@@ -1620,7 +1461,7 @@ class InferenceWrapper:
                 # everywhere), gathered in row order and scanned on every rank, as the thetas above; then the render
                 r0, r1 = rows(0, n)
                 if ex.override is not None:
-                    every = self._expression_rows(ex.override, r0, r1 - r0, 'override')
+                    every = control_streams.rows_of(ex.override, r0, r1 - r0, 'expression override')
                 else:
                     keep_crops = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
                     again = frames_mod.uploaded(chunk, [sp for sp in with_faces if sp[0] not in kept], self.device, plan.upload_stream)
@@ -1751,14 +1592,12 @@ class InferenceWrapper:
         spans = frames_mod.face_spans(counts, 0, len(order), batch_size)
         wins = [w for s, t in order for w in faces[s][0][first[s][t]:first[s][t + 1]]]
         identities = None if not idents or idents[0] is None else [i for s, t in order for i in idents[s][first[s][t]:first[s][t + 1]]]
-        expression = self._stream_expression(expression, [st.get('expression') for st in streams], [len(flat) for flat, _ in faces],
-                                             [(s, first[s][t], first[s][t + 1]) for s, t in order])
+        n_faces, spans_of = [len(flat) for flat, _ in faces], [(s, first[s][t], first[s][t + 1]) for s, t in order]
+        expression = control_streams.stream_expression(expression, [st.get('expression') for st in streams], n_faces, spans_of)
+        head_pose = control_streams.stream_head_pose(head_pose, [st.get('head_pose') for st in streams], n_faces, spans_of)
         plan = self._video_plan(len(wins), wins, identities, batch_size, ring, to_host, smooth_pose, True, mix, mix_old, target_theta,
                                 paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format, colorspace,
-                                full_range, arena=True, expression=expression, where='animate_streams',
-                                head_pose=self._stream_head_pose(head_pose, [st.get('head_pose') for st in streams],
-                                                                 [len(flat) for flat, _ in faces],
-                                                                 [(s, first[s][t], first[s][t + 1]) for s, t in order]))
+                                full_range, arena=True, expression=expression, where='animate_streams', head_pose=head_pose)
         S, host_ring = self.cfg["image_size"], plan.ring
         ids_dev = None if plan.ids is None else plan.ids.to(self.device)
         rows = frames_mod.face_offsets(counts)                                   # rows[i] = faces in front of frame i of the order
@@ -1827,102 +1666,6 @@ class InferenceWrapper:
             for tag, buf in host_ring.drain():
                 yield handed_out(tag, buf)
 
-    @staticmethod
-    def _stream_expression(expression, per_stream, n_faces, order):
-        """animate_streams' expression= and the streams' own 'expression' mappings -> the ExpressionControls of the call's rows:
-        per_stream[s] = stream s's {'gain', 'offset'} or None, n_faces[s] its faces, order = (stream, first face, end) of every
-        frame of the batch order.  Without a stream's own values the call's scalar gain and [E] offset stay as they are."""
-        ex = ExpressionControls.of(expression)
-        if ex is not None:
-            if ex.override is not None:
-                raise ValueError("expression override= replaces the expression embedder of animate_frames: animate_streams takes none")
-            if isinstance(ex.gain, torch.Tensor) and ex.gain.dim() > 0 or hasattr(ex.gain, '__len__') and not isinstance(ex.gain, torch.Tensor):
-                raise ValueError("animate_streams' expression gain is one float: per-face values belong to a stream's 'expression'")
-            if ex.offset is not None and torch.as_tensor(ex.offset).dim() != 1:
-                raise ValueError("animate_streams' expression offset is one [E] row: per-face rows belong to a stream's 'expression'")
-        if all(p is None for p in per_stream):
-            return ex
-        ex = ex or ExpressionControls()
-        gains, offsets = [], []
-        for s, p in enumerate(per_stream):
-            p = {} if p is None else dict(p)
-            unknown = sorted(set(p) - {'gain', 'offset'})
-            if unknown:
-                raise ValueError(f"stream {s}: its 'expression' takes 'gain' and 'offset', not {unknown[0]!r}")
-            g = torch.as_tensor(p.get('gain', ex.gain)).detach().float()
-            if g.dim() > 1 or g.dim() == 1 and g.shape[0] != n_faces[s]:
-                raise ValueError(f"stream {s}: expression gain {tuple(g.shape)} is not a float or one per face ({n_faces[s]})")
-            gains.append(g.expand(n_faces[s]))
-            o = p.get('offset', ex.offset)
-            if o is not None:
-                o = torch.as_tensor(o).detach().float()
-                if o.dim() not in (1, 2) or o.dim() == 2 and o.shape[0] != n_faces[s]:
-                    raise ValueError(f"stream {s}: expression offset {tuple(o.shape)} is not [E] or one row per face ({n_faces[s]})")
-                o = o.expand(n_faces[s], o.shape[-1])
-            offsets.append(o)
-        widths = {o.shape[1] for o in offsets if o is not None}
-        if len(widths) > 1:
-            raise ValueError(f"expression offsets of different widths: {sorted(widths)}")
-        if widths:
-            E = widths.pop()
-            offsets = [torch.zeros((n_faces[s], E)) if o is None else o for s, o in enumerate(offsets)]
-        gain = torch.cat([gains[s][a:b] for s, a, b in order]) if order else torch.zeros(0)
-        offset = torch.cat([offsets[s][a:b] for s, a, b in order]) if order and offsets[0] is not None else None
-        return ExpressionControls(relative=ex.relative, smooth=ex.smooth, momentum=ex.momentum, offset=offset,
-                                  gain=gain if bool((gain != 1.0).any()) else 1.0)
-
-    @staticmethod
-    def _stream_head_pose(head_pose, per_stream, n_faces, order):
-        """animate_streams' head_pose= and the streams' own 'head_pose' mappings -> the HeadPoseControls of the call's rows, by
-        _stream_expression's rule: per_stream[s] = stream s's {'gain', 'zoom', 'rotation_offset', 'translation_offset'} or None,
-        n_faces[s] its faces, order = (stream, first face, end) of every frame of the batch order.  Without a stream's own
-        values the call's scalar gain / zoom and [3] offsets stay as they are."""
-        hp = HeadPoseControls.of(head_pose)
-        scalar = lambda v: isinstance(v, torch.Tensor) and v.dim() == 0 or not isinstance(v, torch.Tensor) and not hasattr(v, '__len__')
-        if hp is not None:
-            for name in ('gain', 'zoom'):
-                if not scalar(getattr(hp, name)):
-                    raise ValueError(f"animate_streams' head_pose {name} is one float: per-face values belong to a stream's 'head_pose'")
-            for name in ('rotation_offset', 'translation_offset'):
-                v = getattr(hp, name)
-                if v is not None and tuple(torch.as_tensor(v).shape) != (3,):
-                    raise ValueError(f"animate_streams' head_pose {name} is one [3] row: per-face rows belong to a stream's 'head_pose'")
-        if all(p is None for p in per_stream):
-            return hp
-        hp = hp or HeadPoseControls()
-        cols = {name: [] for name in ('gain', 'zoom', 'rotation_offset', 'translation_offset')}
-        for s, p in enumerate(per_stream):
-            p = {} if p is None else dict(p)
-            unknown = sorted(set(p) - set(cols))
-            if unknown:
-                raise ValueError(f"stream {s}: its 'head_pose' takes 'gain', 'zoom', 'rotation_offset' and 'translation_offset', "
-                                 f"not {unknown[0]!r}")
-            for name in ('gain', 'zoom'):
-                g = torch.as_tensor(p.get(name, getattr(hp, name))).detach().float()
-                if g.dim() > 1 or g.dim() == 1 and g.shape[0] != n_faces[s]:
-                    raise ValueError(f"stream {s}: head_pose {name} {tuple(g.shape)} is not a float or one per face ({n_faces[s]})")
-                cols[name].append(g.expand(n_faces[s]))
-            for name in ('rotation_offset', 'translation_offset'):
-                o = p.get(name, getattr(hp, name))
-                if o is not None:
-                    o = torch.as_tensor(o).detach().float()
-                    if o.dim() not in (1, 2) or o.shape[-1] != 3 or o.dim() == 2 and o.shape[0] != n_faces[s]:
-                        raise ValueError(f"stream {s}: head_pose {name} {tuple(o.shape)} is not [3] or one row per face ({n_faces[s]}, 3)")
-                    o = o.expand(n_faces[s], 3)
-                cols[name].append(o)
-        out = {}
-        for name in ('gain', 'zoom'):
-            v = torch.cat([cols[name][s][a:b] for s, a, b in order]) if order else torch.zeros(0)
-            out[name] = v if bool((v != 1.0).any()) else 1.0
-        for name in ('rotation_offset', 'translation_offset'):
-            rows = cols[name]
-            if all(o is None for o in rows) or not order:
-                out[name] = None
-            else:
-                rows = [torch.zeros((n_faces[s], 3)) if o is None else o for s, o in enumerate(rows)]
-                out[name] = torch.cat([rows[s][a:b] for s, a, b in order])
-        return HeadPoseControls(relative=hp.relative, frontal=hp.frontal, **out)
-
     def share_source(self, src_rank=0):
         """RCCL broadcast of the per-identity cache computed on `src_rank`: canonical volume
         (25 MB) + idt_embed (32 KB) + source theta."""
@@ -1947,5 +1690,5 @@ class InferenceWrapper:
         self.pred_source_theta = cache["theta_src"]
         self.pred_source_pose_embed = cache["expr_src"].clone() if cache["expr_src"].numel() else None
         self.pred_source_srt = cache["srt_src"].clone() if cache["srt_src"].numel() else None
-        self._pose_anchor = None
+        self._stream.restart(pose_anchor=True)
         self._set_source_cache(canonical=cache["canonical"], idt_embed=cache["idt_embed"])

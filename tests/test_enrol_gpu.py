@@ -140,7 +140,7 @@ def _wrapper(project, tiny, **kw):
 
 
 def _bank_bytes(w):
-    return [t.clone() for t in (w._bank_cl, w._bank_idt, w._bank_theta, w._bank_pose_has)] + [list(w._bank_used)]
+    return [t.clone() for t in (w._bank_cl, w._bank_idt, w._bank_theta, w._bank_streams.theta_has)] + [list(w._bank_used)]
 
 
 def _bank_equal(a, b):
@@ -242,12 +242,12 @@ def test_wrapper_enrol_identities(project, tiny):
         assert _same(wv._bank_cl[k], wf._bank_cl[5 - k]) and _same(wv._bank_theta[k], wf._bank_theta[5 - k]), k
 
     # explicit slots overwrite occupied ones; every written slot starts a new smooth_pose stream
-    w._bank_pose_has.fill_(1)
+    w._bank_streams.theta_has.fill_(1)
     assert w.enrol_identities(imgs[:2], slots=[4, 5], **dict(kw, source_masks=kw["source_masks"][:2],
                                                             custome_idt_embed=kw["custome_idt_embed"][:2],
                                                             custome_source_pose_embed=kw["custome_source_pose_embed"][:2],
                                                             custome_source_theta_embed=kw["custome_source_theta_embed"][:2])) == [4, 5]
-    assert w._bank_pose_has.cpu().tolist() == [1, 1, 1, 1, 0, 0]
+    assert w._bank_streams.theta_has.cpu().tolist() == [1, 1, 1, 1, 0, 0]
     assert _same(w._bank_cl[4], w._bank_cl[0]) and _same(w._bank_cl[5], w._bank_cl[1])     # (chunk (0, 2) again)
     with pytest.raises(ValueError):
         w.enrol_identities(imgs[:1], **dict(kw, source_masks=kw["source_masks"][:1],

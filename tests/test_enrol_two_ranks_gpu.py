@@ -34,7 +34,7 @@ slots = w.enrol_identities([i[0] for i in ids], source_masks=[torch.ones(1, 1, S
                            custome_source_theta_embed=torch.cat([i[3] for i in ids]))
 assert slots == [0, 1, 2, 3, 4], slots
 out = dict(cl=w._bank_cl.cpu(), idt=w._bank_idt.cpu(), theta=w._bank_theta.cpu(), used=list(w._bank_used),
-           pose_has=w._bank_pose_has.cpu())
+           pose_has=w._bank_streams.theta_has.cpu())
 torch.save(out, os.path.join(%(project)r, "enrol_rank%%d_of%%d.pt" %% (w.rank, w.world)))
 parallel.barrier()
 parallel.shutdown()

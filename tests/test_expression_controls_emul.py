@@ -309,10 +309,10 @@ def test_animate_hands_the_restated_rows_to_the_driver_pass(wrapper):
     got2, _ = _run(w, pose2, srt2, identities=ids2, expression=dict(relative=True, gain=0.5, offset=offset[0], smooth=True, momentum=0.3))
     assert _same(got2, want2)
     # batch sizes: the same rows from the same starting state
-    saved = [t.clone() for t in (w._bank_expr_anchor, w._bank_expr_anchor_has, w._bank_expr_ema, w._bank_expr_ema_has)]
+    saved = [t.clone() for t in (w._bank_streams.expr_anchor, w._bank_streams.expr_anchor_has, w._bank_streams.expr_ema, w._bank_streams.expr_ema_has)]
     rows = []
     for bs in (4, 5, 16):
-        for t, s in zip((w._bank_expr_anchor, w._bank_expr_anchor_has, w._bank_expr_ema, w._bank_expr_ema_has), saved):
+        for t, s in zip((w._bank_streams.expr_anchor, w._bank_streams.expr_anchor_has, w._bank_streams.expr_ema, w._bank_streams.expr_ema_has), saved):
             t.copy_(s)
         rows.append(_run(w, pose, srt, batch_size=bs, identities=ids, expression=ex)[0])
     assert _same(rows[0], rows[1]) and _same(rows[0], rows[2])
@@ -334,7 +334,7 @@ def test_animate_hands_the_restated_rows_to_the_driver_pass(wrapper):
     got, _ = _run(w, pose, srt, identities=ids, expression=ex)
     assert _same(got, host(pose, ids, neutrals, gain, offset, True, 0.3))
     assert w.forward(reset_tracking=True) is None
-    assert w._bank_expr_anchor_has.tolist() == [0, 0, 0] and w._bank_expr_ema_has.tolist() == [0, 0, 0]
+    assert w._bank_streams.expr_anchor_has.tolist() == [0, 0, 0] and w._bank_streams.expr_ema_has.tolist() == [0, 0, 0]
     # load_identity restores the slot's source expression as the current identity's
     w.hot_path = None
     import emoportraits_amd.ops as ops
@@ -358,13 +358,13 @@ def test_animate_single_identity_stream_is_carried_on_the_wrapper(wrapper):
     assert _same(got, host(pose, None, w.neutrals[1:2], 1.5, None, True, 0.3))
     got, _ = _run(w, pose[:7], srt, batch_size=5, expression=ex)                # (state from the first call)
     assert _same(got, host(pose[:7], None, w.neutrals[1:2], 1.5, None, True, 0.3))
-    assert _same(w._expr_anchor.numpy(), pose[0].numpy()) and _same(w._expr_ema.numpy(), host.st[2][0])
+    assert _same(w._stream.expr_anchor[0].numpy(), pose[0].numpy()) and _same(w._stream.expr_ema[0].numpy(), host.st[2][0])
     w.reset_expression_state()
-    assert w._expr_anchor is None and w._expr_ema is None
+    assert w._stream.expr_anchor_has.tolist() == [0] and w._stream.expr_ema_has.tolist() == [0]
     # offset alone needs neither a neutral nor a state
     w.pred_source_pose_embed = None
     got, _ = _run(w, pose, srt, expression=dict(offset=torch.ones(E5)))
-    assert _same(got, (pose + 1).numpy()) and w._expr_anchor is None and w._expr_ema is None
+    assert _same(got, (pose + 1).numpy()) and w._stream.expr_anchor_has.tolist() == [0] and w._stream.expr_ema_has.tolist() == [0]
 
 
 def test_defaults_launch_nothing_and_change_nothing(wrapper):
@@ -379,7 +379,7 @@ def test_defaults_launch_nothing_and_change_nothing(wrapper):
         w.lib.calls.clear()
         runs.append(_run(w, pose, srt, **kw, **({} if expression == "absent" else dict(expression=expression))))
         assert w.lib.calls.get("emo_expr_controls_f32", 0) == 0
-        assert w._bank_expr_anchor_has.tolist() == [0, 0, 0] and w._bank_expr_ema_has.tolist() == [0, 0, 0]
+        assert w._bank_streams.expr_anchor_has.tolist() == [0, 0, 0] and w._bank_streams.expr_ema_has.tolist() == [0, 0, 0]
     for got in runs[1:]:
         assert np.array_equal(got[0], runs[0][0]) and np.array_equal(got[1], runs[0][1])
     assert np.array_equal(runs[0][0], pose.numpy())

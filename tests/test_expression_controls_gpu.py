@@ -245,18 +245,18 @@ def test_store_and_load_keep_the_source_expression_and_a_new_identity_restarts_i
     pose, _ = _run_frames(w, rec, frames, batch_size=B, identities=ids, expression=ex)
     embedded = torch.cat(rec.embedded)
     assert _same(pose, _restate(embedded, ids, neutrals, np.full(8, 1.5), None, state, True, 0.3))
-    assert w._bank_expr_anchor_has.tolist() == [1, 1, 0] and w._bank_expr_ema_has.tolist() == [1, 1, 0]
+    assert w._bank_streams.expr_anchor_has.tolist() == [1, 1, 0] and w._bank_streams.expr_ema_has.tolist() == [1, 1, 0]
     img, idt, th = _sources(tiny, 1)[0]
     w.forward(source_image=img, crop=False, source_mask=torch.ones(1, 1, S, S), custome_idt_embed=idt,
               custome_source_pose_embed=neutral_of(tiny, 9), custome_source_theta_embed=th)
     assert w.store_identity(0) == 0
-    assert w._bank_expr_anchor_has.tolist() == [0, 1, 0] and w._bank_expr_ema_has.tolist() == [0, 1, 0]
+    assert w._bank_streams.expr_anchor_has.tolist() == [0, 1, 0] and w._bank_streams.expr_ema_has.tolist() == [0, 1, 0]
     neutrals[0] = neutral_of(tiny, 9)[0]
     state[1][0] = state[3][0] = 0
     pose, _ = _run_frames(w, rec, frames, batch_size=B, identities=ids, expression=ex)
     assert _same(pose, _restate(embedded, ids, neutrals, np.full(8, 1.5), None, state, True, 0.3))
     w.drop_identity(1)
-    assert w._bank_expr_anchor_has.tolist() == [1, 0, 0] and w._bank_expr_has == [True, False, True]
+    assert w._bank_streams.expr_anchor_has.tolist() == [1, 0, 0] and w._bank_expr_has == [True, False, True]
 
 
 @pytest.mark.parametrize("use_graphs", [False, True], ids=["eager", "graphs"])
@@ -273,4 +273,4 @@ def test_defaults_are_bit_identical_to_a_call_without_the_keyword(project, tiny,
     for pose, img in runs[1:]:
         assert _same(pose, runs[0][0]) and _same(img, runs[0][1])
     assert _same(runs[0][0], torch.cat(rec.embedded))
-    assert w._bank_expr_anchor_has.tolist() == [0, 0, 0] and w._bank_expr_ema_has.tolist() == [0, 0, 0]
+    assert w._bank_streams.expr_anchor_has.tolist() == [0, 0, 0] and w._bank_streams.expr_ema_has.tolist() == [0, 0, 0]

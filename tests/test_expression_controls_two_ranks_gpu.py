@@ -58,7 +58,7 @@ for call, kw in enumerate((dict(mix=True, smooth_pose=True, smooth_per_identity=
     for b0, img in w.animate_frames([clip[:n], clip[n:]], batch_size=3, identities=ids, expression=ex, to_host=False, as_uint8=False, **kw):
         for j in range(img.shape[0]):
             out[(call, b0 + j)] = (last["pose"][j].cpu().clone(), img[j].cpu().clone())
-state = [t.cpu().clone() for t in (w._bank_expr_anchor, w._bank_expr_anchor_has, w._bank_expr_ema, w._bank_expr_ema_has)]
+state = [t.cpu().clone() for t in (w._bank_streams.expr_anchor, w._bank_streams.expr_anchor_has, w._bank_streams.expr_ema, w._bank_streams.expr_ema_has)]
 torch.save(dict(rows=out, state=state), os.path.join(%(project)r, "expr_rank%%d_of%%d.pt" %% (w.rank, w.world)))
 parallel.barrier()
 parallel.shutdown()

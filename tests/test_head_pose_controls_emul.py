@@ -389,17 +389,17 @@ def test_animate_hands_the_restated_thetas_to_the_driver_pass(wrapper):
     got2, _ = _run(w, pose2, srt2, identities=ids2, head_pose=dict(relative=True, gain=0.5, rotation_offset=rot[0]))
     assert _same(got2, want2)
     # batch sizes: the same thetas from the same starting state; mix and smooth_pose work on the edited thetas
-    saved = w._bank_pose_anchor.clone(), w._bank_pose_anchor_has.clone()
+    saved = w._bank_streams.pose_anchor.clone(), w._bank_streams.pose_anchor_has.clone()
     rows = []
     for bs in (4, 5, 16):
-        w._bank_pose_anchor.copy_(saved[0]), w._bank_pose_anchor_has.copy_(saved[1])
+        w._bank_streams.pose_anchor.copy_(saved[0]), w._bank_streams.pose_anchor_has.copy_(saved[1])
         rows.append(_run(w, pose, srt, batch_size=bs, identities=ids, head_pose=hp)[0])
     assert _same(rows[0], rows[1]) and _same(rows[0], rows[2])
     _, edited = host(srt, ids, w.sources, gain, rot, trans, zoom, True)
     assert _same(rows[0], edited)
     from emoportraits_amd import hostglue
-    w._bank_pose_anchor.copy_(saved[0]), w._bank_pose_anchor_has.copy_(saved[1])
-    w._bank_pose_has.zero_()
+    w._bank_streams.pose_anchor.copy_(saved[0]), w._bank_streams.pose_anchor_has.copy_(saved[1])
+    w._bank_streams.theta_has.zero_()
     smoothed, _ = _run(w, pose, srt, identities=ids, head_pose=hp, smooth_pose=True, smooth_per_identity=True)
     want_s = np.empty_like(edited)
     for k in range(3):
@@ -424,7 +424,7 @@ def test_animate_hands_the_restated_thetas_to_the_driver_pass(wrapper):
     got, _ = _run(w, pose, srt, identities=ids, head_pose=hp)
     assert _same(got, host(srt, ids, sources, gain, rot, trans, zoom, True)[1])
     w.reset_pose_state()
-    assert w._bank_pose_anchor_has.tolist() == [0, 0, 0]
+    assert w._bank_streams.pose_anchor_has.tolist() == [0, 0, 0]
     import emoportraits_amd.ops as ops
     vol = ops.volume_to_channels_first
     try:
@@ -447,13 +447,13 @@ def test_animate_single_identity_anchor_is_carried_on_the_wrapper(wrapper):
     assert _same(got, host(srt, None, w.sources[1:2], 1.5, None, None, 1.1, True)[1])
     got, _ = _run(w, pose[:7], [t[:7] for t in srt], batch_size=5, head_pose=hp)                 # (the anchor of the first call)
     assert _same(got, host([t[:7] for t in srt], None, w.sources[1:2], 1.5, None, None, 1.1, True)[1])
-    assert _same(w._pose_anchor.numpy(), host.st[0][0])
+    assert _same(w._stream.pose_anchor[0].numpy(), host.st[0][0])
     w.reset_pose_state()
-    assert w._pose_anchor is None
+    assert w._stream.pose_anchor_has.tolist() == [0]
     # offsets, zoom and frontal need neither a source pose nor a state
     w.pred_source_srt = None
     got, _ = _run(w, pose, srt, head_pose=dict(rotation_offset=[0.2, -0.1, 0.0], frontal=True))
-    assert _same(got, HostState(1, w.lib)(srt, None, None, None, [0.2, -0.1, 0.0], None, None, False, True)[1]) and w._pose_anchor is None
+    assert _same(got, HostState(1, w.lib)(srt, None, None, None, [0.2, -0.1, 0.0], None, None, False, True)[1]) and w._stream.pose_anchor_has.tolist() == [0]
 
 
 def test_defaults_launch_nothing_and_change_nothing(wrapper):
@@ -467,7 +467,7 @@ def test_defaults_launch_nothing_and_change_nothing(wrapper):
         w.reset_pose_state()
         w.lib.calls.clear()
         runs.append(_run(w, pose, srt, **kw, **({} if head_pose == "absent" else dict(head_pose=head_pose))))
-        assert w.lib.calls.get(NAME, 0) == 0 and w._bank_pose_anchor_has.tolist() == [0, 0, 0] and w._pose_anchor is None
+        assert w.lib.calls.get(NAME, 0) == 0 and w._bank_streams.pose_anchor_has.tolist() == [0, 0, 0] and w._stream.pose_anchor_has.tolist() == [0]
     for got in runs[1:]:
         assert np.array_equal(got[0], runs[0][0]) and np.array_equal(got[1], runs[0][1])
 

@@ -227,7 +227,7 @@ def test_defaults_are_bit_identical_to_a_call_without_the_keyword(project, tiny,
     for head_pose in ("absent", None, HeadPoseControls(), {}):
         w.reset_pose_state()
         runs.append(_run_frames(w, rec, frames, **kw, **({} if head_pose == "absent" else dict(head_pose=head_pose))))
-        assert w._bank_pose_anchor_has.tolist() == [0, 0, 0] and w._pose_anchor is None
+        assert w._bank_streams.pose_anchor_has.tolist() == [0, 0, 0] and w._stream.pose_anchor_has.tolist() == [0]
     for theta, img in runs[1:]:
         assert _same(theta, runs[0][0]) and _same(img, runs[0][1])
 
@@ -290,4 +290,4 @@ def test_two_streams_of_different_frame_sizes_are_the_faces_path_on_the_canvas_c
     w.reset_pose_state()
     got = TS._items(w.animate_streams([dict(st, head_pose=o) for st, o in zip(streams, own)], to_host=False, as_uint8=False, head_pose=call, **kw))
     assert torch.equal(torch.cat([o for _, _, o in got]), want) and not torch.equal(want, plain)
-    assert w._bank_pose_anchor_has.tolist() == [1, 1]
+    assert w._bank_streams.pose_anchor_has.tolist() == [1, 1]

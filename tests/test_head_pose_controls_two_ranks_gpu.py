@@ -69,7 +69,7 @@ for call, kw in enumerate(({}, dict(mix=True, smooth_pose=True, smooth_per_ident
     assert srt.shape[0] == theta.shape[0] == len(rows)
     for j, i in enumerate(rows):
         out[(call, i)] = (srt[j].clone(), theta[j].clone(), imgs[j].clone())
-state = [t.cpu().clone() for t in (w._bank_pose_anchor, w._bank_pose_anchor_has)]
+state = [t.cpu().clone() for t in (w._bank_streams.pose_anchor, w._bank_streams.pose_anchor_has)]
 torch.save(dict(rows=out, state=state), os.path.join(%(project)r, "hp_rank%%d_of%%d.pt" %% (w.rank, w.world)))
 parallel.barrier()
 parallel.shutdown()

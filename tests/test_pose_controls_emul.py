@@ -376,7 +376,7 @@ def test_animate_bank_mix_and_smooth_feed_the_predicted_thetas(wrapper, mix_old)
                     smooth_per_identity=True)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
     assert w.forward(reset_tracking=True) is None
-    assert w._bank_pose_has.tolist() == [0, 0, 0]
+    assert w._bank_streams.theta_has.tolist() == [0, 0, 0]
 
 
 def test_animate_single_identity_controls(wrapper):

@@ -184,7 +184,7 @@ def test_bank_mix_smooth_source_pose_equal_each_identitys_own_run(project, tiny,
             _collect(w.animate_frames(frames, batch_size=B, ring=2, identities=ids, mix=True, smooth_pose=True,
                                       smooth_per_identity=True, target_theta=target_theta))
         render, expr = rec.thetas()
-        state = (w._bank_pose.clone(), w._bank_pose_has.clone())
+        state = (w._bank_streams.theta.clone(), w._bank_streams.theta_has.clone())
         # each identity's own run: load it, one stream from scratch (the host scan), its frames only
         singles = {}
         for k in range(3):
@@ -284,7 +284,7 @@ for b0, u8 in w.animate_frames([frames[:N // 2], frames[N // 2:]], batch_size=4,
                                smooth_per_identity=True, mix=True):
     for j in range(u8.shape[0]):
         out[b0 + j] = u8[j].clone()
-torch.save(dict(frames=out, state=w._bank_pose.cpu(), has=w._bank_pose_has.cpu()),
+torch.save(dict(frames=out, state=w._bank_streams.theta.cpu(), has=w._bank_streams.theta_has.cpu()),
            os.path.join(%(project)r, "pose_rank%%d_of%%d.pt" %% (w.rank, w.world)))
 parallel.barrier()
 parallel.shutdown()
