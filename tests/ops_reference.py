@@ -1,0 +1,459 @@
+"""fp64 references and error checkers for single launches of the non-convolution ops the passes make (a helper module, not a
+test file; the sibling of conv_reference.py): volume_to_channels_last, add, add_rows_indexed, avgpool, upsample_trilinear,
+groupnorm_affine (own pass / TileStats / RunSums), small_gemm, projector_finalize, mat4_inverse and grid_sample3d (delta= /
+theta=, with and without vol_index).
+
+Every reference is plain torch in fp64, computed one sample at a time on whatever device the inputs live on; none calls a
+kernel of the project.  Every checker compares a launch's output with that reference sample by sample and returns a dict of
+figures: 'frames' (the samples checked), 'frame_fig' (the worst figure of each, in 'unit'), 'worst', 'worst_frame' and
+'failures' (the violations; empty when the launch passes) -- one host synchronisation per launch.
+
+The bounds are the operation's own arithmetic (u = 2^-24, the unit roundoff of fp32) or constants the suite already states
+(conv_reference.FP32_FRAME, STATS_TOL, SPLIT_MAX and the fp16 split's mean margin); each checker's docstring derives its own.
+"""
+import torch
+import torch.nn.functional as F
+
+from conv_reference import FP32_FRAME, SPLIT_MAX, SPLIT_MEAN, STATS_TOL
+
+U = 2.0 ** -24                      # unit roundoff of fp32 (round to nearest)
+TINY = 2.0 ** -149                  # the smallest fp32 subnormal: what a rounding can cost where the result underflows
+# the sampler against ATen's fp32 CPU kernel on the same inputs: the margins the conv checker grants a split kernel over the
+# fp32 kernel (a different, equally valid order of fp32 operations), each plus SAMPLER_FLOOR x mean |ref|
+SAMPLER_MAX, SAMPLER_MEAN, SAMPLER_FLOOR = SPLIT_MAX, SPLIT_MEAN["f16x2"], 1e-7
+
+
+def _f64(t):
+    return t.to(torch.float64)
+
+
+def _bounded_row(got, ref, bound):
+    """-> [worst |err| / bound, outputs outside the bound (NaN included), max |err|, max |ref|] as one fp64 tensor"""
+    assert ref.dtype == torch.float64 and bound.dtype == torch.float64, (ref.dtype, bound.dtype)
+    if got.shape != ref.shape:
+        raise ValueError(f"output {tuple(got.shape)} vs reference {tuple(ref.shape)}")
+    e = (_f64(got) - ref).abs()
+    bad = ~(e <= bound)
+    ratio = torch.where(e == 0, torch.zeros_like(e), torch.nan_to_num(e / bound.clamp_min(1e-300), nan=float("inf")))
+    return torch.stack([ratio.max(), _f64(bad.sum()), torch.nan_to_num(e, nan=float("inf")).max(), ref.abs().max()])
+
+
+def _bounded_fig(rows, frames, what):
+    """figures of a launch held to a per-output bound: rows = _bounded_row per frame"""
+    t = torch.stack(rows).cpu()                       # one host synchronisation per launch
+    frame_fig = t[:, 0].tolist()
+    w = max(range(len(frames)), key=lambda i: frame_fig[i])
+    bad = [f"{what}: frame {n}: {int(t[i, 1])} outputs outside the bound, worst {t[i, 0]:.3g} x bound (max err {t[i, 2]:.3e}, "
+           f"max|ref| {t[i, 3]:.3e})" for i, n in enumerate(frames) if t[i, 1] != 0]
+    return dict(frames=list(frames), frame_fig=frame_fig, unit="x bound", worst=frame_fig[w], worst_frame=frames[w],
+                max_err=float(t[:, 2].max()), ref_max=float(t[:, 3].max()), failures=bad)
+
+
+def _frames(n, frames):
+    return list(range(n)) if frames is None else list(frames)
+
+
+# ---- volume_to_channels_last ---------------------------------------------------------------------------------------------
+def channels_last_fp64(vol):
+    """[N,C,D,H,W] -> [N,D,H,W,C] in fp64 (a permutation: no arithmetic)"""
+    return _f64(vol).permute(0, 2, 3, 4, 1).contiguous()
+
+
+def check_channels_last(out, vol, frames=None):
+    """bit equality with the permutation, sample by sample; the figure is the count of differing elements"""
+    fr = _frames(vol.shape[0], frames)
+    if tuple(out.shape) != (vol.shape[0],) + tuple(vol.shape[2:]) + (vol.shape[1],):
+        raise ValueError(f"output {tuple(out.shape)} is not the channels-last form of {tuple(vol.shape)}")
+    rows = [(out[n].view(torch.int32) != vol[n].permute(1, 2, 3, 0).contiguous().view(torch.int32)).sum() for n in fr]
+    t = torch.stack(rows).cpu().tolist()
+    w = max(range(len(fr)), key=lambda i: t[i])
+    bad = [f"volume_to_channels_last: frame {n}: {t[i]} elements differ from the permutation" for i, n in enumerate(fr) if t[i]]
+    return dict(frames=fr, frame_fig=[float(v) for v in t], unit="differing elements", worst=float(t[w]), worst_frame=fr[w],
+                failures=bad)
+
+
+# ---- add / add_rows_indexed ----------------------------------------------------------------------------------------------
+def _alpha32(alpha):
+    return float(torch.tensor(float(alpha), dtype=torch.float32))      # the kernel takes alpha as an fp32 argument
+
+
+def add_fp64(a, b, alpha=1.0):
+    """(a + b[i % period]) * alpha in fp64 from the fp32 operands; period = b.numel() (b tiles the flattened a)"""
+    if a.numel() % b.numel():
+        raise ValueError("b does not tile a")
+    out = (_f64(a).reshape(-1, b.numel()) + _f64(b).reshape(1, -1)) * _alpha32(alpha)
+    return out.reshape(a.shape)
+
+
+def add_rows_indexed_fp64(a, table, index, alpha=1.0):
+    """(a[b] + table[index[b]]) * alpha in fp64; an index outside [0, K) gives a zero row"""
+    K = table.shape[0]
+    idx = index.to(torch.int64)
+    ok = (idx >= 0) & (idx < K)
+    rows = _f64(table).reshape(K, -1)[idx.clamp(0, K - 1)]
+    out = (_f64(a).reshape(a.shape[0], -1) + rows) * _alpha32(alpha)
+    out = torch.where(ok[:, None], out, torch.zeros_like(out))
+    return out.reshape(a.shape)
+
+
+def _check_add(out, ref, frames, what):
+    """The kernel rounds twice: s = fl(a + b) = (a + b)(1 + d1), out = fl(s alpha) = (a + b) alpha (1 + d1)(1 + d2), |d| <= u.
+    Per element |out - ref| <= (2u + u^2) |ref| <= 2u (1 + u) |ref|, plus TINY where the product underflows (the fp64 reference
+    itself is exact to 2^-52 |ref|, inside the u^2 term's slack)."""
+    fr = _frames(out.shape[0], frames)
+    rows = []
+    for n in fr:
+        r = ref[n]
+        rows.append(_bounded_row(out[n], r, 2.0 * U * (1.0 + U) * r.abs() + TINY))
+    return _bounded_fig(rows, fr, what)
+
+
+def check_add(out, a, b, alpha=1.0, frames=None):
+    """ops.add against add_fp64 under the per-element bound of _check_add; frames = rows of the leading dimension"""
+    return _check_add(out, add_fp64(a, b, alpha), frames, "add")
+
+
+def check_add_rows_indexed(out, a, table, index, alpha=1.0, frames=None):
+    """ops.add_rows_indexed against add_rows_indexed_fp64 under the same per-element bound (a zero row must be exactly zero)"""
+    return _check_add(out, add_rows_indexed_fp64(a, table, index, alpha), frames, "add_rows_indexed")
+
+
+# ---- avgpool -------------------------------------------------------------------------------------------------------------
+def _pool_windows(v, kernel):
+    """v [C, (D,) H, W] -> [C, Do, kd, Ho, kh, Wo, kw]"""
+    if v.dim() == 3:
+        v = v.unsqueeze(1)
+        kernel = (1,) + tuple(kernel)
+    kd, kh, kw = kernel
+    C, D, H, W = v.shape
+    if D % kd or H % kh or W % kw:
+        raise ValueError(f"window {kernel} does not tile {(D, H, W)}")
+    return v.reshape(C, D // kd, kd, H // kh, kh, W // kw, kw)
+
+
+def avgpool_frames(x, kernel, frames=None):
+    """yields (n, fp64 mean of every window [C, (Do,) Ho, Wo], fp64 max |x| of every window) per sample: AvgPool with
+    stride == kernel, 5-D x with (kd, kh, kw) or 4-D x with (kh, kw)"""
+    for n in _frames(x.shape[0], frames):
+        w = _pool_windows(_f64(x[n]), kernel)
+        mean, amax = w.mean(dim=(2, 4, 6)), w.abs().amax(dim=(2, 4, 6))
+        if x.dim() == 4:
+            mean, amax = mean[:, 0], amax[:, 0]
+        yield n, mean, amax
+
+
+def avgpool_fp64(x, kernel):
+    return torch.stack([m for _, m, _ in avgpool_frames(x, kernel)])
+
+
+def check_avgpool(out, x, kernel, frames=None):
+    """The kernel adds the n = kd kh kw values of a window one after the other in fp32 and multiplies by fl(1 / n): n - 1
+    rounded additions (the first lands on 0), the rounding of the reciprocal and of the product, n + 1 roundings.  With M the
+    largest |value| of the window every partial sum is at most k M, so the additions cost at most u M (n (n + 1) / 2 - 1) / n
+    on the mean and the last two u M each: (n + 1) / 2 + 2 - 1 / n <= n + 1 for n >= 2 (n = 1: two roundings).  Per output
+    |out - ref| <= (n + 1) u M (1 + u) with M of its OWN window (an fp64 max-pool of |x|), plus TINY."""
+    n_win = 1
+    for k in kernel:
+        n_win *= int(k)
+    fr = _frames(x.shape[0], frames)
+    rows = [_bounded_row(out[n], mean, (n_win + 1) * U * (1.0 + U) * amax + TINY) for n, mean, amax in avgpool_frames(x, kernel, fr)]
+    return _bounded_fig(rows, fr, f"avgpool {tuple(kernel)}")
+
+
+# ---- upsample_trilinear --------------------------------------------------------------------------------------------------
+def _lin_taps(out_size, in_size, factor, device):
+    """ATen's area_pixel_compute_source_index for align_corners=False and scale 1 / factor: src = 0.5 (o + 0.5) - 0.5 clamped at
+    0 -> (i0, i1, l0, l1); all exact in binary for factor 2"""
+    o = torch.arange(out_size, dtype=torch.float64, device=device)
+    if factor == 1:
+        i = o.to(torch.int64)
+        return i, i, torch.ones_like(o), torch.zeros_like(o)
+    if factor != 2:
+        raise ValueError("factors are 1 or 2")
+    src = (0.5 * (o + 0.5) - 0.5).clamp_min(0.0)
+    i0 = src.floor().to(torch.int64)
+    i1 = i0 + (i0 < in_size - 1).to(torch.int64)
+    l1 = src - i0
+    return i0, i1, 1.0 - l1, l1
+
+
+def upsample_trilinear_frames(x, factors, frames=None):
+    """yields (n, fp64 F.interpolate(x[n], scale_factor=factors, mode='trilinear') [C, Do, Ho, Wo], fp64 largest |tap| that
+    carries weight in each output) per sample of the 5-D x"""
+    D, H, W = x.shape[2:]
+    taps = [_lin_taps(s * f, s, f, x.device) for s, f in zip((D, H, W), factors)]
+    for n in _frames(x.shape[0], frames):
+        v = _f64(x[n])
+        a = v.abs()
+        for axis in (3, 2, 1):
+            i0, i1, l0, l1 = taps[axis - 1]
+            shape = [1, 1, 1, 1]
+            shape[axis] = -1
+            v = l0.view(shape) * v.index_select(axis, i0) + l1.view(shape) * v.index_select(axis, i1)
+            a1 = torch.where((l1 > 0).view(shape), a.index_select(axis, i1), torch.zeros((), dtype=torch.float64, device=x.device))
+            a = torch.maximum(a.index_select(axis, i0), a1)
+        yield n, v, a
+
+
+def upsample_trilinear_fp64(x, factors):
+    return torch.stack([v for _, v, _ in upsample_trilinear_frames(x, factors)])
+
+
+UPSAMPLE_ROUNDINGS = 7
+
+
+def check_upsample_trilinear(out, x, factors, frames=None):
+    """The kernel evaluates ATen's nested form t0 (h0 (w0 a + w1 b) + h1 (...)) + t1 (...): every intermediate is a convex
+    combination of the taps, at most M = the largest |tap| of the output in magnitude, and the longest chain from a tap to the
+    output passes UPSAMPLE_ROUNDINGS = 7 rounded operations (product and sum per axis, and the last sum): per output
+    |out - ref| <= 7 u M (1 + u) with M of its OWN taps, plus TINY."""
+    fr = _frames(x.shape[0], frames)
+    rows = [_bounded_row(out[n], ref, UPSAMPLE_ROUNDINGS * U * (1.0 + U) * amax + TINY)
+            for n, ref, amax in upsample_trilinear_frames(x, factors, fr)]
+    return _bounded_fig(rows, fr, f"upsample_trilinear {tuple(factors)}")
+
+
+# ---- groupnorm_affine ----------------------------------------------------------------------------------------------------
+def groupnorm_affine_frames(x, gamma=None, beta=None, ada_gamma=None, ada_beta=None, groups=32, eps=1e-5, frames=None):
+    """yields (n, scale [C], shift [C]) in fp64 such that GroupNorm(groups)(x)[n, c] == x[n, c] * scale[c] + shift[c], from a
+    direct fp64 reduction of x[n].  gamma / beta: the static affine; ada_gamma / ada_beta [N, C] (any row stride): the adaptive
+    form WITH the reference's quirk (csrc/groupnorm.hip: AdaptiveGroupNorm applies its static affine first): sc ag, sh ag + ab"""
+    C = x.shape[1]
+    cg = C // groups
+    if C % groups:
+        raise ValueError(f"{C} channels in {groups} groups")
+    for n in _frames(x.shape[0], frames):
+        v = _f64(x[n]).reshape(groups, -1)
+        mean = v.mean(-1)
+        var = ((v - mean[:, None]) ** 2).mean(-1)
+        rstd = (1.0 / torch.sqrt(var + float(torch.tensor(eps, dtype=torch.float32)))).repeat_interleave(cg)
+        mean = mean.repeat_interleave(cg)
+        sc = rstd * _f64(gamma) if gamma is not None else rstd
+        sh = -mean * sc
+        if beta is not None:
+            sh = sh + _f64(beta)
+        if ada_gamma is not None:
+            ag, ab = _f64(ada_gamma[n]), _f64(ada_beta[n])
+            sc, sh = sc * ag, sh * ag + ab
+        yield n, sc, sh
+
+
+def groupnorm_affine_fp64(x, gamma=None, beta=None, ada_gamma=None, ada_beta=None, groups=32, eps=1e-5):
+    rows = list(groupnorm_affine_frames(x, gamma, beta, ada_gamma, ada_beta, groups, eps))
+    return torch.stack([s for _, s, _ in rows]), torch.stack([h for _, _, h in rows])
+
+
+def check_groupnorm_affine(scale, shift, x, gamma=None, beta=None, ada_gamma=None, ada_beta=None, groups=32, eps=1e-5, frames=None):
+    """(scale, shift) of any of the three forms (own pass, TileStats, RunSums) against the fp64 statistics of x itself, under
+    the suite's STATS_TOL as test_conv_epilogue_groupnorm_statistics applies it: |scale - ref| <= STATS_TOL max |ref scale| of
+    the launch, |shift - ref| <= STATS_TOL max(1, max |ref shift| of the launch).  The figure is the larger of the two ratios."""
+    fr = _frames(x.shape[0], frames)
+    rows = []
+    for n, sc, sh in groupnorm_affine_frames(x, gamma, beta, ada_gamma, ada_beta, groups, eps, fr):
+        ds, dh = (_f64(scale[n]) - sc).abs(), (_f64(shift[n]) - sh).abs()
+        rows.append(torch.stack([torch.nan_to_num(ds, nan=float("inf")).max(), sc.abs().max(),
+                                 torch.nan_to_num(dh, nan=float("inf")).max(), sh.abs().max()]))
+    t = torch.stack(rows).cpu()
+    s_ref, h_ref = float(t[:, 1].max()), max(1.0, float(t[:, 3].max()))
+    s_rel, h_rel = (t[:, 0] / max(s_ref, 1e-300)).tolist(), (t[:, 2] / h_ref).tolist()
+    frame_fig = [max(a, b) / STATS_TOL for a, b in zip(s_rel, h_rel)]
+    w = max(range(len(fr)), key=lambda i: frame_fig[i])
+    bad = []
+    for i, n in enumerate(fr):
+        if not s_rel[i] <= STATS_TOL:
+            bad.append(f"groupnorm_affine: frame {n}: scale differs by {s_rel[i]:.3e} of max|scale| > {STATS_TOL:g}")
+        if not h_rel[i] <= STATS_TOL:
+            bad.append(f"groupnorm_affine: frame {n}: shift differs by {h_rel[i]:.3e} of max(1, max|shift|) > {STATS_TOL:g}")
+    return dict(frames=fr, frame_fig=frame_fig, unit="x STATS_TOL", worst=frame_fig[w], worst_frame=fr[w],
+                scale_rel=max(s_rel), shift_rel=max(h_rel), failures=bad)
+
+
+# ---- small_gemm / projector_finalize -------------------------------------------------------------------------------------
+def small_gemm_fp64(A, B, NN):
+    """C[b][m][:NN] = sum_k A[m][k] B[b][k][:NN] in fp64: A [M, K], B [batch, K * NN] in any shape -> [batch, M, NN]"""
+    M, K = A.shape
+    return torch.einsum("mk,bkn->bmn", _f64(A), _f64(B).reshape(B.shape[0], K, NN))
+
+
+def _check_rows(pairs, frames, what):
+    """every (out, ref) pair, each batch row against FP32_FRAME x max |ref of that row| (the suite's bound of an fp32 dot
+    product, conv_reference.FP32_FRAME)"""
+    rows = []
+    for n in frames:
+        worst = []
+        for out, ref in pairs:
+            assert ref.dtype == torch.float64
+            if tuple(out.shape) != tuple(ref.shape):
+                raise ValueError(f"output {tuple(out.shape)} vs reference {tuple(ref.shape)}")
+            e = torch.nan_to_num((_f64(out[n]) - ref[n]).abs(), nan=float("inf")).max()
+            worst.append(e / ref[n].abs().max().clamp_min(1e-300))
+        rows.append(torch.stack(worst).max())
+    t = torch.stack(rows).cpu().tolist()
+    w = max(range(len(frames)), key=lambda i: t[i])
+    bad = [f"{what}: frame {n}: max err {t[i]:.3e} of max|ref| > {FP32_FRAME:g}" for i, n in enumerate(frames) if not t[i] <= FP32_FRAME]
+    return dict(frames=list(frames), frame_fig=t, unit="of max|ref|", worst=t[w], worst_frame=frames[w], failures=bad)
+
+
+def check_small_gemm(out, A, B, NN, frames=None):
+    return _check_rows([(out, small_gemm_fp64(A, B, NN))], _frames(B.shape[0], frames), f"small_gemm NN={NN}")
+
+
+def projector_finalize_fp64(T, V, norm_of_row, gamma, beta):
+    """T [B, R, E], V [n, E, 2], norm_of_row [R], gamma / beta [R] -> (ada_gamma, ada_beta) [B, R] in fp64:
+    gamma[r] + sum_e T[b, r, e] V[norm_of_row[r], e, 0] and beta[r] + sum_e T[b, r, e] V[norm_of_row[r], e, 1]"""
+    Vr = _f64(V)[norm_of_row.to(torch.int64)]                            # [R, E, 2]
+    d = torch.einsum("bre,rej->brj", _f64(T), Vr)
+    return _f64(gamma)[None] + d[..., 0], _f64(beta)[None] + d[..., 1]
+
+
+def check_projector_finalize(ag, ab, T, V, norm_of_row, gamma, beta, frames=None):
+    rg, rb = projector_finalize_fp64(T, V, norm_of_row, gamma, beta)
+    return _check_rows([(ag, rg), (ab, rb)], _frames(T.shape[0], frames), "projector_finalize")
+
+
+# ---- mat4_inverse --------------------------------------------------------------------------------------------------------
+def mat4_inverse_fp64(m):
+    """torch.linalg.inv of the fp32 matrices in fp64 (on the CPU: 4 x 4 matrices, no device solver involved)"""
+    return torch.linalg.inv(_f64(m).cpu())
+
+
+def check_mat4_inverse(out, m, frames=None):
+    """The kernel eliminates in double (error ~ cond 2^-53, nothing at fp32 scale for a head-pose affine) and rounds each
+    entry once: per matrix |out - ref| <= 2^-23 max |inverse| (the rounding of the largest entry is at most 2^-24 of it; the
+    other half is room for the elimination's own error, which a value check cannot tell from the rounding)."""
+    fr = _frames(m.shape[0], frames)
+    ref = mat4_inverse_fp64(m)
+    e = torch.nan_to_num((_f64(out).cpu() - ref).abs(), nan=float("inf")).reshape(m.shape[0], -1).amax(1)
+    lim = 2.0 ** -23 * ref.abs().reshape(m.shape[0], -1).amax(1)
+    fig = [float(e[n] / lim[n].clamp_min(1e-300)) for n in fr]
+    w = max(range(len(fr)), key=lambda i: fig[i])
+    bad = [f"mat4_inverse: matrix {n}: max err {float(e[n]):.3e} > 2^-23 x max|inverse| = {float(lim[n]):.3e}"
+           for n in fr if not bool(e[n] <= lim[n])]
+    return dict(frames=fr, frame_fig=fig, unit="x 2^-23 max|inverse|", worst=fig[w], worst_frame=fr[w], failures=bad)
+
+
+# ---- grid_sample3d -------------------------------------------------------------------------------------------------------
+def lattice(n, device):
+    """torch.linspace(-1, 1, n) in fp32, computed on the CPU (the reference's identity lattice), on `device`"""
+    return torch.linspace(-1, 1, n).to(device)
+
+
+def _ncdhw(v, layout):
+    """one volume in `layout` -> its [C, D, H, W] view"""
+    if layout == "ndhwc":
+        return v.permute(3, 0, 1, 2)
+    if layout == "ncdhw":
+        return v
+    raise ValueError(f"layout {layout!r}: 'ncdhw' or 'ndhwc'")
+
+
+def delta_grid_f32(delta_n):
+    """delta [3, Do, Ho, Wo] of one sample -> grid [Do, Ho, Wo, 3] = identity lattice + delta, ONE fp32 addition per coordinate
+    (the contract of ops.grid_sample3d(delta=))"""
+    _, Do, Ho, Wo = delta_n.shape
+    dev = delta_n.device
+    d = delta_n.float()
+    return torch.stack([lattice(Wo, dev).view(1, 1, Wo) + d[0], lattice(Ho, dev).view(1, Ho, 1) + d[1],
+                        lattice(Do, dev).view(Do, 1, 1) + d[2]], dim=-1)
+
+
+def _lattice_points(size, device, dtype):
+    """[Do, Ho, Wo, 4]: (x, y, z, 1) of the identity lattice, x fastest"""
+    Do, Ho, Wo = size
+    z, y, x = torch.meshgrid(lattice(Do, device).to(dtype), lattice(Ho, device).to(dtype), lattice(Wo, device).to(dtype),
+                             indexing="ij")
+    return torch.stack([x, y, z, torch.ones_like(x)], dim=-1)
+
+
+def theta_grid_fp64(theta_n, size):
+    """theta [3 or 4, 4] of one sample -> grid [Do, Ho, Wo, 3] fp64 = fp64 product of the fp32 lattice and the fp32 theta"""
+    return _lattice_points(size, theta_n.device, torch.float64) @ _f64(theta_n[:3]).t()
+
+
+def theta_grid_f32(theta_n, size):
+    """the same as the reference code builds it: identity_grid.bmm(theta[:, :3].transpose(1, 2)) in fp32"""
+    p = _lattice_points(size, theta_n.device, torch.float32)
+    return p.reshape(1, -1, 4).bmm(theta_n[:3].float().t().unsqueeze(0)).reshape(tuple(size) + (3,))
+
+
+def grid_sample3d_frames(vol, delta=None, theta=None, padding_mode="zeros", in_layout="ncdhw", vol_index=None, frames=None,
+                         yardstick=True):
+    """yields (n, fp64 reference [C, Do, Ho, Wo], yardstick or None) per sample of ops.grid_sample3d(vol, delta= / theta=,
+    padding_mode=, in_layout=, vol_index=): F.grid_sample in fp64 (align_corners=False) on the NCDHW view of the sample's volume
+    -- vol[vol_index[n]] (an index outside the bank: zeros), vol[n], or the one shared volume -- and ATen's fp32 CPU
+    F.grid_sample on the same inputs (delta: the same fp32 grid; theta: the fp32 bmm grid) as the yardstick."""
+    if (delta is None) == (theta is None):
+        raise ValueError("exactly one of delta / theta")
+    N = delta.shape[0] if delta is not None else theta.shape[0]
+    Nv = vol.shape[0]
+    index = None if vol_index is None else vol_index.cpu().tolist()       # (with the launch's one synchronisation in mind: [N] ints)
+    if index is None and Nv not in (1, N):
+        raise ValueError(f"volume batch {Nv} does not match grid batch {N}")
+    cpu_vol = {}
+    for n in _frames(N, frames):
+        k = index[n] if index is not None else (n if Nv > 1 else 0)
+        v = _ncdhw(vol[min(max(k, 0), Nv - 1)], in_layout)
+        C, D, H, W = v.shape
+        if delta is not None:
+            g32 = delta_grid_f32(delta[n])
+            g64 = _f64(g32)
+        else:
+            g64 = theta_grid_fp64(theta[n], (D, H, W))
+        if not 0 <= k < Nv:
+            yield n, torch.zeros((C,) + tuple(g64.shape[:3]), dtype=torch.float64, device=vol.device), \
+                (torch.zeros((C,) + tuple(g64.shape[:3])) if yardstick else None)
+            continue
+        ref = F.grid_sample(_f64(v)[None], g64[None], mode="bilinear", padding_mode=padding_mode, align_corners=False)[0]
+        assert ref.dtype == torch.float64
+        yard = None
+        if yardstick:
+            if k not in cpu_vol:
+                cpu_vol.clear()                                            # (one volume resident at a time)
+                cpu_vol[k] = v.float().cpu().contiguous()
+            g = g32.cpu() if delta is not None else theta_grid_f32(theta[n].cpu(), (D, H, W))
+            yard = F.grid_sample(cpu_vol[k][None], g[None], mode="bilinear", padding_mode=padding_mode, align_corners=False)[0]
+            assert yard.dtype == torch.float32 and yard.device.type == "cpu"
+        yield n, ref, yard
+
+
+def grid_sample3d_fp64(vol, delta=None, theta=None, padding_mode="zeros", in_layout="ncdhw", vol_index=None):
+    return torch.stack([r for _, r, _ in grid_sample3d_frames(vol, delta, theta, padding_mode, in_layout, vol_index, yardstick=False)])
+
+
+def check_grid_sample3d(out, vol, delta=None, theta=None, padding_mode="zeros", in_layout="ncdhw", out_layout="ncdhw",
+                        vol_index=None, frames=None):
+    """The sampler's error is conditioned by the volume's gradient (a coordinate off by one ulp moves the result by ulp x
+    gradient), so it is held to ATen's fp32 CPU F.grid_sample on the same inputs, measured against the same fp64 reference:
+    over the launch, max |err| <= SAMPLER_MAX (2) x the yardstick's and mean |err| <= SAMPLER_MEAN (1.25) x the yardstick's,
+    each plus SAMPLER_FLOOR (1e-7) x mean |ref|.  Figures: 'max_ratio' / 'mean_ratio' to the yardstick; 'frame_fig' is each
+    frame's max |err| over the launch's allowance."""
+    N = delta.shape[0] if delta is not None else theta.shape[0]
+    fr = _frames(N, frames)
+    rows = []
+    for n, ref, yard in grid_sample3d_frames(vol, delta, theta, padding_mode, in_layout, vol_index, fr):
+        got = _f64(_ncdhw(out[n], out_layout))
+        if got.shape != ref.shape:
+            raise ValueError(f"frame {n}: output {tuple(got.shape)} vs reference {tuple(ref.shape)}")
+        e = torch.nan_to_num((got - ref).abs(), nan=float("inf"))
+        ey = (_f64(yard.to(ref.device)) - ref).abs()
+        rows.append(torch.stack([e.max(), e.sum(), ey.max(), ey.sum(), ref.abs().sum(),
+                                 torch.tensor(float(ref.numel()), dtype=torch.float64, device=ref.device)]))
+        del got, e, ey, ref, yard
+    t = torch.stack(rows).cpu()
+    count = float(t[:, 5].sum())
+    max_err, mean_err = float(t[:, 0].max()), float(t[:, 1].sum()) / count
+    y_max, y_mean = float(t[:, 2].max()), float(t[:, 3].sum()) / count
+    scale = float(t[:, 4].sum()) / count
+    allow_max, allow_mean = SAMPLER_MAX * y_max + SAMPLER_FLOOR * scale, SAMPLER_MEAN * y_mean + SAMPLER_FLOOR * scale
+    frame_fig = (t[:, 0] / max(allow_max, 1e-300)).tolist()
+    w = max(range(len(fr)), key=lambda i: frame_fig[i])
+    bad = []
+    if not max_err <= allow_max:
+        bad.append(f"grid_sample3d: max err {max_err:.3e} (frame {fr[w]}) > {SAMPLER_MAX} x ATen fp32's {y_max:.3e} + "
+                   f"{SAMPLER_FLOOR:g} x {scale:.3e}")
+    if not mean_err <= allow_mean:
+        bad.append(f"grid_sample3d: mean err {mean_err:.3e} > {SAMPLER_MEAN} x ATen fp32's {y_mean:.3e} + {SAMPLER_FLOOR:g} x {scale:.3e}")
+    return dict(frames=fr, frame_fig=frame_fig, unit="x allowed max err", worst=frame_fig[w], worst_frame=fr[w],
+                max_err=max_err, mean_err=mean_err, yard_max_err=y_max, yard_mean_err=y_mean, scale=scale,
+                max_ratio=max_err / y_max if y_max > 0 else (0.0 if max_err == 0 else float("inf")),
+                mean_ratio=mean_err / y_mean if y_mean > 0 else (0.0 if mean_err == 0 else float("inf")), failures=bad)

@@ -116,6 +116,23 @@ def test_mat4_inverse():
     got = ops.mat4_inverse(theta.to(DEV).contiguous()).cpu()
     assert (got - theta.inverse()).abs().max().item() <= 1e-6
     assert (got @ theta - torch.eye(4)).abs().max().item() <= 1e-6
+    # B = 70: two blocks of 64 threads with a ragged tail; matrices that need the row exchange among them (m[0][0] = 0: a 90
+    # degree rotation about z, and one whose pivot comes up zero in the second column).  The kernel eliminates in double and
+    # rounds once: every entry within 2^-23 of the matrix's largest |inverse| entry of the fp64 inverse of the same fp32 input
+    g = torch.Generator().manual_seed(70)
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    m = O.get_transform_matrix(1 + 0.1 * rnd(70, 3), 0.5 * rnd(70, 3), 0.1 * rnd(70, 3)).float().contiguous()
+    quarter = torch.tensor([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+    for b, s in ((0, 1.0), (37, 1.1), (63, 0.9), (64, 1.05), (69, 0.95)):                 # first / last thread of both blocks
+        m[b, :3, :3] = s * quarter
+    m[5, :3, :3] = torch.tensor([[1.0, 2.0, 0.0], [0.5, 1.0, 1.0], [0.0, 1.0, 1.0]])      # second pivot zero after the first step
+    assert m[0, 0, 0] == 0 and m[69, 0, 0] == 0
+    got = ops.mat4_inverse(m.to(DEV)).cpu()
+    ref = torch.linalg.inv(m.double())
+    assert got.shape == (70, 4, 4) and torch.isfinite(got).all()
+    err = (got.double() - ref).abs().reshape(70, -1).amax(1)
+    lim = 2.0 ** -23 * ref.abs().reshape(70, -1).amax(1)
+    assert bool((err <= lim).all()), (err / lim).max().item()
 
 
 # ---- whole embedders -------------------------------------------------------------------------------------------------

@@ -80,6 +80,30 @@ def test_r512_bank_pass_equals_each_identitys_own_pass():
         assert _same(mixed[b], single[k][b]), (b, k)
 
 
+@pytest.mark.parametrize("row", [512 * 16, 1000, 64 * 256 + 300], ids=lambda r: f"row{r}")
+def test_add_rows_indexed_equals_add_per_row(row):
+    """ops.add_rows_indexed directly: row b is bit for bit ops.add(a[b], table[index[b]], alpha) -- the warp embedding's
+    [B, 512 * 16] rows, a row length that is no multiple of 256, and one longer than the 64 * 256 elements the capped grid
+    covers in one trip; repeated and permuted indices; an index outside the bank gives a zero row"""
+    from emoportraits_amd import ops
+    g = torch.Generator().manual_seed(row)
+    B, K, alpha = 9, 4, 0.5
+    a = torch.randn(B, row, 1, generator=g).to(DEV)
+    table = torch.randn(K, row, 1, generator=g).to(DEV)
+    for index in ([3, 1, 0, 2, 2, 2, 0, 3, 1], [0, 0, 0, 0, 0, 0, 0, 0, 0], [1, 4, 2, -1, 3, 0, 2 ** 31 - 1, 3, -2 ** 31]):
+        idx = torch.tensor(index, dtype=torch.int32, device=DEV)
+        out = ops.add_rows_indexed(a, table, idx, alpha)
+        assert out.shape == a.shape
+        for b, k in enumerate(index):
+            want = ops.add(a[b], table[k], alpha) if 0 <= k < K else torch.zeros_like(a[b])
+            assert _same(out[b], want), (row, index, b, k)
+    # the rows differ from each other (a fixed row of the table for every b would not pass above), and out= is honoured
+    assert not _same(ops.add(a[0], table[0], alpha), ops.add(a[0], table[1], alpha))
+    buf = torch.full_like(a, 7.0)
+    idx = torch.tensor([3, 1, 0, 2, 2, 2, 0, 3, 1], dtype=torch.int32, device=DEV)
+    assert ops.add_rows_indexed(a, table, idx, alpha, out=buf) is buf and _same(buf, ops.add_rows_indexed(a, table, idx, alpha))
+
+
 # ---- the wrapper ---------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def project(tmp_path_factory, tiny):
