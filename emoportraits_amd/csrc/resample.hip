@@ -293,6 +293,38 @@ __global__ __launch_bounds__(256) void add_rows_indexed_kernel(const float* __re
 __device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f; }
 __device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.0f * A) * x + 8.0f * A) * x - 4.0f * A; }
 
+// The bicubic sample at source index (sy, sx) of an H x W window, C channels at once: fraction, A = -0.75 weights and 4 x 4 taps
+// clamped into the WINDOW, rows first.  tap(yy, xx, w, row) adds the C values of window pixel (yy, xx) times w to row -- a float
+// load, an NV12 decode, a byte / 255 -- so every crop shares these sums and their order: row += tap * wx[b] over b, then
+// acc += row * wy[a] over a.  acc is not clamped.
+template <int C, class Tap>
+__device__ __forceinline__ void bicubic_window(int H, int W, float sy, float sx, Tap tap, float acc[C]) {
+  const float fy = floorf(sy), fx = floorf(sx);
+  const int iy = (int)fy, ix = (int)fx;
+  const float ty = sy - fy, tx = sx - fx;
+  const float A = -0.75f;
+  const float wy[4] = {cubic2(ty + 1.0f, A), cubic1(ty, A), cubic1(1.0f - ty, A), cubic2(2.0f - ty, A)};
+  const float wx[4] = {cubic2(tx + 1.0f, A), cubic1(tx, A), cubic1(1.0f - tx, A), cubic2(2.0f - tx, A)};
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 0.0f;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    int yy = iy - 1 + a;
+    yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
+    float row[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) row[c] = 0.0f;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      int xx = ix - 1 + b;
+      xx = xx < 0 ? 0 : (xx > W - 1 ? W - 1 : xx);
+      tap(yy, xx, wx[b], row);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] += row[c] * wy[a];
+  }
+}
+
 // one output element of F.interpolate(size=(Ho, Wo), align_corners=False) from the H x W window at p (row stride in floats)
 __device__ __forceinline__ float resize2d_at(const float* __restrict__ p, long row_stride, int H, int W, float sh, float sw,
                                              int yo, int xo, int bicubic, int clamp01) {
@@ -307,27 +339,9 @@ __device__ __forceinline__ float resize2d_at(const float* __restrict__ p, long r
                     ly1 * (lx0 * p[y1 * row_stride + x0] + lx1 * p[y1 * row_stride + x1]);
     return clamp01 ? fminf(fmaxf(v, 0.0f), 1.0f) : v;
   }
-  const float fy = floorf(sy), fx = floorf(sx);
-  const int iy = (int)fy, ix = (int)fx;
-  const float ty = sy - fy, tx = sx - fx;
-  const float A = -0.75f;
-  const float wy[4] = {cubic2(ty + 1.0f, A), cubic1(ty, A), cubic1(1.0f - ty, A), cubic2(2.0f - ty, A)};
-  const float wx[4] = {cubic2(tx + 1.0f, A), cubic1(tx, A), cubic1(1.0f - tx, A), cubic2(2.0f - tx, A)};
-  float acc = 0.0f;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    int yy = iy - 1 + a;
-    yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
-    float row = 0.0f;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      int xx = ix - 1 + b;
-      xx = xx < 0 ? 0 : (xx > W - 1 ? W - 1 : xx);
-      row += p[yy * row_stride + xx] * wx[b];
-    }
-    acc += row * wy[a];
-  }
-  return clamp01 ? fminf(fmaxf(acc, 0.0f), 1.0f) : acc;   // bicubic overshoots: crop_image clips (infer.py:350)
+  float acc[1];
+  bicubic_window<1>(H, W, sy, sx, [&](int yy, int xx, float w, float row[1]) { row[0] += p[yy * row_stride + xx] * w; }, acc);
+  return clamp01 ? fminf(fmaxf(acc[0], 0.0f), 1.0f) : acc[0];   // bicubic overshoots: crop_image clips (infer.py:350)
 }
 
 __global__ __launch_bounds__(256) void resize2d_kernel(const float* __restrict__ x, long plane_stride, long row_stride,
@@ -344,28 +358,8 @@ __global__ __launch_bounds__(256) void resize2d_kernel(const float* __restrict__
   }
 }
 
-// The same with one crop window PER SAMPLE (ABI 9; animate_frames' `windows`: the reference crops every frame around its own
-// face box, notebooks/infer.py:301-352): win[n] = (x0, y0, w, h) of sample n inside its Hf x Wf frame, read from device memory,
-// so that a batch of B frames is ONE launch instead of B (round 5: a Python loop of single-frame launches).  Per element the
-// arithmetic is resize2d_kernel's on the window's first pixel: the two are bit-identical.
-__global__ __launch_bounds__(256) void resize2d_windows_kernel(const float* __restrict__ x, long plane_stride, long row_stride,
-                                                               const int* __restrict__ win, float* __restrict__ out, long N,
-                                                               int C, int Ho, int Wo, int bicubic, int clamp01) {
-  const long total = N * C * Ho * Wo;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int xo = (int)(i % Wo);
-    const long r = i / Wo;
-    const int yo = (int)(r % Ho);
-    const long nc = r / Ho;
-    const int* const w4 = win + 4 * (nc / C);
-    const int wx0 = w4[0], wy0 = w4[1], ww = w4[2], wh = w4[3];
-    const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
-    out[i] = resize2d_at(x + nc * plane_stride + (long)wy0 * row_stride + wx0, row_stride, wh, ww, sh, sw, yo, xo, bicubic, clamp01);
-  }
-}
-
-// ---- emo_paste_windows_rgb8 (ABI 15): the inverse of resize2d_windows_kernel's crop -- the rendered S x S image of every frame,
-// resized to its window's side, feathered and blended into the frame's bytes in place (definition: include/emo_hip.h).
+// ---- emo_paste_windows_rgb8 (ABI 15): the inverse of the window crop -- the rendered S x S image of every frame, resized to its
+// window's side, feathered and blended into the frame's bytes in place (definition: include/emo_hip.h; kernel: paste_faces_kernel).
 
 // what a window must satisfy to be pasted (the entry point refuses a host-side list that fails it; the kernel leaves the frame of
 // a device-side window that fails it untouched): a square of side s inside the frame, downscaling by at most 4
@@ -450,61 +444,6 @@ __device__ __forceinline__ float paste_alpha(const float* __restrict__ mt, int S
 // (1 - a) f + a r, truncated like pack_rgb8_kernel: a == 1 gives pack_rgb8's byte, a == 0 the frame's, both exactly
 __device__ __forceinline__ unsigned paste_blend(float a, unsigned f, float r) { return (unsigned)(uint8_t)((1.0f - a) * (float)f + a * r); }
 
-// Work items: (frame, window row, run of 4 pixels), grid-stride over N * smax rows * Q runs with smax a host-known bound of the
-// window sides -- the windows themselves are only read on the device.  A pixel is 3 bytes and a window's x0 is arbitrary, so the
-// runs of a row start at its first pixel whose byte address is a multiple of 4 (`head` = address & 3 pixels in: 3 * head = -head
-// mod 4): a run inside the row is 12 bytes = three aligned dwords, read and written as such; run 0 is the head in front of that
-// pixel and the last run the tail, byte by byte.  No byte outside the window is read or written, and no two items share a dword.
-__global__ __launch_bounds__(256) void paste_windows_kernel(const float* __restrict__ img, const float* __restrict__ matte,
-                                                            const int* __restrict__ win, uint8_t* __restrict__ frames,
-                                                            unsigned total, int S, int Hf, int Wf, unsigned smax, float feather) {
-  const unsigned Q = (smax + 3u) / 4u + 1u;
-  const long SS = (long)S * S;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned q = i % Q, rr = i / Q;
-    const int y = (int)(rr % smax);
-    const long n = rr / smax;
-    const int* const w4 = win + 4 * n;
-    const int wx0 = w4[0], wy0 = w4[1], s = w4[2];
-    if (!paste_window_ok(wx0, wy0, s, w4[3], S, Hf, Wf) || y >= s) continue;
-    uint8_t* const row = frames + ((n * Hf + wy0 + y) * Wf + wx0) * 3;
-    const int head = (int)(reinterpret_cast<uintptr_t>(row) & 3);
-    const int xa = head + 4 * ((int)q - 1);
-    if (xa >= s) continue;
-    const float scale = (float)S / (float)s, inv_scale = __fdiv_rn(1.0f, scale), fs = feather * (float)s;
-    const float* const im = img + n * 3 * SS;
-    const float* const mt = matte ? matte + n * SS : nullptr;
-    AaTaps ty = {0, 0, 0.0f, 0.0f};
-    if (s < S) ty = aa_taps(y, scale, inv_scale, S);
-    if (xa >= 0 && xa + 4 <= s) {
-      uint32_t* const dw = reinterpret_cast<uint32_t*>(row + 3 * xa);
-      const uint32_t f[3] = {dw[0], dw[1], dw[2]};
-      uint32_t o[3] = {0u, 0u, 0u};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float r[3];
-        paste_render(im, S, s, scale, inv_scale, ty, y, xa + j, r);
-        const float a = paste_alpha(mt, S, s, scale, feather, fs, y, xa + j);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const int k = 3 * j + c;
-          o[k >> 2] |= paste_blend(a, (f[k >> 2] >> (8 * (k & 3))) & 255u, r[c]) << (8 * (k & 3));
-        }
-      }
-      dw[0] = o[0]; dw[1] = o[1]; dw[2] = o[2];
-    } else {
-      const int xe = xa + 4 < s ? xa + 4 : s;
-      for (int x = xa < 0 ? 0 : xa; x < xe; ++x) {
-        float r[3];
-        paste_render(im, S, s, scale, inv_scale, ty, y, x, r);
-        const float a = paste_alpha(mt, S, s, scale, feather, fs, y, x);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) row[3 * x + c] = (uint8_t)paste_blend(a, row[3 * x + c], r[c]);
-      }
-    }
-  }
-}
-
 // ---- NV12 frames (ABI 17; the definitions D, E, C and P: include/emo_hip.h).  A frame is Hf rows of Y bytes and Hf / 2 rows of
 // Wf / 2 interleaved (U, V) pairs; both planes share the row pitch and the frame stride, in bytes.
 
@@ -564,64 +503,6 @@ __device__ __forceinline__ void nv12_encode(const Nv12Coef& k, const float rgb[3
 // floor(v) held to 0 ... 255; the callers add the 0.5
 __device__ __forceinline__ unsigned nv12_byte(float v) { return (unsigned)fminf(fmaxf(floorf(v), 0.0f), 255.0f); }
 
-// emo_nv12_windows_f32: one thread per output pixel, all three channels.  The arithmetic per channel is resize2d_at's bicubic on
-// the window (taps clamped into the WINDOW, rows first) with every tap decoded from its bytes where it is used: the 16 taps of
-// neighbouring outputs overlap and the bytes under them (1.5 per pixel) stay in L1 / L2, so nothing is staged in LDS -- the
-// footprint of a block grows with the window's scale (up to 8.4 source pixels per output at 1080 -> 128) and has no bound a
-// static tile could be sized for.  A window as large as the output is scale 1, where the bicubic weights are exactly (0, 1, 0,
-// 0): the pixel's own conversion, taken directly.
-__global__ __launch_bounds__(256) void nv12_windows_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp,
-                                                           long pitch, long fstride, int Hf, int Wf,
-                                                           const int* __restrict__ win, float* __restrict__ out, long N, int Ho,
-                                                           int Wo, Nv12Coef k) {
-  const long HWo = (long)Ho * Wo, total = N * HWo;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int xo = (int)(i % Wo);
-    const long r = i / Wo;
-    const int yo = (int)(r % Ho);
-    const long n = r / Ho;
-    int wx0 = 0, wy0 = 0, ww = Wf, wh = Hf;
-    if (win) { wx0 = win[4 * n]; wy0 = win[4 * n + 1]; ww = win[4 * n + 2]; wh = win[4 * n + 3]; }
-    float* const o = out + n * 3 * HWo + (long)yo * Wo + xo;
-    if (!nv12_window_ok(wx0, wy0, ww, wh, Hf, Wf)) { o[0] = 0.0f; o[HWo] = 0.0f; o[2 * HWo] = 0.0f; continue; }
-    const uint8_t* const fy = yp + n * fstride;
-    const uint8_t* const fuv = uvp + n * fstride;
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    if (ww == Wo && wh == Ho) {
-      nv12_decode_at(fy, fuv, pitch, k, wy0 + yo, wx0 + xo, acc);
-    } else {
-      const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
-      const float sy = sh * ((float)yo + 0.5f) - 0.5f, sx = sw * ((float)xo + 0.5f) - 0.5f;
-      const float fyf = floorf(sy), fxf = floorf(sx);
-      const int iy = (int)fyf, ix = (int)fxf;
-      const float ty = sy - fyf, tx = sx - fxf;
-      const float A = -0.75f;
-      const float wy[4] = {cubic2(ty + 1.0f, A), cubic1(ty, A), cubic1(1.0f - ty, A), cubic2(2.0f - ty, A)};
-      const float wx[4] = {cubic2(tx + 1.0f, A), cubic1(tx, A), cubic1(1.0f - tx, A), cubic2(2.0f - tx, A)};
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        int yy = iy - 1 + a;
-        yy = yy < 0 ? 0 : (yy > wh - 1 ? wh - 1 : yy);
-        float row[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          int xx = ix - 1 + b;
-          xx = xx < 0 ? 0 : (xx > ww - 1 ? ww - 1 : xx);
-          float rgb[3];
-          nv12_decode_at(fy, fuv, pitch, k, wy0 + yy, wx0 + xx, rgb);
-#pragma unroll
-          for (int c = 0; c < 3; ++c) row[c] += rgb[c] * wx[b];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += row[c] * wy[a];
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] = fminf(fmaxf(acc[c], 0.0f), 1.0f);
-    }
-    o[0] = acc[0]; o[HWo] = acc[1]; o[2 * HWo] = acc[2];
-  }
-}
-
 // two adjacent bytes: one 16-bit store where the planes allow it (`pairs`: even addresses, pitch and frame stride)
 __device__ __forceinline__ void nv12_store2(uint8_t* p, unsigned lo, unsigned hi, bool pairs) {
   if (pairs) *reinterpret_cast<uint16_t*>(p) = (uint16_t)(lo | (hi << 8));
@@ -656,58 +537,6 @@ __global__ __launch_bounds__(256) void pack_nv12_kernel(const float* __restrict_
       nv12_store2(yp + n * fstride + (long)(2 * cy + dy) * pitch + 2 * cx, yb[0], yb[1], pairs);
     }
     nv12_store2(uvp + n * fstride + (long)cy * pitch + 2 * cx, nv12_byte(cb * 0.25f + 0.5f), nv12_byte(cr * 0.25f + 0.5f), pairs);
-  }
-}
-
-// emo_paste_windows_nv12: the work item is a chroma sample of the window's covering chroma rectangle with those of its four luma
-// pixels that lie inside the window (the image and the blend weight of each from the rgb8 paste's paste_render01 / paste_alpha),
-// grid-stride over N * cmax * cmax with cmax a host-known bound of the samples along a window side.  A luma byte outside the
-// window is neither read nor written; a chroma pair is touched only if one of its luma pixels is inside.
-__global__ __launch_bounds__(256) void paste_windows_nv12_kernel(const float* __restrict__ img, const float* __restrict__ matte,
-                                                                 const int* __restrict__ win, uint8_t* __restrict__ yp,
-                                                                 uint8_t* __restrict__ uvp, long pitch, long fstride,
-                                                                 unsigned total, int S, int Hf, int Wf, unsigned cmax,
-                                                                 float feather, Nv12Coef k) {
-  const long SS = (long)S * S;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned rr = i / cmax;
-    const long n = rr / cmax;
-    const int* const w4 = win + 4 * n;
-    const int wx0 = w4[0], wy0 = w4[1], s = w4[2];
-    if (!paste_window_ok(wx0, wy0, s, w4[3], S, Hf, Wf)) continue;
-    const int cx = (wx0 >> 1) + (int)(i % cmax), cy = (wy0 >> 1) + (int)(rr % cmax);
-    if (2 * cx >= wx0 + s || 2 * cy >= wy0 + s) continue;
-    const float scale = (float)S / (float)s, inv_scale = __fdiv_rn(1.0f, scale), fs = feather * (float)s;
-    const float* const im = img + n * 3 * SS;
-    const float* const mt = matte ? matte + n * SS : nullptr;
-    uint8_t* const fy = yp + n * fstride;
-    uint8_t* const puv = uvp + n * fstride + (long)cy * pitch + 2 * cx;
-    float a4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cb4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cr4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy) {
-      const int y = 2 * cy + dy - wy0;
-      if (y < 0 || y >= s) continue;
-      AaTaps ty = {0, 0, 0.0f, 0.0f};
-      if (s < S) ty = aa_taps(y, scale, inv_scale, S);
-#pragma unroll
-      for (int dx = 0; dx < 2; ++dx) {
-        const int x = 2 * cx + dx - wx0;
-        if (x < 0 || x >= s) continue;
-        float r[3], yc, cbc, crc;
-        paste_render01(im, S, s, scale, inv_scale, ty, y, x, r);
-        const float a = paste_alpha(mt, S, s, scale, feather, fs, y, x);
-        nv12_encode(k, r, yc, cbc, crc);
-        uint8_t* const py = fy + (long)(wy0 + y) * pitch + wx0 + x;
-        *py = (uint8_t)nv12_byte(((1.0f - a) * (float)*py + a * yc) + 0.5f);
-        a4[2 * dy + dx] = a;
-        cb4[2 * dy + dx] = a * cbc;
-        cr4[2 * dy + dx] = a * crc;
-      }
-    }
-    const float na = 1.0f - (((a4[0] + a4[1]) + a4[2]) + a4[3]) * 0.25f;
-    const float u = (float)puv[0], v = (float)puv[1];
-    puv[0] = (uint8_t)nv12_byte((na * u + (((cb4[0] + cb4[1]) + cb4[2]) + cb4[3]) * 0.25f) + 0.5f);
-    puv[1] = (uint8_t)nv12_byte((na * v + (((cr4[0] + cr4[1]) + cr4[2]) + cr4[3]) * 0.25f) + 0.5f);
   }
 }
 
@@ -846,52 +675,7 @@ extern "C" int emo_resize2d_f32(const float* x, int64_t plane_stride, int64_t ro
   return emo_launch_status();
 }
 
-extern "C" int emo_resize2d_windows_f32(const float* x, int64_t plane_stride, int64_t row_stride, const int* windows, float* out,
-                                        int N, int C, int Ho, int Wo, int bicubic, int clamp01, void* stream) {
-  if (!x || !out || !windows || N <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || row_stride <= 0 || plane_stride < 0) return EMO_ERR_BAD_ARG;
-  hipLaunchKernelGGL(resize2d_windows_kernel, dim3(grid_for((long)N * C * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, x,
-                     (long)plane_stride, (long)row_stride, windows, out, (long)N, C, Ho, Wo, bicubic, clamp01);
-  return emo_launch_status();
-}
-
-extern "C" int emo_paste_windows_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
-                                      uint8_t* frames, int N, int S, int Hf, int Wf, float feather, void* stream) {
-  if (!img || !windows || !frames || N <= 0 || S <= 0 || Hf <= 0 || Wf <= 0) return EMO_ERR_BAD_ARG;
-  if (!(feather >= 0.0f && feather <= 0.5f)) return EMO_ERR_BAD_ARG;
-  int smax = Hf < Wf ? Hf : Wf;                    // windows that only the device knows: any valid side
-  if (windows_host) {
-    smax = 0;
-    for (int n = 0; n < N; ++n) {
-      const int32_t* w = windows_host + 4 * n;
-      if (w[2] <= 0 || w[3] <= 0 || w[0] < 0 || w[1] < 0 || w[0] > Wf - w[2] || w[1] > Hf - w[3]) return EMO_ERR_BAD_ARG;
-      if (!paste_window_ok(w[0], w[1], w[2], w[3], S, Hf, Wf)) return EMO_ERR_UNSUPPORTED;   // not square, or 4 s < S
-      smax = w[2] > smax ? w[2] : smax;
-    }
-  }
-  const long total = (long)N * smax * ((smax + 3) / 4 + 1);
-  if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(paste_windows_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frames,
-                     (unsigned)total, S, Hf, Wf, (unsigned)smax, feather);
-  return emo_launch_status();
-}
-
-// ---- ABI 17: NV12 frames in and out (definitions: include/emo_hip.h)
-extern "C" int emo_nv12_windows_f32(const uint8_t* y, const uint8_t* uv, int64_t pitch, int64_t frame_stride, int Hf, int Wf,
-                                    const int32_t* windows, const int32_t* windows_host, float* out, int N, int Ho, int Wo,
-                                    int matrix, int full_range, void* stream) {
-  Nv12Coef k;
-  if (!nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || !out || N <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
-  if (!nv12_coef(matrix, full_range, k) || (windows_host && !windows)) return EMO_ERR_BAD_ARG;
-  if (windows_host)
-    for (int n = 0; n < N; ++n) {
-      const int32_t* w = windows_host + 4 * n;
-      if (!nv12_window_ok(w[0], w[1], w[2], w[3], Hf, Wf)) return EMO_ERR_BAD_ARG;
-    }
-  hipLaunchKernelGGL(nv12_windows_kernel, dim3(grid_for((long)N * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, y, uv, (long)pitch,
-                     (long)frame_stride, Hf, Wf, windows, out, (long)N, Ho, Wo, k);
-  return emo_launch_status();
-}
-
+// ---- ABI 17: NV12 frames out (definitions: include/emo_hip.h; the crop and the paste: below)
 extern "C" int emo_pack_nv12(const float* img, uint8_t* y, uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int H, int W,
                              int matrix, int full_range, void* stream) {
   Nv12Coef k;
@@ -902,45 +686,31 @@ extern "C" int emo_pack_nv12(const float* img, uint8_t* y, uint8_t* uv, int64_t 
   return emo_launch_status();
 }
 
-extern "C" int emo_paste_windows_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
-                                      uint8_t* y, uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int S, int Hf, int Wf,
-                                      float feather, int matrix, int full_range, void* stream) {
-  Nv12Coef k;
-  if (!img || !windows || !nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || N <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
-  if (!(feather >= 0.0f && feather <= 0.5f) || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
-  int smax = Hf < Wf ? Hf : Wf;                    // windows that only the device knows: any valid side
-  if (windows_host) {
-    smax = 0;
-    for (int n = 0; n < N; ++n) {
-      const int32_t* w = windows_host + 4 * n;
-      if (!nv12_window_ok(w[0], w[1], w[2], w[3], Hf, Wf)) return EMO_ERR_BAD_ARG;
-      if (!paste_window_ok(w[0], w[1], w[2], w[3], S, Hf, Wf)) return EMO_ERR_UNSUPPORTED;   // not square, or 4 s < S
-      smax = w[2] > smax ? w[2] : smax;
-    }
-  }
-  const long cmax = smax / 2 + 1;                  // chroma samples under s luma pixels: at most s / 2 + 1 (an odd origin)
-  const long total = (long)N * cmax * cmax;
-  if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(paste_windows_nv12_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, y, uv,
-                     (long)pitch, (long)frame_stride, (unsigned)total, S, Hf, Wf, (unsigned)cmax, feather, k);
-  return emo_launch_status();
-}
-
-// ---- ABI 18: several faces per frame (definitions: include/emo_hip.h).  M faces in F frames, face m in frame frame_of[m];
-// frame_of is sorted, so the faces of a frame are the run of consecutive entries with its value.
+// ---- Frame crops and pastes (ABI 9, 15, 17, 18, 19; definitions: include/emo_hip.h): M rows (faces) cut out of or pasted into F
+// frames.  One kernel per operation; what differs between the entry points is how a launch finds the frame of row m.
 namespace {
 
+enum class Frames {
+  OnePerRow,   // the emo_*_windows_* entry points: row m is frame m and alone in it; frame_of is not read
+  Shared,      // ABI 18: frame frame_of[m] of F frames of one size.  frame_of is sorted, so the faces of a frame are the run of
+               // consecutive entries with its value
+  Table,       // ABI 19: frames of different sizes behind a frame table, one face per blockIdx.y (below)
+};
+
 // [lo, hi): the run of face m, i.e. every face of its frame
+template <Frames FR>
 __device__ __forceinline__ void face_run(const int* __restrict__ frame_of, int M, int m, int& lo, int& hi) {
-  const int f = frame_of[m];
   lo = m;
   hi = m + 1;
-  while (lo > 0 && frame_of[lo - 1] == f) --lo;
-  while (hi < M && frame_of[hi] == f) ++hi;
+  if constexpr (FR != Frames::OnePerRow) {
+    const int f = frame_of[m];
+    while (lo > 0 && frame_of[lo - 1] == f) --lo;
+    while (hi < M && frame_of[hi] == f) ++hi;
+  }
 }
 
 // ABI 19: frames of different sizes.  A row of the frame table is (byte address of the frame's first row, row pitch in bytes,
-// H, W); a RAGGED launch has one face per blockIdx.y, so the face's frame and its table row are uniform across the block and
+// H, W); a Table launch has one face per blockIdx.y, so the face's frame and its table row are uniform across the block and
 // are loaded once, in front of the item loop.  A frame_of outside [0, F) gives an empty frame (H = W = 0): no window fits it.
 struct FrameRow { uint8_t* base; long pitch; int H, W; };
 __device__ __forceinline__ FrameRow frame_row(const long long* __restrict__ ftab, const int* __restrict__ frame_of, int F) {
@@ -956,7 +726,11 @@ __device__ __forceinline__ FrameRow frame_row(const long long* __restrict__ ftab
   return r;
 }
 
-// resize2d_windows_kernel with sample m's planes those of frame frame_of[m]
+// resize2d_kernel with one crop window PER ROW (ABI 9; animate_frames' `windows`: the reference crops every frame around its own
+// face box, notebooks/infer.py:301-352): win[m] = (x0, y0, w, h) of row m inside the planes of its frame, read from device
+// memory, so that a batch is ONE launch instead of one per frame (round 5: a Python loop of single-frame launches).  Per element
+// the arithmetic is resize2d_kernel's on the window's first pixel: the two are bit-identical.
+template <Frames FR>
 __global__ __launch_bounds__(256) void resize2d_faces_kernel(const float* __restrict__ x, long plane_stride, long row_stride,
                                                              const int* __restrict__ win, const int* __restrict__ frame_of,
                                                              float* __restrict__ out, long M, int F, int C, int Ho, int Wo,
@@ -967,24 +741,31 @@ __global__ __launch_bounds__(256) void resize2d_faces_kernel(const float* __rest
     const long r = i / Wo;
     const int yo = (int)(r % Ho);
     const long mc = r / Ho, m = mc / C;
-    const int f = frame_of[m];
-    if ((unsigned)f >= (unsigned)F) { out[i] = 0.0f; continue; }
+    const int f = FR == Frames::OnePerRow ? (int)m : frame_of[m];
+    if (FR != Frames::OnePerRow && (unsigned)f >= (unsigned)F) { out[i] = 0.0f; continue; }
     const int* const w4 = win + 4 * m;
     const int wx0 = w4[0], wy0 = w4[1], ww = w4[2], wh = w4[3];
     const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
-    out[i] = resize2d_at(x + ((long)f * C + mc % C) * plane_stride + (long)wy0 * row_stride + wx0, row_stride, wh, ww, sh, sw, yo,
-                         xo, bicubic, clamp01);
+    const long plane = FR == Frames::OnePerRow ? mc : (long)f * C + mc % C;
+    out[i] = resize2d_at(x + plane * plane_stride + (long)wy0 * row_stride + wx0, row_stride, wh, ww, sh, sw, yo, xo, bicubic, clamp01);
   }
 }
 
-// nv12_windows_kernel with face m's planes those of frame frame_of[m]: the same arithmetic per output
-// RAGGED (emo_nv12_faces_ragged_f32): grid (x, M), the items of a block are the outputs of face blockIdx.y, and the planes,
-// the pitch and the size are those of the face's row of the frame table (frame stride 0: yp IS the frame)
-template <bool RAGGED>
+// The NV12 crop (C of include/emo_hip.h): one thread per output pixel, all three channels.  The arithmetic per channel is
+// resize2d_at's bicubic on the window (bicubic_window, clamp01) with every tap decoded from its bytes where it is used: the 16
+// taps of neighbouring outputs overlap and the bytes under them (1.5 per pixel) stay in L1 / L2, so nothing is staged in LDS --
+// the footprint of a block grows with the window's scale (up to 8.4 source pixels per output at 1080 -> 128) and has no bound a
+// static tile could be sized for.  A window as large as the output is scale 1, where the bicubic weights are exactly (0, 1, 0,
+// 0): the pixel's own conversion, taken directly.  A window outside its frame, or a frame_of outside [0, F), writes zeros.
+// OnePerRow: win == nullptr is the whole frame.  Table (emo_nv12_faces_ragged_f32): grid (x, M), the items of a block are the
+// outputs of face blockIdx.y, and the planes, the pitch and the size are those of the face's row of the frame table (frame
+// stride 0: yp IS the frame).
+template <Frames FR>
 __global__ __launch_bounds__(256) void nv12_faces_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, long pitch,
                                                          long fstride, int Hf, int Wf, const int* __restrict__ win,
                                                          const int* __restrict__ frame_of, float* __restrict__ out, long M, int F,
                                                          int Ho, int Wo, Nv12Coef k, const long long* __restrict__ ftab) {
+  constexpr bool RAGGED = FR == Frames::Table;
   const long HWo = (long)Ho * Wo, total = (RAGGED ? 1 : M) * HWo;
   if constexpr (RAGGED) {
     const FrameRow fr = frame_row(ftab, frame_of, F);
@@ -995,41 +776,28 @@ __global__ __launch_bounds__(256) void nv12_faces_kernel(const uint8_t* __restri
     const long r = i / Wo;
     const int yo = (int)(r % Ho);
     const long m = RAGGED ? (long)blockIdx.y : r / Ho;
-    const int f = frame_of[m];
-    const int wx0 = win[4 * m], wy0 = win[4 * m + 1], ww = win[4 * m + 2], wh = win[4 * m + 3];
+    const int f = FR == Frames::OnePerRow ? (int)m : frame_of[m];
+    int wx0 = 0, wy0 = 0, ww = Wf, wh = Hf;
+    if (FR != Frames::OnePerRow || win) { wx0 = win[4 * m]; wy0 = win[4 * m + 1]; ww = win[4 * m + 2]; wh = win[4 * m + 3]; }
     float* const o = out + m * 3 * HWo + (long)yo * Wo + xo;
-    if ((unsigned)f >= (unsigned)F || !nv12_window_ok(wx0, wy0, ww, wh, Hf, Wf)) { o[0] = 0.0f; o[HWo] = 0.0f; o[2 * HWo] = 0.0f; continue; }
+    if ((FR != Frames::OnePerRow && (unsigned)f >= (unsigned)F) || !nv12_window_ok(wx0, wy0, ww, wh, Hf, Wf)) {
+      o[0] = 0.0f; o[HWo] = 0.0f; o[2 * HWo] = 0.0f;
+      continue;
+    }
     const uint8_t* const fy = yp + f * fstride;
     const uint8_t* const fuv = uvp + f * fstride;
-    float acc[3] = {0.0f, 0.0f, 0.0f};
+    float acc[3];
     if (ww == Wo && wh == Ho) {
       nv12_decode_at(fy, fuv, pitch, k, wy0 + yo, wx0 + xo, acc);
     } else {
       const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
-      const float sy = sh * ((float)yo + 0.5f) - 0.5f, sx = sw * ((float)xo + 0.5f) - 0.5f;
-      const float fyf = floorf(sy), fxf = floorf(sx);
-      const int iy = (int)fyf, ix = (int)fxf;
-      const float ty = sy - fyf, tx = sx - fxf;
-      const float A = -0.75f;
-      const float wy[4] = {cubic2(ty + 1.0f, A), cubic1(ty, A), cubic1(1.0f - ty, A), cubic2(2.0f - ty, A)};
-      const float wx[4] = {cubic2(tx + 1.0f, A), cubic1(tx, A), cubic1(1.0f - tx, A), cubic2(2.0f - tx, A)};
+      bicubic_window<3>(wh, ww, sh * ((float)yo + 0.5f) - 0.5f, sw * ((float)xo + 0.5f) - 0.5f,
+                        [&](int yy, int xx, float w, float row[3]) {
+                          float rgb[3];
+                          nv12_decode_at(fy, fuv, pitch, k, wy0 + yy, wx0 + xx, rgb);
 #pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        int yy = iy - 1 + a;
-        yy = yy < 0 ? 0 : (yy > wh - 1 ? wh - 1 : yy);
-        float row[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          int xx = ix - 1 + b;
-          xx = xx < 0 ? 0 : (xx > ww - 1 ? ww - 1 : xx);
-          float rgb[3];
-          nv12_decode_at(fy, fuv, pitch, k, wy0 + yy, wx0 + xx, rgb);
-#pragma unroll
-          for (int c = 0; c < 3; ++c) row[c] += rgb[c] * wx[b];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += row[c] * wy[a];
-      }
+                          for (int c = 0; c < 3; ++c) row[c] += rgb[c] * w;
+                        }, acc);
 #pragma unroll
       for (int c = 0; c < 3; ++c) acc[c] = fminf(fmaxf(acc[c], 0.0f), 1.0f);
     }
@@ -1037,10 +805,9 @@ __global__ __launch_bounds__(256) void nv12_faces_kernel(const uint8_t* __restri
   }
 }
 
-// emo_rgb8_faces_ragged_f32: one thread per output pixel of face blockIdx.y, all three channels.  Per channel the arithmetic is
-// resize2d_at's bicubic on the window (taps clamped into the WINDOW, rows first, clamp01) with every tap unpack_rgb8_kernel's
-// byte / 255, converted where it is read: bit for bit emo_unpack_rgb8 + emo_resize2d_faces_f32 without the fp32 frame.  The 16
-// taps of neighbouring outputs overlap and the bytes under them stay in L1 / L2 (nv12_windows_kernel's reasoning).
+// emo_rgb8_faces_ragged_f32: the NV12 crop's shape (and its reasoning about L1 / L2) on packed bytes -- one thread per output
+// pixel of face blockIdx.y, all three channels, every tap unpack_rgb8_kernel's byte / 255, converted where it is read: bit for
+// bit emo_unpack_rgb8 + emo_resize2d_faces_f32(bicubic, clamp01) without the fp32 frame.
 __global__ __launch_bounds__(256) void rgb8_faces_ragged_kernel(const long long* __restrict__ ftab, const int* __restrict__ win,
                                                                 const int* __restrict__ frame_of, float* __restrict__ out, int F,
                                                                 int Ho, int Wo) {
@@ -1055,49 +822,37 @@ __global__ __launch_bounds__(256) void rgb8_faces_ragged_kernel(const long long*
     const int xo = (int)(i % Wo), yo = (int)(i / Wo);
     float* const o = out + m * 3 * HWo + i;
     if (!ok) { o[0] = 0.0f; o[HWo] = 0.0f; o[2 * HWo] = 0.0f; continue; }
-    const float sy = sh * ((float)yo + 0.5f) - 0.5f, sx = sw * ((float)xo + 0.5f) - 0.5f;
-    const float fyf = floorf(sy), fxf = floorf(sx);
-    const int iy = (int)fyf, ix = (int)fxf;
-    const float ty = sy - fyf, tx = sx - fxf;
-    const float A = -0.75f;
-    const float wy[4] = {cubic2(ty + 1.0f, A), cubic1(ty, A), cubic1(1.0f - ty, A), cubic2(2.0f - ty, A)};
-    const float wx[4] = {cubic2(tx + 1.0f, A), cubic1(tx, A), cubic1(1.0f - tx, A), cubic2(2.0f - tx, A)};
-    float acc[3] = {0.0f, 0.0f, 0.0f};
+    float acc[3];
+    bicubic_window<3>(wh, ww, sh * ((float)yo + 0.5f) - 0.5f, sw * ((float)xo + 0.5f) - 0.5f, [&](int yy, int xx, float w, float row[3]) {
+      const uint8_t* const px = p + (long)yy * fr.pitch + 3 * xx;
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      int yy = iy - 1 + a;
-      yy = yy < 0 ? 0 : (yy > wh - 1 ? wh - 1 : yy);
-      const uint8_t* const prow = p + (long)yy * fr.pitch;
-      float row[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        int xx = ix - 1 + b;
-        xx = xx < 0 ? 0 : (xx > ww - 1 ? ww - 1 : xx);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) row[c] += __fdiv_rn((float)prow[3 * xx + c], 255.0f) * wx[b];
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] += row[c] * wy[a];
-    }
+      for (int c = 0; c < 3; ++c) row[c] += __fdiv_rn((float)px[c], 255.0f) * w;
+    }, acc);
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c * HWo] = fminf(fmaxf(acc[c], 0.0f), 1.0f);
   }
 }
 
-// emo_paste_faces_rgb8.  Work items as in paste_windows_kernel: (face, window row, run of 4 pixels from the row's first dword
-// boundary).  A pixel belongs to the LAST valid face of its frame that covers it: the item of face m drops the pixels a later
-// face of the run covers, starts from the frame's bytes at the others and applies every covering face lo .. m in list order,
-// the value rounded to a byte after each -- the bytes of pasting the faces one after another.  A run of 4 pixels that is wholly
-// the item's own keeps the three aligned dwords; a mixed run, the head and the tail go byte by byte.  Every byte has one writer
-// and is read by that writer only; `win`, `frame_of` and `img` are read by the items of every face of the frame.
-// RAGGED (emo_paste_faces_ragged_rgb8): grid (x, M), `total` the items of ONE face, the face blockIdx.y; `frames`, the row pitch
+// The rgb8 paste.  Work items: (face, window row, run of 4 pixels), grid-stride over M * smax rows * Q runs with smax a
+// host-known bound of the window sides -- the windows themselves are only read on the device.  A pixel is 3 bytes and a window's
+// x0 is arbitrary, so the runs of a row start at its first pixel whose byte address is a multiple of 4 (`head` = address & 3
+// pixels in: 3 * head = -head mod 4): a run inside the row is 12 bytes = three aligned dwords, read and written as such; run 0
+// is the head in front of that pixel and the last run the tail, byte by byte.  No byte outside a window is read or written.
+// A pixel belongs to the LAST valid face of its frame that covers it: the item of face m drops the pixels a later face of the
+// run covers, starts from the frame's bytes at the others and applies every covering face lo .. m in list order, the value
+// rounded to a byte after each -- the bytes of pasting the faces one after another (OnePerRow: the run is the face itself).  A
+// run of 4 pixels that is wholly the item's own keeps the three aligned dwords; a mixed run, the head and the tail go byte by
+// byte.  Every byte has one writer and is read by that writer only; `win`, `frame_of` and `img` are read by the items of every
+// face of the frame.  A window that fails paste_window_ok, or a frame_of outside [0, F), is absent.
+// Table (emo_paste_faces_ragged_rgb8): grid (x, M), `total` the items of ONE face, the face blockIdx.y; `frames`, the row pitch
 // and the size are those of the face's row of the frame table.  The head of a row is taken from its address, whatever the
 // frame's address and pitch are.
-template <bool RAGGED>
+template <Frames FR>
 __global__ __launch_bounds__(256) void paste_faces_kernel(const float* __restrict__ img, const float* __restrict__ matte,
                                                           const int* __restrict__ win, const int* __restrict__ frame_of,
                                                           uint8_t* __restrict__ frames, unsigned total, int M, int F, int S, int Hf,
                                                           int Wf, unsigned smax, float feather, const long long* __restrict__ ftab) {
+  constexpr bool RAGGED = FR == Frames::Table;
   const unsigned Q = (smax + 3u) / 4u + 1u;
   const long SS = (long)S * S;
   long pitch = 0;
@@ -1110,15 +865,15 @@ __global__ __launch_bounds__(256) void paste_faces_kernel(const float* __restric
     const int y = (int)(rr % smax);
     const int m = RAGGED ? (int)blockIdx.y : (int)(rr / smax);
     const int wx0 = win[4 * m], wy0 = win[4 * m + 1], s = win[4 * m + 2];
-    const int f = frame_of[m];
-    if ((unsigned)f >= (unsigned)F || !paste_window_ok(wx0, wy0, s, win[4 * m + 3], S, Hf, Wf) || y >= s) continue;
+    const int f = FR == Frames::OnePerRow ? m : frame_of[m];
+    if ((FR != Frames::OnePerRow && (unsigned)f >= (unsigned)F) || !paste_window_ok(wx0, wy0, s, win[4 * m + 3], S, Hf, Wf) || y >= s) continue;
     const int py = wy0 + y;
     uint8_t* const row = RAGGED ? frames + (long)py * pitch + 3l * wx0 : frames + (((long)f * Hf + py) * Wf + wx0) * 3;
     const int head = (int)(reinterpret_cast<uintptr_t>(row) & 3);
     const int xa = head + 4 * ((int)q - 1);
     if (xa >= s) continue;
     int lo, hi;
-    face_run(frame_of, M, m, lo, hi);
+    face_run<FR>(frame_of, M, m, lo, hi);
     // bit p: pixel xa + p is inside the window and no later face of the frame covers it
     unsigned own = 0u;
 #pragma unroll
@@ -1182,18 +937,22 @@ __device__ __forceinline__ bool chroma_touched(int x0, int y0, int s, int cy, in
   return cx >= (x0 >> 1) && 2 * cx < x0 + s && cy >= (y0 >> 1) && 2 * cy < y0 + s;
 }
 
-// emo_paste_faces_nv12.  Work items as in paste_windows_nv12_kernel: (face, chroma sample of its covering chroma rectangle, with
-// the sample's four luma pixels).  A sample belongs to the LAST valid face of its frame that touches it; its item starts from
-// the frame's bytes and applies every touching face lo .. m in list order with paste_windows_nv12_kernel's arithmetic, every
-// value rounded to a byte after each face.  A luma byte no window holds is neither read nor written.
-// RAGGED (emo_paste_faces_ragged_nv12): as in paste_faces_kernel -- one face per blockIdx.y, its frame from the frame table
-template <bool RAGGED>
+// The NV12 paste (P of include/emo_hip.h).  Work items: (face, chroma sample of the window's covering chroma rectangle, with
+// those of the sample's four luma pixels that lie inside a window; the image and the blend weight of each from the rgb8
+// paste's paste_render01 / paste_alpha), grid-stride over M * cmax * cmax with cmax a host-known bound of the samples along a
+// window side.  A sample belongs to the LAST valid face of its frame that touches it; its item starts from the frame's bytes
+// and applies every touching face lo .. m in list order, every value rounded to a byte after each face (OnePerRow: the run is
+// the face itself).  A luma byte no window holds is neither read nor written; a chroma pair is touched only if one of its luma
+// pixels is inside a window.
+// Table (emo_paste_faces_ragged_nv12): as in paste_faces_kernel -- one face per blockIdx.y, its frame from the frame table
+template <Frames FR>
 __global__ __launch_bounds__(256) void paste_faces_nv12_kernel(const float* __restrict__ img, const float* __restrict__ matte,
                                                                const int* __restrict__ win, const int* __restrict__ frame_of,
                                                                uint8_t* __restrict__ yp, uint8_t* __restrict__ uvp, long pitch,
                                                                long fstride, unsigned total, int M, int F, int S, int Hf, int Wf,
                                                                unsigned cmax, float feather, Nv12Coef k,
                                                                const long long* __restrict__ ftab) {
+  constexpr bool RAGGED = FR == Frames::Table;
   const long SS = (long)S * S;
   if constexpr (RAGGED) {
     const FrameRow fr = frame_row(ftab, frame_of, F);
@@ -1203,12 +962,12 @@ __global__ __launch_bounds__(256) void paste_faces_nv12_kernel(const float* __re
     const unsigned rr = i / cmax;
     const int m = RAGGED ? (int)blockIdx.y : (int)(rr / cmax);
     const int wx0 = win[4 * m], wy0 = win[4 * m + 1], s = win[4 * m + 2];
-    const int f = frame_of[m];
-    if ((unsigned)f >= (unsigned)F || !paste_window_ok(wx0, wy0, s, win[4 * m + 3], S, Hf, Wf)) continue;
+    const int f = FR == Frames::OnePerRow ? m : frame_of[m];
+    if ((FR != Frames::OnePerRow && (unsigned)f >= (unsigned)F) || !paste_window_ok(wx0, wy0, s, win[4 * m + 3], S, Hf, Wf)) continue;
     const int cx = (wx0 >> 1) + (int)(i % cmax), cy = (wy0 >> 1) + (int)(rr % cmax);
     if (2 * cx >= wx0 + s || 2 * cy >= wy0 + s) continue;
     int lo, hi;
-    face_run(frame_of, M, m, lo, hi);
+    face_run<FR>(frame_of, M, m, lo, hi);
     bool owned = true;
     for (int j = m + 1; j < hi; ++j) {
       const int jx = win[4 * j], jy = win[4 * j + 1], js = win[4 * j + 2];
@@ -1271,6 +1030,8 @@ __global__ __launch_bounds__(256) void paste_faces_nv12_kernel(const float* __re
   }
 }
 
+// ---- the host side of the twelve entry points: what they check before a launch, and the launches
+
 // frame_of_host: non-decreasing, every entry in [0, F)
 inline bool frame_of_ok(const int32_t* frame_of_host, int M, int F) {
   for (int m = 0; m < M; ++m)
@@ -1278,23 +1039,27 @@ inline bool frame_of_ok(const int32_t* frame_of_host, int M, int F) {
   return true;
 }
 
-// the checks the two paste entry points share on a host-side window list -> EMO_OK and the largest side, or the refusal
-inline int paste_faces_windows(const int32_t* windows_host, int M, int S, int Hf, int Wf, int& smax) {
-  smax = Hf < Wf ? Hf : Wf;                        // windows that only the device knows: any valid side
+// A host-side window list: every window inside its frame -- Hf x Wf, or with table_host the frame of ITS OWN face -- or
+// EMO_ERR_BAD_ARG; for a paste also a square with 4 s >= S, or EMO_ERR_UNSUPPORTED.  -> EMO_OK and in smax the largest side;
+// windows that only the device knows: any valid side (with a table the caller's bound stays).
+inline int host_windows(const int32_t* windows_host, int M, int S, bool paste, int Hf, int Wf, const int64_t* table_host,
+                        const int32_t* frame_of_host, int& smax) {
+  if (!table_host) smax = Hf < Wf ? Hf : Wf;
   if (!windows_host) return EMO_OK;
   smax = 0;
   for (int m = 0; m < M; ++m) {
     const int32_t* w = windows_host + 4 * m;
+    if (table_host) { Hf = (int)table_host[4l * frame_of_host[m] + 2]; Wf = (int)table_host[4l * frame_of_host[m] + 3]; }
     if (!nv12_window_ok(w[0], w[1], w[2], w[3], Hf, Wf)) return EMO_ERR_BAD_ARG;
-    if (!paste_window_ok(w[0], w[1], w[2], w[3], S, Hf, Wf)) return EMO_ERR_UNSUPPORTED;   // not square, or 4 s < S
+    if (paste && !paste_window_ok(w[0], w[1], w[2], w[3], S, Hf, Wf)) return EMO_ERR_UNSUPPORTED;   // not square, or 4 s < S
     smax = w[2] > smax ? w[2] : smax;
   }
   return EMO_OK;
 }
 
 // ABI 19.  What the four ragged entry points check on the host copy of the frame table and the lists, before a launch: every
-// row an address, a size that fits an int (NV12: even) and a pitch of at least a row's bytes; frame_of as above; a host-side
-// window inside ITS OWN frame (paste: a square with 4 s >= S).  -> EMO_OK and, for the paste, the largest side to cover.
+// row an address, a size that fits an int (NV12: even) and a pitch of at least a row's bytes; frame_of and the windows as
+// above.  -> EMO_OK and, for the paste, the largest side to cover.
 inline int ragged_args(const int64_t* table_host, int F, int px_bytes, bool nv12, const int32_t* windows_host,
                        const int32_t* frame_of_host, int M, int S, bool paste, int& smax) {
   smax = 0;
@@ -1306,16 +1071,7 @@ inline int ragged_args(const int64_t* table_host, int F, int px_bytes, bool nv12
     smax = side > smax ? side : smax;                // windows that only the device knows: any valid side of any frame
   }
   if (!frame_of_ok(frame_of_host, M, F)) return EMO_ERR_BAD_ARG;
-  if (!windows_host) return EMO_OK;
-  smax = 0;
-  for (int m = 0; m < M; ++m) {
-    const int32_t* w = windows_host + 4 * m;
-    const int64_t* t = table_host + 4l * frame_of_host[m];
-    if (!nv12_window_ok(w[0], w[1], w[2], w[3], (int)t[2], (int)t[3])) return EMO_ERR_BAD_ARG;
-    if (paste && !paste_window_ok(w[0], w[1], w[2], w[3], S, (int)t[2], (int)t[3])) return EMO_ERR_UNSUPPORTED;
-    smax = w[2] > smax ? w[2] : smax;
-  }
-  return EMO_OK;
+  return host_windows(windows_host, M, S, paste, 0, 0, table_host, frame_of_host, smax);
 }
 
 // grid (x, M): one face per blockIdx.y, x covering `per` items of a face, about 8192 blocks in all as grid_for
@@ -1326,15 +1082,107 @@ inline dim3 ragged_grid(long per, int M) {
   return dim3((unsigned)g, (unsigned)M);
 }
 
+// The items of a paste launch over M >= 1 faces from the largest side to cover -> false where they exceed the kernels' 32-bit
+// index.  rgb8: smax rows x ((smax + 3) / 4 + 1) runs per face, bound = smax; NV12: cmax x cmax chroma samples, bound = cmax.
+// `total` is what the kernel strides over: the items of all faces, or with a table those of one (grid (x, M)).
+inline bool paste_items(int smax, bool nv12, bool table, int M, unsigned& bound, unsigned& total, dim3& grid) {
+  const long cmax = smax / 2 + 1;                  // chroma samples under s luma pixels: at most s / 2 + 1 (an odd origin)
+  const long per = nv12 ? cmax * cmax : smax * (((long)smax + 3) / 4 + 1);
+  if (table ? M > 65535 || per > 0x7fffffffl : per > 0x7fffffffl / M) return false;
+  bound = (unsigned)(nv12 ? cmax : smax);
+  total = (unsigned)(table ? per : per * M);
+  grid = table ? ragged_grid(per, M) : dim3(grid_for(per * M));
+  return true;
+}
+
+template <Frames FR>
+int launch_nv12_crop(const uint8_t* y, const uint8_t* uv, int64_t pitch, int64_t frame_stride, int Hf, int Wf, const int32_t* windows,
+                     const int32_t* frame_of, float* out, int M, int F, int Ho, int Wo, const Nv12Coef& k, const int64_t* table,
+                     void* stream) {
+  const dim3 grid = FR == Frames::Table ? ragged_grid((long)Ho * Wo, M) : dim3(grid_for((long)M * Ho * Wo));
+  hipLaunchKernelGGL(nv12_faces_kernel<FR>, grid, dim3(256), 0, (hipStream_t)stream, y, uv, (long)pitch, (long)frame_stride, Hf, Wf,
+                     windows, frame_of, out, (long)M, F, Ho, Wo, k, reinterpret_cast<const long long*>(table));
+  return emo_launch_status();
+}
+
+template <Frames FR>
+int launch_paste_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* frame_of, uint8_t* frames, int M,
+                      int F, int S, int Hf, int Wf, int smax, float feather, const int64_t* table, void* stream) {
+  unsigned bound, total;
+  dim3 grid;
+  if (!paste_items(smax, false, FR == Frames::Table, M, bound, total, grid)) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(paste_faces_kernel<FR>, grid, dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of, frames, total, M, F,
+                     S, Hf, Wf, bound, feather, reinterpret_cast<const long long*>(table));
+  return emo_launch_status();
+}
+
+template <Frames FR>
+int launch_paste_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* frame_of, uint8_t* y, uint8_t* uv,
+                      int64_t pitch, int64_t frame_stride, int M, int F, int S, int Hf, int Wf, int smax, float feather,
+                      const Nv12Coef& k, const int64_t* table, void* stream) {
+  unsigned bound, total;
+  dim3 grid;
+  if (!paste_items(smax, true, FR == Frames::Table, M, bound, total, grid)) return EMO_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(paste_faces_nv12_kernel<FR>, grid, dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of, y, uv,
+                     (long)pitch, (long)frame_stride, total, M, F, S, Hf, Wf, bound, feather, k, reinterpret_cast<const long long*>(table));
+  return emo_launch_status();
+}
+
+inline bool feather_ok(float feather) { return feather >= 0.0f && feather <= 0.5f; }
+
 }  // namespace
 
+// ---- one crop window per frame (ABI 9, 15, 17): the faces kernels with one row per frame
+extern "C" int emo_resize2d_windows_f32(const float* x, int64_t plane_stride, int64_t row_stride, const int* windows, float* out,
+                                        int N, int C, int Ho, int Wo, int bicubic, int clamp01, void* stream) {
+  if (!x || !out || !windows || N <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || row_stride <= 0 || plane_stride < 0) return EMO_ERR_BAD_ARG;
+  hipLaunchKernelGGL(resize2d_faces_kernel<Frames::OnePerRow>, dim3(grid_for((long)N * C * Ho * Wo)), dim3(256), 0, (hipStream_t)stream,
+                     x, (long)plane_stride, (long)row_stride, windows, (const int*)nullptr, out, (long)N, N, C, Ho, Wo, bicubic, clamp01);
+  return emo_launch_status();
+}
+
+extern "C" int emo_nv12_windows_f32(const uint8_t* y, const uint8_t* uv, int64_t pitch, int64_t frame_stride, int Hf, int Wf,
+                                    const int32_t* windows, const int32_t* windows_host, float* out, int N, int Ho, int Wo,
+                                    int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  int smax;
+  if (!nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || !out || N <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
+  if (!nv12_coef(matrix, full_range, k) || (windows_host && !windows)) return EMO_ERR_BAD_ARG;
+  if (host_windows(windows_host, N, 0, false, Hf, Wf, nullptr, nullptr, smax) != EMO_OK) return EMO_ERR_BAD_ARG;
+  return launch_nv12_crop<Frames::OnePerRow>(y, uv, pitch, frame_stride, Hf, Wf, windows, nullptr, out, N, N, Ho, Wo, k, nullptr, stream);
+}
+
+extern "C" int emo_paste_windows_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                                      uint8_t* frames, int N, int S, int Hf, int Wf, float feather, void* stream) {
+  if (!img || !windows || !frames || N <= 0 || S <= 0 || Hf <= 0 || Wf <= 0) return EMO_ERR_BAD_ARG;
+  if (!feather_ok(feather)) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = host_windows(windows_host, N, S, true, Hf, Wf, nullptr, nullptr, smax);
+  if (rc != EMO_OK) return rc;
+  return launch_paste_rgb8<Frames::OnePerRow>(img, matte, windows, nullptr, frames, N, N, S, Hf, Wf, smax, feather, nullptr, stream);
+}
+
+extern "C" int emo_paste_windows_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                                      uint8_t* y, uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int S, int Hf, int Wf,
+                                      float feather, int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  if (!img || !windows || !nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || N <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
+  if (!feather_ok(feather) || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = host_windows(windows_host, N, S, true, Hf, Wf, nullptr, nullptr, smax);
+  if (rc != EMO_OK) return rc;
+  return launch_paste_nv12<Frames::OnePerRow>(img, matte, windows, nullptr, y, uv, pitch, frame_stride, N, N, S, Hf, Wf, smax, feather, k,
+                                              nullptr, stream);
+}
+
+// ---- ABI 18: several faces per frame, face m in frame frame_of[m]
 extern "C" int emo_resize2d_faces_f32(const float* x, int64_t plane_stride, int64_t row_stride, const int32_t* windows,
                                       const int32_t* frame_of, float* out, int M, int F, int C, int Ho, int Wo, int bicubic,
                                       int clamp01, void* stream) {
   if (!x || !out || !windows || !frame_of || M < 0 || F <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || row_stride <= 0 || plane_stride < 0)
     return EMO_ERR_BAD_ARG;
   if (M == 0) return EMO_OK;
-  hipLaunchKernelGGL(resize2d_faces_kernel, dim3(grid_for((long)M * C * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, x,
+  hipLaunchKernelGGL(resize2d_faces_kernel<Frames::Shared>, dim3(grid_for((long)M * C * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, x,
                      (long)plane_stride, (long)row_stride, windows, frame_of, out, (long)M, F, C, Ho, Wo, bicubic, clamp01);
   return emo_launch_status();
 }
@@ -1344,33 +1192,24 @@ extern "C" int emo_nv12_faces_f32(const uint8_t* y, const uint8_t* uv, int64_t p
                                   const int32_t* frame_of_host, float* out, int M, int F, int Ho, int Wo, int matrix, int full_range,
                                   void* stream) {
   Nv12Coef k;
+  int smax;
   if (!nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || !out || !windows || !frame_of || M < 0 || F <= 0 || Ho <= 0 || Wo <= 0)
     return EMO_ERR_BAD_ARG;
   if (!nv12_coef(matrix, full_range, k) || (frame_of_host && !frame_of_ok(frame_of_host, M, F))) return EMO_ERR_BAD_ARG;
-  if (windows_host)
-    for (int m = 0; m < M; ++m) {
-      const int32_t* w = windows_host + 4 * m;
-      if (!nv12_window_ok(w[0], w[1], w[2], w[3], Hf, Wf)) return EMO_ERR_BAD_ARG;
-    }
+  if (host_windows(windows_host, M, 0, false, Hf, Wf, nullptr, nullptr, smax) != EMO_OK) return EMO_ERR_BAD_ARG;
   if (M == 0) return EMO_OK;
-  hipLaunchKernelGGL(nv12_faces_kernel<false>, dim3(grid_for((long)M * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, y, uv, (long)pitch,
-                     (long)frame_stride, Hf, Wf, windows, frame_of, out, (long)M, F, Ho, Wo, k, (const long long*)nullptr);
-  return emo_launch_status();
+  return launch_nv12_crop<Frames::Shared>(y, uv, pitch, frame_stride, Hf, Wf, windows, frame_of, out, M, F, Ho, Wo, k, nullptr, stream);
 }
 
 extern "C" int emo_paste_faces_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
                                     const int32_t* frame_of, const int32_t* frame_of_host, uint8_t* frames, int M, int F, int S,
                                     int Hf, int Wf, float feather, void* stream) {
   if (!img || !windows || !frame_of || !frame_of_host || !frames || M < 0 || F <= 0 || S <= 0 || Hf <= 0 || Wf <= 0) return EMO_ERR_BAD_ARG;
-  if (!(feather >= 0.0f && feather <= 0.5f) || !frame_of_ok(frame_of_host, M, F)) return EMO_ERR_BAD_ARG;
+  if (!feather_ok(feather) || !frame_of_ok(frame_of_host, M, F)) return EMO_ERR_BAD_ARG;
   int smax;
-  const int rc = paste_faces_windows(windows_host, M, S, Hf, Wf, smax);
+  const int rc = host_windows(windows_host, M, S, true, Hf, Wf, nullptr, nullptr, smax);
   if (rc != EMO_OK || M == 0) return rc;
-  const long total = (long)M * smax * ((smax + 3) / 4 + 1);
-  if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(paste_faces_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
-                     frames, (unsigned)total, M, F, S, Hf, Wf, (unsigned)smax, feather, (const long long*)nullptr);
-  return emo_launch_status();
+  return launch_paste_rgb8<Frames::Shared>(img, matte, windows, frame_of, frames, M, F, S, Hf, Wf, smax, feather, nullptr, stream);
 }
 
 extern "C" int emo_paste_faces_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
@@ -1380,20 +1219,15 @@ extern "C" int emo_paste_faces_nv12(const float* img, const float* matte, const 
   Nv12Coef k;
   if (!img || !windows || !frame_of || !frame_of_host || !nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || M < 0 || F <= 0 || S <= 0)
     return EMO_ERR_BAD_ARG;
-  if (!(feather >= 0.0f && feather <= 0.5f) || !nv12_coef(matrix, full_range, k) || !frame_of_ok(frame_of_host, M, F)) return EMO_ERR_BAD_ARG;
+  if (!feather_ok(feather) || !nv12_coef(matrix, full_range, k) || !frame_of_ok(frame_of_host, M, F)) return EMO_ERR_BAD_ARG;
   int smax;
-  const int rc = paste_faces_windows(windows_host, M, S, Hf, Wf, smax);
+  const int rc = host_windows(windows_host, M, S, true, Hf, Wf, nullptr, nullptr, smax);
   if (rc != EMO_OK || M == 0) return rc;
-  const long cmax = smax / 2 + 1;                  // chroma samples under s luma pixels: at most s / 2 + 1 (an odd origin)
-  const long total = (long)M * cmax * cmax;
-  if (total > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(paste_faces_nv12_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
-                     y, uv, (long)pitch, (long)frame_stride, (unsigned)total, M, F, S, Hf, Wf, (unsigned)cmax, feather, k,
-                     (const long long*)nullptr);
-  return emo_launch_status();
+  return launch_paste_nv12<Frames::Shared>(img, matte, windows, frame_of, y, uv, pitch, frame_stride, M, F, S, Hf, Wf, smax, feather, k,
+                                           nullptr, stream);
 }
 
-// ---- ABI 19: the frames of a batch in different sizes, addressed through a frame table (definitions: include/emo_hip.h)
+// ---- ABI 19: the frames of a batch in different sizes, addressed through a frame table
 extern "C" int emo_rgb8_faces_ragged_f32(const int64_t* table, const int64_t* table_host, const int32_t* windows,
                                          const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host,
                                          float* out, int M, int F, int Ho, int Wo, void* stream) {
@@ -1417,25 +1251,18 @@ extern "C" int emo_nv12_faces_ragged_f32(const int64_t* table, const int64_t* ta
   const int rc = ragged_args(table_host, F, 1, true, windows_host, frame_of_host, M, 0, false, smax);
   if (rc != EMO_OK || M == 0) return rc;
   if (M > 65535) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(nv12_faces_kernel<true>, ragged_grid((long)Ho * Wo, M), dim3(256), 0, (hipStream_t)stream,
-                     (const uint8_t*)nullptr, (const uint8_t*)nullptr, 0l, 0l, 0, 0, windows, frame_of, out, (long)M, F, Ho, Wo, k,
-                     reinterpret_cast<const long long*>(table));
-  return emo_launch_status();
+  return launch_nv12_crop<Frames::Table>(nullptr, nullptr, 0, 0, 0, 0, windows, frame_of, out, M, F, Ho, Wo, k, table, stream);
 }
 
 extern "C" int emo_paste_faces_ragged_rgb8(const float* img, const float* matte, const int64_t* table, const int64_t* table_host,
                                            const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
                                            const int32_t* frame_of_host, int M, int F, int S, float feather, void* stream) {
   if (!img || !table || !table_host || !windows || !frame_of || !frame_of_host || M < 0 || F <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
-  if (!(feather >= 0.0f && feather <= 0.5f)) return EMO_ERR_BAD_ARG;
+  if (!feather_ok(feather)) return EMO_ERR_BAD_ARG;
   int smax;
   const int rc = ragged_args(table_host, F, 3, false, windows_host, frame_of_host, M, S, true, smax);
   if (rc != EMO_OK || M == 0) return rc;
-  const long per = (long)smax * ((smax + 3) / 4 + 1);
-  if (M > 65535 || per > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(paste_faces_kernel<true>, ragged_grid(per, M), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
-                     (uint8_t*)nullptr, (unsigned)per, M, F, S, 0, 0, (unsigned)smax, feather, reinterpret_cast<const long long*>(table));
-  return emo_launch_status();
+  return launch_paste_rgb8<Frames::Table>(img, matte, windows, frame_of, nullptr, M, F, S, 0, 0, smax, feather, table, stream);
 }
 
 extern "C" int emo_paste_faces_ragged_nv12(const float* img, const float* matte, const int64_t* table, const int64_t* table_host,
@@ -1444,15 +1271,10 @@ extern "C" int emo_paste_faces_ragged_nv12(const float* img, const float* matte,
                                            int full_range, void* stream) {
   Nv12Coef k;
   if (!img || !table || !table_host || !windows || !frame_of || !frame_of_host || M < 0 || F <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
-  if (!(feather >= 0.0f && feather <= 0.5f) || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
+  if (!feather_ok(feather) || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
   int smax;
   const int rc = ragged_args(table_host, F, 1, true, windows_host, frame_of_host, M, S, true, smax);
   if (rc != EMO_OK || M == 0) return rc;
-  const long cmax = smax / 2 + 1;                  // chroma samples under s luma pixels: at most s / 2 + 1 (an odd origin)
-  const long per = cmax * cmax;
-  if (M > 65535 || per > 0x7fffffffl) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(paste_faces_nv12_kernel<true>, ragged_grid(per, M), dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of,
-                     (uint8_t*)nullptr, (uint8_t*)nullptr, 0l, 0l, (unsigned)per, M, F, S, 0, 0, (unsigned)cmax, feather, k,
-                     reinterpret_cast<const long long*>(table));
-  return emo_launch_status();
+  return launch_paste_nv12<Frames::Table>(img, matte, windows, frame_of, nullptr, nullptr, 0, 0, M, F, S, 0, 0, smax, feather, k, table,
+                                          stream);
 }

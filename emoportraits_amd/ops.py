@@ -771,6 +771,18 @@ def resize2d_windows(x, size, windows, mode="bicubic", clamp01=False, frame_of=N
     return out
 
 
+def _paste_args(img, matte, feather, rows, bad_img):
+    """what the paste ops check on img [rows,3,S,S] (rows None: never right; bad_img: the message), matte and feather -> S"""
+    if rows is None or img.dim() != 4 or img.shape[0] != rows or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
+        raise ValueError(bad_img)
+    S = img.shape[2]
+    if matte is not None and tuple(matte.shape) != (rows, 1, S, S):
+        raise ValueError(f"matte {tuple(matte.shape)}: expected {(rows, 1, S, S)}")
+    if not 0.0 <= float(feather) <= 0.5:
+        raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
+    return S
+
+
 def paste_windows(frames_u8, img, windows, feather=0.0, matte=None, frame_of=None):
     """The inverse of resize2d_windows' crop, in ONE launch and IN PLACE: img [N,3,S,S] fp32 (the renderer's output) goes back
     into frames_u8 [N,Hf,Wf,3] uint8 where each frame's SQUARE window (x0, y0, s, s) was -- bicubic resize to (s, s)
@@ -789,13 +801,8 @@ def paste_windows(frames_u8, img, windows, feather=0.0, matte=None, frame_of=Non
         raise RuntimeError("paste_windows expects a contiguous uint8 tensor [N,H,W,3] on the images' device")
     N, Hf, Wf, C = frames_u8.shape
     F, N = N, (N if frame_of is None else len(frame_of))                     # F frames, N rows of img / matte / windows
-    if C != 3 or img.dim() != 4 or img.shape[0] != N or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
-        raise ValueError(f"frames {tuple(frames_u8.shape)} and images {tuple(img.shape)}: expected [N,Hf,Wf,3] and [N,3,S,S]")
-    S = img.shape[2]
-    if matte is not None and tuple(matte.shape) != (N, 1, S, S):
-        raise ValueError(f"matte {tuple(matte.shape)}: expected {(N, 1, S, S)}")
-    if not 0.0 <= float(feather) <= 0.5:
-        raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
+    S = _paste_args(img, matte, feather, N if C == 3 else None,
+                    f"frames {tuple(frames_u8.shape)} and images {tuple(img.shape)}: expected [N,Hf,Wf,3] and [N,3,S,S]")
     win, host = _windows_arg(windows, N, (Wf, Hf), frames_u8.device, "paste", "frames" if frame_of is None else "faces", S)
     if frame_of is not None:
         fof, fof_host = _frame_of_arg(frame_of, F, frames_u8.device)
@@ -908,13 +915,7 @@ def paste_windows_nv12(nv12, img, windows, feather=0.0, matte=None, colorspace="
     y, uv, pitch, fstride, N, Hf, Wf = _nv12_planes(nv12, "paste_windows_nv12")
     matrix = _nv12_matrix(colorspace)
     F, N = N, (N if frame_of is None else len(frame_of))                     # F frames, N rows of img / matte / windows
-    if img.dim() != 4 or img.shape[0] != N or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
-        raise ValueError(f"frames {tuple(nv12.shape)} and images {tuple(img.shape)}: expected [N,3Hf/2,Wf] and [N,3,S,S]")
-    S = img.shape[2]
-    if matte is not None and tuple(matte.shape) != (N, 1, S, S):
-        raise ValueError(f"matte {tuple(matte.shape)}: expected {(N, 1, S, S)}")
-    if not 0.0 <= float(feather) <= 0.5:
-        raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
+    S = _paste_args(img, matte, feather, N, f"frames {tuple(nv12.shape)} and images {tuple(img.shape)}: expected [N,3Hf/2,Wf] and [N,3,S,S]")
     win, host = _windows_arg(windows, N, (Wf, Hf), img.device, "paste", paste_S=S)
     if frame_of is not None:
         fof, fof_host = _frame_of_arg(frame_of, F, img.device)
@@ -1026,13 +1027,8 @@ def paste_faces_mixed(frames, img, windows, frame_of, feather=0.0, matte=None, f
     device = frames[0].device
     if device != img.device:
         raise RuntimeError("paste_faces_mixed expects the frames on the images' device")
-    if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
-        raise ValueError(f"images {tuple(img.shape)}: expected [M,3,S,S]")
-    M, S, F = img.shape[0], img.shape[2], len(rows)
-    if matte is not None and tuple(matte.shape) != (M, 1, S, S):
-        raise ValueError(f"matte {tuple(matte.shape)}: expected {(M, 1, S, S)}")
-    if not 0.0 <= float(feather) <= 0.5:
-        raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
+    S = _paste_args(img, matte, feather, img.shape[0] if img.dim() else None, f"images {tuple(img.shape)}: expected [M,3,S,S]")
+    M, F = img.shape[0], len(rows)
     table_host = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
     win, host, fof, fof_host = _mixed_windows(windows, frame_of, table_host, device, S, "paste")
     if fof_host.numel() != M:
