@@ -337,122 +337,87 @@ def _shares_storage(a, b):
 def conv_igemm(x, layer, scale=None, shift=None, relu_in=False, ups=False, res=None, res_ups=False, act="none",
                out=None, ksplit=None, want_stats=False):
     """layer: emoportraits_amd.pack.PackedConv.  x [N,Cin,H,W] or [N,Cin,D,H,W].
-    ksplit: K-loop split of the launch (None: pack.plan_launch decides together with the block config).
+    ksplit: K-loop split of the launch (None: the planner decides it together with the block config).
     want_stats: also return the TileStats of the output (None when this launch cannot produce them: K-split launches)
-    -> (out, stats)."""
+    -> (out, stats).  Execution only: checks the shapes, asks layer.launch_plan for the launch (pack.ConvPlan), allocates what the
+    plan names and makes its one or two C calls; the layer keeps the plan as last_launch (last_plan, last_form: parts of it)."""
     lib = hip.load()
     hip.require_cuda_f32(x, scale, shift, res)
     three_d = x.dim() == 5
-    if three_d:
-        N, Cin, D, H, W = x.shape
-    else:
-        N, Cin, H, W = x.shape
-        D = 1
+    N, Cin, D, H, W = x.shape if three_d else (*x.shape[:2], 1, *x.shape[2:])
     if Cin != layer.cin:
         raise ValueError(f"conv expects {layer.cin} input channels, got {Cin}")
     if (layer.kd == 3) != three_d and layer.kd == 3:
         raise ValueError("3x3x3 conv needs a 5-D input")
     Hl, Wl = (2 * H, 2 * W) if ups else (H, W)
     shape = (N, layer.cout, D, Hl, Wl) if three_d else (N, layer.cout, Hl, Wl)
+    new = functools.partial(torch.empty, device=x.device, dtype=torch.float32)
     if out is None:
-        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+        out = new(shape)
     elif tuple(out.shape) != shape:
         raise ValueError("bad out shape")
     elif _shares_storage(out, x):
         raise ValueError("out overlaps x: tiles read their neighbours' input halo while others write")
-    if res is not None:
-        want = (N, layer.cout, D, Hl // 2, Wl // 2) if res_ups else (N, layer.cout, D, Hl, Wl)
-        if res.numel() != want[0] * want[1] * want[2] * want[3] * want[4]:
-            raise ValueError("bad residual shape")
-    positions = N * D * Hl * Wl
-    cfg, ks, prec = layer.plan_for(max(1, -(-positions // 128)), Hl, Wl, ups, affine=scale is not None,
-                                   # (the pointwise split kernel has the straight-line epilogue only: 16-byte aligned out / res)
-                                   aligned16=x.data_ptr() % 16 == 0 and (not getattr(layer, "pointwise_split", False) or (
-                                       (res is None or res.data_ptr() % 16 == 0) and (out is None or out.data_ptr() % 16 == 0))),
-                                   in_elems_per_sample=x.numel() // max(1, N), act=act,
-                                   io_aligned16=(res is None or res.data_ptr() % 16 == 0) and out.data_ptr() % 16 == 0)
-    pointwise_split = prec == "f16x2" and getattr(layer, "pointwise_split", False)
-    if ksplit is not None:
-        ks = int(ksplit)
-    ws = torch.empty((ks, out.numel()), device=x.device, dtype=torch.float32) if ks > 1 else None
-    stats = None
-    # (a pointwise layer on the fp16 split keeps its tile statistics in the 128-position layout of the fp32 MFMA kernel that
-    # recomputes it behind a raised overflow word: csrc/conv_igemm_f16x2_p1.h writes two half entries per 256-position tile)
-    bp = 128 if pointwise_split else pack_mod._BP[cfg]
-    if want_stats and ks == 1 and (D * Hl * Wl) % bp == 0:
-        stats = TileStats(torch.empty((N, D * Hl * Wl // bp, layer.cout, 2), device=x.device, dtype=torch.float32), bp)
-    layer.last_plan = (cfg, ks, prec)        # which kernel ran (bench.py meters the kernels separately)
-    # the fp16 split of an up-convolution as four 2x2 phase convolutions (emo_conv_igemm_f16x2, cfg CFG_F16X2_UP2): same plan
-    up2 = prec == "f16x2" and not pointwise_split and cfg == pack_mod.CFG_D and ks == 1 and not three_d and pack_mod.up2_launch_fits(
-        layer.cout, Cin, layer.kd, layer.kh, layer.kw, N, H, W, ups, affine=scale is not None, res=res is not None, act=act,
-        aligned16=x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0)
-    layer.last_form = "up2" if up2 else None
-    entry = {"f32": lib.emo_conv_igemm_f32, "f16": lib.emo_conv_igemm_f16acc32, "bf16x3": lib.emo_conv_igemm_bf16x3,
-             "f16x2": lib.emo_conv_igemm_f16x2, "f16w8": lib.emo_conv_igemm_f16w8}[prec]
+    if res is not None and res.numel() != N * layer.cout * D * ((Hl // 2) * (Wl // 2) if res_ups else Hl * Wl):
+        raise ValueError("bad residual shape")
+    plan = layer.launch_plan(N, D, H, W, ups, affine=scale is not None, res=res is not None, act=act, x16=x.data_ptr() % 16 == 0,
+                             out16=out.data_ptr() % 16 == 0, res16=res is None or res.data_ptr() % 16 == 0,
+                             in_elems_per_sample=x.numel() // max(1, N), ksplit=ksplit, want_stats=want_stats, guard=F16X2_GUARD)
+    cfg, ks, prec = layer.last_plan = plan[:3]       # which kernel ran (bench.py meters the kernels separately)
+    layer.last_launch, layer.last_form = plan, "up2" if plan.form == "up2" else None
+    ws = new((ks, out.numel())) if ks > 1 else None
+    stats = TileStats(new((N, D * Hl * Wl // plan.stats_bp, layer.cout, 2)), plan.stats_bp) if plan.stats_bp else None
+    caller_out = None
+    if plan.guard and res is not None and _shares_storage(out, res):
+        # the guarded launch re-reads res AFTER the first launch has written out: an output that aliases it (a residual updated in
+        # place) would feed the first launch's result into the recomputation -- conv + clipped conv + res.  Both launches write a
+        # private buffer; the caller's `out` receives the result behind them: `out=` means the same in every mode and guard state
+        caller_out, out = out, new(shape)
+
+    tensors, stream = tuple(map(hip.ptr, (layer.bias, scale, shift, res, out))), hip.current_stream()
+
+    def args(*weights, cfg=cfg, ksplit=ks, workspace=ws, stats=stats):      # what all conv entries share, from x to the stream
+        return (hip.ptr(x), *map(hip.ptr, weights), *tensors, N, Cin, layer.cout, D, H, W, layer.kd, layer.kh, layer.kw, int(ups),
+                int(relu_in), hip.ACT[act], int(res_ups), cfg, ksplit, hip.ptr(workspace),
+                None if stats is None else hip.ptr(stats.stats), stream)
+
     wpk = layer.packed(cfg, prec)
-    common = (hip.ptr(layer.bias), hip.ptr(scale), hip.ptr(shift), hip.ptr(res), hip.ptr(out), N, Cin, layer.cout, D, H, W,
-              layer.kd, layer.kh, layer.kw, int(ups), int(relu_in), hip.ACT[act], int(res_ups), cfg, ks, hip.ptr(ws),
-              hip.ptr(stats.stats) if stats is not None else None, hip.current_stream())
     if prec == "f16x2":
-        # the fp16 split checks its operand range on the device (overflow word of the layer); the guarded bf16x3 launch behind
-        # it recomputes the layer with exact operands when the word is raised -- no host synchronisation, graph-capturable
-        flag = pack_mod.overflow_flag_ptr(x.device, layer.flag_slot) if F16X2_GUARD else None
-        caller_out = None
-        if F16X2_GUARD and res is not None and _shares_storage(out, res):
-            # the guarded launch re-reads res AFTER the first launch has written out: an output that aliases it (a residual
-            # updated in place) would feed the first launch's result into the recomputation -- conv + clipped conv + res.
-            # Both launches write a private buffer; the caller's `out` receives the result behind them, so that `out=` means
-            # the same in every precision mode and guard state
-            caller_out = out
-            out = torch.empty(shape, device=x.device, dtype=torch.float32)
-            common = common[:4] + (hip.ptr(out),) + common[5:]
-        gplan = None
-        if F16X2_GUARD and pointwise_split:
-            # (pointwise layer: the exact recomputation is the fp32 MFMA kernel at its own launch plan -- made BEFORE the fp16-split
-            # launch is enqueued, and without a K split when tile statistics travel with the output: a split launch cannot
-            # produce them, and raising behind the first launch would leave `out` / `stats` un-recomputed with the word raised)
-            gcfg, gks = pack_mod.plan_launch(layer.cout, layer.cin, layer.kd, layer.kh, layer.kw, max(1, -(-positions // 128)),
-                                             layer.allowed, "f32")
-            if stats is not None:
-                gks = 1
-            gplan = (gcfg, gks, layer.packed(gcfg))
-        if up2:
-            ucommon = common[:18] + (pack_mod.CFG_F16X2_UP2,) + common[19:]
-            rc = entry(hip.ptr(x), hip.ptr(layer.packed(cfg, "f16x2_up2")), *ucommon, pack_mod.F16X2_IN_SCALE, layer.w_scale_up2, flag)
-            hip.check(rc, f"emo_conv_igemm_f16x2[{layer.name}, phase form]")
-        else:
-            rc = entry(hip.ptr(x), hip.ptr(wpk), *common, pack_mod.F16X2_IN_SCALE, layer.w_scale, flag)
-            hip.check(rc, f"emo_conv_igemm_f16x2[{layer.name}]")
-        if gplan is not None:
-            gcfg, gks, gw = gplan
-            gws = torch.empty((gks, out.numel()), device=x.device, dtype=torch.float32) if gks > 1 else None
-            gcommon = common[:18] + (gcfg, gks, hip.ptr(gws), None if gks > 1 else common[21], common[22])
-            rc = lib.emo_conv_igemm_f32_guarded(hip.ptr(x), hip.ptr(gw), *gcommon, flag)
-            hip.check(rc, f"emo_conv_igemm_f32_guarded[{layer.name}]")
-        elif F16X2_GUARD:
-            # (the exact recomputation runs the 64-row tile of the bf16 split whatever tile the fp16-split launch used)
-            gcommon = common[:18] + (pack_mod.CFG_D,) + common[19:]
-            rc = lib.emo_conv_igemm_bf16x3(hip.ptr(x), hip.ptr(layer.packed(pack_mod.CFG_D, "bf16x3")), *gcommon, flag)
-            hip.check(rc, f"emo_conv_igemm_bf16x3[{layer.name}, guarded]")
+        # the fp16 split checks its operand range on the device (overflow word of the layer); the guarded launch behind it
+        # recomputes the layer with exact operands when the word is raised -- no host synchronisation, graph-capturable
+        flag = None
+        if plan.guard:      # (its weights are packed BEFORE the fp16-split launch is enqueued)
+            gprec, gcfg, gks = plan.guard
+            gw, flag = layer.packed(gcfg, gprec), pack_mod.overflow_flag_ptr(x.device, layer.flag_slot)
+        up2 = plan.form == "up2"        # (the phase form: the same entry with the phase weights and their layout's cfg word)
+        w1, cfg1 = (layer.packed(cfg, "f16x2_up2"), pack_mod.CFG_F16X2_UP2) if up2 else (wpk, cfg)
+        rc = lib.emo_conv_igemm_f16x2(*args(w1, cfg=cfg1), pack_mod.F16X2_IN_SCALE, layer.w_scale_up2 if up2 else layer.w_scale, flag)
+        hip.check(rc, f"emo_conv_igemm_f16x2[{layer.name}{', phase form' if up2 else ''}]")
+        if plan.guard:
+            # (the bf16 split runs on the first launch's K split and workspace; the fp32 MFMA kernel has a plan of its own)
+            gws = ws if gprec == "bf16x3" else new((gks, out.numel())) if gks > 1 else None
+            gname = "emo_conv_igemm_bf16x3" if gprec == "bf16x3" else "emo_conv_igemm_f32_guarded"
+            hip.check(getattr(lib, gname)(*args(gw, cfg=gcfg, ksplit=gks, workspace=gws, stats=stats if gks == 1 else None), flag),
+                      f"{gname}[{layer.name}, guarded]")
         if caller_out is not None:
-            caller_out.copy_(out)
-            out = caller_out
-    elif prec == "f16w8":
-        # plain fp16 operands on the eight-wave two-tile kernel (opt-in precision 'f16'; csrc/conv_igemm_f16x2_w8.h, NPROD = 1);
-        # the straight-line epilogue reads 16-byte aligned out / res: anything else was planned onto the older fp16 kernel
-        if pack_mod.f16w8_rest_fits(layer.cout, Hl, Wl):
-            # an odd tile count: the pairs on that kernel, the last tile on the older fp16-operand kernel (ABI 10) -- no half-empty pair
-            rc = lib.emo_conv_igemm_f16w8_rest(hip.ptr(x), hip.ptr(wpk), hip.ptr(layer.packed(pack_mod.CFG_D, "f16")), *common,
-                                               layer.w_scale16)
-            hip.check(rc, f"emo_conv_igemm_f16w8_rest[{layer.name}]")
-        else:
-            rc = entry(hip.ptr(x), hip.ptr(wpk), *common, layer.w_scale16)
-            hip.check(rc, f"emo_conv_igemm_f16w8[{layer.name}]")
+            out = caller_out.copy_(out)
+    elif plan.form == "f16w8_rest":
+        # the channel-tile pairs on the eight-wave two-tile kernel, the odd last tile on the older fp16-operand kernel (ABI 10)
+        rc = lib.emo_conv_igemm_f16w8_rest(*args(wpk, layer.packed(pack_mod.CFG_D, "f16")), layer.w_scale16)
+        hip.check(rc, f"emo_conv_igemm_f16w8_rest[{layer.name}]")
     else:
-        extra = (None,) if prec == "bf16x3" else ()
-        rc = entry(hip.ptr(x), hip.ptr(wpk), *common, *extra)
-        hip.check(rc, f"emo_conv_igemm_{prec}[{layer.name}]")
+        # (f16w8: plain fp16 operands on the eight-wave two-tile kernel, csrc/conv_igemm_f16x2_w8.h NPROD = 1; bf16x3: no flag)
+        entry = getattr(lib, "emo_conv_igemm_f16acc32" if prec == "f16" else "emo_conv_igemm_" + prec)
+        extra = (layer.w_scale16,) if prec == "f16w8" else (None,) if prec == "bf16x3" else ()
+        hip.check(entry(*args(wpk), *extra), f"emo_conv_igemm_{prec}[{layer.name}]")
     return (out, stats) if want_stats else out
+
+
+def _stream_head_takes(layer, N, S, *views):
+    """the stream kernel (csrc/conv_head.hip) takes this launch: a 1x1(x1) layer with at most 4 output channels, S positions per
+    channel a multiple of 4, contiguous 16-byte aligned views, EMO_CONV_HEAD not 0"""
+    return (CONV_HEAD_STREAM and (layer.kd, layer.kh, layer.kw) == (1, 1, 1) and layer.cout <= 4 and S % 4 == 0 and N <= 65535
+            and all(t.data_ptr() % 16 == 0 and t.is_contiguous() for t in views))
 
 
 def conv_head(x, layer, scale=None, shift=None, relu_in=False, act="none"):
@@ -463,13 +428,12 @@ def conv_head(x, layer, scale=None, shift=None, relu_in=False, act="none"):
     hip.require_cuda_f32(x, scale, shift)
     N, Cin = x.shape[0], x.shape[1]
     S = x.numel() // max(1, N * Cin)
-    if (not CONV_HEAD_STREAM or (layer.kd, layer.kh, layer.kw) != (1, 1, 1) or layer.cout > 4 or S % 4 or N > 65535
-            or x.data_ptr() % 16 or not x.is_contiguous()):
+    if not _stream_head_takes(layer, N, S, x):
         return conv_igemm(x, layer, scale, shift, relu_in=relu_in, act=act)
     if Cin != layer.cin:
         raise ValueError(f"conv expects {layer.cin} input channels, got {Cin}")
     out = torch.empty((N, layer.cout) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
-    layer.last_plan = ("head", 1, "stream")
+    layer.last_launch, layer.last_plan = pack_mod.STREAM_PLAN, ("head", 1, "stream")
     hip.check(lib.emo_conv_head_f32(hip.ptr(x), hip.ptr(layer.plain_weight()), hip.ptr(layer.bias), hip.ptr(scale), hip.ptr(shift),
                                     hip.ptr(out), N, Cin, layer.cout, S, int(relu_in), hip.ACT[act], hip.current_stream()),
               f"emo_conv_head_f32[{layer.name}]")
@@ -670,14 +634,13 @@ def stage2_head(x, layer, scale, shift, img, mask, face_mask=None, out="u8", rel
         raise ValueError("stage-2 tail: the head is a 1x1 convolution to 3 channels")
     if Cin != layer.cin:
         raise ValueError(f"conv expects {layer.cin} input channels, got {Cin}")
-    views = (x, img, mask) + (() if face_mask is None else (face_mask,))
-    if not CONV_HEAD_STREAM or S % 4 or N > 65535 or any(t.data_ptr() % 16 for t in views):
+    if not _stream_head_takes(layer, N, S, x, img, mask, *(() if face_mask is None else (face_mask,))):
         add = conv_igemm(x, layer, scale, shift, relu_in=relu_in, act="tanh")
         f32 = stage2_compose(img, add, mask, torch.ones_like(mask) if face_mask is None else face_mask)
         return f32 if out == "f32" else pack_rgb8(f32) if out == "u8" else (f32, pack_rgb8(f32))
     f32 = torch.empty_like(img) if out != "u8" else None
     u8 = torch.empty((N, H, W, 3), device=img.device, dtype=torch.uint8) if out != "f32" else None
-    layer.last_plan = ("head", 1, "stream")
+    layer.last_launch, layer.last_plan = pack_mod.STREAM_PLAN, ("head", 1, "stream")
     hip.check(lib.emo_stage2_head_f32(hip.ptr(x), hip.ptr(layer.plain_weight()), hip.ptr(layer.bias), hip.ptr(scale), hip.ptr(shift),
                                       hip.ptr(img), hip.ptr(mask), hip.ptr(face_mask), hip.ptr(f32), hip.ptr(u8), N, Cin, S,
                                       int(relu_in), hip.current_stream()), f"emo_stage2_head_f32[{layer.name}]")

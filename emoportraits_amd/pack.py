@@ -10,6 +10,7 @@ import contextlib
 import ctypes
 import functools
 import math
+from collections import namedtuple
 
 import torch
 
@@ -148,13 +149,12 @@ _flag_pools = {}     # device -> [int32 tensor, next free slot, {slot: layer nam
 
 
 def _flag_pool(device):
-    import torch as _t
-    dev = _t.device(device)
+    dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:      # 'cuda' and 'cuda:<current>' are one pool (tensors report the indexed form)
-        dev = _t.device("cuda", _t.cuda.current_device())
+        dev = torch.device("cuda", torch.cuda.current_device())
     key = str(dev)
     if key not in _flag_pools:
-        _flag_pools[key] = [_t.zeros(_FLAG_POOL_WORDS, dtype=_t.int32, device=device), 0, {}]
+        _flag_pools[key] = [torch.zeros(_FLAG_POOL_WORDS, dtype=torch.int32, device=device), 0, {}]
     return _flag_pools[key]
 
 
@@ -571,6 +571,15 @@ def f16_launch_fits(Hl, Wl):
     return (Wl % 128 == 0 and Hl % 2 == 0) or (Wl == 64 and Hl % 4 == 0) or (Wl == 32 and Hl % 8 == 0)
 
 
+ConvPlan = namedtuple("ConvPlan", "cfg ksplit prec form stats_bp guard")
+ConvPlan.__doc__ = """Everything ops.conv_igemm needs to know about a launch besides its tensors (PackedConv.launch_plan makes it, the
+    layer keeps the last one as last_launch).  cfg, ksplit, prec: block config, K split and kernel, what last_plan holds; form:
+    'direct' | 'up2' | 'pointwise' | 'f16w8_rest' ('stream' for the head ops); stats_bp: output positions per tile-statistics entry,
+    None when the launch cannot produce statistics (a K split, a plane that is no multiple) or none were asked for; guard: None, or
+    (kernel, cfg, ksplit) of the guarded exact recomputation behind an fp16-split launch, kernel 'bf16x3' or 'f32'"""
+STREAM_PLAN = ConvPlan("head", 1, "stream", "stream", None, None)     # ops.conv_head / ops.stage2_head on the stream kernel
+
+
 class PackedConv:
     """One convolution of the hot path, ready for emo_conv_igemm_f32.  Weights are packed lazily per block config
     (the best config depends on the batch size of the call); `cfg` pins one config (tests / benchmarks).
@@ -670,11 +679,6 @@ class PackedConv:
             self._packed[cfg] = pack_weight(self._weight, cfg).to(self.device)
         return self._packed[cfg]
 
-    def cfg_for(self, n_pos_tiles):
-        if self.pinned_cfg is not None:
-            return self.pinned_cfg
-        return choose_cfg_for_launch(self.cout, n_pos_tiles, self.allowed)
-
     def plan_for(self, n_pos_tiles, Hl=None, Wl=None, ups=False, affine=False, aligned16=True, in_elems_per_sample=0, act="none",
                  io_aligned16=True):
         """(cfg, ksplit, precision) for a launch over n_pos_tiles 128-position tiles of an Hl x Wl output; `affine`: the
@@ -683,26 +687,24 @@ class PackedConv:
         Cin*D*H*W of the input -- that kernel addresses a sample with 32-bit byte offsets (conv_igemm_f16_launch), larger
         inputs take the exact-fp32 kernel like every other unsupported case; `io_aligned16`: output and residual pointers are
         16-byte aligned too (the straight-line epilogue of emo_conv_igemm_f16w8 needs it)"""
-        if self.precision == "f16" and self.pinned_cfg in (None, CFG_D) and aligned16 and io_aligned16 \
-                and in_elems_per_sample * 4 < (1 << 32) and not (affine and self.cin > F16_AFFINE_MAX_CIN) \
+        # what the fp16-operand and split kernels all ask: 16-byte input quads, 32-bit offsets in a sample, the 1024-entry affine table
+        fits16 = aligned16 and in_elems_per_sample * 4 < (1 << 32) and not (affine and self.cin > F16_AFFINE_MAX_CIN)
+        if self.precision == "f16" and fits16 and self.pinned_cfg in (None, CFG_D) and io_aligned16 \
                 and f16w8_launch_fits(self.cout, self.cin, self.kd, self.kh, self.kw, Hl, Wl, n_pos_tiles, act,
                                       in_elems_per_sample // max(1, self.cin) * (4 if ups else 1)):
             # the decoders' 3x3 layers in their launch form: plain fp16 operands on the eight-wave two-tile kernel (round 6)
             return CFG_D, 1, "f16w8"
-        if self.precision == "f16" and f16_launch_fits(Hl, Wl) and self.pinned_cfg in (None, CFG_D, CFG_G) and aligned16 \
-                and in_elems_per_sample * 4 < (1 << 32) \
-                and not (affine and self.cin > F16_AFFINE_MAX_CIN) and not (self.pinned_cfg == CFG_G and self.kh != 3):
+        if self.precision == "f16" and fits16 and f16_launch_fits(Hl, Wl) and self.pinned_cfg in (None, CFG_D, CFG_G) \
+                and not (self.pinned_cfg == CFG_G and self.kh != 3):
             tiles = (self.pinned_cfg,) if self.pinned_cfg is not None else \
                 (CFG_D, CFG_G) if (_CFG_EFF[CFG_G] > 0 and self.kh == 3) else (CFG_D,)
             cfg, ks = plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, n_pos_tiles, tiles, "f16")
             return cfg, ks, "f16"
         if self.pointwise_split:
-            if f16x2_pointwise_launch_fits(Hl, Wl, ups, n_pos_tiles, self.cout, act, in_elems_per_sample // max(1, self.cin)) \
-                    and self.pinned_cfg in (None, CFG_D) \
-                    and aligned16 and in_elems_per_sample * 4 < (1 << 32) and not (affine and self.cin > F16_AFFINE_MAX_CIN):
+            if fits16 and self.pinned_cfg in (None, CFG_D) \
+                    and f16x2_pointwise_launch_fits(Hl, Wl, ups, n_pos_tiles, self.cout, act, in_elems_per_sample // max(1, self.cin)):
                 return CFG_D, 1, "f16x2"
-        elif self.precision in ("bf16x3", "f16x2") and bf16x3_launch_fits(Hl, Wl, ups) and self.pinned_cfg in (None, CFG_D) \
-                and aligned16 and in_elems_per_sample * 4 < (1 << 32) and not (affine and self.cin > F16_AFFINE_MAX_CIN):
+        elif self.precision in ("bf16x3", "f16x2") and fits16 and bf16x3_launch_fits(Hl, Wl, ups) and self.pinned_cfg in (None, CFG_D):
             tile = CFG_D
             if self.precision == "f16x2" and f16x2_tile_cfg(self.cout) == CFG_F and Wl % 64 == 0 and not ups:
                 # (the 32-row tile exists for 4 x 64 position tiles without fused upsample; other maps of such a layer run the
@@ -721,6 +723,39 @@ class PackedConv:
             allowed = allowed + (CFG_E,)
         cfg, ks = plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, n_pos_tiles, allowed, "f32")
         return cfg, ks, "f32"
+
+    def launch_plan(self, N, D, H, W, ups=False, affine=False, res=False, act="none", x16=True, out16=True, res16=True,
+                    in_elems_per_sample=0, ksplit=None, want_stats=False, guard=True):
+        """the ConvPlan of one launch on an [N, Cin, D, H, W] input (D = 1: a 2-D one).  affine / res: the launch carries an input
+        scale / shift, a residual; x16 / out16 / res16: those tensors are 16-byte aligned (res16 is True without a residual);
+        ksplit: the caller's K split in place of the planner's; guard: ops.F16X2_GUARD at the time of the call"""
+        Hl, Wl, io16 = (2 * H if ups else H), (2 * W if ups else W), out16 and res16
+        tiles = max(1, -(-N * D * Hl * Wl // 128))
+        # (the pointwise split kernel has the straight-line epilogue only: 16-byte aligned out / res)
+        cfg, ks, prec = self.plan_for(tiles, Hl, Wl, ups, affine, x16 and (io16 or not self.pointwise_split), in_elems_per_sample,
+                                      act, io16)
+        ks = ks if ksplit is None else int(ksplit)
+        form = "direct"
+        if prec == "f16x2" and self.pointwise_split:
+            form = "pointwise"
+        elif ups and prec == "f16x2" and cfg == CFG_D and ks == 1 and D == 1 and up2_launch_fits(
+                self.cout, self.cin, self.kd, self.kh, self.kw, N, H, W, ups, affine=affine, res=res, act=act, aligned16=x16 and out16):
+            form = "up2"        # an up-convolution as four 2x2 phase convolutions: same plan, weight layout CFG_F16X2_UP2
+        elif prec == "f16w8" and f16w8_rest_fits(self.cout, Hl, Wl):
+            form = "f16w8_rest"     # an odd tile count: the pairs on the eight-wave kernel, the last tile on the older fp16 kernel
+        # (a pointwise layer on the fp16 split keeps its tile statistics in the 128-position layout of the fp32 MFMA kernel that
+        # recomputes it behind a raised overflow word: csrc/conv_igemm_f16x2_p1.h writes two half entries per 256-position tile)
+        bp = 128 if form == "pointwise" else _BP[cfg]
+        stats_bp = bp if want_stats and ks == 1 and (D * Hl * Wl) % bp == 0 else None
+        recompute = None
+        if prec == "f16x2" and guard:
+            recompute = ("bf16x3", CFG_D, ks)       # the 64-row tile of the bf16 split whatever tile the fp16-split launch used
+            if form == "pointwise":
+                # the fp32 MFMA kernel at its own launch plan, and without a K split when tile statistics travel with the output:
+                # a split launch cannot produce them, and `out` / `stats` would stay un-recomputed with the word raised
+                gcfg, gks = plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, tiles, self.allowed, "f32")
+                recompute = ("f32", gcfg, 1 if stats_bp else gks)
+        return ConvPlan(cfg, ks, prec, form, stats_bp, recompute)
 
     @classmethod
     def from_state_dict(cls, sd, prefix, kind, device, cfg=None, precision=None):

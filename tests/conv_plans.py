@@ -1,31 +1,23 @@
 """Which convolution kernel a launch ran (a helper module, not a test file).
 
-executed() reads what ops.conv_igemm / ops.conv_head left on the layer and names the launch form; Expect is what a test case
-declares about its launch, and check() holds a launch to it.  One copy: the parity tests (run_conv of tests/test_kernels_gpu.py),
-the launch checker of tests/test_conv_launches_fp64_gpu.py and the plan lattice all derive "what ran" here.
+executed() reads the plan ops.conv_igemm / ops.conv_head left on the layer (last_launch: what the product ran); Expect is what a
+test case declares about its launch, and check() holds a launch to it.  One copy: the parity tests (run_conv of
+tests/test_kernels_gpu.py), the launch checker of tests/test_conv_launches_fp64_gpu.py and the plan lattice all read "what ran" here.
 """
 from collections import namedtuple
-
-from emoportraits_amd import pack
 
 FORMS = ("direct", "up2", "pointwise", "f16w8_rest", "stream")
 
 
 def executed(layer, out):
-    """(precision, block config, K split, form) of the last launch of `layer`, which wrote `out`.
-    precision: 'f32' | 'bf16x3' | 'f16x2' | 'f16' | 'f16w8' | 'stream' (PackedConv.last_plan); form: 'stream' (ops.conv_head's
-    kernel), 'pointwise' (the fp16 split's 1x1 kernel), 'f16w8_rest' (an odd channel-tile count: pairs on the eight-wave kernel, the
-    last tile on the older fp16-operand kernel), 'up2' (the phase form of a fused-upsample 3x3) or 'direct'"""
-    cfg, ks, prec = layer.last_plan
-    if prec == "stream":
-        form = "stream"
-    elif prec == "f16x2" and layer.pointwise_split:
-        form = "pointwise"
-    elif prec == "f16w8" and pack.f16w8_rest_fits(layer.cout, out.shape[-2], out.shape[-1]):
-        form = "f16w8_rest"
-    else:
-        form = getattr(layer, "last_form", None) or "direct"
-    return prec, cfg, ks, form
+    """(precision, block config, K split, form) of the last launch of `layer`, which wrote `out`: the product's own record of it
+    (layer.last_launch, the pack.ConvPlan that ops.conv_igemm / conv_head / stage2_head executed), nothing derived here.
+    precision: 'f32' | 'bf16x3' | 'f16x2' | 'f16' | 'f16w8' | 'stream'; form: 'stream' (ops.conv_head's kernel), 'pointwise' (the
+    fp16 split's 1x1 kernel), 'f16w8_rest' (an odd channel-tile count: pairs on the eight-wave kernel, the last tile on the older
+    fp16-operand kernel), 'up2' (the phase form of a fused-upsample 3x3) or 'direct'"""
+    plan = layer.last_launch
+    assert plan.form in FORMS and tuple(plan[:3]) == tuple(layer.last_plan), (plan, layer.last_plan)
+    return plan.prec, plan.cfg, plan.ksplit, plan.form
 
 
 class Expect(namedtuple("Expect", "prec cfg form split")):
