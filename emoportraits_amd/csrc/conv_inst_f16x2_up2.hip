@@ -8,20 +8,25 @@
 // 4 Cin MACs per output instead of 9 Cin -- 2.25x fewer MFMAs, and a shorter accumulation.  Zero padding stays exact (high-res
 // row -1 reads low-res row -1, row 2H reads low-res row H).
 //
-// Item: one 64-channel output tile x a low-res region of 2 rows x 64 columns (a high-res 4 x 128 block, two 4 x 64 statistics
-// tiles).  Stage: 16 input channels, one converted (2 + 2) x (64 + 2) low-res patch in LDS (the staging of conv_igemm_bf16x3.h
-// and conv_igemm_f16x2_ct2.h on a low-res tile, no upsampling gather).  Half-stage h = row phase p: its kernel W[h] holds the 8 taps
-// (2 column phases x 2 x 2) of that phase, 32 KiB.  Wave w = (q = w & 1, low-res row g = w >> 1): it runs column phase q on the
-// 64 positions of its row, 4 tap steps per half-stage, and keeps both row phases' accumulators (2 x 128 registers, as the
-// two-tile kernel).  One barrier per half-stage, everything in flight drained there (vmcnt(0)):
+// Item: one 64-channel output tile x a low-res region of 4 rows x 64 columns (a high-res 8 x 128 block, four 4 x 64 statistics
+// tiles).  Stage: 16 input channels, one converted (4 + 2) x (64 + 2) low-res patch in LDS (the staging of conv_igemm_bf16x3.h
+// and conv_igemm_f16x2_ct2.h on a low-res tile, no upsampling gather): 108 of the 128 threads of a staging group own a quad or a
+// halo pixel.  Half-stage h = row phase p: its kernel W[h] holds the 8 taps (2 column phases x 2 x 2) of that phase, 32 KiB.
+// Wave w = (q = w & 1, row pair g = w >> 1): it runs column phase q on the 128 positions of low-res rows 2 g, 2 g + 1, 4 tap steps
+// per half-stage, 24 MFMAs per step, and keeps both row phases' accumulators in ONE set (2 x 128 registers): per tap step the two
+// cross products, then the leading product, into the same accumulator.  A phase output sums 4 Cin products, not 9 Cin, so the
+// single set stays inside the split's error bounds; the 9-tap kernels keep two sets.  A map whose height is no
+// multiple of 4 ends in items whose rows 2, 3 lie outside: they are staged as zeros and neither stored nor counted.
+// One barrier per half-stage, everything in flight drained there (vmcnt(0)):
 //   (cg, h)  steps 0 .. 2  pieces 2 .. 7 of the next half-stage's kernel into W[h ^ 1]
 //            step 3        barrier; pieces 0, 1 of the half-stage after it into W[h]; fragments of the next half-stage's step 0
 //   (cg, 0)  steps 0 .. 3  the patch of stage cg + 1 converted from the raw registers into P[pp ^ 1], one pixel per step
-//   (cg, 0)  step 3        behind the last pixel's conversion: the raw loads of stage cg + 2 -- four tap steps (48 MFMAs) ahead of
+//   (cg, 0)  step 3        behind the last pixel's conversion: the raw loads of stage cg + 2 -- four tap steps (96 MFMAs) ahead of
 //                          the barrier of (cg, 1) that drains them (EMO_UP2_LOADS_EARLY = 0: steps 0 .. 2 of (cg, 1), one to
 //                          three steps of flight)
-// Epilogue: through LDS, 32 channels at a time -- the waves' column phases interleaved into whole 128-column high-res rows, + bias,
-// 16-byte stores, the (mean, M2) of the two 4 x 64 tiles (the TileStats layout of block config D).  No residual, no activation.
+// Epilogue: through LDS in eight passes of 32 channels x one 4 x 64 statistics tile (one row pair's two waves, 16-byte LDS writes
+// into an image [channel][row][column phase][32 low-res columns]); the read-out interleaves the column phases into whole rows,
+// + bias, 16-byte stores, the tile's (mean, M2) (the TileStats layout of block config D).  No residual, no activation.
 // CHAINED items (EMO_UP2_CHAIN, the scheme of conv_igemm_f16x2_ct2.h): when the block's next item belongs to the same sample (same
 // scale / shift tables) and the item has >= 2 stages, the look-ahead of the last two stages -- dead re-stages otherwise -- fetches
 // the next item's first stage instead: kernel (stage 0, p = 0) into W[0], the raw loads of its stages 0 and 1 with ITS cursor, its
@@ -42,8 +47,8 @@
 #endif
 
 struct ConvCfgUp2 {
-  static constexpr int BM = 64, TM = 2, TP = 2, KC = 16, NPL = 2;
-  static constexpr int TRL = 2, TWL = 64;                // low-res extent of an item
+  static constexpr int BM = 64, TM = 2, TP = 4, KC = 16, NPL = 2;
+  static constexpr int TRL = 4, TWL = 64;                // low-res extent of an item
   static constexpr int PR = TRL + 2, NQ = TWL / 4, NQ1 = NQ + 1;
   static constexpr int SUB = ((PR * NQ1 + 4 + 11) / 16) * 16 + 4;
   static constexpr int CHS = 4 * SUB, NG = 2, QPG = 128, NHQ = 2 * PR;
@@ -58,11 +63,13 @@ struct ConvCfgUp2 {
   static constexpr int OFF_P = 0, OFF_W = 2 * PBUF, OFF_SCT = OFF_W + WST;
   static constexpr int WSTRIDE = WST + (2 * SCT + BM) / 4;           // W[1] = W[0] + WSTRIDE: behind the tables and the bias
   static constexpr int OFF_BIAS_F = OFF_SCT * 4 + 2 * SCT;          // (float index) [BM]
-  static constexpr int EPI_CS = 4 * 132 + 4;                         // floats per channel of the epilogue image: 4 rows of 128 + 4
+  static constexpr int EPI_CS = 4 * 64 + 4;                          // floats per channel of the epilogue image: 4 rows of 2 x 32, + 4
+  static constexpr int EPI_CH = 32;                                  // channels of one epilogue pass (4 rows x 128 columns do not fit behind W[0])
   static constexpr int OFF_IMG_F = (OFF_W + WSTRIDE) * 4;            // (float index) the image: over W[1] and the tail
-  static constexpr int LDS_BYTES = (OFF_IMG_F + 32 * EPI_CS) * 4;
+  static constexpr int LDS_BYTES = (OFF_IMG_F + EPI_CH * EPI_CS) * 4;
   static_assert(OFF_IMG_F >= OFF_BIAS_F + BM, "the epilogue image spares the patch buffers, W[0], the tables and the bias: a chained successor's");
-  static_assert(32 * EPI_CS * 4 >= WST_BYTES, "W[1] lies inside the image's allocation");
+  static_assert(EPI_CH * EPI_CS * 4 >= WST_BYTES, "W[1] lies inside the image's allocation");
+  static_assert(TRL == 4 && TP == 4, "a wave holds two low-res rows: one epilogue pass is one row pair's 4 high-res rows");
   static_assert(WST_BYTES == 32 * 1024, "eight 1 KiB pieces per wave and half-stage");
   static_assert(PR * NQ + NHQ <= QPG, "one interior quad or one halo pixel per thread and stage");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
@@ -87,7 +94,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l32 = lane & 31;
   const int wq = wave & 1;                               // column phase of the wave
-  const int p0 = (wave >> 1) * TP * 32;                  // its 64 positions: low-res row wave >> 1 of the item
+  const int p0 = (wave >> 1) * TP * 32;                  // its 128 positions: low-res rows 2 (wave >> 1), + 1 of the item
   float sat_m = 0.0f;
 
   const int HW = a.H * a.W;
@@ -115,7 +122,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
     q_slb[i] = ((is_quad || (is_halo && i == (h_side ? 0 : 3))) ? own : dump) * 16;
   }
 
-  floatx16 acc_lo[2][TM][TP], acc_hi[2][TM][TP];         // [row phase]
+  floatx16 acc[2][TM][TP];                               // [row phase]: one set for the three products
 
   // ---- work items: (sample, low-res tile, channel tile), XCD-contiguous, channel tile fastest; persistent blocks ----
   const int q8 = a.n_work >> 3, r8 = a.n_work & 7;
@@ -289,7 +296,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
       const char* const w1_ = EMO_U_WPTR(cotile, 0, 1);
       EMO_U_DMA_PIECE(w1_, 1, 0)
       EMO_U_DMA_PIECE(w1_, 1, 1)
-      EMO_P_BARRIER(40);                  // (at most 2 x 18 stores of the epilogue + these two pieces are outstanding)
+      EMO_P_BARRIER(63);                  // (the epilogue's stores and these two pieces stay outstanding)
     } else {
       // ---- full prologue: tables, bias, the whole kernel of (stage 0, p = 0), pieces 0, 1 of (0, 1), patch 0 converted, loads of stage 1 ----
       {
@@ -339,7 +346,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < TP; ++j)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) { acc_lo[c][i][j][r] = 0.0f; acc_hi[c][i][j][r] = 0.0f; }
+          for (int r = 0; r < 16; ++r) acc[c][i][j][r] = 0.0f;
     {
       const int pb0_ = (Cfg::OFF_P + pp * PBUF) * 16;
 #pragma unroll
@@ -389,15 +396,13 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
             EMO_U_ISSUE_LOADS(0, 8)
           }
 #pragma unroll
-          for (int p = 0; p < NPROD; ++p) {
-            const int pa = PA3[p], pb = PB3[p];
+          for (int p = 0; p < NPROD; ++p) {                // (the cross products first, the leading product last: 8 MFMAs
+            const int pa = PA3[p], pb = PB3[p];              //  lie between two on one accumulator)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-              for (int j = 0; j < TP; ++j) {
-                floatx16& acc_ = (pa == 0 && pb == 0) ? acc_lo[h][i][j] : acc_hi[h][i][j];
-                acc_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb_[fcur][pb][j], fa_[fcur][pa][i], acc_, 0, 0, 0);
-              }
+              for (int j = 0; j < TP; ++j)
+                acc[h][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb_[fcur][pb][j], fa_[fcur][pa][i], acc[h][i][j], 0, 0, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -406,7 +411,9 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
       pp ^= 1;
     }
 
-    // ---- epilogue: 32 channels at a time through an LDS image [channel][4 high-res rows][128 columns (+ 4)] in W[1] + tail ----
+    // ---- epilogue: eight passes (channel block i, row pair g, column half k = one 4 x 64 statistics tile) through an LDS image
+    //      [32 channels][4 high-res rows][column phase][32 low-res columns] (+ 4) in W[1] + tail; a row pair beyond the map (ragged
+    //      height) is skipped ----
     EMO_S_STAMP(2)
     EMO_P_WAIT(0);
     EMO_S_STAMP(5)
@@ -419,70 +426,77 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
     const int Ho = a.Hl, Wo = a.Wl;
     const unsigned oplane = (unsigned)Ho * Wo;
     const int tiles_xo = Wo / 64;
-    const int ec = tid >> 4, eu = tid & 15;                 // read-out: channel ec (+ 16), columns 4 eu + 64 k
+    const int ec = tid >> 4, eu = tid & 15;                 // read-out: channels ec, ec + 16, high-res columns 4 eu .. 4 eu + 3 of the tile
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
-      for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int j = 0; j < TP; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float v = (emo_acc_read(acc_lo[p][i][j][r]) + emo_acc_read(acc_hi[p][i][j][r])) * a.out_scale;
-            const int m = (r >> 2) * 8 + half * 4 + (r & 3);          // low-res column j * 32 + m of the wave's row
-            const int hr = 2 * (wave >> 1) + p, col = 2 * (j * 32 + m) + wq;
-            img[l32 * Cfg::EPI_CS + hr * 132 + col] = v;
-          }
-      __syncthreads();
-#pragma unroll
-      for (int cc = 0; cc < 2; ++cc) {
-        const int c = cc * 16 + ec;
-        const int co = cotile * BM + i * 32 + c;
-        const float bs = smem[Cfg::OFF_BIAS_F + i * 32 + c];
-        float* const obase = a.out + ((long)it_n * a.Cout + co) * oplane;
-        float s_[2] = {0.0f, 0.0f};
-        floatx4 v_[4][2];
-#pragma unroll
-        for (int hr = 0; hr < 4; ++hr)
+      for (int g = 0; g < 2; ++g) {
+        if (y0 + 2 * g < a.H) {                             // (block-uniform: the barriers inside are taken by every thread or none)
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
-            floatx4 v = *reinterpret_cast<const floatx4*>(img + c * Cfg::EPI_CS + hr * 132 + 4 * eu + 64 * k);
-            v = v + floatx4{bs, bs, bs, bs};
-            v_[hr][k] = v;
-            float* const op = obase + (unsigned)(2 * y0 + hr) * Wo + (2 * x0 + 4 * eu + 64 * k);
-            if (EMO_CONV_NT_STORE) __builtin_nontemporal_store(v, reinterpret_cast<floatx4*>(op));
-            else *reinterpret_cast<floatx4*>(op) = v;
-            s_[k] += (v[0] + v[1]) + (v[2] + v[3]);
-          }
-        if (want_stats) {
-          // (mean, M2) of the two 4 x 64 tiles: 16 lanes of a DPP row per channel, 16 values per lane and tile
-          emo_row16_sum_n<2>(s_);
-          float m2_[2] = {0.0f, 0.0f};
+            if (i + g + k > 0) __syncthreads();             // (the image is rewritten: the previous pass has been read out)
+            if ((wave >> 1) == g) {
 #pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            s_[k] *= 1.0f / 256.0f;
+              for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int hr = 0; hr < 4; ++hr)
+                for (int jj = 0; jj < 2; ++jj)              // low-res row 2 g + jj, columns 32 k + m: position tile j = 2 jj + k
 #pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const float d = v_[hr][k][e] - s_[k];
-                m2_[k] = __fmaf_rn(d, d, m2_[k]);
+                  for (int r4 = 0; r4 < 4; ++r4) {
+                    floatx4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = emo_acc_read(acc[p][i][2 * jj + k][4 * r4 + e]) * a.out_scale;
+                    const int m = r4 * 8 + half * 4;        // (the accumulator's rows 4 r4 .. 4 r4 + 3: four consecutive columns)
+                    *reinterpret_cast<floatx4*>(img + l32 * Cfg::EPI_CS + (2 * jj + p) * 64 + wq * 32 + m) = v;
+                  }
+            }
+            __syncthreads();
+            const int ptile = ((y0 >> 1) + g) * tiles_xo + (x0 >> 5) + k;       // the 4 x 64 high-res tile
+            float s_[2] = {0.0f, 0.0f};
+            floatx4 v_[2][4];
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) {
+              const int c = cc * 16 + ec;
+              const float bs = smem[Cfg::OFF_BIAS_F + i * 32 + c];
+              float* const obase = a.out + ((long)it_n * a.Cout + cotile * BM + i * 32 + c) * oplane;
+#pragma unroll
+              for (int hr = 0; hr < 4; ++hr) {
+                const float2 e0 = *reinterpret_cast<const float2*>(img + c * Cfg::EPI_CS + hr * 64 + 2 * eu);
+                const float2 e1 = *reinterpret_cast<const float2*>(img + c * Cfg::EPI_CS + hr * 64 + 32 + 2 * eu);
+                const floatx4 v = floatx4{e0.x, e1.x, e0.y, e1.y} + floatx4{bs, bs, bs, bs};
+                v_[cc][hr] = v;
+                float* const op = obase + (unsigned)(2 * y0 + 4 * g + hr) * Wo + (2 * x0 + 64 * k + 4 * eu);
+                if (EMO_CONV_NT_STORE) __builtin_nontemporal_store(v, reinterpret_cast<floatx4*>(op));
+                else *reinterpret_cast<floatx4*>(op) = v;
+                s_[cc] += (v[0] + v[1]) + (v[2] + v[3]);
               }
-          }
-          emo_row16_sum_n<2>(m2_);
-          if (eu == 0) {
+            }
+            if (want_stats) {
+              // (mean, M2) of the tile for two channels: 16 lanes of a DPP row per channel, 16 values per lane
+              emo_row16_sum_n<2>(s_);
+              float m2_[2] = {0.0f, 0.0f};
 #pragma unroll
-            for (int k = 0; k < 2; ++k) {
-              const int ptile = (y0 >> 1) * tiles_xo + (x0 >> 5) + k;       // the 4 x 64 high-res tile
-              reinterpret_cast<float2*>(a.gn_stats)[((long)it_n * (oplane / 256) + ptile) * a.Cout + co] = make_float2(s_[k], m2_[k]);
+              for (int cc = 0; cc < 2; ++cc) {
+                s_[cc] *= 1.0f / 256.0f;
+#pragma unroll
+                for (int hr = 0; hr < 4; ++hr)
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) {
+                    const float d = v_[cc][hr][e] - s_[cc];
+                    m2_[cc] = __fmaf_rn(d, d, m2_[cc]);
+                  }
+              }
+              emo_row16_sum_n<2>(m2_);
+              if (eu == 0) {
+#pragma unroll
+                for (int cc = 0; cc < 2; ++cc)
+                  reinterpret_cast<float2*>(a.gn_stats)[((long)it_n * (oplane / 256) + ptile) * a.Cout + cotile * BM + i * 32 + cc * 16 + ec] =
+                      make_float2(s_[cc], m2_[cc]);
+              }
             }
           }
         }
       }
-      if (i == 0) {
-        EMO_S_STAMP(8)
-        __syncthreads();     // (the image is rewritten by the next channel block)
-      }
+      if (i == 0) { EMO_S_STAMP(8) }
     }
     EMO_S_STAMP(9)
 #if EMO_S_TIMING
@@ -528,23 +542,24 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
 
 // The launch form (emoportraits_amd.pack.up2_launch_fits mirrors every check): 2-D, 3x3 with the fused nearest x2 upsample, no
 // K split, no residual, no activation, not a guarded launch, whole 64-channel tiles, a multiple of 8 input channels (at most SCT
-// with an affine), a low-res width that is a multiple of 64 and an even low-res height, 16-byte aligned input and output, input
+// with an affine), a low-res width that is a multiple of 64 and an even low-res height (items are 4 rows: the last ones of a
+// height that is no multiple of 4 are half empty), 16-byte aligned input and output, input
 // offsets inside 2^32 bytes per sample, output planes inside 2^31 elements.
 int conv_f16x2_up2_launch(ConvArgs a, hipStream_t s) {
   using Cfg = ConvCfgUp2;
   if (a.KD != 1 || a.D != 1 || a.ksplit != 1 || a.res != nullptr || a.act != EMO_ACT_NONE || a.run_if != nullptr) return EMO_ERR_UNSUPPORTED;
   if (a.Cout % Cfg::BM || a.Cin % 8 || (a.scale && a.Cin > Cfg::SCT)) return EMO_ERR_UNSUPPORTED;
-  if (a.W % Cfg::TWL || a.H % Cfg::TRL) return EMO_ERR_UNSUPPORTED;
+  if (a.W % Cfg::TWL || a.H % 2) return EMO_ERR_UNSUPPORTED;
   if ((reinterpret_cast<unsigned long long>(a.x) & 15ull) || (reinterpret_cast<unsigned long long>(a.out) & 15ull)) return EMO_ERR_ALIGN;
   if ((unsigned long long)a.Cin * a.H * a.W * 4ull >= (1ull << 32) || (long)a.Hl * a.Wl >= (1l << 31)) return EMO_ERR_UNSUPPORTED;
-  const long nt = (long)(a.W / Cfg::TWL) * (a.H / Cfg::TRL);
+  const long nt = (long)(a.W / Cfg::TWL) * ((a.H + Cfg::TRL - 1) / Cfg::TRL);
   const int cot = a.Cout / Cfg::BM;
   if (a.N > 65535 || nt * cot * a.N > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
   auto kern = conv_igemm_f16x2_up2_kernel;
   const int rc = emo_raise_dynamic_lds(kern);
   if (rc != EMO_OK) return rc;
   a.tiles_x = a.W / Cfg::TWL;
-  a.tiles_y = a.H / Cfg::TRL;
+  a.tiles_y = (a.H + Cfg::TRL - 1) / Cfg::TRL;
   a.tiles_z = 1;
   a.n_cchunks = (a.Cin + Cfg::KC - 1) / Cfg::KC;
   a.stages_per_split = a.n_cchunks;

@@ -6,7 +6,8 @@ Needs the measurement build of the library (never the product):
     EMO_HIP_LIB=emoportraits_amd/lib/libemoportraits_hip_timing.so python tools/conv_phase_timing.py [B]
     ... python tools/conv_phase_timing.py [B] --up2      # the decoder's three up-convolutions on the phase kernel
                                                          # (csrc/conv_inst_f16x2_up2.hip); an EMO_S_TIMING=2 build adds, per wave,
-                                                         # the K loop's cycles in s_waitcnt and in s_barrier
+                                                         # the K loop's cycles in s_waitcnt and in s_barrier;
+                                                         # --item-rows 2 for a library from before the 4-row item
 JSON lines: per (layer shape, operand mode) the median / p90 of every phase in shader cycles, the per-CU occupancy of each
 phase (sum of the phase over the CU's blocks / the CU's busy span), and the launch's wall time by HIP events.
 """
@@ -92,6 +93,7 @@ def main_up2(B, lib):
     the phases of analyse(): the share of items that started with the chained prologue, and the EXPOSED time of the launch -- per
     CU, the sum over its items of prologue + epilogue + store drain + gap (and, on an EMO_S_TIMING=2 build, the K loop's cycles in
     s_waitcnt, the slowest wave's), in cycles and in milliseconds at the launch's effective clock"""
+    item_rows = int(sys.argv[sys.argv.index("--item-rows") + 1]) if "--item-rows" in sys.argv else 4
     for cin, cout, dims in UP2_SHAPES:
         x = torch.randn(B, cin, *dims, device=DEV)
         w = torch.randn(cout, cin, 3, 3) / math.sqrt(cin * 9)
@@ -110,14 +112,22 @@ def main_up2(B, lib):
         b.record()
         torch.cuda.synchronize()
         ms = a.elapsed_time(b)
-        n_items = B * (dims[0] // 2) * (dims[1] // 64) * (cout // 64)
+        n_items = B * (-(-dims[0] // item_rows)) * (dims[1] // 64) * (cout // 64)      # item: 64 channels x item_rows x 64 low-res
         stages = -(-cin // 16)
+        slots = stages * 8 * 6 * item_rows                    # MFMAs of a wave's K loop: 8 tap steps, 3 products x 2 x item_rows tiles
         full = stamps(lib, "up2", 65536)
         t = full[:min(n_items, 65536)]
-        rec = dict(B=B, cin=cin, cout=cout, dims=dims, ups=True, mode="up2", statistics=True, ms=round(ms, 3), stages=stages,
+        rec = dict(B=B, cin=cin, cout=cout, dims=dims, ups=True, mode="up2", statistics=True, ms=round(ms, 3), stages=stages, item_rows=item_rows,
                    lib=os.path.basename(os.environ.get("EMO_HIP_LIB", "product")))
         rec.update(analyse(t))
         rec["chained_in_share"] = round(float((t[:, 15] & 1).mean()), 4)
+        # per MFMA slot and per output value (64 channels x 4 item_rows x 64 high-res positions per item), so that items of
+        # different sizes compare
+        n_out = 64 * 4 * item_rows * 64
+        rec["kloop_cycles_per_mfma_slot"] = round(rec["kloop"]["mean"] / slots, 2)
+        rec["epilogue_cycles_per_output"] = round((rec["epilogue_issue"]["mean"] + rec["store_drain"]["mean"]) / n_out, 4)
+        rec["item_cycles_per_output"] = round((rec["prologue"]["mean"] + rec["kloop"]["mean"] + rec["epilogue_issue"]["mean"]
+                                               + rec["store_drain"]["mean"] + max(rec["gap_to_next_block"]["mean"], 0.0)) / n_out, 4)
         rec["eff_clock_ghz"] = round(rec["cu_span_cycles_med"] / (ms * 1e6), 3)
         per_item = rec["prologue"]["mean"] + rec["epilogue_issue"]["mean"] + rec["store_drain"]["mean"] + max(rec["gap_to_next_block"]["mean"], 0.0)
         waves = analyse_waves(full, n_items)
