@@ -444,24 +444,61 @@ __device__ __forceinline__ float paste_alpha(const float* __restrict__ mt, int S
 // (1 - a) f + a r, truncated like pack_rgb8_kernel: a == 1 gives pack_rgb8's byte, a == 0 the frame's, both exactly
 __device__ __forceinline__ unsigned paste_blend(float a, unsigned f, float r) { return (unsigned)(uint8_t)((1.0f - a) * (float)f + a * r); }
 
-// ---- NV12 frames (ABI 17; the definitions D, E, C and P: include/emo_hip.h).  A frame is Hf rows of Y bytes and Hf / 2 rows of
-// Wf / 2 interleaved (U, V) pairs; both planes share the row pitch and the frame stride, in bytes.
+// ---- YUV 4:2:0 frames (ABI 17 and 22; the definitions D, E, C and P: include/emo_hip.h).  A frame is Hf rows of Y samples and
+// Hf / 2 rows of chroma: Wf / 2 interleaved (U, V) pairs, or a U plane and a V plane of Wf / 2 samples a row.  Pitches and the
+// frame stride are in bytes; the chroma planes share their pitch and every plane the frame stride.
 
-// Everything derived from the matrix (Kr, Kb) and the range is formed once on the host in fp64 and rounded to fp32
+// A sample layout: the sample's type, where the chroma lies, and where the code sits in the sample.  Together with yuv_decode_at,
+// yuv_encode, yuv_code and yuv_store / yuv_store2 below it is all that knows where a sample lies and how wide it is.
+template <class T, bool PLANAR, int BITS, int SHIFT>
+struct YuvLayout {
+  using sample = T;
+  static constexpr bool planar = PLANAR;
+  static constexpr int bits = BITS, shift = SHIFT;
+  static constexpr unsigned max_code = (1u << BITS) - 1u;
+  static constexpr float mid = (float)(1u << (BITS - 1)), top = (float)max_code;
+  // the code of a sample: the bits outside it are ignored
+  static __host__ __device__ __forceinline__ unsigned code(T w) {
+    if constexpr (sizeof(T) == 1) return w;
+    else return ((unsigned)w >> SHIFT) & max_code;
+  }
+  // the sample of a code: the bits outside it are zero
+  static __host__ __device__ __forceinline__ T word(unsigned c) { return (T)(c << SHIFT); }
+};
+using Nv12 = YuvLayout<uint8_t, false, 8, 0>;          // layout 0
+using Yuv420p = YuvLayout<uint8_t, true, 8, 0>;        // layout 1
+using P010 = YuvLayout<uint16_t, false, 10, 6>;        // layout 2: the code in the high ten bits
+using Yuv420p10 = YuvLayout<uint16_t, true, 10, 0>;    // layout 3: the code in the low ten bits
+
+// fn(layout trait) of layout id 0 ... 3, or EMO_ERR_BAD_ARG
+template <class Fn>
+inline int with_layout(int layout, Fn fn) {
+  switch (layout) {
+    case 0: return fn(Nv12{});
+    case 1: return fn(Yuv420p{});
+    case 2: return fn(P010{});
+    case 3: return fn(Yuv420p10{});
+    default: return EMO_ERR_BAD_ARG;
+  }
+}
+
+// Everything derived from the matrix (Kr, Kb), the range and the code width is formed once on the host in fp64 and rounded to fp32
 struct Nv12Coef {
   float oy, sy, sc;          // luma offset; luma and chroma code ranges
   float kr, kg, kb;          // y' = kr R + kg G + kb B
   float rv, bu, gv, gu;      // decode: R = y' + rv cr, B = y' + bu cb, G = y' - gv cr - gu cb
-  float cbs, crs;            // encode: Cbc = 128 + cbs (B - y'), Crc = 128 + crs (R - y')
+  float cbs, crs;            // encode: Cbc = mid + cbs (B - y'), Crc = mid + crs (R - y')
 };
 
-inline bool nv12_coef(int matrix, int full_range, Nv12Coef& k) {
+inline bool nv12_coef(int matrix, int full_range, int bits, Nv12Coef& k) {
   double Kr, Kb;
   if (matrix == 0) { Kr = 0.2126; Kb = 0.0722; }            // bt709
   else if (matrix == 1) { Kr = 0.299; Kb = 0.114; }         // bt601
   else return false;
   const double Kg = 1.0 - Kr - Kb;
-  const double oy = full_range ? 0.0 : 16.0, sy = full_range ? 255.0 : 219.0, sc = full_range ? 255.0 : 224.0;
+  const double ten = bits == 10 ? 4.0 : 1.0;                // limited range: the 10-bit constants are 4 x the 8-bit ones
+  const double top = bits == 10 ? 1023.0 : 255.0;
+  const double oy = full_range ? 0.0 : 16.0 * ten, sy = full_range ? top : 219.0 * ten, sc = full_range ? top : 224.0 * ten;
   k.oy = (float)oy; k.sy = (float)sy; k.sc = (float)sc;
   k.kr = (float)Kr; k.kg = (float)Kg; k.kb = (float)Kb;
   k.rv = (float)(2.0 * (1.0 - Kr)); k.bu = (float)(2.0 * (1.0 - Kb));
@@ -470,21 +507,54 @@ inline bool nv12_coef(int matrix, int full_range, Nv12Coef& k) {
   return true;
 }
 
-// what every NV12 entry point refuses before a launch: null planes, an odd frame, a pitch shorter than a row
-inline bool nv12_planes_ok(const void* y, const void* uv, int64_t pitch, int64_t frame_stride, int H, int W) {
-  return y && uv && H > 0 && W > 0 && !(H & 1) && !(W & 1) && pitch >= W && frame_stride >= 0;
+// what every entry point refuses before a launch: null planes (planar: v too), an odd frame, a pitch shorter than a row in
+// bytes, and for 16-bit samples an odd address, pitch or stride
+template <class L>
+inline bool yuv_planes_ok(const void* y, const void* u, const void* v, int64_t pitch_y, int64_t pitch_c, int64_t frame_stride, int H,
+                          int W) {
+  constexpr int64_t B = sizeof(typename L::sample);
+  if (!y || !u || (L::planar && !v) || H <= 0 || W <= 0 || (H & 1) || (W & 1) || frame_stride < 0) return false;
+  if (pitch_y < W * B || pitch_c < (L::planar ? W / 2 : W) * B) return false;
+  if (B == 2 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(u) | (L::planar ? reinterpret_cast<uintptr_t>(v) : 0) |
+                  (uintptr_t)pitch_y | (uintptr_t)pitch_c | (uintptr_t)frame_stride) & 1)) return false;
+  return true;
+}
+
+// may two adjacent samples go out as one store of twice the width: the luma planes' (and, interleaved, the chroma plane's)
+// addresses, pitches and the frame stride are multiples of two samples
+template <class L>
+inline bool yuv_pairs(const void* y, const void* u, int64_t pitch_y, int64_t pitch_c, int64_t frame_stride) {
+  uintptr_t all = reinterpret_cast<uintptr_t>(y) | (uintptr_t)pitch_y | (uintptr_t)frame_stride;
+  if (!L::planar) all |= reinterpret_cast<uintptr_t>(u) | (uintptr_t)pitch_c;
+  return (all & (2 * sizeof(typename L::sample) - 1)) == 0;
 }
 
 __host__ __device__ inline bool nv12_window_ok(int x0, int y0, int w, int h, int Hf, int Wf) {
   return w > 0 && h > 0 && x0 >= 0 && y0 >= 0 && x0 <= Wf - w && y0 <= Hf - h;
 }
 
-// D of frame pixel (y, x): its Y byte and the chroma pair at (y >> 1, x >> 1) -> clamped R, G, B; converted once for all three
-__device__ __forceinline__ void nv12_decode_at(const uint8_t* __restrict__ fy, const uint8_t* __restrict__ fuv, long pitch,
-                                               const Nv12Coef& k, int y, int x, float rgb[3]) {
-  const uint8_t* const c = fuv + (long)(y >> 1) * pitch + (x & ~1);
-  const float yp = __fdiv_rn((float)fy[(long)y * pitch + x] - k.oy, k.sy);
-  const float cb = __fdiv_rn((float)c[0] - 128.0f, k.sc), cr = __fdiv_rn((float)c[1] - 128.0f, k.sc);
+// the planes of one frame and their pitches in bytes (interleaved: v is not used)
+struct YuvFrame { uint8_t* y; uint8_t* u; uint8_t* v; long pitch_y, pitch_c; };
+
+template <class L>
+__device__ __forceinline__ typename L::sample* yuv_row(uint8_t* plane, long row, long pitch) {
+  return reinterpret_cast<typename L::sample*>(plane + row * pitch);
+}
+
+// D of frame pixel (y, x): its Y code and the chroma codes at (y >> 1, x >> 1) -> clamped R, G, B; converted once for all three
+template <class L>
+__device__ __forceinline__ void yuv_decode_at(const YuvFrame& f, const Nv12Coef& k, int y, int x, float rgb[3]) {
+  unsigned cu, cv;
+  if constexpr (L::planar) {
+    cu = L::code(yuv_row<L>(f.u, y >> 1, f.pitch_c)[x >> 1]);
+    cv = L::code(yuv_row<L>(f.v, y >> 1, f.pitch_c)[x >> 1]);
+  } else {
+    const typename L::sample* const c = yuv_row<L>(f.u, y >> 1, f.pitch_c) + (x & ~1);
+    cu = L::code(c[0]);
+    cv = L::code(c[1]);
+  }
+  const float yp = __fdiv_rn((float)L::code(yuv_row<L>(f.y, y, f.pitch_y)[x]) - k.oy, k.sy);
+  const float cb = __fdiv_rn((float)cu - L::mid, k.sc), cr = __fdiv_rn((float)cv - L::mid, k.sc);
   const float r = yp + k.rv * cr, b = yp + k.bu * cb, g = (yp - k.gv * cr) - k.gu * cb;
   rgb[0] = fminf(fmaxf(r, 0.0f), 1.0f);
   rgb[1] = fminf(fmaxf(g, 0.0f), 1.0f);
@@ -492,27 +562,47 @@ __device__ __forceinline__ void nv12_decode_at(const uint8_t* __restrict__ fy, c
 }
 
 // E of one pixel before the rounding: the luma code and the two chroma codes of clamp(rgb, 0, 1)
-__device__ __forceinline__ void nv12_encode(const Nv12Coef& k, const float rgb[3], float& yc, float& cbc, float& crc) {
+template <class L>
+__device__ __forceinline__ void yuv_encode(const Nv12Coef& k, const float rgb[3], float& yc, float& cbc, float& crc) {
   const float r = fminf(fmaxf(rgb[0], 0.0f), 1.0f), g = fminf(fmaxf(rgb[1], 0.0f), 1.0f), b = fminf(fmaxf(rgb[2], 0.0f), 1.0f);
   const float yp = (k.kr * r + k.kg * g) + k.kb * b;
   yc = k.oy + k.sy * yp;
-  cbc = 128.0f + k.cbs * (b - yp);
-  crc = 128.0f + k.crs * (r - yp);
+  cbc = L::mid + k.cbs * (b - yp);
+  crc = L::mid + k.crs * (r - yp);
 }
 
-// floor(v) held to 0 ... 255; the callers add the 0.5
-__device__ __forceinline__ unsigned nv12_byte(float v) { return (unsigned)fminf(fmaxf(floorf(v), 0.0f), 255.0f); }
+// floor(v) held to 0 ... 255 (10 bits: 1023); the callers add the 0.5
+template <class L>
+__device__ __forceinline__ unsigned yuv_code(float v) { return (unsigned)fminf(fmaxf(floorf(v), 0.0f), L::top); }
 
-// two adjacent bytes: one 16-bit store where the planes allow it (`pairs`: even addresses, pitch and frame stride)
-__device__ __forceinline__ void nv12_store2(uint8_t* p, unsigned lo, unsigned hi, bool pairs) {
-  if (pairs) *reinterpret_cast<uint16_t*>(p) = (uint16_t)(lo | (hi << 8));
-  else { p[0] = (uint8_t)lo; p[1] = (uint8_t)hi; }
+// two adjacent samples: one store of twice the width where the planes allow it (`pairs`: yuv_pairs)
+template <class L>
+__device__ __forceinline__ void yuv_store2(typename L::sample* p, unsigned lo, unsigned hi, bool pairs) {
+  if constexpr (sizeof(typename L::sample) == 1) {
+    if (pairs) *reinterpret_cast<uint16_t*>(p) = (uint16_t)(lo | (hi << 8));
+    else { p[0] = (uint8_t)lo; p[1] = (uint8_t)hi; }
+  } else {
+    if (pairs) *reinterpret_cast<uint32_t*>(p) = (uint32_t)L::word(lo) | ((uint32_t)L::word(hi) << 16);
+    else { p[0] = L::word(lo); p[1] = L::word(hi); }
+  }
 }
 
-// emo_pack_nv12: one work item per 2 x 2 luma block -- its four Y bytes and its (U, V) pair have no other writer
-__global__ __launch_bounds__(256) void pack_nv12_kernel(const float* __restrict__ img, uint8_t* __restrict__ yp,
-                                                        uint8_t* __restrict__ uvp, long pitch, long fstride, long N, int H, int W,
-                                                        bool pairs, Nv12Coef k) {
+// the chroma codes of sample (cy, cx): a pair of the interleaved plane, or one sample of each plane (neighbouring lanes hold
+// neighbouring samples)
+template <class L>
+__device__ __forceinline__ void yuv_store_chroma(const YuvFrame& f, int cy, int cx, unsigned u, unsigned v, bool pairs) {
+  if constexpr (L::planar) {
+    yuv_row<L>(f.u, cy, f.pitch_c)[cx] = L::word(u);
+    yuv_row<L>(f.v, cy, f.pitch_c)[cx] = L::word(v);
+  } else {
+    yuv_store2<L>(yuv_row<L>(f.u, cy, f.pitch_c) + 2 * cx, u, v, pairs);
+  }
+}
+
+// emo_pack_nv12 / emo_pack_yuv420: one work item per 2 x 2 luma block -- its four Y samples and its (U, V) have no other writer
+template <class L>
+__global__ __launch_bounds__(256) void pack_yuv420_kernel(const float* __restrict__ img, YuvFrame f0, long fstride, long N, int H,
+                                                          int W, bool pairs, Nv12Coef k) {
   const int Hc = H >> 1, Wc = W >> 1;
   const long HW = (long)H * W, total = N * Hc * Wc;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -520,6 +610,7 @@ __global__ __launch_bounds__(256) void pack_nv12_kernel(const float* __restrict_
     const long r = i / Wc;
     const int cy = (int)(r % Hc);
     const long n = r / Hc;
+    const YuvFrame f = {f0.y + n * fstride, f0.u + n * fstride, L::planar ? f0.v + n * fstride : nullptr, f0.pitch_y, f0.pitch_c};
     const float* const src = img + n * 3 * HW + (long)(2 * cy) * W + 2 * cx;
     float cb = 0.0f, cr = 0.0f;
 #pragma unroll
@@ -529,14 +620,14 @@ __global__ __launch_bounds__(256) void pack_nv12_kernel(const float* __restrict_
       for (int dx = 0; dx < 2; ++dx) {
         const float rgb[3] = {src[dy * W + dx], src[HW + dy * W + dx], src[2 * HW + dy * W + dx]};
         float yc, cbc, crc;
-        nv12_encode(k, rgb, yc, cbc, crc);
-        yb[dx] = nv12_byte(yc + 0.5f);
+        yuv_encode<L>(k, rgb, yc, cbc, crc);
+        yb[dx] = yuv_code<L>(yc + 0.5f);
         cb += cbc;                               // ((c00 + c01) + c10) + c11 (0 + c00 is c00)
         cr += crc;
       }
-      nv12_store2(yp + n * fstride + (long)(2 * cy + dy) * pitch + 2 * cx, yb[0], yb[1], pairs);
+      yuv_store2<L>(yuv_row<L>(f.y, 2 * cy + dy, f.pitch_y) + 2 * cx, yb[0], yb[1], pairs);
     }
-    nv12_store2(uvp + n * fstride + (long)cy * pitch + 2 * cx, nv12_byte(cb * 0.25f + 0.5f), nv12_byte(cr * 0.25f + 0.5f), pairs);
+    yuv_store_chroma<L>(f, cy, cx, yuv_code<L>(cb * 0.25f + 0.5f), yuv_code<L>(cr * 0.25f + 0.5f), pairs);
   }
 }
 
@@ -675,15 +766,31 @@ extern "C" int emo_resize2d_f32(const float* x, int64_t plane_stride, int64_t ro
   return emo_launch_status();
 }
 
-// ---- ABI 17: NV12 frames out (definitions: include/emo_hip.h; the crop and the paste: below)
+// ---- ABI 17 / 22: YUV 4:2:0 frames out (definitions: include/emo_hip.h; the crop and the paste: below)
+namespace {
+template <class L>
+int pack_yuv420(const float* img, void* y, void* u, void* v, int64_t pitch_y, int64_t pitch_c, int64_t frame_stride, int N, int H, int W,
+                int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  if (!img || !yuv_planes_ok<L>(y, u, v, pitch_y, pitch_c, frame_stride, H, W) || N <= 0 || !nv12_coef(matrix, full_range, L::bits, k))
+    return EMO_ERR_BAD_ARG;
+  const YuvFrame f = {static_cast<uint8_t*>(y), static_cast<uint8_t*>(u), static_cast<uint8_t*>(v), (long)pitch_y, (long)pitch_c};
+  hipLaunchKernelGGL((pack_yuv420_kernel<L>), dim3(grid_for((long)N * (H / 2) * (W / 2))), dim3(256), 0, (hipStream_t)stream, img, f,
+                     (long)frame_stride, (long)N, H, W, yuv_pairs<L>(y, u, pitch_y, pitch_c, frame_stride), k);
+  return emo_launch_status();
+}
+}  // namespace
+
 extern "C" int emo_pack_nv12(const float* img, uint8_t* y, uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int H, int W,
                              int matrix, int full_range, void* stream) {
-  Nv12Coef k;
-  if (!img || !nv12_planes_ok(y, uv, pitch, frame_stride, H, W) || N <= 0 || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
-  const bool pairs = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(uv) | (uintptr_t)pitch | (uintptr_t)frame_stride) & 1) == 0;
-  hipLaunchKernelGGL(pack_nv12_kernel, dim3(grid_for((long)N * (H / 2) * (W / 2))), dim3(256), 0, (hipStream_t)stream, img, y, uv,
-                     (long)pitch, (long)frame_stride, (long)N, H, W, pairs, k);
-  return emo_launch_status();
+  return pack_yuv420<Nv12>(img, y, uv, nullptr, pitch, pitch, frame_stride, N, H, W, matrix, full_range, stream);
+}
+
+extern "C" int emo_pack_yuv420(int layout, const float* img, void* y, void* u, void* v, int64_t pitch_y, int64_t pitch_c,
+                               int64_t frame_stride, int N, int H, int W, int matrix, int full_range, void* stream) {
+  return with_layout(layout, [&](auto l) {
+    return pack_yuv420<decltype(l)>(img, y, u, v, pitch_y, pitch_c, frame_stride, N, H, W, matrix, full_range, stream);
+  });
 }
 
 // ---- Frame crops and pastes (ABI 9, 15, 17, 18, 19; definitions: include/emo_hip.h): M rows (faces) cut out of or pasted into F
@@ -726,6 +833,15 @@ __device__ __forceinline__ FrameRow frame_row(const long long* __restrict__ ftab
   return r;
 }
 
+// The planes of a YUV 4:2:0 row of the frame table: the chroma straight after the H luma rows -- interleaved with the luma
+// pitch; planar U with half of it, then V after U's H / 2 rows
+template <class L>
+__device__ __forceinline__ YuvFrame table_frame(const FrameRow& fr) {
+  uint8_t* const u = fr.base + fr.H * fr.pitch;
+  if constexpr (L::planar) return YuvFrame{fr.base, u, u + (fr.H >> 1) * (fr.pitch >> 1), fr.pitch, fr.pitch >> 1};
+  else return YuvFrame{fr.base, u, nullptr, fr.pitch, fr.pitch};
+}
+
 // resize2d_kernel with one crop window PER ROW (ABI 9; animate_frames' `windows`: the reference crops every frame around its own
 // face box, notebooks/infer.py:301-352): win[m] = (x0, y0, w, h) of row m inside the planes of its frame, read from device
 // memory, so that a batch is ONE launch instead of one per frame (round 5: a Python loop of single-frame launches).  Per element
@@ -760,16 +876,15 @@ __global__ __launch_bounds__(256) void resize2d_faces_kernel(const float* __rest
 // OnePerRow: win == nullptr is the whole frame.  Table (emo_nv12_faces_ragged_f32): grid (x, M), the items of a block are the
 // outputs of face blockIdx.y, and the planes, the pitch and the size are those of the face's row of the frame table (frame
 // stride 0: yp IS the frame).
-template <Frames FR>
-__global__ __launch_bounds__(256) void nv12_faces_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, long pitch,
-                                                         long fstride, int Hf, int Wf, const int* __restrict__ win,
-                                                         const int* __restrict__ frame_of, float* __restrict__ out, long M, int F,
-                                                         int Ho, int Wo, Nv12Coef k, const long long* __restrict__ ftab) {
+template <Frames FR, class L>
+__global__ __launch_bounds__(256) void yuv420_faces_kernel(YuvFrame f0, long fstride, int Hf, int Wf, const int* __restrict__ win,
+                                                           const int* __restrict__ frame_of, float* __restrict__ out, long M, int F,
+                                                           int Ho, int Wo, Nv12Coef k, const long long* __restrict__ ftab) {
   constexpr bool RAGGED = FR == Frames::Table;
   const long HWo = (long)Ho * Wo, total = (RAGGED ? 1 : M) * HWo;
   if constexpr (RAGGED) {
     const FrameRow fr = frame_row(ftab, frame_of, F);
-    yp = fr.base; uvp = fr.base + fr.H * fr.pitch; pitch = fr.pitch; fstride = 0; Hf = fr.H; Wf = fr.W;
+    f0 = table_frame<L>(fr); fstride = 0; Hf = fr.H; Wf = fr.W;
   }
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int xo = (int)(i % Wo);
@@ -784,17 +899,16 @@ __global__ __launch_bounds__(256) void nv12_faces_kernel(const uint8_t* __restri
       o[0] = 0.0f; o[HWo] = 0.0f; o[2 * HWo] = 0.0f;
       continue;
     }
-    const uint8_t* const fy = yp + f * fstride;
-    const uint8_t* const fuv = uvp + f * fstride;
+    const YuvFrame fr = {f0.y + f * fstride, f0.u + f * fstride, L::planar ? f0.v + f * fstride : nullptr, f0.pitch_y, f0.pitch_c};
     float acc[3];
     if (ww == Wo && wh == Ho) {
-      nv12_decode_at(fy, fuv, pitch, k, wy0 + yo, wx0 + xo, acc);
+      yuv_decode_at<L>(fr, k, wy0 + yo, wx0 + xo, acc);
     } else {
       const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
       bicubic_window<3>(wh, ww, sh * ((float)yo + 0.5f) - 0.5f, sw * ((float)xo + 0.5f) - 0.5f,
                         [&](int yy, int xx, float w, float row[3]) {
                           float rgb[3];
-                          nv12_decode_at(fy, fuv, pitch, k, wy0 + yy, wx0 + xx, rgb);
+                          yuv_decode_at<L>(fr, k, wy0 + yy, wx0 + xx, rgb);
 #pragma unroll
                           for (int c = 0; c < 3; ++c) row[c] += rgb[c] * w;
                         }, acc);
@@ -945,18 +1059,18 @@ __device__ __forceinline__ bool chroma_touched(int x0, int y0, int s, int cy, in
 // the face itself).  A luma byte no window holds is neither read nor written; a chroma pair is touched only if one of its luma
 // pixels is inside a window.
 // Table (emo_paste_faces_ragged_nv12): as in paste_faces_kernel -- one face per blockIdx.y, its frame from the frame table
-template <Frames FR>
-__global__ __launch_bounds__(256) void paste_faces_nv12_kernel(const float* __restrict__ img, const float* __restrict__ matte,
-                                                               const int* __restrict__ win, const int* __restrict__ frame_of,
-                                                               uint8_t* __restrict__ yp, uint8_t* __restrict__ uvp, long pitch,
-                                                               long fstride, unsigned total, int M, int F, int S, int Hf, int Wf,
-                                                               unsigned cmax, float feather, Nv12Coef k,
-                                                               const long long* __restrict__ ftab) {
+template <Frames FR, class L>
+__global__ __launch_bounds__(256) void paste_faces_yuv420_kernel(const float* __restrict__ img, const float* __restrict__ matte,
+                                                                 const int* __restrict__ win, const int* __restrict__ frame_of,
+                                                                 YuvFrame f0, long fstride, unsigned total, int M, int F, int S,
+                                                                 int Hf, int Wf, unsigned cmax, float feather, Nv12Coef k,
+                                                                 const long long* __restrict__ ftab) {
+  using T = typename L::sample;
   constexpr bool RAGGED = FR == Frames::Table;
   const long SS = (long)S * S;
   if constexpr (RAGGED) {
     const FrameRow fr = frame_row(ftab, frame_of, F);
-    yp = fr.base; uvp = fr.base + fr.H * fr.pitch; pitch = fr.pitch; fstride = 0; Hf = fr.H; Wf = fr.W;
+    f0 = table_frame<L>(fr); fstride = 0; Hf = fr.H; Wf = fr.W;
   }
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     const unsigned rr = i / cmax;
@@ -974,8 +1088,10 @@ __global__ __launch_bounds__(256) void paste_faces_nv12_kernel(const float* __re
       if (paste_window_ok(jx, jy, js, win[4 * j + 3], S, Hf, Wf) && chroma_touched(jx, jy, js, cy, cx)) owned = false;
     }
     if (!owned) continue;
-    uint8_t* const fy = yp + f * fstride + (long)(2 * cy) * pitch + 2 * cx;      // the sample's 2 x 2 luma block
-    uint8_t* const puv = uvp + f * fstride + (long)cy * pitch + 2 * cx;
+    T* const fy0 = yuv_row<L>(f0.y + f * fstride, 2 * cy, f0.pitch_y) + 2 * cx;        // the sample's 2 x 2 luma block
+    T* const fy[2] = {fy0, reinterpret_cast<T*>(reinterpret_cast<uint8_t*>(fy0) + f0.pitch_y)};
+    T* const pu = L::planar ? yuv_row<L>(f0.u + f * fstride, cy, f0.pitch_c) + cx : yuv_row<L>(f0.u + f * fstride, cy, f0.pitch_c) + 2 * cx;
+    T* const pv = L::planar ? yuv_row<L>(f0.v + f * fstride, cy, f0.pitch_c) + cx : pu + 1;
     // which of the block's luma pixels some face lo .. m holds: only those are read, carried and written
     unsigned held = 0u;
     for (int j = lo; j <= m; ++j) {
@@ -989,8 +1105,8 @@ __global__ __launch_bounds__(256) void paste_faces_nv12_kernel(const float* __re
     }
     unsigned yb[4];
 #pragma unroll
-    for (int d = 0; d < 4; ++d) yb[d] = (held >> d) & 1u ? fy[(d >> 1) * pitch + (d & 1)] : 0u;
-    unsigned u = puv[0], v = puv[1];
+    for (int d = 0; d < 4; ++d) yb[d] = (held >> d) & 1u ? L::code(fy[d >> 1][d & 1]) : 0u;
+    unsigned u = L::code(*pu), v = L::code(*pv);
     for (int j = lo; j <= m; ++j) {
       const int jx = win[4 * j], jy = win[4 * j + 1], js = win[4 * j + 2];
       if (!paste_window_ok(jx, jy, js, win[4 * j + 3], S, Hf, Wf) || !chroma_touched(jx, jy, js, cy, cx)) continue;
@@ -1011,22 +1127,22 @@ __global__ __launch_bounds__(256) void paste_faces_nv12_kernel(const float* __re
           float r[3], yc, cbc, crc;
           paste_render01(im, S, js, scale, inv_scale, ty, yj, xj, r);
           const float a = paste_alpha(mt, S, js, scale, feather, fs, yj, xj);
-          nv12_encode(k, r, yc, cbc, crc);
-          yb[2 * dy + dx] = nv12_byte(((1.0f - a) * (float)yb[2 * dy + dx] + a * yc) + 0.5f);
+          yuv_encode<L>(k, r, yc, cbc, crc);
+          yb[2 * dy + dx] = yuv_code<L>(((1.0f - a) * (float)yb[2 * dy + dx] + a * yc) + 0.5f);
           a4[2 * dy + dx] = a;
           cb4[2 * dy + dx] = a * cbc;
           cr4[2 * dy + dx] = a * crc;
         }
       }
       const float na = 1.0f - (((a4[0] + a4[1]) + a4[2]) + a4[3]) * 0.25f;
-      u = nv12_byte((na * (float)u + (((cb4[0] + cb4[1]) + cb4[2]) + cb4[3]) * 0.25f) + 0.5f);
-      v = nv12_byte((na * (float)v + (((cr4[0] + cr4[1]) + cr4[2]) + cr4[3]) * 0.25f) + 0.5f);
+      u = yuv_code<L>((na * (float)u + (((cb4[0] + cb4[1]) + cb4[2]) + cb4[3]) * 0.25f) + 0.5f);
+      v = yuv_code<L>((na * (float)v + (((cr4[0] + cr4[1]) + cr4[2]) + cr4[3]) * 0.25f) + 0.5f);
     }
 #pragma unroll
     for (int d = 0; d < 4; ++d)
-      if ((held >> d) & 1u) fy[(d >> 1) * pitch + (d & 1)] = (uint8_t)yb[d];
-    puv[0] = (uint8_t)u;
-    puv[1] = (uint8_t)v;
+      if ((held >> d) & 1u) fy[d >> 1][d & 1] = L::word(yb[d]);
+    *pu = L::word(u);
+    *pv = L::word(v);
   }
 }
 
@@ -1057,16 +1173,19 @@ inline int host_windows(const int32_t* windows_host, int M, int S, bool paste, i
   return EMO_OK;
 }
 
-// ABI 19.  What the four ragged entry points check on the host copy of the frame table and the lists, before a launch: every
-// row an address, a size that fits an int (NV12: even) and a pitch of at least a row's bytes; frame_of and the windows as
-// above.  -> EMO_OK and, for the paste, the largest side to cover.
-inline int ragged_args(const int64_t* table_host, int F, int px_bytes, bool nv12, const int32_t* windows_host,
+// ABI 19 / 22.  What the ragged entry points check on the host copy of the frame table and the lists, before a launch: every
+// row an address, a size that fits an int (YUV: even) and a pitch of at least a row's bytes (16-bit samples: an even address
+// and pitch; planar: a pitch that halves into whole samples); frame_of and the windows as above.  -> EMO_OK and, for the paste, the largest side to cover.
+enum class Rows { Rgb8, Interleaved, Planar };   // what a row of the frame table holds: packed pixels, or YUV 4:2:0 planes
+inline int ragged_args(const int64_t* table_host, int F, int px_bytes, Rows rows, const int32_t* windows_host,
                        const int32_t* frame_of_host, int M, int S, bool paste, int& smax) {
   smax = 0;
   for (int f = 0; f < F; ++f) {
     const int64_t* t = table_host + 4l * f;
     if (t[0] == 0 || t[2] <= 0 || t[3] <= 0 || t[2] > 0x7fffffffl || t[3] > 0x7fffffffl / px_bytes || t[1] < t[3] * px_bytes) return EMO_ERR_BAD_ARG;
-    if (nv12 && ((t[2] | t[3]) & 1)) return EMO_ERR_BAD_ARG;
+    if (rows != Rows::Rgb8 && ((t[2] | t[3]) & 1)) return EMO_ERR_BAD_ARG;
+    if (rows != Rows::Rgb8 && px_bytes == 2 && ((t[0] | t[1]) & 1)) return EMO_ERR_BAD_ARG;          // 16-bit samples: even address, pitch
+    if (rows == Rows::Planar && t[1] % (2 * px_bytes)) return EMO_ERR_BAD_ARG;                       // the chroma pitch is pitch / 2
     const int side = (int)(t[2] < t[3] ? t[2] : t[3]);
     smax = side > smax ? side : smax;                // windows that only the device knows: any valid side of any frame
   }
@@ -1095,13 +1214,12 @@ inline bool paste_items(int smax, bool nv12, bool table, int M, unsigned& bound,
   return true;
 }
 
-template <Frames FR>
-int launch_nv12_crop(const uint8_t* y, const uint8_t* uv, int64_t pitch, int64_t frame_stride, int Hf, int Wf, const int32_t* windows,
-                     const int32_t* frame_of, float* out, int M, int F, int Ho, int Wo, const Nv12Coef& k, const int64_t* table,
-                     void* stream) {
+template <Frames FR, class L>
+int launch_yuv420_crop(const YuvFrame& f, int64_t frame_stride, int Hf, int Wf, const int32_t* windows, const int32_t* frame_of, float* out,
+                       int M, int F, int Ho, int Wo, const Nv12Coef& k, const int64_t* table, void* stream) {
   const dim3 grid = FR == Frames::Table ? ragged_grid((long)Ho * Wo, M) : dim3(grid_for((long)M * Ho * Wo));
-  hipLaunchKernelGGL(nv12_faces_kernel<FR>, grid, dim3(256), 0, (hipStream_t)stream, y, uv, (long)pitch, (long)frame_stride, Hf, Wf,
-                     windows, frame_of, out, (long)M, F, Ho, Wo, k, reinterpret_cast<const long long*>(table));
+  hipLaunchKernelGGL((yuv420_faces_kernel<FR, L>), grid, dim3(256), 0, (hipStream_t)stream, f, (long)frame_stride, Hf, Wf, windows,
+                     frame_of, out, (long)M, F, Ho, Wo, k, reinterpret_cast<const long long*>(table));
   return emo_launch_status();
 }
 
@@ -1116,19 +1234,93 @@ int launch_paste_rgb8(const float* img, const float* matte, const int32_t* windo
   return emo_launch_status();
 }
 
-template <Frames FR>
-int launch_paste_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* frame_of, uint8_t* y, uint8_t* uv,
-                      int64_t pitch, int64_t frame_stride, int M, int F, int S, int Hf, int Wf, int smax, float feather,
-                      const Nv12Coef& k, const int64_t* table, void* stream) {
+template <Frames FR, class L>
+int launch_paste_yuv420(const float* img, const float* matte, const int32_t* windows, const int32_t* frame_of, const YuvFrame& f,
+                        int64_t frame_stride, int M, int F, int S, int Hf, int Wf, int smax, float feather, const Nv12Coef& k,
+                        const int64_t* table, void* stream) {
   unsigned bound, total;
   dim3 grid;
   if (!paste_items(smax, true, FR == Frames::Table, M, bound, total, grid)) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(paste_faces_nv12_kernel<FR>, grid, dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of, y, uv,
-                     (long)pitch, (long)frame_stride, total, M, F, S, Hf, Wf, bound, feather, k, reinterpret_cast<const long long*>(table));
+  hipLaunchKernelGGL((paste_faces_yuv420_kernel<FR, L>), grid, dim3(256), 0, (hipStream_t)stream, img, matte, windows, frame_of, f,
+                     (long)frame_stride, total, M, F, S, Hf, Wf, bound, feather, k, reinterpret_cast<const long long*>(table));
   return emo_launch_status();
 }
 
 inline bool feather_ok(float feather) { return feather >= 0.0f && feather <= 0.5f; }
+
+inline YuvFrame yuv_frame(const void* y, const void* u, const void* v, int64_t pitch_y, int64_t pitch_c) {
+  return YuvFrame{static_cast<uint8_t*>(const_cast<void*>(y)), static_cast<uint8_t*>(const_cast<void*>(u)),
+                  static_cast<uint8_t*>(const_cast<void*>(v)), (long)pitch_y, (long)pitch_c};
+}
+
+// C on frames of one size.  frame_of == nullptr: row m is frame m (ABI 17's form; windows == nullptr: every frame whole);
+// otherwise face m lies in frame frame_of[m] of F (ABI 18's form)
+template <class L>
+int yuv420_crop(const void* y, const void* u, const void* v, int64_t pitch_y, int64_t pitch_c, int64_t frame_stride, int Hf, int Wf,
+                const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host, float* out,
+                int M, int F, int Ho, int Wo, int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  int smax;
+  if (!yuv_planes_ok<L>(y, u, v, pitch_y, pitch_c, frame_stride, Hf, Wf) || !out || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
+  if (!nv12_coef(matrix, full_range, L::bits, k)) return EMO_ERR_BAD_ARG;
+  if (frame_of ? !windows || M < 0 || F <= 0 || (frame_of_host && !frame_of_ok(frame_of_host, M, F))
+               : M <= 0 || frame_of_host || (windows_host && !windows)) return EMO_ERR_BAD_ARG;
+  if (host_windows(windows_host, M, 0, false, Hf, Wf, nullptr, nullptr, smax) != EMO_OK) return EMO_ERR_BAD_ARG;
+  if (M == 0) return EMO_OK;
+  const YuvFrame f = yuv_frame(y, u, v, pitch_y, pitch_c);
+  if (frame_of) return launch_yuv420_crop<Frames::Shared, L>(f, frame_stride, Hf, Wf, windows, frame_of, out, M, F, Ho, Wo, k, nullptr, stream);
+  return launch_yuv420_crop<Frames::OnePerRow, L>(f, frame_stride, Hf, Wf, windows, nullptr, out, M, M, Ho, Wo, k, nullptr, stream);
+}
+
+// P on frames of one size, in place; frame_of as in yuv420_crop (the faces form needs frame_of_host: the order of the paste)
+template <class L>
+int yuv420_paste(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
+                 const int32_t* frame_of_host, void* y, void* u, void* v, int64_t pitch_y, int64_t pitch_c, int64_t frame_stride, int M,
+                 int F, int S, int Hf, int Wf, float feather, int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  if (!img || !windows || !yuv_planes_ok<L>(y, u, v, pitch_y, pitch_c, frame_stride, Hf, Wf) || S <= 0) return EMO_ERR_BAD_ARG;
+  if (!feather_ok(feather) || !nv12_coef(matrix, full_range, L::bits, k)) return EMO_ERR_BAD_ARG;
+  if (frame_of ? !frame_of_host || M < 0 || F <= 0 || !frame_of_ok(frame_of_host, M, F) : M <= 0 || frame_of_host != nullptr)
+    return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = host_windows(windows_host, M, S, true, Hf, Wf, nullptr, nullptr, smax);
+  if (rc != EMO_OK || M == 0) return rc;
+  const YuvFrame f = yuv_frame(y, u, v, pitch_y, pitch_c);
+  if (frame_of)
+    return launch_paste_yuv420<Frames::Shared, L>(img, matte, windows, frame_of, f, frame_stride, M, F, S, Hf, Wf, smax, feather, k, nullptr, stream);
+  return launch_paste_yuv420<Frames::OnePerRow, L>(img, matte, windows, nullptr, f, frame_stride, M, M, S, Hf, Wf, smax, feather, k, nullptr, stream);
+}
+
+// C and P on the frames of a frame table (ABI 19's form)
+template <class L>
+int yuv420_crop_ragged(const int64_t* table, const int64_t* table_host, const int32_t* windows, const int32_t* windows_host,
+                       const int32_t* frame_of, const int32_t* frame_of_host, float* out, int M, int F, int Ho, int Wo, int matrix,
+                       int full_range, void* stream) {
+  Nv12Coef k;
+  if (!table || !table_host || !windows || !frame_of || !frame_of_host || !out || M < 0 || F <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
+  if (!nv12_coef(matrix, full_range, L::bits, k)) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = ragged_args(table_host, F, (int)sizeof(typename L::sample), L::planar ? Rows::Planar : Rows::Interleaved, windows_host,
+                             frame_of_host, M, 0, false, smax);
+  if (rc != EMO_OK || M == 0) return rc;
+  if (M > 65535) return EMO_ERR_UNSUPPORTED;
+  return launch_yuv420_crop<Frames::Table, L>(YuvFrame{nullptr, nullptr, nullptr, 0, 0}, 0, 0, 0, windows, frame_of, out, M, F, Ho, Wo, k, table, stream);
+}
+
+template <class L>
+int yuv420_paste_ragged(const float* img, const float* matte, const int64_t* table, const int64_t* table_host, const int32_t* windows,
+                        const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host, int M, int F, int S,
+                        float feather, int matrix, int full_range, void* stream) {
+  Nv12Coef k;
+  if (!img || !table || !table_host || !windows || !frame_of || !frame_of_host || M < 0 || F <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
+  if (!feather_ok(feather) || !nv12_coef(matrix, full_range, L::bits, k)) return EMO_ERR_BAD_ARG;
+  int smax;
+  const int rc = ragged_args(table_host, F, (int)sizeof(typename L::sample), L::planar ? Rows::Planar : Rows::Interleaved, windows_host,
+                             frame_of_host, M, S, true, smax);
+  if (rc != EMO_OK || M == 0) return rc;
+  return launch_paste_yuv420<Frames::Table, L>(img, matte, windows, frame_of, YuvFrame{nullptr, nullptr, nullptr, 0, 0}, 0, M, F, S, 0, 0, smax,
+                                               feather, k, table, stream);
+}
 
 }  // namespace
 
@@ -1144,12 +1336,8 @@ extern "C" int emo_resize2d_windows_f32(const float* x, int64_t plane_stride, in
 extern "C" int emo_nv12_windows_f32(const uint8_t* y, const uint8_t* uv, int64_t pitch, int64_t frame_stride, int Hf, int Wf,
                                     const int32_t* windows, const int32_t* windows_host, float* out, int N, int Ho, int Wo,
                                     int matrix, int full_range, void* stream) {
-  Nv12Coef k;
-  int smax;
-  if (!nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || !out || N <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
-  if (!nv12_coef(matrix, full_range, k) || (windows_host && !windows)) return EMO_ERR_BAD_ARG;
-  if (host_windows(windows_host, N, 0, false, Hf, Wf, nullptr, nullptr, smax) != EMO_OK) return EMO_ERR_BAD_ARG;
-  return launch_nv12_crop<Frames::OnePerRow>(y, uv, pitch, frame_stride, Hf, Wf, windows, nullptr, out, N, N, Ho, Wo, k, nullptr, stream);
+  return yuv420_crop<Nv12>(y, uv, nullptr, pitch, pitch, frame_stride, Hf, Wf, windows, windows_host, nullptr, nullptr, out, N, N, Ho, Wo,
+                           matrix, full_range, stream);
 }
 
 extern "C" int emo_paste_windows_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
@@ -1165,14 +1353,8 @@ extern "C" int emo_paste_windows_rgb8(const float* img, const float* matte, cons
 extern "C" int emo_paste_windows_nv12(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
                                       uint8_t* y, uint8_t* uv, int64_t pitch, int64_t frame_stride, int N, int S, int Hf, int Wf,
                                       float feather, int matrix, int full_range, void* stream) {
-  Nv12Coef k;
-  if (!img || !windows || !nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || N <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
-  if (!feather_ok(feather) || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
-  int smax;
-  const int rc = host_windows(windows_host, N, S, true, Hf, Wf, nullptr, nullptr, smax);
-  if (rc != EMO_OK) return rc;
-  return launch_paste_nv12<Frames::OnePerRow>(img, matte, windows, nullptr, y, uv, pitch, frame_stride, N, N, S, Hf, Wf, smax, feather, k,
-                                              nullptr, stream);
+  return yuv420_paste<Nv12>(img, matte, windows, windows_host, nullptr, nullptr, y, uv, nullptr, pitch, pitch, frame_stride, N, N, S, Hf, Wf,
+                            feather, matrix, full_range, stream);
 }
 
 // ---- ABI 18: several faces per frame, face m in frame frame_of[m]
@@ -1191,14 +1373,9 @@ extern "C" int emo_nv12_faces_f32(const uint8_t* y, const uint8_t* uv, int64_t p
                                   const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
                                   const int32_t* frame_of_host, float* out, int M, int F, int Ho, int Wo, int matrix, int full_range,
                                   void* stream) {
-  Nv12Coef k;
-  int smax;
-  if (!nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || !out || !windows || !frame_of || M < 0 || F <= 0 || Ho <= 0 || Wo <= 0)
-    return EMO_ERR_BAD_ARG;
-  if (!nv12_coef(matrix, full_range, k) || (frame_of_host && !frame_of_ok(frame_of_host, M, F))) return EMO_ERR_BAD_ARG;
-  if (host_windows(windows_host, M, 0, false, Hf, Wf, nullptr, nullptr, smax) != EMO_OK) return EMO_ERR_BAD_ARG;
-  if (M == 0) return EMO_OK;
-  return launch_nv12_crop<Frames::Shared>(y, uv, pitch, frame_stride, Hf, Wf, windows, frame_of, out, M, F, Ho, Wo, k, nullptr, stream);
+  if (!frame_of) return EMO_ERR_BAD_ARG;
+  return yuv420_crop<Nv12>(y, uv, nullptr, pitch, pitch, frame_stride, Hf, Wf, windows, windows_host, frame_of, frame_of_host, out, M, F, Ho,
+                           Wo, matrix, full_range, stream);
 }
 
 extern "C" int emo_paste_faces_rgb8(const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
@@ -1216,15 +1393,9 @@ extern "C" int emo_paste_faces_nv12(const float* img, const float* matte, const 
                                     const int32_t* frame_of, const int32_t* frame_of_host, uint8_t* y, uint8_t* uv, int64_t pitch,
                                     int64_t frame_stride, int M, int F, int S, int Hf, int Wf, float feather, int matrix,
                                     int full_range, void* stream) {
-  Nv12Coef k;
-  if (!img || !windows || !frame_of || !frame_of_host || !nv12_planes_ok(y, uv, pitch, frame_stride, Hf, Wf) || M < 0 || F <= 0 || S <= 0)
-    return EMO_ERR_BAD_ARG;
-  if (!feather_ok(feather) || !nv12_coef(matrix, full_range, k) || !frame_of_ok(frame_of_host, M, F)) return EMO_ERR_BAD_ARG;
-  int smax;
-  const int rc = host_windows(windows_host, M, S, true, Hf, Wf, nullptr, nullptr, smax);
-  if (rc != EMO_OK || M == 0) return rc;
-  return launch_paste_nv12<Frames::Shared>(img, matte, windows, frame_of, y, uv, pitch, frame_stride, M, F, S, Hf, Wf, smax, feather, k,
-                                           nullptr, stream);
+  if (!frame_of) return EMO_ERR_BAD_ARG;
+  return yuv420_paste<Nv12>(img, matte, windows, windows_host, frame_of, frame_of_host, y, uv, nullptr, pitch, pitch, frame_stride, M, F, S,
+                            Hf, Wf, feather, matrix, full_range, stream);
 }
 
 // ---- ABI 19: the frames of a batch in different sizes, addressed through a frame table
@@ -1233,7 +1404,7 @@ extern "C" int emo_rgb8_faces_ragged_f32(const int64_t* table, const int64_t* ta
                                          float* out, int M, int F, int Ho, int Wo, void* stream) {
   if (!table || !table_host || !windows || !frame_of || !frame_of_host || !out || M < 0 || F <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
   int smax;
-  const int rc = ragged_args(table_host, F, 3, false, windows_host, frame_of_host, M, 0, false, smax);
+  const int rc = ragged_args(table_host, F, 3, Rows::Rgb8, windows_host, frame_of_host, M, 0, false, smax);
   if (rc != EMO_OK || M == 0) return rc;
   if (M > 65535) return EMO_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(rgb8_faces_ragged_kernel, ragged_grid((long)Ho * Wo, M), dim3(256), 0, (hipStream_t)stream,
@@ -1244,14 +1415,8 @@ extern "C" int emo_rgb8_faces_ragged_f32(const int64_t* table, const int64_t* ta
 extern "C" int emo_nv12_faces_ragged_f32(const int64_t* table, const int64_t* table_host, const int32_t* windows,
                                          const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host,
                                          float* out, int M, int F, int Ho, int Wo, int matrix, int full_range, void* stream) {
-  Nv12Coef k;
-  if (!table || !table_host || !windows || !frame_of || !frame_of_host || !out || M < 0 || F <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
-  if (!nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
-  int smax;
-  const int rc = ragged_args(table_host, F, 1, true, windows_host, frame_of_host, M, 0, false, smax);
-  if (rc != EMO_OK || M == 0) return rc;
-  if (M > 65535) return EMO_ERR_UNSUPPORTED;
-  return launch_nv12_crop<Frames::Table>(nullptr, nullptr, 0, 0, 0, 0, windows, frame_of, out, M, F, Ho, Wo, k, table, stream);
+  return yuv420_crop_ragged<Nv12>(table, table_host, windows, windows_host, frame_of, frame_of_host, out, M, F, Ho, Wo, matrix, full_range,
+                                  stream);
 }
 
 extern "C" int emo_paste_faces_ragged_rgb8(const float* img, const float* matte, const int64_t* table, const int64_t* table_host,
@@ -1260,7 +1425,7 @@ extern "C" int emo_paste_faces_ragged_rgb8(const float* img, const float* matte,
   if (!img || !table || !table_host || !windows || !frame_of || !frame_of_host || M < 0 || F <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
   if (!feather_ok(feather)) return EMO_ERR_BAD_ARG;
   int smax;
-  const int rc = ragged_args(table_host, F, 3, false, windows_host, frame_of_host, M, S, true, smax);
+  const int rc = ragged_args(table_host, F, 3, Rows::Rgb8, windows_host, frame_of_host, M, S, true, smax);
   if (rc != EMO_OK || M == 0) return rc;
   return launch_paste_rgb8<Frames::Table>(img, matte, windows, frame_of, nullptr, M, F, S, 0, 0, smax, feather, table, stream);
 }
@@ -1269,12 +1434,46 @@ extern "C" int emo_paste_faces_ragged_nv12(const float* img, const float* matte,
                                            const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
                                            const int32_t* frame_of_host, int M, int F, int S, float feather, int matrix,
                                            int full_range, void* stream) {
-  Nv12Coef k;
-  if (!img || !table || !table_host || !windows || !frame_of || !frame_of_host || M < 0 || F <= 0 || S <= 0) return EMO_ERR_BAD_ARG;
-  if (!feather_ok(feather) || !nv12_coef(matrix, full_range, k)) return EMO_ERR_BAD_ARG;
-  int smax;
-  const int rc = ragged_args(table_host, F, 1, true, windows_host, frame_of_host, M, S, true, smax);
-  if (rc != EMO_OK || M == 0) return rc;
-  return launch_paste_nv12<Frames::Table>(img, matte, windows, frame_of, nullptr, nullptr, 0, 0, M, F, S, 0, 0, smax, feather, k, table,
-                                          stream);
+  return yuv420_paste_ragged<Nv12>(img, matte, table, table_host, windows, windows_host, frame_of, frame_of_host, M, F, S, feather, matrix,
+                                   full_range, stream);
+}
+
+// ---- ABI 22: the same five operations on any of the four sample layouts (0 nv12, 1 yuv420p, 2 p010, 3 yuv420p10)
+extern "C" int emo_yuv420_crop_f32(int layout, const void* y, const void* u, const void* v, int64_t pitch_y, int64_t pitch_c,
+                                   int64_t frame_stride, int Hf, int Wf, const int32_t* windows, const int32_t* windows_host,
+                                   const int32_t* frame_of, const int32_t* frame_of_host, float* out, int M, int F, int Ho, int Wo,
+                                   int matrix, int full_range, void* stream) {
+  return with_layout(layout, [&](auto l) {
+    return yuv420_crop<decltype(l)>(y, u, v, pitch_y, pitch_c, frame_stride, Hf, Wf, windows, windows_host, frame_of, frame_of_host, out, M,
+                                    F, Ho, Wo, matrix, full_range, stream);
+  });
+}
+
+extern "C" int emo_paste_yuv420(int layout, const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                                const int32_t* frame_of, const int32_t* frame_of_host, void* y, void* u, void* v, int64_t pitch_y,
+                                int64_t pitch_c, int64_t frame_stride, int M, int F, int S, int Hf, int Wf, float feather, int matrix,
+                                int full_range, void* stream) {
+  return with_layout(layout, [&](auto l) {
+    return yuv420_paste<decltype(l)>(img, matte, windows, windows_host, frame_of, frame_of_host, y, u, v, pitch_y, pitch_c, frame_stride, M,
+                                     F, S, Hf, Wf, feather, matrix, full_range, stream);
+  });
+}
+
+extern "C" int emo_yuv420_crop_ragged_f32(int layout, const int64_t* table, const int64_t* table_host, const int32_t* windows,
+                                          const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host,
+                                          float* out, int M, int F, int Ho, int Wo, int matrix, int full_range, void* stream) {
+  return with_layout(layout, [&](auto l) {
+    return yuv420_crop_ragged<decltype(l)>(table, table_host, windows, windows_host, frame_of, frame_of_host, out, M, F, Ho, Wo, matrix,
+                                           full_range, stream);
+  });
+}
+
+extern "C" int emo_paste_ragged_yuv420(int layout, const float* img, const float* matte, const int64_t* table, const int64_t* table_host,
+                                       const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
+                                       const int32_t* frame_of_host, int M, int F, int S, float feather, int matrix, int full_range,
+                                       void* stream) {
+  return with_layout(layout, [&](auto l) {
+    return yuv420_paste_ragged<decltype(l)>(img, matte, table, table_host, windows, windows_host, frame_of, frame_of_host, M, F, S, feather,
+                                            matrix, full_range, stream);
+  });
 }

@@ -53,19 +53,27 @@ def face_spans(counts, lo, hi, batch_size):
     return spans
 
 
-FORMATS = ("rgb8", "nv12")
+FORMATS = ("rgb8", "nv12", "yuv420p", "p010", "yuv420p10")     # packed RGB bytes, or YUV 4:2:0 under ffmpeg's pixel-format names
+YUV420 = FORMATS[1:]
 
 
 def check_format(frame_format, colorspace="bt709", what="frame_format"):
     if frame_format not in FORMATS:
-        raise ValueError(f"{what}={frame_format!r}: 'rgb8' or 'nv12'")
+        raise ValueError(f"{what}={frame_format!r}: one of {', '.join(repr(f) for f in FORMATS)}")
     if colorspace not in ops.NV12_MATRICES:
         raise ValueError(f"colorspace {colorspace!r}: 'bt709' or 'bt601'")
 
 
 def check_frames(chunk, frame_format):
-    """the shape and dtype of one chunk of frames: uint8 [N,H,W,3], or NV12 uint8 [N, 3H/2, W] with H and W even"""
+    """the shape and dtype of one chunk of frames: uint8 [N,H,W,3], or NV12 uint8 [N, 3H/2, W] with H and W even; 'yuv420p',
+    'p010', 'yuv420p10': [N, 3H/2, W] of the format's dtype with the strides ops.yuv420_geometry asks for"""
     check_format(frame_format)
+    if frame_format not in ("rgb8", "nv12"):
+        if not isinstance(chunk, torch.Tensor) or chunk.dim() != 3:
+            raise ValueError(f"{frame_format} frames must be {str(ops.yuv420_dtype(frame_format)).replace('torch.', '')} [N, 3H/2, W] "
+                             f"with H and W even, got {tuple(getattr(chunk, 'shape', ()))}")
+        ops.yuv420_geometry(chunk, frame_format, "frames")
+        return
     if frame_format == "rgb8":
         if chunk.dtype != torch.uint8 or chunk.dim() != 4 or chunk.shape[-1] != 3:
             raise ValueError("frames must be uint8 [N,H,W,3]")
@@ -84,9 +92,12 @@ def crops_of(u8, size, windows=None, frame_format="rgb8", colorspace="bt709", fu
     tensor, ops.resize2d_windows), or without windows the whole frame, resized only where its size differs.
     frame_format 'nv12': NV12 frames [b, 3H/2, W] -> the same crops of the converted frames in ONE launch (ops.nv12_windows:
     only the bytes under the windows are read, no full-frame fp32 picture is written).
+    frame_format 'yuv420p' | 'p010' | 'yuv420p10': the same on the other YUV 4:2:0 layouts (ops.yuv420_windows).
     frame_of: several faces per frame -- windows[m] is cut out of frame frame_of[m], still one launch, [len(windows),3,size,size]."""
     if frame_format == "nv12":
         return ops.nv12_windows(u8, (size, size), windows, colorspace, full_range, frame_of=frame_of)
+    if frame_format != "rgb8":                                   # the other YUV 4:2:0 layouts: the same launch on their samples
+        return ops.yuv420_windows(u8, frame_format, (size, size), windows, colorspace, full_range, frame_of=frame_of)
     x = ops.unpack_rgb8(u8)
     if windows is not None:
         return ops.resize2d_windows(x, (size, size), windows, "bicubic", clamp01=True, frame_of=frame_of)
@@ -101,6 +112,8 @@ def paste_into(full, img, wins, feather, matte, frame_format="rgb8", colorspace=
     feathered edge and the matte; frame_of as in crops_of.  Returns full."""
     if frame_format == "nv12":
         return ops.paste_windows_nv12(full, img, wins, feather, matte, colorspace, full_range, frame_of=frame_of)
+    if frame_format != "rgb8":
+        return ops.paste_windows_yuv420(full, frame_format, img, wins, feather, matte, colorspace, full_range, frame_of=frame_of)
     return ops.paste_windows(full, img, wins, feather, matte, frame_of=frame_of)
 
 
@@ -133,7 +146,8 @@ def uploaded(chunk, spans, device, upload_stream):
 
 
 class HostRing:
-    """Finished uint8 batches go D2H into `ring` pinned buffers on a copy stream; a batch is handed out once ITS copy event has
+    """Finished batches (uint8; uint16 for the 10-bit formats: a slot has its batch's dtype) go D2H into `ring` pinned buffers
+    on a copy stream; a batch is handed out once ITS copy event has
     completed, i.e. the host only ever waits for a batch that is `ring - 1` batches behind the GPU.  What is handed out is a
     view of a ring slot, valid only until the next push()."""
 
@@ -150,12 +164,12 @@ class HostRing:
 
     def push(self, b0, out):
         """queue the copy of batch `out` (first frame b0) behind the compute stream; yields the batches now due"""
-        if self.slots and self.slots[0].shape[1:] != out.shape[1:]:          # full frames of another size: a new ring
+        if self.slots and (self.slots[0].shape[1:] != out.shape[1:] or self.slots[0].dtype != out.dtype):   # other frames: a new ring
             yield from self.drain()
             self.slots.clear()
             self.k = 0
         if len(self.slots) < self.ring:
-            self.slots.append(torch.empty((self.batch_size,) + tuple(out.shape[1:]), dtype=torch.uint8, pin_memory=True))
+            self.slots.append(torch.empty((self.batch_size,) + tuple(out.shape[1:]), dtype=out.dtype, pin_memory=True))
         slot = self.k % self.ring
         self.k += 1
         self.stream.wait_stream(torch.cuda.current_stream())
@@ -179,30 +193,32 @@ def interleave(lengths):
 
 
 def check_frame(frame, frame_format):
-    """one frame of a mixed batch: uint8 [H,W,3], or NV12 uint8 [3H/2, W] with H and W even"""
+    """one frame of a mixed batch: uint8 [H,W,3], or YUV 4:2:0 [3H/2, W] of the format's dtype with H and W even"""
     check_frames(frame[None], frame_format)
 
 
-def arena_layout(shapes):
-    """byte offsets of the frames of a batch in one byte buffer, each at a multiple of ARENA_ALIGN -> (offsets, total bytes)"""
+def arena_layout(shapes, itemsize=1):
+    """byte offsets of the frames of a batch (samples of `itemsize` bytes) in one byte buffer, each at a multiple of
+    ARENA_ALIGN -> (offsets, total bytes)"""
     offsets, total = [], 0
     for shape in shapes:
         offsets.append(total)
         n = 1
         for d in shape:
             n *= d
-        total += -(-n // ARENA_ALIGN) * ARENA_ALIGN
+        total += -(-n * itemsize // ARENA_ALIGN) * ARENA_ALIGN
     return offsets, total
 
 
-def arena_views(buf, shapes, offsets):
-    """the frames of a batch as views of its byte buffer (device arena or pinned ring slot)"""
-    out = []
+def arena_views(buf, shapes, offsets, dtype=torch.uint8):
+    """the frames of a batch as views of its byte buffer (device arena or pinned ring slot): the bytes viewed as `dtype`, not
+    converted"""
+    out, itemsize = [], torch.empty(0, dtype=dtype).element_size()
     for shape, off in zip(shapes, offsets):
-        n = 1
+        n = itemsize
         for d in shape:
             n *= d
-        out.append(buf[off:off + n].view(tuple(shape)))
+        out.append(buf[off:off + n].view(dtype).view(tuple(shape)))
     return out
 
 
@@ -226,12 +242,13 @@ def uploaded_mixed(batches, device, upload_stream, copy_all):
         if batch is not None:
             inside = [copy_all or not f.is_cuda for f in batch]
             shapes = [tuple(f.shape) for f, a in zip(batch, inside) if a]
-            offsets, total = arena_layout(shapes)
+            dtype = batch[0].dtype if batch else torch.uint8
+            offsets, total = arena_layout(shapes, batch[0].element_size() if batch else 1)
             arena, ev, views = None, None, []
             if total:
                 with torch.cuda.stream(upload_stream):
                     arena = torch.empty(total, dtype=torch.uint8, device=device)
-                    views = arena_views(arena, shapes, offsets)
+                    views = arena_views(arena, shapes, offsets, dtype)
                     for f, v in zip([f for f, a in zip(batch, inside) if a], views):
                         if not f.is_cuda:
                             v.copy_(f, non_blocking=True)

@@ -85,6 +85,11 @@ SIGNATURES = {
     "emo_nv12_faces_ragged_f32": [_c_void] * 7 + [_c_int] * 6 + [_c_void],
     "emo_paste_faces_ragged_rgb8": [_c_void] * 8 + [_c_int] * 3 + [_c_float, _c_void],
     "emo_paste_faces_ragged_nv12": [_c_void] * 8 + [_c_int] * 3 + [_c_float, _c_int, _c_int, _c_void],
+    "emo_yuv420_crop_f32": [_c_int] + [_c_void] * 3 + [_c_i64] * 3 + [_c_int, _c_int] + [_c_void] * 5 + [_c_int] * 6 + [_c_void],
+    "emo_pack_yuv420": [_c_int] + [_c_void] * 4 + [_c_i64] * 3 + [_c_int] * 5 + [_c_void],
+    "emo_paste_yuv420": [_c_int] + [_c_void] * 9 + [_c_i64] * 3 + [_c_int] * 5 + [_c_float, _c_int, _c_int, _c_void],
+    "emo_yuv420_crop_ragged_f32": [_c_int] + [_c_void] * 7 + [_c_int] * 6 + [_c_void],
+    "emo_paste_ragged_yuv420": [_c_int] + [_c_void] * 8 + [_c_int] * 3 + [_c_float, _c_int, _c_int, _c_void],
 }
 _RESTYPES = {"emo_build_info": ctypes.c_char_p, "emo_groupnorm_workspace_bytes": _c_i64}
 

@@ -438,11 +438,12 @@ class InferenceWrapper:
         """enrol_identities on the host, before anything is launched -> what the device part needs beside the arguments"""
         S = self.cfg["image_size"]
         frames_mod.check_format(frame_format, colorspace)
-        video = isinstance(sources, torch.Tensor) and sources.dtype == torch.uint8
-        if frame_format == "nv12":
+        video = isinstance(sources, torch.Tensor) and sources.dtype in (torch.uint8, ops.yuv420_dtype(frame_format))
+        if frame_format != "rgb8":
             if not video:
-                raise ValueError("frame_format='nv12' describes uint8 frames [K, 3H/2, W]")
-            frames_mod.check_frames(sources, "nv12")
+                raise ValueError(f"frame_format={frame_format!r} describes {str(ops.yuv420_dtype(frame_format)).replace('torch.', '')} "
+                                 f"frames [K, 3H/2, W]")
+            frames_mod.check_frames(sources, frame_format)
         if isinstance(sources, torch.Tensor):
             if video and frame_format == "rgb8" and (sources.dim() != 4 or sources.shape[-1] != 3):
                 raise ValueError(f"uint8 sources must be frames [K,H,W,3], got {tuple(sources.shape)}")
@@ -1060,13 +1061,13 @@ class InferenceWrapper:
         smooth_pose then work on the edited thetas, and each rank renders its slice."""
         N = target_pose_embeds.shape[0]
         frames_mod.check_format(out_format, colorspace, "out_format")
-        if out_format == "nv12" and not as_uint8:
+        if out_format != "rgb8" and not as_uint8:
             raise ValueError("as_uint8=False yields the fp32 image: it has no out_format")
         masks_of, ids = self._preflight(N, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
-        if out_format == "nv12":
-            self._nv12_size(masks_of)
+        if out_format != "rgb8":
+            self._nv12_size(masks_of, out_format)
         ex, hp = self._control_plans(expression, head_pose, N, ids, 'animate', target_theta)
-        out_kind = "f32" if not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
+        out_kind = "f32" if not as_uint8 else ("u8" if out_format == "rgb8" else out_format)
         lo, hi = parallel.shard_range(N, self.rank, self.world)
         ids_dev = None if ids is None else ids[lo:hi].to(self.device)
         smoothed = edited = None
@@ -1109,21 +1110,22 @@ class InferenceWrapper:
             self._source_theta('mix=True' if mix else 'target_theta=False')
         return masks_of, None
 
-    def _nv12_size(self, masks_of):
-        """NV12 frames have an even side: the size of the image that would be packed, checked before anything is launched"""
+    def _nv12_size(self, masks_of, out_format="nv12"):
+        """YUV 4:2:0 frames have an even side: the size of the image that would be packed, checked before anything is launched"""
         name, S_out = ("image_size", self.cfg["image_size"]) if masks_of is None else ("output_size_s2", self._stage2.cfg["output_size_s2"])
         if S_out % 2:
-            raise ValueError(f"NV12 output needs an even {name}, got {S_out}")
+            raise ValueError(f"{'NV12' if out_format == 'nv12' else out_format} output needs an even {name}, got {S_out}")
 
     def _render(self, pose, theta, ident, target_theta, masks_of, out, nv12=("bt709", False)):
         """The tail of a batch: the theta each frame is rendered with, the driver pass of the current identity or of the bank
         slots `ident`, stage 2 where masks_of is given -> uint8 [b,S,S,3] (out 'u8'), the fp32 image [b,3,S,S] ('f32') or
-        that image as NV12 uint8 [b,3S/2,S] ('nv12': ops.pack_nv12 with nv12 = (colorspace, full_range))"""
+        that image as NV12 uint8 [b,3S/2,S] ('nv12': ops.pack_nv12 with nv12 = (colorspace, full_range)) or in another YUV
+        4:2:0 layout ('yuv420p', 'p010', 'yuv420p10': ops.pack_yuv420, [b,3S/2,S] of the format's dtype)"""
         theta = self._render_theta(theta, ident, target_theta)
         img = self._drive(pose, theta) if ident is None else self._drive_bank(pose, theta, ident)
-        if out == "nv12":
+        if out in frames_mod.YUV420:
             img = img if masks_of is None else self._refine(img, masks_of, "f32")
-            return ops.pack_nv12(img, *nv12)
+            return ops.pack_nv12(img, *nv12) if out == "nv12" else ops.pack_yuv420(img, out, *nv12)
         if masks_of is not None:
             return self._refine(img, masks_of, out)
         return ops.pack_rgb8(img) if out == "u8" else img
@@ -1174,7 +1176,7 @@ class InferenceWrapper:
         img = rendered.to(self.device).float().contiguous()
         m = None if fn is None else fn(img).to(self.device).float().contiguous()
         full = frames_u8.to(self.device, copy=True)
-        return frames_mod.paste_into(full if frame_format == "nv12" else full.contiguous(), img, wins, feather, m, frame_format,
+        return frames_mod.paste_into(full if frame_format != "rgb8" else full.contiguous(), img, wins, feather, m, frame_format,
                                      colorspace, full_range, frame_of)
 
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
@@ -1348,9 +1350,9 @@ class InferenceWrapper:
             if any(4 * w[2] < S_out for w in wins):
                 raise ValueError(f"a paste window is smaller than a quarter of the {S_out}-pixel image: downscaling "
                                  f"stops at image_size / 4")
-        if out_format == "nv12" and as_uint8 and not paste_back:
-            self._nv12_size(masks_of)
-        out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else "nv12")
+        if out_format != "rgb8" and as_uint8 and not paste_back:
+            self._nv12_size(masks_of, out_format)
+        out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else out_format)
         ex, hp = self._control_plans(expression, head_pose, n_rows, ids, where, target_theta, faces)
         host_ring = None if not to_host else (frames_mod.ArenaRing(self.device, ring) if arena and paste_back
                                               else frames_mod.HostRing(self.device, ring, batch_size))
@@ -1633,7 +1635,8 @@ class InferenceWrapper:
             or the rows of the crops split by frame"""
             if paste_back:
                 shapes = [shape for _, _, shape in meta]
-                views = frames_mod.arena_views(buf, shapes, frames_mod.arena_layout(shapes)[0])
+                dtype = ops.yuv420_dtype(frame_format)
+                views = frames_mod.arena_views(buf, shapes, frames_mod.arena_layout(shapes, 2 if dtype == torch.uint16 else 1)[0], dtype)
                 return [(s, t, v) for (s, t, _), v in zip(meta, views)]
             out, m = [], 0
             for s, t, c in meta:

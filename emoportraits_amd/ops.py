@@ -896,14 +896,152 @@ def paste_windows_nv12(nv12, img, windows, feather=0.0, matte=None, colorspace="
     return nv12
 
 
+# ---- planar and 10-bit YUV 4:2:0 frames (ABI 22): the NV12 ops above on the other sample layouts ------------------------------
+YUV420_LAYOUTS = {"nv12": 0, "yuv420p": 1, "p010": 2, "yuv420p10": 3}           # frame_format -> the C ABI's layout id
+
+
+def yuv420_dtype(frame_format):
+    """the dtype of a frame tensor [N, 3H/2, W] of the format: bytes, or 16-bit little-endian words for the 10-bit formats"""
+    return torch.uint16 if frame_format in ("p010", "yuv420p10") else torch.uint8
+
+
+def yuv420_planar(frame_format):
+    return frame_format in ("yuv420p", "yuv420p10")
+
+
+def yuv420_geometry(t, frame_format, what):
+    """One frame's [3H/2, W] rows of a YUV 4:2:0 tensor (its last two dimensions), checked (ValueError) -> (H, W, pitch in
+    bytes): the format's dtype, H and W even, stride 1 along a row; interleaved chroma (nv12, p010): a row pitch >= W samples (a
+    [..., :W] view of a padded surface is taken as it is); planar chroma (yuv420p, yuv420p10): dense rows, the U and V planes of
+    H/2 x W/2 samples each straight after Y -- ffmpeg's rawvideo layout; with H/2 odd the V plane begins mid-row of the tensor"""
+    if frame_format not in YUV420_LAYOUTS:
+        raise ValueError(f"frame_format={frame_format!r}: one of {', '.join(YUV420_LAYOUTS)}")
+    dt = yuv420_dtype(frame_format)
+    name = str(dt).replace("torch.", "")
+    if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() < 2:
+        raise ValueError(f"{what}: {frame_format} frames are {name} [N, 3H/2, W]")
+    rows, W = t.shape[-2:]
+    if rows % 3 or W % 2 or rows == 0 or W == 0:
+        raise ValueError(f"{what}: {frame_format} frames {tuple(t.shape)}: expected {name} [N, 3H/2, W] with H and W even")
+    pitch = t.stride(-2)
+    if yuv420_planar(frame_format):
+        if t.stride(-1) != 1 or pitch != W:
+            raise ValueError(f"{what}: {frame_format} frames need dense rows (stride 1 along a row, a row stride of W): "
+                             f"the chroma planes lie straight after Y")
+    elif t.stride(-1) != 1 or pitch < W:
+        raise ValueError(f"{what}: {frame_format} frames need stride 1 along a row and a row pitch >= W")
+    return rows // 3 * 2, W, pitch * t.element_size()
+
+
+def _yuv420_planes(t, frame_format, what):
+    """[N, 3H/2, W] frames of the format -> (layout id, Y, U, V pointers, luma pitch, chroma pitch, frame stride -- in bytes --
+    N, H, W), as the ABI 22 entry points take them"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        raise ValueError(f"{what}: {frame_format} frames are [N, 3H/2, W]")
+    H, W, pitch = yuv420_geometry(t, frame_format, what)
+    N, B = t.shape[0], t.element_size()
+    fstride = t.stride(0) * B if N > 0 else 3 * H // 2 * pitch
+    if N > 1 and fstride < 3 * H // 2 * pitch:
+        raise ValueError(f"{what}: {frame_format} frames must not overlap")
+    base = t.data_ptr()
+    u = base + H * pitch
+    if yuv420_planar(frame_format):
+        pitch_c, v = pitch // 2, u + (H // 2) * (pitch // 2)
+    else:
+        pitch_c, v = pitch, None
+    return (YUV420_LAYOUTS[frame_format], ctypes.c_void_p(base), ctypes.c_void_p(u), None if v is None else ctypes.c_void_p(v), pitch,
+            pitch_c, fstride, N, H, W)
+
+
+def yuv420_windows(frames, frame_format, size=None, windows=None, colorspace="bt709", full_range=False, frame_of=None):
+    """nv12_windows on any of the four YUV 4:2:0 layouts (emo_yuv420_crop_f32, ONE launch): frames [N, 3H/2, W] of the format's
+    dtype on the device (yuv420_geometry has the forms) -> fp32 [N,3,Ho,Wo] in [0,1]; size, windows, colorspace, full_range and
+    frame_of as in nv12_windows.  10-bit codes: 'p010' the high ten bits of a word, 'yuv420p10' the low ten; the other six
+    bits are ignored.  include/emo_hip.h (ABI 22) has the definition."""
+    lib = hip.load()
+    layout, y, u, v, pitch_y, pitch_c, fstride, N, H, W = _yuv420_planes(frames, frame_format, "yuv420_windows")
+    matrix = _nv12_matrix(colorspace)
+    Ho, Wo = (H, W) if size is None else size
+    if frame_of is not None and windows is None:
+        raise ValueError("frame_of= needs windows=: one per face")
+    M = N if frame_of is None else len(frame_of)
+    out = torch.empty((M, 3, Ho, Wo), device=frames.device, dtype=torch.float32)
+    hip.require_cuda_f32(out)                                    # (the frames' device: GPU only, like every op)
+    win, host = (None, None) if windows is None else _windows_arg(windows, M, (W, H), frames.device, "crop")
+    fof, fof_host = (None, None) if frame_of is None else _frame_of_arg(frame_of, N, frames.device)
+    if M == 0:
+        return out
+    hip.check(lib.emo_yuv420_crop_f32(layout, y, u, v, pitch_y, pitch_c, fstride, H, W, hip.ptr(win), hip.ptr(host), hip.ptr(fof),
+                                      hip.ptr(fof_host), hip.ptr(out), M, N, Ho, Wo, matrix, int(bool(full_range)), hip.current_stream()),
+              "emo_yuv420_crop_f32")
+    return out
+
+
+def pack_yuv420(img, frame_format, colorspace="bt709", full_range=False, out=None):
+    """pack_nv12 into any of the four YUV 4:2:0 layouts (emo_pack_yuv420): [N,3,H,W] fp32 -> frames [N, 3H/2, W] of the format's
+    dtype, H and W even; a written sample holds its code and zeros in the format's unused bits.  out: frames to write into."""
+    lib = hip.load()
+    hip.require_cuda_f32(img)
+    N, C, H, W = img.shape
+    if C != 3:
+        raise ValueError("expected 3 channels")
+    if H % 2 or W % 2:
+        raise ValueError(f"{frame_format} needs an even height and width, got {H}x{W}")
+    if frame_format not in YUV420_LAYOUTS:
+        raise ValueError(f"frame_format={frame_format!r}: one of {', '.join(YUV420_LAYOUTS)}")
+    matrix = _nv12_matrix(colorspace)
+    if out is None:
+        out = torch.empty((N, 3 * H // 2, W), device=img.device, dtype=yuv420_dtype(frame_format))
+    layout, y, u, v, pitch_y, pitch_c, fstride, n, h, w = _yuv420_planes(out, frame_format, "pack_yuv420")
+    if (n, h, w) != (N, H, W) or out.device != img.device:
+        raise ValueError(f"out {tuple(out.shape)} does not hold {N} {frame_format} frames of {W}x{H} on the image's device")
+    if N == 0:
+        return out
+    hip.check(lib.emo_pack_yuv420(layout, hip.ptr(img), y, u, v, pitch_y, pitch_c, fstride, N, H, W, matrix, int(bool(full_range)),
+                                  hip.current_stream()), "emo_pack_yuv420")
+    return out
+
+
+def paste_windows_yuv420(frames, frame_format, img, windows, feather=0.0, matte=None, colorspace="bt709", full_range=False,
+                         frame_of=None):
+    """paste_windows_nv12 on any of the four YUV 4:2:0 layouts, IN PLACE and in one launch (emo_paste_yuv420); every argument as
+    there.  A sample outside the windows' luma rectangles and their covering chroma rectangles keeps all its bits; a sample
+    inside comes out as its code with zeros in the format's unused bits.  Returns frames."""
+    lib = hip.load()
+    hip.require_cuda_f32(img, matte)
+    if isinstance(frames, torch.Tensor) and frames.device != img.device:
+        raise RuntimeError("paste_windows_yuv420 expects the frames on the images' device")
+    layout, y, u, v, pitch_y, pitch_c, fstride, N, Hf, Wf = _yuv420_planes(frames, frame_format, "paste_windows_yuv420")
+    matrix = _nv12_matrix(colorspace)
+    F, N = N, (N if frame_of is None else len(frame_of))                     # F frames, N rows of img / matte / windows
+    S = _paste_args(img, matte, feather, N, f"frames {tuple(frames.shape)} and images {tuple(img.shape)}: expected [N,3Hf/2,Wf] and [N,3,S,S]")
+    win, host = _windows_arg(windows, N, (Wf, Hf), img.device, "paste", paste_S=S)
+    fof, fof_host = (None, None) if frame_of is None else _frame_of_arg(frame_of, F, img.device)
+    if N == 0:
+        return frames
+    hip.check(lib.emo_paste_yuv420(layout, hip.ptr(img), hip.ptr(matte), hip.ptr(win), hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host),
+                                   y, u, v, pitch_y, pitch_c, fstride, N, F, S, Hf, Wf, float(feather), matrix, int(bool(full_range)),
+                                   hip.current_stream()), "emo_paste_yuv420")
+    return frames
+
+
 def _mixed_rows(frames, frame_format, what):
     """frames: a list of tensors, one per frame, uint8 [H,W,3] (rgb8) or NV12 [3H/2,W], all on one device, stride 1 along a row
     (a row-pitch view is taken as it is) -> [(address, pitch in bytes, H, W)] of the CHECKED tensors"""
-    if frame_format not in ("rgb8", "nv12"):
-        raise ValueError(f"frame_format={frame_format!r}: 'rgb8' or 'nv12'")
+    if frame_format != "rgb8" and frame_format not in YUV420_LAYOUTS:
+        raise ValueError(f"frame_format={frame_format!r}: 'rgb8', {', '.join(repr(f) for f in YUV420_LAYOUTS)}")
     if not isinstance(frames, (list, tuple)) or not frames:
         raise ValueError(f"{what} takes a non-empty list of frame tensors, one per frame")
     rows = []
+    if frame_format not in ("rgb8", "nv12"):                                    # (ABI 22: pitches in bytes, planar rows dense)
+        for i, t in enumerate(frames):
+            if not isinstance(t, torch.Tensor) or t.device != frames[0].device:
+                raise RuntimeError(f"{what}: frame {i} must be a tensor on the device of frame 0")
+            if t.dim() != 2:
+                raise ValueError(f"{what}: frame {i} is {tuple(t.shape)}, expected {frame_format} [3H/2, W] with H and W even")
+            H, W, pitch = yuv420_geometry(t, frame_format, f"{what}: frame {i}")
+            rows.append((t.data_ptr(), pitch, H, W))
+        return rows
     for i, t in enumerate(frames):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device != frames[0].device:
             raise RuntimeError(f"{what}: frame {i} must be a uint8 tensor on the device of frame 0")
@@ -964,7 +1102,11 @@ def crop_faces_mixed(frames, size, windows, frame_of, frame_format="rgb8", color
     if M == 0:
         return out
     table = table_host.to(device, non_blocking=True)
-    if frame_format == "nv12":
+    if frame_format not in ("rgb8", "nv12"):
+        hip.check(lib.emo_yuv420_crop_ragged_f32(YUV420_LAYOUTS[frame_format], hip.ptr(table), hip.ptr(table_host), hip.ptr(win),
+                                                 hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host), hip.ptr(out), M, F, Ho, Wo, matrix,
+                                                 int(bool(full_range)), hip.current_stream()), "emo_yuv420_crop_ragged_f32")
+    elif frame_format == "nv12":
         hip.check(lib.emo_nv12_faces_ragged_f32(hip.ptr(table), hip.ptr(table_host), hip.ptr(win), hip.ptr(host), hip.ptr(fof),
                                                 hip.ptr(fof_host), hip.ptr(out), M, F, Ho, Wo, matrix, int(bool(full_range)),
                                                 hip.current_stream()), "emo_nv12_faces_ragged_f32")
@@ -999,7 +1141,12 @@ def paste_faces_mixed(frames, img, windows, frame_of, feather=0.0, matte=None, f
     if M == 0:
         return frames
     table = table_host.to(device, non_blocking=True)
-    if frame_format == "nv12":
+    if frame_format not in ("rgb8", "nv12"):
+        hip.check(lib.emo_paste_ragged_yuv420(YUV420_LAYOUTS[frame_format], hip.ptr(img), hip.ptr(matte), hip.ptr(table),
+                                              hip.ptr(table_host), hip.ptr(win), hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host), M, F,
+                                              S, float(feather), matrix, int(bool(full_range)), hip.current_stream()),
+                  "emo_paste_ragged_yuv420")
+    elif frame_format == "nv12":
         hip.check(lib.emo_paste_faces_ragged_nv12(hip.ptr(img), hip.ptr(matte), hip.ptr(table), hip.ptr(table_host), hip.ptr(win),
                                                   hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host), M, F, S, float(feather), matrix,
                                                   int(bool(full_range)), hip.current_stream()), "emo_paste_faces_ragged_nv12")

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 21
+#define EMO_ABI_VERSION 22
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -660,6 +660,58 @@ int emo_paste_faces_ragged_nv12(const float* img, const float* matte, const int6
                                 const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
                                 const int32_t* frame_of_host, int M, int F, int S, float feather, int matrix, int full_range,
                                 void* stream);
+
+/* ABI 22.  Planar and 10-bit YUV 4:2:0 frames: the NV12 operations of ABI 17 / 18 / 19 on four sample layouts of a frame of even
+ * height H and even width W.
+ *   layout 0  nv12       1-byte samples, chroma interleaved: H / 2 rows of W / 2 (U, V) pairs.            code = the byte
+ *   layout 1  yuv420p    1-byte samples, a U plane and a V plane of H / 2 x W / 2 samples each.           code = the byte
+ *   layout 2  p010       16-bit little-endian words, chroma interleaved (U, V) words.  code = word >> 6: the low 6 bits are
+ *                        ignored on read and written as 0
+ *   layout 3  yuv420p10  16-bit little-endian words, a U plane and a V plane.  code = word & 0x3FF: the high 6 bits are ignored
+ *                        on read and written as 0
+ * Every entry point takes the layout, the pointers of the first frame's Y, U and V planes (interleaved layouts: u is the chroma
+ * plane and v is ignored), the row pitch of the luma plane and the one both chroma planes share, and the stride from one frame
+ * to the next, which all planes share; pitches and the stride are in BYTES.
+ * The definitions D, E, C and P are ABI 17's, word for word, with "code" for "byte":
+ *   the chroma mid-point is 128 for 8-bit codes and 512 for 10-bit codes (where ABI 17 writes 128);
+ *   8-bit codes: oy, sy, sc as in ABI 17.  10-bit codes: limited range oy = 64, sy = 876, sc = 896; full range oy = 0,
+ *   sy = 1023, sc = 1023; every code is held to 0 ... 1023 (where ABI 17 writes 0 ... 255).
+ * Unchanged: the matrices; coefficients formed once in fp64 and rounded to fp32; fp32 arithmetic, each operation rounded on its
+ * own, in the order written; the chroma sample of luma pixel (y, x) is (y >> 1, x >> 1); the (1 - a) f + a r blends of P; every
+ * sample has one writer; no sample outside a window's luma rectangle and its covering chroma rectangle is read or written.  A
+ * sample that is written holds its code and zeros in the ignored bits; a sample that is not written keeps all its bits.
+ * The limited-range 10-bit constants are 4 x the 8-bit ones, so a 10-bit frame of codes 4 * byte decodes (D, C) bit for bit to
+ * what the 8-bit frame of those bytes does.
+ *
+ * emo_yuv420_crop_f32 (C): frame_of == NULL: row m is frame m, M >= 1 rows, F is not read, frame_of_host must be NULL and
+ *   windows == NULL is every frame whole -- emo_nv12_windows_f32's form.  Otherwise face m lies in frame frame_of[m] of F --
+ *   emo_nv12_faces_f32's form, with its windows, frame_of_host and M == 0 rules.
+ * emo_pack_yuv420 (E): img [N,3,H,W] fp32 -> N frames.  Pairs of adjacent samples of an interleaved plane or a luma row go out
+ *   as one store where the addresses, pitches and the stride are multiples of two samples.
+ * emo_paste_yuv420 (P), in place: frame_of == NULL is emo_paste_windows_nv12's form (frame_of_host must be NULL), otherwise
+ *   emo_paste_faces_nv12's, with its order and ownership rules.
+ * emo_yuv420_crop_ragged_f32, emo_paste_ragged_yuv420: ABI 19's frame table [F,4] = (address, pitch, H, W).  Interleaved
+ *   layouts: as NV12 there, the chroma plane at address + H * pitch with the same pitch.  Planar layouts: U at address +
+ *   H * pitch with the chroma pitch pitch / 2, V at U + (H / 2) * (pitch / 2) -- a frame [3H/2, W] of dense rows.
+ * Refusals, before anything is launched and with nothing written: everything ABI 17 / 18 / 19 refuses, with the same return
+ *   codes and precedence; EMO_ERR_BAD_ARG also for an unknown layout, a NULL v of a planar layout, a pitch shorter than a row IN
+ *   BYTES (luma: W samples; chroma: W samples interleaved, W / 2 planar), for 16-bit layouts an odd address, pitch or stride,
+ *   and for planar rows of a frame table a pitch that is not a multiple of two samples.
+ * The ten NV12 entry points of ABI 17 / 18 / 19 are layout 0 of these with pitch_y = pitch_c = pitch: the same floats and bytes. */
+int emo_yuv420_crop_f32(int layout, const void* y, const void* u, const void* v, int64_t pitch_y, int64_t pitch_c, int64_t frame_stride,
+                        int Hf, int Wf, const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of,
+                        const int32_t* frame_of_host, float* out, int M, int F, int Ho, int Wo, int matrix, int full_range, void* stream);
+int emo_pack_yuv420(int layout, const float* img, void* y, void* u, void* v, int64_t pitch_y, int64_t pitch_c, int64_t frame_stride, int N,
+                    int H, int W, int matrix, int full_range, void* stream);
+int emo_paste_yuv420(int layout, const float* img, const float* matte, const int32_t* windows, const int32_t* windows_host,
+                     const int32_t* frame_of, const int32_t* frame_of_host, void* y, void* u, void* v, int64_t pitch_y, int64_t pitch_c,
+                     int64_t frame_stride, int M, int F, int S, int Hf, int Wf, float feather, int matrix, int full_range, void* stream);
+int emo_yuv420_crop_ragged_f32(int layout, const int64_t* table, const int64_t* table_host, const int32_t* windows,
+                               const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host, float* out, int M,
+                               int F, int Ho, int Wo, int matrix, int full_range, void* stream);
+int emo_paste_ragged_yuv420(int layout, const float* img, const float* matte, const int64_t* table, const int64_t* table_host,
+                            const int32_t* windows, const int32_t* windows_host, const int32_t* frame_of, const int32_t* frame_of_host,
+                            int M, int F, int S, float feather, int matrix, int full_range, void* stream);
 
 #ifdef __cplusplus
 }

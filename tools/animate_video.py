@@ -13,7 +13,7 @@
         [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
         [--stage2-experiment <exp2> --stage2-checkpoint <file> [--cloth]       # refine every batch with the stage-2 model
          (--embedders module:factory | --refine-everywhere)]                   # (<project>/logs_s2/<exp2>), inside the same path
-        [--frame-format nv12 --frame-size WxH [--colorspace bt709|bt601] [--full-range]]   # raw NV12 video in and out:
+        [--frame-format nv12|yuv420p|p010|yuv420p10 --frame-size WxH [--colorspace bt709|bt601] [--full-range]]   # raw NV12 video in and out:
          --frames clip.nv12 (or .yuv) as `ffmpeg -pix_fmt nv12 -f rawvideo` writes it; --out a file, raw NV12 of the frames
          (with --paste-back) or of the crops, which e.g. `ffmpeg -f rawvideo -pix_fmt nv12 -s WxH -i <out>` reads back
 
@@ -52,13 +52,17 @@ def load_frames(path, chunk):
         yield torch.from_numpy(np.stack(imgs)).pin_memory()
 
 
-def load_nv12(path, width, height, chunk):
-    """yields pinned uint8 [n, 3H/2, W] chunks of a raw NV12 file (frame after frame: H rows of Y, H/2 rows of interleaved U, V)"""
-    per = width * height * 3 // 2
+def load_nv12(path, width, height, chunk, frame_format="nv12"):
+    """yields pinned uint8 [n, 3H/2, W] chunks of a raw NV12 file (frame after frame: H rows of Y, H/2 rows of interleaved U, V);
+    frame_format 'yuv420p': the same of a planar file (H rows of Y, the U plane, the V plane); 'p010' / 'yuv420p10': uint16
+    chunks of a file of 16-bit little-endian samples -- a frame is 3HW/2 samples of 1 or 2 bytes"""
+    dtype = np.dtype("<u2") if frame_format in ("p010", "yuv420p10") else np.dtype(np.uint8)
+    per = width * height * 3 // 2 * dtype.itemsize
     size = os.path.getsize(path)
     if size == 0 or size % per:
-        raise SystemExit(f"{path}: {size} bytes is not a whole number of {width}x{height} NV12 frames of {per} bytes")
-    arr = np.memmap(path, dtype=np.uint8, mode="r").reshape(-1, 3 * height // 2, width)
+        raise SystemExit(f"{path}: {size} bytes is not a whole number of {width}x{height} {frame_format.upper() if frame_format == 'nv12' else frame_format} "
+                         f"frames of {per} bytes")
+    arr = np.memmap(path, dtype=dtype, mode="r").reshape(-1, 3 * height // 2, width)
     for a in range(0, arr.shape[0], chunk):
         yield torch.from_numpy(np.array(arr[a:a + chunk])).pin_memory()          # (a copy: the map is read-only)
 
@@ -104,12 +108,13 @@ def main():
     ap.add_argument("--cloth", action="store_true", help="stage 2: no face mask (all ones), as infer_s2.py's cloth=True")
     ap.add_argument("--embedders", default=None, help="module:factory returning {'matting': fn, 'face_parsing': fn} for stage 2")
     ap.add_argument("--refine-everywhere", action="store_true", help="stage 2 with both masks all ones (no matting / parsing nets)")
-    ap.add_argument("--frame-format", default="rgb8", choices=["rgb8", "nv12"], help="nv12: --frames and --out are raw NV12 files")
+    ap.add_argument("--frame-format", default="rgb8", choices=["rgb8", "nv12", "yuv420p", "p010", "yuv420p10"],
+                    help="a YUV 4:2:0 format (ffmpeg's -pix_fmt names; p010 is p010le, yuv420p10 is yuv420p10le): --frames and --out are raw files")
     ap.add_argument("--frame-size", default=None, help="with --frame-format nv12: WxH of the frames in --frames")
     ap.add_argument("--colorspace", default="bt709", choices=["bt709", "bt601"])
     ap.add_argument("--full-range", action="store_true", help="NV12 in full range (Y 0 ... 255) instead of limited (16 ... 235)")
     a = ap.parse_args()
-    nv12 = a.frame_format == "nv12"
+    nv12 = a.frame_format != "rgb8"                                # (any of the raw YUV 4:2:0 formats)
     if nv12:
         try:
             width, height = (int(v) for v in (a.frame_size or "").lower().split("x"))
@@ -117,7 +122,7 @@ def main():
             ap.error("--frame-format nv12 needs --frame-size WxH")
         if width <= 0 or height <= 0 or width % 2 or height % 2:
             ap.error("--frame-size: NV12 frames have an even width and height")
-        if not a.frames.lower().endswith((".nv12", ".yuv")):
+        if not a.frames.lower().endswith((".nv12", ".yuv", ".p010")):
             ap.error("--frame-format nv12 reads a raw .nv12 / .yuv file")
     elif a.frame_size or a.full_range or a.colorspace != "bt709":
         ap.error("--frame-size / --colorspace / --full-range belong to --frame-format nv12")
@@ -185,9 +190,9 @@ def main():
     t0, n = time.perf_counter(), 0
     if nv12:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        frames = load_nv12(a.frames, width, height, 8 * a.batch)
+        frames = load_nv12(a.frames, width, height, 8 * a.batch, a.frame_format)
         sink = open(a.out, "wb")
-        fmt = dict(frame_format="nv12", colorspace=a.colorspace, full_range=a.full_range)
+        fmt = dict(frame_format=a.frame_format, colorspace=a.colorspace, full_range=a.full_range)
     else:
         os.makedirs(a.out, exist_ok=True)
         frames = load_frames(a.frames, 8 * a.batch)
