@@ -1176,6 +1176,7 @@ def mfma_stream(iters=2000, lds_reads=False, sink=None):
 # ---- embedder ResNets -----------------------------------------------------------------------
 def conv2d_generic(x, wt, cout, kh, kw, stride, pad, bias=None, scale=None, shift=None, relu_in=False, splits=None):
     """F.conv2d(relu?(x*scale+shift), w, bias, stride, pad); wt = pack.pack_generic(w) [Cin*kh*kw, CoutP].
+    relu_in belongs to the affine: without scale / shift the input is read as it is (include/emo_hip.h).
     splits: K split count (None = the library's launch heuristic)"""
     lib = hip.load()
     hip.require_cuda_f32(x)

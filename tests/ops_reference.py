@@ -1,7 +1,8 @@
 """fp64 references and error checkers for single launches of the non-convolution ops the passes make (a helper module, not a
 test file; the sibling of conv_reference.py): volume_to_channels_last, add, add_rows_indexed, avgpool, upsample_trilinear,
 groupnorm_affine (own pass / TileStats / RunSums), small_gemm, projector_finalize, mat4_inverse and grid_sample3d (delta= /
-theta=, with and without vol_index).
+theta=, with and without vol_index); and for the launches of the embedders (emoportraits_amd/embedders.py): conv2d_generic,
+maxpool2d, affine_add_relu, grid_sample2d (grid= / theta= with its warp), resize2d (bilinear, whole frame) and pose_theta.
 
 Every reference is plain torch in fp64, computed one sample at a time on whatever device the inputs live on; none calls a
 kernel of the project.  Every checker compares a launch's output with that reference sample by sample and returns a dict of
@@ -11,6 +12,9 @@ figures: 'frames' (the samples checked), 'frame_fig' (the worst figure of each, 
 The bounds are the operation's own arithmetic (u = 2^-24, the unit roundoff of fp32) or constants the suite already states
 (conv_reference.FP32_FRAME, STATS_TOL, SPLIT_MAX and the fp16 split's mean margin); each checker's docstring derives its own.
 """
+import os
+import sys
+
 import torch
 import torch.nn.functional as F
 
@@ -332,6 +336,42 @@ def check_mat4_inverse(out, m, frames=None):
     return dict(frames=fr, frame_fig=fig, unit="x 2^-23 max|inverse|", worst=fig[w], worst_frame=fr[w], failures=bad)
 
 
+# ---- launches held to a yardstick ------------------------------------------------------------------------------------------
+def _yardstick_row(got, ref, yard, n):
+    """frame n -> [max |err|, sum |err|, the yardstick's max |err|, its sum |err|, sum |ref|, elements] of one frame as one fp64 tensor"""
+    assert ref.dtype == torch.float64 and yard.dtype == torch.float32, (ref.dtype, yard.dtype)
+    if got.shape != ref.shape:
+        raise ValueError(f"frame {n}: output {tuple(got.shape)} vs reference {tuple(ref.shape)}")
+    e = torch.nan_to_num((_f64(got) - ref).abs(), nan=float("inf"))
+    ey = (_f64(yard.to(ref.device)) - ref).abs()
+    return torch.stack([e.max(), e.sum(), ey.max(), ey.sum(), ref.abs().sum(),
+                        torch.tensor(float(ref.numel()), dtype=torch.float64, device=ref.device)])
+
+
+def _yardstick_fig(rows, fr, what, yardstick="ATen fp32"):
+    """figures of a launch held to a yardstick's error against the same fp64 reference (rows = _yardstick_row per frame): over
+    the launch, max |err| <= SAMPLER_MAX x the yardstick's and mean |err| <= SAMPLER_MEAN x the yardstick's, each plus
+    SAMPLER_FLOOR x mean |ref|; 'yardstick' names what the ratios are taken to"""
+    t = torch.stack(rows).cpu()                       # one host synchronisation per launch
+    count = float(t[:, 5].sum())
+    max_err, mean_err = float(t[:, 0].max()), float(t[:, 1].sum()) / count
+    y_max, y_mean = float(t[:, 2].max()), float(t[:, 3].sum()) / count
+    scale = float(t[:, 4].sum()) / count
+    allow_max, allow_mean = SAMPLER_MAX * y_max + SAMPLER_FLOOR * scale, SAMPLER_MEAN * y_mean + SAMPLER_FLOOR * scale
+    frame_fig = (t[:, 0] / max(allow_max, 1e-300)).tolist()
+    w = max(range(len(fr)), key=lambda i: frame_fig[i])
+    bad = []
+    if not max_err <= allow_max:
+        bad.append(f"{what}: max err {max_err:.3e} (frame {fr[w]}) > {SAMPLER_MAX} x {yardstick}'s {y_max:.3e} + "
+                   f"{SAMPLER_FLOOR:g} x {scale:.3e}")
+    if not mean_err <= allow_mean:
+        bad.append(f"{what}: mean err {mean_err:.3e} > {SAMPLER_MEAN} x {yardstick}'s {y_mean:.3e} + {SAMPLER_FLOOR:g} x {scale:.3e}")
+    return dict(frames=fr, frame_fig=frame_fig, unit="x allowed max err", worst=frame_fig[w], worst_frame=fr[w], yardstick=yardstick,
+                max_err=max_err, mean_err=mean_err, yard_max_err=y_max, yard_mean_err=y_mean, scale=scale,
+                max_ratio=max_err / y_max if y_max > 0 else (0.0 if max_err == 0 else float("inf")),
+                mean_ratio=mean_err / y_mean if y_mean > 0 else (0.0 if mean_err == 0 else float("inf")), failures=bad)
+
+
 # ---- grid_sample3d -------------------------------------------------------------------------------------------------------
 def lattice(n, device):
     """torch.linspace(-1, 1, n) in fp32, computed on the CPU (the reference's identity lattice), on `device`"""
@@ -431,29 +471,288 @@ def check_grid_sample3d(out, vol, delta=None, theta=None, padding_mode="zeros", 
     fr = _frames(N, frames)
     rows = []
     for n, ref, yard in grid_sample3d_frames(vol, delta, theta, padding_mode, in_layout, vol_index, fr):
-        got = _f64(_ncdhw(out[n], out_layout))
-        if got.shape != ref.shape:
-            raise ValueError(f"frame {n}: output {tuple(got.shape)} vs reference {tuple(ref.shape)}")
-        e = torch.nan_to_num((got - ref).abs(), nan=float("inf"))
-        ey = (_f64(yard.to(ref.device)) - ref).abs()
-        rows.append(torch.stack([e.max(), e.sum(), ey.max(), ey.sum(), ref.abs().sum(),
-                                 torch.tensor(float(ref.numel()), dtype=torch.float64, device=ref.device)]))
-        del got, e, ey, ref, yard
-    t = torch.stack(rows).cpu()
-    count = float(t[:, 5].sum())
-    max_err, mean_err = float(t[:, 0].max()), float(t[:, 1].sum()) / count
-    y_max, y_mean = float(t[:, 2].max()), float(t[:, 3].sum()) / count
-    scale = float(t[:, 4].sum()) / count
-    allow_max, allow_mean = SAMPLER_MAX * y_max + SAMPLER_FLOOR * scale, SAMPLER_MEAN * y_mean + SAMPLER_FLOOR * scale
-    frame_fig = (t[:, 0] / max(allow_max, 1e-300)).tolist()
-    w = max(range(len(fr)), key=lambda i: frame_fig[i])
-    bad = []
-    if not max_err <= allow_max:
-        bad.append(f"grid_sample3d: max err {max_err:.3e} (frame {fr[w]}) > {SAMPLER_MAX} x ATen fp32's {y_max:.3e} + "
-                   f"{SAMPLER_FLOOR:g} x {scale:.3e}")
-    if not mean_err <= allow_mean:
-        bad.append(f"grid_sample3d: mean err {mean_err:.3e} > {SAMPLER_MEAN} x ATen fp32's {y_mean:.3e} + {SAMPLER_FLOOR:g} x {scale:.3e}")
-    return dict(frames=fr, frame_fig=frame_fig, unit="x allowed max err", worst=frame_fig[w], worst_frame=fr[w],
-                max_err=max_err, mean_err=mean_err, yard_max_err=y_max, yard_mean_err=y_mean, scale=scale,
-                max_ratio=max_err / y_max if y_max > 0 else (0.0 if max_err == 0 else float("inf")),
-                mean_ratio=mean_err / y_mean if y_mean > 0 else (0.0 if mean_err == 0 else float("inf")), failures=bad)
+        rows.append(_yardstick_row(_ncdhw(out[n], out_layout), ref, yard, n))
+        del ref, yard
+    return _yardstick_fig(rows, fr, "grid_sample3d")
+
+
+# ---- conv2d_generic ------------------------------------------------------------------------------------------------------
+GENERIC_KC = 32                     # the K chunk of conv2d_generic_kernel (csrc/conv_generic.hip, GKC)
+
+
+def unpack_generic(wt, cout, cin, kh, kw):
+    """the weight [Cout, Cin, kh, kw] back from the packed wt [K][CoutP] of pack.pack_generic: a transpose and a slice"""
+    if wt.dim() != 2 or wt.shape[0] != cin * kh * kw or wt.shape[1] < cout:
+        raise ValueError(f"packed weight {tuple(wt.shape)} does not hold a [{cout}, {cin}, {kh}, {kw}] weight")
+    return wt[:, :cout].t().reshape(cout, cin, kh, kw)
+
+
+def generic_splits_run(K, splits):
+    """the K split count emo_conv2d_generic_f32 really runs for a request: clamped to the chunk count, then without the empty
+    splits that rounding the chunks per split up leaves behind (144 chunks, 32 asked: 5 per split, 29 splits)"""
+    chunks = -(-int(K) // GENERIC_KC)
+    per = -(-chunks // min(max(int(splits), 1), chunks))
+    return -(-chunks // per)
+
+
+def conv2d_generic_frames(x, wt, cout, kh, kw, stride, pad, bias=None, scale=None, shift=None, relu_in=False, frames=None):
+    """yields (n, ref [Cout, Ho, Wo], A [Cout, Ho, Wo]) in fp64 per sample of ops.conv2d_generic: x' = relu?(x scale + shift)
+    (the ReLU belongs to the affine: include/emo_hip.h applies it 'when scale/shift are given'), F.unfold of x' with the stride
+    and the zero padding, a matmul with the unpacked weight, the bias; A = sum |w| |x'| + |bias| from the same unfold of |x'|"""
+    N, Cin, H, W = x.shape
+    w = _f64(unpack_generic(wt, cout, Cin, kh, kw)).reshape(cout, -1)
+    Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+    b = None if bias is None else _f64(bias).reshape(cout, 1)
+    if (scale is None) != (shift is None):
+        raise ValueError("scale and shift come together")
+    for n in _frames(N, frames):
+        v = _f64(x[n])
+        if scale is not None:
+            v = v * _f64(scale.reshape(N, Cin)[n]).view(Cin, 1, 1) + _f64(shift.reshape(N, Cin)[n]).view(Cin, 1, 1)
+            if relu_in:
+                v = v.clamp_min(0.0)
+        cols = F.unfold(v[None], (kh, kw), padding=pad, stride=stride)[0]             # [K, Ho Wo]
+        assert cols.dtype == torch.float64
+        ref, mag = w @ cols, w.abs() @ cols.abs()
+        if b is not None:
+            ref, mag = ref + b, mag + b.abs()
+        yield n, ref.reshape(cout, Ho, Wo), mag.reshape(cout, Ho, Wo)
+
+
+def conv2d_generic_fp64(x, wt, cout, kh, kw, stride, pad, bias=None, scale=None, shift=None, relu_in=False):
+    return torch.stack([r for _, r, _ in conv2d_generic_frames(x, wt, cout, kh, kw, stride, pad, bias, scale, shift, relu_in)])
+
+
+def check_conv2d_generic(out, x, wt, cout, kh, kw, stride, pad, bias=None, scale=None, shift=None, relu_in=False, splits=1,
+                         frames=None):
+    """Every output of the kernel is a sum of K = Cin kh kw products and a bias that passes n = K + splits + 2 roundings at
+    most: one for the folded affine (x' = fl(fma(x, scale, shift)) = x'(1 + d); ReLU and the zero padding are exact), the K-term
+    fp32 accumulation of the MFMA pipe in whatever order it takes the terms (at most one rounding per term on any path from a
+    product to the sum), splits - 1 additions of the fixed-order reduction, and the bias (two are room).  With
+    A = sum |w| |x'| + |bias| of the output's OWN terms, the classical bound of a rounded sum gives, per output,
+        |out - ref| <= gamma_n A + TINY,      gamma_n = n u / (1 - n u).
+    `splits` is the count asked of the launcher; the count that enters n is the one the launcher really ran (generic_splits_run:
+    the request clamped to the chunk count, empty splits dropped).  The floor stays TINY: by the MI355X programming guide the
+    C / D operands of an MFMA never flush and its fp32 A / B operands follow the kernel's denormal mode, which hipcc's default
+    keeps at 'preserve', so an underflowing result costs what one rounding to a subnormal costs.
+    At K = 4608 gamma_n A is about one average term, so every frame is ALSO held to max |err| <= FP32_FRAME x max |ref of that
+    frame| (conv_reference.FP32_FRAME, the suite's bound of an fp32-result convolution).
+    Figures besides _bounded_fig's: 'frame_rel' (each frame's max |err| / max |ref|), 'rms_rel' (rms err / rms ref of the
+    launch; reported, not asserted), 'splits_run'."""
+    N, Cin = x.shape[:2]
+    K = Cin * kh * kw
+    run = generic_splits_run(K, splits)
+    n_round = K + run + 2
+    gamma = n_round * U / (1.0 - n_round * U)
+    fr = _frames(N, frames)
+    what = f"conv2d_generic {kh}x{kw}/{stride} K={K} splits={run}"
+    if tuple(out.shape[:2]) != (N, cout):
+        raise ValueError(f"output {tuple(out.shape)} of a launch with N = {N}, Cout = {cout}")
+    rows = []
+    for n, ref, mag in conv2d_generic_frames(x, wt, cout, kh, kw, stride, pad, bias, scale, shift, relu_in, fr):
+        e = torch.nan_to_num(_f64(out[n]) - ref, nan=float("inf"))
+        rows.append(torch.cat([_bounded_row(out[n], ref, gamma * mag + TINY), torch.stack([(e * e).sum(), (ref * ref).sum()])]))
+        del ref, mag, e
+    t = torch.stack(rows).cpu()                       # the launch's one host synchronisation
+    fig = _bounded_fig(list(t[:, :4]), fr, what)
+    frame_rel = (t[:, 2] / t[:, 3].clamp_min(1e-300)).tolist()
+    fig["failures"] += [f"{what}: frame {n}: max err {frame_rel[i]:.3e} of max|ref| > {FP32_FRAME:g}"
+                        for i, n in enumerate(fr) if not frame_rel[i] <= FP32_FRAME]
+    fig.update(frame_rel=frame_rel, splits_run=run,
+               rms_rel=float(torch.sqrt(t[:, 4].sum() / t[:, 5].sum().clamp_min(1e-300))))
+    return fig
+
+
+# ---- maxpool2d -----------------------------------------------------------------------------------------------------------
+def _per_channel(v, scale_n, shift_n):
+    """v [C, ...] * scale [C] + shift [C] in fp64"""
+    b = (-1,) + (1,) * (v.dim() - 1)
+    return v * _f64(scale_n).view(b) + _f64(shift_n).view(b)
+
+
+def maxpool2d_frames(x, k, stride, pad, scale=None, shift=None, relu=False, frames=None):
+    """yields (n, fp64 F.max_pool2d(relu?(x[n] scale[n] + shift[n]), k, stride, pad) [C, Ho, Wo]) (padding: -inf)"""
+    N, C = x.shape[:2]
+    for n in _frames(N, frames):
+        v = _f64(x[n])
+        if scale is not None:
+            v = _per_channel(v, scale.reshape(N, C)[n], shift.reshape(N, C)[n])
+        if relu:
+            v = v.clamp_min(0.0)
+        yield n, F.max_pool2d(v[None], k, stride, pad)[0]
+
+
+def maxpool2d_fp64(x, k, stride, pad, scale=None, shift=None, relu=False):
+    return torch.stack([r for _, r in maxpool2d_frames(x, k, stride, pad, scale, shift, relu)])
+
+
+def check_maxpool2d(out, x, k, stride, pad, scale=None, shift=None, relu=False, frames=None):
+    """The kernel rounds each value of the window once, v = fl(fma(x, scale, shift)), and takes maxima (ReLU is a maximum with
+    0).  Rounding is monotone, so max_i fl(v_i) = fl(max_i v_i): the output IS the rounded reference, per output
+    |out - ref| <= u |ref| + TINY.  Without a scale nothing is rounded: the output must be bit-equal (bound 0), the -inf
+    padding of the border windows included."""
+    fr = _frames(x.shape[0], frames)
+    rows = []
+    for n, ref in maxpool2d_frames(x, k, stride, pad, scale, shift, relu, fr):
+        rows.append(_bounded_row(out[n], ref, U * ref.abs() + TINY if scale is not None else torch.zeros_like(ref)))
+    return _bounded_fig(rows, fr, f"maxpool2d {k}/{stride}/{pad}")
+
+
+# ---- affine_add_relu -----------------------------------------------------------------------------------------------------
+def affine_add_relu_frames(a, sa=None, ta=None, b=None, sb=None, tb=None, relu=True, frames=None):
+    """yields (n, ref, fp64 bound without TINY) per sample of relu?((a sa + ta) + (b sb + tb)); see check_affine_add_relu"""
+    N, C = a.shape[:2]
+    for n in _frames(N, frames):
+        A = _f64(a[n])
+        mag = torch.zeros_like(A)
+        if sa is not None:
+            A = _per_channel(A, sa.reshape(N, C)[n], ta.reshape(N, C)[n])
+            mag = mag + A.abs()
+        ref = A
+        if b is not None:
+            B = _f64(b[n])
+            if sb is not None:
+                B = _per_channel(B, sb.reshape(N, C)[n], tb.reshape(N, C)[n])
+                mag = mag + B.abs()
+            ref = A + B
+            mag = mag + ref.abs()
+        yield n, (ref.clamp_min(0.0) if relu else ref), U * (1.0 + U) * mag
+
+
+def affine_add_relu_fp64(a, sa=None, ta=None, b=None, sb=None, tb=None, relu=True):
+    return torch.stack([r for _, r, _ in affine_add_relu_frames(a, sa, ta, b, sb, tb, relu)])
+
+
+def check_affine_add_relu(out, a, sa=None, ta=None, b=None, sb=None, tb=None, relu=True, frames=None):
+    """With A = a sa + ta and B = b sb + tb in fp64 the kernel computes A^ = fl(fma(a, sa, ta)) = A (1 + d1),
+    B^ = B (1 + d2) and fl(A^ + B^) = (A^ + B^)(1 + d3), |d| <= u: the error is at most u |A| + u |B| + u |A^ + B^| with
+    |A^ + B^| <= |A + B| + u (|A| + |B|), so per output |out - ref| <= u (1 + u) (|A| + |B| + |A + B|) + TINY.  An operand
+    without an affine is exact and drops its term (b as the block input: no |B|); without b there is no sum and no |A + B|.
+    ReLU is 1-Lipschitz, so the bound carries through it."""
+    fr = _frames(a.shape[0], frames)
+    rows = [_bounded_row(out[n], ref, bound + TINY) for n, ref, bound in affine_add_relu_frames(a, sa, ta, b, sb, tb, relu, fr)]
+    return _bounded_fig(rows, fr, "affine_add_relu" + (" +downsample affine" if sb is not None else ""))
+
+
+# ---- grid_sample2d -------------------------------------------------------------------------------------------------------
+def _lattice_points2d(size, device, dtype):
+    """[S, S, 3]: (u, v, 1) of the square identity lattice of ExpressionEmbed, u fastest"""
+    lin = lattice(size, device).to(dtype)
+    v, u = torch.meshgrid(lin, lin, indexing="ij")
+    return torch.stack([u, v, torch.ones_like(u)], dim=-1)
+
+
+def theta_grid2d_fp64(theta_n, size):
+    """theta [2, 3] of one sample -> grid [S, S, 2] fp64 = fp64 product of the fp32 lattice and the fp32 theta"""
+    return _lattice_points2d(size, theta_n.device, torch.float64) @ _f64(theta_n).t()
+
+
+def theta_grid2d_f32(theta_n, size):
+    """the same as the reference code builds it: identity_grid.bmm(theta.transpose(1, 2)) in fp32"""
+    p = _lattice_points2d(size, theta_n.device, torch.float32)
+    return p.reshape(1, -1, 3).bmm(theta_n.float().t().unsqueeze(0)).reshape(size, size, 2)
+
+
+def grid_sample2d_frames(img, grid=None, theta=None, size=None, frames=None, yardstick=True):
+    """yields (n, fp64 reference [C, Ho, Wo], yardstick or None) per sample of ops.grid_sample2d(img, grid= / theta=, size=):
+    F.grid_sample in fp64 (bilinear, zeros, align_corners=False), and ATen's fp32 CPU F.grid_sample on the same inputs (grid=:
+    the same fp32 grid; theta=: the fp32 bmm grid) as the yardstick"""
+    if (grid is None) == (theta is None):
+        raise ValueError("exactly one of grid / theta")
+    for n in _frames(img.shape[0], frames):
+        g64 = _f64(grid[n]) if grid is not None else theta_grid2d_fp64(theta[n], int(size))
+        ref = F.grid_sample(_f64(img[n])[None], g64[None], mode="bilinear", padding_mode="zeros", align_corners=False)[0]
+        assert ref.dtype == torch.float64
+        yard = None
+        if yardstick:
+            g = grid[n].float().cpu() if grid is not None else theta_grid2d_f32(theta[n].cpu(), int(size))
+            yard = F.grid_sample(img[n].float().cpu()[None], g[None], mode="bilinear", padding_mode="zeros", align_corners=False)[0]
+            assert yard.dtype == torch.float32 and yard.device.type == "cpu"
+        yield n, ref, yard
+
+
+def grid_sample2d_fp64(img, grid=None, theta=None, size=None):
+    return torch.stack([r for _, r, _ in grid_sample2d_frames(img, grid, theta, size, yardstick=False)])
+
+
+def warp2d_frames(theta, size, frames=None):
+    """yields (n, fp64 warp [S, S, 2], fp64 bound without TINY) of the theta form's returned grid.  The kernel computes, per
+    coordinate j, p^ = fl(u t[j][0]), q^ = fl(fma(v, t[j][1], p^)) and g^ = fl(fma(1, t[j][2], q^)): three roundings.  On the
+    exact intermediates p = u t0, q = v t1 + p, g = t2 + q: |p^ - p| <= u |p|; |q^ - q| <= |p^ - p| + u (|q| + |p^ - p|);
+    |g^ - g| <= |q^ - q| + u (|g| + |q^ - q|) <= u (1 + u)^2 (|p| + |q| + |g|)."""
+    for n in _frames(theta.shape[0], frames):
+        pts = _lattice_points2d(int(size), theta.device, torch.float64)
+        t = _f64(theta[n])                                                           # [2, 3]
+        p = pts[..., 0:1] * t[:, 0]
+        q = pts[..., 1:2] * t[:, 1] + p
+        g = t[:, 2] + q
+        yield n, g, U * (1.0 + U) ** 2 * (p.abs() + q.abs() + g.abs())
+
+
+def check_grid_sample2d(out, img, grid=None, theta=None, size=None, warp=None, frames=None):
+    """The sampled image is held as check_grid_sample3d holds the 3-D sampler: to ATen's fp32 CPU F.grid_sample on the same
+    inputs against the same fp64 reference, max |err| <= SAMPLER_MAX x and mean |err| <= SAMPLER_MEAN x the yardstick's, each
+    plus SAMPLER_FLOOR x mean |ref|.  warp = the grid the launch returned (want_grid): with theta= every coordinate is held to
+    the fp64 product under the bound of warp2d_frames (+ TINY); with grid= it must be the given grid bit for bit.  Figures
+    besides the yardstick's: 'warp_worst' (x bound)."""
+    fr = _frames(img.shape[0], frames)
+    rows = [_yardstick_row(out[n], ref, yard, n) for n, ref, yard in grid_sample2d_frames(img, grid, theta, size, fr)]
+    fig = _yardstick_fig(rows, fr, "grid_sample2d")
+    if warp is not None:
+        if theta is not None:
+            wrows = [_bounded_row(warp[n], g, bound + TINY) for n, g, bound in warp2d_frames(theta, size, fr)]
+        else:
+            wrows = [_bounded_row(warp[n], _f64(grid[n]), torch.zeros_like(grid[n], dtype=torch.float64)) for n in fr]
+        wfig = _bounded_fig(wrows, fr, "grid_sample2d warp")
+        fig["failures"] += wfig["failures"]
+        fig["warp_worst"] = wfig["worst"]
+    return fig
+
+
+# ---- resize2d (bilinear, whole frame) ------------------------------------------------------------------------------------
+def resize2d_frames(x, size, frames=None, yardstick=True):
+    """yields (n, fp64 F.interpolate(x[n], size, 'bilinear', align_corners=False) [C, Ho, Wo], ATen's fp32 CPU result or None)"""
+    for n in _frames(x.shape[0], frames):
+        ref = F.interpolate(_f64(x[n])[None], size=tuple(size), mode="bilinear", align_corners=False)[0]
+        assert ref.dtype == torch.float64
+        yard = F.interpolate(x[n].float().cpu()[None], size=tuple(size), mode="bilinear", align_corners=False)[0] if yardstick else None
+        yield n, ref, yard
+
+
+def resize2d_fp64(x, size):
+    return torch.stack([r for _, r, _ in resize2d_frames(x, size, yardstick=False)])
+
+
+def check_resize2d(out, x, size, frames=None):
+    """ops.resize2d(x, size, 'bilinear') on the whole frame against the fp64 interpolation, held to ATen's fp32 CPU kernel on
+    the same input with the sampler's margins (the same construction as check_grid_sample2d: another valid order of the same
+    fp32 operations)"""
+    fr = _frames(x.shape[0], frames)
+    rows = [_yardstick_row(out[n], ref, yard, n) for n, ref, yard in resize2d_frames(x, size, fr)]
+    return _yardstick_fig(rows, fr, f"resize2d bilinear -> {tuple(size)}")
+
+
+# ---- pose_theta ----------------------------------------------------------------------------------------------------------
+def _restate():
+    oracle = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
+    if oracle not in sys.path:
+        sys.path.insert(0, oracle)
+    import restate
+    return restate
+
+
+def pose_theta_fp64(scale, rotation, translation):
+    """oracle/restate.get_transform_matrix (S @ R @ T of utils/point_transforms.py) in fp64 on the fp32 inputs, on the CPU"""
+    return _restate().get_transform_matrix(_f64(scale).cpu(), _f64(rotation).cpu(), _f64(translation).cpu())
+
+
+def check_pose_theta(out, scale, rotation, translation, frames=None):
+    """ops.pose_theta against pose_theta_fp64, held to the same function in fp32 on the CPU (torch's sin / cos and two fp32
+    matrix products) with the sampler's margins: the device sinf / cosf carry no stated accuracy to derive an ulp bound from,
+    so the yardstick is another fp32 evaluation of the same formula.  One row of figures per matrix."""
+    fr = _frames(scale.shape[0], frames)
+    ref = pose_theta_fp64(scale, rotation, translation)
+    yard = _restate().get_transform_matrix(scale.float().cpu(), rotation.float().cpu(), translation.float().cpu())
+    assert ref.dtype == torch.float64 and yard.dtype == torch.float32
+    got = out.cpu()
+    return _yardstick_fig([_yardstick_row(got[n], ref[n], yard[n], n) for n in fr], fr, "pose_theta", yardstick="torch fp32")

@@ -6,6 +6,8 @@ Tolerances, relative to max|reference| of each tensor:
   conv kernel        2e-5   exact-fp32 MFMA, different summation order than the CPU library (K up to 4608)
   alignment sampler  2e-6   same formulas as ATen's vectorised CPU kernel, FMA contraction of the CPU build unknown
   embedder outputs   2e-4   20 (resnet18) / 53 (resnet50) conv + GroupNorm layers in sequence
+The conv kernel's edges (uneven last K split, ragged last K chunk, several frames in one 64-column tile) are held per output
+to the bound of tests/ops_reference.py instead (test_conv2d_generic_edges_under_the_per_output_bound).
 """
 import math
 import os
@@ -20,7 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import restate as O  # noqa: E402
 
 from emoportraits_amd import embedders as E  # noqa: E402
-from emoportraits_amd import ops, pack  # noqa: E402
+from emoportraits_amd import hip, ops, pack  # noqa: E402
+import ops_reference as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -64,6 +67,40 @@ def test_conv2d_generic_matches_torch(case):
                                    None if b is None else b.to(DEV), None if sc is None else sc.to(DEV).contiguous(),
                                    None if sh is None else sh.to(DEV).contiguous(), relu_in=affine, splits=splits)
         assert rel_err(again, ref) <= 2e-5
+
+
+@pytest.mark.parametrize("case", [
+    # N, Cin, H, W, Cout, k, stride, pad, affine, relu_in, bias, explicit split counts (besides the heuristic's)
+    (3, 64, 8, 8, 64, 3, 1, 1, True, True, False, (4,)),      # K = 576: 18 chunks, the heuristic's 4 splits of 5, 5, 5 and 3
+    (3, 3, 16, 16, 64, 7, 2, 3, True, False, False, ()),      # K = 147: a ragged last chunk; the stem's affine without ReLU
+    (3, 32, 4, 4, 70, 3, 1, 1, True, True, False, ()),        # 48 columns: three frames in one tile, two channel tiles
+    (3, 32, 4, 4, 70, 3, 1, 1, False, False, True, (9,)),     # the same with a bias and one chunk per split
+    (2, 128, 4, 4, 9, 1, 2, 0, False, False, False, ()),      # 1x1 stride 2: 2x2 outputs, 8 columns
+])
+def test_conv2d_generic_edges_under_the_per_output_bound(case):
+    """The smallest shapes at which each edge of the kernel exists, every frame of every launch under the per-output bound of
+    ops_reference.check_conv2d_generic (gamma_n sum |w||x'| + TINY, n = K + splits + 2) instead of a share of the tensor's
+    maximum; the affine is distinct per frame (scale and shift of different magnitude in each), so a frame of a shared tile
+    that reads its neighbour's row cannot pass."""
+    N, Cin, H, W, Cout, k, stride, pad, affine, relu_in, bias, explicit = case
+    g = torch.Generator().manual_seed(1000 + sum(case[:8]))
+    x = torch.randn(N, Cin, H, W, generator=g).to(DEV)
+    wt = pack.pack_generic(torch.randn(Cout, Cin, k, k, generator=g) / math.sqrt(Cin * k * k)).to(DEV)
+    b = torch.randn(Cout, generator=g).to(DEV) if bias else None
+    sc = sh = None
+    if affine:
+        per_frame = torch.tensor([1.0, -0.5, 2.0])[:N, None]
+        sc = ((1 + 0.3 * torch.randn(N, Cin, generator=g)) * per_frame).to(DEV).contiguous()
+        sh = (0.3 * torch.randn(N, Cin, generator=g) + 0.2 * per_frame).to(DEV).contiguous()
+    heuristic = hip.load().emo_conv2d_generic_splits(N, Cin, H, W, Cout, k, k, stride, pad)
+    if explicit == (4,):
+        assert heuristic == 4                                       # the uneven last split runs through the heuristic itself
+    for splits in (None,) + explicit:
+        got = ops.conv2d_generic(x, wt, Cout, k, k, stride, pad, b, sc, sh, relu_in=relu_in, splits=splits)
+        fig = R.check_conv2d_generic(got, x, wt, Cout, k, k, stride, pad, b, sc, sh, relu_in, heuristic if splits is None else splits)
+        print(f"PARITY conv2d_generic edge {case[:8]} splits={splits} (run {fig['splits_run']}): worst {fig['worst']:.3g} x bound "
+              f"(frame {fig['worst_frame']}), per-frame max/max|ref| {max(fig['frame_rel']):.2e}, rms {fig['rms_rel']:.2e}")
+        assert fig["frames"] == list(range(N)) and fig["failures"] == [], fig["failures"]
 
 
 def test_maxpool_with_folded_norm_and_relu():

@@ -13,7 +13,8 @@ One PARITY line per pass: the worst figure per operation (call site and frame), 
 kernel, and the inventory (operation, form, per-sample shape) -> launches.
 
 The coverage guard at the end runs without a GPU: every ops.<name>( call in nets.py is wrapped here, wrapped by the conv
-checker, or exempt by name with a reason.
+checker, or exempt by name with a reason.  The checker and the guard take a tuple of modules: the embedders' launches
+(test_embedder_launches_fp64_gpu.py) go through the same OpLaunchChecker with their own operations registered.
 """
 import inspect
 import os
@@ -25,7 +26,7 @@ import pytest
 import torch
 
 import ops_reference as R
-from emoportraits_amd import nets, ops
+from emoportraits_amd import embedders, encoder, nets, ops, stage2
 
 DEV = "cuda:0"
 GRID_CAP = 8192 * 256             # work items one trip of a capped grid covers (grid_for: 8192 blocks of 256 threads)
@@ -35,21 +36,33 @@ WRAPPED = ("groupnorm_affine", "upsample_trilinear", "avgpool", "add", "add_rows
 CONV_CHECKER = ("conv_igemm", "conv_head")                   # test_conv_launches_fp64_gpu.LaunchChecker
 EXEMPT = {"clear_overflow_flags": "a fill of the overflow words: no arithmetic; its effect is what overflow_events reads",
           "overflow_events": "a host read of the overflow words: no launch"}
-_REAL = {name: getattr(ops, name) for name in WRAPPED}
-_SIG = {name: inspect.signature(fn) for name, fn in _REAL.items()}
-_NETS = os.path.abspath(nets.__file__)
+_REAL, _SIG = {}, {}
 
 
-def _call_site():
-    """function:line of the nets.py frame that made the launch (with the block's prefix where the caller has one)"""
+def register(names):
+    """keep the real ops.<name> and its signature for a wrapper to call (before anything is patched)"""
+    for name in names:
+        if name not in _REAL:
+            _REAL[name] = getattr(ops, name)
+            _SIG[name] = inspect.signature(_REAL[name])
+
+
+register(WRAPPED)
+NETWORK_MODULES = (nets, embedders, stage2, encoder)            # the modules whose frames name a launch's call site
+_SOURCES = tuple(os.path.abspath(m.__file__) for m in NETWORK_MODULES)
+
+
+def _call_site(sources=_SOURCES):
+    """function:line of the innermost frame of one of the network modules that made the launch (with the block's prefix where
+    the caller has one)"""
     f = sys._getframe(2)
-    while f is not None and os.path.abspath(f.f_code.co_filename) != _NETS:
+    while f is not None and os.path.abspath(f.f_code.co_filename) not in sources:
         f = f.f_back
     if f is None:
         return "?"
     owner = f.f_locals.get("self")
     site = f"{type(owner).__name__ + '.' if owner is not None else ''}{f.f_code.co_name}:{f.f_lineno}"
-    while f is not None and os.path.abspath(f.f_code.co_filename) == _NETS:
+    while f is not None and os.path.abspath(f.f_code.co_filename) in sources:
         prefix = getattr(f.f_locals.get("self"), "prefix", None)
         if prefix:
             return f"{prefix} {site}"
@@ -64,6 +77,9 @@ def _overlaps(out, t):
 class OpLaunchChecker:
     """stands in for the non-conv ops attributes while a pass runs: real launch, fp64 check, one summary row"""
 
+    wrapped = WRAPPED                     # the ops attributes this checker stands in for (a subclass names its own)
+    title = "op launches"
+
     def __init__(self, tag):
         self.tag = tag
         self.rows = []
@@ -71,7 +87,7 @@ class OpLaunchChecker:
         self._inside = False              # a wrapped op that calls another one (grid_sample3d's repack): checked as the outer launch
 
     def install(self, mp):
-        for name in WRAPPED:
+        for name in self.wrapped:
             mp.setattr(ops, name, self._wrapper(name))
 
     def _wrapper(self, name):
@@ -95,7 +111,8 @@ class OpLaunchChecker:
             batch = (result[0] if isinstance(result, tuple) else result).shape[0]
             self.rows.append(dict(op=name, form=form, shape=shape, site=site, batch=batch, frames=len(fig["frames"]),
                                   worst=fig["worst"], frame=fig["worst_frame"], unit=fig["unit"], failures=fig["failures"],
-                                  max_ratio=fig.get("max_ratio"), mean_ratio=fig.get("mean_ratio")))
+                                  max_ratio=fig.get("max_ratio"), mean_ratio=fig.get("mean_ratio"), yardstick=fig.get("yardstick"),
+                                  rms=fig.get("rms_rel")))
             return result
         return call
 
@@ -158,18 +175,25 @@ class OpLaunchChecker:
     def report(self):
         assert self.rows, f"{self.tag}: no launch was intercepted"
         parts = []
-        for name in WRAPPED:
+        for name in self.wrapped:
             rows = [r for r in self.rows if r["op"] == name]
             if not rows:
                 continue
             w = max(rows, key=lambda r: r["worst"])
             s = f"{name} {w['worst']:.3g} {w['unit']} ({w['form']} {w['site']}, frame {w['frame']})"
-            if name == "grid_sample3d":
-                s += ("; error ratios to ATen fp32: " + ", ".join(
+            if rows[0]["max_ratio"] is not None:           # held to a yardstick (the samplers)
+                s += (f"; error ratios to {rows[0]['yardstick']}: " + ", ".join(
                     f"{r['form']} max {r['max_ratio']:.3f} mean {r['mean_ratio']:.3f}" for r in _worst_per_form(rows)))
+            if rows[0]["rms"] is not None:
+                rms = sorted(r["rms"] for r in rows)
+                s += f"; rms err / rms ref: worst {rms[-1]:.2e}, median {rms[len(rms) // 2]:.2e}"
+                by_form = {}
+                for r in rows:
+                    by_form[r["form"]] = max(by_form.get(r["form"], 0.0), r["rms"])
+                s += ", worst per form: " + ", ".join(f"{k} {v:.2e}" for k, v in sorted(by_form.items()))
             parts.append(s)
         inv = self.inventory()
-        print(f"PARITY op launches vs fp64 [{self.tag}]: {len(self.rows)} launches; worst per operation: " + "; ".join(parts)
+        print(f"PARITY {self.title} vs fp64 [{self.tag}]: {len(self.rows)} launches; worst per operation: " + "; ".join(parts)
               + "; inventory (operation, form, per-sample shape) -> launches: " + str(dict(sorted(inv.items(), key=str))))
         return inv
 
@@ -277,10 +301,18 @@ def test_source_pass_every_op_launch_vs_fp64(monkeypatch):
         assert chk.has("groupnorm_affine", lambda f: f.split("+")[0] == form), (form, inv)
 
 
+def ops_called(*modules):
+    """the names of every ops.<name>( call in the source of the given modules"""
+    called = set()
+    for m in modules:
+        with open(os.path.abspath(m.__file__)) as f:
+            called |= set(re.findall(r"\bops\.(\w+)\(", f.read()))
+    return called
+
+
 def test_every_ops_call_of_the_networks_is_checked_or_exempt():
     """a launch added to the passes later cannot go unchecked without someone deciding so"""
-    with open(_NETS) as f:
-        called = set(re.findall(r"\bops\.(\w+)\(", f.read()))
+    called = ops_called(nets)
     assert {"conv_igemm", "groupnorm_affine", "grid_sample3d"} <= called, called            # (the pattern still finds the calls)
     unchecked = sorted(called - set(WRAPPED) - set(CONV_CHECKER) - set(EXEMPT))
     assert not unchecked, f"ops called by nets.py that no launch checker wraps: {unchecked}"

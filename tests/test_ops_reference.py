@@ -1,5 +1,5 @@
 """The fp64 references and launch checkers of tests/ops_reference.py, on the CPU: each reference equals the plain fp32 torch
-composition of its operation, each checker passes an output that carries only fp32 rounding noise, and each checker reports
+composition of its operation (the embedders' references: torch's own fp64 evaluation, to fp64 rounding), each checker passes an output that carries only fp32 rounding noise, and each checker reports
 the kernel faults it is there to catch (planted in that output)."""
 import pytest
 import torch
@@ -16,6 +16,12 @@ def _close(ref64, f32, tol=2e-6):
     assert ref64.dtype == torch.float64 and f32.dtype == torch.float32
     assert tuple(ref64.shape) == tuple(f32.shape)
     return (ref64 - f32.double()).abs().max().item() <= tol * max(1.0, ref64.abs().max().item())
+
+
+def _same64(ref64, own64, tol=1e-14):
+    """a reference against torch's own fp64 evaluation of the operation: the same numbers up to fp64 rounding"""
+    assert ref64.dtype == own64.dtype == torch.float64 and tuple(ref64.shape) == tuple(own64.shape)
+    return (ref64 - own64).abs().max().item() <= tol * max(1.0, own64.abs().max().item())
 
 
 def _clean(fig):
@@ -378,3 +384,276 @@ def test_sampler_checker_reports_the_planted_faults():
     _caught(R.check_grid_sample3d(out, vol3, delta=delta3, vol_index=index))              # the bad index clamped, not zeroed
     # the theta form with the delta form's grid
     _caught(R.check_grid_sample3d(border, vol, theta=theta, padding_mode="border"))
+
+
+# ---- conv2d_generic ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cout", [9, 64, 70])
+def test_unpack_generic_inverts_pack_generic_bit_for_bit(cout):
+    from emoportraits_amd import pack
+    w = torch.randn(cout, 5, 3, 2, generator=_g(20))
+    w[0, 0, 0, 0], w[-1, -1, -1, -1] = -0.0, 2.0 ** -140                                  # a signed zero and a subnormal survive
+    wt = pack.pack_generic(w)
+    assert tuple(wt.shape) == (30, (cout + 63) // 64 * 64) and wt[:, cout:].abs().sum().item() == 0
+    back = R.unpack_generic(wt, cout, 5, 3, 2)
+    assert tuple(back.shape) == tuple(w.shape) and torch.equal(back.contiguous().view(torch.int32), w.view(torch.int32))
+    with pytest.raises(ValueError):
+        R.unpack_generic(wt, cout, 5, 3, 3)
+
+
+def test_generic_splits_run_follows_the_launcher():
+    """requests -> (chunks per split rounded up, empty splits dropped), as emo_conv2d_generic_f32 derives them"""
+    assert R.generic_splits_run(576, 4) == 4            # 18 chunks: 5 + 5 + 5 + 3
+    assert R.generic_splits_run(576, 7) == 6            # 3 per split: the seventh split would be empty
+    assert R.generic_splits_run(4608, 32) == 29         # 144 chunks, 5 per split
+    assert R.generic_splits_run(147, 64) == 5           # clamped to the 5 chunks (the last one ragged: 19 rows)
+    assert R.generic_splits_run(288, 9) == 9 and R.generic_splits_run(288, 1) == 1 and R.generic_splits_run(31, 3) == 1
+
+
+def _conv_case(N, Cin, H, W, Cout, k, stride, pad, seed, affine=True, bias=True, relu=True):
+    from emoportraits_amd import pack
+    g = _g(seed)
+    x = torch.randn(N, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
+    b = torch.randn(Cout, generator=g) if bias else None
+    sc = 1 + 0.3 * torch.randn(N, Cin, generator=g) if affine else None
+    sh = 0.3 * torch.randn(N, Cin, generator=g) if affine else None
+    return dict(x=x, w=w, wt=pack.pack_generic(w), geom=(Cout, k, k, stride, pad), bias=b, scale=sc, shift=sh,
+                relu_in=relu and affine)
+
+
+def _conv_by_hand(c, drop=None, bias_times=1, bias_roll=0, affine_of=None):
+    """the operation in fp64 from the unpacked pieces, rounded once to fp32, with the faults to plant: `drop` = rows of the
+    im2col matrix left out of the sum, the bias added `bias_times` times or rolled by `bias_roll` channels, sample n prepared
+    with the affine of sample affine_of[n]"""
+    Cout, k, _, stride, pad = c["geom"]
+    N = c["x"].shape[0]
+    outs = []
+    for n in range(N):
+        v = c["x"][n].double()
+        if c["scale"] is not None:
+            m = n if affine_of is None else affine_of[n]
+            v = v * c["scale"][m].double()[:, None, None] + c["shift"][m].double()[:, None, None]
+            if c["relu_in"]:
+                v = v.clamp_min(0)
+        cols = F.unfold(v[None], (k, k), padding=pad, stride=stride)[0]
+        if drop is not None:
+            cols[drop] = 0.0
+        o = c["w"].double().reshape(Cout, -1) @ cols
+        if c["bias"] is not None:
+            o = o + bias_times * c["bias"].double().roll(bias_roll)[:, None]
+        outs.append(o)
+    Ho = (c["x"].shape[2] + 2 * pad - k) // stride + 1
+    return torch.stack(outs).reshape(N, Cout, Ho, -1).float()
+
+
+def _conv_check(c, out, splits=1):
+    Cout, kh, kw, stride, pad = c["geom"]
+    return R.check_conv2d_generic(out, c["x"], c["wt"], Cout, kh, kw, stride, pad, c["bias"], c["scale"], c["shift"], c["relu_in"], splits)
+
+
+@pytest.mark.parametrize("case", [
+    (3, 64, 8, 8, 64, 3, 1, 1, True, True),          # K = 576
+    (3, 3, 16, 16, 16, 7, 2, 3, True, False),        # K = 147: the stem, affine without ReLU below
+    (2, 40, 9, 7, 9, 3, 2, 1, False, True),          # odd sizes, no affine
+    (2, 128, 4, 4, 9, 1, 2, 0, False, False),        # 1x1 stride 2: 2x2 outputs
+])
+def test_conv2d_generic_reference_equals_torch(case):
+    N, Cin, H, W, Cout, k, stride, pad, affine, bias = case
+    c = _conv_case(N, Cin, H, W, Cout, k, stride, pad, seed=21, affine=affine, bias=bias, relu=Cin != 3)
+    ref = R.conv2d_generic_fp64(c["x"], c["wt"], Cout, k, k, stride, pad, c["bias"], c["scale"], c["shift"], c["relu_in"])
+    xin = c["x"].double()
+    if affine:
+        xin = xin * c["scale"].double()[:, :, None, None] + c["shift"].double()[:, :, None, None]
+        xin = F.relu(xin) if c["relu_in"] else xin
+    own = F.conv2d(xin, c["w"].double(), None if c["bias"] is None else c["bias"].double(), stride=stride, padding=pad)
+    assert ref.dtype == torch.float64 and tuple(ref.shape) == tuple(own.shape)
+    assert (ref - own).abs().max().item() <= 1e-13 * own.abs().max().item() * Cin * k * k
+    fig = _clean(_conv_check(c, ref.float()))                                              # the rounded reference
+    assert fig["frames"] == list(range(N)) and fig["worst"] <= 1 and len(fig["frame_rel"]) == N and 0 < fig["rms_rel"] < 1e-7
+    assert torch.equal(_conv_by_hand(c), ref.float())
+    _clean(_conv_check(c, F.conv2d(xin.float(), c["w"], c["bias"], stride=stride, padding=pad), splits=3))   # a plain fp32 evaluation
+
+
+def test_conv_checker_reports_faults_in_the_k_loop():
+    c = _conv_case(3, 64, 8, 8, 64, 3, 1, 1, seed=22)                                      # K = 576: 18 chunks
+    _clean(_conv_check(c, _conv_by_hand(c), splits=4))
+    fig = _caught(_conv_check(c, _conv_by_hand(c, drop=[100]), splits=4))                  # one K term of 576
+    assert all(f > 1 for f in fig["frame_fig"])
+    assert max(fig["frame_rel"]) > R.FP32_FRAME                                            # (the frame bound sees this one too)
+    assert _conv_check(c, _conv_by_hand(c), splits=4)["splits_run"] == 4
+    _caught(_conv_check(c, _conv_by_hand(c, drop=slice(15 * 32, 576)), splits=4))          # the last, uneven split: chunks 15..17
+    stem = _conv_case(3, 3, 16, 16, 16, 7, 2, 3, seed=23, bias=False, relu=False)          # K = 147 = 4 chunks + 19 rows
+    _clean(_conv_check(stem, _conv_by_hand(stem)))
+    _caught(_conv_check(stem, _conv_by_hand(stem, drop=slice(128, 147))))                  # the ragged last chunk
+    _caught(_conv_check(stem, _conv_by_hand(stem, drop=[146])))                            # its last row alone
+
+
+def test_conv_checker_reports_faults_in_the_bias():
+    c = _conv_case(3, 32, 4, 4, 70, 3, 1, 1, seed=24, affine=False)                        # K = 288: 9 chunks
+    _clean(_conv_check(c, _conv_by_hand(c), splits=9))
+    _caught(_conv_check(c, _conv_by_hand(c, bias_times=9), splits=9))                      # added by every split
+    _caught(_conv_check(c, _conv_by_hand(c, bias_times=0), splits=9))                      # lost in the reduction
+    fig = _caught(_conv_check(c, _conv_by_hand(c, bias_roll=1), splits=9))                 # the neighbouring channel's
+    assert all(f > 1 for f in fig["frame_fig"])
+    # in one channel with a small bias the wrong bias is far below the tensor's maximum: the bound is per output
+    small = dict(c, bias=c["bias"].clone())
+    small["bias"][5], small["bias"][4] = 3e-4, -2e-4
+    out = _conv_by_hand(small)
+    bad = out.clone()
+    bad[:, 5] = _conv_by_hand(small, bias_roll=1)[:, 5]
+    assert (bad - out).abs().max().item() < 2e-4 * out.abs().max().item()
+    _caught(_conv_check(small, bad, splits=9))
+
+
+def test_conv_checker_reports_faults_between_the_frames_of_one_tile():
+    """N = 3 on a 4x4 map: 48 GEMM columns, all in one 64-column tile"""
+    c = _conv_case(3, 32, 4, 4, 70, 3, 1, 1, seed=25, bias=False)
+    out = _conv_by_hand(c)
+    assert _clean(_conv_check(c, out))["frames"] == [0, 1, 2]
+    fig = _caught(_conv_check(c, _conv_by_hand(c, affine_of=[0, 0, 2])))                   # frame 1 prepared with frame 0's affine
+    assert fig["frame_fig"][0] <= 1 and fig["frame_fig"][2] <= 1 < fig["frame_fig"][1] and fig["worst_frame"] == 1
+    fig = _caught(_conv_check(c, out[[0, 2, 1]]))                                          # frames 1 and 2 exchanged
+    assert fig["frame_fig"][0] <= 1 and fig["frame_fig"][1] > 1 and fig["frame_fig"][2] > 1
+    # a fault in one frame whose values are 1e-4 of the other frames': under 2e-5 of the tensor's maximum
+    quiet = dict(c, x=c["x"] * torch.tensor([1.0, 1e-4, 1.0]).view(3, 1, 1, 1),
+                 shift=c["shift"] * torch.tensor([1.0, 1e-4, 1.0]).view(3, 1))
+    out = _conv_by_hand(quiet)
+    bad = out.clone()
+    bad[1] = _conv_by_hand(quiet, drop=[7])[1]
+    assert (bad - out).abs().max().item() < 2e-5 * out.abs().max().item()
+    assert _caught(_conv_check(quiet, bad))["worst_frame"] == 1
+
+
+def _fma(x, s, t):
+    """fl(x s + t) with ONE rounding, as the kernels' __fmaf_rn: the fp64 product of two fp32 values is exact"""
+    return (x.double() * s.double()[:, :, None, None] + t.double()[:, :, None, None]).float()
+
+
+# ---- maxpool2d -----------------------------------------------------------------------------------------------------------
+def test_maxpool_reference_and_faults():
+    g = _g(26)
+    x = torch.randn(2, 5, 9, 7, generator=g) - 2.5                                        # mostly negative: the padding value shows
+    sc, sh = torch.randn(2, 5, generator=g), torch.randn(2, 5, generator=g)               # negative scales included
+    e = lambda t: t[:, :, None, None]
+    plain = F.max_pool2d(x, 3, 2, 1)
+    assert torch.equal(R.maxpool2d_fp64(x, 3, 2, 1), plain.double())
+    assert _clean(R.check_maxpool2d(plain, x, 3, 2, 1))["worst"] == 0                     # bit-equal
+    folded = F.max_pool2d(F.relu(x * e(sc) + e(sh)), 3, 2, 1)
+    assert _same64(R.maxpool2d_fp64(x, 3, 2, 1, sc, sh, True), F.max_pool2d(F.relu(x.double() * e(sc).double() + e(sh).double()), 3, 2, 1))
+    assert _same64(R.maxpool2d_fp64(x, 3, 2, 1, sc, sh, False), F.max_pool2d(x.double() * e(sc).double() + e(sh).double(), 3, 2, 1))
+    _clean(R.check_maxpool2d(R.maxpool2d_fp64(x, 3, 2, 1, sc, sh, True).float(), x, 3, 2, 1, sc, sh, True))
+    _clean(R.check_maxpool2d(F.max_pool2d(F.relu(_fma(x, sc, sh)), 3, 2, 1), x, 3, 2, 1, sc, sh, True))   # the kernel's arithmetic in fp32
+    _caught(R.check_maxpool2d(folded, x, 3, 2, 1, sc, sh, True))        # product and sum rounded separately: outside one rounding
+    ulp = plain.clone()
+    ulp[1, 2, 3, 1] = torch.nextafter(ulp[1, 2, 3, 1], torch.tensor(9.0))
+    assert _caught(R.check_maxpool2d(ulp, x, 3, 2, 1))["worst_frame"] == 1                # without a scale one ulp is a fault
+    ninf = float("-inf")
+    shifted = F.max_pool2d(F.pad(x, (1, 0, 0, 0), value=ninf)[..., :-1], 3, 2, 1)         # every window one column to the left
+    _caught(R.check_maxpool2d(shifted, x, 3, 2, 1))
+    zero_pad = F.max_pool2d(F.pad(x, (1, 1, 1, 1), value=0.0), 3, 2, 0)                   # 0 in place of -inf at the border
+    assert torch.equal(zero_pad[:, :, 1:-1, 1:-1], plain[:, :, 1:-1, 1:-1]) and not torch.equal(zero_pad, plain)
+    _caught(R.check_maxpool2d(zero_pad, x, 3, 2, 1))
+    no_relu = F.max_pool2d(x * e(sc) + e(sh), 3, 2, 1)
+    _caught(R.check_maxpool2d(no_relu, x, 3, 2, 1, sc, sh, True))
+
+
+# ---- affine_add_relu -----------------------------------------------------------------------------------------------------
+def test_affine_add_relu_reference_and_faults():
+    g = _g(27)
+    a, b = torch.randn(2, 6, 5, 3, generator=g), torch.randn(2, 6, 5, 3, generator=g)
+    sa, ta, sb, tb = (torch.randn(2, 6, generator=g) for _ in range(4))
+    e = lambda t: t[:, :, None, None]
+    both = F.relu(a * e(sa) + e(ta) + (b * e(sb) + e(tb)))
+    d = lambda t: e(t).double()
+    assert _same64(R.affine_add_relu_fp64(a, sa, ta, b, sb, tb), F.relu(a.double() * d(sa) + d(ta) + (b.double() * d(sb) + d(tb))))
+    assert _same64(R.affine_add_relu_fp64(a, sa, ta, b, sb, tb, relu=False), a.double() * d(sa) + d(ta) + (b.double() * d(sb) + d(tb)))
+    _clean(R.check_affine_add_relu(F.relu(_fma(a, sa, ta) + _fma(b, sb, tb)), a, sa, ta, b, sb, tb))     # the kernel's arithmetic in fp32
+    _clean(R.check_affine_add_relu(R.affine_add_relu_fp64(a, sa, ta, b, sb, tb).float(), a, sa, ta, b, sb, tb))
+    skip = F.relu(a * e(sa) + e(ta) + b)                                                  # b = the block input: no affine
+    assert _same64(R.affine_add_relu_fp64(a, sa, ta, b), F.relu(a.double() * d(sa) + d(ta) + b.double()))
+    skip_fma = F.relu(_fma(a, sa, ta) + b)
+    _clean(R.check_affine_add_relu(skip_fma, a, sa, ta, b))
+    _caught(R.check_affine_add_relu(skip_fma, a, sa, ta, b, sb, tb))
+    _caught(R.check_affine_add_relu(F.relu(a * e(sa) + e(ta) + (b * e(sa) + e(ta))), a, sa, ta, b, sb, tb))   # sb / tb taken from sa / ta
+    _caught(R.check_affine_add_relu(a * e(sa) + e(ta) + b, a, sa, ta, b))                 # the ReLU left out
+    rolled = F.relu(a * e(sa.roll(1, 1)) + e(ta.roll(1, 1)) + b)                          # the affine of the neighbouring channel
+    _caught(R.check_affine_add_relu(rolled, a, sa, ta, b))
+    # where A and B cancel the bound follows the operands, not the result: fp32 evaluation of a cancelling pair passes
+    nb = -_fma(a, sa, ta) * 0.999
+    _clean(R.check_affine_add_relu(F.relu(_fma(a, sa, ta) + nb), a, sa, ta, nb))
+
+
+# ---- grid_sample2d -------------------------------------------------------------------------------------------------------
+def _sampler2d_case():
+    g = _g(28)
+    smooth = F.interpolate(torch.randn(3, 4, 4, 5, generator=g), size=(21, 29), mode="bilinear", align_corners=True)
+    img = (smooth + 0.05 * torch.randn(3, 4, 21, 29, generator=g)).contiguous()
+    grid = torch.rand(3, 11, 13, 2, generator=g) * 2.8 - 1.4                              # reaches past the border
+    theta = torch.tensor([[0.9, 0.2, 0.1], [-0.15, 1.1, -0.3]]).repeat(3, 1, 1) + 0.1 * torch.randn(3, 2, 3, generator=g)
+    return img, grid, theta
+
+
+def test_grid_sample2d_reference_and_faults():
+    img, grid, theta = _sampler2d_case()
+    S = 16
+    out = F.grid_sample(img, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
+    assert _same64(R.grid_sample2d_fp64(img, grid=grid),
+                   F.grid_sample(img.double(), grid.double(), mode="bilinear", padding_mode="zeros", align_corners=False))
+    fig = _clean(R.check_grid_sample2d(out, img, grid=grid, warp=grid.clone()))
+    assert fig["max_ratio"] == fig["mean_ratio"] == 1.0 and fig["warp_worst"] == 0 and fig["frames"] == [0, 1, 2]
+    _clean(R.check_grid_sample2d(R.grid_sample2d_fp64(img, grid=grid).float(), img, grid=grid))
+    with pytest.raises(ValueError, match="frame 0: output"):
+        R.check_grid_sample2d(out[:, :, :-1], img, grid=grid)
+    border = F.grid_sample(img, grid, mode="bilinear", padding_mode="border", align_corners=False)
+    _caught(R.check_grid_sample2d(border, img, grid=grid))                                # the corners outside the image not zeroed
+    _caught(R.check_grid_sample2d(out, img, grid=grid, warp=grid.flip(-1)))
+    # the theta form: the lattice of ExpressionEmbed, the grid the reference code builds
+    g32 = torch.stack([R.theta_grid2d_f32(t, S) for t in theta])
+    g64 = torch.stack([R.theta_grid2d_fp64(t, S) for t in theta])
+    lin = torch.linspace(-1, 1, S)
+    assert _close(g64, g32, 2.4e-7) and _close(g64[..., 0], theta[:, 0, 0].view(3, 1, 1) * lin.view(1, 1, S)
+                                               + theta[:, 0, 1].view(3, 1, 1) * lin.view(1, S, 1) + theta[:, 0, 2].view(3, 1, 1), 2.4e-7)
+    aligned = F.grid_sample(img, g32, align_corners=False)
+    assert _same64(R.grid_sample2d_fp64(img, theta=theta, size=S), F.grid_sample(img.double(), g64, align_corners=False))
+    assert _close(R.grid_sample2d_fp64(img, theta=theta, size=S), aligned, 2e-5)          # (and near the fp32 bmm grid's result)
+    fig = _clean(R.check_grid_sample2d(aligned, img, theta=theta, size=S, warp=g64.float()))
+    assert fig["max_ratio"] == 1.0 and fig["warp_worst"] <= 1
+    swapped = theta[:, [1, 0]]                                                            # x and y of theta exchanged
+    gs = torch.stack([R.theta_grid2d_f32(t, S) for t in swapped])
+    _caught(R.check_grid_sample2d(F.grid_sample(img, gs, align_corners=False), img, theta=theta, size=S))
+    fig = R.check_grid_sample2d(aligned, img, theta=theta, size=S, warp=gs)              # ... in the returned warp alone
+    assert fig["failures"] and fig["warp_worst"] > 1 and fig["max_ratio"] == 1.0
+    off = g64.float().clone()
+    off[2, 5, 7, 1] = off[2, 5, 7, 1] + 4 * 2.0 ** -23 * off[2, 5, 7, 1].abs()           # four ulps in one coordinate
+    _caught(R.check_grid_sample2d(aligned, img, theta=theta, size=S, warp=off))
+    frame0_theta = F.grid_sample(img, g32[[0, 0, 2]], align_corners=False)                # frame 1 warped by frame 0's theta
+    assert _caught(R.check_grid_sample2d(frame0_theta, img, theta=theta, size=S))["worst_frame"] == 1
+
+
+# ---- resize2d ------------------------------------------------------------------------------------------------------------
+def test_resize2d_reference_and_faults():
+    x = torch.rand(2, 3, 24, 20, generator=_g(29))
+    for size in ((12, 10), (6, 5), (9, 7)):
+        out = F.interpolate(x, size=size, mode="bilinear", align_corners=False)
+        assert _same64(R.resize2d_fp64(x, size), F.interpolate(x.double(), size=size, mode="bilinear", align_corners=False))
+        fig = _clean(R.check_resize2d(out, x, size))
+        assert fig["frames"] == [0, 1] and fig["max_ratio"] in (0.0, 1.0)
+        _caught(R.check_resize2d(F.interpolate(x, size=size, mode="bilinear", align_corners=True), x, size))
+        _caught(R.check_resize2d(F.interpolate(x, size=size, mode="nearest"), x, size))
+    _caught(R.check_resize2d(F.interpolate(x, size=(9, 7), mode="bilinear", antialias=True), x, (9, 7)))
+
+
+# ---- pose_theta ----------------------------------------------------------------------------------------------------------
+def test_pose_theta_reference_and_faults():
+    g = _g(30)
+    s, r, t = 1 + 0.1 * torch.randn(5, 3, generator=g), 0.5 * torch.randn(5, 3, generator=g), 0.1 * torch.randn(5, 3, generator=g)
+    O = R._restate()
+    out = O.get_transform_matrix(s, r, t)
+    ref = R.pose_theta_fp64(s, r, t)
+    assert _same64(ref, O.get_transform_matrix(s.double(), r.double(), t.double())) and _close(ref, out, 2.4e-7)
+    assert _clean(R.check_pose_theta(out, s, r, t))["max_ratio"] == 1.0
+    _clean(R.check_pose_theta(ref.float(), s, r, t))
+    _caught(R.check_pose_theta(O.get_transform_matrix(s, r[:, [1, 0, 2]], t), s, r, t))   # yaw and pitch exchanged
+    t_not_scaled = out.clone()
+    t_not_scaled[:, :3, 3] = torch.einsum("bij,bj->bi", out[:, :3, :3] / s[:, :, None], t)
+    _caught(R.check_pose_theta(t_not_scaled, s, r, t))                                    # the translation column without the scale
