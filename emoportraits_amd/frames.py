@@ -65,20 +65,17 @@ def check_format(frame_format, colorspace="bt709", what="frame_format"):
 
 
 def check_frames(chunk, frame_format):
-    """the shape and dtype of one chunk of frames: uint8 [N,H,W,3], or NV12 uint8 [N, 3H/2, W] with H and W even; 'yuv420p',
-    'p010', 'yuv420p10': [N, 3H/2, W] of the format's dtype with the strides ops.yuv420_geometry asks for"""
+    """the shape and dtype of one chunk of frames: uint8 [N,H,W,3], or a YUV 4:2:0 format's [N, 3H/2, W] of its dtype with H and
+    W even and the strides ops.yuv420_geometry asks for (the check the ops make, so it is refused before anything is launched)"""
     check_format(frame_format)
-    if frame_format not in ("rgb8", "nv12"):
-        if not isinstance(chunk, torch.Tensor) or chunk.dim() != 3:
-            raise ValueError(f"{frame_format} frames must be {str(ops.yuv420_dtype(frame_format)).replace('torch.', '')} [N, 3H/2, W] "
-                             f"with H and W even, got {tuple(getattr(chunk, 'shape', ()))}")
-        ops.yuv420_geometry(chunk, frame_format, "frames")
-        return
     if frame_format == "rgb8":
         if chunk.dtype != torch.uint8 or chunk.dim() != 4 or chunk.shape[-1] != 3:
             raise ValueError("frames must be uint8 [N,H,W,3]")
-    elif chunk.dtype != torch.uint8 or chunk.dim() != 3 or chunk.shape[1] % 3 or chunk.shape[2] % 2 or 0 in chunk.shape[1:]:
-        raise ValueError(f"NV12 frames must be uint8 [N, 3H/2, W] with H and W even, got {tuple(chunk.shape)}")
+    else:
+        if not isinstance(chunk, torch.Tensor) or chunk.dim() != 3:
+            raise ValueError(f"{ops.yuv420_name(frame_format)} frames must be {str(ops.yuv420_dtype(frame_format)).replace('torch.', '')} "
+                             f"[N, 3H/2, W] with H and W even, got {tuple(getattr(chunk, 'shape', ()))}")
+        ops.yuv420_geometry(chunk, frame_format, "frames")
 
 
 def frame_size(chunk, frame_format):
@@ -90,13 +87,10 @@ def crops_of(u8, size, windows=None, frame_format="rgb8", colorspace="bt709", fu
     """uint8 frames [b,H,W,3] on the device -> fp32 crops [b,3,size,size]: byte -> fp32 CHW (emo_unpack_rgb8), then each frame's
     window (x0, y0, s, s) read in place and resized, the whole batch in one launch (a host list or an int32 [b,4] device
     tensor, ops.resize2d_windows), or without windows the whole frame, resized only where its size differs.
-    frame_format 'nv12': NV12 frames [b, 3H/2, W] -> the same crops of the converted frames in ONE launch (ops.nv12_windows:
-    only the bytes under the windows are read, no full-frame fp32 picture is written).
-    frame_format 'yuv420p' | 'p010' | 'yuv420p10': the same on the other YUV 4:2:0 layouts (ops.yuv420_windows).
+    frame_format 'nv12' | 'yuv420p' | 'p010' | 'yuv420p10': frames [b, 3H/2, W] of the format -> the same crops of the converted
+    frames in ONE launch (ops.yuv420_windows: only the samples under the windows are read, no full-frame fp32 picture is written).
     frame_of: several faces per frame -- windows[m] is cut out of frame frame_of[m], still one launch, [len(windows),3,size,size]."""
-    if frame_format == "nv12":
-        return ops.nv12_windows(u8, (size, size), windows, colorspace, full_range, frame_of=frame_of)
-    if frame_format != "rgb8":                                   # the other YUV 4:2:0 layouts: the same launch on their samples
+    if frame_format != "rgb8":
         return ops.yuv420_windows(u8, frame_format, (size, size), windows, colorspace, full_range, frame_of=frame_of)
     x = ops.unpack_rgb8(u8)
     if windows is not None:
@@ -107,11 +101,9 @@ def crops_of(u8, size, windows=None, frame_format="rgb8", colorspace="bt709", fu
 
 
 def paste_into(full, img, wins, feather, matte, frame_format="rgb8", colorspace="bt709", full_range=False, frame_of=None):
-    """The inverse of crops_of, IN PLACE and in one launch: the rendered fp32 img [M,3,S,S] goes into the uint8 device frames
-    `full` ([b,H,W,3]: ops.paste_windows; 'nv12' [b,3H/2,W]: ops.paste_windows_nv12) where the windows were, blended with the
-    feathered edge and the matte; frame_of as in crops_of.  Returns full."""
-    if frame_format == "nv12":
-        return ops.paste_windows_nv12(full, img, wins, feather, matte, colorspace, full_range, frame_of=frame_of)
+    """The inverse of crops_of, IN PLACE and in one launch: the rendered fp32 img [M,3,S,S] goes into the device frames `full`
+    (uint8 [b,H,W,3]: ops.paste_windows; a YUV 4:2:0 format's [b,3H/2,W]: ops.paste_windows_yuv420) where the windows were,
+    blended with the feathered edge and the matte; frame_of as in crops_of.  Returns full."""
     if frame_format != "rgb8":
         return ops.paste_windows_yuv420(full, frame_format, img, wins, feather, matte, colorspace, full_range, frame_of=frame_of)
     return ops.paste_windows(full, img, wins, feather, matte, frame_of=frame_of)

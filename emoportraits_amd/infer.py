@@ -1052,7 +1052,7 @@ class InferenceWrapper:
         refine=True: every rendered batch goes through the attached stage-2 model (attach_stage2; see animate_frames) and the
         frames come out at its output_size_s2.
         out_format='nv12' (with as_uint8): the frames come out as NV12 uint8 [B, 3S/2, S] -- the fp32 image, refined or not,
-        through ops.pack_nv12 with `colorspace` ('bt709' | 'bt601') and `full_range` (see animate_frames).
+        through ops.pack_yuv420 with `colorspace` ('bt709' | 'bt601') and `full_range` (see animate_frames).
         expression: an ExpressionControls (or a mapping with its fields) applied to target_pose_embeds on the device, see
         animate_frames; like smooth_pose, every rank runs it over the WHOLE stream in one launch and renders its slice, so the
         frames do not depend on batch_size or on the number of ranks.  override= is a ValueError: the expressions are inputs.
@@ -1065,7 +1065,7 @@ class InferenceWrapper:
             raise ValueError("as_uint8=False yields the fp32 image: it has no out_format")
         masks_of, ids = self._preflight(N, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
         if out_format != "rgb8":
-            self._nv12_size(masks_of, out_format)
+            self._yuv420_size(masks_of, out_format)
         ex, hp = self._control_plans(expression, head_pose, N, ids, 'animate', target_theta)
         out_kind = "f32" if not as_uint8 else ("u8" if out_format == "rgb8" else out_format)
         lo, hi = parallel.shard_range(N, self.rank, self.world)
@@ -1110,22 +1110,22 @@ class InferenceWrapper:
             self._source_theta('mix=True' if mix else 'target_theta=False')
         return masks_of, None
 
-    def _nv12_size(self, masks_of, out_format="nv12"):
+    def _yuv420_size(self, masks_of, out_format):
         """YUV 4:2:0 frames have an even side: the size of the image that would be packed, checked before anything is launched"""
         name, S_out = ("image_size", self.cfg["image_size"]) if masks_of is None else ("output_size_s2", self._stage2.cfg["output_size_s2"])
         if S_out % 2:
-            raise ValueError(f"{'NV12' if out_format == 'nv12' else out_format} output needs an even {name}, got {S_out}")
+            raise ValueError(f"{ops.yuv420_name(out_format)} output needs an even {name}, got {S_out}")
 
-    def _render(self, pose, theta, ident, target_theta, masks_of, out, nv12=("bt709", False)):
+    def _render(self, pose, theta, ident, target_theta, masks_of, out, yuv=("bt709", False)):
         """The tail of a batch: the theta each frame is rendered with, the driver pass of the current identity or of the bank
         slots `ident`, stage 2 where masks_of is given -> uint8 [b,S,S,3] (out 'u8'), the fp32 image [b,3,S,S] ('f32') or
-        that image as NV12 uint8 [b,3S/2,S] ('nv12': ops.pack_nv12 with nv12 = (colorspace, full_range)) or in another YUV
-        4:2:0 layout ('yuv420p', 'p010', 'yuv420p10': ops.pack_yuv420, [b,3S/2,S] of the format's dtype)"""
+        that image in a YUV 4:2:0 layout ('nv12', 'yuv420p', 'p010', 'yuv420p10': ops.pack_yuv420 with yuv = (colorspace,
+        full_range), [b,3S/2,S] of the format's dtype)"""
         theta = self._render_theta(theta, ident, target_theta)
         img = self._drive(pose, theta) if ident is None else self._drive_bank(pose, theta, ident)
         if out in frames_mod.YUV420:
             img = img if masks_of is None else self._refine(img, masks_of, "f32")
-            return ops.pack_nv12(img, *nv12) if out == "nv12" else ops.pack_yuv420(img, out, *nv12)
+            return ops.pack_yuv420(img, out, *yuv)
         if masks_of is not None:
             return self._refine(img, masks_of, out)
         return ops.pack_rgb8(img) if out == "u8" else img
@@ -1153,11 +1153,11 @@ class InferenceWrapper:
         embedders['matting']).  One launch (ops.paste_windows / emo_paste_windows_rgb8).
         frames_u8: uint8 [N,Hf,Wf,3], host or device; it is NOT modified (a host tensor is uploaded, a device tensor cloned).
         Returns the device uint8 [N,Hf,Wf,3].  feather = 1/16 of the window is a taste default, not a measured optimum.
-        frame_format='nv12': frames_u8 is NV12 uint8 [N, 3Hf/2, Wf] and so is the result (ops.paste_windows_nv12 /
-        emo_paste_windows_nv12, with `colorspace` and `full_range` as in animate_frames).
+        frame_format='nv12': frames_u8 is NV12 uint8 [N, 3Hf/2, Wf] and so is the result (ops.paste_windows_yuv420 /
+        emo_paste_yuv420, with `colorspace` and `full_range` as in animate_frames).
         faces= instead of windows=: several faces per frame -- faces[i] = the (x_lo, y_lo, side) of frame i in paste order ([]: no
         face), `rendered` and the matte hold one row per face in that order, and the faces of a frame are pasted one over the
-        other, the later one on top, still in one launch (emo_paste_faces_rgb8 / emo_paste_faces_nv12)."""
+        other, the later one on top, still in one launch (emo_paste_faces_rgb8 / emo_paste_yuv420)."""
         frames_mod.check_format(frame_format, colorspace)
         if not isinstance(frames_u8, torch.Tensor):
             raise ValueError("frames must be a uint8 tensor")
@@ -1239,21 +1239,21 @@ class InferenceWrapper:
         frame_format='nv12': the frames are NV12 as video decoders hand them out, uint8 [N, 3H/2, W] (H rows of Y, then H / 2
             rows of interleaved U, V; H and W even; stride 1 along a row and a row pitch >= W, so a [..., :W] view of a padded
             surface is taken as it is), 1.5 bytes per pixel on the bus.  The crop step is then ONE launch
-            (emo_nv12_windows_f32: the bytes under each window converted and resized; no full-frame fp32 picture).
+            (emo_yuv420_crop_f32: the bytes under each window converted and resized; no full-frame fp32 picture).
             colorspace 'bt709' | 'bt601' and full_range (False: Y 16 ... 235, chroma 16 ... 240) say how the bytes are read
             and written (include/emo_hip.h has the arithmetic).
         out_format: None = frame_format; 'rgb8' | 'nv12' asks for the other one (crops only: paste_back returns the uploaded
             frames, so its out_format is frame_format).  NV12 crops are uint8 [b, 3S/2, S]: the fp32 image, refined or not,
-            through emo_pack_nv12 (image_size / output_size_s2 must be even); with paste_back the NV12 frames are pasted in
-            place (emo_paste_windows_nv12).  as_uint8=False has no out_format.  Everything else -- upload-ahead, the ring,
+            through emo_pack_yuv420 (image_size / output_size_s2 must be even); with paste_back the NV12 frames are pasted in
+            place (emo_paste_yuv420).  as_uint8=False has no out_format.  Everything else -- upload-ahead, the ring,
             smooth_pose, identities, the rank sharding, the caller's frames untouched -- is as for rgb8.
         faces= instead of windows= (both: ValueError): several faces per frame.  faces[i] = the (x_lo, y_lo, side) of frame i in
             paste order, [] for a frame without a face, over the whole frame stream.  A batch is a run of whole frames with at
             most batch_size faces and at most batch_size frames (frames.face_spans; a frame with more faces: ValueError before
             anything is launched; batches are not padded).  Its frames are uploaded once, ONE crop launch cuts all its faces
-            out of them (emo_resize2d_faces_f32 / emo_nv12_faces_f32), the networks run on one row per face, and with
+            out of them (emo_resize2d_faces_f32 / emo_yuv420_crop_f32), the networks run on one row per face, and with
             paste_back=True ONE launch pastes the faces of each frame in list order, the later one on top
-            (emo_paste_faces_rgb8 / emo_paste_faces_nv12): what is yielded is (first_frame_index, frames), a batch without a
+            (emo_paste_faces_rgb8 / emo_paste_yuv420): what is yielded is (first_frame_index, frames), a batch without a
             face its frames as they came.  Without paste_back the crops are yielded as (first_face_index, crops), counted over
             the faces of the whole stream; frames without a face yield nothing.  identities= is then one slot per FACE in
             that order, and mix / target_theta=False work per face.  smooth_pose needs identities= and smooth_per_identity=True
@@ -1351,7 +1351,7 @@ class InferenceWrapper:
                 raise ValueError(f"a paste window is smaller than a quarter of the {S_out}-pixel image: downscaling "
                                  f"stops at image_size / 4")
         if out_format != "rgb8" and as_uint8 and not paste_back:
-            self._nv12_size(masks_of, out_format)
+            self._yuv420_size(masks_of, out_format)
         out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else out_format)
         ex, hp = self._control_plans(expression, head_pose, n_rows, ids, where, target_theta, faces)
         host_ring = None if not to_host else (frames_mod.ArenaRing(self.device, ring) if arena and paste_back
@@ -1535,7 +1535,7 @@ class InferenceWrapper:
         batch a list instead of one tensor.  Between the crop and the paste everything is one row per face, so only the two ends
         differ: ONE crop launch reads every face of the batch out of its own frame through a frame table
         (ops.crop_faces_mixed: emo_rgb8_faces_ragged_f32 reads the bytes under the windows only, no full-frame fp32 picture;
-        emo_nv12_faces_ragged_f32), then the steps animate_frames runs (_head_pose, _pose_controls, _expression, _render), and
+        emo_yuv420_crop_ragged_f32), then the steps animate_frames runs (_head_pose, _pose_controls, _expression, _render), and
         with paste_back=True ONE paste launch (ops.paste_faces_mixed).
         streams: a list of mappings, one per stream --
             'frames': uint8 [N_s,H_s,W_s,3] (NV12: [N_s,3H_s/2,W_s]) or an iterable of such chunks, host (ideally pinned) or device;

@@ -785,22 +785,6 @@ def paste_windows(frames_u8, img, windows, feather=0.0, matte=None, frame_of=Non
 NV12_MATRICES = {"bt709": 0, "bt601": 1}
 
 
-def _nv12_planes(nv12, what):
-    """uint8 [N, 3H/2, W] NV12 frames (H rows of Y, then H/2 rows of interleaved U, V; last stride 1, row pitch >= W: a
-    [..., :W] view of a padded surface is taken as it is) -> (Y pointer, UV pointer, pitch, frame stride, N, H, W)"""
-    if nv12.dtype != torch.uint8 or nv12.dim() != 3:
-        raise RuntimeError(f"{what} expects uint8 NV12 frames [N, 3H/2, W]")
-    N, rows, W = nv12.shape
-    if rows % 3 or W % 2 or rows == 0 or W == 0:
-        raise ValueError(f"NV12 frames {tuple(nv12.shape)}: expected [N, 3H/2, W] with H and W even")
-    H = rows // 3 * 2
-    pitch, fstride = (nv12.stride(1), nv12.stride(0)) if N > 0 else (W, rows * W)
-    if nv12.stride(2) != 1 or pitch < W or (N > 1 and fstride < rows * pitch):
-        raise RuntimeError(f"{what}: NV12 frames need stride 1 along a row, a row pitch >= W and frames that do not overlap")
-    base = nv12.data_ptr()
-    return ctypes.c_void_p(base), ctypes.c_void_p(base + H * pitch), pitch, fstride, N, H, W
-
-
 def _nv12_matrix(colorspace):
     if colorspace not in NV12_MATRICES:
         raise ValueError(f"colorspace {colorspace!r}: 'bt709' or 'bt601'")
@@ -808,96 +792,41 @@ def _nv12_matrix(colorspace):
 
 
 def nv12_windows(nv12, size=None, windows=None, colorspace="bt709", full_range=False, frame_of=None):
-    """NV12 frames uint8 [N, 3H/2, W] on the device -> fp32 [N,3,Ho,Wo] in [0,1], ONE launch (emo_nv12_windows_f32): each frame's
+    """NV12 frames uint8 [N, 3H/2, W] on the device -> fp32 [N,3,Ho,Wo] in [0,1], ONE launch (yuv420_windows, layout 0): each frame's
     window (x0, y0, w, h) of the converted frame, resized bicubically to size = (Ho, Wo) and clamped -- bit for bit
     resize2d_windows(..., 'bicubic', clamp01=True) of the whole-frame conversion, which is never written.  windows: a host
     sequence (checked, uploaded), an int32 [N,4] device tensor (a window that leaves the frame gives zeros), or None = the whole
     frame; size None = (H, W), with windows None the plain conversion.  include/emo_hip.h has the definition.
     frame_of (a host sequence of M ints, non-decreasing, inside [0, N)): several faces per frame -- windows has M rows, row m is
-    cut out of frame frame_of[m], and the result has M rows (emo_nv12_faces_f32: the same bits as this op on nv12[frame_of])."""
-    lib = hip.load()
-    y, uv, pitch, fstride, N, H, W = _nv12_planes(nv12, "nv12_windows")
-    matrix = _nv12_matrix(colorspace)
-    Ho, Wo = (H, W) if size is None else size
-    if frame_of is not None and windows is None:
-        raise ValueError("frame_of= needs windows=: one per face")
-    M = N if frame_of is None else len(frame_of)
-    out = torch.empty((M, 3, Ho, Wo), device=nv12.device, dtype=torch.float32)
-    hip.require_cuda_f32(out)                                    # (the frames' device: GPU only, like every op)
-    win, host = (None, None) if windows is None else _windows_arg(windows, M, (W, H), nv12.device, "crop")
-    if frame_of is not None:
-        fof, fof_host = _frame_of_arg(frame_of, N, nv12.device)
-        if M == 0:
-            return out
-        hip.check(lib.emo_nv12_faces_f32(y, uv, pitch, fstride, H, W, hip.ptr(win), hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host),
-                                         hip.ptr(out), M, N, Ho, Wo, matrix, int(bool(full_range)), hip.current_stream()),
-                  "emo_nv12_faces_f32")
-        return out
-    if N == 0:
-        return out
-    hip.check(lib.emo_nv12_windows_f32(y, uv, pitch, fstride, H, W, hip.ptr(win), hip.ptr(host), hip.ptr(out), N, Ho, Wo, matrix,
-                                       int(bool(full_range)), hip.current_stream()), "emo_nv12_windows_f32")
-    return out
+    cut out of frame frame_of[m], and the result has M rows (the same bits as this op on nv12[frame_of])."""
+    return yuv420_windows(nv12, "nv12", size, windows, colorspace, full_range, frame_of)
 
 
 def pack_nv12(img, colorspace="bt709", full_range=False, out=None):
-    """[N,3,H,W] fp32 -> NV12 uint8 [N, 3H/2, W] (emo_pack_nv12: clamp(0,1), the matrix, luma rounded per pixel, chroma the
+    """[N,3,H,W] fp32 -> NV12 uint8 [N, 3H/2, W] (pack_yuv420, layout 0: clamp(0,1), the matrix, luma rounded per pixel, chroma the
     rounded mean of each 2x2 block); H and W even.  out: NV12 frames to write into (a strided view is fine)."""
-    lib = hip.load()
-    hip.require_cuda_f32(img)
-    N, C, H, W = img.shape
-    if C != 3:
-        raise ValueError("expected 3 channels")
-    if H % 2 or W % 2:
-        raise ValueError(f"NV12 needs an even height and width, got {H}x{W}")
-    matrix = _nv12_matrix(colorspace)
-    if out is None:
-        out = torch.empty((N, 3 * H // 2, W), device=img.device, dtype=torch.uint8)
-    y, uv, pitch, fstride, n, h, w = _nv12_planes(out, "pack_nv12")
-    if (n, h, w) != (N, H, W) or out.device != img.device:
-        raise ValueError(f"out {tuple(out.shape)} does not hold {N} NV12 frames of {W}x{H} on the image's device")
-    if N == 0:
-        return out
-    hip.check(lib.emo_pack_nv12(hip.ptr(img), y, uv, pitch, fstride, N, H, W, matrix, int(bool(full_range)), hip.current_stream()),
-              "emo_pack_nv12")
-    return out
+    return pack_yuv420(img, "nv12", colorspace, full_range, out)
 
 
 def paste_windows_nv12(nv12, img, windows, feather=0.0, matte=None, colorspace="bt709", full_range=False, frame_of=None):
-    """paste_windows on NV12 frames uint8 [N, 3Hf/2, Wf], IN PLACE and in one launch (emo_paste_windows_nv12): the resized,
+    """paste_windows on NV12 frames uint8 [N, 3Hf/2, Wf], IN PLACE and in one launch (paste_windows_yuv420, layout 0): the resized,
     clamped image and the blend weight a of paste_windows; luma blended per pixel, each chroma sample under the window with the
     mean of its (up to four) window pixels' weights and weighted chroma (include/emo_hip.h has the definition).  windows as in
     paste_windows.  Bytes outside a window's luma rectangle and its covering chroma rectangle are neither read nor written.
     Returns nv12.
     frame_of: several faces per frame as in paste_windows -- img, matte and windows have M rows, face m goes into frame
-    frame_of[m], the faces of a frame in list order, one launch (emo_paste_faces_nv12)."""
-    lib = hip.load()
-    hip.require_cuda_f32(img, matte)
-    if nv12.device != img.device:
-        raise RuntimeError("paste_windows_nv12 expects the NV12 frames on the images' device")
-    y, uv, pitch, fstride, N, Hf, Wf = _nv12_planes(nv12, "paste_windows_nv12")
-    matrix = _nv12_matrix(colorspace)
-    F, N = N, (N if frame_of is None else len(frame_of))                     # F frames, N rows of img / matte / windows
-    S = _paste_args(img, matte, feather, N, f"frames {tuple(nv12.shape)} and images {tuple(img.shape)}: expected [N,3Hf/2,Wf] and [N,3,S,S]")
-    win, host = _windows_arg(windows, N, (Wf, Hf), img.device, "paste", paste_S=S)
-    if frame_of is not None:
-        fof, fof_host = _frame_of_arg(frame_of, F, img.device)
-        if N == 0:
-            return nv12
-        hip.check(lib.emo_paste_faces_nv12(hip.ptr(img), hip.ptr(matte), hip.ptr(win), hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host),
-                                           y, uv, pitch, fstride, N, F, S, Hf, Wf, float(feather), matrix, int(bool(full_range)),
-                                           hip.current_stream()), "emo_paste_faces_nv12")
-        return nv12
-    if N == 0:
-        return nv12
-    hip.check(lib.emo_paste_windows_nv12(hip.ptr(img), hip.ptr(matte), hip.ptr(win), hip.ptr(host), y, uv, pitch, fstride, N, S, Hf,
-                                         Wf, float(feather), matrix, int(bool(full_range)), hip.current_stream()),
-              "emo_paste_windows_nv12")
-    return nv12
+    frame_of[m], the faces of a frame in list order, one launch."""
+    return paste_windows_yuv420(nv12, "nv12", img, windows, feather, matte, colorspace, full_range, frame_of)
 
 
-# ---- planar and 10-bit YUV 4:2:0 frames (ABI 22): the NV12 ops above on the other sample layouts ------------------------------
+# ---- YUV 4:2:0 frames in the four sample layouts, all through the ABI 22 entry points (NV12 is layout 0; the NV12 entry points
+# of ABI 17 - 19 are the same kernels for C callers) ----------------------------------------------------------------------------
 YUV420_LAYOUTS = {"nv12": 0, "yuv420p": 1, "p010": 2, "yuv420p10": 3}           # frame_format -> the C ABI's layout id
+
+
+def yuv420_name(frame_format):
+    """the format as the messages call it"""
+    return {"nv12": "NV12"}.get(frame_format, frame_format)
 
 
 def yuv420_dtype(frame_format):
@@ -916,20 +845,20 @@ def yuv420_geometry(t, frame_format, what):
     H/2 x W/2 samples each straight after Y -- ffmpeg's rawvideo layout; with H/2 odd the V plane begins mid-row of the tensor"""
     if frame_format not in YUV420_LAYOUTS:
         raise ValueError(f"frame_format={frame_format!r}: one of {', '.join(YUV420_LAYOUTS)}")
-    dt = yuv420_dtype(frame_format)
+    dt, fmt = yuv420_dtype(frame_format), yuv420_name(frame_format)
     name = str(dt).replace("torch.", "")
     if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() < 2:
-        raise ValueError(f"{what}: {frame_format} frames are {name} [N, 3H/2, W]")
+        raise ValueError(f"{what}: {fmt} frames are {name} [N, 3H/2, W]")
     rows, W = t.shape[-2:]
     if rows % 3 or W % 2 or rows == 0 or W == 0:
-        raise ValueError(f"{what}: {frame_format} frames {tuple(t.shape)}: expected {name} [N, 3H/2, W] with H and W even")
+        raise ValueError(f"{what}: {fmt} frames {tuple(t.shape)}: expected {name} [N, 3H/2, W] with H and W even")
     pitch = t.stride(-2)
     if yuv420_planar(frame_format):
         if t.stride(-1) != 1 or pitch != W:
-            raise ValueError(f"{what}: {frame_format} frames need dense rows (stride 1 along a row, a row stride of W): "
+            raise ValueError(f"{what}: {fmt} frames need dense rows (stride 1 along a row, a row stride of W): "
                              f"the chroma planes lie straight after Y")
     elif t.stride(-1) != 1 or pitch < W:
-        raise ValueError(f"{what}: {frame_format} frames need stride 1 along a row and a row pitch >= W")
+        raise ValueError(f"{what}: {fmt} frames need stride 1 along a row and a row pitch >= W")
     return rows // 3 * 2, W, pitch * t.element_size()
 
 
@@ -937,12 +866,12 @@ def _yuv420_planes(t, frame_format, what):
     """[N, 3H/2, W] frames of the format -> (layout id, Y, U, V pointers, luma pitch, chroma pitch, frame stride -- in bytes --
     N, H, W), as the ABI 22 entry points take them"""
     if not isinstance(t, torch.Tensor) or t.dim() != 3:
-        raise ValueError(f"{what}: {frame_format} frames are [N, 3H/2, W]")
+        raise ValueError(f"{what}: {yuv420_name(frame_format)} frames are [N, 3H/2, W]")
     H, W, pitch = yuv420_geometry(t, frame_format, what)
     N, B = t.shape[0], t.element_size()
     fstride = t.stride(0) * B if N > 0 else 3 * H // 2 * pitch
     if N > 1 and fstride < 3 * H // 2 * pitch:
-        raise ValueError(f"{what}: {frame_format} frames must not overlap")
+        raise ValueError(f"{what}: {yuv420_name(frame_format)} frames must not overlap")
     base = t.data_ptr()
     u = base + H * pitch
     if yuv420_planar(frame_format):
@@ -954,10 +883,10 @@ def _yuv420_planes(t, frame_format, what):
 
 
 def yuv420_windows(frames, frame_format, size=None, windows=None, colorspace="bt709", full_range=False, frame_of=None):
-    """nv12_windows on any of the four YUV 4:2:0 layouts (emo_yuv420_crop_f32, ONE launch): frames [N, 3H/2, W] of the format's
-    dtype on the device (yuv420_geometry has the forms) -> fp32 [N,3,Ho,Wo] in [0,1]; size, windows, colorspace, full_range and
-    frame_of as in nv12_windows.  10-bit codes: 'p010' the high ten bits of a word, 'yuv420p10' the low ten; the other six
-    bits are ignored.  include/emo_hip.h (ABI 22) has the definition."""
+    """The crop nv12_windows describes, on any of the four YUV 4:2:0 layouts (emo_yuv420_crop_f32, ONE launch, windows and faces
+    form alike): frames [N, 3H/2, W] of the format's dtype on the device (yuv420_geometry has the forms) -> fp32 [N,3,Ho,Wo] in
+    [0,1]; size, windows, colorspace, full_range and frame_of as there.  10-bit codes: 'p010' the high ten bits of a word,
+    'yuv420p10' the low ten; the other six bits are ignored.  include/emo_hip.h (ABI 22) has the definition."""
     lib = hip.load()
     layout, y, u, v, pitch_y, pitch_c, fstride, N, H, W = _yuv420_planes(frames, frame_format, "yuv420_windows")
     matrix = _nv12_matrix(colorspace)
@@ -978,15 +907,16 @@ def yuv420_windows(frames, frame_format, size=None, windows=None, colorspace="bt
 
 
 def pack_yuv420(img, frame_format, colorspace="bt709", full_range=False, out=None):
-    """pack_nv12 into any of the four YUV 4:2:0 layouts (emo_pack_yuv420): [N,3,H,W] fp32 -> frames [N, 3H/2, W] of the format's
-    dtype, H and W even; a written sample holds its code and zeros in the format's unused bits.  out: frames to write into."""
+    """The packing pack_nv12 describes, into any of the four YUV 4:2:0 layouts (emo_pack_yuv420): [N,3,H,W] fp32 -> frames
+    [N, 3H/2, W] of the format's dtype, H and W even; a written sample holds its code and zeros in the format's unused bits.
+    out: frames to write into."""
     lib = hip.load()
     hip.require_cuda_f32(img)
     N, C, H, W = img.shape
     if C != 3:
         raise ValueError("expected 3 channels")
     if H % 2 or W % 2:
-        raise ValueError(f"{frame_format} needs an even height and width, got {H}x{W}")
+        raise ValueError(f"{yuv420_name(frame_format)} needs an even height and width, got {H}x{W}")
     if frame_format not in YUV420_LAYOUTS:
         raise ValueError(f"frame_format={frame_format!r}: one of {', '.join(YUV420_LAYOUTS)}")
     matrix = _nv12_matrix(colorspace)
@@ -994,7 +924,7 @@ def pack_yuv420(img, frame_format, colorspace="bt709", full_range=False, out=Non
         out = torch.empty((N, 3 * H // 2, W), device=img.device, dtype=yuv420_dtype(frame_format))
     layout, y, u, v, pitch_y, pitch_c, fstride, n, h, w = _yuv420_planes(out, frame_format, "pack_yuv420")
     if (n, h, w) != (N, H, W) or out.device != img.device:
-        raise ValueError(f"out {tuple(out.shape)} does not hold {N} {frame_format} frames of {W}x{H} on the image's device")
+        raise ValueError(f"out {tuple(out.shape)} does not hold {N} {yuv420_name(frame_format)} frames of {W}x{H} on the image's device")
     if N == 0:
         return out
     hip.check(lib.emo_pack_yuv420(layout, hip.ptr(img), y, u, v, pitch_y, pitch_c, fstride, N, H, W, matrix, int(bool(full_range)),
@@ -1004,8 +934,8 @@ def pack_yuv420(img, frame_format, colorspace="bt709", full_range=False, out=Non
 
 def paste_windows_yuv420(frames, frame_format, img, windows, feather=0.0, matte=None, colorspace="bt709", full_range=False,
                          frame_of=None):
-    """paste_windows_nv12 on any of the four YUV 4:2:0 layouts, IN PLACE and in one launch (emo_paste_yuv420); every argument as
-    there.  A sample outside the windows' luma rectangles and their covering chroma rectangles keeps all its bits; a sample
+    """The paste paste_windows_nv12 describes, on any of the four YUV 4:2:0 layouts, IN PLACE and in one launch (emo_paste_yuv420,
+    windows and faces form alike); every argument as there.  A sample outside the windows' luma rectangles and their covering chroma rectangles keeps all its bits; a sample
     inside comes out as its code with zeros in the format's unused bits.  Returns frames."""
     lib = hip.load()
     hip.require_cuda_f32(img, matte)
@@ -1026,42 +956,35 @@ def paste_windows_yuv420(frames, frame_format, img, windows, feather=0.0, matte=
 
 
 def _mixed_rows(frames, frame_format, what):
-    """frames: a list of tensors, one per frame, uint8 [H,W,3] (rgb8) or NV12 [3H/2,W], all on one device, stride 1 along a row
-    (a row-pitch view is taken as it is) -> [(address, pitch in bytes, H, W)] of the CHECKED tensors"""
-    if frame_format != "rgb8" and frame_format not in YUV420_LAYOUTS:
+    """frames: a list of tensors, one per frame, uint8 [H,W,3] (rgb8) or [3H/2,W] of a YUV 4:2:0 layout (yuv420_geometry has the
+    forms), all on one device, stride 1 along a row (a row-pitch view is taken as it is where the layout allows one) ->
+    [(address, pitch in bytes, H, W)] of the CHECKED tensors"""
+    rgb = frame_format == "rgb8"
+    if not rgb and frame_format not in YUV420_LAYOUTS:
         raise ValueError(f"frame_format={frame_format!r}: 'rgb8', {', '.join(repr(f) for f in YUV420_LAYOUTS)}")
     if not isinstance(frames, (list, tuple)) or not frames:
         raise ValueError(f"{what} takes a non-empty list of frame tensors, one per frame")
     rows = []
-    if frame_format not in ("rgb8", "nv12"):                                    # (ABI 22: pitches in bytes, planar rows dense)
-        for i, t in enumerate(frames):
-            if not isinstance(t, torch.Tensor) or t.device != frames[0].device:
-                raise RuntimeError(f"{what}: frame {i} must be a tensor on the device of frame 0")
-            if t.dim() != 2:
-                raise ValueError(f"{what}: frame {i} is {tuple(t.shape)}, expected {frame_format} [3H/2, W] with H and W even")
-            H, W, pitch = yuv420_geometry(t, frame_format, f"{what}: frame {i}")
-            rows.append((t.data_ptr(), pitch, H, W))
-        return rows
     for i, t in enumerate(frames):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device != frames[0].device:
-            raise RuntimeError(f"{what}: frame {i} must be a uint8 tensor on the device of frame 0")
-        if frame_format == "rgb8":
+        if not isinstance(t, torch.Tensor) or t.device != frames[0].device or (rgb and t.dtype != torch.uint8):
+            raise RuntimeError(f"{what}: frame {i} must be a {'uint8 ' if rgb else ''}tensor on the device of frame 0")
+        if rgb:
             if t.dim() != 3 or t.shape[2] != 3 or 0 in t.shape:
                 raise ValueError(f"{what}: frame {i} is {tuple(t.shape)}, expected uint8 [H,W,3]")
-            (H, W), row_bytes, unit = t.shape[:2], 3 * t.shape[1], (t.stride(2) == 1 and t.stride(1) == 3)
+            H, W, pitch = t.shape[0], t.shape[1], t.stride(0)
+            if t.stride(2) != 1 or t.stride(1) != 3 or pitch < 3 * W:
+                raise RuntimeError(f"{what}: frame {i} needs stride 1 along a row and a row pitch of at least the row's {3 * W} bytes")
         else:
-            if t.dim() != 2 or t.shape[0] % 3 or t.shape[1] % 2 or 0 in t.shape:
-                raise ValueError(f"{what}: frame {i} is {tuple(t.shape)}, expected NV12 uint8 [3H/2, W] with H and W even")
-            H, W, row_bytes, unit = t.shape[0] // 3 * 2, t.shape[1], t.shape[1], t.stride(1) == 1
-        if not unit or t.stride(0) < row_bytes:
-            raise RuntimeError(f"{what}: frame {i} needs stride 1 along a row and a row pitch of at least the row's {row_bytes} bytes")
-        rows.append((t.data_ptr(), t.stride(0), H, W))
+            if t.dim() != 2:
+                raise ValueError(f"{what}: frame {i} is {tuple(t.shape)}, expected {yuv420_name(frame_format)} [3H/2, W] with H and W even")
+            H, W, pitch = yuv420_geometry(t, frame_format, f"{what}: frame {i}")
+        rows.append((t.data_ptr(), pitch, H, W))
     return rows
 
 
 def frame_table(frames, frame_format="rgb8"):
     """The frame table of the mixed-size entry points (ABI 19) for a list of frame tensors, one per frame, each uint8 [H_i,W_i,3]
-    or NV12 [3H_i/2,W_i] on the device: int64 [F,4] rows (byte address of the first row, row pitch in bytes, H, W) ->
+    or [3H_i/2,W_i] of a YUV 4:2:0 layout on the device: int64 [F,4] rows (byte address of the first row, row pitch in bytes, H, W) ->
     (device tensor, host tensor).  The rows are raw device addresses, so they are only ever formed here, from tensors whose
     device, dtype, dimensions, row stride and pitch have been checked; the caller keeps the tensors alive while the table is
     in use.  crop_faces_mixed / paste_faces_mixed build their own: no op takes a ready-made table."""
@@ -1082,11 +1005,11 @@ def _mixed_windows(windows, frame_of, table_host, device, S, what):
 
 def crop_faces_mixed(frames, size, windows, frame_of, frame_format="rgb8", colorspace="bt709", full_range=False):
     """The crops of M faces out of frames of DIFFERENT sizes in ONE launch (emo_rgb8_faces_ragged_f32 /
-    emo_nv12_faces_ragged_f32): frames a list of device tensors, one per frame, uint8 [H_i,W_i,3] or NV12 [3H_i/2,W_i] (row-pitch
-    views are taken as they are); windows[m] = (x0, y0, w, h) is cut out of frames[frame_of[m]] (frame_of a host sequence,
+    emo_yuv420_crop_ragged_f32): frames a list of device tensors, one per frame, uint8 [H_i,W_i,3] or [3H_i/2,W_i] of a YUV 4:2:0
+    layout (row-pitch views are taken as they are where the layout allows them); windows[m] = (x0, y0, w, h) is cut out of frames[frame_of[m]] (frame_of a host sequence,
     non-decreasing), resized bicubically to size (an int or (Ho, Wo)) and clamped -> fp32 [M,3,Ho,Wo].  rgb8: bit for bit
     unpack_rgb8 + resize2d_windows(..., 'bicubic', clamp01=True, frame_of=) of each frame, but only the bytes under the windows
-    are read: no full-frame fp32 picture.  nv12: nv12_windows(frame_of=)'s arithmetic.  windows: a host sequence (checked
+    are read: no full-frame fp32 picture.  YUV 4:2:0: yuv420_windows(frame_of=)'s arithmetic.  windows: a host sequence (checked
     against each face's own frame, ValueError) or an int32 [M,4] device tensor (a window that leaves its frame gives zeros).
     The frame table is built here from the checked tensors (frame_table)."""
     lib = hip.load()
@@ -1102,14 +1025,10 @@ def crop_faces_mixed(frames, size, windows, frame_of, frame_format="rgb8", color
     if M == 0:
         return out
     table = table_host.to(device, non_blocking=True)
-    if frame_format not in ("rgb8", "nv12"):
+    if frame_format != "rgb8":
         hip.check(lib.emo_yuv420_crop_ragged_f32(YUV420_LAYOUTS[frame_format], hip.ptr(table), hip.ptr(table_host), hip.ptr(win),
                                                  hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host), hip.ptr(out), M, F, Ho, Wo, matrix,
                                                  int(bool(full_range)), hip.current_stream()), "emo_yuv420_crop_ragged_f32")
-    elif frame_format == "nv12":
-        hip.check(lib.emo_nv12_faces_ragged_f32(hip.ptr(table), hip.ptr(table_host), hip.ptr(win), hip.ptr(host), hip.ptr(fof),
-                                                hip.ptr(fof_host), hip.ptr(out), M, F, Ho, Wo, matrix, int(bool(full_range)),
-                                                hip.current_stream()), "emo_nv12_faces_ragged_f32")
     else:
         hip.check(lib.emo_rgb8_faces_ragged_f32(hip.ptr(table), hip.ptr(table_host), hip.ptr(win), hip.ptr(host), hip.ptr(fof),
                                                 hip.ptr(fof_host), hip.ptr(out), M, F, Ho, Wo, hip.current_stream()),
@@ -1119,8 +1038,8 @@ def crop_faces_mixed(frames, size, windows, frame_of, frame_format="rgb8", color
 
 def paste_faces_mixed(frames, img, windows, frame_of, feather=0.0, matte=None, frame_format="rgb8", colorspace="bt709",
                       full_range=False):
-    """paste_windows(frame_of=) / paste_windows_nv12(frame_of=) into frames of DIFFERENT sizes, IN PLACE and in ONE launch
-    (emo_paste_faces_ragged_rgb8 / emo_paste_faces_ragged_nv12): frames as in crop_faces_mixed, img [M,3,S,S] fp32, matte
+    """paste_windows(frame_of=) / paste_windows_yuv420(frame_of=) into frames of DIFFERENT sizes, IN PLACE and in ONE launch
+    (emo_paste_faces_ragged_rgb8 / emo_paste_ragged_yuv420): frames as in crop_faces_mixed, img [M,3,S,S] fp32, matte
     [M,1,S,S] or None; face m goes into frames[frame_of[m]] where its square window is, the faces of a frame in list order, the
     later one on top.  windows: a host sequence, checked against each face's OWN frame before anything is launched (inside it,
     square, side >= S / 4: ValueError), or an int32 [M,4] device tensor (a window that fails those checks against its frame is
@@ -1141,15 +1060,11 @@ def paste_faces_mixed(frames, img, windows, frame_of, feather=0.0, matte=None, f
     if M == 0:
         return frames
     table = table_host.to(device, non_blocking=True)
-    if frame_format not in ("rgb8", "nv12"):
+    if frame_format != "rgb8":
         hip.check(lib.emo_paste_ragged_yuv420(YUV420_LAYOUTS[frame_format], hip.ptr(img), hip.ptr(matte), hip.ptr(table),
                                               hip.ptr(table_host), hip.ptr(win), hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host), M, F,
                                               S, float(feather), matrix, int(bool(full_range)), hip.current_stream()),
                   "emo_paste_ragged_yuv420")
-    elif frame_format == "nv12":
-        hip.check(lib.emo_paste_faces_ragged_nv12(hip.ptr(img), hip.ptr(matte), hip.ptr(table), hip.ptr(table_host), hip.ptr(win),
-                                                  hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host), M, F, S, float(feather), matrix,
-                                                  int(bool(full_range)), hip.current_stream()), "emo_paste_faces_ragged_nv12")
     else:
         hip.check(lib.emo_paste_faces_ragged_rgb8(hip.ptr(img), hip.ptr(matte), hip.ptr(table), hip.ptr(table_host), hip.ptr(win),
                                                   hip.ptr(host), hip.ptr(fof), hip.ptr(fof_host), M, F, S, float(feather),

@@ -16,7 +16,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+from counting_lib import CountingLib as _Lib  # noqa: E402
 
 
 @pytest.fixture(scope="module", params=[False, True], ids=["loop", "threads"])
@@ -192,25 +194,6 @@ def test_the_entry_point_is_in_the_abi_table():
 
 
 # ---- animate(expression=) on the recorder rig of tests/test_pose_controls_emul.py ------------------------------------------------
-class _Lib:
-    """the host-compiled stream library presented as the package's, with hip.SIGNATURES' argument types; counts calls"""
-
-    def __init__(self, lib):
-        from emoportraits_amd import hip
-        self._lib, self._sig, self._res, self.calls = lib, hip.SIGNATURES, hip._RESTYPES, {}
-
-    def __getattr__(self, name):
-        if name.startswith("_"):
-            raise AttributeError(name)
-        fn = getattr(self._lib, name)
-        fn.argtypes, fn.restype = self._sig[name], self._res.get(name, ctypes.c_int)
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
 E5 = 5            # the width of the recorder rig's `pose` rows
 
 

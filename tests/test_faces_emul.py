@@ -29,6 +29,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+from counting_lib import CountingLib as _Lib  # noqa: E402
 import emulibs  # noqa: E402
 import faces_reference as R  # noqa: E402
 import nv12_reference as NV  # noqa: E402
@@ -36,6 +37,10 @@ import paste_back_reference as PB  # noqa: E402
 
 NEW = ("emo_resize2d_faces_f32", "emo_nv12_faces_f32", "emo_paste_faces_rgb8", "emo_paste_faces_nv12")
 OLD = ("emo_resize2d_windows_f32", "emo_nv12_windows_f32", "emo_paste_windows_rgb8", "emo_paste_windows_nv12")
+# what the Python layer launches: rgb8 the entry points above, NV12 the ABI 22 crop and paste, which serve both forms under one name
+# -- the facade records the form of every call (counting_lib: frame_of null or not)
+RUN_NEW = {"rgb8": (NEW[0], NEW[2]), "nv12": ("emo_yuv420_crop_f32", "emo_paste_yuv420")}
+RUN_OLD = {"rgb8": (OLD[0], OLD[2]), "nv12": RUN_NEW["nv12"]}
 MODE = ("bt601", True)                                   # (colorspace, full_range) of the NV12 cases
 MATRIX = (NV.MATRIX_ID[MODE[0]], int(MODE[1]))
 
@@ -374,25 +379,6 @@ def test_gather_rows():
 
 
 # ---- host logic on CPU tensors ---------------------------------------------------------------------------------------------
-class _Lib:
-    """the host-compiled stream library behind emoportraits_amd.hip's table of signatures; counts the calls"""
-
-    def __init__(self, lib):
-        from emoportraits_amd import hip
-        self._lib, self._sig, self.calls = lib, hip.SIGNATURES, {}
-
-    def __getattr__(self, name):
-        if name.startswith("_") or name == "calls":
-            raise AttributeError(name)
-        fn = getattr(self._lib, name)
-        fn.argtypes, fn.restype = self._sig[name], ctypes.c_int
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
 @pytest.fixture()
 def wrapper(monkeypatch, lib):
     """an InferenceWrapper on CPU tensors: the library the host-compiled one, the networks stand-ins (the driver pass a seeded
@@ -453,7 +439,8 @@ def test_ops_take_frame_of_on_cpu_tensors(wrapper, lib, rgb, nv12):
     assert torch.equal(ops.nv12_windows(nv, (R.S, R.S), sq, *MODE, frame_of=R.FRAME_OF),
                        ops.nv12_windows(nv[R.FRAME_OF].contiguous(), (R.S, R.S), sq, *MODE))
     assert wrapper.lib.calls == {"emo_paste_faces_rgb8": 1, "emo_resize2d_faces_f32": 1, "emo_resize2d_windows_f32": 1,
-                                 "emo_paste_faces_nv12": 1, "emo_nv12_faces_f32": 1, "emo_nv12_windows_f32": 1}
+                                 "emo_paste_yuv420": 1, "emo_yuv420_crop_f32": 2}
+    assert wrapper.lib.forms == {"emo_paste_yuv420": ["faces"], "emo_yuv420_crop_f32": ["faces", "windows"]}
     # no face at all: nothing to launch
     assert ops.paste_windows(work[:0].reshape(0, 1, 1, 3), img[:0], [], frame_of=[]).shape[0] == 0
     assert ops.nv12_windows(nv, (R.S, R.S), [], frame_of=[]).shape == (0, 3, R.S, R.S)
@@ -476,7 +463,7 @@ def test_wrapper_paste_back_takes_faces(wrapper, lib, rgb, nv12, fmt):
     before = frames.clone()
     got = wrapper.paste_back(frames, img, faces=R.FACES, matte=matte, **kw)
     assert torch.equal(got, want) and torch.equal(frames, before) and got.data_ptr() != frames.data_ptr()
-    assert wrapper.lib.calls == {"emo_paste_faces_rgb8" if fmt == "rgb8" else "emo_paste_faces_nv12": 1}
+    assert wrapper.lib.calls == {RUN_NEW[fmt][1]: 1} and wrapper.lib.forms == ({} if fmt == "rgb8" else {RUN_NEW[fmt][1]: ["faces"]})
     for bad in (dict(windows=R.WINDOWS[:4], faces=R.FACES), dict(), dict(faces=R.FACES[:3])):
         with pytest.raises(ValueError, match="faces"):
             wrapper.paste_back(frames, img, **bad, **kw)
@@ -495,8 +482,8 @@ def test_animate_frames_with_faces_is_paste_back_of_its_own_renders(wrapper, lib
     got = list(w.animate_frames(frames, batch_size=4, faces=faces, to_host=False, paste_back=True, feather=0.25,
                                 paste_matte=lambda img: matte[:img.shape[0]], **kw))
     assert [b0 for b0, _ in got] == [0, 2, 6, 10] and [t.shape[0] for _, t in got] == [2, 4, 4, 2]
-    crop, paste = ("emo_resize2d_faces_f32", "emo_paste_faces_rgb8") if fmt == "rgb8" else ("emo_nv12_faces_f32", "emo_paste_faces_nv12")
-    assert w.lib.calls == {crop: 3, paste: 3}
+    crop, paste = RUN_NEW[fmt]
+    assert w.lib.calls == {crop: 3, paste: 3} and w.lib.forms == ({} if fmt == "rgb8" else {crop: ["faces"] * 3, paste: ["faces"] * 3})
     assert w.uploads == [(0, 2), (2, 6), (6, 10), (10, 12)] and [c.shape[0] for c in w.crops] == [2, 4, 1]
     renders, spans = list(w.driven), [(0, 2), (2, 6), (10, 12)]
     want = frames.clone()
@@ -511,6 +498,7 @@ def test_animate_frames_with_faces_is_paste_back_of_its_own_renders(wrapper, lib
     got = list(w.animate_frames(frames, batch_size=4, faces=faces, to_host=False, **kw))
     assert [m0 for m0, _ in got] == [0, 2, 6] and [t.shape[0] for _, t in got] == [2, 4, 1]
     assert w.uploads == spans and w.lib.calls[crop] == 3 and paste not in w.lib.calls
+    assert w.lib.forms == ({} if fmt == "rgb8" else {crop: ["faces"] * 3})
 
 
 def test_animate_frames_checks_its_faces_arguments_before_any_launch(wrapper, rgb):
@@ -547,7 +535,8 @@ def _renamed(calls):
 @pytest.mark.parametrize("fmt", ["rgb8", "nv12"])
 def test_windows_is_faces_with_one_face_per_frame(wrapper, rgb, nv12, fmt, paste, bank):
     """animate_frames(windows=W) and animate_frames(faces=[[w] for w in W]) are one loop: equal indices, equal tensors, and the
-    same launches but for the entry points' names -- the per-frame ones for windows=, the *_faces_* ones for faces=.  5 frames at
+    same launches but for the entry points' names -- the per-frame ones for windows=, the *_faces_* ones for faces= -- or, NV12, but
+    for the form of the ABI 22 entry points' calls: frame_of null for windows=, given for faces=.  5 frames at
     batch_size 2: three spans, the last a tail.  With a bank: identities, mix and the per-identity smooth_pose on the way, and the
     thetas and slots the driver pass receives are equal too."""
     frames, _, matte = _inputs(rgb, nv12, fmt, "noise")
@@ -572,13 +561,16 @@ def test_windows_is_faces_with_one_face_per_frame(wrapper, rgb, nv12, fmt, paste
         w.reset_pose_state()
         seen.clear()
         got = [(i, t.clone()) for i, t in w.animate_frames(frames, batch_size=2, to_host=False, **how, **kw)]
-        runs.append((got, dict(w.lib.calls), list(w.uploads), list(seen)))
-    (got_w, calls_w, up_w, seen_w), (got_f, calls_f, up_f, seen_f) = runs
+        runs.append((got, dict(w.lib.calls), list(w.uploads), list(seen), {k: list(v) for k, v in w.lib.forms.items()}))
+    (got_w, calls_w, up_w, seen_w, forms_w), (got_f, calls_f, up_f, seen_f, forms_f) = runs
     assert [i for i, _ in got_w] == [i for i, _ in got_f] == [0, 2, 4] and [t.shape[0] for _, t in got_w] == [2, 2, 1]
     assert all(torch.equal(a, b) for (_, a), (_, b) in zip(got_w, got_f))
-    crop, pasted = (OLD[0], OLD[2]) if fmt == "rgb8" else (OLD[1], OLD[3])
+    crop, pasted = RUN_OLD[fmt]
     assert calls_w[crop] == 3 and calls_w.get(pasted, 0) == (3 if paste else 0)
     assert not set(calls_w) & set(NEW) and not set(calls_f) & set(OLD) and _renamed(calls_f) == calls_w
+    n_of = {crop: 3, pasted: 3} if paste else {crop: 3}                          # NV12: the form of every one of those calls
+    assert forms_w == ({} if fmt == "rgb8" else {k: ["windows"] * n for k, n in n_of.items()})
+    assert forms_f == ({} if fmt == "rgb8" else {k: ["faces"] * n for k, n in n_of.items()})
     # smooth_pose: the crops of the head-pose pass stay resident, and only a paste needs the frames a second time
     assert up_w == up_f == [(0, 2), (2, 4), (4, 5)] * (2 if bank and paste else 1)
     assert len(seen_w) == len(seen_f) == (3 if bank else 0)

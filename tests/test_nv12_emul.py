@@ -25,10 +25,12 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+from counting_lib import CountingLib as _Lib  # noqa: E402
 import emulibs  # noqa: E402
 import nv12_reference as R  # noqa: E402
+import yuv420_reference as Y  # noqa: E402
 
-GUARD, FILL = 64, 0xA5
+FILL = Y.FILL
 F64, F32 = torch.float64, torch.float32
 
 
@@ -59,26 +61,22 @@ def _w4(wins):
     return np.ascontiguousarray([(w[0], w[1], w[2], w[3] if len(w) > 3 else w[2]) for w in wins], dtype=np.int32)
 
 
-class Surface:
-    """N NV12 frames [rows, W] in one buffer: GUARD bytes in front and behind, rows `pitch` apart, all padding = FILL"""
+class Surface(Y.Surface):
+    """N NV12 frames [rows, W] in one buffer (yuv420_reference.Surface, layout nv12, host memory): GUARD bytes in front and behind,
+    rows `pitch` apart, all padding = FILL"""
 
     def __init__(self, n, rows, w, pitch=None, frames=None):
-        self.n, self.rows, self.w, self.pitch = n, rows, w, pitch or w
-        self.raw = np.full(2 * GUARD + n * rows * self.pitch, FILL, np.uint8)
-        self.view = self.raw[GUARD:GUARD + n * rows * self.pitch].reshape(n, rows, self.pitch)
-        if frames is not None:
-            self.view[:, :, :w] = frames.numpy()
-        self.h = rows // 3 * 2
+        super().__init__(Y.HostMemory(), "nv12", n, rows // 3 * 2, w, pad=(pitch or w) - w, arr=None if frames is None else frames.numpy())
 
     def args(self):
-        base = self.raw.ctypes.data + GUARD
-        return ctypes.c_void_p(base), ctypes.c_void_p(base + self.h * self.pitch), self.pitch, self.rows * self.pitch
+        y, uv, _, pitch, _, fstride = super().args()
+        return y, uv, pitch, fstride
 
     def frames(self):
-        return torch.from_numpy(self.view[:, :, :self.w].copy())
+        return torch.from_numpy(self.read()[0])
 
     def padding_intact(self):
-        return bool((self.raw[:GUARD] == FILL).all() and (self.raw[-GUARD:] == FILL).all() and (self.view[:, :, self.w:] == FILL).all())
+        return self.read()[1]
 
 
 def nv12_windows(lib, nv12, wins, size, mode, host_windows=True, pitch=None):
@@ -353,25 +351,6 @@ def test_the_nv12_entry_points_are_in_the_abi_table():
 
 
 # ---- host logic on CPU tensors ---------------------------------------------------------------------------------------------
-class _Lib:
-    """the host-compiled stream library behind emoportraits_amd.hip's table of signatures; counts the calls"""
-
-    def __init__(self, lib):
-        from emoportraits_amd import hip
-        self._lib, self._sig, self.calls = lib, hip.SIGNATURES, {}
-
-    def __getattr__(self, name):
-        if name.startswith("_") or name == "calls":
-            raise AttributeError(name)
-        fn = getattr(self._lib, name)
-        fn.argtypes, fn.restype = self._sig[name], ctypes.c_int
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
 def _image(k, b):
     """what the stubbed driver pass returns for its k-th call"""
     return torch.rand(b, 3, R.S, R.S, generator=torch.Generator().manual_seed(40 + k)) * 1.2 - 0.1
@@ -451,7 +430,7 @@ def test_ops_on_cpu_tensors_take_a_padded_view(wrapper, lib, small):
         ops.nv12_windows(work[:, :, :479], (R.S, R.S), sq)
     with pytest.raises(ValueError, match="3H/2"):
         ops.nv12_windows(work[:, :404], (R.S, R.S), sq)
-    with pytest.raises(RuntimeError, match="pitch"):
+    with pytest.raises(ValueError, match="pitch"):
         ops.nv12_windows(work[:, :, ::2], (R.S, R.S), sq)
     assert wrapper.lib.calls == {} and torch.equal(work, nv12)
 
@@ -463,7 +442,7 @@ def test_wrapper_paste_back_on_nv12_frames(wrapper, lib, small):
     before = nv12.clone()
     got = wrapper.paste_back(nv12, img, R.WINDOWS, matte=matte, frame_format="nv12", colorspace=mode[0], full_range=mode[1])
     assert torch.equal(got, want) and torch.equal(nv12, before) and got.data_ptr() != nv12.data_ptr()
-    assert wrapper.lib.calls == {"emo_paste_windows_nv12": 1}
+    assert wrapper.lib.calls == {"emo_paste_yuv420": 1} and wrapper.lib.forms == {"emo_paste_yuv420": ["windows"]}
     with pytest.raises(ValueError, match="NV12"):
         wrapper.paste_back(nv12[:, :404], img, R.WINDOWS, frame_format="nv12")
     with pytest.raises(ValueError, match="frame_format"):
@@ -472,16 +451,17 @@ def test_wrapper_paste_back_on_nv12_frames(wrapper, lib, small):
 
 @pytest.mark.parametrize("out_format", [None, "rgb8"])
 def test_animate_frames_nv12_runs_one_crop_launch_per_batch(wrapper, lib, small, out_format):
-    """frames in NV12: per batch ONE emo_nv12_windows_f32 and none of the rgb8 ends; the crops the networks see are
-    ops.nv12_windows' and what is yielded is emo_pack_nv12 (or, out_format='rgb8', emo_pack_rgb8) of the driver pass' images"""
+    """frames in NV12: per batch ONE emo_yuv420_crop_f32 in its one-window-per-frame form and none of the rgb8 ends; the crops the
+    networks see are ops.nv12_windows' and what is yielded is emo_pack_yuv420 (or, out_format='rgb8', emo_pack_rgb8) of the driver
+    pass' images"""
     from emoportraits_amd import ops
     nv12 = small["noise"][0]
     w, mode = wrapper, ("bt601", False)
     kw = dict(frame_format="nv12", colorspace=mode[0], full_range=mode[1])
     got = list(w.animate_frames(nv12, batch_size=4, windows=R.WINDOWS_ODD, to_host=False, out_format=out_format, **kw))
     assert [b0 for b0, _ in got] == [0, 4] and [t.shape[0] for _, t in got] == [4, 2]
-    pack_name = "emo_pack_nv12" if out_format is None else "emo_pack_rgb8"
-    assert w.lib.calls == {"emo_nv12_windows_f32": 2, pack_name: 2}
+    pack_name = "emo_pack_yuv420" if out_format is None else "emo_pack_rgb8"
+    assert w.lib.calls == {"emo_yuv420_crop_f32": 2, pack_name: 2} and w.lib.forms == {"emo_yuv420_crop_f32": ["windows"] * 2}
     rc, crops = nv12_windows(lib, nv12, R.WINDOWS_ODD, (R.S, R.S), mode)
     assert torch.equal(torch.cat(w.crops), crops)
     images = torch.cat(w.driven)
@@ -497,7 +477,8 @@ def test_animate_frames_nv12_paste_back_is_paste_back_of_the_rendered_images(wra
     before = nv12.clone()
     got = list(w.animate_frames(nv12, batch_size=4, windows=R.WINDOWS, to_host=False, paste_back=True, feather=0.25,
                                 paste_matte=lambda img: matte[:img.shape[0]], frame_format="nv12"))
-    assert w.lib.calls == {"emo_nv12_windows_f32": 2, "emo_paste_windows_nv12": 2}
+    assert w.lib.calls == {"emo_yuv420_crop_f32": 2, "emo_paste_yuv420": 2}
+    assert w.lib.forms == {"emo_yuv420_crop_f32": ["windows"] * 2, "emo_paste_yuv420": ["windows"] * 2}
     images = torch.cat(w.driven)
     want = torch.cat([w.paste_back(nv12[a:b], images[a:b], R.WINDOWS[a:b], 0.25, matte[:b - a], frame_format="nv12") for a, b in ((0, 4), (4, 6))])
     assert torch.equal(torch.cat([t for _, t in got]), want) and torch.equal(nv12, before)

@@ -16,10 +16,11 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 import nv12_reference as R  # noqa: E402
+import yuv420_reference as Y  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GUARD, FILL = 64, 0xA5
+FILL = Y.FILL
 F64, F32 = torch.float64, torch.float32
 
 
@@ -32,20 +33,16 @@ def _sq(wins):
     return [(x, y, s, s) for x, y, s in wins]
 
 
-class Surface:
-    """N NV12 frames on the device between GUARD bytes, rows `pitch` apart, all padding = FILL; .view is the [N, rows, W] view"""
+class Surface(Y.Surface):
+    """N NV12 frames on the device between GUARD bytes, rows `pitch` apart, all padding = FILL (yuv420_reference.Surface, layout
+    nv12, device memory); .view is the [N, rows, W] view the ops take"""
 
     def __init__(self, n, rows, w, pitch=None, frames=None):
-        pitch = pitch or w
-        self.raw = torch.full((2 * GUARD + n * rows * pitch,), FILL, dtype=torch.uint8, device=DEV)
-        self.padded = self.raw[GUARD:GUARD + n * rows * pitch].view(n, rows, pitch)
-        self.view = self.padded[:, :, :w]
-        self.w = w
-        if frames is not None:
-            self.view.copy_(frames)
+        super().__init__(Y.DeviceMemory(), "nv12", n, rows // 3 * 2, w, pad=(pitch or w) - w, arr=None if frames is None else frames.numpy())
+        self.view = self.dev[Y.GUARD:Y.GUARD + n * self.fstride].view(n, rows, self.pitch_y)[:, :, :w]
 
     def padding_intact(self):
-        return bool((self.raw[:GUARD] == FILL).all() and (self.raw[-GUARD:] == FILL).all() and (self.padded[:, :, self.w:] == FILL).all())
+        return self.read()[1]
 
 
 def _crop(nv12, wins, size, mode, pitch=None, device_table=False):
@@ -246,7 +243,7 @@ def test_refusals_write_nothing(small):
         ops.nv12_windows(work[:, :, :479], (R.S, R.S), sq)
     with pytest.raises(ValueError, match="3H/2"):
         ops.nv12_windows(work[:, :404], (R.S, R.S), sq)
-    with pytest.raises(RuntimeError, match="pitch"):
+    with pytest.raises(ValueError, match="pitch"):
         ops.nv12_windows(work[:, :, ::2], (R.S, R.S), sq)
     with pytest.raises(RuntimeError, match="GPU only"):
         ops.nv12_windows(nv12, (R.S, R.S), sq)

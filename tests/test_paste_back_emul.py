@@ -23,6 +23,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+from counting_lib import CountingLib as _Lib  # noqa: E402
 import emulibs  # noqa: E402
 import paste_back_reference as R  # noqa: E402
 
@@ -183,25 +184,6 @@ def test_paste_windows_is_in_the_abi_table():
 
 
 # ---- host logic on CPU tensors ---------------------------------------------------------------------------------------------
-class _Lib:
-    """the host-compiled stream library behind emoportraits_amd.hip's table of signatures; counts the calls"""
-
-    def __init__(self, lib):
-        from emoportraits_amd import hip
-        self._lib, self._sig, self.calls = lib, hip.SIGNATURES, {}
-
-    def __getattr__(self, name):
-        if name.startswith("_") or name == "calls":
-            raise AttributeError(name)
-        fn = getattr(self._lib, name)
-        fn.argtypes, fn.restype = self._sig[name], ctypes.c_int
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
 @pytest.fixture()
 def wrapper(monkeypatch, lib):
     from emoportraits_amd import hip

@@ -14,7 +14,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+from counting_lib import CountingLib as _Lib  # noqa: E402
 
 
 @pytest.fixture(scope="module", params=[False, True], ids=["loop", "threads"])
@@ -250,25 +252,6 @@ def test_ema_scan_refusals(stream):
 
 
 # ---- the wrapper on the emulated kernels ----------------------------------------------------------------------------------
-class _Lib:
-    """the host-compiled stream library presented as the package's, with hip.SIGNATURES' argument types; counts calls"""
-
-    def __init__(self, lib):
-        from emoportraits_amd import hip
-        self._lib, self._sig, self._res, self.calls = lib, hip.SIGNATURES, hip._RESTYPES, {}
-
-    def __getattr__(self, name):
-        if name.startswith("_"):
-            raise AttributeError(name)
-        fn = getattr(self._lib, name)
-        fn.argtypes, fn.restype = self._sig[name], self._res.get(name, ctypes.c_int)
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
 @pytest.fixture()
 def wrapper(monkeypatch):
     """an InferenceWrapper with a 3-slot bank and everything but the driver pass: that records (pose, theta, identity)"""

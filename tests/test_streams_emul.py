@@ -24,6 +24,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+from counting_lib import CountingLib as _Lib  # noqa: E402
 import emulibs  # noqa: E402
 import nv12_reference as NV  # noqa: E402
 import paste_back_reference as PB  # noqa: E402
@@ -31,34 +32,17 @@ import streams_reference as R  # noqa: E402
 
 NEW = ("emo_rgb8_faces_ragged_f32", "emo_nv12_faces_ragged_f32", "emo_paste_faces_ragged_rgb8", "emo_paste_faces_ragged_nv12")
 OLD = ("emo_unpack_rgb8", "emo_resize2d_faces_f32", "emo_nv12_faces_f32", "emo_paste_faces_rgb8", "emo_paste_faces_nv12")
+# what the Python layer launches for a mixed batch: rgb8 the ABI 19 entry points above, NV12 the ABI 22 ones with layout 0
+RUN = {"rgb8": (NEW[0], NEW[2]), "nv12": ("emo_yuv420_crop_ragged_f32", "emo_paste_ragged_yuv420")}
 MODE = ("bt601", True)                                   # (colorspace, full_range) of the NV12 cases
 MATRIX = (NV.MATRIX_ID[MODE[0]], int(MODE[1]))
 FMTS = ["rgb8", "nv12"]
 
 
-class _Lib:
-    """the host-compiled stream library behind emoportraits_amd.hip's table of signatures; counts the calls"""
-
-    def __init__(self, lib):
-        from emoportraits_amd import hip
-        self._lib, self._sig, self.calls = lib, hip.SIGNATURES, {}
-
-    def __getattr__(self, name):
-        if name.startswith("_") or name == "calls":
-            raise AttributeError(name)
-        fn = getattr(self._lib, name)
-        fn.argtypes, fn.restype = self._sig[name], ctypes.c_int
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
 @pytest.fixture(scope="module")
 def raw():
     lib = emulibs.stream(False)
-    for name in NEW + OLD:
+    for name in NEW + OLD + RUN["nv12"]:
         assert hasattr(lib, name), f"the host build of csrc does not export {name}"
     return lib
 
@@ -351,14 +335,15 @@ def test_ops_build_the_table_from_checked_tensors_only(lib, inputs, fmt):
     crop = lambda fr=work, w=wins, fo=R.FRAME_OF: ops.crop_faces_mixed(fr, R.S, w, fo, fmt, *mode)
     paste = lambda fr=work, w=wins, fo=R.FRAME_OF, im=img, **kw: ops.paste_faces_mixed(fr, im, w, fo, kw.get("feather", 0.0), None, fmt, *mode)
     bad_win = wins[:1] + [_sq([R.OUTSIDE_ITS_FRAME])[0]] + wins[2:]
+    geometry = RuntimeError if fmt == "rgb8" else ValueError                     # a YUV 4:2:0 frame's dtype, stride or pitch: ValueError
     for call in (crop, paste):
         for kw, err, msg in ((dict(w=bad_win), ValueError, "its own frame"), (dict(fo=[0, 0, 2, 3, 1, 3]), ValueError, "non-decreasing"),
                              (dict(fo=[0, 0, 2, 3, 3, 4]), ValueError, "outside"), (dict(w=wins[:5]), ValueError, "windows for"),
                              (dict(fr=[]), ValueError, "non-empty list"), (dict(fr=torch.zeros(4, 8, 8, 3, dtype=torch.uint8)), ValueError, "list"),
-                             (dict(fr=work[:3] + [work[3].float()]), RuntimeError, "uint8"),
+                             (dict(fr=work[:3] + [work[3].float()]), geometry, "uint8"),
                              (dict(fr=work[:3] + [work[3][None]]), ValueError, "expected"),
                              (dict(fr=work[:3] + [work[3][:, ::2]]), (RuntimeError, ValueError), "stride|expected"),
-                             (dict(fr=work[:3] + [torch.as_strided(work[3], work[3].shape, (1,) + work[3].stride()[1:])]), RuntimeError, "pitch")):
+                             (dict(fr=work[:3] + [torch.as_strided(work[3], work[3].shape, (1,) + work[3].stride()[1:])]), geometry, "pitch")):
             with pytest.raises(err, match=msg):
                 call(**kw)
     for kw, msg in ((dict(w=[(1, 3, 40, 41)] + wins[1:]), "square"), (dict(w=[(1, 3, 31, 31)] + wins[1:]), "quarter"),
@@ -523,6 +508,7 @@ def test_animate_streams_is_animate_frames_of_the_canvas_clip(wrapper, fmt):
     paste = dict(batch_size=4, to_host=False, paste_back=True, feather=0.25, paste_matte=matte, **kw)
     want = torch.cat([t for _, t in w.animate_frames(canvas, faces=faces, **paste)])
     parent_calls, n_driven = dict(w.lib.calls), len(w.driven)
+    assert all(form == "faces" for forms in w.lib.forms.values() for form in forms) and (len(w.lib.forms) == 2) == (fmt == "nv12")
     w.lib.calls.clear()
     w.driven.clear()
     w.crops.clear()
@@ -533,7 +519,7 @@ def test_animate_streams_is_animate_frames_of_the_canvas_clip(wrapper, fmt):
         hw = R.frame_size(frames_of[s][t], fmt)
         assert tuple(out.shape) == tuple(frames_of[s][t].shape) and torch.equal(out, R.region(want[i], hw, fmt)), (s, t)
     assert torch.equal(flat[2][2], frames_of[2][0]) and not torch.equal(flat[0][2], frames_of[0][0])   # (no face: as it went in)
-    crop, pst = ("emo_rgb8_faces_ragged_f32", "emo_paste_faces_ragged_rgb8") if fmt == "rgb8" else ("emo_nv12_faces_ragged_f32", "emo_paste_faces_ragged_nv12")
+    crop, pst = RUN[fmt]
     assert w.lib.calls == {crop: 2, pst: 2} and sum(parent_calls.values()) == 4
     assert _equal_lists(frames_of, before) and len(w.uploads) == 2
     # crops out: frames without a face are left out; the rows are the parent's crops of the canvas clip, split by frame

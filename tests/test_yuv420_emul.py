@@ -10,7 +10,6 @@ themselves are tests/yuv420_reference.py's, shared with tests/test_yuv420_gpu.py
   * ops.* and InferenceWrapper.animate_frames / paste_back / animate_streams / animate on CPU tensors in every new format, the
     package pointed at the host-compiled library inside the test only, calls counted.
 """
-import ctypes
 import os
 import sys
 
@@ -22,6 +21,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+from counting_lib import CountingLib as _Lib  # noqa: E402
 import emulibs  # noqa: E402
 import yuv420_reference as Y  # noqa: E402
 
@@ -102,25 +102,6 @@ def test_the_entry_points_are_in_the_abi_table():
 
 
 # ---- host logic on CPU tensors ---------------------------------------------------------------------------------------------
-class _Lib:
-    """the host-compiled stream library behind emoportraits_amd.hip's table of signatures; counts the calls"""
-
-    def __init__(self, lib):
-        from emoportraits_amd import hip
-        self._lib, self._sig, self.calls = lib, hip.SIGNATURES, {}
-
-    def __getattr__(self, name):
-        if name.startswith("_") or name == "calls":
-            raise AttributeError(name)
-        fn = getattr(self._lib, name)
-        fn.argtypes, fn.restype = self._sig[name], ctypes.c_int
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
 def _image(k, b):
     return torch.rand(b, 3, Y.S, Y.S, generator=torch.Generator().manual_seed(40 + k)) * 1.2 - 0.1
 
