@@ -1,1 +1,1 @@
-from .controls import ExpressionControls, HeadPoseControls  # noqa: F401
+from .controls import CropTracking, ExpressionControls, HeadPoseControls  # noqa: F401

@@ -66,3 +66,38 @@ class HeadPoseControls:
                 raise ValueError(f"head_pose= has no field {unknown[0]!r}")
             return cls(**value)
         raise ValueError("head_pose= takes a HeadPoseControls or a mapping with its fields")
+
+
+@dataclasses.dataclass
+class CropTracking:
+    """The `tracking=` keyword of InferenceWrapper.animate_frames / animate_streams, beside `boxes=`: how the face boxes of a
+    detector become crop windows, on the device (ops.crop_track; the arithmetic is crop_image's, notebooks/infer.py:301-352, and
+    hostglue.crop_track states it).  A row is a frame, or a track of a frame with boxes [N,P,4].
+    smooth: the reference's use_smoothed_crop: an EMA of the box centre and size along each track, started at the track's first box.
+    momentum: the EMA's, 0 < momentum <= 1; None = the wrapper's crop momentum (`momentum`, 0.01), what crop_image uses.
+    fixed: the reference's fixed_bounding_box: with smooth, every row takes the track's first centre and size.
+    scale: multiplies the box size (crop_image's `scale`).
+    box_format: 'xyxy' = pixel boxes (x0, y0, x1, y1); 'relative' = mediapipe's (xmin, ymin, width, height) relative to the frame,
+        made a pixel box as forward(crop=True) makes it (hostglue.detection_to_face).
+    missing: what a row without a usable window is given: 'skip' = it is not pasted (paste_back returns its frame as it came) and
+        is rendered, where crops are returned, from the centred square of its frame; 'hold' = the track's last window, where it
+        has one that fits the row's frame.
+    All defaults = the reference's per-frame window (use_smoothed_crop=False)."""
+    smooth: bool = False
+    momentum: object = None
+    fixed: bool = False
+    scale: float = 1.0
+    box_format: str = "xyxy"
+    missing: str = "skip"
+
+    @classmethod
+    def of(cls, value):
+        """None | CropTracking | a mapping with the same fields -> CropTracking or None"""
+        if value is None or isinstance(value, cls):
+            return value
+        if isinstance(value, Mapping):
+            unknown = sorted(set(value) - {f.name for f in dataclasses.fields(cls)})
+            if unknown:
+                raise ValueError(f"tracking= has no field {unknown[0]!r}")
+            return cls(**value)
+        raise ValueError("tracking= takes a CropTracking or a mapping with its fields")

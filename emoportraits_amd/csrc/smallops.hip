@@ -478,7 +478,134 @@ __global__ __launch_bounds__(64) void head_pose_controls_kernel(
   if (threadIdx.x == blockDim.x - 1 && relative && !had_anchor && first < n) has_anchor[k] = 1;
 }
 
+// Face boxes -> crop and paste windows with the crop tracker's state carried along the row order (include/emo_hip.h, ABI 23;
+// hostglue.crop_track is the contract, which restates notebooks/infer.py:301-352 crop_image).  The launch pattern of
+// theta_ema_scan_kernel: one thread per stream walks the M rows in order and owns its stream's state, flag and last window; a row
+// whose stream lies outside [0, K) has no state and is written by thread 0.  Everything stays a double until it has passed its
+// range test; -ffp-contract=off keeps the two products and the sum of the EMA apart.
+__device__ inline bool crop_window_inside(int x, int y, int s, int W, int H, int min_side) {
+  return s > 0 && x >= 0 && y >= 0 && x <= W - s && y <= H - s && s >= min_side;
+}
+
+__device__ inline bool crop_in_range(double v) { return finite_f64(v) && fabs(v) < 1073741824.0; }
+
+__global__ __launch_bounds__(64) void crop_track_kernel(const double* __restrict__ boxes, const int* __restrict__ stream_of,
+                                                        const int* __restrict__ sizes, int Wf, int Hf, double* __restrict__ state,
+                                                        int* __restrict__ has, int* __restrict__ last, int M, int K, double m,
+                                                        double om, int smooth, int fixed, double scale, int box_format, int hold,
+                                                        int min_side, int* __restrict__ crop, int* __restrict__ paste,
+                                                        double* __restrict__ face_scale) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= K) return;
+  bool had = smooth && has[k] != 0;
+  double st[3] = {0.0, 0.0, 0.0};
+  if (had)
+    for (int j = 0; j < 3; ++j) st[j] = state[(long)k * 3 + j];
+  int lw[4] = {0, 0, 0, 0};
+  if (last)
+    for (int j = 0; j < 4; ++j) lw[j] = last[(long)k * 4 + j];
+  bool touched = false, kept = false;
+  for (int i = 0; i < M; ++i) {
+    const int ki = stream_of ? stream_of[i] : 0;
+    const bool in_range = ki >= 0 && ki < K;
+    if (in_range ? ki != k : k != 0) continue;
+    const int W = sizes ? sizes[2 * i] : Wf, H = sizes ? sizes[2 * i + 1] : Hf;
+    int* const c = crop + (long)i * 4;
+    int* const p = paste + (long)i * 4;
+    if (W < 1 || H < 1) {                                   // (no frame: nothing can be read)
+      for (int j = 0; j < 4; ++j) { c[j] = 0; p[j] = 0; }
+      if (face_scale) face_scale[i] = 0.0;
+      continue;
+    }
+    const double* const b = boxes + (long)i * 4;
+    double x0 = b[0], y0 = b[1], x1 = b[2], y1 = b[3];
+    if (box_format == 1) {                                  // hostglue.detection_to_face, in its order of operations
+      const double wd = (double)W, hd = (double)H, hm1 = (double)(H - 1);
+      const double t = hd * (b[1] + b[3] * 1.2);
+      x0 = wd * b[0];
+      y0 = hd * b[1] * 0.9;
+      x1 = wd * (b[0] + b[2]);
+      y1 = hm1 < t ? hm1 : t;
+    }
+    bool present = false;
+    int wx = 0, wy = 0, ws = 0;
+    double fs = 0.0;
+    if (in_range && crop_in_range(x0) && crop_in_range(y0) && crop_in_range(x1) && crop_in_range(y1)) {
+      double v[3] = {floor((x1 + x0) / 2), floor((y1 + y0) / 2), (((x1 - x0) + y1) - y0) * scale};
+      if (smooth) {
+        for (int j = 0; j < 3; ++j) {
+          if (!had) {
+            st[j] = v[j];
+          } else if (!fixed) {
+            const double a = v[j] * m, bb = st[j] * om;
+            st[j] = a + bb;
+          }
+          v[j] = st[j];
+        }
+        had = true;
+        touched = true;
+      }
+      const double cx = rint(v[0]), cy = rint(v[1]);
+      double sz = rint(v[2]);
+      if (finite_f64(sz) && sz >= 2.0) {
+        sz = sz - fmod(sz, 2.0);
+        const double half = sz / 2;
+        double b0 = cx - half, b1 = cy - half, b2 = cx + half, b3 = cy + half;
+        double over = b0 >= 0 ? 0.0 : -b0;
+        const double o1 = b1 >= 0 ? 0.0 : -b1, o2 = b2 <= (double)W ? 0.0 : b2 - (double)W, o3 = b3 <= (double)H ? 0.0 : b3 - (double)H;
+        if (o1 > over) over = o1;
+        if (o2 > over) over = o2;
+        if (o3 > over) over = o3;
+        b0 = b0 + over; b1 = b1 + over; b2 = b2 - over; b3 = b3 - over;
+        double side = trunc((b2 - b0 + b3 - b1) / 2);
+        side = side - fmod(side, 2.0);
+        if (side >= 2.0 && side < 1073741824.0 && fabs(cx) < 1073741824.0 && fabs(cy) < 1073741824.0) {
+          ws = (int)side;
+          wx = (int)cx - ws / 2;
+          wy = (int)cy - ws / 2;
+          present = crop_window_inside(wx, wy, ws, W, H, min_side);
+          if (present) fs = side / sz;
+        }
+      }
+    }
+    if (present) {
+      lw[0] = wx; lw[1] = wy; lw[2] = ws; lw[3] = ws;
+      kept = true;
+      for (int j = 0; j < 4; ++j) { c[j] = lw[j]; p[j] = lw[j]; }
+    } else if (hold && in_range && crop_window_inside(lw[0], lw[1], lw[2], W, H, min_side)) {
+      for (int j = 0; j < 4; ++j) { c[j] = lw[j]; p[j] = lw[j]; }
+    } else {
+      const int s = W < H ? W : H;
+      c[0] = (W - s) / 2; c[1] = (H - s) / 2; c[2] = s; c[3] = s;
+      for (int j = 0; j < 4; ++j) p[j] = 0;
+    }
+    if (face_scale) face_scale[i] = fs;
+  }
+  if (touched) {
+    for (int j = 0; j < 3; ++j) state[(long)k * 3 + j] = st[j];
+    has[k] = 1;
+  }
+  if (kept && last)
+    for (int j = 0; j < 4; ++j) last[(long)k * 4 + j] = lw[j];
+}
+
 }  // namespace
+
+extern "C" int emo_crop_track_f64(const double* boxes, const int32_t* stream_of, const int32_t* sizes, int Wf, int Hf, double* state,
+                                  int32_t* has_state, int32_t* last, int M, int K, double m, double om, int smooth, int fixed,
+                                  double scale, int box_format, int hold, int min_side, int32_t* crop, int32_t* paste,
+                                  double* face_scale, void* stream) {
+  if (!boxes || !crop || !paste || M <= 0 || K <= 0) return EMO_ERR_BAD_ARG;
+  if (!sizes && (Wf < 1 || Hf < 1)) return EMO_ERR_BAD_ARG;
+  if (smooth && (!state || !has_state)) return EMO_ERR_BAD_ARG;
+  if (hold && !last) return EMO_ERR_BAD_ARG;
+  if (!(m > 0.0 && m <= 1.0) || !(om >= 0.0 && om < 1.0)) return EMO_ERR_BAD_ARG;
+  if (!((scale - scale) == 0.0) || (box_format != 0 && box_format != 1) || min_side < 1) return EMO_ERR_BAD_ARG;
+  hipLaunchKernelGGL(crop_track_kernel, dim3(emo_cdiv(K, 64)), dim3(64), 0, (hipStream_t)stream, boxes, stream_of, sizes, Wf, Hf,
+                     state, has_state, last, M, K, m, om, smooth ? 1 : 0, fixed ? 1 : 0, scale, box_format, hold ? 1 : 0, min_side,
+                     crop, paste, face_scale);
+  return emo_launch_status();
+}
 
 extern "C" int emo_small_gemm_f32(const float* A, const float* B, float* C, int M, int K, int NN, int batch,
                                   int64_t b_stride, int64_t c_stride, void* stream) {

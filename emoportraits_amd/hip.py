@@ -14,7 +14,7 @@ PAD_MODES = {"zeros": 0, "border": 1, "reflection": 2}
 LAYOUT_NCDHW, LAYOUT_NDHWC, LAYOUT_P4 = 0, 1, 3
 ACT = {"none": 0, "relu": 1, "tanh": 2, "sigmoid": 3}
 
-_c_int, _c_i64, _c_void, _c_float = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float
+_c_int, _c_i64, _c_void, _c_float, _c_double = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
 
 # name -> argtypes; restype is int unless listed in _RESTYPES.  Mirrors include/emo_hip.h one to one
 # (tests/test_abi.py checks header <-> this table <-> exported symbols).
@@ -66,6 +66,8 @@ SIGNATURES = {
     "emo_theta_ema_scan_f32": [_c_void] * 4 + [_c_int, _c_int, _c_float, _c_float, _c_void, _c_void],
     "emo_expr_controls_f32": [_c_void] * 9 + [_c_int] * 5 + [_c_float, _c_float, _c_void, _c_void],
     "emo_head_pose_controls_f32": [_c_void, _c_int] + [_c_void] * 10 + [_c_int] * 4 + [_c_void] * 3,
+    "emo_crop_track_f64": [_c_void] * 3 + [_c_int, _c_int] + [_c_void] * 3 + [_c_int, _c_int, _c_double, _c_double, _c_int, _c_int,
+                           _c_double] + [_c_int] * 3 + [_c_void] * 4,
     "emo_mul_mask_f32": [_c_void, _c_void, _c_void, _c_int, _c_int, _c_i64, _c_void],
     "emo_stage2_compose_f32": [_c_void] * 5 + [_c_int, _c_int, _c_i64, _c_void],
     "emo_small_gemm_f32": [_c_void] * 3 + [_c_int] * 4 + [_c_i64, _c_i64, _c_void],

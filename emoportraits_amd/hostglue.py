@@ -64,6 +64,130 @@ def crop_window(face, img_w, img_h, tracker=None, scale=1):
     return int(center[0] - side // 2), int(center[1] - side // 2), side, side / size
 
 
+CROP_BOX_FORMATS = {"xyxy": 0, "relative": 1}
+CROP_MISSING = {"skip": 0, "hold": 1}
+_CROP_RANGE = float(1 << 30)
+
+
+def window_inside(x_lo, y_lo, side, img_w, img_h, min_side=1):
+    """the integer test of a square window against its frame: the predicate of ops.windows_host (and of nv12_window_ok in
+    csrc/resample.hip), and a side of at least min_side"""
+    return side > 0 and x_lo >= 0 and y_lo >= 0 and x_lo <= img_w - side and y_lo <= img_h - side and side >= min_side
+
+
+def crop_track(boxes, stream_of, size, state, has, last, momentum=0.01, smooth=False, fixed=False, scale=1.0, box_format="xyxy",
+               missing="skip", min_side=2, K=None, why=None):
+    """Face boxes -> crop and paste windows for a whole batch of rows, one row after another: crop_window with a CropTracker per
+    stream (notebooks/infer.py:301-352, crop_image's arithmetic), plus what a batch needs that one frame did not -- a row whose
+    face is missing or whose window does not fit still gets a window that can be read, and says so.  The contract that
+    emo_crop_track_f64 (ops.crop_track) is held to bit for bit.  Everything is float64 until a value has passed its range test.
+    boxes [M,4] float64, row order = frame order; stream_of [M] ints or None (every row: stream 0); size = (W, H) of every
+    row's frame, or [M,2]; state [K,3] float64 = (cx, cy, size), has [K] int32 and last [K,4] int32 (the stream's last present
+    window, side 0 = none) are the streams' state, UPDATED IN PLACE (state and has may be None without `smooth`; last may be
+    None without missing='hold', and is then not kept; K: the number of streams where no state says it, default 1); momentum in
+    (0, 1], with om = 1 - momentum formed in float64.
+    box_format 'xyxy': the pixel box (x0, y0, x1, y1); 'relative': mediapipe's (xmin, ymin, width, height), through
+    detection_to_face's arithmetic in its order of operations.  -> (crop [M,4] int32, paste [M,4] int32, face_scale [M] float64).
+    Row i of stream k in a W x H frame:
+        missing: a component of the box (after the format conversion) is not finite or has magnitude >= 2^30, or k is outside
+            [0, K).  A missing row does not touch the tracker (the reference: `face is None` -> face_check = False); a k outside
+            [0, K) touches no state at all.
+        cx = floor((x1 + x0) / 2), cy = floor((y1 + y0) / 2), size = (((x1 - x0) + y1) - y0) * scale
+        smooth: a stream without state takes (cx, cy, size) as its state; otherwise, unless `fixed`, state = v * m + state * om,
+            each product and the sum rounded on its own; the row goes on with the state.
+        cx, cy, size = rint of each (half to even); size -= size % 2; absent unless size is finite and >= 2
+        side = remove_overflow((cx, cy), size, W, H) before its last line, truncated towards zero; side -= side % 2; absent
+            unless side >= 2; absent unless |cx|, |cy| and side are below 2^30 -- only now do they become integers
+        x_lo = cx - side / 2, y_lo = cy - side / 2
+        present: window_inside(x_lo, y_lo, side, W, H, min_side).  Then crop = paste = (x_lo, y_lo, side, side), last[k] is that
+            window and face_scale = side / size.
+        missing or absent: face_scale = 0, and with missing='hold', if last[k] has a side and is window_inside this row's frame
+            with min_side, crop = paste = last[k]; otherwise crop is the centred square of side min(W, H) at ((W - side) // 2,
+            (H - side) // 2), which can always be read, and paste = (0, 0, 0, 0), which every paste kernel skips.
+    why: a list that receives, per row, 'present' or what made the row missing ('stream', 'box') or absent ('size', 'side',
+    'min_side'; 'guard' = the range test of the centre and the side or the inside test, which no finite box below 2^30 in a frame
+    below 2^30 reaches: they are made so that no value is trusted)."""
+    b = np.ascontiguousarray(boxes, dtype=np.float64)
+    if b.ndim != 2 or b.shape[1] != 4:
+        raise ValueError(f"boxes must be [M,4], got {b.shape}")
+    if box_format not in CROP_BOX_FORMATS:
+        raise ValueError(f"box_format {box_format!r}: 'xyxy' or 'relative'")
+    if missing not in CROP_MISSING:
+        raise ValueError(f"missing {missing!r}: 'skip' or 'hold'")
+    m = float(momentum)
+    if not 0.0 < m <= 1.0:
+        raise ValueError(f"crop momentum {momentum} is not in (0, 1]")
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError(f"crop scale {scale} is not finite")
+    if smooth and (state is None or has is None):
+        raise ValueError("smoothing needs state and has")
+    hold = missing == "hold"
+    if hold and last is None:
+        raise ValueError("missing='hold' needs last")
+    if int(min_side) < 1:
+        raise ValueError(f"min_side {min_side} is below 1")
+    M = b.shape[0]
+    K = next((a.shape[0] for a in (state, has, last) if a is not None), 1 if K is None else K)
+    sizes = np.asarray(size, dtype=np.int64)
+    sizes = np.broadcast_to(sizes, (M, 2)) if sizes.ndim == 1 else sizes
+    if sizes.shape != (M, 2) or (sizes < 1).any():
+        raise ValueError("size: the (W, H) of every frame, or one per row, all positive")
+    om = 1.0 - m
+    crop, paste, face_scale = np.zeros((M, 4), np.int32), np.zeros((M, 4), np.int32), np.zeros(M, np.float64)
+    with np.errstate(all="ignore"):                      # (inf and nan boxes are inputs here, not accidents)
+        for i in range(M):
+            W, H = int(sizes[i, 0]), int(sizes[i, 1])
+            k = 0 if stream_of is None else int(stream_of[i])
+            in_range = 0 <= k < K
+            if box_format == "relative":
+                x0, y0, x1, y1 = (np.float64(v) for v in detection_to_face(b[i, 0], b[i, 1], b[i, 2], b[i, 3], W, H))
+            else:
+                x0, y0, x1, y1 = b[i]
+            window, cause = None, "stream" if not in_range else "box"
+            if in_range and all(np.isfinite(v) and abs(v) < _CROP_RANGE for v in (x0, y0, x1, y1)):
+                v = np.array([np.floor((x1 + x0) / 2), np.floor((y1 + y0) / 2), (((x1 - x0) + y1) - y0) * scale])
+                if smooth:
+                    if not has[k]:
+                        state[k] = v
+                        has[k] = 1
+                    elif not fixed:
+                        state[k] = v * m + state[k] * om
+                    v = state[k].copy()
+                cx, cy, sz = np.rint(v)
+                cause = "size"
+                if np.isfinite(sz) and sz >= 2:
+                    sz = sz - np.fmod(sz, 2.0)
+                    half = sz / 2
+                    b0, b1, b2, b3 = cx - half, cy - half, cx + half, cy + half
+                    over = max(0.0 if b0 >= 0 else -b0, 0.0 if b1 >= 0 else -b1, 0.0 if b2 <= W else b2 - W, 0.0 if b3 <= H else b3 - H)
+                    b0, b1, b2, b3 = b0 + over, b1 + over, b2 - over, b3 - over
+                    side = np.trunc((b2 - b0 + b3 - b1) / 2)
+                    side = side - np.fmod(side, 2.0)
+                    cause = "side" if not side >= 2 else "guard"
+                    if side >= 2 and side < _CROP_RANGE and abs(cx) < _CROP_RANGE and abs(cy) < _CROP_RANGE:
+                        side_i = int(side)
+                        x_lo, y_lo = int(cx) - side_i // 2, int(cy) - side_i // 2
+                        if window_inside(x_lo, y_lo, side_i, W, H, min_side):
+                            window, cause = (x_lo, y_lo, side_i, side_i), "present"
+                            face_scale[i] = side / sz
+                        elif window_inside(x_lo, y_lo, side_i, W, H):
+                            cause = "min_side"
+            if why is not None:
+                why.append(cause)
+            if window is not None:
+                crop[i] = paste[i] = window
+                if last is not None:
+                    last[k] = window
+                continue
+            if hold and in_range and window_inside(int(last[k, 0]), int(last[k, 1]), int(last[k, 2]), W, H, min_side):
+                crop[i] = paste[i] = last[k]
+                continue
+            side_i = min(W, H)
+            crop[i] = ((W - side_i) // 2, (H - side_i) // 2, side_i, side_i)
+    return crop, paste, face_scale
+
+
 def mixing_theta(source_theta, target_theta, mix_old=True):
     """notebooks/infer.py:686-736 (get_mixing_theta): keep the source's stretch (scale/shear from the polar decomposition of
     its linear part) and take rotation + translation from the driver.  numpy [B,>=3,4] x [B*T,>=3,4] -> float64 [B*T,3,4].

@@ -197,6 +197,10 @@ class InferenceWrapper:
         # as one [1,9] row (the head-pose controls' source pose; None where the source theta came as a 4x4 matrix)
         self.pred_source_pose_embed = self.pred_source_srt = None
         self._stage2 = self._stage2_wrapper = None                                 # attach_stage2()
+        # crop tracking of animate_frames(boxes=): the tracks' state on the device (control_streams.CropStates, made at the first
+        # use), apart from the host _crop_tracker of forward(crop=True); tracked_windows = (the paste windows of the chunk last
+        # tracked, int32 [rows,4] on the device, side 0 = no face; the index of its first row in the call)
+        self._crop_streams = self.tracked_windows = None
         self._init_identity_bank(identity_capacity)
 
     @property
@@ -358,6 +362,13 @@ class InferenceWrapper:
         """Restart smooth_pose and the head-pose controls' relative transfer: slots=None clears the single-identity state
         (`self.theta`, the relative-pose anchor) and every slot's stream; otherwise only the streams of the given bank slots"""
         self._restart(slots, pose_ema=True, pose_anchor=True)
+
+    def reset_crop_state(self, tracks=None):
+        """Restart the crop tracker of animate_frames(boxes=) -- the EMA of tracking=dict(smooth=True) and the window that
+        missing='hold' holds: tracks=None every track, otherwise the given ones (track p of boxes [N,P,4]; 0 for [N,4]).  The
+        tracks are faces of the video, not identities: store_identity, drop_identity and the other bank events leave them alone."""
+        if self._crop_streams is not None:
+            self._crop_streams.restart(tracks)
 
     def _restart(self, slots, **which):
         """slots=None: the single stream and every slot's; a slot or several: theirs (StreamStates.restart)"""
@@ -914,6 +925,7 @@ class InferenceWrapper:
             if reset_tracking:
                 self.center = self.size = self.delta_yaw = self.delta_pitch = None
                 self._crop_tracker = None
+                self.reset_crop_state()                    # (the reference resets `center` / `size`: the device tracker's too)
                 self.reset_pose_state()
                 self.reset_expression_state()
             self.mix, self.mix_old = mix, mix_old
@@ -1182,7 +1194,7 @@ class InferenceWrapper:
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
                        mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
                        paste_matte=None, as_uint8=True, refine=False, refine_masks=None, frame_format="rgb8", out_format=None,
-                       colorspace="bt709", full_range=False, faces=None, expression=None, head_pose=None):
+                       colorspace="bt709", full_range=False, faces=None, expression=None, head_pose=None, boxes=None, tracking=None):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  Per batch, all on the device and without a host synchronisation:
             byte -> fp32 CHW (emo_unpack_rgb8) -> crop windows read in place + bicubic resize to image_size, the whole batch in
@@ -1192,7 +1204,7 @@ class InferenceWrapper:
         frames: uint8 [N,H,W,3] tensor (host, ideally pinned, or device) or an iterable of such chunks -- decoded video frames,
             uploaded as BYTES, span i + 1 beside the compute of span i (frames.uploaded).
         windows: windows[i] = (x_lo, y_lo, side) from the face detector + hostglue.crop_window, host arithmetic; None = whole
-            frame.
+            frame.  (boxes= below takes the detector's boxes instead and forms the windows on the device.)
         to_host, ring: results go D2H into a ring of `ring` pinned buffers on a copy stream (frames.HostRing); a batch is
             yielded once ITS copy event has completed, i.e. the host only ever waits for a batch that is `ring - 1` batches
             behind the GPU.  What is yielded is a view of a pinned ring slot, valid ONLY until the generator is resumed (the
@@ -1294,11 +1306,44 @@ class InferenceWrapper:
             not depend on batch_size, on the chunking or on the number of ranks: on one rank the anchor is carried on the device
             from batch to batch, on several the regressed rows of every rank are gathered in row order (parallel.gather_rows)
             and edited on every rank in the pass in front of the loop that smooth_pose has; without relative the edit is per row
-            and needs no gather.  None, or all defaults: no launch, no state touched, the frames bit-identical."""
+            and needs no gather.  None, or all defaults: no launch, no state touched, the frames bit-identical.
+        boxes, tracking: face boxes in place of windows= / faces= (with either: ValueError) -- the crop window arithmetic of
+            crop_image (notebooks/infer.py:301-352: box -> centre and size, `scale`, the use_smoothed_crop EMA, fixed_bounding_box,
+            remove_overflow) on the device, so that a detector's boxes need not come to the host and the windows of a stream need
+            not be known before its first frame is rendered.  boxes: float32 / float64 [N,4], host or device, or an iterable that
+            yields one such tensor per chunk of an iterable `frames`, consumed in lockstep (one that ends before the frames do:
+            ValueError).  tracking: a CropTracking or a mapping with its fields (smooth, momentum, fixed, scale, box_format
+            'xyxy' | 'relative', missing 'skip' | 'hold'); boxes alone is the reference's per-frame window
+            (use_smoothed_crop=False).  Per chunk, in front of the batch loop, ONE launch over all rows of the chunk on every rank
+            (ops.crop_track, bit for bit hostglue.crop_track; the boxes are inputs every rank has: no gather) forms a crop and a
+            paste window per row; the batches slice those device tensors, the crop reads `crop`, paste_back=True pastes at
+            `paste`.  The tracker's state is carried on the device from chunk to chunk and from call to call (reset_crop_state,
+            forward(reset_tracking=True)); the result does not depend on batch_size, the chunking or the number of ranks.  A row
+            whose box is missing (not finite, or beyond 2^30) or whose window does not fit its frame -- with paste_back, is
+            smaller than a quarter of the pasted image -- is absent: paste_back returns its frame byte for byte as it went in;
+            without paste_back it is still rendered (fixed batch shapes, graphs replay), from the centred square of its frame (or
+            with missing='hold' from the track's last window).  Its pose still enters smooth_pose and the relative controls:
+            masking it is out of scope.  tracked_windows is left as (the paste windows of the chunk last tracked, int32 [rows,4] on
+            the device, side 0 = absent; the index of its first row).
+            boxes [N,P,4]: P fixed tracks per frame on the faces= path -- rows frame-major, track p is tracker stream p (the
+            tracker is made anew when P changes), P <= batch_size, identities= one slot per row, and faces=' rules for smooth_pose
+            and the relative controls.  Not here: enrol_identities, paste_back() (it takes device windows already), running a
+            detector, and device tensors as windows= (the rgb8 crop kernel trusts its windows; only the tracker's own test makes
+            device windows safe to read)."""
         if isinstance(frames, torch.Tensor):
             frames_mod.check_frames(frames, frame_format)
         n_rows, counts = frames.shape[0] if isinstance(frames, torch.Tensor) else None, None
-        if faces is not None:
+        track = control_streams.crop_plan(boxes, tracking, n_rows, 'windows' if windows is not None else 'faces' if faces is not None
+                                          else None, batch_size, self.momentum, self.device)
+        if track is not None and track.tracks is not None:
+            wins = None
+            if smooth_pose and (identities is None or not smooth_per_identity):
+                raise ValueError("smooth_pose=True with boxes [N,P,4] smooths every face track as its identity's stream: pass identities= "
+                                 "(one slot per row) and smooth_per_identity=True")
+            n_rows = None if n_rows is None else n_rows * track.tracks          # identities: one slot per row
+            if identities is not None and n_rows is not None and len(identities) != n_rows:
+                raise ValueError(f"identities has {len(identities)} entries for {n_rows} rows: one slot per track of every frame")
+        elif faces is not None:
             if windows is not None:
                 raise ValueError("faces= (a list of windows per frame) and windows= (one per frame) are mutually exclusive")
             wins, counts = frames_mod.flatten_faces(faces)
@@ -1316,18 +1361,22 @@ class InferenceWrapper:
             wins = None if windows is None else frames_mod.square_windows(windows)
         plan = self._video_plan(n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
                                 target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format,
-                                out_format, colorspace, full_range, expression=expression, faces=faces is not None, head_pose=head_pose)
+                                out_format, colorspace, full_range, expression=expression,
+                                faces=faces is not None or track is not None and track.tracks is not None, head_pose=head_pose, track=track)
         yield from self._animate_clip(frames, wins, counts, plan)
 
     def _video_plan(self, n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
                     target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format,
-                    colorspace, full_range, arena=False, expression=None, where='animate_frames', faces=False, head_pose=None):
+                    colorspace, full_range, arena=False, expression=None, where='animate_frames', faces=False, head_pose=None,
+                    track=None):
         """The checks of the keywords animate_frames() and animate_streams() share, before anything is launched, and what their
         loops need beside the frames: wins = the (x0, y0, s, s) of every row of the call (None: whole frames), n_rows their
         number where it is known.  -> masks_of, ids (_preflight), matte_fn (_paste_matte), out_kind (_render's `out`), fmt =
         (frame_format, colorspace, full_range), ring = the pinned ring (None without to_host; with `arena` and paste_back a
         frames.ArenaRing), upload_stream, ex, hp = the expression and the head-pose controls (_control_plans;
-        None: none), and the loop's keywords as they came."""
+        None: none), track = the crop tracking of boxes= (control_streams.crop_plan; None: none -- it forms the windows on the
+        device, and `wins` is then None) with min_side = the smallest side it lets through (a quarter of the pasted image, or 2),
+        and the loop's keywords as they came."""
         frames_mod.check_format(frame_format, colorspace)
         if out_format is not None:
             frames_mod.check_format(out_format, colorspace, "out_format")
@@ -1339,15 +1388,16 @@ class InferenceWrapper:
         if not as_uint8 and (to_host or paste_back):
             raise ValueError("as_uint8=False yields the fp32 device image: it needs to_host=False and paste_back=False")
         masks_of, ids = self._preflight(n_rows, identities, mix, target_theta, smooth_pose, smooth_per_identity, refine, refine_masks)
-        matte_fn = None
+        matte_fn, min_side = None, 2
         if paste_back:
-            if wins is None:
+            if wins is None and track is None:
                 raise ValueError("paste_back=True needs windows= or faces=: (x_lo, y_lo, side) says where each rendered crop goes")
             if not 0.0 <= float(feather) <= 0.5:
                 raise ValueError(f"feather {feather} is a fraction of the window side: 0 ... 0.5")
             matte_fn = self._paste_matte(paste_matte, 'paste_matte=True')
             S_out = self.cfg["image_size"] if masks_of is None else self._stage2.cfg["output_size_s2"]
-            if any(4 * w[2] < S_out for w in wins):
+            min_side = max(min_side, -(-S_out // 4))
+            if wins is not None and any(4 * w[2] < S_out for w in wins):
                 raise ValueError(f"a paste window is smaller than a quarter of the {S_out}-pixel image: downscaling "
                                  f"stops at image_size / 4")
         if out_format != "rgb8" and as_uint8 and not paste_back:
@@ -1359,7 +1409,7 @@ class InferenceWrapper:
         return Namespace(masks_of=masks_of, ids=ids, matte_fn=matte_fn, out_kind=out_kind, fmt=(frame_format, colorspace, bool(full_range)),
                          feather=feather, paste_back=paste_back, ring=host_ring, upload_stream=torch.cuda.Stream(device=self.device),
                          batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta, ex=ex,
-                         hp=hp)
+                         hp=hp, track=track, min_side=min_side)
 
     def _drive_crops(self, crops, ident, plan, theta=None, smooth=None, row0=0, pose=None, align=None):
         """The sequence of one driver batch of the video paths, crops [m,3,S,S] -> (the rendered batch as plan.out_kind says, its
@@ -1390,13 +1440,34 @@ class InferenceWrapper:
         out = self._render(pose, theta, ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
         return out, (None if plan.matte_fn is None else plan.matte_fn(out).float().contiguous())
 
+    def _track_chunk(self, track, n, base, frame_hw, min_side, row0):
+        """boxes= for the n frames of a chunk (the frames base ... of the call, H x W = frame_hw): their boxes from the feed, ONE
+        launch over all their rows in frame order (ops.crop_track, bit for bit hostglue.crop_track) with the tracks' state carried
+        in _crop_streams -> (crop, paste) windows of the chunk's rows as ops.DeviceWindows.  Track p of boxes [N,P,4] is tracker
+        stream p; the store is made anew when the number of tracks changes.  tracked_windows = (paste [rows,4], row0)."""
+        boxes = track.feed.take(n, base)
+        K = track.tracks or 1
+        if self._crop_streams is None or self._crop_streams.K != K:
+            self._crop_streams = control_streams.CropStates(K, self.device)
+        stream_of = None
+        if track.tracks is not None:
+            stream_of = torch.arange(K, dtype=torch.int32).repeat(n).to(self.device)
+        crop, paste, _ = ops.crop_track(boxes.reshape(-1, 4), stream_of, (frame_hw[1], frame_hw[0]), *self._crop_streams.arrays(),
+                                        momentum=track.momentum, smooth=track.smooth, fixed=track.fixed, scale=track.scale,
+                                        box_format=track.box_format, missing=track.missing, min_side=min_side)
+        self.tracked_windows = (paste, row0)
+        return ops.DeviceWindows(crop), ops.DeviceWindows(paste)
+
     def _animate_clip(self, frames, wins, counts, plan):
         """animate_frames behind its checks.  A row of everything between the crop and the paste is a face: wins = the
         (x0, y0, s, s) of every row of the stream in frame order, counts[i] = the faces of frame i, plan.ids = the slot of every
         row (host tensor) or None.  counts=None is windows= / whole frames: one row per frame (wins None: the whole frame), the
         per-frame entry points (frame_of=None) and the single-stream smooth_pose.  Per chunk the frames are sharded across the
-        ranks; a batch is a span of whole frames (frames.face_spans)."""
+        ranks; a batch is a span of whole frames (frames.face_spans).  With plan.track (boxes=) wins is None: the windows of a
+        chunk are formed on the device in front of its batches (_track_chunk), P rows per frame where the boxes are [N,P,4]."""
         S, ids, paste_back, ex, hp = self.cfg["image_size"], plan.ids, plan.paste_back, plan.ex, plan.hp
+        track = plan.track
+        P = None if track is None else track.tracks
         first = None if counts is None else frames_mod.face_offsets(counts)
         base = 0
         for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
@@ -1404,10 +1475,14 @@ class InferenceWrapper:
             n = chunk.shape[0]
             if counts is not None and base + n > len(counts):
                 raise ValueError(f"faces has {len(counts)} entries, the frames run past it")
-            if counts is None and ids is not None and base + n > ids.shape[0]:
+            if counts is None and ids is not None and (base + n) * (P or 1) > ids.shape[0]:
                 raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
             lo, hi = parallel.shard_range(n, self.rank, self.world)
-            if counts is None:
+            if P is not None:                                                    # (P tracks in every frame: faces= with counts = [P] * n)
+                spans = frames_mod.face_spans([P] * n, lo, hi, plan.batch_size)
+                rows = lambda b0, b1: ((base + b0) * P, (base + b1) * P)
+                frame_of = lambda b0, b1: [i - b0 for i in range(b0, b1) for _ in range(P)]
+            elif counts is None:
                 spans = [(b0, min(b0 + plan.batch_size, hi)) for b0 in range(lo, hi, plan.batch_size)]
                 rows = lambda b0, b1: (base + b0, base + b1)                     # the rows of the chunk's frames [b0, b1)
                 frame_of = lambda b0, b1: None
@@ -1415,7 +1490,14 @@ class InferenceWrapper:
                 spans = frames_mod.face_spans(counts[base:base + n], lo, hi, plan.batch_size)
                 rows = lambda b0, b1: (first[base + b0], first[base + b1])
                 frame_of = lambda b0, b1: [i - b0 for i in range(b0, b1) for _ in range(counts[base + i])]
-            wins_of = lambda b0, b1: None if wins is None else wins[slice(*rows(b0, b1))]
+            wins_of = paste_wins_of = lambda b0, b1: None if wins is None else wins[slice(*rows(b0, b1))]
+            if track is not None:
+                # every rank tracks the whole chunk (the boxes are inputs every rank has), then slices its batches' windows
+                r00 = rows(0, 0)[0]
+                crop_w, paste_w = self._track_chunk(track, n, base, frames_mod.frame_size(chunk, plan.fmt[0]), plan.min_side, r00) \
+                    if n else (ops.DeviceWindows(torch.empty((0, 4), dtype=torch.int32, device=self.device)),) * 2
+                wins_of = lambda b0, b1: crop_w[slice(*(r - r00 for r in rows(b0, b1)))]
+                paste_wins_of = lambda b0, b1: paste_w[slice(*(r - r00 for r in rows(b0, b1)))]
             crops_of = lambda u8, b0, b1: frames_mod.crops_of(u8, S, wins_of(b0, b1), *plan.fmt, frame_of=frame_of(b0, b1))
             with_faces = [sp for sp in spans if rows(*sp)[0] < rows(*sp)[1]]
             m_lo, m_hi = rows(lo, hi)
@@ -1517,7 +1599,7 @@ class InferenceWrapper:
                                                pose=None if poses is None else poses[m0 - m_lo:m1 - m_lo], align=aligns.pop(b0, None))
                     if paste_back:
                         full = u8.clone() if chunk.is_cuda else u8               # (a host chunk's upload is this span's own)
-                        out = frames_mod.paste_into(full, out, wins_of(b0, b1), plan.feather, m, *plan.fmt, frame_of=frame_of(b0, b1))
+                        out = frames_mod.paste_into(full, out, paste_wins_of(b0, b1), plan.feather, m, *plan.fmt, frame_of=frame_of(b0, b1))
                 index = base + b0 if paste_back else m0
                 if plan.ring is not None:
                     yield from plan.ring.push(index, out)
@@ -1530,7 +1612,7 @@ class InferenceWrapper:
     def animate_streams(self, streams, batch_size=16, ring=3, to_host=True, smooth_pose=False, mix=False, mix_old=True,
                         target_theta=True, paste_back=False, feather=0.0625, paste_matte=None, as_uint8=True, refine=False,
                         refine_masks=None, frame_format="rgb8", out_format=None, colorspace="bt709", full_range=False,
-                        expression=None, head_pose=None):
+                        expression=None, head_pose=None, tracking=None):
         """Several video streams of DIFFERENT frame sizes served by one driver batch: animate_frames(faces=) with the frames of a
         batch a list instead of one tensor.  Between the crop and the paste everything is one row per face, so only the two ends
         differ: ONE crop launch reads every face of the batch out of its own frame through a frame table
@@ -1541,6 +1623,12 @@ class InferenceWrapper:
             'frames': uint8 [N_s,H_s,W_s,3] (NV12: [N_s,3H_s/2,W_s]) or an iterable of such chunks, host (ideally pinned) or device;
             'windows': one (x_lo, y_lo, side) per frame, or 'faces': a list of them per frame in paste order ([]: no face); their
                 length is the stream's number of frames;
+            or 'boxes' in place of both (then in every stream): the face box of every frame, float32 / float64 [N_s,4], or an
+                iterable of such chunks in lockstep with the stream's frames (the stream's length must be known: its frames or
+                its boxes are one tensor) -- animate_frames' boxes=, with tracking= (one per call) saying how they become windows.
+                ONE launch per batch forms the batch's windows (ops.crop_track with stream_of = each row's stream and the (W, H)
+                of each row's own frame); the trackers' state, one per stream, is the call's own and is carried on the device from
+                batch to batch.  Several tracks per stream are out of scope;
             'identities' (optional, then in every stream): one bank slot for the stream, or one per face of the stream;
             'expression' (optional): {'gain': a float or one per face of the stream, 'offset': [E] or one row per face}, in place
                 of the call's values for this stream;
@@ -1567,11 +1655,28 @@ class InferenceWrapper:
         [faces,3S/2,S]; as_uint8=False: fp32 [faces,3,S,S]), frames without a face left out.  Everything yielded is valid until
         the generator is resumed.
         The call is rank-local: no collective, no sharding -- each rank serves its own streams."""
-        faces, idents = [], []
+        faces, idents, tracks = [], [], []
+        tracked = any('boxes' in st for st in streams)
+        if tracking is not None and not tracked:
+            raise ValueError("tracking= says how a stream's 'boxes' become windows: no stream has any")
         for k, st in enumerate(streams):
-            if ('windows' in st) == ('faces' in st):
-                raise ValueError(f"stream {k} takes either 'windows' (one per frame) or 'faces' (a list per frame)")
-            of_stream = [[w] for w in st['windows']] if 'windows' in st else list(st['faces'])
+            if tracked:
+                if 'boxes' not in st:
+                    raise ValueError("'boxes' must be given in every stream or in none")
+                n_k = st['frames'].shape[0] if isinstance(st['frames'], torch.Tensor) else \
+                    st['boxes'].shape[0] if isinstance(st['boxes'], torch.Tensor) and st['boxes'].dim() else None
+                tr = control_streams.crop_plan(st['boxes'], tracking, n_k, next((o for o in ('windows', 'faces') if o in st), None),
+                                               batch_size, self.momentum, self.device, f"stream {k}: 'boxes'")
+                if tr.tracks is not None:
+                    raise ValueError(f"stream {k}: 'boxes' must be [N,4]: several tracks per stream are not served")
+                if n_k is None:
+                    raise ValueError(f"stream {k}: its length must be known before the first batch: give its frames or its boxes as one tensor")
+                tracks.append(tr)
+                of_stream = [[(0, 0, 1)]] * n_k                                  # (one face per frame; the windows come from the tracker)
+            else:
+                if ('windows' in st) == ('faces' in st):
+                    raise ValueError(f"stream {k} takes either 'windows' (one per frame) or 'faces' (a list per frame)")
+                of_stream = [[w] for w in st['windows']] if 'windows' in st else list(st['faces'])
             flat, counts = frames_mod.flatten_faces(of_stream)
             if isinstance(st['frames'], torch.Tensor):
                 frames_mod.check_frames(st['frames'], frame_format)
@@ -1597,9 +1702,11 @@ class InferenceWrapper:
         n_faces, spans_of = [len(flat) for flat, _ in faces], [(s, first[s][t], first[s][t + 1]) for s, t in order]
         expression = control_streams.stream_expression(expression, [st.get('expression') for st in streams], n_faces, spans_of)
         head_pose = control_streams.stream_head_pose(head_pose, [st.get('head_pose') for st in streams], n_faces, spans_of)
-        plan = self._video_plan(len(wins), wins, identities, batch_size, ring, to_host, smooth_pose, True, mix, mix_old, target_theta,
-                                paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format, colorspace,
-                                full_range, arena=True, expression=expression, where='animate_streams', head_pose=head_pose)
+        plan = self._video_plan(len(wins), None if tracked else wins, identities, batch_size, ring, to_host, smooth_pose, True, mix, mix_old,
+                                target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format,
+                                colorspace, full_range, arena=True, expression=expression, where='animate_streams', head_pose=head_pose,
+                                track=tracks[0] if tracked else None)
+        crop_states = control_streams.CropStates(len(streams), self.device) if tracked else None     # (the call's own)
         S, host_ring = self.cfg["image_size"], plan.ring
         ids_dev = None if plan.ids is None else plan.ids.to(self.device)
         rows = frames_mod.face_offsets(counts)                                   # rows[i] = faces in front of frame i of the order
@@ -1616,6 +1723,15 @@ class InferenceWrapper:
                     n += 1
                     yield chunk[i]
         readers = [frames_of(k, st) for k, st in enumerate(streams)]
+
+        def boxes_of(k):
+            """the boxes of stream k one by one, chunk after chunk"""
+            feed = tracks[k].feed
+            for chunk in [feed.whole] if feed.whole is not None else feed.chunks:
+                if control_streams.check_boxes(chunk, f"stream {k}: a chunk of 'boxes'") is not None:
+                    raise ValueError(f"stream {k}: 'boxes' must be [N,4]")
+                yield from chunk
+        box_readers = [boxes_of(k) for k in range(len(tracks))]
 
         def batches():
             at = 0
@@ -1652,10 +1768,26 @@ class InferenceWrapper:
             frame_of = [i - b0 for i in range(b0, b1) for _ in range(counts[i])]
             out = None
             if m1 > m0:
-                crops = ops.crop_faces_mixed(frames, S, wins[m0:m1], frame_of, *plan.fmt)
+                crop_w = paste_w = wins[m0:m1]
+                if tracked:
+                    # the boxes of the batch's rows (row i: frame t of stream s), one upload and ONE launch for the batch
+                    of_row, boxes = [s for s, _ in order[b0:b1]], []
+                    for s, t in order[b0:b1]:
+                        box = next(box_readers[s], None)
+                        if box is None:
+                            raise ValueError(f"stream {s}: its 'boxes' ended before its frames did, at frame {t}")
+                        boxes.append(box.to(self.device).double())
+                    sizes = [frames_mod.frame_size(f[None], plan.fmt[0])[::-1] for f in frames]
+                    crop_w, paste_w, _ = ops.crop_track(torch.stack(boxes), torch.tensor(of_row, dtype=torch.int32).to(self.device), sizes,
+                                                        *crop_states.arrays(), momentum=plan.track.momentum, smooth=plan.track.smooth,
+                                                        fixed=plan.track.fixed, scale=plan.track.scale, box_format=plan.track.box_format,
+                                                        missing=plan.track.missing, min_side=plan.min_side)
+                    self.tracked_windows = (paste_w, m0)
+                    crop_w, paste_w = ops.DeviceWindows(crop_w), ops.DeviceWindows(paste_w)
+                crops = ops.crop_faces_mixed(frames, S, crop_w, frame_of, *plan.fmt)
                 out, m = self._drive_crops(crops, None if ids_dev is None else ids_dev[m0:m1], plan, smooth=smooth_pose, row0=m0)
                 if paste_back:
-                    ops.paste_faces_mixed(frames, out, wins[m0:m1], frame_of, feather, m, *plan.fmt)
+                    ops.paste_faces_mixed(frames, out, paste_w, frame_of, feather, m, *plan.fmt)
             if paste_back:
                 meta, out = [(s, t, tuple(f.shape)) for (s, t), f in zip(order[b0:b1], frames)], arena
             else:

@@ -695,10 +695,29 @@ def windows_host(windows, M, size, what, rows="frames", paste_S=None):
     return host
 
 
+class DeviceWindows:
+    """int32 [M,4] windows that lie in the frames' memory already and were formed there -- crop_track's outputs -- as the `windows`
+    of the crop and paste ops: taken like a cuda tensor (no host copy, so no host check: crop_track has made the test against each
+    row's frame, and the paste kernels repeat it) wherever the frames are.  Slicing gives the windows of those rows."""
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+    def __len__(self):
+        return self.tensor.shape[0]
+
+    def __getitem__(self, rows):
+        return DeviceWindows(self.tensor[rows])
+
+
 def _windows_arg(windows, M, size, device, what, rows="frames", paste_S=None):
     """windows -> (int32 [M,4] device tensor, host tensor or None): a host sequence goes through windows_host and is uploaded
-    (16 bytes per window); a ready device tensor is checked for device, dtype and shape (RuntimeError) and trusted otherwise"""
-    if isinstance(windows, torch.Tensor) and windows.is_cuda:
+    (16 bytes per window); a ready device tensor (or DeviceWindows) is checked for device, dtype and shape (RuntimeError) and
+    trusted otherwise"""
+    formed = isinstance(windows, DeviceWindows)
+    if formed:
+        windows = windows.tensor
+    if formed or isinstance(windows, torch.Tensor) and windows.is_cuda:
         if windows.device != device or windows.dtype != torch.int32 or tuple(windows.shape) != (M, 4) or not windows.is_contiguous():
             raise RuntimeError("windows must be a contiguous int32 tensor [M,4] on the frames' device" if isinstance(size, torch.Tensor)
                                else "windows must be a contiguous int32 cuda tensor [N,4]")
@@ -1332,3 +1351,74 @@ def head_pose_controls(scale, rotation, translation, stream_of=None, source=None
                                              hip.ptr(has_anchor if relative else None), n, K, int(bool(relative)), int(bool(frontal)),
                                              hip.ptr(srt), hip.ptr(theta), hip.current_stream()), "emo_head_pose_controls_f32")
     return srt, theta
+
+
+def crop_track(boxes, stream_of=None, size=None, state=None, has_state=None, last=None, momentum=0.01, smooth=False, fixed=False,
+               scale=1.0, box_format="xyxy", missing="skip", min_side=2, K=None):
+    """Face boxes -> crop and paste windows on the device, the crop tracker's state carried along the row order
+    (emo_crop_track_f64; bit for bit hostglue.crop_track, which states the arithmetic: crop_image's, notebooks/infer.py:301-352).
+    boxes [M,4] float32 or float64 on the device (widened exactly to float64), IN FRAME ORDER; stream_of int32 [M] (or None: one
+    stream, 0); size = (W, H) of every row's frame, or one (W, H) per row as a host sequence (checked and uploaded here) or an
+    int32 [M,2] device tensor; state [K,3] float64, has_state [K] int32 and last [K,4] int32 are the streams' state, updated in
+    place (state and has_state are needed by `smooth`, last by missing='hold'; K says the number of streams where none is given).
+    -> (crop int32 [M,4], paste int32 [M,4], face_scale float64 [M]): every crop window can be read from its row's frame, a paste
+    window of side 0 says that the row has no face.  One launch, no host synchronisation."""
+    from . import hostglue
+    lib = hip.load()
+    if not isinstance(boxes, torch.Tensor) or boxes.dtype not in (torch.float32, torch.float64):
+        raise ValueError("crop_track: boxes must be a float32 or float64 tensor")
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.shape[0] == 0:
+        raise ValueError(f"crop_track expects [M,4] boxes, got {tuple(boxes.shape)}")
+    hip.require_cuda_f32(torch.empty(0, device=boxes.device))                # (GPU only, like every op)
+    M, dev = boxes.shape[0], boxes.device
+    boxes = boxes.double().contiguous()
+    if box_format not in hostglue.CROP_BOX_FORMATS:
+        raise ValueError(f"crop_track: box_format {box_format!r}: 'xyxy' or 'relative'")
+    if missing not in hostglue.CROP_MISSING:
+        raise ValueError(f"crop_track: missing {missing!r}: 'skip' or 'hold'")
+    m = float(momentum)
+    if not 0.0 < m <= 1.0:
+        raise ValueError(f"crop_track: momentum {momentum} is not in (0, 1]")
+    scale = float(scale)
+    if scale != scale or scale in (float("inf"), float("-inf")):
+        raise ValueError(f"crop_track: scale {scale} is not finite")
+    if int(min_side) < 1:
+        raise ValueError(f"crop_track: min_side {min_side} is below 1")
+    hold = missing == "hold"
+    if smooth and (state is None or has_state is None):
+        raise ValueError("crop_track: smoothing needs state and has_state")
+    if hold and last is None:
+        raise ValueError("crop_track: missing='hold' needs last")
+    given = [t.shape[0] for t in (state, has_state, last) if t is not None]
+    K = given[0] if given else (1 if K is None else int(K))
+    if K < 1:
+        raise ValueError("crop_track: no streams")
+    if state is not None and (state.dtype != torch.float64 or state.device != dev or tuple(state.shape) != (K, 3) or not state.is_contiguous()):
+        raise ValueError(f"crop_track: state must be a contiguous float64 [{K},3] tensor on the boxes' device")
+    if has_state is not None:
+        _check_index(has_state, K, dev, "has_state")
+    if last is not None and (last.dtype != torch.int32 or last.device != dev or tuple(last.shape) != (K, 4) or not last.is_contiguous()):
+        raise ValueError(f"crop_track: last must be a contiguous int32 [{K},4] tensor on the boxes' device")
+    if stream_of is not None:
+        _check_index(stream_of, M, dev, "stream_of")
+    sizes, Wf, Hf = None, 0, 0
+    if isinstance(size, torch.Tensor) and size.device == dev and size.dtype == torch.int32 and size.dim() == 2:
+        if tuple(size.shape) != (M, 2) or not size.is_contiguous():
+            raise ValueError(f"crop_track: per-row sizes must be a contiguous int32 [{M},2] tensor, got {tuple(size.shape)}")
+        sizes = size
+    else:
+        host = torch.as_tensor(size, dtype=torch.int64)
+        if tuple(host.shape) not in ((2,), (M, 2)) or bool((host < 1).any()) or bool((host >= 1 << 30).any()):
+            raise ValueError(f"crop_track: size is the (W, H) of every frame or one per row, positive: got {size!r}")
+        if host.dim() == 1:
+            Wf, Hf = int(host[0]), int(host[1])
+        else:
+            sizes = host.to(torch.int32).to(dev, non_blocking=True)
+    crop = torch.empty((M, 4), device=dev, dtype=torch.int32)
+    paste = torch.empty((M, 4), device=dev, dtype=torch.int32)
+    face_scale = torch.empty((M,), device=dev, dtype=torch.float64)
+    hip.check(lib.emo_crop_track_f64(hip.ptr(boxes), hip.ptr(stream_of), hip.ptr(sizes), Wf, Hf, hip.ptr(state if smooth else None),
+                                     hip.ptr(has_state if smooth else None), hip.ptr(last), M, K, m, 1.0 - m, int(bool(smooth)),
+                                     int(bool(fixed)), scale, hostglue.CROP_BOX_FORMATS[box_format], int(hold), int(min_side),
+                                     hip.ptr(crop), hip.ptr(paste), hip.ptr(face_scale), hip.current_stream()), "emo_crop_track_f64")
+    return crop, paste, face_scale

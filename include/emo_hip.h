@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 22
+#define EMO_ABI_VERSION 23
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -516,6 +516,42 @@ int emo_head_pose_controls_f32(const float* scale, int scale_cols, const float* 
                                const int32_t* stream_of, const float* source, const float* gain, const float* rotation_offset,
                                const float* translation_offset, const float* zoom, float* anchor, int32_t* has_anchor, int n,
                                int K, int relative, int frontal, float* out_srt, float* out_theta, void* stream);
+/* ABI 23.  Face boxes in, crop windows out: the window arithmetic of crop_image (notebooks/infer.py:301-352: box -> centre and
+ * size, `scale`, the use_smoothed_crop EMA, fixed_bounding_box, remove_overflow at :243-261) for the M rows of a batch, with the
+ * tracker's state carried along the row order.  Row i (boxes [M,4] DOUBLE, frame order) belongs to tracker stream k = stream_of[i]
+ * ([M] int32 DEVICE memory, or NULL: stream 0) and to a frame of W x H pixels = sizes[i] ([M,2] int32 DEVICE memory = (W, H) per
+ * row, or NULL: Wf x Hf for every row).  state [K,3] double = (cx, cy, size) with its flags has_state [K] int32, and last [K,4]
+ * int32, the stream's last present window (side 0: none), are read and written; state and has_state may be NULL without
+ * `smooth`, last may be NULL without `hold` (it is then not kept).  crop and paste [M,4] int32 = (x0, y0, w, h); face_scale [M]
+ * double or NULL.  Every operation is a double operation rounded on its own (no contraction); a value becomes an integer only
+ * after its range test:
+ *   box:      box_format 0: (x0, y0, x1, y1) = boxes[i].  box_format 1: boxes[i] = (xmin, ymin, width, height) relative to the
+ *             frame, x0 = W * xmin, y0 = (H * ymin) * 0.9, x1 = W * (xmin + width), t = H * (ymin + height * 1.2),
+ *             y1 = H - 1 if H - 1 < t else t   (notebooks/infer.py:385-391)
+ *   missing:  a component of the box is not finite or has magnitude >= 2^30, or k is outside [0, K).  A missing row does not
+ *             touch the tracker; a k outside [0, K) touches no state at all.
+ *   centre:   cx = floor((x1 + x0) / 2), cy = floor((y1 + y0) / 2), size = (((x1 - x0) + y1) - y0) * scale
+ *   smooth:   a stream without state takes (cx, cy, size) as its state (has_state[k] = 1 afterwards); otherwise, unless `fixed`,
+ *             state = v * m + state * om for each of the three, om = 1 - momentum formed by the caller in double; the row goes
+ *             on with the state
+ *   window:   cx, cy, size = rint of each (half to even); absent unless size is finite and >= 2; size -= fmod(size, 2);
+ *             half = size / 2, b = (cx - half, cy - half, cx + half, cy + half), over = max(0 | -b0, 0 | -b1, 0 | b2 - W,
+ *             0 | b3 - H) (each term where the box leaves the frame), b0 += over, b1 += over, b2 -= over, b3 -= over;
+ *             side = trunc((b2 - b0 + b3 - b1) / 2), side -= fmod(side, 2); absent unless side >= 2; absent unless |cx|, |cy| and
+ *             side are below 2^30; then, as integers, x_lo = cx - side / 2, y_lo = cy - side / 2
+ *   present:  side > 0, x_lo >= 0, y_lo >= 0, x_lo <= W - side, y_lo <= H - side (the test the crop and paste entry points make
+ *             of a host window) and side >= min_side.  Then crop[i] = paste[i] = (x_lo, y_lo, side, side), last[k] is that window
+ *             and face_scale[i] = side / size (the even size).
+ *   missing or absent:  face_scale[i] = 0.  With `hold`, if last[k] has a side and passes the test of `present` for this row's
+ *             frame: crop[i] = paste[i] = last[k].  Otherwise crop[i] = the centred square of side s = min(W, H) at
+ *             ((W - s) / 2, (H - s) / 2), which can always be read, and paste[i] = (0, 0, 0, 0), which every paste entry point
+ *             skips.
+ * -- bit for bit hostglue.crop_track.  EMO_ERR_BAD_ARG before any launch: boxes, crop or paste NULL; M or K <= 0; sizes NULL and
+ * Wf or Hf < 1; smooth without state and has_state; hold without last; m outside (0, 1] or om outside [0, 1); a scale that is
+ * not finite; box_format not 0 or 1; min_side < 1.  Streams across threads, each walking its rows in order; no atomics. */
+int emo_crop_track_f64(const double* boxes, const int32_t* stream_of, const int32_t* sizes, int Wf, int Hf, double* state,
+                       int32_t* has_state, int32_t* last, int M, int K, double m, double om, int smooth, int fixed, double scale,
+                       int box_format, int hold, int min_side, int32_t* crop, int32_t* paste, double* face_scale, void* stream);
 int emo_pack_rgb8(const float* img, uint8_t* out, int N, int H, int W, void* stream);
 int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int W, void* stream);
 

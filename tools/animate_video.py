@@ -10,6 +10,11 @@
         [--mix [--mix-new]] [--source-pose] [--smooth-pose]   # forward()'s pose controls (mix, mix_old=False, target_theta=False)
         [--relative-pose] [--pose-gain G] [--yaw R --pitch R --roll R] [--pose-zoom Z] [--frontal]   # the head-pose controls
          (animate_frames' head_pose=): keep the avatar's own head pose and follow the driver's motion, damp it, turn the head, look ahead
+        [--boxes boxes.json|.npy|.pt [--box-format relative] [--smooth-crop [--crop-momentum M] [--fixed-crop]] [--crop-scale S]
+         [--hold-missing]]   # in place of --windows / --faces: the detector's face boxes, [N,4] (x0, y0, x1, y1) in pixels (or mediapipe's
+         relative (xmin, ymin, width, height)), or [N,P,4] for P tracks per frame; the windows are formed on the device
+         (animate_frames' boxes= / tracking=: crop_image's arithmetic with its smoothed-crop tracker); a frame whose box is NaN has
+         no face: it is not pasted, or with --hold-missing pasted at the track's last window
         [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
         [--stage2-experiment <exp2> --stage2-checkpoint <file> [--cloth]       # refine every batch with the stage-2 model
          (--embedders module:factory | --refine-everywhere)]                   # (<project>/logs_s2/<exp2>), inside the same path
@@ -67,6 +72,18 @@ def load_nv12(path, width, height, chunk, frame_format="nv12"):
         yield torch.from_numpy(np.array(arr[a:a + chunk])).pin_memory()          # (a copy: the map is read-only)
 
 
+def load_boxes(path):
+    """face boxes [N,4] or [N,P,4] from a .pt, .npy or .json file as a floating-point tensor; a JSON null is a missing coordinate
+    (NaN: a frame whose box is [null, null, null, null] has no face)"""
+    if path.endswith(".pt"):
+        t = torch.load(path, map_location="cpu")
+    elif path.endswith(".npy"):
+        t = torch.from_numpy(np.load(path))
+    else:
+        t = torch.from_numpy(np.array(json.load(open(path)), dtype=np.float64))
+    return t if t.dtype in (torch.float32, torch.float64) else t.double()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--project", required=True)
@@ -79,6 +96,13 @@ def main():
     ap.add_argument("--frames", required=True)
     ap.add_argument("--windows", default=None)
     ap.add_argument("--faces", default=None, help="several faces per frame: a JSON list per frame of [x_lo, y_lo, side], in paste order")
+    ap.add_argument("--boxes", default=None, help="face boxes [N,4] (or [N,P,4]) as .json, .npy or .pt: windows formed on the device")
+    ap.add_argument("--box-format", default="xyxy", choices=["xyxy", "relative"], help="pixel (x0, y0, x1, y1), or mediapipe's relative box")
+    ap.add_argument("--smooth-crop", action="store_true", help="the reference's use_smoothed_crop: an EMA of the box centre and size")
+    ap.add_argument("--crop-momentum", type=float, default=None, help="with --smooth-crop: 0 < M <= 1 (default: the wrapper's 0.01)")
+    ap.add_argument("--fixed-crop", action="store_true", help="with --smooth-crop: every frame takes the first box (fixed_bounding_box)")
+    ap.add_argument("--crop-scale", type=float, default=1.0, help="multiplies the box size (crop_image's scale)")
+    ap.add_argument("--hold-missing", action="store_true", help="a frame without a usable box takes the track's last window")
     ap.add_argument("--sources", default=None, help="comma-separated source images enrolled into bank slots 0, 1, ... (--identities)")
     ap.add_argument("--identities", default=None, help="JSON list: the bank slot of every frame, or with --faces of every face")
     ap.add_argument("--out", required=True)
@@ -101,7 +125,7 @@ def main():
     ap.add_argument("--roll", type=float, default=0.0, help="radians added to the roll")
     ap.add_argument("--pose-zoom", type=float, default=1.0, help="multiplies the head pose's scale")
     ap.add_argument("--frontal", action="store_true", help="look straight ahead: yaw = pitch = 0, translation = 0 (the reference's normalize)")
-    ap.add_argument("--paste-back", action="store_true", help="write the full frames with the rendered crops pasted back (needs --windows or --faces)")
+    ap.add_argument("--paste-back", action="store_true", help="write the full frames with the rendered crops pasted back (needs --windows, --faces or --boxes)")
     ap.add_argument("--feather", type=float, default=0.0625, help="with --paste-back: blended edge as a fraction of the window side")
     ap.add_argument("--stage2-experiment", default=None, help="refine with the stage-2 model <project>/logs_s2/<this>")
     ap.add_argument("--stage2-checkpoint", default=None)
@@ -128,6 +152,14 @@ def main():
         ap.error("--frame-size / --colorspace / --full-range belong to --frame-format nv12")
     if a.faces and a.windows:
         ap.error("--faces and --windows are mutually exclusive")
+    if a.boxes and (a.faces or a.windows):
+        ap.error("--boxes (windows formed on the device) and --windows / --faces (ready windows) are mutually exclusive")
+    if not a.boxes and (a.box_format != "xyxy" or a.smooth_crop or a.fixed_crop or a.crop_scale != 1.0 or a.hold_missing):
+        ap.error("--box-format / --smooth-crop / --fixed-crop / --crop-scale / --hold-missing belong to --boxes")
+    if (a.crop_momentum is not None or a.fixed_crop) and not a.smooth_crop:
+        ap.error("--crop-momentum / --fixed-crop belong to --smooth-crop")
+    if a.crop_momentum is not None and not 0.0 < a.crop_momentum <= 1.0:
+        ap.error("--crop-momentum: 0 < M <= 1")
     if (a.sources is None) != (a.identities is None):
         ap.error("--sources (the images of the bank's slots) and --identities (the slot of every face or frame) go together")
     if a.smooth_pose and a.faces and not a.identities:
@@ -180,6 +212,11 @@ def main():
     w.forward(source_image=src, crop=False, source_mask=mask)
     windows = json.load(open(a.windows)) if a.windows else None
     faces = json.load(open(a.faces)) if a.faces else None
+    boxes = tracking = None
+    if a.boxes:
+        boxes = load_boxes(a.boxes)
+        tracking = dict(smooth=a.smooth_crop, momentum=a.crop_momentum, fixed=a.fixed_crop, scale=a.crop_scale, box_format=a.box_format,
+                        missing="hold" if a.hold_missing else "skip")
     identities = None
     if sources:
         w.enrol_identities([Image.open(f).convert("RGB") for f in sources], slots=list(range(len(sources))), batch_size=a.batch)
@@ -202,7 +239,7 @@ def main():
                                       mix_old=not a.mix_new, target_theta=not a.source_pose, smooth_pose=a.smooth_pose,
                                       smooth_per_identity=identities is not None, paste_back=a.paste_back,
                                       feather=a.feather, refine=refine, refine_masks=refine_masks, expression=expression,
-                                      head_pose=head_pose, **fmt):
+                                      head_pose=head_pose, boxes=boxes, tracking=tracking, **fmt):
         arr = u8.numpy()
         if nv12:
             sink.write(arr.tobytes())                             # batches come in frame order (one rank)
