@@ -1359,13 +1359,15 @@ class InferenceWrapper:
                 raise ValueError(f"identities has {len(identities)} entries for {n_rows} faces: one slot per face")
         else:
             wins = None if windows is None else frames_mod.square_windows(windows)
-        plan = self._video_plan(n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
-                                target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format,
-                                out_format, colorspace, full_range, expression=expression,
+        plan = self._video_plan(n_rows=n_rows, wins=wins, identities=identities, batch_size=batch_size, ring=ring, to_host=to_host,
+                                smooth_pose=smooth_pose, smooth_per_identity=smooth_per_identity, mix=mix, mix_old=mix_old,
+                                target_theta=target_theta, paste_back=paste_back, feather=feather, paste_matte=paste_matte,
+                                as_uint8=as_uint8, refine=refine, refine_masks=refine_masks, frame_format=frame_format,
+                                out_format=out_format, colorspace=colorspace, full_range=full_range, expression=expression,
                                 faces=faces is not None or track is not None and track.tracks is not None, head_pose=head_pose, track=track)
         yield from self._animate_clip(frames, wins, counts, plan)
 
-    def _video_plan(self, n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
+    def _video_plan(self, *, n_rows, wins, identities, batch_size, ring, to_host, smooth_pose, smooth_per_identity, mix, mix_old,
                     target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format,
                     colorspace, full_range, arena=False, expression=None, where='animate_frames', faces=False, head_pose=None,
                     track=None):
@@ -1411,52 +1413,71 @@ class InferenceWrapper:
                          batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta, ex=ex,
                          hp=hp, track=track, min_side=min_side)
 
+    def _batch_theta(self, crops, ident, plan, row0, edit=True, mix=True, smooth=None):
+        """The front of a driver batch of the video paths, crops [m,3,S,S] = the rows row0 ... of the call -> (theta, align): the head
+        pose the regressor finds, edited per row by the head-pose controls (plan.hp) and then mixed, and what the expression embedder
+        aligns the crops by -- under an active head-pose edit the regressor's OWN theta of the rows, else None = the theta the batch
+        is rendered with.  Either may be the regressor's output buffer: a caller that holds it past the batch clones it.
+        edit=False: a pass that gathers the rows of every rank edits them, and in theta's place come the regressed (scale, rotation,
+        translation) as [m,9] rows.  mix=False: the caller mixes, once over its rows of the chunk.  smooth: None = mix alone, and
+        only where plan.mix asks for it (a clip); a bool = mix and the one-pass smooth_pose of the batch's rows (streams)."""
+        theta, *srt = self._head_pose(crops)
+        align = None
+        if plan.hp is not None:
+            align = theta
+            theta = self._head_pose_controls(srt, ident, plan.hp, row0)[1] if edit else self._srt9(srt)
+        if mix and (plan.mix or smooth is not None):
+            theta = self._pose_controls(theta, ident, plan.mix, plan.mix_old, bool(smooth))
+        return theta, align
+
+    def _batch_expression(self, crops, theta, align):
+        """the expression embedder on a driver batch: its crops aligned by `align` (_batch_theta), or by the theta it is rendered with"""
+        return self._expression(crops, theta if align is None else align, 'a driver call')[0]
+
     def _drive_crops(self, crops, ident, plan, theta=None, smooth=None, row0=0, pose=None, align=None):
         """The sequence of one driver batch of the video paths, crops [m,3,S,S] -> (the rendered batch as plan.out_kind says, its
-        paste matte or None): head pose -> pose controls -> expression embedder (or the override) -> expression controls -> render
-        -> matte, in forward()'s order.  row0: the batch's first row in the call (the controls' per-row values); pose: the batch's
-        controlled expressions where a pass in front of the loop has formed them (a scan over the rows of several ranks).
-        theta: the batch's thetas where a pass in front of the loop has formed them (the two-pass smooth_pose of a clip).
-        smooth: None = mix alone, and only where it is asked for (a clip); a bool = mix and the one-pass smooth_pose of the
-        batch's rows (streams).  With head-pose controls (plan.hp) the regressed (scale, rotation, translation) are edited before
-        mix and smooth_pose, and the expression embedder is handed `align`, the regressor's own theta of the rows (formed here,
-        or by the pass that formed `theta`); align=None: the theta the batch is rendered with, as without the controls."""
+        paste matte or None): head pose -> head-pose controls -> pose controls (_batch_theta) -> expression embedder (or the
+        override) -> expression controls -> render -> matte, in forward()'s order.  row0: the batch's first row in the call (the
+        controls' per-row values).  theta, align: the batch's thetas and what the embedder aligns by where a pass in front of the
+        loop has formed them (the passes of a clip that walk the rows of several ranks); pose: its controlled expressions
+        likewise.  smooth: _batch_theta's."""
         if theta is None:
-            theta, *srt = self._head_pose(crops)
-            if plan.hp is not None:
-                align = theta
-                theta = self._head_pose_controls(srt, ident, plan.hp, row0)[1]
-            if plan.mix or smooth is not None:
-                theta = self._pose_controls(theta, ident, plan.mix, plan.mix_old, bool(smooth))
+            theta, align = self._batch_theta(crops, ident, plan, row0, smooth=smooth)
         self.pred_target_theta = theta                                           # (as forward() leaves it: infer.py:584)
         ex = plan.ex
         if pose is None:
             if ex is not None and ex.override is not None:
                 pose = control_streams.rows_of(ex.override, row0, crops.shape[0], 'expression override')
             else:
-                pose, _ = self._expression(crops, theta if align is None else align, 'a driver call')
+                pose = self._batch_expression(crops, theta, align)
             if ex is not None:
                 pose = self._expression_controls(pose, ident, ex, row0)
         out = self._render(pose, theta, ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
         return out, (None if plan.matte_fn is None else plan.matte_fn(out).float().contiguous())
 
-    def _track_chunk(self, track, n, base, frame_hw, min_side, row0):
-        """boxes= for the n frames of a chunk (the frames base ... of the call, H x W = frame_hw): their boxes from the feed, ONE
-        launch over all their rows in frame order (ops.crop_track, bit for bit hostglue.crop_track) with the tracks' state carried
-        in _crop_streams -> (crop, paste) windows of the chunk's rows as ops.DeviceWindows.  Track p of boxes [N,P,4] is tracker
-        stream p; the store is made anew when the number of tracks changes.  tracked_windows = (paste [rows,4], row0)."""
-        boxes = track.feed.take(n, base)
-        K = track.tracks or 1
-        if self._crop_streams is None or self._crop_streams.K != K:
-            self._crop_streams = control_streams.CropStates(K, self.device)
-        stream_of = None
-        if track.tracks is not None:
-            stream_of = torch.arange(K, dtype=torch.int32).repeat(n).to(self.device)
-        crop, paste, _ = ops.crop_track(boxes.reshape(-1, 4), stream_of, (frame_hw[1], frame_hw[0]), *self._crop_streams.arrays(),
-                                        momentum=track.momentum, smooth=track.smooth, fixed=track.fixed, scale=track.scale,
-                                        box_format=track.box_format, missing=track.missing, min_side=min_side)
+    def _track(self, states, boxes, stream_of, sizes, plan, row0):
+        """boxes= -> windows: ONE launch over the rows `boxes` [m,4] in frame order (ops.crop_track, bit for bit hostglue.crop_track),
+        row i on track stream_of[i] of `states` (a control_streams.CropStates; None: the one track) in a frame of sizes = (W, H), or
+        one (W, H) per row, with the settings of plan.track -> (crop, paste) windows of the rows as ops.DeviceWindows.
+        tracked_windows = (paste [m,4], row0 = the first row's index in the call)."""
+        t = plan.track
+        crop, paste, _ = ops.crop_track(boxes, stream_of, sizes, *states.arrays(), momentum=t.momentum, smooth=t.smooth, fixed=t.fixed,
+                                        scale=t.scale, box_format=t.box_format, missing=t.missing, min_side=plan.min_side)
         self.tracked_windows = (paste, row0)
         return ops.DeviceWindows(crop), ops.DeviceWindows(paste)
+
+    def _track_chunk(self, plan, n, base, frame_hw, row0):
+        """boxes= for the n frames of a chunk (the frames base ... of the call, H x W = frame_hw): their boxes from the feed, tracked
+        over all their rows in frame order (_track) with the tracks' state carried in _crop_streams.  Track p of boxes [N,P,4] is
+        tracker stream p; the store is made anew when the number of tracks changes."""
+        if n == 0:
+            return (ops.DeviceWindows(torch.empty((0, 4), dtype=torch.int32, device=self.device)),) * 2
+        boxes = plan.track.feed.take(n, base)
+        K = plan.track.tracks or 1
+        if self._crop_streams is None or self._crop_streams.K != K:
+            self._crop_streams = control_streams.CropStates(K, self.device)
+        stream_of = None if plan.track.tracks is None else torch.arange(K, dtype=torch.int32).repeat(n).to(self.device)
+        return self._track(self._crop_streams, boxes.reshape(-1, 4), stream_of, (frame_hw[1], frame_hw[0]), plan, row0)
 
     def _animate_clip(self, frames, wins, counts, plan):
         """animate_frames behind its checks.  A row of everything between the crop and the paste is a face: wins = the
@@ -1464,148 +1485,127 @@ class InferenceWrapper:
         row (host tensor) or None.  counts=None is windows= / whole frames: one row per frame (wins None: the whole frame), the
         per-frame entry points (frame_of=None) and the single-stream smooth_pose.  Per chunk the frames are sharded across the
         ranks; a batch is a span of whole frames (frames.face_spans).  With plan.track (boxes=) wins is None: the windows of a
-        chunk are formed on the device in front of its batches (_track_chunk), P rows per frame where the boxes are [N,P,4]."""
+        chunk are formed on the device in front of its batches (_track_chunk), P rows per frame where the boxes are [N,P,4].
+        A chunk is rendered in up to three passes over the spans of the rank's frames, each through `walk`: the head-pose pass
+        (smooth_pose, or a relative head pose on several ranks) and the expression pass (relative / smooth on several ranks) form
+        the thetas and the expressions that follow the frame order across the ranks (`scan`), the render pass drives the batches."""
         S, ids, paste_back, ex, hp = self.cfg["image_size"], plan.ids, plan.paste_back, plan.ex, plan.hp
-        track = plan.track
-        P = None if track is None else track.tracks
-        first = None if counts is None else frames_mod.face_offsets(counts)
-        base = 0
+        P = None if plan.track is None else plan.track.tracks
+        base = row0 = 0
         for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
             frames_mod.check_frames(chunk, plan.fmt[0])
             n = chunk.shape[0]
             if counts is not None and base + n > len(counts):
                 raise ValueError(f"faces has {len(counts)} entries, the frames run past it")
-            if counts is None and ids is not None and (base + n) * (P or 1) > ids.shape[0]:
+            # which rows a span of frames holds: per[i] = the rows of the chunk's frame i -- the faces of faces=, the P tracks of boxes
+            # [N,P,4], or None for one row per frame and the per-frame entry points (windows=, boxes [N,4], whole frames)
+            per = [P] * n if P is not None else None if counts is None else counts[base:base + n]
+            off = frames_mod.face_offsets([1] * n if per is None else per)
+            if counts is None and ids is not None and row0 + off[n] > ids.shape[0]:
                 raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
+            rows = lambda b0, b1: (row0 + off[b0], row0 + off[b1])              # the rows of the chunk's frames [b0, b1)
+            frame_of = lambda b0, b1: None if per is None else [i - b0 for i in range(b0, b1) for _ in range(per[i])]
             lo, hi = parallel.shard_range(n, self.rank, self.world)
-            if P is not None:                                                    # (P tracks in every frame: faces= with counts = [P] * n)
-                spans = frames_mod.face_spans([P] * n, lo, hi, plan.batch_size)
-                rows = lambda b0, b1: ((base + b0) * P, (base + b1) * P)
-                frame_of = lambda b0, b1: [i - b0 for i in range(b0, b1) for _ in range(P)]
-            elif counts is None:
-                spans = [(b0, min(b0 + plan.batch_size, hi)) for b0 in range(lo, hi, plan.batch_size)]
-                rows = lambda b0, b1: (base + b0, base + b1)                     # the rows of the chunk's frames [b0, b1)
-                frame_of = lambda b0, b1: None
-            else:
-                spans = frames_mod.face_spans(counts[base:base + n], lo, hi, plan.batch_size)
-                rows = lambda b0, b1: (first[base + b0], first[base + b1])
-                frame_of = lambda b0, b1: [i - b0 for i in range(b0, b1) for _ in range(counts[base + i])]
-            wins_of = paste_wins_of = lambda b0, b1: None if wins is None else wins[slice(*rows(b0, b1))]
-            if track is not None:
-                # every rank tracks the whole chunk (the boxes are inputs every rank has), then slices its batches' windows
-                r00 = rows(0, 0)[0]
-                crop_w, paste_w = self._track_chunk(track, n, base, frames_mod.frame_size(chunk, plan.fmt[0]), plan.min_side, r00) \
-                    if n else (ops.DeviceWindows(torch.empty((0, 4), dtype=torch.int32, device=self.device)),) * 2
-                wins_of = lambda b0, b1: crop_w[slice(*(r - r00 for r in rows(b0, b1)))]
-                paste_wins_of = lambda b0, b1: paste_w[slice(*(r - r00 for r in rows(b0, b1)))]
-            crops_of = lambda u8, b0, b1: frames_mod.crops_of(u8, S, wins_of(b0, b1), *plan.fmt, frame_of=frame_of(b0, b1))
+            spans = frames_mod.face_spans([1] * n if per is None else per, lo, hi, plan.batch_size)
             with_faces = [sp for sp in spans if rows(*sp)[0] < rows(*sp)[1]]
-            m_lo, m_hi = rows(lo, hi)
+            (r0, r1), (m_lo, m_hi) = rows(0, n), rows(lo, hi)
+            # of something that has one entry per row of the rank's shard of the chunk, the entries of the frames [b0, b1)
+            part = lambda t, b0, b1: None if t is None else t[rows(b0, b1)[0] - m_lo:rows(b0, b1)[1] - m_lo]
+            crop_w = paste_w = None if wins is None else wins[m_lo:m_hi]
+            if plan.track is not None:
+                # every rank tracks the whole chunk (the boxes are inputs every rank has), then slices its batches' windows
+                crop_w, paste_w = (w[m_lo - r0:m_hi - r0]
+                                   for w in self._track_chunk(plan, n, base, frames_mod.frame_size(chunk, plan.fmt[0]), r0))
             ids_dev = None if ids is None else ids[m_lo:m_hi].to(self.device)
-            smoothed, kept, aligns = None, {}, {}
-            # a relative head pose walks the rows of every rank: their regressed (scale, rotation, translation) are gathered in row
-            # order and edited on every rank, so the anchor is the stream's first row whichever rank regressed it
+            # crops stay resident from one pass to the next (3 MB per frame at 512^2) while the rank's rows of the chunk fit the budget
+            keep = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
+            kept, thetas, aligns, poses = {}, {}, {}, None
+
+            def walk(last=False):
+                """(b0, b1, crops, uploaded frames or None) for every span a pass needs: the crops an earlier pass kept, or a fresh
+                upload (span i + 1 beside the compute of span i: frames.uploaded) and ONE crop launch.  A span without a face is not
+                uploaded for crops, a kept span not again -- unless its frames are what the render is pasted into (last, with
+                paste_back: the crops were kept, not the frames, 6 MB at 1080p; a span without a face then comes with crops None).
+                The last pass lets go of what was kept."""
+                pasted = last and paste_back
+                need = spans if pasted else with_faces
+                fresh = frames_mod.uploaded(chunk, [sp for sp in need if pasted or sp[0] not in kept], self.device, plan.upload_stream)
+                for b0, b1 in need:
+                    crops, u8 = kept.pop(b0, None) if last else kept.get(b0), None
+                    if crops is None or pasted:
+                        f0, f1, u8 = next(fresh)
+                        assert (f0, f1) == (b0, b1)
+                    if crops is None and (b0, b1) in with_faces:
+                        crops = frames_mod.crops_of(u8, S, part(crop_w, b0, b1), *plan.fmt, frame_of=frame_of(b0, b1))
+                        if keep and not last:
+                            kept[b0] = crops
+                    yield b0, b1, crops, u8
+
+            def scan(control, local=None, every=None):
+                """A control that walks the rows of every rank in frame order: the rank's rows `local` of the chunk are gathered in
+                row order on every rank (every=: rows every rank has already), control(all rows of the chunk, their slots, the
+                chunk's first row) runs over the whole chunk on every rank -- so the streams' state is the same everywhere,
+                whichever rank formed a row -- and the rank's own rows of the result come back."""
+                if every is None:
+                    per_rank = [rows(*parallel.shard_range(n, r, self.world)) for r in range(self.world)]
+                    every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)
+                return control(every, None if ids is None else ids[r0:r1].to(self.device), r0)[m_lo - r0:m_hi - r0]
+
+            # a relative head pose walks the rows of every rank: their regressed (scale, rotation, translation) are gathered and edited
+            # on every rank, so the anchor is the stream's first row whichever rank regressed it
             gather_srt = hp is not None and hp.relative and self.world > 1
             if plan.smooth_pose or gather_srt:
-                # two passes: the head pose of the rank's rows, gathered and scanned in frame order on every rank, then the render
-                keep_crops = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
                 local = []
-                for b0, b1, u8 in frames_mod.uploaded(chunk, with_faces, self.device, plan.upload_stream):
-                    crops = crops_of(u8, b0, b1)
-                    theta, *srt = self._head_pose(crops)
-                    if hp is None:
-                        local.append(theta.clone())
-                    else:
-                        aligns[b0] = theta.clone()                               # (what the expression embedder aligns by)
-                        if gather_srt:
-                            local.append(self._srt9(srt))
-                        else:
-                            m0, m1 = rows(b0, b1)
-                            ident = None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo]
-                            local.append(self._head_pose_controls(srt, ident, hp, m0)[1])
-                    if keep_crops:
-                        kept[b0] = crops
+                for b0, b1, crops, _ in walk():
+                    theta, align = self._batch_theta(crops, part(ids_dev, b0, b1), plan, rows(b0, b1)[0], edit=not gather_srt, mix=False)
+                    if align is not None:
+                        aligns[b0] = align.clone()
+                    local.append(theta.clone() if align is None else theta)
                 local = torch.cat(local) if local else torch.empty((0, 9) if gather_srt else (0, 4, 4), device=self.device)
-                per_rank = [rows(*parallel.shard_range(n, r, self.world)) for r in range(self.world)]
-                r0, r1 = rows(0, n)
-                ids_chunk = None if ids is None else ids[r0:r1].to(self.device)
                 if gather_srt:
-                    every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)
-                    every = tuple(every[:, i:i + 3].contiguous() for i in (0, 3, 6))
-                    local = self._head_pose_controls(every, ids_chunk, hp, r0)[1][m_lo - r0:m_hi - r0]
+                    local = scan(lambda every, slots, r: self._head_pose_controls(tuple(every[:, i:i + 3].contiguous() for i in (0, 3, 6)),
+                                                                                  slots, hp, r)[1], local)
                 if plan.mix:
                     local = self._pose_controls(local, ids_dev, True, plan.mix_old, False)
-                smoothed = local
                 if plan.smooth_pose:
-                    every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)   # row order, on every rank
-                    smoothed = self._pose_controls(every, ids_chunk, False, plan.mix_old, True)[m_lo - r0:m_hi - r0]
-            poses, thetas = None, {}
+                    local = scan(lambda every, slots, r: self._pose_controls(every, slots, False, plan.mix_old, True), local)
+                thetas = {b0: part(local, b0, b1) for b0, b1 in with_faces}
             if ex is not None and ex.scan and self.world > 1:
-                # relative / smooth walk the rows of every rank: the expressions of the rank's rows (the override's are known
-                # everywhere), gathered in row order and scanned on every rank, as the thetas above; then the render
-                r0, r1 = rows(0, n)
+                # relative / smooth walk the rows of every rank: the expressions of the rank's rows, or the override's, which every rank has
+                control = lambda every, slots, r: self._expression_controls(every, slots, ex, r)
                 if ex.override is not None:
-                    every = control_streams.rows_of(ex.override, r0, r1 - r0, 'expression override')
+                    poses = scan(control, every=control_streams.rows_of(ex.override, r0, r1 - r0, 'expression override'))
                 else:
-                    keep_crops = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
-                    again = frames_mod.uploaded(chunk, [sp for sp in with_faces if sp[0] not in kept], self.device, plan.upload_stream)
                     local = []
-                    for b0, b1 in with_faces:
-                        m0, m1 = rows(b0, b1)
-                        crops = kept.get(b0)
-                        if crops is None:
-                            crops = crops_of(next(again)[2], b0, b1)
-                            if keep_crops:
-                                kept[b0] = crops
-                        if smoothed is not None:
-                            theta = smoothed[m0 - m_lo:m1 - m_lo]
-                        else:
-                            ident = None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo]
-                            theta, *srt = self._head_pose(crops)
-                            if hp is not None:                                   # (not relative here: the edit is per row)
-                                aligns[b0] = theta.clone()
-                                theta = self._head_pose_controls(srt, ident, hp, m0)[1]
-                            if plan.mix:
-                                theta = self._pose_controls(theta, ident, True, plan.mix_old, False)
-                            thetas[b0] = theta = theta.clone()
-                        local.append(self._expression(crops, aligns.get(b0, theta), 'a driver call')[0].float().clone())
+                    for b0, b1, crops, _ in walk():
+                        if b0 not in thetas:
+                            theta, align = self._batch_theta(crops, part(ids_dev, b0, b1), plan, rows(b0, b1)[0])
+                            if align is not None:
+                                aligns[b0] = align.clone()
+                            thetas[b0] = theta.clone()
+                        local.append(self._batch_expression(crops, thetas[b0], aligns.get(b0)).float().clone())
                     if local:
                         local = torch.cat(local)
                     else:                                                        # (a rank without a row still joins the gather)
                         E = self._bank_expr.shape[1] if self._bank_expr is not None else self.cfg["lpe_output_channels_expression"]
                         local = torch.empty((0, E), device=self.device)
-                    per_rank = [rows(*parallel.shard_range(n, r, self.world)) for r in range(self.world)]
-                    every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)
-                ids_chunk = None if ids is None else ids[r0:r1].to(self.device)
-                poses = self._expression_controls(every, ids_chunk, ex, r0)[m_lo - r0:m_hi - r0]
-            # (every span whose crops stayed resident from the head-pose pass needs no second upload -- unless its frames are
-            # what the render is pasted into: the crops were kept, 3 MB per frame, not the frames, 6 MB at 1080p)
-            todo = spans if paste_back else [sp for sp in with_faces if sp[0] not in kept]
-            fresh = frames_mod.uploaded(chunk, todo, self.device, plan.upload_stream)
-            for b0, b1 in spans if paste_back else with_faces:
-                m0, m1 = rows(b0, b1)
-                crops = kept.pop(b0, None)
-                if crops is None or paste_back:
-                    f0, f1, u8 = next(fresh)
-                    assert (f0, f1) == (b0, b1)
-                if m1 == m0:                                                     # (paste_back: frames without a face, as they came)
+                    poses = scan(control, local)
+            for b0, b1, crops, u8 in walk(last=True):
+                m0 = rows(b0, b1)[0]
+                if crops is None:                                                # (paste_back: frames without a face, as they came)
                     out = u8.clone() if chunk.is_cuda else u8
                 else:
-                    if crops is None:
-                        crops = crops_of(u8, b0, b1)
-                    ident = None if ids is None else ids_dev[m0 - m_lo:m1 - m_lo]
-                    theta = thetas.pop(b0, None) if smoothed is None else smoothed[m0 - m_lo:m1 - m_lo]
-                    out, m = self._drive_crops(crops, ident, plan, theta, row0=m0,
-                                               pose=None if poses is None else poses[m0 - m_lo:m1 - m_lo], align=aligns.pop(b0, None))
+                    out, m = self._drive_crops(crops, part(ids_dev, b0, b1), plan, thetas.pop(b0, None), row0=m0, pose=part(poses, b0, b1),
+                                               align=aligns.pop(b0, None))
                     if paste_back:
                         full = u8.clone() if chunk.is_cuda else u8               # (a host chunk's upload is this span's own)
-                        out = frames_mod.paste_into(full, out, paste_wins_of(b0, b1), plan.feather, m, *plan.fmt, frame_of=frame_of(b0, b1))
+                        out = frames_mod.paste_into(full, out, part(paste_w, b0, b1), plan.feather, m, *plan.fmt, frame_of=frame_of(b0, b1))
                 index = base + b0 if paste_back else m0
                 if plan.ring is not None:
                     yield from plan.ring.push(index, out)
                 else:
                     yield index, out
-            base += n
+            base, row0 = base + n, r1
         if plan.ring is not None:
             yield from plan.ring.drain()
 
@@ -1702,10 +1702,12 @@ class InferenceWrapper:
         n_faces, spans_of = [len(flat) for flat, _ in faces], [(s, first[s][t], first[s][t + 1]) for s, t in order]
         expression = control_streams.stream_expression(expression, [st.get('expression') for st in streams], n_faces, spans_of)
         head_pose = control_streams.stream_head_pose(head_pose, [st.get('head_pose') for st in streams], n_faces, spans_of)
-        plan = self._video_plan(len(wins), None if tracked else wins, identities, batch_size, ring, to_host, smooth_pose, True, mix, mix_old,
-                                target_theta, paste_back, feather, paste_matte, as_uint8, refine, refine_masks, frame_format, out_format,
-                                colorspace, full_range, arena=True, expression=expression, where='animate_streams', head_pose=head_pose,
-                                track=tracks[0] if tracked else None)
+        plan = self._video_plan(n_rows=len(wins), wins=None if tracked else wins, identities=identities, batch_size=batch_size, ring=ring,
+                                to_host=to_host, smooth_pose=smooth_pose, smooth_per_identity=True, mix=mix, mix_old=mix_old,
+                                target_theta=target_theta, paste_back=paste_back, feather=feather, paste_matte=paste_matte,
+                                as_uint8=as_uint8, refine=refine, refine_masks=refine_masks, frame_format=frame_format,
+                                out_format=out_format, colorspace=colorspace, full_range=full_range, arena=True, expression=expression,
+                                where='animate_streams', head_pose=head_pose, track=tracks[0] if tracked else None)
         crop_states = control_streams.CropStates(len(streams), self.device) if tracked else None     # (the call's own)
         S, host_ring = self.cfg["image_size"], plan.ring
         ids_dev = None if plan.ids is None else plan.ids.to(self.device)
@@ -1778,12 +1780,8 @@ class InferenceWrapper:
                             raise ValueError(f"stream {s}: its 'boxes' ended before its frames did, at frame {t}")
                         boxes.append(box.to(self.device).double())
                     sizes = [frames_mod.frame_size(f[None], plan.fmt[0])[::-1] for f in frames]
-                    crop_w, paste_w, _ = ops.crop_track(torch.stack(boxes), torch.tensor(of_row, dtype=torch.int32).to(self.device), sizes,
-                                                        *crop_states.arrays(), momentum=plan.track.momentum, smooth=plan.track.smooth,
-                                                        fixed=plan.track.fixed, scale=plan.track.scale, box_format=plan.track.box_format,
-                                                        missing=plan.track.missing, min_side=plan.min_side)
-                    self.tracked_windows = (paste_w, m0)
-                    crop_w, paste_w = ops.DeviceWindows(crop_w), ops.DeviceWindows(paste_w)
+                    crop_w, paste_w = self._track(crop_states, torch.stack(boxes), torch.tensor(of_row, dtype=torch.int32).to(self.device),
+                                                  sizes, plan, m0)
                 crops = ops.crop_faces_mixed(frames, S, crop_w, frame_of, *plan.fmt)
                 out, m = self._drive_crops(crops, None if ids_dev is None else ids_dev[m0:m1], plan, smooth=smooth_pose, row0=m0)
                 if paste_back:

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE ONLY -- the facade the emulated tests put in front of the host-compiled library (tests/emul/emulibs.py) so
 that emoportraits_amd.ops runs on CPU tensors: every entry point gets the argument and result types of emoportraits_amd.hip, and
-every call is counted under its entry's name.  The ABI 22 crop and paste serve the one-window-per-frame form and the
+every call is counted under its entry's name and written down in call order.  The ABI 22 crop and paste serve the one-window-per-frame form and the
 several-faces-per-frame form under ONE name (`frame_of` null or not), so for those two the form of every call is recorded too."""
 import ctypes
 import os
@@ -18,20 +18,22 @@ def argument_index(name, argument):
 
 
 class _Calls(dict):
-    """{entry name: calls}; .forms = {name of a TWO_FORMS entry: ['windows' | 'faces' per call, in call order]}; clear() empties both"""
+    """{entry name: calls}; .forms = {name of a TWO_FORMS entry: ['windows' | 'faces' per call, in call order]}; .order = the entry
+    names of all calls in call order; clear() empties all three"""
 
     def __init__(self):
         super().__init__()
-        self.forms = {}
+        self.forms, self.order = {}, []
 
     def clear(self):
         super().clear()
         self.forms.clear()
+        self.order.clear()
 
 
 class CountingLib:
     """the host-compiled stream library behind emoportraits_amd.hip's table of signatures; .calls counts the calls, .forms is
-    .calls.forms"""
+    .calls.forms, .order is .calls.order"""
 
     def __init__(self, lib):
         from emoportraits_amd import hip
@@ -46,6 +48,10 @@ class CountingLib:
     def forms(self):
         return self.calls.forms
 
+    @property
+    def order(self):
+        return self.calls.order
+
     def __getattr__(self, name):
         if name.startswith("_"):
             raise AttributeError(name)
@@ -54,6 +60,7 @@ class CountingLib:
 
         def counted(*args):
             self.calls[name] = self.calls.get(name, 0) + 1
+            self.calls.order.append(name)
             if name in self._frame_of:
                 self.forms.setdefault(name, []).append("windows" if args[self._frame_of[name]] is None else "faces")
             return fn(*args)

@@ -17,6 +17,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+from bare_wrapper import bare_wrapper as _bare_wrapper, host_uploads  # noqa: E402
 from counting_lib import CountingLib as _Lib  # noqa: E402
 
 
@@ -243,28 +244,6 @@ def test_the_entry_point_is_in_the_abi_table():
 # ---- ops and the wrapper on the recorder rig of tests/test_expression_controls_emul.py ---------------------------------------------
 NAME = "emo_head_pose_controls_f32"
 E5 = 5
-
-
-def _bare_wrapper(monkeypatch, lib, capacity):
-    from emoportraits_amd import hip
-    from emoportraits_amd.infer import InferenceWrapper
-    monkeypatch.setattr(hip, "load", lambda: lib)
-    monkeypatch.setattr(hip, "require_cuda_f32", lambda *a, **k: None)
-    monkeypatch.setattr(hip, "current_stream", lambda: None)
-    w = object.__new__(InferenceWrapper)
-    w.device, w.rank, w.world = torch.device("cpu"), 0, 1
-    w.cfg = dict(latent_volume_channels=4, latent_volume_depth=2, latent_volume_size=2, gen_embed_size=1, gen_max_channels=4, image_size=8)
-    w._init_state(use_graphs=False, identity_capacity=capacity, pose_momentum=0.3)
-    w.embedders = {}
-    w.lib = lib
-    w.recorded = []
-
-    def drive(pose, theta, ident=None):
-        w.recorded.append((pose.clone(), theta.clone(), None if ident is None else ident.clone()))
-        return torch.zeros(pose.shape[0], 3, w.cfg["image_size"], w.cfg["image_size"])
-    w._drive_bank = drive
-    w._drive = lambda pose, theta: drive(pose, theta)
-    return w
 
 
 def _sources(K, seed=70):
@@ -495,26 +474,8 @@ def video(monkeypatch):
     """a wrapper on CPU tensors with a 3-slot bank: the crops through the host-compiled kernels, the head pose a fixed function of
     the crop through emo_pose_theta_f32 (its output recorded), the expression embedder and the driver pass recorders"""
     import emulibs
-    from emoportraits_amd import frames as frames_mod
     from emoportraits_amd import ops
-    monkeypatch.setattr(torch.cuda, "Stream", lambda device=None: None)
-    monkeypatch.setattr(ops, "unpack_rgb8", lambda u8: (u8.permute(0, 3, 1, 2).float() / 255).contiguous())
-
-    def uploaded(chunk, spans, device, stream):
-        for a, b in spans:
-            yield a, b, chunk[a:b].clone()
-
-    def uploaded_mixed(batches, device, stream, copy_all):
-        for batch in batches:
-            shapes = [tuple(f.shape) for f in batch]
-            offsets, total = frames_mod.arena_layout(shapes)
-            arena = torch.zeros(total, dtype=torch.uint8)
-            views = frames_mod.arena_views(arena, shapes, offsets)
-            for v, f in zip(views, batch):
-                v.copy_(f)
-            yield views, arena
-    monkeypatch.setattr(frames_mod, "uploaded", uploaded)
-    monkeypatch.setattr(frames_mod, "uploaded_mixed", uploaded_mixed)
+    host_uploads(monkeypatch)
     w = _bare_wrapper(monkeypatch, _Lib(emulibs.stream(False)), 3)
     _fill(w, 3)
     w.regressed, w.aligned_by = [], []

@@ -16,6 +16,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
+from bare_wrapper import bare_wrapper  # noqa: E402
 from counting_lib import CountingLib as _Lib  # noqa: E402
 
 
@@ -256,30 +257,12 @@ def test_ema_scan_refusals(stream):
 def wrapper(monkeypatch):
     """an InferenceWrapper with a 3-slot bank and everything but the driver pass: that records (pose, theta, identity)"""
     import emulibs
-    from emoportraits_amd import hip
-    from emoportraits_amd.infer import InferenceWrapper
     lib = _Lib(emulibs.stream(True))
-    monkeypatch.setattr(hip, "load", lambda: lib)
-    monkeypatch.setattr(hip, "require_cuda_f32", lambda *a, **k: None)
-    monkeypatch.setattr(hip, "current_stream", lambda: None)
-    w = object.__new__(InferenceWrapper)
-    w.device, w.rank, w.world = torch.device("cpu"), 0, 1
-    w.cfg = dict(latent_volume_channels=4, latent_volume_depth=2, latent_volume_size=2, gen_embed_size=1, gen_max_channels=4,
-                 image_size=8)
-    w._init_state(use_graphs=False, identity_capacity=3, pose_momentum=0.3)
-    w.embedders = {}
+    w = bare_wrapper(monkeypatch, lib, 3)
     th = corpus(lib)
     w.src_thetas = [torch.from_numpy(th[k]) for k in (2, 41, 47)]          # a pose_theta, a reflection, an ill-conditioned one
     for k in range(3):
         w._bank_write(k, torch.zeros(1, 2, 2, 2, 4), torch.zeros(1, 4, 1, 1), w.src_thetas[k])
-    w.recorded = []
-
-    def drive(pose, theta, ident=None):
-        w.recorded.append((pose.clone(), theta.clone(), None if ident is None else ident.clone()))
-        return torch.zeros(pose.shape[0], 3, 8, 8)
-    w._drive_bank = drive
-    w._drive = lambda pose, theta: drive(pose, theta)
-    w.lib = lib
     return w
 
 
