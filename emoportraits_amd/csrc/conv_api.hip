@@ -162,7 +162,7 @@ static int conv_igemm_dispatch(int prec, const float* x, const void* wpk, const 
   a.n_cchunks = 0; a.tiles_x = a.tiles_y = a.tiles_z = 0; a.n_cotiles = 0; a.n_work = 0; a.cot0 = cot0; a.cot_end = cot_end;
   if ((cot0 != 0 && !(prec == PREC_F16 && cfg == CFG_D && ksplit == 1)) || (cot_end != 0 && prec != PREC_H1)) return EMO_ERR_BAD_ARG;
   a.in_scale = in_scale; a.out_scale = 1.0f / (in_scale * w_scale);
-  a.sat_flag = sat_flag; a.run_if = run_if;
+  a.sat_flag = sat_flag; a.run_if = run_if; a.zrun = 0;
   const int shape = shape_of_width(a.Wl);
   if (shape < 0) return EMO_ERR_UNSUPPORTED;
   conv_launch_fn fn = nullptr;

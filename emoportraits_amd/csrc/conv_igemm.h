@@ -89,6 +89,7 @@ struct ConvArgs {
   int* sat_flag;       // conv_igemm_bf16x3.h, fp16 two-term split only, or null: set to 1 when a staged value left the fp16 range
   const int* run_if;   // conv_igemm_bf16x3.h / conv_igemm.h, or null: the launch does nothing unless *run_if != 0 (guarded fallback of a layer
                        // whose fp16-split launch raised its sat_flag)
+  int zrun;            // conv_igemm_f16x2_zs.h only: output slices per work item (a run marches in z); 0 elsewhere
 };
 
 template <int KH, int KW, int KC, int TZ, int TR, int TW, int TM, int TP, int WGM, int WGP, bool UPS>

@@ -4,6 +4,7 @@
 #include "conv_igemm_bf16x3.h"
 int conv_f16x2_ct2_4x64(ConvArgs, hipStream_t, int ups, int* rest_cot0);    // conv_inst_f16x2_ct2.hip
 int conv_f16x2_w8_4x64(ConvArgs, hipStream_t, int ups, int* rest_cot0);     // conv_inst_f16x2_w8.hip
+int conv_f16x2_bm32_4x64(ConvArgs, hipStream_t);                            // conv_inst_f16x2_zs.hip
 // 4 x 64 tiles: the layer's channel-tile pairs on a two-tile kernel where that fills the chip -- the one with two waves per SIMD
 // (conv_igemm_f16x2_w8.h; EMO_CONV_W8=0: the one-wave-per-SIMD kernel of conv_igemm_f16x2_ct2.h) --, the rest (an odd last tile,
 // or everything) on the single-tile one
@@ -19,9 +20,11 @@ static int conv_f16x2_4x64(ConvArgs a, hipStream_t s) {
   return conv_igemm_bf16x3_launch<4, 64, UPS, 2>(a, s);
 }
 // 32-row channel tiles (block config F as the tile id: 32 channels x 256 positions; weights packed for BM = 32): layers with at
-// most 32 output channels per tile row -- the WarpGenerator's last 3-D block, stage 2's 32-channel ResBlocks
+// most 32 output channels per tile row -- the WarpGenerator's last 3-D block, stage 2's 32-channel ResBlocks.  The launcher
+// sends 3x3x3 layers that fill the chip to the depth-shared kernel (conv_igemm_f16x2_zs.h), everything else to
+// conv_igemm_bf16x3_launch<4, 64, false, 2, 32>
 conv_launch_fn conv_lookup_f16x2_3x3_bm32(int Wl, int ups) {
-  if (Wl % 64 == 0 && !ups) return &conv_igemm_bf16x3_launch<4, 64, false, 2, 32>;
+  if (Wl % 64 == 0 && !ups) return &conv_f16x2_bm32_4x64;
   return nullptr;
 }
 conv_launch_fn conv_lookup_f16x2_3x3(int Wl, int ups) {

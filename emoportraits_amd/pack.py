@@ -531,8 +531,9 @@ def supports_bf16x3(cout, cin, kd, kh, kw, precision="bf16x3"):
 
 
 def f16x2_tile_cfg(cout):
-    """block config of an fp16-split 3x3 layer: F (32 channels x 256 positions, csrc/conv_igemm_bf16x3.h BMT = 32) for layers
-    with at most 32 output channels -- they ran the 64-row tile half empty --, D (64 x 256) otherwise"""
+    """block config of an fp16-split 3x3 layer: F (32 channels x 256 positions, csrc/conv_igemm_bf16x3.h BMT = 32; large 3x3x3
+    launches: its depth-shared form, csrc/conv_igemm_f16x2_zs.h -- the C launcher's choice) for layers with at most 32 output
+    channels -- they ran the 64-row tile half empty --, D (64 x 256) otherwise"""
     return CFG_F if (F16X2_BM32 and cout <= 32) else CFG_D
 
 

@@ -313,7 +313,10 @@ int emo_conv_igemm_f16x2(const float* x, const void* wpk2, const float* bias,
  * warp_generator_resnet.py:95-123; stage 2's 32-channel ResBlocks), which ran the 64-row tile half empty.  wpk2 is then packed
  * with BM = 32 (emoportraits_amd.pack.pack_weight_f16x2(w, bm=32)); 4 x 64 position tiles (W % 64 == 0, H % 4 == 0), no fused
  * upsample.  The guarded recomputation of such a layer is emo_conv_igemm_bf16x3 with cfg 3 and the BM = 64 weights, as for
- * every 3x3 layer. */
+ * every 3x3 layer.  A 3x3x3 launch that runs of at least six output slices spread over the whole device is computed by the
+ * depth-shared form of the tile (csrc/conv_igemm_f16x2_zs.h: every staged input slice feeds all three depth taps): same
+ * arguments, weights, statistics layout and overflow word; results differ from the one-slice kernel's only by the order in
+ * which an output's (channel chunk, depth tap) contributions are accumulated. */
 /* ABI 11.  emo_conv_igemm_f16x2 with cfg = EMO_CONV_CFG_F16X2_UP2: a 3x3 layer with the fused nearest x2 upsample (ups = 1) as
  * four 2x2 PHASE convolutions on the low-res input (csrc/conv_inst_f16x2_up2.hip): output pixel (2i + p, 2j + q) = sum over
  * a, b in {0, 1} of w_pq[a][b] . x[i - 1 + p + a][j - 1 + q + b], w_pq[a][b] = sum of the 3x3 taps w[r][s], r in R_p[a],
