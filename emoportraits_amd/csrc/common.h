@@ -19,7 +19,15 @@ static inline int emo_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // Rounded down to a multiple of 8, and at least 8: those kernels hand out their work items in eight contiguous ranges, one per
 // XCD (block b walks the range of XCD b % 8: conv_igemm_bf16x3.h), so a grid of min(items, this) blocks covers every item only
 // when it holds all eight residues equally often.  MI355X has 256 / 128 / 64 / 32 CUs per partition: unchanged there.
+//
+// emo_dry_run (per thread): what emo_conv_accepts sets around a call of a convolution entry -- `on`: the launchers check and
+// compute as always and touch no device (emo_raise_dynamic_lds and emo_launch of conv_igemm.h return EMO_OK at once); `ncu` > 0:
+// the CU count to assume in place of the device's
+struct EmoDryRun { bool on; int ncu; };
+inline thread_local EmoDryRun emo_dry_run = {false, 0};
+
 static inline int emo_cu_count() {
+  if (emo_dry_run.ncu > 0) return emo_dry_run.ncu;
   static int cached[64] = {0};     // (benign race: every writer stores the same value)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;

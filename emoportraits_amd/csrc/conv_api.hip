@@ -223,9 +223,8 @@ static int conv_igemm_dispatch(int prec, const float* x, const void* wpk, const 
   const long total = (long)N * Cout * a.Dl * a.Hl * a.Wl;
   long blocks = (total + 255) / 256;
   if (blocks > 262144) blocks = 262144;
-  hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, workspace, bias,
-                     res, out, total, a.ksplit, Cout, a.Dl, a.Hl, a.Wl, act, res_ups, run_if);
-  return emo_launch_status();
+  return emo_launch(conv_splitk_epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, workspace, bias,
+                    res, out, total, a.ksplit, Cout, a.Dl, a.Hl, a.Wl, act, res_ups, run_if);
 }
 
 extern "C" int emo_conv_igemm_f32(const float* x, const float* wpk, const float* bias, const float* scale,
@@ -308,3 +307,33 @@ extern "C" int emo_conv_igemm_f16w8(const float* x, const void* wpk1, const floa
                              relu_in, act, res_ups, cfg, ksplit, workspace, gn_stats, stream, 1.0f, w_scale, nullptr, nullptr);
 }
 
+// ABI 24.  The code `entry` would return for this launch, asked without launching: the entry itself runs under emo_dry_run
+// (common.h) -- every check of the dispatch and of the launchers, no kernel, no HIP call -- on stand-in tensors that are null
+// or not and have the given address modulo 16: see include/emo_hip.h
+extern "C" int emo_conv_accepts(int entry, const int* tensors, int N, int Cin, int Cout, int D, int H, int W, int KD, int KH,
+                                int KW, int ups, int relu_in, int act, int res_ups, int cfg, int ksplit, float in_scale,
+                                float w_scale, int ncu) {
+  if (!tensors || entry < 0 || entry >= EMO_CONV_ENTRY_COUNT) return EMO_ERR_BAD_ARG;
+  const auto t = [&](int i) { return tensors[i] < 0 ? nullptr : reinterpret_cast<float*>((uintptr_t)4096 + (tensors[i] & 15)); };
+  const float *const x = t(EMO_CONV_T_X), *const w = t(EMO_CONV_T_WPK);
+  int* const flag = reinterpret_cast<int*>(t(EMO_CONV_T_FLAG));
+  const int* const run_if = reinterpret_cast<const int*>(t(EMO_CONV_T_RUN_IF));
+  const EmoDryRun saved = emo_dry_run;
+  emo_dry_run = {true, ncu};
+  // (what the entries share, behind the weights: bias .. stream)
+#define EMO_REST_ t(EMO_CONV_T_BIAS), t(EMO_CONV_T_SCALE), t(EMO_CONV_T_SHIFT), t(EMO_CONV_T_RES), t(EMO_CONV_T_OUT), N, Cin, Cout, D, \
+                  H, W, KD, KH, KW, ups, relu_in, act, res_ups, cfg, ksplit, t(EMO_CONV_T_WORKSPACE), t(EMO_CONV_T_GN_STATS), nullptr
+  int rc = EMO_ERR_BAD_ARG;
+  switch (entry) {
+    case EMO_CONV_ENTRY_F32: rc = emo_conv_igemm_f32(x, w, EMO_REST_); break;
+    case EMO_CONV_ENTRY_F32_GUARDED: rc = emo_conv_igemm_f32_guarded(x, w, EMO_REST_, run_if); break;
+    case EMO_CONV_ENTRY_BF16X3: rc = emo_conv_igemm_bf16x3(x, w, EMO_REST_, run_if); break;
+    case EMO_CONV_ENTRY_F16X2: rc = emo_conv_igemm_f16x2(x, w, EMO_REST_, in_scale, w_scale, flag); break;
+    case EMO_CONV_ENTRY_F16ACC32: rc = emo_conv_igemm_f16acc32(x, w, EMO_REST_); break;
+    case EMO_CONV_ENTRY_F16W8: rc = emo_conv_igemm_f16w8(x, w, EMO_REST_, w_scale); break;
+    case EMO_CONV_ENTRY_F16W8_REST: rc = emo_conv_igemm_f16w8_rest(x, w, t(EMO_CONV_T_WPK16), EMO_REST_, w_scale); break;
+  }
+#undef EMO_REST_
+  emo_dry_run = saved;
+  return rc;
+}

@@ -703,6 +703,7 @@ void conv_igemm_kernel(const ConvArgs a) {
 // has the same function-pointer TYPE, so the bookkeeping is keyed by the pointer VALUE.
 template <typename K>
 static int emo_raise_dynamic_lds(K kern) {
+  if (emo_dry_run.on) return EMO_OK;
   static std::mutex mu;
   static std::set<std::pair<const void*, int>> raised;
   int dev = 0;
@@ -716,6 +717,31 @@ static int emo_raise_dynamic_lds(K kern) {
     raised.insert(key);
   }
   return EMO_OK;
+}
+
+// the tail of every convolution launcher: the launch and its status -- nothing under emo_dry_run (common.h)
+template <typename K, typename... A>
+static int emo_launch(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+  if (emo_dry_run.on) return EMO_OK;
+  hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+  return emo_launch_status();
+}
+
+// 32-bit byte offsets inside one sample of the input
+static inline bool conv_offsets32(const ConvArgs& a) { return (unsigned long long)a.Cin * a.D * a.H * a.W * 4ull < (1ull << 32); }
+
+// what the fp16-operand and split kernels ask of their input: whole 8-channel groups, with an affine at most the `sct` entries of
+// the scale / shift tables in LDS, 32-bit buffer offsets, 16-byte quads
+static inline bool conv_input_quads_fit(const ConvArgs& a, int sct) {
+  return a.Cin % 8 == 0 && !(a.scale && a.Cin > sct) && conv_offsets32(a) && emo_aligned16(a.x) && (a.W & 3) == 0;
+}
+
+// the straight-line epilogue of the pair kernels (conv_igemm_bf16x3.h, epi_mode): final output, no activation, whole `bm`-channel
+// tiles, at most 2^23 positions per sample (offsets inside 2^31 bytes), 16-byte aligned output, 16- / 8-byte aligned same-size /
+// half-size residual
+static inline bool conv_straight_epilogue_fits(const ConvArgs& a, int bm) {
+  return a.act == EMO_ACT_NONE && a.Cout % bm == 0 && (long)a.Dl * a.Hl * a.Wl <= (1l << 23) && emo_aligned16(a.out) &&
+         (a.res == nullptr || (reinterpret_cast<uintptr_t>(a.res) & (a.res_ups ? 7u : 15u)) == 0);
 }
 
 // host-side launcher for one instantiation
@@ -736,8 +762,7 @@ int conv_igemm_launch(ConvArgs a, hipStream_t s) {
   // shapes) and 32-bit byte offsets inside a sample
   constexpr bool CAN_QUAD = KH == 1 && KW == 1 && !UPS && EMO_CONV_PIPE == 2 && EMO_CONV_QUAD_1X1 &&
                             (TZ * TR * TW) % 4 == 0 && 256 % ((TZ * TR * TW) / 4) == 0 && KC % (256 / ((TZ * TR * TW) / 4)) == 0;
-  const bool quad = CAN_QUAD && (reinterpret_cast<unsigned long long>(a.x) & 15ull) == 0 && (a.W & 3) == 0 &&
-                    (unsigned long long)a.Cin * a.D * a.H * a.W * 4ull < (1ull << 32);
+  const bool quad = CAN_QUAD && emo_aligned16(a.x) && (a.W & 3) == 0 && conv_offsets32(a);
   void (*kern)(const ConvArgs) = conv_igemm_kernel<KH, KW, KC, TZ, TR, TW, TM, TP, WGM, WGP, UPS, false>;
   if (quad) kern = conv_igemm_kernel<KH, KW, KC, TZ, TR, TW, TM, TP, WGM, WGP, UPS, CAN_QUAD>;
   if (lds > 64 * 1024) {
@@ -750,6 +775,5 @@ int conv_igemm_launch(ConvArgs a, hipStream_t s) {
   if (a.ksplit > 1 && a.gn_stats) return EMO_ERR_BAD_ARG;
   if (nt * cot * a.N * a.ksplit > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
   dim3 g = EMO_CONV_XCD_ORDER ? dim3((unsigned)(nt * cot * a.N * a.ksplit)) : dim3((unsigned)nt, cot, a.N);
-  hipLaunchKernelGGL(kern, g, dim3(Cfg::THREADS), lds, s, a);
-  return emo_launch_status();
+  return emo_launch(kern, g, dim3(Cfg::THREADS), lds, s, a);
 }

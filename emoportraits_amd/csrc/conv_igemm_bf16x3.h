@@ -1288,10 +1288,7 @@ template <int TR, int TW, bool UPS, int SPLIT = 3, int BMT = 64>
 int conv_igemm_bf16x3_launch(ConvArgs a, hipStream_t s) {
   using Cfg = ConvCfgS<TR, TW, UPS, SPLIT, BMT>;
   if (a.Wl % TW || a.Hl % TR) return EMO_ERR_UNSUPPORTED;
-  if (a.Cin % 8) return EMO_ERR_UNSUPPORTED;   // whole 8-channel groups
-  if (a.scale && a.Cin > Cfg::SCT) return EMO_ERR_UNSUPPORTED;   // scale / shift tables in LDS
-  if ((unsigned long long)a.Cin * a.D * a.H * a.W * 4ull >= (1ull << 32)) return EMO_ERR_UNSUPPORTED;   // 32-bit buffer offsets
-  if ((reinterpret_cast<unsigned long long>(a.x) & 15ull) || (a.W & 3)) return EMO_ERR_UNSUPPORTED;     // 16-byte quads
+  if (!conv_input_quads_fit(a, Cfg::SCT)) return EMO_ERR_UNSUPPORTED;
   a.tiles_x = a.Wl / TW;
   a.tiles_y = a.Hl / TR;
   a.tiles_z = a.Dl;
@@ -1315,6 +1312,5 @@ int conv_igemm_bf16x3_launch(ConvArgs a, hipStream_t s) {
   a.n_work = (int)(nt * a.n_cotiles * a.N * a.ksplit);
   // (a guarded fallback launch is normally skipped: min(n_work, CUs) blocks read the flag and leave instead of n_work)
   const int grid = (persistent || a.run_if != nullptr) && a.n_work > ncu ? ncu : a.n_work;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
-  return emo_launch_status();
+  return emo_launch(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
 }

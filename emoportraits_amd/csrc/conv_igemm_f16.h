@@ -476,10 +476,7 @@ template <int KH, int KW, int KC, int TZ, int TR, int TW, int TM, int TP, int WG
 int conv_igemm_f16_launch(ConvArgs a, hipStream_t s) {
   using Cfg = ConvCfgH<KH, KW, KC, TZ, TR, TW, TM, TP, WGM, WGP, UPS>;
   if (a.Wl % TW || a.Hl % TR || a.Dl % TZ) return EMO_ERR_UNSUPPORTED;
-  if (a.Cin % 8) return EMO_ERR_UNSUPPORTED;   // whole 8-channel groups
-  if (a.scale && a.Cin > Cfg::SCT) return EMO_ERR_UNSUPPORTED;   // scale / shift tables in LDS
-  if ((unsigned long long)a.Cin * a.D * a.H * a.W * 4ull >= (1ull << 32)) return EMO_ERR_UNSUPPORTED;   // 32-bit buffer offsets
-  if ((reinterpret_cast<unsigned long long>(a.x) & 15ull) || (a.W & 3)) return EMO_ERR_UNSUPPORTED;     // 16-byte quads
+  if (!conv_input_quads_fit(a, Cfg::SCT)) return EMO_ERR_UNSUPPORTED;
   a.tiles_x = a.Wl / TW;
   a.tiles_y = a.Hl / TR;
   a.tiles_z = a.Dl / TZ;
@@ -501,6 +498,5 @@ int conv_igemm_f16_launch(ConvArgs a, hipStream_t s) {
   if (a.ksplit == 1) { a.stages_per_split = a.n_cchunks * a.KD; a.partial = nullptr; }
   if (a.ksplit > 1 && a.gn_stats) return EMO_ERR_BAD_ARG;
   if (nt * ncot * a.N * a.ksplit > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nt * ncot * a.N * a.ksplit)), dim3(256), lds, s, a);
-  return emo_launch_status();
+  return emo_launch(kern, dim3((unsigned)(nt * ncot * a.N * a.ksplit)), dim3(256), lds, s, a);
 }

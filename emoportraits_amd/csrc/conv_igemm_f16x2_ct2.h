@@ -520,40 +520,15 @@ template <int TR, int TW, bool UPS>
 int conv_f16x2_ct2_launch(ConvArgs a, hipStream_t s, int* rest_cot0) {
   using Cfg = ConvCfgS2<TR, TW, UPS>;
   *rest_cot0 = 0;
-  // (read at every launch: tests and A/B runs toggle them inside one process; a launch is microseconds)
   const char* const e_on = getenv("EMO_CONV_CT2");
-  const char* const e_min = getenv("EMO_CONV_CT2_MIN_ITEMS");
-  if ((e_on && atoi(e_on) == 0) || a.ksplit != 1 || a.run_if != nullptr) return EMO_OK;
-  // the straight-line epilogue forms only (conv_igemm_bf16x3.h, epi_mode): final output, no activation, whole 64-channel tiles,
-  // 16-byte aligned output, 16- / 8-byte aligned same-size / half-size residual, offsets inside 2^31 bytes per sample
-  if (a.act != EMO_ACT_NONE || a.Cout % Cfg::BM != 0 || (a.Wl & 3) != 0 || (long)a.Dl * a.Hl * a.Wl > (1l << 23) ||
-      (reinterpret_cast<unsigned long long>(a.out) & 15ull) != 0 ||
-      (a.res != nullptr && (reinterpret_cast<unsigned long long>(a.res) & (a.res_ups ? 7ull : 15ull)) != 0)) return EMO_OK;
-  if (a.Wl % TW || a.Hl % TR || a.Cin % 8) return EMO_OK;                 // (the single-tile launcher reports what is unsupported)
-  if (a.scale && a.Cin > Cfg::SCT) return EMO_OK;
-  if ((unsigned long long)a.Cin * a.D * a.H * a.W * 4ull >= (1ull << 32)) return EMO_OK;
-  if ((reinterpret_cast<unsigned long long>(a.x) & 15ull) || (a.W & 3)) return EMO_OK;
-  const int cot = (a.Cout + Cfg::BM - 1) / Cfg::BM;
-  const int pairs = cot / 2;
-  const long nt = (long)(a.Wl / TW) * (a.Hl / TR) * a.Dl;
-  const int ncu = emo_cu_count();
-  // enough pair items for two per CU: below that the single-tile kernel's twice as many, half as long items balance better
-  const long min_items = e_min ? atol(e_min) : 2l * ncu;
-  if (pairs < 1 || nt > 0x7fffffffL || a.N > 65535 || nt * pairs * a.N > 0x7fffffffL || nt * pairs * a.N < min_items) return EMO_OK;
+  // (whatever is not in the pair form: the single-tile launcher runs it, or reports what is unsupported)
+  if ((e_on && atoi(e_on) == 0) || !conv_pair_form<Cfg, TR, TW>(a)) return EMO_OK;
+  const int pairs = (a.Cout / Cfg::BM) / 2;
+  int grid = 0;
+  if (!conv_pair_fill<TR, TW>(a, pairs, Cfg::KC, &grid)) return EMO_OK;
   auto kern = conv_igemm_bf16x3_ct2_kernel<TR, TW, UPS>;
   const int rc = emo_raise_dynamic_lds(kern);
   if (rc != EMO_OK) return rc;
-  a.tiles_x = a.Wl / TW;
-  a.tiles_y = a.Hl / TR;
-  a.tiles_z = a.Dl;
-  a.n_cchunks = (a.Cin + Cfg::KC - 1) / Cfg::KC;
-  a.stages_per_split = a.n_cchunks * a.KD;
-  a.partial = nullptr;
-  a.cot0 = 0;
-  a.n_cotiles = pairs;                         // (pairs: EMO_P_DECODE)
-  a.n_work = (int)(nt * pairs * a.N);
-  const int grid = a.n_work > ncu ? ncu : a.n_work;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
   *rest_cot0 = 2 * pairs;
-  return emo_launch_status();
+  return emo_launch(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
 }

@@ -453,19 +453,14 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
 #undef EMO_P_BARRIER
 }
 
-// Host side.  EMO_ERR_UNSUPPORTED for anything but the launch form of the header comment: the caller (conv_api.hip) then reports it,
-// the Python planner (pack.PackedConv.plan_for) does not route such a launch here.
+// Host side.  EMO_ERR_UNSUPPORTED for anything but the launch form of the header comment: the caller (conv_api.hip) reports it,
+// and the Python planner, which asks emo_conv_accepts first, does not route such a launch here.
 template <int TR, int TW>
 int conv_f16x2_p1_launch(ConvArgs a, hipStream_t s) {
   using Cfg = ConvCfgP<TR, TW>;
   if (a.KD != 1 || a.ksplit != 1 || a.run_if != nullptr) return EMO_ERR_UNSUPPORTED;
   if (a.Wl % TW || a.Hl % TR || a.Wl != a.W || a.Hl != a.H) return EMO_ERR_UNSUPPORTED;          // (no fused upsample)
-  if (a.scale && a.Cin > Cfg::SCT) return EMO_ERR_UNSUPPORTED;
-  if ((unsigned long long)a.Cin * a.D * a.H * a.W * 4ull >= (1ull << 32)) return EMO_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<unsigned long long>(a.x) & 15ull) || (a.W & 3)) return EMO_ERR_UNSUPPORTED;
-  if (a.act != EMO_ACT_NONE || a.Cout % Cfg::BM != 0 || (long)a.Dl * a.Hl * a.Wl > (1l << 23) ||
-      (reinterpret_cast<unsigned long long>(a.out) & 15ull) != 0 ||
-      (a.res != nullptr && (reinterpret_cast<unsigned long long>(a.res) & (a.res_ups ? 7ull : 15ull)) != 0)) return EMO_ERR_UNSUPPORTED;
+  if (!conv_input_quads_fit(a, Cfg::SCT) || !conv_straight_epilogue_fits(a, Cfg::BM)) return EMO_ERR_UNSUPPORTED;
   const int cot = a.Cout / Cfg::BM;
   const int pairs = (cot + 1) / 2;
   const long nt = (long)(a.Wl / TW) * (a.Hl / TR) * a.Dl;
@@ -485,6 +480,5 @@ int conv_f16x2_p1_launch(ConvArgs a, hipStream_t s) {
   a.n_work = (int)(nt * pairs * a.N);
   const int ncu = emo_cu_count();
   const int grid = a.n_work > ncu ? ncu : a.n_work;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
-  return emo_launch_status();
+  return emo_launch(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
 }

@@ -25,8 +25,8 @@
 // an 8-lane butterfly per 32-position pass, which is the first three levels of the 16-lane butterfly of conv_epilogue_fast_finish,
 // and the two passes are added as its fourth level adds the halves: the three kernels are BIT-IDENTICAL, output, statistics and
 // overflow word (tests/test_conv_bf16x3_gpu.py, tests/test_conv_split_emul.py).
-// Launch: conv_f16x2_w8_launch() under the conditions of conv_f16x2_ct2_launch(); EMO_CONV_W8=0 leaves the pairs to the
-// one-wave-per-SIMD kernel (A/B).
+// Launch: conv_f16x2_w8_launch() behind the gate it shares with conv_f16x2_ct2_launch() (conv_split_pair_common.h);
+// EMO_CONV_W8=0 leaves the pairs to the one-wave-per-SIMD kernel (A/B).
 #pragma once
 #include "conv_igemm_bf16x3.h"
 #include "conv_split_pair_common.h"
@@ -713,7 +713,7 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
 #undef EMO_W_BIAS_SLOT
 }
 
-// Launches the channel-tile PAIRS of the layer on conv_igemm_f16x2_w8_kernel under the conditions of conv_f16x2_ct2_launch (same
+// Launches the channel-tile PAIRS of the layer on conv_igemm_f16x2_w8_kernel behind the gate of conv_f16x2_ct2_launch (same
 // contract: *rest_cot0 = the first channel tile NOT covered; 0: nothing was launched).
 // NPROD = 3 (fp16 split): only with EMO_CONV_W8=1 -- measured on one box, A B A B, the eight-wave kernel needs 4-7 % fewer cycles
 // per item than the four-wave one and the chip answers with a clock 8-10 % lower: the same frames per second (DESIGN.md
@@ -725,40 +725,19 @@ int conv_f16x2_w8_launch(ConvArgs a, hipStream_t s, int* rest_cot0) {
   *rest_cot0 = 0;
   const char* const e_on = getenv(NPROD == 3 ? "EMO_CONV_W8" : "EMO_F16_W8");
   const char* const e_ct2 = getenv("EMO_CONV_CT2");
-  const char* const e_min = getenv("EMO_CONV_CT2_MIN_ITEMS");
   if (NPROD == 3 && (!(e_on && atoi(e_on) == 1) || (e_ct2 && atoi(e_ct2) == 0))) return EMO_OK;
   if (NPROD == 1 && e_on && atoi(e_on) == 0) return EMO_OK;
-  if (a.ksplit != 1 || a.run_if != nullptr) return EMO_OK;
-  if (a.act != EMO_ACT_NONE || a.Cout % Cfg::BM != 0 || (a.Wl & 3) != 0 || (long)a.Dl * a.Hl * a.Wl > (1l << 23) ||
-      (reinterpret_cast<unsigned long long>(a.out) & 15ull) != 0 ||
-      (a.res != nullptr && (reinterpret_cast<unsigned long long>(a.res) & (a.res_ups ? 7ull : 15ull)) != 0)) return EMO_OK;
-  if (a.Wl % TW || a.Hl % TR || a.Cin % 8) return EMO_OK;
-  if (a.scale && a.Cin > Cfg::SCT) return EMO_OK;
-  if ((unsigned long long)a.Cin * a.D * a.H * a.W * 4ull >= (1ull << 32)) return EMO_OK;
-  if ((reinterpret_cast<unsigned long long>(a.x) & 15ull) || (a.W & 3)) return EMO_OK;
-  const int cot_all = (a.Cout + Cfg::BM - 1) / Cfg::BM;
+  if (!conv_pair_form<Cfg, TR, TW>(a)) return EMO_OK;
+  const int cot_all = a.Cout / Cfg::BM;
   if (a.cot_end != 0 && (NPROD != 1 || a.cot_end < 2 || a.cot_end > cot_all || (a.cot_end & 1))) return EMO_ERR_BAD_ARG;
   const int cot = a.cot_end != 0 ? a.cot_end : cot_all;          // (cot_end: whole pairs only, the rest is the caller's)
   const int pairs = NPROD == 1 ? (cot + 1) / 2 : cot / 2;
-  const long nt = (long)(a.Wl / TW) * (a.Hl / TR) * a.Dl;
-  const int ncu = emo_cu_count();
-  const long min_items = e_min ? atol(e_min) : 2l * ncu;
-  if (pairs < 1 || nt > 0x7fffffffL || a.N > 65535 || nt * pairs * a.N > 0x7fffffffL || nt * pairs * a.N < min_items) return EMO_OK;
+  constexpr int KCE = NPROD == 1 ? 32 : Cfg::KC;   // (plain fp16 operands: 32 input channels per stage)
+  int grid = 0;
+  if (!conv_pair_fill<TR, TW>(a, pairs, KCE, &grid)) return EMO_OK;
   auto kern = conv_igemm_f16x2_w8_kernel<TR, TW, UPS, NPROD>;
   const int rc = emo_raise_dynamic_lds(kern);
   if (rc != EMO_OK) return rc;
-  a.tiles_x = a.Wl / TW;
-  a.tiles_y = a.Hl / TR;
-  a.tiles_z = a.Dl;
-  constexpr int KCE = NPROD == 1 ? 32 : Cfg::KC;   // (plain fp16 operands: 32 input channels per stage)
-  a.n_cchunks = (a.Cin + KCE - 1) / KCE;
-  a.stages_per_split = a.n_cchunks * a.KD;
-  a.partial = nullptr;
-  a.cot0 = 0;
-  a.n_cotiles = pairs;                         // (pairs: EMO_P_DECODE)
-  a.n_work = (int)(nt * pairs * a.N);
-  const int grid = a.n_work > ncu ? ncu : a.n_work;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(Cfg::NTH), (size_t)Cfg::LDS_BYTES, s, a);
   *rest_cot0 = NPROD == 1 ? cot : 2 * pairs;
-  return emo_launch_status();
+  return emo_launch(kern, dim3((unsigned)grid), dim3(Cfg::NTH), (size_t)Cfg::LDS_BYTES, s, a);
 }

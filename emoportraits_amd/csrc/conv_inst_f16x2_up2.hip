@@ -540,7 +540,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
 #undef EMO_U_DMA_PIECE
 }
 
-// The launch form (emoportraits_amd.pack.up2_launch_fits mirrors every check): 2-D, 3x3 with the fused nearest x2 upsample, no
+// The launch form (the Python planner asks emo_conv_accepts for it): 2-D, 3x3 with the fused nearest x2 upsample, no
 // K split, no residual, no activation, not a guarded launch, whole 64-channel tiles, a multiple of 8 input channels (at most SCT
 // with an affine), a low-res width that is a multiple of 64 and an even low-res height (items are 4 rows: the last ones of a
 // height that is no multiple of 4 are half empty), 16-byte aligned input and output, input
@@ -550,8 +550,8 @@ int conv_f16x2_up2_launch(ConvArgs a, hipStream_t s) {
   if (a.KD != 1 || a.D != 1 || a.ksplit != 1 || a.res != nullptr || a.act != EMO_ACT_NONE || a.run_if != nullptr) return EMO_ERR_UNSUPPORTED;
   if (a.Cout % Cfg::BM || a.Cin % 8 || (a.scale && a.Cin > Cfg::SCT)) return EMO_ERR_UNSUPPORTED;
   if (a.W % Cfg::TWL || a.H % 2) return EMO_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<unsigned long long>(a.x) & 15ull) || (reinterpret_cast<unsigned long long>(a.out) & 15ull)) return EMO_ERR_ALIGN;
-  if ((unsigned long long)a.Cin * a.H * a.W * 4ull >= (1ull << 32) || (long)a.Hl * a.Wl >= (1l << 31)) return EMO_ERR_UNSUPPORTED;
+  if (!emo_aligned16(a.x) || !emo_aligned16(a.out)) return EMO_ERR_ALIGN;
+  if (!conv_offsets32(a) || (long)a.Hl * a.Wl >= (1l << 31)) return EMO_ERR_UNSUPPORTED;
   const long nt = (long)(a.W / Cfg::TWL) * ((a.H + Cfg::TRL - 1) / Cfg::TRL);
   const int cot = a.Cout / Cfg::BM;
   if (a.N > 65535 || nt * cot * a.N > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
@@ -569,8 +569,7 @@ int conv_f16x2_up2_launch(ConvArgs a, hipStream_t s) {
   a.n_work = (int)(nt * cot * a.N);
   const int ncu = emo_cu_count();
   const int grid = a.n_work > ncu ? ncu : a.n_work;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
-  return emo_launch_status();
+  return emo_launch(kern, dim3((unsigned)grid), dim3(256), (size_t)Cfg::LDS_BYTES, s, a);
 }
 
 #if EMO_S_TIMING

@@ -7,7 +7,7 @@ int conv_f16x2_w8_4x64(ConvArgs a, hipStream_t s, int ups, int* rest_cot0) {
 }
 
 // plain fp16 operands (NPROD = 1; emo_conv_igemm_f16w8): the whole layer in one launch, or EMO_ERR_UNSUPPORTED when the launch is
-// not in the kernel's form (the caller -- emoportraits_amd/pack.py mirrors the conditions -- then runs conv_igemm_f16.h)
+// not in the kernel's form (the Python planner asks emo_conv_accepts first and runs conv_igemm_f16.h then)
 template <bool UPS>
 static int conv_f16_w8_4x64(ConvArgs a, hipStream_t s) {
   int rest = 0;

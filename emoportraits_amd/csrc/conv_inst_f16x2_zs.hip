@@ -28,11 +28,12 @@ static int zs_last_run = 0;
 // The config-F launcher of 4 x 64 tiles: 3x3x3 layers the rule takes run the depth-shared kernel, everything else (2-D layers,
 // launches too small to fill the chip with any run, more input channels than its tables hold) the one-slice kernel
 int conv_f16x2_bm32_4x64(ConvArgs a, hipStream_t s) {
-  zs_last_run = 0;
+  int unused = 0;
+  int& last_run = emo_dry_run.on ? unused : zs_last_run;      // (a question to emo_conv_accepts is no launch)
+  last_run = 0;
   const bool fits = a.KD == 3 && a.ksplit == 1 && a.run_if == nullptr && a.cot0 == 0 && !a.res_ups && a.Cin % 8 == 0 &&
                     a.Cin <= ConvCfgZ::SCT && a.D == a.Dl && a.H == a.Hl && a.W == a.Wl && a.N <= 65535 &&
-                    (unsigned long long)a.Cin * a.D * a.H * a.W * 4ull < (1ull << 32) &&      // 32-bit buffer offsets
-                    (reinterpret_cast<unsigned long long>(a.x) & 15ull) == 0;
+                    conv_offsets32(a) && emo_aligned16(a.x);
   const int ncu = emo_cu_count();
   const int run = fits ? conv_f16x2_zs_choose(a.N, a.Cout, a.D, a.H, a.W, ncu) : 0;
   if (run <= 0) return conv_igemm_bf16x3_launch<4, 64, false, 2, 32>(a, s);
@@ -51,9 +52,8 @@ int conv_f16x2_bm32_4x64(ConvArgs a, hipStream_t s) {
   const int rc = emo_raise_dynamic_lds(kern);
   if (rc != EMO_OK) return rc;
   const int grid = a.n_work > ncu ? ncu : a.n_work;       // persistent blocks: block b walks items b, b + grid, ...
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), (size_t)ConvCfgZ::LDS_BYTES, s, a);
-  zs_last_run = run;
-  return emo_launch_status();
+  last_run = run;
+  return emo_launch(kern, dim3((unsigned)grid), dim3(256), (size_t)ConvCfgZ::LDS_BYTES, s, a);
 }
 
 // the run length the rule gives a config-F 3x3x3 launch of these sizes on `ncu` compute units (0: the one-slice kernel;

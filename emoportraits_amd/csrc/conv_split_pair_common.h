@@ -19,6 +19,40 @@
 #endif
 
 
+// Host side: the gate of the two pair launchers (conv_f16x2_ct2_launch, conv_f16x2_w8_launch).  They differ in the switch they
+// read, in how they count pairs and in the input channels per stage.
+// conv_pair_form: the launch is in the pair kernels' form -- a final output (no K split, not a guarded launch) through the
+// straight-line epilogue, TR x TW position tiles, the input by 16-byte quads (conv_igemm.h)
+template <class Cfg, int TR, int TW>
+static bool conv_pair_form(const ConvArgs& a) {
+  static_assert(TW % 4 == 0, "rows of whole quads");
+  return a.ksplit == 1 && a.run_if == nullptr && conv_straight_epilogue_fits(a, Cfg::BM) && a.Wl % TW == 0 && a.Hl % TR == 0 &&
+         conv_input_quads_fit(a, Cfg::SCT);
+}
+// conv_pair_fill: the work items of `pairs` channel-tile pairs, `kc` input channels per stage, into the arguments and the
+// persistent grid -- false when there are none, more than 32-bit counts hold, or fewer than two per CU: below that the
+// single-tile kernels' twice as many, half as long items balance better (EMO_CONV_CT2_MIN_ITEMS: another threshold, for tests
+// and A/B runs, which toggle it inside one process: read at every launch, a launch is microseconds)
+template <int TR, int TW>
+static bool conv_pair_fill(ConvArgs& a, int pairs, int kc, int* grid) {
+  const long nt = (long)(a.Wl / TW) * (a.Hl / TR) * a.Dl;
+  const int ncu = emo_cu_count();
+  const char* const e_min = getenv("EMO_CONV_CT2_MIN_ITEMS");
+  const long min_items = e_min ? atol(e_min) : 2l * ncu;
+  if (pairs < 1 || nt > 0x7fffffffL || a.N > 65535 || nt * pairs * a.N > 0x7fffffffL || nt * pairs * a.N < min_items) return false;
+  a.tiles_x = a.Wl / TW;
+  a.tiles_y = a.Hl / TR;
+  a.tiles_z = a.Dl;
+  a.n_cchunks = (a.Cin + kc - 1) / kc;
+  a.stages_per_split = a.n_cchunks * a.KD;
+  a.partial = nullptr;
+  a.cot0 = 0;
+  a.n_cotiles = pairs;                         // (pairs: EMO_P_DECODE)
+  a.n_work = (int)(nt * pairs * a.N);
+  *grid = a.n_work > ncu ? ncu : a.n_work;
+  return true;
+}
+
 // work item l -> (sample, position tile, channel-tile PAIR): XCD-contiguous order, pair fastest.  Every result through
 // readfirstlane (conv_igemm_bf16x3.h); n_cotiles counts PAIRS here, cot0 is the first tile of the launch
 #define EMO_P_DECODE(P_, L_)                                                                          \

@@ -250,30 +250,52 @@ def pack_weight_f16x2_up2(w):
     return planes.view(-1), w_scale
 
 
+_ENTRIES = {"f32": 0, "f32_guarded": 1, "bf16x3": 2, "f16x2": 3, "f16": 4, "f16w8": 5, "f16w8_rest": 6}    # EMO_CONV_ENTRY_*
+_Tensors = ctypes.c_int * 12                                                                            # EMO_CONV_T_COUNT
+
+
+@functools.lru_cache(maxsize=None)
+def _tensors(x16, wpk16, affine, res, res16, out16, workspace):
+    """the tensors of a question, each as -1 (null) or its address modulo 16: x, wpk, wpk16, bias, scale, shift, res, out,
+    workspace, gn_stats, overflow flag, run_if (EMO_CONV_T_*; at most 2^7 arrays, each made once)"""
+    return _Tensors(0 if x16 else 4, 0, 0 if wpk16 else -1, -1, 0 if affine else -1, 0 if affine else -1,
+                    -1 if not res else 0 if res16 else 4, 0 if out16 else 4, 0 if workspace else -1, -1, -1, -1)
+
+
+def launch_accepted(entry, cout, cin, kd, kh, kw, N, D, H, W, ups=False, cfg=CFG_D, ksplit=1, affine=False, res=False, act="none",
+                    x16=True, out16=True, res16=True):
+    """whether the C entry `entry` (a key of _ENTRIES: emo_conv_igemm_<entry>, 'f16' = emo_conv_igemm_f16acc32) takes this launch
+    on an [N, cin, D, H, W] input.  The entry itself answers, through emo_conv_accepts (ABI 24, include/emo_hip.h): the conditions of
+    a launch form -- tiles, channel groups, the affine table, offsets, alignment, the fill rule of the pair kernels on cu_count()
+    compute units -- stand in the launcher that enforces them and nowhere in Python.  No launch, no device.  affine / res: the
+    launch carries an input scale / shift, a residual (same size; 16-byte aligned or not: res16); x16, out16: those tensors are
+    16-byte aligned"""
+    tensors = _tensors(x16, entry == "f16w8_rest", affine, res, res16, out16, ksplit > 1)
+    return hip.load().emo_conv_accepts(_ENTRIES[entry], tensors, N, cin, cout, D, H, W, kd, kh, kw, int(ups), 0, hip.ACT[act], 0,
+                                       cfg, ksplit, F16X2_IN_SCALE, 1.0, cu_count()) == 0
+
+
+def _plane_accepted(entry, Hl, Wl, ups=False, cout=BF16X3_BM, cin=8, taps=(1, 3, 3), **launch):
+    """a question about an output plane alone: the full one for an aligned one-sample launch with 8 input channels"""
+    if Hl is None:
+        return False
+    H, W = (Hl // 2, Wl // 2) if ups else (Hl, Wl)
+    return launch_accepted(entry, cout, cin, *taps, 1, launch.pop("D", 1), H, W, ups, **launch)
+
+
 def width_class(Wl):
-    """the width class the C entry point files an output width under (shape_of_width, csrc/conv_api.hip: the first thing
-    conv_igemm_dispatch asks, for every kernel): 128 for the multiples of 128, 64 / 32 / 16 / 8 for exactly those widths, None for
-    every other width -- which the entry point refuses with EMO_ERR_UNSUPPORTED whatever the kernel's own tiles would divide"""
-    if Wl is None:
+    """the width class the C entry point files an output width under, for every kernel: 128 for the multiples of 128, 64 / 32 / 16 /
+    8 for exactly those widths, None for every other width -- which the entry point refuses whatever the kernel's own tiles would
+    divide (asked for a plane that every class's tiles divide)"""
+    if Wl is None or not _plane_accepted("f32", 8, Wl, cfg=CFG_B, D=2):
         return None
-    if Wl >= 128 and Wl % 128 == 0:
-        return 128
-    return Wl if Wl in (64, 32, 16, 8) else None
+    return 128 if Wl % 128 == 0 else Wl
 
 
 def up2_launch_fits(cout, cin, kd, kh, kw, N, H, W, ups, affine=False, res=False, act="none", ksplit=1, aligned16=True):
-    """the launch form of the phase kernel (conv_f16x2_up2_launch and its dispatch -- every check of the C side has its
-    mirror here): nearest x2 upsample, 2-D 3x3, whole 64-channel tiles, 8-channel groups (at most the 1024-entry scale table
-    with an affine), a low-res width that is a multiple of 64 (the output's is then a multiple of 128: always a width class of the
-    entry point) and an even low-res height, no residual, no activation, no K split, 16-byte aligned input and output, 32-bit
-    byte offsets inside a sample's input"""
-    if not up2_enabled() or not ups or kd != 1 or (kh, kw) != (3, 3) or res or act != "none" or ksplit != 1 or not aligned16:
-        return False
-    if cout % BF16X3_BM or cin % 8 or (affine and cin > 1024) or W % 64 or H % 2:
-        return False
-    if cin * H * W * 4 >= (1 << 32) or 4 * H * W >= (1 << 31) or H * W >= (1 << 30):
-        return False
-    return N <= 65535 and (W // 64) * (H // 2) * (cout // BF16X3_BM) * N <= 0x7fffffff
+    """the phase kernel (csrc/conv_inst_f16x2_up2.hip) takes the launch, and EMO_CONV_UP2 is not 0"""
+    return up2_enabled() and launch_accepted("f16x2", cout, cin, kd, kh, kw, N, 1, H, W, ups, CFG_F16X2_UP2, ksplit, affine, res, act,
+                                             aligned16, aligned16)
 
 
 def pack_weight_f16w8(w):
@@ -312,29 +334,8 @@ F16_W8_REST = __import__("os").environ.get("EMO_F16_W8_REST", "1") != "0"
 
 
 def f16w8_rest_fits(cout, Hl, Wl):
-    """emo_conv_igemm_f16w8_rest takes the layer: an odd tile count >= 3 and an output plane that is in the older kernel's
-    launch form too (f16_launch_fits: its 2 x 128 / 4 x 64 tiles)"""
-    cot = cout // BF16X3_BM
-    return F16_W8_REST and cout % BF16X3_BM == 0 and cot >= 3 and cot % 2 == 1 and Hl is not None and f16_launch_fits(Hl, Wl)
-
-
-def f16w8_launch_fits(cout, cin, kd, kh, kw, Hl, Wl, n_pos_tiles, act="none", positions_per_sample=0):
-    """the one launch form of emo_conv_igemm_f16w8 (conv_f16x2_w8_launch<.., NPROD = 1> -- every check of the C launcher has its
-    mirror here): 3x3 / 3x3x3, whole 64-channel tiles and 8-channel groups, 4 x 64 position tiles, no activation, at most 2^23
-    positions per sample, two pair items per CU.  And -- a choice of the planner, not a limit of the kernel -- an even number of
-    channel tiles, or an odd one from F16_W8_ODD tiles on: the kernel runs an odd last tile in a half-empty pair, which costs a
-    whole pair's staging"""
-    if not F16_W8 or (kh, kw) != (3, 3) or kd not in (1, 3) or cout % BF16X3_BM or cin % 8 or act != "none":
-        return False
-    if cout % (2 * BF16X3_BM) and not (F16_W8_ODD and cout // BF16X3_BM >= F16_W8_ODD) \
-            and not f16w8_rest_fits(cout, Hl, Wl):
-        return False
-    if Hl is None or width_class(Wl) not in (128, 64) or Hl % 4 or positions_per_sample > (1 << 23):
-        return False                                  # (4 x 64 tiles on the widths shape_of_width admits: 64 and the multiples of 128)
-    min_items = int(__import__("os").environ.get("EMO_CONV_CT2_MIN_ITEMS", 2 * cu_count()))
-    cot = cout // BF16X3_BM
-    pairs = cot // 2 if f16w8_rest_fits(cout, Hl, Wl) else -(-cot // 2)
-    return (n_pos_tiles // 2) * pairs >= min_items
+    """emo_conv_igemm_f16w8_rest takes a layer of cout channels on this output plane, and EMO_F16_W8_REST is not 0"""
+    return F16_W8_REST and _plane_accepted("f16w8_rest", Hl, Wl, cout=cout)
 
 
 F16X2_P1_KC = 32     # conv_igemm_f16x2_p1.h: input channels per stage of the pointwise kernel
@@ -406,20 +407,6 @@ def cu_count():
 
 def _fill_blocks():
     return 2 * cu_count()   # 2 blocks per CU
-
-
-def cfg_d_fits(kd, kh, kw, Hl, Wl):
-    """the 64 x 256 (and 32 x 256) tiles exist for 3x3 / 3x3x3 fp32 layers whose output planes are tiled by 2x128 / 4x64 /
-    8x32 positions (the depth taps of a 3-D layer run as K stages, one depth slice per tile)"""
-    if kd not in (1, 3) or (kh, kw) != (3, 3) or Hl is None:
-        return False
-    return (Wl % 128 == 0 and Hl % 2 == 0) or (Wl == 64 and Hl % 4 == 0) or (Wl == 32 and Hl % 8 == 0)
-
-
-def cfg_e_fits(kd, kh, kw, Hl, Wl):
-    if kd != 1 or (kh, kw) != (3, 3) or Hl is None:
-        return False
-    return (Wl % 128 == 0 and Hl % 4 == 0) or (Wl == 64 and Hl % 8 == 0)
 
 
 def choose_cfg_for_launch(cout, n_pos_tiles, allowed=(CFG_A, CFG_B, CFG_C)):
@@ -538,38 +525,35 @@ def f16x2_tile_cfg(cout):
 
 
 def supports_f16x2_pointwise(cout, cin, kd, kh, kw):
-    """pointwise layers the fp16 split takes (csrc/conv_igemm_f16x2_p1.h): whole 64-channel tiles, at least one PAIR of them,
-    whole 8-channel input groups, an even number of 32-channel stages"""
-    return (kd, kh, kw) == (1, 1, 1) and cout % BF16X3_BM == 0 and cout >= 2 * BF16X3_BM and cin % 8 == 0 \
-        and (-(-cin // F16X2_P1_KC)) % 2 == 0          # (its K loop runs two 32-channel stages per iteration)
+    """pointwise layers the fp16 split takes: what csrc/conv_igemm_f16x2_p1.h takes on a plane of its tiles, and -- the planner's
+    rule -- at least one PAIR of channel tiles"""
+    return (kh, kw) == (1, 1) and cout >= 2 * BF16X3_BM and _plane_accepted("f16x2", 4, 64, cout=cout, cin=cin, taps=(kd, kh, kw))
 
 
-def f16x2_pointwise_launch_fits(Hl, Wl, ups, n_pos_tiles, cout, act="none", positions_per_sample=0):
-    """the launch form of the pointwise kernel (conv_f16x2_p1_launch, csrc/conv_igemm_f16x2_p1.h -- every check of the C launcher
-    has its mirror here, so that a launch it would refuse with EMO_ERR_UNSUPPORTED is planned onto the fp32 MFMA kernel instead):
-    4 x 64 position tiles on the source grid, no activation, at most 2^23 positions per sample (its 32-bit offsets), and enough
-    pair items for two per CU of THIS device (below that the fp32 MFMA kernel's K split fills the chip better)"""
-    if Hl is None or ups or act != "none" or width_class(Wl) not in (128, 64) or Hl % 4 or positions_per_sample > (1 << 23):
-        return False
+def _pointwise_fills(n_pos_tiles, cout):
+    """enough pair items of the pointwise kernel for two per CU of THIS device (below that the fp32 MFMA kernel's K split fills the
+    chip better): the planner's rule, no launcher knows it"""
     min_items = int(__import__("os").environ.get("EMO_F16X2_P1_MIN_ITEMS", 2 * cu_count()))      # (tests lower it to reach small shapes)
     return (n_pos_tiles // 2) * (-(-(cout // BF16X3_BM) // 2)) >= min_items
 
 
+def f16x2_pointwise_launch_fits(Hl, Wl, ups, n_pos_tiles, cout, act="none", positions_per_sample=0):
+    """the pointwise kernel takes an output plane (of positions_per_sample positions: a 3-D one) and the launch fills the chip"""
+    return _pointwise_fills(n_pos_tiles, cout) and _plane_accepted(
+        "f16x2", Hl, Wl, ups, cout, 2 * F16X2_P1_KC, (1, 1, 1), act=act, D=max(1, positions_per_sample // ((Hl or 1) * (Wl or 1))))
+
+
 def bf16x3_launch_fits(Hl, Wl, ups=False):
-    """output planes tiled by 4 x 64 positions (widths the C entry point admits: 64 and the multiples of 128, width_class), or
-    (32- / 16-wide maps, no fused upsample) 8 x 32 / 16 x 16"""
-    return Hl is not None and ((width_class(Wl) in (128, 64) and Hl % 4 == 0) or (Wl == 32 and Hl % 8 == 0 and not ups)
-                               or (Wl == 16 and Hl % 16 == 0 and not ups))
+    """the split-operand 3x3 kernels take this output plane"""
+    return _plane_accepted("bf16x3", Hl, Wl, ups)
 
 
-F16_AFFINE_MAX_CIN = 1024   # ConvCfgH::SCT (conv_igemm_f16.h)
+F16_AFFINE_MAX_CIN = 1024   # most input channels of an fp16-operand or split launch with an affine (the launchers enforce it)
 
 
 def f16_launch_fits(Hl, Wl):
-    """output planes tiled by the 64 x 256 tile of the fp16-operand kernel: 2x128 / 4x64 / 8x32 positions"""
-    if Hl is None:
-        return False
-    return (Wl % 128 == 0 and Hl % 2 == 0) or (Wl == 64 and Hl % 4 == 0) or (Wl == 32 and Hl % 8 == 0)
+    """the fp16-operand kernel takes this output plane"""
+    return _plane_accepted("f16", Hl, Wl)
 
 
 ConvPlan = namedtuple("ConvPlan", "cfg ksplit prec form stats_bp guard")
@@ -680,70 +664,84 @@ class PackedConv:
             self._packed[cfg] = pack_weight(self._weight, cfg).to(self.device)
         return self._packed[cfg]
 
+    def _f16w8_entry(self):
+        """the odd-tile policy of the plain-fp16 mode: the entry of the eight-wave two-tile kernel this layer's 3x3 launches ask, or
+        None.  An odd tile count >= 3: its pairs there, the last tile on the older kernel, one call (emo_conv_igemm_f16w8_rest;
+        EMO_F16_W8_REST=0: A/B); an even count, or an odd one from F16_W8_ODD tiles on: the whole layer there -- the kernel runs an
+        odd last tile in a half-empty pair, which costs a whole pair's staging"""
+        cot = -(-self.cout // BF16X3_BM)
+        if not (self.precision == "f16" and F16_W8 and self.pinned_cfg in (None, CFG_D)):
+            return None
+        if F16_W8_REST and cot >= 3 and cot % 2:
+            return "f16w8_rest"
+        return "f16w8" if cot % 2 == 0 or (F16_W8_ODD and cot >= F16_W8_ODD) else None
+
     def plan_for(self, n_pos_tiles, Hl=None, Wl=None, ups=False, affine=False, aligned16=True, in_elems_per_sample=0, act="none",
-                 io_aligned16=True):
-        """(cfg, ksplit, precision) for a launch over n_pos_tiles 128-position tiles of an Hl x Wl output; `affine`: the
-        launch carries a per-sample input scale / shift (the fp16-operand kernel keeps those in a 1024-entry LDS table);
-        `aligned16`: the input pointer is 16-byte aligned (that kernel loads 16-byte quads); `in_elems_per_sample`:
-        Cin*D*H*W of the input -- that kernel addresses a sample with 32-bit byte offsets (conv_igemm_f16_launch), larger
-        inputs take the exact-fp32 kernel like every other unsupported case; `io_aligned16`: output and residual pointers are
-        16-byte aligned too (the straight-line epilogue of emo_conv_igemm_f16w8 needs it)"""
-        # what the fp16-operand and split kernels all ask: 16-byte input quads, 32-bit offsets in a sample, the 1024-entry affine table
-        fits16 = aligned16 and in_elems_per_sample * 4 < (1 << 32) and not (affine and self.cin > F16_AFFINE_MAX_CIN)
-        if self.precision == "f16" and fits16 and self.pinned_cfg in (None, CFG_D) and io_aligned16 \
-                and f16w8_launch_fits(self.cout, self.cin, self.kd, self.kh, self.kw, Hl, Wl, n_pos_tiles, act,
-                                      in_elems_per_sample // max(1, self.cin) * (4 if ups else 1)):
+                 io_aligned16=True, launch=None):
+        """(cfg, ksplit, precision) for a launch over n_pos_tiles 128-position tiles.  launch: what launch_accepted asks about it
+        behind the layer's sizes (launch_plan gives it).  Callers with no launch at hand describe the Hl x Wl output instead, and
+        one is made up (the samples from the tile count) -- `affine`: it carries a per-sample input scale / shift; `aligned16`,
+        `io_aligned16`: the input, the output pointer is 16-byte aligned; `in_elems_per_sample`: Cin*D*H*W of the input (0: 2-D);
+        without Hl no kernel with a launch form is planned.
+        Here stand the planner's choices -- the layer's precision and pinned config, the A/B switches, the odd-tile policy,
+        plan_launch's scores -- and the library says which of the chosen entries takes the launch"""
+        if launch is None and Hl is not None:
+            H, W = (Hl // 2, Wl // 2) if ups else (Hl, Wl)
+            D = max(1, in_elems_per_sample // max(1, self.cin * H * W))
+            launch = dict(N=max(1, n_pos_tiles * 128 // (D * Hl * Wl)), D=D, H=H, W=W, ups=ups, affine=affine, act=act, x16=aligned16,
+                          out16=io_aligned16)
+
+        def takes(entry, cfg=CFG_D):
+            return launch is not None and launch_accepted(entry, self.cout, self.cin, self.kd, self.kh, self.kw, cfg=cfg, **launch)
+        pin = self.pinned_cfg
+        if self._f16w8_entry() and takes(self._f16w8_entry()):
             # the decoders' 3x3 layers in their launch form: plain fp16 operands on the eight-wave two-tile kernel (round 6)
             return CFG_D, 1, "f16w8"
-        if self.precision == "f16" and fits16 and f16_launch_fits(Hl, Wl) and self.pinned_cfg in (None, CFG_D, CFG_G) \
-                and not (self.pinned_cfg == CFG_G and self.kh != 3):
-            tiles = (self.pinned_cfg,) if self.pinned_cfg is not None else \
-                (CFG_D, CFG_G) if (_CFG_EFF[CFG_G] > 0 and self.kh == 3) else (CFG_D,)
-            cfg, ks = plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, n_pos_tiles, tiles, "f16")
-            return cfg, ks, "f16"
+        if self.precision == "f16" and pin in (None, CFG_D, CFG_G) and takes("f16", CFG_D if pin is None else pin):
+            tiles = (pin,) if pin is not None else (CFG_D, CFG_G) if (_CFG_EFF[CFG_G] > 0 and self.kh == 3) else (CFG_D,)
+            return (*plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, n_pos_tiles, tiles, "f16"), "f16")
         if self.pointwise_split:
-            if fits16 and self.pinned_cfg in (None, CFG_D) \
-                    and f16x2_pointwise_launch_fits(Hl, Wl, ups, n_pos_tiles, self.cout, act, in_elems_per_sample // max(1, self.cin)):
+            if pin in (None, CFG_D) and _pointwise_fills(n_pos_tiles, self.cout) and takes("f16x2"):
                 return CFG_D, 1, "f16x2"
-        elif self.precision in ("bf16x3", "f16x2") and fits16 and bf16x3_launch_fits(Hl, Wl, ups) and self.pinned_cfg in (None, CFG_D):
-            tile = CFG_D
-            if self.precision == "f16x2" and f16x2_tile_cfg(self.cout) == CFG_F and Wl % 64 == 0 and not ups:
-                # (the 32-row tile exists for 4 x 64 position tiles without fused upsample; other maps of such a layer run the
-                # half-empty 64-row tile -- still the fp16 split's arithmetic, 1.3-1.6x the fp32 MFMA kernel -- from a 64-row
-                # packing made on first use: PackedConv.packed)
-                tile = CFG_F
-            cfg, ks = plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, n_pos_tiles, (tile,), self.precision)
-            return cfg, ks, self.precision
-        pinned = None if self.pinned_cfg == CFG_G else self.pinned_cfg   # (G exists for fp16 operands only)
+        elif self.precision in ("bf16x3", "f16x2") and pin in (None, CFG_D):
+            # (the 32-row tile exists for 4 x 64 position tiles without fused upsample; other maps of such a layer run the
+            # half-empty 64-row tile -- still the fp16 split's arithmetic, 1.3-1.6x the fp32 MFMA kernel -- from a 64-row
+            # packing made on first use: PackedConv.packed)
+            tile = CFG_F if self.precision == "f16x2" and f16x2_tile_cfg(self.cout) == CFG_F and takes("f16x2", CFG_F) else \
+                CFG_D if takes(self.precision) else None
+            if tile is not None:
+                return (*plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, n_pos_tiles, (tile,), self.precision), self.precision)
+        pinned = None if pin == CFG_G else pin   # (G exists for fp16 operands only)
         allowed = (pinned,) if pinned is not None else self.allowed
-        if self.pinned_cfg is None and _CFG_EFF[CFG_D] > 0 and cfg_d_fits(self.kd, self.kh, self.kw, Hl, Wl):
+        if pin is None and _CFG_EFF[CFG_D] > 0 and takes("f32", CFG_D):
             allowed = allowed + (CFG_D,)
-            if _CFG_EFF[CFG_F] > 0 and (not ups or Wl % 128 == 0):
+            if _CFG_EFF[CFG_F] > 0 and takes("f32", CFG_F):
                 allowed = allowed + (CFG_F,)
-        if self.pinned_cfg is None and _CFG_EFF[CFG_E] > 0 and cfg_e_fits(self.kd, self.kh, self.kw, Hl, Wl):
+        if pin is None and _CFG_EFF[CFG_E] > 0 and takes("f32", CFG_E):
             allowed = allowed + (CFG_E,)
-        cfg, ks = plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, n_pos_tiles, allowed, "f32")
-        return cfg, ks, "f32"
+        return (*plan_launch(self.cout, self.cin, self.kd, self.kh, self.kw, n_pos_tiles, allowed, "f32"), "f32")
 
     def launch_plan(self, N, D, H, W, ups=False, affine=False, res=False, act="none", x16=True, out16=True, res16=True,
                     in_elems_per_sample=0, ksplit=None, want_stats=False, guard=True):
         """the ConvPlan of one launch on an [N, Cin, D, H, W] input (D = 1: a 2-D one).  affine / res: the launch carries an input
         scale / shift, a residual; x16 / out16 / res16: those tensors are 16-byte aligned (res16 is True without a residual);
-        ksplit: the caller's K split in place of the planner's; guard: ops.F16X2_GUARD at the time of the call"""
-        Hl, Wl, io16 = (2 * H if ups else H), (2 * W if ups else W), out16 and res16
+        ksplit: the caller's K split in place of the planner's; guard: ops.F16X2_GUARD at the time of the call
+        (in_elems_per_sample: Cin * D * H * W, which the sizes say already)"""
+        Hl, Wl = (2 * H if ups else H), (2 * W if ups else W)
         tiles = max(1, -(-N * D * Hl * Wl // 128))
-        # (the pointwise split kernel has the straight-line epilogue only: 16-byte aligned out / res)
-        cfg, ks, prec = self.plan_for(tiles, Hl, Wl, ups, affine, x16 and (io16 or not self.pointwise_split), in_elems_per_sample,
-                                      act, io16)
+        launch = dict(N=N, D=D, H=H, W=W, ups=ups, affine=affine, res=res, act=act, x16=x16, out16=out16, res16=res16)
+        # (a fused upsample on a 3-D input: every entry refuses it, whatever the kernel.  It is planned as its N * D slices are, so
+        # that the error is the one of the entry the layer runs on its 2-D launches)
+        cfg, ks, prec = self.plan_for(tiles, launch=dict(launch, N=N * D, D=1) if ups and D != 1 else launch)
         ks = ks if ksplit is None else int(ksplit)
         form = "direct"
         if prec == "f16x2" and self.pointwise_split:
             form = "pointwise"
-        elif ups and prec == "f16x2" and cfg == CFG_D and ks == 1 and D == 1 and up2_launch_fits(
-                self.cout, self.cin, self.kd, self.kh, self.kw, N, H, W, ups, affine=affine, res=res, act=act, aligned16=x16 and out16):
+        elif ups and prec == "f16x2" and cfg == CFG_D and up2_enabled() and launch_accepted(
+                "f16x2", self.cout, self.cin, self.kd, self.kh, self.kw, cfg=CFG_F16X2_UP2, ksplit=ks, **launch):
             form = "up2"        # an up-convolution as four 2x2 phase convolutions: same plan, weight layout CFG_F16X2_UP2
-        elif prec == "f16w8" and f16w8_rest_fits(self.cout, Hl, Wl):
-            form = "f16w8_rest"     # an odd tile count: the pairs on the eight-wave kernel, the last tile on the older fp16 kernel
+        elif prec == "f16w8":
+            form = {"f16w8": "direct", "f16w8_rest": "f16w8_rest"}[self._f16w8_entry()]
         # (a pointwise layer on the fp16 split keeps its tile statistics in the 128-position layout of the fp32 MFMA kernel that
         # recomputes it behind a raised overflow word: csrc/conv_igemm_f16x2_p1.h writes two half entries per 256-position tile)
         bp = 128 if form == "pointwise" else _BP[cfg]

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 23
+#define EMO_ABI_VERSION 24
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -253,6 +253,25 @@ int emo_conv_igemm_f16w8_rest(const float* x, const void* wpk1, const void* wpk1
                               int KD, int KH, int KW, int ups, int relu_in, int act, int res_ups, int cfg, int ksplit,
                               float* workspace, float* gn_stats, void* stream, float w_scale);
 
+/* ABI 24.  A question, not a launch: the code the convolution entry `entry` would return for a launch with these arguments --
+ * EMO_OK, or the EMO_ERR_* of the first condition of the entry or of its kernel's launcher that the launch misses; for
+ * EMO_CONV_ENTRY_F16W8_REST both of that entry's launches.  The entry's own code answers, run in a mode in which it launches
+ * nothing and makes no HIP call, so a condition of a launch form is written once, in the launcher that enforces it, and a
+ * planner asks here (emoportraits_amd.pack).  N .. ksplit, in_scale, w_scale: the entry's arguments of those names (the scales
+ * where the entry has them; cfg may be EMO_CONV_CFG_F16X2_UP2 for EMO_CONV_ENTRY_F16X2).  tensors[EMO_CONV_T_COUNT]: each
+ * tensor argument as what the conditions read of it, -1 for a null pointer, otherwise its address modulo 16 (FLAG: the
+ * overflow_flag of emo_conv_igemm_f16x2; RUN_IF: the run_if of the guarded entries).  ncu > 0: the compute units to assume for
+ * the fill rules of the pair kernels (no device is asked, the call works on a machine without one); ncu <= 0: the current
+ * device's.  The A/B switches of the launchers (EMO_CONV_CT2, EMO_CONV_CT2_MIN_ITEMS, EMO_F16_W8, ...) apply as they do to a
+ * launch.  Thread safe; EMO_ERR_BAD_ARG for an unknown entry or null tensors. */
+enum { EMO_CONV_ENTRY_F32 = 0, EMO_CONV_ENTRY_F32_GUARDED = 1, EMO_CONV_ENTRY_BF16X3 = 2, EMO_CONV_ENTRY_F16X2 = 3,
+       EMO_CONV_ENTRY_F16ACC32 = 4, EMO_CONV_ENTRY_F16W8 = 5, EMO_CONV_ENTRY_F16W8_REST = 6, EMO_CONV_ENTRY_COUNT = 7 };
+enum { EMO_CONV_T_X = 0, EMO_CONV_T_WPK = 1, EMO_CONV_T_WPK16 = 2, EMO_CONV_T_BIAS = 3, EMO_CONV_T_SCALE = 4, EMO_CONV_T_SHIFT = 5,
+       EMO_CONV_T_RES = 6, EMO_CONV_T_OUT = 7, EMO_CONV_T_WORKSPACE = 8, EMO_CONV_T_GN_STATS = 9, EMO_CONV_T_FLAG = 10,
+       EMO_CONV_T_RUN_IF = 11, EMO_CONV_T_COUNT = 12 };
+int emo_conv_accepts(int entry, const int* tensors, int N, int Cin, int Cout, int D, int H, int W, int KD, int KH, int KW,
+                     int ups, int relu_in, int act, int res_ups, int cfg, int ksplit, float in_scale, float w_scale, int ncu);
+
 /* fp32 3x3 convolution on the bf16 matrix pipes (NOT a reduced-precision mode): every fp32 operand is the exact sum of three
  * bf16 terms (x = xh + xm + xl, 24 significand bits kept), the six partial products of order <= 2^-16 are accumulated in fp32
  * by v_mfma_f32_32x32x16_bf16; the dropped terms are <= 2^-23 |x w| per product, below the fp32 accumulation error of either
@@ -326,7 +345,7 @@ int emo_conv_igemm_f16x2(const float* x, const void* wpk2, const float* bias,
  *   wpk2 then is [co_tile][Cin chunk of 16][p][q][a][b][plane 1|2][half][BM = 64][8] fp16 of w_pq * w_scale, the sums taken in
  *          fp64 from the fp32 weights, w_scale = the power of two that puts max|w_pq| into [512, 1024), both planes split from
  *          fp64 (channel in chunk = 8 * half + 0..7; emoportraits_amd.pack.pack_weight_f16x2_up2).
- * Launch form (emoportraits_amd.pack.up2_launch_fits mirrors every check): ups 1, D 1, KD 1, KH = KW = 3, ksplit 1, no residual,
+ * Launch form (a planner asks emo_conv_accepts for it, ABI 24): ups 1, D 1, KD 1, KH = KW = 3, ksplit 1, no residual,
  * act EMO_ACT_NONE, Cout % 64 == 0, Cin % 8 == 0 (Cin <= 1024 with scale / shift), W % 64 == 0, H % 2 == 0, 16-byte aligned
  * x and out, Cin * H * W * 4 < 2^32; EMO_ERR_UNSUPPORTED (EMO_ERR_ALIGN) otherwise.  gn_stats: the TileStats layout of block
  * config D, [N][4 x 64 output tiles][Cout][2]. */

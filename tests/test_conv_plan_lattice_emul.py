@@ -18,7 +18,10 @@ row, the same fp32 weights and plan): it runs once, in the f32 mode, and the oth
 
 The plan of a geometry is read from a planning-only call (a library stand-in that refuses every launch) with the geometry's own
 N and its tensors at their offsets, so the selection runs no kernel and groups by the plan that will execute.  The drawn table is
-held to its generator here as well."""
+held to its generator here as well.
+
+Every C call of a refused or a run geometry also goes, with the same arguments, to emo_conv_accepts (_Asked): the question the
+planner plans by returns the code the entry returns."""
 import ctypes
 import os
 import sys
@@ -66,6 +69,45 @@ def host():
     _PLANS.clear()
     yield lib
     mp.undo()
+
+
+_ENTRY_OF = {"emo_conv_igemm_f32": "f32", "emo_conv_igemm_f32_guarded": "f32_guarded", "emo_conv_igemm_bf16x3": "bf16x3",
+             "emo_conv_igemm_f16x2": "f16x2", "emo_conv_igemm_f16acc32": "f16", "emo_conv_igemm_f16w8": "f16w8",
+             "emo_conv_igemm_f16w8_rest": "f16w8_rest"}
+
+
+class _Asked:
+    """the host library, whose convolution entries first put their own arguments to emo_conv_accepts (tensors as null or not and
+    their address modulo 16, the library's CU count): the question's code must be the code the entry then returns"""
+
+    def __init__(self, lib):
+        self._lib, self.asked, self.bad = lib, 0, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name not in _ENTRY_OF:
+            return fn
+
+        def entry(*args):
+            k = 3 if name.endswith("_rest") else 2          # x, the weights, then what all entries share: bias .. stream
+            x, w, w16 = args[0], args[1], args[2] if k == 3 else None
+            ints, (ws, gn, _), extra = args[k + 5:k + 20], args[k + 20:k + 23], args[k + 23:]
+            in_scale, w_scale, flag, run_if = 1.0, 1.0, None, None
+            if name == "emo_conv_igemm_f16x2":
+                in_scale, w_scale, flag = extra
+            elif name in ("emo_conv_igemm_bf16x3", "emo_conv_igemm_f32_guarded"):
+                run_if, = extra
+            elif extra:
+                w_scale, = extra
+            addr = [p.value if isinstance(p, ctypes.c_void_p) else p for p in (x, w, w16, *args[k:k + 5], ws, gn, flag, run_if)]
+            tensors = (ctypes.c_int * 12)(*(-1 if not a else a % 16 for a in addr))
+            code = self._lib.emo_conv_accepts(pack._ENTRIES[_ENTRY_OF[name]], tensors, *ints, in_scale, w_scale, 0)
+            rc = fn(*args)
+            self.asked += 1
+            if rc != code:
+                self.bad.append(f"{name}{tuple(ints)}: the entry returned {rc}, emo_conv_accepts {code}")
+            return rc
+        return entry
 
 
 _PLANS = {}     # geometry -> its planned launch (one planning call per geometry and session)
@@ -143,6 +185,8 @@ def subset(mode, lib, mp):
 @pytest.mark.parametrize("mode", L.MODES)
 def test_lattice_subset_on_the_host(mode, host, monkeypatch):
     refused, accepted, left = subset(mode, host, monkeypatch)
+    asked = _Asked(host)
+    monkeypatch.setattr(hip, "load", lambda: asked)
     rows, bad = L.run_slice(refused + accepted, dev="cpu", affine=R.groupnorm_affine_fp64, seed0=1000 * L.MODES.index(mode))
     named = sorted(f"EXTRA {g.taps} {g.cout}<-{g.cin} {g.Hl}x{g.W} N={g.N}" if isinstance(g, L.Geometry) else str(g) for g in left)
     print(L.summary(f"host emulation, {mode}", rows) + f"; {len(left)} groups (plan, taps, upsample, width class) / entries of EXTRA "
@@ -153,6 +197,7 @@ def test_lattice_subset_on_the_host(mode, host, monkeypatch):
     if mode != "f32":
         assert ran - {"f32"}, f"no launch of the {mode} mode ran one of its own kernels on the host: {ran}"
     assert pack.overflow_events("cpu") == {}
+    assert asked.asked >= len(accepted) and not asked.bad, f"{len(asked.bad)} of {asked.asked} questions:\n" + "\n".join(asked.bad[:40])
 
 
 def test_the_table_is_the_drawn_one():

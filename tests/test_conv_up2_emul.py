@@ -95,7 +95,7 @@ def test_up2_overflow_word(lib):
 
 
 def test_up2_leaves_other_launch_forms_to_the_direct_kernels(lib):
-    """a 32-wide low-res map (and the other forms the kernel does not take) is refused by the C launcher and by its mirror in
+    """a 32-wide low-res map (and the other forms the kernel does not take) is refused by the C launcher and by the planner's question to it,
     pack.up2_launch_fits, so ops.conv_igemm runs the direct kernels there"""
     c = Case(1, 16, 64, (2, 32), ups=True, seed=5)
     rc, _, _ = _launch(lib, c)

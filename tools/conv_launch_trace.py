@@ -22,7 +22,7 @@ hex digits of the sha256 of every case's canonical JSON, and tests/test_conv_lau
 The cases (CASES below): the plan lattice of tests/test_conv_plan_lattice_gpu.py in its four modes and its EXTRA entries, under the
 product's fill thresholds and under the lowered ones; the fp16-split lattice with the guard off; explicit ksplit= and pinned block
 configs; out= aliasing res; HotPath.driver_pass and the stage-2 passes in the four conv modes.  pack.cu_count is pinned to 256
-(under the stub the library would answer 0) and every case starts with an empty overflow-flag pool, so a record depends neither
+(the planner's questions to the library carry it) and every case starts with an empty overflow-flag pool, so a record depends neither
 on the machine nor on the cases that ran before it.
 """
 import contextlib

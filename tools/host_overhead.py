@@ -1,5 +1,5 @@
 """Python-side cost of one driver pass: the host code runs against a STUB of libemoportraits_hip.so (every kernel entry point
-returns 0 at once; the pack-info queries go to the real library) on CPU tensors, so what is timed is argument checking, launch
+returns 0 at once; the pack-info queries and the planner's questions, emo_conv_accepts, go to the real library) on CPU tensors, so what is timed is argument checking, launch
 planning, output allocation and the ctypes calls -- no GPU needed.
 
     python tools/host_overhead.py [512] [16]   ->   ms per driver pass, launches per entry point, cProfile top list
@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from emoportraits_amd import hip  # noqa: E402
 
 QUERIES = ("emo_groupnorm_workspace_bytes", "emo_conv_pack_info", "emo_conv_pack_info_f16", "emo_conv_pack_info_bf16x3",
-           "emo_conv_tile_positions", "emo_abi_version", "emo_conv_igemm_ksplit")
+           "emo_conv_tile_positions", "emo_abi_version", "emo_conv_igemm_ksplit", "emo_conv_accepts")
 
 
 class StubLibrary:
@@ -29,6 +29,9 @@ class StubLibrary:
     def __getattr__(self, name):
         if name in QUERIES:
             return getattr(self.real, name)
+
+        if name == "emo_device_cu_count":      # (no device behind the stub: the library's answer without one)
+            return lambda: 256
 
         def entry(*args):
             self.calls[name] += 1
