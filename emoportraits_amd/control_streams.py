@@ -3,7 +3,8 @@
 the two keywords (expression_plan, head_pose_plan, and stream_expression / stream_head_pose for animate_streams).  The value types
 are in controls.py, which stays pure Python; the arithmetic is ops.theta_ema_scan / expression_controls / head_pose_controls.
 Crop tracking (boxes=, tracking=) has its own store, CropStates -- its streams are tracks of the video, not identities -- its own
-checks, crop_plan, and BoxFeed, which hands out the boxes as the frames come; the arithmetic is ops.crop_track."""
+checks, crop_plan, and BoxFeed, which hands out the boxes as the frames come; the arithmetic is ops.crop_track.  detections= (unordered
+detections in place of ordered boxes) adds TrackStates, the tracks that ops.track_assign associates the detections to."""
 import itertools
 from argparse import Namespace
 
@@ -292,6 +293,27 @@ class CropStates:
             self.last.index_fill_(0, rows, 0)
 
 
+class TrackStates:
+    """The tracks of K video streams that detections= are associated to (ops.track_assign), on the device: `ref` [K,P,4] float64 =
+    each track's last matched box and `age` [K,P] int32 (-1: the slot is free; >= 0: live, that many consecutive frames without a
+    detection).  Beside CropStates, whose stream p is the crop tracker of track p; restarted with it."""
+
+    def __init__(self, K, P, device):
+        self.K, self.P, self.device = K, P, device
+        self.ref = torch.zeros((K, P, 4), device=device, dtype=torch.float64)
+        self.age = torch.full((K, P), -1, device=device, dtype=torch.int32)
+
+    def restart(self, tracks=None):
+        """the slots `tracks` of every stream (host ints; None: all of them) are free again: device fills, no host synchronisation"""
+        if tracks is None:
+            self.age.fill_(-1)
+        else:
+            cols = torch.tensor([int(p) for p in tracks], dtype=torch.int64)
+            if cols.numel() and (int(cols.min()) < 0 or int(cols.max()) >= self.P):
+                raise ValueError(f"a track outside the {self.P} being tracked")
+            self.age.index_fill_(1, cols.to(self.device), -1)
+
+
 def check_boxes(t, what):
     """one tensor of boxes: floating point, [n,4] or [n,P,4] -> P (None: one box per frame)"""
     if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.float64):
@@ -328,12 +350,21 @@ class BoxFeed:
         return t.to(self.device)
 
 
-def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, device, what="boxes"):
+def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, device, what="boxes", detections=None):
     """The checks of boxes= and tracking= (a CropTracking or a mapping with its fields), before anything is launched -> None (no
     boxes: nothing will be launched) or what InferenceWrapper._track_chunk needs: the tracker's settings, tracks = P of boxes
     [N,P,4] (None: [N,4]) and feed, the BoxFeed.  n_frames: the frames of the call where known; other: the name of a keyword given
-    beside boxes that also says where the faces are ('windows' | 'faces'), or None; default_momentum: the wrapper's crop momentum."""
+    beside boxes that also says where the faces are ('windows' | 'faces'), or None; default_momentum: the wrapper's crop momentum.
+    detections: unordered detections [N,D,4] (or an iterable of chunks) in place of boxes -- mutually exclusive with it and with
+    `other`; tracking.tracks = P <= min(16, batch_size) says how many track slots a frame has, D <= 32.  The plan then has
+    detections = D (None: boxes=), tracks = P, min_iou and max_missed, and its feed hands out the detections."""
     tr = CropTracking.of(tracking)
+    if detections is not None:
+        if boxes is not None:
+            raise ValueError("detections= (unordered, the tracks are formed on the device) and boxes= (ordered tracks) are mutually exclusive")
+        boxes, what = detections, "detections"
+    elif tr is not None and tr.tracks is not None:
+        raise ValueError("tracking tracks= says how many tracks detections= are associated to: detections= is missing")
     if boxes is None:
         if tr is not None:
             raise ValueError("tracking= says how boxes= become windows: boxes= is missing")
@@ -352,6 +383,21 @@ def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, de
     scale = float(tr.scale)
     if scale != scale or scale in (float("inf"), float("-inf")):
         raise ValueError(f"crop scale {tr.scale} is not finite")
+    n_dets = min_iou = max_missed = None
+    if detections is not None:
+        from .hostglue import TRACK_MAX_DETECTIONS, TRACK_MAX_TRACKS
+        P = tr.tracks
+        if P is None:
+            raise ValueError("detections= needs tracking tracks=P: the number of track slots per frame")
+        if isinstance(P, bool) or not isinstance(P, int) or not 1 <= P <= TRACK_MAX_TRACKS:
+            raise ValueError(f"tracking tracks {P!r} is not an integer in 1 ... {TRACK_MAX_TRACKS}")
+        if P > batch_size:
+            raise ValueError(f"tracking tracks={P}: more tracks per frame than batch_size={batch_size}")
+        min_iou, max_missed = float(tr.min_iou), tr.max_missed
+        if not 0.0 < min_iou <= 1.0:
+            raise ValueError(f"tracking min_iou {tr.min_iou} is not in (0, 1]")
+        if isinstance(max_missed, bool) or not isinstance(max_missed, int) or max_missed < 0:
+            raise ValueError(f"tracking max_missed {max_missed!r} is not an integer >= 0")
     tracks = None
     if isinstance(boxes, torch.Tensor):
         tracks = check_boxes(boxes, what)
@@ -367,7 +413,14 @@ def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, de
             raise ValueError(f"{what} ended before the frames did: it is empty")
         tracks = check_boxes(head, f"a chunk of {what}")
         boxes = itertools.chain([head], boxes)
-    if tracks is not None and tracks > batch_size:
+    if detections is not None:
+        if tracks is None:
+            raise ValueError("detections must be [N,D,4], D detections per frame padded with NaN rows: got [N,4]")
+        if tracks > TRACK_MAX_DETECTIONS:
+            raise ValueError(f"detections has D = {tracks} per frame: at most {TRACK_MAX_DETECTIONS} are served")
+        n_dets, tracks = tracks, tr.tracks
+    elif tracks is not None and tracks > batch_size:
         raise ValueError(f"{what} has {tracks} tracks per frame: more than batch_size={batch_size}")
     return Namespace(smooth=bool(tr.smooth), fixed=bool(tr.fixed), momentum=m, scale=scale, box_format=tr.box_format, missing=tr.missing,
-                     tracks=tracks, feed=BoxFeed(boxes, device, tracks, what))
+                     tracks=tracks, detections=n_dets, min_iou=min_iou, max_missed=max_missed,
+                     feed=BoxFeed(boxes, device, tracks if n_dets is None else n_dets, what))

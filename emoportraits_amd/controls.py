@@ -82,6 +82,12 @@ class CropTracking:
     missing: what a row without a usable window is given: 'skip' = it is not pasted (paste_back returns its frame as it came) and
         is rendered, where crops are returned, from the centred square of its frame; 'hold' = the track's last window, where it
         has one that fits the row's frame.
+    tracks, min_iou, max_missed: for `detections=` only (unordered detections [N,D,4] in place of boxes=; ops.track_assign,
+        hostglue.track_assign states it).  tracks = P, the number of track slots per frame, 1 ... min(16, batch_size): column p of
+        the rows is one face from frame to frame, rendered as the identity given for column p.  A detection continues the track
+        whose last matched box it overlaps most, if their IoU is at least min_iou (in (0, 1]); a track that finds no detection
+        for more than max_missed consecutive frames is dropped and its slot is free for the next new face.  0.3 and 15 are
+        taste defaults, not measured optima.
     All defaults = the reference's per-frame window (use_smoothed_crop=False)."""
     smooth: bool = False
     momentum: object = None
@@ -89,6 +95,9 @@ class CropTracking:
     scale: float = 1.0
     box_format: str = "xyxy"
     missing: str = "skip"
+    tracks: object = None
+    min_iou: float = 0.3
+    max_missed: int = 15
 
     @classmethod
     def of(cls, value):

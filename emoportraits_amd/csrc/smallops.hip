@@ -493,8 +493,8 @@ __global__ __launch_bounds__(64) void crop_track_kernel(const double* __restrict
                                                         const int* __restrict__ sizes, int Wf, int Hf, double* __restrict__ state,
                                                         int* __restrict__ has, int* __restrict__ last, int M, int K, double m,
                                                         double om, int smooth, int fixed, double scale, int box_format, int hold,
-                                                        int min_side, int* __restrict__ crop, int* __restrict__ paste,
-                                                        double* __restrict__ face_scale) {
+                                                        int min_side, const int* __restrict__ restart, int* __restrict__ crop,
+                                                        int* __restrict__ paste, double* __restrict__ face_scale) {
   const int k = blockIdx.x * 64 + threadIdx.x;
   if (k >= K) return;
   bool had = smooth && has[k] != 0;
@@ -504,11 +504,18 @@ __global__ __launch_bounds__(64) void crop_track_kernel(const double* __restrict
   int lw[4] = {0, 0, 0, 0};
   if (last)
     for (int j = 0; j < 4; ++j) lw[j] = last[(long)k * 4 + j];
-  bool touched = false, kept = false;
+  bool touched = false, kept = false, cleared = false;
   for (int i = 0; i < M; ++i) {
     const int ki = stream_of ? stream_of[i] : 0;
     const bool in_range = ki >= 0 && ki < K;
     if (in_range ? ki != k : k != 0) continue;
+    if (restart && in_range && restart[i] != 0) {             // (ABI 25: the stream begins again at this row)
+      had = false;
+      touched = false;
+      kept = false;
+      cleared = true;
+      for (int j = 0; j < 4; ++j) lw[j] = 0;
+    }
     const int W = sizes ? sizes[2 * i] : Wf, H = sizes ? sizes[2 * i + 1] : Hf;
     int* const c = crop + (long)i * 4;
     int* const p = paste + (long)i * 4;
@@ -584,17 +591,166 @@ __global__ __launch_bounds__(64) void crop_track_kernel(const double* __restrict
   if (touched) {
     for (int j = 0; j < 3; ++j) state[(long)k * 3 + j] = st[j];
     has[k] = 1;
+  } else if (cleared && smooth) {
+    has[k] = 0;
   }
-  if (kept && last)
+  if ((kept || cleared) && last)
     for (int j = 0; j < 4; ++j) last[(long)k * 4 + j] = lw[j];
+}
+
+// Unordered detections -> ordered track rows (include/emo_hip.h, ABI 25; hostglue.track_assign is the contract): greedy IoU
+// association, one block of one wave per video stream, the frames of the stream walked in order.  The stream's tracks (ref, age)
+// live in LDS for the whole walk; per frame the lanes d < D take a detection each, the P x D IoU matrix lies across the lanes (pair
+// p * D + d on lane (p * D + d) % 64, at most eight a lane, in registers), and every round of the matching is an xor butterfly over
+// the total order (IoU, then the smaller pair index = the smaller p, then the smaller d): every lane ends with the same winner, so
+// the loop's trip count is uniform and its result does not depend on the butterfly's shape.  Lane 0 books the winner; births are a
+// serial walk of lane 0 over at most 32 detections; the rows of the frame are written by the lanes p < P and d < D at its end.
+// The block is one wave, so its barriers cost nothing on the device; they are what orders the lanes' LDS traffic.
+constexpr int kTrackMaxP = 16, kTrackMaxD = 32, kTrackPairs = kTrackMaxP * kTrackMaxD / 64;
+constexpr unsigned long long kQuietNaN = 0x7ff8000000000000ull;
+
+__global__ __launch_bounds__(64) void track_assign_kernel(const double* __restrict__ dets, const int* __restrict__ stream_of, int F,
+                                                          int D, int P, int K, double* __restrict__ ref, int* __restrict__ age,
+                                                          double min_iou, int max_missed, int box_format,
+                                                          double* __restrict__ boxes_out, int* __restrict__ restart,
+                                                          int* __restrict__ track_of) {
+  __shared__ double s_ref[kTrackMaxP][4];
+  __shared__ double s_box[kTrackMaxD][4];
+  __shared__ int s_age[kTrackMaxP], s_row[kTrackMaxP], s_restart[kTrackMaxP], s_done[kTrackMaxP];
+  __shared__ int s_usable[kTrackMaxD], s_track[kTrackMaxD];
+  const int k = blockIdx.x, lane = threadIdx.x;
+  if (lane < P) {
+    s_age[lane] = age[(long)k * P + lane];
+    for (int j = 0; j < 4; ++j) s_ref[lane][j] = ref[((long)k * P + lane) * 4 + j];
+  }
+  __syncthreads();
+  const unsigned long long* const dets_bits = reinterpret_cast<const unsigned long long*>(dets);
+  unsigned long long* const out_bits = reinterpret_cast<unsigned long long*>(boxes_out);
+  for (int f = 0; f < F; ++f) {
+    const int kf = stream_of ? stream_of[f] : 0;
+    const bool in_range = kf >= 0 && kf < K;
+    if (in_range ? kf != k : k != 0) continue;                // (uniform over the block: f and k are)
+    if (!in_range) {                                          // no stream: block 0 says so, no state is touched
+      if (lane < P) {
+        for (int j = 0; j < 4; ++j) out_bits[((long)f * P + lane) * 4 + j] = kQuietNaN;
+        restart[(long)f * P + lane] = 0;
+      }
+      if (lane < D) track_of[(long)f * D + lane] = -1;
+      continue;
+    }
+    // the frame's detections, one a lane: the box and whether it can be used; s_done[p]: the row of track p is decided
+    if (lane < D) {
+      const double* const b = dets + ((long)f * D + lane) * 4;
+      double x0 = b[0], y0 = b[1], x1 = b[2], y1 = b[3];
+      if (box_format == 1) { x1 = b[0] + b[2]; y1 = b[1] + b[3]; }
+      s_box[lane][0] = x0; s_box[lane][1] = y0; s_box[lane][2] = x1; s_box[lane][3] = y1;
+      s_usable[lane] = crop_in_range(x0) && crop_in_range(y0) && crop_in_range(x1) && crop_in_range(y1) && x1 > x0 && y1 > y0;
+      s_track[lane] = -1;
+    }
+    if (lane < P) { s_done[lane] = 0; s_row[lane] = -1; s_restart[lane] = 0; }
+    __syncthreads();
+    // the IoU of the lane's pairs; -1 where the track is free or the detection unusable
+    double iou[kTrackPairs];
+    for (int j = 0; j < kTrackPairs; ++j) {
+      const int idx = lane + 64 * j;
+      iou[j] = -1.0;
+      if (idx >= P * D) continue;
+      const int p = idx / D, d = idx % D;
+      if (s_age[p] < 0 || !s_usable[d]) continue;
+      const double ax0 = s_ref[p][0], ay0 = s_ref[p][1], ax1 = s_ref[p][2], ay1 = s_ref[p][3];
+      const double bx0 = s_box[d][0], by0 = s_box[d][1], bx1 = s_box[d][2], by1 = s_box[d][3];
+      const double iw = (ax1 < bx1 ? ax1 : bx1) - (ax0 > bx0 ? ax0 : bx0), ih = (ay1 < by1 ? ay1 : by1) - (ay0 > by0 ? ay0 : by0);
+      double v = 0.0;
+      if (iw > 0.0 && ih > 0.0) {
+        const double inter = iw * ih;
+        const double area_a = (ax1 - ax0) * (ay1 - ay0), area_b = (bx1 - bx0) * (by1 - by0);
+        v = inter / ((area_a + area_b) - inter);
+      }
+      iou[j] = v;
+    }
+    // 1. match: the best remaining pair, until none reaches min_iou
+    for (int round = 0; round < kTrackMaxP; ++round) {
+      double best = -1.0;
+      int best_idx = 0x7fffffff;
+      for (int j = 0; j < kTrackPairs; ++j) {
+        const int idx = lane + 64 * j;
+        if (idx >= P * D || !(iou[j] >= 0.0)) continue;
+        if (s_done[idx / D] || s_track[idx % D] >= 0) continue;
+        if (iou[j] > best || (iou[j] == best && idx < best_idx)) { best = iou[j]; best_idx = idx; }
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(best, off);
+        const int oi = __shfl_xor(best_idx, off);
+        if (o > best || (o == best && oi < best_idx)) { best = o; best_idx = oi; }
+      }
+      if (best_idx == 0x7fffffff || !(best >= min_iou)) break;   // (the same on every lane)
+      if (lane == 0) {
+        const int p = best_idx / D, d = best_idx % D;
+        for (int j = 0; j < 4; ++j) s_ref[p][j] = s_box[d][j];
+        s_age[p] = 0;
+        s_done[p] = 1;
+        s_row[p] = d;
+        s_track[d] = p;
+      }
+      __syncthreads();
+    }
+    __syncthreads();
+    // 2. age: a live track without a match waits, or dies past max_missed
+    if (lane < P && s_age[lane] >= 0 && !s_done[lane]) {
+      s_age[lane] = s_age[lane] + 1;
+      if (s_age[lane] > max_missed) { s_age[lane] = -1; s_restart[lane] = 1; }
+      s_done[lane] = 1;
+    }
+    __syncthreads();
+    // 3. births: the detections left over, in ascending d, each into the lowest free slot
+    if (lane == 0) {
+      int p = 0;
+      for (int d = 0; d < D; ++d) {
+        if (!s_usable[d] || s_track[d] >= 0) continue;
+        while (p < P && s_age[p] >= 0) ++p;
+        if (p >= P) break;
+        for (int j = 0; j < 4; ++j) s_ref[p][j] = s_box[d][j];
+        s_age[p] = 0;
+        s_done[p] = 1;
+        s_row[p] = d;
+        s_restart[p] = 1;
+        s_track[d] = p;
+      }
+    }
+    __syncthreads();
+    // 4. the frame's rows: a track's detection bit for bit, or the quiet NaN
+    if (lane < P) {
+      const int d = s_row[lane];
+      for (int j = 0; j < 4; ++j)
+        out_bits[((long)f * P + lane) * 4 + j] = d < 0 ? kQuietNaN : dets_bits[((long)f * D + d) * 4 + j];
+      restart[(long)f * P + lane] = s_restart[lane];
+    }
+    if (lane < D) track_of[(long)f * D + lane] = s_track[lane];
+    __syncthreads();
+  }
+  if (lane < P) {
+    age[(long)k * P + lane] = s_age[lane];
+    for (int j = 0; j < 4; ++j) ref[((long)k * P + lane) * 4 + j] = s_ref[lane][j];
+  }
 }
 
 }  // namespace
 
-extern "C" int emo_crop_track_f64(const double* boxes, const int32_t* stream_of, const int32_t* sizes, int Wf, int Hf, double* state,
-                                  int32_t* has_state, int32_t* last, int M, int K, double m, double om, int smooth, int fixed,
-                                  double scale, int box_format, int hold, int min_side, int32_t* crop, int32_t* paste,
-                                  double* face_scale, void* stream) {
+extern "C" int emo_track_assign_f64(const double* dets, const int32_t* stream_of, int F, int D, int P, int K, double* ref,
+                                    int32_t* age, double min_iou, int max_missed, int box_format, double* boxes_out,
+                                    int32_t* restart, int32_t* track_of, void* stream) {
+  if (!dets || !ref || !age || !boxes_out || !restart || !track_of) return EMO_ERR_BAD_ARG;
+  if (F <= 0 || D <= 0 || P <= 0 || K <= 0 || P > kTrackMaxP || D > kTrackMaxD) return EMO_ERR_BAD_ARG;
+  if (!(min_iou > 0.0 && min_iou <= 1.0) || max_missed < 0 || (box_format != 0 && box_format != 1)) return EMO_ERR_BAD_ARG;
+  hipLaunchKernelGGL(track_assign_kernel, dim3(K), dim3(64), 0, (hipStream_t)stream, dets, stream_of, F, D, P, K, ref, age, min_iou,
+                     max_missed, box_format, boxes_out, restart, track_of);
+  return emo_launch_status();
+}
+
+extern "C" int emo_crop_track_restarts_f64(const double* boxes, const int32_t* stream_of, const int32_t* sizes, int Wf, int Hf,
+                                           double* state, int32_t* has_state, int32_t* last, int M, int K, double m, double om,
+                                           int smooth, int fixed, double scale, int box_format, int hold, int min_side,
+                                           const int32_t* restart, int32_t* crop, int32_t* paste, double* face_scale, void* stream) {
   if (!boxes || !crop || !paste || M <= 0 || K <= 0) return EMO_ERR_BAD_ARG;
   if (!sizes && (Wf < 1 || Hf < 1)) return EMO_ERR_BAD_ARG;
   if (smooth && (!state || !has_state)) return EMO_ERR_BAD_ARG;
@@ -603,8 +759,16 @@ extern "C" int emo_crop_track_f64(const double* boxes, const int32_t* stream_of,
   if (!((scale - scale) == 0.0) || (box_format != 0 && box_format != 1) || min_side < 1) return EMO_ERR_BAD_ARG;
   hipLaunchKernelGGL(crop_track_kernel, dim3(emo_cdiv(K, 64)), dim3(64), 0, (hipStream_t)stream, boxes, stream_of, sizes, Wf, Hf,
                      state, has_state, last, M, K, m, om, smooth ? 1 : 0, fixed ? 1 : 0, scale, box_format, hold ? 1 : 0, min_side,
-                     crop, paste, face_scale);
+                     restart, crop, paste, face_scale);
   return emo_launch_status();
+}
+
+extern "C" int emo_crop_track_f64(const double* boxes, const int32_t* stream_of, const int32_t* sizes, int Wf, int Hf, double* state,
+                                  int32_t* has_state, int32_t* last, int M, int K, double m, double om, int smooth, int fixed,
+                                  double scale, int box_format, int hold, int min_side, int32_t* crop, int32_t* paste,
+                                  double* face_scale, void* stream) {
+  return emo_crop_track_restarts_f64(boxes, stream_of, sizes, Wf, Hf, state, has_state, last, M, K, m, om, smooth, fixed, scale,
+                                     box_format, hold, min_side, nullptr, crop, paste, face_scale, stream);
 }
 
 extern "C" int emo_small_gemm_f32(const float* A, const float* B, float* C, int M, int K, int NN, int batch,

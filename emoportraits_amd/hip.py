@@ -69,6 +69,9 @@ SIGNATURES = {
     "emo_head_pose_controls_f32": [_c_void, _c_int] + [_c_void] * 10 + [_c_int] * 4 + [_c_void] * 3,
     "emo_crop_track_f64": [_c_void] * 3 + [_c_int, _c_int] + [_c_void] * 3 + [_c_int, _c_int, _c_double, _c_double, _c_int, _c_int,
                            _c_double] + [_c_int] * 3 + [_c_void] * 4,
+    "emo_crop_track_restarts_f64": [_c_void] * 3 + [_c_int, _c_int] + [_c_void] * 3 + [_c_int, _c_int, _c_double, _c_double, _c_int,
+                                    _c_int, _c_double] + [_c_int] * 3 + [_c_void] * 5,
+    "emo_track_assign_f64": [_c_void, _c_void] + [_c_int] * 4 + [_c_void, _c_void, _c_double, _c_int, _c_int] + [_c_void] * 4,
     "emo_mul_mask_f32": [_c_void, _c_void, _c_void, _c_int, _c_int, _c_i64, _c_void],
     "emo_stage2_compose_f32": [_c_void] * 5 + [_c_int, _c_int, _c_i64, _c_void],
     "emo_small_gemm_f32": [_c_void] * 3 + [_c_int] * 4 + [_c_i64, _c_i64, _c_void],

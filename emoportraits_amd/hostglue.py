@@ -76,7 +76,7 @@ def window_inside(x_lo, y_lo, side, img_w, img_h, min_side=1):
 
 
 def crop_track(boxes, stream_of, size, state, has, last, momentum=0.01, smooth=False, fixed=False, scale=1.0, box_format="xyxy",
-               missing="skip", min_side=2, K=None, why=None):
+               missing="skip", min_side=2, K=None, why=None, restart=None):
     """Face boxes -> crop and paste windows for a whole batch of rows, one row after another: crop_window with a CropTracker per
     stream (notebooks/infer.py:301-352, crop_image's arithmetic), plus what a batch needs that one frame did not -- a row whose
     face is missing or whose window does not fit still gets a window that can be read, and says so.  The contract that
@@ -106,7 +106,10 @@ def crop_track(boxes, stream_of, size, state, has, last, momentum=0.01, smooth=F
             (H - side) // 2), which can always be read, and paste = (0, 0, 0, 0), which every paste kernel skips.
     why: a list that receives, per row, 'present' or what made the row missing ('stream', 'box') or absent ('size', 'side',
     'min_side'; 'guard' = the range test of the centre and the side or the inside test, which no finite box below 2^30 in a frame
-    below 2^30 reaches: they are made so that no value is trusted)."""
+    below 2^30 reaches: they are made so that no value is trusted).
+    restart [M] ints or None (emo_crop_track_restarts_f64; track_assign's, flattened to the rows): a row i of a stream in [0, K)
+    with restart[i] != 0 first clears its stream -- has[k] = 0 under `smooth`, last[k] = 0 where last is given -- and is then
+    processed as above: a birth starts the EMA at its own box, a track that died is no longer held."""
     b = np.ascontiguousarray(boxes, dtype=np.float64)
     if b.ndim != 2 or b.shape[1] != 4:
         raise ValueError(f"boxes must be [M,4], got {b.shape}")
@@ -140,6 +143,11 @@ def crop_track(boxes, stream_of, size, state, has, last, momentum=0.01, smooth=F
             W, H = int(sizes[i, 0]), int(sizes[i, 1])
             k = 0 if stream_of is None else int(stream_of[i])
             in_range = 0 <= k < K
+            if restart is not None and in_range and int(restart[i]) != 0:
+                if smooth:
+                    has[k] = 0
+                if last is not None:
+                    last[k] = 0
             if box_format == "relative":
                 x0, y0, x1, y1 = (np.float64(v) for v in detection_to_face(b[i, 0], b[i, 1], b[i, 2], b[i, 3], W, H))
             else:
@@ -186,6 +194,93 @@ def crop_track(boxes, stream_of, size, state, has, last, momentum=0.01, smooth=F
             side_i = min(W, H)
             crop[i] = ((W - side_i) // 2, (H - side_i) // 2, side_i, side_i)
     return crop, paste, face_scale
+
+
+TRACK_MAX_TRACKS, TRACK_MAX_DETECTIONS = 16, 32
+_QUIET_NAN = np.uint64(0x7ff8000000000000)
+
+
+def box_iou(a, b):
+    """IoU of two boxes (x0, y0, x1, y1) of float64, in the order of operations of include/emo_hip.h (ABI 25)"""
+    iw = min(a[2], b[2]) - max(a[0], b[0])
+    ih = min(a[3], b[3]) - max(a[1], b[1])
+    if iw <= 0 or ih <= 0:
+        return np.float64(0.0)
+    inter = iw * ih
+    return inter / (((a[2] - a[0]) * (a[3] - a[1]) + (b[2] - b[0]) * (b[3] - b[1])) - inter)
+
+
+def track_assign(dets, stream_of, ref, age, min_iou=0.3, max_missed=15, box_format="xyxy"):
+    """Unordered detections -> ordered track rows, one frame after another: greedy IoU association of the detections of every frame
+    to the P track slots of its video stream.  The contract that emo_track_assign_f64 (ops.track_assign) is held to bit for bit;
+    include/emo_hip.h (ABI 25) has the same text.
+    dets [F,D,4] float64, frame order, D <= 32, NaN rows = padding; stream_of [F] ints or None (every frame: stream 0); ref [K,P,4]
+    float64 = each track's last matched box (x0, y0, x1, y1) and age [K,P] int32 (-1: the slot is free; >= 0: live, that many
+    consecutive frames without a match) are the streams' state, UPDATED IN PLACE (numpy arrays), P <= 16; min_iou in (0, 1];
+    max_missed >= 0; box_format 'xyxy', or 'relative' = (xmin, ymin, width, height), whose box is (d0, d1, d0 + d2, d1 + d3): IoU does
+    not change under a scaling of an axis, so neither the frame size nor detection_to_face's 0.9 / 1.2 enter here.
+    -> (boxes [F,P,4] float64, restart [F,P] int32, track_of [F,D] int32).  A frame of stream k:
+        usable: a detection whose box is finite and below 2^30 in all four values, with x1 > x0 and y1 > y0
+        1. match: repeat -- among the live tracks without a match in this frame and the usable detections without a track, the
+           pair of the largest box_iou(ref[k,p], box), ties to the smaller p, then the smaller d; stop when there is none or its IoU
+           < min_iou.  ref[k,p] = the box, age[k,p] = 0, boxes[f,p] = dets[f,d] bit for bit, restart[f,p] = 0, track_of[f,d] = p
+        2. age: every live track without a match: age += 1; past max_missed it dies: age = -1, restart[f,p] = 1.  Its row is NaN
+        3. birth: the usable detections without a track, in ascending d, each into the lowest free slot (those freed in step 2
+           included): ref, age = 0, boxes[f,p] = dets[f,d], restart[f,p] = 1, track_of[f,d] = p; -1 with no slot left
+        4. every other slot: a NaN row, restart 0; every other detection: track_of = -1
+    NaN rows are the quiet NaN 0x7ff8000000000000.  A frame whose stream lies outside [0, K) gets NaN rows, restart 0, track_of
+    -1 and touches no state."""
+    d = np.ascontiguousarray(dets, dtype=np.float64)
+    if d.ndim != 3 or d.shape[2] != 4 or d.shape[0] == 0 or not 0 < d.shape[1] <= TRACK_MAX_DETECTIONS:
+        raise ValueError(f"dets must be [F,D,4] with 1 <= D <= {TRACK_MAX_DETECTIONS}, got {d.shape}")
+    if box_format not in CROP_BOX_FORMATS:
+        raise ValueError(f"box_format {box_format!r}: 'xyxy' or 'relative'")
+    if ref.ndim != 3 or ref.shape[2] != 4 or age.shape != ref.shape[:2] or not 0 < ref.shape[1] <= TRACK_MAX_TRACKS or ref.shape[0] == 0:
+        raise ValueError(f"ref [K,P,4] and age [K,P] with 1 <= P <= {TRACK_MAX_TRACKS}, got {ref.shape} and {age.shape}")
+    min_iou = np.float64(min_iou)
+    if not 0.0 < min_iou <= 1.0:
+        raise ValueError(f"min_iou {min_iou} is not in (0, 1]")
+    if int(max_missed) != max_missed or max_missed < 0:
+        raise ValueError(f"max_missed {max_missed} is not an integer >= 0")
+    F, D = d.shape[:2]
+    K, P = age.shape
+    boxes = np.empty((F, P, 4), np.float64)
+    boxes.view(np.uint64)[:] = _QUIET_NAN
+    restart, track_of = np.zeros((F, P), np.int32), np.full((F, D), -1, np.int32)
+    with np.errstate(all="ignore"):
+        for f in range(F):
+            k = 0 if stream_of is None else int(stream_of[f])
+            if not 0 <= k < K:
+                continue
+            box = d[f].copy()
+            if box_format == "relative":
+                box[:, 2], box[:, 3] = d[f, :, 0] + d[f, :, 2], d[f, :, 1] + d[f, :, 3]
+            usable = [bool(all(np.isfinite(v) and abs(v) < _CROP_RANGE for v in b) and b[2] > b[0] and b[3] > b[1]) for b in box]
+            iou = {(p, j): box_iou(ref[k, p], box[j]) for p in range(P) if age[k, p] >= 0 for j in range(D) if usable[j]}
+            matched = set()
+            while True:
+                best = None
+                for (p, j), v in sorted(iou.items()):                              # (ascending p, then d: the first of equals wins)
+                    if p not in matched and track_of[f, j] < 0 and v >= 0 and (best is None or v > best[0]):
+                        best = (v, p, j)
+                if best is None or not best[0] >= min_iou:
+                    break
+                _, p, j = best
+                ref[k, p], age[k, p], boxes[f, p], track_of[f, j] = box[j], 0, d[f, j], p
+                matched.add(p)
+            for p in range(P):
+                if age[k, p] >= 0 and p not in matched:
+                    age[k, p] += 1
+                    if age[k, p] > max_missed:
+                        age[k, p], restart[f, p] = -1, 1
+            for j in range(D):
+                if usable[j] and track_of[f, j] < 0:
+                    free = [p for p in range(P) if age[k, p] < 0]
+                    if not free:
+                        break
+                    p = free[0]
+                    ref[k, p], age[k, p], boxes[f, p], restart[f, p], track_of[f, j] = box[j], 0, d[f, j], 1, p
+    return boxes, restart, track_of
 
 
 def mixing_theta(source_theta, target_theta, mix_old=True):

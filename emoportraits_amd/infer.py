@@ -199,8 +199,11 @@ class InferenceWrapper:
         self._stage2 = self._stage2_wrapper = None                                 # attach_stage2()
         # crop tracking of animate_frames(boxes=): the tracks' state on the device (control_streams.CropStates, made at the first
         # use), apart from the host _crop_tracker of forward(crop=True); tracked_windows = (the paste windows of the chunk last
-        # tracked, int32 [rows,4] on the device, side 0 = no face; the index of its first row in the call)
+        # tracked, int32 [rows,4] on the device, side 0 = no face; the index of its first row in the call).  detections=: the
+        # tracks the detections are associated to (control_streams.TrackStates), and tracked_assignment = (track_of [n,D], restart
+        # [n,P]) of the chunk last tracked, int32 on the device
         self._crop_streams = self.tracked_windows = None
+        self._track_states = self.tracked_assignment = None
         self._init_identity_bank(identity_capacity)
 
     @property
@@ -366,9 +369,12 @@ class InferenceWrapper:
     def reset_crop_state(self, tracks=None):
         """Restart the crop tracker of animate_frames(boxes=) -- the EMA of tracking=dict(smooth=True) and the window that
         missing='hold' holds: tracks=None every track, otherwise the given ones (track p of boxes [N,P,4]; 0 for [N,4]).  The
-        tracks are faces of the video, not identities: store_identity, drop_identity and the other bank events leave them alone."""
+        tracks are faces of the video, not identities: store_identity, drop_identity and the other bank events leave them alone.
+        The tracks of animate_frames(detections=) are freed as well: their slots take the next new faces."""
         if self._crop_streams is not None:
             self._crop_streams.restart(tracks)
+        if getattr(self, "_track_states", None) is not None:
+            self._track_states.restart(tracks)
 
     def _restart(self, slots, **which):
         """slots=None: the single stream and every slot's; a slot or several: theirs (StreamStates.restart)"""
@@ -1194,7 +1200,8 @@ class InferenceWrapper:
     def animate_frames(self, frames, batch_size=16, windows=None, ring=3, to_host=True, smooth_pose=False, identities=None,
                        mix=False, mix_old=True, target_theta=True, smooth_per_identity=False, paste_back=False, feather=0.0625,
                        paste_matte=None, as_uint8=True, refine=False, refine_masks=None, frame_format="rgb8", out_format=None,
-                       colorspace="bt709", full_range=False, faces=None, expression=None, head_pose=None, boxes=None, tracking=None):
+                       colorspace="bt709", full_range=False, faces=None, expression=None, head_pose=None, boxes=None, tracking=None,
+                       detections=None):
         """Video in -> video out, device resident (notebooks/infer.py:511-556, :562-601, :641-644 per
         frame there).  Per batch, all on the device and without a host synchronisation:
             byte -> fp32 CHW (emo_unpack_rgb8) -> crop windows read in place + bicubic resize to image_size, the whole batch in
@@ -1329,16 +1336,33 @@ class InferenceWrapper:
             tracker is made anew when P changes), P <= batch_size, identities= one slot per row, and faces=' rules for smooth_pose
             and the relative controls.  Not here: enrol_identities, paste_back() (it takes device windows already), running a
             detector, and device tensors as windows= (the rgb8 crop kernel trusts its windows; only the tracker's own test makes
-            device windows safe to read)."""
+            device windows safe to read).
+        detections: a detector's output as it comes, in place of boxes= (with boxes=, windows= or faces=: ValueError) -- float32 /
+            float64 [N,D,4], host or device, or an iterable of one such tensor per chunk in lockstep: up to D <= 32 boxes per frame
+            in NO stable order, a frame with fewer padded with NaN rows.  tracking= must say tracks=P, the number of track slots
+            per frame (P <= min(16, batch_size)), and may say min_iou and max_missed.  Per chunk, in front of the tracker's
+            launch, ONE more launch on every rank (ops.track_assign, bit for bit hostglue.track_assign: greedy IoU association,
+            one wave, the frames in order; no gather) orders the detections into boxes [n,P,4] and a restart flag per row, and
+            from there on it is the boxes [N,P,4] path above with ops.crop_track(restart=): rows frame-major, identities= one
+            slot per row -- track p is rendered as the identity given for column p -- and faces=' rules for smooth_pose and the
+            relative controls.  A new face is born into the lowest free slot and starts the crop EMA at its own box; a track
+            without a detection for more than max_missed frames dies, is no longer held by missing='hold', and frees its slot.
+            The tracks are carried on the device from chunk to chunk and call to call like the tracker's state, and freed with
+            it (reset_crop_state, forward(reset_tracking=True)); the result does not depend on batch_size, the chunking or the
+            number of ranks.  tracked_assignment is left as (track_of int32 [n,D]: the track of every detection of the chunk
+            last tracked or -1; restart int32 [n,P]), beside tracked_windows.  Not done: an identity's pose and expression
+            streams (smooth_pose, the relative controls) are not restarted at a birth in its column -- reset them by hand where
+            that matters; a row without a face is still rendered, as above, and not pasted; animate_streams keeps one track per
+            stream and takes no detections=.  Without the keyword nothing of this is launched."""
         if isinstance(frames, torch.Tensor):
             frames_mod.check_frames(frames, frame_format)
         n_rows, counts = frames.shape[0] if isinstance(frames, torch.Tensor) else None, None
         track = control_streams.crop_plan(boxes, tracking, n_rows, 'windows' if windows is not None else 'faces' if faces is not None
-                                          else None, batch_size, self.momentum, self.device)
+                                          else None, batch_size, self.momentum, self.device, detections=detections)
         if track is not None and track.tracks is not None:
             wins = None
             if smooth_pose and (identities is None or not smooth_per_identity):
-                raise ValueError("smooth_pose=True with boxes [N,P,4] smooths every face track as its identity's stream: pass identities= "
+                raise ValueError("smooth_pose=True with boxes [N,P,4] / detections= smooths every face track as its identity's stream: pass identities= "
                                  "(one slot per row) and smooth_per_identity=True")
             n_rows = None if n_rows is None else n_rows * track.tracks          # identities: one slot per row
             if identities is not None and n_rows is not None and len(identities) != n_rows:
@@ -1455,29 +1479,43 @@ class InferenceWrapper:
         out = self._render(pose, theta, ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
         return out, (None if plan.matte_fn is None else plan.matte_fn(out).float().contiguous())
 
-    def _track(self, states, boxes, stream_of, sizes, plan, row0):
+    def _track(self, states, boxes, stream_of, sizes, plan, row0, restart=None):
         """boxes= -> windows: ONE launch over the rows `boxes` [m,4] in frame order (ops.crop_track, bit for bit hostglue.crop_track),
         row i on track stream_of[i] of `states` (a control_streams.CropStates; None: the one track) in a frame of sizes = (W, H), or
         one (W, H) per row, with the settings of plan.track -> (crop, paste) windows of the rows as ops.DeviceWindows.
-        tracked_windows = (paste [m,4], row0 = the first row's index in the call)."""
+        tracked_windows = (paste [m,4], row0 = the first row's index in the call).  restart [m] int32 or None: the rows at which
+        their track begins again (ops.track_assign's)."""
         t = plan.track
+        more = {} if restart is None else dict(restart=restart)
         crop, paste, _ = ops.crop_track(boxes, stream_of, sizes, *states.arrays(), momentum=t.momentum, smooth=t.smooth, fixed=t.fixed,
-                                        scale=t.scale, box_format=t.box_format, missing=t.missing, min_side=plan.min_side)
+                                        scale=t.scale, box_format=t.box_format, missing=t.missing, min_side=plan.min_side, **more)
         self.tracked_windows = (paste, row0)
         return ops.DeviceWindows(crop), ops.DeviceWindows(paste)
 
     def _track_chunk(self, plan, n, base, frame_hw, row0):
         """boxes= for the n frames of a chunk (the frames base ... of the call, H x W = frame_hw): their boxes from the feed, tracked
         over all their rows in frame order (_track) with the tracks' state carried in _crop_streams.  Track p of boxes [N,P,4] is
-        tracker stream p; the store is made anew when the number of tracks changes."""
+        tracker stream p; the store is made anew when the number of tracks changes.  detections=: the feed hands out the chunk's
+        detections [n,D,4], which ONE launch in front (ops.track_assign, the tracks carried in _track_states and made anew with
+        the tracker's store) orders into boxes [n,P,4] and the rows' restart flags; tracked_assignment = (track_of, restart)."""
         if n == 0:
             return (ops.DeviceWindows(torch.empty((0, 4), dtype=torch.int32, device=self.device)),) * 2
-        boxes = plan.track.feed.take(n, base)
-        K = plan.track.tracks or 1
+        t = plan.track
+        boxes = t.feed.take(n, base)
+        K = t.tracks or 1
         if self._crop_streams is None or self._crop_streams.K != K:
             self._crop_streams = control_streams.CropStates(K, self.device)
-        stream_of = None if plan.track.tracks is None else torch.arange(K, dtype=torch.int32).repeat(n).to(self.device)
-        return self._track(self._crop_streams, boxes.reshape(-1, 4), stream_of, (frame_hw[1], frame_hw[0]), plan, row0)
+            self._track_states = None
+        restart = None
+        if t.detections is not None:
+            if self._track_states is None:
+                self._track_states = control_streams.TrackStates(1, K, self.device)
+            ts = self._track_states
+            boxes, restart, track_of = ops.track_assign(boxes, None, ts.ref, ts.age, t.min_iou, t.max_missed, t.box_format)
+            self.tracked_assignment = (track_of, restart)
+            restart = restart.reshape(-1)
+        stream_of = None if t.tracks is None else torch.arange(K, dtype=torch.int32).repeat(n).to(self.device)
+        return self._track(self._crop_streams, boxes.reshape(-1, 4), stream_of, (frame_hw[1], frame_hw[0]), plan, row0, restart)
 
     def _animate_clip(self, frames, wins, counts, plan):
         """animate_frames behind its checks.  A row of everything between the crop and the paste is a face: wins = the

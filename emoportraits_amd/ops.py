@@ -1354,7 +1354,7 @@ def head_pose_controls(scale, rotation, translation, stream_of=None, source=None
 
 
 def crop_track(boxes, stream_of=None, size=None, state=None, has_state=None, last=None, momentum=0.01, smooth=False, fixed=False,
-               scale=1.0, box_format="xyxy", missing="skip", min_side=2, K=None):
+               scale=1.0, box_format="xyxy", missing="skip", min_side=2, K=None, restart=None):
     """Face boxes -> crop and paste windows on the device, the crop tracker's state carried along the row order
     (emo_crop_track_f64; bit for bit hostglue.crop_track, which states the arithmetic: crop_image's, notebooks/infer.py:301-352).
     boxes [M,4] float32 or float64 on the device (widened exactly to float64), IN FRAME ORDER; stream_of int32 [M] (or None: one
@@ -1362,7 +1362,9 @@ def crop_track(boxes, stream_of=None, size=None, state=None, has_state=None, las
     int32 [M,2] device tensor; state [K,3] float64, has_state [K] int32 and last [K,4] int32 are the streams' state, updated in
     place (state and has_state are needed by `smooth`, last by missing='hold'; K says the number of streams where none is given).
     -> (crop int32 [M,4], paste int32 [M,4], face_scale float64 [M]): every crop window can be read from its row's frame, a paste
-    window of side 0 says that the row has no face.  One launch, no host synchronisation."""
+    window of side 0 says that the row has no face.  One launch, no host synchronisation.
+    restart: int32 [M] on the boxes' device or None (track_assign's, flattened to the rows): a row with restart != 0 first clears
+    its stream's EMA flag and last window (emo_crop_track_restarts_f64; hostglue.crop_track(restart=))."""
     from . import hostglue
     lib = hip.load()
     if not isinstance(boxes, torch.Tensor) or boxes.dtype not in (torch.float32, torch.float64):
@@ -1401,6 +1403,8 @@ def crop_track(boxes, stream_of=None, size=None, state=None, has_state=None, las
         raise ValueError(f"crop_track: last must be a contiguous int32 [{K},4] tensor on the boxes' device")
     if stream_of is not None:
         _check_index(stream_of, M, dev, "stream_of")
+    if restart is not None:
+        _check_index(restart, M, dev, "restart")
     sizes, Wf, Hf = None, 0, 0
     if isinstance(size, torch.Tensor) and size.device == dev and size.dtype == torch.int32 and size.dim() == 2:
         if tuple(size.shape) != (M, 2) or not size.is_contiguous():
@@ -1417,8 +1421,59 @@ def crop_track(boxes, stream_of=None, size=None, state=None, has_state=None, las
     crop = torch.empty((M, 4), device=dev, dtype=torch.int32)
     paste = torch.empty((M, 4), device=dev, dtype=torch.int32)
     face_scale = torch.empty((M,), device=dev, dtype=torch.float64)
-    hip.check(lib.emo_crop_track_f64(hip.ptr(boxes), hip.ptr(stream_of), hip.ptr(sizes), Wf, Hf, hip.ptr(state if smooth else None),
-                                     hip.ptr(has_state if smooth else None), hip.ptr(last), M, K, m, 1.0 - m, int(bool(smooth)),
-                                     int(bool(fixed)), scale, hostglue.CROP_BOX_FORMATS[box_format], int(hold), int(min_side),
-                                     hip.ptr(crop), hip.ptr(paste), hip.ptr(face_scale), hip.current_stream()), "emo_crop_track_f64")
+    args = (hip.ptr(boxes), hip.ptr(stream_of), hip.ptr(sizes), Wf, Hf, hip.ptr(state if smooth else None),
+            hip.ptr(has_state if smooth else None), hip.ptr(last), M, K, m, 1.0 - m, int(bool(smooth)), int(bool(fixed)), scale,
+            hostglue.CROP_BOX_FORMATS[box_format], int(hold), int(min_side))
+    out = (hip.ptr(crop), hip.ptr(paste), hip.ptr(face_scale), hip.current_stream())
+    if restart is None:
+        hip.check(lib.emo_crop_track_f64(*args, *out), "emo_crop_track_f64")
+    else:
+        hip.check(lib.emo_crop_track_restarts_f64(*args, hip.ptr(restart), *out), "emo_crop_track_restarts_f64")
     return crop, paste, face_scale
+
+
+def track_assign(dets, stream_of=None, ref=None, age=None, min_iou=0.3, max_missed=15, box_format="xyxy"):
+    """Unordered face detections -> ordered track rows on the device, the tracks' state carried along the frame order
+    (emo_track_assign_f64; bit for bit hostglue.track_assign, which states the association: greedy, by IoU, per video stream).
+    dets [F,D,4] float32 or float64 on the device (widened exactly to float64), IN FRAME ORDER, D <= 32, NaN rows = padding;
+    stream_of int32 [F] (or None: one stream, 0); ref [K,P,4] float64 and age [K,P] int32 (-1 = free) are the streams' tracks,
+    updated in place, P <= 16; min_iou in (0, 1]; max_missed >= 0; box_format 'xyxy' | 'relative'.
+    -> (boxes float64 [F,P,4]: the detection of track p in frame f as it came, NaN where it has none; restart int32 [F,P]: 1
+    where the track was born or died in that frame; track_of int32 [F,D]: the track of each detection or -1).  One launch, one
+    wave per stream, no host synchronisation."""
+    from . import hostglue
+    lib = hip.load()
+    if not isinstance(dets, torch.Tensor) or dets.dtype not in (torch.float32, torch.float64):
+        raise ValueError("track_assign: dets must be a float32 or float64 tensor")
+    if dets.dim() != 3 or dets.shape[2] != 4 or dets.shape[0] == 0 or dets.shape[1] == 0:
+        raise ValueError(f"track_assign expects [F,D,4] detections, got {tuple(dets.shape)}")
+    F, D, dev = dets.shape[0], dets.shape[1], dets.device
+    if D > hostglue.TRACK_MAX_DETECTIONS:
+        raise ValueError(f"track_assign: {D} detections per frame, at most {hostglue.TRACK_MAX_DETECTIONS} are served")
+    hip.require_cuda_f32(torch.empty(0, device=dev))                         # (GPU only, like every op)
+    if box_format not in hostglue.CROP_BOX_FORMATS:
+        raise ValueError(f"track_assign: box_format {box_format!r}: 'xyxy' or 'relative'")
+    min_iou = float(min_iou)
+    if not 0.0 < min_iou <= 1.0:
+        raise ValueError(f"track_assign: min_iou {min_iou} is not in (0, 1]")
+    if isinstance(max_missed, bool) or not isinstance(max_missed, int) or max_missed < 0:
+        raise ValueError(f"track_assign: max_missed {max_missed!r} is not an integer >= 0")
+    if not isinstance(ref, torch.Tensor) or not isinstance(age, torch.Tensor) or ref.dim() != 3 or age.dim() != 2:
+        raise ValueError("track_assign: the tracks' state is missing: ref float64 [K,P,4] and age int32 [K,P]")
+    K, P = age.shape
+    if K < 1 or not 1 <= P <= hostglue.TRACK_MAX_TRACKS:
+        raise ValueError(f"track_assign: age is {tuple(age.shape)}: [K,P] with K >= 1 and 1 <= P <= {hostglue.TRACK_MAX_TRACKS}")
+    if ref.dtype != torch.float64 or ref.device != dev or tuple(ref.shape) != (K, P, 4) or not ref.is_contiguous():
+        raise ValueError(f"track_assign: ref must be a contiguous float64 [{K},{P},4] tensor on the detections' device")
+    if age.dtype != torch.int32 or age.device != dev or not age.is_contiguous():
+        raise ValueError(f"track_assign: age must be a contiguous int32 [{K},{P}] tensor on the detections' device")
+    if stream_of is not None:
+        _check_index(stream_of, F, dev, "stream_of")
+    dets = dets.double().contiguous()
+    boxes = torch.empty((F, P, 4), device=dev, dtype=torch.float64)
+    restart = torch.empty((F, P), device=dev, dtype=torch.int32)
+    track_of = torch.empty((F, D), device=dev, dtype=torch.int32)
+    hip.check(lib.emo_track_assign_f64(hip.ptr(dets), hip.ptr(stream_of), F, D, P, K, hip.ptr(ref), hip.ptr(age), min_iou, max_missed,
+                                       hostglue.CROP_BOX_FORMATS[box_format], hip.ptr(boxes), hip.ptr(restart), hip.ptr(track_of),
+                                       hip.current_stream()), "emo_track_assign_f64")
+    return boxes, restart, track_of

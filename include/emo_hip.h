@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 24
+#define EMO_ABI_VERSION 25
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -574,6 +574,51 @@ int emo_head_pose_controls_f32(const float* scale, int scale_cols, const float* 
 int emo_crop_track_f64(const double* boxes, const int32_t* stream_of, const int32_t* sizes, int Wf, int Hf, double* state,
                        int32_t* has_state, int32_t* last, int M, int K, double m, double om, int smooth, int fixed, double scale,
                        int box_format, int hold, int min_side, int32_t* crop, int32_t* paste, double* face_scale, void* stream);
+/* ABI 25.  Unordered face detections in, ordered track rows out: greedy IoU association of the detections of every frame to the
+ * P track slots of its video stream, the frames walked in order, so that a detector's output (a varying number of boxes per frame,
+ * in no stable order) becomes the boxes [F,P,4] that emo_crop_track_restarts_f64 takes, column p the same face from frame to frame.
+ *   dets [F,D,4] DOUBLE, frame order, D <= 32 detections per frame, rows that are not detections padded with NaN; stream_of [F]
+ *   int32 DEVICE memory (or NULL: stream 0): the video stream of frame f; ref [K,P,4] double = (x0, y0, x1, y1) of each track's
+ *   last matched box and age [K,P] int32 are the streams' state, read and written (P <= 16): age[k,p] = -1 means slot p is free,
+ *   >= 0 that the track is live and has gone that many consecutive frames without a match (ref of a free slot means nothing).
+ *   boxes_out [F,P,4] double, restart [F,P] int32, track_of [F,D] int32.
+ * Every operation is a double operation rounded on its own (no contraction).
+ *   box:      of detection d of frame f.  box_format 0: (x0, y0, x1, y1) = dets[f,d].  box_format 1: dets[f,d] = (xmin, ymin, width,
+ *             height): (x0, y0, x1, y1) = (d0, d1, d0 + d2, d1 + d3) -- IoU does not change under a scaling of an axis, so the
+ *             association needs neither the frame size nor emo_crop_track_f64's 0.9 and 1.2, which stay there: boxes_out holds
+ *             the four numbers as they came.
+ *   usable:   all four values of the box are finite and below 2^30 in magnitude, x1 > x0 and y1 > y0.
+ *   IoU:      of a track's ref a and a box b: iw = min(ax1, bx1) - max(ax0, bx0), ih = min(ay1, by1) - max(ay0, by0); 0 if iw <= 0
+ *             or ih <= 0, otherwise inter = iw * ih and IoU = inter / (((ax1 - ax0) * (ay1 - ay0) + (bx1 - bx0) * (by1 - by0)) - inter).
+ * A frame f of stream k = stream_of[f], in this order:
+ *   1. match: repeat: among the live tracks without a match in this frame and the usable detections without a track, take the
+ *             pair of the largest IoU, ties to the smaller p, then to the smaller d; stop when there is no pair or its IoU <
+ *             min_iou (a pair at exactly min_iou matches).  For the pair: ref[k,p] = the box, age[k,p] = 0, boxes_out[f,p] = the
+ *             four values of dets[f,d] bit for bit, restart[f,p] = 0, track_of[f,d] = p.
+ *   2. age:   every live track without a match: age += 1; if age > max_missed it dies: age = -1 and restart[f,p] = 1, otherwise
+ *             restart[f,p] = 0.  Either way boxes_out[f,p] = the quiet NaN 0x7ff8000000000000 four times.
+ *   3. birth: the usable detections without a track, in ascending d, each take the lowest free slot p, those that step 2 freed
+ *             in this frame included: ref[k,p] = the box, age[k,p] = 0, boxes_out[f,p] = dets[f,d] bit for bit, restart[f,p] = 1,
+ *             track_of[f,d] = p.  With no free slot left track_of[f,d] = -1.
+ *   4. rest:  a slot that was free when the frame began and had no birth: boxes_out[f,p] = the quiet NaN row, restart[f,p] = 0.
+ *             A detection that is not usable: track_of[f,d] = -1.
+ * A frame whose stream lies outside [0, K): quiet NaN rows, restart = 0, track_of = -1, and no state is touched.
+ * -- bit for bit hostglue.track_assign.  EMO_ERR_BAD_ARG before any launch: dets, ref, age or an output NULL; F, D, P or K <= 0;
+ * P > 16 or D > 32; min_iou outside (0, 1]; max_missed < 0; box_format not 0 or 1.  One block of one wave per stream: the P x D
+ * IoUs of a frame lie across the lanes, the pair of a round is a wave reduction over the total order (IoU, smaller p, smaller
+ * d), whose result does not depend on the reduction's shape; frames are sequential; no atomics. */
+int emo_track_assign_f64(const double* dets, const int32_t* stream_of, int F, int D, int P, int K, double* ref, int32_t* age,
+                         double min_iou, int max_missed, int box_format, double* boxes_out, int32_t* restart, int32_t* track_of,
+                         void* stream);
+/* ABI 25.  emo_crop_track_f64 with restart [M] int32 DEVICE memory (or NULL: none) -- emo_track_assign_f64's, flattened to the rows:
+ * a row i of a stream k in [0, K) with restart[i] != 0 first clears its stream (has_state[k] = 0 under `smooth`, last[k] = (0, 0,
+ * 0, 0) where last is given) and is then processed as above: a birth starts the EMA at its own box, and a track that has died is
+ * no longer held by `hold`.  emo_crop_track_f64 is this entry point with restart = NULL.  Bit for bit
+ * hostglue.crop_track(restart=); the same refusals. */
+int emo_crop_track_restarts_f64(const double* boxes, const int32_t* stream_of, const int32_t* sizes, int Wf, int Hf, double* state,
+                                int32_t* has_state, int32_t* last, int M, int K, double m, double om, int smooth, int fixed,
+                                double scale, int box_format, int hold, int min_side, const int32_t* restart, int32_t* crop,
+                                int32_t* paste, double* face_scale, void* stream);
 int emo_pack_rgb8(const float* img, uint8_t* out, int N, int H, int W, void* stream);
 int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int W, void* stream);
 

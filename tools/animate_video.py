@@ -15,6 +15,10 @@
          relative (xmin, ymin, width, height)), or [N,P,4] for P tracks per frame; the windows are formed on the device
          (animate_frames' boxes= / tracking=: crop_image's arithmetic with its smoothed-crop tracker); a frame whose box is NaN has
          no face: it is not pasted, or with --hold-missing pasted at the track's last window
+        [--detections dets.json|.npy|.pt --tracks P [--min-iou X] [--max-missed N]]   # in place of --boxes, with its options: the
+         detector's output as it comes, up to 32 boxes per frame in no stable order ([N,D,4], or a JSON list per frame of any length:
+         rows are padded with NaN); they are associated to P track slots on the device (animate_frames' detections=), and track p is
+         rendered as the identity that --identities names for column p
         [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
         [--stage2-experiment <exp2> --stage2-checkpoint <file> [--cloth]       # refine every batch with the stage-2 model
          (--embedders module:factory | --refine-everywhere)]                   # (<project>/logs_s2/<exp2>), inside the same path
@@ -84,6 +88,20 @@ def load_boxes(path):
     return t if t.dtype in (torch.float32, torch.float64) else t.double()
 
 
+def load_detections(path):
+    """detections [N,D,4] from a .pt, .npy or .json file; a JSON file may hold a list of any length per frame ([]: nobody), which
+    is padded to the longest with NaN rows"""
+    if not path.endswith(".json"):
+        return load_boxes(path)
+    frames = json.load(open(path))
+    D = max(1, max((len(f) for f in frames), default=1))
+    out = np.full((len(frames), D, 4), np.nan)
+    for i, f in enumerate(frames):
+        for j, box in enumerate(f):
+            out[i, j] = [np.nan if v is None else v for v in box]
+    return torch.from_numpy(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--project", required=True)
@@ -103,6 +121,11 @@ def main():
     ap.add_argument("--fixed-crop", action="store_true", help="with --smooth-crop: every frame takes the first box (fixed_bounding_box)")
     ap.add_argument("--crop-scale", type=float, default=1.0, help="multiplies the box size (crop_image's scale)")
     ap.add_argument("--hold-missing", action="store_true", help="a frame without a usable box takes the track's last window")
+    ap.add_argument("--detections", default=None, help="unordered detections [N,D,4] (or a JSON list per frame) in place of --boxes: "
+                                                       "associated to --tracks track slots on the device")
+    ap.add_argument("--tracks", type=int, default=None, help="with --detections: P, the track slots per frame (<= 16 and <= --batch)")
+    ap.add_argument("--min-iou", type=float, default=0.3, help="with --detections: a detection continues a track from this IoU on")
+    ap.add_argument("--max-missed", type=int, default=15, help="with --detections: frames a track may go without a detection")
     ap.add_argument("--sources", default=None, help="comma-separated source images enrolled into bank slots 0, 1, ... (--identities)")
     ap.add_argument("--identities", default=None, help="JSON list: the bank slot of every frame, or with --faces of every face")
     ap.add_argument("--out", required=True)
@@ -154,8 +177,12 @@ def main():
         ap.error("--faces and --windows are mutually exclusive")
     if a.boxes and (a.faces or a.windows):
         ap.error("--boxes (windows formed on the device) and --windows / --faces (ready windows) are mutually exclusive")
-    if not a.boxes and (a.box_format != "xyxy" or a.smooth_crop or a.fixed_crop or a.crop_scale != 1.0 or a.hold_missing):
-        ap.error("--box-format / --smooth-crop / --fixed-crop / --crop-scale / --hold-missing belong to --boxes")
+    if a.detections and (a.boxes or a.faces or a.windows):
+        ap.error("--detections (tracks formed on the device) and --boxes / --windows / --faces are mutually exclusive")
+    if bool(a.detections) != (a.tracks is not None) or not a.detections and (a.min_iou != 0.3 or a.max_missed != 15):
+        ap.error("--detections and --tracks go together; --min-iou / --max-missed belong to them")
+    if not (a.boxes or a.detections) and (a.box_format != "xyxy" or a.smooth_crop or a.fixed_crop or a.crop_scale != 1.0 or a.hold_missing):
+        ap.error("--box-format / --smooth-crop / --fixed-crop / --crop-scale / --hold-missing belong to --boxes / --detections")
     if (a.crop_momentum is not None or a.fixed_crop) and not a.smooth_crop:
         ap.error("--crop-momentum / --fixed-crop belong to --smooth-crop")
     if a.crop_momentum is not None and not 0.0 < a.crop_momentum <= 1.0:
@@ -217,6 +244,11 @@ def main():
         boxes = load_boxes(a.boxes)
         tracking = dict(smooth=a.smooth_crop, momentum=a.crop_momentum, fixed=a.fixed_crop, scale=a.crop_scale, box_format=a.box_format,
                         missing="hold" if a.hold_missing else "skip")
+    detections = None
+    if a.detections:
+        detections = load_detections(a.detections)
+        tracking = dict(smooth=a.smooth_crop, momentum=a.crop_momentum, fixed=a.fixed_crop, scale=a.crop_scale, box_format=a.box_format,
+                        missing="hold" if a.hold_missing else "skip", tracks=a.tracks, min_iou=a.min_iou, max_missed=a.max_missed)
     identities = None
     if sources:
         w.enrol_identities([Image.open(f).convert("RGB") for f in sources], slots=list(range(len(sources))), batch_size=a.batch)
@@ -239,7 +271,7 @@ def main():
                                       mix_old=not a.mix_new, target_theta=not a.source_pose, smooth_pose=a.smooth_pose,
                                       smooth_per_identity=identities is not None, paste_back=a.paste_back,
                                       feather=a.feather, refine=refine, refine_masks=refine_masks, expression=expression,
-                                      head_pose=head_pose, boxes=boxes, tracking=tracking, **fmt):
+                                      head_pose=head_pose, boxes=boxes, tracking=tracking, detections=detections, **fmt):
         arr = u8.numpy()
         if nv12:
             sink.write(arr.tobytes())                             # batches come in frame order (one rank)
