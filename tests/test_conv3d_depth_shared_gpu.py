@@ -14,7 +14,9 @@ from emoportraits_amd import hip, ops, pack
 from conv_plans import Expect
 from test_kernels_gpu import DEV, rel_err, run_conv
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 RUN = 3      # forced run length: three live accumulator sets, and a seam wherever D > 3
 
 
@@ -88,8 +90,8 @@ def test_statistics_and_range_check():
     xa[1, 7, 2, 5, 33] = 5000.0
     got, sg = ops.conv_igemm(xa.to(DEV), l2, relu_in=True, want_stats=True)
     assert list(ops.overflow_events(DEV).values()) == ["zs"]
-    want = torch.empty_like(got)
-    stw = torch.empty_like(sg.stats)
+    want = ops.torch.empty_like(got)             # (ops.torch: the guarded allocator of this module's tests)
+    stw = ops.torch.empty_like(sg.stats)
     lib = hip.load()
     rc = lib.emo_conv_igemm_bf16x3(hip.ptr(xa.to(DEV)), hip.ptr(l2.packed(pack.CFG_D, "bf16x3")), hip.ptr(l2.bias), None, None, None,
                                    hip.ptr(want), N, Cin, Cout, D, H, W, 3, 3, 3, 0, 1, 0, 0, pack.CFG_D, 1, None, hip.ptr(stw),

@@ -11,7 +11,9 @@ from emoportraits_amd import ops, pack
 from conv_plans import Expect, split_case
 from test_kernels_gpu import DEV, F16_CASES, F16W8_CASES, rel_err, run_conv
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 
 
 def declared(case, prec, cfg, form="direct"):
@@ -84,8 +86,8 @@ def test_fp16_split_32_row_tiles_statistics_and_range_check():
     got, sg = ops.conv_igemm(xa.to(DEV), l2, relu_in=True, want_stats=True)
     assert list(ops.overflow_events(DEV).values()) == ["bm32"]
     # the exact launch the guard issued, on its own: the bf16 split on the (half-empty) 64-row tile
-    want = torch.empty_like(got)
-    stw = torch.empty_like(sg.stats)
+    want = ops.torch.empty_like(got)             # (ops.torch: the guarded allocator of this module's tests)
+    stw = ops.torch.empty_like(sg.stats)
     from emoportraits_amd import hip
     lib = hip.load()
     rc = lib.emo_conv_igemm_bf16x3(hip.ptr(xa.to(DEV)), hip.ptr(l2.packed(pack.CFG_D, "bf16x3")), hip.ptr(l2.bias), None, None, None,
@@ -445,9 +447,10 @@ def test_conv_f16x2_guarded_recomputation_with_the_residual_updated_in_place(ksp
     ops.clear_overflow_flags(DEV)
 
 
-def test_overflow_flag_pool_is_one_per_device_whatever_the_spelling():
+def test_overflow_flag_pool_is_one_per_device_whatever_the_spelling(guarded_outputs):
     """'cuda' and 'cuda:<current>' name the same pool (advisor, round 4: a HotPath built with device='cuda' cleared and
     reported a pool the launches never wrote)"""
+    guarded_outputs.may_serve_nothing("the flag pool's bookkeeping on the host, a fill and a read of its words: no kernel of ops")
     ops.clear_overflow_flags("cuda")
     slot = pack.overflow_flag_slot("cuda", "spelling")
     idx = torch.cuda.current_device()

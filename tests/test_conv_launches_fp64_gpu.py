@@ -22,7 +22,9 @@ from conv_plans import executed
 from emoportraits_amd import config, nets, ops, pack, random_init, stage2
 from test_nets_gpu import _full_size
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 
 _REAL_IGEMM, _REAL_HEAD = ops.conv_igemm, ops.conv_head

@@ -42,7 +42,9 @@ import conv_reference as R
 from conv_plans import executed
 from emoportraits_amd import config, nets, ops, pack, random_init
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 
 MODES = ("f32", "f16", "bf16x3", "f16x2")
@@ -270,7 +272,7 @@ def form_key(layer, out, ups, res_kind, stats):
 
 def _offset4(t):
     """the same values in a tensor 4 bytes off a 16-byte boundary"""
-    buf = torch.empty(t.numel() + 4, device=t.device, dtype=t.dtype)
+    buf = ops.torch.empty(t.numel() + 4, device=t.device, dtype=t.dtype)    # (ops.torch: the guarded allocator where a test has it)
     v = buf[1:1 + t.numel()].view(t.shape)
     v.copy_(t)
     assert v.data_ptr() % 16 == 4
@@ -327,7 +329,7 @@ def run_geometry(g, seed, dev=DEV, affine=None):
     flags = dict(relu_in=g.relu_in, ups=g.ups, res_ups=g.res == "up2", act="none")
 
     def out_buffer():
-        o = torch.empty(oshape, device=dev, dtype=torch.float32)
+        o = ops.torch.empty(oshape, device=dev, dtype=torch.float32)
         return _offset4(o) if g.offset == "out" else o
 
     def launch(lay, want_stats):
@@ -408,8 +410,12 @@ def low_fill_thresholds(mp):
     mp.setenv("EMO_F16X2_P1_MIN_ITEMS", "1")
 
 
+_SLICES_RUN = set()         # the (mode, taps) slices that have run: a later test reads the cached rows and launches nothing
+
+
 @functools.lru_cache(maxsize=None)
 def _gpu_slice(mode, taps):
+    _SLICES_RUN.add((mode, taps))
     mp = pytest.MonkeyPatch()
     try:
         low_fill_thresholds(mp)
@@ -426,9 +432,12 @@ def _gpu_slice(mode, taps):
 
 @pytest.mark.parametrize("taps", TAPS + ("extra",))
 @pytest.mark.parametrize("mode", MODES)
-def test_planner_and_launcher_agree_and_launches_meet_fp64(mode, taps):
+def test_planner_and_launcher_agree_and_launches_meet_fp64(mode, taps, guarded_outputs):
     """properties 1 - 6 of the module docstring on one (mode, taps) slice of the product, or on the mode's entries of EXTRA"""
+    cached = (mode, taps) in _SLICES_RUN
     rows, bad = _gpu_slice(mode, taps)
+    if cached or not rows:
+        guarded_outputs.may_serve_nothing("the slice ran in an earlier test of the session (its rows are cached), or EXTRA has no entry for the mode")
     print(summary(f"{mode} {taps}", rows))
     assert not bad, f"{len(bad)} violations:\n" + "\n".join(bad[:40])
     assert all(r["status"] in ("ran", "refused") for _, r in rows)
@@ -436,9 +445,11 @@ def test_planner_and_launcher_agree_and_launches_meet_fp64(mode, taps):
         assert len(rows) == len(WIDTHS) * len(HEIGHTS) * len(UPS) + (taps == "3x3")
 
 
-def test_every_extra_geometry_runs_a_form_of_its_own():
+def test_every_extra_geometry_runs_a_form_of_its_own(guarded_outputs):
     """EXTRA is there for launch forms the product does not run: an entry whose form the product runs, or an earlier entry, is not
     needed and goes"""
+    if all((mode, taps) in _SLICES_RUN for mode in MODES for taps in TAPS + ("extra",)):
+        guarded_outputs.may_serve_nothing("every slice ran in an earlier test of the session: only their cached rows are read")
     product = {r["key"] for mode in MODES for taps in TAPS for _, r in _gpu_slice(mode, taps)[0] if r["status"] == "ran"}
     seen, spare = set(), []
     for mode in MODES:

@@ -14,7 +14,9 @@ import torch.nn.functional as F
 from emoportraits_amd import ops, pack
 from test_kernels_gpu import DEV
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 
 
 def _operands(N, Cin, Cout, H, W, seed):

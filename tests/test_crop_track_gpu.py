@@ -17,7 +17,9 @@ sys.path.insert(0, HERE)
 import crop_track_cases as C  # noqa: E402
 from test_head_pose_controls_gpu import make_wrapper, project, tiny  # noqa: E402,F401
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 TRACK = dict(smooth=True, momentum=0.5)
 

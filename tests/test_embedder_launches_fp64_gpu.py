@@ -22,6 +22,7 @@ import torch
 import ops_reference as R
 from emoportraits_amd import embedders as E
 from emoportraits_amd import encoder, hip, ops, stage2
+from guarded_outputs import guarded_outputs  # noqa: F401  (every output ops allocates: poisoned, between guards; the GPU tests ask for it)
 from test_op_launches_fp64_gpu import CONV_CHECKER, EXEMPT, OpLaunchChecker, ops_called, register
 
 DEV = "cuda:0"
@@ -168,6 +169,7 @@ def _thetas(B, seed):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_outputs")
 def test_idt_embed_every_launch_vs_fp64(monkeypatch):
     """the ResNet-50 of an enrolment: released flags (GroupNorm + weight standardisation), 512 px crops, so the resize launches"""
     cfg = E.embedder_config()
@@ -184,6 +186,7 @@ def test_idt_embed_every_launch_vs_fp64(monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_outputs")
 def test_head_pose_regressor_every_launch_vs_fp64(monkeypatch):
     net = E.HeadPoseRegressor(E.random_state_dict(E.head_pose_schema(), 13), torch.device(DEV))
     x = _crops(3, 14)
@@ -196,6 +199,7 @@ def test_head_pose_regressor_every_launch_vs_fp64(monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_outputs")
 @pytest.mark.parametrize("released", [True, False])
 def test_expression_embed_every_launch_vs_fp64(released, monkeypatch):
     """released: GroupNorm + weight standardisation, 128 expression channels; default: eval BatchNorm, 512 channels"""

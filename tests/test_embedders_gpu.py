@@ -25,7 +25,9 @@ from emoportraits_amd import embedders as E  # noqa: E402
 from emoportraits_amd import hip, ops, pack  # noqa: E402
 import ops_reference as R  # noqa: E402
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 
 
@@ -223,7 +225,8 @@ def test_expression_embed_matches_reference_golden(emb):
     assert rel_err(chain, blob["pose_embed_chain"]) <= 1e-3
 
 
-def test_embedders_reject_mismatched_checkpoints(emb):
+def test_embedders_reject_mismatched_checkpoints(emb, guarded_outputs):
+    guarded_outputs.may_serve_nothing("only the constructors' checkpoint errors are provoked: nothing is launched")
     blob, sds, _ = emb
     bad = dict(sds["expression"])
     bad.pop("expression_embedder_nw.net_face.net.layer3.1.conv2.bias")

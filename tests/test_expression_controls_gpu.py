@@ -14,7 +14,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 
 
@@ -56,7 +58,7 @@ def test_ops_expression_controls_is_the_restatement_bit_for_bit(E):
             sl = lambda a, on=True: a[lo:hi] if on else None
             want = hostglue.expression_controls(values[lo:hi], so[lo:hi], neutral if use_neutral else None, sl(gain, use_gain),
                                                 sl(offset, use_offset), *host, relative, momentum)
-            out = torch.full((hi - lo, E), float("nan"), device=DEV)
+            out = ops.torch.empty((hi - lo, E), device=DEV, dtype=torch.float32).fill_(float("nan"))    # (ops.torch: between guards)
             got = ops.expression_controls(dev(values[lo:hi]), dev(so[lo:hi]), dev(neutral) if use_neutral else None,
                                           dev(sl(gain, use_gain)), dev(sl(offset, use_offset)), *state, relative, momentum, out=out)
             assert got is out and _same(got.cpu().numpy()[inside[lo:hi]], want[inside[lo:hi]])

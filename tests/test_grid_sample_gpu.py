@@ -16,7 +16,9 @@ import restate as O  # noqa: E402
 
 from emoportraits_amd import ops  # noqa: E402
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 PADS = ["zeros", "border", "reflection"]
 DEV = "cuda:0"
 

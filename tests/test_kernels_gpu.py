@@ -19,7 +19,9 @@ import restate as O  # noqa: E402
 from emoportraits_amd import ops, pack  # noqa: E402
 from conv_plans import Expect, check as check_plan, split_case  # noqa: E402
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import assert_written, guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 
 
@@ -236,13 +238,14 @@ F16W8_CASES = [
 
 @pytest.mark.parametrize("rest", [True, False])
 @pytest.mark.parametrize("case", F16W8_CASES)
-def test_conv_fp16_operands_on_the_eight_wave_two_tile_kernel(case, rest, monkeypatch):
+def test_conv_fp16_operands_on_the_eight_wave_two_tile_kernel(case, rest, monkeypatch, guarded_outputs):
     """precision='f16' in the decoders' launch form runs emo_conv_igemm_f16w8 (round 6: conv_igemm_f16x2_w8.h with the leading
     product alone -- plain fp16 operands, two waves per SIMD): the fp16-operand bound against torch CPU fp32, deterministic, and
     within accumulation-order noise of the older fp16-operand kernel (EMO_F16_W8=0), which rounds the same operands.  An odd
     channel-tile count runs its last tile on that older kernel (rest: emo_conv_igemm_f16w8_rest, ABI 10 -- the planner's choice)
     or in a half-empty pair of the eight-wave kernel (EMO_F16_W8_REST=0)"""
     if not rest and (case["Cout"] // 64) % 2 == 0:
+        guarded_outputs.may_serve_nothing("skipped before the first launch")
         pytest.skip("even tile count: one launch form")
     monkeypatch.setenv("EMO_CONV_CT2_MIN_ITEMS", "1")
     monkeypatch.setattr(pack, "F16_W8_ODD", 1)           # (every odd tile count: the planner takes them from five tiles on only)
@@ -304,7 +307,7 @@ def test_conv_on_tensors_that_are_not_16_byte_aligned():
     N, C, S = 1, 32, 64
     w = torch.randn(64, C, 3, 3, generator=g) / math.sqrt(C * 9)
     xa = torch.randn(N, C, S, S, generator=g).to(DEV)
-    xm = torch.empty(xa.numel() + 1, device=DEV)[1:].view_as(xa)
+    xm = ops.torch.empty(xa.numel() + 1, device=DEV)[1:].view_as(xa)     # (ops.torch: the guarded allocator of this module's tests)
     xm.copy_(xa)
     assert xm.data_ptr() % 16 == 4
     ref = F.conv2d(xa.cpu(), w, padding=1)
@@ -313,13 +316,15 @@ def test_conv_on_tensors_that_are_not_16_byte_aligned():
     assert rel_err(got_h, ref) < 2e-5                       # fp32 accuracy: the fp32 kernel ran
     assert rel_err(ops.conv_igemm(xa, lh), ref) > 1e-5      # (the aligned tensor does take the fp16-operand kernel)
     lf = pack.PackedConv("f", w, None, DEV)
-    om = torch.empty(ref.numel() + 1, device=DEV)[1:].view_as(ref)
-    rm = torch.empty(ref.numel() + 1, device=DEV)[1:].view_as(ref)
+    ob = ops.torch.empty(ref.numel() + 2, device=DEV)            # one poisoned element before the output and one behind it
+    om = ob[1:-1].view_as(ref)
+    rm = ops.torch.empty(ref.numel() + 1, device=DEV)[1:].view_as(ref)
     r = torch.randn(ref.shape, generator=g)
     rm.copy_(r.to(DEV))
     got = ops.conv_igemm(xa, lf, res=rm, out=om)
     assert got.data_ptr() == om.data_ptr() and om.data_ptr() % 16 == 4
     assert rel_err(got, ref + r) < 2e-5
+    assert bool(torch.isnan(ob[[0, -1]]).all()), "the scalar-store epilogue wrote next to its output"
 
 
 def test_conv_fp16_operands_saturate():
@@ -390,7 +395,7 @@ def test_conv_residual_may_alias_output():
     r = torch.randn(1, 16, 64, 64, generator=g)
     ref = F.conv2d(x, w, padding=1) + r
     layer = pack.PackedConv("alias", w, None, DEV)
-    buf = r.to(DEV).clone()
+    buf = ops.torch.empty_like(r, device=DEV).copy_(r)           # (ops.torch: written in place between the guards of this module's tests)
     ops.conv_igemm(x.to(DEV), layer, res=buf, out=buf)
     assert rel_err(buf, ref) < 2e-5
 
@@ -440,6 +445,47 @@ def test_groupnorm_large_mean_is_stable():
     got = x * s.cpu().view(1, 32, 1, 1) + h.cpu().view(1, 32, 1, 1)
     ref = F.group_norm(x.double(), 32).float()
     assert (got - ref).abs().max().item() < 0.05   # fp32 x*scale+shift cancellation bound at |x|=1e3, rstd=1e2
+
+
+def _gn_bound(scale, shift, x, gamma, beta, what):
+    """ops_reference.check_groupnorm_affine: the fp64 statistics of x itself, under the bound derived there"""
+    import ops_reference
+    assert_written(scale, what + " scale")
+    assert_written(shift, what + " shift")
+    fig = ops_reference.check_groupnorm_affine(scale, shift, x, gamma, beta)
+    print(f"PARITY groupnorm_affine {what}: {fig['worst']:.3f} {fig['unit']}")
+    assert not fig["failures"], fig["failures"]
+
+
+def test_groupnorm_scalar_path_with_two_slices():
+    """gn_partial_kernel's scalar loop (a run length that is no multiple of 4) over more than one slice: L = 131 * 127 = 16637
+    elements per (sample, group) make split = 2 with the slice boundary rounded up to 8320, so the second slice is the shorter
+    one and ends at L, not at a multiple of 4"""
+    g = torch.Generator().manual_seed(131)
+    x = (torch.randn(1, 32, 131, 127, generator=g) * 2 + 0.5).to(DEV)
+    gamma, beta = torch.randn(32, generator=g).to(DEV), torch.randn(32, generator=g).to(DEV)
+    L = x[0, 0].numel()
+    assert L % 4 != 0 and (L + 16383) // 16384 == 2 and ((L + 1) // 2 + 3) // 4 * 4 == 8320
+    scale, shift = ops.groupnorm_affine(x, gamma, beta)
+    _gn_bound(scale, shift, x, gamma, beta, "scalar path, two slices")
+
+
+def test_groupnorm_scalar_path_through_an_unaligned_base():
+    """the [2, 64, 8, 8] case (L = 128, a multiple of 4) read from a buffer one float off 16-byte alignment: every run's base is
+    unaligned, so gn_partial_kernel takes its scalar loop where the aligned call takes the float4 loop.  Both accumulate fp64
+    sums of the same values in another order: the scale and shift agree bit for bit, and each meets the fp64 bound"""
+    g = torch.Generator().manual_seed(sum((2, 64, 8, 8)))
+    x = (torch.randn(2, 64, 8, 8, generator=g) * 3 + 1.5).to(DEV)
+    gamma, beta = torch.randn(64, generator=g).to(DEV), torch.randn(64, generator=g).to(DEV)
+    buf = ops.torch.empty(x.numel() + 4, device=DEV)
+    xm = buf[1:1 + x.numel()].view_as(x)
+    xm.copy_(x)
+    assert x.data_ptr() % 16 == 0 and xm.data_ptr() % 16 == 4 and x[0, 0].numel() * 2 % 4 == 0
+    aligned = ops.groupnorm_affine(x, gamma, beta)
+    off = ops.groupnorm_affine(xm, gamma, beta)
+    _gn_bound(*aligned, x, gamma, beta, "float4 path, aligned base")
+    _gn_bound(*off, x, gamma, beta, "scalar path, unaligned base")
+    assert torch.equal(off[0], aligned[0]) and torch.equal(off[1], aligned[1])
 
 
 # ---- GroupNorm statistics reduced in the conv epilogue (conv_igemm.h gn_stats -> emo_groupnorm_affine_from_tiles_f32) ----
@@ -581,7 +627,7 @@ def test_conv_head_launch_forms_the_stream_does_not_take_run_the_mfma_kernel():
     w, b = torch.randn(3, 16, 1, 1, generator=g) / 4, torch.randn(3, generator=g)
     layer = pack.PackedConv("head", w, b, DEV)
     x = torch.randn(1, 16, 8, 32, generator=g)
-    buf = torch.empty(x.numel() + 4, device=DEV)
+    buf = ops.torch.empty(x.numel() + 4, device=DEV)
     xd = buf[1:1 + x.numel()].view_as(x)                                        # 4 bytes off a 16-byte boundary
     xd.copy_(x)
     got = ops.conv_head(xd, layer, act="sigmoid")
@@ -614,11 +660,12 @@ def test_upsample_trilinear_even_widths_take_the_block_kernel(shape, factors):
     xd = x.to(DEV)
     got = ops.upsample_trilinear(xd, factors)
     assert got.shape == ref.shape and got.data_ptr() % 16 == 0
-    buf = torch.empty(ref.numel() + 4, device=DEV)
+    buf = ops.torch.empty(ref.numel() + 4, device=DEV)          # (the guarded allocator: NaN until written)
     plain = buf[1:1 + ref.numel()]                              # 4 bytes off: the generic kernel
     N, C, D, H, W = shape
     hip.check(lib.emo_upsample_trilinear_f32(hip.ptr(xd), hip.ptr(plain), N * C, D, H, W, *factors, hip.current_stream()), "upsample")
     assert torch.equal(got.flatten(), plain)
+    assert bool(torch.isnan(buf[:1]).all()) and bool(torch.isnan(buf[1 + ref.numel():]).all()), "the generic kernel wrote next to its output"
     assert rel_err(got, ref) < 1e-6
 
 

@@ -18,7 +18,9 @@ sys.path.insert(0, HERE)
 import nv12_reference as R  # noqa: E402
 import yuv420_reference as Y  # noqa: E402
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 FILL = Y.FILL
 F64, F32 = torch.float64, torch.float32
@@ -492,7 +494,8 @@ def test_enrol_identities_from_nv12_frames_is_enrolment_from_their_crops(project
         w.enrol_identities(nv12[:, :, :-1], source_masks=masks, windows=wins, frame_format="nv12", **custom)
 
 
-def test_every_value_error_is_raised_before_the_first_launch(wrapper, tiny):
+def test_every_value_error_is_raised_before_the_first_launch(wrapper, tiny, guarded_outputs):
+    guarded_outputs.may_serve_nothing("only argument errors are provoked, each before anything is allocated or launched")
     w = wrapper
     S = tiny["cfg"]["image_size"]
     nv12, wins = _clip(S, 4, S + 10, S + 30, seed=3)

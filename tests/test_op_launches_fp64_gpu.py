@@ -27,6 +27,7 @@ import torch
 
 import ops_reference as R
 from emoportraits_amd import embedders, encoder, nets, ops, stage2
+from guarded_outputs import guarded_outputs  # noqa: F401  (every output ops allocates: poisoned, between guards; the GPU tests ask for it)
 
 DEV = "cuda:0"
 GRID_CAP = 8192 * 256             # work items one trip of a capped grid covers (grid_for: 8192 blocks of 256 threads)
@@ -247,6 +248,7 @@ def _driver_pass(B, seed, bank=None):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_outputs")
 def test_driver_pass_every_op_launch_vs_fp64(monkeypatch):
     """B = 5, the smallest batch at which a capped grid (grid_for: 8192 blocks) actually loops: the depth pooling (2, 1, 1) of the
     warp generator's last block writes B x 32 x 16 x 64 x 64 outputs, four per thread of avgpool_x4_kernel -- B x 524288 quads
@@ -270,6 +272,7 @@ def test_driver_pass_every_op_launch_vs_fp64(monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_outputs")
 def test_driver_pass_with_identity_bank_every_op_launch_vs_fp64(monkeypatch):
     """K = 2 identities, B = 3 frames, identity = [1, 0, 1]: the indexed add and the indexed uv sampler read the bank"""
     hp, fn = _driver_pass(3, seed=257, bank=[1, 0, 1])
@@ -282,6 +285,7 @@ def test_driver_pass_with_identity_bank_every_op_launch_vs_fp64(monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("guarded_outputs")
 def test_source_pass_every_op_launch_vs_fp64(monkeypatch):
     from test_nets_gpu import _full_size
     cfg, sd, x = _full_size(256, 1, seed=21)

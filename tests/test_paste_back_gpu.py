@@ -16,7 +16,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 import paste_back_reference as R  # noqa: E402
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 
 
@@ -31,7 +33,7 @@ def _sq(wins):
 
 def _paste(frames, img, wins, feather=0.0, matte=None):
     from emoportraits_amd import ops
-    work = frames.to(DEV)
+    work = ops.torch.empty_like(frames, device=DEV).copy_(frames)       # (ops.torch: pasted into between the guards of this module's tests)
     out = ops.paste_windows(work, img.to(DEV), _sq(wins), feather, None if matte is None else matte.to(DEV))
     assert out is work
     return out.cpu()

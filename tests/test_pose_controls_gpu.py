@@ -14,7 +14,9 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "emul"))
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 
 
@@ -292,12 +294,13 @@ print("WORKER_OK", w.rank, flush=True)
 """
 
 
-def test_two_ranks_bank_smooth_mix_equal_one_rank(tmp_path, golden_dir):
+def test_two_ranks_bank_smooth_mix_equal_one_rank(tmp_path, golden_dir, guarded_outputs):
     """animate_frames(identities=..., smooth_pose=True, mix=True) on 2 ranks (gloo, one GPU) = 1 rank: the same frames and the
     same slot states (every rank scans the whole gathered chunk); two chunks, so the streams carry across a chunk boundary"""
     import subprocess
     from emoportraits_amd import parallel
     from test_two_ranks_gpu import _free_port, _project as make_project
+    guarded_outputs.may_serve_nothing("the ranks are child processes: this process launches nothing")
     project = make_project(tmp_path, golden_dir)
 
     def spawn(world):

@@ -16,7 +16,9 @@ import restate as O  # noqa: E402
 
 from emoportraits_amd import ops  # noqa: E402
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 
 
@@ -64,7 +66,7 @@ def test_tile_kernel_equals_direct_gather_kernels_at_batch_16():
     out_ref = ops.grid_sample3d(mid_ref, theta=theta.to(DEV))
     vp4 = ops.volume_to_p4(v)
     for chunk, variant in ((16, 0), (4, ops.tile_variant((16, 8, 4), 24))):
-        out = torch.empty_like(out_ref)
+        out = ops.torch.empty_like(out_ref)      # (ops.torch: the guarded allocator of this module's tests)
         for a in range(0, N, chunk):
             mid = ops.grid_sample3d(vp4, delta=delta[a:a + chunk].to(DEV), in_layout="p4", out_layout="p4", variant=variant)
             assert torch.equal(ops.volume_from_p4(mid), mid_ref[a:a + chunk])

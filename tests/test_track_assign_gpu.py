@@ -20,7 +20,9 @@ import track_assign_cases as C  # noqa: E402
 from test_crop_track_gpu import _clip, _run, _walk  # noqa: E402
 from test_head_pose_controls_gpu import make_wrapper, project, tiny  # noqa: E402,F401
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 TRACK = dict(smooth=True, momentum=0.5)
 

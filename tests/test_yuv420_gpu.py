@@ -16,7 +16,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 import yuv420_reference as Y  # noqa: E402
 
-pytestmark = pytest.mark.gpu
+from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 DEV = "cuda:0"
 
 
@@ -250,7 +252,8 @@ def test_enrol_identities_from_frames_is_enrolment_from_their_crops(project, tin
         w.enrol_identities(frames[:, :, :-1], source_masks=masks, windows=wins, frame_format=fmt, **custom)
 
 
-def test_every_value_error_is_raised_before_the_first_launch(wrapper, tiny):
+def test_every_value_error_is_raised_before_the_first_launch(wrapper, tiny, guarded_outputs):
+    guarded_outputs.may_serve_nothing("only argument errors are provoked, each before anything is allocated or launched")
     w = wrapper
     S = tiny["cfg"]["image_size"]
     for fmt in Y.NEW:
