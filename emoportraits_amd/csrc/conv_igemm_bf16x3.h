@@ -535,10 +535,7 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   opx8* const lds8 = reinterpret_cast<opx8*>(smem);
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l32 = lane & 31;
+  EMO_SPLIT_THREAD_IDS()
   const int wp = wave;
   const int m0 = 0, p0 = wp * TP * 32;
 
@@ -573,28 +570,10 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
   const int nstages_all = a.n_cchunks * a.KD;
   const int nptiles = a.tiles_x * a.tiles_y * a.tiles_z;
 
-  // ---- staging map: thread t belongs to channel group t / QPG; within the group, lane u < PR * NQ owns interior quad u (4
-  //      consecutive pixels of one patch row), lane PR * NQ + 2 * row + side owns one halo pixel.  A halo lane issues the SAME
-  //      16-byte loads as everybody else -- the aligned quad that contains its pixel (left: x0 - 4 .. x0 - 1, element 3;
-  //      right: x0 + TWS .. + 3, element 0) -- and runs the same conversion; the three pixels it does not own go to dump slots
-  //      at the tail of their sub-row.  No wave does extra work: with a dedicated halo wave (8 dword loads + an 8-value
+  // ---- staging map (conv_split_common.h).  No wave does extra work: with a dedicated halo wave (8 dword loads + an 8-value
   //      conversion per stage on wave 3 only) the other three waves sat 700-850 cycles per stage in the K loop's barriers
   //      (tools/conv_phase_timing.py on an EMO_S_TIMING=2 build, profiles/r4_conv_phase_waves.jsonl) ----
-  const int q_u = tid % QPG;
-  const int q_g = __builtin_amdgcn_readfirstlane(tid / QPG);
-  const bool is_quad = q_u < PR * NQ;
-  const int hq = q_u - PR * NQ;
-  const bool is_halo = !is_quad && hq < NHQ;
-  const int h_side = hq & 1;
-  const int q_r = is_quad ? q_u / NQ : (is_halo ? hq >> 1 : 0);
-  const int q_c = is_quad ? q_u - q_r * NQ : 0;
-  int q_slb[4];                                           // byte offsets of the lane's four staging slots inside a patch buffer
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int dump = q_g * CHS + i * SUB + PR * NQ1 + (q_u & 3);
-    const int own = is_quad ? q_g * CHS + i * SUB + q_r * NQ1 + q_c : q_g * CHS + h_side * SUB + q_r * NQ1 + NQ;
-    q_slb[i] = ((is_quad || (is_halo && i == (h_side ? 0 : 3))) ? own : dump) * 16;
-  }
+  EMO_SPLIT_STAGING_MAP(tid / QPG, 0)
 
   constexpr int TPH = TP;
   floatx16 acc_lo[TM][TPH], acc_hi[TM][TPH];
@@ -608,11 +587,7 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
   //      spill moves per stage pair against 47: tools/session/r4_call13.sh) and computed wrong tiles in the bf16 split -- the
   //      former went away with the accumulators read where they are used and a branch-free loop, the latter was, in all
   //      likelihood, the scalar-register hazard described at EMO_SGPR_HAZARD_NOP (conv_igemm.h) ----
-  const int q8 = a.n_work >> 3, r8 = a.n_work & 7;
-  const int xcd = blockIdx.x & 7;
-  const int n_mine = q8 + (xcd < r8 ? 1 : 0);
-  const int l_base = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int l_stride = (gridDim.x + 7) >> 3;
+  EMO_SPLIT_ITEM_WALK()
   // the item being computed (it_*) and the tile of its patch loads (lq_*)
   int it_L = 0, it_cotile = 0, it_ks = 0, it_n = 0, it_ptile = 0, it_x0 = 0, it_y0 = 0, it_z0 = 0, it_st_begin = 0, it_st_end = 0;
   unsigned lq_off = 0;
@@ -621,86 +596,40 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
 // (every result through readfirstlane: the uniform divisions run on the vector ALU, and once these variables are carried from
 // one iteration of the item loop to the next the compiler would otherwise keep the whole web in vector registers -- which the
 // "s" operands of the pinned loads cannot take)
+// the shared decode with the K split between the channel tile and the sample
 #define EMO_S_DECODE(P_, L_)                                                                          \
   {                                                                                                   \
     P_##L = (L_);                                                                                     \
-    int cot_ = P_##L % a.n_cotiles;                                                                   \
-    int rest_ = P_##L / a.n_cotiles;                                                                  \
-    int ks_ = 0;                                                                                      \
-    if (a.ksplit > 1) {                                                                               \
-      ks_ = rest_ % a.ksplit;                                                                         \
-      rest_ /= a.ksplit;                                                                              \
-    }                                                                                                 \
-    const int n_ = rest_ / nptiles;                                                                   \
-    int bx_ = rest_ - n_ * nptiles;                                                                   \
-    P_##ptile = __builtin_amdgcn_readfirstlane(bx_);                                                  \
-    const int tx_ = bx_ % a.tiles_x; bx_ /= a.tiles_x;                                                \
-    const int ty_ = bx_ % a.tiles_y; bx_ /= a.tiles_y;                                                \
-    P_##cotile = __builtin_amdgcn_readfirstlane(cot_ + a.cot0);                                       \
-    P_##ks = __builtin_amdgcn_readfirstlane(ks_);                                                     \
-    P_##n = __builtin_amdgcn_readfirstlane(n_);                                                       \
-    P_##x0 = __builtin_amdgcn_readfirstlane(tx_ * TW);                                                \
-    P_##y0 = __builtin_amdgcn_readfirstlane(ty_ * TR);                                                \
-    P_##z0 = __builtin_amdgcn_readfirstlane(bx_);                                                     \
+    EMO_SPLIT_DECODE(P_, P_##L, cot_ + a.cot0,                                                        \
+                     int ks_ = 0; if (a.ksplit > 1) { ks_ = rest_ % a.ksplit; rest_ /= a.ksplit; }    \
+                     P_##ks = __builtin_amdgcn_readfirstlane(ks_);)                                   \
     P_##st_begin = __builtin_amdgcn_readfirstlane(P_##ks * a.stages_per_split);                       \
     P_##st_end = __builtin_amdgcn_readfirstlane(min(nstages_all, P_##st_begin + a.stages_per_split)); \
   }
 // the packed kernel rows of an item's channel tile
 #define EMO_S_WSRC(P_) (reinterpret_cast<const char*>(a.wpk) + ((long)P_##cotile * nstages_all) * (3 * Cfg::WROW_BYTES))
 #define it_wsrc EMO_S_WSRC(it_)
-// points the patch-load cursor at the tile of item P_: the lane's 16-byte load (its quad, or the aligned quad that contains its
-// halo pixel) and whether it lies inside the image.  Per-lane values are derived where the cursor moves, not carried per item
-#define EMO_S_CURSOR_OF(P_, ok_, off_)                                                                \
-  {                                                                                                   \
-    const int x0s_ = UPS ? P_##x0 >> 1 : P_##x0, y0s_ = UPS ? P_##y0 >> 1 : P_##y0;   /* tile origin in source pixels */ \
-    const int q_y_ = y0s_ - 1 + q_r;                                                                  \
-    const int q_x_ = is_quad ? x0s_ + 4 * q_c : (h_side ? x0s_ + TWS : x0s_ - 4);   /* first pixel of the lane's 16-byte load */ \
-    ok_ = (is_quad || is_halo) && (unsigned)q_y_ < (unsigned)a.H && q_x_ >= 0 && q_x_ < a.W;          \
-    off_ = ok_ ? (unsigned)(q_y_ * a.W + q_x_) * 4u : 0u;                                             \
-  }
-#define EMO_S_CURSOR_TO(P_) { EMO_S_CURSOR_OF(P_, lq_ok, lq_off) lq_z0 = P_##z0; }
+// points the patch-load cursor at the tile of item P_.  Per-lane values are derived where the cursor moves, not carried per item
+#define EMO_S_CURSOR_TO(P_) { EMO_SPLIT_CURSOR_OF(P_, lq_ok, lq_off) lq_z0 = P_##z0; }
 
   // LDS byte offsets of the lane's operands: weight fragment (+ row buffer / plane / tap column immediates) and, for every tap,
-  // the patch slot of the lane's output pixel (+ half * CHS: the lane's 8-channel group; + buffer / plane immediates)
-  // Kernel row r adds r patch rows = r * NQ1 slots (an immediate); with the fused upsample the source row of kernel row r is
-  // (row + r + 1) >> 1: kernel row 2 is kernel row 0 plus one patch row, kernel row 1 depends on the parity of the pixel row
-  // and keeps its own registers.
+  // the patch slot of the lane's output pixel (conv_split_common.h; + buffer / plane immediates)
   const int a_off = (half * BM + m0 + l32) * 16;
-  constexpr int NBR = UPS ? 2 : 1;
-  int b_off[TP][NBR][3];
-#pragma unroll
-  for (int j = 0; j < TP; ++j) {
-    const int p = p0 + j * 32 + l32;
-    const int col = p % TW, row = p / TW;
-#pragma unroll
-    for (int r = 0; r < NBR; ++r)
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        const int pr = UPS ? ((row + r - 1 + 2) >> 1) - 1 + 1 : row + r;
-        const int pc = UPS ? ((col + s - 1 + 2) >> 1) - 1 : col + s - 1;
-        const int slot = pc < 0 ? pr * NQ1 + NQ : (pc >= TWS ? SUB + pr * NQ1 + NQ : (pc & 3) * SUB + pr * NQ1 + (pc >> 2));
-        b_off[j][r][s] = (half * CHS + slot) * 16;
-      }
-  }
-#define EMO_S_B_OFF(j_, r_, s_) (UPS ? ((r_) == 2 ? b_off[j_][0][s_] + NQ1 * 16 : b_off[j_][(r_) < NBR ? (r_) : 0][s_]) \
-                                     : b_off[j_][0][s_] + (r_) * NQ1 * 16)
+  EMO_SPLIT_DECLARE_B_OFF()
 
-  const char* const lds_c = reinterpret_cast<const char*>(smem);
-  char* const lds_w = reinterpret_cast<char*>(smem);
+  EMO_SPLIT_LDS_VIEWS()
   opx8 fa_[2][NPL][TM], fb_[2][NPL][TP];     // [register set: this step / the next][plane][tile]
 #define EMO_S_LOAD_FRAGS_PLANE(set_, pl_, wbase_, pbase_, r_, s_)                                      \
   {                                                                                                   \
     _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                    \
       fa_[set_][pl_][i] = *reinterpret_cast<const opx8*>(lds_c + a_off + ((wbase_) + (pl_) * WPLANE + (s_) * 2 * BM + i * 32) * 16); \
     _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                    \
-      fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + EMO_S_B_OFF(j, r_, s_) + ((pbase_) + (pl_) * PPL) * 16); \
+      fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + EMO_SPLIT_B_OFF(j, r_, s_) + ((pbase_) + (pl_) * PPL) * 16); \
   }
 #define EMO_S_LOAD_FRAGS(set_, wbase_, pbase_, r_, s_)                                                \
   { _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl) EMO_S_LOAD_FRAGS_PLANE(set_, pl, wbase_, pbase_, r_, s_) }
 
-  float* const sct = smem + Cfg::OFF_SCT * 4;
-  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(smem);
-  const unsigned lane16 = (unsigned)lane * 16u;
+  EMO_SPLIT_LDS_TABLES_ADDR()
 
   // raw patch registers, double-buffered by stage parity: the loads of stage k + 2 are issued (into buffer k & 1) while the
   // conversion of stage k + 1 still reads buffer (k + 1) & 1 -- that lets the conversion spread over eight steps of a stage,
@@ -712,9 +641,7 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
   floatx4 q_sc, q_sh;                       // scale / shift of the four channels being converted (read at the top of the step)
   opx8 cv_h, cv_m, cv_l;                    // the pixel under conversion: 8 channels per plane, filled in two halves
   emo_intx4 xrs = emo_raw_buffer(a.x);      // (re-based on the item's sample by the prologue)
-  unsigned usoff[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) usoff[u] = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)u * (unsigned)DHW * 4u));
+  EMO_SPLIT_USOFF(8, 0, DHW, 1u)
 
   int n_ci0, n_zu;
   bool n_zv;
@@ -743,37 +670,20 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
   }
   unsigned q_vo;
 #define EMO_S_ISSUE_BEGIN(b_)                                                                         \
-  {                                                                                                   \
-    const int c0_ = n_ci0 + q_g * 8;                                                                  \
-    const bool cv_ = c0_ < a.Cin;                                                                     \
-    const int cs_ = cv_ ? c0_ : 0;                                                                    \
-    const bool keep_ = lq_ok && cv_ && n_zv;                                                          \
-    q_lo[b_] = keep_ ? clamp_lo : 0.0f;                                                               \
-    q_hi[b_] = keep_ ? CLAMP_HI : 0.0f;                                                               \
-    q_vo = lq_off + ((unsigned)cs_ * (unsigned)DHW + (unsigned)((n_zv ? n_zu : 0) * HW)) * 4u;        \
-    q_tix[b_] = (has_affine ? cs_ : (cs_ & (Cfg::SCT - 1))) >> 2;                                     \
-  }
-#define EMO_S_ISSUE_LOADS(b_, u0_, u1_)                                                               \
-  { _Pragma("unroll") for (int u = (u0_); u < (u1_); u += 2) emo_bload4x2_pinned(xrs, q_vo, usoff[u], usoff[u + 1], qv[b_][u], qv[b_][u + 1]); }
-#define EMO_S_HALF_TABLE(b_, hf_)                                                                     \
-  {                                                                                                   \
-    const floatx4* t4_ = reinterpret_cast<const floatx4*>(sct) + q_tix[b_] + (hf_);                   \
-    q_sc = t4_[0]; q_sh = t4_[Cfg::SCT / 4];                                                          \
-  }
-#define EMO_S_TOUCH_QUAD(b_) { _Pragma("unroll") for (int u = 0; u < 8; ++u) emo_touch4(qv[b_][u]); }
-// Conversion of channels 4 * hf_ .. + 3 of pixel i_ of buffer b_: fp32 transform (GroupNorm affine of the producer; ReLU,
-// saturation and zero padding in one v_med3: bounds [0, 0] where the pixel is padding), then the exact split into the operand
+  EMO_SPLIT_ISSUE_BEGIN([b_], q_vo, n_ci0 + q_g * 8, lq_ok && cv_ && n_zv,                            \
+                        ((unsigned)cs_ * (unsigned)DHW + (unsigned)((n_zv ? n_zu : 0) * HW)) * 4u)
+#define EMO_S_ISSUE_LOADS(b_, u0_, u1_) EMO_SPLIT_ISSUE_LOADS(qv[b_], q_vo, u0_, u1_)
+#define EMO_S_HALF_TABLE(b_, hf_) EMO_SPLIT_TABLE(q_tix[b_] + (hf_), q_sc, q_sh)
+#define EMO_S_TOUCH_QUAD(b_) EMO_SPLIT_TOUCH(qv[b_], 8)
+// Conversion of channels 4 * hf_ .. + 3 of pixel i_ of buffer b_ (conv_split_common.h), then the exact split into the operand
 // planes -- v = h + m + l, round-to-nearest-even at every level, the residuals are exact (SPLIT = 2: h + m of the scaled value).
 // The second half stores the pixel's slot of every plane (every lane stores all four pixels of its loads: its own, or into
 // dump slots).
 #define EMO_S_CONV_HALF(b_, pbase_, i_, hf_)                                                          \
   {                                                                                                   \
-    float t_[4];                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                     \
-      t_[k] = __fmaf_rn(qv[b_][4 * (hf_) + k][i_], q_sc[k], q_sh[k]);                                 \
-    if constexpr (SPLIT == 2) {   /* range check of the fp16 split: max |pre-clamp value| (v_max3 with |.| modifiers) */ \
-      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[0])), __builtin_fabsf(t_[1])); \
-      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[2])), __builtin_fabsf(t_[3])); \
+    EMO_SPLIT_AFFINE4(t_, qv[b_], 4 * (hf_), i_, q_sc, q_sh)                                          \
+    if constexpr (SPLIT == 2) {                                                                       \
+      EMO_SPLIT_RANGE4(t_)                                                                            \
     }                                                                                                 \
     if constexpr (SPLIT == 3) {                                                                       \
       _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                 \
@@ -786,14 +696,11 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
         cv_l[u] = (__bf16)r2;                                                                         \
       }                                                                                               \
     } else {                                                                                          \
-      _Pragma("unroll") for (int k = 0; k < 4; k += 2)                                                \
-        emo_split_f16x2_pair(__builtin_amdgcn_fmed3f(t_[k], q_lo[b_], q_hi[b_]),                      \
-                             __builtin_amdgcn_fmed3f(t_[k + 1], q_lo[b_], q_hi[b_]), cv_h, cv_m, 4 * (hf_) + k); \
+      EMO_SPLIT_F16X2_4(t_, q_lo[b_], q_hi[b_], cv_h, cv_m, 4 * (hf_))                                \
     }                                                                                                 \
     if ((hf_) == 1) {                                                                                 \
       char* d_ = lds_w + q_slb[i_] + (pbase_) * 16;                                                   \
-      *reinterpret_cast<opx8*>(d_) = cv_h;                                                            \
-      *reinterpret_cast<opx8*>(d_ + PPL * 16) = cv_m;                                                 \
+      EMO_SPLIT_STORE_PLANES(opx8, d_, cv_h, cv_m)                                                    \
       if constexpr (SPLIT == 3) *reinterpret_cast<opx8*>(d_ + 2 * PPL * 16) = cv_l;                   \
     }                                                                                                 \
   }
@@ -815,24 +722,7 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
     const int j = (BMT == 64 || (k_) < 4) ? wave + 4 * (k_) : 16 + (wave & 1);                        \
     emo_dma16_pinned_s((ptr_) + j * 1024, lane16, smem_lds + (unsigned)((Cfg::OFF_W + (wb_) * Cfg::WSTAGE) * 16 + j * 1024)); \
   }
-#define EMO_S_WAIT(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
-#if EMO_S_TIMING == 2
-// measurement build: how long every wave sits in the waitcnt of a K-loop barrier (memory / LDS latency it did not hide) and in
-// the s_barrier itself (skew between the block's waves), summed per work item and wave
-#define EMO_S_BARRIER(n_)                                                                             \
-  {                                                                                                   \
-    const unsigned long long b0_ = __builtin_amdgcn_s_memtime();                                      \
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(n_) : "memory");                              \
-    const unsigned long long b1_ = __builtin_amdgcn_s_memtime();                                      \
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                  \
-    const unsigned long long b2_ = __builtin_amdgcn_s_memtime();                                      \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                \
-    tw_wait += b1_ - b0_; tw_bar += b2_ - b1_; ++tw_n;                                                \
-  }
-#else
-#define EMO_S_BARRIER(n_) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(n_) : "memory")
-#endif
-#define EMO_S_LOOP_BARRIER(n_) { if (EMO_S_ABLATE & 2) { EMO_S_WAIT(n_); } else { EMO_S_BARRIER(n_); } }
+#define EMO_S_LOOP_BARRIER(n_) { if (EMO_S_ABLATE & 2) { EMO_SPLIT_WAIT(n_); } else { EMO_SPLIT_TIMED_BARRIER(n_); } }
 
 
   // the partial products, smallest first: (weight plane, patch plane); the last one is the leading product
@@ -916,7 +806,7 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
     chain_out = nx_n == it_n && nst_ >= 2 && (nst_ & 1) == 0 && nxst_ >= 2 && (nxst_ & 1) == 0;
     // the next item's load cursor, ready for the stage that switches to it (the K loop stays free of branches: with one
     // around the switch the compiler moved 109 accumulators to ordinary registers and back in every stage pair)
-    EMO_S_CURSOR_OF(nx_, nxq_ok, nxq_off)
+    EMO_SPLIT_CURSOR_OF(nx_, nxq_ok, nxq_off)
     nx_cc0 = __builtin_amdgcn_readfirstlane(nx_st_begin / a.KD);
     nx_kd0 = nx_st_begin - nx_cc0 * a.KD;
   }
@@ -945,7 +835,7 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
     const char* const w1_ = it_wsrc + (long)(it_st_begin + 1) * (3 * Cfg::WROW_BYTES);
     EMO_S_DMA_STAGE_PIECE(w1_, 1, 0)
     EMO_S_DMA_STAGE_PIECE(w1_, 1, 1)
-    EMO_S_BARRIER(2);
+    EMO_SPLIT_TIMED_BARRIER(2);
   } else {
   EMO_S_PROLOGUE_ISSUE(it_, true)
   // ---- prologue, second part: the tables into LDS, the first patch converted into P[0]; it leaves the state every stage leaves
@@ -961,7 +851,7 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
   }
   // bias of the block's channels in the order the epilogue's row layout reads it (conv_epilogue_rows)
   if (tid < BM) smem[Cfg::OFF_BIAS_F + (tid >> 5) * 32 + (tid & 3) * 8 + ((tid & 31) >> 2)] = te_b;
-  EMO_S_WAIT(0);
+  EMO_SPLIT_WAIT(0);
   EMO_S_TOUCH_QUAD(0)
   EMO_S_TOUCH_QUAD(1)
   __syncthreads();   // scale / shift tables visible
@@ -978,12 +868,12 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
     const char* const w1_ = it_wsrc + (long)((it_st_begin + 1) < it_st_end ? it_st_begin + 1 : it_st_begin) * (3 * Cfg::WROW_BYTES);
     EMO_S_DMA_STAGE_PIECE(w1_, 1, 0)
     EMO_S_DMA_STAGE_PIECE(w1_, 1, 1)
-    EMO_S_BARRIER(2);                    // (LDS stores of P[0] visible; the two pieces stay in flight)
+    EMO_SPLIT_TIMED_BARRIER(2);                    // (LDS stores of P[0] visible; the two pieces stay in flight)
   } else {
     // the first two pieces of the first stage's kernel row 2 (its other three follow in steps 0 and 1)
     EMO_S_DMA_PIECE(it_wsrc + (long)it_st_begin * (3 * Cfg::WROW_BYTES), 2, 0)
     EMO_S_DMA_PIECE(it_wsrc + (long)it_st_begin * (3 * Cfg::WROW_BYTES), 2, 1)
-    EMO_S_BARRIER(2);                    // (LDS stores of P[0] visible; the two pieces stay in flight)
+    EMO_SPLIT_TIMED_BARRIER(2);                    // (LDS stores of P[0] visible; the two pieces stay in flight)
   }
   }
 
@@ -1196,7 +1086,7 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
     // Between the K loop and the epilogue: the re-issued loads / DMA of the clamped last stages are dead and are drained (a
     // chained item's are the next item's first stages: they have landed behind this), and every wave must be past its last
     // fragment read of the item's last stage before its buffers become the epilogue's scratch
-    EMO_S_WAIT(0);
+    EMO_SPLIT_WAIT(0);
     EMO_S_STAMP(5)
     __syncthreads();
     EMO_S_STAMP(6)
@@ -1204,15 +1094,7 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
       const int co_ = nx_cotile * BM + tid;
       te_b = a.bias[co_ < a.Cout ? co_ : a.Cout - 1];
     }
-#define EMO_S_EPI_FAST(RES_)                                                                                                      \
-    {                                                                                                                              \
-      floatx4 rv_[8];                                                                                                              \
-      conv_epilogue_fast_issue<TW, TP, BM, RES_, 0>(a, rv_, ep_n, ep_cotile, ep_x0, ep_y0, ep_z0, wp, lane);                       \
-      conv_epilogue_fast_finish<TW, TM, TP, WGP, BM, SPLIT, Cfg::EPI_ROWF, RES_>(a, acc_lo, acc_hi, rv_, scratch,                  \
-                                                                                 smem + Cfg::OFF_BIAS_F, smem + Cfg::OFF_STAT_F, ep_n, \
-                                                                                 ep_cotile, ep_ptile, ep_x0, ep_y0, ep_z0, wp, half, \
-                                                                                 l32, lane, tid EMO_S_TSTAMP_ARG);                  \
-    }
+#define EMO_S_EPI_FAST(RES_) EMO_SPLIT_EPI_FAST(RES_, acc_lo, acc_hi, EMO_SPLIT_STAMPS)
     if (epi_mode == 1) EMO_S_EPI_FAST(1)
     else if (epi_mode == 2) EMO_S_EPI_FAST(2)
     else if (epi_mode == 0) EMO_S_EPI_FAST(0)
@@ -1263,15 +1145,12 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
 #undef EMO_S_ISSUE_BEGIN
 #undef EMO_S_ISSUE_LOADS
 #undef EMO_S_HALF_TABLE
-#undef EMO_S_B_OFF
 #undef EMO_S_CONV_HALF
 #undef EMO_S_TOUCH_QUAD
 #undef EMO_S_DMA_PIECE
 #undef EMO_S_DMA_PIECE_TO
 #undef EMO_S_DMA_STAGE_PIECE
 #undef EMO_S_DMA_ROW
-#undef EMO_S_WAIT
-#undef EMO_S_BARRIER
 #undef EMO_S_LOOP_BARRIER
 #undef EMO_S_LOAD_FRAGS_PLANE
 #undef EMO_S_LOAD_FRAGS
@@ -1281,7 +1160,6 @@ void conv_igemm_bf16x3_kernel(const ConvArgs a) {
 #undef EMO_S_WSRC
 #undef EMO_S_PROLOGUE_ISSUE
 #undef EMO_S_CURSOR_TO
-#undef EMO_S_CURSOR_OF
 }
 
 template <int TR, int TW, bool UPS, int SPLIT = 3, int BMT = 64>

@@ -35,6 +35,8 @@
 // carry 11 significand bits, products and sums are exact fp32 MFMA accumulation.
 #pragma once
 #include "conv_igemm.h"
+#include "conv_split_pair_common.h"   // (first and by name: see its header comment)
+#include "conv_split_common.h"
 
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
 typedef int emo_intx4 __attribute__((ext_vector_type(4)));
@@ -233,7 +235,7 @@ void conv_igemm_f16_kernel(const ConvArgs a) {
         // source pixel of tap (r, s), relative to the patch origin (row 0 = y0s - HALO, column -1 = left halo)
         const int pr = UPS ? ((row + r - HALO + 2) >> 1) - 1 + HALO : row + r;
         const int pc = UPS ? ((col + s - HALO + 2) >> 1) - 1 : col + s - HALO;
-        const int slot = pc < 0 ? pr * NQ1 + NQ : (pc >= TWS ? SUB + pr * NQ1 + NQ : (pc & 3) * SUB + pr * NQ1 + (pc >> 2));
+        const int slot = EMO_SPLIT_PATCH_SLOT(pr, pc);
         b_slot[j][r][s] = half * CHS + slot;
       }
   }
@@ -353,11 +355,9 @@ void conv_igemm_f16_kernel(const ConvArgs a) {
       if (i < Cfg::NDMA_MIN || boff < ASZ_H * 2) emo_dma16_pinned(ws_ + boff, (dst_lds_) + (unsigned)(j * 1024)); \
     }                                                                                                 \
   }
-#define EMO_H_WAIT(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
-#define EMO_H_BARRIER(n_) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(n_) : "memory")
 #define EMO_H_STAGE_BARRIER()                                                                         \
   {                                                                                                   \
-    if (is_halo_wave) { EMO_H_BARRIER(16); } else { EMO_H_BARRIER(8); }                               \
+    if (is_halo_wave) { EMO_SPLIT_BARRIER(16); } else { EMO_SPLIT_BARRIER(8); }                       \
   }
 
   // ---- prologue: stage st_begin into buffer 0, issue the loads of stage st_begin + 1.  The first loads go out before the
@@ -371,7 +371,7 @@ void conv_igemm_f16_kernel(const ConvArgs a) {
     sct[c] = real ? a.scale[(long)n * a.Cin + c] : 1.0f;
     sct[Cfg::SCT + c] = real ? a.shift[(long)n * a.Cin + c] : 0.0f;
   }
-  EMO_H_WAIT(0);
+  EMO_SPLIT_WAIT(0);
   __syncthreads();   // scale / shift tables visible
   EMO_H_QUAD_TABLE()
   if (is_halo_wave) EMO_H_HALO_TABLE()
@@ -431,7 +431,7 @@ void conv_igemm_f16_kernel(const ConvArgs a) {
         for (int pc = 0; pc < NPIECE; ++pc) {
           if ((pc * NSTEPS * NSLOT) / PIECE_SPAN != step * NSLOT + m) continue;
           if (pc == 0) {
-            EMO_H_WAIT(0);
+            EMO_SPLIT_WAIT(0);
             EMO_H_TOUCH_QUAD()
             if (is_halo_wave) EMO_H_TOUCH_HALO()
             EMO_H_STORE_QUAD(nxt, 0)
@@ -452,7 +452,7 @@ void conv_igemm_f16_kernel(const ConvArgs a) {
     if (EMO_CONV_SETPRIO) __builtin_amdgcn_s_setprio(0);
     EMO_H_STAGE_BARRIER()
   }
-  EMO_H_WAIT(0);   // the re-issued loads of the clamped last stage are dead: drain them before their registers are reused
+  EMO_SPLIT_WAIT(0);   // the re-issued loads of the clamped last stage are dead: drain them before their registers are reused
 #undef EMO_H_SET_STAGE
 #undef EMO_H_ISSUE_QUAD
 #undef EMO_H_ISSUE_HALO
@@ -463,8 +463,6 @@ void conv_igemm_f16_kernel(const ConvArgs a) {
 #undef EMO_H_TOUCH_QUAD
 #undef EMO_H_TOUCH_HALO
 #undef EMO_H_DMA_WEIGHTS
-#undef EMO_H_WAIT
-#undef EMO_H_BARRIER
 #undef EMO_H_STAGE_BARRIER
 #undef EMO_H_LOAD_FRAGS
 #undef acc_at

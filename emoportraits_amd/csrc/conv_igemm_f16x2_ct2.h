@@ -31,7 +31,6 @@
 // sets): the two are BIT-IDENTICAL (tests/test_conv_bf16x3_gpu.py).
 #pragma once
 #include "conv_igemm_bf16x3.h"
-#include "conv_split_pair_common.h"
 
 #ifndef EMO_CT2_RES_EARLY
 #define EMO_CT2_RES_EARLY 0   /* 1: the first tile's residual loads go out in front of the K loop instead of at the top of the epilogue.
@@ -63,10 +62,7 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l32 = lane & 31;
+  EMO_SPLIT_THREAD_IDS()
   const int wp = wave;
   const int p0 = wp * TP * 32;
   float sat_m = 0.0f;                                    // largest |scaled staged value| this thread has seen
@@ -87,31 +83,13 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
   const int nst = a.n_cchunks * a.KD;                    // stages of an item (no K split)
   const int nptiles = a.tiles_x * a.tiles_y * a.tiles_z;
 
-  // ---- staging map (conv_igemm_bf16x3.h: interior quads and, on the lanes that own none, one halo pixel each) ----
-  const int q_u = tid % QPG;
-  const int q_g = __builtin_amdgcn_readfirstlane(tid / QPG);
-  const bool is_quad = q_u < PR * NQ;
-  const int hq = q_u - PR * NQ;
-  const bool is_halo = !is_quad && hq < NHQ;
-  const int h_side = hq & 1;
-  const int q_r = is_quad ? q_u / NQ : (is_halo ? hq >> 1 : 0);
-  const int q_c = is_quad ? q_u - q_r * NQ : 0;
-  int q_slb[4];                                           // byte offsets of the lane's four staging slots inside a patch buffer
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int dump = q_g * CHS + i * SUB + PR * NQ1 + (q_u & 3);
-    const int own = is_quad ? q_g * CHS + i * SUB + q_r * NQ1 + q_c : q_g * CHS + h_side * SUB + q_r * NQ1 + NQ;
-    q_slb[i] = ((is_quad || (is_halo && i == (h_side ? 0 : 3))) ? own : dump) * 16;
-  }
+  // ---- staging map (conv_split_common.h: interior quads and, on the lanes that own none, one halo pixel each) ----
+  EMO_SPLIT_STAGING_MAP(tid / QPG, 0)
 
   floatx16 acc_lo[2][TM][TP], acc_hi[2][TM][TP];         // [channel tile of the pair]: all 256 accumulation registers
 
   // ---- work items: (sample, position tile, channel-tile PAIR), XCD-contiguous, pair fastest; persistent blocks ----
-  const int q8 = a.n_work >> 3, r8 = a.n_work & 7;
-  const int xcd = blockIdx.x & 7;
-  const int n_mine = q8 + (xcd < r8 ? 1 : 0);
-  const int l_base = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int l_stride = (gridDim.x + 7) >> 3;
+  EMO_SPLIT_ITEM_WALK()
   int it_cotile = 0, it_n = 0, it_ptile = 0, it_x0 = 0, it_y0 = 0, it_z0 = 0;
   unsigned lq_off = 0;
   bool lq_ok = false;
@@ -119,13 +97,12 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
 // byte address of the packed kernel rows of (channel tile c_, stage k_)
 #define EMO_T_WPTR(c_, k_) (reinterpret_cast<const char*>(a.wpk) + (long)((c_) * nst + (k_)) * (3 * Cfg::WROW_BYTES))
 
-  // LDS byte offsets of the lane's operands (conv_igemm_bf16x3.h); the patch buffer of a stage is a RUN-TIME parity here (two
+  // LDS byte offsets of the lane's operands (conv_split_common.h); the patch buffer of a stage is a RUN-TIME parity here (two
   // half-stages per stage make the unrolled pair of loop bodies the two channel tiles, not two stages): + pcur_b / pnxt_b
   const int a_off = (half * BM + l32) * 16;
-  EMO_P_DECLARE_B_OFF()
+  EMO_SPLIT_DECLARE_B_OFF()
 
-  const char* const lds_c = reinterpret_cast<const char*>(smem);
-  char* const lds_w = reinterpret_cast<char*>(smem);
+  EMO_SPLIT_LDS_VIEWS()
   opx8 fa_[2][NPL][TM], fb_[2][NPL][TP];     // [register set: this step / the next][plane][tile]
 // (wbase_: slots, compile-time; pbyte_: byte offset of the patch buffer, run-time)
 #define EMO_T_LOAD_FRAGS_PLANE(set_, pl_, wbase_, pbyte_, r_, s_)                                      \
@@ -133,12 +110,10 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
     _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                    \
       fa_[set_][pl_][i] = *reinterpret_cast<const opx8*>(lds_c + a_off + ((wbase_) + (pl_) * WPLANE + (s_) * 2 * BM + i * 32) * 16); \
     _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                    \
-      fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + (EMO_P_B_OFF(j, r_, s_) + (pbyte_)) + ((pl_) * PPL) * 16); \
+      fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + (EMO_SPLIT_B_OFF(j, r_, s_) + (pbyte_)) + ((pl_) * PPL) * 16); \
   }
 
-  float* const sct = smem + Cfg::OFF_SCT * 4;
-  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(smem);
-  const unsigned lane16 = (unsigned)lane * 16u;
+  EMO_SPLIT_LDS_TABLES_ADDR()
 
   // raw patch registers: ONE buffer -- converted during half-stage 0, reloaded during half-stage 1
   floatx4 qv[8];
@@ -147,9 +122,7 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
   floatx4 q_sc, q_sh;
   opx8 cv_h, cv_m;
   emo_intx4 xrs = emo_raw_buffer(a.x);
-  unsigned usoff[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) usoff[u] = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)u * (unsigned)DHW * 4u * (EMO_CT2_X_CONST ? 0u : 1u)));
+  EMO_SPLIT_USOFF(8, 0, DHW, (EMO_CT2_X_CONST ? 0u : 1u))
 
   int n_ci0, n_zu;
   bool n_zv;
@@ -162,39 +135,20 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
   }
   unsigned q_vo;
 #define EMO_T_ISSUE_BEGIN()                                                                           \
-  {                                                                                                   \
-    const int c0_ = n_ci0 + q_g * 8;                                                                  \
-    const bool cv_ = c0_ < a.Cin;                                                                     \
-    const int cs_ = cv_ ? c0_ : 0;                                                                    \
-    const bool keep_ = lq_ok && cv_ && n_zv;                                                          \
-    q_lo = keep_ ? clamp_lo : 0.0f;                                                                   \
-    q_hi = keep_ ? CLAMP_HI : 0.0f;                                                                   \
-    q_vo = lq_off + (EMO_CT2_X_CONST ? 0u : ((unsigned)cs_ * (unsigned)DHW + (unsigned)((n_zv ? n_zu : 0) * HW)) * 4u);   \
-    q_tix = (has_affine ? cs_ : (cs_ & (Cfg::SCT - 1))) >> 2;                                         \
-  }
-#define EMO_T_ISSUE_LOADS(u0_, u1_)                                                                   \
-  { _Pragma("unroll") for (int u = (u0_); u < (u1_); u += 2) emo_bload4x2_pinned(xrs, q_vo, usoff[u], usoff[u + 1], qv[u], qv[u + 1]); }
-#define EMO_T_HALF_TABLE(hf_)                                                                         \
-  {                                                                                                   \
-    const floatx4* t4_ = reinterpret_cast<const floatx4*>(sct) + q_tix + (hf_);                       \
-    q_sc = t4_[0]; q_sh = t4_[Cfg::SCT / 4];                                                          \
-  }
-#define EMO_T_TOUCH_QUAD() { _Pragma("unroll") for (int u = 0; u < 8; ++u) emo_touch4(qv[u]); }
-// conversion of channels 4 * hf_ .. + 3 of pixel i_ (conv_igemm_bf16x3.h, SPLIT = 2); pbyte_: byte offset of the target patch buffer
+  EMO_SPLIT_ISSUE_BEGIN(, q_vo, n_ci0 + q_g * 8, lq_ok && cv_ && n_zv,                                \
+                        (EMO_CT2_X_CONST ? 0u : ((unsigned)cs_ * (unsigned)DHW + (unsigned)((n_zv ? n_zu : 0) * HW)) * 4u))
+#define EMO_T_ISSUE_LOADS(u0_, u1_) EMO_SPLIT_ISSUE_LOADS(qv, q_vo, u0_, u1_)
+#define EMO_T_HALF_TABLE(hf_) EMO_SPLIT_TABLE(q_tix + (hf_), q_sc, q_sh)
+#define EMO_T_TOUCH_QUAD() EMO_SPLIT_TOUCH(qv, 8)
+// conversion of channels 4 * hf_ .. + 3 of pixel i_ (conv_split_common.h); pbyte_: byte offset of the target patch buffer
 #define EMO_T_CONV_HALF(pbyte_, i_, hf_)                                                              \
   {                                                                                                   \
-    float t_[4];                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                     \
-      t_[k] = __fmaf_rn(qv[4 * (hf_) + k][i_], q_sc[k], q_sh[k]);                                     \
-    sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[0])), __builtin_fabsf(t_[1])); \
-    sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[2])), __builtin_fabsf(t_[3])); \
-    _Pragma("unroll") for (int k = 0; k < 4; k += 2)                                                  \
-      emo_split_f16x2_pair(__builtin_amdgcn_fmed3f(t_[k], q_lo, q_hi), __builtin_amdgcn_fmed3f(t_[k + 1], q_lo, q_hi), \
-                           cv_h, cv_m, 4 * (hf_) + k);                                                \
+    EMO_SPLIT_AFFINE4(t_, qv, 4 * (hf_), i_, q_sc, q_sh)                                              \
+    EMO_SPLIT_RANGE4(t_)                                                                              \
+    EMO_SPLIT_F16X2_4(t_, q_lo, q_hi, cv_h, cv_m, 4 * (hf_))                                          \
     if ((hf_) == 1) {                                                                                 \
       char* d_ = lds_w + (q_slb[i_] + (pbyte_));                                                      \
-      *reinterpret_cast<opx8*>(d_) = cv_h;                                                            \
-      *reinterpret_cast<opx8*>(d_ + PPL * 16) = cv_m;                                                 \
+      EMO_SPLIT_STORE_PLANES(opx8, d_, cv_h, cv_m)                                                    \
     }                                                                                                 \
   }
 #define EMO_T_WSRC(p_) (EMO_CT2_W_CONST ? reinterpret_cast<const char*>(a.wpk) : (p_))
@@ -219,14 +173,14 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
   for (int k = 0; k < 12; ++k) tstamp[k] = 0;
 #endif
   EMO_S_STAMP(0)
-  EMO_P_DECODE(it_, l_base + idx8)
+  EMO_SPLIT_DECODE(it_, l_base + idx8, a.cot0 + 2 * cot_, )
   int nx_cotile = 0, nx_n = 0, nx_ptile = 0, nx_x0 = 0, nx_y0 = 0, nx_z0 = 0;
   bool chain_out = false, nxq_ok = false;
   unsigned nxq_off = 0;
   if (EMO_S_CHAIN && idx8 + l_stride < n_mine) {
-    EMO_P_DECODE(nx_, l_base + idx8 + l_stride)
+    EMO_SPLIT_DECODE(nx_, l_base + idx8 + l_stride, a.cot0 + 2 * cot_, )
     chain_out = nx_n == it_n && nst >= 2;
-    EMO_P_CURSOR_OF(nx_, nxq_ok, nxq_off)
+    EMO_SPLIT_CURSOR_OF(nx_, nxq_ok, nxq_off)
   }
   (void)nx_ptile;
   // (declared dead here: conv_igemm_bf16x3.h)
@@ -252,13 +206,13 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
     const char* const w1_ = EMO_T_WPTR(it_cotile + 1, 0);
     EMO_T_DMA_PIECE(w1_, 1, 0)
     EMO_T_DMA_PIECE(w1_, 1, 1)
-    EMO_P_BARRIER(2);
+    EMO_SPLIT_BARRIER(2);
   } else {
     // ---- full prologue: tables, the nine pieces of (c0, stage 0), the patch of stage 0 converted into P[0], the loads of stage 1 ----
 #pragma unroll
     for (int u = 0; u < 8; ++u) asm volatile("" : "=v"(qv[u]));
     xrs = emo_raw_buffer(a.x + (long)it_n * a.Cin * DHW);
-    EMO_P_CURSOR_OF(it_, lq_ok, lq_off)
+    EMO_SPLIT_CURSOR_OF(it_, lq_ok, lq_off)
     lq_z0 = it_z0;
 #pragma unroll
     for (int k = 0; k < NTE; ++k) {
@@ -292,7 +246,7 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
       const int t2_ = tid & (BM - 1);
       smem[(tid < BM ? Cfg::OFF_BIAS_F : Cfg::OFF_BIAS2_F) + (t2_ >> 5) * 32 + (t2_ & 3) * 8 + ((t2_ & 31) >> 2)] = te_b;
     }
-    EMO_P_WAIT(0);
+    EMO_SPLIT_WAIT(0);
     EMO_T_TOUCH_QUAD()
     __syncthreads();   // scale / shift tables visible
 #pragma unroll
@@ -315,7 +269,7 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
       EMO_T_DMA_PIECE(w1_, 1, 0)
       EMO_T_DMA_PIECE(w1_, 1, 1)
     }
-    EMO_P_BARRIER(0);                    // (P[0] visible, W[0] and the loads of stage 1 landed)
+    EMO_SPLIT_BARRIER(0);                    // (P[0] visible, W[0] and the loads of stage 1 landed)
     EMO_T_TOUCH_QUAD()
     pp = 0;
   }
@@ -362,7 +316,7 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
         const int r = gs / 3, s = gs % 3;
         const int fcur = (h * 9 + gs) & 1, fnxt = fcur ^ 1;
         (void)r; (void)s;
-        if (gs == 8) { EMO_P_BARRIER(0); }
+        if (gs == 8) { EMO_SPLIT_BARRIER(0); }
         if (gs == 8 && h == 1) EMO_T_TOUCH_QUAD()          // (the loads of stage cg + 2 have landed behind the barrier)
         if (gs == 0 && h == 1) {
           // the patch loads of stage cg + 2; past the item's end: the next item's stages 0 / 1 (chained), a dead re-stage otherwise
@@ -442,7 +396,7 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
     // ---- epilogue, once per channel tile of the pair; the transposition scratch is W[1] ----
     float* const scratch = smem + (Cfg::OFF_W + Cfg::WSTAGE) * 4 + wave * Cfg::EPI_WAVE;
     const int ep_n = it_n, ep_cotile = it_cotile, ep_ptile = it_ptile, ep_x0 = it_x0, ep_y0 = it_y0, ep_z0 = it_z0;
-    EMO_P_WAIT(0);
+    EMO_SPLIT_WAIT(0);
     EMO_S_STAMP(5)
     __syncthreads();
     EMO_S_STAMP(6)
@@ -454,19 +408,15 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
 // both tiles of the pair: the second tile's first residual loads are issued in front of the first tile's epilogue (they have landed
 // when their turn comes: the residual is a tensor another kernel wrote long ago -- an HBM round trip that the single-tile kernel
 // waits out in every item)
-#define EMO_T_EPI_FAST(RES_)                                                                                                      \
-    {                                                                                                                              \
-      floatx4 (&rv_)[8] = rv_first;                                                                                                \
-      floatx4 rvn_[8];                                                                                                             \
-      if (!EMO_CT2_RES_EARLY) conv_epilogue_fast_issue<TW, TP, BM, RES_, 0, true>(a, rv_, ep_n, ep_cotile, ep_x0, ep_y0, ep_z0, wp, lane); \
-      conv_epilogue_fast_issue<TW, TP, BM, RES_, 0, true>(a, rvn_, ep_n, ep_cotile + 1, ep_x0, ep_y0, ep_z0, wp, lane);            \
-      conv_epilogue_fast_finish<TW, TM, TP, WGP, BM, SPLIT, Cfg::EPI_ROWF, RES_, true, true>(                                      \
-          a, acc_lo[0], acc_hi[0], rv_, scratch, smem + Cfg::OFF_BIAS_F, smem + Cfg::OFF_STAT_F, ep_n, ep_cotile, ep_ptile, ep_x0,  \
-          ep_y0, ep_z0, wp, half, l32, lane, tid EMO_S_TSTAMP_ARG);                                                                \
-      EMO_S_STAMP(10)                                                                                                              \
-      conv_epilogue_fast_finish<TW, TM, TP, WGP, BM, SPLIT, Cfg::EPI_ROWF, RES_, true, true>(                                      \
-          a, acc_lo[1], acc_hi[1], rvn_, scratch, smem + Cfg::OFF_BIAS2_F, smem + Cfg::OFF_STAT2_F, ep_n, ep_cotile + 1, ep_ptile,  \
-          ep_x0, ep_y0, ep_z0, wp, half, l32, lane, tid EMO_S_TSTAMP_ARG);                                                         \
+#define EMO_T_EPI_FAST(RES_)                                                                          \
+    {                                                                                                 \
+      floatx4 (&rv_)[8] = rv_first;                                                                   \
+      floatx4 rvn_[8];                                                                                \
+      if (!EMO_CT2_RES_EARLY) EMO_SPLIT_EPI_ISSUE(RES_, true, rv_, ep_cotile)                         \
+      EMO_SPLIT_EPI_ISSUE(RES_, true, rvn_, ep_cotile + 1)                                            \
+      EMO_SPLIT_EPI_FINISH(RES_, true, acc_lo[0], acc_hi[0], rv_, Cfg::OFF_BIAS_F, Cfg::OFF_STAT_F, ep_cotile, EMO_SPLIT_STAMPS)      \
+      EMO_S_STAMP(10)                                                                                 \
+      EMO_SPLIT_EPI_FINISH(RES_, true, acc_lo[1], acc_hi[1], rvn_, Cfg::OFF_BIAS2_F, Cfg::OFF_STAT2_F, ep_cotile + 1, EMO_SPLIT_STAMPS) \
     }
     if (epi_mode == 1) EMO_T_EPI_FAST(1)
     else if (epi_mode == 2) EMO_T_EPI_FAST(2)
@@ -498,7 +448,7 @@ void conv_igemm_bf16x3_ct2_kernel(const ConvArgs a) {
   // tile statistics, second half (conv_epilogue_rows_stats, for both tiles at once and behind the barrier above instead of one of
   // their own each): thread c of the first 128 combines the four waves' (mean, M2) of channel c with the equal-count update.
   // The exchange areas are next written by the NEXT item's epilogue, a K loop away
-  EMO_P_COMBINE_STATS(Cfg::OFF_STAT_F, Cfg::OFF_STAT2_F, true)
+  EMO_SPLIT_COMBINE_STATS(Cfg::OFF_STAT_F, Cfg::OFF_STAT2_F, true)
   chained_in = chain_out;
   }
 #undef EMO_T_WPTR

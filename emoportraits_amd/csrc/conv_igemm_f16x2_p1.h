@@ -69,10 +69,7 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l32 = lane & 31;
+  EMO_SPLIT_THREAD_IDS()
   const int wp = wave;
   const int p0 = wp * TP * 32;
   float sat_m = 0.0f;
@@ -96,33 +93,13 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
 
   floatx16 acc_lo[2][TM][TP], acc_hi[2][TM][TP];
 
-  const int q8 = a.n_work >> 3, r8 = a.n_work & 7;
-  const int xcd = blockIdx.x & 7;
-  const int n_mine = q8 + (xcd < r8 ? 1 : 0);
-  const int l_base = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int l_stride = (gridDim.x + 7) >> 3;
+  EMO_SPLIT_ITEM_WALK()
   int it_cotile = 0, it_n = 0, it_ptile = 0, it_x0 = 0, it_y0 = 0, it_z0 = 0;
   unsigned lq_off = 0;
   int lq_z0 = 0;
-#define EMO_P_DECODE(P_, L_)                                                                          \
-  {                                                                                                   \
-    const int l_ = (L_);                                                                              \
-    const int cot_ = l_ % a.n_cotiles;                                                                \
-    const int rest_ = l_ / a.n_cotiles;                                                               \
-    const int n_ = rest_ / nptiles;                                                                   \
-    int bx_ = rest_ - n_ * nptiles;                                                                   \
-    P_##ptile = __builtin_amdgcn_readfirstlane(bx_);                                                  \
-    const int tx_ = bx_ % a.tiles_x; bx_ /= a.tiles_x;                                                \
-    const int ty_ = bx_ % a.tiles_y; bx_ /= a.tiles_y;                                                \
-    P_##cotile = __builtin_amdgcn_readfirstlane(2 * cot_);                                            \
-    P_##n = __builtin_amdgcn_readfirstlane(n_);                                                       \
-    P_##x0 = __builtin_amdgcn_readfirstlane(tx_ * TW);                                                \
-    P_##y0 = __builtin_amdgcn_readfirstlane(ty_ * TR);                                                \
-    P_##z0 = __builtin_amdgcn_readfirstlane(bx_);                                                     \
-  }
 // packed weights of (channel tile c_, stage k_); the host pads the tiles to an even count (pack.pack_weight_f16x2_1x1)
-#define EMO_P_WPTR(c_, k_) (reinterpret_cast<const char*>(a.wpk) + (long)((c_) * nst + (k_)) * Cfg::WTILE_BYTES)
-#define EMO_P_CURSOR_OF(P_, off_) { off_ = (unsigned)((P_##y0 + q_r) * a.W + P_##x0 + 4 * q_c) * 4u; }
+#define EMO_P1_WPTR(c_, k_) (reinterpret_cast<const char*>(a.wpk) + (long)((c_) * nst + (k_)) * Cfg::WTILE_BYTES)
+#define EMO_P1_CURSOR_OF(P_, off_) { off_ = (unsigned)((P_##y0 + q_r) * a.W + P_##x0 + 4 * q_c) * 4u; }
 
   // LDS byte offsets of the lane's operands: weight fragment (+ buffer / tile / plane / k-step immediates) and the patch slot of
   // the lane's output pixel (+ half * CHS: the lane's 8-channel group of the k-step; + buffer / plane / k-step immediates)
@@ -134,20 +111,17 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
     const int col = p % TW, row = p / TW;
     b_off[j] = (half * CHS + (col & 3) * SUB + row * NQ + (col >> 2)) * 16;
   }
-  const char* const lds_c = reinterpret_cast<const char*>(smem);
-  char* const lds_w = reinterpret_cast<char*>(smem);
+  EMO_SPLIT_LDS_VIEWS()
   opx8 fa_[2][NPL][TM];        // [register set: step parity][plane][tile row]
   opx8 fb_[2][NPL][TP];        // [k-step][plane][tile column]: read once per stage and k-step, used by both channel tiles
-#define EMO_P_LOAD_A(set_, wb_, h_, ks_)                                                              \
-  { _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl) _Pragma("unroll") for (int i = 0; i < TM; ++i)  \
+#define EMO_P1_LOAD_A(set_, wb_, h_, ks_)                                                             \
+  { _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl) _Pragma("unroll") for (int i = 0; i < TM; ++i) \
       fa_[set_][pl][i] = *reinterpret_cast<const opx8*>(lds_c + a_off + (Cfg::OFF_W + (wb_) * Cfg::WSTAGE + (h_) * Cfg::WTILE + ((pl * 2 + (ks_)) * 2) * BM + i * 32) * 16); }
-#define EMO_P_LOAD_B(pb_, ks_)                                                                        \
-  { _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl) _Pragma("unroll") for (int j = 0; j < TP; ++j)  \
+#define EMO_P1_LOAD_B(pb_, ks_)                                                                       \
+  { _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl) _Pragma("unroll") for (int j = 0; j < TP; ++j) \
       fb_[ks_][pl][j] = *reinterpret_cast<const opx8*>(lds_c + b_off[j] + (Cfg::OFF_P + (pb_) * PBUF + pl * PPL + (ks_) * 2 * CHS) * 16); }
 
-  float* const sct = smem + Cfg::OFF_SCT * 4;
-  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(smem);
-  const unsigned lane16 = (unsigned)lane * 16u;
+  EMO_SPLIT_LDS_TABLES_ADDR()
 
   floatx4 qv[2][8];             // raw patch registers, double-buffered by stage parity
   float q_lo[2], q_hi[2];
@@ -155,56 +129,33 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
   floatx4 t_sc[2], t_sh[2];     // scale / shift of the 8 channels of the group being converted
   opx8 cv_h, cv_m;
   emo_intx4 xrs = emo_raw_buffer(a.x);
-  unsigned usoff[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) usoff[u] = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)u * (unsigned)DHW * 4u));
+  EMO_SPLIT_USOFF(8, 0, DHW, 1u)
 
   int ld_stage;                 // the stage whose patch is being loaded
   unsigned q_vo;
-#define EMO_P_ISSUE_BEGIN(b_)                                                                         \
+#define EMO_P1_ISSUE_BEGIN(b_)                                                                        \
+  EMO_SPLIT_ISSUE_BEGIN([b_], q_vo, ld_stage * KC + wave * 8, cv_, ((unsigned)cs_ * (unsigned)DHW + (unsigned)(lq_z0 * HW)) * 4u)
+#define EMO_P1_ISSUE_LOADS(b_) EMO_SPLIT_ISSUE_LOADS(qv[b_], q_vo, 0, 8)
+#define EMO_P1_TABLES(b_) EMO_SPLIT_TABLE2(q_tix[b_], t_sc, t_sh)
+#define EMO_P1_TOUCH_QUAD(b_) EMO_SPLIT_TOUCH(qv[b_], 8)
+// conversion unit: channels 4 * hf_ .. + 3 of pixel i_ of buffer b_ into patch buffer pb_ (conv_split_common.h)
+#define EMO_P1_CONV_HALF(b_, pb_, i_, hf_)                                                            \
   {                                                                                                   \
-    const int c0_ = ld_stage * KC + wave * 8;                                                         \
-    const bool cv_ = c0_ < a.Cin;                                                                     \
-    const int cs_ = cv_ ? c0_ : 0;                                                                    \
-    q_lo[b_] = cv_ ? clamp_lo : 0.0f;                                                                 \
-    q_hi[b_] = cv_ ? CLAMP_HI : 0.0f;                                                                 \
-    q_vo = lq_off + ((unsigned)cs_ * (unsigned)DHW + (unsigned)(lq_z0 * HW)) * 4u;                    \
-    q_tix[b_] = (has_affine ? cs_ : (cs_ & (Cfg::SCT - 1))) >> 2;                                     \
-  }
-#define EMO_P_ISSUE_LOADS(b_)                                                                         \
-  { _Pragma("unroll") for (int u = 0; u < 8; u += 2) emo_bload4x2_pinned(xrs, q_vo, usoff[u], usoff[u + 1], qv[b_][u], qv[b_][u + 1]); }
-#define EMO_P_TABLES(b_)                                                                              \
-  {                                                                                                   \
-    const floatx4* t4_ = reinterpret_cast<const floatx4*>(sct) + q_tix[b_];                           \
-    t_sc[0] = t4_[0]; t_sc[1] = t4_[1]; t_sh[0] = t4_[Cfg::SCT / 4]; t_sh[1] = t4_[Cfg::SCT / 4 + 1]; \
-  }
-#define EMO_P_TOUCH_QUAD(b_) { _Pragma("unroll") for (int u = 0; u < 8; ++u) emo_touch4(qv[b_][u]); }
-// conversion unit: channels 4 * hf_ .. + 3 of pixel i_ of buffer b_ into patch buffer pb_ (conv_igemm_bf16x3.h, SPLIT = 2)
-#define EMO_P_CONV_HALF(b_, pb_, i_, hf_)                                                             \
-  {                                                                                                   \
-    float t_[4];                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                     \
-      t_[k] = __fmaf_rn(qv[b_][4 * (hf_) + k][i_], t_sc[hf_][k], t_sh[hf_][k]);                       \
-    sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[0])), __builtin_fabsf(t_[1])); \
-    sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[2])), __builtin_fabsf(t_[3])); \
-    _Pragma("unroll") for (int k = 0; k < 4; k += 2)                                                  \
-      emo_split_f16x2_pair(__builtin_amdgcn_fmed3f(t_[k], q_lo[b_], q_hi[b_]),                        \
-                           __builtin_amdgcn_fmed3f(t_[k + 1], q_lo[b_], q_hi[b_]), cv_h, cv_m, 4 * (hf_) + k); \
+    EMO_SPLIT_AFFINE4(t_, qv[b_], 4 * (hf_), i_, t_sc[hf_], t_sh[hf_])                                \
+    EMO_SPLIT_RANGE4(t_)                                                                              \
+    EMO_SPLIT_F16X2_4(t_, q_lo[b_], q_hi[b_], cv_h, cv_m, 4 * (hf_))                                  \
     if ((hf_) == 1) {                                                                                 \
       char* d_ = lds_w + q_slb[i_] + (Cfg::OFF_P + (pb_) * PBUF) * 16;                                \
-      *reinterpret_cast<opx8*>(d_) = cv_h;                                                            \
-      *reinterpret_cast<opx8*>(d_ + PPL * 16) = cv_m;                                                 \
+      EMO_SPLIT_STORE_PLANES(opx8, d_, cv_h, cv_m)                                                    \
     }                                                                                                 \
   }
 // piece k = 0 .. 3 of a stage's weights: wave w copies pieces w and w + 4 of tile k >> 1 (k & 1 selects which) into W[wb_]
-#define EMO_P_DMA_PIECE(ptr0_, ptr1_, wb_, k_)                                                        \
+#define EMO_P1_DMA_PIECE(ptr0_, ptr1_, wb_, k_)                                                       \
   {                                                                                                   \
     const int j_ = wave + 4 * ((k_) & 1);                                                             \
     emo_dma16_pinned_s((((k_) >> 1) ? (ptr1_) : (ptr0_)) + j_ * 1024, lane16,                         \
                        smem_lds + (unsigned)((Cfg::OFF_W + (wb_) * Cfg::WSTAGE + ((k_) >> 1) * Cfg::WTILE) * 16 + j_ * 1024)); \
   }
-#define EMO_P_WAIT(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
-#define EMO_P_BARRIER(n_) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(n_) : "memory")
 
   constexpr int PA3[3] = {1, 0, 0}, PB3[3] = {0, 1, 0};
   constexpr int NTE = Cfg::SCT / 256;
@@ -212,14 +163,14 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
 
   bool chained_in = false;
   for (int idx8 = blockIdx.x >> 3; idx8 < n_mine; idx8 += l_stride) {
-  EMO_P_DECODE(it_, l_base + idx8)
+  EMO_SPLIT_DECODE(it_, l_base + idx8, 2 * cot_, )
   int nx_cotile = 0, nx_n = 0, nx_ptile = 0, nx_x0 = 0, nx_y0 = 0, nx_z0 = 0;
   bool chain_out = false;
   unsigned nxq_off = 0;
   if (EMO_S_CHAIN && idx8 + l_stride < n_mine) {
-    EMO_P_DECODE(nx_, l_base + idx8 + l_stride)
+    EMO_SPLIT_DECODE(nx_, l_base + idx8 + l_stride, 2 * cot_, )
     chain_out = nx_n == it_n;            // (stage counts are even: the buffer parities line up)
-    EMO_P_CURSOR_OF(nx_, nxq_off)
+    EMO_P1_CURSOR_OF(nx_, nxq_off)
   }
   (void)nx_ptile;
 #pragma unroll
@@ -243,10 +194,10 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
       const int t2_ = tid & (BM - 1);
       smem[(tid < BM ? Cfg::OFF_BIAS_F : Cfg::OFF_BIAS2_F) + (t2_ >> 5) * 32 + (t2_ & 3) * 8 + ((t2_ & 31) >> 2)] = te_b;
     }
-    EMO_P_BARRIER(0);
+    EMO_SPLIT_BARRIER(0);
   } else {
     xrs = emo_raw_buffer(a.x + (long)it_n * a.Cin * DHW);
-    EMO_P_CURSOR_OF(it_, lq_off)
+    EMO_P1_CURSOR_OF(it_, lq_off)
     lq_z0 = it_z0;
 #pragma unroll
     for (int k = 0; k < NTE; ++k) {
@@ -260,17 +211,17 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
       te_b = a.bias[co_ < a.Cout ? co_ : a.Cout - 1];
     }
     {
-      const char* const w0_ = EMO_P_WPTR(it_cotile, 0);
-      const char* const w1_ = EMO_P_WPTR(it_cotile + 1, 0);
+      const char* const w0_ = EMO_P1_WPTR(it_cotile, 0);
+      const char* const w1_ = EMO_P1_WPTR(it_cotile + 1, 0);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) EMO_P_DMA_PIECE(w0_, w1_, 0, k)
+      for (int k = 0; k < 4; ++k) EMO_P1_DMA_PIECE(w0_, w1_, 0, k)
     }
     ld_stage = 0;
-    EMO_P_ISSUE_BEGIN(0)
-    EMO_P_ISSUE_LOADS(0)
+    EMO_P1_ISSUE_BEGIN(0)
+    EMO_P1_ISSUE_LOADS(0)
     if (nst > 1) ++ld_stage;             // (one-stage item: the same patch again, a dead re-stage)
-    EMO_P_ISSUE_BEGIN(1)
-    EMO_P_ISSUE_LOADS(1)
+    EMO_P1_ISSUE_BEGIN(1)
+    EMO_P1_ISSUE_LOADS(1)
 #pragma unroll
     for (int k = 0; k < NTE; ++k) {       // (without an affine the index wraps at SCT: identity entries)
       const int c = tid + 256 * k;
@@ -283,18 +234,18 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
       const int t2_ = tid & (BM - 1);
       smem[(tid < BM ? Cfg::OFF_BIAS_F : Cfg::OFF_BIAS2_F) + (t2_ >> 5) * 32 + (t2_ & 3) * 8 + ((t2_ & 31) >> 2)] = te_b;
     }
-    EMO_P_WAIT(0);
-    EMO_P_TOUCH_QUAD(0)
-    EMO_P_TOUCH_QUAD(1)
+    EMO_SPLIT_WAIT(0);
+    EMO_P1_TOUCH_QUAD(0)
+    EMO_P1_TOUCH_QUAD(1)
     __syncthreads();   // scale / shift tables visible
-    EMO_P_TABLES(0)
+    EMO_P1_TABLES(0)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      EMO_P_CONV_HALF(0, 0, i, 0)
-      EMO_P_CONV_HALF(0, 0, i, 1)
+      EMO_P1_CONV_HALF(0, 0, i, 0)
+      EMO_P1_CONV_HALF(0, 0, i, 1)
     }
-    EMO_P_TABLES(1)                      // (what the first stage converts with)
-    EMO_P_BARRIER(0);                    // (P[0] visible)
+    EMO_P1_TABLES(1)                      // (what the first stage converts with)
+    EMO_SPLIT_BARRIER(0);                    // (P[0] visible)
   }
 
   // ---- K loop, two stages per iteration (buffer parities and fragment sets are compile-time constants) ----
@@ -306,8 +257,8 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
       for (int j = 0; j < TP; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc_lo[c][i][j][r] = 0.0f; acc_hi[c][i][j][r] = 0.0f; }
-  EMO_P_LOAD_A(0, 0, 0, 0)
-  EMO_P_LOAD_B(0, 0)
+  EMO_P1_LOAD_A(0, 0, 0, 0)
+  EMO_P1_LOAD_B(0, 0)
   for (int cg0 = 0; cg0 < nst; cg0 += 2) {
 #pragma unroll
     for (int par = 0; par < 2; ++par) {
@@ -318,15 +269,15 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
       const bool nx1_ = EMO_S_CHAIN && par == 1 && chain_out && cg + 1 >= nst;
       const int k1_ = nx1_ ? 0 : ((cg + 1) < nst ? cg + 1 : nst - 1);
       const int c1_ = nx1_ ? nx_cotile : it_cotile;
-      const char* const dma0 = EMO_P_WPTR(c1_, k1_);
-      const char* const dma1 = EMO_P_WPTR(c1_ + 1, k1_);
+      const char* const dma0 = EMO_P1_WPTR(c1_, k1_);
+      const char* const dma1 = EMO_P1_WPTR(c1_ + 1, k1_);
       if (EMO_CONV_SETPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int gs = 0; gs < 4; ++gs) {
         const int h = gs >> 1, ks = gs & 1;
         const int fcur = gs & 1, fnxt = fcur ^ 1;          // (weight fragment sets alternate by step; four steps per stage)
-        if (gs == 3) { EMO_P_BARRIER(0); }
-        if (gs == 3) EMO_P_TOUCH_QUAD(par)                  // (the loads of stage cg + 2 have landed behind the barrier)
+        if (gs == 3) { EMO_SPLIT_BARRIER(0); }
+        if (gs == 3) EMO_P1_TOUCH_QUAD(par)                  // (the loads of stage cg + 2 have landed behind the barrier)
         if (gs == 0) {
           // the patch loads of stage cg + 2; chained item: past its end the next item's stages 0 / 1 (the cursor moves on in a
           // stage of parity 0: stage counts of chained items are even)
@@ -335,24 +286,24 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
           lq_off = sw_ ? nxq_off : lq_off;
           lq_z0 = sw_ ? nx_z0 : lq_z0;
           ld_stage = sw_ ? 0 : tgt_;
-          EMO_P_ISSUE_BEGIN(par)
+          EMO_P1_ISSUE_BEGIN(par)
         }
         __builtin_amdgcn_sched_barrier(0);
         // fragments of the next step: weights of (h', k') = step gs + 1 -- of the next stage's step 0 behind the barrier -- and, in
         // steps 0 and 3, the patch fragments of the k-step that comes next
-        if (gs < 3) { EMO_P_LOAD_A(fnxt, par, (gs + 1) >> 1, (gs + 1) & 1) } else { EMO_P_LOAD_A(fnxt, par ^ 1, 0, 0) }
-        if (gs == 0) { EMO_P_LOAD_B(par, 1) }
-        if (gs == 3) { EMO_P_LOAD_B(par ^ 1, 0) }
-        if (gs == 0) EMO_P_ISSUE_LOADS(par)
+        if (gs < 3) { EMO_P1_LOAD_A(fnxt, par, (gs + 1) >> 1, (gs + 1) & 1) } else { EMO_P1_LOAD_A(fnxt, par ^ 1, 0, 0) }
+        if (gs == 0) { EMO_P1_LOAD_B(par, 1) }
+        if (gs == 3) { EMO_P1_LOAD_B(par ^ 1, 0) }
+        if (gs == 0) EMO_P1_ISSUE_LOADS(par)
         if (gs == 1) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) EMO_P_DMA_PIECE(dma0, dma1, par ^ 1, k)
+          for (int k = 0; k < 4; ++k) EMO_P1_DMA_PIECE(dma0, dma1, par ^ 1, k)
         }
         // conversion of the patch of stage cg + 1: units 0 .. 7 = (pixel, half), 3 + 3 + 2 over steps 0 .. 2
-        if (gs == 0) { EMO_P_CONV_HALF(par ^ 1, par ^ 1, 0, 0) EMO_P_CONV_HALF(par ^ 1, par ^ 1, 0, 1) EMO_P_CONV_HALF(par ^ 1, par ^ 1, 1, 0) }
-        if (gs == 1) { EMO_P_CONV_HALF(par ^ 1, par ^ 1, 1, 1) EMO_P_CONV_HALF(par ^ 1, par ^ 1, 2, 0) EMO_P_CONV_HALF(par ^ 1, par ^ 1, 2, 1) }
-        if (gs == 2) { EMO_P_CONV_HALF(par ^ 1, par ^ 1, 3, 0) EMO_P_CONV_HALF(par ^ 1, par ^ 1, 3, 1) }
-        if (gs == 3) { EMO_P_TABLES(par) }                  // (what the next stage converts with: the loads issued in this one)
+        if (gs == 0) { EMO_P1_CONV_HALF(par ^ 1, par ^ 1, 0, 0) EMO_P1_CONV_HALF(par ^ 1, par ^ 1, 0, 1) EMO_P1_CONV_HALF(par ^ 1, par ^ 1, 1, 0) }
+        if (gs == 1) { EMO_P1_CONV_HALF(par ^ 1, par ^ 1, 1, 1) EMO_P1_CONV_HALF(par ^ 1, par ^ 1, 2, 0) EMO_P1_CONV_HALF(par ^ 1, par ^ 1, 2, 1) }
+        if (gs == 2) { EMO_P1_CONV_HALF(par ^ 1, par ^ 1, 3, 0) EMO_P1_CONV_HALF(par ^ 1, par ^ 1, 3, 1) }
+        if (gs == 3) { EMO_P1_TABLES(par) }                  // (what the next stage converts with: the loads issued in this one)
 #pragma unroll
         for (int p = 0; p < NPROD; ++p) {
           const int pa = PA3[p], pb = PB3[p];
@@ -390,29 +341,24 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
     float* const scratch = smem + (Cfg::OFF_P + last_par * PBUF) * 4 + wave * Cfg::EPI_WAVE;
     const int ep_n = it_n, ep_cotile = it_cotile, ep_ptile = it_ptile, ep_x0 = it_x0, ep_y0 = it_y0, ep_z0 = it_z0;
     const bool second = ep_cotile + 1 < n_cot_all;          // (an odd count of channel tiles: the last pair's second half is padding)
-    EMO_P_WAIT(0);
+    EMO_SPLIT_WAIT(0);
     __syncthreads();
     if (EMO_S_CHAIN && chain_out && tid < 2 * BM && a.bias != nullptr) {
       const int co_ = nx_cotile * BM + tid;
       te_b = a.bias[co_ < a.Cout ? co_ : a.Cout - 1];
     }
-#define EMO_P_EPI_FAST(RES_)                                                                                                      \
-    {                                                                                                                              \
-      floatx4 rv_[8], rvn_[8];                                                                                                     \
-      conv_epilogue_fast_issue<TW, TP, BM, RES_, 0, true>(a, rv_, ep_n, ep_cotile, ep_x0, ep_y0, ep_z0, wp, lane);                 \
-      if (second) conv_epilogue_fast_issue<TW, TP, BM, RES_, 0, true>(a, rvn_, ep_n, ep_cotile + 1, ep_x0, ep_y0, ep_z0, wp, lane); \
-      conv_epilogue_fast_finish<TW, TM, TP, WGP, BM, SPLIT, Cfg::EPI_ROWF, RES_, true, true>(                                      \
-          a, acc_lo[0], acc_hi[0], rv_, scratch, smem + Cfg::OFF_BIAS_F, smem + Cfg::OFF_STAT_F, ep_n, ep_cotile, ep_ptile, ep_x0,  \
-          ep_y0, ep_z0, wp, half, l32, lane, tid);                                                                                 \
-      if (second)                                                                                                                  \
-        conv_epilogue_fast_finish<TW, TM, TP, WGP, BM, SPLIT, Cfg::EPI_ROWF, RES_, true, true>(                                    \
-            a, acc_lo[1], acc_hi[1], rvn_, scratch, smem + Cfg::OFF_BIAS2_F, smem + Cfg::OFF_STAT2_F, ep_n, ep_cotile + 1,          \
-            ep_ptile, ep_x0, ep_y0, ep_z0, wp, half, l32, lane, tid);                                                              \
+#define EMO_P1_EPI_FAST(RES_)                                                                         \
+    {                                                                                                 \
+      floatx4 rv_[8], rvn_[8];                                                                        \
+      EMO_SPLIT_EPI_ISSUE(RES_, true, rv_, ep_cotile)                                                 \
+      if (second) EMO_SPLIT_EPI_ISSUE(RES_, true, rvn_, ep_cotile + 1)                                \
+      EMO_SPLIT_EPI_FINISH(RES_, true, acc_lo[0], acc_hi[0], rv_, Cfg::OFF_BIAS_F, Cfg::OFF_STAT_F, ep_cotile, EMO_SPLIT_NO_STAMPS) \
+      if (second) EMO_SPLIT_EPI_FINISH(RES_, true, acc_lo[1], acc_hi[1], rvn_, Cfg::OFF_BIAS2_F, Cfg::OFF_STAT2_F, ep_cotile + 1, EMO_SPLIT_NO_STAMPS) \
     }
-    if (epi_mode == 1) EMO_P_EPI_FAST(1)
-    else if (epi_mode == 2) EMO_P_EPI_FAST(2)
-    else EMO_P_EPI_FAST(0)
-#undef EMO_P_EPI_FAST
+    if (epi_mode == 1) EMO_P1_EPI_FAST(1)
+    else if (epi_mode == 2) EMO_P1_EPI_FAST(2)
+    else EMO_P1_EPI_FAST(0)
+#undef EMO_P1_EPI_FAST
   }
   if (a.sat_flag != nullptr && sat_m > 65504.0f) *a.sat_flag = 1;
   __syncthreads();
@@ -438,19 +384,16 @@ void conv_igemm_bf16x3_p1_kernel(const ConvArgs a) {
   }
   chained_in = chain_out;
   }
-#undef EMO_P_DECODE
-#undef EMO_P_WPTR
-#undef EMO_P_CURSOR_OF
-#undef EMO_P_LOAD_A
-#undef EMO_P_LOAD_B
-#undef EMO_P_ISSUE_BEGIN
-#undef EMO_P_ISSUE_LOADS
-#undef EMO_P_TABLES
-#undef EMO_P_TOUCH_QUAD
-#undef EMO_P_CONV_HALF
-#undef EMO_P_DMA_PIECE
-#undef EMO_P_WAIT
-#undef EMO_P_BARRIER
+#undef EMO_P1_WPTR
+#undef EMO_P1_CURSOR_OF
+#undef EMO_P1_LOAD_A
+#undef EMO_P1_LOAD_B
+#undef EMO_P1_ISSUE_BEGIN
+#undef EMO_P1_ISSUE_LOADS
+#undef EMO_P1_TABLES
+#undef EMO_P1_TOUCH_QUAD
+#undef EMO_P1_CONV_HALF
+#undef EMO_P1_DMA_PIECE
 }
 
 // Host side.  EMO_ERR_UNSUPPORTED for anything but the launch form of the header comment: the caller (conv_api.hip) reports it,

@@ -25,11 +25,10 @@
 // an 8-lane butterfly per 32-position pass, which is the first three levels of the 16-lane butterfly of conv_epilogue_fast_finish,
 // and the two passes are added as its fourth level adds the halves: the three kernels are BIT-IDENTICAL, output, statistics and
 // overflow word (tests/test_conv_bf16x3_gpu.py, tests/test_conv_split_emul.py).
-// Launch: conv_f16x2_w8_launch() behind the gate it shares with conv_f16x2_ct2_launch() (conv_split_pair_common.h);
+// Launch: conv_f16x2_w8_launch() behind the gate it shares with conv_f16x2_ct2_launch() (conv_split_common.h);
 // EMO_CONV_W8=0 leaves the pairs to the one-wave-per-SIMD kernel (A/B).
 #pragma once
 #include "conv_igemm_bf16x3.h"
-#include "conv_split_pair_common.h"
 
 #ifndef EMO_W8_EARLY_LOADS
 #define EMO_W8_EARLY_LOADS 1   /* 0: A/B builds (loads of stage cg + 2 in half-stage 1, as the fp16 split) */
@@ -224,10 +223,7 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l32 = lane & 31;
+  EMO_SPLIT_THREAD_IDS()
   const int wp = wave & 3;                               // position group
   const int ch = wave >> 2;                              // channel half of both tiles; also the 4-channel half this wave stages
   const int p0 = wp * TP * 32;
@@ -247,32 +243,14 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
   const int n_cot_all = a.Cout / BM;                     // channel tiles of the layer (an odd count only with NPROD = 1)
 
   // ---- staging map: the 256 threads of a channel half (waves 0-3 / 4-7) are two 8-channel groups of 128 lanes, mapped onto the
-  //      interior quads and halo pixels of the patch exactly as the 256 threads of conv_igemm_bf16x3.h; a thread stages the four
+  //      interior quads and halo pixels of the patch by the shared staging map (conv_split_common.h); a thread stages the four
   //      channels 4 ch .. 4 ch + 3 of its group's eight: bytes 8 ch .. 8 ch + 7 of the 16-byte slots ----
-  const int q_u = tid % QPG;
-  const int q_g = __builtin_amdgcn_readfirstlane((tid / QPG) & 1);
-  const bool is_quad = q_u < PR * NQ;
-  const int hq = q_u - PR * NQ;
-  const bool is_halo = !is_quad && hq < NHQ;
-  const int h_side = hq & 1;
-  const int q_r = is_quad ? q_u / NQ : (is_halo ? hq >> 1 : 0);
-  const int q_c = is_quad ? q_u - q_r * NQ : 0;
-  int q_slb[4];                                           // byte offsets of the lane's four staging half-slots inside a patch buffer
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int dump = q_g * CHS + i * SUB + PR * NQ1 + (q_u & 3);
-    const int own = is_quad ? q_g * CHS + i * SUB + q_r * NQ1 + q_c : q_g * CHS + h_side * SUB + q_r * NQ1 + NQ;
-    q_slb[i] = ((is_quad || (is_halo && i == (h_side ? 0 : 3))) ? own : dump) * 16 + ch * 8;
-  }
+  EMO_SPLIT_STAGING_MAP((tid / QPG) & 1, ch * 8)
 
   floatx16 acc_lo[2][TP], acc_hi[2][TP];                 // [channel tile of the pair][position tile]: 128 accumulation registers
 
   // ---- work items: (sample, position tile, channel-tile PAIR), XCD-contiguous, pair fastest; persistent blocks ----
-  const int q8 = a.n_work >> 3, r8 = a.n_work & 7;
-  const int xcd = blockIdx.x & 7;
-  const int n_mine = q8 + (xcd < r8 ? 1 : 0);
-  const int l_base = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int l_stride = (gridDim.x + 7) >> 3;
+  EMO_SPLIT_ITEM_WALK()
   int it_cotile = 0, it_n = 0, it_ptile = 0, it_x0 = 0, it_y0 = 0, it_z0 = 0;
   unsigned lq_off = 0;
   bool lq_ok = false;
@@ -282,12 +260,11 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
 #define EMO_W_WPTR(c_, k_) (reinterpret_cast<const char*>(a.wpk) + \
                             (long)(((c_) < n_cot_all ? (c_) : n_cot_all - 1) * nst + (k_)) * (NCHK * 1024))
 
-  // LDS byte offsets of the lane's operands (conv_igemm_f16x2_ct2.h): the wave's weight rows are ch * 32 + l32 of the tile's 64
+  // LDS byte offsets of the lane's operands (conv_split_common.h): the wave's weight rows are ch * 32 + l32 of the tile's 64
   const int a_off = (half * BM + ch * 32 + l32) * 16;
-  EMO_P_DECLARE_B_OFF()
+  EMO_SPLIT_DECLARE_B_OFF()
 
-  const char* const lds_c = reinterpret_cast<const char*>(smem);
-  char* const lds_w = reinterpret_cast<char*>(smem);
+  EMO_SPLIT_LDS_VIEWS()
   opx8 fa_[2][NPL], fb_[2][NPL][TP];         // [register set: this step / the next][plane]([position tile])
 // (wbase_: slots, compile-time; pbyte_: byte offset of the patch buffer, run-time)
 // (a kernel row of a stage buffer holds NPL planes: rows are NPL * WPLANE slots apart)
@@ -295,12 +272,10 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
   {                                                                                                   \
     fa_[set_][pl_] = *reinterpret_cast<const opx8*>(lds_c + a_off + ((wbase_) + (pl_) * WPLANE + (s_) * 2 * BM) * 16); \
     _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                    \
-      fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + (EMO_P_B_OFF(j, r_, s_) + (pbyte_)) + ((pl_) * PPL) * 16); \
+      fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + (EMO_SPLIT_B_OFF(j, r_, s_) + (pbyte_)) + ((pl_) * PPL) * 16); \
   }
 
-  float* const sct = smem + Cfg::OFF_SCT * 4;
-  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(smem);
-  const unsigned lane16 = (unsigned)lane * 16u;
+  EMO_SPLIT_LDS_TABLES_ADDR()
 
   // raw patch registers: ONE buffer of four channel planes -- converted during half-stage 0, reloaded during half-stage 1
   floatx4 qv[NKB][4];
@@ -308,9 +283,7 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
   int q_tix[NKB];
   floatx4 q_sc[NKB], q_sh[NKB];
   emo_intx4 xrs = emo_raw_buffer(a.x);
-  unsigned usoff[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) usoff[u] = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(4 * ch + u) * (unsigned)DHW * 4u * (EMO_CT2_X_CONST ? 0u : 1u)));
+  EMO_SPLIT_USOFF(4, 4 * ch, DHW, (EMO_CT2_X_CONST ? 0u : 1u))
 
   int n_ci0, n_zu;
   bool n_zv;
@@ -325,47 +298,28 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
 #define EMO_W_ISSUE_BEGIN()                                                                           \
   {                                                                                                   \
     _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) {                                              \
-      const int c0_ = n_ci0 + 16 * kb + q_g * 8;                                                      \
-      const bool cv_ = c0_ < a.Cin;                                                                   \
-      const int cs_ = cv_ ? c0_ : 0;                                                                  \
-      const bool keep_ = lq_ok && cv_ && n_zv;                                                        \
-      q_lo[kb] = keep_ ? clamp_lo : 0.0f;                                                             \
-      q_hi[kb] = keep_ ? CLAMP_HI : 0.0f;                                                             \
-      q_vo[kb] = lq_off + (EMO_CT2_X_CONST ? 0u : ((unsigned)cs_ * (unsigned)DHW + (unsigned)((n_zv ? n_zu : 0) * HW)) * 4u);  \
-      q_tix[kb] = ((has_affine ? cs_ : (cs_ & (Cfg::SCT - 1))) >> 2) + ch;                            \
+      EMO_SPLIT_ISSUE_BEGIN([kb], q_vo[kb], n_ci0 + 16 * kb + q_g * 8, lq_ok && cv_ && n_zv,          \
+                            (EMO_CT2_X_CONST ? 0u : ((unsigned)cs_ * (unsigned)DHW + (unsigned)((n_zv ? n_zu : 0) * HW)) * 4u))  \
+      q_tix[kb] += ch;                                                                                \
     }                                                                                                 \
   }
 // paired load v_ = 0 .. 2 NKB - 1 of a stage: channel planes 2 (v_ & 1), 2 (v_ & 1) + 1 of k-block v_ >> 1
-#define EMO_W_ISSUE_LOADS(v_)                                                                         \
-  { emo_bload4x2_pinned(xrs, q_vo[(v_) >> 1], usoff[2 * ((v_) & 1)], usoff[2 * ((v_) & 1) + 1], qv[(v_) >> 1][2 * ((v_) & 1)],  \
-                        qv[(v_) >> 1][2 * ((v_) & 1) + 1]); }
-#define EMO_W_TABLE()                                                                                 \
-  {                                                                                                   \
-    _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) {                                              \
-      const floatx4* t4_ = reinterpret_cast<const floatx4*>(sct) + q_tix[kb];                         \
-      q_sc[kb] = t4_[0]; q_sh[kb] = t4_[Cfg::SCT / 4];                                                \
-    }                                                                                                 \
-  }
-#define EMO_W_TOUCH_QUAD() { _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) _Pragma("unroll") for (int u = 0; u < 4; ++u) emo_touch4(qv[kb][u]); }
-// conversion of the lane's four channels (of k-block kb_) of pixel i_ (conv_igemm_bf16x3.h, SPLIT = 2); pbyte_: byte offset of the
-// target patch buffer.  NPROD = 3: both planes of the one k-block; NPROD = 1: the fp16 value into plane kb_
+#define EMO_W_ISSUE_LOADS(v_) EMO_SPLIT_ISSUE_LOADS(qv[(v_) >> 1], q_vo[(v_) >> 1], 2 * ((v_) & 1), 2 * ((v_) & 1) + 2)
+#define EMO_W_TABLE() { _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) EMO_SPLIT_TABLE(q_tix[kb], q_sc[kb], q_sh[kb]) }
+#define EMO_W_TOUCH_QUAD() { _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) EMO_SPLIT_TOUCH(qv[kb], 4) }
+// conversion of the lane's four channels (of k-block kb_) of pixel i_ (conv_split_common.h); pbyte_: byte offset of the target
+// patch buffer.  NPROD = 3: both planes of the one k-block; NPROD = 1: the fp16 value into plane kb_
 #define EMO_W_CONV_UNIT(pbyte_, i_, kb_)                                                              \
   {                                                                                                   \
-    float t_[4];                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                     \
-      t_[k] = __fmaf_rn(qv[kb_][k][i_], q_sc[kb_][k], q_sh[kb_][k]);                                  \
+    EMO_SPLIT_AFFINE4(t_, qv[kb_], 0, i_, q_sc[kb_], q_sh[kb_])                                       \
     if constexpr (NPROD == 3) {                                                                       \
-      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[0])), __builtin_fabsf(t_[1])); \
-      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[2])), __builtin_fabsf(t_[3])); \
+      EMO_SPLIT_RANGE4(t_)                                                                            \
     }                                                                                                 \
     halfx4 cvh_, cvm_;                                                                                \
-    _Pragma("unroll") for (int k = 0; k < 4; k += 2)                                                  \
-      emo_split_f16x2_pair(__builtin_amdgcn_fmed3f(t_[k], q_lo[kb_], q_hi[kb_]),                      \
-                           __builtin_amdgcn_fmed3f(t_[k + 1], q_lo[kb_], q_hi[kb_]), cvh_, cvm_, k);  \
+    EMO_SPLIT_F16X2_4(t_, q_lo[kb_], q_hi[kb_], cvh_, cvm_, 0)                                        \
     char* d_ = lds_w + (q_slb[i_] + (pbyte_));                                                        \
     if constexpr (NPROD == 3) {                                                                       \
-      *reinterpret_cast<halfx4*>(d_) = cvh_;                                                          \
-      *reinterpret_cast<halfx4*>(d_ + PPL * 16) = cvm_;                                               \
+      EMO_SPLIT_STORE_PLANES(halfx4, d_, cvh_, cvm_)                                                  \
     } else {                                                                                          \
       *reinterpret_cast<halfx4*>(d_ + (kb_) * PPL * 16) = cvh_;                                       \
     }                                                                                                 \
@@ -399,14 +353,14 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
   for (int k = 0; k < 12; ++k) tstamp[k] = 0;
 #endif
   EMO_S_STAMP(0)
-  EMO_P_DECODE(it_, l_base + idx8)
+  EMO_SPLIT_DECODE(it_, l_base + idx8, a.cot0 + 2 * cot_, )
   int nx_cotile = 0, nx_n = 0, nx_ptile = 0, nx_x0 = 0, nx_y0 = 0, nx_z0 = 0;
   bool chain_out = false, nxq_ok = false;
   unsigned nxq_off = 0;
   if (EMO_S_CHAIN && idx8 + l_stride < n_mine) {
-    EMO_P_DECODE(nx_, l_base + idx8 + l_stride)
+    EMO_SPLIT_DECODE(nx_, l_base + idx8 + l_stride, a.cot0 + 2 * cot_, )
     chain_out = nx_n == it_n && nst >= 2;
-    EMO_P_CURSOR_OF(nx_, nxq_ok, nxq_off)
+    EMO_SPLIT_CURSOR_OF(nx_, nxq_ok, nxq_off)
   }
   (void)nx_ptile;
   // (declared dead here: conv_igemm_bf16x3.h)
@@ -434,7 +388,7 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
     const char* const w1_ = EMO_W_WPTR(it_cotile + 1, 0);
     EMO_W_DMA_CHUNK(w1_, EMO_W_WBUF(1), 0)
     EMO_W_TABLE()
-    EMO_P_BARRIER(1);
+    EMO_SPLIT_BARRIER(1);
   } else {
     // ---- full prologue: tables, the chunks of (c0, stage 0), the patch of stage 0 converted into P[0], the loads of stage 1 ----
 #pragma unroll
@@ -442,7 +396,7 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) asm volatile("" : "=v"(qv[kb][u]));
     xrs = emo_raw_buffer(a.x + (long)it_n * a.Cin * DHW);
-    EMO_P_CURSOR_OF(it_, lq_ok, lq_off)
+    EMO_SPLIT_CURSOR_OF(it_, lq_ok, lq_off)
     lq_z0 = it_z0;
 #pragma unroll
     for (int k = 0; k < NTE; ++k) {
@@ -477,7 +431,7 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
       const int t2_ = tid & (BM - 1);
       smem[(tid < BM ? Cfg::OFF_BIAS_F : Cfg::OFF_BIAS2_F) + EMO_W_BIAS_SLOT(t2_)] = te_b;
     }
-    EMO_P_WAIT(0);
+    EMO_SPLIT_WAIT(0);
     EMO_W_TOUCH_QUAD()
     __syncthreads();   // scale / shift tables visible
     EMO_W_TABLE()
@@ -498,7 +452,7 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
       const char* const w1_ = EMO_W_WPTR(it_cotile + 1, 0);
       EMO_W_DMA_CHUNK(w1_, EMO_W_WBUF(1), 0)
     }
-    EMO_P_BARRIER(0);                    // (P[0] visible, W[0] and the loads of stage 1 landed)
+    EMO_SPLIT_BARRIER(0);                    // (P[0] visible, W[0] and the loads of stage 1 landed)
     EMO_W_TOUCH_QUAD()
     pp = 0;
   }
@@ -542,7 +496,7 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
         const int fcur = (h * 9 + gs) & 1, fnxt = fcur ^ 1;
         if (gs == 8) {
           // (EARLY: the patch loads issued in this half-stage 0 -- 2 NKB pairs, younger than its weight chunks -- stay in flight)
-          if (EARLY && h == 0) { EMO_P_BARRIER(4 * NKB); } else { EMO_P_BARRIER(0); }
+          if (EARLY && h == 0) { EMO_SPLIT_BARRIER(4 * NKB); } else { EMO_SPLIT_BARRIER(0); }
         }
         if (gs == 8 && h == 1) EMO_W_TOUCH_QUAD()          // (the loads of stage cg + 2 have landed behind the barrier)
         if (EARLY ? (gs == ESTEPS && h == 0) : (gs == 0 && h == 1)) {
@@ -639,7 +593,7 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
     float* const scratch = smem + (Cfg::OFF_W + Cfg::WSTAGE) * 4 + wave * Cfg::EPI_WAVE8;
     const int ep_n = it_n, ep_cot32 = 2 * it_cotile + ch, ep_x0 = it_x0, ep_y0 = it_y0, ep_z0 = it_z0;
     const bool has_t1 = NPROD == 3 || it_cotile + 1 < n_cot_all;      // (false: the half-empty last pair of an odd tile count)
-    EMO_P_WAIT(0);
+    EMO_SPLIT_WAIT(0);
     EMO_S_STAMP(5)
     __syncthreads();
     EMO_S_STAMP(6)
@@ -694,9 +648,9 @@ void conv_igemm_f16x2_w8_kernel(const ConvArgs a) {
 #endif
   // the next prologue overwrites the tables and W[1]: every wave must be out of the epilogue first
   __syncthreads();
-  // tile statistics, second half (conv_igemm_f16x2_ct2.h): thread c of the first 128 combines the four position groups' (mean, M2)
+  // tile statistics, second half (conv_split_common.h): thread c of the first 128 combines the four position groups' (mean, M2)
   // of channel c with the equal-count update
-  EMO_P_COMBINE_STATS(Cfg::OFF_STAT_F, Cfg::OFF_STAT2_F, it_cotile * BM + tid < a.Cout)
+  EMO_SPLIT_COMBINE_STATS(Cfg::OFF_STAT_F, Cfg::OFF_STAT2_F, it_cotile * BM + tid < a.Cout)
   chained_in = chain_out;
   }
 #undef EMO_W_WPTR

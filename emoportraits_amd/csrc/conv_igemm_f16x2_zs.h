@@ -64,7 +64,7 @@ struct ConvCfgZ {
 // convert(i), i = 0 .. 3: the conversion of pixel i of the NEXT stage's patch (registers to registers), placed in steps 5 .. 8 --
 // 45 vector instructions beside 18 MFMAs: inside the five an MFMA gap hides
 template <int KD0, int KD1, typename F>
-__device__ __forceinline__ void conv_zs_mma(const char* lds_c, int w_off, const int (&b_off)[2][3],
+__device__ __forceinline__ void conv_zs_mma(const char* lds_c, int w_off, const int (&b_off)[2][1][3],
                                             floatx16 (&lo0)[1][2], floatx16 (&hi0)[1][2], floatx16 (&lo1)[1][2],
                                             floatx16 (&hi1)[1][2], floatx16 (&lo2)[1][2], floatx16 (&hi2)[1][2], F&& convert) {
   using Cfg = ConvCfgZ;
@@ -76,7 +76,7 @@ __device__ __forceinline__ void conv_zs_mma(const char* lds_c, int w_off, const 
   {                                                                                                                   \
     _Pragma("unroll") for (int pl = 0; pl < 2; ++pl)                                                                  \
       _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                   \
-        fb[set_][pl][j] = *reinterpret_cast<const halfx8*>(lds_c + b_off[j][s_] + ((r_) * S::NQ1 + Cfg::OFF_P + pl * S::PPL) * 16); \
+        fb[set_][pl][j] = *reinterpret_cast<const halfx8*>(lds_c + b_off[j][0][s_] + ((r_) * S::NQ1 + Cfg::OFF_P + pl * S::PPL) * 16); \
     _Pragma("unroll") for (int k = 0; k < NK; ++k)                                                                    \
       _Pragma("unroll") for (int pl = 0; pl < 2; ++pl)                                                                \
         fa[set_][k][pl] = *reinterpret_cast<const halfx8*>(lds_c + w_off + ((KD0 + k) * Cfg::WST + (r_) * S::WROW + pl * S::WPLANE + (s_) * 2 * Cfg::BM) * 16); \
@@ -125,12 +125,13 @@ __device__ __forceinline__ void conv_f16x2_zs_body(const ConvArgs& a, float* sme
   using S = Cfg::S;
   constexpr int BM = Cfg::BM, TP = Cfg::TP, WGP = Cfg::WGP, KC = Cfg::KC, TW = Cfg::TW, TR = Cfg::TR;
   constexpr int PR = S::PR, NQ = S::NQ, NQ1 = S::NQ1, SUB = S::SUB, CHS = S::CHS, QPG = S::QPG, NHQ = S::NHQ, PPL = S::PPL;
+  // (names of the shared macros, conv_split_common.h: no upsampling gather; one 32-channel tile of the fp16 split)
+  constexpr bool UPS = false;
+  constexpr int TWS = TW, TM = 1, SPLIT = 2;
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l32 = lane & 31;
+  EMO_SPLIT_THREAD_IDS()
   const int wp = wave;
+  const int p0 = wp * TP * 32;
   float sat_m = 0.0f;                                    // largest |scaled staged value| this thread has seen
 
   const int HW = a.H * a.W;
@@ -146,45 +147,15 @@ __device__ __forceinline__ void conv_f16x2_zs_body(const ConvArgs& a, float* sme
   const int ncc = a.n_cchunks;
   const int nruns = (a.D + a.zrun - 1) / a.zrun;
 
-  // ---- staging map of conv_igemm_bf16x3_kernel: thread t belongs to channel group t / QPG; lane u < PR * NQ of the group owns
-  //      interior quad u, lane PR * NQ + 2 * row + side one halo pixel (it loads the aligned quad that contains it; the three
-  //      pixels it does not own go to dump slots) ----
-  const int q_u = tid % QPG;
-  const int q_g = __builtin_amdgcn_readfirstlane(tid / QPG);
-  const bool is_quad = q_u < PR * NQ;
-  const int hq = q_u - PR * NQ;
-  const bool is_halo = !is_quad && hq < NHQ;
-  const int h_side = hq & 1;
-  const int q_r = is_quad ? q_u / NQ : (is_halo ? hq >> 1 : 0);
-  const int q_c = is_quad ? q_u - q_r * NQ : 0;
-  int q_slb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int dump = q_g * CHS + i * SUB + PR * NQ1 + (q_u & 3);
-    const int own = is_quad ? q_g * CHS + i * SUB + q_r * NQ1 + q_c : q_g * CHS + h_side * SUB + q_r * NQ1 + NQ;
-    q_slb[i] = ((is_quad || (is_halo && i == (h_side ? 0 : 3))) ? own : dump) * 16;
-  }
-  // fragment offsets (bytes): weight fragment of the lane, and for every tap column the patch slot of its two output pixels
+  // ---- staging map, fragment offsets (bytes): weight fragment of the lane, and for every tap column the patch slot of its two
+  //      output pixels (conv_split_common.h) ----
+  EMO_SPLIT_STAGING_MAP(tid / QPG, 0)
   const int a_off = (half * BM + l32) * 16;
-  int b_off[2][3];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int p = wp * TP * 32 + j * 32 + l32;
-    const int col = p % TW, row = p / TW;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      const int pc = col + s - 1;
-      const int slot = pc < 0 ? row * NQ1 + NQ : (pc >= TW ? SUB + row * NQ1 + NQ : (pc & 3) * SUB + row * NQ1 + (pc >> 2));
-      b_off[j][s] = (half * CHS + slot) * 16;
-    }
-  }
-  const char* const lds_c = reinterpret_cast<const char*>(smem);
-  char* const lds_w = reinterpret_cast<char*>(smem);
-  float* const sct = smem + Cfg::OFF_SCT * 4;
+  EMO_SPLIT_DECLARE_B_OFF()
+  EMO_SPLIT_LDS_VIEWS()
+  float* const sct = smem + Cfg::OFF_SCT * 4;         // (EMO_SPLIT_LDS_TABLES_ADDR without smem_lds, a parameter here)
   const unsigned lane16 = (unsigned)lane * 16u;
-  unsigned usoff[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) usoff[u] = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)u * (unsigned)DHW * 4u));
+  EMO_SPLIT_USOFF(8, 0, DHW, 1u)
 
   floatx4 qv[8];                 // the raw patch of the next stage: 8 channels x one quad
   halfx8 cv_h[4], cv_m[4];       // ... converted: the two planes of its four pixels
@@ -209,11 +180,9 @@ __device__ __forceinline__ void conv_f16x2_zs_body(const ConvArgs& a, float* sme
     const int zi_last = min(zb + nout, a.D - 1);            // input slices max(zb - 1, 0) .. zi_last
     const int zi_first = zb > 0 ? zb - 1 : 0;
 
-    // the lane's 16-byte patch load (its quad, or the aligned quad that contains its halo pixel) and whether it lies in the image
-    const int q_y = it_y0 - 1 + q_r;
-    const int q_x = is_quad ? it_x0 + 4 * q_c : (h_side ? it_x0 + TW : it_x0 - 4);
-    const bool lq_ok = (is_quad || is_halo) && (unsigned)q_y < (unsigned)a.H && q_x >= 0 && q_x < a.W;
-    const unsigned lq_off = lq_ok ? (unsigned)(q_y * a.W + q_x) * 4u : 0u;
+    bool lq_ok;
+    unsigned lq_off;
+    EMO_SPLIT_CURSOR_OF(it_, lq_ok, lq_off)
     const emo_intx4 xrs = emo_raw_buffer(a.x + (long)it_n * a.Cin * DHW);
     const char* const wsrc = reinterpret_cast<const char*>(a.wpk) + (long)it_cotile * ncc * (Cfg::WCH * 16);
 
@@ -233,24 +202,16 @@ __device__ __forceinline__ void conv_f16x2_zs_body(const ConvArgs& a, float* sme
     q_hi = keep_ ? CLAMP_HI : 0.0f;                                                                                   \
     q_tix = cs_ >> 2;                                                                                                 \
     const unsigned q_vo = lq_off + ((unsigned)cs_ * (unsigned)DHW + (unsigned)((zi_) * HW)) * 4u;                     \
-    _Pragma("unroll") for (int u = 0; u < 8; u += 2) emo_bload4x2_pinned(xrs, q_vo, usoff[u], usoff[u + 1], qv[u], qv[u + 1]); \
+    EMO_SPLIT_ISSUE_LOADS(qv, q_vo, 0, 8)                                                                             \
   }
-// qv -> registers: fp32 transform (affine of the producer; ReLU, saturation and zero padding in one v_med3: bounds [0, 0] where
-// the pixel is padding), range check, the exact split into two fp16 planes -- pixel i_ of the lane's four
+// qv -> registers: pixel i_ of the lane's four through the conversion core (conv_split_common.h)
 #define EMO_Z_CONVERT_PX(i_)                                                                                          \
   {                                                                                                                   \
-    if ((i_) == 0) {    /* scale / shift of the lane's eight channels: read once per stage */                         \
-      const floatx4* t4_ = reinterpret_cast<const floatx4*>(sct) + q_tix;                                             \
-      q_sc[0] = t4_[0]; q_sc[1] = t4_[1]; q_sh[0] = t4_[Cfg::SCT / 4]; q_sh[1] = t4_[Cfg::SCT / 4 + 1];               \
-    }                                                                                                                 \
+    if ((i_) == 0) EMO_SPLIT_TABLE2(q_tix, q_sc, q_sh)    /* scale / shift of the lane's eight channels: read once per stage */ \
     _Pragma("unroll") for (int hf = 0; hf < 2; ++hf) {                                                                \
-      float t_[4];                                                                                                    \
-      _Pragma("unroll") for (int k = 0; k < 4; ++k) t_[k] = __fmaf_rn(qv[4 * hf + k][i_], q_sc[hf][k], q_sh[hf][k]);  \
-      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[0])), __builtin_fabsf(t_[1]));                \
-      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[2])), __builtin_fabsf(t_[3]));                \
-      _Pragma("unroll") for (int k = 0; k < 4; k += 2)                                                                \
-        emo_split_f16x2_pair(__builtin_amdgcn_fmed3f(t_[k], q_lo, q_hi), __builtin_amdgcn_fmed3f(t_[k + 1], q_lo, q_hi), \
-                             cv_h[i_], cv_m[i_], 4 * hf + k);                                                         \
+      EMO_SPLIT_AFFINE4(t_, qv, 4 * hf, i_, q_sc[hf], q_sh[hf])                                                       \
+      EMO_SPLIT_RANGE4(t_)                                                                                            \
+      EMO_SPLIT_F16X2_4(t_, q_lo, q_hi, cv_h[i_], cv_m[i_], 4 * hf)                                                   \
     }                                                                                                                 \
   }
 // the converted pixels -> P (every lane stores all four pixels of its loads: its own, or into dump slots)
@@ -258,11 +219,10 @@ __device__ __forceinline__ void conv_f16x2_zs_body(const ConvArgs& a, float* sme
   {                                                                                                                   \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                   \
       char* d_ = lds_w + q_slb[i] + Cfg::OFF_P * 16;                                                                  \
-      *reinterpret_cast<halfx8*>(d_) = cv_h[i];                                                                       \
-      *reinterpret_cast<halfx8*>(d_ + PPL * 16) = cv_m[i];                                                            \
+      EMO_SPLIT_STORE_PLANES(halfx8, d_, cv_h[i], cv_m[i])                                                            \
     }                                                                                                                 \
   }
-#define EMO_Z_LANDED() { emo_wait_vmem0(); _Pragma("unroll") for (int u = 0; u < 8; ++u) emo_touch4(qv[u]); }
+#define EMO_Z_LANDED() { emo_wait_vmem0(); EMO_SPLIT_TOUCH(qv, 8) }
 
     // ---- prologue: tables and bias of the item, the first stage ----
     {
@@ -298,14 +258,6 @@ __device__ __forceinline__ void conv_f16x2_zs_body(const ConvArgs& a, float* sme
     __syncthreads();                      // P and W[0] hold the first stage
 
     int wb = 0;                           // the weight stage buffer of the current stage
-#define EMO_Z_EPI_FAST(RES_, lo_, hi_)                                                                                \
-  {                                                                                                                   \
-    floatx4 rv_[8];                                                                                                   \
-    conv_epilogue_fast_issue<TW, TP, BM, RES_, 0>(a, rv_, it_n, it_cotile, it_x0, it_y0, zo_, wp, lane);              \
-    conv_epilogue_fast_finish<TW, 1, TP, WGP, BM, 2, Cfg::EPI_ROWF, RES_>(a, lo_, hi_, rv_, scratch_, smem + Cfg::OFF_BIAS_F, \
-                                                                          smem + Cfg::OFF_STAT_F, it_n, it_cotile, ptile_, it_x0, \
-                                                                          it_y0, zo_, wp, half, l32, lane, tid);      \
-  }
     // ---- the march.  Step t: input slice zb - 1 + t feeds output slices t - kd of the run; the accumulator sets have fixed
     //      roles -- set kd holds output t - kd -- and move up one role behind the step (128 register moves per slice against
     //      >= 324 MFMAs: with the sets rotated by index instead, the three copies of the loop body it takes cost more in
@@ -340,15 +292,15 @@ __device__ __forceinline__ void conv_f16x2_zs_body(const ConvArgs& a, float* sme
       }
       if (t >= 2) {
         // output slice zb + t - 2 is complete; scratch: the weight stage buffer the next stage does not use
-        const int zo_ = zb + t - 2;
-        const int ptile_ = zo_ * (a.tiles_x * a.tiles_y) + ptile_yx;
-        float* const scratch_ = smem + (Cfg::OFF_W + (wb ^ 1) * Cfg::WCH) * 4 + wave * Cfg::EPI_WAVE;
-        if (epi_mode == 1) EMO_Z_EPI_FAST(1, acc_lo[2], acc_hi[2])
-        else if (epi_mode == 0) EMO_Z_EPI_FAST(0, acc_lo[2], acc_hi[2])
+        const int ep_n = it_n, ep_cotile = it_cotile, ep_x0 = it_x0, ep_y0 = it_y0, ep_z0 = zb + t - 2;
+        const int ep_ptile = ep_z0 * (a.tiles_x * a.tiles_y) + ptile_yx;
+        float* const scratch = smem + (Cfg::OFF_W + (wb ^ 1) * Cfg::WCH) * 4 + wave * Cfg::EPI_WAVE;
+        if (epi_mode == 1) EMO_SPLIT_EPI_FAST(1, acc_lo[2], acc_hi[2], EMO_SPLIT_NO_STAMPS)
+        else if (epi_mode == 0) EMO_SPLIT_EPI_FAST(0, acc_lo[2], acc_hi[2], EMO_SPLIT_NO_STAMPS)
         else {
-          conv_epilogue_rows<TR, TW, 1, TP, WGP, BM, 2, Cfg::EPI_ROWF>(a, acc_lo[2], acc_hi[2], scratch_, smem + Cfg::OFF_BIAS_F,
-                                                                       smem + Cfg::OFF_STAT_F, it_n, it_cotile, ptile_, 0, it_x0,
-                                                                       it_y0, zo_, wp, half, l32, lane, tid);
+          conv_epilogue_rows<TR, TW, 1, TP, WGP, BM, 2, Cfg::EPI_ROWF>(a, acc_lo[2], acc_hi[2], scratch, smem + Cfg::OFF_BIAS_F,
+                                                                       smem + Cfg::OFF_STAT_F, ep_n, ep_cotile, ep_ptile, 0, ep_x0,
+                                                                       ep_y0, ep_z0, wp, half, l32, lane, tid);
 #if defined(__HIP_DEVICE_COMPILE__)
           // (the general epilogue has paths on which the compiler's wait-count model keeps a residual load pending for ever -- a
           // K-split launch, which never comes here, does not read what it loaded -- and with that state arriving over the loop's
@@ -367,7 +319,6 @@ __device__ __forceinline__ void conv_f16x2_zs_body(const ConvArgs& a, float* sme
         for (int r = 0; r < 16; ++r) { acc_lo[0][0][j][r] = 0.0f; acc_hi[0][0][j][r] = 0.0f; }
       }
     }
-#undef EMO_Z_EPI_FAST
 #undef EMO_Z_LANDED
 #undef EMO_Z_STORE_PATCH
 #undef EMO_Z_CONVERT_PX

@@ -27,7 +27,8 @@
 // Epilogue: through LDS in eight passes of 32 channels x one 4 x 64 statistics tile (one row pair's two waves, 16-byte LDS writes
 // into an image [channel][row][column phase][32 low-res columns]); the read-out interleaves the column phases into whole rows,
 // + bias, 16-byte stores, the tile's (mean, M2) (the TileStats layout of block config D).  No residual, no activation.
-// CHAINED items (EMO_UP2_CHAIN, the scheme of conv_igemm_f16x2_ct2.h): when the block's next item belongs to the same sample (same
+// CHAINED items (EMO_UP2_CHAIN; the stage machinery is conv_split_common.h's, the chaining that of the pair kernels): when
+// the block's next item belongs to the same sample (same
 // scale / shift tables) and the item has >= 2 stages, the look-ahead of the last two stages -- dead re-stages otherwise -- fetches
 // the next item's first stage instead: kernel (stage 0, p = 0) into W[0], the raw loads of its stages 0 and 1 with ITS cursor, its
 // stage-0 patch converted into P[pp ^ 1].  The epilogue image lies in W[1] and the tail of LDS (dead at an item's end: the last
@@ -37,7 +38,6 @@
 // the instantiation files and a fixed list of headers, compiles it.
 #include "conv_dispatch.h"
 #include "conv_igemm_bf16x3.h"
-#include "conv_split_pair_common.h"
 
 #ifndef EMO_UP2_CHAIN
 #define EMO_UP2_CHAIN 1         /* 0: A/B builds -- every item runs the full prologue */
@@ -89,10 +89,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l32 = lane & 31;
+  EMO_SPLIT_THREAD_IDS()
   const int wq = wave & 1;                               // column phase of the wave
   const int p0 = (wave >> 1) * TP * 32;                  // its 128 positions: low-res rows 2 (wave >> 1), + 1 of the item
   float sat_m = 0.0f;
@@ -105,39 +102,19 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
   const int nst = a.n_cchunks;
   const int nptiles = a.tiles_x * a.tiles_y;
 
-  // ---- staging map (conv_igemm_bf16x3.h) ----
-  const int q_u = tid % QPG;
-  const int q_g = __builtin_amdgcn_readfirstlane(tid / QPG);
-  const bool is_quad = q_u < PR * NQ;
-  const int hq = q_u - PR * NQ;
-  const bool is_halo = !is_quad && hq < NHQ;
-  const int h_side = hq & 1;
-  const int q_r = is_quad ? q_u / NQ : (is_halo ? hq >> 1 : 0);
-  const int q_c = is_quad ? q_u - q_r * NQ : 0;
-  int q_slb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int dump = q_g * CHS + i * SUB + PR * NQ1 + (q_u & 3);
-    const int own = is_quad ? q_g * CHS + i * SUB + q_r * NQ1 + q_c : q_g * CHS + h_side * SUB + q_r * NQ1 + NQ;
-    q_slb[i] = ((is_quad || (is_halo && i == (h_side ? 0 : 3))) ? own : dump) * 16;
-  }
+  EMO_SPLIT_STAGING_MAP(tid / QPG, 0)
 
   floatx16 acc[2][TM][TP];                               // [row phase]: one set for the three products
 
   // ---- work items: (sample, low-res tile, channel tile), XCD-contiguous, channel tile fastest; persistent blocks ----
-  const int q8 = a.n_work >> 3, r8 = a.n_work & 7;
-  const int xcd = blockIdx.x & 7;
-  const int n_mine = q8 + (xcd < r8 ? 1 : 0);
-  const int l_base = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int l_stride = (gridDim.x + 7) >> 3;
+  EMO_SPLIT_ITEM_WALK()
 // byte address of the packed kernel of (channel tile c_, stage k_, row phase p_)
 #define EMO_U_WPTR(c_, k_, p_) (reinterpret_cast<const char*>(a.wpk) + ((long)((c_) * nst + (k_)) * 2 + (p_)) * Cfg::WST_BYTES)
 
   const int a_off = (half * BM + l32) * 16;
-  EMO_P_DECLARE_B_OFF()
+  EMO_SPLIT_DECLARE_B_OFF()
 
-  const char* const lds_c = reinterpret_cast<const char*>(smem);
-  char* const lds_w = reinterpret_cast<char*>(smem);
+  EMO_SPLIT_LDS_VIEWS()
   opx8 fa_[2][NPL][TM], fb_[2][NPL][TP];
 // fragments of tap (a_, b_) of half-stage buffer hb_ (patch buffer at byte pbyte_): the wave's column phase wq
 #define EMO_U_LOAD_FRAGS_PLANE(set_, pl_, hb_, pbyte_, a_, b_)                                        \
@@ -146,12 +123,10 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
       fa_[set_][pl_][i] = *reinterpret_cast<const opx8*>(lds_c + a_off + (Cfg::OFF_W + (hb_) * Cfg::WSTRIDE + \
           ((wq * 4 + (a_) * 2 + (b_)) * NPL + (pl_)) * Cfg::WPLANE + i * 32) * 16);                   \
     _Pragma("unroll") for (int j = 0; j < TP; ++j)                                                    \
-      fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + (EMO_P_B_OFF(j, (hb_) + (a_), wq + (b_)) + (pbyte_)) + ((pl_) * PPL) * 16); \
+      fb_[set_][pl_][j] = *reinterpret_cast<const opx8*>(lds_c + (EMO_SPLIT_B_OFF(j, (hb_) + (a_), wq + (b_)) + (pbyte_)) + ((pl_) * PPL) * 16); \
   }
 
-  float* const sct = smem + Cfg::OFF_SCT * 4;
-  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(smem);
-  const unsigned lane16 = (unsigned)lane * 16u;
+  EMO_SPLIT_LDS_TABLES_ADDR()
 
   floatx4 qv[8];
   float q_lo, q_hi;
@@ -159,49 +134,25 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
   floatx4 q_sc, q_sh;
   opx8 cv_h, cv_m;
   emo_intx4 xrs = emo_raw_buffer(a.x);
-  unsigned usoff[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) usoff[u] = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)u * (unsigned)HW * 4u));
+  EMO_SPLIT_USOFF(8, 0, HW, 1u)
   unsigned lq_off = 0;
   bool lq_ok = false;
   unsigned q_vo;
 // the raw loads of stage st_ (16 input channels)
-#define EMO_U_ISSUE_BEGIN(st_)                                                                        \
-  {                                                                                                   \
-    const int c0_ = (st_) * KC + q_g * 8;                                                             \
-    const bool cv_ = c0_ < a.Cin;                                                                     \
-    const int cs_ = cv_ ? c0_ : 0;                                                                    \
-    const bool keep_ = lq_ok && cv_;                                                                  \
-    q_lo = keep_ ? clamp_lo : 0.0f;                                                                   \
-    q_hi = keep_ ? CLAMP_HI : 0.0f;                                                                   \
-    q_vo = lq_off + (unsigned)cs_ * (unsigned)HW * 4u;                                                \
-    q_tix = (has_affine ? cs_ : (cs_ & (Cfg::SCT - 1))) >> 2;                                         \
-  }
-#define EMO_U_ISSUE_LOADS(u0_, u1_)                                                                   \
-  { _Pragma("unroll") for (int u = (u0_); u < (u1_); u += 2) emo_bload4x2_pinned(xrs, q_vo, usoff[u], usoff[u + 1], qv[u], qv[u + 1]); }
-#define EMO_U_HALF_TABLE(hf_)                                                                         \
-  {                                                                                                   \
-    const floatx4* t4_ = reinterpret_cast<const floatx4*>(sct) + q_tix + (hf_);                       \
-    q_sc = t4_[0]; q_sh = t4_[Cfg::SCT / 4];                                                          \
-  }
-#define EMO_U_TOUCH_QUAD() { _Pragma("unroll") for (int u = 0; u < 8; ++u) emo_touch4(qv[u]); }
+#define EMO_U_ISSUE_BEGIN(st_) EMO_SPLIT_ISSUE_BEGIN(, q_vo, (st_) * KC + q_g * 8, lq_ok && cv_, (unsigned)cs_ * (unsigned)HW * 4u)
+#define EMO_U_ISSUE_LOADS(u0_, u1_) EMO_SPLIT_ISSUE_LOADS(qv, q_vo, u0_, u1_)
+#define EMO_U_TOUCH_QUAD() EMO_SPLIT_TOUCH(qv, 8)
 // conversion of pixel i_ of the raw registers (both halves of the lane's 8 channels) into the patch buffer at byte pbyte_
 #define EMO_U_CONV_PIXEL(pbyte_, i_)                                                                  \
   {                                                                                                   \
     _Pragma("unroll") for (int hf_ = 0; hf_ < 2; ++hf_) {                                             \
-      EMO_U_HALF_TABLE(hf_)                                                                           \
-      float t_[4];                                                                                    \
-      _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                   \
-        t_[k] = __fmaf_rn(qv[4 * hf_ + k][i_], q_sc[k], q_sh[k]);                                     \
-      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[0])), __builtin_fabsf(t_[1])); \
-      sat_m = __builtin_fmaxf(__builtin_fmaxf(sat_m, __builtin_fabsf(t_[2])), __builtin_fabsf(t_[3])); \
-      _Pragma("unroll") for (int k = 0; k < 4; k += 2)                                                \
-        emo_split_f16x2_pair(__builtin_amdgcn_fmed3f(t_[k], q_lo, q_hi), __builtin_amdgcn_fmed3f(t_[k + 1], q_lo, q_hi), \
-                             cv_h, cv_m, 4 * hf_ + k);                                                \
+      EMO_SPLIT_TABLE(q_tix + hf_, q_sc, q_sh)                                                        \
+      EMO_SPLIT_AFFINE4(t_, qv, 4 * hf_, i_, q_sc, q_sh)                                              \
+      EMO_SPLIT_RANGE4(t_)                                                                            \
+      EMO_SPLIT_F16X2_4(t_, q_lo, q_hi, cv_h, cv_m, 4 * hf_)                                          \
     }                                                                                                 \
     char* d_ = lds_w + (q_slb[i_] + (pbyte_));                                                        \
-    *reinterpret_cast<opx8*>(d_) = cv_h;                                                              \
-    *reinterpret_cast<opx8*>(d_ + PPL * 16) = cv_m;                                                   \
+    EMO_SPLIT_STORE_PLANES(opx8, d_, cv_h, cv_m)                                                      \
   }
 // piece k_ = 0 .. 7 of a half-stage's kernel (wave w copies the 1 KiB pieces w + 4 k) into W[wb_]
 #define EMO_U_DMA_PIECE(ptr_, wb_, k_)                                                                \
@@ -224,14 +175,6 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
     P_##x0 = __builtin_amdgcn_readfirstlane((lt_ % a.tiles_x) * Cfg::TWL);     /* low-res origin */   \
     P_##y0 = __builtin_amdgcn_readfirstlane((lt_ / a.tiles_x) * Cfg::TRL);                            \
   }
-// the lane's 16-byte patch load for the tile of item P_ and whether it lies inside the image
-#define EMO_U_CURSOR_OF(P_, ok_, off_)                                                                \
-  {                                                                                                   \
-    const int q_y_ = P_##y0 - 1 + q_r;                                                                \
-    const int q_x_ = is_quad ? P_##x0 + 4 * q_c : (h_side ? P_##x0 + TWS : P_##x0 - 4);               \
-    ok_ = (is_quad || is_halo) && (unsigned)q_y_ < (unsigned)a.H && q_x_ >= 0 && q_x_ < a.W;          \
-    off_ = ok_ ? (unsigned)(q_y_ * a.W + q_x_) * 4u : 0u;                                             \
-  }
 // the raw loads of stage cg + 2, first part; past the item's end: the next item's stages 0 / 1 with its cursor (chained), a dead
 // re-load of the last stage otherwise.  Indices are SELECTED: no branch
 #define EMO_U_NEXT_STAGE_BEGIN()                                                                      \
@@ -242,21 +185,6 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
     lq_off = sw_ ? nxq_off : lq_off;                                                                  \
     EMO_U_ISSUE_BEGIN(tgt_)                                                                           \
   }
-#if EMO_S_TIMING == 2
-// measurement build: the cycles a wave sits in the waitcnt of a K-loop barrier and in the s_barrier itself (conv_igemm_bf16x3.h)
-#define EMO_U_LOOP_BARRIER(n_)                                                                        \
-  {                                                                                                   \
-    const unsigned long long b0_ = __builtin_amdgcn_s_memtime();                                      \
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(n_) : "memory");                              \
-    const unsigned long long b1_ = __builtin_amdgcn_s_memtime();                                      \
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                  \
-    const unsigned long long b2_ = __builtin_amdgcn_s_memtime();                                      \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                \
-    tw_wait += b1_ - b0_; tw_bar += b2_ - b1_; ++tw_n;                                                \
-  }
-#else
-#define EMO_U_LOOP_BARRIER(n_) EMO_P_BARRIER(n_)
-#endif
 
   constexpr bool CHAIN = EMO_UP2_CHAIN != 0, LOADS_EARLY = EMO_UP2_LOADS_EARLY != 0;
   float te_b = 0.0f;
@@ -282,7 +210,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
     if (CHAIN && idx8 + l_stride < n_mine) {
       EMO_U_DECODE(nx_, l_base + idx8 + l_stride)
       chain_out = nx_n == it_n && nst >= 2;
-      EMO_U_CURSOR_OF(nx_, nxq_ok, nxq_off)
+      EMO_SPLIT_CURSOR_OF(nx_, nxq_ok, nxq_off)
     }
     xrs = emo_raw_buffer(a.x + (long)it_n * a.Cin * HW);
     asm volatile("" : "=v"(cv_h));
@@ -296,12 +224,12 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
       const char* const w1_ = EMO_U_WPTR(cotile, 0, 1);
       EMO_U_DMA_PIECE(w1_, 1, 0)
       EMO_U_DMA_PIECE(w1_, 1, 1)
-      EMO_P_BARRIER(63);                  // (the epilogue's stores and these two pieces stay outstanding)
+      EMO_SPLIT_BARRIER(63);                  // (the epilogue's stores and these two pieces stay outstanding)
     } else {
       // ---- full prologue: tables, bias, the whole kernel of (stage 0, p = 0), pieces 0, 1 of (0, 1), patch 0 converted, loads of stage 1 ----
       {
         int it_x0 = x0, it_y0 = y0;
-        EMO_U_CURSOR_OF(it_, lq_ok, lq_off)
+        EMO_SPLIT_CURSOR_OF(it_, lq_ok, lq_off)
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) asm volatile("" : "=v"(qv[u]));
@@ -325,14 +253,14 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
         }
       }
       if (tid < BM) smem[Cfg::OFF_BIAS_F + tid] = a.bias != nullptr ? a.bias[cotile * BM + tid] : 0.0f;
-      EMO_P_WAIT(0);
+      EMO_SPLIT_WAIT(0);
       EMO_U_TOUCH_QUAD()
       __syncthreads();   // scale / shift tables visible
 #pragma unroll
       for (int i = 0; i < 4; ++i) EMO_U_CONV_PIXEL(Cfg::OFF_P * 16, i)
       EMO_U_ISSUE_BEGIN(nst > 1 ? 1 : 0)
       EMO_U_ISSUE_LOADS(0, 8)
-      EMO_P_BARRIER(0);                    // (P[0] visible, W[0] and the loads of stage 1 landed)
+      EMO_SPLIT_BARRIER(0);                    // (P[0] visible, W[0] and the loads of stage 1 landed)
       EMO_U_TOUCH_QUAD()
       pp = 0;
     }
@@ -371,7 +299,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
 #pragma unroll
         for (int gs = 0; gs < 4; ++gs) {
           const int fcur = (h * 4 + gs) & 1, fnxt = fcur ^ 1;
-          if (gs == 3) { EMO_U_LOOP_BARRIER(0); }
+          if (gs == 3) { EMO_SPLIT_TIMED_BARRIER(0); }
           if (gs == 3 && h == 1) EMO_U_TOUCH_QUAD()
           if (!LOADS_EARLY && gs == 0 && h == 1) EMO_U_NEXT_STAGE_BEGIN()
           __builtin_amdgcn_sched_barrier(0);
@@ -415,7 +343,7 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
     //      [32 channels][4 high-res rows][column phase][32 low-res columns] (+ 4) in W[1] + tail; a row pair beyond the map (ragged
     //      height) is skipped ----
     EMO_S_STAMP(2)
-    EMO_P_WAIT(0);
+    EMO_SPLIT_WAIT(0);
     EMO_S_STAMP(5)
     __syncthreads();
     EMO_S_STAMP(6)
@@ -528,13 +456,10 @@ void conv_igemm_f16x2_up2_kernel(const ConvArgs a) {
   if (a.sat_flag != nullptr && sat_m > 65504.0f) *a.sat_flag = 1;   // (every writer stores the same value)
 #undef EMO_U_WPTR
 #undef EMO_U_DECODE
-#undef EMO_U_CURSOR_OF
 #undef EMO_U_NEXT_STAGE_BEGIN
-#undef EMO_U_LOOP_BARRIER
 #undef EMO_U_LOAD_FRAGS_PLANE
 #undef EMO_U_ISSUE_BEGIN
 #undef EMO_U_ISSUE_LOADS
-#undef EMO_U_HALF_TABLE
 #undef EMO_U_TOUCH_QUAD
 #undef EMO_U_CONV_PIXEL
 #undef EMO_U_DMA_PIECE

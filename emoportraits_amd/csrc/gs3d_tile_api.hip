@@ -1,11 +1,8 @@
 // Entry of the LDS-staged 3-D grid_sample behind emo_grid_sample3d_f32 (grid_sample3d.hip checks the arguments), and the
 // packed-4 layout repack -- SURVEY.md section 8 rows a1 + a2.
 #include "common.h"
+#include "gs3d_tile_signature.h"
 
-#define EMO_GS3D_TILE_PAD_SIGNATURE(name)                                                                              \
-  int name(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,            \
-           const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, \
-           int in_layout, int out_layout, int variant, int grid_kind, hipStream_t s)
 EMO_GS3D_TILE_PAD_SIGNATURE(emo_gs3d_tile_zeros);
 EMO_GS3D_TILE_PAD_SIGNATURE(emo_gs3d_tile_border);
 EMO_GS3D_TILE_PAD_SIGNATURE(emo_gs3d_tile_reflection);

@@ -5,6 +5,7 @@
 #include <set>
 #include <utility>
 #include "gs3d_tile.h"
+#include "gs3d_tile_signature.h"
 
 namespace gs3d {
 
@@ -147,7 +148,3 @@ int launch_tile_pad(const float* vol, const float* grid, const float* theta, con
 
 }  // namespace gs3d
 
-#define EMO_GS3D_TILE_PAD_SIGNATURE(name)                                                                              \
-  int name(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,            \
-           const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, \
-           int in_layout, int out_layout, int variant, int grid_kind, hipStream_t s)

@@ -32,6 +32,32 @@ def test_the_measurement_build_of_the_split_kernel_passes_the_same_audit():
     assert "0 violations" in r.stdout
 
 
+def test_every_function_like_macro_has_one_home_and_every_conv_header_is_emulated():
+    """the kernels share their stage machinery as macros over local names (csrc/conv_split_common.h): a second `#define` of the
+    same name in another file is a private copy that a fix will miss -- and builds only while no unit includes both.  Text only."""
+    import re
+    from collections import defaultdict
+    csrc = os.path.join(ROOT, "emoportraits_amd", "csrc")
+    homes = defaultdict(set)
+    for dirpath, _, files in os.walk(csrc):
+        for f in files:
+            with open(os.path.join(dirpath, f), errors="replace") as fh:
+                for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(EMO_\w*)\(", fh.read(), re.M):
+                    homes[m.group(1)].add(os.path.relpath(os.path.join(dirpath, f), csrc))
+    assert len(homes) > 50, "the scan found the kernels' macros"
+    twice = {n: sorted(fs) for n, fs in homes.items() if len(fs) > 1}
+    assert not twice, f"function-like macros defined in more than one file: {twice}"
+    # the host emulation rewrites COPIES of the headers it lists: one it does not list is compiled unrewritten
+    sys.path.insert(0, os.path.join(ROOT, "tests", "emul"))
+    try:
+        import convlib
+    finally:
+        sys.path.pop(0)
+    conv_headers = {f for f in os.listdir(csrc) if f.startswith("conv_") and f.endswith(".h")}
+    assert "conv_split_common.h" in conv_headers and "conv_igemm_f16x2_zs.h" in conv_headers
+    assert conv_headers <= set(convlib.HEADERS), sorted(conv_headers - set(convlib.HEADERS))
+
+
 LISTING = """
 \t#ASMSTART
 \tglobal_load_dword v10, v1, s[2:3]

@@ -1,7 +1,9 @@
 """sha256 of the gfx950 device assembly of the convolution units (conv_api.hip, conv_inst_*.hip), to hold a host-side change to
 "the device code is the same": compiled with the flags of emoportraits_amd/build.py plus --cuda-device-only -S.
 
-    python tools/device_code_digest.py [CSRC_DIR] > digests.json       {unit: digest}, CSRC_DIR: another checkout's csrc
+    python tools/device_code_digest.py [CSRC_DIR] [-DNAME=V ...] > digests.json
+                                                                       {unit: digest}, CSRC_DIR: another checkout's csrc; -DNAME=V:
+                                                                       a measurement build (as tools/kernel_resources.py --audit)
     python tools/device_code_digest.py --diff A.json B.json            the units whose digests differ (exit status 1 if any)
 
 The digest covers every line of the assembly -- instruction streams, kernel descriptors, metadata -- except what names the source
@@ -33,6 +35,8 @@ def main(argv):
         bad = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
         print("identical" if not bad else "DIFFERENT: " + ", ".join(bad))
         return 1 if bad else 0
+    while argv and argv[-1].startswith("-D"):
+        build.FLAGS = build.FLAGS + [argv.pop()]
     csrc = argv[0] if argv else build.CSRC
     units = sorted(f for f in os.listdir(csrc) if f == "conv_api.hip" or (f.startswith("conv_inst_") and f.endswith(".hip")))
     with concurrent.futures.ThreadPoolExecutor(max_workers=8) as ex:
