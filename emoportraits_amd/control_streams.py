@@ -4,7 +4,9 @@ the two keywords (expression_plan, head_pose_plan, and stream_expression / strea
 are in controls.py, which stays pure Python; the arithmetic is ops.theta_ema_scan / expression_controls / head_pose_controls.
 Crop tracking (boxes=, tracking=) has its own store, CropStates -- its streams are tracks of the video, not identities -- its own
 checks, crop_plan, and BoxFeed, which hands out the boxes as the frames come; the arithmetic is ops.crop_track.  detections= (unordered
-detections in place of ordered boxes) adds TrackStates, the tracks that ops.track_assign associates the detections to."""
+detections in place of ordered boxes) adds TrackStates, the tracks that ops.track_assign associates the detections to.  With
+tracking follow_tracks=True the streams of StreamStates follow those tracks: row_masks hands the tracker's restart flags and its
+"this row has a face" to the three controls, which restart a stream at a birth and keep a row without a face out of it."""
 import itertools
 from argparse import Namespace
 
@@ -16,7 +18,8 @@ from .controls import CropTracking, ExpressionControls, HeadPoseControls
 class StreamStates:
     """The state of K streams of rows, on the device: per stream the smooth_pose EMA `theta` [K,4,4], the relative-pose anchor
     `pose_anchor` [K,9], the expression controls' relative-transfer anchor `expr_anchor` and EMA `expr_ema` [K,E], each with an int32
-    flag vector `*_has` [K]: 0 until the stream's first row (the kernels set it), and 0 again after a restart.  The expression rows
+    flag vector `*_has` [K]: 0 until the stream's first row (the kernels set it), and 0 again after a restart -- restart() here, or
+    under tracking follow_tracks=True a row at which the row's face track restarts (the kernels clear it).  The expression rows
     are allocated at the first use (expression()), from the width of the row at hand; until then they and their flags are None.
     InferenceWrapper holds two: `_bank_streams`, one stream per slot of the identity bank (None without a bank), and `_stream`, the
     one stream of the current identity, which the calls without identities= walk.
@@ -350,6 +353,20 @@ class BoxFeed:
         return t.to(self.device)
 
 
+def row_masks(masks, r0, m):
+    """The row masks of the control streams under tracking follow_tracks=True, for the rows r0 ... r0 + m of the call: masks =
+    None (the streams do not follow the tracks: {}) or (restart int32 [rows] on the device or None, present int32 [rows], the
+    first row of the chunk they belong to) -> the restart= and present= of ops.theta_ema_scan / expression_controls /
+    head_pose_controls: slices of the chunk's tensors, no launch"""
+    if masks is None:
+        return {}
+    restart, present, first = masks
+    if r0 < first or r0 + m > first + present.shape[0]:
+        raise ValueError(f"the rows {r0} ... {r0 + m} are not rows of the chunk last tracked ({first} ... {first + present.shape[0]})")
+    a = r0 - first
+    return dict(restart=None if restart is None else restart[a:a + m], present=present[a:a + m])
+
+
 def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, device, what="boxes", detections=None):
     """The checks of boxes= and tracking= (a CropTracking or a mapping with its fields), before anything is launched -> None (no
     boxes: nothing will be launched) or what InferenceWrapper._track_chunk needs: the tracker's settings, tracks = P of boxes
@@ -357,7 +374,8 @@ def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, de
     beside boxes that also says where the faces are ('windows' | 'faces'), or None; default_momentum: the wrapper's crop momentum.
     detections: unordered detections [N,D,4] (or an iterable of chunks) in place of boxes -- mutually exclusive with it and with
     `other`; tracking.tracks = P <= min(16, batch_size) says how many track slots a frame has, D <= 32.  The plan then has
-    detections = D (None: boxes=), tracks = P, min_iou and max_missed, and its feed hands out the detections."""
+    detections = D (None: boxes=), tracks = P, min_iou and max_missed, and its feed hands out the detections.  follow_tracks: the
+    control streams follow the tracks (row_masks)."""
     tr = CropTracking.of(tracking)
     if detections is not None:
         if boxes is not None:
@@ -422,5 +440,5 @@ def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, de
     elif tracks is not None and tracks > batch_size:
         raise ValueError(f"{what} has {tracks} tracks per frame: more than batch_size={batch_size}")
     return Namespace(smooth=bool(tr.smooth), fixed=bool(tr.fixed), momentum=m, scale=scale, box_format=tr.box_format, missing=tr.missing,
-                     tracks=tracks, detections=n_dets, min_iou=min_iou, max_missed=max_missed,
+                     tracks=tracks, detections=n_dets, min_iou=min_iou, max_missed=max_missed, follow_tracks=bool(tr.follow_tracks),
                      feed=BoxFeed(boxes, device, tracks if n_dets is None else n_dets, what))

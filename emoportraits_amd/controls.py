@@ -88,6 +88,11 @@ class CropTracking:
         whose last matched box it overlaps most, if their IoU is at least min_iou (in (0, 1]); a track that finds no detection
         for more than max_missed consecutive frames is dropped and its slot is free for the next new face.  0.3 and 15 are
         taste defaults, not measured optima.
+    follow_tracks: animate_frames only.  The per-identity control streams -- the smooth_pose EMA, the expression controls' relative
+        anchor and EMA, the head-pose controls' relative anchor -- follow the tracks: a row at which detections= restarts its track
+        (a birth, a death) first restarts the stream its identity walks, and a row without a face (a paste window of side 0) is
+        still rendered, from a copy of the stream's state, but leaves no mark on the stream: it is neither an anchor nor a step of
+        an EMA.  False: every row enters its stream, as before the field existed.
     All defaults = the reference's per-frame window (use_smoothed_crop=False)."""
     smooth: bool = False
     momentum: object = None
@@ -98,6 +103,7 @@ class CropTracking:
     tracks: object = None
     min_iou: float = 0.3
     max_missed: int = 15
+    follow_tracks: bool = False
 
     @classmethod
     def of(cls, value):

@@ -327,30 +327,41 @@ __global__ __launch_bounds__(64) void mixing_theta_kernel(const float* __restric
 // notebooks/infer.py:571-581 smooth_pose, one EMA stream per source identity: frame i belongs to stream stream_of[i] (NULL:
 // all to stream 0) and is smoothed within that stream's frames in frame order, fp32 exactly as hostglue.ema_scan (two
 // rounded products, one rounded sum).  One thread per stream walks all 16 elements, so the stream's flag is read and
-// written by one thread only.
+// written by one thread only.  ABI 26 (hostglue.ema_scan_tracks): a row with restart[i] != 0 first drops the stream's state; a
+// row with present[i] == 0 is smoothed from a private copy of the state (started at the row where there is none) and leaves
+// the stream as it was.  Both masks NULL: the scan as it always was.
 __global__ __launch_bounds__(64) void theta_ema_scan_kernel(const float* __restrict__ values, const int* __restrict__ stream_of,
                                                             float* __restrict__ state, int* __restrict__ has_state, int n, int K,
-                                                            float m, float om, float* __restrict__ out) {
+                                                            float m, float om, const int* __restrict__ restart,
+                                                            const int* __restrict__ present, float* __restrict__ out) {
   const int k = blockIdx.x * 64 + threadIdx.x;
   if (k >= K) return;
-  bool has = has_state[k] != 0;
+  bool has = has_state[k] != 0, cleared = false;
   float cur[16];
   for (int e = 0; e < 16; ++e) cur[e] = has ? state[(long)k * 16 + e] : 0.0f;
   for (int i = 0; i < n; ++i) {
     if ((stream_of ? stream_of[i] : 0) != k) continue;
+    if (restart && restart[i] != 0) {
+      has = false;
+      cleared = true;
+    }
+    const bool here = !present || present[i] != 0;
     const float* v = values + (long)i * 16;
     float* o = out + (long)i * 16;
     for (int e = 0; e < 16; ++e) {
-      if (!has) cur[e] = v[e];
-      const float a = v[e] * m, b = cur[e] * om;
-      cur[e] = a + b;
-      o[e] = cur[e];
+      const float prev = has ? cur[e] : v[e];
+      const float a = v[e] * m, b = prev * om;
+      const float next = a + b;
+      if (here) cur[e] = next;
+      o[e] = next;
     }
-    has = true;
+    if (here) has = true;
   }
   if (has) {
     for (int e = 0; e < 16; ++e) state[(long)k * 16 + e] = cur[e];
     has_state[k] = 1;
+  } else if (cleared) {
+    has_state[k] = 0;
   }
 }
 
@@ -359,30 +370,37 @@ __global__ __launch_bounds__(64) void theta_ema_scan_kernel(const float* __restr
 // One block per stream; a thread owns the elements j = threadIdx.x, + blockDim.x, ... of every row and of the stream's anchor
 // and EMA, and walks the n rows in order, so `out` may be `values`.  Every thread reads the stream's flags, then the barrier;
 // the block's LAST thread alone writes them, at its end (a host build that runs thread after thread reaches it last as well).
+// ABI 26: a row with restart[i] != 0 first drops the stream's anchor and EMA; a row with present[i] == 0 is its own anchor and
+// the start of its own EMA where the stream has none, and leaves the stream as it was.  The flags the last thread writes are
+// what the walk ends with: 1 only if a present row came after the stream's last restart.  Both masks NULL: as it always was.
 __global__ __launch_bounds__(128) void expr_controls_kernel(const float* values, const int* __restrict__ stream_of,
                                                             const float* __restrict__ neutral, const float* __restrict__ gain,
                                                             const float* __restrict__ offset, float* __restrict__ anchor,
                                                             int* has_anchor, float* __restrict__ ema, int* has_ema, int n, int E,
-                                                            int relative, int smooth, float m, float om, float* out) {
+                                                            int relative, int smooth, float m, float om,
+                                                            const int* __restrict__ restart, const int* __restrict__ present,
+                                                            float* out) {
   const int k = blockIdx.x;
   const bool had_anchor = relative && has_anchor[k] != 0;
   const bool had_ema = smooth && has_ema[k] != 0;
   __syncthreads();
   for (int j = threadIdx.x; j < E; j += blockDim.x) {
     const long kj = (long)k * E + j;
-    bool ha = had_anchor, he = had_ema;
+    bool ha = had_anchor, he = had_ema, taken = false;
     float anc = ha ? anchor[kj] : 0.0f;
     float cur = he ? ema[kj] : 0.0f;
     const float neu = neutral ? neutral[kj] : 0.0f;
     for (int i = 0; i < n; ++i) {
       if ((stream_of ? stream_of[i] : 0) != k) continue;
+      if (restart && restart[i] != 0) { ha = false; he = false; }
+      const bool here = !present || present[i] != 0;
       const long ij = (long)i * E + j;
       float e = values[ij];
       if (neutral) {
         float r = neu;
         if (relative) {
-          if (!ha) { anc = e; ha = true; }
-          r = anc;
+          if (!ha && here) { anc = e; ha = true; taken = true; }
+          r = ha ? anc : e;
         }
         float t = e - r;
         if (gain) t = t * gain[i];
@@ -390,38 +408,57 @@ __global__ __launch_bounds__(128) void expr_controls_kernel(const float* values,
       }
       if (offset) e = e + offset[ij];
       if (smooth) {
-        if (!he) { cur = e; he = true; }
-        const float a = e * m, b = cur * om;
-        cur = a + b;
-        e = cur;
+        const float prev = he ? cur : e;
+        const float a = e * m, b = prev * om;
+        e = a + b;
+        if (here) { cur = e; he = true; }
       }
       out[ij] = e;
     }
-    if (ha && !had_anchor) anchor[kj] = anc;
+    if (ha && taken) anchor[kj] = anc;
     if (he) ema[kj] = cur;
   }
   if (threadIdx.x == blockDim.x - 1 && (relative || smooth)) {
-    bool seen = false;
-    for (int i = 0; i < n && !seen; ++i) seen = (stream_of ? stream_of[i] : 0) == k;
-    if (seen && relative) has_anchor[k] = 1;
-    if (seen && smooth) has_ema[k] = 1;
+    bool seen = false, live_a = had_anchor, live_e = had_ema;
+    for (int i = 0; i < n; ++i) {
+      if ((stream_of ? stream_of[i] : 0) != k) continue;
+      seen = true;
+      if (restart && restart[i] != 0) { live_a = false; live_e = false; }
+      if (!present || present[i] != 0) { live_a = true; live_e = true; }
+    }
+    if (seen && relative) has_anchor[k] = live_a ? 1 : 0;
+    if (seen && smooth) has_ema[k] = live_e ? 1 : 0;
   }
 }
 
 // The head-pose controls of the batched entry points (include/emo_hip.h, ABI 21; hostglue.head_pose_controls is the contract):
 // the regressed (scale, rotation, translation) of every row edited before theta is formed -- frontal, relative transfer and gain
 // about the identity's source pose, offsets, zoom.  One block per stream.  Only the anchor depends on the row order: every
-// thread reads the stream's flag, then the barrier; a stream without an anchor takes it from its first row (every thread finds
-// that row for itself and holds the anchor in registers, thread 0 stores it); then the threads take the stream's rows strided
-// by blockDim.x, a whole row each: nine floats in, nine floats and theta's sixteen out.  The block's LAST thread alone writes the
-// flag, at its end (a host build that runs thread after thread reaches it last as well).  The outputs alias no input.
+// thread reads the stream's flag and its stored anchor, then the barrier; every thread then walks the row indices once in
+// order and carries the anchor of the segment it is in -- the stored one until a restart, else the segment's first present row,
+// which it loads for itself into registers (ABI 26: a row with restart[i] != 0 begins a segment, a row with present[i] == 0
+// cannot be an anchor and is its own reference while its segment has none; both masks NULL: one segment, its anchor the stored
+// one or the stream's first row, as it always was) -- and edits the rows i = threadIdx.x, + blockDim.x, ... of the walk, a whole
+// row each: nine floats in, nine floats and theta's sixteen out.  The block's LAST thread alone writes the anchor and the flag
+// its walk ended with, at its end (a host build that runs thread after thread reaches it last as well, so no thread reads what
+// it wrote).  The outputs alias no input.
 __global__ __launch_bounds__(64) void head_pose_controls_kernel(
     const float* __restrict__ scale, int scale_cols, const float* __restrict__ rotation, const float* __restrict__ translation,
     const int* __restrict__ stream_of, const float* __restrict__ source, const float* __restrict__ gain,
     const float* __restrict__ rotation_offset, const float* __restrict__ translation_offset, const float* __restrict__ zoom,
-    float* anchor, int* has_anchor, int n, int relative, int frontal, float* __restrict__ out_srt, float* __restrict__ out_theta) {
+    float* anchor, int* has_anchor, int n, int relative, int frontal, const int* __restrict__ restart,
+    const int* __restrict__ present, float* __restrict__ out_srt, float* __restrict__ out_theta) {
   const int k = blockIdx.x;
   const bool had_anchor = relative && has_anchor[k] != 0;
+  float q[9], ref[9];
+  for (int j = 0; j < 9; ++j) { q[j] = 0.0f; ref[j] = 0.0f; }
+  if (source) {
+    for (int j = 0; j < 9; ++j) q[j] = source[(long)k * 9 + j];
+    for (int j = 3; j < 6; ++j) q[j] = pose_clamp_angle(q[j]);
+    for (int j = 0; j < 9; ++j) ref[j] = q[j];
+  }
+  if (had_anchor)
+    for (int j = 0; j < 9; ++j) ref[j] = anchor[(long)k * 9 + j];
   __syncthreads();
   // step 0 of row i: the scale in three columns, the rotation clamped, the translation
   auto load = [&](int i, float* p) {
@@ -433,39 +470,31 @@ __global__ __launch_bounds__(64) void head_pose_controls_kernel(
       p[6 + j] = translation[(long)i * 3 + j];
     }
   };
-  float q[9], ref[9];
-  if (source) {
-    for (int j = 0; j < 9; ++j) q[j] = source[(long)k * 9 + j];
-    for (int j = 3; j < 6; ++j) q[j] = pose_clamp_angle(q[j]);
-    for (int j = 0; j < 9; ++j) ref[j] = q[j];
-  }
-  int first = n;
-  if (relative) {
-    if (had_anchor) {
-      for (int j = 0; j < 9; ++j) ref[j] = anchor[(long)k * 9 + j];
-    } else {
-      for (int i = 0; i < n && first == n; ++i)
-        if ((stream_of ? stream_of[i] : 0) == k) first = i;
-      if (first < n) {
-        load(first, ref);
-        if (threadIdx.x == 0)
-          for (int j = 0; j < 9; ++j) anchor[(long)k * 9 + j] = ref[j];
+  bool anchored = had_anchor;                                 // the segment at hand has an anchor, and `ref` holds it
+  int taken = -1;                                             // the row it was taken from in this call (-1: the stored one)
+  for (int i = 0; i < n; ++i) {
+    if ((stream_of ? stream_of[i] : 0) != k) continue;
+    if (relative) {
+      if (restart && restart[i] != 0) anchored = false;
+      if (!anchored && (!present || present[i] != 0)) {
+        load(i, ref);
+        anchored = true;
+        taken = i;
       }
     }
-  }
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    if ((stream_of ? stream_of[i] : 0) != k) continue;
-    float p[9];
+    if (i % (int)blockDim.x != (int)threadIdx.x) continue;
+    float p[9], r[9];
     load(i, p);
+    for (int j = 0; j < 9; ++j) r[j] = relative && !anchored ? p[j] : ref[j];
     if (frontal) { p[3] = 0.0f; p[4] = 0.0f; p[6] = 0.0f; p[7] = 0.0f; p[8] = 0.0f; }
     if (source) {
       for (int j = 3; j < 9; ++j) {
-        float d = p[j] - ref[j];
+        float d = p[j] - r[j];
         if (gain) d = d * gain[i];
         p[j] = q[j] + d;
       }
       if (relative)
-        for (int j = 0; j < 3; ++j) p[j] = q[j] * __fdiv_rn(p[j], ref[j]);
+        for (int j = 0; j < 3; ++j) p[j] = q[j] * __fdiv_rn(p[j], r[j]);
     }
     for (int j = 0; j < 3; ++j) {
       if (rotation_offset) p[3 + j] = p[3 + j] + rotation_offset[(long)i * 3 + j];
@@ -475,7 +504,11 @@ __global__ __launch_bounds__(64) void head_pose_controls_kernel(
     for (int j = 0; j < 9; ++j) out_srt[(long)i * 9 + j] = p[j];
     pose_theta_row(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], out_theta + (long)i * 16);
   }
-  if (threadIdx.x == blockDim.x - 1 && relative && !had_anchor && first < n) has_anchor[k] = 1;
+  if (threadIdx.x == blockDim.x - 1 && relative) {
+    if (anchored && taken >= 0)
+      for (int j = 0; j < 9; ++j) anchor[(long)k * 9 + j] = ref[j];
+    if (anchored != had_anchor) has_anchor[k] = anchored ? 1 : 0;
+  }
 }
 
 // Face boxes -> crop and paste windows with the crop tracker's state carried along the row order (include/emo_hip.h, ABI 23;
@@ -840,24 +873,55 @@ extern "C" int emo_mixing_theta_f32(const float* target, const float* source, co
   return emo_launch_status();
 }
 
-extern "C" int emo_theta_ema_scan_f32(const float* values, const int32_t* stream_of, float* state, int32_t* has_state, int n, int K,
-                                      float m, float om, float* out, void* stream) {
+extern "C" int emo_theta_ema_scan_tracks_f32(const float* values, const int32_t* stream_of, float* state, int32_t* has_state, int n,
+                                             int K, float m, float om, const int32_t* restart, const int32_t* present, float* out,
+                                             void* stream) {
   if (!values || !state || !has_state || !out || n <= 0 || K <= 0) return EMO_ERR_BAD_ARG;
   hipLaunchKernelGGL(theta_ema_scan_kernel, dim3(emo_cdiv(K, 64)), dim3(64), 0, (hipStream_t)stream, values, stream_of, state,
-                     has_state, n, K, m, om, out);
+                     has_state, n, K, m, om, restart, present, out);
   return emo_launch_status();
 }
 
-extern "C" int emo_expr_controls_f32(const float* values, const int32_t* stream_of, const float* neutral, const float* gain,
-                                     const float* offset, float* anchor, int32_t* has_anchor, float* ema, int32_t* has_ema, int n,
-                                     int K, int E, int relative, int smooth, float m, float om, float* out, void* stream) {
+extern "C" int emo_theta_ema_scan_f32(const float* values, const int32_t* stream_of, float* state, int32_t* has_state, int n, int K,
+                                      float m, float om, float* out, void* stream) {
+  return emo_theta_ema_scan_tracks_f32(values, stream_of, state, has_state, n, K, m, om, nullptr, nullptr, out, stream);
+}
+
+extern "C" int emo_expr_controls_tracks_f32(const float* values, const int32_t* stream_of, const float* neutral, const float* gain,
+                                            const float* offset, float* anchor, int32_t* has_anchor, float* ema, int32_t* has_ema,
+                                            int n, int K, int E, int relative, int smooth, float m, float om,
+                                            const int32_t* restart, const int32_t* present, float* out, void* stream) {
   if (!values || !out || n <= 0 || K <= 0 || E <= 0) return EMO_ERR_BAD_ARG;
   if ((relative || gain) && !neutral) return EMO_ERR_BAD_ARG;
   if (relative && (!anchor || !has_anchor)) return EMO_ERR_BAD_ARG;
   if (smooth && (!ema || !has_ema)) return EMO_ERR_BAD_ARG;
   const int threads = E >= 128 ? 128 : emo_cdiv(E, 64) * 64;
   hipLaunchKernelGGL(expr_controls_kernel, dim3(K), dim3(threads), 0, (hipStream_t)stream, values, stream_of, neutral, gain, offset,
-                     anchor, has_anchor, ema, has_ema, n, E, relative ? 1 : 0, smooth ? 1 : 0, m, om, out);
+                     anchor, has_anchor, ema, has_ema, n, E, relative ? 1 : 0, smooth ? 1 : 0, m, om, restart, present, out);
+  return emo_launch_status();
+}
+
+extern "C" int emo_expr_controls_f32(const float* values, const int32_t* stream_of, const float* neutral, const float* gain,
+                                     const float* offset, float* anchor, int32_t* has_anchor, float* ema, int32_t* has_ema, int n,
+                                     int K, int E, int relative, int smooth, float m, float om, float* out, void* stream) {
+  return emo_expr_controls_tracks_f32(values, stream_of, neutral, gain, offset, anchor, has_anchor, ema, has_ema, n, K, E, relative,
+                                      smooth, m, om, nullptr, nullptr, out, stream);
+}
+
+extern "C" int emo_head_pose_controls_tracks_f32(const float* scale, int scale_cols, const float* rotation, const float* translation,
+                                                 const int32_t* stream_of, const float* source, const float* gain,
+                                                 const float* rotation_offset, const float* translation_offset, const float* zoom,
+                                                 float* anchor, int32_t* has_anchor, int n, int K, int relative, int frontal,
+                                                 const int32_t* restart, const int32_t* present, float* out_srt, float* out_theta,
+                                                 void* stream) {
+  if (!scale || !rotation || !translation || !out_srt || !out_theta || n <= 0 || K <= 0) return EMO_ERR_BAD_ARG;
+  if (scale_cols != 1 && scale_cols != 3) return EMO_ERR_BAD_ARG;
+  if ((relative || gain) && !source) return EMO_ERR_BAD_ARG;
+  if (relative && (!anchor || !has_anchor)) return EMO_ERR_BAD_ARG;
+  if (relative && frontal) return EMO_ERR_BAD_ARG;
+  hipLaunchKernelGGL(head_pose_controls_kernel, dim3(K), dim3(64), 0, (hipStream_t)stream, scale, scale_cols, rotation, translation,
+                     stream_of, source, gain, rotation_offset, translation_offset, zoom, anchor, has_anchor, n, relative ? 1 : 0,
+                     frontal ? 1 : 0, restart, present, out_srt, out_theta);
   return emo_launch_status();
 }
 
@@ -866,13 +930,7 @@ extern "C" int emo_head_pose_controls_f32(const float* scale, int scale_cols, co
                                           const float* rotation_offset, const float* translation_offset, const float* zoom,
                                           float* anchor, int32_t* has_anchor, int n, int K, int relative, int frontal,
                                           float* out_srt, float* out_theta, void* stream) {
-  if (!scale || !rotation || !translation || !out_srt || !out_theta || n <= 0 || K <= 0) return EMO_ERR_BAD_ARG;
-  if (scale_cols != 1 && scale_cols != 3) return EMO_ERR_BAD_ARG;
-  if ((relative || gain) && !source) return EMO_ERR_BAD_ARG;
-  if (relative && (!anchor || !has_anchor)) return EMO_ERR_BAD_ARG;
-  if (relative && frontal) return EMO_ERR_BAD_ARG;
-  hipLaunchKernelGGL(head_pose_controls_kernel, dim3(K), dim3(64), 0, (hipStream_t)stream, scale, scale_cols, rotation, translation,
-                     stream_of, source, gain, rotation_offset, translation_offset, zoom, anchor, has_anchor, n, relative ? 1 : 0,
-                     frontal ? 1 : 0, out_srt, out_theta);
-  return emo_launch_status();
+  return emo_head_pose_controls_tracks_f32(scale, scale_cols, rotation, translation, stream_of, source, gain, rotation_offset,
+                                           translation_offset, zoom, anchor, has_anchor, n, K, relative, frontal, nullptr, nullptr,
+                                           out_srt, out_theta, stream);
 }

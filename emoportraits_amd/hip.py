@@ -67,6 +67,9 @@ SIGNATURES = {
     "emo_theta_ema_scan_f32": [_c_void] * 4 + [_c_int, _c_int, _c_float, _c_float, _c_void, _c_void],
     "emo_expr_controls_f32": [_c_void] * 9 + [_c_int] * 5 + [_c_float, _c_float, _c_void, _c_void],
     "emo_head_pose_controls_f32": [_c_void, _c_int] + [_c_void] * 10 + [_c_int] * 4 + [_c_void] * 3,
+    "emo_theta_ema_scan_tracks_f32": [_c_void] * 4 + [_c_int, _c_int, _c_float, _c_float] + [_c_void] * 4,
+    "emo_expr_controls_tracks_f32": [_c_void] * 9 + [_c_int] * 5 + [_c_float, _c_float] + [_c_void] * 4,
+    "emo_head_pose_controls_tracks_f32": [_c_void, _c_int] + [_c_void] * 10 + [_c_int] * 4 + [_c_void] * 5,
     "emo_crop_track_f64": [_c_void] * 3 + [_c_int, _c_int] + [_c_void] * 3 + [_c_int, _c_int, _c_double, _c_double, _c_int, _c_int,
                            _c_double] + [_c_int] * 3 + [_c_void] * 4,
     "emo_crop_track_restarts_f64": [_c_void] * 3 + [_c_int, _c_int] + [_c_void] * 3 + [_c_int, _c_int, _c_double, _c_double, _c_int,

@@ -344,7 +344,50 @@ def ema_scan(values, state, momentum):
     return out, cur
 
 
-def expression_controls(values, stream_of, neutral, gain, offset, anchor, has_anchor, ema, has_ema, relative, momentum):
+def _row_mask(mask, n, name):
+    """a row mask of the control streams: None, or n ints -> None or a bool [n] array (!= 0)"""
+    if mask is None:
+        return None
+    mask = np.asarray(mask)
+    if mask.shape != (n,):
+        raise ValueError(f"{name} must have one entry per row ({n}), got {mask.shape}")
+    return mask != 0
+
+
+def ema_scan_tracks(values, stream_of, state, has_state, momentum, restart=None, present=None):
+    """ema_scan over the rows of K streams that follow face tracks -- the contract that emo_theta_ema_scan_tracks_f32
+    (ops.theta_ema_scan(restart=, present=)) is held to bit for bit; include/emo_hip.h (ABI 26) has the same text.
+    values [n, ...] fp32 in frame order; stream_of [n] ints or None (every row: stream 0); state [K, ...] fp32 and has_state [K]
+    are the streams' states, UPDATED IN PLACE (numpy arrays); restart, present: [n] ints or None (no restarts; every row
+    present).  Row i of a stream k in [0, K), within the stream in row order:
+        1. restart[i] != 0: has_state[k] = 0, before the row is looked at and whether or not it is present
+        2. present: a stream without state starts at the row's value; cur = v * m + cur * fp32(1 - m); state[k] = cur,
+           has_state[k] = 1; out[i] = cur  (ema_scan's recurrence)
+        3. absent: out[i] = v * m + cur * fp32(1 - m) with cur = state[k], or = v where the stream has none; nothing is written
+    -> out [n, ...]; a row whose stream lies outside [0, K) is left unwritten (NaN here), touches no state, and its masks are
+    not looked at.  With both masks None every stream is ema_scan of its rows."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    n, K = v.shape[0], state.shape[0]
+    restart, present = _row_mask(restart, n, "restart"), _row_mask(present, n, "present")
+    m, om = np.float32(momentum), np.float32(1 - momentum)
+    out = np.full_like(v, np.nan)
+    for i in range(n):
+        k = 0 if stream_of is None else int(stream_of[i])
+        if not 0 <= k < K:
+            continue
+        if restart is not None and restart[i]:
+            has_state[k] = 0
+        cur = state[k].reshape(v.shape[1:]) if has_state[k] else v[i]
+        cur = v[i] * m + cur * om
+        if present is None or present[i]:
+            state[k] = cur.reshape(state.shape[1:])
+            has_state[k] = 1
+        out[i] = cur
+    return out
+
+
+def expression_controls(values, stream_of, neutral, gain, offset, anchor, has_anchor, ema, has_ema, relative, momentum,
+                        restart=None, present=None):
     """The expression controls of the batched entry points on the host, one row after another -- the contract that
     emo_expr_controls_f32 (ops.expression_controls) is held to bit for bit, as ema_scan is for the theta scan.  The reference has
     no such controls beyond the `custome_target_pose_embed` override (notebooks/infer.py:603-604).
@@ -355,8 +398,15 @@ def expression_controls(values, stream_of, neutral, gain, offset, anchor, has_an
         with neutral:  r = neutral[k], or with `relative` the stream's anchor (its first row);  e = neutral[k] + (e - r) * gain[i]
         with offset:   e = e + offset[i]
         with momentum: the smooth_pose recurrence, cur = e * m + cur * fp32(1 - m), started at the stream's first e
-    -> out [n,E]; a row whose stream lies outside [0, K) is left unwritten (NaN here) and touches no state."""
+    restart, present: [n] ints or None (emo_expr_controls_tracks_f32; include/emo_hip.h, ABI 26, has the same text): a row with
+    restart[i] != 0 first clears its stream's has_anchor (under `relative`) and has_ema (with momentum), whether or not it is
+    present; a present row (present None or present[i] != 0) is processed as above; an absent row is computed from a private copy
+    of the stream's state -- it is its own anchor where the stream has none, and its EMA starts at itself where the stream has
+    none -- and writes nothing of the stream.  With both None this is the function as it always was.
+    -> out [n,E]; a row whose stream lies outside [0, K) is left unwritten (NaN here), touches no state, and its masks are not
+    looked at."""
     v = np.ascontiguousarray(values, dtype=np.float32)
+    restart, present = _row_mask(restart, v.shape[0], "restart"), _row_mask(present, v.shape[0], "present")
     if v.ndim != 2:
         raise ValueError(f"values must be [n,E], got {v.shape}")
     smooth = momentum is not None
@@ -376,14 +426,20 @@ def expression_controls(values, stream_of, neutral, gain, offset, anchor, has_an
         k = 0 if stream_of is None else int(stream_of[i])
         if not 0 <= k < K:
             continue
+        if restart is not None and restart[i]:
+            if relative:
+                has_anchor[k] = 0
+            if smooth:
+                has_ema[k] = 0
+        here = present is None or bool(present[i])
         e = v[i].copy()
         if neutral is not None:
             r = neutral[k]
             if relative:
-                if not has_anchor[k]:
+                if not has_anchor[k] and here:
                     anchor[k] = e
                     has_anchor[k] = 1
-                r = anchor[k]
+                r = anchor[k] if has_anchor[k] else e
             t = e - r
             if gain is not None:
                 t = t * gain[i]
@@ -391,11 +447,11 @@ def expression_controls(values, stream_of, neutral, gain, offset, anchor, has_an
         if offset is not None:
             e = e + offset[i]
         if smooth:
-            if not has_ema[k]:
+            cur = ema[k] if has_ema[k] else e
+            e = e * m + cur * om
+            if here:
                 ema[k] = e
                 has_ema[k] = 1
-            e = e * m + ema[k] * om
-            ema[k] = e
         out[i] = e
     return out
 
@@ -422,7 +478,7 @@ def srt_theta(srt):
 
 
 def head_pose_controls(scale, rotation, translation, stream_of, source, gain, rotation_offset, translation_offset, zoom, anchor,
-                       has_anchor, relative, frontal, K=None):
+                       has_anchor, relative, frontal, K=None, restart=None, present=None):
     """The head-pose controls of the batched entry points on the host, one row after another -- the contract that
     emo_head_pose_controls_f32 (ops.head_pose_controls) is held to bit for bit.  frontal and the rotation offsets are the
     reference's `normalize`, `delta_yaw` and `delta_pitch` (ExpressionEmbed.forward_image, expression_embedder.py:302-316: the
@@ -438,8 +494,13 @@ def head_pose_controls(scale, rotation, translation, stream_of, source, gain, ro
            step 0);  p.rot = q.rot + (p.rot - ref.rot) * gain[i],  p.trans = q.trans + (p.trans - ref.trans) * gain[i] (no
            product without gain);  with `relative` only:  p.scale = q.scale * (p.scale / ref.scale)
         3. p.rot += rotation_offset[i];  p.trans += translation_offset[i];  p.scale *= zoom[i]  (each where given)
+    restart, present: [n] ints or None (emo_head_pose_controls_tracks_f32; include/emo_hip.h, ABI 26, has the same text): under
+    `relative` a row with restart[i] != 0 first clears its stream's has_anchor, whether or not it is present; a present row
+    (present None or present[i] != 0) is processed as above; an absent row never becomes the anchor, and where the stream has none
+    it is its own reference (ref = the row after step 0).  Without `relative` there is no state and the masks change nothing; with
+    both None this is the function as it always was.
     -> (rows [n,9] fp32, theta [n,4,4] = srt_theta(rows) rounded to fp32); a row whose stream lies outside [0, K) is left
-    unwritten (NaN here) and touches no state."""
+    unwritten (NaN here), touches no state, and its masks are not looked at."""
     f32 = lambda a: None if a is None else np.asarray(a, dtype=np.float32)
     scale, rotation, translation = (np.ascontiguousarray(a, dtype=np.float32) for a in (scale, rotation, translation))
     if scale.ndim != 2 or scale.shape[1] not in (1, 3) or rotation.shape != (scale.shape[0], 3) or translation.shape != rotation.shape:
@@ -455,6 +516,7 @@ def head_pose_controls(scale, rotation, translation, stream_of, source, gain, ro
     rotation_offset, translation_offset = f32(rotation_offset), f32(translation_offset)
     lo, hi = _POSE_CLAMP
     n = scale.shape[0]
+    restart, present = _row_mask(restart, n, "restart"), _row_mask(present, n, "present")
     out = np.full((n, 9), np.nan, np.float32)
     for i in range(n):
         k = 0 if stream_of is None else int(stream_of[i])
@@ -464,16 +526,19 @@ def head_pose_controls(scale, rotation, translation, stream_of, source, gain, ro
         p[0:3] = scale[i]
         p[3:6] = np.clip(rotation[i], lo, hi)
         p[6:9] = translation[i]
-        if relative and not has_anchor[k]:
+        if relative and restart is not None and restart[i]:
+            has_anchor[k] = 0
+        if relative and not has_anchor[k] and (present is None or present[i]):
             anchor[k] = p
             has_anchor[k] = 1
+        own = p.copy()
         if frontal:
             p[3] = p[4] = 0.0
             p[6:9] = 0.0
         if source is not None:
             q = source[k].copy()
             q[3:6] = np.clip(q[3:6], lo, hi)
-            ref = anchor[k] if relative else q
+            ref = (anchor[k] if has_anchor[k] else own) if relative else q
             d = p[3:9] - ref[3:9]
             if gain is not None:
                 d = d * gain[i]

@@ -201,9 +201,11 @@ class InferenceWrapper:
         # use), apart from the host _crop_tracker of forward(crop=True); tracked_windows = (the paste windows of the chunk last
         # tracked, int32 [rows,4] on the device, side 0 = no face; the index of its first row in the call).  detections=: the
         # tracks the detections are associated to (control_streams.TrackStates), and tracked_assignment = (track_of [n,D], restart
-        # [n,P]) of the chunk last tracked, int32 on the device
+        # [n,P]) of the chunk last tracked, int32 on the device.  tracking follow_tracks=True: tracked_present = (present int32 [rows]
+        # on the device: 1 where the row has a face, the index of its first row), beside tracked_windows
         self._crop_streams = self.tracked_windows = None
         self._track_states = self.tracked_assignment = None
+        self.tracked_present = None
         self._init_identity_bank(identity_capacity)
 
     @property
@@ -829,11 +831,12 @@ class InferenceWrapper:
                                f"share_source) first")
         return theta.reshape(1, 4, 4).float().contiguous()
 
-    def _pose_controls(self, theta, ids_dev, mix, mix_old, smooth):
+    def _pose_controls(self, theta, ids_dev, mix, mix_old, smooth, r0=0, masks=None):
         """forward()'s order (infer.py:568-581) on a batch of driver thetas IN FRAME ORDER, on the device: mix against each
         frame's identity (bank slot ids_dev[i], or the current identity), then smooth_pose (ops.theta_ema_scan, bit for bit
         hostglue.ema_scan = the reference's per-frame loop) -- with a bank one stream per slot, else the single stream, whose
-        state (`self.theta` reads it) carries from call to call as the reference's does"""
+        state (`self.theta` reads it) carries from call to call as the reference's does.  masks: where the streams follow face
+        tracks, the chunk's row masks (control_streams.row_masks), and r0 the first row's index in the call"""
         theta = theta.to(self.device).float().contiguous()
         if theta.shape[0] == 0:
             return theta
@@ -844,10 +847,11 @@ class InferenceWrapper:
                 theta = ops.mixing_theta(theta, self._bank_theta, ids_dev, mix_old)
         if smooth:
             st = self._stream if ids_dev is None else self._bank_streams
-            theta = ops.theta_ema_scan(theta, ids_dev, st.theta, st.theta_has, self.pose_momentum)
+            masks = control_streams.row_masks(masks, r0, theta.shape[0])
+            theta = ops.theta_ema_scan(theta, ids_dev, st.theta, st.theta_has, self.pose_momentum, **masks)
         return theta
 
-    def _expression_controls(self, values, ids_dev, ex, r0):
+    def _expression_controls(self, values, ids_dev, ex, r0, masks=None):
         """The expression controls `ex` (control_streams.expression_plan) on values [m,E] = the rows r0 ... of the call IN FRAME
         ORDER, one launch (ops.expression_controls, bit for bit hostglue.expression_controls): every row about its identity's source
         expression (bank slot ids_dev[i], or the current identity's), and for relative / smooth within its slot's stream -- without
@@ -867,10 +871,11 @@ class InferenceWrapper:
         else:
             self._expr_bank(values.shape[1])
             neutral = self._bank_expr if ex.step1 else None
+        masks = control_streams.row_masks(masks, r0, m) if ex.scan else {}       # (masks: _pose_controls'; no stream state, none)
         return ops.expression_controls(values, ids_dev, neutral, gain, offset, st.expr_anchor, st.expr_anchor_has, st.expr_ema,
-                                       st.expr_ema_has, ex.relative, ex.momentum)
+                                       st.expr_ema_has, ex.relative, ex.momentum, **masks)
 
-    def _head_pose_controls(self, srt, ids_dev, hp, r0):
+    def _head_pose_controls(self, srt, ids_dev, hp, r0, masks=None):
         """The head-pose controls `hp` (control_streams.head_pose_plan) on srt = (scale, rotation, translation) of the rows r0 ... of
         the call IN FRAME ORDER, one launch (ops.head_pose_controls, bit for bit hostglue.head_pose_controls) -> (the edited rows
         [m,9], their theta [m,4,4]): every row about its identity's source pose (bank slot ids_dev[i], or the current identity's),
@@ -890,9 +895,10 @@ class InferenceWrapper:
         st, source = self._stream if ids_dev is None else self._bank_streams, None
         if hp.step1:
             source = self._bank_srt if ids_dev is not None else self.pred_source_srt.to(self.device).float().reshape(1, 9).contiguous()
-        # (without step1 there is no source and no stream: every row by itself)
+        # (without step1 there is no source and no stream: every row by itself; only `relative` has a state that follows the tracks)
+        masks = control_streams.row_masks(masks, r0, m) if hp.relative else {}           # (masks: _pose_controls')
         out = ops.head_pose_controls(scale, rotation, translation, ids_dev if hp.step1 else None, source, gain, rot, trans, zoom,
-                                     st.pose_anchor, st.pose_anchor_has, hp.relative, hp.frontal)
+                                     st.pose_anchor, st.pose_anchor_has, hp.relative, hp.frontal, **masks)
         self.pred_target_srt = tuple(out[0][:, i:i + 3] for i in (0, 3, 6))
         return out
 
@@ -1329,9 +1335,9 @@ class InferenceWrapper:
             whose box is missing (not finite, or beyond 2^30) or whose window does not fit its frame -- with paste_back, is
             smaller than a quarter of the pasted image -- is absent: paste_back returns its frame byte for byte as it went in;
             without paste_back it is still rendered (fixed batch shapes, graphs replay), from the centred square of its frame (or
-            with missing='hold' from the track's last window).  Its pose still enters smooth_pose and the relative controls:
-            masking it is out of scope.  tracked_windows is left as (the paste windows of the chunk last tracked, int32 [rows,4] on
-            the device, side 0 = absent; the index of its first row).
+            with missing='hold' from the track's last window).  Its pose still enters smooth_pose and the relative controls
+            unless tracking follow_tracks=True keeps it out (below).  tracked_windows is left as (the paste windows of the chunk
+            last tracked, int32 [rows,4] on the device, side 0 = absent; the index of its first row).
             boxes [N,P,4]: P fixed tracks per frame on the faces= path -- rows frame-major, track p is tracker stream p (the
             tracker is made anew when P changes), P <= batch_size, identities= one slot per row, and faces=' rules for smooth_pose
             and the relative controls.  Not here: enrol_identities, paste_back() (it takes device windows already), running a
@@ -1350,10 +1356,26 @@ class InferenceWrapper:
             The tracks are carried on the device from chunk to chunk and call to call like the tracker's state, and freed with
             it (reset_crop_state, forward(reset_tracking=True)); the result does not depend on batch_size, the chunking or the
             number of ranks.  tracked_assignment is left as (track_of int32 [n,D]: the track of every detection of the chunk
-            last tracked or -1; restart int32 [n,P]), beside tracked_windows.  Not done: an identity's pose and expression
-            streams (smooth_pose, the relative controls) are not restarted at a birth in its column -- reset them by hand where
-            that matters; a row without a face is still rendered, as above, and not pasted; animate_streams keeps one track per
-            stream and takes no detections=.  Without the keyword nothing of this is launched."""
+            last tracked or -1; restart int32 [n,P]), beside tracked_windows.  Not done: a row without a face is still rendered,
+            as above, and not pasted; animate_streams keeps one track per stream and takes no detections=.  Without the keyword
+            nothing of this is launched.
+            tracking follow_tracks=True (with boxes= or detections=): the per-identity control streams -- the smooth_pose EMA, the
+            expression controls' relative anchor and EMA, the head-pose controls' relative anchor -- follow the tracks.  Per chunk,
+            from what the tracker's launch returned and without a host synchronisation, `present` = the row's paste window has a
+            side (a face of its own, or a held window under missing='hold') is formed on the device, and with detections=
+            `restart` is track_assign's flag of the row (boxes= has no births: none).  Every launch of the three controls takes
+            the slices of both for its rows -- the batches of one rank, the per-chunk passes over all rows on several (every rank
+            tracks the whole chunk, so nothing more is gathered) -- through ops.theta_ema_scan / expression_controls /
+            head_pose_controls(restart=, present=): emo_*_tracks_f32, bit for bit hostglue.ema_scan_tracks and
+            hostglue.expression_controls / head_pose_controls(restart=, present=).  A row walks the stream it walks without the
+            field (its identity's bank stream, or the single stream): a birth or a death in its column first restarts that stream,
+            so a new face is not smoothed towards the last one's pose nor measured from its first frame; a row without a face is
+            rendered from a copy of the stream's state (its own anchor, the start of its own EMA where the stream has none) and
+            leaves the stream as it was, so a dropout neither drags the EMA nor becomes the anchor.  mix has no state and stays.
+            The result does not depend on batch_size, the chunking or the number of ranks.  tracked_present is left as (present
+            int32 [rows] on the device, the index of its first row), beside tracked_windows: a caller can drop the crops of rows
+            without a face by it.  Where no control that carries state is active no control launch changes.  Not done:
+            animate_streams (ValueError), and skipping the rendering of absent rows."""
         if isinstance(frames, torch.Tensor):
             frames_mod.check_frames(frames, frame_format)
         n_rows, counts = frames.shape[0] if isinstance(frames, torch.Tensor) else None, None
@@ -1402,7 +1424,7 @@ class InferenceWrapper:
         frames.ArenaRing), upload_stream, ex, hp = the expression and the head-pose controls (_control_plans;
         None: none), track = the crop tracking of boxes= (control_streams.crop_plan; None: none -- it forms the windows on the
         device, and `wins` is then None) with min_side = the smallest side it lets through (a quarter of the pasted image, or 2),
-        and the loop's keywords as they came."""
+        row_masks = None until _track fills it per chunk under tracking follow_tracks=True, and the loop's keywords as they came."""
         frames_mod.check_format(frame_format, colorspace)
         if out_format is not None:
             frames_mod.check_format(out_format, colorspace, "out_format")
@@ -1435,7 +1457,7 @@ class InferenceWrapper:
         return Namespace(masks_of=masks_of, ids=ids, matte_fn=matte_fn, out_kind=out_kind, fmt=(frame_format, colorspace, bool(full_range)),
                          feather=feather, paste_back=paste_back, ring=host_ring, upload_stream=torch.cuda.Stream(device=self.device),
                          batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta, ex=ex,
-                         hp=hp, track=track, min_side=min_side)
+                         hp=hp, track=track, min_side=min_side, row_masks=None)
 
     def _batch_theta(self, crops, ident, plan, row0, edit=True, mix=True, smooth=None):
         """The front of a driver batch of the video paths, crops [m,3,S,S] = the rows row0 ... of the call -> (theta, align): the head
@@ -1449,9 +1471,9 @@ class InferenceWrapper:
         align = None
         if plan.hp is not None:
             align = theta
-            theta = self._head_pose_controls(srt, ident, plan.hp, row0)[1] if edit else self._srt9(srt)
+            theta = self._head_pose_controls(srt, ident, plan.hp, row0, plan.row_masks)[1] if edit else self._srt9(srt)
         if mix and (plan.mix or smooth is not None):
-            theta = self._pose_controls(theta, ident, plan.mix, plan.mix_old, bool(smooth))
+            theta = self._pose_controls(theta, ident, plan.mix, plan.mix_old, bool(smooth), row0, plan.row_masks)
         return theta, align
 
     def _batch_expression(self, crops, theta, align):
@@ -1475,7 +1497,7 @@ class InferenceWrapper:
             else:
                 pose = self._batch_expression(crops, theta, align)
             if ex is not None:
-                pose = self._expression_controls(pose, ident, ex, row0)
+                pose = self._expression_controls(pose, ident, ex, row0, plan.row_masks)
         out = self._render(pose, theta, ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
         return out, (None if plan.matte_fn is None else plan.matte_fn(out).float().contiguous())
 
@@ -1484,12 +1506,18 @@ class InferenceWrapper:
         row i on track stream_of[i] of `states` (a control_streams.CropStates; None: the one track) in a frame of sizes = (W, H), or
         one (W, H) per row, with the settings of plan.track -> (crop, paste) windows of the rows as ops.DeviceWindows.
         tracked_windows = (paste [m,4], row0 = the first row's index in the call).  restart [m] int32 or None: the rows at which
-        their track begins again (ops.track_assign's)."""
+        their track begins again (ops.track_assign's).  With tracking follow_tracks=True tracked_present = (present int32 [m]: the
+        row's paste window has a side, row0) and plan.row_masks = (restart, present, row0), which the control streams of the chunk's
+        batches take (control_streams.row_masks)."""
         t = plan.track
         more = {} if restart is None else dict(restart=restart)
         crop, paste, _ = ops.crop_track(boxes, stream_of, sizes, *states.arrays(), momentum=t.momentum, smooth=t.smooth, fixed=t.fixed,
                                         scale=t.scale, box_format=t.box_format, missing=t.missing, min_side=plan.min_side, **more)
         self.tracked_windows = (paste, row0)
+        if t.follow_tracks:
+            # a row has a face where the tracker gave it a paste window with a side: one comparison on the device per chunk
+            self.tracked_present = ((paste[:, 2] > 0).to(torch.int32), row0)
+            plan.row_masks = (restart, self.tracked_present[0], row0)
         return ops.DeviceWindows(crop), ops.DeviceWindows(paste)
 
     def _track_chunk(self, plan, n, base, frame_hw, row0):
@@ -1602,15 +1630,16 @@ class InferenceWrapper:
                 local = torch.cat(local) if local else torch.empty((0, 9) if gather_srt else (0, 4, 4), device=self.device)
                 if gather_srt:
                     local = scan(lambda every, slots, r: self._head_pose_controls(tuple(every[:, i:i + 3].contiguous() for i in (0, 3, 6)),
-                                                                                  slots, hp, r)[1], local)
+                                                                                  slots, hp, r, plan.row_masks)[1], local)
                 if plan.mix:
                     local = self._pose_controls(local, ids_dev, True, plan.mix_old, False)
                 if plan.smooth_pose:
-                    local = scan(lambda every, slots, r: self._pose_controls(every, slots, False, plan.mix_old, True), local)
+                    local = scan(lambda every, slots, r: self._pose_controls(every, slots, False, plan.mix_old, True, r, plan.row_masks),
+                                 local)
                 thetas = {b0: part(local, b0, b1) for b0, b1 in with_faces}
             if ex is not None and ex.scan and self.world > 1:
                 # relative / smooth walk the rows of every rank: the expressions of the rank's rows, or the override's, which every rank has
-                control = lambda every, slots, r: self._expression_controls(every, slots, ex, r)
+                control = lambda every, slots, r: self._expression_controls(every, slots, ex, r, plan.row_masks)
                 if ex.override is not None:
                     poses = scan(control, every=control_streams.rows_of(ex.override, r0, r1 - r0, 'expression override'))
                 else:
@@ -1707,6 +1736,9 @@ class InferenceWrapper:
                                                batch_size, self.momentum, self.device, f"stream {k}: 'boxes'")
                 if tr.tracks is not None:
                     raise ValueError(f"stream {k}: 'boxes' must be [N,4]: several tracks per stream are not served")
+                if tr.follow_tracks:
+                    raise ValueError("tracking follow_tracks=True is animate_frames': the control streams of animate_streams do not "
+                                     "follow its tracks")
                 if n_k is None:
                     raise ValueError(f"stream {k}: its length must be known before the first batch: give its frames or its boxes as one tensor")
                 tracks.append(tr)

@@ -1207,10 +1207,25 @@ def mixing_theta(target, source_bank, index=None, mix_old=True):
     return out
 
 
-def theta_ema_scan(values, stream_of, state, has_state, momentum):
+def _row_masks(restart, present, n, device):
+    """the row masks of the control streams (restart, present: int32 [n] on the rows' device, or None), checked like stream_of
+    -> their pointers, or None where neither is given: the entry point without masks is then the one to call"""
+    if restart is None and present is None:
+        return None
+    if restart is not None:
+        _check_index(restart, n, device, "restart")
+    if present is not None:
+        _check_index(present, n, device, "present")
+    return hip.ptr(restart), hip.ptr(present)
+
+
+def theta_ema_scan(values, stream_of, state, has_state, momentum, restart=None, present=None):
     """notebooks/infer.py:571-581 smooth_pose over a batch IN FRAME ORDER with one EMA stream per identity, on the device:
     values [n,4,4], stream_of int32 [n] (or None: one stream, 0), state [K,4,4] and has_state int32 [K] updated in place.
-    Per stream bit for bit hostglue.ema_scan (1 - momentum rounded to fp32 once, as there) -> smoothed [n,4,4]."""
+    Per stream bit for bit hostglue.ema_scan (1 - momentum rounded to fp32 once, as there) -> smoothed [n,4,4].
+    restart, present: int32 [n] on the values' device or None -- the streams follow face tracks (emo_theta_ema_scan_tracks_f32; bit
+    for bit hostglue.ema_scan_tracks): a row with restart != 0 first drops its stream's state, a row with present == 0 is
+    smoothed from a copy of the state and leaves the stream as it was."""
     import numpy as np
     lib = hip.load()
     hip.require_cuda_f32(values, state)
@@ -1222,21 +1237,28 @@ def theta_ema_scan(values, stream_of, state, has_state, momentum):
     _check_index(has_state, K, state.device, "has_state")
     if stream_of is not None:
         _check_index(stream_of, n, values.device, "stream_of")
+    masks = _row_masks(restart, present, n, values.device)
     out = torch.empty_like(values)
     m, om = float(np.float32(momentum)), float(np.float32(1 - momentum))
-    hip.check(lib.emo_theta_ema_scan_f32(hip.ptr(values), hip.ptr(stream_of), hip.ptr(state), hip.ptr(has_state), n, K, m, om,
-                                         hip.ptr(out), hip.current_stream()), "emo_theta_ema_scan_f32")
+    args = (hip.ptr(values), hip.ptr(stream_of), hip.ptr(state), hip.ptr(has_state), n, K, m, om)
+    if masks is None:
+        hip.check(lib.emo_theta_ema_scan_f32(*args, hip.ptr(out), hip.current_stream()), "emo_theta_ema_scan_f32")
+    else:
+        hip.check(lib.emo_theta_ema_scan_tracks_f32(*args, *masks, hip.ptr(out), hip.current_stream()), "emo_theta_ema_scan_tracks_f32")
     return out
 
 
 def expression_controls(values, stream_of=None, neutral=None, gain=None, offset=None, anchor=None, has_anchor=None, ema=None,
-                        has_ema=None, relative=False, momentum=None, out=None):
+                        has_ema=None, relative=False, momentum=None, out=None, restart=None, present=None):
     """The expression controls of the batched entry points on the device (emo_expr_controls_f32; bit for bit
     hostglue.expression_controls, which states the arithmetic): values [n,E] IN FRAME ORDER, stream_of int32 [n] (or None: one
     stream, 0), neutral [K,E] or None, gain a float or [n] or None, offset [E] or [n,E] or None -- a scalar gain and an [E]
     offset are broadcast to the rows here; anchor, ema [K,E] and has_anchor, has_ema int32 [K] are the streams' states, updated
     in place; momentum None = no smoothing (else 1 - momentum is rounded to fp32 once, as in theta_ema_scan).  -> [n,E]
-    (`out`, which may be `values`, or a new tensor).  One launch, no host synchronisation."""
+    (`out`, which may be `values`, or a new tensor).  One launch, no host synchronisation.
+    restart, present: int32 [n] on the values' device or None -- the streams follow face tracks (emo_expr_controls_tracks_f32; bit
+    for bit hostglue.expression_controls(restart=, present=)): a row with restart != 0 first drops its stream's anchor and EMA, a
+    row with present == 0 is computed from a copy of the stream's state and leaves the stream as it was."""
     import numpy as np
     lib = hip.load()
     hip.require_cuda_f32(values, neutral, offset, anchor, ema, out)
@@ -1276,28 +1298,35 @@ def expression_controls(values, stream_of=None, neutral=None, gain=None, offset=
             offset = offset.expand(n, E).contiguous()
         elif tuple(offset.shape) != (n, E):
             raise ValueError(f"expression_controls: offset must be [{E}] or [{n},{E}], got {tuple(offset.shape)}")
+    masks = _row_masks(restart, present, n, dev)
     if out is None:
         out = torch.empty_like(values)
     elif tuple(out.shape) != (n, E):
         raise ValueError(f"expression_controls: out must be [{n},{E}], got {tuple(out.shape)}")
     m, om = (float(np.float32(momentum)), float(np.float32(1 - momentum))) if smooth else (0.0, 0.0)
-    hip.check(lib.emo_expr_controls_f32(hip.ptr(values), hip.ptr(stream_of), hip.ptr(neutral), hip.ptr(gain), hip.ptr(offset),
-                                        hip.ptr(anchor if relative else None), hip.ptr(has_anchor if relative else None),
-                                        hip.ptr(ema if smooth else None), hip.ptr(has_ema if smooth else None), n, K, E,
-                                        int(bool(relative)), int(smooth), m, om, hip.ptr(out), hip.current_stream()),
-              "emo_expr_controls_f32")
+    args = (hip.ptr(values), hip.ptr(stream_of), hip.ptr(neutral), hip.ptr(gain), hip.ptr(offset),
+            hip.ptr(anchor if relative else None), hip.ptr(has_anchor if relative else None), hip.ptr(ema if smooth else None),
+            hip.ptr(has_ema if smooth else None), n, K, E, int(bool(relative)), int(smooth), m, om)
+    if masks is None:
+        hip.check(lib.emo_expr_controls_f32(*args, hip.ptr(out), hip.current_stream()), "emo_expr_controls_f32")
+    else:
+        hip.check(lib.emo_expr_controls_tracks_f32(*args, *masks, hip.ptr(out), hip.current_stream()), "emo_expr_controls_tracks_f32")
     return out
 
 
 def head_pose_controls(scale, rotation, translation, stream_of=None, source=None, gain=None, rotation_offset=None,
-                       translation_offset=None, zoom=None, anchor=None, has_anchor=None, relative=False, frontal=False):
+                       translation_offset=None, zoom=None, anchor=None, has_anchor=None, relative=False, frontal=False, restart=None,
+                       present=None):
     """The head-pose controls of the batched entry points on the device (emo_head_pose_controls_f32; bit for bit
     hostglue.head_pose_controls, which states the arithmetic): scale [n,1] or [n,3], rotation and translation [n,3] IN FRAME
     ORDER, stream_of int32 [n] (or None: one stream, 0), source [K,9] or None (needed by relative and gain), gain and zoom a
     float or [n] or None, rotation_offset and translation_offset [3] or [n,3] or None -- a scalar gain / zoom and a [3] offset
     are broadcast to the rows here; anchor [K,9] and has_anchor int32 [K] are the streams' state for `relative`, updated in
     place.  -> (srt [n,9] = the edited rows, theta [n,4,4] = ops.pose_theta of them), both new tensors: the kernel's outputs
-    alias none of its inputs.  One launch, no host synchronisation."""
+    alias none of its inputs.  One launch, no host synchronisation.
+    restart, present: int32 [n] on the rows' device or None -- the streams follow face tracks (emo_head_pose_controls_tracks_f32;
+    bit for bit hostglue.head_pose_controls(restart=, present=)): under `relative` a row with restart != 0 first drops its
+    stream's anchor, and a row with present == 0 never becomes one (it is its own reference where the stream has none)."""
     lib = hip.load()
     hip.require_cuda_f32(scale, rotation, translation, source, anchor)
     if scale.dim() != 2 or scale.shape[0] == 0 or scale.shape[1] not in (1, 3):
@@ -1321,6 +1350,7 @@ def head_pose_controls(scale, rotation, translation, stream_of=None, source=None
         _check_index(has_anchor, K, dev, "has_anchor")
     if stream_of is not None:
         _check_index(stream_of, n, dev, "stream_of")
+    masks = _row_masks(restart, present, n, dev)
 
     def per_row(v, what):
         if v is None:
@@ -1345,11 +1375,14 @@ def head_pose_controls(scale, rotation, translation, stream_of=None, source=None
     rotation_offset, translation_offset = rows3(rotation_offset, "rotation_offset"), rows3(translation_offset, "translation_offset")
     srt = torch.empty((n, 9), device=dev, dtype=torch.float32)
     theta = torch.empty((n, 4, 4), device=dev, dtype=torch.float32)
-    hip.check(lib.emo_head_pose_controls_f32(hip.ptr(scale), scale.shape[1], hip.ptr(rotation), hip.ptr(translation), hip.ptr(stream_of),
-                                             hip.ptr(source), hip.ptr(gain), hip.ptr(rotation_offset), hip.ptr(translation_offset),
-                                             hip.ptr(zoom), hip.ptr(anchor if relative else None),
-                                             hip.ptr(has_anchor if relative else None), n, K, int(bool(relative)), int(bool(frontal)),
-                                             hip.ptr(srt), hip.ptr(theta), hip.current_stream()), "emo_head_pose_controls_f32")
+    args = (hip.ptr(scale), scale.shape[1], hip.ptr(rotation), hip.ptr(translation), hip.ptr(stream_of), hip.ptr(source), hip.ptr(gain),
+            hip.ptr(rotation_offset), hip.ptr(translation_offset), hip.ptr(zoom), hip.ptr(anchor if relative else None),
+            hip.ptr(has_anchor if relative else None), n, K, int(bool(relative)), int(bool(frontal)))
+    out = (hip.ptr(srt), hip.ptr(theta), hip.current_stream())
+    if masks is None:
+        hip.check(lib.emo_head_pose_controls_f32(*args, *out), "emo_head_pose_controls_f32")
+    else:
+        hip.check(lib.emo_head_pose_controls_tracks_f32(*args, *masks, *out), "emo_head_pose_controls_tracks_f32")
     return srt, theta
 
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 25
+#define EMO_ABI_VERSION 26
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -619,6 +619,41 @@ int emo_crop_track_restarts_f64(const double* boxes, const int32_t* stream_of, c
                                 int32_t* has_state, int32_t* last, int M, int K, double m, double om, int smooth, int fixed,
                                 double scale, int box_format, int hold, int min_side, const int32_t* restart, int32_t* crop,
                                 int32_t* paste, double* face_scale, void* stream);
+/* ABI 26.  The three per-identity control streams follow the face tracks: emo_theta_ema_scan_f32, emo_expr_controls_f32 and
+ * emo_head_pose_controls_f32 with two row masks in front of their outputs, both [n] int32 DEVICE memory:
+ *   restart  emo_track_assign_f64's flag, flattened to the rows, or NULL: no restarts;
+ *   present  != 0 where the row has a face (emo_crop_track_f64 gave it a paste window with a side), or NULL: every row present.
+ * For a row i of a stream k in [0, K), within the stream in row order:
+ *   1. restart:  if restart[i] != 0 the stream begins again before the row is looked at -- the scan: has_state[k] = 0; the
+ *                expression controls: has_anchor[k] = 0 under `relative`, has_ema[k] = 0 under `smooth`; the head-pose controls:
+ *                has_anchor[k] = 0 under `relative` -- whether or not the row is present: a track that died does not leave its
+ *                state to the next birth.
+ *   2. present:  if present is NULL or present[i] != 0 the row is processed exactly as the entry point without masks processes
+ *                it, and the stream's state advances.
+ *   3. absent:   otherwise out[i] is what the entry point without masks would write for this row from a private copy of the
+ *                stream's state at this point -- the row is its own anchor where the stream has none, and an EMA starts at the
+ *                row where the stream has none -- and nothing of the stream is written, neither a state value nor a flag.  The row
+ *                is still rendered: its outputs are finite whenever its inputs are.
+ * When the launch returns a flag is 1 only if a present row set it after the stream's last restart: a flag that came in as 1 can
+ * leave as 0.  The state values of a stream whose flag is 0 mean nothing.  A stream index outside [0, K) leaves its row
+ * unwritten, touches no state, and its masks are not looked at.  For the head-pose controls this makes the anchor one per
+ * segment: a row's reference is the stored anchor if no restart precedes it in the call, otherwise the first present row at or
+ * after the last restart at or before it; an absent row ahead of that first present row is its own reference.  Without
+ * `relative` (and for the expression controls without `smooth`) there is no state and the masks change nothing.
+ * Each entry point without masks is this one with restart = present = NULL.  Bit for bit hostglue.ema_scan_tracks,
+ * hostglue.expression_controls(restart=, present=) and hostglue.head_pose_controls(restart=, present=); the refusals, the launch
+ * shapes and "no atomics" are those of the entry points without masks. */
+int emo_theta_ema_scan_tracks_f32(const float* values, const int32_t* stream_of, float* state, int32_t* has_state, int n, int K,
+                                  float m, float om, const int32_t* restart, const int32_t* present, float* out, void* stream);
+int emo_expr_controls_tracks_f32(const float* values, const int32_t* stream_of, const float* neutral, const float* gain,
+                                 const float* offset, float* anchor, int32_t* has_anchor, float* ema, int32_t* has_ema, int n, int K,
+                                 int E, int relative, int smooth, float m, float om, const int32_t* restart, const int32_t* present,
+                                 float* out, void* stream);
+int emo_head_pose_controls_tracks_f32(const float* scale, int scale_cols, const float* rotation, const float* translation,
+                                      const int32_t* stream_of, const float* source, const float* gain, const float* rotation_offset,
+                                      const float* translation_offset, const float* zoom, float* anchor, int32_t* has_anchor, int n,
+                                      int K, int relative, int frontal, const int32_t* restart, const int32_t* present,
+                                      float* out_srt, float* out_theta, void* stream);
 int emo_pack_rgb8(const float* img, uint8_t* out, int N, int H, int W, void* stream);
 int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int W, void* stream);
 

@@ -19,6 +19,9 @@
          detector's output as it comes, up to 32 boxes per frame in no stable order ([N,D,4], or a JSON list per frame of any length:
          rows are padded with NaN); they are associated to P track slots on the device (animate_frames' detections=), and track p is
          rendered as the identity that --identities names for column p
+        [--follow-tracks]   # with --boxes / --detections: --smooth-pose, --relative-expression / --smooth-expression and
+         --relative-pose follow the face tracks (tracking follow_tracks=True): a new face in a freed slot starts its own streams, and a
+         frame without a face leaves no mark on them
         [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
         [--stage2-experiment <exp2> --stage2-checkpoint <file> [--cloth]       # refine every batch with the stage-2 model
          (--embedders module:factory | --refine-everywhere)]                   # (<project>/logs_s2/<exp2>), inside the same path
@@ -126,6 +129,8 @@ def main():
     ap.add_argument("--tracks", type=int, default=None, help="with --detections: P, the track slots per frame (<= 16 and <= --batch)")
     ap.add_argument("--min-iou", type=float, default=0.3, help="with --detections: a detection continues a track from this IoU on")
     ap.add_argument("--max-missed", type=int, default=15, help="with --detections: frames a track may go without a detection")
+    ap.add_argument("--follow-tracks", action="store_true", help="with --boxes / --detections: the pose and expression streams restart at a "
+                                                                 "track's birth and skip the frames without a face")
     ap.add_argument("--sources", default=None, help="comma-separated source images enrolled into bank slots 0, 1, ... (--identities)")
     ap.add_argument("--identities", default=None, help="JSON list: the bank slot of every frame, or with --faces of every face")
     ap.add_argument("--out", required=True)
@@ -183,6 +188,8 @@ def main():
         ap.error("--detections and --tracks go together; --min-iou / --max-missed belong to them")
     if not (a.boxes or a.detections) and (a.box_format != "xyxy" or a.smooth_crop or a.fixed_crop or a.crop_scale != 1.0 or a.hold_missing):
         ap.error("--box-format / --smooth-crop / --fixed-crop / --crop-scale / --hold-missing belong to --boxes / --detections")
+    if a.follow_tracks and not (a.boxes or a.detections):
+        ap.error("--follow-tracks belongs to --boxes / --detections")
     if (a.crop_momentum is not None or a.fixed_crop) and not a.smooth_crop:
         ap.error("--crop-momentum / --fixed-crop belong to --smooth-crop")
     if a.crop_momentum is not None and not 0.0 < a.crop_momentum <= 1.0:
@@ -243,12 +250,13 @@ def main():
     if a.boxes:
         boxes = load_boxes(a.boxes)
         tracking = dict(smooth=a.smooth_crop, momentum=a.crop_momentum, fixed=a.fixed_crop, scale=a.crop_scale, box_format=a.box_format,
-                        missing="hold" if a.hold_missing else "skip")
+                        missing="hold" if a.hold_missing else "skip", follow_tracks=a.follow_tracks)
     detections = None
     if a.detections:
         detections = load_detections(a.detections)
         tracking = dict(smooth=a.smooth_crop, momentum=a.crop_momentum, fixed=a.fixed_crop, scale=a.crop_scale, box_format=a.box_format,
-                        missing="hold" if a.hold_missing else "skip", tracks=a.tracks, min_iou=a.min_iou, max_missed=a.max_missed)
+                        missing="hold" if a.hold_missing else "skip", tracks=a.tracks, min_iou=a.min_iou, max_missed=a.max_missed,
+                        follow_tracks=a.follow_tracks)
     identities = None
     if sources:
         w.enrol_identities([Image.open(f).convert("RGB") for f in sources], slots=list(range(len(sources))), batch_size=a.batch)
