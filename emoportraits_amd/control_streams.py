@@ -375,7 +375,8 @@ def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, de
     detections: unordered detections [N,D,4] (or an iterable of chunks) in place of boxes -- mutually exclusive with it and with
     `other`; tracking.tracks = P <= min(16, batch_size) says how many track slots a frame has, D <= 32.  The plan then has
     detections = D (None: boxes=), tracks = P, min_iou and max_missed, and its feed hands out the detections.  follow_tracks: the
-    control streams follow the tracks (row_masks)."""
+    control streams follow the tracks (row_masks).  skip_absent: the rows without a face are left out of the render
+    (InferenceWrapper._animate_clip; boxes [N,P,4] or detections= only)."""
     tr = CropTracking.of(tracking)
     if detections is not None:
         if boxes is not None:
@@ -385,7 +386,9 @@ def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, de
         raise ValueError("tracking tracks= says how many tracks detections= are associated to: detections= is missing")
     if boxes is None:
         if tr is not None:
-            raise ValueError("tracking= says how boxes= become windows: boxes= is missing")
+            raise ValueError("tracking= says how boxes= become windows: boxes= is missing" +
+                             (" (skip_absent=True leaves out rows the tracker found empty: it needs boxes= or detections=)"
+                              if tr.skip_absent else ""))
         return None
     if other is not None:
         raise ValueError(f"{what}= (the tracker forms the windows) and {other}= (ready windows) are mutually exclusive")
@@ -439,6 +442,10 @@ def crop_plan(boxes, tracking, n_frames, other, batch_size, default_momentum, de
         n_dets, tracks = tracks, tr.tracks
     elif tracks is not None and tracks > batch_size:
         raise ValueError(f"{what} has {tracks} tracks per frame: more than batch_size={batch_size}")
+    if tr.skip_absent and tracks is None:
+        raise ValueError(f"tracking skip_absent=True leaves out the rows of {what} [N,P,4] that have no face: skipping lives on the "
+                         f"faces path, pass [N,1,4] for one track per frame")
     return Namespace(smooth=bool(tr.smooth), fixed=bool(tr.fixed), momentum=m, scale=scale, box_format=tr.box_format, missing=tr.missing,
                      tracks=tracks, detections=n_dets, min_iou=min_iou, max_missed=max_missed, follow_tracks=bool(tr.follow_tracks),
+                     skip_absent=bool(tr.skip_absent),
                      feed=BoxFeed(boxes, device, tracks if n_dets is None else n_dets, what))

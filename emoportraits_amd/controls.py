@@ -93,6 +93,12 @@ class CropTracking:
         (a birth, a death) first restarts the stream its identity walks, and a row without a face (a paste window of side 0) is
         still rendered, from a copy of the stream's state, but leaves no mark on the stream: it is neither an anchor nor a step of
         an EMA.  False: every row enters its stream, as before the field existed.
+    skip_absent: animate_frames only, with boxes [N,P,4] or detections=.  A row without a face (a paste window of side 0) is not
+        cropped, not embedded, not rendered, not refined and not returned: one more launch per chunk (ops.present_rows,
+        hostglue.present_rows states it) puts the present rows first, the number of faces of every frame comes to the host (the
+        one host wait per chunk the field adds), and the batches hold at most batch_size present rows.  The controls still run
+        over all rows of a batch's frames, so a control that carries state needs follow_tracks=True beside it.  False: every
+        row is rendered, as before the field existed.
     All defaults = the reference's per-frame window (use_smoothed_crop=False)."""
     smooth: bool = False
     momentum: object = None
@@ -104,6 +110,7 @@ class CropTracking:
     min_iou: float = 0.3
     max_missed: int = 15
     follow_tracks: bool = False
+    skip_absent: bool = False
 
     @classmethod
     def of(cls, value):

@@ -767,7 +767,78 @@ __global__ __launch_bounds__(64) void track_assign_kernel(const double* __restri
   }
 }
 
+// The present rows of the tracker's windows, first and in order (include/emo_hip.h, ABI 27; hostglue.present_rows is the contract):
+// a stable stream compaction in one block.  Thread t owns the contiguous run of rows [t * run, (t + 1) * run), run = ceil(M /
+// threads): it counts the present rows of its run, the run totals meet in LDS behind the one barrier, every thread sums the totals
+// in front of it and walks its run again, writing each present row at its place; the thread that meets the first row of a frame
+// books the frame (first, count).  The rows behind the T present ones are filled by all threads, strided.  A window row is one
+// 16-byte load and one 16-byte store.  Only sums of integers: the result does not depend on the number of threads.
+constexpr int kPresentThreads = 256;
+struct alignas(16) WindowRow { int x, y, w, h; };
+
+__global__ __launch_bounds__(kPresentThreads) void present_rows_kernel(const WindowRow* __restrict__ crop,
+                                                                       const WindowRow* __restrict__ paste, int F, int P,
+                                                                       int* __restrict__ count, int* __restrict__ first,
+                                                                       int* __restrict__ row_of, WindowRow* __restrict__ crop_out,
+                                                                       WindowRow* __restrict__ paste_out) {
+  __shared__ int s_total[kPresentThreads];
+  const int M = F * P, t = threadIdx.x, nt = blockDim.x;       // (nt <= kPresentThreads: the launch below)
+  const int run = (M + nt - 1) / nt;                           // (M <= 2^24: t * run stays below 2^25)
+  const int lo = t * run < M ? t * run : M, hi = M - lo < run ? M : lo + run;
+  int mine = 0;
+  for (int i = lo; i < hi; ++i) mine += paste[i].w > 0;
+  s_total[t] = mine;
+  __syncthreads();
+  int before = 0, total = 0;
+  for (int u = 0; u < nt; ++u) {
+    if (u == t) before = total;
+    total += s_total[u];
+  }
+  int j = before;
+  for (int i = lo; i < hi; ++i) {
+    if (i % P == 0) {                                          // the first row of frame i / P: the frame is this thread's to book
+      int c = 0;
+      for (int p = 0; p < P; ++p) c += paste[i + p].w > 0;
+      first[i / P] = j;
+      count[i / P] = c;
+    }
+    const WindowRow w = paste[i];
+    if (w.w > 0) {
+      row_of[j] = i;
+      crop_out[j] = crop[i];
+      paste_out[j] = w;
+      ++j;
+    }
+  }
+  if (t == 0) first[F] = total;
+  const WindowRow none = {0, 0, 0, 0};
+  for (int k = total + t; k < M; k += nt) {
+    row_of[k] = -1;
+    crop_out[k] = none;
+    paste_out[k] = none;
+  }
+}
+
 }  // namespace
+
+extern "C" int emo_present_rows_i32(const int32_t* crop, const int32_t* paste, int F, int P, int32_t* count, int32_t* first,
+                                    int32_t* row_of, int32_t* crop_out, int32_t* paste_out, void* stream) {
+  if (!crop || !paste || !count || !first || !row_of || !crop_out || !paste_out) return EMO_ERR_BAD_ARG;
+  if (F <= 0 || P < 1 || P > kTrackMaxP || (long)F * P > (1l << 24)) return EMO_ERR_BAD_ARG;
+  const long M = (long)F * P;
+  const struct { const void* p; long bytes; } in[2] = {{crop, M * 16}, {paste, M * 16}},
+      out[5] = {{count, F * 4l}, {first, (F + 1) * 4l}, {row_of, M * 4}, {crop_out, M * 16}, {paste_out, M * 16}};
+  for (const auto& o : out)
+    for (const auto& i : in) {
+      const uintptr_t a = (uintptr_t)o.p, b = (uintptr_t)i.p;
+      if (a < b + (uintptr_t)i.bytes && b < a + (uintptr_t)o.bytes) return EMO_ERR_BAD_ARG;
+    }
+  if ((((uintptr_t)crop | (uintptr_t)paste | (uintptr_t)crop_out | (uintptr_t)paste_out) & 15) != 0) return EMO_ERR_ALIGN;
+  hipLaunchKernelGGL(present_rows_kernel, dim3(1), dim3(kPresentThreads), 0, (hipStream_t)stream,
+                     reinterpret_cast<const WindowRow*>(crop), reinterpret_cast<const WindowRow*>(paste), F, P, count, first, row_of,
+                     reinterpret_cast<WindowRow*>(crop_out), reinterpret_cast<WindowRow*>(paste_out));
+  return emo_launch_status();
+}
 
 extern "C" int emo_track_assign_f64(const double* dets, const int32_t* stream_of, int F, int D, int P, int K, double* ref,
                                     int32_t* age, double min_iou, int max_missed, int box_format, double* boxes_out,

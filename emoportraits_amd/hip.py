@@ -75,6 +75,7 @@ SIGNATURES = {
     "emo_crop_track_restarts_f64": [_c_void] * 3 + [_c_int, _c_int] + [_c_void] * 3 + [_c_int, _c_int, _c_double, _c_double, _c_int,
                                     _c_int, _c_double] + [_c_int] * 3 + [_c_void] * 5,
     "emo_track_assign_f64": [_c_void, _c_void] + [_c_int] * 4 + [_c_void, _c_void, _c_double, _c_int, _c_int] + [_c_void] * 4,
+    "emo_present_rows_i32": [_c_void, _c_void, _c_int, _c_int] + [_c_void] * 6,
     "emo_mul_mask_f32": [_c_void, _c_void, _c_void, _c_int, _c_int, _c_i64, _c_void],
     "emo_stage2_compose_f32": [_c_void] * 5 + [_c_int, _c_int, _c_i64, _c_void],
     "emo_small_gemm_f32": [_c_void] * 3 + [_c_int] * 4 + [_c_i64, _c_i64, _c_void],

@@ -283,6 +283,34 @@ def track_assign(dets, stream_of, ref, age, min_iou=0.3, max_missed=15, box_form
     return boxes, restart, track_of
 
 
+PRESENT_MAX_ROWS = 1 << 24
+
+
+def present_rows(crop, paste, F, P):
+    """The present rows of the tracker's windows, first and in order: a stable compaction of the M = F * P frame-major rows.  The
+    contract that emo_present_rows_i32 (ops.present_rows) is held to bit for bit; include/emo_hip.h (ABI 27) has the same text.
+    crop, paste [M,4] int32 as crop_track returns them; row i is present iff paste[i][2] > 0.
+    -> (count [F], first [F + 1], row_of [M], crop_out [M,4], paste_out [M,4]), int32: first[f] = the present rows with an index <
+    f * P (first[F] = T, their total), count[f] = first[f + 1] - first[f]; for j < T row_of[j] = the index of the j-th present row,
+    crop_out[j] = crop[row_of[j]], paste_out[j] = paste[row_of[j]]; for T <= j < M row_of[j] = -1 and both windows (0, 0, 0, 0)."""
+    F, P = int(F), int(P)
+    if F <= 0 or not 1 <= P <= TRACK_MAX_TRACKS or F * P > PRESENT_MAX_ROWS:
+        raise ValueError(f"present_rows: F = {F} frames of P = {P} rows: F >= 1, 1 <= P <= {TRACK_MAX_TRACKS}, F * P <= 2^24")
+    M = F * P
+    crop, paste = (np.ascontiguousarray(w, dtype=np.int32) for w in (crop, paste))
+    if crop.shape != (M, 4) or paste.shape != (M, 4):
+        raise ValueError(f"present_rows: crop and paste must be [{M},4], got {crop.shape} and {paste.shape}")
+    present = paste[:, 2] > 0
+    rows = np.nonzero(present)[0].astype(np.int32)
+    T = rows.shape[0]
+    count = present.reshape(F, P).sum(axis=1).astype(np.int32)
+    first = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
+    row_of = np.full((M,), -1, np.int32)
+    crop_out, paste_out = np.zeros((M, 4), np.int32), np.zeros((M, 4), np.int32)
+    row_of[:T], crop_out[:T], paste_out[:T] = rows, crop[rows], paste[rows]
+    return count, first, row_of, crop_out, paste_out
+
+
 def mixing_theta(source_theta, target_theta, mix_old=True):
     """notebooks/infer.py:686-736 (get_mixing_theta): keep the source's stretch (scale/shear from the polar decomposition of
     its linear part) and take rotation + translation from the driver.  numpy [B,>=3,4] x [B*T,>=3,4] -> float64 [B*T,3,4].

@@ -202,10 +202,12 @@ class InferenceWrapper:
         # tracked, int32 [rows,4] on the device, side 0 = no face; the index of its first row in the call).  detections=: the
         # tracks the detections are associated to (control_streams.TrackStates), and tracked_assignment = (track_of [n,D], restart
         # [n,P]) of the chunk last tracked, int32 on the device.  tracking follow_tracks=True: tracked_present = (present int32 [rows]
-        # on the device: 1 where the row has a face, the index of its first row), beside tracked_windows
+        # on the device: 1 where the row has a face, the index of its first row), beside tracked_windows.  tracking skip_absent=True:
+        # tracked_rows = (row_of int32 [T] on the device: the row of the chunk that each rendered row is, first: the rendered rows
+        # in front of every frame of the chunk, a host list of n + 1, the index of the chunk's first row in the call)
         self._crop_streams = self.tracked_windows = None
         self._track_states = self.tracked_assignment = None
-        self.tracked_present = None
+        self.tracked_present = self.tracked_rows = None
         self._init_identity_bank(identity_capacity)
 
     @property
@@ -372,7 +374,9 @@ class InferenceWrapper:
         """Restart the crop tracker of animate_frames(boxes=) -- the EMA of tracking=dict(smooth=True) and the window that
         missing='hold' holds: tracks=None every track, otherwise the given ones (track p of boxes [N,P,4]; 0 for [N,4]).  The
         tracks are faces of the video, not identities: store_identity, drop_identity and the other bank events leave them alone.
-        The tracks of animate_frames(detections=) are freed as well: their slots take the next new faces."""
+        The tracks of animate_frames(detections=) are freed as well: their slots take the next new faces.  tracked_rows (tracking
+        skip_absent=True) is forgotten."""
+        self.tracked_rows = None
         if self._crop_streams is not None:
             self._crop_streams.restart(tracks)
         if getattr(self, "_track_states", None) is not None:
@@ -1356,9 +1360,9 @@ class InferenceWrapper:
             The tracks are carried on the device from chunk to chunk and call to call like the tracker's state, and freed with
             it (reset_crop_state, forward(reset_tracking=True)); the result does not depend on batch_size, the chunking or the
             number of ranks.  tracked_assignment is left as (track_of int32 [n,D]: the track of every detection of the chunk
-            last tracked or -1; restart int32 [n,P]), beside tracked_windows.  Not done: a row without a face is still rendered,
-            as above, and not pasted; animate_streams keeps one track per stream and takes no detections=.  Without the keyword
-            nothing of this is launched.
+            last tracked or -1; restart int32 [n,P]), beside tracked_windows.  A row without a face is still rendered, as
+            above, and not pasted, unless tracking skip_absent=True leaves it out (below).  Not done: animate_streams keeps one
+            track per stream and takes no detections=.  Without the keyword nothing of this is launched.
             tracking follow_tracks=True (with boxes= or detections=): the per-identity control streams -- the smooth_pose EMA, the
             expression controls' relative anchor and EMA, the head-pose controls' relative anchor -- follow the tracks.  Per chunk,
             from what the tracker's launch returned and without a host synchronisation, `present` = the row's paste window has a
@@ -1375,7 +1379,31 @@ class InferenceWrapper:
             The result does not depend on batch_size, the chunking or the number of ranks.  tracked_present is left as (present
             int32 [rows] on the device, the index of its first row), beside tracked_windows: a caller can drop the crops of rows
             without a face by it.  Where no control that carries state is active no control launch changes.  Not done:
-            animate_streams (ValueError), and skipping the rendering of absent rows."""
+            animate_streams (ValueError).
+            tracking skip_absent=True (with boxes [N,P,4] or detections=; boxes [N,4]: ValueError, pass [N,1,4]): a row without a
+            face is not cropped, not embedded, not rendered, not refined and not returned.  Per chunk, behind the tracker's
+            launch, ONE more launch over all rows of the chunk on every rank (ops.present_rows, bit for bit
+            hostglue.present_rows: a stable compaction in one block) puts the present rows and their windows first, and the
+            number of faces of every frame is copied to the host: the ONE host wait per chunk the field adds.  From there the
+            call is the faces= call on those windows: a batch is a run of whole frames with at most batch_size present rows and at
+            most batch_size frames (frames.face_spans on the counts; batch shapes vary with them, and each shape that recurs is
+            captured as a graph of its own), the crop launch, the networks and the paste see kept rows only, the identities are
+            identities[row_of].  With paste_back=True what is yielded is (first_frame_index, frames), a batch without a face its
+            frames as they came; without it (the index of the batch's first kept row, counted over the kept rows of the call, the
+            crops of the kept rows only).  The controls still run over ALL rows of a batch's frames (of the chunk's, in the passes
+            over several ranks, which gather the kept rows of every rank): the kept rows are scattered into zeros by row_of, the
+            launch is the one of the call that skips nothing -- per-row values (gain, offset, override ...) and the row masks
+            stay indexed by the full rows -- and the kept rows of its result are gathered back.  Under follow_tracks an absent row
+            neither reads nor writes a stream, so the kept rows and the streams' state after the call are those of the call that
+            skips nothing; a control that carries state (smooth_pose, expression relative / smooth, head_pose relative) therefore
+            needs follow_tracks=True beside it (ValueError), as_uint8=False is not served (ValueError), and where tracks can
+            restart a batch without a face still launches those controls, over zeros, so that a death in it clears its stream.
+            Ranks shard by frames; the result does not depend on batch_size, the chunking or the number of ranks.  tracked_rows
+            is left as (row_of int32 [T] on the device: the row of the chunk that each kept row is; first: the kept rows in
+            front of every frame of the chunk, a host list of n + 1; the index of the chunk's first row); tracked_windows,
+            tracked_present and tracked_assignment stay in the full row space.  Not done: animate_streams (ValueError),
+            enrol_identities, sharding the ranks by kept rows, padding the batches to a few fixed shapes, hiding the host wait
+            behind a tracker stream of its own."""
         if isinstance(frames, torch.Tensor):
             frames_mod.check_frames(frames, frame_format)
         n_rows, counts = frames.shape[0] if isinstance(frames, torch.Tensor) else None, None
@@ -1452,6 +1480,15 @@ class InferenceWrapper:
             self._yuv420_size(masks_of, out_format)
         out_kind = "f32" if paste_back or not as_uint8 else ("u8" if out_format == "rgb8" else out_format)
         ex, hp = self._control_plans(expression, head_pose, n_rows, ids, where, target_theta, faces)
+        if track is not None and track.skip_absent:
+            if not as_uint8:
+                raise ValueError("tracking skip_absent=True yields the rows that have a face: as_uint8=False (the render's own output "
+                                 "buffer, one row per slot) is not served")
+            stateful = [name for name, on in (("smooth_pose", smooth_pose), ("expression relative / smooth", ex is not None and ex.scan),
+                                              ("head_pose relative", hp is not None and hp.relative)) if on]
+            if stateful and not track.follow_tracks:
+                raise ValueError(f"tracking skip_absent=True with {stateful[0]}: without follow_tracks=True a row without a face is a "
+                                 f"step of its identity's stream and cannot be left out: pass follow_tracks=True as well")
         host_ring = None if not to_host else (frames_mod.ArenaRing(self.device, ring) if arena and paste_back
                                               else frames_mod.HostRing(self.device, ring, batch_size))
         return Namespace(masks_of=masks_of, ids=ids, matte_fn=matte_fn, out_kind=out_kind, fmt=(frame_format, colorspace, bool(full_range)),
@@ -1459,19 +1496,44 @@ class InferenceWrapper:
                          batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta, ex=ex,
                          hp=hp, track=track, min_side=min_side, row_masks=None)
 
-    def _batch_theta(self, crops, ident, plan, row0, edit=True, mix=True, smooth=None):
+    def _over_full_rows(self, full, control, *inputs):
+        """tracking skip_absent=True: a control launch of kept rows over the full rows they were taken from.  full = (at, slots, r0,
+        n): at int64 [m] on the device = where each kept row lies among the n full rows r0 ... r0 + n of the call, slots = the
+        identities of those n rows (None: the current identity).  inputs [m, ...] are scattered into zeros [n, ...] (an absent row
+        reads zeros), control(*full inputs, slots, r0) is the launch of the call that skips nothing -- per-row values and row masks
+        indexed by the full rows -- and its result, a tensor or a tuple of tensors over the n rows, comes back as the kept rows."""
+        at, slots, r0, n = full
+        wide = []
+        for t in inputs:
+            t = t.to(self.device).float()
+            wide.append(torch.zeros((n,) + tuple(t.shape[1:]), device=self.device, dtype=t.dtype).index_copy_(0, at, t))
+        out = control(*wide, slots, r0)
+        if isinstance(out, tuple):
+            return tuple(t.index_select(0, at) for t in out)
+        return out.index_select(0, at)
+
+    def _batch_theta(self, crops, ident, plan, row0, edit=True, mix=True, smooth=None, full=None):
         """The front of a driver batch of the video paths, crops [m,3,S,S] = the rows row0 ... of the call -> (theta, align): the head
         pose the regressor finds, edited per row by the head-pose controls (plan.hp) and then mixed, and what the expression embedder
         aligns the crops by -- under an active head-pose edit the regressor's OWN theta of the rows, else None = the theta the batch
         is rendered with.  Either may be the regressor's output buffer: a caller that holds it past the batch clones it.
         edit=False: a pass that gathers the rows of every rank edits them, and in theta's place come the regressed (scale, rotation,
         translation) as [m,9] rows.  mix=False: the caller mixes, once over its rows of the chunk.  smooth: None = mix alone, and
-        only where plan.mix asks for it (a clip); a bool = mix and the one-pass smooth_pose of the batch's rows (streams)."""
+        only where plan.mix asks for it (a clip); a bool = mix and the one-pass smooth_pose of the batch's rows (streams).
+        full: tracking skip_absent=True -- the crops are the kept rows of whole frames, and the head-pose controls run over the full
+        rows of those frames (_over_full_rows); mix has neither state nor per-row values and stays on the kept rows."""
         theta, *srt = self._head_pose(crops)
         align = None
         if plan.hp is not None:
             align = theta
-            theta = self._head_pose_controls(srt, ident, plan.hp, row0, plan.row_masks)[1] if edit else self._srt9(srt)
+            if not edit:
+                theta = self._srt9(srt)
+            elif full is None:
+                theta = self._head_pose_controls(srt, ident, plan.hp, row0, plan.row_masks)[1]
+            else:
+                edited, theta = self._over_full_rows(full, lambda a, b, c, slots, r: self._head_pose_controls(
+                    (a, b, c), slots, plan.hp, r, plan.row_masks), *srt)
+                self.pred_target_srt = tuple(edited[:, i:i + 3] for i in (0, 3, 6))
         if mix and (plan.mix or smooth is not None):
             theta = self._pose_controls(theta, ident, plan.mix, plan.mix_old, bool(smooth), row0, plan.row_masks)
         return theta, align
@@ -1480,24 +1542,27 @@ class InferenceWrapper:
         """the expression embedder on a driver batch: its crops aligned by `align` (_batch_theta), or by the theta it is rendered with"""
         return self._expression(crops, theta if align is None else align, 'a driver call')[0]
 
-    def _drive_crops(self, crops, ident, plan, theta=None, smooth=None, row0=0, pose=None, align=None):
+    def _drive_crops(self, crops, ident, plan, theta=None, smooth=None, row0=0, pose=None, align=None, full=None):
         """The sequence of one driver batch of the video paths, crops [m,3,S,S] -> (the rendered batch as plan.out_kind says, its
         paste matte or None): head pose -> head-pose controls -> pose controls (_batch_theta) -> expression embedder (or the
         override) -> expression controls -> render -> matte, in forward()'s order.  row0: the batch's first row in the call (the
         controls' per-row values).  theta, align: the batch's thetas and what the embedder aligns by where a pass in front of the
         loop has formed them (the passes of a clip that walk the rows of several ranks); pose: its controlled expressions
-        likewise.  smooth: _batch_theta's."""
+        likewise.  smooth, full: _batch_theta's; with `full` the override is read and the expression controls run over the full rows."""
         if theta is None:
-            theta, align = self._batch_theta(crops, ident, plan, row0, smooth=smooth)
+            theta, align = self._batch_theta(crops, ident, plan, row0, smooth=smooth, full=full)
         self.pred_target_theta = theta                                           # (as forward() leaves it: infer.py:584)
         ex = plan.ex
         if pose is None:
             if ex is not None and ex.override is not None:
-                pose = control_streams.rows_of(ex.override, row0, crops.shape[0], 'expression override')
+                pose = control_streams.rows_of(ex.override, row0, crops.shape[0], 'expression override') if full is None else \
+                    control_streams.rows_of(ex.override, full[2], full[3], 'expression override').index_select(0, full[0])
             else:
                 pose = self._batch_expression(crops, theta, align)
-            if ex is not None:
+            if ex is not None and full is None:
                 pose = self._expression_controls(pose, ident, ex, row0, plan.row_masks)
+            elif ex is not None:
+                pose = self._over_full_rows(full, lambda v, slots, r: self._expression_controls(v, slots, ex, r, plan.row_masks), pose)
         out = self._render(pose, theta, ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
         return out, (None if plan.matte_fn is None else plan.matte_fn(out).float().contiguous())
 
@@ -1554,10 +1619,20 @@ class InferenceWrapper:
         chunk are formed on the device in front of its batches (_track_chunk), P rows per frame where the boxes are [N,P,4].
         A chunk is rendered in up to three passes over the spans of the rank's frames, each through `walk`: the head-pose pass
         (smooth_pose, or a relative head pose on several ranks) and the expression pass (relative / smooth on several ranks) form
-        the thetas and the expressions that follow the frame order across the ranks (`scan`), the render pass drives the batches."""
+        the thetas and the expressions that follow the frame order across the ranks (`scan`), the render pass drives the batches.
+        tracking skip_absent=True: the rows of the loop are the KEPT rows, those the tracker found a face for.  The chunk is
+        tracked first, ONE launch over all its rows on every rank puts the present rows and their windows first
+        (ops.present_rows), and the number of faces of every frame is copied to the host -- the one host wait per chunk the field
+        adds, on every rank.  From there per[i] is that number, exactly as faces= counts its faces: the spans hold at most
+        batch_size kept rows, the crop, the networks, the paste and what is yielded see kept rows only, and the identities are
+        ids[row_of].  The controls alone still run over the full rows of a span's frames (_over_full_rows; over the chunk's in
+        `scan`), and where a track can restart a span without a kept row still launches the controls that carry state, over
+        zeros: a death in it clears its stream as it does in the call that skips nothing.  tracked_rows = (row_of [T], first,
+        the chunk's first full row); tracked_windows, tracked_present and tracked_assignment stay in the full row space."""
         S, ids, paste_back, ex, hp = self.cfg["image_size"], plan.ids, plan.paste_back, plan.ex, plan.hp
         P = None if plan.track is None else plan.track.tracks
-        base = row0 = 0
+        skip = plan.track is not None and plan.track.skip_absent
+        base = row0 = full0 = 0                                                  # (full0: the chunk's first full row, under skip)
         for chunk in [frames] if isinstance(frames, torch.Tensor) else frames:
             frames_mod.check_frames(chunk, plan.fmt[0])
             n = chunk.shape[0]
@@ -1566,8 +1641,20 @@ class InferenceWrapper:
             # which rows a span of frames holds: per[i] = the rows of the chunk's frame i -- the faces of faces=, the P tracks of boxes
             # [N,P,4], or None for one row per frame and the per-frame entry points (windows=, boxes [N,4], whole frames)
             per = [P] * n if P is not None else None if counts is None else counts[base:base + n]
+            tracked = row_of = None
+            if skip and not n:
+                tracked, row_of = self._track_chunk(plan, n, base, None, full0), torch.empty((0,), dtype=torch.int64, device=self.device)
+            elif skip:
+                if ids is not None and full0 + n * P > ids.shape[0]:
+                    raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
+                tracked = self._track_chunk(plan, n, base, frames_mod.frame_size(chunk, plan.fmt[0]), full0)
+                count, _, row_of, *tracked = ops.present_rows(tracked[0].tensor, tracked[1].tensor, n, P)
+                per = count.tolist()                                             # (the host wait of the chunk)
+                self.tracked_rows = (row_of[:sum(per)], frames_mod.face_offsets(per), full0)
+                row_of = self.tracked_rows[0].long()
+                tracked = [ops.DeviceWindows(w) for w in tracked]
             off = frames_mod.face_offsets([1] * n if per is None else per)
-            if counts is None and ids is not None and row0 + off[n] > ids.shape[0]:
+            if counts is None and not skip and ids is not None and row0 + off[n] > ids.shape[0]:
                 raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
             rows = lambda b0, b1: (row0 + off[b0], row0 + off[b1])              # the rows of the chunk's frames [b0, b1)
             frame_of = lambda b0, b1: None if per is None else [i - b0 for i in range(b0, b1) for _ in range(per[i])]
@@ -1578,11 +1665,23 @@ class InferenceWrapper:
             # of something that has one entry per row of the rank's shard of the chunk, the entries of the frames [b0, b1)
             part = lambda t, b0, b1: None if t is None else t[rows(b0, b1)[0] - m_lo:rows(b0, b1)[1] - m_lo]
             crop_w = paste_w = None if wins is None else wins[m_lo:m_hi]
-            if plan.track is not None:
+            if tracked is not None:
+                crop_w, paste_w = (w[m_lo - r0:m_hi - r0] for w in tracked)      # (the kept rows' windows, compacted)
+            elif plan.track is not None:
                 # every rank tracks the whole chunk (the boxes are inputs every rank has), then slices its batches' windows
                 crop_w, paste_w = (w[m_lo - r0:m_hi - r0]
                                    for w in self._track_chunk(plan, n, base, frames_mod.frame_size(chunk, plan.fmt[0]), r0))
             ids_dev = None if ids is None else ids[m_lo:m_hi].to(self.device)
+            full_of = lambda b0, b1: None
+            if skip:
+                ids_full = None if ids is None else ids[full0:full0 + n * P].to(self.device)
+                ids_dev = None if ids is None else ids_full.index_select(0, row_of[m_lo - r0:m_hi - r0])
+                # of the frames [b0, b1): where their kept rows lie among their full rows, those rows' slots, the first, their number
+                full_of = lambda b0, b1: (row_of[off[b0]:off[b1]] - b0 * P, None if ids is None else ids_full[b0 * P:b1 * P],
+                                          full0 + b0 * P, (b1 - b0) * P)
+            # a track that restarts does so whether or not its row is kept: under skip, with restart flags, the spans without a
+            # kept row still launch the controls that carry state from batch to batch on this rank
+            restarts = skip and plan.row_masks is not None and plan.row_masks[0] is not None
             # crops stay resident from one pass to the next (3 MB per frame at 512^2) while the rank's rows of the chunk fit the budget
             keep = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
             kept, thetas, aligns, poses = {}, {}, {}, None
@@ -1594,11 +1693,12 @@ class InferenceWrapper:
                 paste_back: the crops were kept, not the frames, 6 MB at 1080p; a span without a face then comes with crops None).
                 The last pass lets go of what was kept."""
                 pasted = last and paste_back
-                need = spans if pasted else with_faces
-                fresh = frames_mod.uploaded(chunk, [sp for sp in need if pasted or sp[0] not in kept], self.device, plan.upload_stream)
+                need = spans if pasted or restarts else with_faces              # (restarts: walk's callers launch `absent`)
+                fresh = frames_mod.uploaded(chunk, [sp for sp in need if pasted or sp[0] not in kept and sp in with_faces], self.device,
+                                            plan.upload_stream)
                 for b0, b1 in need:
                     crops, u8 = kept.pop(b0, None) if last else kept.get(b0), None
-                    if crops is None or pasted:
+                    if pasted or crops is None and (b0, b1) in with_faces:
                         f0, f1, u8 = next(fresh)
                         assert (f0, f1) == (b0, b1)
                     if crops is None and (b0, b1) in with_faces:
@@ -1614,8 +1714,23 @@ class InferenceWrapper:
                 whichever rank formed a row -- and the rank's own rows of the result come back."""
                 if every is None:
                     per_rank = [rows(*parallel.shard_range(n, r, self.world)) for r in range(self.world)]
-                    every = parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)
+                    every = local if skip and r1 == r0 else parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)
+                    if skip:                                                     # the chunk's kept rows -> its full rows, absent ones zeros
+                        every = torch.zeros((n * P,) + tuple(every.shape[1:]), device=self.device, dtype=every.dtype).index_copy_(0, row_of, every)
+                if skip:
+                    return control(every, ids_full, full0).index_select(0, row_of)[m_lo - r0:m_hi - r0]
                 return control(every, None if ids is None else ids[r0:r1].to(self.device), r0)[m_lo - r0:m_hi - r0]
+
+            def absent(b0, b1, head, expression):
+                """skip with restart flags: the frames [b0, b1) hold no kept row, and the controls that carry state from batch to
+                batch on this rank are still launched over their rows, as zeros: a restart in them reaches its stream"""
+                full = full_of(b0, b1)
+                if head and hp is not None and hp.relative and not gather_srt:
+                    zeros = tuple(torch.zeros((full[3], 3), device=self.device) for _ in range(3))
+                    self._head_pose_controls(zeros, full[1], hp, full[2], plan.row_masks)
+                if expression and ex is not None and ex.scan and self.world == 1:
+                    E = self._bank_expr.shape[1] if self._bank_expr is not None else self.cfg["lpe_output_channels_expression"]
+                    self._expression_controls(torch.zeros((full[3], E), device=self.device), full[1], ex, full[2], plan.row_masks)
 
             # a relative head pose walks the rows of every rank: their regressed (scale, rotation, translation) are gathered and edited
             # on every rank, so the anchor is the stream's first row whichever rank regressed it
@@ -1623,7 +1738,11 @@ class InferenceWrapper:
             if plan.smooth_pose or gather_srt:
                 local = []
                 for b0, b1, crops, _ in walk():
-                    theta, align = self._batch_theta(crops, part(ids_dev, b0, b1), plan, rows(b0, b1)[0], edit=not gather_srt, mix=False)
+                    if crops is None:
+                        absent(b0, b1, True, False)
+                        continue
+                    theta, align = self._batch_theta(crops, part(ids_dev, b0, b1), plan, rows(b0, b1)[0], edit=not gather_srt, mix=False,
+                                                     full=full_of(b0, b1))
                     if align is not None:
                         aligns[b0] = align.clone()
                     local.append(theta.clone() if align is None else theta)
@@ -1641,12 +1760,15 @@ class InferenceWrapper:
                 # relative / smooth walk the rows of every rank: the expressions of the rank's rows, or the override's, which every rank has
                 control = lambda every, slots, r: self._expression_controls(every, slots, ex, r, plan.row_masks)
                 if ex.override is not None:
-                    poses = scan(control, every=control_streams.rows_of(ex.override, r0, r1 - r0, 'expression override'))
+                    poses = scan(control, every=control_streams.rows_of(ex.override, *((full0, n * P) if skip else (r0, r1 - r0)),
+                                                                        'expression override'))
                 else:
                     local = []
                     for b0, b1, crops, _ in walk():
+                        if crops is None:                                        # (restarts: nothing here carries state on this rank alone)
+                            continue
                         if b0 not in thetas:
-                            theta, align = self._batch_theta(crops, part(ids_dev, b0, b1), plan, rows(b0, b1)[0])
+                            theta, align = self._batch_theta(crops, part(ids_dev, b0, b1), plan, rows(b0, b1)[0], full=full_of(b0, b1))
                             if align is not None:
                                 aligns[b0] = align.clone()
                             thetas[b0] = theta.clone()
@@ -1659,11 +1781,15 @@ class InferenceWrapper:
                     poses = scan(control, local)
             for b0, b1, crops, u8 in walk(last=True):
                 m0 = rows(b0, b1)[0]
+                if crops is None and restarts:                                   # (the head pose: unless a pass in front has walked it)
+                    absent(b0, b1, not plan.smooth_pose, True)
+                    if not paste_back:
+                        continue
                 if crops is None:                                                # (paste_back: frames without a face, as they came)
                     out = u8.clone() if chunk.is_cuda else u8
                 else:
                     out, m = self._drive_crops(crops, part(ids_dev, b0, b1), plan, thetas.pop(b0, None), row0=m0, pose=part(poses, b0, b1),
-                                               align=aligns.pop(b0, None))
+                                               align=aligns.pop(b0, None), full=full_of(b0, b1))
                     if paste_back:
                         full = u8.clone() if chunk.is_cuda else u8               # (a host chunk's upload is this span's own)
                         out = frames_mod.paste_into(full, out, part(paste_w, b0, b1), plan.feather, m, *plan.fmt, frame_of=frame_of(b0, b1))
@@ -1672,7 +1798,7 @@ class InferenceWrapper:
                     yield from plan.ring.push(index, out)
                 else:
                     yield index, out
-            base, row0 = base + n, r1
+            base, row0, full0 = base + n, r1, full0 + (n * P if skip else 0)
         if plan.ring is not None:
             yield from plan.ring.drain()
 
@@ -1726,6 +1852,8 @@ class InferenceWrapper:
         tracked = any('boxes' in st for st in streams)
         if tracking is not None and not tracked:
             raise ValueError("tracking= says how a stream's 'boxes' become windows: no stream has any")
+        if tracking is not None and control_streams.CropTracking.of(tracking).skip_absent:
+            raise ValueError("tracking skip_absent=True is animate_frames': animate_streams renders every row of its streams")
         for k, st in enumerate(streams):
             if tracked:
                 if 'boxes' not in st:

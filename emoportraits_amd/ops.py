@@ -1510,3 +1510,34 @@ def track_assign(dets, stream_of=None, ref=None, age=None, min_iou=0.3, max_miss
                                        hostglue.CROP_BOX_FORMATS[box_format], hip.ptr(boxes), hip.ptr(restart), hip.ptr(track_of),
                                        hip.current_stream()), "emo_track_assign_f64")
     return boxes, restart, track_of
+
+
+def present_rows(crop, paste, F, P):
+    """The present rows of the tracker's windows, first and in order, on the device (emo_present_rows_i32; bit for bit
+    hostglue.present_rows, which states the contract): a stable compaction of the M = F * P frame-major rows of crop_track's
+    crop and paste [M,4] int32 (contiguous, on one device); row i is present iff paste[i][2] > 0.
+    -> (count int32 [F]: the present rows of every frame; first int32 [F + 1]: those in front of every frame, first[F] = T their
+    total; row_of int32 [M]: the index of the j-th present row, -1 from T on; crop_out, paste_out int32 [M,4]: their windows,
+    zeros from T on).  One launch of one block, no host synchronisation."""
+    from . import hostglue
+    lib = hip.load()
+    F, P = int(F), int(P)
+    if F <= 0 or not 1 <= P <= hostglue.TRACK_MAX_TRACKS or F * P > hostglue.PRESENT_MAX_ROWS:
+        raise ValueError(f"present_rows: F = {F} frames of P = {P} rows: F >= 1, 1 <= P <= {hostglue.TRACK_MAX_TRACKS}, F * P <= 2^24")
+    M = F * P
+    for t, name in ((crop, "crop"), (paste, "paste")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (M, 4) or not t.is_contiguous():
+            raise ValueError(f"present_rows: {name} must be a contiguous int32 [{M},4] tensor, got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+    dev = crop.device
+    if paste.device != dev:
+        raise ValueError("present_rows: crop and paste are on different devices")
+    hip.require_cuda_f32(torch.empty(0, device=dev))                         # (GPU only, like every op)
+    count = torch.empty((F,), device=dev, dtype=torch.int32)
+    first = torch.empty((F + 1,), device=dev, dtype=torch.int32)
+    row_of = torch.empty((M,), device=dev, dtype=torch.int32)
+    crop_out = torch.empty((M, 4), device=dev, dtype=torch.int32)
+    paste_out = torch.empty((M, 4), device=dev, dtype=torch.int32)
+    hip.check(lib.emo_present_rows_i32(hip.ptr(crop), hip.ptr(paste), F, P, hip.ptr(count), hip.ptr(first), hip.ptr(row_of),
+                                       hip.ptr(crop_out), hip.ptr(paste_out), hip.current_stream()), "emo_present_rows_i32")
+    return count, first, row_of, crop_out, paste_out

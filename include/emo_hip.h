@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 26
+#define EMO_ABI_VERSION 27
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -654,6 +654,23 @@ int emo_head_pose_controls_tracks_f32(const float* scale, int scale_cols, const 
                                       const float* translation_offset, const float* zoom, float* anchor, int32_t* has_anchor, int n,
                                       int K, int relative, int frontal, const int32_t* restart, const int32_t* present,
                                       float* out_srt, float* out_theta, void* stream);
+/* ABI 27.  The present rows of the crop tracker's windows, first and in order: a stable stream compaction of the M = F * P
+ * frame-major rows (frame f holds the rows f * P ... f * P + P - 1) that emo_crop_track(_restarts)_f64 wrote, so that a caller
+ * renders the faces that are there and no slot that is empty.
+ *   crop, paste [M,4] int32 DEVICE memory: the tracker's windows.  Row i is present iff paste[i][2] > 0 (a side of 0, whatever
+ *   its x and y, and a negative side are absent).  count [F], first [F + 1], row_of [M], crop_out [M,4], paste_out [M,4] int32.
+ *   first[f], f = 0 ... F: the number of present rows with an index < f * P; first[F] = T, their total.
+ *   count[f] = first[f + 1] - first[f], the present rows of frame f.
+ *   j < T:   row_of[j] = the index of the j-th present row, ascending; crop_out[j] = crop[row_of[j]], paste_out[j] =
+ *            paste[row_of[j]], the four values as they are.
+ *   T <= j < M:  row_of[j] = -1, crop_out[j] = paste_out[j] = (0, 0, 0, 0).
+ * Every element of every output is written -- bit for bit hostglue.present_rows.  EMO_ERR_BAD_ARG before any launch: a NULL
+ * pointer; F <= 0; P outside 1 ... 16; F * P > 2^24; an output that overlaps crop or paste.  EMO_ERR_ALIGN: a window array that is
+ * not 16-byte aligned (a row moves as one 16-byte load and one 16-byte store).  One block of 256 threads, each owning a contiguous
+ * run of rows: the runs are counted, the run totals meet in LDS behind one barrier, every thread sums those in front of it and
+ * writes its run.  Integer sums only: the result does not depend on the block's shape; no atomics. */
+int emo_present_rows_i32(const int32_t* crop, const int32_t* paste, int F, int P, int32_t* count, int32_t* first, int32_t* row_of,
+                         int32_t* crop_out, int32_t* paste_out, void* stream);
 int emo_pack_rgb8(const float* img, uint8_t* out, int N, int H, int W, void* stream);
 int emo_unpack_rgb8(const uint8_t* in, float* out, int N, int H, int W, void* stream);
 

@@ -22,6 +22,8 @@
         [--follow-tracks]   # with --boxes / --detections: --smooth-pose, --relative-expression / --smooth-expression and
          --relative-pose follow the face tracks (tracking follow_tracks=True): a new face in a freed slot starts its own streams, and a
          frame without a face leaves no mark on them
+        [--skip-absent]     # with --boxes [N,P,4] / --detections: a track slot without a face is not rendered (tracking
+         skip_absent=True); the controls that carry state then need --follow-tracks
         [--paste-back [--feather F]]   # with --windows: write the FULL frames, the rendered head pasted back where its window was
         [--stage2-experiment <exp2> --stage2-checkpoint <file> [--cloth]       # refine every batch with the stage-2 model
          (--embedders module:factory | --refine-everywhere)]                   # (<project>/logs_s2/<exp2>), inside the same path
@@ -131,6 +133,8 @@ def main():
     ap.add_argument("--max-missed", type=int, default=15, help="with --detections: frames a track may go without a detection")
     ap.add_argument("--follow-tracks", action="store_true", help="with --boxes / --detections: the pose and expression streams restart at a "
                                                                  "track's birth and skip the frames without a face")
+    ap.add_argument("--skip-absent", action="store_true", help="with --boxes [N,P,4] / --detections: render only the track slots that hold "
+                                                               "a face")
     ap.add_argument("--sources", default=None, help="comma-separated source images enrolled into bank slots 0, 1, ... (--identities)")
     ap.add_argument("--identities", default=None, help="JSON list: the bank slot of every frame, or with --faces of every face")
     ap.add_argument("--out", required=True)
@@ -190,6 +194,8 @@ def main():
         ap.error("--box-format / --smooth-crop / --fixed-crop / --crop-scale / --hold-missing belong to --boxes / --detections")
     if a.follow_tracks and not (a.boxes or a.detections):
         ap.error("--follow-tracks belongs to --boxes / --detections")
+    if a.skip_absent and not (a.boxes or a.detections):
+        ap.error("--skip-absent belongs to --boxes / --detections")
     if (a.crop_momentum is not None or a.fixed_crop) and not a.smooth_crop:
         ap.error("--crop-momentum / --fixed-crop belong to --smooth-crop")
     if a.crop_momentum is not None and not 0.0 < a.crop_momentum <= 1.0:
@@ -250,13 +256,13 @@ def main():
     if a.boxes:
         boxes = load_boxes(a.boxes)
         tracking = dict(smooth=a.smooth_crop, momentum=a.crop_momentum, fixed=a.fixed_crop, scale=a.crop_scale, box_format=a.box_format,
-                        missing="hold" if a.hold_missing else "skip", follow_tracks=a.follow_tracks)
+                        missing="hold" if a.hold_missing else "skip", follow_tracks=a.follow_tracks, skip_absent=a.skip_absent)
     detections = None
     if a.detections:
         detections = load_detections(a.detections)
         tracking = dict(smooth=a.smooth_crop, momentum=a.crop_momentum, fixed=a.fixed_crop, scale=a.crop_scale, box_format=a.box_format,
                         missing="hold" if a.hold_missing else "skip", tracks=a.tracks, min_iou=a.min_iou, max_missed=a.max_missed,
-                        follow_tracks=a.follow_tracks)
+                        follow_tracks=a.follow_tracks, skip_absent=a.skip_absent)
     identities = None
     if sources:
         w.enrol_identities([Image.open(f).convert("RGB") for f in sources], slots=list(range(len(sources))), batch_size=a.batch)
