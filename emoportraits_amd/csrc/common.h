@@ -15,6 +15,10 @@ static inline bool emo_aligned16(const void* p) { return (((uintptr_t)p) & 15u) 
 
 static inline int emo_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// groupnorm.hip's half of emo_op_launch_form (resample.hip; ABI 28): the plan of emo_groupnorm_affine_f32's own pass for
+// dims = (N, C, S, G); launches nothing
+int emo_groupnorm_launch_plan(const void* x, const int64_t* dims, int64_t* plan);
+
 // compute units of the CURRENT device (the persistent grids of the split convolution are sized by it), cached per device id.
 // Rounded down to a multiple of 8, and at least 8: those kernels hand out their work items in eight contiguous ranges, one per
 // XCD (block b walks the range of XCD b % 8: conv_igemm_bf16x3.h), so a grid of min(items, this) blocks covers every item only

@@ -88,7 +88,13 @@ __global__ __launch_bounds__(256) void grid_sample2d_kernel(const float* __restr
     const float fx = floorf(ix), fy = floorf(iy);
     const float w = __fsub_rn(ix, fx), e = __fsub_rn(1.0f, w);
     const float s_ = __fsub_rn(iy, fy), n_ = __fsub_rn(1.0f, s_);   // s_: weight of the south row, n_: north row
-    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
+    // A grid value of +-Inf, NaN or beyond +-2^31 pixels: the conversion of such a float is undefined in C++ (the device
+    // saturates it to INT_MAX) and x0 + 1 then overflows, which let the compiler test x1 >= 0 as x0 > -2 and x1 < W on the wrapped
+    // sum -- both true at INT_MAX, and the tap was loaded 2^31 floats in front of the row.  The floors are held to [-2, 2^31 - 128]
+    // (the largest float below 2^31) before they are converted: every corner of such a sample fails its range test, as in ATen;
+    // a floor inside [-2, W] -- every corner that can be in range -- converts as before.  The weights keep the unclamped values.
+    const int x0 = (int)fminf(fmaxf(fx, -2.0f), 2147483520.0f), y0 = (int)fminf(fmaxf(fy, -2.0f), 2147483520.0f);
+    const int x1 = x0 + 1, y1 = y0 + 1;
     const bool okx0 = x0 >= 0 && x0 < W, okx1 = x1 >= 0 && x1 < W, oky0 = y0 >= 0 && y0 < H, oky1 = y1 >= 0 && y1 < H;
     const float wnw = __fmul_rn(n_, e), wne = __fmul_rn(n_, w), wsw = __fmul_rn(s_, e), wse = __fmul_rn(s_, w);
     for (int c = 0; c < C; ++c) {

@@ -164,7 +164,36 @@ __global__ __launch_bounds__(256) void gn_from_tiles_kernel(const float2* __rest
   }
 }
 
+// The plan of the own pass, decided once: gn_partial_kernel's grid is (N G runs) x split, a slice of at least 16384 elements
+// where the run is that long.  rc: what the launcher returns for these arguments before any launch
+struct GnPlan { int rc; long L; int split; };
+
+inline GnPlan gn_plan(const void* x, int N, int C, int64_t S, int G) {
+  GnPlan p = {EMO_OK, 0, 1};
+  if (!x || N <= 0 || C <= 0 || S <= 0 || G <= 0 || C % G) { p.rc = EMO_ERR_BAD_ARG; return p; }
+  if ((long)N * G > 0x7fffffffL) { p.rc = EMO_ERR_UNSUPPORTED; return p; }
+  p.L = (long)(C / G) * S;
+  int split = (int)((p.L + 16383) / 16384);
+  if (split < 1) split = 1;
+  if (split > GN_MAX_SPLIT) split = GN_MAX_SPLIT;
+  p.split = split;
+  return p;
+}
+
 }  // namespace
+
+int emo_groupnorm_launch_plan(const void* x, const int64_t* dims, int64_t* plan) {
+  if (dims[0] != (int64_t)(int)dims[0] || dims[1] != (int64_t)(int)dims[1] || dims[3] != (int64_t)(int)dims[3]) return EMO_ERR_BAD_ARG;
+  const GnPlan p = gn_plan(x, (int)dims[0], (int)dims[1], dims[2], (int)dims[3]);
+  if (p.rc != EMO_OK) return p.rc;
+  plan[EMO_OP_PLAN_FORM] = EMO_GROUPNORM_FORM_PASS;
+  plan[EMO_OP_PLAN_RUNS] = dims[0] * dims[3];
+  plan[EMO_OP_PLAN_SPLIT] = p.split;
+  plan[EMO_OP_PLAN_GRID] = dims[0] * dims[3] * p.split;
+  plan[EMO_OP_PLAN_RUN_ITEMS] = p.L;
+  plan[EMO_OP_PLAN_ITEMS] = dims[0] * dims[3] * p.L;
+  return EMO_OK;
+}
 
 extern "C" int64_t emo_groupnorm_workspace_bytes(int N, int G) {
   if (N <= 0 || G <= 0) return EMO_ERR_BAD_ARG;
@@ -180,11 +209,10 @@ extern "C" int emo_groupnorm_affine_f32(const float* x, int N, int C, int64_t S,
   if ((ada_gamma == nullptr) != (ada_beta == nullptr)) return EMO_ERR_BAD_ARG;
   if ((mean_out == nullptr) != (rstd_out == nullptr)) return EMO_ERR_BAD_ARG;
   if (workspace_bytes < emo_groupnorm_workspace_bytes(N, G)) return EMO_ERR_BAD_ARG;
-  if ((long)N * G > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
-  const long L = (long)(C / G) * S;
-  int split = (int)((L + 16383) / 16384);
-  if (split < 1) split = 1;
-  if (split > GN_MAX_SPLIT) split = GN_MAX_SPLIT;
+  const GnPlan p = gn_plan(x, N, C, S, G);
+  if (p.rc != EMO_OK) return p.rc;
+  const long L = p.L;
+  const int split = p.split;
   hipStream_t s = (hipStream_t)stream;
   double* part = reinterpret_cast<double*>(workspace);
   hipLaunchKernelGGL(gn_partial_kernel, dim3(N * G, split), dim3(256), 0, s, x, L, split, part);

@@ -290,8 +290,14 @@ __global__ __launch_bounds__(256) void add_rows_indexed_kernel(const float* __re
 // UpSampleBilinear2d / UpSampleBicubic2d: area_pixel_compute_source_index + cubic convolution, A = -0.75).
 // Wrapper glue of the reference: bicubic resize of source / driver crops to image_size (notebooks/infer.py:399-401,
 // :548-552), bilinear resize to output_size_s2 (notebooks/infer_s2.py:360-362).
-__device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f; }
-__device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.0f * A) * x + 8.0f * A) * x - 4.0f * A; }
+// The two cubic-convolution polynomials in Horner form, every step one FMA.  The coefficients reach 8 |A| = 6 while the weights sum
+// to 1, so each rounding of a step shows in the weight at up to 3e-07; with a product and a sum rounded apart the four weights of
+// an axis came to 1 + 4.8e-07 (t = 2/3), on a one-pixel plane 1.8 x the error of ATen's CPU kernel
+// (tests/test_op_launch_forms_gpu.py, `bicubic (1, 1) to (5, 3)`).  At t = 0 every step is exact: the weights are (0, 1, 0, 0).
+__device__ __forceinline__ float cubic1(float x, float A) { return __fmaf_rn(__fmaf_rn(A + 2.0f, x, -(A + 3.0f)) * x, x, 1.0f); }
+__device__ __forceinline__ float cubic2(float x, float A) {
+  return __fmaf_rn(__fmaf_rn(__fmaf_rn(A, x, -5.0f * A), x, 8.0f * A), x, -4.0f * A);
+}
 
 // The bicubic sample at source index (sy, sx) of an H x W window, C channels at once: fraction, A = -0.75 weights and 4 x 4 taps
 // clamped into the WINDOW, rows first.  tap(yy, xx, w, row) adds the C values of window pixel (yy, xx) times w to row -- a float
@@ -662,23 +668,80 @@ inline int grid_for(long total) {
   return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
 
-}  // namespace
+// ---- The launch forms of the two launchers that have more than one (ABI 28): each decided by ONE host function, which its
+// launcher calls and emo_op_launch_form reports.  rc: what the launcher returns before any launch (EMO_OK: it launches `form`).
 
-extern "C" int emo_upsample_trilinear_f32(const float* x, float* out, int64_t NC, int D, int H, int W, int fd, int fh,
-                                          int fw, void* stream) {
-  if (!x || !out || NC <= 0 || D <= 0 || H <= 0 || W <= 0) return EMO_ERR_BAD_ARG;
-  if ((fd != 1 && fd != 2) || (fh != 1 && fh != 2) || (fw != 1 && fw != 2)) return EMO_ERR_UNSUPPORTED;
-  const long total = NC * D * fd * H * fh * W * fw;
+// emo_upsample_trilinear_f32 (stats = false) and emo_upsample_trilinear_gn_sums_f32 (stats = true: the run is the GroupNorm group,
+// cr = the channels of a group, and there is no generic form to fall back to).  grid = runs x split blocks; items = the thread
+// blocks of outputs (block kernel) or the outputs (generic kernel) of the launch
+struct UpsForm { int rc, form; long cr, runs, qrun, items; unsigned split, per; long grid; };
+
+inline UpsForm ups_form(const void* x, const void* out, long NC, int D, int H, int W, int fd, int fh, int fw) {
+  UpsForm f = {EMO_OK, EMO_UPSAMPLE_FORM_GENERIC, 1, 0, 0, 0, 1, 0, 0};
+  if (!x || !out || NC <= 0 || D <= 0 || H <= 0 || W <= 0) { f.rc = EMO_ERR_BAD_ARG; return f; }
+  if ((fd != 1 && fd != 2) || (fh != 1 && fh != 2) || (fw != 1 && fw != 2)) { f.rc = EMO_ERR_UNSUPPORTED; return f; }
   const long qvol = (long)(fd == 2 ? D + 1 : D) * (fh == 2 ? H + 1 : H) * (W / 2);      // thread blocks of outputs per volume
   long cr = 1;                                                                         // volumes per run: small ones in groups
   while (qvol * cr < 2048 && NC % (2 * cr) == 0) cr *= 2;
   unsigned split, per;
   if (fw == 2 && (W & 1) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && ups_w2_plan(NC / cr, qvol * cr, split, per)) {
-    hipLaunchKernelGGL(upsample_trilinear_w2_kernel<false>, dim3((unsigned)(NC / cr), split), dim3(256), 0, (hipStream_t)stream,
-                       x, out, (unsigned)(qvol * cr), per, (unsigned)cr, D, H, W, fd, fh, (double*)nullptr);
+    f.form = EMO_UPSAMPLE_FORM_BLOCK;
+    f.cr = cr; f.runs = NC / cr; f.qrun = qvol * cr; f.split = split; f.per = per;
+    f.items = f.qrun * f.runs; f.grid = f.runs * split;
+    return f;
+  }
+  f.items = NC * D * fd * H * fh * W * fw;
+  f.grid = grid_for(f.items);
+  return f;
+}
+
+inline UpsForm ups_gn_form(const void* x, const void* out, const void* partial, int64_t partial_bytes, const void* split_out, int N,
+                           int C, int G, int D, int H, int W, int fd, int fh, int fw) {
+  UpsForm f = {EMO_OK, EMO_UPSAMPLE_FORM_BLOCK, 1, 0, 0, 0, 1, 0, 0};
+  if (!x || !out || !partial || !split_out || N <= 0 || C <= 0 || G <= 0 || C % G || D <= 0 || H <= 0 || W <= 0) { f.rc = EMO_ERR_BAD_ARG; return f; }
+  if ((fd != 1 && fd != 2) || (fh != 1 && fh != 2) || fw != 2 || (W & 1)) { f.rc = EMO_ERR_UNSUPPORTED; return f; }
+  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) { f.rc = EMO_ERR_UNSUPPORTED; return f; }
+  if (partial_bytes < (int64_t)N * G * UPS_MAX_SPLIT * 2 * (int64_t)sizeof(double)) { f.rc = EMO_ERR_BAD_ARG; return f; }
+  f.cr = C / G;
+  f.runs = (long)N * G;
+  f.qrun = f.cr * (fd == 2 ? D + 1 : D) * (fh == 2 ? H + 1 : H) * (W / 2);
+  if (!ups_w2_plan(f.runs, f.qrun, f.split, f.per)) { f.rc = EMO_ERR_UNSUPPORTED; return f; }
+  f.items = f.qrun * f.runs; f.grid = f.runs * f.split;
+  return f;
+}
+
+// emo_avgpool_f32: items = the quads of outputs (x4 kernels) or the outputs (generic kernel); grid blocks of 256 threads
+struct PoolForm { int rc, form; long items, grid; };
+
+inline PoolForm pool_form(const void* x, const void* out, long NC, int D, int H, int W, int kd, int kh, int kw) {
+  PoolForm f = {EMO_OK, EMO_AVGPOOL_FORM_GENERIC, 0, 0};
+  if (!x || !out || NC <= 0 || D <= 0 || H <= 0 || W <= 0) { f.rc = EMO_ERR_BAD_ARG; return f; }
+  if (kd < 1 || kh < 1 || kw < 1 || kd > 16 || kh > 16 || kw > 16) { f.rc = EMO_ERR_UNSUPPORTED; return f; }
+  if (D % kd || H % kh || W % kw) { f.rc = EMO_ERR_UNSUPPORTED; return f; }
+  const long total = NC * (D / kd) * (H / kh) * (W / kw);
+  if ((kw == 1 || kw == 2) && W % (4 * kw) == 0 && total / 4 < (1l << 32) &&
+      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
+    f.form = kw == 1 ? EMO_AVGPOOL_FORM_X4_W1 : EMO_AVGPOOL_FORM_X4_W2;
+    f.items = total / 4;
+  } else {
+    f.items = total;
+  }
+  f.grid = grid_for(f.items);
+  return f;
+}
+
+}  // namespace
+
+extern "C" int emo_upsample_trilinear_f32(const float* x, float* out, int64_t NC, int D, int H, int W, int fd, int fh,
+                                          int fw, void* stream) {
+  const UpsForm f = ups_form(x, out, NC, D, H, W, fd, fh, fw);
+  if (f.rc != EMO_OK) return f.rc;
+  if (f.form == EMO_UPSAMPLE_FORM_BLOCK) {
+    hipLaunchKernelGGL(upsample_trilinear_w2_kernel<false>, dim3((unsigned)f.runs, f.split), dim3(256), 0, (hipStream_t)stream,
+                       x, out, (unsigned)f.qrun, f.per, (unsigned)f.cr, D, H, W, fd, fh, (double*)nullptr);
     return emo_launch_status();
   }
-  hipLaunchKernelGGL(upsample_trilinear_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, out,
+  hipLaunchKernelGGL(upsample_trilinear_kernel, dim3((unsigned)f.grid), dim3(256), 0, (hipStream_t)stream, x, out,
                      (long)NC, D, H, W, fd, fh, fw);
   return emo_launch_status();
 }
@@ -691,38 +754,66 @@ extern "C" int emo_upsample_trilinear_f32(const float* x, float* out, int64_t NC
 extern "C" int emo_upsample_trilinear_gn_sums_f32(const float* x, float* out, int N, int C, int G, int D, int H, int W, int fd,
                                                   int fh, int fw, void* partial, int64_t partial_bytes, int* split_out,
                                                   void* stream) {
-  if (!x || !out || !partial || !split_out || N <= 0 || C <= 0 || G <= 0 || C % G || D <= 0 || H <= 0 || W <= 0) return EMO_ERR_BAD_ARG;
-  if ((fd != 1 && fd != 2) || (fh != 1 && fh != 2) || fw != 2 || (W & 1)) return EMO_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return EMO_ERR_UNSUPPORTED;
-  if (partial_bytes < (int64_t)N * G * UPS_MAX_SPLIT * 2 * (int64_t)sizeof(double)) return EMO_ERR_BAD_ARG;
-  const unsigned cpg = (unsigned)(C / G);
-  const long qrun = (long)cpg * (fd == 2 ? D + 1 : D) * (fh == 2 ? H + 1 : H) * (W / 2);
-  unsigned split, per;
-  if (!ups_w2_plan((long)N * G, qrun, split, per)) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(upsample_trilinear_w2_kernel<true>, dim3((unsigned)(N * G), split), dim3(256), 0, (hipStream_t)stream, x, out,
-                     (unsigned)qrun, per, cpg, D, H, W, fd, fh, reinterpret_cast<double*>(partial));
-  *split_out = (int)split;
+  const UpsForm f = ups_gn_form(x, out, partial, partial_bytes, split_out, N, C, G, D, H, W, fd, fh, fw);
+  if (f.rc != EMO_OK) return f.rc;
+  hipLaunchKernelGGL(upsample_trilinear_w2_kernel<true>, dim3((unsigned)f.runs, f.split), dim3(256), 0, (hipStream_t)stream, x, out,
+                     (unsigned)f.qrun, f.per, (unsigned)f.cr, D, H, W, fd, fh, reinterpret_cast<double*>(partial));
+  *split_out = (int)f.split;
   return emo_launch_status();
 }
 
 extern "C" int emo_avgpool_f32(const float* x, float* out, int64_t NC, int D, int H, int W, int kd, int kh, int kw,
                                void* stream) {
-  if (!x || !out || NC <= 0 || D <= 0 || H <= 0 || W <= 0) return EMO_ERR_BAD_ARG;
-  if (kd < 1 || kh < 1 || kw < 1 || kd > 16 || kh > 16 || kw > 16) return EMO_ERR_UNSUPPORTED;
-  if (D % kd || H % kh || W % kw) return EMO_ERR_UNSUPPORTED;
-  const long total = NC * (D / kd) * (H / kh) * (W / kw);
-  if ((kw == 1 || kw == 2) && W % (4 * kw) == 0 && total / 4 < (1l << 32) &&
-      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
-    const long quads = total / 4;
-    if (kw == 1)
-      hipLaunchKernelGGL(avgpool_x4_kernel<1>, dim3(grid_for(quads)), dim3(256), 0, (hipStream_t)stream, x, out, (unsigned)quads, D, H, W, kd, kh);
-    else
-      hipLaunchKernelGGL(avgpool_x4_kernel<2>, dim3(grid_for(quads)), dim3(256), 0, (hipStream_t)stream, x, out, (unsigned)quads, D, H, W, kd, kh);
-    return emo_launch_status();
-  }
-  hipLaunchKernelGGL(avgpool_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, out, (long)NC, D, H,
-                     W, kd, kh, kw);
+  const PoolForm f = pool_form(x, out, NC, D, H, W, kd, kh, kw);
+  if (f.rc != EMO_OK) return f.rc;
+  const dim3 grid((unsigned)f.grid);
+  if (f.form == EMO_AVGPOOL_FORM_X4_W1)
+    hipLaunchKernelGGL(avgpool_x4_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, out, (unsigned)f.items, D, H, W, kd, kh);
+  else if (f.form == EMO_AVGPOOL_FORM_X4_W2)
+    hipLaunchKernelGGL(avgpool_x4_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, x, out, (unsigned)f.items, D, H, W, kd, kh);
+  else
+    hipLaunchKernelGGL(avgpool_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, out, (long)NC, D, H, W, kd, kh, kw);
   return emo_launch_status();
+}
+
+// ABI 28 (definition: include/emo_hip.h): the form and plan the launcher of `op` takes for these arguments; nothing is launched
+extern "C" int emo_op_launch_form(int op, const void* x, const void* out, const int64_t* dims, int64_t* plan) {
+  if (!dims || !plan) return EMO_ERR_BAD_ARG;
+  for (int i = 0; i < EMO_OP_PLAN_COUNT; ++i) plan[i] = 0;
+  const auto i32 = [&](int i) { return (int)dims[i]; };
+  // an int argument of the launcher that does not fit one: dims[first .. last]
+  const auto ints = [&](int first, int last) {
+    for (int i = first; i <= last; ++i)
+      if (dims[i] != (int64_t)(int)dims[i]) return false;
+    return true;
+  };
+  if (op == EMO_OP_UPSAMPLE_TRILINEAR || op == EMO_OP_UPSAMPLE_TRILINEAR_GN_SUMS) {
+    UpsForm f;
+    if (op == EMO_OP_UPSAMPLE_TRILINEAR) {
+      if (!ints(1, 6)) return EMO_ERR_BAD_ARG;
+      f = ups_form(x, out, (long)dims[0], i32(1), i32(2), i32(3), i32(4), i32(5), i32(6));
+    } else {
+      if (!ints(0, 8)) return EMO_ERR_BAD_ARG;
+      // (the workspace and split_out of the launcher: any non-null address, a size that is enough)
+      f = ups_gn_form(x, out, plan, INT64_MAX, plan, i32(0), i32(1), i32(2), i32(3), i32(4), i32(5), i32(6), i32(7), i32(8));
+    }
+    if (f.rc != EMO_OK) return f.rc;
+    plan[EMO_OP_PLAN_FORM] = f.form; plan[EMO_OP_PLAN_GRID] = f.grid; plan[EMO_OP_PLAN_ITEMS] = f.items;
+    if (f.form == EMO_UPSAMPLE_FORM_BLOCK) {
+      plan[EMO_OP_PLAN_CR] = f.cr; plan[EMO_OP_PLAN_RUNS] = f.runs; plan[EMO_OP_PLAN_SPLIT] = f.split;
+      plan[EMO_OP_PLAN_PER] = f.per; plan[EMO_OP_PLAN_RUN_ITEMS] = f.qrun;
+    }
+    return EMO_OK;
+  }
+  if (op == EMO_OP_AVGPOOL) {
+    if (!ints(1, 6)) return EMO_ERR_BAD_ARG;
+    const PoolForm f = pool_form(x, out, (long)dims[0], i32(1), i32(2), i32(3), i32(4), i32(5), i32(6));
+    if (f.rc != EMO_OK) return f.rc;
+    plan[EMO_OP_PLAN_FORM] = f.form; plan[EMO_OP_PLAN_GRID] = f.grid; plan[EMO_OP_PLAN_ITEMS] = f.items;
+    return EMO_OK;
+  }
+  if (op == EMO_OP_GROUPNORM_AFFINE) return emo_groupnorm_launch_plan(x, dims, plan);
+  return EMO_ERR_BAD_ARG;
 }
 
 extern "C" int emo_add_f32(const float* a, const float* b, float* out, int64_t n, int64_t period, float alpha,

@@ -55,6 +55,7 @@ SIGNATURES = {
     "emo_avgpool_f32": [_c_void, _c_void, _c_i64] + [_c_int] * 6 + [_c_void],
     "emo_add_f32": [_c_void, _c_void, _c_void, _c_i64, _c_i64, _c_float, _c_void],
     "emo_add_rows_indexed_f32": [_c_void] * 4 + [_c_int, _c_int, _c_i64, _c_float, _c_void],
+    "emo_op_launch_form": [_c_int, _c_void, _c_void, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)],
     "emo_resize2d_f32": [_c_void, _c_i64, _c_i64, _c_void, _c_i64] + [_c_int] * 6 + [_c_void],
     "emo_resize2d_windows_f32": [_c_void, _c_i64, _c_i64, _c_void, _c_void] + [_c_int] * 6 + [_c_void],
     "emo_conv2d_generic_f32": [_c_void] * 6 + [_c_int] * 11 + [_c_void, _c_void],
@@ -135,6 +136,27 @@ def load():
         raise HipLibraryError(f"ABI mismatch: library {v}, python {_abi_version.EMO_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
+
+
+# emo_op_launch_form (ABI 28): the ops, their forms and the plan slots of include/emo_hip.h (tests/test_abi.py pins them to it)
+OPS = {"upsample_trilinear": 0, "upsample_trilinear_gn_sums": 1, "avgpool": 2, "groupnorm_affine": 3}
+OP_FORMS = {"upsample_trilinear": ("generic", "block"), "upsample_trilinear_gn_sums": ("generic", "block"),
+            "avgpool": ("generic", "x4_w1", "x4_w2"), "groupnorm_affine": ("pass",)}
+OP_PLAN = ("form", "grid", "items", "cr", "runs", "split", "per", "run_items")
+
+
+def op_launch_form(op, x, out, dims):
+    """What the launcher of `op` would do with these arguments, launching nothing: (rc, plan).  x, out: addresses (ints) or None;
+    dims: the launcher's integer shape arguments in its order.  plan: OP_PLAN names -> ints, 'form' as its name; None if rc != 0"""
+    lib = load()
+    d = (_c_i64 * 9)(*[int(v) for v in dims])              # (the longest argument list; the rest zero)
+    p = (_c_i64 * len(OP_PLAN))()
+    rc = lib.emo_op_launch_form(OPS[op], ctypes.c_void_p(x) if x else None, ctypes.c_void_p(out) if out else None, d, p)
+    if rc != 0:
+        return rc, None
+    plan = dict(zip(OP_PLAN, (int(v) for v in p)))
+    plan["form"] = OP_FORMS[op][plan["form"]]
+    return rc, plan
 
 
 _ERR = {-1: "EMO_ERR_BAD_ARG", -2: "EMO_ERR_UNSUPPORTED", -3: "EMO_ERR_ALIGN"}

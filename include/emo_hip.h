@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 27
+#define EMO_ABI_VERSION 28
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -410,6 +410,31 @@ int emo_add_f32(const float* a, const float* b, float* out, int64_t n, int64_t p
 int emo_add_rows_indexed_f32(const float* a, const float* table, const int32_t* index, float* out, int B, int num_rows,
                              int64_t row, float alpha, void* stream);
 
+/* ABI 28.  A question, not a launch: the kernel and the launch plan that the launcher of `op` takes for these arguments.  The
+ * launcher's own host function answers -- the one it calls itself before it launches -- so a condition of a form is written
+ * once; no HIP call is made and the call works on a machine without a device.  Returns what the launcher would return before
+ * any launch (EMO_ERR_BAD_ARG, EMO_ERR_UNSUPPORTED; then plan is all zero), otherwise EMO_OK with plan[EMO_OP_PLAN_COUNT] filled.
+ *   x, out: the launcher's first input and its output, read for nullness and 16-byte alignment only (out is not read for
+ *           EMO_OP_GROUPNORM_AFFINE).  dims: the launcher's integer shape arguments in its own order --
+ *     EMO_OP_UPSAMPLE_TRILINEAR          (NC, D, H, W, fd, fh, fw)        emo_upsample_trilinear_f32
+ *     EMO_OP_UPSAMPLE_TRILINEAR_GN_SUMS  (N, C, G, D, H, W, fd, fh, fw)   emo_upsample_trilinear_gn_sums_f32
+ *     EMO_OP_AVGPOOL                     (NC, D, H, W, kd, kh, kw)        emo_avgpool_f32
+ *     EMO_OP_GROUPNORM_AFFINE            (N, C, S, G)                     emo_groupnorm_affine_f32, its own pass
+ *   plan[EMO_OP_PLAN_FORM]: the kernel, an EMO_*_FORM_* of the op.  GRID: thread blocks of the launch.  ITEMS: work items of the
+ *   launch (outputs; quads of outputs for the x4 pooling kernels; blocks of up to 4 x 2 x 2 outputs for the block upsampling
+ *   kernel; elements read for GroupNorm) -- a grid-stride kernel takes a second trip where ITEMS > 256 GRID.
+ *   Block upsampling kernel and GroupNorm only (0 otherwise): RUNS x SPLIT = GRID, a run being CR consecutive (sample, channel)
+ *   volumes (GN_SUMS: the channels of a group; GroupNorm: one (sample, group), CR = 0) of RUN_ITEMS items, cut into SPLIT slices;
+ *   PER: items per slice of the upsampling kernel, the last slice holding the rest (RUN_ITEMS - (SPLIT - 1) PER, never empty). */
+enum { EMO_OP_UPSAMPLE_TRILINEAR = 0, EMO_OP_UPSAMPLE_TRILINEAR_GN_SUMS = 1, EMO_OP_AVGPOOL = 2, EMO_OP_GROUPNORM_AFFINE = 3,
+       EMO_OP_COUNT = 4 };
+enum { EMO_UPSAMPLE_FORM_GENERIC = 0, EMO_UPSAMPLE_FORM_BLOCK = 1, EMO_UPSAMPLE_FORM_COUNT = 2 };
+enum { EMO_AVGPOOL_FORM_GENERIC = 0, EMO_AVGPOOL_FORM_X4_W1 = 1, EMO_AVGPOOL_FORM_X4_W2 = 2, EMO_AVGPOOL_FORM_COUNT = 3 };
+enum { EMO_GROUPNORM_FORM_PASS = 0, EMO_GROUPNORM_FORM_COUNT = 1 };
+enum { EMO_OP_PLAN_FORM = 0, EMO_OP_PLAN_GRID = 1, EMO_OP_PLAN_ITEMS = 2, EMO_OP_PLAN_CR = 3, EMO_OP_PLAN_RUNS = 4,
+       EMO_OP_PLAN_SPLIT = 5, EMO_OP_PLAN_PER = 6, EMO_OP_PLAN_RUN_ITEMS = 7, EMO_OP_PLAN_COUNT = 8 };
+int emo_op_launch_form(int op, const void* x, const void* out, const int64_t* dims, int64_t* plan);
+
 /* f4 -- F.interpolate(x, size=(Ho, Wo), mode='bilinear' (bicubic = 0) | 'bicubic' (1), align_corners=False) on NC
  * planes of H x W: the wrappers' crop resize (notebooks/infer.py:346,399-401,548-552; notebooks/infer_s2.py:360-362).
  * The input is strided (plane_stride / row_stride in floats; H*W / W when contiguous) so that a crop window of a larger
@@ -437,7 +462,8 @@ int emo_resize2d_windows_f32(const float* x, int64_t plane_stride, int64_t row_s
  *   BasicBlock / Bottleneck.forward.
  * emo_grid_sample2d_f32: F.grid_sample(img, grid) 4-D bilinear / zeros / align_corners=False; either an explicit
  *   grid [N,Ho,Wo,2] or theta [N,2,3] + lin [Ho] (grid = theta @ (lin[xo], lin[yo], 1): expression_embedder.py:221-231);
- *   grid_out (optional) receives the grid that was used. */
+ *   grid_out (optional) receives the grid that was used.  A grid value that is NaN, infinite or beyond the int range in pixels
+ *   has no corner in range and reads nothing: the output is ATen's there (NaN from the weights of a NaN or infinite value, else 0). */
 int emo_conv2d_generic_f32(const float* x, const float* wt, const float* bias, const float* scale, const float* shift,
                            float* out, int N, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad,
                            int relu_in, int splits, float* workspace, void* stream);

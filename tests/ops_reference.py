@@ -1,8 +1,9 @@
 """fp64 references and error checkers for single launches of the non-convolution ops the passes make (a helper module, not a
 test file; the sibling of conv_reference.py): volume_to_channels_last, add, add_rows_indexed, avgpool, upsample_trilinear,
 groupnorm_affine (own pass / TileStats / RunSums), small_gemm, projector_finalize, mat4_inverse and grid_sample3d (delta= /
-theta=, with and without vol_index); and for the launches of the embedders (emoportraits_amd/embedders.py): conv2d_generic,
-maxpool2d, affine_add_relu, grid_sample2d (grid= / theta= with its warp), resize2d (bilinear, whole frame) and pose_theta.
+theta=, with and without vol_index); for the launches of the embedders (emoportraits_amd/embedders.py): conv2d_generic,
+maxpool2d, affine_add_relu, grid_sample2d (grid= / theta= with its warp), resize2d (both modes, window=, clamp01=) and
+pose_theta; and for the stage-2 and frame glue: mul_mask, stage2_compose, pack_rgb8 and unpack_rgb8.
 
 Every reference is plain torch in fp64, computed one sample at a time on whatever device the inputs live on; none calls a
 kernel of the project.  Every checker compares a launch's output with that reference sample by sample and returns a dict of
@@ -709,27 +710,182 @@ def check_grid_sample2d(out, img, grid=None, theta=None, size=None, warp=None, f
     return fig
 
 
-# ---- resize2d (bilinear, whole frame) ------------------------------------------------------------------------------------
-def resize2d_frames(x, size, frames=None, yardstick=True):
-    """yields (n, fp64 F.interpolate(x[n], size, 'bilinear', align_corners=False) [C, Ho, Wo], ATen's fp32 CPU result or None)"""
+# ---- resize2d ------------------------------------------------------------------------------------------------------------
+def _window(v, window):
+    """v [C, H, W] -> its window (x0, y0, w, h); None: the whole frame"""
+    if window is None:
+        return v
+    x0, y0, w, h = (int(k) for k in window)
+    H, W = v.shape[-2:]
+    if not (0 <= x0 and 0 <= y0 and w > 0 and h > 0 and x0 + w <= W and y0 + h <= H):
+        raise ValueError(f"window {tuple(window)} is not inside the {W}x{H} frame")
+    return v[:, y0:y0 + h, x0:x0 + w]
+
+
+def resize2d_frames(x, size, mode="bilinear", window=None, clamp01=False, frames=None, yardstick=True):
+    """yields (n, fp64 F.interpolate(window of x[n], size, mode, align_corners=False) [C, Ho, Wo] -- clamped to [0, 1] with
+    clamp01 --, ATen's fp32 CPU result of the same or None).  The window is a SLICE: what lies outside it does not exist for the
+    interpolation, so a tap that leaves the window is clamped into the window, not into the frame"""
+    if mode not in ("bilinear", "bicubic"):
+        raise ValueError(f"mode {mode!r}: 'bilinear' or 'bicubic'")
     for n in _frames(x.shape[0], frames):
-        ref = F.interpolate(_f64(x[n])[None], size=tuple(size), mode="bilinear", align_corners=False)[0]
+        v = _window(x[n], window)
+        ref = F.interpolate(_f64(v)[None], size=tuple(size), mode=mode, align_corners=False)[0]
         assert ref.dtype == torch.float64
-        yard = F.interpolate(x[n].float().cpu()[None], size=tuple(size), mode="bilinear", align_corners=False)[0] if yardstick else None
+        yard = F.interpolate(v.float().cpu().contiguous()[None], size=tuple(size), mode=mode, align_corners=False)[0] if yardstick else None
+        if clamp01:
+            ref, yard = ref.clamp(0.0, 1.0), (None if yard is None else yard.clamp(0.0, 1.0))
         yield n, ref, yard
 
 
-def resize2d_fp64(x, size):
-    return torch.stack([r for _, r, _ in resize2d_frames(x, size, yardstick=False)])
+def resize2d_fp64(x, size, mode="bilinear", window=None, clamp01=False):
+    return torch.stack([r for _, r, _ in resize2d_frames(x, size, mode, window, clamp01, yardstick=False)])
 
 
-def check_resize2d(out, x, size, frames=None):
-    """ops.resize2d(x, size, 'bilinear') on the whole frame against the fp64 interpolation, held to ATen's fp32 CPU kernel on
-    the same input with the sampler's margins (the same construction as check_grid_sample2d: another valid order of the same
-    fp32 operations)"""
+def check_resize2d(out, x, size, mode="bilinear", window=None, clamp01=False, frames=None):
+    """ops.resize2d(x, size, mode, window=, clamp01=) against the fp64 interpolation of the window's slice, held to ATen's fp32 CPU
+    kernel on the same slice with the sampler's margins (the same construction as check_grid_sample2d: another valid order of
+    the same fp32 operations).  Two things hold exactly, whatever the margins would allow:
+      * a window as large as the output is the input itself, bit for bit, in both modes: every source index is an integer, the
+        bilinear weights are (1, 0) and the bicubic ones at t = 0 are (0, 1, 0, 0) in fp32 (cubic2(1) = A - 5A + 8A - 4A = 0,
+        cubic1(0) = 1, cubic1(1) = (A + 2) - (A + 3) + 1 = 0, cubic2(2) = 0 for A = -0.75, every step exact), so each output is
+        one tap times 1 plus zeros (clamp01: that value clamped);
+      * with clamp01 no output lies outside [0, 1]: the bicubic overshoot is clipped to exactly 0 or 1.
+    Figures besides the yardstick's: 'exact_bad' (outputs that miss one of the two)."""
     fr = _frames(x.shape[0], frames)
-    rows = [_yardstick_row(out[n], ref, yard, n) for n, ref, yard in resize2d_frames(x, size, fr)]
-    return _yardstick_fig(rows, fr, f"resize2d bilinear -> {tuple(size)}")
+    size = tuple(int(s) for s in size)
+    what = f"resize2d {mode} -> {size}" + (f" window {tuple(window)}" if window is not None else "") + (" clamp01" if clamp01 else "")
+    rows, exact = [], []
+    for n, ref, yard in resize2d_frames(x, size, mode, window, clamp01, fr):
+        rows.append(_yardstick_row(out[n], ref, yard, n))
+        bad = torch.zeros((), dtype=torch.int64, device=out.device)
+        if clamp01:
+            bad = bad + (~((out[n] >= 0.0) & (out[n] <= 1.0))).sum()
+        v = _window(x[n], window)
+        if tuple(v.shape[-2:]) == size:
+            same = v.float().clamp(0.0, 1.0) if clamp01 else v.float()
+            bad = bad + (out[n].contiguous().view(torch.int32) != same.contiguous().view(torch.int32)).sum()
+        exact.append(bad)
+    fig = _yardstick_fig(rows, fr, what)
+    e = torch.stack(exact).cpu().tolist()
+    fig["exact_bad"] = int(sum(e))
+    fig["failures"] += [f"{what}: frame {n}: {e[i]} outputs outside [0, 1] under clamp01 or not the input's bits at equal size"
+                        for i, n in enumerate(fr) if e[i]]
+    return fig
+
+
+# ---- mul_mask / stage2_compose -------------------------------------------------------------------------------------------
+def _mask_of(mask, n, hw):
+    """mask [N, 1, H, W] (or [N, H, W]) -> sample n as [1, H, W]"""
+    return mask[n].reshape((1,) + tuple(hw))
+
+
+def _bits_fig(rows, fr, what):
+    """figures of a launch held to bit equality: rows = the count of differing elements per frame"""
+    t = torch.stack(rows).cpu().tolist()
+    w = max(range(len(fr)), key=lambda i: t[i])
+    bad = [f"{what}: frame {n}: {t[i]} elements differ from the reference's bits" for i, n in enumerate(fr) if t[i]]
+    return dict(frames=fr, frame_fig=[float(v) for v in t], unit="differing elements", worst=float(t[w]), worst_frame=fr[w], failures=bad)
+
+
+def mul_mask_fp64(img, mask):
+    """img [N, C, H, W] * mask [N, 1, H, W] in fp64: exact (two 24-bit significands)"""
+    return torch.stack([_f64(img[n]) * _f64(_mask_of(mask, n, img.shape[2:])) for n in range(img.shape[0])])
+
+
+def check_mul_mask(out, img, mask, frames=None):
+    """The kernel rounds once: out = fl(img mask).  The fp64 product of two fp32 values is exact, so its rounding to fp32 IS the
+    kernel's result: bit equality, sample by sample (signed zeros included); the figure is the count of differing elements."""
+    fr = _frames(img.shape[0], frames)
+    if tuple(out.shape) != tuple(img.shape):
+        raise ValueError(f"output {tuple(out.shape)} of an image {tuple(img.shape)}")
+    rows = []
+    for n in fr:
+        ref = (_f64(img[n]) * _f64(_mask_of(mask, n, img.shape[2:]))).float()
+        rows.append((out[n].contiguous().view(torch.int32) != ref.contiguous().view(torch.int32)).sum())
+    return _bits_fig(rows, fr, "mul_mask")
+
+
+def stage2_compose_frames(img, add, mask, face_mask, frames=None):
+    """yields (n, r = img + add (mask face_mask) in fp64 BEFORE the clamp [C, H, W], fp64 bound without the floor, |add|) per
+    sample; see check_stage2_compose"""
+    hw = img.shape[2:]
+    for n in _frames(img.shape[0], frames):
+        M = _f64(_mask_of(mask, n, hw)) * _f64(_mask_of(face_mask, n, hw))          # exact
+        P = _f64(add[n]) * M
+        r = _f64(img[n]) + P
+        yield n, r, U * (1.0 + U) ** 2 * (2.0 * P.abs() + r.abs()), _f64(add[n]).abs()
+
+
+def stage2_compose_fp64(img, add, mask, face_mask):
+    return torch.stack([r.clamp(0.0, 1.0) for _, r, _, _ in stage2_compose_frames(img, add, mask, face_mask)])
+
+
+def check_stage2_compose(out, img, add, mask, face_mask, frames=None):
+    """The kernel computes m^ = fl(mask face) = M (1 + d1), p^ = fl(add m^) = add M (1 + d1)(1 + d2), v = fl(img + p^) =
+    (img + p^)(1 + d3), |d| <= u, then clamps.  With P = add M and r = img + P exact: |p^ - P| <= |P| (2u + u^2) and
+    |v - r| <= |p^ - P| (1 + u) + u |r| <= u (1 + u)^2 (2 |P| + |r|).  A compiler that contracts the last two operations into one
+    FMA drops d2: fewer roundings, the same bound.  Where m^ or p^ underflows a rounding costs TINY instead (m^'s times |add|):
+    + TINY (2 + |add|).  The clamp is 1-Lipschitz, so the bound holds for the clamped values -- and where r lies outside [0, 1]
+    by more than the bound the clamp decides the output alone: it must be exactly 0 or 1 (bound 0 there).  No output may lie
+    outside [0, 1] at all."""
+    fr = _frames(img.shape[0], frames)
+    rows, outside = [], []
+    for n, r, bound, amag in stage2_compose_frames(img, add, mask, face_mask, fr):
+        bound = bound + TINY * (2.0 + amag)
+        decided = (r < -bound) | (r > 1.0 + bound)
+        rows.append(_bounded_row(out[n], r.clamp(0.0, 1.0), torch.where(decided, torch.zeros_like(bound), bound)))
+        outside.append((~((out[n] >= 0.0) & (out[n] <= 1.0))).sum())
+    fig = _bounded_fig(rows, fr, "stage2_compose")
+    o = torch.stack(outside).cpu().tolist()
+    fig["failures"] += [f"stage2_compose: frame {n}: {o[i]} outputs outside [0, 1]" for i, n in enumerate(fr) if o[i]]
+    return fig
+
+
+# ---- pack_rgb8 / unpack_rgb8 ---------------------------------------------------------------------------------------------
+def rgb8_edge_image():
+    """[1, 3, 4, 193] fp32 on the CPU, the pixels at which a packing can go wrong: k / 255 for every byte k and the fp32 values on
+    either side of each; -0.0, -1e-3, 1 + 2^-23 and 1 - 2^-24.  Every channel holds all of them, in another order"""
+    k = torch.arange(256, dtype=torch.float32) / 255
+    v = torch.cat([k, torch.nextafter(k, torch.tensor(-9.0)), torch.nextafter(k, torch.tensor(9.0)),
+                   torch.tensor([-0.0, -1e-3, 1 + 2.0 ** -23, 1 - 2.0 ** -24])])
+    assert v.numel() == 4 * 193
+    return torch.stack([v, v.flip(0), v.roll(97)]).reshape(1, 3, 4, 193)
+
+
+def pack_rgb8_ref(img):
+    """[N, 3, H, W] fp32 -> [N, H, W, 3] uint8: clamp(0, 1) * 255 in fp64 (exact: 24 + 8 bits), rounded to fp32 as the kernel's one
+    product is, truncated -- torch's img.clamp(0, 1).mul(255).byte().permute(0, 2, 3, 1), the reference wrapper's ToPILImage.
+    Finite inputs only (the byte of a NaN is undefined)"""
+    return torch.stack([(_f64(img[n]).clamp(0.0, 1.0) * 255.0).float().to(torch.uint8).permute(1, 2, 0) for n in range(img.shape[0])])
+
+
+def check_pack_rgb8(out, img, frames=None):
+    """byte equality with pack_rgb8_ref, sample by sample: one rounded product and a truncation, nothing to bound"""
+    fr = _frames(img.shape[0], frames)
+    if tuple(out.shape) != (img.shape[0],) + tuple(img.shape[2:]) + (3,) or out.dtype != torch.uint8:
+        raise ValueError(f"output {tuple(out.shape)} {out.dtype} is not the HWC byte form of {tuple(img.shape)}")
+    rows = [(out[n] != pack_rgb8_ref(img[n:n + 1])[0]).sum() for n in fr]
+    return _bits_fig(rows, fr, "pack_rgb8")
+
+
+def unpack_rgb8_fp64(frames_u8):
+    """[N, H, W, 3] uint8 -> [N, 3, H, W] fp64 = byte / 255"""
+    return _f64(frames_u8).permute(0, 3, 1, 2) / 255.0
+
+
+def check_unpack_rgb8(out, frames_u8, frames=None):
+    """The kernel divides in fp32, correctly rounded: out = fl(byte / 255) -- torch's byte.float() / 255.  The fp64 quotient
+    rounded to fp32 is the same number for each of the 256 bytes (no quotient lies close enough to the middle of two fp32
+    values for the first rounding to move it across; tests/test_ops_reference.py compares all 256): bit equality."""
+    fr = _frames(frames_u8.shape[0], frames)
+    if tuple(out.shape) != (frames_u8.shape[0], 3) + tuple(frames_u8.shape[1:3]) or out.dtype != torch.float32:
+        raise ValueError(f"output {tuple(out.shape)} {out.dtype} is not the CHW float form of {tuple(frames_u8.shape)}")
+    rows = []
+    for n in fr:
+        ref = (_f64(frames_u8[n]).permute(2, 0, 1) / 255.0).float()
+        rows.append((out[n].contiguous().view(torch.int32) != ref.contiguous().view(torch.int32)).sum())
+    return _bits_fig(rows, fr, "unpack_rgb8")
 
 
 # ---- pose_theta ----------------------------------------------------------------------------------------------------------

@@ -32,11 +32,12 @@ EMBEDDER_OPS = ("conv2d_generic", "maxpool2d", "affine_add_relu", "grid_sample2d
 register(EMBEDDER_OPS)
 # calls of stage2.py / encoder.py, none of which runs under the checker here: the test that holds each one to its reference
 HELD_ELSEWHERE = {
-    "resize2d": "tests/test_kernels_gpu.py::test_resize2d_matches_interpolate (bilinear, whole frame, up and down, against F.interpolate)",
-    "mul_mask": "tests/test_stage2_gpu.py::test_compose_kernels (bit equality with img * mask)",
-    "stage2_compose": "tests/test_stage2_gpu.py::test_compose_kernels (against the fp32 composition)",
+    "resize2d": "tests/test_op_launch_forms_gpu.py::test_resize2d (both modes, windows, clamp01, the wrap: check_resize2d)",
+    "mul_mask": "tests/test_op_launch_forms_gpu.py::test_mul_mask_and_stage2_compose (check_mul_mask: the fp32 product's bits)",
+    "stage2_compose": "tests/test_op_launch_forms_gpu.py::test_mul_mask_and_stage2_compose (check_stage2_compose: the derived bound, exact clamps)",
     "stage2_head": "tests/test_refine_gpu.py::test_stage2_head_kernel_is_the_three_launch_chain_bit_for_bit_at_the_real_shape",
-    "pack_rgb8": "tests/test_kernels_gpu.py::test_pose_theta_and_pack (bit equality with clamp * 255 truncated)",
+    "pack_rgb8": "tests/test_op_launch_forms_gpu.py::test_pack_and_unpack_rgb8 (check_pack_rgb8: byte equality at every byte's edges)",
+    "unpack_rgb8": "tests/test_op_launch_forms_gpu.py::test_pack_and_unpack_rgb8 (check_unpack_rgb8: the fp32 quotient's bits, all 256 bytes)",
 }
 
 
@@ -130,9 +131,8 @@ class EmbedderLaunchChecker(OpLaunchChecker):
         return form, tuple(a["img"].shape[1:]), R.check_grid_sample2d(out, a["img"], a["grid"], a["theta"], a["size"], warp)
 
     def _check_resize2d(self, a, out):
-        if a["mode"] != "bilinear" or a["window"] is not None or a["clamp01"]:
-            raise AssertionError("a resize form the embedders did not use when this checker was written: give it a reference")
-        return f"bilinear -> {tuple(a['size'])}", tuple(a["x"].shape[1:]), R.check_resize2d(out, a["x"], a["size"])
+        form = f"{a['mode']} -> {tuple(a['size'])}" + (" window" if a["window"] is not None else "") + (" clamp01" if a["clamp01"] else "")
+        return form, tuple(a["x"].shape[1:]), R.check_resize2d(out, a["x"], a["size"], a["mode"], a["window"], a["clamp01"])
 
     def _check_pose_theta(self, a, out):
         return f"scale [{a['scale'].shape[1]}]", (4, 4), R.check_pose_theta(out, a["scale"], a["rotation"], a["translation"])

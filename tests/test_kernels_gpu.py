@@ -18,6 +18,7 @@ import restate as O  # noqa: E402
 
 from emoportraits_amd import ops, pack  # noqa: E402
 from conv_plans import Expect, check as check_plan, split_case  # noqa: E402
+import ops_reference as R  # noqa: E402
 
 from guarded_outputs import assert_written, guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
 
@@ -705,14 +706,20 @@ def test_upsample_trilinear_without_a_fused_form_returns_no_sums():
 @pytest.mark.parametrize("kernel", [(2, 1, 1), (1, 2, 2), (2, 2, 2)])
 def test_avgpool3d(kernel):
     x = torch.randn(2, 3, 4, 6, 8, generator=torch.Generator().manual_seed(2))
-    assert rel_err(ops.avgpool(x.to(DEV), kernel), F.avg_pool3d(x, kernel, kernel)) < 1e-6
+    got = ops.avgpool(x.to(DEV), kernel)
+    assert rel_err(got, F.avg_pool3d(x, kernel, kernel)) < 1e-6
+    assert R.check_avgpool(got, x.to(DEV), kernel)["failures"] == []
 
 
 def test_avgpool2d_and_add():
     x = torch.randn(2, 3, 6, 8, generator=torch.Generator().manual_seed(3))
-    assert rel_err(ops.avgpool(x.to(DEV), (2, 2)), F.avg_pool2d(x, 2)) < 1e-6
+    got = ops.avgpool(x.to(DEV), (2, 2))
+    assert rel_err(got, F.avg_pool2d(x, 2)) < 1e-6
+    assert R.check_avgpool(got, x.to(DEV), (2, 2))["failures"] == []
     y = torch.randn(3, 6, 8)
-    assert rel_err(ops.add(x.to(DEV), y.to(DEV), 0.5), (x + y[None]) * 0.5) < 1e-7
+    got = ops.add(x.to(DEV), y.to(DEV), 0.5)
+    assert rel_err(got, (x + y[None]) * 0.5) < 1e-7
+    assert R.check_add(got, x.to(DEV), y.to(DEV), 0.5)["failures"] == []
 
 
 def test_small_gemm_and_projector():
@@ -722,6 +729,7 @@ def test_small_gemm_and_projector():
         B = torch.randn(3, 300, NN, generator=g)
         got = ops.small_gemm(A.to(DEV), B.to(DEV), NN)
         assert rel_err(got, torch.einsum("mk,bkn->bmn", A, B)) < 1e-5
+        assert R.check_small_gemm(got, A.to(DEV), B.to(DEV), NN)["failures"] == []
     T = torch.randn(2, 10, 16, generator=g)
     V = torch.randn(3, 16, 2, generator=g)
     nor = torch.tensor([0, 0, 0, 1, 1, 1, 1, 2, 2, 2], dtype=torch.int32)
@@ -730,6 +738,7 @@ def test_small_gemm_and_projector():
     P = torch.einsum("brk,rkj->brj", T, V[nor.long()])
     assert rel_err(ag, gamma[None] + P[..., 0]) < 1e-5
     assert rel_err(ab, beta[None] + P[..., 1]) < 1e-5
+    assert R.check_projector_finalize(ag, ab, T.to(DEV), V.to(DEV), nor.to(DEV), gamma.to(DEV), beta.to(DEV))["failures"] == []
 
 
 def test_pose_theta_and_pack(golden_dir):
@@ -742,7 +751,9 @@ def test_pose_theta_and_pack(golden_dir):
     assert (got1 - torch.from_numpy(p["theta_scalar_scale"])).abs().max().item() < 2e-6
     img = torch.rand(2, 3, 16, 24, generator=torch.Generator().manual_seed(9)) * 1.4 - 0.2
     ref = img.clamp(0, 1).mul(255).byte().permute(0, 2, 3, 1)
-    assert torch.equal(ops.pack_rgb8(img.to(DEV)).cpu(), ref)
+    got = ops.pack_rgb8(img.to(DEV))
+    assert torch.equal(got.cpu(), ref)
+    assert R.check_pack_rgb8(got, img.to(DEV))["failures"] == []
 
 
 def test_resize2d_windows_is_one_launch_of_the_per_frame_crops():

@@ -643,6 +643,148 @@ def test_resize2d_reference_and_faults():
     _caught(R.check_resize2d(F.interpolate(x, size=(9, 7), mode="bilinear", antialias=True), x, (9, 7)))
 
 
+def _bicubic(x, window, size, A=-0.75, clamp_into="window"):
+    """the bicubic resize of a window, written out (fp64 sums of the 4 x 4 taps, rounded once): source index s = scale (o + 0.5) -
+    0.5, taps floor(s) - 1 ... floor(s) + 2, cubic-convolution weights with parameter A; a tap that leaves the window is clamped
+    into the window -- or, the planted fault, into the frame, where it reads the pixels next to the window"""
+    x0, y0, w, h = window
+    H, W = x.shape[-2:]
+
+    def axis(n_out, n_in, off, full):
+        s = (n_in / n_out) * (torch.arange(n_out, dtype=torch.float64) + 0.5) - 0.5
+        f = s.floor()
+        t = s - f
+        idx = f.long()[:, None] + torch.arange(-1, 3)[None]
+        idx = idx.clamp(0, n_in - 1) + off if clamp_into == "window" else (idx + off).clamp(0, full - 1)
+        c1 = lambda v: ((A + 2) * v - (A + 3)) * v * v + 1
+        c2 = lambda v: ((A * v - 5 * A) * v + 8 * A) * v - 4 * A
+        return idx, torch.stack([c2(t + 1), c1(t), c1(1 - t), c2(2 - t)], 1)
+
+    (iy, wy), (ix, wx) = axis(size[0], h, y0, H), axis(size[1], w, x0, W)
+    v = x.double()[:, :, iy][..., ix]                                                     # [N, C, Ho, 4, Wo, 4]
+    return (v * wy[None, None, :, :, None, None] * wx[None, None, None, None]).sum((3, 5)).float()
+
+
+@pytest.mark.parametrize("mode", ["bilinear", "bicubic"])
+def test_resize2d_windows_modes_and_clamp(mode):
+    x = torch.rand(2, 3, 24, 32, generator=_g(31)) * 1.4 - 0.2                            # values in [-0.2, 1.2]
+    for window, size in (((5, 3, 14, 12), (30, 28)), ((0, 0, 16, 10), (7, 9)), ((18, 14, 14, 10), (10, 14)), (None, (12, 16))):
+        sl = x if window is None else x[:, :, window[1]:window[1] + window[3], window[0]:window[0] + window[2]]
+        for clamp01 in (False, True):
+            own = F.interpolate(sl.double(), size=size, mode=mode, align_corners=False)
+            assert _same64(R.resize2d_fp64(x, size, mode, window, clamp01), own.clamp(0, 1) if clamp01 else own)
+            out = F.interpolate(sl.contiguous(), size=size, mode=mode, align_corners=False)
+            fig = _clean(R.check_resize2d(out.clamp(0, 1) if clamp01 else out, x, size, mode, window, clamp01))
+            assert fig["max_ratio"] in (0.0, 1.0) and fig["exact_bad"] == 0
+    # the clamp dropped: an overshoot (bicubic) or an input outside [0, 1] (both modes) survives
+    out = F.interpolate(x[:, :, 3:15, 5:19].contiguous(), size=(30, 28), mode=mode, align_corners=False)
+    assert out.min() < 0 and out.max() > 1
+    assert _caught(R.check_resize2d(out, x, (30, 28), mode, (5, 3, 14, 12), True))["exact_bad"] > 0
+    # equal size: the input's bits, in both modes; one ulp on one element is no longer the input
+    same = x[:, :, 3:15, 5:19].contiguous()
+    _clean(R.check_resize2d(same, x, (12, 14), mode, (5, 3, 14, 12)))
+    _clean(R.check_resize2d(same.clamp(0, 1), x, (12, 14), mode, (5, 3, 14, 12), True))
+    off = same.clone()
+    off[1, 2, 5, 6] = torch.nextafter(off[1, 2, 5, 6], torch.tensor(9.0))
+    assert _caught(R.check_resize2d(off, x, (12, 14), mode, (5, 3, 14, 12)))["exact_bad"] == 1
+    with pytest.raises(ValueError):
+        R.check_resize2d(same, x, (12, 14), mode, (20, 3, 14, 12))                        # a window that leaves the frame
+
+
+def test_resize2d_bicubic_taps_and_parameter():
+    """the written-out bicubic is the reference (so the plants below differ from it in what they plant alone); taps clamped into
+    the frame read the pixels next to the window, A = -0.5 is the antialiased filter's parameter, not this one's"""
+    x = torch.rand(2, 3, 24, 32, generator=_g(32))
+    window, size = (6, 5, 12, 10), (40, 36)                                               # interior, upscaled: the border taps leave it
+    _clean(R.check_resize2d(_bicubic(x, window, size), x, size, "bicubic", window))
+    frame = _bicubic(x, window, size, clamp_into="frame")
+    assert torch.equal(frame[:, :, 8:-8, 8:-8], _bicubic(x, window, size)[:, :, 8:-8, 8:-8])      # (the interior is untouched)
+    _caught(R.check_resize2d(frame, x, size, "bicubic", window))
+    _caught(R.check_resize2d(_bicubic(x, window, size, A=-0.5), x, size, "bicubic", window))
+    # a window at the frame's corner has nothing beyond two of its edges, and the other two are caught all the same
+    _caught(R.check_resize2d(_bicubic(x, (0, 0, 12, 10), size, clamp_into="frame"), x, size, "bicubic", (0, 0, 12, 10)))
+
+
+# ---- mul_mask / stage2_compose -------------------------------------------------------------------------------------------
+def _wrong_sample(mask, N, C):
+    """[N, C, H, W]: the mask a kernel reads that computes the sample as i / HW, without the channels: plane n C + c (here
+    modulo N, where the kernel would leave the tensor)"""
+    planes = (torch.arange(N)[:, None] * C + torch.arange(C)[None]) % N
+    return mask[:, 0][planes]
+
+
+def test_mul_mask_reference_and_mask_of_the_wrong_sample():
+    g = _g(33)
+    img, mask = torch.randn(2, 3, 5, 7, generator=g), torch.rand(2, 1, 5, 7, generator=g)
+    out = img * mask
+    assert torch.equal(R.mul_mask_fp64(img, mask).float(), out) and R.mul_mask_fp64(img, mask).dtype == torch.float64
+    assert _clean(R.check_mul_mask(out, img, mask))["worst"] == 0
+    fig = _caught(R.check_mul_mask(img * _wrong_sample(mask, 2, 3), img, mask))
+    assert fig["frame_fig"] == [35.0, 35.0]               # planes 0 1 0 | 1 0 1 where the masks are 0 0 0 | 1 1 1: channel 1 of each
+    off = out.clone()
+    off[1, 0, 2, 3] = torch.nextafter(off[1, 0, 2, 3], torch.tensor(9.0))
+    assert _caught(R.check_mul_mask(off, img, mask))["frame_fig"] == [0.0, 1.0]
+    zero = torch.zeros_like(img)
+    _caught(R.check_mul_mask(zero, -img.abs(), torch.zeros_like(mask)))                   # -x * 0 is -0: the sign is part of the bits
+
+
+def test_stage2_compose_reference_and_faults():
+    g = _g(34)
+    img, add = torch.rand(2, 3, 6, 9, generator=g), 2.0 * torch.randn(2, 3, 6, 9, generator=g)
+    mask, face = torch.rand(2, 1, 6, 9, generator=g), (torch.rand(2, 1, 6, 9, generator=g) > 0.3).float()
+    raw = img + add * (mask * face)
+    out = raw.clamp(0, 1)
+    assert (raw < 0).any() and (raw > 1).any()                                            # both clamps act
+    assert _close(R.stage2_compose_fp64(img, add, mask, face), out, 2.4e-7)
+    assert _clean(R.check_stage2_compose(out, img, add, mask, face))["worst"] <= 1
+    fused = (img.double() + add.double() * (mask * face).double()).float().clamp(0, 1)    # the contracted form: one rounding fewer
+    _clean(R.check_stage2_compose(fused, img, add, mask, face))
+    _caught(R.check_stage2_compose(raw, img, add, mask, face))                            # the clamp dropped
+    wrong = (img + add * (_wrong_sample(mask, 2, 3) * face)).clamp(0, 1)
+    _caught(R.check_stage2_compose(wrong, img, add, mask, face))
+    _caught(R.check_stage2_compose((img + add * mask).clamp(0, 1), img, add, mask, face))             # face_mask not applied
+    # an output the clamp decides is exactly 1: one ulp below is inside any error bound and still wrong
+    i = (raw > 1.5).flatten().nonzero()[0].item()
+    off = out.clone()
+    off.view(-1)[i] = torch.nextafter(torch.tensor(1.0), torch.tensor(0.0))
+    _caught(R.check_stage2_compose(off, img, add, mask, face))
+    # four ulps on an output inside (0, 1)
+    j = ((raw > 0.4) & (raw < 0.6)).flatten().nonzero()[0].item()
+    off = out.clone()
+    off.view(-1)[j] = out.view(-1)[j] * (1 + 8 * 2.0 ** -23)
+    _caught(R.check_stage2_compose(off, img, add, mask, face))
+
+
+# ---- pack_rgb8 / unpack_rgb8 ---------------------------------------------------------------------------------------------
+def test_pack_rgb8_reference_and_rounding_instead_of_truncation():
+    img = torch.cat([R.rgb8_edge_image(), torch.rand(1, 3, 4, 193, generator=_g(35)) * 1.4 - 0.2])
+    want = img.clamp(0, 1).mul(255).byte().permute(0, 2, 3, 1)
+    assert torch.equal(R.pack_rgb8_ref(img), want)
+    assert _clean(R.check_pack_rgb8(want.contiguous(), img))["frames"] == [0, 1]
+    rounded = img.clamp(0, 1).mul(255).round().byte().permute(0, 2, 3, 1)
+    assert _caught(R.check_pack_rgb8(rounded, img))["frame_fig"][1] > 100                 # about half of a random image
+    _caught(R.check_pack_rgb8(img.mul(255).byte().permute(0, 2, 3, 1), img))              # the clamp dropped: bytes wrap
+    _caught(R.check_pack_rgb8(want.flip(-1), img))                                        # BGR
+    with pytest.raises(ValueError):
+        R.check_pack_rgb8(want.permute(0, 3, 1, 2), img)
+
+
+def test_unpack_rgb8_reference_and_multiplication_by_the_reciprocal():
+    b = torch.arange(256, dtype=torch.uint8)
+    frames = torch.stack([b, b.flip(0), b.roll(50)], -1).reshape(1, 16, 16, 3)
+    want = frames.float().div(255).permute(0, 3, 1, 2)
+    # the fp64 quotient rounded to fp32 is the fp32 quotient, for every byte
+    assert torch.equal(R.unpack_rgb8_fp64(frames).float(), want) and R.unpack_rgb8_fp64(frames).dtype == torch.float64
+    _clean(R.check_unpack_rgb8(want.contiguous(), frames))
+    recip = frames.float().mul(torch.tensor(1.0 / 255)).permute(0, 3, 1, 2)
+    assert 0 < (recip != want).sum() and (recip - want).abs().max() <= 2.0 ** -24        # one ulp, on some bytes
+    _caught(R.check_unpack_rgb8(recip.contiguous(), frames))
+    _caught(R.check_unpack_rgb8(want.flip(1).contiguous(), frames))                       # channels reversed
+    # the round trip the video path relies on: every byte comes back
+    assert torch.equal(R.pack_rgb8_ref(want), frames)
+    assert torch.equal(R.pack_rgb8_ref(R.unpack_rgb8_fp64(frames).float()), frames)
+
+
 # ---- pose_theta ----------------------------------------------------------------------------------------------------------
 def test_pose_theta_reference_and_faults():
     g = _g(30)

@@ -11,6 +11,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import restate as O  # noqa: E402
 
 from emoportraits_amd import ops, stage2  # noqa: E402
+import ops_reference as R  # noqa: E402
 
 from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
 
@@ -32,8 +33,8 @@ def test_compose_kernels():
     img, add = torch.rand(2, 3, 8, 12, generator=g), torch.randn(2, 3, 8, 12, generator=g)
     m, f = torch.rand(2, 1, 8, 12, generator=g), (torch.rand(2, 1, 8, 12, generator=g) > 0.5).float()
     d = lambda t: t.to(DEV)
-    assert torch.equal(ops.mul_mask(d(img), d(m)).cpu(), img * m)
-    assert torch.allclose(ops.stage2_compose(d(img), d(add), d(m), d(f)).cpu(), (img + add * (m * f)).clamp(0, 1), atol=1e-7)
+    assert R.check_mul_mask(ops.mul_mask(d(img), d(m)), d(img), d(m))["failures"] == []
+    assert R.check_stage2_compose(ops.stage2_compose(d(img), d(add), d(m), d(f)), d(img), d(add), d(m), d(f))["failures"] == []
 
 
 def test_stage2_batchnorm_default_flags_vs_reference_golden(tiny):
