@@ -1,11 +1,12 @@
 """The frame plumbing of InferenceWrapper.animate_frames / animate_streams / paste_back / enrol_identities that touches no
 wrapper state: crop windows and the faces of a frame, uint8 frames -> fp32 crops (crops_of) and rendered crops -> frames
 (paste_into), the upload-ahead of a host chunk and the pinned ring that takes finished batches back to the host."""
+import collections
 import itertools
 
 import torch
 
-from . import ops
+from . import ops, parallel
 
 
 def square_windows(windows):
@@ -51,6 +52,73 @@ def face_spans(counts, lo, hi, batch_size):
     if hi > b0:
         spans.append((b0, hi))
     return spans
+
+
+# What a control launch needs to know about the rows of a batch (ChunkRows.where) or of a chunk (where_chunk).  ident: the slots of
+# the rows as the loop sees them (device tensor, None: the current identity) -- what mix and the render take.  The controls run over
+# the FULL rows these were taken from: r0 = the first full row's index in the call, n their number, slots their slots; at = None
+# where the loop's rows ARE the full rows, else int64 [rows] on the device: where each of the loop's rows lies among the n.
+RowsAt = collections.namedtuple("RowsAt", "ident r0 n slots at")
+
+
+class ChunkRows:
+    """The row arithmetic of one chunk of the clip loop (InferenceWrapper._animate_clip), host integers but for the tensors it hands on.
+    n frames, the chunk's frame i holding per[i] rows (per None: one row each -- windows=, boxes [N,4], whole frames), the first row
+    the call's row `row0`; `rank` of `world` takes the frames [lo, hi) (parallel.shard_range) in batches of whole frames with at most
+    batch_size rows and frames (face_spans).  ids: the slot of every row of the call (host tensor) or None, moved to `device` where
+    a launch takes them.
+    Under tracking skip_absent=True the rows are the KEPT rows: per[i] = the faces of frame i, row_of int64 [T] on the device = the row
+    among the chunk's n * P full rows that each kept row is, full0 = the chunk's first full row in the call, and ids are indexed
+    by the full rows.
+    Fields: off (the rows in front of every frame, n + 1), r0, r1 (the chunk's rows in the call), lo, hi, m_lo, m_hi (the shard's
+    frames and rows), spans and with_rows (the shard's batches, and those that hold a row), ident (the slots of the shard's rows, on
+    the device), counts (the rows of every rank's shard, as parallel.gather_rows takes them; None where the chunk holds no kept row
+    and nothing is to be gathered)."""
+
+    def __init__(self, n, per, rank, world, batch_size, row0, ids=None, device=None, P=None, full0=0, row_of=None):
+        self.n, self.per, self.r0, self.P, self.full0, self.row_of, self._ids, self._device = n, per, row0, P, full0, row_of, ids, device
+        counts = [1] * n if per is None else per
+        self.off = face_offsets(counts)
+        self.r1 = row0 + self.off[n]
+        self.lo, self.hi = parallel.shard_range(n, rank, world)
+        self.m_lo, self.m_hi = self.rows(self.lo, self.hi)
+        self.spans = face_spans(counts, self.lo, self.hi, batch_size)
+        self.with_rows = [sp for sp in self.spans if self.off[sp[0]] < self.off[sp[1]]]
+        self.counts = None if row_of is not None and self.r1 == self.r0 else \
+            [self.off[b] - self.off[a] for a, b in (parallel.shard_range(n, r, world) for r in range(world))]
+        # (slots: under skip, the slots of the chunk's full rows)
+        self.slots = None if ids is None or row_of is None else ids[full0:full0 + n * P].to(device)
+        self.ident = None if ids is None else ids[self.m_lo:self.m_hi].to(device) if row_of is None else self.slots.index_select(0, self.shard(row_of))
+
+    def rows(self, b0, b1):
+        """the rows of the chunk's frames [b0, b1), as indices in the call"""
+        return self.r0 + self.off[b0], self.r0 + self.off[b1]
+
+    def frame_of(self, b0, b1):
+        """the frame, counted from b0, of every row of the frames [b0, b1); None: one row per frame"""
+        return None if self.per is None else [i - b0 for i in range(b0, b1) for _ in range(self.per[i])]
+
+    def part(self, t, b0, b1):
+        """of something that has one entry per row of the rank's shard of the chunk, the entries of the frames [b0, b1)"""
+        return None if t is None else t[self.rows(b0, b1)[0] - self.m_lo:self.rows(b0, b1)[1] - self.m_lo]
+
+    def shard(self, t):
+        """of something that has one entry per row of the chunk, the entries of the rank's shard"""
+        return t[self.m_lo - self.r0:self.m_hi - self.r0]
+
+    def where(self, b0, b1):
+        """the RowsAt of the frames [b0, b1) of the shard"""
+        ident, (a, b) = self.part(self.ident, b0, b1), self.rows(b0, b1)
+        if self.row_of is None:
+            return RowsAt(ident, a, b - a, ident, None)
+        f0, f1 = b0 * self.P, b1 * self.P                                   # (the frames' full rows, counted from the chunk's first)
+        return RowsAt(ident, self.full0 + f0, f1 - f0, None if self.slots is None else self.slots[f0:f1], self.row_of[a - self.r0:b - self.r0] - f0)
+
+    def where_chunk(self):
+        """the RowsAt of the whole chunk, every rank's rows: what a pass over the gathered rows takes (its ident is the shard's)"""
+        if self.row_of is None:
+            return RowsAt(self.ident, self.r0, self.r1 - self.r0, None if self._ids is None else self._ids[self.r0:self.r1].to(self._device), None)
+        return RowsAt(self.ident, self.full0, self.n * self.P, self.slots, self.row_of)
 
 
 FORMATS = ("rgb8", "nv12", "yuv420p", "p010", "yuv420p10")     # packed RGB bytes, or YUV 4:2:0 under ffmpeg's pixel-format names

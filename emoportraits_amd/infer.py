@@ -1496,74 +1496,72 @@ class InferenceWrapper:
                          batch_size=batch_size, smooth_pose=smooth_pose, mix=mix, mix_old=mix_old, target_theta=target_theta, ex=ex,
                          hp=hp, track=track, min_side=min_side, row_masks=None)
 
-    def _over_full_rows(self, full, control, *inputs):
-        """tracking skip_absent=True: a control launch of kept rows over the full rows they were taken from.  full = (at, slots, r0,
-        n): at int64 [m] on the device = where each kept row lies among the n full rows r0 ... r0 + n of the call, slots = the
-        identities of those n rows (None: the current identity).  inputs [m, ...] are scattered into zeros [n, ...] (an absent row
-        reads zeros), control(*full inputs, slots, r0) is the launch of the call that skips nothing -- per-row values and row masks
-        indexed by the full rows -- and its result, a tensor or a tuple of tensors over the n rows, comes back as the kept rows."""
-        at, slots, r0, n = full
-        wide = []
-        for t in inputs:
-            t = t.to(self.device).float()
-            wide.append(torch.zeros((n,) + tuple(t.shape[1:]), device=self.device, dtype=t.dtype).index_copy_(0, at, t))
-        out = control(*wide, slots, r0)
-        if isinstance(out, tuple):
-            return tuple(t.index_select(0, at) for t in out)
-        return out.index_select(0, at)
+    def _control(self, at, fn, *inputs):
+        """One launch of a control over the rows `at` (a frames.RowsAt): fn(*inputs over the full rows, their slots, the first one's
+        index in the call) -> a tensor or a tuple of tensors over those rows.  at.at None: the inputs [m, ...] ARE the full rows and go
+        to fn as they came.  Else (tracking skip_absent=True) they are the kept rows: they are scattered into zeros [at.n, ...] by at.at
+        (an absent row reads zeros), the launch is the one of the call that skips nothing -- per-row values and row masks indexed by the
+        full rows -- and the kept rows of its result come back.  No kept row at all: the launch over zeros, nothing comes back."""
+        if at.at is None:
+            return fn(*inputs, at.slots, at.r0)
+        wide = [torch.zeros((at.n,) + tuple(t.shape[1:]), device=self.device, dtype=t.dtype).index_copy_(0, at.at, t)
+                for t in (t.to(self.device).float() for t in inputs)]
+        out = fn(*wide, at.slots, at.r0)
+        return tuple(t.index_select(0, at.at) for t in out) if isinstance(out, tuple) else out.index_select(0, at.at)
 
-    def _batch_theta(self, crops, ident, plan, row0, edit=True, mix=True, smooth=None, full=None):
-        """The front of a driver batch of the video paths, crops [m,3,S,S] = the rows row0 ... of the call -> (theta, align): the head
-        pose the regressor finds, edited per row by the head-pose controls (plan.hp) and then mixed, and what the expression embedder
-        aligns the crops by -- under an active head-pose edit the regressor's OWN theta of the rows, else None = the theta the batch
-        is rendered with.  Either may be the regressor's output buffer: a caller that holds it past the batch clones it.
+    def _expression_width(self):
+        """E of the expression vectors: the bank's rows' where it has some, else the configuration's"""
+        return self._bank_expr.shape[1] if self._bank_expr is not None else self.cfg["lpe_output_channels_expression"]
+
+    def _override_rows(self, ex, at):
+        """the expression override of the rows `at`: read over their full rows, the kept ones selected where rows were left out"""
+        rows = control_streams.rows_of(ex.override, at.r0, at.n, 'expression override')
+        return rows if at.at is None else rows.index_select(0, at.at)
+
+    def _batch_theta(self, crops, at, plan, edit=True, mix=True, smooth=None):
+        """The front of a driver batch of the video paths, crops [m,3,S,S] = the rows `at` of the call (a frames.RowsAt) -> (theta,
+        align): the head pose the regressor finds, edited per row by the head-pose controls (plan.hp, over the full rows: _control) and
+        then mixed (mix has neither state nor per-row values: on the rows themselves), and what the expression embedder aligns the
+        crops by -- under an active head-pose edit the regressor's OWN theta of the rows, else None = the theta the batch is rendered
+        with.  Either may be the regressor's output buffer: a caller that holds it past the batch clones it.  pred_target_srt is
+        left as the edit of the batch's rows.
         edit=False: a pass that gathers the rows of every rank edits them, and in theta's place come the regressed (scale, rotation,
         translation) as [m,9] rows.  mix=False: the caller mixes, once over its rows of the chunk.  smooth: None = mix alone, and
-        only where plan.mix asks for it (a clip); a bool = mix and the one-pass smooth_pose of the batch's rows (streams).
-        full: tracking skip_absent=True -- the crops are the kept rows of whole frames, and the head-pose controls run over the full
-        rows of those frames (_over_full_rows); mix has neither state nor per-row values and stays on the kept rows."""
+        only where plan.mix asks for it (a clip); a bool = mix and the one-pass smooth_pose of the batch's rows (streams)."""
         theta, *srt = self._head_pose(crops)
         align = None
         if plan.hp is not None:
             align = theta
             if not edit:
                 theta = self._srt9(srt)
-            elif full is None:
-                theta = self._head_pose_controls(srt, ident, plan.hp, row0, plan.row_masks)[1]
             else:
-                edited, theta = self._over_full_rows(full, lambda a, b, c, slots, r: self._head_pose_controls(
-                    (a, b, c), slots, plan.hp, r, plan.row_masks), *srt)
+                edited, theta = self._control(at, lambda a, b, c, slots, r: self._head_pose_controls((a, b, c), slots, plan.hp, r,
+                                                                                                     plan.row_masks), *srt)
                 self.pred_target_srt = tuple(edited[:, i:i + 3] for i in (0, 3, 6))
         if mix and (plan.mix or smooth is not None):
-            theta = self._pose_controls(theta, ident, plan.mix, plan.mix_old, bool(smooth), row0, plan.row_masks)
+            theta = self._pose_controls(theta, at.ident, plan.mix, plan.mix_old, bool(smooth), at.r0, plan.row_masks)
         return theta, align
 
     def _batch_expression(self, crops, theta, align):
         """the expression embedder on a driver batch: its crops aligned by `align` (_batch_theta), or by the theta it is rendered with"""
         return self._expression(crops, theta if align is None else align, 'a driver call')[0]
 
-    def _drive_crops(self, crops, ident, plan, theta=None, smooth=None, row0=0, pose=None, align=None, full=None):
-        """The sequence of one driver batch of the video paths, crops [m,3,S,S] -> (the rendered batch as plan.out_kind says, its
-        paste matte or None): head pose -> head-pose controls -> pose controls (_batch_theta) -> expression embedder (or the
-        override) -> expression controls -> render -> matte, in forward()'s order.  row0: the batch's first row in the call (the
-        controls' per-row values).  theta, align: the batch's thetas and what the embedder aligns by where a pass in front of the
-        loop has formed them (the passes of a clip that walk the rows of several ranks); pose: its controlled expressions
-        likewise.  smooth, full: _batch_theta's; with `full` the override is read and the expression controls run over the full rows."""
+    def _drive_crops(self, crops, at, plan, theta=None, smooth=None, pose=None, align=None):
+        """The sequence of one driver batch of the video paths, crops [m,3,S,S] = the rows `at` of the call (a frames.RowsAt: the
+        controls' per-row values and slots) -> (the rendered batch as plan.out_kind says, its paste matte or None): head pose ->
+        head-pose controls -> pose controls (_batch_theta) -> expression embedder (or the override) -> expression controls -> render
+        -> matte, in forward()'s order.  theta, align: the batch's thetas and what the embedder aligns by where a pass in front of
+        the loop has formed them (the passes of a clip that walk the rows of several ranks); pose: its controlled expressions
+        likewise.  smooth: _batch_theta's."""
         if theta is None:
-            theta, align = self._batch_theta(crops, ident, plan, row0, smooth=smooth, full=full)
+            theta, align = self._batch_theta(crops, at, plan, smooth=smooth)
         self.pred_target_theta = theta                                           # (as forward() leaves it: infer.py:584)
         ex = plan.ex
         if pose is None:
-            if ex is not None and ex.override is not None:
-                pose = control_streams.rows_of(ex.override, row0, crops.shape[0], 'expression override') if full is None else \
-                    control_streams.rows_of(ex.override, full[2], full[3], 'expression override').index_select(0, full[0])
-            else:
-                pose = self._batch_expression(crops, theta, align)
-            if ex is not None and full is None:
-                pose = self._expression_controls(pose, ident, ex, row0, plan.row_masks)
-            elif ex is not None:
-                pose = self._over_full_rows(full, lambda v, slots, r: self._expression_controls(v, slots, ex, r, plan.row_masks), pose)
-        out = self._render(pose, theta, ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
+            pose = self._override_rows(ex, at) if ex is not None and ex.override is not None else self._batch_expression(crops, theta, align)
+            if ex is not None:
+                pose = self._control(at, lambda v, slots, r: self._expression_controls(v, slots, ex, r, plan.row_masks), pose)
+        out = self._render(pose, theta, at.ident, plan.target_theta, plan.masks_of, plan.out_kind, plan.fmt[1:])
         return out, (None if plan.matte_fn is None else plan.matte_fn(out).float().contiguous())
 
     def _track(self, states, boxes, stream_of, sizes, plan, row0, restart=None):
@@ -1617,6 +1615,9 @@ class InferenceWrapper:
         per-frame entry points (frame_of=None) and the single-stream smooth_pose.  Per chunk the frames are sharded across the
         ranks; a batch is a span of whole frames (frames.face_spans).  With plan.track (boxes=) wins is None: the windows of a
         chunk are formed on the device in front of its batches (_track_chunk), P rows per frame where the boxes are [N,P,4].
+        The row arithmetic of a chunk -- which rows a span of frames holds, the rank's shard, its batches -- is one
+        frames.ChunkRows, `rows`; a batch is handed rows.where(b0, b1), a frames.RowsAt, and every control is launched through
+        _control with it.
         A chunk is rendered in up to three passes over the spans of the rank's frames, each through `walk`: the head-pose pass
         (smooth_pose, or a relative head pose on several ranks) and the expression pass (relative / smooth on several ranks) form
         the thetas and the expressions that follow the frame order across the ranks (`scan`), the render pass drives the batches.
@@ -1625,9 +1626,10 @@ class InferenceWrapper:
         (ops.present_rows), and the number of faces of every frame is copied to the host -- the one host wait per chunk the field
         adds, on every rank.  From there per[i] is that number, exactly as faces= counts its faces: the spans hold at most
         batch_size kept rows, the crop, the networks, the paste and what is yielded see kept rows only, and the identities are
-        ids[row_of].  The controls alone still run over the full rows of a span's frames (_over_full_rows; over the chunk's in
-        `scan`), and where a track can restart a span without a kept row still launches the controls that carry state, over
-        zeros: a death in it clears its stream as it does in the call that skips nothing.  tracked_rows = (row_of [T], first,
+        ids[row_of].  The controls alone still run over the full rows of a span's frames (the RowsAt then says where the kept rows
+        lie among them, and _control scatters and gathers; over the chunk's in `scan`), and where a track can restart a span
+        without a kept row still launches the controls that carry state -- the same _control, with no kept row: over zeros -- so a
+        death in it clears its stream as it does in the call that skips nothing.  tracked_rows = (row_of [T], first,
         the chunk's first full row); tracked_windows, tracked_present and tracked_assignment stay in the full row space."""
         S, ids, paste_back, ex, hp = self.cfg["image_size"], plan.ids, plan.paste_back, plan.ex, plan.hp
         P = None if plan.track is None else plan.track.tracks
@@ -1641,50 +1643,31 @@ class InferenceWrapper:
             # which rows a span of frames holds: per[i] = the rows of the chunk's frame i -- the faces of faces=, the P tracks of boxes
             # [N,P,4], or None for one row per frame and the per-frame entry points (windows=, boxes [N,4], whole frames)
             per = [P] * n if P is not None else None if counts is None else counts[base:base + n]
-            tracked = row_of = None
-            if skip and not n:
-                tracked, row_of = self._track_chunk(plan, n, base, None, full0), torch.empty((0,), dtype=torch.int64, device=self.device)
-            elif skip:
-                if ids is not None and full0 + n * P > ids.shape[0]:
-                    raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
-                tracked = self._track_chunk(plan, n, base, frames_mod.frame_size(chunk, plan.fmt[0]), full0)
+            if counts is None and ids is not None and (full0 if skip else row0) + n * (P or 1) > ids.shape[0]:
+                raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
+            tracked, row_of = None, torch.empty((0,), dtype=torch.int64, device=self.device) if skip else None
+            if plan.track is not None:
+                # every rank tracks the whole chunk (the boxes are inputs every rank has), then slices its batches' windows
+                tracked = self._track_chunk(plan, n, base, frames_mod.frame_size(chunk, plan.fmt[0]) if n else None, full0 if skip else row0)
+            if skip and n:
                 count, _, row_of, *tracked = ops.present_rows(tracked[0].tensor, tracked[1].tensor, n, P)
                 per = count.tolist()                                             # (the host wait of the chunk)
                 self.tracked_rows = (row_of[:sum(per)], frames_mod.face_offsets(per), full0)
                 row_of = self.tracked_rows[0].long()
-                tracked = [ops.DeviceWindows(w) for w in tracked]
-            off = frames_mod.face_offsets([1] * n if per is None else per)
-            if counts is None and not skip and ids is not None and row0 + off[n] > ids.shape[0]:
-                raise ValueError(f"identities has {ids.shape[0]} entries, the frames run past it")
-            rows = lambda b0, b1: (row0 + off[b0], row0 + off[b1])              # the rows of the chunk's frames [b0, b1)
-            frame_of = lambda b0, b1: None if per is None else [i - b0 for i in range(b0, b1) for _ in range(per[i])]
-            lo, hi = parallel.shard_range(n, self.rank, self.world)
-            spans = frames_mod.face_spans([1] * n if per is None else per, lo, hi, plan.batch_size)
-            with_faces = [sp for sp in spans if rows(*sp)[0] < rows(*sp)[1]]
-            (r0, r1), (m_lo, m_hi) = rows(0, n), rows(lo, hi)
-            # of something that has one entry per row of the rank's shard of the chunk, the entries of the frames [b0, b1)
-            part = lambda t, b0, b1: None if t is None else t[rows(b0, b1)[0] - m_lo:rows(b0, b1)[1] - m_lo]
-            crop_w = paste_w = None if wins is None else wins[m_lo:m_hi]
+                tracked = [ops.DeviceWindows(w) for w in tracked]                # (the kept rows' windows, compacted)
+            rows =frames_mod.ChunkRows(n, per, self.rank, self.world, plan.batch_size, row0, ids, self.device, P, full0, row_of)
+            crop_w = paste_w = None if wins is None else wins[rows.m_lo:rows.m_hi]
             if tracked is not None:
-                crop_w, paste_w = (w[m_lo - r0:m_hi - r0] for w in tracked)      # (the kept rows' windows, compacted)
-            elif plan.track is not None:
-                # every rank tracks the whole chunk (the boxes are inputs every rank has), then slices its batches' windows
-                crop_w, paste_w = (w[m_lo - r0:m_hi - r0]
-                                   for w in self._track_chunk(plan, n, base, frames_mod.frame_size(chunk, plan.fmt[0]), r0))
-            ids_dev = None if ids is None else ids[m_lo:m_hi].to(self.device)
-            full_of = lambda b0, b1: None
-            if skip:
-                ids_full = None if ids is None else ids[full0:full0 + n * P].to(self.device)
-                ids_dev = None if ids is None else ids_full.index_select(0, row_of[m_lo - r0:m_hi - r0])
-                # of the frames [b0, b1): where their kept rows lie among their full rows, those rows' slots, the first, their number
-                full_of = lambda b0, b1: (row_of[off[b0]:off[b1]] - b0 * P, None if ids is None else ids_full[b0 * P:b1 * P],
-                                          full0 + b0 * P, (b1 - b0) * P)
+                crop_w, paste_w = (rows.shard(w) for w in tracked)
             # a track that restarts does so whether or not its row is kept: under skip, with restart flags, the spans without a
             # kept row still launch the controls that carry state from batch to batch on this rank
             restarts = skip and plan.row_masks is not None and plan.row_masks[0] is not None
             # crops stay resident from one pass to the next (3 MB per frame at 512^2) while the rank's rows of the chunk fit the budget
-            keep = (m_hi - m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
+            keep = (rows.m_hi - rows.m_lo) * 3 * S * S * 4 <= _SMOOTH_KEEP_BYTES
             kept, thetas, aligns, poses = {}, {}, {}, None
+            # the two controls as _control launches them: fn(the full rows, their slots, the first one's index in the call)
+            hp_fn = lambda a, b, c, slots, r: self._head_pose_controls((a, b, c), slots, hp, r, plan.row_masks)
+            ex_fn = lambda v, slots, r: self._expression_controls(v, slots, ex, r, plan.row_masks)
 
             def walk(last=False):
                 """(b0, b1, crops, uploaded frames or None) for every span a pass needs: the crops an earlier pass kept, or a fresh
@@ -1693,44 +1676,46 @@ class InferenceWrapper:
                 paste_back: the crops were kept, not the frames, 6 MB at 1080p; a span without a face then comes with crops None).
                 The last pass lets go of what was kept."""
                 pasted = last and paste_back
-                need = spans if pasted or restarts else with_faces              # (restarts: walk's callers launch `absent`)
-                fresh = frames_mod.uploaded(chunk, [sp for sp in need if pasted or sp[0] not in kept and sp in with_faces], self.device,
+                need = rows.spans if pasted or restarts else rows.with_rows     # (restarts: walk's callers launch `absent`)
+                fresh = frames_mod.uploaded(chunk, [sp for sp in need if pasted or sp[0] not in kept and sp in rows.with_rows], self.device,
                                             plan.upload_stream)
                 for b0, b1 in need:
                     crops, u8 = kept.pop(b0, None) if last else kept.get(b0), None
-                    if pasted or crops is None and (b0, b1) in with_faces:
+                    if pasted or crops is None and (b0, b1) in rows.with_rows:
                         f0, f1, u8 = next(fresh)
                         assert (f0, f1) == (b0, b1)
-                    if crops is None and (b0, b1) in with_faces:
-                        crops = frames_mod.crops_of(u8, S, part(crop_w, b0, b1), *plan.fmt, frame_of=frame_of(b0, b1))
+                    if crops is None and (b0, b1) in rows.with_rows:
+                        crops = frames_mod.crops_of(u8, S, rows.part(crop_w, b0, b1), *plan.fmt, frame_of=rows.frame_of(b0, b1))
                         if keep and not last:
                             kept[b0] = crops
                     yield b0, b1, crops, u8
 
-            def scan(control, local=None, every=None):
+            def scan(fn, local=None, every=None):
                 """A control that walks the rows of every rank in frame order: the rank's rows `local` of the chunk are gathered in
-                row order on every rank (every=: rows every rank has already), control(all rows of the chunk, their slots, the
-                chunk's first row) runs over the whole chunk on every rank -- so the streams' state is the same everywhere,
-                whichever rank formed a row -- and the rank's own rows of the result come back."""
-                if every is None:
-                    per_rank = [rows(*parallel.shard_range(n, r, self.world)) for r in range(self.world)]
-                    every = local if skip and r1 == r0 else parallel.gather_rows(local, [b - a for a, b in per_rank], self.rank, self.world)
-                    if skip:                                                     # the chunk's kept rows -> its full rows, absent ones zeros
-                        every = torch.zeros((n * P,) + tuple(every.shape[1:]), device=self.device, dtype=every.dtype).index_copy_(0, row_of, every)
-                if skip:
-                    return control(every, ids_full, full0).index_select(0, row_of)[m_lo - r0:m_hi - r0]
-                return control(every, None if ids is None else ids[r0:r1].to(self.device), r0)[m_lo - r0:m_hi - r0]
+                row order on every rank (every=: a function of the chunk's RowsAt that returns rows every rank has already),
+                fn runs over the whole chunk on every rank (_control) -- so the streams' state is the same everywhere, whichever
+                rank formed a row -- and the rank's own rows of the result come back."""
+                at = rows.where_chunk()
+                every = every(at) if every is not None else local if rows.counts is None else \
+                    parallel.gather_rows(local, rows.counts, self.rank, self.world)
+                return rows.shard(self._control(at, fn, every))
 
             def absent(b0, b1, head, expression):
                 """skip with restart flags: the frames [b0, b1) hold no kept row, and the controls that carry state from batch to
-                batch on this rank are still launched over their rows, as zeros: a restart in them reaches its stream"""
-                full = full_of(b0, b1)
+                batch on this rank are still launched over their rows -- _control with no kept row: over zeros -- so that a restart
+                in them reaches its stream.  (pred_target_srt is then the edit of those full rows.)"""
+                at = rows.where(b0, b1)
                 if head and hp is not None and hp.relative and not gather_srt:
-                    zeros = tuple(torch.zeros((full[3], 3), device=self.device) for _ in range(3))
-                    self._head_pose_controls(zeros, full[1], hp, full[2], plan.row_masks)
+                    self._control(at, hp_fn, *(torch.empty((0, 3), device=self.device) for _ in range(3)))
                 if expression and ex is not None and ex.scan and self.world == 1:
-                    E = self._bank_expr.shape[1] if self._bank_expr is not None else self.cfg["lpe_output_channels_expression"]
-                    self._expression_controls(torch.zeros((full[3], E), device=self.device), full[1], ex, full[2], plan.row_masks)
+                    self._control(at, ex_fn, torch.empty((0, self._expression_width()), device=self.device))
+
+            def front(b0, b1, crops, **kw):
+                """_batch_theta on a span in a pass in front of the render; what the embedder aligns by is kept for the passes behind"""
+                theta, align = self._batch_theta(crops, rows.where(b0, b1), plan, **kw)
+                if align is not None:
+                    aligns[b0] = align.clone()
+                return theta, align
 
             # a relative head pose walks the rows of every rank: their regressed (scale, rotation, translation) are gathered and edited
             # on every rank, so the anchor is the stream's first row whichever rank regressed it
@@ -1741,46 +1726,33 @@ class InferenceWrapper:
                     if crops is None:
                         absent(b0, b1, True, False)
                         continue
-                    theta, align = self._batch_theta(crops, part(ids_dev, b0, b1), plan, rows(b0, b1)[0], edit=not gather_srt, mix=False,
-                                                     full=full_of(b0, b1))
-                    if align is not None:
-                        aligns[b0] = align.clone()
+                    theta, align = front(b0, b1, crops, edit=not gather_srt, mix=False)
                     local.append(theta.clone() if align is None else theta)
                 local = torch.cat(local) if local else torch.empty((0, 9) if gather_srt else (0, 4, 4), device=self.device)
                 if gather_srt:
-                    local = scan(lambda every, slots, r: self._head_pose_controls(tuple(every[:, i:i + 3].contiguous() for i in (0, 3, 6)),
-                                                                                  slots, hp, r, plan.row_masks)[1], local)
+                    local = scan(lambda every, slots, r: hp_fn(*(every[:, i:i + 3].contiguous() for i in (0, 3, 6)), slots, r)[1], local)
                 if plan.mix:
-                    local = self._pose_controls(local, ids_dev, True, plan.mix_old, False)
+                    local = self._pose_controls(local, rows.ident, True, plan.mix_old, False)
                 if plan.smooth_pose:
                     local = scan(lambda every, slots, r: self._pose_controls(every, slots, False, plan.mix_old, True, r, plan.row_masks),
                                  local)
-                thetas = {b0: part(local, b0, b1) for b0, b1 in with_faces}
+                thetas = {b0: rows.part(local, b0, b1) for b0, b1 in rows.with_rows}
             if ex is not None and ex.scan and self.world > 1:
                 # relative / smooth walk the rows of every rank: the expressions of the rank's rows, or the override's, which every rank has
-                control = lambda every, slots, r: self._expression_controls(every, slots, ex, r, plan.row_masks)
                 if ex.override is not None:
-                    poses = scan(control, every=control_streams.rows_of(ex.override, *((full0, n * P) if skip else (r0, r1 - r0)),
-                                                                        'expression override'))
+                    poses = scan(ex_fn, every=lambda at: self._override_rows(ex, at))
                 else:
                     local = []
                     for b0, b1, crops, _ in walk():
                         if crops is None:                                        # (restarts: nothing here carries state on this rank alone)
                             continue
                         if b0 not in thetas:
-                            theta, align = self._batch_theta(crops, part(ids_dev, b0, b1), plan, rows(b0, b1)[0], full=full_of(b0, b1))
-                            if align is not None:
-                                aligns[b0] = align.clone()
-                            thetas[b0] = theta.clone()
+                            thetas[b0] = front(b0, b1, crops)[0].clone()
                         local.append(self._batch_expression(crops, thetas[b0], aligns.get(b0)).float().clone())
-                    if local:
-                        local = torch.cat(local)
-                    else:                                                        # (a rank without a row still joins the gather)
-                        E = self._bank_expr.shape[1] if self._bank_expr is not None else self.cfg["lpe_output_channels_expression"]
-                        local = torch.empty((0, E), device=self.device)
-                    poses = scan(control, local)
+                    # (a rank without a row still joins the gather)
+                    poses = scan(ex_fn, torch.cat(local) if local else torch.empty((0, self._expression_width()), device=self.device))
             for b0, b1, crops, u8 in walk(last=True):
-                m0 = rows(b0, b1)[0]
+                m0 = rows.rows(b0, b1)[0]
                 if crops is None and restarts:                                   # (the head pose: unless a pass in front has walked it)
                     absent(b0, b1, not plan.smooth_pose, True)
                     if not paste_back:
@@ -1788,17 +1760,18 @@ class InferenceWrapper:
                 if crops is None:                                                # (paste_back: frames without a face, as they came)
                     out = u8.clone() if chunk.is_cuda else u8
                 else:
-                    out, m = self._drive_crops(crops, part(ids_dev, b0, b1), plan, thetas.pop(b0, None), row0=m0, pose=part(poses, b0, b1),
-                                               align=aligns.pop(b0, None), full=full_of(b0, b1))
+                    out, m = self._drive_crops(crops, rows.where(b0, b1), plan, thetas.pop(b0, None), pose=rows.part(poses, b0, b1),
+                                               align=aligns.pop(b0, None))
                     if paste_back:
                         full = u8.clone() if chunk.is_cuda else u8               # (a host chunk's upload is this span's own)
-                        out = frames_mod.paste_into(full, out, part(paste_w, b0, b1), plan.feather, m, *plan.fmt, frame_of=frame_of(b0, b1))
+                        out = frames_mod.paste_into(full, out, rows.part(paste_w, b0, b1), plan.feather, m, *plan.fmt,
+                                                    frame_of=rows.frame_of(b0, b1))
                 index = base + b0 if paste_back else m0
                 if plan.ring is not None:
                     yield from plan.ring.push(index, out)
                 else:
                     yield index, out
-            base, row0, full0 = base + n, r1, full0 + (n * P if skip else 0)
+            base, row0, full0 = base + n, rows.r1, full0 + (n * P if skip else 0)
         if plan.ring is not None:
             yield from plan.ring.drain()
 
@@ -1981,7 +1954,8 @@ class InferenceWrapper:
                     crop_w, paste_w = self._track(crop_states, torch.stack(boxes), torch.tensor(of_row, dtype=torch.int32).to(self.device),
                                                   sizes, plan, m0)
                 crops = ops.crop_faces_mixed(frames, S, crop_w, frame_of, *plan.fmt)
-                out, m = self._drive_crops(crops, None if ids_dev is None else ids_dev[m0:m1], plan, smooth=smooth_pose, row0=m0)
+                ident = None if ids_dev is None else ids_dev[m0:m1]
+                out, m = self._drive_crops(crops, frames_mod.RowsAt(ident, m0, m1 - m0, ident, None), plan, smooth=smooth_pose)
                 if paste_back:
                     ops.paste_faces_mixed(frames, out, paste_w, frame_of, feather, m, *plan.fmt)
             if paste_back:

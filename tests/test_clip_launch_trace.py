@@ -39,6 +39,54 @@ def _items(run):
     return {first + (i,) if isinstance(first, tuple) else first + i: out[i] for first, out in run["yields"] for i in range(out.shape[0])}
 
 
+def _batches(counts, world):
+    """[(rank, first frame, last frame + 1)] of every batch of the clip whose frame i holds counts[i] rows, as the clip loop forms them"""
+    from emoportraits_amd import frames as frames_mod
+    from emoportraits_amd import parallel
+    out, base = [], 0
+    for n in T.CHUNKS:
+        for rank in range(world):
+            lo, hi = parallel.shard_range(n, rank, world)
+            out += [(rank, base + a, base + b) for a, b in frames_mod.face_spans(counts[base:base + n], lo, hi, T.BATCH)]
+        base += n
+    return out
+
+
+def test_the_cases_show_what_they_are_there_for():
+    """the planted dropouts of the combinations 14 ... 17 leave, on one rank and on two, a batch without a kept row, a chunk whose shard
+    on rank 1 has none, frames with one kept row and with two; the detections of 16 let a track die in such a batch, on one rank and
+    on two, and bear a face into a slot a death freed"""
+    from emoportraits_amd import hostglue, parallel
+    kept = T.KEPT_COUNTS
+    assert len(kept) == T.N == sum(T.CHUNKS) and 1 in kept and 2 in kept
+    boxes = T._dropout_boxes()
+    assert tuple(boxes.shape) == (T.N, 2, 4) and (2 - boxes.isnan().any(-1).sum(1)).tolist() == kept
+    assert all(boxes[f, p].isnan().all() == (p in T.MISSING.get(f, ())) for f in range(T.N) for p in (0, 1))
+    empty = {world: [(r, a, b) for r, a, b in _batches(kept, world) if not sum(kept[a:b])] for world in (1, 2)}
+    assert (0, 3, 6) in empty[1] and (0, 3, 4) in empty[2]
+    lo, hi = parallel.shard_range(T.CHUNKS[1], 1, 2)
+    first = T.CHUNKS[0]
+    assert sum(kept[first + lo:first + hi]) == 0 < sum(kept[first:first + lo])      # rank 1 of the second chunk: nobody, rank 0: somebody
+    # detections=: hostglue's account of the association
+    dets = T._detections().numpy()
+    assert dets.shape == (T.N, 4, 4) and len({tuple(np.isfinite(dets[t, :, 0]).tolist()) for t in range(T.N)}) > 3  # (no stable order)
+    ref, age = np.zeros((1, 2, 4)), np.full((1, 2), -1, np.int32)
+    tracked, restart, _ = hostglue.track_assign(dets, None, ref, age, min_iou=0.3, max_missed=1)
+    present = np.isfinite(tracked).all(-1)
+    seen = T.SEEN_COUNTS
+    assert present.sum(1).tolist() == seen == [sum(t in frames for frames, _ in T.SEEN.values()) for t in range(T.N)]
+    assert seen[:T.CHUNKS[0]] == kept[:T.CHUNKS[0]]                             # (the first chunk's batches are those above)
+    deaths = [(f, p) for f in range(T.N) for p in (0, 1) if restart[f, p] and not present[f, p]]
+    births = [(f, p) for f in range(T.N) for p in (0, 1) if restart[f, p] and present[f, p]]
+    assert deaths == [(3, 0), (4, 1)] and births == [(0, 0), (2, 1), (6, 0), (6, 1)]
+    empty = {world: [(r, a, b) for r, a, b in _batches(seen, world) if not sum(seen[a:b])] for world in (1, 2)}
+    assert empty == {1: [(0, 3, 6)], 2: [(0, 3, 4)]}
+    for world in (1, 2):                                                         # a death in a batch that holds no kept row
+        assert any(a <= f < b for f, _ in deaths for _, a, b in empty[world]), world
+    assert any(fd < fb and pd == pb for fd, pd in deaths for fb, pb in births)   # a birth into a freed slot
+    assert present[-1].all()                                                     # both tracks live at the end: the streams end with a state
+
+
 @pytest.mark.parametrize("keep", ["default", "0"])
 @pytest.mark.parametrize("combo", SHARDED)
 def test_two_ranks_render_the_rows_of_one(runs, combo, keep):

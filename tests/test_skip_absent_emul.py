@@ -317,8 +317,17 @@ def test_the_controls_walk_the_full_rows_and_the_kept_rows_are_those_of_the_call
     ids, td = [0, 2] * N, torch.from_numpy(dets)
     follow = dict(TC.TRACKING, follow_tracks=True)
     TC._reset(w)
+    from emoportraits_amd import ops
+    edits, controls = [], ops.head_pose_controls
+
+    def head_pose_controls(*args, **kwargs):
+        out = controls(*args, **kwargs)
+        edits.append(out[0].clone())
+        return out
+    monkeypatch.setattr(ops, "head_pose_controls", head_pose_controls)
     pose, theta = _drive(w, clip, td, tracking=follow, identities=ids, batch_size=4, **TC.CONTROLS)
     assert pose.shape[0] == 2 * N
+    edited = torch.cat(edits)[torch.from_numpy(keep)]                            # the edited (scale, rotation, translation) of the kept rows
     states = _states(w)
     full_in = {kind: torch.cat([s[0] for s in w.seen[kind]]) for kind in w.seen}
     assert NAME not in w.lib.calls
@@ -330,6 +339,9 @@ def test_the_controls_walk_the_full_rows_and_the_kept_rows_are_those_of_the_call
         got = _drive(w, kw.pop("frames"), kw.pop("detections"), tracking=skip, identities=ids, **kw, **TC.CONTROLS)
         assert TC.C.same_bits(got[0], pose[keep]) and TC.C.same_bits(got[1], theta[keep]), kw
         assert _same_states(_states(w), states), kw
+        # pred_target_srt is the last batch's edit of the rows it rendered: its kept rows, not the full rows of its frames
+        left = torch.cat(w.pred_target_srt, 1)
+        assert 1 <= left.shape[0] <= kw["batch_size"] and torch.equal(left.view(torch.int32), edited[-left.shape[0]:].view(torch.int32)), kw
         assert sum(r.shape[0] for r in w.regressed) == keep.sum() == sum(e.shape[0] for e in w.embedded)
         for kind in ("scan", "expr", "pose"):
             rows, r, p = (torch.cat([s[i] for s in w.seen[kind]]) for i in (0, 1, 2))
@@ -367,5 +379,8 @@ def test_the_controls_walk_the_full_rows_and_the_kept_rows_are_those_of_the_call
             for kind in ("scan", "expr", "pose"):
                 assert w.seen[kind][0][0].shape[0] == 2 * N == w.seen[kind][0][2].shape[0]
             assert _same_states(_states(w), states), (world, rank)
+            # (the pass over the gathered rows edits the chunk's full rows, and pred_target_srt is left as that edit)
+            left = torch.cat(w.pred_target_srt, 1)
+            assert left.shape[0] == 2 * N and torch.equal(left[torch.from_numpy(keep)].view(torch.int32), edited.view(torch.int32)), (world, rank)
         assert TC.C.same_bits(np.concatenate([p[0] for p in parts]), pose[keep]), world
         assert TC.C.same_bits(np.concatenate([p[1] for p in parts]), theta[keep]), world

@@ -39,6 +39,19 @@ IDS = [0, 2, 2, 0, 1, 0, 2, 0, 0, 2, 1, 1, 0]
 FACE_COUNTS = [1, 2, 0, 0, 0, 0, 1, 2, 1, 0, 1, 2, 1]
 FACE_IDS = [0, 1, 2, 0, 1, 2, 2, 0, 1, 1, 0]
 RUNS = ((1, "default"), (1, "0"), (2, "default"), (2, "0"))          # (world, EMO_SMOOTH_KEEP_GB)
+# two tracks per frame (boxes [N,2,4], detections= with tracks=2), the rows without a face planted: MISSING[frame] = its tracks without
+# a box, KEPT_COUNTS[frame] = 2 - their number, written out.  In batches of 3 kept rows / 3 frames and chunks of 7 + 6 that leaves the
+# frames 3 ... 5 a batch of their own on one rank and frame 3 one on rank 0 of two, and nobody in rank 1's shard of the second chunk
+# (frames 10 ... 12); tests/test_clip_launch_trace.py asserts it
+MISSING = {0: (1,), 1: (0,), 2: (1,), 3: (0, 1), 4: (0, 1), 5: (0, 1), 8: (0,), 10: (0, 1), 11: (0, 1), 12: (0, 1)}
+KEPT_COUNTS = [1, 1, 1, 0, 0, 0, 2, 2, 1, 2, 0, 0, 0]
+TRACK_IDS = [0, 2] * N                                                # one slot per row: track p of every frame is one identity
+# detections=: which frames each face is seen in and where.  With max_missed=1 A's track (slot 0) dies in frame 3 and B's (slot 1) in
+# frame 4, both in frames nobody is in; C and D are born in frame 6 into the slots they freed and stay to the end (so every stream
+# ends with a state that can be compared), C dropping out in frame 8.  SEEN_COUNTS[frame] = the faces seen in it, written out
+SEEN = dict(A=((0, 1), (1, 1, 8, 8)), B=((2,), (8, 7, 15, 15)), C=((6, 7, 9, 10, 11, 12), (1, 6, 9, 14)),
+            D=((6, 7, 8, 9, 10, 11, 12), (8, 1, 15, 8)))
+SEEN_COUNTS = [1, 1, 1, 0, 0, 0, 2, 2, 1, 2, 2, 2, 2]
 
 
 class _Resident(torch.Tensor):
@@ -75,6 +88,26 @@ def _boxes(n, tracks=None, seed=11):
     return torch.cat([lo, lo + side], dim=-1)
 
 
+def _dropout_boxes():
+    """boxes [N,2,4] of two faces, NaN where MISSING says the track has none"""
+    boxes = _boxes(N, 2)
+    for frame, tracks in MISSING.items():
+        boxes[frame, list(tracks)] = float("nan")
+    return boxes
+
+
+def _detections():
+    """detections [N,4,4] of the faces of SEEN, each drifting a little, in a shuffled order per frame, NaN rows the padding"""
+    g = torch.Generator().manual_seed(17)
+    dets = torch.full((N, 4, 4), float("nan"), dtype=torch.float64)
+    for t in range(N):
+        at = torch.randperm(4, generator=g).tolist()
+        for k, (frames, box) in enumerate(SEEN.values()):
+            if t in frames:
+                dets[t, at[k]] = torch.tensor(box, dtype=torch.float64) + 0.05 * t
+    return dets
+
+
 def _per_row(n, seed):
     g = torch.Generator().manual_seed(seed)
     return torch.rand(n, generator=g) * 2, 0.2 * torch.randn(n, 3, generator=g)
@@ -86,8 +119,9 @@ def _frames_combo(counts=None, **kw):
         clip = _clip(N, HW, 80)
         kw_ = dict(kw)
         frames = clip.as_subclass(_Resident) if kw_.pop("resident", False) else clip
-        if isinstance(kw_.get("boxes"), torch.Tensor):
-            kw_["boxes"] = _chunks(kw_["boxes"])
+        for name in ("boxes", "detections"):
+            if isinstance(kw_.get(name), torch.Tensor):
+                kw_[name] = _chunks(kw_[name])
         return w.animate_frames(_chunks(frames), batch_size=kw_.pop("batch_size", BATCH), to_host=False, **kw_), [clip, clip.clone()]
     return dict(call=call, counts=counts or [1] * N, chunks=CHUNKS, paste=bool(kw.get("paste_back")))
 
@@ -118,6 +152,8 @@ def _combos():
     per_id = dict(smooth_pose=True, smooth_per_identity=True)
     faces7 = dict(faces=_faces(), identities=FACE_IDS, head_pose=dict(relative=True), expression=dict(relative=True), mix=True, **per_id)
     f32 = dict(as_uint8=False)
+    over2 = torch.randn(2 * N, E, generator=torch.Generator().manual_seed(83))
+    tracked = dict(identities=TRACK_IDS, expression=dict(relative=True, smooth=True), head_pose=dict(relative=True), **per_id)
     return {
         "1 identities, head_pose relative per row, expression relative smooth gain, smooth_pose, mix": _frames_combo(
             identities=IDS, head_pose=dict(relative=True, gain=gain, rotation_offset=rot),
@@ -140,6 +176,16 @@ def _combos():
         "12 animate, head_pose, expression, smooth_pose": _animate_combo(
             head_pose=dict(relative=True, gain=gain), expression=dict(relative=True, smooth=True), smooth_pose=True),
         "13 animate_streams, two frame sizes, boxes, smooth_pose, per-stream head_pose": _streams_combo(),
+        "14 boxes [N,2,4] with dropouts, follow_tracks, head_pose relative, expression relative smooth, smooth_pose": _frames_combo(
+            [2] * N, boxes=_dropout_boxes(), tracking=dict(follow_tracks=True, smooth=True), **tracked, **f32),
+        "15 as 14, skip_absent": _frames_combo(
+            KEPT_COUNTS, boxes=_dropout_boxes(), tracking=dict(follow_tracks=True, smooth=True, skip_absent=True), **tracked),
+        "16 detections [N,4,4] shuffled, tracks=2 max_missed=1, follow_tracks, skip_absent, controls as 14, paste_back": _frames_combo(
+            SEEN_COUNTS, detections=_detections(), tracking=dict(tracks=2, follow_tracks=True, skip_absent=True, max_missed=1),
+            paste_back=True, **tracked),
+        "17 as 15, expression override over the full rows, mix": _frames_combo(
+            KEPT_COUNTS, boxes=_dropout_boxes(), tracking=dict(follow_tracks=True, smooth=True, skip_absent=True), mix=True,
+            **dict(tracked, expression=dict(relative=True, smooth=True, override=over2))),
     }
 
 
@@ -159,6 +205,18 @@ def expected_rows(combo, world, rank):
     return rows
 
 
+class _Builds:
+    """the association and the compaction (a wave exchange, a block barrier) from the threaded host build, every other entry point from
+    the loop build, which runs the crops and the pastes of whole frames in reasonable time"""
+    THREADED = ("emo_track_assign_f64", "emo_present_rows_i32")
+
+    def __init__(self, loop, threads):
+        self._loop, self._threads = loop, threads
+
+    def __getattr__(self, name):
+        return getattr(self._threads if name in self.THREADED else self._loop, name)
+
+
 def _rig(patch, rank, world):
     """the wrapper of one combination: a filled 3-slot bank and a current identity, the stand-ins writing their events into
     w.lib.order between the C entries"""
@@ -166,7 +224,7 @@ def _rig(patch, rank, world):
     import emulibs
     from counting_lib import CountingLib
     from emoportraits_amd import ops, parallel
-    lib = CountingLib(emulibs.stream(False))
+    lib = CountingLib(_Builds(emulibs.stream(False), emulibs.stream(True)))
     events = lib.order
     bare_wrapper.host_uploads(patch, lambda n: events.append(("upload", n)))
     w = bare_wrapper.bare_wrapper(patch, lib, K, lpe_output_channels_expression=E)
@@ -257,7 +315,7 @@ def _free_port():
 def run_all():
     """every combination at every (world, budget) of RUNS, each rank a spawned process -> {(world, budget, rank): {combo: run_combo's}}"""
     import emulibs
-    emulibs.stream(False)                                                        # (built once, before the children load it)
+    emulibs.stream(False), emulibs.stream(True)                                  # (built once, before the children load them)
     ctx = mp.get_context("spawn")
     q, procs, before = ctx.Queue(), [], os.environ.get("EMO_SMOOTH_KEEP_GB")
     try:
