@@ -18,6 +18,7 @@
 // The analytic variant (theta != NULL) fuses the head-pose affine of the identity lattice into the sampler
 // (row a2: notebooks/infer.py:441-444, :583-588), removing the 0.79 MB grid tensor from HBM.
 #include "gs3d_coord.h"
+#include "gs3d_launch_form.h"
 
 #define EMO_GS3D_TILE_FLAG (1 << 30)   /* variant bit: NCDHW -> NCDHW through the LDS-staged planar kernel (gs3d_tile.h) */
 
@@ -450,79 +451,94 @@ struct Bank {
   int num;
 };
 
-template <int PAD, int MODE, int ORDER, bool FMA = false>
-int launch_cl_v2(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
-                 const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-                 long vol_bstride, bool out_cl, hipStream_t s, int nt_out, Bank bank) {
+// ------------------------------------------------------------------------------------------------------
+// The launch decision of the direct kernels (ABI 29), made HERE and nowhere else: `launch` calls it and launches what it says,
+// emo_grid_sample3d_launch_form reports it.  No HIP call.
+//
+// NCDHW -> NCDHW: the planar gather, variant = channels per block (0: 8), clipped to C.
+// NDHWC -> NDHWC / NCDHW, variant word (bits): 1 = 4 x 4 x 4 output bricks per block instead of 64-voxel rows (NDHWC output,
+// Do / Ho / Wo multiples of 4; otherwise the bit is ignored): half the L1 fills per voxel, the uv call alone 11.7 instead of
+// 12.3 us per frame -- but the rotation call that reads its output back is then 0.6-0.8 us slower (its blocks walk the volume in
+// row order), so the pair is 1.3 us per frame slower: opt-in.  The brick kernel has no FMA form: bit 1 wins over bit 4.
+// 2 = non-temporal stores of an NCDHW output (the driver pass's rotation call); ignored for an NDHWC output.
+// 4 = fused multiply-add accumulation (gather_quad<true>: taps bit-identical, values within 8 * 2^-24 * max|v w| of ATen).
+// Default: 64-voxel rows, XCD-contiguous (ORDER 1), and for a volume shared by N >= 8 samples (no bank) row-group-major over the
+// XCD's samples (ORDER 3) where the work divides into whole slices and groups: N % 8 == 0, nvox % 64 == 0, bps % Do == 0 and
+// (bps / Do) % 8 == 0 -- otherwise ORDER 1.  (archive/profiles/r3_sampler_nt_stores_ab.jsonl, r3_sampler_nt_out_ab.jsonl)
+// ------------------------------------------------------------------------------------------------------
+gs3d::LaunchForm direct_form(int N, int C, int D, int H, int W, int Do, int Ho, int Wo, long vol_bstride, int in_layout,
+                             int out_layout, int variant, bool banked) {
+  gs3d::LaunchForm f = {};
+  auto refuse = [&f](int rc) { f = gs3d::LaunchForm{}; f.rc = rc; return f; };
   const int nvox = Do * Ho * Wo;
-  const int bps = emo_cdiv(nvox, CL_VPB);
-  const long total = (long)bps * N;
-  if (total > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
-  if (ORDER == 3 && ((N & 7) || (bps % Do) || (nvox % CL_VPB) || ((bps / Do) % 8)))   // whole slices / groups, N % 8 == 0
-    return launch_cl_v2<PAD, MODE, 1, FMA>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                           out_cl, s, nt_out, bank);
-  const size_t lds = CL_VPB * sizeof(TapRec) + (size_t)C * (CL_VPB + 1) * sizeof(float);
-  if (!out_cl && lds > 64 * 1024) return EMO_ERR_UNSUPPORTED;
-  if constexpr (ORDER == 1) {     // (a bank never gets ORDER 3, which is for one shared volume: dispatch_cl_v2)
-    if (bank.index) {
-      if (out_cl)
-        hipLaunchKernelGGL((gs3d_cl_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA, const int*, int>), dim3((unsigned)total), dim3(256), 0, s, vol, grid,
-                           theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, bank.index, bank.num);
-      else
-        hipLaunchKernelGGL((gs3d_cl2ncdhw_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA, const int*, int>), dim3((unsigned)total), dim3(256), lds, s,
-                           vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, nt_out, bank.index,
-                           bank.num);
-      return emo_launch_status();
+  f.bank = banked;
+  f.gy = f.gz = 1;
+  if (in_layout == EMO_LAYOUT_NCDHW && out_layout == EMO_LAYOUT_NCDHW) {
+    int cpb = variant > 0 ? variant : 8;
+    if (cpb > C) cpb = C;
+    f.form = EMO_GS3D_FORM_PLANAR;
+    f.cpb = cpb;
+    f.bps = emo_cdiv(nvox, 256);
+    f.gx = f.bps; f.gy = emo_cdiv(C, cpb); f.gz = N;
+    f.last_vox = nvox - (int)(f.bps - 1) * 256;
+    return f;
+  }
+  if (in_layout != EMO_LAYOUT_NDHWC || (out_layout != EMO_LAYOUT_NDHWC && out_layout != EMO_LAYOUT_NCDHW))
+    return refuse(EMO_ERR_UNSUPPORTED);
+  if (C % 4) return refuse(EMO_ERR_UNSUPPORTED);
+  if ((long)D * H * W * C * 4 >= (1L << 32)) return refuse(EMO_ERR_UNSUPPORTED);   // 32-bit byte offsets
+  if (variant < 0 || variant > 7) return refuse(EMO_ERR_BAD_ARG);
+  const bool out_cl = out_layout == EMO_LAYOUT_NDHWC;
+  f.cpb = C;
+  f.order = 1;
+  if ((variant & 1) && out_cl && !(Do & 3) && !(Ho & 3) && !(Wo & 3)) {
+    f.form = EMO_GS3D_FORM_BRICK;
+    f.bps = nvox >> 6;
+    f.last_vox = 64;
+  } else {
+    f.form = out_cl ? EMO_GS3D_FORM_ROWS : EMO_GS3D_FORM_ROWS_NCDHW;
+    f.fma = (variant & 4) != 0;
+    f.nt = (variant & 2) && !out_cl;
+    f.bps = emo_cdiv(nvox, CL_VPB);
+    f.last_vox = nvox - (int)(f.bps - 1) * CL_VPB;
+    const bool shared = vol_bstride == 0 && !banked;
+    if (shared && N >= 8 && !(N & 7) && !(nvox % CL_VPB) && !(f.bps % Do) && !((f.bps / Do) % 8)) f.order = 3;
+    if (!out_cl) {
+      f.lds = CL_VPB * sizeof(TapRec) + (size_t)C * (CL_VPB + 1) * sizeof(float);
+      if (f.lds > 64 * 1024) return refuse(EMO_ERR_UNSUPPORTED);
     }
   }
-  if (out_cl) {
-    hipLaunchKernelGGL((gs3d_cl_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA>), dim3((unsigned)total), dim3(256), 0, s, vol, grid,
-                       theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps);
-  } else {
-    hipLaunchKernelGGL((gs3d_cl2ncdhw_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA>), dim3((unsigned)total), dim3(256), lds, s, vol,
-                       grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, nt_out);
-  }
-  return emo_launch_status();
+  if (f.bps * N > 0x7fffffffL) return refuse(EMO_ERR_UNSUPPORTED);
+  f.gx = f.bps * N;
+  return f;
 }
 
-// variant word of the channels-last kernels (bits): 1 = 4 x 4 x 4 output bricks per block instead of 64-voxel rows (NDHWC output,
-// Do / Ho / Wo multiples of 4): half the L1 fills per voxel, the uv call alone 11.7 instead of 12.3 us per frame -- but the
-// rotation call that reads its output back is then 0.6-0.8 us slower (its blocks walk the volume in row order), so the pair
-// is 1.3 us per frame slower: opt-in.  2 = non-temporal stores of an NCDHW output (the driver pass's rotation call).
-// 4 = fused multiply-add accumulation (gather_quad<true>: taps bit-identical, values within 8 * 2^-24 * max|v w| of ATen).
-// Default: 64-voxel rows, XCD-contiguous, and for a volume shared by N % 8 == 0 samples also row-group-major over the XCD's
-// samples.  (archive/profiles/r3_sampler_nt_stores_ab.jsonl, r3_sampler_nt_out_ab.jsonl)
-template <int PAD, int MODE>
-int dispatch_cl_v2(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
-                   const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-                   long vol_bstride, bool out_cl, int variant, hipStream_t s, Bank bank) {
-  if (variant < 0 || variant > 7) return EMO_ERR_BAD_ARG;
-  const int nt_out = (variant & 2) && !out_cl;
-  const bool shared = vol_bstride == 0 && !bank.index;
-  if ((variant & 1) && out_cl && !(Do & 3) && !(Ho & 3) && !(Wo & 3)) {
-    const int bps = (Do * Ho * Wo) >> 6;
-    const long total = (long)bps * N;
-    if (total > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
-    if (bank.index)
-      hipLaunchKernelGGL((gs3d_cl_brick_kernel<PAD, MODE, 1, const int*, int>), dim3((unsigned)total), dim3(256), 0, s, vol, grid, theta, lin_x,
-                         lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, bank.index, bank.num);
-    else
-      hipLaunchKernelGGL((gs3d_cl_brick_kernel<PAD, MODE, 1>), dim3((unsigned)total), dim3(256), 0, s, vol, grid, theta, lin_x,
-                         lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps);
-    return emo_launch_status();
+// the row-shaped channels-last kernels in the block order and accumulation `f` names (a bank never gets ORDER 3: direct_form)
+template <int PAD, int MODE, int ORDER, bool FMA>
+void run_rows(const gs3d::LaunchForm& f, const float* vol, const float* grid, const float* theta, const float* lin_x,
+              const float* lin_y, const float* lin_z, float* out, int C, int D, int H, int W, int Do, int Ho, int Wo,
+              long vol_bstride, hipStream_t s, Bank bank) {
+  const bool out_cl = f.form == EMO_GS3D_FORM_ROWS;
+  const dim3 g((unsigned)f.gx);
+  const int bps = (int)f.bps;
+  if constexpr (ORDER == 1) {
+    if (bank.index) {
+      if (out_cl)
+        hipLaunchKernelGGL((gs3d_cl_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA, const int*, int>), g, dim3(256), 0, s, vol, grid,
+                           theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, bank.index, bank.num);
+      else
+        hipLaunchKernelGGL((gs3d_cl2ncdhw_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA, const int*, int>), g, dim3(256), f.lds, s,
+                           vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, f.nt, bank.index,
+                           bank.num);
+      return;
+    }
   }
-  if (variant & 4) {      // fused multiply-add accumulation (gather_quad<true>): row kernels only
-    if (shared && N >= 8)
-      return launch_cl_v2<PAD, MODE, 3, true>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                              out_cl, s, nt_out, bank);
-    return launch_cl_v2<PAD, MODE, 1, true>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                            out_cl, s, nt_out, bank);
-  }
-  if (shared && N >= 8)
-    return launch_cl_v2<PAD, MODE, 3>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                      out_cl, s, nt_out, bank);
-  return launch_cl_v2<PAD, MODE, 1>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                    out_cl, s, nt_out, bank);
+  if (out_cl)
+    hipLaunchKernelGGL((gs3d_cl_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA>), g, dim3(256), 0, s, vol, grid, theta, lin_x, lin_y,
+                       lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps);
+  else
+    hipLaunchKernelGGL((gs3d_cl2ncdhw_v2_kernel<PAD, MODE, CL_VPB, ORDER, FMA>), g, dim3(256), f.lds, s, vol, grid, theta, lin_x,
+                       lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, bps, f.nt);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -557,29 +573,34 @@ __global__ __launch_bounds__(256) void repack_kernel(const float* __restrict__ i
   }
 }
 
+// executes a form direct_form decided (f.rc == EMO_OK)
 template <int PAD, int MODE>
-int launch(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
-           const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-           long vol_bstride, int in_layout, int out_layout, int variant, hipStream_t s, Bank bank) {
-  const int nvox = Do * Ho * Wo;
-  if (in_layout == EMO_LAYOUT_NCDHW && out_layout == EMO_LAYOUT_NCDHW) {
-    int cpb = variant > 0 ? variant : 8;
-    if (cpb > C) cpb = C;
-    dim3 g(emo_cdiv(nvox, 256), emo_cdiv(C, cpb), N);
+int launch(const gs3d::LaunchForm& f, const float* vol, const float* grid, const float* theta, const float* lin_x,
+           const float* lin_y, const float* lin_z, float* out, int C, int D, int H, int W, int Do, int Ho, int Wo,
+           long vol_bstride, hipStream_t s, Bank bank) {
+#define EMO_GS3D_ROWS(ORDER, FMA) \
+  run_rows<PAD, MODE, ORDER, FMA>(f, vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, s, bank)
+  if (f.form == EMO_GS3D_FORM_PLANAR) {
+    const dim3 g((unsigned)f.gx, f.gy, f.gz);
     if (bank.index)
       hipLaunchKernelGGL((gs3d_ncdhw_kernel<PAD, MODE, const int*, int>), g, dim3(256), 0, s, vol, grid, theta, lin_x, lin_y, lin_z,
-                         out, C, D, H, W, Do, Ho, Wo, vol_bstride, cpb, bank.index, bank.num);
+                         out, C, D, H, W, Do, Ho, Wo, vol_bstride, f.cpb, bank.index, bank.num);
     else
       hipLaunchKernelGGL((gs3d_ncdhw_kernel<PAD, MODE>), g, dim3(256), 0, s, vol, grid, theta, lin_x, lin_y, lin_z,
-                         out, C, D, H, W, Do, Ho, Wo, vol_bstride, cpb);
-  } else if (in_layout == EMO_LAYOUT_NDHWC && (out_layout == EMO_LAYOUT_NDHWC || out_layout == EMO_LAYOUT_NCDHW)) {
-    if (C % 4) return EMO_ERR_UNSUPPORTED;
-    if ((long)D * H * W * C * 4 >= (1L << 32)) return EMO_ERR_UNSUPPORTED;   // 32-bit byte offsets
-    return dispatch_cl_v2<PAD, MODE>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                     out_layout == EMO_LAYOUT_NDHWC, variant, s, bank);
+                         out, C, D, H, W, Do, Ho, Wo, vol_bstride, f.cpb);
+  } else if (f.form == EMO_GS3D_FORM_BRICK) {
+    if (bank.index)
+      hipLaunchKernelGGL((gs3d_cl_brick_kernel<PAD, MODE, 1, const int*, int>), dim3((unsigned)f.gx), dim3(256), 0, s, vol, grid, theta,
+                         lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, (int)f.bps, bank.index, bank.num);
+    else
+      hipLaunchKernelGGL((gs3d_cl_brick_kernel<PAD, MODE, 1>), dim3((unsigned)f.gx), dim3(256), 0, s, vol, grid, theta, lin_x,
+                         lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, (int)f.bps);
+  } else if (f.order == 3) {
+    if (f.fma) EMO_GS3D_ROWS(3, true); else EMO_GS3D_ROWS(3, false);
   } else {
-    return EMO_ERR_UNSUPPORTED;
+    if (f.fma) EMO_GS3D_ROWS(1, true); else EMO_GS3D_ROWS(1, false);
   }
+#undef EMO_GS3D_ROWS
   return emo_launch_status();
 }
 
@@ -605,17 +626,14 @@ __global__ __launch_bounds__(256) void affine_grid3d_kernel(const float* __restr
 }
 
 template <int PAD>
-int launch_pad(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
-               const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-               long vol_bstride, int in_layout, int out_layout, int variant, int grid_kind, hipStream_t s, Bank bank) {
+int launch_pad(const gs3d::LaunchForm& f, const float* vol, const float* grid, const float* theta, const float* lin_x,
+               const float* lin_y, const float* lin_z, float* out, int C, int D, int H, int W, int Do, int Ho, int Wo,
+               long vol_bstride, int grid_kind, hipStream_t s, Bank bank) {
   if (theta)
-    return launch<PAD, MODE_THETA>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                   in_layout, out_layout, variant, s, bank);
+    return launch<PAD, MODE_THETA>(f, vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, s, bank);
   if (grid_kind == 1)
-    return launch<PAD, MODE_DELTA>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                   in_layout, out_layout, variant, s, bank);
-  return launch<PAD, MODE_GRID>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_bstride,
-                                in_layout, out_layout, variant, s, bank);
+    return launch<PAD, MODE_DELTA>(f, vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, s, bank);
+  return launch<PAD, MODE_GRID>(f, vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_bstride, s, bank);
 }
 
 }  // namespace
@@ -625,8 +643,47 @@ int emo_gs3d_tile_dispatch(const float* vol, const float* grid, const float* the
                            int64_t vol_batch_stride, int padding_mode, int in_layout, int out_layout, int variant,
                            int grid_kind, void* stream);
 int emo_repack_p4_dispatch(const float* in, float* out, int N, int C, int DHW, int to_p4, void* stream);
+// The decisions the launchers behind the two dispatchers make for these arguments (gs3d_tile_api.hip; tile_form of
+// gs3d_tile_launch.h), nothing launched.  Weak references: a build of this file alone whose dispatchers are stubs that refuse
+// (the host-compiled test library) need not define them -- absent, the answer is the stubs': EMO_ERR_UNSUPPORTED.
+__attribute__((weak)) int emo_gs3d_tile_form(int N, int C, int D, int H, int W, int Do, int Ho, int Wo, int in_layout,
+                                             int out_layout, int variant, gs3d::LaunchForm* form);
+__attribute__((weak)) int emo_repack_p4_form(int N, int C, int DHW, long* blocks);
 
 namespace {
+
+// What a sampler call does before any launch, from the argument checks to the kernel and its plan: sample3d calls it and launches
+// what it says, emo_grid_sample3d_launch_form reports it.  kind: EMO_GS3D_KIND_* (grid, delta, theta).  *tile: the LDS-staged
+// kernels take the call (emo_gs3d_tile_dispatch), else the direct kernels of this file.
+gs3d::LaunchForm sampler_form(const void* vol, const void* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
+                              int64_t vol_batch_stride, int padding_mode, int in_layout, int out_layout, int variant, int kind,
+                              bool banked, bool* tile) {
+  gs3d::LaunchForm f = {};
+  *tile = false;
+  auto refuse = [&f](int rc) { f = gs3d::LaunchForm{}; f.rc = rc; return f; };
+  if (!vol || !out) return refuse(EMO_ERR_BAD_ARG);
+  if (kind != EMO_GS3D_KIND_GRID && kind != EMO_GS3D_KIND_DELTA && kind != EMO_GS3D_KIND_THETA) return refuse(EMO_ERR_BAD_ARG);
+  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0) return refuse(EMO_ERR_BAD_ARG);
+  if (vol_batch_stride < 0) return refuse(EMO_ERR_BAD_ARG);
+  if (N > 65535) return refuse(EMO_ERR_UNSUPPORTED);
+  if ((long)D * H * W >= (1L << 31) / 4 || (long)Do * Ho * Wo >= (1L << 31) / 4) return refuse(EMO_ERR_UNSUPPORTED);
+  if (!emo_aligned16(vol) || !emo_aligned16(out)) return refuse(EMO_ERR_ALIGN);
+  if (banked && (in_layout == EMO_LAYOUT_P4 || (variant & EMO_GS3D_TILE_FLAG))) return refuse(EMO_ERR_UNSUPPORTED);
+  if (padding_mode != EMO_PAD_ZEROS && padding_mode != EMO_PAD_BORDER && padding_mode != EMO_PAD_REFLECTION)
+    return refuse(EMO_ERR_BAD_ARG);
+  const bool planar = in_layout == EMO_LAYOUT_NCDHW && out_layout == EMO_LAYOUT_NCDHW;
+  if (in_layout == EMO_LAYOUT_P4 || (planar && (variant & EMO_GS3D_TILE_FLAG))) {
+    if (emo_gs3d_tile_form) emo_gs3d_tile_form(N, C, D, H, W, Do, Ho, Wo, in_layout, out_layout, variant & ~EMO_GS3D_TILE_FLAG, &f);
+    else f.rc = EMO_ERR_UNSUPPORTED;
+    // LDS-staged planar kernel; shapes it does not take (W % 4, huge extents) fall through to the direct-gather kernel
+    if (in_layout == EMO_LAYOUT_P4 || f.rc != EMO_ERR_UNSUPPORTED) {
+      *tile = f.rc == EMO_OK;
+      return f.rc == EMO_OK ? f : refuse(f.rc);
+    }
+    variant = 0;
+  }
+  return direct_form(N, C, D, H, W, Do, Ho, Wo, (long)vol_batch_stride, in_layout, out_layout, variant, banked);
+}
 
 int sample3d(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y, const float* lin_z,
              float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo, int64_t vol_batch_stride, int padding_mode,
@@ -635,39 +692,83 @@ int sample3d(const float* vol, const float* grid, const float* theta, const floa
   if (grid_kind != 0 && grid_kind != 1) return EMO_ERR_BAD_ARG;
   if ((theta || grid_kind == 1) && (!lin_x || !lin_y || !lin_z)) return EMO_ERR_BAD_ARG;
   if (theta && grid_kind == 1) return EMO_ERR_BAD_ARG;
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0) return EMO_ERR_BAD_ARG;
-  if (vol_batch_stride < 0) return EMO_ERR_BAD_ARG;
-  if (N > 65535) return EMO_ERR_UNSUPPORTED;
-  if ((long)D * H * W >= (1L << 31) / 4 || (long)Do * Ho * Wo >= (1L << 31) / 4) return EMO_ERR_UNSUPPORTED;
-  if (!emo_aligned16(vol) || !emo_aligned16(out)) return EMO_ERR_ALIGN;
-  if (bank.index && (in_layout == EMO_LAYOUT_P4 || (variant & EMO_GS3D_TILE_FLAG))) return EMO_ERR_UNSUPPORTED;
-  if (in_layout == EMO_LAYOUT_P4)
+  bool tile;
+  const gs3d::LaunchForm f = sampler_form(vol, out, N, C, D, H, W, Do, Ho, Wo, vol_batch_stride, padding_mode, in_layout, out_layout,
+                                          variant, theta ? EMO_GS3D_KIND_THETA : grid_kind, bank.index != nullptr, &tile);
+  if (f.rc != EMO_OK) return f.rc;
+  if (tile)
     return emo_gs3d_tile_dispatch(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_batch_stride,
                                   padding_mode, in_layout, out_layout, variant & ~EMO_GS3D_TILE_FLAG, grid_kind, stream);
-  if (in_layout == EMO_LAYOUT_NCDHW && out_layout == EMO_LAYOUT_NCDHW && (variant & EMO_GS3D_TILE_FLAG)) {
-    // LDS-staged planar kernel; shapes it does not take (W % 4, huge extents) fall through to the direct-gather kernel
-    const int rc = emo_gs3d_tile_dispatch(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo, vol_batch_stride,
-                                          padding_mode, in_layout, out_layout, variant & ~EMO_GS3D_TILE_FLAG, grid_kind, stream);
-    if (rc != EMO_ERR_UNSUPPORTED) return rc;
-    variant = 0;
-  }
   hipStream_t s = (hipStream_t)stream;
   switch (padding_mode) {
     case EMO_PAD_ZEROS:
-      return launch_pad<EMO_PAD_ZEROS>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo,
-                                       vol_batch_stride, in_layout, out_layout, variant, grid_kind, s, bank);
+      return launch_pad<EMO_PAD_ZEROS>(f, vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_batch_stride,
+                                       grid_kind, s, bank);
     case EMO_PAD_BORDER:
-      return launch_pad<EMO_PAD_BORDER>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo,
-                                        vol_batch_stride, in_layout, out_layout, variant, grid_kind, s, bank);
-    case EMO_PAD_REFLECTION:
-      return launch_pad<EMO_PAD_REFLECTION>(vol, grid, theta, lin_x, lin_y, lin_z, out, N, C, D, H, W, Do, Ho, Wo,
-                                            vol_batch_stride, in_layout, out_layout, variant, grid_kind, s, bank);
+      return launch_pad<EMO_PAD_BORDER>(f, vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo, vol_batch_stride,
+                                        grid_kind, s, bank);
     default:
-      return EMO_ERR_BAD_ARG;
+      return launch_pad<EMO_PAD_REFLECTION>(f, vol, grid, theta, lin_x, lin_y, lin_z, out, C, D, H, W, Do, Ho, Wo,
+                                            vol_batch_stride, grid_kind, s, bank);
   }
 }
 
+// The launch decision of the two repack entries: `dir` is an EMO_REPACK_*; grid (g[0], g[1], g[2]).  No HIP call.
+int repack_form(const void* in, const void* out, int N, int C, int DHW, int to_channels_last, bool indexed, int* dir, long* g) {
+  *dir = 0; g[0] = g[1] = g[2] = 0;
+  if (!in || !out || N <= 0 || C <= 0 || DHW <= 0) return EMO_ERR_BAD_ARG;
+  if (N > 65535) return EMO_ERR_UNSUPPORTED;
+  if (!indexed && (to_channels_last == 4 || to_channels_last == 5)) {     // NCDHW <-> packed-4
+    const int rc = emo_repack_p4_form ? emo_repack_p4_form(N, C, DHW, &g[0]) : EMO_ERR_UNSUPPORTED;
+    if (rc != EMO_OK) { g[0] = 0; return rc; }
+    *dir = to_channels_last == 4 ? EMO_REPACK_TO_P4 : EMO_REPACK_FROM_P4;
+    g[1] = N; g[2] = 1;
+    return EMO_OK;
+  }
+  if (indexed ? to_channels_last != 1 : (to_channels_last != 0 && to_channels_last != 1)) return EMO_ERR_BAD_ARG;
+  const int R = to_channels_last ? C : DHW;       // rows of the input matrix
+  const int Ccols = to_channels_last ? DHW : C;   // columns of the input matrix
+  if (emo_cdiv(R, 64) > 65535) return EMO_ERR_UNSUPPORTED;     // grid y
+  *dir = indexed ? EMO_REPACK_TO_CHANNELS_LAST_INDEXED : to_channels_last ? EMO_REPACK_TO_CHANNELS_LAST : EMO_REPACK_FROM_CHANNELS_LAST;
+  g[0] = emo_cdiv(Ccols, 64); g[1] = emo_cdiv(R, 64); g[2] = N;
+  return EMO_OK;
+}
+
 }  // namespace
+
+// ABI 29 (definition: include/emo_hip.h): the kernel and plan a sampler call with these arguments takes; nothing is launched
+extern "C" int emo_grid_sample3d_launch_form(const void* vol, const void* out, int banked, int N, int C, int D, int H, int W,
+                                             int Do, int Ho, int Wo, int64_t vol_batch_stride, int padding_mode, int in_layout,
+                                             int out_layout, int variant, int grid_kind, int64_t* plan) {
+  if (!plan) return EMO_ERR_BAD_ARG;
+  for (int i = 0; i < EMO_GS3D_PLAN_COUNT; ++i) plan[i] = 0;
+  bool tile;
+  if (banked) vol_batch_stride = (int64_t)C * D * H * W;     // (as emo_grid_sample3d_indexed_f32 passes it)
+  const gs3d::LaunchForm f = sampler_form(vol, out, N, C, D, H, W, Do, Ho, Wo, vol_batch_stride, padding_mode, in_layout, out_layout,
+                                          variant, grid_kind, banked != 0, &tile);
+  if (f.rc != EMO_OK) return f.rc;
+  plan[EMO_GS3D_PLAN_FORM] = f.form; plan[EMO_GS3D_PLAN_ORDER] = f.order; plan[EMO_GS3D_PLAN_FMA] = f.fma;
+  plan[EMO_GS3D_PLAN_NT] = f.nt; plan[EMO_GS3D_PLAN_BANK] = f.bank;
+  plan[EMO_GS3D_PLAN_GRID_X] = f.gx; plan[EMO_GS3D_PLAN_GRID_Y] = f.gy; plan[EMO_GS3D_PLAN_GRID_Z] = f.gz;
+  plan[EMO_GS3D_PLAN_BPS] = f.bps; plan[EMO_GS3D_PLAN_LAST_VOX] = f.last_vox; plan[EMO_GS3D_PLAN_CPB] = f.cpb;
+  plan[EMO_GS3D_PLAN_LDS] = (int64_t)f.lds; plan[EMO_GS3D_PLAN_THREADS] = f.threads; plan[EMO_GS3D_PLAN_VPT] = f.vpt;
+  plan[EMO_GS3D_PLAN_UPB] = f.upb; plan[EMO_GS3D_PLAN_TXS] = f.txs; plan[EMO_GS3D_PLAN_TYS] = f.tys;
+  plan[EMO_GS3D_PLAN_TZS] = f.tzs; plan[EMO_GS3D_PLAN_STAGE_SLOTS] = f.cap_slots;
+  return EMO_OK;
+}
+
+// ABI 29: the direction and grid of emo_volume_repack_f32 (indexed = 0) / emo_volume_repack_indexed_f32 (indexed != 0, with
+// to_channels_last = 1); nothing is launched
+extern "C" int emo_volume_repack_launch_form(const void* in, const void* out, int N, int C, int DHW, int to_channels_last,
+                                             int indexed, int64_t* plan) {
+  if (!plan) return EMO_ERR_BAD_ARG;
+  int dir;
+  long g[3];
+  const int rc = repack_form(in, out, N, C, DHW, to_channels_last, indexed != 0, &dir, g);
+  plan[EMO_REPACK_PLAN_DIRECTION] = rc == EMO_OK ? dir : 0;
+  plan[EMO_REPACK_PLAN_GRID_X] = g[0]; plan[EMO_REPACK_PLAN_GRID_Y] = g[1]; plan[EMO_REPACK_PLAN_GRID_Z] = g[2];
+  return rc;
+}
 
 extern "C" int emo_grid_sample3d_f32(const float* vol, const float* grid, const float* theta, const float* lin_x,
                                      const float* lin_y, const float* lin_z, float* out, int N, int C, int D, int H,
@@ -702,27 +803,27 @@ extern "C" int emo_affine_grid3d_f32(const float* theta, const float* lin_x, con
 
 extern "C" int emo_volume_repack_f32(const float* in, float* out, int N, int C, int DHW, int to_channels_last,
                                      void* stream) {
-  if (!in || !out || N <= 0 || C <= 0 || DHW <= 0) return EMO_ERR_BAD_ARG;
-  if (N > 65535) return EMO_ERR_UNSUPPORTED;
-  if (to_channels_last == 4 || to_channels_last == 5)     // NCDHW <-> packed-4
-    return emo_repack_p4_dispatch(in, out, N, C, DHW, to_channels_last == 4, stream);
-  if (to_channels_last != 0 && to_channels_last != 1) return EMO_ERR_BAD_ARG;
+  int dir;
+  long g[3];
+  const int rc = repack_form(in, out, N, C, DHW, to_channels_last, false, &dir, g);
+  if (rc != EMO_OK) return rc;
+  if (dir == EMO_REPACK_TO_P4 || dir == EMO_REPACK_FROM_P4)
+    return emo_repack_p4_dispatch(in, out, N, C, DHW, dir == EMO_REPACK_TO_P4, stream);
   const int R = to_channels_last ? C : DHW;       // rows of the input matrix
   const int Ccols = to_channels_last ? DHW : C;   // columns of the input matrix
-  dim3 g(emo_cdiv(Ccols, 64), emo_cdiv(R, 64), N);
-  if (g.y > 65535) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(repack_kernel<>, g, dim3(256), 0, (hipStream_t)stream, in, out, R, Ccols);
+  hipLaunchKernelGGL(repack_kernel<>, dim3(g[0], g[1], g[2]), dim3(256), 0, (hipStream_t)stream, in, out, R, Ccols);
   return emo_launch_status();
 }
 
 // emo_volume_repack_f32(to_channels_last = 1) of N volumes into rows row[n] of a channels-last bank of num_rows volumes
 extern "C" int emo_volume_repack_indexed_f32(const float* in, float* bank, const int32_t* row, int N, int C, int DHW,
                                              int num_rows, void* stream) {
-  if (!in || !bank || !row || N <= 0 || C <= 0 || DHW <= 0 || num_rows <= 0) return EMO_ERR_BAD_ARG;
-  if (N > 65535) return EMO_ERR_UNSUPPORTED;
-  dim3 g(emo_cdiv(DHW, 64), emo_cdiv(C, 64), N);
-  if (g.y > 65535) return EMO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((repack_kernel<const int*, int>), g, dim3(256), 0, (hipStream_t)stream, in, bank, C, DHW, (const int*)row,
-                     num_rows);
+  if (!row || num_rows <= 0) return EMO_ERR_BAD_ARG;
+  int dir;
+  long g[3];
+  const int rc = repack_form(in, bank, N, C, DHW, 1, true, &dir, g);
+  if (rc != EMO_OK) return rc;
+  hipLaunchKernelGGL((repack_kernel<const int*, int>), dim3(g[0], g[1], g[2]), dim3(256), 0, (hipStream_t)stream, in, bank, C, DHW,
+                     (const int*)row, num_rows);
   return emo_launch_status();
 }

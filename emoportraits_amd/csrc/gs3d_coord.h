@@ -62,8 +62,13 @@ GS_FN float source_index(float g, int size) {
     const float span = (float)size;
     float in = fabsf(gs_fsub(c, mn));
     float extra = fmodf(in, span);
-    int flips = (int)floorf(gs_fdiv(in, span));
-    c = (flips % 2 == 0) ? gs_fadd(extra, mn) : gs_fadd(gs_fsub(span, extra), mn);
+    // ATen: int flips = (int)floor(in / span); flips % 2.  The parity is decided on the float quotient, not on a conversion
+    // that may be out of range: every float >= 2^24 is an even integer, and that is also what ATen's x86 build gets beyond
+    // 2^31 (cvttss2si yields INT_MIN, even) -- whereas v_cvt_i32_f32 saturates to INT_MAX, odd, and would mirror the sample
+    // for |g| >= 2^32.  Below 2^24 the conversion is exact; a NaN quotient converts to 0 here and to INT_MIN there: even.
+    const float quot = floorf(gs_fdiv(in, span));
+    const bool even = (quot >= 16777216.0f) || ((int)quot % 2 == 0);
+    c = even ? gs_fadd(extra, mn) : gs_fadd(gs_fsub(span, extra), mn);
     const float lim = (float)(size - 1);
     c = (c < 0.0f) ? 0.0f : c;
     c = (c < lim) ? c : lim;
@@ -116,8 +121,11 @@ GS_FN void load_coord(const float* __restrict__ grid, const float* __restrict__ 
   load_coord_xyz<MODE>(grid, theta, lin_x, lin_y, lin_z, n, x, y, z, vox, nvox, gx, gy, gz);
 }
 
-// Floor corner (x0, y0, z0) and the 8 corner weights of one sample point.  Non-finite / absurdly large coordinates are
-// mapped to a point far outside the volume: every corner out of range (ATen's integer cast would be UB there).
+// Floor corner (x0, y0, z0) and the 8 corner weights of one sample point.  A source index that is NaN or beyond 1e9 in
+// magnitude (ATen's integer cast of the corner would be UB there) is mapped to a point far outside the volume: every corner
+// out of range.  Only zeros padding produces one: border clips and reflection folds and then clips EVERY coordinate into the
+// volume (source_index: a NaN fails both comparisons of the clip and leaves it as size - 1, as in ATen's std::min / std::max),
+// so under those two paddings an absurd or non-finite coordinate samples a voxel -- the one ATen samples.
 template <int PAD>
 GS_FN void corner_weights(float gx, float gy, float gz, int D, int H, int W, int& x0, int& y0, int& z0, float (&w)[8]) {
   float ix = source_index<PAD>(gx, W);

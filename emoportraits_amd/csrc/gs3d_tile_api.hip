@@ -1,7 +1,7 @@
 // Entry of the LDS-staged 3-D grid_sample behind emo_grid_sample3d_f32 (grid_sample3d.hip checks the arguments), and the
 // packed-4 layout repack -- SURVEY.md section 8 rows a1 + a2.
 #include "common.h"
-#include "gs3d_tile_signature.h"
+#include "gs3d_tile_launch.h"   // tile_form, the launchers' decision (no kernel is instantiated in this translation unit)
 
 EMO_GS3D_TILE_PAD_SIGNATURE(emo_gs3d_tile_zeros);
 EMO_GS3D_TILE_PAD_SIGNATURE(emo_gs3d_tile_border);
@@ -20,6 +20,16 @@ int emo_gs3d_tile_dispatch(const float* vol, const float* grid, const float* the
     default: return EMO_ERR_BAD_ARG;
   }
 #undef EMO_GS3D_ARGS
+}
+
+// ABI 29: what launch_tile decides for these arguments, for emo_grid_sample3d_launch_form (grid_sample3d.hip); nothing launched
+int emo_gs3d_tile_form(int N, int C, int D, int H, int W, int Do, int Ho, int Wo, int in_layout, int out_layout, int variant,
+                       gs3d::LaunchForm* form) {
+  bool in_p4, out_p4;
+  *form = gs3d::LaunchForm{};
+  if (!gs3d::tile_layouts(in_layout, out_layout, in_p4, out_p4)) return form->rc = EMO_ERR_UNSUPPORTED;
+  *form = gs3d::tile_form(in_p4, out_p4, N, C, D, H, W, Do, Ho, Wo, variant);
+  return form->rc;
 }
 
 namespace {
@@ -44,11 +54,20 @@ __global__ __launch_bounds__(256) void repack_p4_kernel(const float* __restrict_
 }
 }  // namespace
 
-int emo_repack_p4_dispatch(const float* in, float* out, int N, int C, int DHW, int to_p4, void* stream) {
+// the launch decision of the packed-4 repack: *blocks = grid x (grid y = N); emo_volume_repack_launch_form reports it
+int emo_repack_p4_form(int N, int C, int DHW, long* blocks) {
+  *blocks = 0;
   if (C % 4) return EMO_ERR_UNSUPPORTED;
   const long items = (long)(C / 4) * DHW;
   if ((items + 255) / 256 > 0x7fffffffL || N > 65535) return EMO_ERR_UNSUPPORTED;
-  dim3 g((unsigned)((items + 255) / 256), N);
-  hipLaunchKernelGGL(repack_p4_kernel, g, dim3(256), 0, (hipStream_t)stream, in, out, C / 4, DHW, to_p4);
+  *blocks = (items + 255) / 256;
+  return EMO_OK;
+}
+
+int emo_repack_p4_dispatch(const float* in, float* out, int N, int C, int DHW, int to_p4, void* stream) {
+  long blocks;
+  const int rc = emo_repack_p4_form(N, C, DHW, &blocks);
+  if (rc != EMO_OK) return rc;
+  hipLaunchKernelGGL(repack_p4_kernel, dim3((unsigned)blocks, N), dim3(256), 0, (hipStream_t)stream, in, out, C / 4, DHW, to_p4);
   return emo_launch_status();
 }

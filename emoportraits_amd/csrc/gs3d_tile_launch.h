@@ -4,6 +4,7 @@
 #include <mutex>
 #include <set>
 #include <utility>
+#include "gs3d_launch_form.h"
 #include "gs3d_tile.h"
 #include "gs3d_tile_signature.h"
 
@@ -52,36 +53,31 @@ static int raise_dynamic_lds(K kern) {
 }
 
 template <int PAD, int MODE, bool IN_P4, bool OUT_P4, int THREADS, int VPT>
-int launch_tile_cfg(const TileParams& p, size_t lds_bytes, hipStream_t s) {
-  const long total = (long)p.ngroups * p.N * p.ntx * p.nty * p.ntz;
-  if (total > 0x7fffffffL) return EMO_ERR_UNSUPPORTED;
+int launch_tile_cfg(const TileParams& p, const LaunchForm& f, hipStream_t s) {
   auto kern = tile_kernel<PAD, MODE, IN_P4, OUT_P4, THREADS, VPT>;
-  if (lds_bytes > 64 * 1024) {
+  if (f.lds > 64 * 1024) {
     const int rc = raise_dynamic_lds(kern);
     if (rc != EMO_OK) return rc;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(THREADS), lds_bytes, s, p);
+  hipLaunchKernelGGL(kern, dim3((unsigned)f.gx), dim3(THREADS), f.lds, s, p);
   return emo_launch_status();
 }
 
+// The launch decision of the tile kernels (ABI 29), made HERE and nowhere else: launch_tile calls it before anything else and
+// launches what it says, emo_grid_sample3d_launch_form reports it (emo_gs3d_tile_form).  No HIP call.
 // Tuning word of the tile kernels (the `variant` argument of emo_grid_sample3d_f32; 0 = defaults):
 //   bits  3..0  log2 tile x     7..4  log2 tile y     11..8  log2 tile z     (all three 0: default tile)
 //   bits 16..12 channel units per block (0: default)  24..17 LDS per block in KiB (0: default)
 //   bit  25     512 threads per block instead of 256
-template <int PAD, int MODE, bool IN_P4, bool OUT_P4>
-int launch_tile(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
-                const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
-                long vol_bstride, int variant, hipStream_t s) {
-  if (IN_P4 && (C % 4)) return EMO_ERR_UNSUPPORTED;
-  if (!IN_P4 && (W % 4)) return EMO_ERR_UNSUPPORTED;                            // 16-byte pieces of the planar box rows
-  if (W > 2046 || H > 2046 || D > 1022) return EMO_ERR_UNSUPPORTED;              // packed floor corner
-  if ((long)D * H * W * (IN_P4 ? 16 : 4) >= (1L << 31)) return EMO_ERR_UNSUPPORTED;   // 32-bit byte offsets inside a unit
-  if ((long)Do * Ho * Wo * 16 >= (1L << 32)) return EMO_ERR_UNSUPPORTED;         // 32-bit store offsets
-  TileParams p;
-  p.vol = vol; p.grid = grid; p.theta = theta; p.lin_x = lin_x; p.lin_y = lin_y; p.lin_z = lin_z; p.out = out;
-  p.N = N; p.C = C; p.D = D; p.H = H; p.W = W; p.Do = Do; p.Ho = Ho; p.Wo = Wo;
-  p.vol_bstride = vol_bstride;
-  p.units = IN_P4 ? C / 4 : C;
+inline LaunchForm tile_form(bool in_p4, bool out_p4, int N, int C, int D, int H, int W, int Do, int Ho, int Wo, int variant) {
+  LaunchForm f = {};
+  auto refuse = [&f](int rc) { f = LaunchForm{}; f.rc = rc; return f; };
+  if (in_p4 && (C % 4)) return refuse(EMO_ERR_UNSUPPORTED);
+  if (!in_p4 && (W % 4)) return refuse(EMO_ERR_UNSUPPORTED);                     // 16-byte pieces of the planar box rows
+  if (W > 2046 || H > 2046 || D > 1022) return refuse(EMO_ERR_UNSUPPORTED);      // packed floor corner
+  if ((long)D * H * W * (in_p4 ? 16 : 4) >= (1L << 31)) return refuse(EMO_ERR_UNSUPPORTED);   // 32-bit byte offsets inside a unit
+  if ((long)Do * Ho * Wo * 16 >= (1L << 32)) return refuse(EMO_ERR_UNSUPPORTED); // 32-bit store offsets
+  const int units = in_p4 ? C / 4 : C;
   int txs = variant & 15, tys = (variant >> 4) & 15, tzs = (variant >> 8) & 15;
   int upb = (variant >> 12) & 31, lds_kib = (variant >> 17) & 255;
   int threads = (variant >> 25) & 1 ? 512 : 256;
@@ -93,31 +89,60 @@ int launch_tile(const float* vol, const float* grid, const float* theta, const f
     while (tzs > 0 && (1 << tzs) >= 2 * Do) { --tzs; ++tys; }
     while (tys > 0 && (1 << tys) >= 2 * Ho) { --tys; ++txs; }
   }
-  int lv = txs + tys + tzs - (threads == 512 ? 9 : 8);                            // log2(VPT)
-  if (lv < 0 || lv > 1) return EMO_ERR_BAD_ARG;
+  const int lv = txs + tys + tzs - (threads == 512 ? 9 : 8);                      // log2(VPT)
+  if (lv < 0 || lv > 1) return refuse(EMO_ERR_BAD_ARG);
   // all channel units of a tile in one block: the per-block planning (taps, box, slot map: ~800 VALU + 3900 SALU instructions
   // per wave) is the kernel's largest fixed cost (3 units per block: 43 us per frame, all 24: 23 us)
-  if (upb == 0) upb = p.units < 31 ? p.units : 31;
-  if (upb > p.units) upb = p.units;
+  if (upb == 0) upb = units < 31 ? units : 31;
+  if (upb > units) upb = units;
   if (lds_kib == 0) lds_kib = threads == 512 ? 80 : 40;
-  if (lds_kib > 160 || lds_kib < 1) return EMO_ERR_BAD_ARG;
-  p.txs = txs; p.tys = tys; p.tzs = tzs;
-  p.ntx = emo_cdiv(Wo, 1 << txs); p.nty = emo_cdiv(Ho, 1 << tys); p.ntz = emo_cdiv(Do, 1 << tzs);
-  p.upb = upb;
-  p.ngroups = emo_cdiv(p.units, upb);
+  if (lds_kib > 160 || lds_kib < 1) return refuse(EMO_ERR_BAD_ARG);
   const size_t lds = (size_t)lds_kib * 1024;
   // header + scratch + a stage of at least 64 slots, or the tuning word is rejected (an unsigned underflow here would let the
   // kernel stage far beyond the LDS it was given; a tile whose box does not fit the stage takes the kernel's direct-gather path)
-  const size_t lds_fixed = (size_t)TILE_HDR_BYTES + tile_scratch_bytes(IN_P4, OUT_P4, threads);
-  if (lds < lds_fixed + 1024) return EMO_ERR_BAD_ARG;
-  p.cap_slots = (int)((lds - lds_fixed) / 16);
-  if (p.cap_slots > TILE_MAXI * threads) p.cap_slots = TILE_MAXI * threads;
-  if (threads == 256) {
-    if (lv == 0) return launch_tile_cfg<PAD, MODE, IN_P4, OUT_P4, 256, 1>(p, lds, s);
-    return launch_tile_cfg<PAD, MODE, IN_P4, OUT_P4, 256, 2>(p, lds, s);
+  const size_t lds_fixed = (size_t)TILE_HDR_BYTES + tile_scratch_bytes(in_p4, out_p4, threads);
+  if (lds < lds_fixed + 1024) return refuse(EMO_ERR_BAD_ARG);
+  int cap_slots = (int)((lds - lds_fixed) / 16);
+  if (cap_slots > TILE_MAXI * threads) cap_slots = TILE_MAXI * threads;
+  if (threads == 512 && lv == 0) return refuse(EMO_ERR_BAD_ARG);
+  f.bps = (long)emo_cdiv(units, upb) * emo_cdiv(Wo, 1 << txs) * emo_cdiv(Ho, 1 << tys) * emo_cdiv(Do, 1 << tzs);
+  if (f.bps * N > 0x7fffffffL) return refuse(EMO_ERR_UNSUPPORTED);
+  f.form = in_p4 ? (out_p4 ? EMO_GS3D_FORM_TILE_P4 : EMO_GS3D_FORM_TILE_P4_NCDHW) : EMO_GS3D_FORM_TILE_PLANAR;
+  f.gx = f.bps * N; f.gy = f.gz = 1;
+  f.cpb = in_p4 ? 4 * upb : upb;
+  f.lds = lds;
+  f.threads = threads; f.vpt = 1 << lv; f.upb = upb; f.txs = txs; f.tys = tys; f.tzs = tzs; f.cap_slots = cap_slots;
+  return f;
+}
+
+// which of the three tile launchers serves a layout pair: false = none (EMO_ERR_UNSUPPORTED)
+inline bool tile_layouts(int in_layout, int out_layout, bool& in_p4, bool& out_p4) {
+  in_p4 = in_layout == EMO_LAYOUT_P4;
+  out_p4 = out_layout == EMO_LAYOUT_P4;
+  return (in_p4 && (out_p4 || out_layout == EMO_LAYOUT_NCDHW)) || (in_layout == EMO_LAYOUT_NCDHW && out_layout == EMO_LAYOUT_NCDHW);
+}
+
+template <int PAD, int MODE, bool IN_P4, bool OUT_P4>
+int launch_tile(const float* vol, const float* grid, const float* theta, const float* lin_x, const float* lin_y,
+                const float* lin_z, float* out, int N, int C, int D, int H, int W, int Do, int Ho, int Wo,
+                long vol_bstride, int variant, hipStream_t s) {
+  const LaunchForm f = tile_form(IN_P4, OUT_P4, N, C, D, H, W, Do, Ho, Wo, variant);
+  if (f.rc != EMO_OK) return f.rc;
+  TileParams p;
+  p.vol = vol; p.grid = grid; p.theta = theta; p.lin_x = lin_x; p.lin_y = lin_y; p.lin_z = lin_z; p.out = out;
+  p.N = N; p.C = C; p.D = D; p.H = H; p.W = W; p.Do = Do; p.Ho = Ho; p.Wo = Wo;
+  p.vol_bstride = vol_bstride;
+  p.units = IN_P4 ? C / 4 : C;
+  p.txs = f.txs; p.tys = f.tys; p.tzs = f.tzs;
+  p.ntx = emo_cdiv(Wo, 1 << f.txs); p.nty = emo_cdiv(Ho, 1 << f.tys); p.ntz = emo_cdiv(Do, 1 << f.tzs);
+  p.upb = f.upb;
+  p.ngroups = emo_cdiv(p.units, f.upb);
+  p.cap_slots = f.cap_slots;
+  if (f.threads == 256) {
+    if (f.vpt == 1) return launch_tile_cfg<PAD, MODE, IN_P4, OUT_P4, 256, 1>(p, f, s);
+    return launch_tile_cfg<PAD, MODE, IN_P4, OUT_P4, 256, 2>(p, f, s);
   }
-  if (lv == 0) return EMO_ERR_BAD_ARG;
-  return launch_tile_cfg<PAD, MODE, IN_P4, OUT_P4, 512, 2>(p, lds, s);
+  return launch_tile_cfg<PAD, MODE, IN_P4, OUT_P4, 512, 2>(p, f, s);
 }
 
 template <int PAD, int MODE>

@@ -25,6 +25,8 @@ SIGNATURES = {
     "emo_mfma_stream_f16": [_c_void, _c_int, _c_int, ctypes.POINTER(_c_i64), _c_void],
     "emo_grid_sample3d_f32": [_c_void] * 7 + [_c_int] * 8 + [_c_i64] + [_c_int] * 5 + [_c_void],
     "emo_grid_sample3d_indexed_f32": [_c_void, _c_void, _c_int] + [_c_void] * 6 + [_c_int] * 13 + [_c_void],
+    "emo_grid_sample3d_launch_form": [_c_void, _c_void] + [_c_int] * 9 + [_c_i64] + [_c_int] * 5 + [ctypes.POINTER(_c_i64)],
+    "emo_volume_repack_launch_form": [_c_void, _c_void] + [_c_int] * 5 + [ctypes.POINTER(_c_i64)],
     "emo_affine_grid3d_f32": [_c_void] * 5 + [_c_int] * 4 + [_c_void],
     "emo_volume_repack_f32": [_c_void, _c_void, _c_int, _c_int, _c_int, _c_int, _c_void],
     "emo_volume_repack_indexed_f32": [_c_void, _c_void, _c_void, _c_int, _c_int, _c_int, _c_int, _c_void],
@@ -156,6 +158,50 @@ def op_launch_form(op, x, out, dims):
         return rc, None
     plan = dict(zip(OP_PLAN, (int(v) for v in p)))
     plan["form"] = OP_FORMS[op][plan["form"]]
+    return rc, plan
+
+
+# emo_grid_sample3d_launch_form / emo_volume_repack_launch_form (ABI 29): the enums of include/emo_hip.h (tests/test_abi.py)
+GS3D_KINDS = {"grid": 0, "delta": 1, "theta": 2}
+GS3D_FORMS = ("planar", "rows", "rows_ncdhw", "brick", "tile_p4", "tile_p4_ncdhw", "tile_planar")
+GS3D_PLAN = ("form", "order", "fma", "nt", "bank", "grid_x", "grid_y", "grid_z", "bps", "last_vox", "cpb", "lds", "threads", "vpt",
+             "upb", "txs", "tys", "tzs", "stage_slots")
+REPACK_DIRECTIONS = ("from_channels_last", "to_channels_last", "to_channels_last_indexed", "to_p4", "from_p4")
+REPACK_PLAN = ("direction", "grid_x", "grid_y", "grid_z")
+_LAYOUTS = {"ncdhw": LAYOUT_NCDHW, "ndhwc": LAYOUT_NDHWC, "p4": LAYOUT_P4}
+
+
+def sampler_launch_form(vol, out, N, C, vol_dims, out_dims, padding_mode="zeros", in_layout="ncdhw", out_layout="ncdhw", variant=0,
+                        mode="grid", shared=False, banked=False):
+    """What grid_sample3d's entry would do with these arguments, launching nothing: (rc, plan).  vol, out: addresses (ints) or
+    None; vol_dims (D, H, W), out_dims (Do, Ho, Wo); mode 'grid' / 'delta' / 'theta'; shared: one volume for the N samples
+    (stride 0); banked: the indexed entry.  plan: GS3D_PLAN names -> ints, 'form' as its name; None if rc != 0"""
+    lib = load()
+    D, H, W = (int(v) for v in vol_dims)
+    Do, Ho, Wo = (int(v) for v in out_dims)
+    p = (_c_i64 * len(GS3D_PLAN))()
+    rc = lib.emo_grid_sample3d_launch_form(ctypes.c_void_p(vol) if vol else None, ctypes.c_void_p(out) if out else None, int(bool(banked)),
+                                           int(N), int(C), D, H, W, Do, Ho, Wo, 0 if shared else int(C) * D * H * W,
+                                           PAD_MODES[padding_mode], _LAYOUTS[in_layout], _LAYOUTS[out_layout], int(variant),
+                                           GS3D_KINDS[mode], p)
+    if rc != 0:
+        return rc, None
+    plan = dict(zip(GS3D_PLAN, (int(v) for v in p)))
+    plan["form"] = GS3D_FORMS[plan["form"]]
+    return rc, plan
+
+
+def repack_launch_form(inp, out, N, C, DHW, to_channels_last, indexed=False):
+    """The same question about emo_volume_repack_f32 / emo_volume_repack_indexed_f32: (rc, plan), plan REPACK_PLAN names -> ints
+    with 'direction' as its name; None if rc != 0"""
+    lib = load()
+    p = (_c_i64 * len(REPACK_PLAN))()
+    rc = lib.emo_volume_repack_launch_form(ctypes.c_void_p(inp) if inp else None, ctypes.c_void_p(out) if out else None, int(N), int(C),
+                                           int(DHW), int(to_channels_last), int(bool(indexed)), p)
+    if rc != 0:
+        return rc, None
+    plan = dict(zip(REPACK_PLAN, (int(v) for v in p)))
+    plan["direction"] = REPACK_DIRECTIONS[plan["direction"]]
     return rc, plan
 
 

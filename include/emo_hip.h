@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define EMO_ABI_VERSION 28
+#define EMO_ABI_VERSION 29
 
 #define EMO_OK 0
 #define EMO_ERR_BAD_ARG (-1)       /* null pointer / non-positive size / unknown enum          */
@@ -138,6 +138,60 @@ int emo_volume_repack_f32(const float* in, float* out, int N, int C, int DHW, in
  * in, bank or row NULL, N, C, DHW or num_rows <= 0: EMO_ERR_BAD_ARG.  N > 65535: EMO_ERR_UNSUPPORTED. */
 int emo_volume_repack_indexed_f32(const float* in, float* bank, const int32_t* row, int N, int C, int DHW, int num_rows,
                                   void* stream);
+
+/* ABI 29.  A question, not a launch: the kernel and the launch plan a 3-D sampler call with these arguments takes.  The
+ * launchers' own host functions answer -- the ones they call themselves before they launch -- so a condition of a form is
+ * written once; no HIP call is made and the call works on a machine without a device.  The arguments are those of
+ * emo_grid_sample3d_indexed_f32 with the same meaning, except:
+ *   vol, out   read for nullness and 16-byte alignment only.
+ *   banked     != 0: the question is about emo_grid_sample3d_indexed_f32 (vol_batch_stride is then ignored: C D H W);
+ *              0: about emo_grid_sample3d_f32 with this vol_batch_stride (0 = one volume shared by the N samples).
+ *   grid_kind  an EMO_GS3D_KIND_*: 0 and 1 as in the entries, 2 = theta is given (the entries' non-NULL theta).
+ * Returns what the entry would return before any launch (EMO_ERR_BAD_ARG, EMO_ERR_UNSUPPORTED, EMO_ERR_ALIGN; then plan is all
+ * zero), otherwise EMO_OK with plan[EMO_GS3D_PLAN_COUNT] filled:
+ *   FORM   the kernel --
+ *     EMO_GS3D_FORM_PLANAR          NCDHW -> NCDHW direct gather, one lane per output voxel          (default for that pair)
+ *     EMO_GS3D_FORM_ROWS            NDHWC -> NDHWC, 64 consecutive output voxels per block           (default for that pair)
+ *     EMO_GS3D_FORM_ROWS_NCDHW      NDHWC -> NCDHW, the same blocks, transposed through LDS; refused (UNSUPPORTED) where
+ *                                   64 tap records + C rows of 65 floats pass 64 KiB: C > 232
+ *     EMO_GS3D_FORM_BRICK           NDHWC -> NDHWC, a 4 x 4 x 4 output brick per block: variant bit 1 AND Do, Ho, Wo multiples of
+ *                                   4 (else the bit is ignored: ROWS).  The brick kernel accumulates without FMA: bit 1 wins
+ *                                   over bit 4.
+ *     EMO_GS3D_FORM_TILE_P4, _TILE_P4_NCDHW, _TILE_PLANAR   the LDS-staged kernels: P4 -> P4, P4 -> NCDHW, and NCDHW -> NCDHW
+ *                                   with variant bit 30 where W % 4 == 0 and the extents fit (else PLANAR with variant 0)
+ *   ORDER  block order of ROWS / ROWS_NCDHW / BRICK: 1 = XCD-contiguous; 3 = also row-group-major over an XCD's samples, taken by
+ *          the two ROWS forms for one volume shared (stride 0, no bank) by N >= 8 samples where N % 8 == 0, Do Ho Wo % 64 == 0,
+ *          BPS % Do == 0 and (BPS / Do) % 8 == 0 -- each condition failing alone gives ORDER 1.  0 for the other forms.
+ *   FMA    variant bit 4 taken (ROWS forms).  NT: variant bit 2 taken (ROWS_NCDHW only; ignored for an NDHWC output).  BANK: the
+ *          (index, num) instantiation.
+ *   GRID_X, GRID_Y, GRID_Z  the launch grid.  BPS: blocks per sample (PLANAR: per sample and channel chunk).  LAST_VOX: output
+ *          voxels of a sample's last block (PLANAR: of 256; ROWS forms and BRICK: of 64; tile forms: 0).
+ *   CPB    channels per block: PLANAR min(variant > 0 ? variant : 8, C) with GRID_Y = ceil(C / CPB) chunks, the last one ragged
+ *          where C % CPB; the channels-last forms C; tile forms the channels of UPB units.
+ *   LDS    dynamic LDS bytes of the launch (ROWS_NCDHW: 5120 + 260 C; tile forms: the tuning word's KiB, default 40 / 80).
+ *   THREADS, VPT, UPB, TXS, TYS, TZS, STAGE_SLOTS  tile forms only: block size, voxels per thread, channel units per block, log2
+ *          of the tile extents x / y / z, 16-byte slots of the stage. */
+enum { EMO_GS3D_KIND_GRID = 0, EMO_GS3D_KIND_DELTA = 1, EMO_GS3D_KIND_THETA = 2, EMO_GS3D_KIND_COUNT = 3 };
+enum { EMO_GS3D_FORM_PLANAR = 0, EMO_GS3D_FORM_ROWS = 1, EMO_GS3D_FORM_ROWS_NCDHW = 2, EMO_GS3D_FORM_BRICK = 3,
+       EMO_GS3D_FORM_TILE_P4 = 4, EMO_GS3D_FORM_TILE_P4_NCDHW = 5, EMO_GS3D_FORM_TILE_PLANAR = 6, EMO_GS3D_FORM_COUNT = 7 };
+enum { EMO_GS3D_PLAN_FORM = 0, EMO_GS3D_PLAN_ORDER = 1, EMO_GS3D_PLAN_FMA = 2, EMO_GS3D_PLAN_NT = 3, EMO_GS3D_PLAN_BANK = 4,
+       EMO_GS3D_PLAN_GRID_X = 5, EMO_GS3D_PLAN_GRID_Y = 6, EMO_GS3D_PLAN_GRID_Z = 7, EMO_GS3D_PLAN_BPS = 8,
+       EMO_GS3D_PLAN_LAST_VOX = 9, EMO_GS3D_PLAN_CPB = 10, EMO_GS3D_PLAN_LDS = 11, EMO_GS3D_PLAN_THREADS = 12,
+       EMO_GS3D_PLAN_VPT = 13, EMO_GS3D_PLAN_UPB = 14, EMO_GS3D_PLAN_TXS = 15, EMO_GS3D_PLAN_TYS = 16, EMO_GS3D_PLAN_TZS = 17,
+       EMO_GS3D_PLAN_STAGE_SLOTS = 18, EMO_GS3D_PLAN_COUNT = 19 };
+int emo_grid_sample3d_launch_form(const void* vol, const void* out, int banked, int N, int C, int D, int H, int W, int Do, int Ho, int Wo, int64_t vol_batch_stride, int padding_mode, int in_layout, int out_layout, int variant, int grid_kind, int64_t* plan);
+
+/* ABI 29.  The same question about emo_volume_repack_f32 (indexed = 0) and emo_volume_repack_indexed_f32 (indexed != 0, which
+ * has to_channels_last = 1; its row / num_rows arguments are no part of the question).  in, out: nullness only.  Returns what
+ * the entry would return before any launch, plan all zero then -- among them EMO_ERR_UNSUPPORTED where the 64 x 64 tile grid
+ * has more than 65535 rows of tiles (grid y: C for to_channels_last = 1, DHW for 0) -- otherwise EMO_OK and
+ * plan[EMO_REPACK_PLAN_COUNT]: DIRECTION, an EMO_REPACK_*, and the grid: (ceil(columns / 64), ceil(rows / 64), N) tiles of the
+ * [rows][columns] input matrices, or (ceil(C / 4 * DHW / 256), N, 1) for the packed-4 directions. */
+enum { EMO_REPACK_FROM_CHANNELS_LAST = 0, EMO_REPACK_TO_CHANNELS_LAST = 1, EMO_REPACK_TO_CHANNELS_LAST_INDEXED = 2,
+       EMO_REPACK_TO_P4 = 3, EMO_REPACK_FROM_P4 = 4, EMO_REPACK_COUNT = 5 };
+enum { EMO_REPACK_PLAN_DIRECTION = 0, EMO_REPACK_PLAN_GRID_X = 1, EMO_REPACK_PLAN_GRID_Y = 2, EMO_REPACK_PLAN_GRID_Z = 3,
+       EMO_REPACK_PLAN_COUNT = 4 };
+int emo_volume_repack_launch_form(const void* in, const void* out, int N, int C, int DHW, int to_channels_last, int indexed, int64_t* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * a10 -- GroupNorm statistics folded to a per-(sample, channel) affine.

@@ -15,19 +15,13 @@ import c_oracle  # noqa: E402
 import restate as O  # noqa: E402
 
 from emoportraits_amd import ops  # noqa: E402
+from sampler_launch_forms import TILE_TUNINGS  # noqa: E402  (tag, tuning word) of the LDS-staged kernels: the case list's
 
 from guarded_outputs import guarded_outputs  # noqa: E402,F401  (every output ops allocates: poisoned, between guards)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_outputs")]
 PADS = ["zeros", "border", "reflection"]
 DEV = "cuda:0"
-
-
-# (tag, tuning word) of the LDS-staged kernels: default; one voxel per thread; two bricks per thread; 512-thread blocks;
-# a 2 KiB stage (union box never fits: brick-by-brick and direct passes); 1 channel unit per block
-TILE_TUNINGS = [("", 0), ("_8x8x4", ops.tile_variant((8, 8, 4))), ("_16x8x4", ops.tile_variant((16, 8, 4), units_per_block=5)),
-                ("_8x8x16_512", ops.tile_variant((8, 8, 16), threads=512)),
-                ("_tiny_stage", ops.tile_variant((8, 8, 8), lds_kib=2)), ("_upb1", ops.tile_variant((4, 8, 8), units_per_block=1, lds_kib=16))]
 
 
 def _all_layouts(vol_cpu, grid_cpu=None, theta_cpu=None, pm="zeros", shared=False):
