@@ -75,16 +75,31 @@ def _overlaps(out, t):
     return isinstance(t, torch.Tensor) and ops._shares_storage(out, t)
 
 
+def _before(v):
+    """a copy of an argument a launch mutates, taken before the real call: a tensor, a list of tensors (the frames of a ragged
+    batch) or an object that holds one as .tensor; None stays None"""
+    if v is None:
+        return None
+    if isinstance(v, (list, tuple)):
+        return type(v)(_before(t) for t in v)
+    return v.clone() if isinstance(v, torch.Tensor) else type(v)(v.tensor.clone())
+
+
 class OpLaunchChecker:
     """stands in for the non-conv ops attributes while a pass runs: real launch, fp64 check, one summary row"""
 
     wrapped = WRAPPED                     # the ops attributes this checker stands in for (a subclass names its own)
     title = "op launches"
+    modules = NETWORK_MODULES             # the modules whose frames name a launch's call site
+    # op -> the arguments its launch writes in place (frames, the streams' state and flags): a checker is handed their copies from
+    # before the real call under their names, and the caller's own objects, as the launch left them, under "after"
+    mutated = {}
 
     def __init__(self, tag):
         self.tag = tag
         self.rows = []
         self.intercepted = 0
+        self._sources = tuple(os.path.abspath(m.__file__) for m in self.modules)
         self._inside = False              # a wrapped op that calls another one (grid_sample3d's repack): checked as the outer launch
 
     def install(self, mp):
@@ -99,21 +114,25 @@ class OpLaunchChecker:
             a.apply_defaults()
             a = dict(a.arguments)
             self.intercepted += 1
-            site = _call_site()
+            site = _call_site(self._sources)
             out_arg = a.get("out")
             if out_arg is not None:       # a launch that writes into a caller's buffer: keep what it could overwrite
                 a = {k: (v.clone() if _overlaps(out_arg, v) and v is not out_arg else v) for k, v in a.items()}
+            if name in self.mutated:      # a launch that writes into its arguments: what they held before it
+                a["after"] = {k: a[k] for k in self.mutated[name]}
+                a.update({k: _before(a[k]) for k in self.mutated[name]})
             self._inside = True
             try:
                 result = _REAL[name](*args, **kwargs)
                 form, shape, fig = getattr(self, "_check_" + name)(a, result)
             finally:
                 self._inside = False
-            batch = (result[0] if isinstance(result, tuple) else result).shape[0]
+            # (a launch whose result does not carry its rows -- frames pasted into in place, a bank -- says their number itself)
+            batch = fig["batch"] if "batch" in fig else (result[0] if isinstance(result, tuple) else result).shape[0]
             self.rows.append(dict(op=name, form=form, shape=shape, site=site, batch=batch, frames=len(fig["frames"]),
                                   worst=fig["worst"], frame=fig["worst_frame"], unit=fig["unit"], failures=fig["failures"],
                                   max_ratio=fig.get("max_ratio"), mean_ratio=fig.get("mean_ratio"), yardstick=fig.get("yardstick"),
-                                  rms=fig.get("rms_rel")))
+                                  rms=fig.get("rms_rel"), extra=fig.get("extra")))
             return result
         return call
 
@@ -182,9 +201,10 @@ class OpLaunchChecker:
                 continue
             w = max(rows, key=lambda r: r["worst"])
             s = f"{name} {w['worst']:.3g} {w['unit']} ({w['form']} {w['site']}, frame {w['frame']})"
-            if rows[0]["max_ratio"] is not None:           # held to a yardstick (the samplers)
-                s += (f"; error ratios to {rows[0]['yardstick']}: " + ", ".join(
-                    f"{r['form']} max {r['max_ratio']:.3f} mean {r['mean_ratio']:.3f}" for r in _worst_per_form(rows)))
+            held = [r for r in rows if r["max_ratio"] is not None]
+            if held:                                       # held to a yardstick (the samplers)
+                s += (f"; error ratios to {held[0]['yardstick']}: " + ", ".join(
+                    f"{r['form']} max {r['max_ratio']:.3f} mean {r['mean_ratio']:.3f}" for r in _worst_per_form(held)))
             if rows[0]["rms"] is not None:
                 rms = sorted(r["rms"] for r in rows)
                 s += f"; rms err / rms ref: worst {rms[-1]:.2e}, median {rms[len(rms) // 2]:.2e}"
